@@ -1,17 +1,26 @@
 #!/usr/bin/env python3
 """bench.py -- graphs/s of the GIN (dim 100) hot path on molhiv-shaped synthetic graphs.
 
-    python bench.py --gpus N --steps K --warmup W [--model M] [--graphs G] [--scaling weak|strong]
+    python bench.py --gpus N --steps K --warmup W [--model M] [--graphs G] [--scaling weak|strong] [--dump-outputs DIR] [--full]
 
 A "step" = one full batched forward of the resident batch through the C ABI (flowgnn_run):
 batched load_graph (CSR build) -> atom encoder -> 5 x (aggregation + node MLP) -> mean-pool +
 head, for G graphs per GPU (weak scaling, default) or G graphs in the whole job cut by sum(N+E)
 (strong scaling), followed for N > 1 by the RCCL all-gather that concatenates the per-graph results.
 Inputs are resident in HBM when the timed region starts (the reference also times kernel execution
-only: run_experiments.sh:44).  Rank 0 prints ONE JSON line, which carries `roofline`, `cpu_baseline`
-(N = 1) and `parity` (GPU logits of the timed batch vs the oracle); the default single-GPU GIN run also measures the other
-BASELINE configs after the timed region and reports them as `configs`.  A failed parity check -- headline or any config --
-is exit code 3 after the line is printed.
+only: run_experiments.sh:44).  Rank 0 prints ONE JSON line: `metric`, `value` (graphs/s of the job), `unit`, `higher_is_better`,
+`dtype`, `ms_per_step` (wall clock of one timed step), the batch (`config`) and the per-kernel averages of the timed steps
+(`kernel_avg_ms`).  A plain run does nothing else: set-up, warm-up, the K timed steps, the outputs, the line.
+
+--dump-outputs DIR: after the timed steps rank 0 writes what the last timed step computed, the per-graph logits of the whole job
+in job order (what a caller of flowgnn_run receives), as DIR/logits.npy (float32; a job larger than 64 MB of logits is written as a
+fixed, seeded sample of graphs, DIR/logits.npy + DIR/logits_index.npy).  The inputs are seeded: the same arguments give the same
+batch and weights in every run, so two builds can be compared output for output.
+
+--full: everything else the benchmark measures, after the timed region: `roofline` / `aggregation_roofline` (with a stand-alone
+run of the aggregation kernel), `entry_point_host_arrays` (N = 1), `cpu_baseline` (N = 1) and `parity` (GPU logits of the timed
+batch vs the oracle); the default single-GPU GIN run also measures the other BASELINE configs and reports them as `configs`.  A
+failed parity check -- headline or any config -- is exit code 3 after the line is printed.
 
 Run plainly with --gpus N > 1 it starts the N ranks itself (one process per GPU, 127.0.0.1
 rendezvous); under torchrun it uses the launcher's RANK / LOCAL_RANK / WORLD_SIZE.  It refuses to
@@ -548,6 +557,95 @@ def dry_run(args):
         sys.exit(3)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory, arrays):
+    """`--dump-outputs`: every array as <directory>/<name>.npy in float32.  Past DUMP_LIMIT_BYTES in all, each array is cut to the same
+    fixed, seeded sample of its rows (sorted), and the row numbers are written beside it as <name>_index.npy (float64)."""
+    os.makedirs(directory, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_LIMIT_BYTES:
+            row_bytes = a.nbytes // max(a.shape[0], 1) + 8
+            k = min(a.shape[0], DUMP_LIMIT_BYTES // len(arrays) // row_bytes)
+            idx = np.sort(np.random.default_rng(0).choice(a.shape[0], k, replace=False))
+            np.save(os.path.join(directory, name + "_index.npy"), idx.astype(np.float64))
+            a = a[idx]
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
+def full_run(args, line, eng, batch, w, out_local, prof, kern, split, qmode, world, local_rank):
+    """`--full`: what the benchmark measures and checks beyond the headline, after the timed region, into `line`: the rooflines (with a
+    stand-alone run of the aggregation kernel where the timed path fuses it), the drop-in symbol with host arrays, the CPU baseline,
+    parity of the timed batch against the oracle and (default single-GPU GIN run) the other BASELINE configs.
+    Returns (the engine, or None once closed; whether every parity check passed)."""
+    M = MODELS[args.model]
+    G, N, E = batch.num_graphs, batch.total_nodes, batch.total_edges
+    agg_name = next((k for k in M["hbm_kernels"] if k in kern), M["hbm_kernels"][0])
+    if agg_name not in kern and not qmode:  # fused layer: measure the message-passing unit alone as well
+        try:
+            kern[agg_name] = eng.aggregation_only_ms(layer=0, iters=10)
+        except Exception:  # a model without a standalone aggregation kernel
+            pass
+    line["roofline"], line["aggregation_roofline"] = rooflines(args.model, M, prof, kern, G, N, E, args.steps, split, qmode,
+                                                               tile_count(eng, args.model, batch))
+    value = line["value"]
+    if world == 1 and not qmode and not args.no_entry_point:
+        # the drop-in symbol itself with HOST arrays in the clock (validation, tile packing, PCIe copies, kernels, logits back):
+        # reported beside `value`, never as `value` (DESIGN.md section 5)
+        from flowgnn_amd import compute_graphs
+        ts = []
+        for _ in range(3):
+            t0 = time.perf_counter()
+            out_entry = compute_graphs(args.model, batch, [w])
+            ts.append(time.perf_counter() - t0)
+        line["entry_point_host_arrays"] = {"symbol": ("GIN" if args.model == "GIN-VN" else args.model) + "_compute_graphs", "ms": min(ts) * 1e3,
+                                           "value": G / min(ts), "unit": "graphs/s",
+                                           "matches_timed_logits": bool(np.allclose(out_entry, out_local, rtol=1e-5, atol=1e-5))}
+    want = None
+    if world == 1 and not args.no_cpu_baseline:
+        line["cpu_baseline"], want = cpu_baseline(args.model, batch, w, numeric=args.numeric)
+        line["gpu_over_cpu"] = value / line["cpu_baseline"]["value"]
+    else:  # no timed CPU leg: still check a slice of rank 0's shard of the timed batch against the oracle
+        n = min(G, 4096)
+        want = np.asarray(oracle_forward(args.model, batch.slice(0, n), w, effective_cpus(), args.numeric), np.float32)
+    if args.inject_parity_failure:
+        out_local = out_local + np.float32(1.0)
+    line["parity"] = parity_record(args.model, out_local[: want.shape[0]], want, args.numeric)
+    parity_ok = bool(line["parity"]["ok"])
+    do_configs = args.configs == "on" or (args.configs == "auto" and world == 1 and args.model == "GIN" and not args.graphs and not qmode)
+    if do_configs and world == 1:
+        # every BASELINE config in the driver's one run: after the headline's timed region, same process, same GPU
+        eng.close()
+        eng = None
+        from flowgnn_amd import graphpack as gp
+        cfgs = {}
+        # (warm-up long enough for the clocks to come back up after the seconds of host-side batch generation in between: with 2
+        # warm-up steps the same kernels measured ~10 % slower than in a run of their own)
+        csteps, cwarm = max(3, min(args.steps, 10)), 8
+        mol = batch  # the headline's molhiv batch is reused for GAT and (plus virtual nodes) for GIN-VN
+        # the dataset-sized batch: a step is 0.16 ms, so 50 steps behind 5 warm-up steps were 10 ms of GPU time in all -- shorter than
+        # the clocks take to come back up after the host-side batch generation (0.180 ms per step measured that way, 0.155 in any
+        # loop of 100 ms).  500 timed steps behind 300 of warm-up: 0.13 s.
+        cfgs["GIN@4113"] = measure_config("GIN", make_batch("molhiv", 4113, 99), 500, 300, local_rank)
+        cfgs["GAT"] = measure_config("GAT", mol, csteps, cwarm, local_rank)
+        cfgs["GIN-VN"] = measure_config("GIN-VN", gp.add_virtual_nodes(mol), csteps, cwarm, local_rank)
+        del mol
+        cfgs["GCN"] = measure_config("GCN", make_batch("molpcba", MODELS["GCN"]["graphs"], 1234), csteps, cwarm, local_rank)
+        hep = make_batch("hep10k", MODELS["PNA"]["graphs"], 1234)  # SURVEY 8(d)'s 2^16: every [N][D] fp32 tensor >= 1 GB
+        cfgs["PNA"] = measure_config("PNA", hep, csteps, cwarm, local_rank)
+        cfgs["DGN"] = measure_config("DGN", hep, csteps, cwarm, local_rank)
+        half = hep.slice(0, 1 << 15)  # ... and half of it once, beside: how much of the stand-alone aggregation probe's rate is the
+        del hep                       # 256 MiB Infinity Cache (the resident kernels keep h on chip: their rate should not move)
+        cfgs["PNA@32768"] = measure_config("PNA", half, csteps, cwarm, local_rank)
+        cfgs["DGN@32768"] = measure_config("DGN", half, csteps, cwarm, local_rank)
+        line["configs"] = cfgs
+        parity_ok = parity_ok and all(c["parity_ok"] for c in cfgs.values())
+    return eng, parity_ok
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -558,13 +656,18 @@ def main():
                     help="graphs per GPU per step (weak scaling; default: the model's roofline batch) or in the whole job (strong scaling)")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak: fixed graphs per GPU; strong: ONE job batch cut by sum(N+E) with flowgnn_amd.dist.shard_ranges")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-entry-point", action="store_true", help="skip the timing of the drop-in symbol with host arrays (profiling runs: its launches would mix into the kernel trace)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the per-graph logits of the last timed step to DIR/logits.npy (float32, job order)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: rooflines, the drop-in symbol with host arrays, the CPU "
+                         "baseline, parity against the oracle and (default single-GPU GIN run) the other BASELINE configs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the timed CPU leg (parity still checks a slice)")
+    ap.add_argument("--no-entry-point", action="store_true", help="--full: skip the timing of the drop-in symbol with host arrays (profiling runs: its launches would mix into the kernel trace)")
     ap.add_argument("--configs", default="auto", choices=["auto", "on", "off"],
-                    help="also measure the other BASELINE configs (GIN at dataset size, GIN-VN, GCN, GAT, PNA, DGN) in the same run and "
+                    help="--full: also measure the other BASELINE configs (GIN at dataset size, GIN-VN, GCN, GAT, PNA, DGN) in the same run and "
                          "report them in a compact `configs` object; auto = on for the default single-GPU GIN run")
     ap.add_argument("--inject-parity-failure", action="store_true",
-                    help="test hook: perturb the GPU logits before they are compared with the oracle (the run must then exit with code 3)")
+                    help="--full, test hook: perturb the GPU logits before they are compared with the oracle (the run must then exit with code 3)")
     ap.add_argument("--numeric", default="f32", choices=["f32", "q6.10"],
                     help="q6.10: the reference's ap_fixed<16,6> bit-faithful mode (a fidelity mode, ~10x slower)")
     ap.add_argument("--dry-run", action="store_true",
@@ -572,6 +675,10 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    if not args.full and (args.configs == "on" or args.inject_parity_failure):
+        raise SystemExit("--configs on and --inject-parity-failure are part of a --full run")
     if args.dry_run:
         return dry_run(args)
 
@@ -666,6 +773,7 @@ def main():
         logits_all = res.assemble()
         ok = bool(torch.isfinite(logits_all).all().item())
         out_local = res.local()[:G].detach().cpu().numpy()
+        job_logits = logits_all.detach().cpu().numpy() if args.dump_outputs and rank == 0 else None
     total_job_graphs = ranges[-1][1]
     if int(logits_all.shape[0]) != total_job_graphs:
         raise SystemExit(f"result concat has {int(logits_all.shape[0])} graphs, the job has {total_job_graphs}")
@@ -676,19 +784,13 @@ def main():
 
     exit_code = 0
     if rank == 0:
+        if args.dump_outputs:  # what the last timed step computed: the job's logits in job order, before anything else runs
+            dump_outputs(args.dump_outputs, {"logits": job_logits})
         value = total_job_graphs * args.steps / elapsed
         kern = {k: (v["total_ms"] / max(v["launches"], 1)) for k, v in prof.items()}
-        agg_name = next((k for k in M["hbm_kernels"] if k in kern), M["hbm_kernels"][0])
         qmode = args.numeric != "f32"
-        if agg_name not in kern and not qmode:  # fused layer: measure the message-passing unit alone as well
-            try:
-                kern[agg_name] = eng.aggregation_only_ms(layer=0, iters=10)
-            except Exception:  # a model without a standalone aggregation kernel
-                pass
-
         # the dense updates of every model run as three f16 MFMAs per fp32 product unless option <m>_mfma = 32 ("f32")
         split = eng.get_option({"GIN-VN": "gin"}.get(args.model, args.model.lower()) + "_mfma") != 32
-        roof, agg = rooflines(args.model, M, prof, kern, G, N, E, args.steps, split, qmode, tile_count(eng, args.model, batch))
         par = f"batch-sharded x{world}, RCCL all-gather of logits" if world > 1 else "single GPU"
         if collectives and world == 1:
             par = "single GPU, the N > 1 code path forced (RCCL group of one rank: barriers, per-step all-gather, max over ranks)"
@@ -702,68 +804,18 @@ def main():
                        "graphs_per_step_job": total_job_graphs, "graphs_rank0": G, "nodes_rank0": N, "edges_rank0": E,
                        "parallelism": par},
             "finite": ok, "exact_reruns": eng.exact_reruns(),
-            "roofline": roof,
-            "aggregation_roofline": agg,
             "kernel_avg_ms": kern,
             "vs_fpga_u50": (value / FPGA_U50_GRAPHS_PER_S) if args.model == "GIN" else None,
         }
         if balance is not None:
             line["shard_balance"] = balance
-        if world == 1 and not qmode and not args.no_entry_point:
-            # the drop-in symbol itself with HOST arrays in the clock (validation, tile packing, PCIe copies, kernels, logits back):
-            # reported beside `value`, never as `value`
-            from flowgnn_amd import compute_graphs
-            ts = []
-            for _ in range(3):
-                t0 = time.perf_counter()
-                out_entry = compute_graphs(args.model, batch, [w])
-                ts.append(time.perf_counter() - t0)
-            line["entry_point_host_arrays"] = {"symbol": ("GIN" if args.model == "GIN-VN" else args.model) + "_compute_graphs", "ms": min(ts) * 1e3,
-                                               "value": G / min(ts), "unit": "graphs/s",
-                                               "matches_timed_logits": bool(np.allclose(out_entry, out_local, rtol=1e-5, atol=1e-5))}
-        want = None
-        if world == 1 and not args.no_cpu_baseline:
-            line["cpu_baseline"], want = cpu_baseline(args.model, batch, w, numeric=args.numeric)
-            line["gpu_over_cpu"] = value / line["cpu_baseline"]["value"]
-        else:  # no timed CPU leg: still check a slice of rank 0's shard of the timed batch against the oracle
-            n = min(G, 4096)
-            want = np.asarray(oracle_forward(args.model, batch.slice(0, n), w, effective_cpus(), args.numeric), np.float32)
-        if args.inject_parity_failure:
-            out_local = out_local + np.float32(1.0)
-        line["parity"] = parity_record(args.model, out_local[: want.shape[0]], want, args.numeric)
-        parity_ok = bool(line["parity"]["ok"])
-        do_configs = args.configs == "on" or (args.configs == "auto" and world == 1 and args.model == "GIN" and not args.graphs and not qmode)
-        if do_configs and world == 1:
-            # every BASELINE config in the driver's one run: after the headline's timed region, same process, same GPU
-            eng.close()
-            eng = None
-            from flowgnn_amd import graphpack as gp
-            cfgs = {}
-            # (warm-up long enough for the clocks to come back up after the seconds of host-side batch generation in between: with 2
-            # warm-up steps the same kernels measured ~10 % slower than in a run of their own)
-            csteps, cwarm = max(3, min(args.steps, 10)), 8
-            mol = batch  # the headline's molhiv batch is reused for GAT and (plus virtual nodes) for GIN-VN
-            # the dataset-sized batch: a step is 0.16 ms, so 50 steps behind 5 warm-up steps were 10 ms of GPU time in all -- shorter than
-            # the clocks take to come back up after the host-side batch generation (0.180 ms per step measured that way, 0.155 in any
-            # loop of 100 ms).  500 timed steps behind 300 of warm-up: 0.13 s.
-            cfgs["GIN@4113"] = measure_config("GIN", make_batch("molhiv", 4113, 99), 500, 300, local_rank)
-            cfgs["GAT"] = measure_config("GAT", mol, csteps, cwarm, local_rank)
-            cfgs["GIN-VN"] = measure_config("GIN-VN", gp.add_virtual_nodes(mol), csteps, cwarm, local_rank)
-            del mol
-            cfgs["GCN"] = measure_config("GCN", make_batch("molpcba", MODELS["GCN"]["graphs"], 1234), csteps, cwarm, local_rank)
-            hep = make_batch("hep10k", MODELS["PNA"]["graphs"], 1234)  # SURVEY 8(d)'s 2^16: every [N][D] fp32 tensor >= 1 GB
-            cfgs["PNA"] = measure_config("PNA", hep, csteps, cwarm, local_rank)
-            cfgs["DGN"] = measure_config("DGN", hep, csteps, cwarm, local_rank)
-            half = hep.slice(0, 1 << 15)  # ... and half of it once, beside: how much of the stand-alone aggregation probe's rate is the
-            del hep                       # 256 MiB Infinity Cache (the resident kernels keep h on chip: their rate should not move)
-            cfgs["PNA@32768"] = measure_config("PNA", half, csteps, cwarm, local_rank)
-            cfgs["DGN@32768"] = measure_config("DGN", half, csteps, cwarm, local_rank)
-            line["configs"] = cfgs
-            parity_ok = parity_ok and all(c["parity_ok"] for c in cfgs.values())
+        if args.full:
+            eng, parity_ok = full_run(args, line, eng, batch, w, out_local, prof, kern, split, qmode, world, local_rank)
+            if not parity_ok:
+                exit_code = 3
         os.write(json_fd, (json.dumps(line) + "\n").encode())
-        if not parity_ok:
+        if exit_code == 3:
             sys.stderr.write("bench.py: PARITY FAILURE against the oracle -- the throughput above is not a valid measurement\n")
-            exit_code = 3
     if eng is not None:
         eng.close()
     if collectives:  # (rank 0 leaves through the same barrier as the others even when it is about to report a failure)

@@ -3,7 +3,7 @@
 # One rocprofv3 --pmc pass (counters only, no trace domains); prints per-kernel averages.
 set -u
 TAG=$1; CTRS=$2; shift 2
-ARGS=${@:---steps 2 --warmup 1 --no-cpu-baseline}
+ARGS=${@:---steps 2 --warmup 1 --full --no-cpu-baseline}
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp

@@ -4,7 +4,7 @@
 # and HBM-side traffic counters, each PMC counter in its own pass (no trace domains mixed in).
 set -u
 TAG=${1:-prof}; shift || true
-ARGS=${@:---steps 3 --warmup 1 --no-cpu-baseline}
+ARGS=${@:---steps 3 --warmup 1 --full --no-cpu-baseline}
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp

@@ -20,8 +20,9 @@ mode = sys.argv[4] if len(sys.argv) > 4 else "f32"
 base = model.replace("-VN", "").lower()
 w = getattr(weights, f"synth_{base}_weights")(seed=11)
 if os.environ.get("FUZZ_WEIGHTS", "") == "trained":  # the reference's own trained set (a data fixture of the tests) instead of synthetic weights
-    z = np.load(os.path.join(ROOT, "tests", "golden", f"ref_weights_{base}.npz"))
-    w = {k: z[k] for k in z.files}
+    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+    import make_ref_weights
+    w = dict(make_ref_weights.load(model))
 wscale = float(os.environ.get("FUZZ_WEIGHT_SCALE", "1"))  # > 1: activations grow layer by layer -- the f16 range flag and the exact-fp32 re-run get exercised
 if wscale != 1.0:
     w = {k: (v * np.float32(wscale) if ("weight" in k.lower() or "mlp" in k.lower() or "conv" in k.lower()) and "emb" not in k.lower() and "bn" not in k.lower() else v) for k, v in w.items()}

@@ -1,8 +1,16 @@
-"""Host-side pieces of bench.py that need no GPU: the CPU count the cpu_baseline leg is sized from, and the model table."""
+"""Host-side pieces of bench.py that need no GPU: the CPU count the cpu_baseline leg is sized from, the model table, the writer of
+--dump-outputs and the checks of the command line."""
 import builtins
 import io
+import os
+import subprocess
+import sys
+
+import numpy as np
 
 import bench
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _fake_open(files):
@@ -44,3 +52,26 @@ def test_model_table_is_complete():
             assert all(f(n, e) > 0 for f in fb.values())
         elif fb is not None:
             assert fb(n, e) > 0
+
+
+def test_dump_outputs_writes_float32_and_samples_past_the_limit(tmp_path, monkeypatch):
+    a = np.arange(1000, dtype=np.float64).reshape(500, 2) * 0.5
+    bench.dump_outputs(str(tmp_path / "all"), {"h": a})
+    got = np.load(tmp_path / "all" / "h.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, a.astype(np.float32))
+    assert not (tmp_path / "all" / "h_index.npy").exists()
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 1600)  # 16 B per row (two floats + an 8-byte row number): 100 rows
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), {"h": a})
+    idx = np.load(tmp_path / "s1" / "h_index.npy")
+    got = np.load(tmp_path / "s1" / "h.npy")
+    assert idx.dtype == np.float64 and len(idx) == 100 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(got, a[idx.astype(np.int64)].astype(np.float32))
+    assert np.array_equal(idx, np.load(tmp_path / "s2" / "h_index.npy"))  # a fixed sample: the same rows in every run
+
+
+def test_full_only_options_and_step_counts_are_checked_before_any_work():
+    for args, msg in ((["--configs", "on"], "--full"), (["--inject-parity-failure"], "--full"), (["--steps", "0"], "--steps")):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, capture_output=True, text=True, timeout=120)
+        assert p.returncode != 0 and msg in p.stderr, (args, p.returncode, p.stderr[-500:])
+        assert p.stdout == ""

@@ -2,13 +2,12 @@
 import os
 
 import numpy as np
-import pytest
 
 from flowgnn_amd import graphpack as gp, weights
 from tests import numpy_ref
+from tests.golden.make_ref_weights import shipped_dir
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden", "dgn_hep24.npz")
-REF = "/root/reference/DGN"
 
 
 def with_eigen(b, seed):
@@ -40,8 +39,8 @@ def test_oracle_golden_vectors(oracle):
     assert np.array_equal(oracle.dgn_forward(from_npz(z), [weights.synth_dgn_weights(seed=7)]), z["logits_synth_weights"])
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference weights not on this machine")
-def test_reference_weights(oracle):
+def test_reference_weights(oracle, tmp_path):
+    REF = shipped_dir("DGN", tmp_path)  # the reference's own weight files, rebuilt byte for byte
     assert os.path.getsize(os.path.join(REF, weights.DGN_FILE)) == 4 * 104051
     w = weights.load_dgn_weights(REF)
     z = np.load(GOLDEN)

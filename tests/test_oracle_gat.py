@@ -3,14 +3,13 @@ reference's feature-offset quirk."""
 import os
 
 import numpy as np
-import pytest
 
 from flowgnn_amd import graphpack as gp, weights
 from tests import numpy_ref
+from tests.golden.make_ref_weights import shipped_dir
 from tests.test_oracle_gcn import directed_variant
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden", "gat_molhiv48.npz")
-REF = "/root/reference/GAT"
 
 
 def batches():
@@ -51,8 +50,8 @@ def test_oracle_golden_vectors(oracle):
     assert np.array_equal(oracle.gat_forward(b, [weights.synth_gat_weights(seed=7)]), z["logits_synth_weights"])
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference weights not on this machine")
-def test_reference_weights(oracle):
+def test_reference_weights(oracle, tmp_path):
+    REF = shipped_dir("GAT", tmp_path)  # the reference's own weight files, rebuilt byte for byte
     w = weights.load_gat_weights(REF)
     assert os.path.getsize(os.path.join(REF, "gat_ep1_linear_proj_weight_1_layer5.bin")) == 4 * 4 * 4 * 16 * 4 * 16
     assert os.path.getsize(os.path.join(REF, "gat_ep1_skip_proj_weight_0_layer5.bin")) == 4 * 4 * 16 * 9

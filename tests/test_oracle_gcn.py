@@ -2,13 +2,12 @@
 import os
 
 import numpy as np
-import pytest
 
 from flowgnn_amd import graphpack as gp, weights
 from tests import numpy_ref
+from tests.golden.make_ref_weights import shipped_dir
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden", "gcn_molpcba48.npz")
-REF = "/root/reference/GCN"
 
 
 def directed_variant(b):
@@ -36,8 +35,8 @@ def test_oracle_golden_vectors(oracle):
     assert np.array_equal(out, z["logits_synth_weights"])
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference weights not on this machine")
-def test_reference_weights(oracle):
+def test_reference_weights(oracle, tmp_path):
+    REF = shipped_dir("GCN", tmp_path)  # the reference's own weight files, rebuilt byte for byte
     assert os.path.getsize(os.path.join(REF, weights.GCN_FILE)) == 4 * 76906
     w = weights.load_gcn_weights(REF)
     assert (w["bn_var"] > 0).all()  # a wrong BN offset would land on means/biases

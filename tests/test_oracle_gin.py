@@ -3,13 +3,12 @@ against the committed golden vectors, and the integer tables of load_graph."""
 import os
 
 import numpy as np
-import pytest
 
 from flowgnn_amd import graphpack as gp, weights
 from tests import numpy_ref
+from tests.golden.make_ref_weights import shipped_dir
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden", "gin_molhiv64.npz")
-REF_GIN = "/root/reference/GIN"
 
 
 def test_oracle_matches_numpy_float64(oracle, gin_weights):
@@ -37,21 +36,20 @@ def test_oracle_golden_vectors(oracle, gin_weights):
     assert np.array_equal(hd[:, :n4], z["h_first4_graphs"])
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_GIN), reason="reference weights not on this machine")
-def test_oracle_golden_real_weights(oracle):
+def test_oracle_golden_real_weights(oracle, tmp_path):
     z = np.load(GOLDEN)
     b = gp.GraphBatch(z["nums_of_nodes"], z["nums_of_edges"], z["node_feature"], z["edge_list"], z["edge_attr"])
-    w = weights.load_gin_weights(REF_GIN)
+    w = weights.load_gin_weights(shipped_dir("GIN", tmp_path))  # the reference's own weight files, rebuilt byte for byte
     out = oracle.gin_forward(b, [w])
     assert np.array_equal(out, z["logits_reference_weights"])
     # independent restatement with the shipped weights as well
     assert np.allclose(out, numpy_ref.gin_forward(b, w), rtol=1e-4, atol=1e-4)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_GIN), reason="reference weights not on this machine")
-def test_reference_weight_files_have_expected_sizes():
+def test_reference_weight_files_have_expected_sizes(tmp_path):
+    ref = shipped_dir("GIN", tmp_path)
     for k, (f, shp) in weights.GIN_FILES.items():
-        assert os.path.getsize(os.path.join(REF_GIN, f)) == 4 * int(np.prod(shp)), f
+        assert os.path.getsize(os.path.join(ref, f)) == 4 * int(np.prod(shp)), f
 
 
 def test_load_graph_tables(oracle):

@@ -5,6 +5,7 @@ import numpy as np
 
 from flowgnn_amd import graphpack as gp, weights
 from tests import numpy_ref
+from tests.golden.make_ref_weights import shipped_dir
 
 
 def test_quantisation_primitives(oracle):
@@ -39,24 +40,22 @@ def test_threads_and_weight_sets(oracle, gin_weights):
     assert np.array_equal(a[17:], oracle.gin_forward_q(b.slice(17, 30), [w2])[1])
 
 
-def test_distance_from_float_oracle(oracle, gin_weights):
+def test_distance_from_float_oracle(oracle, gin_weights, tmp_path):
     """Where the two number systems can be compared exactly: the atom encoder adds nine quantised table rows, so
     0 <= float - Q < 9 * 2^-10 element-wise.  Deeper stages accumulate one truncation per stored product (up to 2^-10
-    each, 100-200 per output) and are amplified by the layers; with the shipped weights (when the reference checkout is
-    present) the logits of graphs that never wrap stay within ~1.5 of the float oracle (mean +0.03, sigma 0.14,
+    each, 100-200 per output) and are amplified by the layers; with the shipped weights (the reference's own files) the
+    logits of graphs that never wrap stay within ~1.5 of the float oracle (mean +0.03, sigma 0.14,
     max 0.75 on the reference's own test graphs)."""
-    import os
     b = gp.synth_molhiv_batch(120, seed=21)
     f, hd = oracle.gin_forward(b, [gin_weights], dump_h=True, nthreads=4)
     q, _, hq = oracle.gin_forward_q(b, [gin_weights], dump_h=True, nthreads=4)
     d0 = hd[0].astype(np.float64) - hq[0].astype(np.float64) / 1024.0
     assert d0.min() >= -1e-6 and d0.max() < 9 / 1024 + 1e-6, (d0.min(), d0.max())
     assert np.isfinite(q).all() and np.abs(q).max() < 32.0
-    if os.path.exists("/root/reference/GIN/gin_ep1_mlp_1_weights_dim100.bin"):
-        wr = weights.LOADERS["GIN"]("/root/reference/GIN")
-        f, hd = oracle.gin_forward(b, [wr], dump_h=True, nthreads=4)
-        q = oracle.gin_forward_q(b, [wr], nthreads=4)[0]
-        off = b.node_offsets()
-        calm = np.array([np.abs(hd[:, off[g]:off[g + 1]]).max() < 10.0 for g in range(b.num_graphs)])
-        d = (q - f)[calm]
-        assert calm.sum() > 30 and np.abs(d).mean() < 0.8 and np.abs(d).max() < 4.0, (calm.sum(), np.abs(d).mean(), np.abs(d).max())
+    wr = weights.LOADERS["GIN"](shipped_dir("GIN", tmp_path))
+    f, hd = oracle.gin_forward(b, [wr], dump_h=True, nthreads=4)
+    q = oracle.gin_forward_q(b, [wr], nthreads=4)[0]
+    off = b.node_offsets()
+    calm = np.array([np.abs(hd[:, off[g]:off[g + 1]]).max() < 10.0 for g in range(b.num_graphs)])
+    d = (q - f)[calm]
+    assert calm.sum() > 30 and np.abs(d).mean() < 0.8 and np.abs(d).max() < 4.0, (calm.sum(), np.abs(d).mean(), np.abs(d).max())

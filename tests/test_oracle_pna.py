@@ -2,14 +2,13 @@
 import os
 
 import numpy as np
-import pytest
 
 from flowgnn_amd import graphpack as gp, weights
 from tests import numpy_ref
+from tests.golden.make_ref_weights import shipped_dir
 from tests.test_oracle_gcn import directed_variant
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden", "pna_hep24.npz")
-REF = "/root/reference/PNA"
 
 
 def batches():
@@ -34,8 +33,8 @@ def test_oracle_golden_vectors(oracle):
     assert np.array_equal(oracle.pna_forward(b, [weights.synth_pna_weights(seed=7)]), z["logits_synth_weights"])
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference weights not on this machine")
-def test_reference_weights(oracle):
+def test_reference_weights(oracle, tmp_path):
+    REF = shipped_dir("PNA", tmp_path)  # the reference's own weight files, rebuilt byte for byte
     assert os.path.getsize(os.path.join(REF, weights.PNA_FILE)) == 4 * 325441
     w = weights.load_pna_weights(REF)
     z = np.load(GOLDEN)

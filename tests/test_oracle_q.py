@@ -1,17 +1,15 @@
 """oracle/q_oracle.c (GCN / GAT / PNA in ap_fixed<16,6>, DGN in ap_fixed<16,3>): internal consistency of the rules it assumes
-(R0..R8 in its header), and the magnitudes it produces with the shipped trained weights when /root/reference is present
+(R0..R8 in its header), and the magnitudes it produces with the shipped trained weights (read from the reference's own files)
 (SURVEY 8c observed the reference's own kernels, run with a throw-away header stand-in, at GCN ~ -2.4..-3.2, GAT ~ -0.2..-1.4,
 PNA ~ -1.2..-1.4, DGN ~ -0.40..-0.43 on its synthetic graphs)."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
 from flowgnn_amd import graphpack as gp, weights
+from tests.golden.make_ref_weights import shipped_dir
 from tests.test_oracle_dgn import with_eigen
-
-REF = "/root/reference"
 
 
 def test_function_tables(oracle):
@@ -65,12 +63,11 @@ def test_gat_tracks_float_when_nothing_wraps(oracle):
     assert np.abs(q - f).max() < 0.1, np.abs(q - f).max()
 
 
-@pytest.mark.skipif(not os.path.isdir(REF + "/GCN"), reason="reference weights only exist in the build container")
-def test_magnitudes_with_shipped_weights(oracle):
+def test_magnitudes_with_shipped_weights(oracle, tmp_path):
     loaders = {"GCN": weights.load_gcn_weights, "GAT": weights.load_gat_weights, "PNA": weights.load_pna_weights, "DGN": weights.load_dgn_weights}
     lo_hi = {"GCN": (-4.5, 1.5), "GAT": (-2.0, 0.5), "PNA": (-2.5, -0.5), "DGN": (-0.6, -0.2)}
     for model, ld in loaders.items():
-        w = ld(f"{REF}/{model}")
+        w = ld(shipped_dir(model, tmp_path / model))
         b = gp.synth_molhiv_batch(64, seed=4)
         if model == "DGN":
             b = with_eigen(b, 1)

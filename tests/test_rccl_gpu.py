@@ -34,7 +34,7 @@ def test_bench_collective_path_runs_on_rccl_with_a_group_of_one(model, graphs, l
     head = [sys.executable] if launcher == "plain" else [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node",
                                                          "1", "--master-addr", "127.0.0.1", "--master-port", port]
     p = subprocess.run(head + [os.path.join(ROOT, "bench.py"), "--gpus", "1", "--model", model, "--graphs", str(graphs), "--steps", "5",
-                        "--warmup", "2", "--configs", "off", "--no-entry-point"], env=env, cwd=ROOT, capture_output=True, text=True,
+                        "--warmup", "2", "--full", "--configs", "off", "--no-entry-point"], env=env, cwd=ROOT, capture_output=True, text=True,
                        timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     out = p.stdout.strip().splitlines()

@@ -89,7 +89,8 @@ def test_bench_exits_with_code_3_on_a_parity_failure():
     a wrong-answer run must not hand anyone a throughput number with rc 0."""
     import json
     import sys
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--graphs", "96", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--configs", "off"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--graphs", "96", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline",
+           "--configs", "off"]
     ok = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     assert ok.returncode == 0, ok.stderr[-2000:]
     line = json.loads(ok.stdout.strip().splitlines()[-1])

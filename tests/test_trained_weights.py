@@ -1,7 +1,8 @@
 """The TRAINED weight sets the reference ships (tests/golden/ref_weights_<model>.npz, made by tests/golden/make_ref_weights.py from the
 reference's .bin files) on the GPU: the synthetic sets have the shipped sets' per-tensor scales, but not their structure -- GIN logits of
 -3 .. -6, PNA's saturating readout head, BatchNorm statistics of a trained GCN.  CPU: the fixtures are what the loaders read from the
-reference (when it is present) and the oracle reproduces the `logits_reference_weights` of the per-model fixtures from them.  GPU: the
+reference's own files (rebuilt byte for byte from them and tests/golden/ref_files.json) and the oracle reproduces the
+`logits_reference_weights` of the per-model fixtures from them.  GPU: the
 engine does, through the C ABI, on the graph-resident / fused kernels and on the per-layer ones; the fixed-point modes stay bit-exact."""
 import os
 import sys
@@ -12,6 +13,7 @@ import pytest
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "golden"))
 import make_modes_golden as mk  # noqa: E402  (fixture_batch)
+import make_ref_weights as mrw  # noqa: E402  (load, shipped_dir)
 from tests.parity import assert_close, oracle_scale  # noqa: E402
 
 MODELS = ["GIN", "GCN", "GAT", "PNA", "DGN"]
@@ -20,8 +22,7 @@ SWITCH = {"GIN": "gin_resident", "GCN": "gcn_resident", "GAT": "gat_resident", "
 
 
 def trained(model):
-    z = np.load(os.path.join(HERE, "golden", f"ref_weights_{model.lower()}.npz"))
-    return {k: z[k] for k in z.files}
+    return dict(mrw.load(model))
 
 
 def expected(model):
@@ -29,14 +30,12 @@ def expected(model):
 
 
 @pytest.mark.parametrize("model", MODELS)
-def test_fixture_is_the_shipped_set_and_the_oracle_reproduces_its_logits(model, oracle):
+def test_fixture_is_the_shipped_set_and_the_oracle_reproduces_its_logits(model, oracle, tmp_path):
     from flowgnn_amd import weights
     w = trained(model)
-    ref = os.path.join(os.environ.get("FLOWGNN_REFERENCE", "/root/reference"), model)
-    if os.path.isdir(ref):
-        shipped = weights.LOADERS[model](ref)
-        assert sorted(shipped) == sorted(w)
-        assert all(np.array_equal(np.asarray(shipped[k], np.float32), w[k]) for k in w)
+    shipped = weights.LOADERS[model](mrw.shipped_dir(model, tmp_path))  # the reference's own files, rebuilt byte for byte
+    assert sorted(shipped) == sorted(w)
+    assert all(np.array_equal(np.asarray(shipped[k], np.float32), w[k]) for k in w)
     got = getattr(oracle, model.lower() + "_forward")(mk.fixture_batch(model), [w])
     want = expected(model)
     assert np.allclose(got, want, rtol=1e-6, atol=1e-6), np.abs(got - want).max()
