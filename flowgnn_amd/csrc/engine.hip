@@ -190,6 +190,9 @@ namespace fg {
 size_t h2d_pack_bytes(size_t n_nodes, size_t n_edges, bool attr, size_t* off_edges, size_t* off_attr);
 void h2d_pack(const int* node_feature, const int* edge_list, const int* edge_attr, size_t n_nodes, size_t n_edges, uint8_t* dst, int threads);
 void host_parallel_for(int parts, const std::function<void(int)>& fn);
+// ingest.hip
+void launch_ingest_pyg(const long long* x, const long long* ei, const long long* ea, int* nf, int* el, int* ea_out, const int* noff,
+                       const int* eoff, int G, long long N, long long E, int* err, int x_err, int device, hipStream_t s);
 
 // the packed arrays back into the reference's int32 layout (what every kernel reads): 255 / 65 535 = "did not fit" -> -1, which the
 // validation on the device refuses as it would have refused the original value
@@ -567,17 +570,22 @@ int flowgnn_graph_tile_fill(flowgnn_engine* e, int num_graphs, const int* nums_o
     return FLOWGNN_OK;
 }
 
-// copy_mu (flowgnn_group_compute): held around the large host -> device copies only -- one copier per DEVICE at a time, while another
-// engine of the same device packs its next range on the host or packs its tiles
-static int set_batch_impl(flowgnn_engine* e, int num_graphs, const int* nums_of_nodes, const int* nums_of_edges,
-                          const int* node_feature, const int* edge_list, const int* edge_attr, const float* node_eigen, std::mutex* copy_mu) {
+// per-graph counts of a batch and what the host derives from them: prefix sums, totals, largest graph (the limit checks of
+// flowgnn_set_batch, shared by flowgnn_set_batch_device)
+struct BatchCounts {
+    std::vector<int> noff, eoff;  // [G + 1]
+    long long N = 0, E = 0;
+    int mx_n = 0, mx_e = 0;
+};
+static int batch_counts(flowgnn_engine* e, int num_graphs, const int* nums_of_nodes, const int* nums_of_edges, BatchCounts* c) {
     if (!e || num_graphs < 0) return FLOWGNN_ERR_ARG;
     if (num_graphs > 0 && (!nums_of_nodes || !nums_of_edges)) return FLOWGNN_ERR_ARG;
-    const bool attr = e->model->has_edge_attr();
-    const bool eig = (e->model_id == FLOWGNN_MODEL_DGN);
     // prefix sums of node / edge counts: what the reference carries as nodes_offset / edges_offset
     // (GIN/src/GIN_compute.cc:44,96-97)
-    std::vector<int> noff((size_t)num_graphs + 1), eoff((size_t)num_graphs + 1);
+    std::vector<int>& noff = c->noff;
+    std::vector<int>& eoff = c->eoff;
+    noff.assign((size_t)num_graphs + 1, 0);
+    eoff.assign((size_t)num_graphs + 1, 0);
     long long N = 0, E = 0;
     int mx_n = 0, mx_e = 0;
     for (int g = 0; g < num_graphs; g++) {
@@ -598,42 +606,38 @@ static int set_batch_impl(flowgnn_engine* e, int num_graphs, const int* nums_of_
     }
     noff[num_graphs] = (int)N;
     eoff[num_graphs] = (int)E;
-    if (N > 0 && !node_feature) return FLOWGNN_ERR_ARG;
-    if (E > 0 && (!edge_list || (attr && !edge_attr))) return FLOWGNN_ERR_ARG;
-    if (eig && N > 0 && !node_eigen) return FLOWGNN_ERR_ARG;
+    c->N = N; c->E = E; c->mx_n = mx_n; c->mx_e = mx_e;
+    return FLOWGNN_OK;
+}
 
-    ENGINE_TRY(e, use_device(e));
-    e->drop_graph();
-    if (e->stream) EHIP_TRY(e, hipStreamSynchronize(e->stream));
-    e->batch_ready = false;
-    e->ran = false;
-    ENGINE_TRY(e, alloc_batch(e, (size_t)num_graphs, (size_t)N, (size_t)E, attr, eig));
-    auto h2d = [&](void* dst, const void* src, size_t bytes) -> int {
-        if (bytes == 0) return 0;
-        if (e->copy_stream) {  // (the source is the caller's pageable memory: the call returns when the data has left it)
-            EHIP_TRY(e, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, e->copy_stream));
-            EHIP_TRY(e, hipStreamSynchronize(e->copy_stream));
-        } else {
-            EHIP_TRY(e, hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
-        }
-        return 0;
-    };
-    {   // counts and offsets: one staging vector, one copy
-        const size_t G = (size_t)num_graphs;
-        std::vector<int> meta(4 * G + 2);
-        if (G) { memcpy(meta.data(), nums_of_nodes, sizeof(int) * G); memcpy(meta.data() + G, nums_of_edges, sizeof(int) * G); }
-        memcpy(meta.data() + 2 * G, noff.data(), sizeof(int) * (G + 1));
-        memcpy(meta.data() + 3 * G + 1, eoff.data(), sizeof(int) * (G + 1));
-        e->d_ne = e->d_nn + G; e->d_noff = e->d_nn + 2 * G; e->d_eoff = e->d_nn + 3 * G + 1;
-        ENGINE_TRY(e, h2d(e->d_nn, meta.data(), sizeof(int) * meta.size()));
+// a synchronous host -> device copy on the engine's copy queue (the source is the caller's pageable memory: the call returns when
+// the data has left it)
+static int h2d_sync(flowgnn_engine* e, void* dst, const void* src, size_t bytes) {
+    if (bytes == 0) return 0;
+    if (e->copy_stream) {
+        EHIP_TRY(e, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, e->copy_stream));
+        EHIP_TRY(e, hipStreamSynchronize(e->copy_stream));
+    } else {
+        EHIP_TRY(e, hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
     }
+    return 0;
+}
+
+// the bulk arrays of flowgnn_set_batch, host -> d_nf / d_el / d_ea / d_eig.
+// copy_mu (flowgnn_group_compute): held around the large host -> device copies only -- one copier per DEVICE at a time, while another
+// engine of the same device packs its next range on the host or packs its tiles
+static int upload_host_arrays(flowgnn_engine* e, const BatchCounts& c, const int* node_feature, const int* edge_list, const int* edge_attr,
+                              const float* node_eigen, std::mutex* copy_mu) {
+    const bool attr = e->model->has_edge_attr();
+    const bool eig = (e->model_id == FLOWGNN_MODEL_DGN);
+    const long long N = c.N, E = c.E;
     // The three int32 arrays narrowed on the host (9 B per node, 5 B per edge: a quarter of the bytes), copied from pinned memory and
     // widened again on the GPU (h2d_pack.cpp; option h2d_pack, 0 = off).  Large batches only: below a few megabytes the plain copies
     // are latency, not bytes.  Not for GAT (its nine node features are NUMBERS, any integer is valid input) nor for graphs whose
     // node ids do not fit 16 bits.
     const size_t plain_bytes = sizeof(int) * ((size_t)N * ND_FEATURE + (size_t)E * 2 + (attr ? (size_t)E * EDGE_ATTR : 0));
     const int pack_threads = e->opts.i("h2d_pack") > 0 ? host_threads(e->opts.i("h2d_pack")) : 0;
-    if (pack_threads > 0 && e->copy_stream && plain_bytes >= ((size_t)8 << 20) && mx_n <= 65535 && e->model_id != FLOWGNN_MODEL_GAT) {
+    if (pack_threads > 0 && e->copy_stream && plain_bytes >= ((size_t)8 << 20) && c.mx_n <= 65535 && e->model_id != FLOWGNN_MODEL_GAT) {
         size_t off_e = 0, off_a = 0;
         const size_t pb = fg::h2d_pack_bytes((size_t)N, (size_t)E, attr, &off_e, &off_a);
         if (pb > e->cap_pack) {
@@ -657,11 +661,43 @@ static int set_batch_impl(flowgnn_engine* e, int num_graphs, const int* nums_of_
     } else {
         std::unique_lock<std::mutex> lk;
         if (copy_mu) lk = std::unique_lock<std::mutex>(*copy_mu);
-        ENGINE_TRY(e, h2d(e->d_nf, node_feature, sizeof(int) * (size_t)N * ND_FEATURE));
-        ENGINE_TRY(e, h2d(e->d_el, edge_list, sizeof(int) * (size_t)E * 2));
-        if (attr) ENGINE_TRY(e, h2d(e->d_ea, edge_attr, sizeof(int) * (size_t)E * EDGE_ATTR));
-        if (eig) ENGINE_TRY(e, h2d(e->d_eig, node_eigen, sizeof(float) * (size_t)N * 4));
+        ENGINE_TRY(e, h2d_sync(e, e->d_nf, node_feature, sizeof(int) * (size_t)N * ND_FEATURE));
+        ENGINE_TRY(e, h2d_sync(e, e->d_el, edge_list, sizeof(int) * (size_t)E * 2));
+        if (attr) ENGINE_TRY(e, h2d_sync(e, e->d_ea, edge_attr, sizeof(int) * (size_t)E * EDGE_ATTR));
+        if (eig) ENGINE_TRY(e, h2d_sync(e, e->d_eig, node_eigen, sizeof(float) * (size_t)N * 4));
     }
+    return 0;
+}
+
+// The batch state both set_batch entry points build from the per-graph counts: buffers, counts and offsets on the device, graph
+// tiles, bin-packed tiles, job totals and fill.  `upload` fills d_nf / d_el / d_ea / d_eig, synchronously, where flowgnn_set_batch
+// always copied them (after the buffers, before the tiles); nullptr: the caller enqueues that transfer itself once this returns
+// (flowgnn_set_batch_device: after the reset of the error word, so that what its ingest reports survives until the next batch).
+static int set_batch_state(flowgnn_engine* e, int num_graphs, const int* nums_of_nodes, const int* nums_of_edges, const BatchCounts& c,
+                           const std::function<int()>& upload) {
+    const bool attr = e->model->has_edge_attr();
+    const bool eig = (e->model_id == FLOWGNN_MODEL_DGN);
+    const std::vector<int>& noff = c.noff;
+    const long long N = c.N, E = c.E;
+    const int mx_n = c.mx_n, mx_e = c.mx_e;
+
+    ENGINE_TRY(e, use_device(e));
+    e->drop_graph();
+    if (e->stream) EHIP_TRY(e, hipStreamSynchronize(e->stream));
+    e->batch_ready = false;
+    e->ran = false;
+    ENGINE_TRY(e, alloc_batch(e, (size_t)num_graphs, (size_t)N, (size_t)E, attr, eig));
+    auto h2d = [&](void* dst, const void* src, size_t bytes) -> int { return h2d_sync(e, dst, src, bytes); };
+    {   // counts and offsets: one staging vector, one copy
+        const size_t G = (size_t)num_graphs;
+        std::vector<int> meta(4 * G + 2);
+        if (G) { memcpy(meta.data(), nums_of_nodes, sizeof(int) * G); memcpy(meta.data() + G, nums_of_edges, sizeof(int) * G); }
+        memcpy(meta.data() + 2 * G, noff.data(), sizeof(int) * (G + 1));
+        memcpy(meta.data() + 3 * G + 1, c.eoff.data(), sizeof(int) * (G + 1));
+        e->d_ne = e->d_nn + G; e->d_noff = e->d_nn + 2 * G; e->d_eoff = e->d_nn + 3 * G + 1;
+        ENGINE_TRY(e, h2d(e->d_nn, meta.data(), sizeof(int) * meta.size()));
+    }
+    if (upload) ENGINE_TRY(e, upload());
 
     // graph-aligned tiles for kernels that keep whole graphs on chip across layers (GraphTiles, common.h)
     e->db.gtiles = GraphTiles{};
@@ -919,9 +955,111 @@ static int set_batch_impl(flowgnn_engine* e, int num_graphs, const int* nums_of_
     return FLOWGNN_OK;
 }
 
+// flowgnn_set_batch (and the group's ranges): host arrays
+static int set_batch_impl(flowgnn_engine* e, int num_graphs, const int* nums_of_nodes, const int* nums_of_edges,
+                          const int* node_feature, const int* edge_list, const int* edge_attr, const float* node_eigen, std::mutex* copy_mu) {
+    BatchCounts c;
+    const int rc = batch_counts(e, num_graphs, nums_of_nodes, nums_of_edges, &c);
+    if (rc) return rc;
+    const bool attr = e->model->has_edge_attr();
+    const bool eig = (e->model_id == FLOWGNN_MODEL_DGN);
+    if (c.N > 0 && !node_feature) return FLOWGNN_ERR_ARG;
+    if (c.E > 0 && (!edge_list || (attr && !edge_attr))) return FLOWGNN_ERR_ARG;
+    if (eig && c.N > 0 && !node_eigen) return FLOWGNN_ERR_ARG;
+    return set_batch_state(e, num_graphs, nums_of_nodes, nums_of_edges, c,
+                           [&]() { return upload_host_arrays(e, c, node_feature, edge_list, edge_attr, node_eigen, copy_mu); });
+}
+
 int flowgnn_set_batch(flowgnn_engine* e, int num_graphs, const int* nums_of_nodes, const int* nums_of_edges,
                       const int* node_feature, const int* edge_list, const int* edge_attr, const float* node_eigen) {
     return set_batch_impl(e, num_graphs, nums_of_nodes, nums_of_edges, node_feature, edge_list, edge_attr, node_eigen, nullptr);
+}
+
+// flowgnn_set_batch_device's guard: a non-empty array must be memory of the engine's device, and the bytes the counts imply must lie
+// inside its allocation (with XNACK off, a kernel that reads pageable host memory or runs past an allocation faults the device)
+static int check_device_array(const flowgnn_engine* e, const void* p, size_t bytes, const char* what) {
+    if (!p || bytes == 0) return 0;
+    char msg[256];
+    hipPointerAttribute_t a{};
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+        (void)hipGetLastError();
+        snprintf(msg, sizeof(msg), "flowgnn_set_batch_device: %s is not memory the HIP runtime knows (pageable host memory?)", what);
+        fg::set_last_error(msg);  // (ENGINE_TRY hands it to the engine)
+        return FLOWGNN_ERR_ARG;
+    }
+    if (a.type != hipMemoryTypeDevice || a.device != e->device) {
+        snprintf(msg, sizeof(msg), "flowgnn_set_batch_device: %s is not device memory of device %d (memory type %d, device %d)", what,
+                 e->device, (int)a.type, a.device);
+        fg::set_last_error(msg);  // (ENGINE_TRY hands it to the engine)
+        return FLOWGNN_ERR_ARG;
+    }
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) {
+        (void)hipGetLastError();
+        snprintf(msg, sizeof(msg), "flowgnn_set_batch_device: no allocation range for %s", what);
+        fg::set_last_error(msg);  // (ENGINE_TRY hands it to the engine)
+        return FLOWGNN_ERR_ARG;
+    }
+    const uintptr_t lo = (uintptr_t)p, end = (uintptr_t)base + size;
+    if (lo < (uintptr_t)base || bytes > end - lo) {
+        snprintf(msg, sizeof(msg), "flowgnn_set_batch_device: %s holds %zu bytes from this pointer to the end of its allocation, the counts imply %zu",
+                 what, (size_t)(end > lo ? end - lo : 0), bytes);
+        fg::set_last_error(msg);  // (ENGINE_TRY hands it to the engine)
+        return FLOWGNN_ERR_ARG;
+    }
+    return 0;
+}
+
+int flowgnn_set_batch_device(flowgnn_engine* e, int num_graphs, const int* nums_of_nodes, const int* nums_of_edges, int layout,
+                             const void* node_feature, const void* edge_list, const void* edge_attr, const float* node_eigen) {
+    BatchCounts c;
+    int rc = batch_counts(e, num_graphs, nums_of_nodes, nums_of_edges, &c);
+    if (rc) return rc;
+    if (layout != FLOWGNN_LAYOUT_REFERENCE && layout != FLOWGNN_LAYOUT_PYG) {
+        e->err = "flowgnn_set_batch_device: unknown layout";
+        return FLOWGNN_ERR_ARG;
+    }
+    const bool attr = e->model->has_edge_attr();
+    const bool eig = (e->model_id == FLOWGNN_MODEL_DGN);
+    const size_t N = (size_t)c.N, E = (size_t)c.E;
+    if ((N > 0 && !node_feature) || (E > 0 && (!edge_list || (attr && !edge_attr))) || (eig && N > 0 && !node_eigen)) {
+        e->err = "flowgnn_set_batch_device: an array the model needs is NULL";
+        return FLOWGNN_ERR_ARG;
+    }
+    // the guard, before anything is enqueued (every non-null array, whether the model reads it or not)
+    const size_t w = layout == FLOWGNN_LAYOUT_PYG ? sizeof(long long) : sizeof(int);
+    ENGINE_TRY(e, use_device(e));
+    ENGINE_TRY(e, check_device_array(e, node_feature, w * N * ND_FEATURE, "node_feature"));
+    ENGINE_TRY(e, check_device_array(e, edge_list, w * E * 2, "edge_list"));
+    ENGINE_TRY(e, check_device_array(e, edge_attr, w * E * EDGE_ATTR, "edge_attr"));
+    ENGINE_TRY(e, check_device_array(e, node_eigen, sizeof(float) * N * 4, "node_eigen"));
+    rc = set_batch_state(e, num_graphs, nums_of_nodes, nums_of_edges, c, nullptr);
+    if (rc) return rc;
+    // the ingest, on the launch stream: ordered after the caller's work on it, before the next flowgnn_run; nothing waits for it
+    {
+        ProfScope p(e->prof, "ingest", e->stream);
+        hipError_t he = hipSuccess;
+        if (layout == FLOWGNN_LAYOUT_PYG) {
+            fg::launch_ingest_pyg((const long long*)node_feature, (const long long*)edge_list, attr ? (const long long*)edge_attr : nullptr,
+                                  e->d_nf, e->d_el, attr ? e->d_ea : nullptr, e->d_noff, e->d_eoff, num_graphs, c.N, c.E, e->d_err,
+                                  e->model_id == FLOWGNN_MODEL_GAT ? ERR_NODE_FEAT : 0, e->device, e->stream);
+            he = hipGetLastError();
+        } else {
+            if (N) he = hipMemcpyAsync(e->d_nf, node_feature, sizeof(int) * N * ND_FEATURE, hipMemcpyDeviceToDevice, e->stream);
+            if (he == hipSuccess && E) he = hipMemcpyAsync(e->d_el, edge_list, sizeof(int) * E * 2, hipMemcpyDeviceToDevice, e->stream);
+            if (he == hipSuccess && E && attr)
+                he = hipMemcpyAsync(e->d_ea, edge_attr, sizeof(int) * E * EDGE_ATTR, hipMemcpyDeviceToDevice, e->stream);
+        }
+        if (he == hipSuccess && eig && N) he = hipMemcpyAsync(e->d_eig, node_eigen, sizeof(float) * N * 4, hipMemcpyDeviceToDevice, e->stream);
+        if (he != hipSuccess) {
+            set_hip_error("flowgnn_set_batch_device: ingest", he, __FILE__, __LINE__);
+            e->err = fg::last_error_text();
+            e->batch_ready = false;
+            return FLOWGNN_ERR_HIP;
+        }
+    }
+    return FLOWGNN_OK;
 }
 
 int flowgnn_run(flowgnn_engine* e) {

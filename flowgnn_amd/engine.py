@@ -55,6 +55,7 @@ class Engine:
             raise ValueError(f"unknown model {model}")
         self._h = C.c_void_p()
         self._check(self.lib.flowgnn_create(_lib.MODEL_IDS[self.model], device, C.byref(self._h)), "flowgnn_create")
+        self.device = int(device)
         self._keep = []
         self.num_tasks = 1
         for k, v in (options or {}).items():
@@ -80,6 +81,7 @@ class Engine:
         if getattr(self, "_h", None):
             self.lib.flowgnn_destroy(self._h)
             self._h = C.c_void_p()
+        self._results_tensor = None  # (forward_device's output: released once the engine, and its stream, are gone)
 
     def __del__(self):
         try:
@@ -128,6 +130,112 @@ class Engine:
         self.num_graphs = batch.num_graphs
         self.total_nodes = batch.total_nodes
         self.total_edges = batch.total_edges
+
+    def set_batch_device_ptrs(self, nums_of_nodes, nums_of_edges, layout: str, node_feature: int, edge_list: int,
+                              edge_attr: int = 0, node_eigen: int = 0):
+        """flowgnn_set_batch_device with raw DEVICE addresses (ints, 0 = NULL), for callers without torch.  Counts are host arrays;
+        `layout` "pyg" (int64 x [N][9], edge_index [2][E] with batch-global ids, edge_attr [E][3]) or "reference" (int32, as
+        set_batch takes them).  The arrays must be complete on the engine's launch stream (stream_handle()) and stay unchanged until
+        the ingest has run there; validation errors surface at sync() / results()."""
+        nn, ne = _i32(nums_of_nodes), _i32(nums_of_edges)
+        if layout not in _lib.LAYOUT_IDS:
+            raise ValueError(f"unknown layout {layout!r} (pyg / reference)")
+        ptrs = [C.c_void_p(int(p)) if p else None for p in (node_feature, edge_list, edge_attr, node_eigen)]
+        self._check(self.lib.flowgnn_set_batch_device(self._h, len(nn), _pi(nn), _pi(ne), _lib.LAYOUT_IDS[layout], *ptrs),
+                    "flowgnn_set_batch_device")
+        self.num_graphs = len(nn)
+        self.total_nodes = int(nn.sum(dtype=np.int64))
+        self.total_edges = int(ne.sum(dtype=np.int64))
+
+    def stream_handle(self) -> int:
+        """The hipStream_t the engine launches on (its own, or the one given to set_stream), as an int."""
+        p = C.c_void_p()
+        self._check(self.lib.flowgnn_stream(self._h, C.byref(p)), "flowgnn_stream")
+        return int(p.value or 0)
+
+    def _device_batch_args(self, x, edge_index, edge_attr, node_eigen, ptr, nums_of_edges):
+        import torch
+        dev = torch.device("cuda", self.device)
+        if x.dtype == torch.int64 and edge_index.dtype == torch.int64:
+            layout, n_e = "pyg", (edge_index.shape[1] if edge_index.dim() == 2 and edge_index.shape[0] == 2 else -1)
+        elif x.dtype == torch.int32 and edge_index.dtype == torch.int32:
+            layout, n_e = "reference", (edge_index.shape[0] if edge_index.dim() == 2 and edge_index.shape[1] == 2 else -1)
+        else:
+            raise TypeError("x / edge_index: both int64 (PyG layout) or both int32 (reference layout)")
+        if n_e < 0:
+            raise ValueError("edge_index: [2][E] in the PyG layout, [E][2] in the reference layout")
+        need = [("x", x, x.dtype, (-1, 9)), ("edge_index", edge_index, x.dtype, None)]
+        if edge_attr is not None:
+            need.append(("edge_attr", edge_attr, x.dtype, (n_e, 3)))
+        if node_eigen is not None:
+            need.append(("node_eigen", node_eigen, torch.float32, (x.shape[0], 4)))
+        for name, t, dtype, shape in need:
+            if t.device != dev:
+                raise ValueError(f"{name} is on {t.device}, the engine on {dev}")
+            if t.dtype != dtype:
+                raise TypeError(f"{name}: dtype {t.dtype}, expected {dtype}")
+            if not t.is_contiguous():
+                raise ValueError(f"{name} is not contiguous")
+            if shape is not None and (t.dim() != 2 or t.shape[1] != shape[1] or (shape[0] >= 0 and t.shape[0] != shape[0])):
+                raise ValueError(f"{name}: shape {tuple(t.shape)}, expected [{'N' if shape[0] < 0 else shape[0]}][{shape[1]}]")
+        if ptr is None:
+            raise ValueError("ptr (the node pointer, [G + 1]) is required")
+        ptr_h = ptr.detach().to("cpu", torch.int64).numpy() if isinstance(ptr, torch.Tensor) else np.asarray(ptr, dtype=np.int64)
+        nn = np.diff(ptr_h)
+        if ptr_h.size < 1 or ptr_h[0] != 0 or ptr_h[-1] != x.shape[0]:
+            raise ValueError("ptr must run from 0 to N (the rows of x)")
+        if nums_of_edges is None:
+            if layout != "pyg":
+                raise ValueError("the reference layout holds local ids: pass nums_of_edges")
+            # each edge's graph from its source id, bucketed against ptr (the edges of a PyG Batch are grouped by graph)
+            gid = torch.bucketize(edge_index[0], torch.as_tensor(ptr_h[1:], device=dev), right=True)
+            ne = torch.bincount(gid, minlength=len(nn))[: len(nn)].cpu().numpy()
+            if int(ne.sum()) != n_e:
+                raise ValueError("edge_index[0] holds ids outside [0, N): pass nums_of_edges")
+        else:
+            ne = (nums_of_edges.detach().cpu().numpy() if isinstance(nums_of_edges, torch.Tensor) else np.asarray(nums_of_edges))
+        return layout, nn, ne
+
+    def set_batch_device(self, x, edge_index, edge_attr=None, node_eigen=None, *, ptr, nums_of_edges=None):
+        """A batch whose arrays are torch tensors on the engine's device (flowgnn.h: flowgnn_set_batch_device).  The layout follows
+        the dtypes: int64 x [N][9] / edge_index [2][E] with batch-global ids / edge_attr [E][3] (a PyG Batch), or int32 x [N][9] /
+        edge_list [E][2] with local ids / edge_attr [E][3] (the reference's).  node_eigen: float32 [N][4] (DGN).  Per-graph sizes:
+        `ptr` (node pointer [G + 1], any device) and `nums_of_edges` ([G]; PyG layout: computed from edge_index[0] when omitted).
+        The engine's stream is ordered after torch's current stream, and torch's current stream after the ingest, so the call needs
+        no synchronisation and the caller may drop or overwrite the tensors at once."""
+        import torch
+        layout, nn, ne = self._device_batch_args(x, edge_index, edge_attr, node_eigen, ptr, nums_of_edges)
+        cur = torch.cuda.current_stream(self.device)
+        es = torch.cuda.ExternalStream(self.stream_handle(), device=torch.device("cuda", self.device))
+        es.wait_stream(cur)
+        self.set_batch_device_ptrs(nn, ne, layout, x.data_ptr(), edge_index.data_ptr(),
+                                   edge_attr.data_ptr() if edge_attr is not None else 0,
+                                   node_eigen.data_ptr() if node_eigen is not None else 0)
+        # The caching allocator must not recycle the inputs before the ingest has read them: torch's current stream waits for it and
+        # the inputs are recorded on THAT stream (whichever stream allocated them).  Not on the engine's own stream: torch records an
+        # event on every recorded stream when a tensor is freed, and the engine's stream dies with the engine.
+        cur.wait_stream(es)
+        for t in (x, edge_index, edge_attr, node_eigen):
+            if t is not None:
+                t.record_stream(cur)
+
+    def forward_device(self, x, edge_index, edge_attr=None, node_eigen=None, *, ptr, nums_of_edges=None):
+        """set_batch_device, then one forward into a new torch tensor on the device ([G], or [G][num_tasks]); torch's current stream
+        waits for the engine's, the host does not.  Validation errors (and the range check that can repeat a pass on the exact
+        kernels) are seen by sync(), which raises; without it the tensor of a refused batch holds whatever the kernels wrote."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        cur = torch.cuda.current_stream(dev)
+        G = (len(ptr) - 1) if not isinstance(ptr, torch.Tensor) else int(ptr.numel()) - 1
+        out = torch.empty(G * self.num_tasks, dtype=torch.float32, device=dev)  # (before the engine's stream waits for torch's)
+        self.set_batch_device(x, edge_index, edge_attr, node_eigen, ptr=ptr, nums_of_edges=nums_of_edges)
+        es = torch.cuda.ExternalStream(self.stream_handle(), device=dev)
+        if G:
+            self.set_results_buffer(out.data_ptr())
+            self._results_tensor = out  # the engine writes there until the next set_batch: keep it alive
+        self.run()
+        cur.wait_stream(es)
+        return out.view(G, self.num_tasks) if self.num_tasks > 1 else out
 
     def run(self):
         self._check(self.lib.flowgnn_run(self._h), "flowgnn_run")

@@ -74,6 +74,35 @@ class GraphBatch:
         gid = np.repeat(np.arange(self.num_graphs), self.nums_of_edges)
         return self.edge_list.astype(np.int64) + no[gid][:, None]
 
+    def to_pyg(self, device=None) -> dict:
+        """The batch in PyG's layout: x int64 [N][9], edge_index int64 [2][E] with batch-global ids, edge_attr int64 [E][3], ptr int64
+        [G + 1] (+ node_eigen float32 [N][4] when present) -- torch tensors on `device`, numpy arrays when it is None.  The keys are
+        the arguments of Engine.set_batch_device / forward_device."""
+        d = {"x": self.node_feature.astype(np.int64),
+             "edge_index": np.ascontiguousarray(self.global_edges().T),
+             "edge_attr": self.edge_attr.astype(np.int64),
+             "ptr": self.node_offsets()}
+        if self.node_eigen is not None:
+            d["node_eigen"] = np.ascontiguousarray(self.node_eigen, dtype=np.float32)
+        if device is None:
+            return d
+        import torch
+        return {k: torch.from_numpy(v).to(device) for k, v in d.items()}
+
+    @classmethod
+    def from_pyg(cls, x, edge_index, edge_attr, ptr, node_eigen=None) -> "GraphBatch":
+        """Inverse of to_pyg (numpy arrays or CPU tensors; edges grouped by graph): local ids, int32 arrays, counts from ptr and
+        from each edge's source id."""
+        x, ei, ea, ptr = (np.asarray(a) for a in (x, edge_index, edge_attr, ptr))
+        ptr = ptr.astype(np.int64)
+        G = ptr.size - 1
+        gid = np.searchsorted(ptr[1:], ei[0], side="right")
+        ne = np.bincount(gid, minlength=G)[:G]
+        el = (ei.T - ptr[gid][:, None]).astype(np.int32)
+        eig = None if node_eigen is None else np.asarray(node_eigen, dtype=np.float32)
+        return cls(np.diff(ptr).astype(np.int32), ne.astype(np.int32), x.astype(np.int32), np.ascontiguousarray(el),
+                   ea.astype(np.int32), eig)
+
 
 def concat_batches(batches) -> GraphBatch:
     eig = None

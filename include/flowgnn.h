@@ -229,6 +229,39 @@ int flowgnn_set_batch(flowgnn_engine* e, int num_graphs,
                       const int* node_feature, const int* edge_list, const int* edge_attr,
                       const float* node_eigen);
 /*
+ * Upload one concatenated batch whose arrays are already in DEVICE memory of the engine's device (e.g. a PyG Batch moved to the
+ * GPU, or a dataset kept in HBM), in one of two layouts:
+ */
+#define FLOWGNN_LAYOUT_REFERENCE 0  /* int32 arrays exactly as flowgnn_set_batch takes them: node_feature [N][9], edge_list [E][2] local ids, edge_attr [E][3] */
+#define FLOWGNN_LAYOUT_PYG       1  /* int64 x [N][9], int64 edge_index [2][E] with batch-global node ids (PyG Batch), int64 edge_attr [E][3] */
+/*
+ *  nums_of_nodes / nums_of_edges are HOST arrays, as for flowgnn_set_batch: counts, offsets, limit checks, graph tiles,
+ *  bin-packed tiles and the job totals / fill are built from them exactly as flowgnn_set_batch builds them, and the results are
+ *  bit-identical to flowgnn_set_batch with the same arrays.  The edges of graph g are [eoff[g], eoff[g + 1]) (eoff = prefix sums of
+ *  nums_of_edges), in both layouts: the order of a PyG Batch.  In the PyG layout an endpoint becomes local as id - noff[g]; an
+ *  endpoint outside [noff[g], noff[g + 1]) or an int64 value that does not fit int32 becomes -1, which the device validation then
+ *  refuses with the code flowgnn_set_batch would give (FLOWGNN_ERR_EDGE_RANGE / _EDGE_ATTR / _NODE_FEAT).  GAT reads its node
+ *  features as raw numbers: there an x value outside int32 sets FLOWGNN_ERR_NODE_FEAT itself.  Such errors surface at
+ *  flowgnn_sync / flowgnn_get_results, as validation errors do, and hold until the next set_batch.
+ *  edge_attr may be NULL for GAT / PNA / DGN; node_eigen (float32 [N][4], both layouts) may be NULL except for DGN.
+ *
+ *  Asynchronous and stream-ordered: the ingest (PyG: one kernel that narrows, transposes and localises; reference: device-to-device
+ *  copies) is enqueued on the engine's launch stream -- its own, or the one given to flowgnn_set_stream -- and the call does not
+ *  wait for it; flowgnn_run needs no event to follow it.  The caller's arrays must be complete ON THAT STREAM when the call is made
+ *  (order the stream after the producer's, e.g. with an event) and must stay unchanged until the ingest has run (a flowgnn_sync, or
+ *  any later point on that stream).  The engine always copies into buffers of its own and keeps no pointer to the caller's.
+ *
+ *  Before anything is enqueued, every non-null array must be memory of the engine's device (hipPointerGetAttributes: pinned or
+ *  pageable host memory is refused) and the bytes the counts imply must lie inside its allocation (hipMemGetAddressRange);
+ *  otherwise, and for a NULL array the model needs or an unknown layout, FLOWGNN_ERR_ARG with a flowgnn_last_error text and no
+ *  change to the engine.  Drops a recorded launch sequence (option hipgraph), as flowgnn_set_batch does.  Single engines only (a
+ *  group's shards live on other devices).
+ */
+int flowgnn_set_batch_device(flowgnn_engine* e, int num_graphs,
+                             const int* nums_of_nodes, const int* nums_of_edges,
+                             int layout, const void* node_feature, const void* edge_list, const void* edge_attr,
+                             const float* node_eigen);
+/*
  * Declare the next flowgnn_set_batch batches to be SHARDS of a job of this many nodes and edges (a multi-process caller that cuts
  * one job over several GPUs, one engine each; flowgnn_group_* does it by itself).  The one choice between kernels that depends on the
  * batch size -- DGN's aggregation, by the density E / N (GIN's front end has had no size rule since round 4) -- is then made from
