@@ -204,7 +204,8 @@ public:
     virtual void set_exact(bool) {}
     // debug taps: make forward() materialise the last layer's node embeddings even if that costs a round trip
     virtual void set_keep_h(bool) {}
-    // 0 = fp32 (default); 1 = the reference's ap_fixed<16,6> bit patterns (GIN / GIN-VN only: ginq.hip)
+    // 0 = fp32 (default); 1 = the reference's ap_fixed<16,6> bit patterns (GIN / GIN-VN only: ginq.hip); 2 = f16 MLP operands
+    // (GIN / GIN-VN only: the single-product kernels of gin_split_f16.hip)
     virtual int set_numeric_mode(int mode) { return mode == 0 ? 0 : 8 /* FLOWGNN_ERR_UNSUPPORTED */; }
     // NUM_TASK of the readout (graph_pred_weights [NUM_TASK][EMB_DIM], out [G][NUM_TASK]); takes effect at the next set_weights
     virtual int set_num_tasks(int t) { return t == 1 ? 0 : 8; }

@@ -1274,7 +1274,8 @@ int flowgnn_set_numeric_mode(flowgnn_engine* e, int mode) {
     if (!e) return FLOWGNN_ERR_ARG;
     e->drop_graph();
     const int rc = e->model->set_numeric_mode(mode);
-    if (rc) e->err = "flowgnn_set_numeric_mode: unknown mode, or the fixed-point readout is single-task and NUM_TASK != 1";
+    if (rc) e->err = "flowgnn_set_numeric_mode: unknown mode, a mode this model does not have (f16: GIN / GIN-VN only), or the fixed-point "
+                     "readout is single-task and NUM_TASK != 1";
     return rc;
 }
 

@@ -620,6 +620,15 @@ public:
         for (int l = 0; l < GIN_L; l++)
             gin_resident_pack_layer(w1 + (size_t)l * GIN_H * GIN_D, b1 + (size_t)l * GIN_H, w2 + (size_t)l * GIN_D * GIN_H,
                                     b2 + (size_t)l * GIN_D, rsplit.data() + (size_t)l * gin_resident_layer_bytes());
+        // both streams once more in the single-product form of FLOWGNN_NUMERIC_F16 (packed here, whatever the mode: switching the mode
+        // later needs no repacking)
+        std::vector<uint8_t> split16(split.size()), rsplit16(rsplit.size());
+        for (int l = 0; l < GIN_L; l++) {
+            gin_split_pack_layer(w1 + (size_t)l * GIN_H * GIN_D, b1 + (size_t)l * GIN_H, w2 + (size_t)l * GIN_D * GIN_H,
+                                 b2 + (size_t)l * GIN_D, split16.data() + (size_t)l * GS_LAYER_BYTES, true);
+            gin_resident_pack_layer(w1 + (size_t)l * GIN_H * GIN_D, b1 + (size_t)l * GIN_H, w2 + (size_t)l * GIN_D * GIN_H,
+                                    b2 + (size_t)l * GIN_D, rsplit16.data() + (size_t)l * gin_resident_layer_bytes(), true, true);
+        }
 #ifdef FLOWGNN_DEV
         // ... re-cut into the ping-pong kernel's pieces, with the edge-embedding tables as half tables (development builds only)
         std::vector<uint8_t> pp_pieces((size_t)GIN_L * gin_pp_layer_bytes());
@@ -640,11 +649,15 @@ public:
         if ((rc = ginq_upload(qw_, nemb, eemb, w1, b1, w2, b2, pw, pb))) return rc;  // Q6.10 copies (numeric mode 1)
         if ((rc = upload(&d_split_, split))) return rc;
         if ((rc = upload(&d_rsplit_, rsplit))) return rc;
+        if ((rc = upload(&d_split16_, split16))) return rc;
+        if ((rc = upload(&d_rsplit16_, rsplit16))) return rc;
         {   // the single-task readout folded through the last layer's second linear layer (gin_resident_kernel, gr_layer)
-            std::vector<float> head(GIN_RESIDENT_HEAD_FLOATS);
+            std::vector<float> head(GIN_RESIDENT_HEAD_FLOATS), head16(GIN_RESIDENT_HEAD_FLOATS);
             const int l = GIN_L - 1;
             gin_resident_head_fold(w1 + (size_t)l * GIN_H * GIN_D, w2 + (size_t)l * GIN_D * GIN_H, b2 + (size_t)l * GIN_D, pw, head.data());
+            gin_resident_head_fold(w1 + (size_t)l * GIN_H * GIN_D, w2 + (size_t)l * GIN_D * GIN_H, b2 + (size_t)l * GIN_D, pw, head16.data(), true);
             if ((rc = upload(&d_head_, head))) return rc;
+            if ((rc = upload(&d_head16_, head16))) return rc;
         }
         {   // pre-combined encoder table of the one-pass tile loader (gin_tile_build_kernel + the resident kernel's ENC form)
             std::vector<float> etab(gin_resident_enc_table_floats());
@@ -750,14 +763,14 @@ public:
     }
 #ifdef FLOWGNN_DEV  // the ping-pong form (dev/gin_pp_device.inc: bit-identical, measured slower) exists in development builds only
     void sub_tile_limits(int& rows, int& edges) const override {
-        const bool on = resident_ && pingpong_ && !virtual_node_;
+        const bool on = resident_ && pingpong_ && !virtual_node_ && !f16_;
         rows = on ? GIN_PP_ROWS : 0;
         edges = on ? GIN_PP_EDGES : 0;
     }
     // the batch's half-tiles on gin_pp_kernel, the few graphs beyond the half-tile limits on gin_resident_kernel.  (Decided from the
     // SHARD's own half-tile fill: unlike the shipped kernels' choices this one does not follow the job -- development only.)
     bool use_pingpong(const DeviceBatch& db) const {
-        return pingpong_ && !virtual_node_ && use_resident(db) && !keep_h_ && num_tasks_ == 1 && fold_readout_ && head_fold_ && db.gtiles.sub_ok &&
+        return pingpong_ && !f16_ && !virtual_node_ && use_resident(db) && !keep_h_ && num_tasks_ == 1 && fold_readout_ && head_fold_ && db.gtiles.sub_ok &&
                db.gtiles.n_sub > 0 && db.gtiles.sub_fill >= resident_min_fill_;
     }
 #endif
@@ -778,13 +791,13 @@ public:
         // 0.51: ahead at every size now -- 8.49 vs 8.73 ms per step at 2^18 graphs, 1.23 vs 1.24 at 32 768, 0.206 vs 0.222 at 4 113.
         // -1 = default = on (development builds: an explicit gin_pingpong keeps the three-kernel front end -- the ping-pong kernel has no
         // encoder in its loader and is never used with a virtual node).
-        const bool want = tile_build_ < 0 ? !(pingpong_ && !virtual_node_) : tile_build_ != 0;
+        const bool want = tile_build_ < 0 ? !(pingpong_ && !virtual_node_ && !f16_) : tile_build_ != 0;
         return want && use_resident(db) && !qmode_ && !keep_h_ && num_tasks_ == 1 && fold_readout_ && head_fold_ && db.b.edge_attr != nullptr;
     }
     bool needs_csr(const DeviceBatch& db) const override { return !one_pass(db); }
     // (asked at flowgnn_set_batch, before the batch is known: the lists are built whenever the one-pass path could take them)
     bool wants_packed_tile_lists() const override {
-        return binpack_ && resident_ && !qmode_ && num_tasks_ == 1 && fold_readout_ && head_fold_ && tile_build_ != 0 && !pingpong_;
+        return binpack_ && resident_ && !qmode_ && num_tasks_ == 1 && fold_readout_ && head_fold_ && tile_build_ != 0 && (!pingpong_ || f16_);
     }
 
     int forward(DeviceBatch& db, Profiler& prof, hipStream_t s) override {
@@ -806,9 +819,9 @@ public:
                 launch_gin_tile_build(tb, t_row, t_graph, reinterpret_cast<uint8_t*>(perm_.p), n_tiles, virtual_node_, resident_order_, s);
             }
             ProfScope p(prof, "gin_resident", s);  // the whole model
-            launch_gin_resident(nullptr, nullptr, nullptr, nullptr, nullptr, d_ecomb_res_, d_rsplit_, d_pw_, d_pb_, t_row, t_graph,
+            launch_gin_resident(nullptr, nullptr, nullptr, nullptr, nullptr, d_ecomb_res_, rsplit(), d_pw_, d_pb_, t_row, t_graph,
                                 reinterpret_cast<uint8_t*>(perm_.p), db.b.node_off, db.out, n_tiles,
-                                db.range_flag, s, virtual_node_, d_head_, resident_order_, resident_prof_, &tb);
+                                db.range_flag, s, virtual_node_, head(), resident_order_, resident_prof_, &tb, 1, f16_);
             db.final_h = 0;
             db.h_valid = false;
             h0_in_hbm_ = false;  // the tile loader computed h_0 on chip
@@ -848,10 +861,10 @@ public:
             const bool rows = keep_h_ || multi;
             {
                 ProfScope p(prof, "gin_resident", s);
-                launch_gin_resident(db.h[0], rows ? db.h[1] : nullptr, db.csr.row_ptr, db.csr.src, db.csr.ecode, d_ecomb_res_, d_rsplit_, d_pw_, d_pb_,
+                launch_gin_resident(db.h[0], rows ? db.h[1] : nullptr, db.csr.row_ptr, db.csr.src, db.csr.ecode, d_ecomb_res_, rsplit(), d_pw_, d_pb_,
                                     db.gtiles.row_start, db.gtiles.graph_start, reinterpret_cast<uint8_t*>(perm_.p), db.b.node_off,
                                     multi ? nullptr : db.out, db.gtiles.n_tiles, db.range_flag, s, virtual_node_,
-                                    (!rows && fold_readout_ && head_fold_) ? d_head_ : nullptr, resident_order_, resident_prof_);
+                                    (!rows && fold_readout_ && head_fold_) ? head() : nullptr, resident_order_, resident_prof_, nullptr, 1, f16_);
             }
             db.final_h = rows ? 1 : 0;
             db.h_valid = rows;
@@ -867,8 +880,8 @@ public:
                 // leaves the kernel (db.scratch as float[n]); the rows are written only for the flowgnn_get_h tap
                 const bool fold = l == GIN_L - 1 && fold_readout_ && !keep_h_ && !multi;
                 launch_gin_layer_split(db.h[cur], fold ? db.scratch : db.h[cur ^ 1], db.csr.row_ptr, db.csr.src, db.csr.ecode,
-                                       layer_dev(l).ecomb, d_split_ + (size_t)l * GS_LAYER_BYTES, n, db.b.e_tot, l != GIN_L - 1,
-                                       db.range_flag, split_nt_, s, fold ? d_pw_ : nullptr);
+                                       layer_dev(l).ecomb, (f16_ ? d_split16_ : d_split_) + (size_t)l * GS_LAYER_BYTES, n, db.b.e_tot,
+                                       l != GIN_L - 1, db.range_flag, split_nt_, s, fold ? d_pw_ : nullptr, f16_);
                 if (fold) {
                     folded = true;
                     break;
@@ -946,9 +959,10 @@ public:
     void set_exact(bool on) override { exact_ = on; }
     void set_keep_h(bool on) override { keep_h_ = on; }
     int set_numeric_mode(int mode) override {
-        if (mode != 0 && mode != 1) return 8;
+        if (mode != 0 && mode != 1 && mode != 2) return 8;
         if (mode == 1 && num_tasks_ != 1) return 8;  // the Q6.10 readout is single-task (as the reference's)
         qmode_ = mode == 1;
+        f16_ = mode == 2;
         return 0;
     }
     int set_num_tasks(int t) override {
@@ -970,6 +984,10 @@ public:
     }
 
 private:
+    // the weight streams of the numeric mode: FLOWGNN_NUMERIC_F16 runs the single-product instances of the split kernels on their own
+    // streams (the exact re-run and the options that select non-split kernels -- gin_mfma 32, gin_unfused 1 -- read neither)
+    const uint8_t* rsplit() const { return f16_ ? d_rsplit16_ : d_rsplit_; }
+    const float* head() const { return f16_ ? d_head16_ : d_head_; }
     void free_all() {
         float** ptrs[] = {&d_chunks_, &d_nemb_, &d_pw_, &d_pb_, &d_ecomb_, &d_ecomb_res_, &d_w1f_, &d_w1tail_, &d_b1p_, &d_w2f_, &d_b2p_};
         for (auto p : ptrs)
@@ -977,6 +995,9 @@ private:
         if (d_split_) { (void)hipFree(d_split_); d_split_ = nullptr; }
         if (d_rsplit_) { (void)hipFree(d_rsplit_); d_rsplit_ = nullptr; }
         if (d_head_) { (void)hipFree(d_head_); d_head_ = nullptr; }
+        if (d_split16_) { (void)hipFree(d_split16_); d_split16_ = nullptr; }
+        if (d_rsplit16_) { (void)hipFree(d_rsplit16_); d_rsplit16_ = nullptr; }
+        if (d_head16_) { (void)hipFree(d_head16_); d_head16_ = nullptr; }
         if (d_enc_tab_) { (void)hipFree(d_enc_tab_); d_enc_tab_ = nullptr; }
         if (d_pp_pieces_) { (void)hipFree(d_pp_pieces_); d_pp_pieces_ = nullptr; }
         if (d_pp_tables_) { (void)hipFree(d_pp_tables_); d_pp_tables_ = nullptr; }
@@ -1001,6 +1022,7 @@ private:
     bool exact_ = false;
     bool keep_h_ = false;
     bool qmode_ = false;  // flowgnn_set_numeric_mode(FLOWGNN_NUMERIC_Q6_10)
+    bool f16_ = false;    // flowgnn_set_numeric_mode(FLOWGNN_NUMERIC_F16): single-product instances of the split kernels
     int num_tasks_ = 1;   // NUM_TASK (GIN/src/dcl.h:25) as a run-time dimension
     GinQWeights qw_;
     GrowBufI perm_;  // graph-resident path: per-tile descriptors (gin_tile_prep_kernel / gin_tile_build_kernel)
@@ -1021,6 +1043,9 @@ private:
     uint8_t* d_split_ = nullptr;
     uint8_t* d_rsplit_ = nullptr;  // weight stream of the graph-resident kernel
     float* d_head_ = nullptr;      // gin_resident_head_fold
+    uint8_t* d_split16_ = nullptr;   // FLOWGNN_NUMERIC_F16: the two weight streams and the folded head in single-product form
+    uint8_t* d_rsplit16_ = nullptr;
+    float* d_head16_ = nullptr;
     bool head_fold_ = true;  // gin_head_fold=0: the last layer's second linear layer is computed (readout not folded through it)
     float* d_chunks_ = nullptr;
     float* d_ecomb_res_ = nullptr;  // ecomb * 2^-16: the resident kernel's walk (GR_MSG2, gin_split.hip)

@@ -21,15 +21,18 @@ constexpr int GS_CHUNK_STRIDE = 27648; // in global memory: 27 pieces of 1 KiB
 constexpr size_t GS_LAYER_BYTES = (size_t)GS_STEPS * GS_CHUNK_STRIDE;
 
 // w1[200][100], b1[200], w2[100][200], b2[100] (row-major, host) -> GS_LAYER_BYTES at `out` (host)
-void gin_split_pack_layer(const float* w1, const float* b1, const float* w2, const float* b2, uint8_t* out);
+// f16 = true: the stream of the single-product kernels (FLOWGNN_NUMERIC_F16): hi halves = the scaled weights rounded to nearest
+// even, lo halves 0, the fp32 K-tail fragments rounded the same way
+void gin_split_pack_layer(const float* w1, const float* b1, const float* w2, const float* b2, uint8_t* out, bool f16 = false);
 
 // variant (FLOWGNN_GIN_SPLIT_NT): 4 = eight-wave workgroups of 128 nodes (default), 1 / 2 = four waves x 1 / 2 node tiles
 // pool_w != null (last layer, readout folded in): hout is float[n_tot] and receives h'[v] . pool_w instead of the rows
 // one GIN layer: hout = MLP(h[v] + sum_e relu(h[src_e] + ecomb[code_e])); *range_flag |= 1 if an operand left the
 // range in which the split is fp32-accurate (the caller then repeats the forward pass on the fp32 MFMA kernel)
+// f16 = true: the single-product instance (FLOWGNN_NUMERIC_F16; chunks packed with f16 = true)
 void launch_gin_layer_split(const float* h, float* hout, const int* row_ptr, const int* src, const uint8_t* ecode,
                             const float* ecomb, const uint8_t* chunks, int n_tot, int e_tot, int relu_out, int* range_flag,
-                            int variant, hipStream_t s, const float* pool_w = nullptr);
+                            int variant, hipStream_t s, const float* pool_w = nullptr, bool f16 = false);
 
 // Graph-resident form (gin_split.hip, gin_resident_kernel): all five layers + readout in one launch; a persistent workgroup
 // keeps a tile of whole graphs (GraphTiles: <= GIN_RESIDENT_ROWS rows, <= GIN_RESIDENT_EDGES in-edges) in LDS across the layers.
@@ -37,7 +40,9 @@ void launch_gin_layer_split(const float* h, float* hout, const int* row_ptr, con
 // the flowgnn_get_h tap; out [G] receives the logits.
 // weight stream of the resident kernel (its own chunk format: gin_split.hip "GR chunks"); chunks_all = 5 x gin_resident_layer_bytes()
 size_t gin_resident_layer_bytes();
-void gin_resident_pack_layer(const float* w1, const float* b1, const float* w2, const float* b2, uint8_t* out, bool merged = true);
+// f16 = true: the single-product stream (FLOWGNN_NUMERIC_F16): hi halves rounded to nearest even, every lo half (packed K tails included) 0
+void gin_resident_pack_layer(const float* w1, const float* b1, const float* w2, const float* b2, uint8_t* out, bool merged = true,
+                             bool f16 = false);
 constexpr int GIN_RESIDENT_ROWS = 256;
 constexpr int GIN_RESIDENT_EDGES = 1280;
 constexpr int GIN_RESIDENT_DESC_BYTES = 3584;  // per-tile descriptor built by gin_tile_prep_kernel (CSR slice as 16-bit words, row offsets, column owners)
@@ -77,11 +82,12 @@ void launch_gin_resident(const float* h0, float* hout, const int* row_ptr, const
                          const uint8_t* chunks_all, const float* pool_w, const float* pool_b, const int* tile_row, const int* tile_graph,
                          uint8_t* tile_desc /* scratch, n_tiles x GIN_RESIDENT_DESC_BYTES */, const int* node_off, float* out, int n_tiles,
                          int* range_flag, hipStream_t s, bool hubs = false, const float* head_u = nullptr, int col_order = 0, bool prof = false,
-                         const GinTileBuild* tb = nullptr, int tstride = 1);
+                         const GinTileBuild* tb = nullptr, int tstride = 1, bool f16 = false /* single-product instances, FLOWGNN_NUMERIC_F16 */);
 // head_u for launch_gin_resident (GIN_RESIDENT_HEAD_FLOATS floats): the single-task readout folded through the LAST layer's second
 // linear layer -- u = W2^T w_pred divided by the first layer's power-of-two weight scale, padded to 208, then c = b2 . w_pred
 constexpr int GIN_RESIDENT_HEAD_FLOATS = 209;
-void gin_resident_head_fold(const float* w1_last, const float* w2_last, const float* b2_last, const float* pool_w, float* out);
+// (f16 = true: u rounded to f16 once, to nearest even -- the folded readout of FLOWGNN_NUMERIC_F16)
+void gin_resident_head_fold(const float* w1_last, const float* w2_last, const float* b2_last, const float* pool_w, float* out, bool f16 = false);
 
 
 }  // namespace fg

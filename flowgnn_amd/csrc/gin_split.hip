@@ -27,6 +27,10 @@
 //   hidden tiles 2 ks, 2 ks + 1 after the first layer.  K = 100 = 3 x 32 + 4: the 4-feature tail is one fp32 MFMA.
 //   8 steps: step s runs hidden tiles 2s, 2s+1 of MLP1 (13 tiles, 20 MFMAs per node tile) and K-step s-1 of MLP2
 //   (7 output tiles x 3 = 21 MFMAs per node tile).
+//
+// Single-product instances (FLOWGNN_NUMERIC_F16): gin_split_f16.hip compiles this file once more with GS_SINGLE_PRODUCT = 1 -- the
+// same kernels under their own names (gin_layer_split_f16_kernel, gin_resident_f16_kernel), with GS_F16 = true, behind the launchers'
+// f16 argument.  Everything else (tile builders, weight packing, the launchers themselves) exists in this file's own translation unit only.
 #include "gin_split.h"
 
 #include <cmath>
@@ -37,10 +41,15 @@
 
 #include "device_common.h"
 
+#ifndef GS_SINGLE_PRODUCT
+#define GS_SINGLE_PRODUCT 0
+#endif
+
 namespace fg {
 
 namespace {
 
+constexpr bool GS_F16 = GS_SINGLE_PRODUCT != 0;  // the kernels of this translation unit: single-product (f16 mode) or split (f32)
 constexpr int GS_D = 100;
 constexpr int GS_H = 200;
 constexpr int GS_T2 = 7;
@@ -63,6 +72,20 @@ typedef uint32_t uint4_t __attribute__((ext_vector_type(4)));
         asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(lb_) : "v"(hp_), "v"(b_));   \
         (HI) = hp_;                                                                                               \
         (LO) = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(la_, lb_));                                \
+    } while (0)
+
+// Single-product instances (FLOWGNN_NUMERIC_F16, template flag F16 below): every MLP operand is ONE f16 value, rounded to nearest
+// even -- (_Float16) casts, one v_cvt_pk_f16_f32 per pair on gfx950 -- and a product is the single MFMA w x (fp32 accumulate).  The
+// weight streams of that mode carry zeros in their lo halves (put_split, gin_resident_pack_layer), so the packed K-tail MFMAs, which
+// hold all split terms in one instruction, compute the single term as they stand; the hi.lo / lo.hi MFMAs are not issued.
+typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint32_t gs_pack_rne(float a, float b) { return __builtin_bit_cast(uint32_t, (half2_t){(_Float16)a, (_Float16)b}); }
+__device__ __forceinline__ float gs_rne(float a) { return (float)(_Float16)a; }  // the operand an f16 MFMA would see, as a float
+// the B operands of a pair: split (hi + lo) or, F16, the rounded pair and lo = 0
+#define GS_OPER2(F16_, a, b, HI, LO)                                              \
+    do {                                                                          \
+        if constexpr (F16_) { (HI) = gs_pack_rne((a), (b)); (LO) = 0u; }          \
+        else { GS_SPLIT2(a, b, HI, LO); }                                         \
     } while (0)
 
 __device__ __forceinline__ float gs_relu(float x) {  // max(x, 0) as v_max_i32: one instruction where fmaxf on an MFMA
@@ -90,7 +113,7 @@ __device__ __forceinline__ void gs_issue_chunk(const uint8_t* __restrict__ gchun
     }
 }
 
-template <int NT>
+template <int NT, bool F16>
 __device__ __forceinline__ void gs_step(const char* wb, int s, int lane, int g, const uint4_t (&in_hi)[NT][3],
                                         const uint4_t (&in_lo)[NT][3], const float (&in_t)[NT], uint4_t (&h_hi)[NT],
                                         uint4_t (&h_lo)[NT], float4_t (&acc2)[NT][GS_T2], float& vmax) {
@@ -109,20 +132,22 @@ __device__ __forceinline__ void gs_step(const char* wb, int s, int lane, int g, 
 #pragma unroll
             for (int tl = 0; tl < 2; tl++)
 #pragma unroll
-                for (int p = 0; p < 2; p++)
+                for (int p = 0; p < (F16 ? 1 : 2); p++)
                     a[tl][p] = *reinterpret_cast<const uint4_t*>(wb + ((ks * 2 + tl) * 2 + p) * 1024 + lane * 16);
 #pragma unroll
             for (int tl = 0; tl < 2; tl++)
 #pragma unroll
                 for (int nt = 0; nt < NT; nt++) acc1[tl][nt] = GS_MFMA16(a[tl][0], in_hi[nt][ks], acc1[tl][nt]);
+            if constexpr (!F16) {
 #pragma unroll
-            for (int tl = 0; tl < 2; tl++)
+                for (int tl = 0; tl < 2; tl++)
 #pragma unroll
-                for (int nt = 0; nt < NT; nt++) acc1[tl][nt] = GS_MFMA16(a[tl][0], in_lo[nt][ks], acc1[tl][nt]);
+                    for (int nt = 0; nt < NT; nt++) acc1[tl][nt] = GS_MFMA16(a[tl][0], in_lo[nt][ks], acc1[tl][nt]);
 #pragma unroll
-            for (int tl = 0; tl < 2; tl++)
+                for (int tl = 0; tl < 2; tl++)
 #pragma unroll
-                for (int nt = 0; nt < NT; nt++) acc1[tl][nt] = GS_MFMA16(a[tl][1], in_hi[nt][ks], acc1[tl][nt]);
+                    for (int nt = 0; nt < NT; nt++) acc1[tl][nt] = GS_MFMA16(a[tl][1], in_hi[nt][ks], acc1[tl][nt]);
+            }
         }
 #pragma unroll
         for (int tl = 0; tl < 2; tl++) {
@@ -140,10 +165,10 @@ __device__ __forceinline__ void gs_step(const char* wb, int s, int lane, int g, 
             vmax = __builtin_fmaxf(__builtin_fmaxf(vmax, r1.x), r1.y);
             vmax = __builtin_fmaxf(__builtin_fmaxf(vmax, r1.z), r1.w);
             asm volatile("" : "+v"(vmax));
-            GS_SPLIT2(r0.x, r0.y, n_hi[nt].x, n_lo[nt].x);
-            GS_SPLIT2(r0.z, r0.w, n_hi[nt].y, n_lo[nt].y);
-            GS_SPLIT2(r1.x, r1.y, n_hi[nt].z, n_lo[nt].z);
-            GS_SPLIT2(r1.z, r1.w, n_hi[nt].w, n_lo[nt].w);
+            GS_OPER2(F16, r0.x, r0.y, n_hi[nt].x, n_lo[nt].x);
+            GS_OPER2(F16, r0.z, r0.w, n_hi[nt].y, n_lo[nt].y);
+            GS_OPER2(F16, r1.x, r1.y, n_hi[nt].z, n_lo[nt].z);
+            GS_OPER2(F16, r1.z, r1.w, n_hi[nt].w, n_lo[nt].w);
         }
     }
     if (s > 0) {  // MLP2: K-step s-1 = hidden tiles 2(s-1), 2(s-1)+1 of the previous step
@@ -153,7 +178,7 @@ __device__ __forceinline__ void gs_step(const char* wb, int s, int lane, int g, 
 #pragma unroll
             for (int tl = 0; tl < 2; tl++)
 #pragma unroll
-                for (int p = 0; p < 2; p++)
+                for (int p = 0; p < (F16 ? 1 : 2); p++)
                     if (t0 + tl < GS_T2)
                         a[tl][p] = *reinterpret_cast<const uint4_t*>(wb + GS_W2_OFF + ((t0 + tl) * 2 + p) * 1024 + lane * 16);
 #pragma unroll
@@ -161,16 +186,18 @@ __device__ __forceinline__ void gs_step(const char* wb, int s, int lane, int g, 
 #pragma unroll
                 for (int nt = 0; nt < NT; nt++)
                     if (t0 + tl < GS_T2) acc2[nt][t0 + tl] = GS_MFMA16(a[tl][0], h_hi[nt], acc2[nt][t0 + tl]);
+            if constexpr (!F16) {
 #pragma unroll
-            for (int tl = 0; tl < 2; tl++)
+                for (int tl = 0; tl < 2; tl++)
 #pragma unroll
-                for (int nt = 0; nt < NT; nt++)
-                    if (t0 + tl < GS_T2) acc2[nt][t0 + tl] = GS_MFMA16(a[tl][0], h_lo[nt], acc2[nt][t0 + tl]);
+                    for (int nt = 0; nt < NT; nt++)
+                        if (t0 + tl < GS_T2) acc2[nt][t0 + tl] = GS_MFMA16(a[tl][0], h_lo[nt], acc2[nt][t0 + tl]);
 #pragma unroll
-            for (int tl = 0; tl < 2; tl++)
+                for (int tl = 0; tl < 2; tl++)
 #pragma unroll
-                for (int nt = 0; nt < NT; nt++)
-                    if (t0 + tl < GS_T2) acc2[nt][t0 + tl] = GS_MFMA16(a[tl][1], h_hi[nt], acc2[nt][t0 + tl]);
+                    for (int nt = 0; nt < NT; nt++)
+                        if (t0 + tl < GS_T2) acc2[nt][t0 + tl] = GS_MFMA16(a[tl][1], h_hi[nt], acc2[nt][t0 + tl]);
+            }
         }
     }
     if (s < GS_STEPS - 1) {
@@ -192,6 +219,7 @@ __global__ __launch_bounds__(WAVES * 64) void gin_layer_split_kernel(const float
     __shared__ __attribute__((aligned(16))) char s_a[GS_CHUNK_BYTES];  // edge-embedding combos, then odd chunks
     __shared__ __attribute__((aligned(16))) char s_b[GS_CHUNK_BYTES];  // even chunks
     __shared__ float s_hub[NT == 1 ? WAVES * GS_MAXHUB * GS_D : 1];     // parked sums of hub rows
+    constexpr bool F16 = GS_F16;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // in an SGPR: DMA addresses = scalar base + lane * 16
     const int j = lane & 15, g = lane >> 4;
@@ -352,15 +380,18 @@ __global__ __launch_bounds__(WAVES * 64) void gin_layer_split_kernel(const float
         bq[nt][24] += self_t[nt];
 #pragma unroll
         for (int ks = 0; ks < 3; ks++) {
-            GS_SPLIT2(bq[nt][8 * ks + 0], bq[nt][8 * ks + 1], in_hi[nt][ks].x, in_lo[nt][ks].x);
-            GS_SPLIT2(bq[nt][8 * ks + 2], bq[nt][8 * ks + 3], in_hi[nt][ks].y, in_lo[nt][ks].y);
-            GS_SPLIT2(bq[nt][8 * ks + 4], bq[nt][8 * ks + 5], in_hi[nt][ks].z, in_lo[nt][ks].z);
-            GS_SPLIT2(bq[nt][8 * ks + 6], bq[nt][8 * ks + 7], in_hi[nt][ks].w, in_lo[nt][ks].w);
+            GS_OPER2(F16, bq[nt][8 * ks + 0], bq[nt][8 * ks + 1], in_hi[nt][ks].x, in_lo[nt][ks].x);
+            GS_OPER2(F16, bq[nt][8 * ks + 2], bq[nt][8 * ks + 3], in_hi[nt][ks].y, in_lo[nt][ks].y);
+            GS_OPER2(F16, bq[nt][8 * ks + 4], bq[nt][8 * ks + 5], in_hi[nt][ks].z, in_lo[nt][ks].z);
+            GS_OPER2(F16, bq[nt][8 * ks + 6], bq[nt][8 * ks + 7], in_hi[nt][ks].w, in_lo[nt][ks].w);
         }
 #pragma unroll
         for (int k = 0; k < 24; k += 2)
             vmax = __builtin_fmaxf(__builtin_fmaxf(vmax, __builtin_fabsf(bq[nt][k])), __builtin_fabsf(bq[nt][k + 1]));
-        in_t[nt] = bq[nt][24];
+        // K tail (features 96..99): an fp32 MFMA; F16: of the rounded operand and the rounded weights (gin_split_pack_layer), whose
+        // products are exact in fp32 -- the single term an f16 MFMA would form
+        if constexpr (F16) vmax = __builtin_fmaxf(vmax, __builtin_fabsf(bq[nt][24]));
+        in_t[nt] = F16 ? gs_rne(bq[nt][24]) : bq[nt][24];
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's pieces of chunk 0
     __syncthreads();  // chunk 0 resident; every wave is done with the edge-embedding combos: s_a may be overwritten
@@ -381,12 +412,12 @@ __global__ __launch_bounds__(WAVES * 64) void gin_layer_split_kernel(const float
     for (int c = 0; c < GS_STEPS; c += 2) {
         // even step: compute from s_b while chunk c+1 streams into s_a
         gs_issue_chunk<WAVES>(wchunks + (size_t)(c + 1) * GS_CHUNK_STRIDE, s_a, wave, lane);
-        gs_step<NT>(s_b, c, lane, g, in_hi, in_lo, in_t, h_hi, h_lo, acc2, vmax);
+        gs_step<NT, F16>(s_b, c, lane, g, in_hi, in_lo, in_t, h_hi, h_lo, acc2, vmax);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's pieces of chunk c+1 have landed
         __syncthreads();                                  // everyone's landed; everyone is done with s_b
         // odd step: compute from s_a while chunk c+2 streams into s_b
         if (c + 2 < GS_STEPS) gs_issue_chunk<WAVES>(wchunks + (size_t)(c + 2) * GS_CHUNK_STRIDE, s_b, wave, lane);
-        gs_step<NT>(s_a, c + 1, lane, g, in_hi, in_lo, in_t, h_hi, h_lo, acc2, vmax);
+        gs_step<NT, F16>(s_a, c + 1, lane, g, in_hi, in_lo, in_t, h_hi, h_lo, acc2, vmax);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
     }
@@ -565,7 +596,8 @@ struct GrNoHook { __device__ __forceinline__ void operator()() const {} };
 // HOOK: work of the caller's run in the MIDDLE of the step -- between its two hidden tiles (KIND 4), behind the first unit of its only one
 // (KIND 5) -- where the SIMD's two waves arrive at different times: one wave's VALU / memory instructions then issue beside its partner's
 // MFMAs.  At the step's ends, where both waves stand at the barrier together, the same instructions stop the matrix pipe.
-template <int KIND, bool PEND_IN = false, bool PEND_OUT = false, class HOOK = GrNoHook>
+// F16: the single-product instance (GS_OPER2): only the w_hi x_hi MFMAs of every unit are issued and only hi fragments are read.
+template <int KIND, bool F16, bool PEND_IN = false, bool PEND_OUT = false, class HOOK = GrNoHook>
 __device__ __forceinline__ void gr_step(const char* wb, int lane, int g, const uint4_t (&in_hi)[2][3], const uint4_t (&in_lo)[2][3],
                                         const uint4_t (&in_tb)[2], uint4_t (&hb_hi)[2], uint4_t (&hb_lo)[2], float4_t (&acc2)[2][GS_T2],
                                         float& vmax, float4_t (&pend)[2], const float* u_step = nullptr, float* dot = nullptr, int wave = 0,
@@ -576,30 +608,27 @@ __device__ __forceinline__ void gr_step(const char* wb, int lane, int g, const u
 #define GR_PRIO_FLIP(TO_OLD) if (GR_FLIP) { if ((wave >= 4) != (TO_OLD)) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0); }
     constexpr int NTL = KIND == 5 ? 1 : 2;
     uint4_t f0[2], f1[2];  // fragment double buffer: f0 = even units, f1 = odd units
-#define GR_U2_LOAD(F, T) F[0] = GR_LD(GRC_W2_OFF + (2 * (T)) * 1024); F[1] = GR_LD(GRC_W2_OFF + (2 * (T) + 1) * 1024);
-#define GR_U2_MFMA(F, T)                                          \
-    acc2[0][T] = GS_MFMA16(F[0], hb_hi[0], acc2[0][T]);           \
-    acc2[1][T] = GS_MFMA16(F[0], hb_hi[1], acc2[1][T]);           \
-    acc2[0][T] = GS_MFMA16(F[0], hb_lo[0], acc2[0][T]);           \
-    acc2[1][T] = GS_MFMA16(F[0], hb_lo[1], acc2[1][T]);           \
-    acc2[0][T] = GS_MFMA16(F[1], hb_hi[0], acc2[0][T]);           \
-    acc2[1][T] = GS_MFMA16(F[1], hb_hi[1], acc2[1][T]);
-#define GR_U1_LOAD(F, TL, KS) F[0] = GR_LD((TL) * 6144 + (2 * (KS)) * 1024); F[1] = GR_LD((TL) * 6144 + (2 * (KS) + 1) * 1024);
-#define GR_U1_MFMA(F, TL, KS)                                             \
-    acc1[TL][0] = GS_MFMA16(F[0], in_hi[0][KS], acc1[TL][0]);             \
-    acc1[TL][1] = GS_MFMA16(F[0], in_hi[1][KS], acc1[TL][1]);             \
-    acc1[TL][0] = GS_MFMA16(F[0], in_lo[0][KS], acc1[TL][0]);             \
-    acc1[TL][1] = GS_MFMA16(F[0], in_lo[1][KS], acc1[TL][1]);             \
-    acc1[TL][0] = GS_MFMA16(F[1], in_hi[0][KS], acc1[TL][0]);             \
-    acc1[TL][1] = GS_MFMA16(F[1], in_hi[1][KS], acc1[TL][1]);
+#define GR_U2_LOAD(F, T) F[0] = GR_LD(GRC_W2_OFF + (2 * (T)) * 1024); if constexpr (!F16) F[1] = GR_LD(GRC_W2_OFF + (2 * (T) + 1) * 1024);
+#define GR_U2_MFMA(F, T)                                              \
+    acc2[0][T] = GS_MFMA16(F[0], hb_hi[0], acc2[0][T]);               \
+    acc2[1][T] = GS_MFMA16(F[0], hb_hi[1], acc2[1][T]);               \
+    if constexpr (!F16) {                                             \
+        acc2[0][T] = GS_MFMA16(F[0], hb_lo[0], acc2[0][T]);           \
+        acc2[1][T] = GS_MFMA16(F[0], hb_lo[1], acc2[1][T]);           \
+        acc2[0][T] = GS_MFMA16(F[1], hb_hi[0], acc2[0][T]);           \
+        acc2[1][T] = GS_MFMA16(F[1], hb_hi[1], acc2[1][T]);           \
+    }
+#define GR_U1_LOAD(F, TL, KS) F[0] = GR_LD((TL) * 6144 + (2 * (KS)) * 1024); if constexpr (!F16) F[1] = GR_LD((TL) * 6144 + (2 * (KS) + 1) * 1024);
     float4_t acc1[2];  // one hidden tile at a time: its ReLU + split then overlap the next tile's MFMAs
-#define GR_U1_MFMA1(F, KS)                                        \
-    acc1[0] = GS_MFMA16(F[0], in_hi[0][KS], acc1[0]);             \
-    acc1[1] = GS_MFMA16(F[0], in_hi[1][KS], acc1[1]);             \
-    acc1[0] = GS_MFMA16(F[0], in_lo[0][KS], acc1[0]);             \
-    acc1[1] = GS_MFMA16(F[0], in_lo[1][KS], acc1[1]);             \
-    acc1[0] = GS_MFMA16(F[1], in_hi[0][KS], acc1[0]);             \
-    acc1[1] = GS_MFMA16(F[1], in_hi[1][KS], acc1[1]);
+#define GR_U1_MFMA1(F, KS)                                            \
+    acc1[0] = GS_MFMA16(F[0], in_hi[0][KS], acc1[0]);                 \
+    acc1[1] = GS_MFMA16(F[0], in_hi[1][KS], acc1[1]);                 \
+    if constexpr (!F16) {                                             \
+        acc1[0] = GS_MFMA16(F[0], in_lo[0][KS], acc1[0]);             \
+        acc1[1] = GS_MFMA16(F[0], in_lo[1][KS], acc1[1]);             \
+        acc1[0] = GS_MFMA16(F[1], in_hi[0][KS], acc1[0]);             \
+        acc1[1] = GS_MFMA16(F[1], in_hi[1][KS], acc1[1]);             \
+    }
 #define GR_TAIL_LOAD(F, TL) F[0] = *reinterpret_cast<const uint4_t*>(wb + GRC_TAIL_OFF + (TL) * 512 + (lane & 31) * 16);
 #define GR_BIAS(TL) acc1[0] = *reinterpret_cast<const float4_t*>(wb + GRC_B1_OFF + (TL) * 64 + g * 16);
     // ReLU, range watch, split of hidden tile TL into its half (.xy / .zw) of the next step's B operands
@@ -609,14 +638,19 @@ __device__ __forceinline__ void gr_step(const char* wb, int lane, int g, const u
         float4_t r = SRC[nt];                                                                             \
         r.x = gs_relu(r.x); r.y = gs_relu(r.y); r.z = gs_relu(r.z); r.w = gs_relu(r.w);                   \
         if constexpr (DOT) {                                                                              \
+            if constexpr (F16) { /* the folded product's operand is rounded as the second layer's would be (u: on the host) */ \
+                vmax = __builtin_fmaxf(__builtin_fmaxf(vmax, r.x), r.y);                                  \
+                vmax = __builtin_fmaxf(__builtin_fmaxf(vmax, r.z), r.w);                                  \
+                r.x = gs_rne(r.x); r.y = gs_rne(r.y); r.z = gs_rne(r.z); r.w = gs_rne(r.w);               \
+            }                                                                                             \
             const float4 uu = *reinterpret_cast<const float4*>(u_step + 16 * (TL) + 4 * g);              \
             dot[nt] += r.x * uu.x; dot[nt] += r.y * uu.y; dot[nt] += r.z * uu.z; dot[nt] += r.w * uu.w;   \
             continue;                                                                                     \
         }                                                                                                 \
         vmax = __builtin_fmaxf(__builtin_fmaxf(vmax, r.x), r.y);                                          \
         vmax = __builtin_fmaxf(__builtin_fmaxf(vmax, r.z), r.w);                                          \
-        if ((TL) == 0) { GS_SPLIT2(r.x, r.y, hb_hi[nt].x, hb_lo[nt].x); GS_SPLIT2(r.z, r.w, hb_hi[nt].y, hb_lo[nt].y); } \
-        else { GS_SPLIT2(r.x, r.y, hb_hi[nt].z, hb_lo[nt].z); GS_SPLIT2(r.z, r.w, hb_hi[nt].w, hb_lo[nt].w); }           \
+        if ((TL) == 0) { GS_OPER2(F16, r.x, r.y, hb_hi[nt].x, hb_lo[nt].x); GS_OPER2(F16, r.z, r.w, hb_hi[nt].y, hb_lo[nt].y); } \
+        else { GS_OPER2(F16, r.x, r.y, hb_hi[nt].z, hb_lo[nt].z); GS_OPER2(F16, r.z, r.w, hb_hi[nt].w, hb_lo[nt].w); }           \
     }
     if constexpr (DO2) {  // second linear layer, K-step s-1: acc2[nt][t] += W2 frag(t) x relu(hidden) of the previous step
         GR_U2_LOAD(f0, 0)
@@ -680,7 +714,6 @@ __device__ __forceinline__ void gr_step(const char* wb, int lane, int g, const u
 #undef GR_U2_LOAD
 #undef GR_U2_MFMA
 #undef GR_U1_LOAD
-#undef GR_U1_MFMA
 }
 // The LAST step of a layer that computes its second linear layer (steps 6 and 7 of the eight-step schedule as ONE step; chunk 6 of the
 // stream carries both, GR chunks above).  Hidden tile 12 first (the half tile: hidden units 192..199), then per OUTPUT tile t the unit
@@ -689,28 +722,32 @@ __device__ __forceinline__ void gr_step(const char* wb, int lane, int g, const u
 // MLP) one unit later, under the MFMAs of the following output tiles.  Stored after the last step the tile's 102 KB of rows cost
 // 0.28 ms per launch at the ~80 B per clock of ds_write_b128 with the matrix pipe idle (measured by leaving them out), and the
 // eighth step a barrier and a fragment round trip of its own for 14 MFMAs.
-template <bool STORE>
+template <bool STORE, bool F16>
 __device__ __forceinline__ void gr_step_final(const char* wb, int lane, int g, const uint4_t (&in_hi)[2][3], const uint4_t (&in_lo)[2][3],
                                               const uint4_t (&in_tb)[2], const uint4_t (&hb_hi)[2], const uint4_t (&hb_lo)[2],
                                               float4_t (&acc2)[2][GS_T2], float& vmax, float oscale, float* rw0, float* rw1) {
     uint4_t f0[2], f1[2], pa, hp[2];
     float4_t acc1[2];
-#define GRF_U2_LOAD(F, T) F[0] = GR_LD(GRC_W2_OFF + (2 * (T)) * 1024); F[1] = GR_LD(GRC_W2_OFF + (2 * (T) + 1) * 1024);
-#define GRF_U2_MFMA(F, T)                                         \
-    acc2[0][T] = GS_MFMA16(F[0], hb_hi[0], acc2[0][T]);           \
-    acc2[1][T] = GS_MFMA16(F[0], hb_hi[1], acc2[1][T]);           \
-    acc2[0][T] = GS_MFMA16(F[0], hb_lo[0], acc2[0][T]);           \
-    acc2[1][T] = GS_MFMA16(F[0], hb_lo[1], acc2[1][T]);           \
-    acc2[0][T] = GS_MFMA16(F[1], hb_hi[0], acc2[0][T]);           \
-    acc2[1][T] = GS_MFMA16(F[1], hb_hi[1], acc2[1][T]);
-#define GRF_U1_LOAD(F, KS) F[0] = GR_LD((2 * (KS)) * 1024); F[1] = GR_LD((2 * (KS) + 1) * 1024);
-#define GRF_U1_MFMA(F, KS)                                        \
-    acc1[0] = GS_MFMA16(F[0], in_hi[0][KS], acc1[0]);             \
-    acc1[1] = GS_MFMA16(F[0], in_hi[1][KS], acc1[1]);             \
-    acc1[0] = GS_MFMA16(F[0], in_lo[0][KS], acc1[0]);             \
-    acc1[1] = GS_MFMA16(F[0], in_lo[1][KS], acc1[1]);             \
-    acc1[0] = GS_MFMA16(F[1], in_hi[0][KS], acc1[0]);             \
-    acc1[1] = GS_MFMA16(F[1], in_hi[1][KS], acc1[1]);
+#define GRF_U2_LOAD(F, T) F[0] = GR_LD(GRC_W2_OFF + (2 * (T)) * 1024); if constexpr (!F16) F[1] = GR_LD(GRC_W2_OFF + (2 * (T) + 1) * 1024);
+#define GRF_U2_MFMA(F, T)                                             \
+    acc2[0][T] = GS_MFMA16(F[0], hb_hi[0], acc2[0][T]);               \
+    acc2[1][T] = GS_MFMA16(F[0], hb_hi[1], acc2[1][T]);               \
+    if constexpr (!F16) {                                             \
+        acc2[0][T] = GS_MFMA16(F[0], hb_lo[0], acc2[0][T]);           \
+        acc2[1][T] = GS_MFMA16(F[0], hb_lo[1], acc2[1][T]);           \
+        acc2[0][T] = GS_MFMA16(F[1], hb_hi[0], acc2[0][T]);           \
+        acc2[1][T] = GS_MFMA16(F[1], hb_hi[1], acc2[1][T]);           \
+    }
+#define GRF_U1_LOAD(F, KS) F[0] = GR_LD((2 * (KS)) * 1024); if constexpr (!F16) F[1] = GR_LD((2 * (KS) + 1) * 1024);
+#define GRF_U1_MFMA(F, KS)                                            \
+    acc1[0] = GS_MFMA16(F[0], in_hi[0][KS], acc1[0]);                 \
+    acc1[1] = GS_MFMA16(F[0], in_hi[1][KS], acc1[1]);                 \
+    if constexpr (!F16) {                                             \
+        acc1[0] = GS_MFMA16(F[0], in_lo[0][KS], acc1[0]);             \
+        acc1[1] = GS_MFMA16(F[0], in_lo[1][KS], acc1[1]);             \
+        acc1[0] = GS_MFMA16(F[1], in_hi[0][KS], acc1[0]);             \
+        acc1[1] = GS_MFMA16(F[1], in_hi[1][KS], acc1[1]);             \
+    }
     // packed fragment of output tile T: tiles 0..5 in the slot of the (non-existent) hidden tile 13, tile 6 -- outputs 96..99: four real
     // rows -- as 16 lanes x 16 B behind the K-tail fragments
 #define GRF_PK_LOAD(P, T)                                                                                                          \
@@ -753,8 +790,8 @@ __device__ __forceinline__ void gr_step_final(const char* wb, int lane, int g, c
         vmax = __builtin_fmaxf(__builtin_fmaxf(vmax, r.x), r.y);
         vmax = __builtin_fmaxf(__builtin_fmaxf(vmax, r.z), r.w);
         uint32_t hx, hy, lx, ly;  // lanes g = 0 / 1 hold hidden units 192..195 / 196..199
-        GS_SPLIT2(r.x, r.y, hx, lx);
-        GS_SPLIT2(r.z, r.w, hy, ly);
+        GS_OPER2(F16, r.x, r.y, hx, lx);
+        GS_OPER2(F16, r.z, r.w, hy, ly);
         // the packed operand:  g = 0, 1: [hi, lo] (own)   g = 2, 3: [hi of lane - 32, 0]
         const uint32_t ox = __shfl(hx, lane & 31, 64), oy = __shfl(hy, lane & 31, 64);
         hp[nt] = g < 2 ? (uint4_t){hx, hy, lx, ly} : (uint4_t){ox, oy, 0u, 0u};
@@ -942,6 +979,7 @@ __device__ __forceinline__ void gr_write_column_order(uint8_t* d, int r, int row
     d[GR_DESC_PERM + wave * 32 + nt * 16 + j] = (uint8_t)r;
 }
 
+#if !GS_SINGLE_PRODUCT  // (the tile builders run ahead of either instance of the resident kernel: this translation unit only)
 __global__ __launch_bounds__(256) void gin_tile_prep_kernel(const int* __restrict__ row_ptr, const int* __restrict__ src,
                                                             const uint8_t* __restrict__ ecode, const int* __restrict__ tile_row,
                                                             uint8_t* __restrict__ desc, int n_tiles, int order, int tstride) {
@@ -973,6 +1011,7 @@ __global__ __launch_bounds__(256) void gin_tile_prep_kernel(const int* __restric
     }
     gr_write_column_order(d, r, rows, deg, order);
 }
+#endif
 
 // ---------------------------------------------------------------- the tile's descriptor straight from the caller's arrays
 // gin_tile_build_kernel = load_graph (GIN/src/load_inputs.cc:87-172) + the index part of the atom encoder (:174-220) for ONE tile of
@@ -1002,6 +1041,7 @@ __device__ __forceinline__ int gr_wave_inclusive_scan(int x, int lane) {
     return x;
 }
 
+#if !GS_SINGLE_PRODUCT
 __global__ __launch_bounds__(256) void gin_tile_build_kernel(BatchView b, const int* __restrict__ tile_row, const int* __restrict__ tile_graph,
                                                              uint8_t* __restrict__ desc, uint32_t* __restrict__ enc_idx, int n_tiles, int order,
                                                              int* __restrict__ err, const int* __restrict__ list) {
@@ -1146,6 +1186,7 @@ __global__ __launch_bounds__(256) void gin_tile_build_kernel(BatchView b, const 
     }
     gr_write_column_order(d, r, rows, r < rows ? (deg < ne ? deg : ne) : 0, order);
 }
+#endif
 
 // ---- the tile loader's atom encoder (resident kernel, ENC form): rows of h_0 computed straight into the tile's LDS rows
 // A tile's rows are encoded in GRE_PARTS parts of GRE_PART rows, one part per MLP step of the folded last layer (the rows of the
@@ -1198,7 +1239,7 @@ __device__ __forceinline__ void gr_issue_desc(const uint8_t* __restrict__ desc, 
         lds_dma16(reinterpret_cast<const char*>(desc) + (size_t)tile * GR_DESC_BYTES + wave * 1024, (uint32_t)lane * 16u, lds_addr_of(s_desc) + wave * 1024);
 }
 
-template <bool PROF, bool HUBS, bool LAST, bool FOLD, bool ENC>
+template <bool PROF, bool HUBS, bool LAST, bool FOLD, bool ENC, bool F16>
 __device__ __forceinline__ void gr_layer(unsigned long long (&tacc)[6], char* bx, char* by, float* s_h, char* s_desc, float* s_dot,
                                          const GrTile& cur, const GrTile& nxt, bool has_next, int next_tile, int l,
                                          const float* __restrict__ h0, const uint8_t* __restrict__ desc, const float* __restrict__ ecomb_all,
@@ -1506,10 +1547,10 @@ __device__ __forceinline__ void gr_layer(unsigned long long (&tacc)[6], char* bx
     for (int nt = 0; nt < NT; nt++) {
 #pragma unroll
         for (int ks = 0; ks < 3; ks++) {
-            GS_SPLIT2(bq[nt][8 * ks + 0], bq[nt][8 * ks + 1], in_hi[nt][ks].x, in_lo[nt][ks].x);
-            GS_SPLIT2(bq[nt][8 * ks + 2], bq[nt][8 * ks + 3], in_hi[nt][ks].y, in_lo[nt][ks].y);
-            GS_SPLIT2(bq[nt][8 * ks + 4], bq[nt][8 * ks + 5], in_hi[nt][ks].z, in_lo[nt][ks].z);
-            GS_SPLIT2(bq[nt][8 * ks + 6], bq[nt][8 * ks + 7], in_hi[nt][ks].w, in_lo[nt][ks].w);
+            GS_OPER2(F16, bq[nt][8 * ks + 0], bq[nt][8 * ks + 1], in_hi[nt][ks].x, in_lo[nt][ks].x);
+            GS_OPER2(F16, bq[nt][8 * ks + 2], bq[nt][8 * ks + 3], in_hi[nt][ks].y, in_lo[nt][ks].y);
+            GS_OPER2(F16, bq[nt][8 * ks + 4], bq[nt][8 * ks + 5], in_hi[nt][ks].z, in_lo[nt][ks].z);
+            GS_OPER2(F16, bq[nt][8 * ks + 6], bq[nt][8 * ks + 7], in_hi[nt][ks].w, in_lo[nt][ks].w);
         }
 #pragma unroll
         for (int k = 0; k < 24; k += 2)
@@ -1520,8 +1561,8 @@ __device__ __forceinline__ void gr_layer(unsigned long long (&tacc)[6], char* bx
             const float t0 = __shfl(bq[nt][24], j, 64), t1 = __shfl(bq[nt][24], j + 16, 64);
             const float t2 = __shfl(bq[nt][24], j + 32, 64), t3 = __shfl(bq[nt][24], j + 48, 64);
             uint32_t h01, h23, l01, l23;
-            GS_SPLIT2(t0, t1, h01, l01);
-            GS_SPLIT2(t2, t3, h23, l23);
+            GS_OPER2(F16, t0, t1, h01, l01);
+            GS_OPER2(F16, t2, t3, h23, l23);
             in_tb[nt] = g == 0 ? (uint4_t){h01, h23, l01, l23} : (g == 1 ? (uint4_t){h01, h23, 0u, 0u} : (uint4_t){0u, 0u, 0u, 0u});
         }
     }
@@ -1583,8 +1624,8 @@ __device__ __forceinline__ void gr_layer(unsigned long long (&tacc)[6], char* bx
                     }
                 }
             };
-            if (c < GS_STEPS - 2) gr_step<4>(cb, lane, g, in_hi, in_lo, in_tb, h_hi, h_lo, acc2, vmax, pend, s_u + 32 * c, dot, wave, enc_hook);
-            else gr_step<5>(cb, lane, g, in_hi, in_lo, in_tb, h_hi, h_lo, acc2, vmax, pend, s_u + 32 * c, dot, wave, enc_hook);
+            if (c < GS_STEPS - 2) gr_step<4, F16>(cb, lane, g, in_hi, in_lo, in_tb, h_hi, h_lo, acc2, vmax, pend, s_u + 32 * c, dot, wave, enc_hook);
+            else gr_step<5, F16>(cb, lane, g, in_hi, in_lo, in_tb, h_hi, h_lo, acc2, vmax, pend, s_u + 32 * c, dot, wave, enc_hook);
             if (c + 1 < GS_STEPS - 1) {
                 unsigned long long tw = 0;
                 if constexpr (PROF) tw = wall_clock64();
@@ -1616,8 +1657,8 @@ __device__ __forceinline__ void gr_layer(unsigned long long (&tacc)[6], char* bx
         // even step: compute from by while chunk c+1 streams into bx
         grc_issue_chunk(wchunks + (size_t)(c + 1) * GRC_CHUNK_STRIDE, bx, wave, lane);
         if (last && has_next) gr_issue_rows(h0, reinterpret_cast<char*>(s_h), nxt, c, wave, lane);
-        if (c == 0) gr_step<0, false, GR_DEFER>(by, lane, g, in_hi, in_lo, in_tb, h_hi, h_lo, acc2, vmax, pend, nullptr, nullptr, wave);
-        else gr_step<1, GR_DEFER, GR_DEFER>(by, lane, g, in_hi, in_lo, in_tb, h_hi, h_lo, acc2, vmax, pend, nullptr, nullptr, wave);
+        if (c == 0) gr_step<0, F16, false, GR_DEFER>(by, lane, g, in_hi, in_lo, in_tb, h_hi, h_lo, acc2, vmax, pend, nullptr, nullptr, wave);
+        else gr_step<1, F16, GR_DEFER, GR_DEFER>(by, lane, g, in_hi, in_lo, in_tb, h_hi, h_lo, acc2, vmax, pend, nullptr, nullptr, wave);
         unsigned long long tw = 0;
         if constexpr (PROF) tw = wall_clock64();
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's pieces of chunk c+1 (and of the next tile) have landed
@@ -1627,8 +1668,8 @@ __device__ __forceinline__ void gr_layer(unsigned long long (&tacc)[6], char* bx
         // odd step: compute from bx while chunk c+2 streams into by
         grc_issue_chunk(wchunks + (size_t)(c + 2) * GRC_CHUNK_STRIDE, by, wave, lane);
         if (last && has_next) gr_issue_rows(h0, reinterpret_cast<char*>(s_h), nxt, c + 1, wave, lane);
-        if (c + 1 == GR_STEPS - 2) gr_step<1, GR_DEFER, false>(bx, lane, g, in_hi, in_lo, in_tb, h_hi, h_lo, acc2, vmax, pend, nullptr, nullptr, wave);
-        else gr_step<1, GR_DEFER, GR_DEFER>(bx, lane, g, in_hi, in_lo, in_tb, h_hi, h_lo, acc2, vmax, pend, nullptr, nullptr, wave);
+        if (c + 1 == GR_STEPS - 2) gr_step<1, F16, GR_DEFER, false>(bx, lane, g, in_hi, in_lo, in_tb, h_hi, h_lo, acc2, vmax, pend, nullptr, nullptr, wave);
+        else gr_step<1, F16, GR_DEFER, GR_DEFER>(bx, lane, g, in_hi, in_lo, in_tb, h_hi, h_lo, acc2, vmax, pend, nullptr, nullptr, wave);
         if constexpr (PROF) tw = wall_clock64();
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if constexpr (PROF) { const unsigned long long t = wall_clock64(); tacc[GR_TACC_DMA] += t - tw; tw = t; }
@@ -1643,7 +1684,7 @@ __device__ __forceinline__ void gr_layer(unsigned long long (&tacc)[6], char* bx
         gr_issue_rows(h0, reinterpret_cast<char*>(s_h), nxt, GR_STEPS - 1, wave, lane);
         gr_issue_rows(h0, reinterpret_cast<char*>(s_h), nxt, GR_STEPS, wave, lane);
     }
-    gr_step_final<!last>(by, lane, g, in_hi, in_lo, in_tb, h_hi, h_lo, acc2, vmax, oscale, s_h + row[0] * GS_D, s_h + row[1] * GS_D);
+    gr_step_final<!last, F16>(by, lane, g, in_hi, in_lo, in_tb, h_hi, h_lo, acc2, vmax, oscale, s_h + row[0] * GS_D, s_h + row[1] * GS_D);
 
     }
     if constexpr (PROF) { const unsigned long long t = wall_clock64(); tacc[2] += t - tp; tp = t; }
@@ -1740,9 +1781,9 @@ __global__ __launch_bounds__(GR_WAVES * 64, 2) void gin_resident_kernel(const fl
         const GrTile nxt = gr_load_tile(tile_row, tile_graph, ntile, n_tiles, tstride);  // used five layers from now
 #pragma unroll 1
         for (int l = 0; l < 4; l++)
-            gr_layer<PROF, HUBS, false, FOLD, ENC>(tacc, s_a, s_b, s_h, s_desc, s_dot, cur, nxt, has_next, ntile, l, h0, desc, ecomb_all, wchunks_all, pool_w, hout, vmax, wave, lane, nullptr, enc_idx, enc_tab, tile_trips);
+            gr_layer<PROF, HUBS, false, FOLD, ENC, GS_F16>(tacc, s_a, s_b, s_h, s_desc, s_dot, cur, nxt, has_next, ntile, l, h0, desc, ecomb_all, wchunks_all, pool_w, hout, vmax, wave, lane, nullptr, enc_idx, enc_tab, tile_trips);
         // (every layer runs an odd number of MLP steps -- seven -- so the table buffer s_a and the first chunk's buffer s_b keep their roles)
-        gr_layer<PROF, HUBS, true, FOLD, ENC>(tacc, s_a, s_b, s_h, s_desc, s_dot, cur, nxt, has_next, ntile, 4, h0, desc, ecomb_all, wchunks_all, pool_w, hout, vmax, wave, lane, fold_head ? s_u : nullptr, enc_idx, enc_tab, tile_trips);
+        gr_layer<PROF, HUBS, true, FOLD, ENC, GS_F16>(tacc, s_a, s_b, s_h, s_desc, s_dot, cur, nxt, has_next, ntile, 4, h0, desc, ecomb_all, wchunks_all, pool_w, hout, vmax, wave, lane, fold_head ? s_u : nullptr, enc_idx, enc_tab, tile_trips);
         // readout (GIN/src/finalize.cc:36-113): out[g] = mean_v(h5[v] . w) + b, node order; the terms stay valid until the next
         // tile's last layer rewrites them, so no barrier is needed before the next tile starts
         {
@@ -1774,10 +1815,52 @@ __global__ __launch_bounds__(GR_WAVES * 64, 2) void gin_resident_kernel(const fl
 }
 
 
-#ifdef FLOWGNN_DEV
+#if defined(FLOWGNN_DEV) && !GS_SINGLE_PRODUCT
 #include "dev/gin_pp_device.inc"  // gin_pp_kernel: the ping-pong form, measured slower -- development builds only
 #endif
 
+// this translation unit's per-layer kernels (GS_F16: which instance)
+void launch_split_nt(const float* h, float* hout, const int* row_ptr, const int* src, const uint8_t* ecode, const float* ecomb,
+                     const uint8_t* chunks, int n_tot, int relu_out, int* range_flag, int nt, hipStream_t s, const float* pool_w) {
+    if (nt == 4) {  // 8 waves, 128 nodes per workgroup, 2 workgroups per CU
+        const int blocks = (int)ceil_div_ll(n_tot, 128);
+        gin_layer_split_kernel<1, 8><<<blocks, 512, 0, s>>>(h, hout, row_ptr, src, ecode, ecomb, chunks, n_tot, relu_out, range_flag, pool_w);
+        return;
+    }
+    if (nt == 2) {
+        const int blocks = (int)ceil_div_ll(n_tot, 128);
+        gin_layer_split_kernel<2, 4><<<blocks, 256, 0, s>>>(h, hout, row_ptr, src, ecode, ecomb, chunks, n_tot, relu_out, range_flag, pool_w);
+    } else {
+        const int blocks = (int)ceil_div_ll(n_tot, 64);
+        gin_layer_split_kernel<1, 4><<<blocks, 256, 0, s>>>(h, hout, row_ptr, src, ecode, ecomb, chunks, n_tot, relu_out, range_flag, pool_w);
+    }
+}
+
+// this translation unit's resident kernels (GS_F16: which instance), every PROF / HUBS / FOLD / ENC form the launcher can pick
+void gr_dispatch(bool prof, bool hubs, bool fold, bool enc, int grid, hipStream_t s, const float* h0, float* hout, const float* ecomb_all,
+                 const uint8_t* chunks_all, const float* pool_w, const float* pool_b, const int* tile_row, const int* tile_graph,
+                 const uint8_t* tile_desc, const int* node_off, float* out, int n_tiles, int* range_flag, unsigned long long* d,
+                 const float* head_u, const uint32_t* eidx, const float4* etab, int tstride, const int* list, const int* lrow) {
+#define GR_LAUNCH(P, H, F, E)                                                                                                        \
+    gin_resident_kernel<P, H, F, E><<<grid, GR_WAVES * 64, 0, s>>>(h0, hout, ecomb_all, chunks_all, pool_w, pool_b, tile_row, tile_graph, \
+                                                                   tile_desc, node_off, out, n_tiles, range_flag, d, head_u, eidx, etab, tstride, \
+                                                                   list, lrow)
+#define GR_LAUNCH_FE(P, H)                                    \
+    do {                                                      \
+        if (enc) GR_LAUNCH(P, H, true, true);                 \
+        else if (fold) GR_LAUNCH(P, H, true, false);          \
+        else GR_LAUNCH(P, H, false, false);                   \
+    } while (0)
+    if (prof) {
+        if (hubs) GR_LAUNCH_FE(true, true); else GR_LAUNCH_FE(true, false);
+    } else {
+        if (hubs) GR_LAUNCH_FE(false, true); else GR_LAUNCH_FE(false, false);
+    }
+#undef GR_LAUNCH_FE
+#undef GR_LAUNCH
+}
+
+#if !GS_SINGLE_PRODUCT
 inline float pow2_scale(const float* w, size_t n) {
     float m = 0.0f;
     for (size_t i = 0; i < n; i++) m = std::fmax(m, std::fabs(w[i]));
@@ -1785,16 +1868,42 @@ inline float pow2_scale(const float* w, size_t n) {
     return std::ldexp(1.0f, -std::ilogb(m));  // m * scale in [1, 2)
 }
 
-inline void put_split(uint8_t* frag, int lane, int e, float v) {
+// f16 = true (the single-product streams of FLOWGNN_NUMERIC_F16): hi = v rounded to nearest even, lo = 0
+inline void put_split(uint8_t* frag, int lane, int e, float v, bool f16 = false) {
     const _Float16 hi = (_Float16)v;
-    const _Float16 lo = (_Float16)(v - (float)hi);
+    const _Float16 lo = f16 ? (_Float16)0.0f : (_Float16)(v - (float)hi);
     std::memcpy(frag + lane * 16 + e * 2, &hi, 2);
     std::memcpy(frag + 1024 + lane * 16 + e * 2, &lo, 2);
 }
 
+#endif
 }  // namespace
 
-void gin_split_pack_layer(const float* w1, const float* b1, const float* w2, const float* b2, uint8_t* out) {
+#if GS_SINGLE_PRODUCT
+// the entry points of the single-product instances (called by the launchers of gin_split.hip's own translation unit)
+void launch_gin_layer_split_f16(const float* h, float* hout, const int* row_ptr, const int* src, const uint8_t* ecode, const float* ecomb,
+                                const uint8_t* chunks, int n_tot, int relu_out, int* range_flag, int nt, hipStream_t s, const float* pool_w) {
+    launch_split_nt(h, hout, row_ptr, src, ecode, ecomb, chunks, n_tot, relu_out, range_flag, nt, s, pool_w);
+}
+void gin_resident_dispatch_f16(bool prof, bool hubs, bool fold, bool enc, int grid, hipStream_t s, const float* h0, float* hout,
+                               const float* ecomb_all, const uint8_t* chunks_all, const float* pool_w, const float* pool_b, const int* tile_row,
+                               const int* tile_graph, const uint8_t* tile_desc, const int* node_off, float* out, int n_tiles, int* range_flag,
+                               unsigned long long* d, const float* head_u, const uint32_t* eidx, const float4* etab, int tstride,
+                               const int* list, const int* lrow) {
+    gr_dispatch(prof, hubs, fold, enc, grid, s, h0, hout, ecomb_all, chunks_all, pool_w, pool_b, tile_row, tile_graph, tile_desc, node_off, out,
+                n_tiles, range_flag, d, head_u, eidx, etab, tstride, list, lrow);
+}
+#else
+// (gin_split_f16.hip)
+void launch_gin_layer_split_f16(const float* h, float* hout, const int* row_ptr, const int* src, const uint8_t* ecode, const float* ecomb,
+                                const uint8_t* chunks, int n_tot, int relu_out, int* range_flag, int nt, hipStream_t s, const float* pool_w);
+void gin_resident_dispatch_f16(bool prof, bool hubs, bool fold, bool enc, int grid, hipStream_t s, const float* h0, float* hout,
+                               const float* ecomb_all, const uint8_t* chunks_all, const float* pool_w, const float* pool_b, const int* tile_row,
+                               const int* tile_graph, const uint8_t* tile_desc, const int* node_off, float* out, int n_tiles, int* range_flag,
+                               unsigned long long* d, const float* head_u, const uint32_t* eidx, const float4* etab, int tstride,
+                               const int* list, const int* lrow);
+
+void gin_split_pack_layer(const float* w1, const float* b1, const float* w2, const float* b2, uint8_t* out, bool f16) {
     std::memset(out, 0, GS_LAYER_BYTES);
     const float s1 = pow2_scale(w1, (size_t)GS_H * GS_D);
     const float s2 = pow2_scale(w2, (size_t)GS_D * GS_H);
@@ -1809,9 +1918,10 @@ void gin_split_pack_layer(const float* w1, const float* b1, const float* w2, con
                     for (int ks = 0; ks < 3; ks++)
                         for (int e = 0; e < 8; e++) {
                             const int f = 16 * (2 * ks + (e >> 2)) + 4 * gk + (e & 3);
-                            put_split(ck + (size_t)((ks * 2 + tl) * 2) * 1024, lane, e, o < GS_H ? w1[o * GS_D + f] * s1 : 0.0f);
+                            put_split(ck + (size_t)((ks * 2 + tl) * 2) * 1024, lane, e, o < GS_H ? w1[o * GS_D + f] * s1 : 0.0f, f16);
                         }
-                    const float tail = o < GS_H ? w1[o * GS_D + 96 + gk] * s1 : 0.0f;
+                    float tail = o < GS_H ? w1[o * GS_D + 96 + gk] * s1 : 0.0f;
+                    if (f16) tail = (float)(_Float16)tail;  // the fp32 tail MFMA then forms the single product exactly
                     std::memcpy(ck + GS_TAIL_OFF + tl * 256 + lane * 4, &tail, 4);
                 }
                 for (int x = 0; x < 16; x++) {
@@ -1829,7 +1939,7 @@ void gin_split_pack_layer(const float* w1, const float* b1, const float* w2, con
                     const int d = 16 * t2 + i;
                     for (int e = 0; e < 8; e++) {
                         const int k = 16 * (2 * ks + (e >> 2)) + 4 * gk + (e & 3);
-                        put_split(ck + GS_W2_OFF + (size_t)(t2 * 2) * 1024, lane, e, (d < GS_D && k < GS_H) ? w2[d * GS_H + k] * s2 : 0.0f);
+                        put_split(ck + GS_W2_OFF + (size_t)(t2 * 2) * 1024, lane, e, (d < GS_D && k < GS_H) ? w2[d * GS_H + k] * s2 : 0.0f, f16);
                     }
                 }
         } else {
@@ -1845,14 +1955,15 @@ void gin_split_pack_layer(const float* w1, const float* b1, const float* w2, con
 
 size_t gin_resident_layer_bytes() { return (size_t)GS_STEPS * GRC_CHUNK_STRIDE; }
 
-void gin_resident_head_fold(const float* w1_last, const float* w2_last, const float* b2_last, const float* pool_w, float* out) {
+void gin_resident_head_fold(const float* w1_last, const float* w2_last, const float* b2_last, const float* pool_w, float* out, bool f16) {
     // the hidden tiles the kernel holds are scaled by s1 (the first layer's weights and bias are pre-scaled by that power of two)
     const double s1 = (double)pow2_scale(w1_last, (size_t)GS_H * GS_D);
     for (int k = 0; k < 208; k++) {
         double a = 0.0;
         if (k < GS_H)
             for (int d = 0; d < GS_D; d++) a += (double)w2_last[(size_t)d * GS_H + k] * (double)pool_w[d];
-        out[k] = (float)(a / s1);
+        // f16: u rounded once, to nearest even (the operand of the folded product; a power-of-two scale commutes with the rounding)
+        out[k] = f16 ? (float)(_Float16)(a / s1) : (float)(a / s1);
     }
     double c = 0.0;
     for (int d = 0; d < GS_D; d++) c += (double)b2_last[d] * (double)pool_w[d];
@@ -1862,14 +1973,14 @@ void gin_resident_head_fold(const float* w1_last, const float* w2_last, const fl
 // merged = true (the resident kernel's stream): chunk 6 also carries the packed K-step of hidden units 192..199 -- output tiles 0..5 in
 // the W1 slot of hidden tile 13 (pure padding: 200 hidden units are 12.5 tiles), output tile 6 (rows 96..99) as 16 lanes x 16 B behind
 // the K tails -- and chunk 7 is empty: seven MLP steps (gr_step_final).  merged = false: the eight-chunk form gin_pp_pack_layer re-cuts.
-void gin_resident_pack_layer(const float* w1, const float* b1, const float* w2, const float* b2, uint8_t* out, bool merged) {
+void gin_resident_pack_layer(const float* w1, const float* b1, const float* w2, const float* b2, uint8_t* out, bool merged, bool f16) {
     std::memset(out, 0, gin_resident_layer_bytes());
     const float s1 = pow2_scale(w1, (size_t)GS_H * GS_D);
     const float s2 = pow2_scale(w2, (size_t)GS_D * GS_H);
     auto w1s = [&](int o, int f) { return (o < GS_H && f < GS_D) ? w1[o * GS_D + f] * s1 : 0.0f; };
     auto w2s = [&](int d, int k) { return (d < GS_D && k < GS_H) ? w2[d * GS_H + k] * s2 : 0.0f; };
     auto hi16 = [](float v) { return (_Float16)v; };
-    auto lo16 = [](float v) { const _Float16 h = (_Float16)v; return (_Float16)(v - (float)h); };
+    auto lo16 = [f16](float v) { const _Float16 h = (_Float16)v; return f16 ? (_Float16)0.0f : (_Float16)(v - (float)h); };
     auto put16 = [](uint8_t* p, _Float16 v) { std::memcpy(p, &v, 2); };
     for (int s = 0; s < GS_STEPS; s++) {
         uint8_t* ck = out + (size_t)s * GRC_CHUNK_STRIDE;
@@ -1883,7 +1994,7 @@ void gin_resident_pack_layer(const float* w1, const float* b1, const float* w2, 
                     for (int ks = 0; ks < 3; ks++)
                         for (int e = 0; e < 8; e++) {
                             const int f = 16 * (2 * ks + (e >> 2)) + 4 * gk + (e & 3);
-                            put_split(ck + (size_t)tl * 6144 + (size_t)(ks * 2) * 1024, lane, e, w1s(o, f));
+                            put_split(ck + (size_t)tl * 6144 + (size_t)(ks * 2) * 1024, lane, e, w1s(o, f), f16);
                         }
                     if (lane < 32) {  // K tail: g = 0 -> [w_hi(96..99), w_hi(96..99)], g = 1 -> [w_lo(96..99), 0]
                         uint8_t* tp = ck + GRC_TAIL_OFF + tl * 512 + lane * 16;
@@ -1909,7 +2020,7 @@ void gin_resident_pack_layer(const float* w1, const float* b1, const float* w2, 
                     const int d = 16 * t2 + i;
                     for (int e = 0; e < 8; e++) {
                         const int k = 16 * (2 * ks + (e >> 2)) + 4 * gk + (e & 3);
-                        put_split(ck + GRC_W2_OFF + (size_t)(t2 * 2) * 1024, lane, e, w2s(d, k));
+                        put_split(ck + GRC_W2_OFF + (size_t)(t2 * 2) * 1024, lane, e, w2s(d, k), f16);
                     }
                 }
         } else if (s == 7) {  // packed K-step: hidden units 192..199
@@ -1944,25 +2055,14 @@ void gin_resident_pack_layer(const float* w1, const float* b1, const float* w2, 
 
 void launch_gin_layer_split(const float* h, float* hout, const int* row_ptr, const int* src, const uint8_t* ecode,
                             const float* ecomb, const uint8_t* chunks, int n_tot, int e_tot, int relu_out, int* range_flag,
-                            int nt, hipStream_t s, const float* pool_w) {
-    if (nt == 4) {  // 8 waves, 128 nodes per workgroup, 2 workgroups per CU
-        const int blocks = (int)ceil_div_ll(n_tot, 128);
-        gin_layer_split_kernel<1, 8><<<blocks, 512, 0, s>>>(h, hout, row_ptr, src, ecode, ecomb, chunks, n_tot, relu_out, range_flag, pool_w);
-        return;
-    }
-    if (nt == 2) {
-        const int blocks = (int)ceil_div_ll(n_tot, 128);
-        gin_layer_split_kernel<2, 4><<<blocks, 256, 0, s>>>(h, hout, row_ptr, src, ecode, ecomb, chunks, n_tot, relu_out, range_flag, pool_w);
-    } else {
-        const int blocks = (int)ceil_div_ll(n_tot, 64);
-        gin_layer_split_kernel<1, 4><<<blocks, 256, 0, s>>>(h, hout, row_ptr, src, ecode, ecomb, chunks, n_tot, relu_out, range_flag, pool_w);
-    }
+                            int nt, hipStream_t s, const float* pool_w, bool f16) {
+    (f16 ? launch_gin_layer_split_f16 : launch_split_nt)(h, hout, row_ptr, src, ecode, ecomb, chunks, n_tot, relu_out, range_flag, nt, s, pool_w);
 }
 
 void launch_gin_resident(const float* h0, float* hout, const int* row_ptr, const int* src, const uint8_t* ecode, const float* ecomb_all,
                          const uint8_t* chunks_all, const float* pool_w, const float* pool_b, const int* tile_row, const int* tile_graph,
                          uint8_t* tile_desc, const int* node_off, float* out, int n_tiles, int* range_flag, hipStream_t s, bool hubs,
-                         const float* head_u, int col_order, bool prof, const GinTileBuild* tb, int tstride) {
+                         const float* head_u, int col_order, bool prof, const GinTileBuild* tb, int tstride, bool f16) {
     if (n_tiles <= 0) return;
     const int order = hubs ? 3 : col_order;
     const bool fold = head_u != nullptr && out != nullptr && hout == nullptr;  // single-task readout, no per-node tap
@@ -1977,23 +2077,9 @@ void launch_gin_resident(const float* h0, float* hout, const int* row_ptr, const
     }
     const uint32_t* eidx = enc ? reinterpret_cast<const uint32_t*>(tb->enc_idx) : nullptr;
     const float4* etab = enc ? reinterpret_cast<const float4*>(tb->enc_tab) : nullptr;
-#define GR_LAUNCH(P, H, F, E)                                                                                                        \
-    gin_resident_kernel<P, H, F, E><<<grid, GR_WAVES * 64, 0, s>>>(h0, hout, ecomb_all, chunks_all, pool_w, pool_b, tile_row, tile_graph, \
-                                                                   tile_desc, node_off, out, n_tiles, range_flag, d, head_u, eidx, etab, tstride, \
-                                                                   enc ? tb->list : nullptr, enc ? tb->lrow : nullptr)
-#define GR_LAUNCH_FE(P, H)                                    \
-    do {                                                      \
-        if (enc) GR_LAUNCH(P, H, true, true);                 \
-        else if (fold) GR_LAUNCH(P, H, true, false);          \
-        else GR_LAUNCH(P, H, false, false);                   \
-    } while (0)
-    if (prof) {
-        if (hubs) GR_LAUNCH_FE(true, true); else GR_LAUNCH_FE(true, false);
-    } else {
-        if (hubs) GR_LAUNCH_FE(false, true); else GR_LAUNCH_FE(false, false);
-    }
-#undef GR_LAUNCH_FE
-#undef GR_LAUNCH
+    (f16 ? gin_resident_dispatch_f16 : gr_dispatch)(prof, hubs, fold, enc, grid, s, h0, hout, ecomb_all, chunks_all, pool_w, pool_b, tile_row,
+                                                    tile_graph, tile_desc, node_off, out, n_tiles, range_flag, d, head_u, eidx, etab, tstride,
+                                                    enc ? tb->list : nullptr, enc ? tb->lrow : nullptr);
     if (prof) {
         std::vector<unsigned long long> hbuf(cnt);
         (void)hipStreamSynchronize(s);
@@ -2064,5 +2150,7 @@ void gin_resident_pack_enc_table(const float* nemb /* [173][100] */, float* out)
                     for (int d = 0; d < GS_D; d++)
                         out[(size_t)(GRB_T5678 + ((f5 * 6 + f6) * 2 + f7) * 2 + f8) * GS_D + d] = ((E(5, f5, d) + E(6, f6, d)) + E(7, f7, d)) + E(8, f8, d);
 }
+
+#endif  // GS_SINGLE_PRODUCT
 
 }  // namespace fg

@@ -2,7 +2,7 @@
 // OpenCL host (GIN/src/host.cc): load the model's .bin weights, read a graph pack in the reference's on-disk
 // layout, run the whole dataset as ONE batched launch NUM_TRIALS times, write HLS_output.txt.
 //
-//   host <MODEL> [--graphs DIR] [--weights DIR] [--num-graphs N] [--trials T] [--out FILE] [--device D | --devices D0,D1,..] [--option key=value] [--numeric f32|q6.10] [XCLBIN]
+//   host <MODEL> [--graphs DIR] [--weights DIR] [--num-graphs N] [--trials T] [--out FILE] [--device D | --devices D0,D1,..] [--option key=value] [--numeric f32|q6.10|f16] [XCLBIN]
 //
 //   MODEL        GIN | GIN-VN | GCN | GAT | PNA | DGN
 //   --graphs     directory holding graph_info/ and graph_bin/      (default ../graphs, host.cc:14-15)
@@ -76,7 +76,7 @@ static bool read_eig_txt(const std::string& path, std::vector<float>& eig, size_
 int main(int argc, char** argv) {
     if (argc < 2) {
         fprintf(stderr, "Usage: %s <GIN|GIN-VN|GCN|GAT|PNA|DGN> [--graphs DIR] [--weights DIR] [--num-graphs N] [--trials T] "
-                        "[--out FILE] [--device D | --devices D0,D1,..] [--option key=value] [--numeric f32|q6.10] [--num-tasks T] [XCLBIN File]\n", argv[0]);
+                        "[--out FILE] [--device D | --devices D0,D1,..] [--option key=value] [--numeric f32|q6.10|f16] [--num-tasks T] [XCLBIN File]\n", argv[0]);
         return EXIT_FAILURE;
     }
     const std::string model = argv[1];
@@ -115,7 +115,10 @@ int main(int argc, char** argv) {
             options.emplace_back(kv.substr(0, eq), atof(kv.c_str() + eq + 1));
         }
         else if (a == "--num-tasks") num_tasks = atoi(next("--num-tasks"));  // NUM_TASK of the readout (GIN/src/dcl.h:25), GIN / GIN-VN / GCN
-        else if (a == "--numeric") numeric = std::string(next("--numeric")) == "q6.10" ? FLOWGNN_NUMERIC_Q6_10 : FLOWGNN_NUMERIC_F32;
+        else if (a == "--numeric") {
+            const std::string m = next("--numeric");
+            numeric = m == "q6.10" ? FLOWGNN_NUMERIC_Q6_10 : m == "f16" ? FLOWGNN_NUMERIC_F16 : FLOWGNN_NUMERIC_F32;
+        }
         // anything else (e.g. an .xclbin path) is ignored
     }
     if (num_graphs < 0) num_graphs = read_count_file(graphs + "/dataset_size.txt");
@@ -137,7 +140,7 @@ int main(int argc, char** argv) {
     }
     rc = flowgnn_group_load_weights_dir(eng, wdir.c_str());
     if (rc) { fprintf(stderr, "loading weights failed: %d %s\n", rc, flowgnn_group_last_error(eng)); return EXIT_FAILURE; }
-    if (numeric != FLOWGNN_NUMERIC_F32) {  // the reference's ap_fixed<16,6> bit patterns (GIN / GIN-VN)
+    if (numeric != FLOWGNN_NUMERIC_F32) {  // the reference's ap_fixed<16,6> bit patterns, or f16 MLP operands (GIN / GIN-VN)
         rc = flowgnn_group_set_numeric_mode(eng, numeric);
         if (rc) { fprintf(stderr, "numeric mode: %d %s\n", rc, flowgnn_group_last_error(eng)); return EXIT_FAILURE; }
     }

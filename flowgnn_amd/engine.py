@@ -15,6 +15,10 @@ from . import _lib
 from .graphpack import GraphBatch
 
 
+# flowgnn_set_numeric_mode codes (flowgnn.h: FLOWGNN_NUMERIC_F32 / _Q6_10 / _F16)
+NUMERIC_MODES = {"f32": 0, "q6.10": 1, "f16": 2}
+
+
 class FlowGNNError(RuntimeError):
     def __init__(self, code: int, where: str, detail: str = ""):
         self.code = code
@@ -268,8 +272,9 @@ class Engine:
 
     # ---- taps
     def set_numeric_mode(self, mode: str = "f32"):
-        """"f32" (default) or "q6.10": the bit patterns of the reference's own fixed-point format (ap_fixed<16,6>; DGN: ap_fixed<16,3>)."""
-        code = {"f32": 0, "q6.10": 1}[mode]
+        """"f32" (default), "q6.10": the bit patterns of the reference's own fixed-point format (ap_fixed<16,6>; DGN: ap_fixed<16,3>),
+        or "f16" (GIN / GIN-VN): MLP operands rounded to f16, fp32 accumulation (flowgnn.h: FLOWGNN_NUMERIC_F16)."""
+        code = NUMERIC_MODES[mode]
         self._check(self.lib.flowgnn_set_numeric_mode(self._h, code), "flowgnn_set_numeric_mode")
 
     def exact_reruns(self) -> int:
@@ -378,7 +383,7 @@ class EngineGroup:
         self.num_tasks = int(num_tasks)
 
     def set_numeric_mode(self, mode: str = "f32"):
-        self._check(self.lib.flowgnn_group_set_numeric_mode(self._h, {"f32": 0, "q6.10": 1}[mode]), "flowgnn_group_set_numeric_mode")
+        self._check(self.lib.flowgnn_group_set_numeric_mode(self._h, NUMERIC_MODES[mode]), "flowgnn_group_set_numeric_mode")
 
     def set_batch(self, batch: GraphBatch):
         nn, ne = _i32(batch.nums_of_nodes), _i32(batch.nums_of_edges)

@@ -372,6 +372,27 @@ int flowgnn_num_tasks(const flowgnn_engine* e);
  */
 #define FLOWGNN_NUMERIC_F32 0
 #define FLOWGNN_NUMERIC_Q6_10 1
+/*
+ * FLOWGNN_NUMERIC_F16 (GIN and GIN-VN only, NUM_TASK 1 or more; every other model returns FLOWGNN_ERR_UNSUPPORTED): the
+ * 16-bit operand speed of the matrix pipe.  Every operand of the node MLP's two linear layers -- the weights and the
+ * activation each of them multiplies -- is rounded to f16 (round to nearest even), and each product is ONE f16 x f16 MFMA
+ * with fp32 accumulation (the default mode forms every product from three).  The weights are rounded after the exact
+ * power-of-two scale the kernels apply per matrix: the same values as rounding the weights themselves unless an entry
+ * falls below the f16 normal range (6.1e-5 times the matrix's largest entry).  fp32 as in the default mode: the atom
+ * encoder, the in-edge walk and its sums, biases, BatchNorm (folded into the weights as in the default mode), the ReLUs,
+ * the mean pool and the readout's dot product.  Where the readout rounds:
+ *   - single-task, graph-resident path (the default for molecule-sized graphs): the readout is folded through the last
+ *     layer's second linear layer, logit = mean_v(f16(hidden_v) . f16(u)) + b2 . w_pred + b, with u = W2^T w_pred
+ *     rounded to f16 once;
+ *   - every other path (NUM_TASK > 1, the per-layer kernels of option gin_resident 0 and of batches the resident kernel
+ *     does not take, flowgnn_get_h taps): h_5 = W2 f16(hidden) + b2 with f16(W2), then the fp32 readout of h_5.
+ * Range fallback as in the default mode: an MLP operand beyond the f16 range (|x| > 6e4) raises the range flag and the
+ * forward pass is repeated on the fp32 kernels -- that batch's results are then f32-mode results (flowgnn_exact_reruns
+ * counts it).  Options that select non-split kernels (gin_mfma 32, gin_unfused 1) give f32-mode results in this mode.
+ * Within one path results are bit-identical under batch order, slices and group cuts, as in the default mode.  The
+ * reference-compatible <M>_compute_graphs entry points keep the default mode.  Switch before or after setting weights.
+ */
+#define FLOWGNN_NUMERIC_F16 2
 int flowgnn_set_numeric_mode(flowgnn_engine* e, int mode);
 
 /*
