@@ -273,6 +273,37 @@ __global__ __launch_bounds__(256) void mean_pool_linear_mt_kernel(const float* _
     }
 }
 
+// ---------------------------------------------------------------- graph embeddings: mean pool of the readout's rows, no head
+// emb[g][:] = (sum of rows[v][:] over the nodes of graph g, in node order) / n_g  (flowgnn_set_embeddings).  One wavefront per
+// graph; lane c < D / 4 owns the float4 chunk c of the row, so a row is one coalesced request and every column is a single chain of
+// adds in node order: the sum depends on the graph alone.  Four rows are in flight before the first is added.
+template <int D>
+__global__ __launch_bounds__(256) void mean_pool_rows_kernel(const float* __restrict__ rows, const int* __restrict__ node_off,
+                                                             float* __restrict__ emb, int num_graphs) {
+    constexpr int C = D / 4;
+    static_assert(D % 4 == 0 && C <= 64, "a row must fit one wavefront in float4 chunks");
+    const int lane = threadIdx.x & 63;
+    const int g = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (g >= num_graphs || lane >= C) return;
+    const int n0 = node_off[g], n1 = node_off[g + 1];
+    const float4* r = reinterpret_cast<const float4*>(rows);
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    int v = n0;
+    for (; v + 3 < n1; v += 4) {
+        float4 x[4];
+#pragma unroll
+        for (int i = 0; i < 4; i++) x[i] = r[(size_t)(v + i) * C + lane];
+#pragma unroll
+        for (int i = 0; i < 4; i++) { acc.x += x[i].x; acc.y += x[i].y; acc.z += x[i].z; acc.w += x[i].w; }
+    }
+    for (; v < n1; v++) {
+        const float4 x = r[(size_t)v * C + lane];
+        acc.x += x.x; acc.y += x.y; acc.z += x.z; acc.w += x.w;
+    }
+    const float n = (float)(n1 - n0);
+    reinterpret_cast<float4*>(emb + (size_t)g * D)[lane] = make_float4(acc.x / n, acc.y / n, acc.z / n, acc.w / n);
+}
+
 static inline int grid_for(long long items, int per_block, int cap) {
     long long nb = (items + per_block - 1) / per_block;
     if (nb > cap) nb = cap;
@@ -282,12 +313,14 @@ static inline int grid_for(long long items, int per_block, int cap) {
 
 
 // ---------------------------------------------------------------- readout: mean pool + 3-layer head, one wavefront per graph (PNA D=80, DGN D=100 share it)
-template <int D, int H1, int H2>
+// EMB (flowgnn_set_embeddings): the instance that also stores the pooled row to emb[g].
+template <int D, int H1, int H2, bool EMB = false>
 __global__ __launch_bounds__(256) void pool_mlp3_kernel(const float* __restrict__ h, const int* __restrict__ node_off,
                                                          const float* __restrict__ w1, const float* __restrict__ b1,
                                                          const float* __restrict__ w2, const float* __restrict__ b2,
                                                          const float* __restrict__ w3, const float* __restrict__ b3,
-                                                         float* __restrict__ out, int num_graphs) {
+                                                         float* __restrict__ out, int num_graphs,
+                                                         float* __restrict__ emb = nullptr /* [G][D] pooled rows (EMB instance) */) {
     constexpr int C = D / 4;
     static_assert(C <= 32 && H1 <= 64 && H2 <= 64, "sizes must fit one wavefront");
     __shared__ float s_hg[4][D];
@@ -307,6 +340,9 @@ __global__ __launch_bounds__(256) void pool_mlp3_kernel(const float* __restrict_
         s_hg[wv][4 * c + 2] = acc.z / n; s_hg[wv][4 * c + 3] = acc.w / n;
     }
     __builtin_amdgcn_wave_barrier();
+    if constexpr (EMB) {
+        if (lane < C) reinterpret_cast<float4*>(emb + (size_t)g * D)[lane] = make_float4(s_hg[wv][4 * lane], s_hg[wv][4 * lane + 1], s_hg[wv][4 * lane + 2], s_hg[wv][4 * lane + 3]);
+    }
     if (lane < H1) {
         float s = b1[lane];
         for (int i = 0; i < D; i++) s = __builtin_fmaf(s_hg[wv][i], w1[lane * D + i], s);  // (spelled out: the resident kernels' heads round alike)

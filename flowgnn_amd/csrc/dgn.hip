@@ -20,6 +20,17 @@
 #include <cstring>
 
 namespace fg {
+// dgn_emb.hip compiles this file once more with FG_RESIDENT_EMB_TU defined, for ONE kernel: dgn_resident_kernel under the name
+// dgn_resident_emb_kernel, the instance that also stores every graph's pooled row (flowgnn_set_embeddings).  A second instance in
+// this translation unit or a pointer tested at run time both cost the default kernel registers (and 0.4 - 1.7 % of its time); this way
+// the default kernel is the code it was.  In that translation unit the host side is left out and the other kernels, with internal linkage and unused, are dropped.
+void launch_dgn_resident_emb(const void* resident_args, int grid, hipStream_t s);  // dgn_emb.hip
+#ifdef FG_RESIDENT_EMB_TU
+namespace {
+constexpr bool RESIDENT_EMB = true;
+#else
+constexpr bool RESIDENT_EMB = false;
+#endif
 
 constexpr int DGN_D = 100;
 constexpr int DGN_L = 4;
@@ -983,12 +994,14 @@ __device__ __forceinline__ float dgn_head_wave(const float* s_hg, float* s_o1, c
 // in [unit][input] order every lane of a step touches another cache line, and the head then costs more than the pooling it follows.
 // PARTS false: the pooled row from the rows of h themselves (even rows | odd rows, then the two halves: pool_mlp3_kernel's order, which
 // is also the graph-resident kernel's) -- the readout of the per-layer path when the last layer's rows are kept.
-template <bool PARTS>
+// EMB (flowgnn_set_embeddings): the instances that also store the pooled row to emb[g].
+template <bool PARTS, bool EMB = false>
 __global__ __launch_bounds__(256) void dgn_pool_part_mlp3_kernel(const float* __restrict__ part /* [G][8][100], or h [N][100] */, const int* __restrict__ cnt,
                                                                  const int* __restrict__ node_off, const float* __restrict__ w1,
                                                                  const float* __restrict__ b1, const float* __restrict__ w2,
                                                                  const float* __restrict__ b2, const float* __restrict__ w3,
-                                                                 const float* __restrict__ b3, float* __restrict__ out, int num_graphs) {
+                                                                 const float* __restrict__ b3, float* __restrict__ out, int num_graphs,
+                                                                 float* __restrict__ emb = nullptr /* [G][100] pooled rows (EMB instances) */) {
     constexpr int D = DGN_D, H1 = 50, H2 = 25, P1 = H1 + 1, P2 = H2 + 2;
     __shared__ float s_w1t[D * P1];   // [input][unit]
     __shared__ float s_w2t[H1 * P2];  // [input][unit]
@@ -1021,6 +1034,9 @@ __global__ __launch_bounds__(256) void dgn_pool_part_mlp3_kernel(const float* __
             }
         }
         __builtin_amdgcn_wave_barrier();
+        if constexpr (EMB) {
+            if (lane < DGN_C) reinterpret_cast<float4*>(emb + (size_t)gph * D)[lane] = *reinterpret_cast<const float4*>(&s_hg[wv][4 * lane]);
+        }
         const float p = dgn_head_wave(s_hg[wv], s_o1[wv], s_w1t, P1, s_w2t, P2, bias1, bias2, w3l, lane);
         if (lane == 0) out[gph] = bias3 + p;
         __builtin_amdgcn_wave_barrier();  // s_hg / s_o1 are rewritten for the wave's next graph
@@ -1070,6 +1086,7 @@ struct DgnResidentArgs {
     BatchView b;              // node counts for the readout; the edge list for rows with duplicate in-edges
     const float* head;        // DGN_HEAD_BYTES: w1 [100][50] and w2 [50][25] transposed ([in][out]: unit along the lanes), b1, b2, w3, b3
     float* out;               // [G]
+    float* emb;               // [G][100]: the pooled rows the head reads (flowgnn_set_embeddings), or null
     int* range_flag;
     int n_tiles;
 };
@@ -1434,6 +1451,9 @@ __global__ __launch_bounds__(512, 2) void dgn_resident_kernel(const DgnResidentA
                     s_hg[4 * c + 2] = sum.z / n; s_hg[4 * c + 3] = sum.w / n;
                 }
                 __builtin_amdgcn_wave_barrier();
+                if constexpr (RESIDENT_EMB) {  // the pooled row the head is about to read, as it stands in LDS: 25 lanes, one float4 each
+                    if (lane < DGN_C) reinterpret_cast<float4*>(a.emb + (size_t)gph * DGN_D)[lane] = *reinterpret_cast<const float4*>(s_hg + 4 * lane);
+                }
                 return gph;
             };
             auto head = [&](int gi) {
@@ -1462,6 +1482,7 @@ __global__ __launch_bounds__(512, 2) void dgn_resident_kernel(const DgnResidentA
 }
 
 // host: W [100][2][100] (out, block, in), b [100] -> DGN_FT_LAYER_BYTES in the feature-major K order of dgn_layer_fused_kernel
+#ifndef FG_RESIDENT_EMB_TU  // (host side: the model's own translation unit only)
 static void dgn_pack_fused_layer(const float* W, const float* b, uint8_t* out) {
     std::memset(out, 0, DGN_FT_LAYER_BYTES);
     float m = 0.0f;
@@ -1673,12 +1694,13 @@ public:
         a.tile_row = t_row; a.tile_graph = t_graph; a.list = t_list;
         a.b = db.b;
         a.head = d_head_;
-        a.out = db.out; a.range_flag = db.range_flag;
+        a.out = db.out; a.emb = db.emb; a.range_flag = db.range_flag;
         a.n_tiles = n_tiles;
         const int grid = n_tiles < 256 ? n_tiles : 256;  // persistent: one 8-wave workgroup per CU (157 KB of LDS)
         {
             ProfScope p(prof, "dgn_resident", s);
-            dgn_resident_kernel<<<grid, 512, 0, s>>>(a);
+            if (a.emb) launch_dgn_resident_emb(&a, grid, s);  // the same kernel's storing instance (dgn_emb.hip)
+            else dgn_resident_kernel<<<grid, 512, 0, s>>>(a);
         }
         db.final_h = 0;
         db.h_valid = false;  // no per-node tensor leaves the kernel: flowgnn_get_h repeats the pass on the per-layer kernels
@@ -1777,7 +1799,13 @@ public:
         db.h_valid = !pooled;  // pooled: h[cur] was never written; flowgnn_get_h repeats the pass with the rows kept
         {
             ProfScope p(prof, "pool_mlp3", s);
-            if (pooled)
+            if (pooled && db.emb)
+                dgn_pool_part_mlp3_kernel<true, true><<<grid_for(db.b.num_graphs, 4, 256 * 4), 256, 0, s>>>(pool_part_.p, pool_cnt_.p, db.b.node_off, d_w0_, d_b0_, d_w1_,
+                                                                                                d_b1_, d_w2_, d_b2_, db.out, db.b.num_graphs, db.emb);
+            else if (db.emb)
+                dgn_pool_part_mlp3_kernel<false, true><<<grid_for(db.b.num_graphs, 4, 256 * 4), 256, 0, s>>>(db.h[cur], nullptr, db.b.node_off, d_w0_, d_b0_, d_w1_,
+                                                                                                 d_b1_, d_w2_, d_b2_, db.out, db.b.num_graphs, db.emb);
+            else if (pooled)
                 dgn_pool_part_mlp3_kernel<true><<<grid_for(db.b.num_graphs, 4, 256 * 4), 256, 0, s>>>(pool_part_.p, pool_cnt_.p, db.b.node_off, d_w0_, d_b0_, d_w1_,
                                                                                           d_b1_, d_w2_, d_b2_, db.out, db.b.num_graphs);
             else
@@ -1863,5 +1891,13 @@ private:
 };
 
 Model* make_dgn_model() { return new DgnModel(); }
+#endif  // FG_RESIDENT_EMB_TU
+
+#ifdef FG_RESIDENT_EMB_TU
+}  // namespace
+void launch_dgn_resident_emb(const void* resident_args, int grid, hipStream_t s) {
+    dgn_resident_kernel<<<grid, 512, 0, s>>>(*static_cast<const DgnResidentArgs*>(resident_args));
+}
+#endif
 
 }  // namespace fg

@@ -292,6 +292,15 @@ struct flowgnn_engine {
     bool has_attr = false, has_eig = false;
     DeviceBatch db{};
 
+    // graph embeddings (flowgnn_set_embeddings): off by default; db.emb is null then and every forward is the one it was
+    bool emb_on = false;
+    int numeric_mode = FLOWGNN_NUMERIC_F32;
+    float* d_emb = nullptr;         // the engine's own [G][dim] buffer (allocated when first needed, grows only)
+    size_t cap_emb = 0;             // floats
+    float* emb_user = nullptr;      // flowgnn_set_embeddings_buffer (reset by set_batch)
+    float* emb_last = nullptr;      // where the last flowgnn_run put them (null: it ran with embeddings off)
+    float* emb_target() const { return emb_on ? (emb_user ? emb_user : d_emb) : nullptr; }
+
     // hipGraph replay of the launch sequence (index build + forward), opt-in (FLOWGNN_HIPGRAPH=1; 2 = batches of any size).
     // Measured on this runtime it does not pay: asynchronous launches already pipeline, and a replay of the dozen kernels
     // of a step is 1-4 % SLOWER than launching them (4 113 molhiv graphs: 0.267 ms plain, 0.271 ms replayed; 512 graphs:
@@ -381,7 +390,34 @@ static void ensure_csr(flowgnn_engine* e) {
     e->db.csr_built = true;
 }
 
+// embeddings on: the engine's own buffer holds the resident batch's [G][dim]; db.emb follows the switch and the caller's buffer
+static int place_embeddings(flowgnn_engine* e) {
+    if (e->emb_on && e->batch_ready && !e->emb_user) {
+        const size_t need = (size_t)e->G * (size_t)flowgnn_embedding_dim(e->model_id);
+        if (need > e->cap_emb || !e->d_emb) {
+            if (e->stream) EHIP_TRY(e, hipStreamSynchronize(e->stream));  // (a run in flight may still write the old one)
+            if (e->emb_last == e->d_emb) e->emb_last = nullptr;
+            if (e->d_emb) (void)hipFree(e->d_emb);
+            e->d_emb = nullptr;
+            e->cap_emb = 0;
+            EHIP_TRY(e, hipMalloc((void**)&e->d_emb, sizeof(float) * (need ? need : 1)));
+            e->cap_emb = need;
+        }
+    }
+    e->db.emb = e->batch_ready ? e->emb_target() : nullptr;
+    return FLOWGNN_OK;
+}
+
 extern "C" {
+
+int flowgnn_embedding_dim(int model) {
+    switch (model) {
+        case FLOWGNN_MODEL_GIN: case FLOWGNN_MODEL_GIN_VN: case FLOWGNN_MODEL_GCN: case FLOWGNN_MODEL_DGN: return 100;
+        case FLOWGNN_MODEL_GAT: return 16;
+        case FLOWGNN_MODEL_PNA: return 80;
+        default: return -1;
+    }
+}
 
 int flowgnn_create(int model, int device_id, flowgnn_engine** out) {
     if (!out) return FLOWGNN_ERR_ARG;
@@ -437,6 +473,7 @@ int flowgnn_destroy(flowgnn_engine* e) {
     if (e->stream) (void)hipStreamSynchronize(e->stream);
     e->drop_graph();
     e->free_batch();
+    if (e->d_emb) (void)hipFree(e->d_emb);
     if (e->d_err) (void)hipFree(e->d_err);
     delete e->model;
     if (e->own_stream) (void)hipStreamDestroy(e->own_stream);
@@ -952,7 +989,9 @@ static int set_batch_state(flowgnn_engine* e, int num_graphs, const int* nums_of
     e->db.range_flag = e->d_err + 1;
     e->force_exact = false;
     e->batch_ready = true;
-    return FLOWGNN_OK;
+    e->emb_user = nullptr;
+    e->emb_last = nullptr;
+    return place_embeddings(e);
 }
 
 // flowgnn_set_batch (and the group's ranges): host arrays
@@ -1069,6 +1108,7 @@ int flowgnn_run(flowgnn_engine* e) {
         return FLOWGNN_ERR_STATE;
     }
     ENGINE_TRY(e, use_device(e));
+    e->emb_last = e->db.emb;
     if (e->G == 0) { e->ran = true; return FLOWGNN_OK; }
     const bool want_graph = e->graph_mode != 0 && !e->prof.enabled && (e->graph_mode > 1 || e->N <= (1ll << 20));
     if (want_graph && e->graph_ok) {
@@ -1163,7 +1203,13 @@ int flowgnn_sync(flowgnn_engine* e) {
         e->drop_graph();  // the captured launches are the split-f16 ones
         EHIP_TRY(e, hipMemsetAsync(e->d_err + 1, 0, sizeof(int), e->stream));
         e->model->set_exact(true);
-        ENGINE_TRY(e, engine_forward(e));
+        {   // the repeated pass refills what the run filled: the logits, and the embeddings where that run had them on
+            float* const now = e->db.emb;
+            e->db.emb = e->emb_last;
+            const int frc = engine_forward(e);
+            e->db.emb = now;
+            ENGINE_TRY(e, frc);
+        }
         he = hipStreamSynchronize(e->stream);
         if (he != hipSuccess) {
             set_hip_error("hipStreamSynchronize (exact re-run)", he, __FILE__, __LINE__);
@@ -1220,6 +1266,64 @@ int flowgnn_set_results_buffer(flowgnn_engine* e, void* device_ptr) {
     return FLOWGNN_OK;
 }
 
+int flowgnn_set_embeddings(flowgnn_engine* e, int on) {
+    if (!e) return FLOWGNN_ERR_ARG;
+    if (on && e->numeric_mode == FLOWGNN_NUMERIC_Q6_10) {
+        e->err = "flowgnn_set_embeddings: there are no fixed-point embeddings (FLOWGNN_NUMERIC_Q6_10)";
+        return FLOWGNN_ERR_UNSUPPORTED;
+    }
+    ENGINE_TRY(e, use_device(e));
+    e->drop_graph();  // a recorded launch sequence is that of the other setting
+    e->emb_on = on != 0;
+    return place_embeddings(e);
+}
+
+int flowgnn_get_embeddings(flowgnn_engine* e, float* out_host) {
+    if (!e || (!out_host && e->G > 0)) return FLOWGNN_ERR_ARG;
+    if (!e->ran || (!e->emb_last && e->G > 0) || (e->G == 0 && !e->emb_on)) {
+        e->err = "flowgnn_get_embeddings: the last flowgnn_run did not have embeddings on (flowgnn_set_embeddings)";
+        return FLOWGNN_ERR_STATE;
+    }
+    int rc = flowgnn_sync(e);
+    if (rc) return rc;
+    if (e->G > 0) {
+        const size_t bytes = sizeof(float) * (size_t)e->G * (size_t)flowgnn_embedding_dim(e->model_id);
+        hipError_t he;
+        if (e->copy_stream) {
+            he = hipMemcpyAsync(out_host, e->emb_last, bytes, hipMemcpyDeviceToHost, e->copy_stream);
+            if (he == hipSuccess) he = hipStreamSynchronize(e->copy_stream);
+        } else {
+            he = hipMemcpy(out_host, e->emb_last, bytes, hipMemcpyDeviceToHost);
+        }
+        if (he != hipSuccess) {
+            set_hip_error("copy embeddings", he, __FILE__, __LINE__);
+            e->err = fg::last_error_text();
+            return FLOWGNN_ERR_HIP;
+        }
+    }
+    return FLOWGNN_OK;
+}
+
+int flowgnn_embeddings_device(flowgnn_engine* e, void** d_emb) {
+    if (!e || !d_emb) return FLOWGNN_ERR_ARG;
+    if (!e->ran || !e->emb_last) {
+        e->err = "flowgnn_embeddings_device: the last flowgnn_run did not have embeddings on (flowgnn_set_embeddings)";
+        return FLOWGNN_ERR_STATE;
+    }
+    *d_emb = e->emb_last;
+    return FLOWGNN_OK;
+}
+
+int flowgnn_set_embeddings_buffer(flowgnn_engine* e, void* device_ptr) {
+    if (!e) return FLOWGNN_ERR_ARG;
+    if (!e->batch_ready) return FLOWGNN_ERR_STATE;
+    // as flowgnn_set_results_buffer: no device synchronisation, the pointer matters to the launches enqueued after this call
+    ENGINE_TRY(e, use_device(e));
+    if (e->gexec) e->drop_graph();
+    e->emb_user = (float*)device_ptr;
+    return place_embeddings(e);
+}
+
 int flowgnn_stream(flowgnn_engine* e, void** stream) {
     if (!e || !stream) return FLOWGNN_ERR_ARG;
     *stream = (void*)e->stream;
@@ -1272,8 +1376,13 @@ int flowgnn_num_tasks(const flowgnn_engine* e) { return e ? e->num_tasks : -1; }
 
 int flowgnn_set_numeric_mode(flowgnn_engine* e, int mode) {
     if (!e) return FLOWGNN_ERR_ARG;
+    if (mode == FLOWGNN_NUMERIC_Q6_10 && e->emb_on) {
+        e->err = "flowgnn_set_numeric_mode: graph embeddings are on, and there are no fixed-point embeddings";
+        return FLOWGNN_ERR_UNSUPPORTED;
+    }
     e->drop_graph();
     const int rc = e->model->set_numeric_mode(mode);
+    if (!rc) e->numeric_mode = mode;
     if (rc) e->err = "flowgnn_set_numeric_mode: unknown mode, a mode this model does not have (f16: GIN / GIN-VN only), or the fixed-point "
                      "readout is single-task and NUM_TASK != 1";
     return rc;
@@ -1328,7 +1437,10 @@ static int ensure_rows(flowgnn_engine* e) {
     if (e->db.h_valid || e->db.tap) return FLOWGNN_OK;
     e->model->set_keep_h(true);
     e->model->set_exact(e->force_exact);
+    float* const emb = e->db.emb;
+    e->db.emb = nullptr;  // a tap's pass leaves the run's embeddings as they are
     rc = engine_forward(e);
+    e->db.emb = emb;
     e->model->set_keep_h(false);
     if (rc) { e->err = fg::last_error_text(); return rc; }
     return flowgnn_sync(e);
@@ -1662,6 +1774,12 @@ int flowgnn_group_set_numeric_mode(flowgnn_group* g, int mode) {
     return group_each(g, [&](int i) { return flowgnn_set_numeric_mode(g->eng[(size_t)i], mode); });
 }
 
+int flowgnn_group_set_embeddings(flowgnn_group* g, int on) {
+    if (!g) return FLOWGNN_ERR_ARG;
+    g->err.clear();
+    return group_each(g, [&](int i) { return flowgnn_set_embeddings(g->eng[(size_t)i], on); });
+}
+
 int flowgnn_group_set_batch(flowgnn_group* g, int num_graphs, const int* nums_of_nodes, const int* nums_of_edges,
                             const int* node_feature, const int* edge_list, const int* edge_attr, const float* node_eigen) {
     if (!g) return FLOWGNN_ERR_ARG;
@@ -1747,6 +1865,20 @@ int flowgnn_group_get_results(flowgnn_group* g, float* out_host) {
         flowgnn_engine* e = g->eng[(size_t)i];
         if (e->G == 0) return flowgnn_sync(e);
         return flowgnn_get_results(e, out_host + (size_t)g->cut[(size_t)i] * g->num_tasks);
+    });
+}
+
+int flowgnn_group_get_embeddings(flowgnn_group* g, float* out_host) {
+    if (!g) return FLOWGNN_ERR_ARG;
+    g->err.clear();
+    if (!g->batch_valid) return group_fail(g, FLOWGNN_ERR_STATE, "flowgnn_group_get_embeddings: no batch set by flowgnn_group_set_batch (flowgnn_group_compute and the entry points leave none)");
+    if (int rc = group_shards_intact(g, "flowgnn_group_get_embeddings")) return rc;
+    if (!out_host && g->cut.back() > 0) return group_fail(g, FLOWGNN_ERR_ARG, "flowgnn_group_get_embeddings: null output");
+    const size_t dim = (size_t)flowgnn_embedding_dim(g->model_id);
+    return group_each(g, [&](int i) {
+        flowgnn_engine* e = g->eng[(size_t)i];
+        if (e->G == 0) return e->emb_on ? flowgnn_sync(e) : (int)FLOWGNN_ERR_STATE;
+        return flowgnn_get_embeddings(e, out_host + (size_t)g->cut[(size_t)i] * dim);
     });
 }
 

@@ -1052,7 +1052,8 @@ public:
         if (qmode_) return gatq_forward(q_, db, feat_row, prof, s);
         // all five layers in one launch when the batch packs into graph tiles (tiles under half full, e.g. graphs of 65..128
         // nodes, waste MFMA columns: the per-layer kernels take those); per-node taps (flowgnn_get_h) come from the per-layer path
-        if (resident_ && !keep_h_ && fold_readout_ && split_ && !exact_ && db.gtiles.ok && db.gtiles.n_tiles > 0 && db.gtiles.fill >= 0.5) {
+        // (graph embeddings, db.emb: the resident kernel never forms the pooled row -- the per-layer path with the un-folded last stage does)
+        if (resident_ && !keep_h_ && !db.emb && fold_readout_ && split_ && !exact_ && db.gtiles.ok && db.gtiles.n_tiles > 0 && db.gtiles.fill >= 0.5) {
             GatResidentDev rw;
             rw.layers = d_res_;
             rw.scales = d_scales_;
@@ -1078,7 +1079,7 @@ public:
             ProfScope p(prof, "gat_scores0", s);
             gat_scores0_kernel<<<(n + 255) / 256, 256, 0, s>>>(db.b.node_feature, feat_row, d_lin0_, d_asrc_, d_atgt_, scoreb[0], n);
         }
-        const bool fold = fold_readout_;
+        const bool fold = fold_readout_ && !db.emb;  // embeddings pool the `emb` rows themselves
         int cur = 0;
         for (int l = 0; l < GAT_L; l++) {
             GatLayerDev w;
@@ -1126,6 +1127,10 @@ public:
             else
                 mean_pool_linear_kernel<GAT_D><<<(db.b.num_graphs + 3) / 4, 256, 0, s>>>(emb, db.b.node_off, d_pw_, d_pb_, db.out,
                                                                                          db.b.num_graphs);
+        }
+        if (db.emb) {
+            ProfScope p(prof, "mean_pool_rows", s);
+            mean_pool_rows_kernel<GAT_D><<<(db.b.num_graphs + 3) / 4, 256, 0, s>>>(emb, db.b.node_off, db.emb, db.b.num_graphs);
         }
         return 0;
     }

@@ -53,9 +53,12 @@ struct GcnAggPolicy {
     __device__ static const float* const_ptr(const Params& p) { return p.ep; }
     __device__ static void init(Acc& a) { a.m = make_float4(0.f, 0.f, 0.f, 0.f); }
     __device__ static void edge(Acc& a, const float4& x, const float4& w, float ss, const float* sd) {
+        // (the FMAs spelled out: the kernel inlines this at four places -- the straight-line body of four in-edges, the one with a
+        // source outside the tile, the two tails -- and which of them a row meets depends on where its graph sits in the batch; left to
+        // the compiler's contraction they did not all round alike, and a slice of a batch differed from the batch in the last bit)
         const float norm = ss * sd[0];
-        a.m.x += norm * relu1(w.x + x.x); a.m.y += norm * relu1(w.y + x.y);
-        a.m.z += norm * relu1(w.z + x.z); a.m.w += norm * relu1(w.w + x.w);
+        a.m.x = __builtin_fmaf(norm, relu1(w.x + x.x), a.m.x); a.m.y = __builtin_fmaf(norm, relu1(w.y + x.y), a.m.y);
+        a.m.z = __builtin_fmaf(norm, relu1(w.z + x.z), a.m.z); a.m.w = __builtin_fmaf(norm, relu1(w.w + x.w), a.m.w);
     }
     __device__ static void finish(const Params&, const Acc& a, const float4& xs, int v, int c, int, const float* sd,
                                   const float* cst, float* out) {
@@ -1232,7 +1235,8 @@ public:
     // x_0 by the encoder, then everything else in one launch when the batch packs into graph tiles (tiles under half full waste MFMA
     // columns: the per-layer kernels take those; so do per-node taps and the multi-task readout)
     bool use_resident(const DeviceBatch& db) const {
-        return resident_ && table_ok_ && !qmode_ && !keep_h_ && split_ && !exact_ && fused_ && num_tasks_ == 1 && db.gtiles.ok && db.gtiles.n_tiles > 0 &&
+        // (graph embeddings, db.emb: the resident kernel folds the head per node and never forms the pooled row -- the per-layer path does)
+        return resident_ && table_ok_ && !qmode_ && !keep_h_ && !db.emb && split_ && !exact_ && fused_ && num_tasks_ == 1 && db.gtiles.ok && db.gtiles.n_tiles > 0 &&
                db.gtiles.fill >= 0.5;
     }
     // the one-pass front end (gcn_tile_build_kernel + the resident kernel's own encoder): the default; gcn_tile_build = 0 restores the
@@ -1321,7 +1325,7 @@ public:
         }
         db.final_h = cur;
         db.h_valid = true;
-        if (split_ && !exact_ && fused_ && db.b.e_tot > 0 && num_tasks_ == 1) {
+        if (split_ && !exact_ && fused_ && db.b.e_tot > 0 && num_tasks_ == 1 && !db.emb) {
             // last stage: aggregation + BatchNorm with the readout's linear head folded in (per-node scores in db.scratch;
             // flowgnn_get_h returns x_4 = db.h[final_h], which is untouched by this)
             {
@@ -1349,6 +1353,10 @@ public:
             } else
             mean_pool_linear_kernel<GCN_D><<<(db.b.num_graphs + 3) / 4, 256, 0, s>>>(db.scratch, db.b.node_off, d_pw_, d_pb_,
                                                                                      db.out, db.b.num_graphs);
+        }
+        if (db.emb) {
+            ProfScope p(prof, "mean_pool_rows", s);
+            mean_pool_rows_kernel<GCN_D><<<(db.b.num_graphs + 3) / 4, 256, 0, s>>>(db.scratch, db.b.node_off, db.emb, db.b.num_graphs);
         }
         return 0;
     }

@@ -792,7 +792,8 @@ public:
         // -1 = default = on (development builds: an explicit gin_pingpong keeps the three-kernel front end -- the ping-pong kernel has no
         // encoder in its loader and is never used with a virtual node).
         const bool want = tile_build_ < 0 ? !(pingpong_ && !virtual_node_ && !f16_) : tile_build_ != 0;
-        return want && use_resident(db) && !qmode_ && !keep_h_ && num_tasks_ == 1 && fold_readout_ && head_fold_ && db.b.edge_attr != nullptr;
+        // (graph embeddings, db.emb: the un-folded resident instance pools h_5 on chip; it has the three-kernel front end)
+        return want && use_resident(db) && !qmode_ && !keep_h_ && !db.emb && num_tasks_ == 1 && fold_readout_ && head_fold_ && db.b.edge_attr != nullptr;
     }
     bool needs_csr(const DeviceBatch& db) const override { return !one_pass(db); }
     // (asked at flowgnn_set_batch, before the batch is known: the lists are built whenever the one-pass path could take them)
@@ -859,16 +860,20 @@ public:
             // all five layers and the readout in one launch; h_5 rows are written (to h[1]) only for the flowgnn_get_h tap
             if (int rc = perm_.reserve((size_t)db.gtiles.n_tiles * (GIN_RESIDENT_DESC_BYTES / 4))) return rc;
             const bool rows = keep_h_ || multi;
+            // graph embeddings, single task: the un-folded instance that pools the h_5 rows out of LDS (no row goes to HBM); with the
+            // rows in HBM anyway (NUM_TASK > 1, taps) they are pooled from there, behind the launch
+            float* pool_emb = rows ? nullptr : db.emb;
             {
                 ProfScope p(prof, "gin_resident", s);
                 launch_gin_resident(db.h[0], rows ? db.h[1] : nullptr, db.csr.row_ptr, db.csr.src, db.csr.ecode, d_ecomb_res_, rsplit(), d_pw_, d_pb_,
                                     db.gtiles.row_start, db.gtiles.graph_start, reinterpret_cast<uint8_t*>(perm_.p), db.b.node_off,
                                     multi ? nullptr : db.out, db.gtiles.n_tiles, db.range_flag, s, virtual_node_,
-                                    (!rows && fold_readout_ && head_fold_) ? head() : nullptr, resident_order_, resident_prof_, nullptr, 1, f16_);
+                                    (!rows && fold_readout_ && head_fold_) ? head() : nullptr, resident_order_, resident_prof_, nullptr, 1, f16_, pool_emb);
             }
             db.final_h = rows ? 1 : 0;
             db.h_valid = rows;
             if (multi) launch_readout_mt(db, db.h[1], prof, s);
+            if (rows) launch_pool_rows(db, db.h[1], prof, s);
             return 0;
         }
         int cur = 0;
@@ -878,7 +883,7 @@ public:
                 ProfScope p(prof, "gin_layer_fused", s);
                 // last layer: the readout's per-node dot product h'[v] . w_pred is taken in the epilogue and only that
                 // leaves the kernel (db.scratch as float[n]); the rows are written only for the flowgnn_get_h tap
-                const bool fold = l == GIN_L - 1 && fold_readout_ && !keep_h_ && !multi;
+                const bool fold = l == GIN_L - 1 && fold_readout_ && !keep_h_ && !multi && !db.emb;
                 launch_gin_layer_split(db.h[cur], fold ? db.scratch : db.h[cur ^ 1], db.csr.row_ptr, db.csr.src, db.csr.ecode,
                                        layer_dev(l).ecomb, (f16_ ? d_split16_ : d_split_) + (size_t)l * GS_LAYER_BYTES, n, db.b.e_tot,
                                        l != GIN_L - 1, db.range_flag, split_nt_, s, fold ? d_pw_ : nullptr, f16_);
@@ -914,6 +919,7 @@ public:
         }
         db.final_h = cur;
         db.h_valid = !folded;
+        if (!folded) launch_pool_rows(db, db.h[cur], prof, s);
         if (multi) {
             launch_readout_mt(db, db.h[cur], prof, s);
             return 0;
@@ -928,6 +934,13 @@ public:
                                                                                          db.out, db.b.num_graphs);
         }
         return 0;
+    }
+
+    // graph embeddings from h_5 rows that are in HBM anyway (per-layer path, NUM_TASK > 1, taps)
+    void launch_pool_rows(DeviceBatch& db, const float* h, Profiler& prof, hipStream_t s) {
+        if (!db.emb) return;
+        ProfScope p(prof, "mean_pool_rows", s);
+        mean_pool_rows_kernel<GIN_D><<<(db.b.num_graphs + 3) / 4, 256, 0, s>>>(h, db.b.node_off, db.emb, db.b.num_graphs);
     }
 
     void launch_readout_mt(DeviceBatch& db, const float* h, Profiler& prof, hipStream_t s) {

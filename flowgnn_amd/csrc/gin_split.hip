@@ -44,6 +44,12 @@
 #ifndef GS_SINGLE_PRODUCT
 #define GS_SINGLE_PRODUCT 0
 #endif
+// Pooling instances (flowgnn_set_embeddings): gin_split_pool.hip compiles this file a third time with GS_POOL_TU = 1, for the
+// resident kernel's instances that pool h_5 into graph embeddings (gin_resident_pool_kernel<HUBS, F16>, both numeric modes) and their
+// launcher alone -- the kernels of the other two translation units stay the code they were, names and register figures included.
+#ifndef GS_POOL_TU
+#define GS_POOL_TU 0
+#endif
 
 namespace fg {
 
@@ -722,7 +728,9 @@ __device__ __forceinline__ void gr_step(const char* wb, int lane, int g, const u
 // MLP) one unit later, under the MFMAs of the following output tiles.  Stored after the last step the tile's 102 KB of rows cost
 // 0.28 ms per launch at the ~80 B per clock of ds_write_b128 with the matrix pipe idle (measured by leaving them out), and the
 // eighth step a barrier and a fragment round trip of its own for 14 MFMAs.
-template <bool STORE, bool F16>
+// STORE 0: acc2 only (the last layer's readout terms come from it); 1: ReLU'd rows into the tile; 2: the rows as they are (the last
+// layer has no ReLU) into the tile, for the instances that pool h_5 out of LDS (gin_resident_pool_kernel, gin_split_pool.hip).
+template <int STORE, bool F16>
 __device__ __forceinline__ void gr_step_final(const char* wb, int lane, int g, const uint4_t (&in_hi)[2][3], const uint4_t (&in_lo)[2][3],
                                               const uint4_t (&in_tb)[2], const uint4_t (&hb_hi)[2], const uint4_t (&hb_lo)[2],
                                               float4_t (&acc2)[2][GS_T2], float& vmax, float oscale, float* rw0, float* rw1) {
@@ -757,12 +765,14 @@ __device__ __forceinline__ void gr_step_final(const char* wb, int lane, int g, c
     acc2[0][T] = GS_MFMA16(P, hp[0], acc2[0][T]);          \
     acc2[1][T] = GS_MFMA16(P, hp[1], acc2[1][T]);
 #define GRF_STORE(T)                                                                                                  \
-    if constexpr (STORE) {                                                                                            \
+    if constexpr (STORE != 0) {                                                                                       \
         constexpr int col0_ = 16 * (T);                                                                               \
         if (col0_ + 4 * g < GS_D) {                                                                                   \
             float4_t r0_ = acc2[0][T] * oscale, r1_ = acc2[1][T] * oscale;                                            \
-            r0_.x = gs_relu(r0_.x); r0_.y = gs_relu(r0_.y); r0_.z = gs_relu(r0_.z); r0_.w = gs_relu(r0_.w);           \
-            r1_.x = gs_relu(r1_.x); r1_.y = gs_relu(r1_.y); r1_.z = gs_relu(r1_.z); r1_.w = gs_relu(r1_.w);           \
+            if constexpr (STORE == 1) {                                                                               \
+                r0_.x = gs_relu(r0_.x); r0_.y = gs_relu(r0_.y); r0_.z = gs_relu(r0_.z); r0_.w = gs_relu(r0_.w);       \
+                r1_.x = gs_relu(r1_.x); r1_.y = gs_relu(r1_.y); r1_.z = gs_relu(r1_.z); r1_.w = gs_relu(r1_.w);       \
+            }                                                                                                         \
             *reinterpret_cast<float4_t*>(rw0 + col0_ + 4 * g) = r0_;                                                  \
             *reinterpret_cast<float4_t*>(rw1 + col0_ + 4 * g) = r1_;                                                  \
         }                                                                                                             \
@@ -1239,7 +1249,7 @@ __device__ __forceinline__ void gr_issue_desc(const uint8_t* __restrict__ desc, 
         lds_dma16(reinterpret_cast<const char*>(desc) + (size_t)tile * GR_DESC_BYTES + wave * 1024, (uint32_t)lane * 16u, lds_addr_of(s_desc) + wave * 1024);
 }
 
-template <bool PROF, bool HUBS, bool LAST, bool FOLD, bool ENC, bool F16>
+template <bool PROF, bool HUBS, bool LAST, bool FOLD, bool ENC, bool F16, bool POOL = false>
 __device__ __forceinline__ void gr_layer(unsigned long long (&tacc)[6], char* bx, char* by, float* s_h, char* s_desc, float* s_dot,
                                          const GrTile& cur, const GrTile& nxt, bool has_next, int next_tile, int l,
                                          const float* __restrict__ h0, const uint8_t* __restrict__ desc, const float* __restrict__ ecomb_all,
@@ -1256,6 +1266,11 @@ __device__ __forceinline__ void gr_layer(unsigned long long (&tacc)[6], char* bx
     // last layer with the readout folded through its second linear layer: h_5 . w = hid . (W2^T w) + b2 . w, so only the hidden tiles
     // are computed and dotted with u = W2^T w_pred (s_u, pre-divided by the first layer's power-of-two scale)
     constexpr bool fold = LAST && FOLD;  // compile-time as well: the folded kernel carries no second linear layer for its last layer
+    // POOL (graph embeddings): the last layer's rows h_5 go back into the tile as the earlier layers' do, to be pooled per graph out of
+    // LDS behind this layer -- so the NEXT tile's rows, which the other instances bring in under this layer's MLP steps, wait until
+    // the pooling is done (gin_resident_kernel)
+    constexpr bool prefetch_rows = LAST && !POOL;
+    static_assert(!POOL || !FOLD, "the pooled rows are those of the un-folded last layer");
     const uint16_t* s_edge = reinterpret_cast<const uint16_t*>(s_desc);
     const uint16_t* s_rp = reinterpret_cast<const uint16_t*>(s_desc + GR_DESC_RP);
     const uint8_t* s_perm = reinterpret_cast<const uint8_t*>(s_desc + GR_DESC_PERM);
@@ -1656,7 +1671,7 @@ __device__ __forceinline__ void gr_layer(unsigned long long (&tacc)[6], char* bx
     for (int c = 0; c < GR_STEPS - 1; c += 2) {
         // even step: compute from by while chunk c+1 streams into bx
         grc_issue_chunk(wchunks + (size_t)(c + 1) * GRC_CHUNK_STRIDE, bx, wave, lane);
-        if (last && has_next) gr_issue_rows(h0, reinterpret_cast<char*>(s_h), nxt, c, wave, lane);
+        if (prefetch_rows && has_next) gr_issue_rows(h0, reinterpret_cast<char*>(s_h), nxt, c, wave, lane);
         if (c == 0) gr_step<0, F16, false, GR_DEFER>(by, lane, g, in_hi, in_lo, in_tb, h_hi, h_lo, acc2, vmax, pend, nullptr, nullptr, wave);
         else gr_step<1, F16, GR_DEFER, GR_DEFER>(by, lane, g, in_hi, in_lo, in_tb, h_hi, h_lo, acc2, vmax, pend, nullptr, nullptr, wave);
         unsigned long long tw = 0;
@@ -1667,7 +1682,7 @@ __device__ __forceinline__ void gr_layer(unsigned long long (&tacc)[6], char* bx
         if constexpr (PROF) { const unsigned long long t = wall_clock64(); tacc[GR_TACC_BAR] += t - tw; }
         // odd step: compute from bx while chunk c+2 streams into by
         grc_issue_chunk(wchunks + (size_t)(c + 2) * GRC_CHUNK_STRIDE, by, wave, lane);
-        if (last && has_next) gr_issue_rows(h0, reinterpret_cast<char*>(s_h), nxt, c + 1, wave, lane);
+        if (prefetch_rows && has_next) gr_issue_rows(h0, reinterpret_cast<char*>(s_h), nxt, c + 1, wave, lane);
         if (c + 1 == GR_STEPS - 2) gr_step<1, F16, GR_DEFER, false>(bx, lane, g, in_hi, in_lo, in_tb, h_hi, h_lo, acc2, vmax, pend, nullptr, nullptr, wave);
         else gr_step<1, F16, GR_DEFER, GR_DEFER>(bx, lane, g, in_hi, in_lo, in_tb, h_hi, h_lo, acc2, vmax, pend, nullptr, nullptr, wave);
         if constexpr (PROF) tw = wall_clock64();
@@ -1680,11 +1695,11 @@ __device__ __forceinline__ void gr_layer(unsigned long long (&tacc)[6], char* bx
     // nobody reads any more -- an odd number of steps, so the two buffers keep their roles from layer to layer.  In the layers that
     // feed another one the finished rows go back into the tile from inside the step (gr_step_final).
     gr_issue_ecomb(ecomb_all + (size_t)ln * EDGE_COMBOS * GS_D, bx, wave, lane);
-    if (last && has_next) {
+    if (prefetch_rows && has_next) {
         gr_issue_rows(h0, reinterpret_cast<char*>(s_h), nxt, GR_STEPS - 1, wave, lane);
         gr_issue_rows(h0, reinterpret_cast<char*>(s_h), nxt, GR_STEPS, wave, lane);
     }
-    gr_step_final<!last, F16>(by, lane, g, in_hi, in_lo, in_tb, h_hi, h_lo, acc2, vmax, oscale, s_h + row[0] * GS_D, s_h + row[1] * GS_D);
+    gr_step_final<(last ? (POOL ? 2 : 0) : 1), F16>(by, lane, g, in_hi, in_lo, in_tb, h_hi, h_lo, acc2, vmax, oscale, s_h + row[0] * GS_D, s_h + row[1] * GS_D);
 
     }
     if constexpr (PROF) { const unsigned long long t = wall_clock64(); tacc[2] += t - tp; tp = t; }
@@ -1725,7 +1740,16 @@ __device__ __forceinline__ void gr_layer(unsigned long long (&tacc)[6], char* bx
     if constexpr (PROF) { const unsigned long long t = wall_clock64(); tacc[3] += t - tp; }
 }
 
+// POOL (flowgnn_set_embeddings; un-folded, no in-kernel encoder): emb[g][:] = mean of the graph's h_5 rows.  The last layer writes
+// h_5 into the tile, and behind its closing barrier thread t takes the (graph, column) pairs t, t + 512, ... of the tile: consecutive
+// lanes read consecutive columns of one row (no bank conflict at a row stride of 100 floats) and store consecutive floats of one
+// embedding; a column's sum is one chain of adds in node order, so it depends on the graph alone.  Only then are the next tile's rows
+// requested, all at once as in the prologue: that load is the price of this form (graph embeddings).
+#if GS_POOL_TU
+template <bool HUBS, bool F16>
+#else
 template <bool PROF, bool HUBS, bool FOLD, bool ENC>
+#endif
 __global__ __launch_bounds__(GR_WAVES * 64, 2) void gin_resident_kernel(const float* __restrict__ h0, float* __restrict__ hout,
                                                                        const float* __restrict__ ecomb_all,
                                                                        const uint8_t* __restrict__ wchunks_all,
@@ -1736,8 +1760,17 @@ __global__ __launch_bounds__(GR_WAVES * 64, 2) void gin_resident_kernel(const fl
                                                                        int* __restrict__ range_flag, unsigned long long* __restrict__ prof_out,
                                                                        const float* __restrict__ head_u, const uint32_t* __restrict__ enc_idx,
                                                                        const float4* __restrict__ enc_tab, int tstride,
-                                                                       const int* __restrict__ list, const int* __restrict__ lrow) {
+                                                                       const int* __restrict__ list, const int* __restrict__ lrow
+#if GS_POOL_TU
+                                                                       , float* __restrict__ emb) {
+    constexpr bool PROF = false, FOLD = false, ENC = false, POOL = true;
+#else
+                                                                       ) {
+    constexpr bool POOL = false, F16 = GS_F16;
+    float* const emb = nullptr;
+#endif
     static_assert(!ENC || FOLD, "the in-kernel encoder rides on the folded last layer's steps");
+    static_assert(!POOL || (!FOLD && !ENC), "the pooling instance is the un-folded one");
     __shared__ __attribute__((aligned(16))) char s_a[GRC_CHUNK_BYTES];
     __shared__ __attribute__((aligned(16))) char s_b[GRC_CHUNK_BYTES];
     __shared__ __attribute__((aligned(16))) float s_h[(GR_ROWS + 1) * GS_D];  // + the no-edge row (GR_NO_EDGE)
@@ -1781,9 +1814,33 @@ __global__ __launch_bounds__(GR_WAVES * 64, 2) void gin_resident_kernel(const fl
         const GrTile nxt = gr_load_tile(tile_row, tile_graph, ntile, n_tiles, tstride);  // used five layers from now
 #pragma unroll 1
         for (int l = 0; l < 4; l++)
-            gr_layer<PROF, HUBS, false, FOLD, ENC, GS_F16>(tacc, s_a, s_b, s_h, s_desc, s_dot, cur, nxt, has_next, ntile, l, h0, desc, ecomb_all, wchunks_all, pool_w, hout, vmax, wave, lane, nullptr, enc_idx, enc_tab, tile_trips);
+            gr_layer<PROF, HUBS, false, FOLD, ENC, F16>(tacc, s_a, s_b, s_h, s_desc, s_dot, cur, nxt, has_next, ntile, l, h0, desc, ecomb_all, wchunks_all, pool_w, hout, vmax, wave, lane, nullptr, enc_idx, enc_tab, tile_trips);
         // (every layer runs an odd number of MLP steps -- seven -- so the table buffer s_a and the first chunk's buffer s_b keep their roles)
-        gr_layer<PROF, HUBS, true, FOLD, ENC, GS_F16>(tacc, s_a, s_b, s_h, s_desc, s_dot, cur, nxt, has_next, ntile, 4, h0, desc, ecomb_all, wchunks_all, pool_w, hout, vmax, wave, lane, fold_head ? s_u : nullptr, enc_idx, enc_tab, tile_trips);
+        gr_layer<PROF, HUBS, true, FOLD, ENC, F16, POOL>(tacc, s_a, s_b, s_h, s_desc, s_dot, cur, nxt, has_next, ntile, 4, h0, desc, ecomb_all, wchunks_all, pool_w, hout, vmax, wave, lane, fold_head ? s_u : nullptr, enc_idx, enc_tab, tile_trips);
+        if constexpr (POOL) {  // every row of h_5 is in the tile (the layer's closing barrier)
+            const int items = (cur.g1 - cur.g0) * GS_D;
+            for (int item = (int)threadIdx.x; item < items; item += GR_WAVES * 64) {
+                const int gl = item / GS_D, col = item - gl * GS_D;
+                const int gph = cur.g0 + gl;  // (tiles are ranges of graphs here: bin-packed lists exist in the ENC form only)
+                const int n0 = node_off[gph], n = node_off[gph + 1] - n0;
+                const float* p = s_h + (n0 - cur.t0) * GS_D + col;
+                float sum = 0.0f;
+                int v = 0;
+                for (; v + 3 < n; v += 4) {  // (four reads in flight; added in node order)
+                    const float x0 = p[v * GS_D], x1 = p[(v + 1) * GS_D], x2 = p[(v + 2) * GS_D], x3 = p[(v + 3) * GS_D];
+                    sum += x0; sum += x1; sum += x2; sum += x3;
+                }
+                for (; v < n; v++) sum += p[v * GS_D];
+                emb[(size_t)gph * GS_D + col] = sum / (float)n;
+            }
+            if (has_next) {
+                __syncthreads();  // the tile's rows are dead now: the next tile's may land
+#pragma unroll 1
+                for (int part = 0; part < 8; part++) gr_issue_rows(h0, reinterpret_cast<char*>(s_h), nxt, part, wave, lane);
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                __syncthreads();
+            }
+        }
         // readout (GIN/src/finalize.cc:36-113): out[g] = mean_v(h5[v] . w) + b, node order; the terms stay valid until the next
         // tile's last layer rewrites them, so no barrier is needed before the next tile starts
         {
@@ -1819,6 +1876,7 @@ __global__ __launch_bounds__(GR_WAVES * 64, 2) void gin_resident_kernel(const fl
 #include "dev/gin_pp_device.inc"  // gin_pp_kernel: the ping-pong form, measured slower -- development builds only
 #endif
 
+#if !GS_POOL_TU
 // this translation unit's per-layer kernels (GS_F16: which instance)
 void launch_split_nt(const float* h, float* hout, const int* row_ptr, const int* src, const uint8_t* ecode, const float* ecomb,
                      const uint8_t* chunks, int n_tot, int relu_out, int* range_flag, int nt, hipStream_t s, const float* pool_w) {
@@ -1859,6 +1917,7 @@ void gr_dispatch(bool prof, bool hubs, bool fold, bool enc, int grid, hipStream_
 #undef GR_LAUNCH_FE
 #undef GR_LAUNCH
 }
+#endif  // !GS_POOL_TU
 
 #if !GS_SINGLE_PRODUCT
 inline float pow2_scale(const float* w, size_t n) {
@@ -1879,7 +1938,19 @@ inline void put_split(uint8_t* frag, int lane, int e, float v, bool f16 = false)
 #endif
 }  // namespace
 
-#if GS_SINGLE_PRODUCT
+#if GS_POOL_TU
+void gin_resident_pool_dispatch(bool hubs, bool f16, int grid, hipStream_t s, const float* h0, const float* ecomb_all, const uint8_t* chunks_all,
+                                const float* pool_w, const float* pool_b, const int* tile_row, const int* tile_graph, const uint8_t* tile_desc,
+                                const int* node_off, float* out, int n_tiles, int* range_flag, int tstride, float* emb) {
+#define GR_LAUNCH_POOL(H, F)                                                                                                              \
+    gin_resident_kernel<H, F><<<grid, GR_WAVES * 64, 0, s>>>(h0, nullptr, ecomb_all, chunks_all, pool_w, pool_b, tile_row, tile_graph, tile_desc, \
+                                                             node_off, out, n_tiles, range_flag, nullptr, nullptr, nullptr, nullptr, tstride,   \
+                                                             nullptr, nullptr, emb)
+    if (f16) { if (hubs) GR_LAUNCH_POOL(true, true); else GR_LAUNCH_POOL(false, true); }
+    else { if (hubs) GR_LAUNCH_POOL(true, false); else GR_LAUNCH_POOL(false, false); }
+#undef GR_LAUNCH_POOL
+}
+#elif GS_SINGLE_PRODUCT
 // the entry points of the single-product instances (called by the launchers of gin_split.hip's own translation unit)
 void launch_gin_layer_split_f16(const float* h, float* hout, const int* row_ptr, const int* src, const uint8_t* ecode, const float* ecomb,
                                 const uint8_t* chunks, int n_tot, int relu_out, int* range_flag, int nt, hipStream_t s, const float* pool_w) {
@@ -1902,6 +1973,10 @@ void gin_resident_dispatch_f16(bool prof, bool hubs, bool fold, bool enc, int gr
                                const int* tile_graph, const uint8_t* tile_desc, const int* node_off, float* out, int n_tiles, int* range_flag,
                                unsigned long long* d, const float* head_u, const uint32_t* eidx, const float4* etab, int tstride,
                                const int* list, const int* lrow);
+// (gin_split_pool.hip) the instances that pool h_5 into emb [G][100]: un-folded, rows from HBM, no phase stamps
+void gin_resident_pool_dispatch(bool hubs, bool f16, int grid, hipStream_t s, const float* h0, const float* ecomb_all, const uint8_t* chunks_all,
+                                const float* pool_w, const float* pool_b, const int* tile_row, const int* tile_graph, const uint8_t* tile_desc,
+                                const int* node_off, float* out, int n_tiles, int* range_flag, int tstride, float* emb);
 
 void gin_split_pack_layer(const float* w1, const float* b1, const float* w2, const float* b2, uint8_t* out, bool f16) {
     std::memset(out, 0, GS_LAYER_BYTES);
@@ -2062,9 +2137,10 @@ void launch_gin_layer_split(const float* h, float* hout, const int* row_ptr, con
 void launch_gin_resident(const float* h0, float* hout, const int* row_ptr, const int* src, const uint8_t* ecode, const float* ecomb_all,
                          const uint8_t* chunks_all, const float* pool_w, const float* pool_b, const int* tile_row, const int* tile_graph,
                          uint8_t* tile_desc, const int* node_off, float* out, int n_tiles, int* range_flag, hipStream_t s, bool hubs,
-                         const float* head_u, int col_order, bool prof, const GinTileBuild* tb, int tstride, bool f16) {
+                         const float* head_u, int col_order, bool prof, const GinTileBuild* tb, int tstride, bool f16, float* emb) {
     if (n_tiles <= 0) return;
     const int order = hubs ? 3 : col_order;
+    if (emb != nullptr) { head_u = nullptr; hout = nullptr; prof = false; }  // the pooling instance: un-folded, no tap, no phase stamps
     const bool fold = head_u != nullptr && out != nullptr && hout == nullptr;  // single-task readout, no per-node tap
     const bool enc = tb != nullptr && fold;  // descriptor + encoder indices straight from the caller's arrays, h_0 computed by the tile loader
     if (!enc) gin_tile_prep_kernel<<<n_tiles, 256, 0, s>>>(row_ptr, src, ecode, tile_row, tile_desc, n_tiles, order, tstride);
@@ -2077,6 +2153,11 @@ void launch_gin_resident(const float* h0, float* hout, const int* row_ptr, const
     }
     const uint32_t* eidx = enc ? reinterpret_cast<const uint32_t*>(tb->enc_idx) : nullptr;
     const float4* etab = enc ? reinterpret_cast<const float4*>(tb->enc_tab) : nullptr;
+    if (emb != nullptr) {
+        gin_resident_pool_dispatch(hubs, f16, grid, s, h0, ecomb_all, chunks_all, pool_w, pool_b, tile_row, tile_graph, tile_desc, node_off, out,
+                                   n_tiles, range_flag, tstride, emb);
+        return;
+    }
     (f16 ? gin_resident_dispatch_f16 : gr_dispatch)(prof, hubs, fold, enc, grid, s, h0, hout, ecomb_all, chunks_all, pool_w, pool_b, tile_row,
                                                     tile_graph, tile_desc, node_off, out, n_tiles, range_flag, d, head_u, eidx, etab, tstride,
                                                     enc ? tb->list : nullptr, enc ? tb->lrow : nullptr);

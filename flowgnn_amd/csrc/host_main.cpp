@@ -76,13 +76,13 @@ static bool read_eig_txt(const std::string& path, std::vector<float>& eig, size_
 int main(int argc, char** argv) {
     if (argc < 2) {
         fprintf(stderr, "Usage: %s <GIN|GIN-VN|GCN|GAT|PNA|DGN> [--graphs DIR] [--weights DIR] [--num-graphs N] [--trials T] "
-                        "[--out FILE] [--device D | --devices D0,D1,..] [--option key=value] [--numeric f32|q6.10|f16] [--num-tasks T] [XCLBIN File]\n", argv[0]);
+                        "[--out FILE] [--embeddings FILE] [--device D | --devices D0,D1,..] [--option key=value] [--numeric f32|q6.10|f16] [--num-tasks T] [XCLBIN File]\n", argv[0]);
         return EXIT_FAILURE;
     }
     const std::string model = argv[1];
     const int mid = model_id(model);
     if (mid < 0) { fprintf(stderr, "unknown model %s\n", model.c_str()); return EXIT_FAILURE; }
-    std::string graphs = "../graphs", wdir = ".", out_path = "HLS_output.txt", eig_dir = "eig";
+    std::string graphs = "../graphs", wdir = ".", out_path = "HLS_output.txt", eig_dir = "eig", emb_path;
     long num_graphs = -1;
     int trials = 25, numeric = FLOWGNN_NUMERIC_F32, num_tasks = 1;
     std::vector<int> devices;
@@ -99,6 +99,7 @@ int main(int argc, char** argv) {
         else if (a == "--num-graphs") num_graphs = atol(next("--num-graphs"));
         else if (a == "--trials") trials = atoi(next("--trials"));
         else if (a == "--out") out_path = next("--out");
+        else if (a == "--embeddings") emb_path = next("--embeddings");  // the per-graph pooled embeddings, one line of dim values per graph
         else if (a == "--device") { devices.clear(); devices.push_back(atoi(next("--device"))); }
         else if (a == "--devices") {  // e.g. 0,1,2,3,4,5,6,7: the batch is cut by sum(N + E), one engine + host thread per device
             devices.clear();
@@ -218,6 +219,20 @@ int main(int argc, char** argv) {
     for (long g = 1; g <= num_graphs; g++)  // one line per task, as host.cc:213-222
         for (int t = 0; t < num_tasks; t++) fprintf(o, "g%ld: %.8f\n", g, result[(size_t)(g - 1) * num_tasks + t]);
     fclose(o);
+    if (!emb_path.empty()) {
+        // one more run with embeddings on, behind the timed ones: the figures and the logits above are those of a run without the flag
+        const int dim = flowgnn_embedding_dim(mid);
+        std::vector<float> emb((size_t)num_graphs * dim);
+        rc = flowgnn_group_set_embeddings(eng, 1);
+        if (!rc) rc = flowgnn_group_run(eng);
+        if (!rc) rc = flowgnn_group_get_embeddings(eng, emb.data());
+        if (rc) { fprintf(stderr, "--embeddings: %d %s\n", rc, flowgnn_group_last_error(eng)); return EXIT_FAILURE; }
+        FILE* ef = fopen(emb_path.c_str(), "w");
+        if (!ef) { fprintf(stderr, "cannot write %s\n", emb_path.c_str()); return EXIT_FAILURE; }
+        for (long g = 0; g < num_graphs; g++)
+            for (int d = 0; d < dim; d++) fprintf(ef, d + 1 < dim ? "%.8f " : "%.8f\n", emb[(size_t)g * dim + d]);
+        fclose(ef);
+    }
     flowgnn_group_destroy(eng);
     return 0;
 }

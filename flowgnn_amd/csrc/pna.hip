@@ -22,6 +22,17 @@
 #include <cstring>
 
 namespace fg {
+// pna_emb.hip compiles this file once more with FG_RESIDENT_EMB_TU defined, for ONE kernel: pna_resident_kernel under the name
+// pna_resident_emb_kernel, the instance that also stores every graph's pooled row (flowgnn_set_embeddings).  A second instance in
+// this translation unit or a pointer tested at run time both cost the default kernel registers (and 0.4 - 1.7 % of its time); this way
+// the default kernel is the code it was.  In that translation unit the host side is left out and the other kernels, with internal linkage and unused, are dropped.
+void launch_pna_resident_emb(const void* resident_args, int grid, hipStream_t s);  // pna_emb.hip
+#ifdef FG_RESIDENT_EMB_TU
+namespace {
+constexpr bool RESIDENT_EMB = true;
+#else
+constexpr bool RESIDENT_EMB = false;
+#endif
 
 constexpr int PNA_D = 80;
 constexpr int PNA_L = 4;
@@ -791,6 +802,7 @@ struct PnaResidentArgs {
     const int* node_off;       // [G + 1]
     const float *w1t, *b1, *w2t, *b2, *w3, *b3;  // head, w1 / w2 transposed ([in][out]: coalesced over the output lanes)
     float* out;                // [G]
+    float* emb;                // [G][80]: the pooled rows the head reads (flowgnn_set_embeddings; pna_resident_emb_kernel stores them), or null
     int* range_flag;
     int* err;
     float avg_deg;
@@ -954,6 +966,9 @@ __global__ __launch_bounds__(PNA_FT_WAVES * 64, 4) void pna_resident_kernel(cons
                     s_hg[4 * c + 2] = acc.z / n; s_hg[4 * c + 3] = acc.w / n;
                 }
                 __builtin_amdgcn_wave_barrier();
+                if constexpr (RESIDENT_EMB) {  // the pooled row the head is about to read, as it stands in LDS: twenty lanes, one float4 each
+                    if (lane < PNA_C) reinterpret_cast<float4*>(a.emb + (size_t)gi * PNA_D)[lane] = *reinterpret_cast<const float4*>(s_hg + 4 * lane);
+                }
                 if (lane < 40) {
                     float s = a.b1[lane];
                     for (int i = 0; i < PNA_D; i++) s = __builtin_fmaf(s_hg[i], a.w1t[i * 40 + lane], s);
@@ -985,6 +1000,7 @@ __global__ __launch_bounds__(PNA_FT_WAVES * 64, 4) void pna_resident_kernel(cons
 // host: conv_w of one layer [80][3][4][80] -> the FEATURE-major weight stream of pna_layer_fused_kernel (same chunk geometry as
 // pna_pack_split_layer: chunk ks = fragments of the 15 (scaler, output tile) pairs, hi then lo, 1 KiB each); K-slot e of lane
 // group gk in K-step ks is (feature 8 ks + 2 gk + (e >> 2), aggregator e & 3).  The scale is the one pna_pack_split_layer returns.
+#ifndef FG_RESIDENT_EMB_TU  // (host side: the model's own translation unit only)
 static void pna_pack_stream_layer(const float* cw, uint8_t* out) {
     float m = 0.0f;
     for (size_t i = 0; i < (size_t)PNA_D * PNA_NS * PNA_NA * PNA_D; i++) m = std::fmax(m, std::fabs(cw[i]));
@@ -1170,14 +1186,15 @@ public:
         a.wpk = d_stream_; a.bias = d_cb_;
         a.tile_row = t_row; a.tile_graph = t_graph; a.node_off = db.b.node_off;
         a.w1t = d_w1t_; a.b1 = d_b1_; a.w2t = d_w2t_; a.b2 = d_b2_; a.w3 = d_w3_; a.b3 = d_b3_;
-        a.out = db.out; a.range_flag = db.range_flag; a.err = db.csr.err;
+        a.out = db.out; a.emb = db.emb; a.range_flag = db.range_flag; a.err = db.csr.err;
         a.avg_deg = avg_deg_;
         for (int l = 0; l < PNA_L; l++) a.oscale[l] = oscale_[l];
         a.n_tiles = n_tiles;
         const int grid = n_tiles < 256 ? n_tiles : 256;  // persistent: one 16-wave workgroup per CU
         {
             ProfScope p(prof, "pna_resident", s);
-            pna_resident_kernel<<<grid, PNA_FT_WAVES * 64, 0, s>>>(a);
+            if (a.emb) launch_pna_resident_emb(&a, grid, s);  // the same kernel's storing instance (pna_emb.hip)
+            else pna_resident_kernel<<<grid, PNA_FT_WAVES * 64, 0, s>>>(a);
         }
         db.final_h = 0;
         db.h_valid = false;  // no per-node tensor leaves the kernel: flowgnn_get_h repeats the pass on the per-layer kernels
@@ -1236,6 +1253,10 @@ public:
         db.final_h = cur;
         {
             ProfScope p(prof, "pool_mlp3", s);
+            if (db.emb)
+                pool_mlp3_kernel<PNA_D, 40, 20, true><<<(db.b.num_graphs + 3) / 4, 256, 0, s>>>(db.h[cur], db.b.node_off, d_w1_, d_b1_, d_w2_, d_b2_,
+                                                                                                d_w3_, d_b3_, db.out, db.b.num_graphs, db.emb);
+            else
             pool_mlp3_kernel<PNA_D, 40, 20><<<(db.b.num_graphs + 3) / 4, 256, 0, s>>>(db.h[cur], db.b.node_off, d_w1_, d_b1_, d_w2_,
                                                                                       d_b2_, d_w3_, d_b3_, db.out, db.b.num_graphs);
         }
@@ -1335,5 +1356,13 @@ private:
 };
 
 Model* make_pna_model() { return new PnaModel(); }
+#endif  // FG_RESIDENT_EMB_TU
+
+#ifdef FG_RESIDENT_EMB_TU
+}  // namespace
+void launch_pna_resident_emb(const void* resident_args, int grid, hipStream_t s) {
+    pna_resident_kernel<<<grid, PNA_FT_WAVES * 64, 0, s>>>(*static_cast<const PnaResidentArgs*>(resident_args));
+}
+#endif
 
 }  // namespace fg

@@ -48,6 +48,14 @@ def option_value(v) -> float:
     return float(v)
 
 
+def embedding_dim(model: str) -> int:
+    """Floats per graph of a model's graph embedding (flowgnn.h: flowgnn_embedding_dim); host code only, no GPU needed."""
+    model = model.upper()
+    if model not in _lib.MODEL_IDS:
+        raise ValueError(f"unknown model {model}")
+    return int(_lib.load().flowgnn_embedding_dim(_lib.MODEL_IDS[model]))
+
+
 class Engine:
     """One engine = one GPU, one stream, one model's weights, one resident batch.
     `options`: {key: value} passed to flowgnn_set_option right after creation (e.g. {"gin_resident": 0})."""
@@ -86,6 +94,7 @@ class Engine:
             self.lib.flowgnn_destroy(self._h)
             self._h = C.c_void_p()
         self._results_tensor = None  # (forward_device's output: released once the engine, and its stream, are gone)
+        self._embeddings_tensor = None
 
     def __del__(self):
         try:
@@ -223,23 +232,33 @@ class Engine:
             if t is not None:
                 t.record_stream(cur)
 
-    def forward_device(self, x, edge_index, edge_attr=None, node_eigen=None, *, ptr, nums_of_edges=None):
+    def forward_device(self, x, edge_index, edge_attr=None, node_eigen=None, *, ptr, nums_of_edges=None, return_embeddings=False):
         """set_batch_device, then one forward into a new torch tensor on the device ([G], or [G][num_tasks]); torch's current stream
         waits for the engine's, the host does not.  Validation errors (and the range check that can repeat a pass on the exact
-        kernels) are seen by sync(), which raises; without it the tensor of a refused batch holds whatever the kernels wrote."""
+        kernels) are seen by sync(), which raises; without it the tensor of a refused batch holds whatever the kernels wrote.
+        return_embeddings: (logits, embeddings), the graph embeddings ([G][embedding_dim]) in a new device tensor as well, written
+        by the kernels themselves (flowgnn_set_embeddings_buffer); embeddings stay on for later runs (set_embeddings(False) ends it)."""
         import torch
         dev = torch.device("cuda", self.device)
         cur = torch.cuda.current_stream(dev)
         G = (len(ptr) - 1) if not isinstance(ptr, torch.Tensor) else int(ptr.numel()) - 1
         out = torch.empty(G * self.num_tasks, dtype=torch.float32, device=dev)  # (before the engine's stream waits for torch's)
+        emb = None
+        if return_embeddings:
+            emb = torch.empty((G, embedding_dim(self.model)), dtype=torch.float32, device=dev)
+            self.set_embeddings(True)
         self.set_batch_device(x, edge_index, edge_attr, node_eigen, ptr=ptr, nums_of_edges=nums_of_edges)
         es = torch.cuda.ExternalStream(self.stream_handle(), device=dev)
         if G:
             self.set_results_buffer(out.data_ptr())
             self._results_tensor = out  # the engine writes there until the next set_batch: keep it alive
+            if emb is not None:
+                self.set_embeddings_buffer(emb.data_ptr())
+                self._embeddings_tensor = emb
         self.run()
         cur.wait_stream(es)
-        return out.view(G, self.num_tasks) if self.num_tasks > 1 else out
+        logits = out.view(G, self.num_tasks) if self.num_tasks > 1 else out
+        return (logits, emb) if return_embeddings else logits
 
     def run(self):
         self._check(self.lib.flowgnn_run(self._h), "flowgnn_run")
@@ -265,10 +284,34 @@ class Engine:
     def set_results_buffer(self, device_ptr: int):
         self._check(self.lib.flowgnn_set_results_buffer(self._h, C.c_void_p(device_ptr)), "flowgnn_set_results_buffer")
 
-    def forward(self, batch: GraphBatch) -> np.ndarray:
+    def forward(self, batch: GraphBatch, return_embeddings: bool = False):
+        """set_batch + run + results; return_embeddings: (logits, embeddings) -- embeddings stay on for later runs."""
+        if return_embeddings:
+            self.set_embeddings(True)
         self.set_batch(batch)
         self.run()
-        return self.results()
+        return (self.results(), self.embeddings()) if return_embeddings else self.results()
+
+    # ---- graph embeddings (flowgnn.h: flowgnn_set_embeddings)
+    def set_embeddings(self, on: bool = True):
+        """Runs enqueued after this also produce the per-graph pooled embeddings, the vector the readout head is applied to."""
+        self._check(self.lib.flowgnn_set_embeddings(self._h, 1 if on else 0), "flowgnn_set_embeddings")
+
+    def embeddings(self) -> np.ndarray:
+        """[G][embedding_dim(model)] of the last run (synchronises); FLOWGNN_ERR_STATE if that run had embeddings off."""
+        out = np.empty((self.num_graphs, embedding_dim(self.model)), dtype=np.float32)
+        self._check(self.lib.flowgnn_get_embeddings(self._h, _pf(out)), "flowgnn_get_embeddings")
+        return out
+
+    def embeddings_device_ptr(self) -> int:
+        p = C.c_void_p()
+        self._check(self.lib.flowgnn_embeddings_device(self._h, C.byref(p)), "flowgnn_embeddings_device")
+        return int(p.value or 0)
+
+    def set_embeddings_buffer(self, device_ptr: Optional[int]):
+        """Caller-owned device buffer of >= G * embedding_dim floats for the embeddings; None / 0 restores the engine's own."""
+        self._check(self.lib.flowgnn_set_embeddings_buffer(self._h, C.c_void_p(device_ptr) if device_ptr else None),
+                    "flowgnn_set_embeddings_buffer")
 
     # ---- taps
     def set_numeric_mode(self, mode: str = "f32"):
@@ -408,6 +451,15 @@ class EngineGroup:
         out = np.empty(self.num_graphs * self.num_tasks, dtype=np.float32)
         self._check(self.lib.flowgnn_group_get_results(self._h, _pf(out)), "flowgnn_group_get_results")
         return out.reshape(self.num_graphs, self.num_tasks) if self.num_tasks > 1 else out
+
+    def set_embeddings(self, on: bool = True):
+        self._check(self.lib.flowgnn_group_set_embeddings(self._h, 1 if on else 0), "flowgnn_group_set_embeddings")
+
+    def embeddings(self) -> np.ndarray:
+        """[G][embedding_dim(model)] of the last run, in job order (flowgnn.h: flowgnn_group_get_embeddings)."""
+        out = np.empty((self.num_graphs, embedding_dim(self.model)), dtype=np.float32)
+        self._check(self.lib.flowgnn_group_get_embeddings(self._h, _pf(out)), "flowgnn_group_get_embeddings")
+        return out
 
     def forward(self, batch: GraphBatch) -> np.ndarray:
         self.set_batch(batch)

@@ -303,6 +303,43 @@ int flowgnn_results_device(flowgnn_engine* e, void** d_out);
  * affects the runs enqueued after it (a caller alternating two buffers from step to step pays no host synchronisation).
  */
 int flowgnn_set_results_buffer(flowgnn_engine* e, void* device_ptr);
+/*
+ * Graph embeddings: beside the logits, the vector the model's readout head is applied to,
+ *     emb[g][:] = (1 / n_g) * sum over the nodes v of graph g of r[v][:]          (fp32, [num_graphs][flowgnn_embedding_dim(model)])
+ * with r = the rows the readout pools, so that head(emb[g]) is the graph's logit:
+ *     GIN, GIN-VN  h_5, the last layer's output (no ReLU after it)                               100
+ *     GCN          BatchNorm_4(aggregation of x_4), no ReLU                                      100
+ *     GAT          the last layer's output averaged over its 4 heads                              16
+ *     PNA          h_4                                                                            80
+ *     DGN          h_4                                                                           100
+ * and n_g the node count the readout divides by (GIN-VN: the virtual node counts, as in its logit).  A graph's rows are summed in
+ * an order that depends on the graph alone, so embeddings -- like the logits -- are bit-identical under batch order, slices and
+ * group cuts wherever the paragraph above flowgnn_group promises that of the logits.
+ *  flowgnn_embedding_dim: floats per graph (-1: unknown model).  Needs no GPU.
+ *  flowgnn_set_embeddings(e, 1): the runs enqueued after it also produce the embeddings.  Off by default, and off means off: the
+ *     same kernels launch with the same arguments and every result bit is what it was.  On, PNA and DGN run the instance of their
+ *     kernels that also stores the pooled row the readout forms anyway (logits bit-identical to off); GIN / GIN-VN run the
+ *     graph-resident kernel's UN-FOLDED
+ *     instance, which pools h_5 out of on-chip memory -- their logits are then those of the un-folded rule, which differ from the
+ *     default folded ones by fp32 rounding (FLOWGNN_NUMERIC_F16: by the "every other path" rule of that mode, and the embedding is
+ *     the pooled h_5 = f16(W2) f16(hidden) + b2 of that rule); GCN and GAT leave their graph-resident kernels for the per-layer
+ *     path with the un-folded last stage (same rule for their logits), which costs them their on-chip speed: DESIGN.md.
+ *     FLOWGNN_ERR_UNSUPPORTED in FLOWGNN_NUMERIC_Q6_10 (there are no fixed-point embeddings), and flowgnn_set_numeric_mode
+ *     answers the same for that mode while embeddings are on.  Drops a recorded launch sequence (option hipgraph).  Survives
+ *     flowgnn_set_batch.  The <M>_compute_graphs entry points never produce embeddings.
+ *  flowgnn_get_embeddings: copy [num_graphs][dim] to the host (synchronises first, like flowgnn_get_results; an exact-fp32
+ *     re-run refills the embeddings with the logits).  FLOWGNN_ERR_STATE when the last run did not have embeddings on.
+ *  flowgnn_embeddings_device: where the last run put them (same condition); valid until the next flowgnn_set_batch.
+ *  flowgnn_set_embeddings_buffer: redirect them into a caller-owned DEVICE buffer of at least num_graphs * dim floats, as
+ *     flowgnn_set_results_buffer does for the logits; NULL restores the engine's own buffer; reset by flowgnn_set_batch; drops a
+ *     recorded launch sequence.
+ */
+int flowgnn_embedding_dim(int model);
+int flowgnn_set_embeddings(flowgnn_engine* e, int on);
+int flowgnn_get_embeddings(flowgnn_engine* e, float* out_host);
+int flowgnn_embeddings_device(flowgnn_engine* e, void** d_emb);
+int flowgnn_set_embeddings_buffer(flowgnn_engine* e, void* device_ptr);
+
 /* The engine's hipStream_t as an opaque pointer (for event timing by a caller). */
 int flowgnn_stream(flowgnn_engine* e, void** stream);
 
@@ -452,6 +489,9 @@ int flowgnn_group_shards(const flowgnn_group* g, int* cuts /* [size + 1] */);
 int flowgnn_group_run(flowgnn_group* g);
 int flowgnn_group_sync(flowgnn_group* g);
 int flowgnn_group_get_results(flowgnn_group* g, float* out_host);
+/* flowgnn_set_embeddings on every member; flowgnn_group_get_embeddings writes [num_graphs][dim] in job order, like flowgnn_group_get_results. */
+int flowgnn_group_set_embeddings(flowgnn_group* g, int on);
+int flowgnn_group_get_embeddings(flowgnn_group* g, float* out_host);
 /* set_batch + run + get_results for a batch in HOST memory, cut into size x chunks_per_engine ranges; engine i takes ranges
  * i, i + size, ... in turn, so that one engine's copies overlap the others' kernels.  out_host: [num_graphs][NUM_TASK]. */
 int flowgnn_group_compute(flowgnn_group* g, int num_graphs, const int* nums_of_nodes, const int* nums_of_edges,
