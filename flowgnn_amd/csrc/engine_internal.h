@@ -1,0 +1,162 @@
+// engine_internal.h -- what engine.hip, group.hip and entry.hip share beyond the C ABI of include/flowgnn.h.
+#pragma once
+#include "common.h"
+#include "../../include/flowgnn.h"
+#include <functional>
+#include <memory>
+#include <mutex>
+#include <string>
+#include <vector>
+
+namespace fg {
+void set_last_error(const char* what);
+int option_index(const char* key);  // index into the option table of engine.hip, -1: no such option
+// THE place where the library reads its environment (engine.hip)
+void read_environment(std::vector<double>* option_values, std::vector<int>* devices, bool* stale_num_task = nullptr);
+
+// A device buffer (pinned: a pinned host buffer) that only grows.
+struct GrowBuf {
+    void* p = nullptr;
+    size_t cap = 0;  // bytes
+    bool pinned = false;
+    bool holds(size_t bytes) const { return p && bytes <= cap; }
+    // at least `bytes` (never null afterwards); headroom: a regrow takes an eighth more than asked for, for callers whose sizes differ by
+    // a few percent from call to call (the ranges of a cut job)
+    hipError_t reserve(size_t bytes, bool headroom) {
+        if (holds(bytes)) return hipSuccess;
+        release();
+        const size_t want = (bytes ? bytes : 1) + (headroom ? bytes / 8 : 0);
+        const hipError_t he = pinned ? hipHostMalloc(&p, want, hipHostMallocDefault) : hipMalloc(&p, want);
+        if (he == hipSuccess) cap = want; else p = nullptr;
+        return he;
+    }
+    void release() {
+        if (p) (void)(pinned ? hipHostFree(p) : hipFree(p));
+        p = nullptr; cap = 0;
+    }
+};
+}  // namespace fg
+
+struct flowgnn_engine {
+    int model_id = 0;
+    int device = 0;
+    hipStream_t stream = nullptr;      // the stream every launch goes to
+    hipStream_t own_stream = nullptr;  // the engine's own stream (stream == own_stream unless flowgnn_set_stream redirected it)
+    hipStream_t copy_stream = nullptr; // flowgnn_set_batch's host -> device copies: the engine's own queue, not the process's null stream
+    fg::Model* model = nullptr;
+    fg::Options opts;   // defaults <- environment (read once, here) <- flowgnn_set_option
+    fg::Profiler prof;
+    std::string err;
+
+    // resident batch
+    bool batch_ready = false;
+    bool ran = false;
+    int num_tasks = 1;          // NUM_TASK of the readout: results are [G][num_tasks]
+    bool force_exact = false;   // the resident batch tripped the range flag once: run it on the exact kernels
+    int exact_reruns = 0;
+    long long G = 0, N = 0, E = 0;
+    double job_fill = -1.0;            // flowgnn_set_job_tile_fill: the graph-tile fill of the JOB (-1: the batch's own packing decides)
+    long long job_n = -1, job_e = -1;  // flowgnn_set_job_totals: the job the next batches are shards of (-1: each batch is its own job)
+    int max_nodes = 0, max_edges = 0;
+    size_t capG = 0, capN = 0, capE = 0;
+    int *d_nn = nullptr, *d_ne = nullptr, *d_noff = nullptr, *d_eoff = nullptr;
+    int *d_nf = nullptr, *d_el = nullptr, *d_ea = nullptr;
+    float* d_eig = nullptr;
+    int *d_rowptr = nullptr, *d_src = nullptr, *d_eid = nullptr, *d_outdeg = nullptr, *d_gsrc = nullptr, *d_gdst = nullptr,
+        *d_cursor = nullptr, *d_tmp = nullptr, *d_bsums = nullptr, *d_err = nullptr;
+    uint8_t* d_ecode = nullptr;
+    float *d_h0 = nullptr, *d_h1 = nullptr, *d_scratch = nullptr, *d_out = nullptr;
+    fg::GrowBuf tiles;  // GraphTiles::row_start | graph_start in one allocation
+    fg::GrowBuf bp;     // GraphTiles::bp_list | bp_lrow | bp_graph | bp_row in one allocation
+    fg::GrowBuf sub;    // GraphTiles::sub | big_row | big_graph in one allocation
+    fg::GrowBuf h_pack{nullptr, 0, true}, d_pack;  // packed host -> device transfer (h2d_pack.cpp): pinned staging + its device copy
+    bool has_attr = false, has_eig = false;
+    fg::DeviceBatch db{};
+
+    // graph embeddings (flowgnn_set_embeddings): off by default; db.emb is null then and every forward is the one it was
+    bool emb_on = false;
+    int numeric_mode = FLOWGNN_NUMERIC_F32;
+    fg::GrowBuf emb;                // the engine's own [G][dim] buffer (allocated when first needed, outlives the batch)
+    float* emb_user = nullptr;      // flowgnn_set_embeddings_buffer (reset by set_batch)
+    float* emb_last = nullptr;      // where the last flowgnn_run put them (null: it ran with embeddings off)
+    float* emb_target() const { return emb_on ? (emb_user ? emb_user : (float*)emb.p) : nullptr; }
+
+    // hipGraph replay of the launch sequence (index build + forward), opt-in (FLOWGNN_HIPGRAPH=1; 2 = batches of any size).
+    // Measured on this runtime it does not pay: asynchronous launches already pipeline, and a replay of the dozen kernels
+    // of a step is 1-4 % SLOWER than launching them (4 113 molhiv graphs: 0.267 ms plain, 0.271 ms replayed; 512 graphs:
+    // 0.099 vs 0.103 ms) -- so it is off by default and kept for hosts whose launch path is the bottleneck.
+    // The first run of a batch is plain (models size their scratch buffers there), the second is captured, later ones
+    // replay.  Every call that changes what the captured kernels would read or write drops the recording.
+    hipGraphExec_t gexec = nullptr;
+    bool graph_ok = false;
+    bool graph_h_valid = true;   // what the captured forward left in db.h_valid / tap / tap_dim / final_h (host-side outputs)
+    const float* graph_tap = nullptr;
+    int graph_tap_dim = 0, graph_final_h = 0;
+    int plain_runs = 0;
+    int graph_mode = 0;  // option hipgraph
+    long long graph_replays = 0;
+    void drop_graph() {
+        if (gexec) (void)hipGraphExecDestroy(gexec);
+        gexec = nullptr;
+        graph_ok = false;
+        plain_runs = 0;
+    }
+
+    void free_batch() {
+        void* ptrs[] = {d_nn /* base of d_ne, d_noff, d_eoff too */, d_nf, d_el, d_ea, d_eig, d_rowptr, d_src, d_eid, d_outdeg, d_gsrc,
+                        d_gdst, d_cursor, d_tmp, d_bsums, d_ecode, d_h0, d_h1, d_scratch, d_out};
+        for (void* p : ptrs)
+            if (p) (void)hipFree(p);
+        d_nn = d_ne = d_noff = d_eoff = d_nf = d_el = d_ea = nullptr;
+        d_eig = nullptr;
+        d_rowptr = d_src = d_eid = d_outdeg = d_gsrc = d_gdst = d_cursor = d_tmp = d_bsums = nullptr;
+        d_ecode = nullptr;
+        d_h0 = d_h1 = d_scratch = d_out = nullptr;
+        for (fg::GrowBuf* b : {&tiles, &bp, &sub, &h_pack, &d_pack}) b->release();
+        capG = capN = capE = 0;
+    }
+};
+
+#define ENGINE_TRY(e, expr)                                     \
+    do {                                                        \
+        int _rc = (expr);                                       \
+        if (_rc) { (e)->err = fg::last_error_text(); return _rc; } \
+    } while (0)
+
+// HIP call made in an engine context: the failure text goes to the thread-local slot AND to the engine, so
+// flowgnn_last_error(e) always reports the latest failure (never a stale earlier one)
+#define EHIP_TRY(e, expr)                                                   \
+    do {                                                                    \
+        hipError_t _he = (expr);                                            \
+        if (_he != hipSuccess) {                                            \
+            fg::set_hip_error(#expr, _he, __FILE__, __LINE__);              \
+            (e)->err = fg::last_error_text();                               \
+            return FLOWGNN_ERR_HIP;                                         \
+        }                                                                   \
+    } while (0)
+
+// ... and a failed HIP call the caller has a text of its own for: the status to return
+#define EHIP_FAIL(e, what, he) (fg::set_hip_error(what, he, __FILE__, __LINE__), (e)->err = fg::last_error_text(), (int)FLOWGNN_ERR_HIP)
+
+// fill of the model's graph tiles when the graphs are packed greedily in batch order (flowgnn_graph_tile_fill)
+double graph_tile_fill(fg::Model* model, int num_graphs, const int* nums_of_nodes, const int* nums_of_edges);
+// flowgnn_set_batch with copy_mu (flowgnn_group_compute): held around the large host -> device copies only -- one copier per DEVICE at
+// a time, while another engine of the same device packs its next range on the host or plans its tiles
+int set_batch_impl(flowgnn_engine* e, int num_graphs, const int* nums_of_nodes, const int* nums_of_edges, const int* node_feature,
+                   const int* edge_list, const int* edge_attr, const float* node_eigen, std::mutex* copy_mu);
+
+class GroupWorkers;  // group.hip
+struct flowgnn_group {
+    ~flowgnn_group();
+    int model_id = 0;
+    std::unique_ptr<GroupWorkers> workers;
+    std::mutex call_mu;  // one group call at a time (the workers hold one function)
+    std::vector<flowgnn_engine*> eng;
+    std::vector<int> cut;  // [n + 1] graph cuts of the resident batch
+    bool batch_valid = false;  // the engines hold the shards `cut` describes (flowgnn_group_set_batch); flowgnn_group_compute and the
+                               // entry points leave each engine on its LAST range and clear this
+    std::vector<std::unique_ptr<std::mutex>> copy_mu;  // flowgnn_group_compute: one copier per device ...
+    std::vector<int> copy_of;                          // ... engine i uses copy_mu[copy_of[i]] (the first engine on its device)
+    int num_tasks = 1;
+    std::string err;
+};

@@ -1,5 +1,5 @@
 """Host cost of the multi-device group's call path, measured with device 0 listed eight times (round-4 verdict item 6): every engine
-has a persistent host thread (GroupWorkers, engine.hip), so the timed loop of `host --devices` -- flowgnn_group_run back to back --
+has a persistent host thread (GroupWorkers, group.hip), so the timed loop of `host --devices` -- flowgnn_group_run back to back --
 pays no thread creation.  Measured on MI355X (scripts/dev/group_overhead.py): the run call returns in 17-20 us with eight engines
 (6-7 us for one engine), and eight engines sharing ONE GPU finish a 2^18-graph step within 1.5 % of one engine.  The bars below are
 loose on purpose (shared CI boxes): they catch a return to thread-per-call (60-100 us per call) or a serialised group, not noise."""

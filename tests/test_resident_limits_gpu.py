@@ -140,3 +140,33 @@ def test_random_tileable_batches(model, oracle):
             assert np.allclose(got, want, rtol=2e-4, atol=2e-4 * scale), (model, seed, np.abs(got - want).max(), scale)
     finally:
         e.close()
+
+
+def test_batch_tiles_match_the_recorded_plans():
+    """flowgnn_batch_tiles for the batches of tests/golden/tile_plans.npz (tests/test_tile_pack_cpu.py pins the tile lists themselves on
+    the CPU): the engine reports the tile counts those lists imply, under every model's limits and options."""
+    import json
+    import os
+    z = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "tile_plans.npz"))
+    made = {"molhiv": gp.synth_molhiv_batch, "hep": lambda n, seed: gp.synth_hep10k_batch(n, seed=seed, with_eigen=False)}
+    seeds = {"molhiv4113": 1234, "molhiv300": 1, "molhiv1025": 5, "hep2500": 3, "molhiv24000": 7, "molhiv1": 1, "molhiv2": 1}
+    batches, checked = {}, 0
+    for c in json.loads(str(z["cases"])):
+        if c["sub_rows"]:  # the half-tile lists: development builds only
+            continue
+        name = c["input"]
+        if name not in batches:
+            kind = "hep" if name.startswith("hep") else "molhiv"
+            batches[name] = made[kind](int(name[len(kind):]), seed=seeds[name])
+        b = batches[name]
+        if c["model"] == "DGN":  # (its eigenvectors do not enter the packing)
+            b = gp.GraphBatch(b.nums_of_nodes, b.nums_of_edges, b.node_feature, b.edge_list, b.edge_attr, np.zeros((b.total_nodes, 4), np.float32))
+        e = Engine(c["model"], device=0, options=c["options"])
+        try:
+            e.set_batch(b)
+            want = (c["arrays"]["row_start"]["len"] - 1 if c["ok"] else 0, c["arrays"]["bp_graph"]["len"] - 1 if "bp_graph" in c["arrays"] else 0)
+            assert e.batch_tiles() == want, (c["name"], e.batch_tiles(), want)
+            checked += 1
+        finally:
+            e.close()
+    assert checked >= 40
