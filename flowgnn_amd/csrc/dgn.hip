@@ -25,11 +25,22 @@ namespace fg {
 // this translation unit or a pointer tested at run time both cost the default kernel registers (and 0.4 - 1.7 % of its time); this way
 // the default kernel is the code it was.  In that translation unit the host side is left out and the other kernels, with internal linkage and unused, are dropped.
 void launch_dgn_resident_emb(const void* resident_args, int grid, hipStream_t s);  // dgn_emb.hip
-#ifdef FG_RESIDENT_EMB_TU
+// ... and dgn_rows.hip with FG_RESIDENT_ROWS_TU, for dgn_resident_rows_kernel: the instance that also stores every node's h_4 row, in
+// the caller's node order (flowgnn_set_node_embeddings).  That one tests the embeddings pointer at run time, to serve both at once.
+void launch_dgn_resident_rows(const void* resident_args, int grid, hipStream_t s);  // dgn_rows.hip
+#if defined(FG_RESIDENT_EMB_TU) || defined(FG_RESIDENT_ROWS_TU)
+#define FG_RESIDENT_KERNEL_TU 1
 namespace {
+#endif
+#ifdef FG_RESIDENT_EMB_TU
 constexpr bool RESIDENT_EMB = true;
 #else
 constexpr bool RESIDENT_EMB = false;
+#endif
+#ifdef FG_RESIDENT_ROWS_TU
+constexpr bool RESIDENT_ROWS = true;
+#else
+constexpr bool RESIDENT_ROWS = false;
 #endif
 
 constexpr int DGN_D = 100;
@@ -1089,6 +1100,8 @@ struct DgnResidentArgs {
     float* emb;               // [G][100]: the pooled rows the head reads (flowgnn_set_embeddings), or null
     int* range_flag;
     int n_tiles;
+    float* node_emb;          // [N][100]: every node's h_4 row in the caller's node order (flowgnn_set_node_embeddings;
+                              // dgn_resident_rows_kernel stores them), or null.  Last: the other members keep their places
 };
 
 __global__ __launch_bounds__(512, 2) void dgn_resident_kernel(const DgnResidentArgs a) {
@@ -1419,6 +1432,20 @@ __global__ __launch_bounds__(512, 2) void dgn_resident_kernel(const DgnResidentA
                         *reinterpret_cast<float4*>(s_rows + lr * DGN_D + 16 * t + 4 * g) = make_float4(hreg[t].x, hreg[t].y, hreg[t].z, hreg[t].w);
             }
             __syncthreads();  // every row of h_4 is in place
+            if constexpr (RESIDENT_ROWS) {
+                // h_4 of the tile's graphs, as the fp32 rows the pool is about to read (they stay until the barrier that ends the readout).
+                // A graph's rows are contiguous in the tile and in the caller's batch: one contiguous run of float4 stores per graph, dealt
+                // over the whole workgroup (the readout itself occupies five waves).  A bin-packed tile is a list of graphs: the run
+                // starts at node_off[graph], not at t0 + the graph's first row in the tile.  Rows past the tile's end belong to no graph.
+                for (int gl = 0; gl < g1 - g0; gl++) {
+                    int n0, n1;
+                    const int gph = tile_graph_at(gl, n0, n1);
+                    if (n1 > DGN_FT_ROWS) n1 = DGN_FT_ROWS;
+                    float4* dst = reinterpret_cast<float4*>(a.node_emb + (size_t)a.b.node_off[gph] * DGN_D);
+                    const float4* srcr = reinterpret_cast<const float4*>(s_rows + n0 * DGN_D);
+                    for (int i = (int)threadIdx.x; i < (n1 - n0) * DGN_C; i += 512) dst[i] = srcr[i];
+                }
+            }
             constexpr int RW = 5;  // waves that read out (a tile holds two or three graphs; the scratch below has room for five)
             const float* s_head = reinterpret_cast<const float*>(s_w);
             float* s_hg = s_rows + DGN_FT_ROWS * DGN_D + (wave < RW ? wave : 0) * 160;  // behind the rows: [0, 100) pooled row, [100, 150) first hidden layer
@@ -1451,8 +1478,8 @@ __global__ __launch_bounds__(512, 2) void dgn_resident_kernel(const DgnResidentA
                     s_hg[4 * c + 2] = sum.z / n; s_hg[4 * c + 3] = sum.w / n;
                 }
                 __builtin_amdgcn_wave_barrier();
-                if constexpr (RESIDENT_EMB) {  // the pooled row the head is about to read, as it stands in LDS: 25 lanes, one float4 each
-                    if (lane < DGN_C) reinterpret_cast<float4*>(a.emb + (size_t)gph * DGN_D)[lane] = *reinterpret_cast<const float4*>(s_hg + 4 * lane);
+                if constexpr (RESIDENT_EMB || RESIDENT_ROWS) {  // the pooled row the head is about to read, as it stands in LDS: 25 lanes, one float4 each
+                    if ((RESIDENT_EMB || a.emb != nullptr) && lane < DGN_C) reinterpret_cast<float4*>(a.emb + (size_t)gph * DGN_D)[lane] = *reinterpret_cast<const float4*>(s_hg + 4 * lane);
                 }
                 return gph;
             };
@@ -1482,7 +1509,7 @@ __global__ __launch_bounds__(512, 2) void dgn_resident_kernel(const DgnResidentA
 }
 
 // host: W [100][2][100] (out, block, in), b [100] -> DGN_FT_LAYER_BYTES in the feature-major K order of dgn_layer_fused_kernel
-#ifndef FG_RESIDENT_EMB_TU  // (host side: the model's own translation unit only)
+#ifndef FG_RESIDENT_KERNEL_TU  // (host side: the model's own translation unit only)
 static void dgn_pack_fused_layer(const float* W, const float* b, uint8_t* out) {
     std::memset(out, 0, DGN_FT_LAYER_BYTES);
     float m = 0.0f;
@@ -1696,10 +1723,12 @@ public:
         a.head = d_head_;
         a.out = db.out; a.emb = db.emb; a.range_flag = db.range_flag;
         a.n_tiles = n_tiles;
+        a.node_emb = db.node_emb;
         const int grid = n_tiles < 256 ? n_tiles : 256;  // persistent: one 8-wave workgroup per CU (157 KB of LDS)
         {
             ProfScope p(prof, "dgn_resident", s);
-            if (a.emb) launch_dgn_resident_emb(&a, grid, s);  // the same kernel's storing instance (dgn_emb.hip)
+            if (a.node_emb) launch_dgn_resident_rows(&a, grid, s);  // the row-storing instance (dgn_rows.hip), embeddings or not
+            else if (a.emb) launch_dgn_resident_emb(&a, grid, s);  // the same kernel's storing instance (dgn_emb.hip)
             else dgn_resident_kernel<<<grid, 512, 0, s>>>(a);
         }
         db.final_h = 0;
@@ -1739,6 +1768,8 @@ public:
             launch_build_csr(db.b, db.csr, false, db.max_nodes, db.max_edges, s, dupflag_.p);
         }
         for (int l = 0; l < DGN_L; l++) {
+            // (node embeddings: the last layer writes h_4 straight into the caller's buffer, and the readout pools it from there)
+            float* const hn = (l == DGN_L - 1 && db.node_emb) ? db.node_emb : db.h[cur ^ 1];
             if (fused) {
                 ProfScope p(prof, "dgn_layer_fused", s);
                 const int grid = db.gtiles.n_tiles < 256 ? db.gtiles.n_tiles : 256;  // persistent: one 8-wave workgroup per CU (153 KB of LDS)
@@ -1750,14 +1781,14 @@ public:
                     uint32_t* ri = reinterpret_cast<uint32_t*>(rowinfo_.p);
                     const bool stored = direct || l > 0;  // rowinfo of this batch exists: every layer loads it
 #define DGN_MFMA_LAUNCH(I, P)                                                                                                                 \
-    dgn_layer_mfma_kernel<I, P><<<grid, 512, 0, s>>>(db.h[cur], db.h[cur ^ 1], db.csr.row_ptr, db.csr.src, db.csr.out_deg, db.node_eigen,       \
+    dgn_layer_mfma_kernel<I, P><<<grid, 512, 0, s>>>(db.h[cur], hn, db.csr.row_ptr, db.csr.src, db.csr.out_deg, db.node_eigen,       \
                                                      d_fused_ + (size_t)l * DGN_FT_LAYER_BYTES, db.gtiles.row_start, db.gtiles.n_tiles,       \
                                                      db.range_flag, ablate_, ri, reinterpret_cast<const int2*>(ginfo_.p), pool_part_.p,      \
                                                      pool_cnt_.p)
                     // without a stored pass the first layer's launch makes and stores it (adjacency mask, wsum, abssum per row), the
                     // others load it; the last one keeps h' on chip and hands the readout per-wave partial sums (POOL) unless the rows
                     // are asked for
-                    const bool pool = l == DGN_L - 1 && fold_readout_ && !keep_h_ && DGN_L > 1;
+                    const bool pool = l == DGN_L - 1 && fold_readout_ && !keep_h_ && !db.node_emb && DGN_L > 1;
                     if (pool) {
                         if (int rc = ginfo_.reserve((size_t)n * 2)) return rc;
                         if (int rc = pool_part_.reserve((size_t)db.b.num_graphs * 8 * DGN_D)) return rc;
@@ -1771,7 +1802,7 @@ public:
                     cur ^= 1;
                     continue;
                 }
-                dgn_layer_fused_kernel<<<grid, 512, 0, s>>>(db.h[cur], db.h[cur ^ 1], db.csr.row_ptr, db.csr.src, db.csr.out_deg, db.node_eigen,
+                dgn_layer_fused_kernel<<<grid, 512, 0, s>>>(db.h[cur], hn, db.csr.row_ptr, db.csr.src, db.csr.out_deg, db.node_eigen,
                                                             d_fused_ + (size_t)l * DGN_FT_LAYER_BYTES, db.gtiles.row_start, db.gtiles.n_tiles,
                                                             db.range_flag, ablate_);
                 cur ^= 1;
@@ -1787,29 +1818,30 @@ public:
                 if (split_ && !exact_) {
                     const long long wgs = ceil_div_ll(n, 256);
                     dense200_res_relu_split_kernel<DGN_OT><<<(int)(wgs < 256 ? wgs : 256), 1024, 0, s>>>(
-                        db.scratch, db.h[cur], db.h[cur ^ 1], d_split_ + (size_t)l * dense200_split_bytes(DGN_OT), n, DGN_D, db.range_flag);
+                        db.scratch, db.h[cur], hn, d_split_ + (size_t)l * dense200_split_bytes(DGN_OT), n, DGN_D, db.range_flag);
                 } else
-                dgn_dense_kernel<<<(waves + 3) / 4, 256, 0, s>>>(db.scratch, db.h[cur], db.h[cur ^ 1],
+                dgn_dense_kernel<<<(waves + 3) / 4, 256, 0, s>>>(db.scratch, db.h[cur], hn,
                                                                   d_wf_ + (size_t)l * 2 * DGN_OT * 6 * 64 * 4,
                                                                   d_wt_ + (size_t)l * 2 * DGN_OT * 64, d_bp_ + (size_t)l * DGN_OT * 16, n);
             }
             cur ^= 1;
         }
         db.final_h = cur;
-        db.h_valid = !pooled;  // pooled: h[cur] was never written; flowgnn_get_h repeats the pass with the rows kept
+        db.h_valid = !pooled && !db.node_emb;  // pooled: h[cur] was never written; flowgnn_get_h repeats the pass with the rows kept
+        const float* const h4 = db.node_emb ? db.node_emb : db.h[cur];
         {
             ProfScope p(prof, "pool_mlp3", s);
             if (pooled && db.emb)
                 dgn_pool_part_mlp3_kernel<true, true><<<grid_for(db.b.num_graphs, 4, 256 * 4), 256, 0, s>>>(pool_part_.p, pool_cnt_.p, db.b.node_off, d_w0_, d_b0_, d_w1_,
                                                                                                 d_b1_, d_w2_, d_b2_, db.out, db.b.num_graphs, db.emb);
             else if (db.emb)
-                dgn_pool_part_mlp3_kernel<false, true><<<grid_for(db.b.num_graphs, 4, 256 * 4), 256, 0, s>>>(db.h[cur], nullptr, db.b.node_off, d_w0_, d_b0_, d_w1_,
+                dgn_pool_part_mlp3_kernel<false, true><<<grid_for(db.b.num_graphs, 4, 256 * 4), 256, 0, s>>>(h4, nullptr, db.b.node_off, d_w0_, d_b0_, d_w1_,
                                                                                                  d_b1_, d_w2_, d_b2_, db.out, db.b.num_graphs, db.emb);
             else if (pooled)
                 dgn_pool_part_mlp3_kernel<true><<<grid_for(db.b.num_graphs, 4, 256 * 4), 256, 0, s>>>(pool_part_.p, pool_cnt_.p, db.b.node_off, d_w0_, d_b0_, d_w1_,
                                                                                           d_b1_, d_w2_, d_b2_, db.out, db.b.num_graphs);
             else
-                dgn_pool_part_mlp3_kernel<false><<<grid_for(db.b.num_graphs, 4, 256 * 4), 256, 0, s>>>(db.h[cur], nullptr, db.b.node_off, d_w0_, d_b0_, d_w1_,
+                dgn_pool_part_mlp3_kernel<false><<<grid_for(db.b.num_graphs, 4, 256 * 4), 256, 0, s>>>(h4, nullptr, db.b.node_off, d_w0_, d_b0_, d_w1_,
                                                                                            d_b1_, d_w2_, d_b2_, db.out, db.b.num_graphs);
         }
         return 0;
@@ -1891,11 +1923,18 @@ private:
 };
 
 Model* make_dgn_model() { return new DgnModel(); }
-#endif  // FG_RESIDENT_EMB_TU
+#endif  // FG_RESIDENT_KERNEL_TU
 
-#ifdef FG_RESIDENT_EMB_TU
+#ifdef FG_RESIDENT_KERNEL_TU
 }  // namespace
+#endif
+#ifdef FG_RESIDENT_EMB_TU
 void launch_dgn_resident_emb(const void* resident_args, int grid, hipStream_t s) {
+    dgn_resident_kernel<<<grid, 512, 0, s>>>(*static_cast<const DgnResidentArgs*>(resident_args));
+}
+#endif
+#ifdef FG_RESIDENT_ROWS_TU
+void launch_dgn_resident_rows(const void* resident_args, int grid, hipStream_t s) {
     dgn_resident_kernel<<<grid, 512, 0, s>>>(*static_cast<const DgnResidentArgs*>(resident_args));
 }
 #endif

@@ -291,6 +291,19 @@ static int place_embeddings(flowgnn_engine* e) {
     e->db.emb = e->batch_ready ? e->emb_target() : nullptr;
     return FLOWGNN_OK;
 }
+// ... and the same for the node embeddings, [N][dim]
+static int place_node_embeddings(flowgnn_engine* e) {
+    if (e->nemb_on && e->batch_ready && !e->nemb_user) {
+        const size_t need = sizeof(float) * (size_t)e->N * (size_t)flowgnn_embedding_dim(e->model_id);
+        if (!e->nemb.holds(need)) {
+            if (e->stream) EHIP_TRY(e, hipStreamSynchronize(e->stream));
+            if (e->nemb_last == e->nemb.p) e->nemb_last = nullptr;
+            EHIP_TRY(e, e->nemb.reserve(need, false));
+        }
+    }
+    e->db.node_emb = e->batch_ready ? e->nemb_target() : nullptr;
+    return FLOWGNN_OK;
+}
 
 extern "C" {
 
@@ -358,6 +371,7 @@ int flowgnn_destroy(flowgnn_engine* e) {
     e->drop_graph();
     e->free_batch();
     e->emb.release();
+    e->nemb.release();
     if (e->d_err) (void)hipFree(e->d_err);
     delete e->model;
     if (e->own_stream) (void)hipStreamDestroy(e->own_stream);
@@ -663,7 +677,10 @@ static int set_batch_state(flowgnn_engine* e, int num_graphs, const int* nums_of
     e->batch_ready = true;
     e->emb_user = nullptr;
     e->emb_last = nullptr;
-    return place_embeddings(e);
+    e->nemb_user = nullptr;
+    e->nemb_last = nullptr;
+    if (int rc = place_embeddings(e)) return rc;
+    return place_node_embeddings(e);
 }
 
 }  // extern "C"
@@ -792,6 +809,7 @@ int flowgnn_run(flowgnn_engine* e) {
     }
     ENGINE_TRY(e, use_device(e));
     e->emb_last = e->db.emb;
+    e->nemb_last = e->db.node_emb;
     if (e->G == 0) { e->ran = true; return FLOWGNN_OK; }
     const bool want_graph = e->graph_mode != 0 && !e->prof.enabled && (e->graph_mode > 1 || e->N <= (1ll << 20));
     if (want_graph && e->graph_ok) {
@@ -868,11 +886,14 @@ int flowgnn_sync(flowgnn_engine* e) {
         e->drop_graph();  // the captured launches are the split-f16 ones
         EHIP_TRY(e, hipMemsetAsync(e->d_err + 1, 0, sizeof(int), e->stream));
         e->model->set_exact(true);
-        {   // the repeated pass refills what the run filled: the logits, and the embeddings where that run had them on
+        {   // the repeated pass refills what the run filled: the logits, and the embeddings / node embeddings where that run had them on
             float* const now = e->db.emb;
+            float* const nnow = e->db.node_emb;
             e->db.emb = e->emb_last;
+            e->db.node_emb = e->nemb_last;
             const int frc = engine_forward(e);
             e->db.emb = now;
+            e->db.node_emb = nnow;
             ENGINE_TRY(e, frc);
         }
         he = hipStreamSynchronize(e->stream);
@@ -959,6 +980,51 @@ int flowgnn_set_embeddings_buffer(flowgnn_engine* e, void* device_ptr) {
     return place_embeddings(e);
 }
 
+int flowgnn_set_node_embeddings(flowgnn_engine* e, int on) {
+    if (!e) return FLOWGNN_ERR_ARG;
+    if (on && e->numeric_mode == FLOWGNN_NUMERIC_Q6_10) {
+        e->err = "flowgnn_set_node_embeddings: there are no fixed-point node embeddings (FLOWGNN_NUMERIC_Q6_10)";
+        return FLOWGNN_ERR_UNSUPPORTED;
+    }
+    ENGINE_TRY(e, use_device(e));
+    e->drop_graph();  // a recorded launch sequence is that of the other setting
+    e->nemb_on = on != 0;
+    return place_node_embeddings(e);
+}
+
+int flowgnn_get_node_embeddings(flowgnn_engine* e, float* out_host) {
+    if (!e || (!out_host && e->N > 0)) return FLOWGNN_ERR_ARG;
+    if (!e->ran || (!e->nemb_last && e->G > 0) || (e->G == 0 && !e->nemb_on)) {
+        e->err = "flowgnn_get_node_embeddings: the last flowgnn_run did not have node embeddings on (flowgnn_set_node_embeddings)";
+        return FLOWGNN_ERR_STATE;
+    }
+    int rc = flowgnn_sync(e);
+    if (rc) return rc;
+    const size_t bytes = sizeof(float) * (size_t)e->N * (size_t)flowgnn_embedding_dim(e->model_id);
+    if (e->G > 0 && e->N > 0) return d2h_sync(e, out_host, e->nemb_last, bytes, "copy node embeddings");
+    return FLOWGNN_OK;
+}
+
+int flowgnn_node_embeddings_device(flowgnn_engine* e, void** d_rows) {
+    if (!e || !d_rows) return FLOWGNN_ERR_ARG;
+    if (!e->ran || !e->nemb_last) {
+        e->err = "flowgnn_node_embeddings_device: the last flowgnn_run did not have node embeddings on (flowgnn_set_node_embeddings)";
+        return FLOWGNN_ERR_STATE;
+    }
+    *d_rows = e->nemb_last;
+    return FLOWGNN_OK;
+}
+
+int flowgnn_set_node_embeddings_buffer(flowgnn_engine* e, void* device_ptr) {
+    if (!e) return FLOWGNN_ERR_ARG;
+    if (!e->batch_ready) return FLOWGNN_ERR_STATE;
+    // as flowgnn_set_embeddings_buffer: no device synchronisation, the pointer matters to the launches enqueued after this call
+    ENGINE_TRY(e, use_device(e));
+    if (e->gexec) e->drop_graph();
+    e->nemb_user = (float*)device_ptr;
+    return place_node_embeddings(e);
+}
+
 int flowgnn_stream(flowgnn_engine* e, void** stream) {
     if (!e || !stream) return FLOWGNN_ERR_ARG;
     *stream = (void*)e->stream;
@@ -1011,6 +1077,10 @@ int flowgnn_set_numeric_mode(flowgnn_engine* e, int mode) {
     if (!e) return FLOWGNN_ERR_ARG;
     if (mode == FLOWGNN_NUMERIC_Q6_10 && e->emb_on) {
         e->err = "flowgnn_set_numeric_mode: graph embeddings are on, and there are no fixed-point embeddings";
+        return FLOWGNN_ERR_UNSUPPORTED;
+    }
+    if (mode == FLOWGNN_NUMERIC_Q6_10 && e->nemb_on) {
+        e->err = "flowgnn_set_numeric_mode: node embeddings are on, and there are no fixed-point node embeddings";
         return FLOWGNN_ERR_UNSUPPORTED;
     }
     e->drop_graph();
@@ -1069,9 +1139,12 @@ static int ensure_rows(flowgnn_engine* e) {
     e->model->set_keep_h(true);
     e->model->set_exact(e->force_exact);
     float* const emb = e->db.emb;
+    float* const nemb = e->db.node_emb;
     e->db.emb = nullptr;  // a tap's pass leaves the run's embeddings as they are
+    e->db.node_emb = nullptr;
     rc = engine_forward(e);
     e->db.emb = emb;
+    e->db.node_emb = nemb;
     e->model->set_keep_h(false);
     if (rc) { e->err = fg::last_error_text(); return rc; }
     return flowgnn_sync(e);

@@ -80,6 +80,12 @@ struct flowgnn_engine {
     float* emb_user = nullptr;      // flowgnn_set_embeddings_buffer (reset by set_batch)
     float* emb_last = nullptr;      // where the last flowgnn_run put them (null: it ran with embeddings off)
     float* emb_target() const { return emb_on ? (emb_user ? emb_user : (float*)emb.p) : nullptr; }
+    // node embeddings (flowgnn_set_node_embeddings): the same rules, [N][dim]
+    bool nemb_on = false;
+    fg::GrowBuf nemb;
+    float* nemb_user = nullptr;
+    float* nemb_last = nullptr;
+    float* nemb_target() const { return nemb_on ? (nemb_user ? nemb_user : (float*)nemb.p) : nullptr; }
 
     // hipGraph replay of the launch sequence (index build + forward), opt-in (FLOWGNN_HIPGRAPH=1; 2 = batches of any size).
     // Measured on this runtime it does not pay: asynchronous launches already pipeline, and a replay of the dozen kernels

@@ -1042,7 +1042,8 @@ public:
         if (n <= 0) return 0;
         float* skipb[2] = {db.scratch, db.scratch + (size_t)n * GAT_F};
         float* scoreb[2] = {db.scratch + (size_t)n * 2 * GAT_F, db.scratch + (size_t)n * (2 * GAT_F + 8)};
-        float* emb = db.scratch + (size_t)n * (2 * GAT_F + 16);
+        // the 16-wide rows the readout pools: in the model's scratch, or straight in the caller's node-embedding buffer (db.node_emb)
+        float* emb = db.node_emb ? db.node_emb : db.scratch + (size_t)n * (2 * GAT_F + 16);
         int* feat_row = nullptr;
         // gat_reference_quirk=1: node features read without the per-graph offset (GAT_compute.cc:72)
         if (reference_quirk_) {
@@ -1053,7 +1054,8 @@ public:
         // all five layers in one launch when the batch packs into graph tiles (tiles under half full, e.g. graphs of 65..128
         // nodes, waste MFMA columns: the per-layer kernels take those); per-node taps (flowgnn_get_h) come from the per-layer path
         // (graph embeddings, db.emb: the resident kernel never forms the pooled row -- the per-layer path with the un-folded last stage does)
-        if (resident_ && !keep_h_ && !db.emb && fold_readout_ && split_ && !exact_ && db.gtiles.ok && db.gtiles.n_tiles > 0 && db.gtiles.fill >= 0.5) {
+        // (node embeddings, db.node_emb: likewise -- the resident kernel folds the last layer's skip contraction into the readout)
+        if (resident_ && !keep_h_ && !db.emb && !db.node_emb && fold_readout_ && split_ && !exact_ && db.gtiles.ok && db.gtiles.n_tiles > 0 && db.gtiles.fill >= 0.5) {
             GatResidentDev rw;
             rw.layers = d_res_;
             rw.scales = d_scales_;
@@ -1079,7 +1081,7 @@ public:
             ProfScope p(prof, "gat_scores0", s);
             gat_scores0_kernel<<<(n + 255) / 256, 256, 0, s>>>(db.b.node_feature, feat_row, d_lin0_, d_asrc_, d_atgt_, scoreb[0], n);
         }
-        const bool fold = fold_readout_ && !db.emb;  // embeddings pool the `emb` rows themselves
+        const bool fold = fold_readout_ && !db.emb && !db.node_emb;  // embeddings pool the `emb` rows themselves; node embeddings are those rows
         int cur = 0;
         for (int l = 0; l < GAT_L; l++) {
             GatLayerDev w;

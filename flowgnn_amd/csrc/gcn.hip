@@ -21,6 +21,30 @@
 #include <cstring>
 
 namespace fg {
+// gcn_rows.hip compiles this file once more with FG_RESIDENT_ROWS_TU defined, for ONE kernel: gcn_resident_kernel under the name
+// gcn_resident_rows_kernel, the instance that also stores every node's last-layer row, in the caller's node order
+// (flowgnn_set_node_embeddings).  As pna_emb.hip / dgn_emb.hip do it: the default kernel stays the code it was.  In that
+// translation unit the host side is left out and the other kernels, with internal linkage and unused, are dropped.
+// what a launch of the resident kernel takes, for the storing instance in its own translation unit (gcn_rows.hip)
+struct GcnResidentLaunch {
+    bool onepass;
+    int grid;
+    const float* x0; const int* row_ptr; const int* src; const uint8_t* ecode; const int* out_deg;
+    const uint8_t* layers; const float* pool_w; const float* pool_b;
+    const int* tile_row; const int* tile_graph; const int* node_off;
+    float* out; int n_tiles; int* range_flag; int ablate;
+    const uint8_t* desc; const float4* enc_tab; const int* list; const int* lrow;
+    float* node_emb;  // [N][100], caller order
+};
+void launch_gcn_resident_rows(const GcnResidentLaunch& a, hipStream_t s);  // gcn_rows.hip
+#ifdef FG_RESIDENT_ROWS_TU
+namespace {
+constexpr bool RESIDENT_ROWS = true;
+#define GCN_ROWS_PARAM , float* __restrict__ node_emb
+#else
+constexpr bool RESIDENT_ROWS = false;
+#define GCN_ROWS_PARAM
+#endif
 
 constexpr int GCN_D = 100;
 constexpr int GCN_L = 5;
@@ -550,7 +574,13 @@ __global__ __launch_bounds__(GCNR_WAVES * 64, 3) void gcn_resident_kernel(const 
                                                                          const int* __restrict__ node_off, float* __restrict__ out, int n_tiles,
                                                                          int* __restrict__ range_flag, int ablate_arg,
                                                                          const uint8_t* __restrict__ desc, const float4* __restrict__ enc_tab,
-                                                                         const int* __restrict__ list, const int* __restrict__ lrow) {
+                                                                         const int* __restrict__ list, const int* __restrict__ lrow GCN_ROWS_PARAM) {
+#ifndef FG_RESIDENT_ROWS_TU
+    constexpr float* node_emb = nullptr;  // (the storing instance has it as its last argument)
+#endif
+    // RESIDENT_ROWS: the caller-order row of every row of the tile.  A bin-packed tile is a list of graphs, and its rows live in a
+    // tile-ordered row space: row r of the tile is node_off[graph] + (r - the graph's first row inside the tile), not t0 + r.
+    __shared__ int s_grow[RESIDENT_ROWS ? GCNR_ROWS : 1];
     // ONEPASS (the default front end since round 5): no x0 / row_ptr / src / ecode / out_deg -- the tile's CSR slice, out-degrees and
     // encoder row numbers come from gcn_tile_build_kernel's descriptor, and the loader computes the tile's x_0 rows itself from the
     // pre-combined projected table (three 400-B rows per node out of L2 instead of one out of HBM that another launch wrote).
@@ -719,6 +749,14 @@ __global__ __launch_bounds__(GCNR_WAVES * 64, 3) void gcn_resident_kernel(const 
             s_idp1[tid] = 65536.0f / (float)(dpre + 1);  // 2^16 / (deg + 1): the self term arrives scaled by 2^-16 (epilogue below)
         }
         if (tid < 16) { s_cnt[tid] = 0; s_cur[tid] = 0; }
+        if constexpr (RESIDENT_ROWS) {
+            // (its last readers were the previous tile's stores, two barriers ago; read in this tile's last layer)
+            if (list && g0 + tid < g1) {
+                const int gph = list[g0 + tid], lr0 = lrow[g0 + tid];
+                const int nb = node_off[gph], cnt = node_off[gph + 1] - nb;
+                for (int k = 0; k < cnt && lr0 + k < GCNR_ROWS; k++) s_grow[lr0 + k] = nb + k;
+            }
+        }
         if (ONEPASS) issue_idx(has_next ? ntile : tile);  // (its last readers were the previous tile's closing requests, a barrier ago)
         __syncthreads();
         int skey = 15;  // in-degree class of row tid: 0 = longest (>= 14 in-edges) .. 14 = none, 15 = no such row
@@ -914,6 +952,17 @@ __global__ __launch_bounds__(GCNR_WAVES * 64, 3) void gcn_resident_kernel(const 
                     ro_n0 = node_off[ro_g]; ro_n1 = node_off[ro_g + 1];
                     if (list) { const int lr0 = lrow[ro_gi]; ro_n1 = lr0 + t0 + (ro_n1 - ro_n0); ro_n0 = lr0 + t0; }
                 }
+                if constexpr (RESIDENT_ROWS) {
+                    // the node's row as its four lanes hold it: six quads of 16 B (a node's four lanes cover 64 contiguous bytes) and the
+                    // tail column 96 + g, straight from the registers; rows past the tile's end are never stored
+                    if (valid) {
+                        float* dst = node_emb + (size_t)(list ? s_grow[r] : t0 + r) * GCN_D;
+#pragma unroll
+                        for (int q = 0; q < 6; q++)
+                            *reinterpret_cast<float4*>(dst + 16 * q + 4 * g) = make_float4(a[4 * q + 0], a[4 * q + 1], a[4 * q + 2], a[4 * q + 3]);
+                        dst[96 + g] = a[24];
+                    }
+                }
                 // no ReLU after the last BatchNorm; the readout's linear head per node (mean_v(a[v]) . w = mean_v(a[v] . w),
                 // finalize.cc:79-113): 25 terms in the lane, then the node's 4 lanes
                 float part = 0.0f;
@@ -1033,6 +1082,7 @@ __global__ __launch_bounds__(GCNR_WAVES * 64, 3) void gcn_resident_kernel(const 
     }
 }
 
+#ifndef FG_RESIDENT_ROWS_TU  // (host side: the model's own translation unit only)
 class GcnModel : public Model {
 public:
     ~GcnModel() override { free_all(); }
@@ -1235,8 +1285,9 @@ public:
     // x_0 by the encoder, then everything else in one launch when the batch packs into graph tiles (tiles under half full waste MFMA
     // columns: the per-layer kernels take those; so do per-node taps and the multi-task readout)
     bool use_resident(const DeviceBatch& db) const {
-        // (graph embeddings, db.emb: the resident kernel folds the head per node and never forms the pooled row -- the per-layer path does)
-        return resident_ && table_ok_ && !qmode_ && !keep_h_ && !db.emb && split_ && !exact_ && fused_ && num_tasks_ == 1 && db.gtiles.ok && db.gtiles.n_tiles > 0 &&
+        // (graph embeddings, db.emb: the resident kernel folds the head per node and never forms the pooled row -- the per-layer path does;
+        // with node embeddings on as well, db.node_emb, the storing instance leaves the rows in HBM and they are pooled from there)
+        return resident_ && table_ok_ && !qmode_ && !keep_h_ && (!db.emb || db.node_emb) && split_ && !exact_ && fused_ && num_tasks_ == 1 && db.gtiles.ok && db.gtiles.n_tiles > 0 &&
                db.gtiles.fill >= 0.5;
     }
     // the one-pass front end (gcn_tile_build_kernel + the resident kernel's own encoder): the default; gcn_tile_build = 0 restores the
@@ -1267,6 +1318,12 @@ public:
                                                                   bp ? db.gtiles.bp_list : nullptr);
                 }
                 ProfScope p(prof, "gcn_resident", s);
+                if (db.node_emb)  // the same kernel's row-storing instance (gcn_rows.hip)
+                    launch_gcn_resident_rows(GcnResidentLaunch{true, n_tiles < 256 ? n_tiles : 256, nullptr, nullptr, nullptr, nullptr, nullptr, d_res_, d_pw_, d_pb_,
+                                                               t_row, t_graph, db.b.node_off, db.out, n_tiles, db.range_flag, ablate_,
+                                                               reinterpret_cast<const uint8_t*>(desc_.p), reinterpret_cast<const float4*>(d_enc_tab_),
+                                                               bp ? db.gtiles.bp_list : nullptr, bp ? db.gtiles.bp_lrow : nullptr, db.node_emb}, s);
+                else
                 gcn_resident_kernel<true><<<n_tiles < 256 ? n_tiles : 256, GCNR_WAVES * 64, 0, s>>>(
                     nullptr, nullptr, nullptr, nullptr, nullptr, d_res_, d_pw_, d_pb_, t_row, t_graph, db.b.node_off, db.out, n_tiles, db.range_flag,
                     ablate_, reinterpret_cast<const uint8_t*>(desc_.p), reinterpret_cast<const float4*>(d_enc_tab_), bp ? db.gtiles.bp_list : nullptr,
@@ -1277,9 +1334,18 @@ public:
                     atom_encoder_kernel<GCN_D><<<atom_encoder_grid(n, GCN_C), 512, 0, s>>>(db.b.node_feature, d_nemb_proj_, db.h[0], n, db.csr.err);
                 }
                 ProfScope p(prof, "gcn_resident", s);
+                if (db.node_emb)
+                    launch_gcn_resident_rows(GcnResidentLaunch{false, grid, db.h[0], db.csr.row_ptr, db.csr.src, db.csr.ecode, db.csr.out_deg, d_res_, d_pw_, d_pb_,
+                                                               db.gtiles.row_start, db.gtiles.graph_start, db.b.node_off, db.out, db.gtiles.n_tiles,
+                                                               db.range_flag, ablate_, nullptr, nullptr, nullptr, nullptr, db.node_emb}, s);
+                else
                 gcn_resident_kernel<false><<<grid, GCNR_WAVES * 64, 0, s>>>(db.h[0], db.csr.row_ptr, db.csr.src, db.csr.ecode, db.csr.out_deg, d_res_, d_pw_,
                                                                            d_pb_, db.gtiles.row_start, db.gtiles.graph_start, db.b.node_off, db.out,
                                                                            db.gtiles.n_tiles, db.range_flag, ablate_, nullptr, nullptr, nullptr, nullptr);
+            }
+            if (db.emb) {  // (only with db.node_emb: use_resident)
+                ProfScope p(prof, "mean_pool_rows", s);
+                mean_pool_rows_kernel<GCN_D><<<(db.b.num_graphs + 3) / 4, 256, 0, s>>>(db.node_emb, db.b.node_off, db.emb, db.b.num_graphs);
             }
             agg_ready_ = false;
             db.final_h = 0;
@@ -1325,7 +1391,7 @@ public:
         }
         db.final_h = cur;
         db.h_valid = true;
-        if (split_ && !exact_ && fused_ && db.b.e_tot > 0 && num_tasks_ == 1 && !db.emb) {
+        if (split_ && !exact_ && fused_ && db.b.e_tot > 0 && num_tasks_ == 1 && !db.emb && !db.node_emb) {
             // last stage: aggregation + BatchNorm with the readout's linear head folded in (per-node scores in db.scratch;
             // flowgnn_get_h returns x_4 = db.h[final_h], which is untouched by this)
             {
@@ -1340,23 +1406,25 @@ public:
             segment_mean_bias_kernel<0><<<(db.b.num_graphs + 255) / 256, 256, 0, s>>>(db.scratch, db.b.node_off, d_pb_, db.out, db.b.num_graphs);
             return 0;
         }
+        // the rows the readout pools: in the model's scratch, or straight in the caller's node-embedding buffer (db.node_emb)
+        float* const rows = db.node_emb ? db.node_emb : db.scratch;
         {
             ProfScope p(prof, "gcn_aggregate", s);
-            launch_aggregate<false>(db, GCN_L - 1, db.h[cur], db.scratch, s);  // BN_4(...), no ReLU
+            launch_aggregate<false>(db, GCN_L - 1, db.h[cur], rows, s);  // BN_4(...), no ReLU
         }
         {
             ProfScope p(prof, "mean_pool_linear", s);
             if (num_tasks_ > 1) {  // NUM_TASK outputs per graph (linear_input_stationary over [NUM_TASK][100], GCN/src/finalize.cc:79-113)
                 const int blocks = (db.b.num_graphs + 3) / 4;
-                mean_pool_linear_mt_kernel<GCN_D><<<blocks < 512 ? blocks : 512, 256, 0, s>>>(db.scratch, db.b.node_off, d_pw_, d_pb_, db.out,
+                mean_pool_linear_mt_kernel<GCN_D><<<blocks < 512 ? blocks : 512, 256, 0, s>>>(rows, db.b.node_off, d_pw_, d_pb_, db.out,
                                                                                               db.b.num_graphs, num_tasks_);
             } else
-            mean_pool_linear_kernel<GCN_D><<<(db.b.num_graphs + 3) / 4, 256, 0, s>>>(db.scratch, db.b.node_off, d_pw_, d_pb_,
+            mean_pool_linear_kernel<GCN_D><<<(db.b.num_graphs + 3) / 4, 256, 0, s>>>(rows, db.b.node_off, d_pw_, d_pb_,
                                                                                      db.out, db.b.num_graphs);
         }
         if (db.emb) {
             ProfScope p(prof, "mean_pool_rows", s);
-            mean_pool_rows_kernel<GCN_D><<<(db.b.num_graphs + 3) / 4, 256, 0, s>>>(db.scratch, db.b.node_off, db.emb, db.b.num_graphs);
+            mean_pool_rows_kernel<GCN_D><<<(db.b.num_graphs + 3) / 4, 256, 0, s>>>(rows, db.b.node_off, db.emb, db.b.num_graphs);
         }
         return 0;
     }
@@ -1442,5 +1510,20 @@ private:
 };
 
 Model* make_gcn_model() { return new GcnModel(); }
+#endif  // FG_RESIDENT_ROWS_TU
+
+#ifdef FG_RESIDENT_ROWS_TU
+}  // namespace
+void launch_gcn_resident_rows(const GcnResidentLaunch& a, hipStream_t s) {
+    if (a.onepass)
+        gcn_resident_kernel<true><<<a.grid, GCNR_WAVES * 64, 0, s>>>(a.x0, a.row_ptr, a.src, a.ecode, a.out_deg, a.layers, a.pool_w, a.pool_b, a.tile_row,
+                                                                     a.tile_graph, a.node_off, a.out, a.n_tiles, a.range_flag, a.ablate, a.desc, a.enc_tab,
+                                                                     a.list, a.lrow, a.node_emb);
+    else
+        gcn_resident_kernel<false><<<a.grid, GCNR_WAVES * 64, 0, s>>>(a.x0, a.row_ptr, a.src, a.ecode, a.out_deg, a.layers, a.pool_w, a.pool_b, a.tile_row,
+                                                                      a.tile_graph, a.node_off, a.out, a.n_tiles, a.range_flag, a.ablate, a.desc, a.enc_tab,
+                                                                      a.list, a.lrow, a.node_emb);
+}
+#endif
 
 }  // namespace fg

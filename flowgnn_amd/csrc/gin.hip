@@ -792,8 +792,9 @@ public:
         // -1 = default = on (development builds: an explicit gin_pingpong keeps the three-kernel front end -- the ping-pong kernel has no
         // encoder in its loader and is never used with a virtual node).
         const bool want = tile_build_ < 0 ? !(pingpong_ && !virtual_node_ && !f16_) : tile_build_ != 0;
-        // (graph embeddings, db.emb: the un-folded resident instance pools h_5 on chip; it has the three-kernel front end)
-        return want && use_resident(db) && !qmode_ && !keep_h_ && !db.emb && num_tasks_ == 1 && fold_readout_ && head_fold_ && db.b.edge_attr != nullptr;
+        // (graph embeddings, db.emb: the un-folded resident instance pools h_5 on chip; it has the three-kernel front end.  Node
+        // embeddings, db.node_emb: the same instance writes its h_5 rows, batch-order tiles)
+        return want && use_resident(db) && !qmode_ && !keep_h_ && !db.emb && !db.node_emb && num_tasks_ == 1 && fold_readout_ && head_fold_ && db.b.edge_attr != nullptr;
     }
     bool needs_csr(const DeviceBatch& db) const override { return !one_pass(db); }
     // (asked at flowgnn_set_batch, before the batch is known: the lists are built whenever the one-pass path could take them)
@@ -859,32 +860,36 @@ public:
         if (use_resident(db)) {
             // all five layers and the readout in one launch; h_5 rows are written (to h[1]) only for the flowgnn_get_h tap
             if (int rc = perm_.reserve((size_t)db.gtiles.n_tiles * (GIN_RESIDENT_DESC_BYTES / 4))) return rc;
-            const bool rows = keep_h_ || multi;
+            const bool rows = keep_h_ || multi || db.node_emb;
+            // (node embeddings: the rows go straight into the caller's buffer, and whatever reads h_5 behind the launch reads it there)
+            float* const h5 = db.node_emb ? db.node_emb : db.h[1];
             // graph embeddings, single task: the un-folded instance that pools the h_5 rows out of LDS (no row goes to HBM); with the
             // rows in HBM anyway (NUM_TASK > 1, taps) they are pooled from there, behind the launch
             float* pool_emb = rows ? nullptr : db.emb;
             {
                 ProfScope p(prof, "gin_resident", s);
-                launch_gin_resident(db.h[0], rows ? db.h[1] : nullptr, db.csr.row_ptr, db.csr.src, db.csr.ecode, d_ecomb_res_, rsplit(), d_pw_, d_pb_,
+                launch_gin_resident(db.h[0], rows ? h5 : nullptr, db.csr.row_ptr, db.csr.src, db.csr.ecode, d_ecomb_res_, rsplit(), d_pw_, d_pb_,
                                     db.gtiles.row_start, db.gtiles.graph_start, reinterpret_cast<uint8_t*>(perm_.p), db.b.node_off,
                                     multi ? nullptr : db.out, db.gtiles.n_tiles, db.range_flag, s, virtual_node_,
                                     (!rows && fold_readout_ && head_fold_) ? head() : nullptr, resident_order_, resident_prof_, nullptr, 1, f16_, pool_emb);
             }
             db.final_h = rows ? 1 : 0;
-            db.h_valid = rows;
-            if (multi) launch_readout_mt(db, db.h[1], prof, s);
-            if (rows) launch_pool_rows(db, db.h[1], prof, s);
+            db.h_valid = rows && !db.node_emb;
+            if (multi) launch_readout_mt(db, h5, prof, s);
+            if (rows) launch_pool_rows(db, h5, prof, s);
             return 0;
         }
         int cur = 0;
         bool folded = false;
         for (int l = 0; l < GIN_L; l++) {
+            // (node embeddings: the last layer writes h_5 straight into the caller's buffer, and the readout reads it there)
+            float* const hn = (l == GIN_L - 1 && db.node_emb) ? db.node_emb : db.h[cur ^ 1];
             if (fused_ && split_ && !exact_) {
                 ProfScope p(prof, "gin_layer_fused", s);
                 // last layer: the readout's per-node dot product h'[v] . w_pred is taken in the epilogue and only that
                 // leaves the kernel (db.scratch as float[n]); the rows are written only for the flowgnn_get_h tap
-                const bool fold = l == GIN_L - 1 && fold_readout_ && !keep_h_ && !multi && !db.emb;
-                launch_gin_layer_split(db.h[cur], fold ? db.scratch : db.h[cur ^ 1], db.csr.row_ptr, db.csr.src, db.csr.ecode,
+                const bool fold = l == GIN_L - 1 && fold_readout_ && !keep_h_ && !multi && !db.emb && !db.node_emb;
+                launch_gin_layer_split(db.h[cur], fold ? db.scratch : hn, db.csr.row_ptr, db.csr.src, db.csr.ecode,
                                        layer_dev(l).ecomb, (f16_ ? d_split16_ : d_split_) + (size_t)l * GS_LAYER_BYTES, n, db.b.e_tot,
                                        l != GIN_L - 1, db.range_flag, split_nt_, s, fold ? d_pw_ : nullptr, f16_);
                 if (fold) {
@@ -899,7 +904,7 @@ public:
                 constexpr int NT = 1;
                 const int blocks = (int)ceil_div_ll(n, 64 * NT);
                 gin_layer_fused_kernel<NT><<<blocks, 256, 0, s>>>(
-                    db.h[cur], db.h[cur ^ 1], db.csr.row_ptr, db.csr.src, db.csr.ecode, layer_dev(l).ecomb,
+                    db.h[cur], hn, db.csr.row_ptr, db.csr.src, db.csr.ecode, layer_dev(l).ecomb,
                     d_chunks_ + (size_t)l * GIN_CHUNKS * GIN_CHUNK_FLOATS, n, l != GIN_L - 1);
                 cur ^= 1;
                 continue;
@@ -912,16 +917,17 @@ public:
                 ProfScope p(prof, "gin_mlp", s);
                 constexpr int NT = 2;
                 const int waves = (int)ceil_div_ll(n, 16 * NT);
-                gin_mlp_kernel<NT><<<(waves + 3) / 4, 256, 0, s>>>(db.scratch, db.h[cur ^ 1], layer_dev(l), n,
+                gin_mlp_kernel<NT><<<(waves + 3) / 4, 256, 0, s>>>(db.scratch, hn, layer_dev(l), n,
                                                                      l != GIN_L - 1);
             }
             cur ^= 1;
         }
         db.final_h = cur;
-        db.h_valid = !folded;
-        if (!folded) launch_pool_rows(db, db.h[cur], prof, s);
+        db.h_valid = !folded && !db.node_emb;
+        const float* const h5 = db.node_emb ? db.node_emb : db.h[cur];
+        if (!folded) launch_pool_rows(db, h5, prof, s);
         if (multi) {
-            launch_readout_mt(db, db.h[cur], prof, s);
+            launch_readout_mt(db, h5, prof, s);
             return 0;
         }
         {
@@ -930,7 +936,7 @@ public:
                 segment_mean_bias_kernel<0><<<(db.b.num_graphs + 255) / 256, 256, 0, s>>>(db.scratch, db.b.node_off, d_pb_, db.out,
                                                                                        db.b.num_graphs);
             else
-                mean_pool_linear_kernel<GIN_D><<<(db.b.num_graphs + 3) / 4, 256, 0, s>>>(db.h[cur], db.b.node_off, d_pw_, d_pb_,
+                mean_pool_linear_kernel<GIN_D><<<(db.b.num_graphs + 3) / 4, 256, 0, s>>>(h5, db.b.node_off, d_pw_, d_pb_,
                                                                                          db.out, db.b.num_graphs);
         }
         return 0;

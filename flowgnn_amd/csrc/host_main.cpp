@@ -76,13 +76,13 @@ static bool read_eig_txt(const std::string& path, std::vector<float>& eig, size_
 int main(int argc, char** argv) {
     if (argc < 2) {
         fprintf(stderr, "Usage: %s <GIN|GIN-VN|GCN|GAT|PNA|DGN> [--graphs DIR] [--weights DIR] [--num-graphs N] [--trials T] "
-                        "[--out FILE] [--embeddings FILE] [--device D | --devices D0,D1,..] [--option key=value] [--numeric f32|q6.10|f16] [--num-tasks T] [XCLBIN File]\n", argv[0]);
+                        "[--out FILE] [--embeddings FILE] [--node-embeddings FILE] [--device D | --devices D0,D1,..] [--option key=value] [--numeric f32|q6.10|f16] [--num-tasks T] [XCLBIN File]\n", argv[0]);
         return EXIT_FAILURE;
     }
     const std::string model = argv[1];
     const int mid = model_id(model);
     if (mid < 0) { fprintf(stderr, "unknown model %s\n", model.c_str()); return EXIT_FAILURE; }
-    std::string graphs = "../graphs", wdir = ".", out_path = "HLS_output.txt", eig_dir = "eig", emb_path;
+    std::string graphs = "../graphs", wdir = ".", out_path = "HLS_output.txt", eig_dir = "eig", emb_path, nemb_path;
     long num_graphs = -1;
     int trials = 25, numeric = FLOWGNN_NUMERIC_F32, num_tasks = 1;
     std::vector<int> devices;
@@ -99,6 +99,7 @@ int main(int argc, char** argv) {
         else if (a == "--num-graphs") num_graphs = atol(next("--num-graphs"));
         else if (a == "--trials") trials = atoi(next("--trials"));
         else if (a == "--out") out_path = next("--out");
+        else if (a == "--node-embeddings") nemb_path = next("--node-embeddings");  // the rows that pool is taken over, one line of dim values per node
         else if (a == "--embeddings") emb_path = next("--embeddings");  // the per-graph pooled embeddings, one line of dim values per graph
         else if (a == "--device") { devices.clear(); devices.push_back(atoi(next("--device"))); }
         else if (a == "--devices") {  // e.g. 0,1,2,3,4,5,6,7: the batch is cut by sum(N + E), one engine + host thread per device
@@ -232,6 +233,22 @@ int main(int argc, char** argv) {
         for (long g = 0; g < num_graphs; g++)
             for (int d = 0; d < dim; d++) fprintf(ef, d + 1 < dim ? "%.8f " : "%.8f\n", emb[(size_t)g * dim + d]);
         fclose(ef);
+    }
+    if (!nemb_path.empty()) {
+        // likewise one more run, with node embeddings on (and graph embeddings off again)
+        const int dim = flowgnn_embedding_dim(mid);
+        const size_t n_tot = N;
+        std::vector<float> rows(n_tot * dim);
+        rc = flowgnn_group_set_embeddings(eng, 0);
+        if (!rc) rc = flowgnn_group_set_node_embeddings(eng, 1);
+        if (!rc) rc = flowgnn_group_run(eng);
+        if (!rc) rc = flowgnn_group_get_node_embeddings(eng, rows.data());
+        if (rc) { fprintf(stderr, "--node-embeddings: %d %s\n", rc, flowgnn_group_last_error(eng)); return EXIT_FAILURE; }
+        FILE* nf = fopen(nemb_path.c_str(), "w");
+        if (!nf) { fprintf(stderr, "cannot write %s\n", nemb_path.c_str()); return EXIT_FAILURE; }
+        for (size_t v = 0; v < n_tot; v++)
+            for (int d = 0; d < dim; d++) fprintf(nf, d + 1 < dim ? "%.8f " : "%.8f\n", rows[v * dim + d]);
+        fclose(nf);
     }
     flowgnn_group_destroy(eng);
     return 0;

@@ -27,11 +27,22 @@ namespace fg {
 // this translation unit or a pointer tested at run time both cost the default kernel registers (and 0.4 - 1.7 % of its time); this way
 // the default kernel is the code it was.  In that translation unit the host side is left out and the other kernels, with internal linkage and unused, are dropped.
 void launch_pna_resident_emb(const void* resident_args, int grid, hipStream_t s);  // pna_emb.hip
-#ifdef FG_RESIDENT_EMB_TU
+// ... and pna_rows.hip with FG_RESIDENT_ROWS_TU, for pna_resident_rows_kernel: the instance that also stores every node's h_4 row, in
+// the caller's node order (flowgnn_set_node_embeddings).  That one tests the embeddings pointer at run time, to serve both at once.
+void launch_pna_resident_rows(const void* resident_args, int grid, hipStream_t s);  // pna_rows.hip
+#if defined(FG_RESIDENT_EMB_TU) || defined(FG_RESIDENT_ROWS_TU)
+#define FG_RESIDENT_KERNEL_TU 1
 namespace {
+#endif
+#ifdef FG_RESIDENT_EMB_TU
 constexpr bool RESIDENT_EMB = true;
 #else
 constexpr bool RESIDENT_EMB = false;
+#endif
+#ifdef FG_RESIDENT_ROWS_TU
+constexpr bool RESIDENT_ROWS = true;
+#else
+constexpr bool RESIDENT_ROWS = false;
 #endif
 
 constexpr int PNA_D = 80;
@@ -808,6 +819,8 @@ struct PnaResidentArgs {
     float avg_deg;
     float oscale[PNA_L];
     int n_tiles;
+    float* node_emb;           // [N][80]: every node's h_4 row in the caller's node order (flowgnn_set_node_embeddings;
+                               // pna_resident_rows_kernel stores them), or null.  Last: the other members keep their places
 };
 
 // development only (-DFLOWGNN_DEV -DPNAR_TIMING=<bits>, scripts/dev/variant.sh): TIMING variants that leave a phase out and compute wrong
@@ -941,6 +954,23 @@ __global__ __launch_bounds__(PNA_FT_WAVES * 64, 4) void pna_resident_kernel(cons
             }
             __syncthreads();  // h' of every row is in place
         }
+        if constexpr (RESIDENT_ROWS) {
+            // h_4 of the tile's graphs, out of the LDS tile (the last epilogue's barrier is behind us; nothing writes the rows before the
+            // barrier that ends the readout).  A graph's rows are contiguous in the tile and in the caller's batch, so every graph is
+            // one contiguous run of float4 stores, dealt over the whole workgroup.  A bin-packed tile is a list of graphs: the run
+            // starts at node_off[graph], not at t0 + the graph's first row in the tile.  Rows past the tile's end belong to no graph.
+            const int g0 = a.tile_graph[tile], g1 = a.tile_graph[tile + 1];
+            for (int gp = g0; gp < g1; gp++) {
+                const int gi = a.list ? a.list[gp] : gp;
+                const int nb = a.node_off[gi], cnt = a.node_off[gi + 1] - nb;
+                const int n0 = a.list ? a.lrow[gp] : nb - t0;
+                float4* dst = reinterpret_cast<float4*>(a.node_emb + (size_t)nb * PNA_D);
+                for (int i = (int)threadIdx.x; i < cnt * PNA_C; i += PNA_FT_WAVES * 64) {
+                    const int v = i / PNA_C, c = i - v * PNA_C;
+                    if (n0 + v < PNA_FT_ROWS) dst[i] = *reinterpret_cast<const float4*>(s_h + (n0 + v) * PNA_FT_STRIDE + 4 * c);
+                }
+            }
+        }
         if (PNAR_SKIP(2)) {
             if (threadIdx.x == 0) a.out[a.list ? a.list[a.tile_graph[tile]] : a.tile_graph[tile]] = s_h[0];
         } else {   // ---- readout: one wave per graph of the tile (pool_mlp3_kernel's association)
@@ -966,8 +996,8 @@ __global__ __launch_bounds__(PNA_FT_WAVES * 64, 4) void pna_resident_kernel(cons
                     s_hg[4 * c + 2] = acc.z / n; s_hg[4 * c + 3] = acc.w / n;
                 }
                 __builtin_amdgcn_wave_barrier();
-                if constexpr (RESIDENT_EMB) {  // the pooled row the head is about to read, as it stands in LDS: twenty lanes, one float4 each
-                    if (lane < PNA_C) reinterpret_cast<float4*>(a.emb + (size_t)gi * PNA_D)[lane] = *reinterpret_cast<const float4*>(s_hg + 4 * lane);
+                if constexpr (RESIDENT_EMB || RESIDENT_ROWS) {  // the pooled row the head is about to read, as it stands in LDS: twenty lanes, one float4 each
+                    if ((RESIDENT_EMB || a.emb != nullptr) && lane < PNA_C) reinterpret_cast<float4*>(a.emb + (size_t)gi * PNA_D)[lane] = *reinterpret_cast<const float4*>(s_hg + 4 * lane);
                 }
                 if (lane < 40) {
                     float s = a.b1[lane];
@@ -1000,7 +1030,7 @@ __global__ __launch_bounds__(PNA_FT_WAVES * 64, 4) void pna_resident_kernel(cons
 // host: conv_w of one layer [80][3][4][80] -> the FEATURE-major weight stream of pna_layer_fused_kernel (same chunk geometry as
 // pna_pack_split_layer: chunk ks = fragments of the 15 (scaler, output tile) pairs, hi then lo, 1 KiB each); K-slot e of lane
 // group gk in K-step ks is (feature 8 ks + 2 gk + (e >> 2), aggregator e & 3).  The scale is the one pna_pack_split_layer returns.
-#ifndef FG_RESIDENT_EMB_TU  // (host side: the model's own translation unit only)
+#ifndef FG_RESIDENT_KERNEL_TU  // (host side: the model's own translation unit only)
 static void pna_pack_stream_layer(const float* cw, uint8_t* out) {
     float m = 0.0f;
     for (size_t i = 0; i < (size_t)PNA_D * PNA_NS * PNA_NA * PNA_D; i++) m = std::fmax(m, std::fabs(cw[i]));
@@ -1190,10 +1220,12 @@ public:
         a.avg_deg = avg_deg_;
         for (int l = 0; l < PNA_L; l++) a.oscale[l] = oscale_[l];
         a.n_tiles = n_tiles;
+        a.node_emb = db.node_emb;
         const int grid = n_tiles < 256 ? n_tiles : 256;  // persistent: one 16-wave workgroup per CU
         {
             ProfScope p(prof, "pna_resident", s);
-            if (a.emb) launch_pna_resident_emb(&a, grid, s);  // the same kernel's storing instance (pna_emb.hip)
+            if (a.node_emb) launch_pna_resident_rows(&a, grid, s);  // the row-storing instance (pna_rows.hip), embeddings or not
+            else if (a.emb) launch_pna_resident_emb(&a, grid, s);  // the same kernel's storing instance (pna_emb.hip)
             else pna_resident_kernel<<<grid, PNA_FT_WAVES * 64, 0, s>>>(a);
         }
         db.final_h = 0;
@@ -1216,6 +1248,8 @@ public:
         int cur = 0;
         const bool fused = use_fused(db);
         for (int l = 0; l < PNA_L; l++) {
+            // (node embeddings: the last layer writes h_4 straight into the caller's buffer, and the readout pools it from there)
+            float* const hn = (l == PNA_L - 1 && db.node_emb) ? db.node_emb : db.h[cur ^ 1];
             if (fused) {
                 ProfScope p(prof, "pna_layer_fused", s);
                 const int grid = db.gtiles.n_tiles < 256 ? db.gtiles.n_tiles : 256;  // persistent: one 16-wave workgroup per CU (151 KB of LDS)
@@ -1224,7 +1258,7 @@ public:
                     pna_tile_desc_kernel<<<db.gtiles.n_tiles, 256, 0, s>>>(db.csr.row_ptr, db.csr.src, db.csr.out_deg, db.gtiles.row_start,
                                                                           reinterpret_cast<uint8_t*>(desc_.p), db.gtiles.n_tiles);
                 }
-                pna_layer_fused_kernel<<<grid, PNA_FT_WAVES * 64, 0, s>>>(db.h[cur], db.h[cur ^ 1], reinterpret_cast<const uint8_t*>(desc_.p), db.csr.out_deg,
+                pna_layer_fused_kernel<<<grid, PNA_FT_WAVES * 64, 0, s>>>(db.h[cur], hn, reinterpret_cast<const uint8_t*>(desc_.p), db.csr.out_deg,
                                                             d_stream_ + (size_t)l * PNA_SPLIT_LAYER_BYTES, d_cb_ + (size_t)l * PNA_D, avg_deg_,
                                                             oscale_[l], db.gtiles.row_start, db.gtiles.n_tiles, db.range_flag,
                                                             ablate_, prof_buf(grid, l));
@@ -1239,25 +1273,27 @@ public:
                 ProfScope p(prof, "pna_dense", s);
                 const int waves = (int)ceil_div_ll(n, 16);
                 if (split_ && !exact_) {
-                    pna_dense_split_kernel<<<(int)ceil_div_ll(n, 128), 512, 0, s>>>(db.scratch, db.h[cur], db.h[cur ^ 1], db.csr.out_deg,
+                    pna_dense_split_kernel<<<(int)ceil_div_ll(n, 128), 512, 0, s>>>(db.scratch, db.h[cur], hn, db.csr.out_deg,
                                                                                     d_split_ + (size_t)l * PNA_SPLIT_LAYER_BYTES,
                                                                                     d_cb_ + (size_t)l * PNA_D, avg_deg_, oscale_[l], n,
                                                                                     db.range_flag);
                 } else
-                pna_dense_kernel<<<(waves + 3) / 4, 256, 0, s>>>(db.scratch, db.h[cur], db.h[cur ^ 1], db.csr.out_deg,
+                pna_dense_kernel<<<(waves + 3) / 4, 256, 0, s>>>(db.scratch, db.h[cur], hn, db.csr.out_deg,
                                                                   d_wf_ + (size_t)l * PNA_NS * PNA_OT * PNA_NA * 5 * 64 * 4,
                                                                   d_cb_ + (size_t)l * PNA_D, avg_deg_, n);
             }
             cur ^= 1;
         }
         db.final_h = cur;
+        const float* const h4 = db.node_emb ? db.node_emb : db.h[cur];
+        db.h_valid = !db.node_emb;  // (a tap repeats the pass with the rows in h[])
         {
             ProfScope p(prof, "pool_mlp3", s);
             if (db.emb)
-                pool_mlp3_kernel<PNA_D, 40, 20, true><<<(db.b.num_graphs + 3) / 4, 256, 0, s>>>(db.h[cur], db.b.node_off, d_w1_, d_b1_, d_w2_, d_b2_,
+                pool_mlp3_kernel<PNA_D, 40, 20, true><<<(db.b.num_graphs + 3) / 4, 256, 0, s>>>(h4, db.b.node_off, d_w1_, d_b1_, d_w2_, d_b2_,
                                                                                                 d_w3_, d_b3_, db.out, db.b.num_graphs, db.emb);
             else
-            pool_mlp3_kernel<PNA_D, 40, 20><<<(db.b.num_graphs + 3) / 4, 256, 0, s>>>(db.h[cur], db.b.node_off, d_w1_, d_b1_, d_w2_,
+            pool_mlp3_kernel<PNA_D, 40, 20><<<(db.b.num_graphs + 3) / 4, 256, 0, s>>>(h4, db.b.node_off, d_w1_, d_b1_, d_w2_,
                                                                                       d_b2_, d_w3_, d_b3_, db.out, db.b.num_graphs);
         }
         return 0;
@@ -1356,11 +1392,18 @@ private:
 };
 
 Model* make_pna_model() { return new PnaModel(); }
-#endif  // FG_RESIDENT_EMB_TU
+#endif  // FG_RESIDENT_KERNEL_TU
 
-#ifdef FG_RESIDENT_EMB_TU
+#ifdef FG_RESIDENT_KERNEL_TU
 }  // namespace
+#endif
+#ifdef FG_RESIDENT_EMB_TU
 void launch_pna_resident_emb(const void* resident_args, int grid, hipStream_t s) {
+    pna_resident_kernel<<<grid, PNA_FT_WAVES * 64, 0, s>>>(*static_cast<const PnaResidentArgs*>(resident_args));
+}
+#endif
+#ifdef FG_RESIDENT_ROWS_TU
+void launch_pna_resident_rows(const void* resident_args, int grid, hipStream_t s) {
     pna_resident_kernel<<<grid, PNA_FT_WAVES * 64, 0, s>>>(*static_cast<const PnaResidentArgs*>(resident_args));
 }
 #endif

@@ -95,6 +95,7 @@ class Engine:
             self._h = C.c_void_p()
         self._results_tensor = None  # (forward_device's output: released once the engine, and its stream, are gone)
         self._embeddings_tensor = None
+        self._node_embeddings_tensor = None
 
     def __del__(self):
         try:
@@ -232,12 +233,16 @@ class Engine:
             if t is not None:
                 t.record_stream(cur)
 
-    def forward_device(self, x, edge_index, edge_attr=None, node_eigen=None, *, ptr, nums_of_edges=None, return_embeddings=False):
+    def forward_device(self, x, edge_index, edge_attr=None, node_eigen=None, *, ptr, nums_of_edges=None, return_embeddings=False,
+                       return_node_embeddings=False):
         """set_batch_device, then one forward into a new torch tensor on the device ([G], or [G][num_tasks]); torch's current stream
         waits for the engine's, the host does not.  Validation errors (and the range check that can repeat a pass on the exact
         kernels) are seen by sync(), which raises; without it the tensor of a refused batch holds whatever the kernels wrote.
         return_embeddings: (logits, embeddings), the graph embeddings ([G][embedding_dim]) in a new device tensor as well, written
-        by the kernels themselves (flowgnn_set_embeddings_buffer); embeddings stay on for later runs (set_embeddings(False) ends it)."""
+        by the kernels themselves (flowgnn_set_embeddings_buffer); embeddings stay on for later runs (set_embeddings(False) ends it).
+        return_node_embeddings: the node embeddings ([N][embedding_dim], in the order of the rows of x, i.e. of the PyG Batch's nodes)
+        in a new device tensor, appended to the returned tuple; written by the kernels themselves
+        (flowgnn_set_node_embeddings_buffer), and on for later runs until set_node_embeddings(False)."""
         import torch
         dev = torch.device("cuda", self.device)
         cur = torch.cuda.current_stream(dev)
@@ -247,6 +252,10 @@ class Engine:
         if return_embeddings:
             emb = torch.empty((G, embedding_dim(self.model)), dtype=torch.float32, device=dev)
             self.set_embeddings(True)
+        rows = None
+        if return_node_embeddings:
+            rows = torch.empty((int(x.shape[0]), embedding_dim(self.model)), dtype=torch.float32, device=dev)
+            self.set_node_embeddings(True)
         self.set_batch_device(x, edge_index, edge_attr, node_eigen, ptr=ptr, nums_of_edges=nums_of_edges)
         es = torch.cuda.ExternalStream(self.stream_handle(), device=dev)
         if G:
@@ -255,10 +264,14 @@ class Engine:
             if emb is not None:
                 self.set_embeddings_buffer(emb.data_ptr())
                 self._embeddings_tensor = emb
+            if rows is not None:
+                self.set_node_embeddings_buffer(rows.data_ptr())
+                self._node_embeddings_tensor = rows
         self.run()
         cur.wait_stream(es)
         logits = out.view(G, self.num_tasks) if self.num_tasks > 1 else out
-        return (logits, emb) if return_embeddings else logits
+        ret = (logits,) + ((emb,) if return_embeddings else ()) + ((rows,) if return_node_embeddings else ())
+        return ret if len(ret) > 1 else logits
 
     def run(self):
         self._check(self.lib.flowgnn_run(self._h), "flowgnn_run")
@@ -284,13 +297,17 @@ class Engine:
     def set_results_buffer(self, device_ptr: int):
         self._check(self.lib.flowgnn_set_results_buffer(self._h, C.c_void_p(device_ptr)), "flowgnn_set_results_buffer")
 
-    def forward(self, batch: GraphBatch, return_embeddings: bool = False):
-        """set_batch + run + results; return_embeddings: (logits, embeddings) -- embeddings stay on for later runs."""
+    def forward(self, batch: GraphBatch, return_embeddings: bool = False, return_node_embeddings: bool = False):
+        """set_batch + run + results; return_embeddings: (logits, embeddings) -- embeddings stay on for later runs;
+        return_node_embeddings: the node embeddings [N][embedding_dim] appended to the tuple (they stay on likewise)."""
         if return_embeddings:
             self.set_embeddings(True)
+        if return_node_embeddings:
+            self.set_node_embeddings(True)
         self.set_batch(batch)
         self.run()
-        return (self.results(), self.embeddings()) if return_embeddings else self.results()
+        ret = (self.results(),) + ((self.embeddings(),) if return_embeddings else ()) + ((self.node_embeddings(),) if return_node_embeddings else ())
+        return ret if len(ret) > 1 else ret[0]
 
     # ---- graph embeddings (flowgnn.h: flowgnn_set_embeddings)
     def set_embeddings(self, on: bool = True):
@@ -312,6 +329,27 @@ class Engine:
         """Caller-owned device buffer of >= G * embedding_dim floats for the embeddings; None / 0 restores the engine's own."""
         self._check(self.lib.flowgnn_set_embeddings_buffer(self._h, C.c_void_p(device_ptr) if device_ptr else None),
                     "flowgnn_set_embeddings_buffer")
+
+    # ---- node embeddings (flowgnn.h: flowgnn_set_node_embeddings)
+    def set_node_embeddings(self, on: bool = True):
+        """Runs enqueued after this also store, per node and in the caller's node order, the row the readout pools."""
+        self._check(self.lib.flowgnn_set_node_embeddings(self._h, 1 if on else 0), "flowgnn_set_node_embeddings")
+
+    def node_embeddings(self) -> np.ndarray:
+        """[N][embedding_dim(model)] of the last run (synchronises); FLOWGNN_ERR_STATE if that run had node embeddings off."""
+        out = np.empty((self.total_nodes, embedding_dim(self.model)), dtype=np.float32)
+        self._check(self.lib.flowgnn_get_node_embeddings(self._h, _pf(out)), "flowgnn_get_node_embeddings")
+        return out
+
+    def node_embeddings_device_ptr(self) -> int:
+        p = C.c_void_p()
+        self._check(self.lib.flowgnn_node_embeddings_device(self._h, C.byref(p)), "flowgnn_node_embeddings_device")
+        return int(p.value or 0)
+
+    def set_node_embeddings_buffer(self, device_ptr: Optional[int]):
+        """Caller-owned device buffer of >= N * embedding_dim floats for the node embeddings; None / 0 restores the engine's own."""
+        self._check(self.lib.flowgnn_set_node_embeddings_buffer(self._h, C.c_void_p(device_ptr) if device_ptr else None),
+                    "flowgnn_set_node_embeddings_buffer")
 
     # ---- taps
     def set_numeric_mode(self, mode: str = "f32"):
@@ -395,6 +433,7 @@ class EngineGroup:
             raise FlowGNNError(rc, "flowgnn_create_multi")
         self.num_tasks = 1
         self.num_graphs = 0
+        self.total_nodes = 0
         for k, v in (options or {}).items():
             self._check(self.lib.flowgnn_group_set_option(self._h, k.encode(), option_value(v)), f"flowgnn_group_set_option({k})")
 
@@ -435,6 +474,7 @@ class EngineGroup:
         self._check(self.lib.flowgnn_group_set_batch(self._h, batch.num_graphs, _pi(nn), _pi(ne), _pi(nf), _pi(el), _pi(ea), _pf(eig)),
                     "flowgnn_group_set_batch")
         self.num_graphs = batch.num_graphs
+        self.total_nodes = batch.total_nodes
 
     def shards(self):
         cuts = np.zeros(len(self.devices) + 1, dtype=np.int32)
@@ -459,6 +499,15 @@ class EngineGroup:
         """[G][embedding_dim(model)] of the last run, in job order (flowgnn.h: flowgnn_group_get_embeddings)."""
         out = np.empty((self.num_graphs, embedding_dim(self.model)), dtype=np.float32)
         self._check(self.lib.flowgnn_group_get_embeddings(self._h, _pf(out)), "flowgnn_group_get_embeddings")
+        return out
+
+    def set_node_embeddings(self, on: bool = True):
+        self._check(self.lib.flowgnn_group_set_node_embeddings(self._h, 1 if on else 0), "flowgnn_group_set_node_embeddings")
+
+    def node_embeddings(self) -> np.ndarray:
+        """[N][embedding_dim(model)] of the last run, in job order (flowgnn.h: flowgnn_group_get_node_embeddings)."""
+        out = np.empty((self.total_nodes, embedding_dim(self.model)), dtype=np.float32)
+        self._check(self.lib.flowgnn_group_get_node_embeddings(self._h, _pf(out)), "flowgnn_group_get_node_embeddings")
         return out
 
     def forward(self, batch: GraphBatch) -> np.ndarray:

@@ -340,6 +340,40 @@ int flowgnn_get_embeddings(flowgnn_engine* e, float* out_host);
 int flowgnn_embeddings_device(flowgnn_engine* e, void** d_emb);
 int flowgnn_set_embeddings_buffer(flowgnn_engine* e, void* device_ptr);
 
+/*
+ * Node embeddings: the rows that pool is taken over, one per node,
+ *     node_emb[v][:] = r[v][:]                                                     (fp32, [N_tot][flowgnn_embedding_dim(model)])
+ * with r as defined above (GIN / GIN-VN h_5 without ReLU, GCN BatchNorm_4(aggregation of x_4) without ReLU, GAT the last layer's
+ * output averaged over its 4 heads, PNA / DGN h_4) and v the node's position in the batch AS THE CALLER PASSED IT, whatever order
+ * the bin-packed tiles walk the graphs in.  GIN-VN: the virtual nodes are rows like any other.  mean over a graph's rows = emb[g],
+ * and head(emb[g]) = the graph's logit.  What a pooling of the caller's own, a node-level head or an attribution reads.
+ *  flowgnn_set_node_embeddings(e, 1): the runs enqueued after it also store the rows.  Off by default, and off means off: the same
+ *     kernels launch with the same arguments and every result bit is what it was.  The logits while it is on:
+ *       GCN, PNA, DGN   bit-identical to off.  Where the batch runs on the graph-resident kernel it stays there: the instance
+ *                       gcn_resident_rows_kernel / pna_resident_rows_kernel / dgn_resident_rows_kernel keeps its folded / pooled
+ *                       readout and additionally stores the rows it holds on chip at the end of the last layer;
+ *       GIN, GIN-VN     those of the un-folded rule, exactly as documented for flowgnn_set_embeddings (FLOWGNN_NUMERIC_F16: the
+ *                       "every other path" rule of that mode): the graph-resident kernel's un-folded instance writes h_5;
+ *       GAT             those of its un-folded per-layer path, as with flowgnn_set_embeddings: gat_resident_kernel folds the last
+ *                       layer's skip contraction into the readout and never forms the 16-wide row (the open item).
+ *     The per-layer paths (options <model>_resident 0, batches under the fill threshold, graphs beyond the tile limits) and the
+ *     exact-fp32 re-run fill the buffer from the rows they keep in HBM, with the last stage un-folded.
+ *     FLOWGNN_ERR_UNSUPPORTED in FLOWGNN_NUMERIC_Q6_10, and flowgnn_set_numeric_mode answers the same for that mode while node
+ *     embeddings are on.  Drops a recorded launch sequence (option hipgraph).  Survives flowgnn_set_batch.  Works together with
+ *     flowgnn_set_embeddings, NUM_TASK > 1, FLOWGNN_NUMERIC_F16 and option hipgraph.  The <M>_compute_graphs entry points never
+ *     produce rows.
+ *  flowgnn_get_node_embeddings: copy [N_tot][dim] to the host (synchronises first; an exact-fp32 re-run refills the rows with the
+ *     logits).  FLOWGNN_ERR_STATE when the last run did not have node embeddings on.
+ *  flowgnn_node_embeddings_device: where the last run put them (same condition); valid until the next flowgnn_set_batch.
+ *  flowgnn_set_node_embeddings_buffer: redirect them into a caller-owned DEVICE buffer of at least N_tot * dim floats; NULL
+ *     restores the engine's own buffer; reset by flowgnn_set_batch; drops a recorded launch sequence.  The engine writes only into
+ *     its own buffer or this one, on its stream: a stream-ordered caller needs no host synchronisation.
+ */
+int flowgnn_set_node_embeddings(flowgnn_engine* e, int on);
+int flowgnn_get_node_embeddings(flowgnn_engine* e, float* out_host);
+int flowgnn_node_embeddings_device(flowgnn_engine* e, void** d_rows);
+int flowgnn_set_node_embeddings_buffer(flowgnn_engine* e, void* device_ptr);
+
 /* The engine's hipStream_t as an opaque pointer (for event timing by a caller). */
 int flowgnn_stream(flowgnn_engine* e, void** stream);
 
@@ -492,6 +526,9 @@ int flowgnn_group_get_results(flowgnn_group* g, float* out_host);
 /* flowgnn_set_embeddings on every member; flowgnn_group_get_embeddings writes [num_graphs][dim] in job order, like flowgnn_group_get_results. */
 int flowgnn_group_set_embeddings(flowgnn_group* g, int on);
 int flowgnn_group_get_embeddings(flowgnn_group* g, float* out_host);
+/* flowgnn_set_node_embeddings on every member; flowgnn_group_get_node_embeddings writes [N_tot][dim] in job order (the shards are contiguous graph ranges). */
+int flowgnn_group_set_node_embeddings(flowgnn_group* g, int on);
+int flowgnn_group_get_node_embeddings(flowgnn_group* g, float* out_host);
 /* set_batch + run + get_results for a batch in HOST memory, cut into size x chunks_per_engine ranges; engine i takes ranges
  * i, i + size, ... in turn, so that one engine's copies overlap the others' kernels.  out_host: [num_graphs][NUM_TASK]. */
 int flowgnn_group_compute(flowgnn_group* g, int num_graphs, const int* nums_of_nodes, const int* nums_of_edges,

@@ -7,12 +7,13 @@ src=flowgnn_amd/csrc
 obj=${TMPDIR:-/tmp}/flowgnn_devobj_$name
 mkdir -p $obj
 pids=""
-for f in engine graph_build gin gin_split ginq modelq gcn pna dgn gat; do
+for f in engine group entry ingest graph_build gin gin_split gin_split_f16 gin_split_pool ginq modelq gcn gcn_rows pna pna_emb pna_rows dgn dgn_emb dgn_rows gat; do
   if [ ! -f $obj/$f.o ] || [ $src/$f.hip -nt $obj/$f.o ] || [ -n "$FORCE" ]; then
     ( /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -DFLOWGNN_DEV $flags -c $src/$f.hip -o $obj/$f.o 2>$obj/$f.log || { grep -A5 "error" $obj/$f.log | head -40; exit 1; } ) &
     pids="$pids $!"
   fi
 done
 for p in $pids; do wait $p; done
+for f in h2d_pack tile_pack; do g++ -O3 -std=c++17 -fPIC -c $src/$f.cpp -o $obj/$f.o; done  # the host-side packer and tile planner: plain C++
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o scripts/dev/_$name.so $obj/*.o -lpthread
 echo scripts/dev/_$name.so
