@@ -161,6 +161,9 @@ struct DeviceBatch {
                               // that finds it set must fill it: every path of every model does, on chip where the graphs are resident
     float* node_emb;          // [N][flowgnn_embedding_dim(model)] the rows that pool is taken over, in the caller's node order
                               // (flowgnn_set_node_embeddings), or null: not asked for.  A forward that finds it set must fill it too
+    float* node_logits;       // [N][num_tasks] the per-node terms of the mean-pool + linear readout, r[v] . W[t] + b[t], in the caller's node
+                              // order (flowgnn_set_node_logits; GIN, GIN-VN, GCN, GAT), or null: not asked for.  The same contract: a
+                              // forward of these four models that finds it set must fill it, on every path
     int num_tasks;            // NUM_TASK of the readout (1 unless flowgnn_set_num_tasks said otherwise)
     int final_h;              // which h[] holds the last stage's output (set by forward)
     const float* tap;         // optional debug tap returned by flowgnn_get_h instead of h[final_h]

@@ -304,6 +304,58 @@ __global__ __launch_bounds__(256) void mean_pool_rows_kernel(const float* __rest
     reinterpret_cast<float4*>(emb + (size_t)g * D)[lane] = make_float4(acc.x / n, acc.y / n, acc.z / n, acc.w / n);
 }
 
+// ---------------------------------------------------------------- node logits: the per-node terms of a mean-pool + linear readout
+// (flowgnn_set_node_logits) on the paths whose graph-resident kernel does not store them itself.
+// The folded per-layer paths leave score[v] = r[v] . w in device memory (the input of segment_mean_bias_kernel): the term is that
+// plus the head's bias.
+template <int UNUSED = 0>
+__global__ __launch_bounds__(256) void node_logits_bias_kernel(const float* __restrict__ score, const float* __restrict__ pb,
+                                                               float* __restrict__ node_logits, int n_tot) {
+    const int v = blockIdx.x * 256 + threadIdx.x;
+    if (v < n_tot) node_logits[v] = score[v] + pb[0];
+}
+
+// Where the rows r[v] are in device memory: node_logits[v][t] = pb[t] + rows[v] . pw[t].  One 16-lane group per node: lane j takes the
+// float4 chunks j, j + 16, ... of the row in that order (a row is a few coalesced requests), then the group's sixteen partial sums are
+// folded by a fixed xor tree -- the order of every value's additions depends on D alone.  The row stays in registers across the tasks.
+template <int D>
+__global__ __launch_bounds__(256) void node_logits_rows_kernel(const float* __restrict__ rows, const float* __restrict__ pw,
+                                                               const float* __restrict__ pb, float* __restrict__ node_logits, int n_tot,
+                                                               int num_tasks) {
+    constexpr int C = D / 4, K = (C + 15) / 16;
+    static_assert(D % 4 == 0, "rows are read as float4 chunks");
+    const int j = threadIdx.x & 15;
+    const long long v = (long long)blockIdx.x * 16 + (threadIdx.x >> 4);
+    const bool live = v < n_tot;  // (no early return: the shuffles below are wave-wide)
+    float4 x[K];
+#pragma unroll
+    for (int k = 0; k < K; k++) {
+        const int c = j + 16 * k;
+        x[k] = (live && c < C) ? reinterpret_cast<const float4*>(rows)[(size_t)v * C + c] : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    for (int t = 0; t < num_tasks; t++) {
+        float part = 0.0f;
+#pragma unroll
+        for (int k = 0; k < K; k++) {
+            const int c = j + 16 * k;
+            if (c < C) {
+                const float4 w = reinterpret_cast<const float4*>(pw + (size_t)t * D)[c];
+                part += x[k].x * w.x; part += x[k].y * w.y; part += x[k].z * w.z; part += x[k].w * w.w;
+            }
+        }
+#pragma unroll
+        for (int d = 8; d >= 1; d >>= 1) part += __shfl_xor(part, d, 64);
+        if (live && j == 0) node_logits[(size_t)v * num_tasks + t] = part + pb[t];
+    }
+}
+
+template <int D>
+inline void launch_node_logits_rows(const float* rows, const float* pw, const float* pb, float* node_logits, int n_tot, int num_tasks,
+                                    hipStream_t s) {
+    if (n_tot <= 0) return;
+    node_logits_rows_kernel<D><<<(n_tot + 15) / 16, 256, 0, s>>>(rows, pw, pb, node_logits, n_tot, num_tasks);
+}
+
 static inline int grid_for(long long items, int per_block, int cap) {
     long long nb = (items + per_block - 1) / per_block;
     if (nb > cap) nb = cap;

@@ -304,6 +304,19 @@ static int place_node_embeddings(flowgnn_engine* e) {
     e->db.node_emb = e->batch_ready ? e->nemb_target() : nullptr;
     return FLOWGNN_OK;
 }
+// ... and for the node logits, [N][num_tasks]
+static int place_node_logits(flowgnn_engine* e) {
+    if (e->nlog_on && e->batch_ready && !e->nlog_user) {
+        const size_t need = sizeof(float) * (size_t)e->N * (size_t)e->num_tasks;
+        if (!e->nlog.holds(need)) {
+            if (e->stream) EHIP_TRY(e, hipStreamSynchronize(e->stream));
+            if (e->nlog_last == e->nlog.p) e->nlog_last = nullptr;
+            EHIP_TRY(e, e->nlog.reserve(need, false));
+        }
+    }
+    e->db.node_logits = e->batch_ready ? e->nlog_target() : nullptr;
+    return FLOWGNN_OK;
+}
 
 extern "C" {
 
@@ -372,6 +385,7 @@ int flowgnn_destroy(flowgnn_engine* e) {
     e->free_batch();
     e->emb.release();
     e->nemb.release();
+    e->nlog.release();
     if (e->d_err) (void)hipFree(e->d_err);
     delete e->model;
     if (e->own_stream) (void)hipStreamDestroy(e->own_stream);
@@ -414,7 +428,8 @@ int flowgnn_load_weights_dir(flowgnn_engine* e, const char* dir) {
 static int alloc_batch(flowgnn_engine* e, size_t G, size_t N, size_t E, bool attr, bool eig) {
     const int D = e->model->emb_dim(), SD = e->model->scratch_dim();
     G *= (size_t)e->num_tasks;  // capG counts result slots (only d_out and the small per-graph arrays scale with it)
-    if (G > e->capG || N > e->capN || E > e->capE || (attr && !e->d_ea) || (eig && !e->d_eig)) {
+    // (!d_nn: an engine's first batch may be an empty one -- a model without edge attributes would allocate nothing for it)
+    if (G > e->capG || N > e->capN || E > e->capE || !e->d_nn || (attr && !e->d_ea) || (eig && !e->d_eig)) {
         // Capacities only grow, each on its own, and a regrow leaves an eighth of headroom: an engine that is handed the ranges of
         // a cut job one after the other (flowgnn_group_compute) sees counts that differ by a few percent from range to range, and
         // every reallocation is two dozen hipFree / hipMalloc pairs that wait for the device.
@@ -679,8 +694,11 @@ static int set_batch_state(flowgnn_engine* e, int num_graphs, const int* nums_of
     e->emb_last = nullptr;
     e->nemb_user = nullptr;
     e->nemb_last = nullptr;
+    e->nlog_user = nullptr;
+    e->nlog_last = nullptr;
     if (int rc = place_embeddings(e)) return rc;
-    return place_node_embeddings(e);
+    if (int rc = place_node_embeddings(e)) return rc;
+    return place_node_logits(e);
 }
 
 }  // extern "C"
@@ -810,6 +828,7 @@ int flowgnn_run(flowgnn_engine* e) {
     ENGINE_TRY(e, use_device(e));
     e->emb_last = e->db.emb;
     e->nemb_last = e->db.node_emb;
+    e->nlog_last = e->db.node_logits;
     if (e->G == 0) { e->ran = true; return FLOWGNN_OK; }
     const bool want_graph = e->graph_mode != 0 && !e->prof.enabled && (e->graph_mode > 1 || e->N <= (1ll << 20));
     if (want_graph && e->graph_ok) {
@@ -886,14 +905,17 @@ int flowgnn_sync(flowgnn_engine* e) {
         e->drop_graph();  // the captured launches are the split-f16 ones
         EHIP_TRY(e, hipMemsetAsync(e->d_err + 1, 0, sizeof(int), e->stream));
         e->model->set_exact(true);
-        {   // the repeated pass refills what the run filled: the logits, and the embeddings / node embeddings where that run had them on
+        {   // the repeated pass refills what the run filled: the logits, and the embeddings / node embeddings / node logits where that run had them on
             float* const now = e->db.emb;
             float* const nnow = e->db.node_emb;
+            float* const lnow = e->db.node_logits;
             e->db.emb = e->emb_last;
             e->db.node_emb = e->nemb_last;
+            e->db.node_logits = e->nlog_last;
             const int frc = engine_forward(e);
             e->db.emb = now;
             e->db.node_emb = nnow;
+            e->db.node_logits = lnow;
             ENGINE_TRY(e, frc);
         }
         he = hipStreamSynchronize(e->stream);
@@ -1025,6 +1047,55 @@ int flowgnn_set_node_embeddings_buffer(flowgnn_engine* e, void* device_ptr) {
     return place_node_embeddings(e);
 }
 
+int flowgnn_set_node_logits(flowgnn_engine* e, int on) {
+    if (!e) return FLOWGNN_ERR_ARG;
+    if (on && (e->model_id == FLOWGNN_MODEL_PNA || e->model_id == FLOWGNN_MODEL_DGN)) {
+        e->err = "flowgnn_set_node_logits: PNA and DGN read the pooled vector through an MLP head, so a graph's logit is no mean of per-node terms";
+        return FLOWGNN_ERR_UNSUPPORTED;
+    }
+    if (on && e->numeric_mode == FLOWGNN_NUMERIC_Q6_10) {
+        e->err = "flowgnn_set_node_logits: there are no fixed-point node logits (FLOWGNN_NUMERIC_Q6_10)";
+        return FLOWGNN_ERR_UNSUPPORTED;
+    }
+    ENGINE_TRY(e, use_device(e));
+    e->drop_graph();  // a recorded launch sequence is that of the other setting
+    e->nlog_on = on != 0;
+    return place_node_logits(e);
+}
+
+int flowgnn_get_node_logits(flowgnn_engine* e, float* out_host) {
+    if (!e || (!out_host && e->N > 0)) return FLOWGNN_ERR_ARG;
+    if (!e->ran || (!e->nlog_last && e->G > 0) || (e->G == 0 && !e->nlog_on)) {
+        e->err = "flowgnn_get_node_logits: the last flowgnn_run did not have node logits on (flowgnn_set_node_logits)";
+        return FLOWGNN_ERR_STATE;
+    }
+    int rc = flowgnn_sync(e);
+    if (rc) return rc;
+    const size_t bytes = sizeof(float) * (size_t)e->N * (size_t)e->num_tasks;
+    if (e->G > 0 && e->N > 0) return d2h_sync(e, out_host, e->nlog_last, bytes, "copy node logits");
+    return FLOWGNN_OK;
+}
+
+int flowgnn_node_logits_device(flowgnn_engine* e, void** d_terms) {
+    if (!e || !d_terms) return FLOWGNN_ERR_ARG;
+    if (!e->ran || !e->nlog_last) {
+        e->err = "flowgnn_node_logits_device: the last flowgnn_run did not have node logits on (flowgnn_set_node_logits)";
+        return FLOWGNN_ERR_STATE;
+    }
+    *d_terms = e->nlog_last;
+    return FLOWGNN_OK;
+}
+
+int flowgnn_set_node_logits_buffer(flowgnn_engine* e, void* device_ptr) {
+    if (!e) return FLOWGNN_ERR_ARG;
+    if (!e->batch_ready) return FLOWGNN_ERR_STATE;
+    // as flowgnn_set_embeddings_buffer: no device synchronisation, the pointer matters to the launches enqueued after this call
+    ENGINE_TRY(e, use_device(e));
+    if (e->gexec) e->drop_graph();
+    e->nlog_user = (float*)device_ptr;
+    return place_node_logits(e);
+}
+
 int flowgnn_stream(flowgnn_engine* e, void** stream) {
     if (!e || !stream) return FLOWGNN_ERR_ARG;
     *stream = (void*)e->stream;
@@ -1081,6 +1152,10 @@ int flowgnn_set_numeric_mode(flowgnn_engine* e, int mode) {
     }
     if (mode == FLOWGNN_NUMERIC_Q6_10 && e->nemb_on) {
         e->err = "flowgnn_set_numeric_mode: node embeddings are on, and there are no fixed-point node embeddings";
+        return FLOWGNN_ERR_UNSUPPORTED;
+    }
+    if (mode == FLOWGNN_NUMERIC_Q6_10 && e->nlog_on) {
+        e->err = "flowgnn_set_numeric_mode: node logits are on, and there are no fixed-point node logits";
         return FLOWGNN_ERR_UNSUPPORTED;
     }
     e->drop_graph();
@@ -1140,11 +1215,14 @@ static int ensure_rows(flowgnn_engine* e) {
     e->model->set_exact(e->force_exact);
     float* const emb = e->db.emb;
     float* const nemb = e->db.node_emb;
+    float* const nlog = e->db.node_logits;
     e->db.emb = nullptr;  // a tap's pass leaves the run's embeddings as they are
     e->db.node_emb = nullptr;
+    e->db.node_logits = nullptr;
     rc = engine_forward(e);
     e->db.emb = emb;
     e->db.node_emb = nemb;
+    e->db.node_logits = nlog;
     e->model->set_keep_h(false);
     if (rc) { e->err = fg::last_error_text(); return rc; }
     return flowgnn_sync(e);

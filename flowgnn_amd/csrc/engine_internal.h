@@ -86,6 +86,12 @@ struct flowgnn_engine {
     float* nemb_user = nullptr;
     float* nemb_last = nullptr;
     float* nemb_target() const { return nemb_on ? (nemb_user ? nemb_user : (float*)nemb.p) : nullptr; }
+    // node logits (flowgnn_set_node_logits): the same rules, [N][num_tasks]
+    bool nlog_on = false;
+    fg::GrowBuf nlog;
+    float* nlog_user = nullptr;
+    float* nlog_last = nullptr;
+    float* nlog_target() const { return nlog_on ? (nlog_user ? nlog_user : (float*)nlog.p) : nullptr; }
 
     // hipGraph replay of the launch sequence (index build + forward), opt-in (FLOWGNN_HIPGRAPH=1; 2 = batches of any size).
     // Measured on this runtime it does not pay: asynchronous launches already pipeline, and a replay of the dozen kernels

@@ -23,6 +23,42 @@
 #include <cstring>
 
 namespace fg {
+// gat_nlogit.hip compiles this file once more with FG_RESIDENT_NLOGIT_TU defined, for ONE kernel: gat_resident_kernel under the name
+// gat_resident_nlogit_kernel, the instance that also stores every node's term of the readout (flowgnn_set_node_logits).  As
+// gcn_rows.hip does it: the default kernel stays the code it was; in that translation unit the host side is left out and the other
+// kernels, with internal linkage and unused, are dropped.
+// the graph-resident kernel's weights (per layer in device memory, GatModel::d_res_: see GATR_LAYER_BYTES below)
+struct GatResidentDev {
+    const uint8_t* layers;     // [5][GATR_LAYER_BYTES]
+    const float* scales;       // [3][5]: what undoes the power-of-two scale of W_skip, W_lin, score tile (device memory: a run-time
+                               // index into a kernel argument would go through scratch)
+    const float* a_src;        // [5][16 dim][4 head] (layer 0's scores)
+    const float* a_tgt;
+    const float* lin0;         // [16 dim][9][4 head]
+    const float* pool_w;       // [16]
+    const float* pool_b;
+    // the readout folded through the LAST layer's skip contraction: logit terms are linear in o_3, so sum_{d,h} (pw[d] / 4)
+    // (W_skip_4 o_3)[d][h] = o_3 . u4 with u4 = W_skip_4^T v, v[(d, h)] = pw[d] / 4 -- the last layer needs no MFMA and no weights
+    const float* u4;           // [64]
+    int* range_flag;
+};
+// what a launch of the resident kernel takes, for the storing instance in its own translation unit (gat_nlogit.hip)
+struct GatResidentLaunch {
+    int grid;
+    const int* node_feature; const int* feat_row; const int* row_ptr; const int* src;
+    const int* tile_row; const int* tile_graph; const int* node_off;
+    float* out; int n_tiles; GatResidentDev w; int ablate;
+    float* node_logits;  // [N], caller order (GAT's tiles are ranges of the batch's rows: row r of a tile is node t0 + r)
+};
+void launch_gat_resident_nlogit(const GatResidentLaunch& a, hipStream_t s);  // gat_nlogit.hip
+#ifdef FG_RESIDENT_NLOGIT_TU
+namespace {
+constexpr bool RESIDENT_NLOGIT = true;
+#define GAT_NLOGIT_PARAM , float* __restrict__ node_logits
+#else
+constexpr bool RESIDENT_NLOGIT = false;
+#define GAT_NLOGIT_PARAM
+#endif
 
 constexpr int GAT_D = 16;
 constexpr int GAT_H = 4;
@@ -484,20 +520,6 @@ constexpr int GATR_WAVES = 16;
 // next layer's attention scores (node_embedding.cc:235-268) come out of the same MFMA chain as the projection, already in the lanes
 // that store them (g = 0: ssrc, g = 1: stgt), instead of 32 multiply-adds and 16 cross-lane shuffles per lane.
 constexpr int GATR_LAYER_BYTES = 36 * 1024;
-struct GatResidentDev {
-    const uint8_t* layers;     // [5][GATR_LAYER_BYTES]
-    const float* scales;       // [3][5]: what undoes the power-of-two scale of W_skip, W_lin, score tile (device memory: a run-time
-                               // index into a kernel argument would go through scratch)
-    const float* a_src;        // [5][16 dim][4 head] (layer 0's scores)
-    const float* a_tgt;
-    const float* lin0;         // [16 dim][9][4 head]
-    const float* pool_w;       // [16]
-    const float* pool_b;
-    // the readout folded through the LAST layer's skip contraction: logit terms are linear in o_3, so sum_{d,h} (pw[d] / 4)
-    // (W_skip_4 o_3)[d][h] = o_3 . u4 with u4 = W_skip_4^T v, v[(d, h)] = pw[d] / 4 -- the last layer needs no MFMA and no weights
-    const float* u4;           // [64]
-    int* range_flag;
-};
 
 #define GATR_ABSMAX(v, a, b) asm("v_max3_f32 %0, |%1|, |%2|, %0" : "+v"(v) : "v"(a), "v"(b))
 
@@ -508,7 +530,10 @@ __global__ __launch_bounds__(GATR_WAVES * 64, 4) void gat_resident_kernel(const 
                                                                          const int* __restrict__ row_ptr, const int* __restrict__ src,
                                                                          const int* __restrict__ tile_row, const int* __restrict__ tile_graph,
                                                                          const int* __restrict__ node_off, float* __restrict__ out, int n_tiles,
-                                                                         GatResidentDev w, int ablate_arg) {
+                                                                         GatResidentDev w, int ablate_arg GAT_NLOGIT_PARAM) {
+#ifndef FG_RESIDENT_NLOGIT_TU
+    constexpr float* node_logits = nullptr;  // (the storing instance has it as its last argument)
+#endif
     const int ablate = FG_ABLATE(ablate_arg);  // 0 in the shipped build: the branches below fold away (common.h)
     (void)ablate_arg;
     const bool sort_rows = !(ablate & 4);  // development aid: gat_ablate, -DFLOWGNN_DEV builds=4 keeps rows in natural order
@@ -845,6 +870,10 @@ __global__ __launch_bounds__(GATR_WAVES * 64, 4) void gat_resident_kernel(const 
             __syncthreads();  // #2: the next layer's projections and scores are complete
         }
         __syncthreads();  // the per-node readout terms are in s_dot
+        if constexpr (RESIDENT_NLOGIT) {
+            // tiles are ranges of the batch's rows, so the tile's row r is node t0 + r: one coalesced 4-byte store per node
+            if ((int)threadIdx.x < rows) node_logits[(size_t)t0 + threadIdx.x] = s_dot[threadIdx.x] + pool_bias;
+        }
         if (g0 + (int)threadIdx.x < g1) out[g0 + threadIdx.x] = lds_sum_in_order(s_dot + (ro_n0 - t0), ro_n1 - ro_n0) / (float)(ro_n1 - ro_n0) + pool_bias;
         if (!has_next) break;
         tile = ntile; t0 = nt0; rows = nrows; g0 = ng0; g1 = ng1; e0 = ne0; ne = nne;
@@ -855,6 +884,7 @@ __global__ __launch_bounds__(GATR_WAVES * 64, 4) void gat_resident_kernel(const 
 }
 #undef GATR_ABSMAX
 
+#ifndef FG_RESIDENT_NLOGIT_TU  // (host side: the model's own translation unit only)
 class GatModel : public Model {
 public:
     ~GatModel() override { free_all(); }
@@ -1068,9 +1098,14 @@ public:
             rw.range_flag = db.range_flag;
             ProfScope p(prof, "gat_resident", s);
             const int grid = db.gtiles.n_tiles < 256 ? db.gtiles.n_tiles : 256;  // persistent: one 16-wave workgroup per CU (118 KB of LDS)
-            gat_resident_kernel<<<grid, GATR_WAVES * 64, 0, s>>>(db.b.node_feature, feat_row, db.csr.row_ptr, db.csr.src, db.gtiles.row_start,
-                                                               db.gtiles.graph_start, db.b.node_off, db.out, db.gtiles.n_tiles, rw,
-                                                               ablate_);
+            if (db.node_logits)  // the same kernel's instance that also stores the per-node readout terms (gat_nlogit.hip)
+                launch_gat_resident_nlogit(GatResidentLaunch{grid, db.b.node_feature, feat_row, db.csr.row_ptr, db.csr.src, db.gtiles.row_start,
+                                                             db.gtiles.graph_start, db.b.node_off, db.out, db.gtiles.n_tiles, rw, ablate_,
+                                                             db.node_logits}, s);
+            else
+                gat_resident_kernel<<<grid, GATR_WAVES * 64, 0, s>>>(db.b.node_feature, feat_row, db.csr.row_ptr, db.csr.src, db.gtiles.row_start,
+                                                                   db.gtiles.graph_start, db.b.node_off, db.out, db.gtiles.n_tiles, rw,
+                                                                   ablate_);
             db.final_h = 0;
             db.tap = nullptr;
             db.h_valid = false;  // no per-node tensor leaves the kernel: flowgnn_get_h repeats the pass on the per-layer kernels
@@ -1134,6 +1169,12 @@ public:
             ProfScope p(prof, "mean_pool_rows", s);
             mean_pool_rows_kernel<GAT_D><<<(db.b.num_graphs + 3) / 4, 256, 0, s>>>(emb, db.b.node_off, db.emb, db.b.num_graphs);
         }
+        if (db.node_logits) {
+            // node logits (flowgnn_set_node_logits): the folded last stage left emb[v] . w as float[n], the un-folded one the 16-wide rows
+            ProfScope p(prof, "node_logits", s);
+            if (fold) node_logits_bias_kernel<0><<<(n + 255) / 256, 256, 0, s>>>(emb, d_pb_, db.node_logits, n);
+            else launch_node_logits_rows<GAT_D>(emb, d_pw_, d_pb_, db.node_logits, n, 1, s);
+        }
         return 0;
     }
 
@@ -1165,5 +1206,14 @@ private:
 };
 
 Model* make_gat_model() { return new GatModel(); }
+#endif  // FG_RESIDENT_NLOGIT_TU
+
+#ifdef FG_RESIDENT_NLOGIT_TU
+}  // namespace
+void launch_gat_resident_nlogit(const GatResidentLaunch& a, hipStream_t s) {
+    gat_resident_kernel<<<a.grid, GATR_WAVES * 64, 0, s>>>(a.node_feature, a.feat_row, a.row_ptr, a.src, a.tile_row, a.tile_graph, a.node_off, a.out,
+                                                           a.n_tiles, a.w, a.ablate, a.node_logits);
+}
+#endif
 
 }  // namespace fg

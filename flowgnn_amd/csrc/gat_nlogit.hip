@@ -1,0 +1,6 @@
+// GAT's graph-resident kernel once more, as the instance that also stores every node's term of the readout, emb[v] . w + b, in the
+// caller's node order (flowgnn_set_node_logits): gat.hip compiled with FG_RESIDENT_NLOGIT_TU, which leaves launch_gat_resident_nlogit
+// as this translation unit's only symbol.  The kernel carries its own name, so profiles and traces tell the two apart.
+#define FG_RESIDENT_NLOGIT_TU 1
+#define gat_resident_kernel gat_resident_nlogit_kernel
+#include "gat.hip"

@@ -35,14 +35,29 @@ struct GcnResidentLaunch {
     float* out; int n_tiles; int* range_flag; int ablate;
     const uint8_t* desc; const float4* enc_tab; const int* list; const int* lrow;
     float* node_emb;  // [N][100], caller order
+    float* node_logits = nullptr;  // [N], caller order (launch_gcn_resident_nlogit)
 };
 void launch_gcn_resident_rows(const GcnResidentLaunch& a, hipStream_t s);  // gcn_rows.hip
-#ifdef FG_RESIDENT_ROWS_TU
+// gcn_nlogit.hip does the same with FG_RESIDENT_NLOGIT_TU, for gcn_resident_nlogit_kernel: the instance that also stores every node's
+// term of the readout, a[v] . w + b, in the caller's node order (flowgnn_set_node_logits)
+void launch_gcn_resident_nlogit(const GcnResidentLaunch& a, hipStream_t s);  // gcn_nlogit.hip
+#if defined(FG_RESIDENT_ROWS_TU) || defined(FG_RESIDENT_NLOGIT_TU)
+#define FG_RESIDENT_STORING_TU 1
 namespace {
+#endif
+#ifdef FG_RESIDENT_ROWS_TU
 constexpr bool RESIDENT_ROWS = true;
 #define GCN_ROWS_PARAM , float* __restrict__ node_emb
 #else
 constexpr bool RESIDENT_ROWS = false;
+#endif
+#ifdef FG_RESIDENT_NLOGIT_TU
+constexpr bool RESIDENT_NLOGIT = true;
+#define GCN_ROWS_PARAM , float* __restrict__ node_logits
+#else
+constexpr bool RESIDENT_NLOGIT = false;
+#endif
+#ifndef GCN_ROWS_PARAM
 #define GCN_ROWS_PARAM
 #endif
 
@@ -578,9 +593,12 @@ __global__ __launch_bounds__(GCNR_WAVES * 64, 3) void gcn_resident_kernel(const 
 #ifndef FG_RESIDENT_ROWS_TU
     constexpr float* node_emb = nullptr;  // (the storing instance has it as its last argument)
 #endif
-    // RESIDENT_ROWS: the caller-order row of every row of the tile.  A bin-packed tile is a list of graphs, and its rows live in a
-    // tile-ordered row space: row r of the tile is node_off[graph] + (r - the graph's first row inside the tile), not t0 + r.
-    __shared__ int s_grow[RESIDENT_ROWS ? GCNR_ROWS : 1];
+#ifndef FG_RESIDENT_NLOGIT_TU
+    constexpr float* node_logits = nullptr;  // (likewise)
+#endif
+    // RESIDENT_ROWS / RESIDENT_NLOGIT: the caller-order row of every row of the tile.  A bin-packed tile is a list of graphs, and its rows live
+    // in a tile-ordered row space: row r of the tile is node_off[graph] + (r - the graph's first row inside the tile), not t0 + r.
+    __shared__ int s_grow[(RESIDENT_ROWS || RESIDENT_NLOGIT) ? GCNR_ROWS : 1];
     // ONEPASS (the default front end since round 5): no x0 / row_ptr / src / ecode / out_deg -- the tile's CSR slice, out-degrees and
     // encoder row numbers come from gcn_tile_build_kernel's descriptor, and the loader computes the tile's x_0 rows itself from the
     // pre-combined projected table (three 400-B rows per node out of L2 instead of one out of HBM that another launch wrote).
@@ -749,8 +767,8 @@ __global__ __launch_bounds__(GCNR_WAVES * 64, 3) void gcn_resident_kernel(const 
             s_idp1[tid] = 65536.0f / (float)(dpre + 1);  // 2^16 / (deg + 1): the self term arrives scaled by 2^-16 (epilogue below)
         }
         if (tid < 16) { s_cnt[tid] = 0; s_cur[tid] = 0; }
-        if constexpr (RESIDENT_ROWS) {
-            // (its last readers were the previous tile's stores, two barriers ago; read in this tile's last layer)
+        if constexpr (RESIDENT_ROWS || RESIDENT_NLOGIT) {
+            // (its last readers were the previous tile's stores, at least a barrier ago; read in or behind this tile's last layer)
             if (list && g0 + tid < g1) {
                 const int gph = list[g0 + tid], lr0 = lrow[g0 + tid];
                 const int nb = node_off[gph], cnt = node_off[gph + 1] - nb;
@@ -1066,6 +1084,11 @@ __global__ __launch_bounds__(GCNR_WAVES * 64, 3) void gcn_resident_kernel(const 
             x0_request(XH, XK);  // the second half travels under the readout, the CSR staging and the row sort of the next tile
         }
         if (ro_gi < g1) out[ro_g] = lds_sum_in_order(s_dot + (ro_n0 - t0), ro_n1 - ro_n0) / (float)(ro_n1 - ro_n0) + pool_bias;
+        if constexpr (RESIDENT_NLOGIT) {
+            // the terms the readout is summing, one thread per row of the tile: a graph's rows are consecutive in the tile and in the
+            // batch, so the 4-byte stores of a wave fall into a few runs; rows of padding (tid >= rows) are never stored
+            if (tid < rows) node_logits[list ? (size_t)s_grow[tid] : (size_t)t0 + tid] = s_dot[tid] + pool_bias;
+        }
         if (!has_next) break;
         tile = ntile; t0 = nt0; rows = nrows; g0 = ng0; g1 = ng1; e0 = ne0; ne = nne;
         GCN_STAMP(6);  // last layer's tail, readout, next tile's requests
@@ -1082,7 +1105,7 @@ __global__ __launch_bounds__(GCNR_WAVES * 64, 3) void gcn_resident_kernel(const 
     }
 }
 
-#ifndef FG_RESIDENT_ROWS_TU  // (host side: the model's own translation unit only)
+#ifndef FG_RESIDENT_STORING_TU  // (host side: the model's own translation unit only)
 class GcnModel : public Model {
 public:
     ~GcnModel() override { free_all(); }
@@ -1323,6 +1346,11 @@ public:
                                                                t_row, t_graph, db.b.node_off, db.out, n_tiles, db.range_flag, ablate_,
                                                                reinterpret_cast<const uint8_t*>(desc_.p), reinterpret_cast<const float4*>(d_enc_tab_),
                                                                bp ? db.gtiles.bp_list : nullptr, bp ? db.gtiles.bp_lrow : nullptr, db.node_emb}, s);
+                else if (db.node_logits)  // ... or the instance that stores the per-node readout terms (gcn_nlogit.hip)
+                    launch_gcn_resident_nlogit(GcnResidentLaunch{true, n_tiles < 256 ? n_tiles : 256, nullptr, nullptr, nullptr, nullptr, nullptr, d_res_, d_pw_, d_pb_,
+                                                                 t_row, t_graph, db.b.node_off, db.out, n_tiles, db.range_flag, ablate_,
+                                                                 reinterpret_cast<const uint8_t*>(desc_.p), reinterpret_cast<const float4*>(d_enc_tab_),
+                                                                 bp ? db.gtiles.bp_list : nullptr, bp ? db.gtiles.bp_lrow : nullptr, nullptr, db.node_logits}, s);
                 else
                 gcn_resident_kernel<true><<<n_tiles < 256 ? n_tiles : 256, GCNR_WAVES * 64, 0, s>>>(
                     nullptr, nullptr, nullptr, nullptr, nullptr, d_res_, d_pw_, d_pb_, t_row, t_graph, db.b.node_off, db.out, n_tiles, db.range_flag,
@@ -1338,6 +1366,10 @@ public:
                     launch_gcn_resident_rows(GcnResidentLaunch{false, grid, db.h[0], db.csr.row_ptr, db.csr.src, db.csr.ecode, db.csr.out_deg, d_res_, d_pw_, d_pb_,
                                                                db.gtiles.row_start, db.gtiles.graph_start, db.b.node_off, db.out, db.gtiles.n_tiles,
                                                                db.range_flag, ablate_, nullptr, nullptr, nullptr, nullptr, db.node_emb}, s);
+                else if (db.node_logits)
+                    launch_gcn_resident_nlogit(GcnResidentLaunch{false, grid, db.h[0], db.csr.row_ptr, db.csr.src, db.csr.ecode, db.csr.out_deg, d_res_, d_pw_, d_pb_,
+                                                                 db.gtiles.row_start, db.gtiles.graph_start, db.b.node_off, db.out, db.gtiles.n_tiles,
+                                                                 db.range_flag, ablate_, nullptr, nullptr, nullptr, nullptr, nullptr, db.node_logits}, s);
                 else
                 gcn_resident_kernel<false><<<grid, GCNR_WAVES * 64, 0, s>>>(db.h[0], db.csr.row_ptr, db.csr.src, db.csr.ecode, db.csr.out_deg, d_res_, d_pw_,
                                                                            d_pb_, db.gtiles.row_start, db.gtiles.graph_start, db.b.node_off, db.out,
@@ -1346,6 +1378,10 @@ public:
             if (db.emb) {  // (only with db.node_emb: use_resident)
                 ProfScope p(prof, "mean_pool_rows", s);
                 mean_pool_rows_kernel<GCN_D><<<(db.b.num_graphs + 3) / 4, 256, 0, s>>>(db.node_emb, db.b.node_off, db.emb, db.b.num_graphs);
+            }
+            if (db.node_emb && db.node_logits) {  // node embeddings on as well: the rows are in HBM, the terms are taken from them
+                ProfScope p(prof, "node_logits", s);
+                launch_node_logits_rows<GCN_D>(db.node_emb, d_pw_, d_pb_, db.node_logits, n, 1, s);
             }
             agg_ready_ = false;
             db.final_h = 0;
@@ -1404,6 +1440,10 @@ public:
             }
             ProfScope p(prof, "mean_pool_linear", s);
             segment_mean_bias_kernel<0><<<(db.b.num_graphs + 255) / 256, 256, 0, s>>>(db.scratch, db.b.node_off, d_pb_, db.out, db.b.num_graphs);
+            if (db.node_logits) {  // node logits: the per-node scores plus the head's bias
+                ProfScope p2(prof, "node_logits", s);
+                node_logits_bias_kernel<0><<<(n + 255) / 256, 256, 0, s>>>(db.scratch, d_pb_, db.node_logits, n);
+            }
             return 0;
         }
         // the rows the readout pools: in the model's scratch, or straight in the caller's node-embedding buffer (db.node_emb)
@@ -1425,6 +1465,10 @@ public:
         if (db.emb) {
             ProfScope p(prof, "mean_pool_rows", s);
             mean_pool_rows_kernel<GCN_D><<<(db.b.num_graphs + 3) / 4, 256, 0, s>>>(rows, db.b.node_off, db.emb, db.b.num_graphs);
+        }
+        if (db.node_logits) {  // node logits from the rows the readout pools, every task
+            ProfScope p(prof, "node_logits", s);
+            launch_node_logits_rows<GCN_D>(rows, d_pw_, d_pb_, db.node_logits, n, num_tasks_, s);
         }
         return 0;
     }
@@ -1510,19 +1554,25 @@ private:
 };
 
 Model* make_gcn_model() { return new GcnModel(); }
-#endif  // FG_RESIDENT_ROWS_TU
+#endif  // FG_RESIDENT_STORING_TU
 
-#ifdef FG_RESIDENT_ROWS_TU
+#ifdef FG_RESIDENT_STORING_TU
 }  // namespace
+#ifdef FG_RESIDENT_NLOGIT_TU
+#define GCN_STORE_ARG a.node_logits
+void launch_gcn_resident_nlogit(const GcnResidentLaunch& a, hipStream_t s) {
+#else
+#define GCN_STORE_ARG a.node_emb
 void launch_gcn_resident_rows(const GcnResidentLaunch& a, hipStream_t s) {
+#endif
     if (a.onepass)
         gcn_resident_kernel<true><<<a.grid, GCNR_WAVES * 64, 0, s>>>(a.x0, a.row_ptr, a.src, a.ecode, a.out_deg, a.layers, a.pool_w, a.pool_b, a.tile_row,
                                                                      a.tile_graph, a.node_off, a.out, a.n_tiles, a.range_flag, a.ablate, a.desc, a.enc_tab,
-                                                                     a.list, a.lrow, a.node_emb);
+                                                                     a.list, a.lrow, GCN_STORE_ARG);
     else
         gcn_resident_kernel<false><<<a.grid, GCNR_WAVES * 64, 0, s>>>(a.x0, a.row_ptr, a.src, a.ecode, a.out_deg, a.layers, a.pool_w, a.pool_b, a.tile_row,
                                                                       a.tile_graph, a.node_off, a.out, a.n_tiles, a.range_flag, a.ablate, a.desc, a.enc_tab,
-                                                                      a.list, a.lrow, a.node_emb);
+                                                                      a.list, a.lrow, GCN_STORE_ARG);
 }
 #endif
 

@@ -770,7 +770,7 @@ public:
     // the batch's half-tiles on gin_pp_kernel, the few graphs beyond the half-tile limits on gin_resident_kernel.  (Decided from the
     // SHARD's own half-tile fill: unlike the shipped kernels' choices this one does not follow the job -- development only.)
     bool use_pingpong(const DeviceBatch& db) const {
-        return pingpong_ && !f16_ && !virtual_node_ && use_resident(db) && !keep_h_ && num_tasks_ == 1 && fold_readout_ && head_fold_ && db.gtiles.sub_ok &&
+        return pingpong_ && !f16_ && !virtual_node_ && use_resident(db) && !keep_h_ && !db.node_logits && num_tasks_ == 1 && fold_readout_ && head_fold_ && db.gtiles.sub_ok &&
                db.gtiles.n_sub > 0 && db.gtiles.sub_fill >= resident_min_fill_;
     }
 #endif
@@ -823,7 +823,7 @@ public:
             ProfScope p(prof, "gin_resident", s);  // the whole model
             launch_gin_resident(nullptr, nullptr, nullptr, nullptr, nullptr, d_ecomb_res_, rsplit(), d_pw_, d_pb_, t_row, t_graph,
                                 reinterpret_cast<uint8_t*>(perm_.p), db.b.node_off, db.out, n_tiles,
-                                db.range_flag, s, virtual_node_, head(), resident_order_, resident_prof_, &tb, 1, f16_);
+                                db.range_flag, s, virtual_node_, head(), resident_order_, resident_prof_, &tb, 1, f16_, nullptr, db.node_logits);
             db.final_h = 0;
             db.h_valid = false;
             h0_in_hbm_ = false;  // the tile loader computed h_0 on chip
@@ -860,7 +860,9 @@ public:
         if (use_resident(db)) {
             // all five layers and the readout in one launch; h_5 rows are written (to h[1]) only for the flowgnn_get_h tap
             if (int rc = perm_.reserve((size_t)db.gtiles.n_tiles * (GIN_RESIDENT_DESC_BYTES / 4))) return rc;
-            const bool rows = keep_h_ || multi || db.node_emb;
+            // (node logits where the folded instance does not run -- graph embeddings on as well, or un-folded by option: the rows go
+            // to HBM and the terms are taken from them, as the pooled rows are)
+            const bool rows = keep_h_ || multi || db.node_emb || (db.node_logits && (db.emb || !(fold_readout_ && head_fold_)));
             // (node embeddings: the rows go straight into the caller's buffer, and whatever reads h_5 behind the launch reads it there)
             float* const h5 = db.node_emb ? db.node_emb : db.h[1];
             // graph embeddings, single task: the un-folded instance that pools the h_5 rows out of LDS (no row goes to HBM); with the
@@ -871,12 +873,14 @@ public:
                 launch_gin_resident(db.h[0], rows ? h5 : nullptr, db.csr.row_ptr, db.csr.src, db.csr.ecode, d_ecomb_res_, rsplit(), d_pw_, d_pb_,
                                     db.gtiles.row_start, db.gtiles.graph_start, reinterpret_cast<uint8_t*>(perm_.p), db.b.node_off,
                                     multi ? nullptr : db.out, db.gtiles.n_tiles, db.range_flag, s, virtual_node_,
-                                    (!rows && fold_readout_ && head_fold_) ? head() : nullptr, resident_order_, resident_prof_, nullptr, 1, f16_, pool_emb);
+                                    (!rows && fold_readout_ && head_fold_) ? head() : nullptr, resident_order_, resident_prof_, nullptr, 1, f16_, pool_emb,
+                                    db.node_logits);
             }
             db.final_h = rows ? 1 : 0;
             db.h_valid = rows && !db.node_emb;
             if (multi) launch_readout_mt(db, h5, prof, s);
             if (rows) launch_pool_rows(db, h5, prof, s);
+            if (rows) launch_node_logits(db, h5, prof, s);  // (else the folded instance stored them)
             return 0;
         }
         int cur = 0;
@@ -926,6 +930,11 @@ public:
         db.h_valid = !folded && !db.node_emb;
         const float* const h5 = db.node_emb ? db.node_emb : db.h[cur];
         if (!folded) launch_pool_rows(db, h5, prof, s);
+        if (!folded) launch_node_logits(db, h5, prof, s);
+        else if (db.node_logits) {  // the folded last layer left h_5[v] . w in db.scratch: the term is that plus the bias
+            ProfScope p(prof, "node_logits", s);
+            node_logits_bias_kernel<0><<<(n + 255) / 256, 256, 0, s>>>(db.scratch, d_pb_, db.node_logits, n);
+        }
         if (multi) {
             launch_readout_mt(db, h5, prof, s);
             return 0;
@@ -947,6 +956,13 @@ public:
         if (!db.emb) return;
         ProfScope p(prof, "mean_pool_rows", s);
         mean_pool_rows_kernel<GIN_D><<<(db.b.num_graphs + 3) / 4, 256, 0, s>>>(h, db.b.node_off, db.emb, db.b.num_graphs);
+    }
+
+    // node logits from h_5 rows that are in HBM (per-layer path, NUM_TASK > 1, taps, embeddings on as well): every task
+    void launch_node_logits(DeviceBatch& db, const float* h, Profiler& prof, hipStream_t s) {
+        if (!db.node_logits) return;
+        ProfScope p(prof, "node_logits", s);
+        launch_node_logits_rows<GIN_D>(h, d_pw_, d_pb_, db.node_logits, db.b.n_tot, num_tasks_, s);
     }
 
     void launch_readout_mt(DeviceBatch& db, const float* h, Profiler& prof, hipStream_t s) {

@@ -83,7 +83,8 @@ void launch_gin_resident(const float* h0, float* hout, const int* row_ptr, const
                          uint8_t* tile_desc /* scratch, n_tiles x GIN_RESIDENT_DESC_BYTES */, const int* node_off, float* out, int n_tiles,
                          int* range_flag, hipStream_t s, bool hubs = false, const float* head_u = nullptr, int col_order = 0, bool prof = false,
                          const GinTileBuild* tb = nullptr, int tstride = 1, bool f16 = false /* single-product instances, FLOWGNN_NUMERIC_F16 */,
-                         float* emb = nullptr /* [G][100]: the per-graph mean of the h_5 rows, pooled inside the un-folded kernel (out [G] required) */);
+                         float* emb = nullptr /* [G][100]: the per-graph mean of the h_5 rows, pooled inside the un-folded kernel (out [G] required) */,
+                         float* node_logits = nullptr /* [N]: every node's term of the folded readout, caller order (folded forms only: head_u, out, no hout) */);
 // head_u for launch_gin_resident (GIN_RESIDENT_HEAD_FLOATS floats): the single-task readout folded through the LAST layer's second
 // linear layer -- u = W2^T w_pred divided by the first layer's power-of-two weight scale, padded to 208, then c = b2 . w_pred
 constexpr int GIN_RESIDENT_HEAD_FLOATS = 209;

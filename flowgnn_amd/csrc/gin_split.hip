@@ -50,6 +50,12 @@
 #ifndef GS_POOL_TU
 #define GS_POOL_TU 0
 #endif
+// Node-logit instances (flowgnn_set_node_logits): gin_split_nlogit.hip compiles this file a fourth time with GS_NLOGIT_TU = 1, for the
+// FOLDED resident kernel's instances that also store every node's term of the readout (gin_resident_nlogit_kernel<HUBS, ENC, F16>) and
+// their launcher alone, in the same way.
+#ifndef GS_NLOGIT_TU
+#define GS_NLOGIT_TU 0
+#endif
 
 namespace fg {
 
@@ -1747,6 +1753,8 @@ __device__ __forceinline__ void gr_layer(unsigned long long (&tacc)[6], char* bx
 // requested, all at once as in the prologue: that load is the price of this form (graph embeddings).
 #if GS_POOL_TU
 template <bool HUBS, bool F16>
+#elif GS_NLOGIT_TU
+template <bool HUBS, bool ENC, bool F16>
 #else
 template <bool PROF, bool HUBS, bool FOLD, bool ENC>
 #endif
@@ -1763,11 +1771,17 @@ __global__ __launch_bounds__(GR_WAVES * 64, 2) void gin_resident_kernel(const fl
                                                                        const int* __restrict__ list, const int* __restrict__ lrow
 #if GS_POOL_TU
                                                                        , float* __restrict__ emb) {
-    constexpr bool PROF = false, FOLD = false, ENC = false, POOL = true;
+    constexpr bool PROF = false, FOLD = false, ENC = false, POOL = true, NLOGIT = false;
+    float* const node_logits = nullptr;
+#elif GS_NLOGIT_TU
+                                                                       , float* __restrict__ node_logits) {
+    constexpr bool PROF = false, FOLD = true, POOL = false, NLOGIT = true;
+    float* const emb = nullptr;
 #else
                                                                        ) {
-    constexpr bool POOL = false, F16 = GS_F16;
+    constexpr bool POOL = false, F16 = GS_F16, NLOGIT = false;
     float* const emb = nullptr;
+    float* const node_logits = nullptr;
 #endif
     static_assert(!ENC || FOLD, "the in-kernel encoder rides on the folded last layer's steps");
     static_assert(!POOL || (!FOLD && !ENC), "the pooling instance is the un-folded one");
@@ -1855,6 +1869,22 @@ __global__ __launch_bounds__(GR_WAVES * 64, 2) void gin_resident_kernel(const fl
                     out[gph] = sum / (float)(n1 - n0) + pool_b[0] + head_c;
                 }
             }
+            if constexpr (NLOGIT) {
+                // node logits: the same terms plus the readout's constant.  A graph's rows are one run in the tile (from lrow[gi], or
+                // n0 - cur.t0) and one run in the batch (from node_off[gph]); a quarter-wave walks a run, sixteen nodes -- one 64-byte
+                // segment -- per trip, and the tile's graphs are dealt to the 32 quarter-waves of the workgroup, so a tile of
+                // molecule-sized graphs is stored in one or two trips.  (A lane per graph, as the readout's sum has it, would store
+                // 4 bytes per lane at a stride of a graph.)  Like the readout it needs no barrier: every wave reads the terms before it
+                // enters the next tile's layers, and they are rewritten in that tile's LAST layer, several barriers on.
+                const float cst = pool_b[0] + head_c;
+                const int j = lane & 15;
+                for (int gi = cur.g0 + wave * 4 + (lane >> 4); gi < cur.g1; gi += GR_WAVES * 4) {
+                    const int gph = list ? list[gi] : gi;
+                    const int n0 = node_off[gph], n = node_off[gph + 1] - n0;
+                    const float* t = s_dot + (list ? lrow[gi] : n0 - cur.t0);
+                    for (int k = j; k < n; k += 16) node_logits[(size_t)n0 + k] = t[k] + cst;
+                }
+            }
         }
         if (!has_next) break;
         tile = ntile;
@@ -1876,7 +1906,7 @@ __global__ __launch_bounds__(GR_WAVES * 64, 2) void gin_resident_kernel(const fl
 #include "dev/gin_pp_device.inc"  // gin_pp_kernel: the ping-pong form, measured slower -- development builds only
 #endif
 
-#if !GS_POOL_TU
+#if !GS_POOL_TU && !GS_NLOGIT_TU
 // this translation unit's per-layer kernels (GS_F16: which instance)
 void launch_split_nt(const float* h, float* hout, const int* row_ptr, const int* src, const uint8_t* ecode, const float* ecomb,
                      const uint8_t* chunks, int n_tot, int relu_out, int* range_flag, int nt, hipStream_t s, const float* pool_w) {
@@ -1917,7 +1947,7 @@ void gr_dispatch(bool prof, bool hubs, bool fold, bool enc, int grid, hipStream_
 #undef GR_LAUNCH_FE
 #undef GR_LAUNCH
 }
-#endif  // !GS_POOL_TU
+#endif  // !GS_POOL_TU && !GS_NLOGIT_TU
 
 #if !GS_SINGLE_PRODUCT
 inline float pow2_scale(const float* w, size_t n) {
@@ -1950,6 +1980,24 @@ void gin_resident_pool_dispatch(bool hubs, bool f16, int grid, hipStream_t s, co
     else { if (hubs) GR_LAUNCH_POOL(true, false); else GR_LAUNCH_POOL(false, false); }
 #undef GR_LAUNCH_POOL
 }
+#elif GS_NLOGIT_TU
+void gin_resident_nlogit_dispatch(bool hubs, bool enc, bool f16, int grid, hipStream_t s, const float* h0, const float* ecomb_all,
+                                  const uint8_t* chunks_all, const float* pool_w, const float* pool_b, const int* tile_row, const int* tile_graph,
+                                  const uint8_t* tile_desc, const int* node_off, float* out, int n_tiles, int* range_flag, const float* head_u,
+                                  const uint32_t* eidx, const float4* etab, int tstride, const int* list, const int* lrow, float* node_logits) {
+#define GR_LAUNCH_NLOGIT(H, E, F)                                                                                                              \
+    gin_resident_kernel<H, E, F><<<grid, GR_WAVES * 64, 0, s>>>(h0, nullptr, ecomb_all, chunks_all, pool_w, pool_b, tile_row, tile_graph, tile_desc, \
+                                                                node_off, out, n_tiles, range_flag, nullptr, head_u, eidx, etab, tstride, list, lrow, \
+                                                                node_logits)
+#define GR_LAUNCH_NLOGIT_EF(H)                                                                  \
+    do {                                                                                        \
+        if (enc) { if (f16) GR_LAUNCH_NLOGIT(H, true, true); else GR_LAUNCH_NLOGIT(H, true, false); }   \
+        else { if (f16) GR_LAUNCH_NLOGIT(H, false, true); else GR_LAUNCH_NLOGIT(H, false, false); }     \
+    } while (0)
+    if (hubs) GR_LAUNCH_NLOGIT_EF(true); else GR_LAUNCH_NLOGIT_EF(false);
+#undef GR_LAUNCH_NLOGIT_EF
+#undef GR_LAUNCH_NLOGIT
+}
 #elif GS_SINGLE_PRODUCT
 // the entry points of the single-product instances (called by the launchers of gin_split.hip's own translation unit)
 void launch_gin_layer_split_f16(const float* h, float* hout, const int* row_ptr, const int* src, const uint8_t* ecode, const float* ecomb,
@@ -1977,6 +2025,12 @@ void gin_resident_dispatch_f16(bool prof, bool hubs, bool fold, bool enc, int gr
 void gin_resident_pool_dispatch(bool hubs, bool f16, int grid, hipStream_t s, const float* h0, const float* ecomb_all, const uint8_t* chunks_all,
                                 const float* pool_w, const float* pool_b, const int* tile_row, const int* tile_graph, const uint8_t* tile_desc,
                                 const int* node_off, float* out, int n_tiles, int* range_flag, int tstride, float* emb);
+
+// (gin_split_nlogit.hip) the folded instances that also store the per-node readout terms into node_logits [N], caller order
+void gin_resident_nlogit_dispatch(bool hubs, bool enc, bool f16, int grid, hipStream_t s, const float* h0, const float* ecomb_all,
+                                  const uint8_t* chunks_all, const float* pool_w, const float* pool_b, const int* tile_row, const int* tile_graph,
+                                  const uint8_t* tile_desc, const int* node_off, float* out, int n_tiles, int* range_flag, const float* head_u,
+                                  const uint32_t* eidx, const float4* etab, int tstride, const int* list, const int* lrow, float* node_logits);
 
 void gin_split_pack_layer(const float* w1, const float* b1, const float* w2, const float* b2, uint8_t* out, bool f16) {
     std::memset(out, 0, GS_LAYER_BYTES);
@@ -2137,7 +2191,8 @@ void launch_gin_layer_split(const float* h, float* hout, const int* row_ptr, con
 void launch_gin_resident(const float* h0, float* hout, const int* row_ptr, const int* src, const uint8_t* ecode, const float* ecomb_all,
                          const uint8_t* chunks_all, const float* pool_w, const float* pool_b, const int* tile_row, const int* tile_graph,
                          uint8_t* tile_desc, const int* node_off, float* out, int n_tiles, int* range_flag, hipStream_t s, bool hubs,
-                         const float* head_u, int col_order, bool prof, const GinTileBuild* tb, int tstride, bool f16, float* emb) {
+                         const float* head_u, int col_order, bool prof, const GinTileBuild* tb, int tstride, bool f16, float* emb,
+                         float* node_logits) {
     if (n_tiles <= 0) return;
     const int order = hubs ? 3 : col_order;
     if (emb != nullptr) { head_u = nullptr; hout = nullptr; prof = false; }  // the pooling instance: un-folded, no tap, no phase stamps
@@ -2156,6 +2211,13 @@ void launch_gin_resident(const float* h0, float* hout, const int* row_ptr, const
     if (emb != nullptr) {
         gin_resident_pool_dispatch(hubs, f16, grid, s, h0, ecomb_all, chunks_all, pool_w, pool_b, tile_row, tile_graph, tile_desc, node_off, out,
                                    n_tiles, range_flag, tstride, emb);
+        return;
+    }
+    if (node_logits != nullptr && fold) {  // the folded instance that also stores the per-node terms (no phase stamps)
+        gin_resident_nlogit_dispatch(hubs, enc, f16, grid, s, h0, ecomb_all, chunks_all, pool_w, pool_b, tile_row, tile_graph, tile_desc, node_off,
+                                     out, n_tiles, range_flag, head_u, eidx, etab, tstride, enc ? tb->list : nullptr, enc ? tb->lrow : nullptr,
+                                     node_logits);
+        if (d) (void)hipFree(d);
         return;
     }
     (f16 ? gin_resident_dispatch_f16 : gr_dispatch)(prof, hubs, fold, enc, grid, s, h0, hout, ecomb_all, chunks_all, pool_w, pool_b, tile_row,

@@ -235,6 +235,7 @@ int flowgnn_group_set_numeric_mode(flowgnn_group* g, int mode) { return group_al
 
 int flowgnn_group_set_embeddings(flowgnn_group* g, int on) { return group_all(g, [&](flowgnn_engine* e) { return flowgnn_set_embeddings(e, on); }); }
 int flowgnn_group_set_node_embeddings(flowgnn_group* g, int on) { return group_all(g, [&](flowgnn_engine* e) { return flowgnn_set_node_embeddings(e, on); }); }
+int flowgnn_group_set_node_logits(flowgnn_group* g, int on) { return group_all(g, [&](flowgnn_engine* e) { return flowgnn_set_node_logits(e, on); }); }
 
 int flowgnn_group_set_batch(flowgnn_group* g, int num_graphs, const int* nums_of_nodes, const int* nums_of_edges,
                             const int* node_feature, const int* edge_list, const int* edge_attr, const float* node_eigen) {
@@ -332,6 +333,22 @@ int flowgnn_group_get_node_embeddings(flowgnn_group* g, float* out_host) {
         flowgnn_engine* e = g->eng[(size_t)i];
         if (e->G == 0) return e->nemb_on ? flowgnn_sync(e) : (int)FLOWGNN_ERR_STATE;
         return flowgnn_get_node_embeddings(e, out_host + first[(size_t)i] * dim);
+    });
+}
+
+// [N_tot][NUM_TASK] in job order, likewise
+int flowgnn_group_get_node_logits(flowgnn_group* g, float* out_host) {
+    if (!g) return FLOWGNN_ERR_ARG;
+    g->err.clear();
+    if (!g->batch_valid) return group_fail(g, FLOWGNN_ERR_STATE, "flowgnn_group_get_node_logits: no batch set by flowgnn_group_set_batch (flowgnn_group_compute and the entry points leave none)");
+    if (int rc = group_shards_intact(g, "flowgnn_group_get_node_logits")) return rc;
+    std::vector<size_t> first(g->eng.size() + 1, 0);
+    for (size_t i = 0; i < g->eng.size(); i++) first[i + 1] = first[i] + (size_t)g->eng[i]->N;
+    if (!out_host && first.back() > 0) return group_fail(g, FLOWGNN_ERR_ARG, "flowgnn_group_get_node_logits: null output");
+    return group_each(g, [&](int i) {
+        flowgnn_engine* e = g->eng[(size_t)i];
+        if (e->G == 0) return e->nlog_on ? flowgnn_sync(e) : (int)FLOWGNN_ERR_STATE;
+        return flowgnn_get_node_logits(e, out_host + first[(size_t)i] * (size_t)e->num_tasks);
     });
 }
 

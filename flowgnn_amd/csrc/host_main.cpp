@@ -2,7 +2,7 @@
 // OpenCL host (GIN/src/host.cc): load the model's .bin weights, read a graph pack in the reference's on-disk
 // layout, run the whole dataset as ONE batched launch NUM_TRIALS times, write HLS_output.txt.
 //
-//   host <MODEL> [--graphs DIR] [--weights DIR] [--num-graphs N] [--trials T] [--out FILE] [--device D | --devices D0,D1,..] [--option key=value] [--numeric f32|q6.10|f16] [XCLBIN]
+//   host <MODEL> [--graphs DIR] [--weights DIR] [--num-graphs N] [--trials T] [--out FILE] [--node-logits FILE] [--device D | --devices D0,D1,..] [--option key=value] [--numeric f32|q6.10|f16] [XCLBIN]
 //
 //   MODEL        GIN | GIN-VN | GCN | GAT | PNA | DGN
 //   --graphs     directory holding graph_info/ and graph_bin/      (default ../graphs, host.cc:14-15)
@@ -11,6 +11,7 @@
 //                (the reference compiles it in: common/includes/dataset/dataset.hpp)
 //   --trials     launches to time                                   (default 25 = NUM_TRIALS, host.h:8)
 //   --out        result file                                        (default HLS_output.txt, host.cc:213)
+//   --node-logits one more run behind the timed ones, with flowgnn_set_node_logits on: one line per node, NUM_TASK values (GIN, GIN-VN, GCN, GAT)
 //   XCLBIN       accepted and ignored, so `./host <xclbin>`-style command lines keep working
 //
 // Only the C ABI of include/flowgnn.h is used; no HIP or torch types here.
@@ -76,13 +77,13 @@ static bool read_eig_txt(const std::string& path, std::vector<float>& eig, size_
 int main(int argc, char** argv) {
     if (argc < 2) {
         fprintf(stderr, "Usage: %s <GIN|GIN-VN|GCN|GAT|PNA|DGN> [--graphs DIR] [--weights DIR] [--num-graphs N] [--trials T] "
-                        "[--out FILE] [--embeddings FILE] [--node-embeddings FILE] [--device D | --devices D0,D1,..] [--option key=value] [--numeric f32|q6.10|f16] [--num-tasks T] [XCLBIN File]\n", argv[0]);
+                        "[--out FILE] [--embeddings FILE] [--node-embeddings FILE] [--node-logits FILE] [--device D | --devices D0,D1,..] [--option key=value] [--numeric f32|q6.10|f16] [--num-tasks T] [XCLBIN File]\n", argv[0]);
         return EXIT_FAILURE;
     }
     const std::string model = argv[1];
     const int mid = model_id(model);
     if (mid < 0) { fprintf(stderr, "unknown model %s\n", model.c_str()); return EXIT_FAILURE; }
-    std::string graphs = "../graphs", wdir = ".", out_path = "HLS_output.txt", eig_dir = "eig", emb_path, nemb_path;
+    std::string graphs = "../graphs", wdir = ".", out_path = "HLS_output.txt", eig_dir = "eig", emb_path, nemb_path, nlog_path;
     long num_graphs = -1;
     int trials = 25, numeric = FLOWGNN_NUMERIC_F32, num_tasks = 1;
     std::vector<int> devices;
@@ -99,6 +100,7 @@ int main(int argc, char** argv) {
         else if (a == "--num-graphs") num_graphs = atol(next("--num-graphs"));
         else if (a == "--trials") trials = atoi(next("--trials"));
         else if (a == "--out") out_path = next("--out");
+        else if (a == "--node-logits") nlog_path = next("--node-logits");  // the per-node terms of the readout, one line of NUM_TASK values per node
         else if (a == "--node-embeddings") nemb_path = next("--node-embeddings");  // the rows that pool is taken over, one line of dim values per node
         else if (a == "--embeddings") emb_path = next("--embeddings");  // the per-graph pooled embeddings, one line of dim values per graph
         else if (a == "--device") { devices.clear(); devices.push_back(atoi(next("--device"))); }
@@ -249,6 +251,22 @@ int main(int argc, char** argv) {
         for (size_t v = 0; v < n_tot; v++)
             for (int d = 0; d < dim; d++) fprintf(nf, d + 1 < dim ? "%.8f " : "%.8f\n", rows[v * dim + d]);
         fclose(nf);
+    }
+    if (!nlog_path.empty()) {
+        // likewise one more run, with node logits on (and both kinds of embeddings off again)
+        const size_t n_tot = N;
+        std::vector<float> terms(n_tot * num_tasks);
+        rc = flowgnn_group_set_embeddings(eng, 0);
+        if (!rc) rc = flowgnn_group_set_node_embeddings(eng, 0);
+        if (!rc) rc = flowgnn_group_set_node_logits(eng, 1);
+        if (!rc) rc = flowgnn_group_run(eng);
+        if (!rc) rc = flowgnn_group_get_node_logits(eng, terms.data());
+        if (rc) { fprintf(stderr, "--node-logits: %d %s\n", rc, flowgnn_group_last_error(eng)); return EXIT_FAILURE; }
+        FILE* lf = fopen(nlog_path.c_str(), "w");
+        if (!lf) { fprintf(stderr, "cannot write %s\n", nlog_path.c_str()); return EXIT_FAILURE; }
+        for (size_t v = 0; v < n_tot; v++)
+            for (int t = 0; t < num_tasks; t++) fprintf(lf, t + 1 < num_tasks ? "%.8f " : "%.8f\n", terms[v * num_tasks + t]);
+        fclose(lf);
     }
     flowgnn_group_destroy(eng);
     return 0;

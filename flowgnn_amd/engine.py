@@ -96,6 +96,7 @@ class Engine:
         self._results_tensor = None  # (forward_device's output: released once the engine, and its stream, are gone)
         self._embeddings_tensor = None
         self._node_embeddings_tensor = None
+        self._node_logits_tensor = None
 
     def __del__(self):
         try:
@@ -234,7 +235,7 @@ class Engine:
                 t.record_stream(cur)
 
     def forward_device(self, x, edge_index, edge_attr=None, node_eigen=None, *, ptr, nums_of_edges=None, return_embeddings=False,
-                       return_node_embeddings=False):
+                       return_node_embeddings=False, return_node_logits=False):
         """set_batch_device, then one forward into a new torch tensor on the device ([G], or [G][num_tasks]); torch's current stream
         waits for the engine's, the host does not.  Validation errors (and the range check that can repeat a pass on the exact
         kernels) are seen by sync(), which raises; without it the tensor of a refused batch holds whatever the kernels wrote.
@@ -242,7 +243,9 @@ class Engine:
         by the kernels themselves (flowgnn_set_embeddings_buffer); embeddings stay on for later runs (set_embeddings(False) ends it).
         return_node_embeddings: the node embeddings ([N][embedding_dim], in the order of the rows of x, i.e. of the PyG Batch's nodes)
         in a new device tensor, appended to the returned tuple; written by the kernels themselves
-        (flowgnn_set_node_embeddings_buffer), and on for later runs until set_node_embeddings(False)."""
+        (flowgnn_set_node_embeddings_buffer), and on for later runs until set_node_embeddings(False).
+        return_node_logits: the per-node terms of the readout ([N], or [N][num_tasks], in the order of the rows of x) in a new device
+        tensor, appended last; written by the kernels themselves (flowgnn_set_node_logits_buffer), on until set_node_logits(False)."""
         import torch
         dev = torch.device("cuda", self.device)
         cur = torch.cuda.current_stream(dev)
@@ -256,6 +259,11 @@ class Engine:
         if return_node_embeddings:
             rows = torch.empty((int(x.shape[0]), embedding_dim(self.model)), dtype=torch.float32, device=dev)
             self.set_node_embeddings(True)
+        terms = None
+        if return_node_logits:
+            n_rows = int(x.shape[0])
+            terms = torch.empty((n_rows, self.num_tasks) if self.num_tasks > 1 else (n_rows,), dtype=torch.float32, device=dev)
+            self.set_node_logits(True)
         self.set_batch_device(x, edge_index, edge_attr, node_eigen, ptr=ptr, nums_of_edges=nums_of_edges)
         es = torch.cuda.ExternalStream(self.stream_handle(), device=dev)
         if G:
@@ -267,10 +275,13 @@ class Engine:
             if rows is not None:
                 self.set_node_embeddings_buffer(rows.data_ptr())
                 self._node_embeddings_tensor = rows
+            if terms is not None:
+                self.set_node_logits_buffer(terms.data_ptr())
+                self._node_logits_tensor = terms
         self.run()
         cur.wait_stream(es)
         logits = out.view(G, self.num_tasks) if self.num_tasks > 1 else out
-        ret = (logits,) + ((emb,) if return_embeddings else ()) + ((rows,) if return_node_embeddings else ())
+        ret = (logits,) + ((emb,) if return_embeddings else ()) + ((rows,) if return_node_embeddings else ()) + ((terms,) if return_node_logits else ())
         return ret if len(ret) > 1 else logits
 
     def run(self):
@@ -297,16 +308,21 @@ class Engine:
     def set_results_buffer(self, device_ptr: int):
         self._check(self.lib.flowgnn_set_results_buffer(self._h, C.c_void_p(device_ptr)), "flowgnn_set_results_buffer")
 
-    def forward(self, batch: GraphBatch, return_embeddings: bool = False, return_node_embeddings: bool = False):
+    def forward(self, batch: GraphBatch, return_embeddings: bool = False, return_node_embeddings: bool = False,
+                return_node_logits: bool = False):
         """set_batch + run + results; return_embeddings: (logits, embeddings) -- embeddings stay on for later runs;
-        return_node_embeddings: the node embeddings [N][embedding_dim] appended to the tuple (they stay on likewise)."""
+        return_node_embeddings: the node embeddings [N][embedding_dim] appended to the tuple (they stay on likewise);
+        return_node_logits: the per-node readout terms [N] or [N][num_tasks] appended last (likewise)."""
         if return_embeddings:
             self.set_embeddings(True)
         if return_node_embeddings:
             self.set_node_embeddings(True)
+        if return_node_logits:
+            self.set_node_logits(True)
         self.set_batch(batch)
         self.run()
         ret = (self.results(),) + ((self.embeddings(),) if return_embeddings else ()) + ((self.node_embeddings(),) if return_node_embeddings else ())
+        ret += (self.node_logits(),) if return_node_logits else ()
         return ret if len(ret) > 1 else ret[0]
 
     # ---- graph embeddings (flowgnn.h: flowgnn_set_embeddings)
@@ -350,6 +366,28 @@ class Engine:
         """Caller-owned device buffer of >= N * embedding_dim floats for the node embeddings; None / 0 restores the engine's own."""
         self._check(self.lib.flowgnn_set_node_embeddings_buffer(self._h, C.c_void_p(device_ptr) if device_ptr else None),
                     "flowgnn_set_node_embeddings_buffer")
+
+    # ---- node logits (flowgnn.h: flowgnn_set_node_logits; GIN, GIN-VN, GCN, GAT)
+    def set_node_logits(self, on: bool = True):
+        """Runs enqueued after this also store, per node and in the caller's node order, the node's term of the readout:
+        r[v] . W[t] + b[t], whose mean over a graph's nodes is the graph's logit."""
+        self._check(self.lib.flowgnn_set_node_logits(self._h, 1 if on else 0), "flowgnn_set_node_logits")
+
+    def node_logits(self) -> np.ndarray:
+        """[N], or [N][num_tasks], of the last run (synchronises); FLOWGNN_ERR_STATE if that run had node logits off."""
+        out = np.empty((self.total_nodes, self.num_tasks) if self.num_tasks > 1 else (self.total_nodes,), dtype=np.float32)
+        self._check(self.lib.flowgnn_get_node_logits(self._h, _pf(out)), "flowgnn_get_node_logits")
+        return out
+
+    def node_logits_device_ptr(self) -> int:
+        p = C.c_void_p()
+        self._check(self.lib.flowgnn_node_logits_device(self._h, C.byref(p)), "flowgnn_node_logits_device")
+        return int(p.value or 0)
+
+    def set_node_logits_buffer(self, device_ptr: Optional[int]):
+        """Caller-owned device buffer of >= N * num_tasks floats for the node logits; None / 0 restores the engine's own."""
+        self._check(self.lib.flowgnn_set_node_logits_buffer(self._h, C.c_void_p(device_ptr) if device_ptr else None),
+                    "flowgnn_set_node_logits_buffer")
 
     # ---- taps
     def set_numeric_mode(self, mode: str = "f32"):
@@ -508,6 +546,15 @@ class EngineGroup:
         """[N][embedding_dim(model)] of the last run, in job order (flowgnn.h: flowgnn_group_get_node_embeddings)."""
         out = np.empty((self.total_nodes, embedding_dim(self.model)), dtype=np.float32)
         self._check(self.lib.flowgnn_group_get_node_embeddings(self._h, _pf(out)), "flowgnn_group_get_node_embeddings")
+        return out
+
+    def set_node_logits(self, on: bool = True):
+        self._check(self.lib.flowgnn_group_set_node_logits(self._h, 1 if on else 0), "flowgnn_group_set_node_logits")
+
+    def node_logits(self) -> np.ndarray:
+        """[N], or [N][num_tasks], of the last run, in job order (flowgnn.h: flowgnn_group_get_node_logits)."""
+        out = np.empty((self.total_nodes, self.num_tasks) if self.num_tasks > 1 else (self.total_nodes,), dtype=np.float32)
+        self._check(self.lib.flowgnn_group_get_node_logits(self._h, _pf(out)), "flowgnn_group_get_node_logits")
         return out
 
     def forward(self, batch: GraphBatch) -> np.ndarray:

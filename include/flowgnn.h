@@ -374,6 +374,38 @@ int flowgnn_get_node_embeddings(flowgnn_engine* e, float* out_host);
 int flowgnn_node_embeddings_device(flowgnn_engine* e, void** d_rows);
 int flowgnn_set_node_embeddings_buffer(flowgnn_engine* e, void* device_ptr);
 
+/*
+ * Node logits (GIN, GIN-VN, GCN, GAT): these four models read out with a mean pool and a linear head, so a graph's logit is the
+ * mean of one number per node,
+ *     node_logit[v][t] = r[v] . W[t] + b[t]                                         (fp32, [N_tot][NUM_TASK])
+ *     logit[g][t]      = (1 / n_g) * sum over the nodes v of g of node_logit[v][t]
+ * with r[v] the row flowgnn_set_node_embeddings returns, W / b the head, and v the node's position in the batch AS THE CALLER
+ * PASSED IT (GIN-VN: the virtual nodes are nodes).  An exact additive attribution of a graph's prediction to its nodes, and a
+ * per-node output for node-level use -- 4 bytes per node and task where the row is 64 or 400.
+ *  flowgnn_set_node_logits(e, 1): the runs enqueued after it also store the terms.  Off by default, and off means off: the same
+ *     kernels launch with the same arguments.  While it is on, alone, the batch stays on the kernels it runs on with it off and
+ *     the graph logits keep their bits: on the graph-resident path the instances gin_resident_nlogit_kernel /
+ *     gcn_resident_nlogit_kernel / gat_resident_nlogit_kernel are the default kernels plus one 4-byte store per node of the term
+ *     they hold in LDS anyway (GAT included: it keeps its graph-resident launch); the folded per-layer paths add the constant to
+ *     the per-node scores they leave in device memory; wherever the rows themselves are in device memory (un-folded paths,
+ *     NUM_TASK > 1, the exact-fp32 re-run, graph or node embeddings on as well) one small kernel takes rows[v] . W[t] + b[t], a
+ *     fixed summation order per value.  No atomics anywhere.
+ *     FLOWGNN_ERR_UNSUPPORTED for PNA and DGN: they read the pooled vector through an MLP head, so no such decomposition exists.
+ *     FLOWGNN_ERR_UNSUPPORTED in FLOWGNN_NUMERIC_Q6_10, and flowgnn_set_numeric_mode answers the same for that mode while node
+ *     logits are on.  Drops a recorded launch sequence (option hipgraph).  Survives flowgnn_set_batch.  Works together with
+ *     flowgnn_set_embeddings, flowgnn_set_node_embeddings, NUM_TASK > 1, FLOWGNN_NUMERIC_F16 (GIN / GIN-VN) and option hipgraph.
+ *     The <M>_compute_graphs entry points never produce them.
+ *  flowgnn_get_node_logits: copy [N_tot][NUM_TASK] to the host (synchronises first; an exact-fp32 re-run refills them with the
+ *     logits).  FLOWGNN_ERR_STATE when the last run did not have node logits on.
+ *  flowgnn_node_logits_device: where the last run put them (same condition); valid until the next flowgnn_set_batch.
+ *  flowgnn_set_node_logits_buffer: redirect them into a caller-owned DEVICE buffer of at least N_tot * NUM_TASK floats; NULL
+ *     restores the engine's own buffer; reset by flowgnn_set_batch; drops a recorded launch sequence.
+ */
+int flowgnn_set_node_logits(flowgnn_engine* e, int on);
+int flowgnn_get_node_logits(flowgnn_engine* e, float* out_host);
+int flowgnn_node_logits_device(flowgnn_engine* e, void** d_terms);
+int flowgnn_set_node_logits_buffer(flowgnn_engine* e, void* device_ptr);
+
 /* The engine's hipStream_t as an opaque pointer (for event timing by a caller). */
 int flowgnn_stream(flowgnn_engine* e, void** stream);
 
@@ -529,6 +561,9 @@ int flowgnn_group_get_embeddings(flowgnn_group* g, float* out_host);
 /* flowgnn_set_node_embeddings on every member; flowgnn_group_get_node_embeddings writes [N_tot][dim] in job order (the shards are contiguous graph ranges). */
 int flowgnn_group_set_node_embeddings(flowgnn_group* g, int on);
 int flowgnn_group_get_node_embeddings(flowgnn_group* g, float* out_host);
+/* flowgnn_set_node_logits on every member; flowgnn_group_get_node_logits writes [N_tot][NUM_TASK] in job order. */
+int flowgnn_group_set_node_logits(flowgnn_group* g, int on);
+int flowgnn_group_get_node_logits(flowgnn_group* g, float* out_host);
 /* set_batch + run + get_results for a batch in HOST memory, cut into size x chunks_per_engine ranges; engine i takes ranges
  * i, i + size, ... in turn, so that one engine's copies overlap the others' kernels.  out_host: [num_graphs][NUM_TASK]. */
 int flowgnn_group_compute(flowgnn_group* g, int num_graphs, const int* nums_of_nodes, const int* nums_of_edges,
