@@ -58,6 +58,11 @@ def _declare(lib):
     lib.flowgnn_get_node_logits.argtypes = [eng, p_float]
     lib.flowgnn_node_logits_device.argtypes = [eng, C.POINTER(C.c_void_p)]
     lib.flowgnn_set_node_logits_buffer.argtypes = [eng, C.c_void_p]
+    lib.flowgnn_attention_shape.argtypes = [C.c_int, p_int, p_int]
+    lib.flowgnn_set_attention.argtypes = [eng, C.c_int]
+    lib.flowgnn_get_attention.argtypes = [eng, p_float, p_float]
+    lib.flowgnn_attention_device.argtypes = [eng, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    lib.flowgnn_set_attention_buffers.argtypes = [eng, C.c_void_p, C.c_void_p]
     lib.flowgnn_stream.argtypes = [eng, C.POINTER(C.c_void_p)]
     lib.flowgnn_batch_info.argtypes = [eng] + [C.POINTER(C.c_longlong)] * 3
     lib.flowgnn_batch_tiles.argtypes = [eng] + [C.POINTER(C.c_int)] * 2
@@ -110,6 +115,8 @@ def _declare(lib):
     lib.flowgnn_group_get_node_embeddings.argtypes = [grp, p_float]
     lib.flowgnn_group_set_node_logits.argtypes = [grp, C.c_int]
     lib.flowgnn_group_get_node_logits.argtypes = [grp, p_float]
+    lib.flowgnn_group_set_attention.argtypes = [grp, C.c_int]
+    lib.flowgnn_group_get_attention.argtypes = [grp, p_float, p_float]
     lib.flowgnn_group_compute.argtypes = [grp, C.c_int, p_int, p_int, p_int, p_int, p_int, p_float, p_float, C.c_int]
     lib.GIN_compute_graphs_mt.argtypes = [C.c_int, p_int, p_int, p_int, p_float, p_int, p_int, p_int] + [p_float] * 8 + [C.c_int]
     lib.GCN_compute_graphs_mt.argtypes = [C.c_int, p_int, p_int, p_int, p_float, p_int, p_int, p_int] + [p_float] * 11 + [C.c_int]
@@ -134,6 +141,8 @@ def _declare(lib):
                  "flowgnn_set_node_embeddings_buffer", "flowgnn_group_set_node_embeddings", "flowgnn_group_get_node_embeddings",
                  "flowgnn_set_node_logits", "flowgnn_get_node_logits", "flowgnn_node_logits_device",
                  "flowgnn_set_node_logits_buffer", "flowgnn_group_set_node_logits", "flowgnn_group_get_node_logits",
+                 "flowgnn_attention_shape", "flowgnn_set_attention", "flowgnn_get_attention", "flowgnn_attention_device",
+                 "flowgnn_set_attention_buffers", "flowgnn_group_set_attention", "flowgnn_group_get_attention",
                  "GIN_compute_graphs_mt", "GCN_compute_graphs_mt", "GIN_compute_graphs", "GCN_compute_graphs", "PNA_compute_graphs", "DGN_compute_graphs", "GAT_compute_graphs"):
         getattr(lib, name).restype = C.c_int
 

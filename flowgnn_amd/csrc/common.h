@@ -164,6 +164,9 @@ struct DeviceBatch {
     float* node_logits;       // [N][num_tasks] the per-node terms of the mean-pool + linear readout, r[v] . W[t] + b[t], in the caller's node
                               // order (flowgnn_set_node_logits; GIN, GIN-VN, GCN, GAT), or null: not asked for.  The same contract: a
                               // forward of these four models that finds it set must fill it, on every path
+    int attn_mask;            // GAT (flowgnn_set_attention): bit l selects layer l, 0: not asked for.  A GAT forward that finds it set must fill,
+    float* attn_edge;         // for the selected layers in ascending order, [n_sel][e_tot][4 heads] by the caller's edge index and
+    float* attn_self;         // [n_sel][n_tot][4 heads] (the implicit self edge) by the caller's node index, on every path
     int num_tasks;            // NUM_TASK of the readout (1 unless flowgnn_set_num_tasks said otherwise)
     int final_h;              // which h[] holds the last stage's output (set by forward)
     const float* tap;         // optional debug tap returned by flowgnn_get_h instead of h[final_h]

@@ -318,6 +318,30 @@ static int place_node_logits(flowgnn_engine* e) {
     return FLOWGNN_OK;
 }
 
+// ... and for the attention coefficients of the selected layers, [n_sel][E][4] and [n_sel][N][4]
+static int place_attention(flowgnn_engine* e) {
+    if (e->attn_mask && e->batch_ready) {
+        const size_t n_sel = (size_t)__builtin_popcount((unsigned)e->attn_mask);
+        const size_t need_e = sizeof(float) * n_sel * (size_t)e->E * 4, need_s = sizeof(float) * n_sel * (size_t)e->N * 4;
+        if ((!e->attn_e_user && !e->attn_e.holds(need_e)) || (!e->attn_s_user && !e->attn_s.holds(need_s))) {
+            if (e->stream) EHIP_TRY(e, hipStreamSynchronize(e->stream));
+            if (!e->attn_e_user && !e->attn_e.holds(need_e)) {
+                if (e->attn_e_last == e->attn_e.p) e->attn_e_last = nullptr;
+                EHIP_TRY(e, e->attn_e.reserve(need_e, false));
+            }
+            if (!e->attn_s_user && !e->attn_s.holds(need_s)) {
+                if (e->attn_s_last == e->attn_s.p) e->attn_s_last = nullptr;
+                EHIP_TRY(e, e->attn_s.reserve(need_s, false));
+            }
+        }
+    }
+    const bool on = e->batch_ready && e->attn_mask;
+    e->db.attn_mask = on ? e->attn_mask : 0;
+    e->db.attn_edge = on ? e->attn_e_target() : nullptr;
+    e->db.attn_self = on ? e->attn_s_target() : nullptr;
+    return FLOWGNN_OK;
+}
+
 extern "C" {
 
 int flowgnn_embedding_dim(int model) {
@@ -386,6 +410,8 @@ int flowgnn_destroy(flowgnn_engine* e) {
     e->emb.release();
     e->nemb.release();
     e->nlog.release();
+    e->attn_e.release();
+    e->attn_s.release();
     if (e->d_err) (void)hipFree(e->d_err);
     delete e->model;
     if (e->own_stream) (void)hipStreamDestroy(e->own_stream);
@@ -696,9 +722,13 @@ static int set_batch_state(flowgnn_engine* e, int num_graphs, const int* nums_of
     e->nemb_last = nullptr;
     e->nlog_user = nullptr;
     e->nlog_last = nullptr;
+    e->attn_e_user = e->attn_s_user = nullptr;
+    e->attn_e_last = e->attn_s_last = nullptr;
+    e->attn_mask_last = 0;
     if (int rc = place_embeddings(e)) return rc;
     if (int rc = place_node_embeddings(e)) return rc;
-    return place_node_logits(e);
+    if (int rc = place_node_logits(e)) return rc;
+    return place_attention(e);
 }
 
 }  // extern "C"
@@ -829,6 +859,9 @@ int flowgnn_run(flowgnn_engine* e) {
     e->emb_last = e->db.emb;
     e->nemb_last = e->db.node_emb;
     e->nlog_last = e->db.node_logits;
+    e->attn_mask_last = e->db.attn_mask;
+    e->attn_e_last = e->db.attn_edge;
+    e->attn_s_last = e->db.attn_self;
     if (e->G == 0) { e->ran = true; return FLOWGNN_OK; }
     const bool want_graph = e->graph_mode != 0 && !e->prof.enabled && (e->graph_mode > 1 || e->N <= (1ll << 20));
     if (want_graph && e->graph_ok) {
@@ -912,10 +945,19 @@ int flowgnn_sync(flowgnn_engine* e) {
             e->db.emb = e->emb_last;
             e->db.node_emb = e->nemb_last;
             e->db.node_logits = e->nlog_last;
+            const int anow = e->db.attn_mask;  // ... and the attention coefficients
+            float* const aenow = e->db.attn_edge;
+            float* const asnow = e->db.attn_self;
+            e->db.attn_mask = e->attn_mask_last;
+            e->db.attn_edge = e->attn_e_last;
+            e->db.attn_self = e->attn_s_last;
             const int frc = engine_forward(e);
             e->db.emb = now;
             e->db.node_emb = nnow;
             e->db.node_logits = lnow;
+            e->db.attn_mask = anow;
+            e->db.attn_edge = aenow;
+            e->db.attn_self = asnow;
             ENGINE_TRY(e, frc);
         }
         he = hipStreamSynchronize(e->stream);
@@ -1096,6 +1138,84 @@ int flowgnn_set_node_logits_buffer(flowgnn_engine* e, void* device_ptr) {
     return place_node_logits(e);
 }
 
+int flowgnn_attention_shape(int model, int* layers, int* heads) {
+    if (model != FLOWGNN_MODEL_GAT) {
+        fg::set_last_error("flowgnn_attention_shape: only GAT has attention coefficients");
+        return FLOWGNN_ERR_UNSUPPORTED;
+    }
+    if (layers) *layers = 5;
+    if (heads) *heads = 4;
+    return FLOWGNN_OK;
+}
+
+int flowgnn_set_attention(flowgnn_engine* e, int layer_mask) {
+    if (!e) return FLOWGNN_ERR_ARG;
+    if (layer_mask != 0 && e->model_id != FLOWGNN_MODEL_GAT) {
+        e->err = "flowgnn_set_attention: only GAT has attention coefficients (the other models aggregate with fixed or degree-derived weights)";
+        return FLOWGNN_ERR_UNSUPPORTED;
+    }
+    if (layer_mask < 0 || layer_mask > 31) {
+        e->err = "flowgnn_set_attention: the layer mask has bits 0..4 (GAT's five layers), 0 = off";
+        return FLOWGNN_ERR_ARG;
+    }
+    if (layer_mask && e->numeric_mode == FLOWGNN_NUMERIC_Q6_10) {
+        e->err = "flowgnn_set_attention: there are no fixed-point attention coefficients (FLOWGNN_NUMERIC_Q6_10)";
+        return FLOWGNN_ERR_UNSUPPORTED;
+    }
+    ENGINE_TRY(e, use_device(e));
+    e->drop_graph();  // a recorded launch sequence is that of the other setting
+    e->attn_mask = layer_mask;
+    return place_attention(e);
+}
+}  // extern "C"
+
+int get_attention_strided(flowgnn_engine* e, float* edge_host, size_t edge_stride, float* self_host, size_t self_stride) {
+    if (!e) return FLOWGNN_ERR_ARG;
+    // (the shapes are those of the mask, so a mask changed since the run is "not the last run's" too: the caller sized its arrays by it)
+    if (!e->ran || !e->attn_mask || e->attn_mask_last != e->attn_mask || (e->G > 0 && (!e->attn_e_last || !e->attn_s_last))) {
+        e->err = "flowgnn_get_attention: the last flowgnn_run did not have attention on with this layer mask (flowgnn_set_attention)";
+        return FLOWGNN_ERR_STATE;
+    }
+    int rc = flowgnn_sync(e);
+    if (rc) return rc;
+    if (e->G == 0) return FLOWGNN_OK;
+    const size_t n_sel = (size_t)__builtin_popcount((unsigned)e->attn_mask_last);
+    const size_t le = (size_t)e->E * 4, ls = (size_t)e->N * 4;  // floats per layer
+    for (size_t k = 0; k < n_sel; k++) {
+        if (edge_host && le && (rc = d2h_sync(e, edge_host + k * edge_stride, e->attn_e_last + k * le, sizeof(float) * le, "copy attention (edges)"))) return rc;
+        if (self_host && ls && (rc = d2h_sync(e, self_host + k * self_stride, e->attn_s_last + k * ls, sizeof(float) * ls, "copy attention (self)"))) return rc;
+    }
+    return FLOWGNN_OK;
+}
+
+extern "C" {
+int flowgnn_get_attention(flowgnn_engine* e, float* edge_host, float* self_host) {
+    if (!e) return FLOWGNN_ERR_ARG;
+    return get_attention_strided(e, edge_host, (size_t)e->E * 4, self_host, (size_t)e->N * 4);
+}
+
+int flowgnn_attention_device(flowgnn_engine* e, void** d_edge, void** d_self) {
+    if (!e || (!d_edge && !d_self)) return FLOWGNN_ERR_ARG;
+    if (!e->ran || !e->attn_mask || e->attn_mask_last != e->attn_mask || !e->attn_e_last || !e->attn_s_last) {
+        e->err = "flowgnn_attention_device: the last flowgnn_run did not have attention on with this layer mask (flowgnn_set_attention)";
+        return FLOWGNN_ERR_STATE;
+    }
+    if (d_edge) *d_edge = e->attn_e_last;
+    if (d_self) *d_self = e->attn_s_last;
+    return FLOWGNN_OK;
+}
+
+int flowgnn_set_attention_buffers(flowgnn_engine* e, void* d_edge, void* d_self) {
+    if (!e) return FLOWGNN_ERR_ARG;
+    if (!e->batch_ready) return FLOWGNN_ERR_STATE;
+    // as flowgnn_set_embeddings_buffer: no device synchronisation, the pointers matter to the launches enqueued after this call
+    ENGINE_TRY(e, use_device(e));
+    if (e->gexec) e->drop_graph();
+    e->attn_e_user = (float*)d_edge;
+    e->attn_s_user = (float*)d_self;
+    return place_attention(e);
+}
+
 int flowgnn_stream(flowgnn_engine* e, void** stream) {
     if (!e || !stream) return FLOWGNN_ERR_ARG;
     *stream = (void*)e->stream;
@@ -1156,6 +1276,10 @@ int flowgnn_set_numeric_mode(flowgnn_engine* e, int mode) {
     }
     if (mode == FLOWGNN_NUMERIC_Q6_10 && e->nlog_on) {
         e->err = "flowgnn_set_numeric_mode: node logits are on, and there are no fixed-point node logits";
+        return FLOWGNN_ERR_UNSUPPORTED;
+    }
+    if (mode == FLOWGNN_NUMERIC_Q6_10 && e->attn_mask) {
+        e->err = "flowgnn_set_numeric_mode: attention is on, and there are no fixed-point attention coefficients";
         return FLOWGNN_ERR_UNSUPPORTED;
     }
     e->drop_graph();
@@ -1219,10 +1343,13 @@ static int ensure_rows(flowgnn_engine* e) {
     e->db.emb = nullptr;  // a tap's pass leaves the run's embeddings as they are
     e->db.node_emb = nullptr;
     e->db.node_logits = nullptr;
+    const int amask = e->db.attn_mask;
+    e->db.attn_mask = 0;  // (the models read the mask alone)
     rc = engine_forward(e);
     e->db.emb = emb;
     e->db.node_emb = nemb;
     e->db.node_logits = nlog;
+    e->db.attn_mask = amask;
     e->model->set_keep_h(false);
     if (rc) { e->err = fg::last_error_text(); return rc; }
     return flowgnn_sync(e);

@@ -92,6 +92,15 @@ struct flowgnn_engine {
     float* nlog_user = nullptr;
     float* nlog_last = nullptr;
     float* nlog_target() const { return nlog_on ? (nlog_user ? nlog_user : (float*)nlog.p) : nullptr; }
+    // attention coefficients (flowgnn_set_attention; GAT): the same rules for two buffers, [n_sel][E][4] and [n_sel][N][4], n_sel =
+    // popcount(attn_mask); the mask of the last run is kept beside where it put them (the shapes a get copies are that run's)
+    int attn_mask = 0;
+    fg::GrowBuf attn_e, attn_s;
+    float *attn_e_user = nullptr, *attn_s_user = nullptr;
+    float *attn_e_last = nullptr, *attn_s_last = nullptr;
+    int attn_mask_last = 0;
+    float* attn_e_target() const { return attn_mask ? (attn_e_user ? attn_e_user : (float*)attn_e.p) : nullptr; }
+    float* attn_s_target() const { return attn_mask ? (attn_s_user ? attn_s_user : (float*)attn_s.p) : nullptr; }
 
     // hipGraph replay of the launch sequence (index build + forward), opt-in (FLOWGNN_HIPGRAPH=1; 2 = batches of any size).
     // Measured on this runtime it does not pay: asynchronous launches already pipeline, and a replay of the dozen kernels
@@ -156,6 +165,10 @@ double graph_tile_fill(fg::Model* model, int num_graphs, const int* nums_of_node
 // a time, while another engine of the same device packs its next range on the host or plans its tiles
 int set_batch_impl(flowgnn_engine* e, int num_graphs, const int* nums_of_nodes, const int* nums_of_edges, const int* node_feature,
                    const int* edge_list, const int* edge_attr, const float* node_eigen, std::mutex* copy_mu);
+
+// flowgnn_get_attention with the distance, in floats, between two selected layers of each host array (the group's members write their
+// edge / node range of every layer into the job's arrays)
+int get_attention_strided(flowgnn_engine* e, float* edge_host, size_t edge_stride, float* self_host, size_t self_stride);
 
 class GroupWorkers;  // group.hip
 struct flowgnn_group {

@@ -27,6 +27,11 @@ namespace fg {
 // gat_resident_nlogit_kernel, the instance that also stores every node's term of the readout (flowgnn_set_node_logits).  As
 // gcn_rows.hip does it: the default kernel stays the code it was; in that translation unit the host side is left out and the other
 // kernels, with internal linkage and unused, are dropped.
+// gat_attn.hip does the same with FG_RESIDENT_ATTN_TU, for gat_resident_attn_kernel: the instance that also stores the attention
+// coefficients of the selected layers (flowgnn_set_attention), and the node logits too when those are on as well.
+#if defined(FG_RESIDENT_NLOGIT_TU) || defined(FG_RESIDENT_ATTN_TU)
+#define FG_RESIDENT_INSTANCE_TU 1
+#endif
 // the graph-resident kernel's weights (per layer in device memory, GatModel::d_res_: see GATR_LAYER_BYTES below)
 struct GatResidentDev {
     const uint8_t* layers;     // [5][GATR_LAYER_BYTES]
@@ -49,10 +54,19 @@ struct GatResidentLaunch {
     const int* tile_row; const int* tile_graph; const int* node_off;
     float* out; int n_tiles; GatResidentDev w; int ablate;
     float* node_logits;  // [N], caller order (GAT's tiles are ranges of the batch's rows: row r of a tile is node t0 + r)
+    // gat_attn.hip only: bit l of the mask selects layer l; [n_sel][e_tot][4] by the caller's edge index (csr.eid), [n_sel][n_tot][4]
+    int attn_mask = 0; float* attn_edge = nullptr; float* attn_self = nullptr; const int* eid = nullptr; int e_tot = 0, n_tot = 0;
 };
 void launch_gat_resident_nlogit(const GatResidentLaunch& a, hipStream_t s);  // gat_nlogit.hip
-#ifdef FG_RESIDENT_NLOGIT_TU
+void launch_gat_resident_attn(const GatResidentLaunch& a, hipStream_t s);    // gat_attn.hip (node_logits may be null there)
+#ifdef FG_RESIDENT_INSTANCE_TU
 namespace {
+#endif
+#if defined(FG_RESIDENT_ATTN_TU)
+constexpr bool RESIDENT_NLOGIT = false;
+#define GAT_NLOGIT_PARAM , float* __restrict__ node_logits, int attn_mask, float* __restrict__ attn_edge, float* __restrict__ attn_self, \
+                         const int* __restrict__ eid, int e_tot, int n_tot
+#elif defined(FG_RESIDENT_NLOGIT_TU)
 constexpr bool RESIDENT_NLOGIT = true;
 #define GAT_NLOGIT_PARAM , float* __restrict__ node_logits
 #else
@@ -143,6 +157,38 @@ __global__ __launch_bounds__(256) void gat_local_rows_kernel(const int* __restri
     const int g = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (g >= num_graphs) return;
     for (int v = node_off[g] + lane; v < node_off[g + 1]; v += 64) feat_row[v] = v - node_off[g];
+}
+
+// Attention coefficients of ONE layer on every path but the graph-resident one (flowgnn_set_attention): launched beside that layer's
+// gat_layer_kernel, on the scores it reads.  A lane per destination row: e of the self edge, then of the CSR row in order -- the
+// expression and the summation order of the gather below -- gives den; the second walk stores e / den at the caller's edge index.
+__global__ __launch_bounds__(256) void gat_attention_kernel(const float* __restrict__ scores, const int* __restrict__ row_ptr,
+                                                             const int* __restrict__ src, const int* __restrict__ eid,
+                                                             float* __restrict__ attn_edge, float* __restrict__ attn_self, int n_tot) {
+    const long long v = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (v >= n_tot) return;
+    const float4* sc4 = reinterpret_cast<const float4*>(scores);
+    const float4 ssrc = sc4[v * 2 + 0];
+    auto e_of = [&](long long u) {
+        const float4 st = sc4[u * 2 + 1];
+        float4 s = make_float4(ssrc.x + st.x, ssrc.y + st.y, ssrc.z + st.z, ssrc.w + st.w);
+        s.x = __expf(s.x < 0.f ? s.x * 0.2f : s.x); s.y = __expf(s.y < 0.f ? s.y * 0.2f : s.y);
+        s.z = __expf(s.z < 0.f ? s.z * 0.2f : s.z); s.w = __expf(s.w < 0.f ? s.w * 0.2f : s.w);
+        return s;
+    };
+    const int e_begin = row_ptr[v], e_end = row_ptr[v + 1];
+    const float4 es = e_of(v);
+    float4 den = make_float4(0.f, 0.f, 0.f, 0.f);
+    den.x += es.x; den.y += es.y; den.z += es.z; den.w += es.w;
+    for (int e = e_begin; e < e_end; e++) {
+        const float4 s = e_of(src[e]);
+        den.x += s.x; den.y += s.y; den.z += s.z; den.w += s.w;
+    }
+    reinterpret_cast<float4*>(attn_self)[v] = make_float4(es.x / den.x, es.y / den.y, es.z / den.z, es.w / den.w);
+    for (int e = e_begin; e < e_end; e++) {
+        const float4 s = e_of(src[e]);
+        reinterpret_cast<float4*>(attn_edge)[eid[e]] = make_float4(s.x / den.x, s.y / den.y, s.z / den.z, s.w / den.w);
+    }
 }
 
 struct GatLayerDev {
@@ -531,8 +577,8 @@ __global__ __launch_bounds__(GATR_WAVES * 64, 4) void gat_resident_kernel(const 
                                                                          const int* __restrict__ tile_row, const int* __restrict__ tile_graph,
                                                                          const int* __restrict__ node_off, float* __restrict__ out, int n_tiles,
                                                                          GatResidentDev w, int ablate_arg GAT_NLOGIT_PARAM) {
-#ifndef FG_RESIDENT_NLOGIT_TU
-    constexpr float* node_logits = nullptr;  // (the storing instance has it as its last argument)
+#ifndef FG_RESIDENT_INSTANCE_TU
+    constexpr float* node_logits = nullptr;  // (the storing instances have it as an argument)
 #endif
     const int ablate = FG_ABLATE(ablate_arg);  // 0 in the shipped build: the branches below fold away (common.h)
     (void)ablate_arg;
@@ -570,6 +616,13 @@ __global__ __launch_bounds__(GATR_WAVES * 64, 4) void gat_resident_kernel(const 
     // the layers' three dequantisation scales, staged once: read from global memory where they are used, each cost its wave an
     // exposed L2 round trip (the load sits directly in front of its first use), two per layer and tile
     __shared__ float s_scales[3 * GAT_L + 1];
+#ifdef FG_RESIDENT_ATTN_TU
+    // Attention (selected layers only): the raw e = exp2(..) of every in-edge of the tile at its CSR position, of every row's self edge
+    // behind them, and one slot that takes the trips that are nobody's edge (the no-edge row, rows past the tile's end).  den is known
+    // only after the walk; the lanes that wrote a row's slots read them back then, so no barrier is involved.  24.6 KB.
+    constexpr int ATT_SELF = GATR_EDGES, ATT_DUMP = GATR_EDGES + GATR_ROWS;
+    __shared__ __attribute__((aligned(16))) float4_t s_ae[GATR_EDGES + GATR_ROWS + 1];
+#endif
     if (threadIdx.x < 3 * GAT_L) s_scales[threadIdx.x] = w.scales[threadIdx.x];
     const float pool_bias = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, w.pool_b[0])));  // (an SGPR)
     float vmax = 0.0f;
@@ -741,6 +794,9 @@ __global__ __launch_bounds__(GATR_WAVES * 64, 4) void gat_resident_kernel(const 
             float4 num[4];
 #pragma unroll
             for (int t = 0; t < 4; t++) num[t] = make_float4(0.f, 0.f, 0.f, 0.f);
+#ifdef FG_RESIDENT_ATTN_TU
+            const bool attn_sel = (attn_mask >> l) & 1;  // wave-uniform (an SGPR argument and the layer counter)
+#endif
             {
                 // Branch-free trips over a wave-uniform count (as gcn_resident_kernel's and gin_resident_kernel's walks).  The former
                 // `while (any lane has an edge) if (this lane has one) ...` cost, per trip, ten 64-bit moves of the accumulators (hipcc
@@ -775,6 +831,16 @@ __global__ __launch_bounds__(GATR_WAVES * 64, 4) void gat_resident_kernel(const 
                         nm[q][0] = __builtin_elementwise_fma(sv.lo, p[q].lo, nm[q][0]);
                         nm[q][1] = __builtin_elementwise_fma(sv.hi, p[q].hi, nm[q][1]);
                     }
+#ifdef FG_RESIDENT_ATTN_TU
+                    if (attn_sel) {
+                        // this trip's edge is CSR position e - 2 of the tile (trip 0: the self edge); nothing is carried across trips for it.
+                        // The node's four g lanes hold the same sv and write it to the same address.
+                        const int ce = e - 2;
+                        int slot = ce < e_end ? ce : ATT_DUMP;
+                        if (t == 0) slot = valid ? ATT_SELF + r : ATT_DUMP;
+                        s_ae[slot] = sv;
+                    }
+#endif
                 }
                 den = make_float4(dn[0].x, dn[0].y, dn[1].x, dn[1].y);
 #pragma unroll
@@ -785,6 +851,23 @@ __global__ __launch_bounds__(GATR_WAVES * 64, 4) void gat_resident_kernel(const 
                 const float4 rd = make_float4(__builtin_amdgcn_rcpf(den.x), __builtin_amdgcn_rcpf(den.y), __builtin_amdgcn_rcpf(den.z), __builtin_amdgcn_rcpf(den.w));
 #pragma unroll
                 for (int t = 0; t < 4; t++) acc[t] = (float4_t){num[t].x * rd.x, num[t].y * rd.y, num[t].z * rd.z, num[t].w * rd.w};
+#ifdef FG_RESIDENT_ATTN_TU
+                if (attn_sel && valid) {
+                    // alpha = e * rcp(den): the factors the message above is formed with.  The row's slots are read back by the lanes
+                    // that wrote them (LDS operations of a wave complete in order); lane g takes every fourth in-edge.  Edge values go
+                    // to the caller's edge index (csr.eid), the self term to the caller's node index (row r of the tile is node t0 + r).
+                    // A coefficient is at most 1, and the self term of a row without in-edges IS 1 (den = e): v_rcp_f32 is a 1-ulp
+                    // reciprocal, so e * rcp(e) may miss 1 by an ulp either way -- the product is capped at 1, and such a row stores 1.
+                    const size_t k = (size_t)__builtin_popcount((unsigned)attn_mask & ((1u << l) - 1u));
+                    const float4_t rdv = {rd.x, rd.y, rd.z, rd.w}, one = {1.f, 1.f, 1.f, 1.f};
+                    if (g == 0) {
+                        const float4_t a = __builtin_elementwise_min(s_ae[ATT_SELF + r] * rdv, one);
+                        reinterpret_cast<float4_t*>(attn_self)[k * (size_t)n_tot + (size_t)(t0 + r)] = e_begin < e_end ? a : one;
+                    }
+                    float4_t* ae = reinterpret_cast<float4_t*>(attn_edge) + k * (size_t)e_tot;
+                    for (int ee = e_begin + g; ee < e_end; ee += 4) ae[eid[e0 + ee]] = __builtin_elementwise_min(s_ae[ee] * rdv, one);
+                }
+#endif
             }
             if (l == GAT_L - 1) {
                 // emb[v][d] = mean_h(msg + W_skip_4 o_3)[d][h]; the logit is mean_v(emb[v]) . w + b = mean_v(emb[v] . w) + b
@@ -874,6 +957,9 @@ __global__ __launch_bounds__(GATR_WAVES * 64, 4) void gat_resident_kernel(const 
             // tiles are ranges of the batch's rows, so the tile's row r is node t0 + r: one coalesced 4-byte store per node
             if ((int)threadIdx.x < rows) node_logits[(size_t)t0 + threadIdx.x] = s_dot[threadIdx.x] + pool_bias;
         }
+#ifdef FG_RESIDENT_ATTN_TU
+        if (node_logits != nullptr && (int)threadIdx.x < rows) node_logits[(size_t)t0 + threadIdx.x] = s_dot[threadIdx.x] + pool_bias;
+#endif
         if (g0 + (int)threadIdx.x < g1) out[g0 + threadIdx.x] = lds_sum_in_order(s_dot + (ro_n0 - t0), ro_n1 - ro_n0) / (float)(ro_n1 - ro_n0) + pool_bias;
         if (!has_next) break;
         tile = ntile; t0 = nt0; rows = nrows; g0 = ng0; g1 = ng1; e0 = ne0; ne = nne;
@@ -884,7 +970,7 @@ __global__ __launch_bounds__(GATR_WAVES * 64, 4) void gat_resident_kernel(const 
 }
 #undef GATR_ABSMAX
 
-#ifndef FG_RESIDENT_NLOGIT_TU  // (host side: the model's own translation unit only)
+#ifndef FG_RESIDENT_INSTANCE_TU  // (host side: the model's own translation unit only)
 class GatModel : public Model {
 public:
     ~GatModel() override { free_all(); }
@@ -1098,7 +1184,11 @@ public:
             rw.range_flag = db.range_flag;
             ProfScope p(prof, "gat_resident", s);
             const int grid = db.gtiles.n_tiles < 256 ? db.gtiles.n_tiles : 256;  // persistent: one 16-wave workgroup per CU (118 KB of LDS)
-            if (db.node_logits)  // the same kernel's instance that also stores the per-node readout terms (gat_nlogit.hip)
+            if (db.attn_mask)  // the instance that also stores the selected layers' attention coefficients, and the node logits if on (gat_attn.hip)
+                launch_gat_resident_attn(GatResidentLaunch{grid, db.b.node_feature, feat_row, db.csr.row_ptr, db.csr.src, db.gtiles.row_start,
+                                                           db.gtiles.graph_start, db.b.node_off, db.out, db.gtiles.n_tiles, rw, ablate_,
+                                                           db.node_logits, db.attn_mask, db.attn_edge, db.attn_self, db.csr.eid, db.b.e_tot, n}, s);
+            else if (db.node_logits)  // the same kernel's instance that also stores the per-node readout terms (gat_nlogit.hip)
                 launch_gat_resident_nlogit(GatResidentLaunch{grid, db.b.node_feature, feat_row, db.csr.row_ptr, db.csr.src, db.gtiles.row_start,
                                                              db.gtiles.graph_start, db.b.node_off, db.out, db.gtiles.n_tiles, rw, ablate_,
                                                              db.node_logits}, s);
@@ -1130,6 +1220,13 @@ public:
             w.wlin_scale = wlin_scale_[l];
             w.range_flag = db.range_flag;
             const bool sp = split_ && !exact_;
+            if ((db.attn_mask >> l) & 1) {  // this layer's attention coefficients, from the scores its launch below reads (scoreb[cur])
+                ProfScope p(prof, "gat_attention", s);
+                const size_t k = (size_t)__builtin_popcount((unsigned)db.attn_mask & ((1u << l) - 1u));
+                gat_attention_kernel<<<(n + 255) / 256, 256, 0, s>>>(scoreb[cur], db.csr.row_ptr, db.csr.src, db.csr.eid,
+                                                                     db.attn_edge + k * (size_t)db.b.e_tot * GAT_H,
+                                                                     db.attn_self + k * (size_t)n * GAT_H, n);
+            }
             ProfScope p(prof, "gat_layer", s);
             const int n_tiles = (n + GAT_TR - 1) / GAT_TR;
             const int layer_grid = n_tiles < 512 ? n_tiles : 512;  // persistent: two 8-wave workgroups per CU (68 KB of LDS each)
@@ -1206,10 +1303,19 @@ private:
 };
 
 Model* make_gat_model() { return new GatModel(); }
-#endif  // FG_RESIDENT_NLOGIT_TU
+#endif  // FG_RESIDENT_INSTANCE_TU
 
-#ifdef FG_RESIDENT_NLOGIT_TU
+#ifdef FG_RESIDENT_INSTANCE_TU
 }  // namespace
+#endif
+#ifdef FG_RESIDENT_ATTN_TU
+void launch_gat_resident_attn(const GatResidentLaunch& a, hipStream_t s) {
+    gat_resident_kernel<<<a.grid, GATR_WAVES * 64, 0, s>>>(a.node_feature, a.feat_row, a.row_ptr, a.src, a.tile_row, a.tile_graph, a.node_off, a.out,
+                                                           a.n_tiles, a.w, a.ablate, a.node_logits, a.attn_mask, a.attn_edge, a.attn_self, a.eid,
+                                                           a.e_tot, a.n_tot);
+}
+#endif
+#ifdef FG_RESIDENT_NLOGIT_TU
 void launch_gat_resident_nlogit(const GatResidentLaunch& a, hipStream_t s) {
     gat_resident_kernel<<<a.grid, GATR_WAVES * 64, 0, s>>>(a.node_feature, a.feat_row, a.row_ptr, a.src, a.tile_row, a.tile_graph, a.node_off, a.out,
                                                            a.n_tiles, a.w, a.ablate, a.node_logits);

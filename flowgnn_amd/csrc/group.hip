@@ -237,6 +237,8 @@ int flowgnn_group_set_embeddings(flowgnn_group* g, int on) { return group_all(g,
 int flowgnn_group_set_node_embeddings(flowgnn_group* g, int on) { return group_all(g, [&](flowgnn_engine* e) { return flowgnn_set_node_embeddings(e, on); }); }
 int flowgnn_group_set_node_logits(flowgnn_group* g, int on) { return group_all(g, [&](flowgnn_engine* e) { return flowgnn_set_node_logits(e, on); }); }
 
+int flowgnn_group_set_attention(flowgnn_group* g, int layer_mask) { return group_all(g, [&](flowgnn_engine* e) { return flowgnn_set_attention(e, layer_mask); }); }
+
 int flowgnn_group_set_batch(flowgnn_group* g, int num_graphs, const int* nums_of_nodes, const int* nums_of_edges,
                             const int* node_feature, const int* edge_list, const int* edge_attr, const float* node_eigen) {
     if (!g) return FLOWGNN_ERR_ARG;
@@ -349,6 +351,26 @@ int flowgnn_group_get_node_logits(flowgnn_group* g, float* out_host) {
         flowgnn_engine* e = g->eng[(size_t)i];
         if (e->G == 0) return e->nlog_on ? flowgnn_sync(e) : (int)FLOWGNN_ERR_STATE;
         return flowgnn_get_node_logits(e, out_host + first[(size_t)i] * (size_t)e->num_tasks);
+    });
+}
+
+// [n_sel][E_tot][4] and [n_sel][N_tot][4] in job order: per selected layer, member i's edges / nodes start where those of members
+// 0 .. i - 1 end (the shards are contiguous graph ranges; edge indices are the caller's, per graph range)
+int flowgnn_group_get_attention(flowgnn_group* g, float* edge_host, float* self_host) {
+    if (!g) return FLOWGNN_ERR_ARG;
+    g->err.clear();
+    if (!g->batch_valid) return group_fail(g, FLOWGNN_ERR_STATE, "flowgnn_group_get_attention: no batch set by flowgnn_group_set_batch (flowgnn_group_compute and the entry points leave none)");
+    if (int rc = group_shards_intact(g, "flowgnn_group_get_attention")) return rc;
+    std::vector<size_t> nfirst(g->eng.size() + 1, 0), efirst(g->eng.size() + 1, 0);
+    for (size_t i = 0; i < g->eng.size(); i++) {
+        nfirst[i + 1] = nfirst[i] + (size_t)g->eng[i]->N;
+        efirst[i + 1] = efirst[i] + (size_t)g->eng[i]->E;
+    }
+    return group_each(g, [&](int i) {
+        flowgnn_engine* e = g->eng[(size_t)i];
+        if (e->G == 0) return e->attn_mask ? flowgnn_sync(e) : (int)FLOWGNN_ERR_STATE;
+        return get_attention_strided(e, edge_host ? edge_host + efirst[(size_t)i] * 4 : nullptr, efirst.back() * 4,
+                                     self_host ? self_host + nfirst[(size_t)i] * 4 : nullptr, nfirst.back() * 4);
     });
 }
 

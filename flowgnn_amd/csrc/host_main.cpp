@@ -2,7 +2,7 @@
 // OpenCL host (GIN/src/host.cc): load the model's .bin weights, read a graph pack in the reference's on-disk
 // layout, run the whole dataset as ONE batched launch NUM_TRIALS times, write HLS_output.txt.
 //
-//   host <MODEL> [--graphs DIR] [--weights DIR] [--num-graphs N] [--trials T] [--out FILE] [--node-logits FILE] [--device D | --devices D0,D1,..] [--option key=value] [--numeric f32|q6.10|f16] [XCLBIN]
+//   host <MODEL> [--graphs DIR] [--weights DIR] [--num-graphs N] [--trials T] [--out FILE] [--node-logits FILE] [--attention FILE [--attention-layers MASK]] [--device D | --devices D0,D1,..] [--option key=value] [--numeric f32|q6.10|f16] [XCLBIN]
 //
 //   MODEL        GIN | GIN-VN | GCN | GAT | PNA | DGN
 //   --graphs     directory holding graph_info/ and graph_bin/      (default ../graphs, host.cc:14-15)
@@ -12,6 +12,8 @@
 //   --trials     launches to time                                   (default 25 = NUM_TRIALS, host.h:8)
 //   --out        result file                                        (default HLS_output.txt, host.cc:213)
 //   --node-logits one more run behind the timed ones, with flowgnn_set_node_logits on: one line per node, NUM_TASK values (GIN, GIN-VN, GCN, GAT)
+//   --attention  one more run behind the timed ones, with flowgnn_set_attention on (GAT): one line per selected layer and edge,
+//                `layer edge h0 h1 h2 h3`, edges in the pack's order; --attention-layers: the layer mask (default 16, the last layer)
 //   XCLBIN       accepted and ignored, so `./host <xclbin>`-style command lines keep working
 //
 // Only the C ABI of include/flowgnn.h is used; no HIP or torch types here.
@@ -77,14 +79,15 @@ static bool read_eig_txt(const std::string& path, std::vector<float>& eig, size_
 int main(int argc, char** argv) {
     if (argc < 2) {
         fprintf(stderr, "Usage: %s <GIN|GIN-VN|GCN|GAT|PNA|DGN> [--graphs DIR] [--weights DIR] [--num-graphs N] [--trials T] "
-                        "[--out FILE] [--embeddings FILE] [--node-embeddings FILE] [--node-logits FILE] [--device D | --devices D0,D1,..] [--option key=value] [--numeric f32|q6.10|f16] [--num-tasks T] [XCLBIN File]\n", argv[0]);
+                        "[--out FILE] [--embeddings FILE] [--node-embeddings FILE] [--node-logits FILE] [--attention FILE [--attention-layers MASK]] [--device D | --devices D0,D1,..] [--option key=value] [--numeric f32|q6.10|f16] [--num-tasks T] [XCLBIN File]\n", argv[0]);
         return EXIT_FAILURE;
     }
     const std::string model = argv[1];
     const int mid = model_id(model);
     if (mid < 0) { fprintf(stderr, "unknown model %s\n", model.c_str()); return EXIT_FAILURE; }
-    std::string graphs = "../graphs", wdir = ".", out_path = "HLS_output.txt", eig_dir = "eig", emb_path, nemb_path, nlog_path;
+    std::string graphs = "../graphs", wdir = ".", out_path = "HLS_output.txt", eig_dir = "eig", emb_path, nemb_path, nlog_path, attn_path;
     long num_graphs = -1;
+    int attn_mask = 16;
     int trials = 25, numeric = FLOWGNN_NUMERIC_F32, num_tasks = 1;
     std::vector<int> devices;
     std::vector<std::pair<std::string, double>> options;
@@ -101,6 +104,8 @@ int main(int argc, char** argv) {
         else if (a == "--trials") trials = atoi(next("--trials"));
         else if (a == "--out") out_path = next("--out");
         else if (a == "--node-logits") nlog_path = next("--node-logits");  // the per-node terms of the readout, one line of NUM_TASK values per node
+        else if (a == "--attention") attn_path = next("--attention");  // GAT's attention coefficients, one line per selected layer and edge
+        else if (a == "--attention-layers") attn_mask = (int)strtol(next("--attention-layers"), nullptr, 0);
         else if (a == "--node-embeddings") nemb_path = next("--node-embeddings");  // the rows that pool is taken over, one line of dim values per node
         else if (a == "--embeddings") emb_path = next("--embeddings");  // the per-graph pooled embeddings, one line of dim values per graph
         else if (a == "--device") { devices.clear(); devices.push_back(atoi(next("--device"))); }
@@ -267,6 +272,34 @@ int main(int argc, char** argv) {
         for (size_t v = 0; v < n_tot; v++)
             for (int t = 0; t < num_tasks; t++) fprintf(lf, t + 1 < num_tasks ? "%.8f " : "%.8f\n", terms[v * num_tasks + t]);
         fclose(lf);
+    }
+    if (!attn_path.empty()) {
+        // likewise one more run, with attention on (and everything else off again)
+        const size_t e_tot = E;
+        size_t n_sel = 0;
+        for (int l = 0; l < 5; l++) n_sel += (attn_mask >> l) & 1;
+        std::vector<float> attn(n_sel * e_tot * 4);
+        rc = flowgnn_group_set_embeddings(eng, 0);
+        if (!rc) rc = flowgnn_group_set_node_embeddings(eng, 0);
+        if (!rc && (mid == FLOWGNN_MODEL_GIN || mid == FLOWGNN_MODEL_GIN_VN || mid == FLOWGNN_MODEL_GCN || mid == FLOWGNN_MODEL_GAT))
+            rc = flowgnn_group_set_node_logits(eng, 0);
+        if (!rc) rc = flowgnn_group_set_attention(eng, attn_mask);
+        if (!rc && n_sel == 0) { fprintf(stderr, "--attention-layers 0 selects no layer\n"); return EXIT_FAILURE; }
+        if (!rc) rc = flowgnn_group_run(eng);
+        if (!rc) rc = flowgnn_group_get_attention(eng, attn.data(), nullptr);
+        if (rc) { fprintf(stderr, "--attention: %d %s\n", rc, flowgnn_group_last_error(eng)); return EXIT_FAILURE; }
+        FILE* af = fopen(attn_path.c_str(), "w");
+        if (!af) { fprintf(stderr, "cannot write %s\n", attn_path.c_str()); return EXIT_FAILURE; }
+        size_t k = 0;
+        for (int l = 0; l < 5; l++) {
+            if (!((attn_mask >> l) & 1)) continue;
+            for (size_t i = 0; i < e_tot; i++) {
+                const float* a = &attn[(k * e_tot + i) * 4];
+                fprintf(af, "%d %zu %.8f %.8f %.8f %.8f\n", l, i, a[0], a[1], a[2], a[3]);
+            }
+            k++;
+        }
+        fclose(af);
     }
     flowgnn_group_destroy(eng);
     return 0;

@@ -56,6 +56,38 @@ def embedding_dim(model: str) -> int:
     return int(_lib.load().flowgnn_embedding_dim(_lib.MODEL_IDS[model]))
 
 
+def attention_shape(model: str):
+    """(layers, heads) of a model's attention coefficients (flowgnn.h: flowgnn_attention_shape): (5, 4) for GAT, FlowGNNError with
+    code 8 for the models that have none; host code only, no GPU needed."""
+    model = model.upper()
+    if model not in _lib.MODEL_IDS:
+        raise ValueError(f"unknown model {model}")
+    a, b = C.c_int(0), C.c_int(0)
+    rc = int(_lib.load().flowgnn_attention_shape(_lib.MODEL_IDS[model], C.byref(a), C.byref(b)))
+    if rc:
+        raise FlowGNNError(rc, "flowgnn_attention_shape", f"{model} has no attention coefficients")
+    return int(a.value), int(b.value)
+
+
+def attention_mask(model: str, layers) -> int:
+    """The layer mask of flowgnn_set_attention from an iterable of layer indices, "all", "last", or None / False (0: off)."""
+    if layers is None or layers is False:
+        return 0
+    n_layers = 5  # (GAT; a model without attention is refused by the library with its own text)
+    if isinstance(layers, str):
+        if layers not in ("all", "last"):
+            raise ValueError(f"attention layers: {layers!r} (an iterable of layer indices, 'all', 'last' or None)")
+        return (1 << n_layers) - 1 if layers == "all" else 1 << (n_layers - 1)
+    if layers is True:
+        return 1 << (n_layers - 1)
+    mask = 0
+    for l in layers:
+        if int(l) != l or not 0 <= int(l) < n_layers:
+            raise ValueError(f"attention layer {l!r}: layers are 0..{n_layers - 1}")
+        mask |= 1 << int(l)
+    return mask
+
+
 class Engine:
     """One engine = one GPU, one stream, one model's weights, one resident batch.
     `options`: {key: value} passed to flowgnn_set_option right after creation (e.g. {"gin_resident": 0})."""
@@ -97,6 +129,7 @@ class Engine:
         self._embeddings_tensor = None
         self._node_embeddings_tensor = None
         self._node_logits_tensor = None
+        self._attention_tensors = None
 
     def __del__(self):
         try:
@@ -235,7 +268,7 @@ class Engine:
                 t.record_stream(cur)
 
     def forward_device(self, x, edge_index, edge_attr=None, node_eigen=None, *, ptr, nums_of_edges=None, return_embeddings=False,
-                       return_node_embeddings=False, return_node_logits=False):
+                       return_node_embeddings=False, return_node_logits=False, return_attention=None):
         """set_batch_device, then one forward into a new torch tensor on the device ([G], or [G][num_tasks]); torch's current stream
         waits for the engine's, the host does not.  Validation errors (and the range check that can repeat a pass on the exact
         kernels) are seen by sync(), which raises; without it the tensor of a refused batch holds whatever the kernels wrote.
@@ -245,7 +278,10 @@ class Engine:
         in a new device tensor, appended to the returned tuple; written by the kernels themselves
         (flowgnn_set_node_embeddings_buffer), and on for later runs until set_node_embeddings(False).
         return_node_logits: the per-node terms of the readout ([N], or [N][num_tasks], in the order of the rows of x) in a new device
-        tensor, appended last; written by the kernels themselves (flowgnn_set_node_logits_buffer), on until set_node_logits(False)."""
+        tensor, appended last; written by the kernels themselves (flowgnn_set_node_logits_buffer), on until set_node_logits(False).
+        return_attention (GAT): what set_attention takes ("last", "all", layer indices); the pair (edge [n_sel][E][4] in the order of
+        edge_index's columns, self [n_sel][N][4]) of new device tensors is appended after everything else; written by the kernels
+        themselves (flowgnn_set_attention_buffers), on until set_attention(None)."""
         import torch
         dev = torch.device("cuda", self.device)
         cur = torch.cuda.current_stream(dev)
@@ -264,6 +300,13 @@ class Engine:
             n_rows = int(x.shape[0])
             terms = torch.empty((n_rows, self.num_tasks) if self.num_tasks > 1 else (n_rows,), dtype=torch.float32, device=dev)
             self.set_node_logits(True)
+        attn = None
+        if return_attention is not None and return_attention is not False:
+            self.set_attention(return_attention)
+            n_sel = bin(self._attn_mask).count("1")
+            n_edges = int(edge_index.shape[1] if edge_index.dtype == torch.int64 else edge_index.shape[0])
+            attn = (torch.empty((n_sel, n_edges, 4), dtype=torch.float32, device=dev),
+                    torch.empty((n_sel, int(x.shape[0]), 4), dtype=torch.float32, device=dev))
         self.set_batch_device(x, edge_index, edge_attr, node_eigen, ptr=ptr, nums_of_edges=nums_of_edges)
         es = torch.cuda.ExternalStream(self.stream_handle(), device=dev)
         if G:
@@ -278,10 +321,14 @@ class Engine:
             if terms is not None:
                 self.set_node_logits_buffer(terms.data_ptr())
                 self._node_logits_tensor = terms
+            if attn is not None:
+                self.set_attention_buffers(attn[0].data_ptr(), attn[1].data_ptr())
+                self._attention_tensors = attn
         self.run()
         cur.wait_stream(es)
         logits = out.view(G, self.num_tasks) if self.num_tasks > 1 else out
         ret = (logits,) + ((emb,) if return_embeddings else ()) + ((rows,) if return_node_embeddings else ()) + ((terms,) if return_node_logits else ())
+        ret += (attn,) if attn is not None else ()
         return ret if len(ret) > 1 else logits
 
     def run(self):
@@ -309,10 +356,14 @@ class Engine:
         self._check(self.lib.flowgnn_set_results_buffer(self._h, C.c_void_p(device_ptr)), "flowgnn_set_results_buffer")
 
     def forward(self, batch: GraphBatch, return_embeddings: bool = False, return_node_embeddings: bool = False,
-                return_node_logits: bool = False):
+                return_node_logits: bool = False, return_attention=None):
         """set_batch + run + results; return_embeddings: (logits, embeddings) -- embeddings stay on for later runs;
         return_node_embeddings: the node embeddings [N][embedding_dim] appended to the tuple (they stay on likewise);
-        return_node_logits: the per-node readout terms [N] or [N][num_tasks] appended last (likewise)."""
+        return_node_logits: the per-node readout terms [N] or [N][num_tasks] appended last (likewise);
+        return_attention (GAT): what set_attention takes; the pair attention() returns is appended after everything else (likewise)."""
+        want_attn = return_attention is not None and return_attention is not False
+        if want_attn:
+            self.set_attention(return_attention)
         if return_embeddings:
             self.set_embeddings(True)
         if return_node_embeddings:
@@ -323,6 +374,7 @@ class Engine:
         self.run()
         ret = (self.results(),) + ((self.embeddings(),) if return_embeddings else ()) + ((self.node_embeddings(),) if return_node_embeddings else ())
         ret += (self.node_logits(),) if return_node_logits else ()
+        ret += (self.attention(),) if want_attn else ()
         return ret if len(ret) > 1 else ret[0]
 
     # ---- graph embeddings (flowgnn.h: flowgnn_set_embeddings)
@@ -388,6 +440,34 @@ class Engine:
         """Caller-owned device buffer of >= N * num_tasks floats for the node logits; None / 0 restores the engine's own."""
         self._check(self.lib.flowgnn_set_node_logits_buffer(self._h, C.c_void_p(device_ptr) if device_ptr else None),
                     "flowgnn_set_node_logits_buffer")
+
+    # ---- attention coefficients (flowgnn.h: flowgnn_set_attention; GAT)
+    def set_attention(self, layers="last"):
+        """Runs enqueued after this also store the attention coefficients of the selected layers: an iterable of layer indices,
+        "all", "last" (the fifth layer: what explanation and edge pruning use), or None / False for off."""
+        mask = attention_mask(self.model, layers)
+        self._check(self.lib.flowgnn_set_attention(self._h, mask), "flowgnn_set_attention")
+        self._attn_mask = mask
+
+    def attention(self):
+        """(edge [n_sel][E][4], self [n_sel][N][4]) of the last run (synchronises): per selected layer in ascending order, per edge
+        of the batch as it was passed / per node (the implicit self edge), per head.  FLOWGNN_ERR_STATE if that run had it off."""
+        n_sel = bin(getattr(self, "_attn_mask", 0)).count("1")
+        edge = np.empty((n_sel, self.total_edges, 4), dtype=np.float32)
+        own = np.empty((n_sel, self.total_nodes, 4), dtype=np.float32)
+        self._check(self.lib.flowgnn_get_attention(self._h, _pf(edge), _pf(own)), "flowgnn_get_attention")
+        return edge, own
+
+    def attention_device_ptrs(self):
+        """(edge, self) device addresses of the last run's attention coefficients (flowgnn.h: flowgnn_attention_device)."""
+        a, b = C.c_void_p(), C.c_void_p()
+        self._check(self.lib.flowgnn_attention_device(self._h, C.byref(a), C.byref(b)), "flowgnn_attention_device")
+        return int(a.value or 0), int(b.value or 0)
+
+    def set_attention_buffers(self, edge_ptr: Optional[int], self_ptr: Optional[int]):
+        """Caller-owned device buffers of >= n_sel * E * 4 and n_sel * N * 4 floats; None / 0 restores the engine's own (each)."""
+        self._check(self.lib.flowgnn_set_attention_buffers(self._h, C.c_void_p(edge_ptr) if edge_ptr else None,
+                                                           C.c_void_p(self_ptr) if self_ptr else None), "flowgnn_set_attention_buffers")
 
     # ---- taps
     def set_numeric_mode(self, mode: str = "f32"):
@@ -472,6 +552,7 @@ class EngineGroup:
         self.num_tasks = 1
         self.num_graphs = 0
         self.total_nodes = 0
+        self.total_edges = 0
         for k, v in (options or {}).items():
             self._check(self.lib.flowgnn_group_set_option(self._h, k.encode(), option_value(v)), f"flowgnn_group_set_option({k})")
 
@@ -513,6 +594,7 @@ class EngineGroup:
                     "flowgnn_group_set_batch")
         self.num_graphs = batch.num_graphs
         self.total_nodes = batch.total_nodes
+        self.total_edges = batch.total_edges
 
     def shards(self):
         cuts = np.zeros(len(self.devices) + 1, dtype=np.int32)
@@ -550,6 +632,19 @@ class EngineGroup:
 
     def set_node_logits(self, on: bool = True):
         self._check(self.lib.flowgnn_group_set_node_logits(self._h, 1 if on else 0), "flowgnn_group_set_node_logits")
+
+    def set_attention(self, layers="last"):
+        mask = attention_mask(self.model, layers)
+        self._check(self.lib.flowgnn_group_set_attention(self._h, mask), "flowgnn_group_set_attention")
+        self._attn_mask = mask
+
+    def attention(self):
+        """(edge [n_sel][E][4], self [n_sel][N][4]) of the last run, in job order (flowgnn.h: flowgnn_group_get_attention)."""
+        n_sel = bin(getattr(self, "_attn_mask", 0)).count("1")
+        edge = np.empty((n_sel, self.total_edges, 4), dtype=np.float32)
+        own = np.empty((n_sel, self.total_nodes, 4), dtype=np.float32)
+        self._check(self.lib.flowgnn_group_get_attention(self._h, _pf(edge), _pf(own)), "flowgnn_group_get_attention")
+        return edge, own
 
     def node_logits(self) -> np.ndarray:
         """[N], or [N][num_tasks], of the last run, in job order (flowgnn.h: flowgnn_group_get_node_logits)."""

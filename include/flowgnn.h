@@ -406,6 +406,46 @@ int flowgnn_get_node_logits(flowgnn_engine* e, float* out_host);
 int flowgnn_node_logits_device(flowgnn_engine* e, void** d_terms);
 int flowgnn_set_node_logits_buffer(flowgnn_engine* e, void* device_ptr);
 
+/*
+ * Attention coefficients (GAT): what PyG's GATConv(return_attention_weights=True) returns, for explanation and edge pruning.
+ * For layer l (0..4), head h (0..3) and destination v, with the reference's implicit self edge first:
+ *     e(u->v)[l][h]       = exp(leaky_0.2(ssrc_l[v][h] + stgt_l[u][h]))                  (no max subtraction, as the reference)
+ *     den[v][l][h]        = e(v->v) + sum over the in-edges (u->v) of e(u->v)
+ *     attn_edge[l][i][h]  = e(u_i->v_i) / den[v_i]     for edge i of the batch AS THE CALLER PASSED IT
+ *     attn_self[l][v][h]  = e(v->v) / den[v]           for node v in the caller's node order
+ * An explicit [v, v] entry of the edge list is an ordinary edge beside the self term; duplicate edges each get their own (equal)
+ * value.  fp32, and the very coefficients the kernel's message is formed with (the same e, the same 1 / den).  Outputs are
+ * layer-major over the SELECTED layers only, in ascending layer order: attn_edge [n_sel][E_tot][4], attn_self [n_sel][N_tot][4].
+ *  flowgnn_attention_shape: layers = 5, heads = 4 for GAT; FLOWGNN_ERR_UNSUPPORTED for every other model.  Needs no GPU.
+ *  flowgnn_set_attention(e, layer_mask): bit l selects layer l, n_sel = popcount(mask), 0 = off (the default); 16 is the last layer,
+ *     what the common uses want -- all five layers are 80 bytes per edge and node.  Off means off: the same kernels launch with
+ *     the same arguments.  On, alone, the batch stays on the kernels it runs on with it off and the graph logits keep their bits:
+ *     the graph-resident path launches gat_resident_attn_kernel (gat_attn.hip: the default kernel, which in the selected layers
+ *     parks every edge's e in LDS during its walk and stores e * rcp(den) when the walk has formed den -- by the lane that walked
+ *     the row, edge values through the index build's edge ids, no atomics; it stores the node logits as well when those are on).
+ *     Every other path (gat_resident 0, batches under the fill threshold, graphs beyond 256 rows / 1 280 in-edges, the exact-fp32
+ *     re-run, graph or node embeddings on) launches gat_attention_kernel beside each selected layer: a lane per destination, the
+ *     row's CSR order, e / den.  The two paths may differ by fp32 rounding (exp2 of pre-scaled scores and a reciprocal against
+ *     expf and a division), as their logits do; neither depends on tile placement or on the order of the caller's edge list.
+ *     FLOWGNN_ERR_UNSUPPORTED (flowgnn_last_error says why) for a non-zero mask on any other model, and in FLOWGNN_NUMERIC_Q6_10;
+ *     flowgnn_set_numeric_mode answers the same for that mode while attention is on.  FLOWGNN_ERR_ARG for a mask outside 0..31.
+ *     Drops a recorded launch sequence (option hipgraph).  Survives flowgnn_set_batch.  Works together with
+ *     flowgnn_set_embeddings, flowgnn_set_node_embeddings, flowgnn_set_node_logits, option hipgraph, gat_reference_quirk and
+ *     flowgnn_set_batch_device.  The <M>_compute_graphs entry points never produce them.
+ *  flowgnn_get_attention: copy to the host (either pointer may be NULL; synchronises first; an exact-fp32 re-run refills the values
+ *     with the logits).  FLOWGNN_ERR_STATE when the last run had attention off, or on with another mask than the current one.
+ *  flowgnn_attention_device: where the last run put them (same condition; either pointer may be NULL); valid until the next
+ *     flowgnn_set_batch.
+ *  flowgnn_set_attention_buffers: redirect them into caller-owned DEVICE buffers of at least n_sel * E_tot * 4 and n_sel * N_tot * 4
+ *     floats; NULL restores the engine's own buffer (each of the two on its own); reset by flowgnn_set_batch; drops a recorded
+ *     launch sequence; stream-ordered, no host synchronisation.
+ */
+int flowgnn_attention_shape(int model, int* layers, int* heads);
+int flowgnn_set_attention(flowgnn_engine* e, int layer_mask);
+int flowgnn_get_attention(flowgnn_engine* e, float* edge_host, float* self_host);
+int flowgnn_attention_device(flowgnn_engine* e, void** d_edge, void** d_self);
+int flowgnn_set_attention_buffers(flowgnn_engine* e, void* d_edge, void* d_self);
+
 /* The engine's hipStream_t as an opaque pointer (for event timing by a caller). */
 int flowgnn_stream(flowgnn_engine* e, void** stream);
 
@@ -564,6 +604,10 @@ int flowgnn_group_get_node_embeddings(flowgnn_group* g, float* out_host);
 /* flowgnn_set_node_logits on every member; flowgnn_group_get_node_logits writes [N_tot][NUM_TASK] in job order. */
 int flowgnn_group_set_node_logits(flowgnn_group* g, int on);
 int flowgnn_group_get_node_logits(flowgnn_group* g, float* out_host);
+/* flowgnn_set_attention on every member; flowgnn_group_get_attention writes [n_sel][E_tot][4] and [n_sel][N_tot][4] in job order
+ * (either pointer may be NULL). */
+int flowgnn_group_set_attention(flowgnn_group* g, int layer_mask);
+int flowgnn_group_get_attention(flowgnn_group* g, float* edge_host, float* self_host);
 /* set_batch + run + get_results for a batch in HOST memory, cut into size x chunks_per_engine ranges; engine i takes ranges
  * i, i + size, ... in turn, so that one engine's copies overlap the others' kernels.  out_host: [num_graphs][NUM_TASK]. */
 int flowgnn_group_compute(flowgnn_group* g, int num_graphs, const int* nums_of_nodes, const int* nums_of_edges,
