@@ -83,6 +83,7 @@ namespace fg {
 
 void set_hip_error(const char* what, hipError_t e, const char* file, int line);
 const char* last_error_text();
+void set_last_error(const char* what);  // (engine.hip) the text of a failure that is not a HIP call's
 
 // HIP-event profiler: brackets launches on the engine stream; read after a sync.
 class Profiler {
@@ -168,6 +169,8 @@ struct DeviceBatch {
     float* attn_edge;         // for the selected layers in ascending order, [n_sel][e_tot][4 heads] by the caller's edge index and
     float* attn_self;         // [n_sel][n_tot][4 heads] (the implicit self edge) by the caller's node index, on every path
     int num_tasks;            // NUM_TASK of the readout (1 unless flowgnn_set_num_tasks said otherwise)
+    int pooling;              // FLOWGNN_POOL_* (flowgnn_set_pooling; GIN, GIN-VN, GCN, GAT): 0 = mean, every launch is the one it always was; 1 = sum,
+                              // 2 = max.  Decides what out and emb hold; node_emb and the attention buffers do not depend on it
     int final_h;              // which h[] holds the last stage's output (set by forward)
     const float* tap;         // optional debug tap returned by flowgnn_get_h instead of h[final_h]
     int tap_dim;

@@ -162,10 +162,37 @@ inline int atom_encoder_grid(long long n_tot, int C) {
     return (int)(blocks < 512 ? (blocks > 0 ? blocks : 1) : 512);
 }
 
+// ---------------------------------------------------------------- the readout's pooling operation (flowgnn_set_pooling)
+// The readout kernels below take it as a template parameter; POOL_OP_MEAN is the default argument, so `kernel<D>` names the instance
+// it always named, with the arithmetic it always had.  Sum: the same chains of adds without the division.  Max: every chain takes the
+// larger value instead, starting from -inf (a graph has at least one node, so no -inf survives; these kernels read rows of device
+// memory, where there is neither a padding row nor a no-edge row to see).
+constexpr int POOL_OP_MEAN = 0, POOL_OP_SUM = 1, POOL_OP_MAX = 2;  // = FLOWGNN_POOL_*
+template <int OP>
+__device__ __forceinline__ float pool_init() {
+    if constexpr (OP == POOL_OP_MAX) return -__builtin_inff();
+    else return 0.0f;
+}
+template <int OP>
+__device__ __forceinline__ void pool_fold(float& acc, float x) {
+    if constexpr (OP == POOL_OP_MAX) acc = __builtin_fmaxf(acc, x);
+    else acc += x;
+}
+template <int OP>
+__device__ __forceinline__ void pool_fold4(float4& acc, const float4& x) {
+    pool_fold<OP>(acc.x, x.x); pool_fold<OP>(acc.y, x.y); pool_fold<OP>(acc.z, x.z); pool_fold<OP>(acc.w, x.w);
+}
+template <int OP>
+__device__ __forceinline__ float pool_finish(float acc, float n) {
+    if constexpr (OP == POOL_OP_MEAN) return acc / n;
+    else return acc;
+}
+
 // ---------------------------------------------------------------- readout with the linear head already applied per node
 // out[g] = (sum of score[v] over the nodes of graph g, in node order) / n_g + bias: the second half of a mean-pool +
 // linear readout whose per-node dot products were computed in the last layer's epilogue (gin_split.hip).
-template <int UNUSED = 0>  // a template only for its linkage (the header is included by several translation units)
+// OP (sum only besides the mean: a maximum of per-node scores is not the head applied to a maximum) leaves the division out.
+template <int UNUSED = 0, int OP = POOL_OP_MEAN>  // (UNUSED: a template only for its linkage -- the header is included by several translation units)
 __global__ __launch_bounds__(256) void segment_mean_bias_kernel(const float* __restrict__ score, const int* __restrict__ node_off,
                                                                          const float* __restrict__ pb, float* __restrict__ out,
                                                                          int num_graphs) {
@@ -174,13 +201,14 @@ __global__ __launch_bounds__(256) void segment_mean_bias_kernel(const float* __r
     const int n0 = node_off[gidx], n1 = node_off[gidx + 1];
     float s = 0.0f;
     for (int v = n0; v < n1; v++) s += score[v];
-    out[gidx] = s / (float)(n1 - n0) + pb[0];
+    static_assert(OP != POOL_OP_MAX, "per-node scores have no maximum to pool");
+    out[gidx] = pool_finish<OP>(s, (float)(n1 - n0)) + pb[0];
 }
 
 
 // Sum of the rows v0, v0 + 2, ... < n1 of a graph (one float4 chunk c of each), in that order: four rows are requested before the first
 // is added.  One at a time, every row was its own global round trip on the graph's wavefront (the readout kernels below).
-template <int C>
+template <int C, int OP = POOL_OP_MEAN>
 __device__ __forceinline__ void pool_rows_in_order(float4& acc, const float* __restrict__ h, int v0, int n1, int c) {
     int v = v0;
     for (; v + 6 < n1; v += 8) {
@@ -188,17 +216,23 @@ __device__ __forceinline__ void pool_rows_in_order(float4& acc, const float* __r
 #pragma unroll
         for (int i = 0; i < 4; i++) x[i] = reinterpret_cast<const float4*>(h)[(size_t)(v + 2 * i) * C + c];
 #pragma unroll
-        for (int i = 0; i < 4; i++) { acc.x += x[i].x; acc.y += x[i].y; acc.z += x[i].z; acc.w += x[i].w; }
+        for (int i = 0; i < 4; i++) pool_fold4<OP>(acc, x[i]);
     }
     for (; v < n1; v += 2) {
         const float4 x = reinterpret_cast<const float4*>(h)[(size_t)v * C + c];
-        acc.x += x.x; acc.y += x.y; acc.z += x.z; acc.w += x.w;
+        pool_fold4<OP>(acc, x);
     }
+}
+// ... and the two half-waves' partial results (lanes c and c + 32) folded into the lower half
+template <int OP>
+__device__ __forceinline__ void pool_join_halves(float4& acc) {
+    pool_fold<OP>(acc.x, __shfl_down(acc.x, 32, 64)); pool_fold<OP>(acc.y, __shfl_down(acc.y, 32, 64));
+    pool_fold<OP>(acc.z, __shfl_down(acc.z, 32, 64)); pool_fold<OP>(acc.w, __shfl_down(acc.w, 32, 64));
 }
 
 // ---------------------------------------------------------------- readout: mean pool + linear head
 // One wavefront per graph; lanes 0..24 take even rows, lanes 32..56 odd rows (float4 chunks).
-template <int D>
+template <int D, int OP = POOL_OP_MEAN>
 __global__ __launch_bounds__(256) void mean_pool_linear_kernel(const float* __restrict__ h,
                                                                 const int* __restrict__ node_off,
                                                                 const float* __restrict__ pw,
@@ -211,15 +245,14 @@ __global__ __launch_bounds__(256) void mean_pool_linear_kernel(const float* __re
     if (g >= num_graphs) return;
     const int n0 = node_off[g], n1 = node_off[g + 1];
     const int half = lane >> 5, c = lane & 31;
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (c < C) pool_rows_in_order<C>(acc, h, n0 + half, n1, c);
-    acc.x += __shfl_down(acc.x, 32, 64); acc.y += __shfl_down(acc.y, 32, 64);
-    acc.z += __shfl_down(acc.z, 32, 64); acc.w += __shfl_down(acc.w, 32, 64);
+    float4 acc = make_float4(pool_init<OP>(), pool_init<OP>(), pool_init<OP>(), pool_init<OP>());
+    if (c < C) pool_rows_in_order<C, OP>(acc, h, n0 + half, n1, c);
+    pool_join_halves<OP>(acc);
     float part = 0.f;
     if (half == 0 && c < C) {
         const float n = (float)(n1 - n0);
         const float4 w = reinterpret_cast<const float4*>(pw)[c];
-        part = (acc.x / n) * w.x + (acc.y / n) * w.y + (acc.z / n) * w.z + (acc.w / n) * w.w;
+        part = pool_finish<OP>(acc.x, n) * w.x + pool_finish<OP>(acc.y, n) * w.y + pool_finish<OP>(acc.z, n) * w.z + pool_finish<OP>(acc.w, n) * w.w;
     }
 #pragma unroll
     for (int d = 16; d >= 1; d >>= 1) part += __shfl_down(part, d, 64);
@@ -232,7 +265,7 @@ __global__ __launch_bounds__(256) void mean_pool_linear_kernel(const float* __re
 // Persistent workgroups; the head is kept in LDS transposed ([d][t], so the lanes of a wave read consecutive words), TCH tasks
 // at a time; one wavefront per graph pools its rows (two half-waves over alternate rows, float4 chunks) and then takes the
 // tasks t = lane, lane + 64, ...  Summation order per output: d = 0..D-1.
-template <int D>
+template <int D, int OP = POOL_OP_MEAN>
 __global__ __launch_bounds__(256) void mean_pool_linear_mt_kernel(const float* __restrict__ h, const int* __restrict__ node_off,
                                                                    const float* __restrict__ pw, const float* __restrict__ pb,
                                                                    float* __restrict__ out, int num_graphs, int num_tasks) {
@@ -253,14 +286,13 @@ __global__ __launch_bounds__(256) void mean_pool_linear_mt_kernel(const float* _
         for (int g = blockIdx.x * 4 + wv; g < num_graphs; g += gridDim.x * 4) {
             const int n0 = node_off[g], n1 = node_off[g + 1];
             const int half = lane >> 5, c = lane & 31;
-            float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (c < C) pool_rows_in_order<C>(acc, h, n0 + half, n1, c);
-            acc.x += __shfl_down(acc.x, 32, 64); acc.y += __shfl_down(acc.y, 32, 64);
-            acc.z += __shfl_down(acc.z, 32, 64); acc.w += __shfl_down(acc.w, 32, 64);
+            float4 acc = make_float4(pool_init<OP>(), pool_init<OP>(), pool_init<OP>(), pool_init<OP>());
+            if (c < C) pool_rows_in_order<C, OP>(acc, h, n0 + half, n1, c);
+            pool_join_halves<OP>(acc);
             if (half == 0 && c < C) {
                 const float n = (float)(n1 - n0);
-                s_hg[wv][4 * c + 0] = acc.x / n; s_hg[wv][4 * c + 1] = acc.y / n;
-                s_hg[wv][4 * c + 2] = acc.z / n; s_hg[wv][4 * c + 3] = acc.w / n;
+                s_hg[wv][4 * c + 0] = pool_finish<OP>(acc.x, n); s_hg[wv][4 * c + 1] = pool_finish<OP>(acc.y, n);
+                s_hg[wv][4 * c + 2] = pool_finish<OP>(acc.z, n); s_hg[wv][4 * c + 3] = pool_finish<OP>(acc.w, n);
             }
             __builtin_amdgcn_wave_barrier();
             for (int t = lane; t < nt; t += 64) {
@@ -277,7 +309,7 @@ __global__ __launch_bounds__(256) void mean_pool_linear_mt_kernel(const float* _
 // emb[g][:] = (sum of rows[v][:] over the nodes of graph g, in node order) / n_g  (flowgnn_set_embeddings).  One wavefront per
 // graph; lane c < D / 4 owns the float4 chunk c of the row, so a row is one coalesced request and every column is a single chain of
 // adds in node order: the sum depends on the graph alone.  Four rows are in flight before the first is added.
-template <int D>
+template <int D, int OP = POOL_OP_MEAN>
 __global__ __launch_bounds__(256) void mean_pool_rows_kernel(const float* __restrict__ rows, const int* __restrict__ node_off,
                                                              float* __restrict__ emb, int num_graphs) {
     constexpr int C = D / 4;
@@ -287,21 +319,100 @@ __global__ __launch_bounds__(256) void mean_pool_rows_kernel(const float* __rest
     if (g >= num_graphs || lane >= C) return;
     const int n0 = node_off[g], n1 = node_off[g + 1];
     const float4* r = reinterpret_cast<const float4*>(rows);
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 acc = make_float4(pool_init<OP>(), pool_init<OP>(), pool_init<OP>(), pool_init<OP>());
     int v = n0;
     for (; v + 3 < n1; v += 4) {
         float4 x[4];
 #pragma unroll
         for (int i = 0; i < 4; i++) x[i] = r[(size_t)(v + i) * C + lane];
 #pragma unroll
-        for (int i = 0; i < 4; i++) { acc.x += x[i].x; acc.y += x[i].y; acc.z += x[i].z; acc.w += x[i].w; }
+        for (int i = 0; i < 4; i++) pool_fold4<OP>(acc, x[i]);
     }
     for (; v < n1; v++) {
         const float4 x = r[(size_t)v * C + lane];
-        acc.x += x.x; acc.y += x.y; acc.z += x.z; acc.w += x.w;
+        pool_fold4<OP>(acc, x);
     }
     const float n = (float)(n1 - n0);
-    reinterpret_cast<float4*>(emb + (size_t)g * D)[lane] = make_float4(acc.x / n, acc.y / n, acc.z / n, acc.w / n);
+    reinterpret_cast<float4*>(emb + (size_t)g * D)[lane] = make_float4(pool_finish<OP>(acc.x, n), pool_finish<OP>(acc.y, n), pool_finish<OP>(acc.z, n), pool_finish<OP>(acc.w, n));
+}
+
+// ---------------------------------------------------------------- the linear head on pooled rows: [G][D] x [T][D] -> [G][T]
+// out[g][t] = pb[t] + emb[g] . pw[t], for the paths that pool on chip and leave only the pooled row (GIN's maximum).  One 16-lane
+// group per graph, as node_logits_rows_kernel has it per node: lane j takes the float4 chunks j, j + 16, ... in that order, the
+// sixteen partial sums are folded by a fixed xor tree -- the order of a value's additions depends on D alone.
+template <int D>
+__global__ __launch_bounds__(256) void pooled_head_kernel(const float* __restrict__ emb, const float* __restrict__ pw, const float* __restrict__ pb,
+                                                          float* __restrict__ out, int num_graphs, int num_tasks) {
+    constexpr int C = D / 4, K = (C + 15) / 16;
+    static_assert(D % 4 == 0, "rows are read as float4 chunks");
+    const int j = threadIdx.x & 15;
+    const long long g = (long long)blockIdx.x * 16 + (threadIdx.x >> 4);
+    const bool live = g < num_graphs;  // (no early return: the shuffles below are wave-wide)
+    float4 x[K];
+#pragma unroll
+    for (int k = 0; k < K; k++) {
+        const int c = j + 16 * k;
+        x[k] = (live && c < C) ? reinterpret_cast<const float4*>(emb)[(size_t)g * C + c] : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    for (int t = 0; t < num_tasks; t++) {
+        float part = 0.0f;
+#pragma unroll
+        for (int k = 0; k < K; k++) {
+            const int c = j + 16 * k;
+            if (c < C) {
+                const float4 w = reinterpret_cast<const float4*>(pw + (size_t)t * D)[c];
+                part += x[k].x * w.x; part += x[k].y * w.y; part += x[k].z * w.z; part += x[k].w * w.w;
+            }
+        }
+#pragma unroll
+        for (int d = 8; d >= 1; d >>= 1) part += __shfl_xor(part, d, 64);
+        if (live && j == 0) out[(size_t)g * num_tasks + t] = part + pb[t];
+    }
+}
+
+// ---------------------------------------------------------------- launchers that pick the instance by the engine's pooling mode
+// (op = DeviceBatch::pooling; POOL_OP_MEAN launches what the call sites always launched, with the same arguments)
+template <int D>
+inline void launch_pool_linear(int op, const float* rows, const int* node_off, const float* pw, const float* pb, float* out, int num_graphs,
+                               hipStream_t s) {
+    const int grid = (num_graphs + 3) / 4;
+    if (op == POOL_OP_SUM) mean_pool_linear_kernel<D, POOL_OP_SUM><<<grid, 256, 0, s>>>(rows, node_off, pw, pb, out, num_graphs);
+    else if (op == POOL_OP_MAX) mean_pool_linear_kernel<D, POOL_OP_MAX><<<grid, 256, 0, s>>>(rows, node_off, pw, pb, out, num_graphs);
+    else mean_pool_linear_kernel<D><<<grid, 256, 0, s>>>(rows, node_off, pw, pb, out, num_graphs);
+}
+template <int D>
+inline void launch_pool_linear_mt(int op, const float* rows, const int* node_off, const float* pw, const float* pb, float* out, int num_graphs,
+                                  int num_tasks, hipStream_t s) {
+    const int blocks = (num_graphs + 3) / 4;
+    const int grid = blocks < 512 ? blocks : 512;
+    if (op == POOL_OP_SUM) mean_pool_linear_mt_kernel<D, POOL_OP_SUM><<<grid, 256, 0, s>>>(rows, node_off, pw, pb, out, num_graphs, num_tasks);
+    else if (op == POOL_OP_MAX) mean_pool_linear_mt_kernel<D, POOL_OP_MAX><<<grid, 256, 0, s>>>(rows, node_off, pw, pb, out, num_graphs, num_tasks);
+    else mean_pool_linear_mt_kernel<D><<<grid, 256, 0, s>>>(rows, node_off, pw, pb, out, num_graphs, num_tasks);
+}
+template <int D>
+inline void launch_pool_rows(int op, const float* rows, const int* node_off, float* emb, int num_graphs, hipStream_t s) {
+    const int grid = (num_graphs + 3) / 4;
+    if (op == POOL_OP_SUM) mean_pool_rows_kernel<D, POOL_OP_SUM><<<grid, 256, 0, s>>>(rows, node_off, emb, num_graphs);
+    else if (op == POOL_OP_MAX) mean_pool_rows_kernel<D, POOL_OP_MAX><<<grid, 256, 0, s>>>(rows, node_off, emb, num_graphs);
+    else mean_pool_rows_kernel<D><<<grid, 256, 0, s>>>(rows, node_off, emb, num_graphs);
+}
+// (the folded paths: mean or sum -- a caller un-folds its last stage under the maximum; asked for the maximum, or for a mode that does
+// not exist, it launches nothing and answers FLOWGNN_ERR_UNSUPPORTED: never the mean's logits under another mode's name)
+template <int UNUSED = 0>  // (a template so that only the translation units that call it hold the kernels)
+inline int launch_segment_bias(int op, const float* score, const int* node_off, const float* pb, float* out, int num_graphs, hipStream_t s) {
+    const int grid = (num_graphs + 255) / 256;
+    if (op == POOL_OP_SUM) segment_mean_bias_kernel<0, POOL_OP_SUM><<<grid, 256, 0, s>>>(score, node_off, pb, out, num_graphs);
+    else if (op == POOL_OP_MEAN) segment_mean_bias_kernel<0><<<grid, 256, 0, s>>>(score, node_off, pb, out, num_graphs);
+    else {
+        set_last_error("launch_segment_bias: per-node scores can be pooled by mean or sum only (a maximum needs the un-folded last stage)");
+        return 8;  // FLOWGNN_ERR_UNSUPPORTED
+    }
+    return 0;
+}
+template <int D>
+inline void launch_pooled_head(const float* emb, const float* pw, const float* pb, float* out, int num_graphs, int num_tasks, hipStream_t s) {
+    if (num_graphs <= 0) return;
+    pooled_head_kernel<D><<<(num_graphs + 15) / 16, 256, 0, s>>>(emb, pw, pb, out, num_graphs, num_tasks);
 }
 
 // ---------------------------------------------------------------- node logits: the per-node terms of a mean-pool + linear readout

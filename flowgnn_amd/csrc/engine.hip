@@ -707,6 +707,7 @@ static int set_batch_state(flowgnn_engine* e, int num_graphs, const int* nums_of
     db.node_eigen = eig ? e->d_eig : nullptr;
     db.h[0] = e->d_h0; db.h[1] = e->d_h1; db.scratch = e->d_scratch; db.out = e->d_out;
     db.num_tasks = e->num_tasks;
+    db.pooling = e->pooling;
     db.final_h = 0;
     db.tap = nullptr;
     db.tap_dim = 0;
@@ -1099,6 +1100,10 @@ int flowgnn_set_node_logits(flowgnn_engine* e, int on) {
         e->err = "flowgnn_set_node_logits: there are no fixed-point node logits (FLOWGNN_NUMERIC_Q6_10)";
         return FLOWGNN_ERR_UNSUPPORTED;
     }
+    if (on && e->pooling != FLOWGNN_POOL_MEAN) {
+        e->err = "flowgnn_set_node_logits: the pooling is not the mean (flowgnn_set_pooling), and node logits are the terms whose mean is the logit";
+        return FLOWGNN_ERR_UNSUPPORTED;
+    }
     ENGINE_TRY(e, use_device(e));
     e->drop_graph();  // a recorded launch sequence is that of the other setting
     e->nlog_on = on != 0;
@@ -1282,6 +1287,10 @@ int flowgnn_set_numeric_mode(flowgnn_engine* e, int mode) {
         e->err = "flowgnn_set_numeric_mode: attention is on, and there are no fixed-point attention coefficients";
         return FLOWGNN_ERR_UNSUPPORTED;
     }
+    if (mode == FLOWGNN_NUMERIC_Q6_10 && e->pooling != FLOWGNN_POOL_MEAN) {
+        e->err = "flowgnn_set_numeric_mode: the pooling is not the mean (flowgnn_set_pooling), and the fixed-point readout is the reference's mean";
+        return FLOWGNN_ERR_UNSUPPORTED;
+    }
     e->drop_graph();
     const int rc = e->model->set_numeric_mode(mode);
     if (!rc) e->numeric_mode = mode;
@@ -1289,6 +1298,33 @@ int flowgnn_set_numeric_mode(flowgnn_engine* e, int mode) {
                      "readout is single-task and NUM_TASK != 1";
     return rc;
 }
+
+int flowgnn_set_pooling(flowgnn_engine* e, int mode) {
+    if (!e) return FLOWGNN_ERR_ARG;
+    if (mode != FLOWGNN_POOL_MEAN && mode != FLOWGNN_POOL_SUM && mode != FLOWGNN_POOL_MAX) {
+        e->err = "flowgnn_set_pooling: the modes are FLOWGNN_POOL_MEAN (0), FLOWGNN_POOL_SUM (1) and FLOWGNN_POOL_MAX (2)";
+        return FLOWGNN_ERR_ARG;
+    }
+    if (mode != FLOWGNN_POOL_MEAN && (e->model_id == FLOWGNN_MODEL_PNA || e->model_id == FLOWGNN_MODEL_DGN)) {
+        e->err = "flowgnn_set_pooling: PNA and DGN read the pooled vector through an MLP head that was trained on the mean";
+        return FLOWGNN_ERR_UNSUPPORTED;
+    }
+    if (mode != FLOWGNN_POOL_MEAN && e->numeric_mode == FLOWGNN_NUMERIC_Q6_10) {
+        e->err = "flowgnn_set_pooling: the fixed-point readout (FLOWGNN_NUMERIC_Q6_10) is the reference's mean";
+        return FLOWGNN_ERR_UNSUPPORTED;
+    }
+    if (mode != FLOWGNN_POOL_MEAN && e->nlog_on) {
+        e->err = "flowgnn_set_pooling: node logits are on, and they are the terms whose mean is the logit";
+        return FLOWGNN_ERR_UNSUPPORTED;
+    }
+    ENGINE_TRY(e, use_device(e));
+    e->drop_graph();  // a recorded launch sequence is that of the other mode
+    e->pooling = mode;
+    e->db.pooling = mode;  // (launches are stream-ordered: the mode matters to those enqueued after this call)
+    return FLOWGNN_OK;
+}
+
+int flowgnn_pooling(const flowgnn_engine* e) { return e ? e->pooling : -1; }
 
 int flowgnn_set_option(flowgnn_engine* e, const char* key, double value) {
     if (!e || !key) return FLOWGNN_ERR_ARG;

@@ -76,6 +76,7 @@ struct flowgnn_engine {
     // graph embeddings (flowgnn_set_embeddings): off by default; db.emb is null then and every forward is the one it was
     bool emb_on = false;
     int numeric_mode = FLOWGNN_NUMERIC_F32;
+    int pooling = FLOWGNN_POOL_MEAN;  // flowgnn_set_pooling: the engine's, across batches (db.pooling follows it)
     fg::GrowBuf emb;                // the engine's own [G][dim] buffer (allocated when first needed, outlives the batch)
     float* emb_user = nullptr;      // flowgnn_set_embeddings_buffer (reset by set_batch)
     float* emb_last = nullptr;      // where the last flowgnn_run put them (null: it ran with embeddings off)

@@ -16,6 +16,7 @@ static flowgnn_group* g_entry_group[6] = {nullptr, nullptr, nullptr, nullptr, nu
 static std::vector<int> g_entry_devices;  // empty: not decided yet (the environment is asked at the first call)
 static int g_entry_pipeline = 0;          // flowgnn_entry_set_pipeline: ranges per engine (0: by the size of the host arrays, 1: off)
 static std::vector<std::pair<std::string, double>> g_entry_options[6];
+static int g_entry_pooling[6] = {0, 0, 0, 0, 0, 0};  // flowgnn_entry_set_pooling (FLOWGNN_POOL_MEAN)
 // The weight set an entry-point group holds, kept on the host: a caller that reloads the SAME set on every graph
 // (reload_weights = 1 everywhere is legal in the reference and cheap there) must not pay a repack + upload per graph.
 // Compared with memcmp -- no hash, no collision to reason about.
@@ -77,6 +78,21 @@ int flowgnn_entry_set_option(int model, const char* key, double value) {
     return FLOWGNN_OK;
 }
 
+int flowgnn_entry_set_pooling(int model, int mode) {
+    if (model < 0 || model >= 6 || mode < FLOWGNN_POOL_MEAN || mode > FLOWGNN_POOL_MAX) return FLOWGNN_ERR_ARG;
+    if (mode != FLOWGNN_POOL_MEAN && (model == FLOWGNN_MODEL_PNA || model == FLOWGNN_MODEL_DGN)) {
+        fg::set_last_error("flowgnn_entry_set_pooling: PNA and DGN read the pooled vector through an MLP head that was trained on the mean");
+        return FLOWGNN_ERR_UNSUPPORTED;
+    }
+    std::lock_guard<std::mutex> lock(g_entry_mutex);
+    if (g_entry_group[model]) {  // (remembered only once the engines have accepted it: a refused mode must not reach a later group)
+        const int rc = flowgnn_group_set_pooling(g_entry_group[model], mode);
+        if (rc) return rc;
+    }
+    g_entry_pooling[model] = mode;
+    return FLOWGNN_OK;
+}
+
 static int compute_graphs_generic(int model, int num_graphs, const int* nums_of_nodes, const int* nums_of_edges,
                                   const int* reload_weights, float* out, const int* node_feature, const float* node_eigen,
                                   const int* edge_list, const int* edge_attr, int ntens, const float* const* tens,
@@ -100,6 +116,10 @@ static int compute_graphs_generic(int model, int num_graphs, const int* nums_of_
         if (rc) return rc;
         for (auto& kv : g_entry_options[model]) {
             rc = flowgnn_group_set_option(grp, kv.first.c_str(), kv.second);
+            if (rc) return rc;
+        }
+        if (g_entry_pooling[model] != FLOWGNN_POOL_MEAN) {
+            rc = flowgnn_group_set_pooling(grp, g_entry_pooling[model]);
             if (rc) return rc;
         }
         g_entry_wcopy[model].clear();

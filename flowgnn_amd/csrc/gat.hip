@@ -29,8 +29,15 @@ namespace fg {
 // kernels, with internal linkage and unused, are dropped.
 // gat_attn.hip does the same with FG_RESIDENT_ATTN_TU, for gat_resident_attn_kernel: the instance that also stores the attention
 // coefficients of the selected layers (flowgnn_set_attention), and the node logits too when those are on as well.
-#if defined(FG_RESIDENT_NLOGIT_TU) || defined(FG_RESIDENT_ATTN_TU)
+// gat_poolsum.hip: FG_RESIDENT_POOLSUM_TU, for gat_resident_poolsum_kernel -- the instance whose readout is the SUM of the graph's terms
+// (flowgnn_set_pooling, FLOWGNN_POOL_SUM): the same kernel without the readout's division, the same arguments.
+#if defined(FG_RESIDENT_NLOGIT_TU) || defined(FG_RESIDENT_ATTN_TU) || defined(FG_RESIDENT_POOLSUM_TU)
 #define FG_RESIDENT_INSTANCE_TU 1
+#endif
+#ifdef FG_RESIDENT_POOLSUM_TU
+#define GAT_POOL_SUM 1
+#else
+#define GAT_POOL_SUM 0
 #endif
 // the graph-resident kernel's weights (per layer in device memory, GatModel::d_res_: see GATR_LAYER_BYTES below)
 struct GatResidentDev {
@@ -59,6 +66,7 @@ struct GatResidentLaunch {
 };
 void launch_gat_resident_nlogit(const GatResidentLaunch& a, hipStream_t s);  // gat_nlogit.hip
 void launch_gat_resident_attn(const GatResidentLaunch& a, hipStream_t s);    // gat_attn.hip (node_logits may be null there)
+void launch_gat_resident_poolsum(const GatResidentLaunch& a, hipStream_t s); // gat_poolsum.hip (node_logits unused)
 #ifdef FG_RESIDENT_INSTANCE_TU
 namespace {
 #endif
@@ -577,7 +585,7 @@ __global__ __launch_bounds__(GATR_WAVES * 64, 4) void gat_resident_kernel(const 
                                                                          const int* __restrict__ tile_row, const int* __restrict__ tile_graph,
                                                                          const int* __restrict__ node_off, float* __restrict__ out, int n_tiles,
                                                                          GatResidentDev w, int ablate_arg GAT_NLOGIT_PARAM) {
-#ifndef FG_RESIDENT_INSTANCE_TU
+#if !defined(FG_RESIDENT_INSTANCE_TU) || defined(FG_RESIDENT_POOLSUM_TU)
     constexpr float* node_logits = nullptr;  // (the storing instances have it as an argument)
 #endif
     const int ablate = FG_ABLATE(ablate_arg);  // 0 in the shipped build: the branches below fold away (common.h)
@@ -960,7 +968,11 @@ __global__ __launch_bounds__(GATR_WAVES * 64, 4) void gat_resident_kernel(const 
 #ifdef FG_RESIDENT_ATTN_TU
         if (node_logits != nullptr && (int)threadIdx.x < rows) node_logits[(size_t)t0 + threadIdx.x] = s_dot[threadIdx.x] + pool_bias;
 #endif
+#if GAT_POOL_SUM  // (the same chain of adds, the same lane, no division)
+        if (g0 + (int)threadIdx.x < g1) out[g0 + threadIdx.x] = lds_sum_in_order(s_dot + (ro_n0 - t0), ro_n1 - ro_n0) + pool_bias;
+#else
         if (g0 + (int)threadIdx.x < g1) out[g0 + threadIdx.x] = lds_sum_in_order(s_dot + (ro_n0 - t0), ro_n1 - ro_n0) / (float)(ro_n1 - ro_n0) + pool_bias;
+#endif
         if (!has_next) break;
         tile = ntile; t0 = nt0; rows = nrows; g0 = ng0; g1 = ng1; e0 = ne0; ne = nne;
     }
@@ -1171,7 +1183,10 @@ public:
         // nodes, waste MFMA columns: the per-layer kernels take those); per-node taps (flowgnn_get_h) come from the per-layer path
         // (graph embeddings, db.emb: the resident kernel never forms the pooled row -- the per-layer path with the un-folded last stage does)
         // (node embeddings, db.node_emb: likewise -- the resident kernel folds the last layer's skip contraction into the readout)
-        if (resident_ && !keep_h_ && !db.emb && !db.node_emb && fold_readout_ && split_ && !exact_ && db.gtiles.ok && db.gtiles.n_tiles > 0 && db.gtiles.fill >= 0.5) {
+        // (pooling, db.pooling: the sum has an instance of the resident kernel -- gat_poolsum.hip; with attention on as well, and for the
+        // maximum, the per-layer path pools)
+        if (resident_ && !keep_h_ && !db.emb && !db.node_emb && fold_readout_ && split_ && !exact_ && db.gtiles.ok && db.gtiles.n_tiles > 0 && db.gtiles.fill >= 0.5 &&
+            (db.pooling == POOL_OP_MEAN || (db.pooling == POOL_OP_SUM && !db.attn_mask))) {
             GatResidentDev rw;
             rw.layers = d_res_;
             rw.scales = d_scales_;
@@ -1184,7 +1199,10 @@ public:
             rw.range_flag = db.range_flag;
             ProfScope p(prof, "gat_resident", s);
             const int grid = db.gtiles.n_tiles < 256 ? db.gtiles.n_tiles : 256;  // persistent: one 16-wave workgroup per CU (118 KB of LDS)
-            if (db.attn_mask)  // the instance that also stores the selected layers' attention coefficients, and the node logits if on (gat_attn.hip)
+            if (db.pooling == POOL_OP_SUM)  // the instance whose readout is the sum (gat_poolsum.hip)
+                launch_gat_resident_poolsum(GatResidentLaunch{grid, db.b.node_feature, feat_row, db.csr.row_ptr, db.csr.src, db.gtiles.row_start,
+                                                              db.gtiles.graph_start, db.b.node_off, db.out, db.gtiles.n_tiles, rw, ablate_, nullptr}, s);
+            else if (db.attn_mask)  // the instance that also stores the selected layers' attention coefficients, and the node logits if on (gat_attn.hip)
                 launch_gat_resident_attn(GatResidentLaunch{grid, db.b.node_feature, feat_row, db.csr.row_ptr, db.csr.src, db.gtiles.row_start,
                                                            db.gtiles.graph_start, db.b.node_off, db.out, db.gtiles.n_tiles, rw, ablate_,
                                                            db.node_logits, db.attn_mask, db.attn_edge, db.attn_self, db.csr.eid, db.b.e_tot, n}, s);
@@ -1206,7 +1224,8 @@ public:
             ProfScope p(prof, "gat_scores0", s);
             gat_scores0_kernel<<<(n + 255) / 256, 256, 0, s>>>(db.b.node_feature, feat_row, d_lin0_, d_asrc_, d_atgt_, scoreb[0], n);
         }
-        const bool fold = fold_readout_ && !db.emb && !db.node_emb;  // embeddings pool the `emb` rows themselves; node embeddings are those rows
+        // embeddings pool the `emb` rows themselves; node embeddings are those rows; the maximum needs the rows too (W . max is not a maximum of scores)
+        const bool fold = fold_readout_ && !db.emb && !db.node_emb && db.pooling != POOL_OP_MAX;
         int cur = 0;
         for (int l = 0; l < GAT_L; l++) {
             GatLayerDev w;
@@ -1257,14 +1276,13 @@ public:
         {
             ProfScope p(prof, "mean_pool_linear", s);
             if (fold)
-                segment_mean_bias_kernel<0><<<(db.b.num_graphs + 255) / 256, 256, 0, s>>>(emb, db.b.node_off, d_pb_, db.out, db.b.num_graphs);
+                { if (int rc = launch_segment_bias(db.pooling, emb, db.b.node_off, d_pb_, db.out, db.b.num_graphs, s)) return rc; }
             else
-                mean_pool_linear_kernel<GAT_D><<<(db.b.num_graphs + 3) / 4, 256, 0, s>>>(emb, db.b.node_off, d_pw_, d_pb_, db.out,
-                                                                                         db.b.num_graphs);
+                launch_pool_linear<GAT_D>(db.pooling, emb, db.b.node_off, d_pw_, d_pb_, db.out, db.b.num_graphs, s);
         }
         if (db.emb) {
             ProfScope p(prof, "mean_pool_rows", s);
-            mean_pool_rows_kernel<GAT_D><<<(db.b.num_graphs + 3) / 4, 256, 0, s>>>(emb, db.b.node_off, db.emb, db.b.num_graphs);
+            launch_pool_rows<GAT_D>(db.pooling, emb, db.b.node_off, db.emb, db.b.num_graphs, s);
         }
         if (db.node_logits) {
             // node logits (flowgnn_set_node_logits): the folded last stage left emb[v] . w as float[n], the un-folded one the 16-wide rows
@@ -1313,6 +1331,12 @@ void launch_gat_resident_attn(const GatResidentLaunch& a, hipStream_t s) {
     gat_resident_kernel<<<a.grid, GATR_WAVES * 64, 0, s>>>(a.node_feature, a.feat_row, a.row_ptr, a.src, a.tile_row, a.tile_graph, a.node_off, a.out,
                                                            a.n_tiles, a.w, a.ablate, a.node_logits, a.attn_mask, a.attn_edge, a.attn_self, a.eid,
                                                            a.e_tot, a.n_tot);
+}
+#endif
+#ifdef FG_RESIDENT_POOLSUM_TU
+void launch_gat_resident_poolsum(const GatResidentLaunch& a, hipStream_t s) {
+    gat_resident_kernel<<<a.grid, GATR_WAVES * 64, 0, s>>>(a.node_feature, a.feat_row, a.row_ptr, a.src, a.tile_row, a.tile_graph, a.node_off, a.out,
+                                                           a.n_tiles, a.w, a.ablate);
 }
 #endif
 #ifdef FG_RESIDENT_NLOGIT_TU

@@ -41,9 +41,17 @@ void launch_gcn_resident_rows(const GcnResidentLaunch& a, hipStream_t s);  // gc
 // gcn_nlogit.hip does the same with FG_RESIDENT_NLOGIT_TU, for gcn_resident_nlogit_kernel: the instance that also stores every node's
 // term of the readout, a[v] . w + b, in the caller's node order (flowgnn_set_node_logits)
 void launch_gcn_resident_nlogit(const GcnResidentLaunch& a, hipStream_t s);  // gcn_nlogit.hip
-#if defined(FG_RESIDENT_ROWS_TU) || defined(FG_RESIDENT_NLOGIT_TU)
+// gcn_poolsum.hip: FG_RESIDENT_POOLSUM_TU, for gcn_resident_poolsum_kernel -- the instance whose readout is the SUM of the graph's terms
+// (flowgnn_set_pooling, FLOWGNN_POOL_SUM): the same kernel without the readout's division, the same arguments
+void launch_gcn_resident_poolsum(const GcnResidentLaunch& a, hipStream_t s);  // gcn_poolsum.hip
+#if defined(FG_RESIDENT_ROWS_TU) || defined(FG_RESIDENT_NLOGIT_TU) || defined(FG_RESIDENT_POOLSUM_TU)
 #define FG_RESIDENT_STORING_TU 1
 namespace {
+#endif
+#ifdef FG_RESIDENT_POOLSUM_TU
+constexpr bool RESIDENT_POOL_SUM = true;
+#else
+constexpr bool RESIDENT_POOL_SUM = false;
 #endif
 #ifdef FG_RESIDENT_ROWS_TU
 constexpr bool RESIDENT_ROWS = true;
@@ -1083,7 +1091,11 @@ __global__ __launch_bounds__(GCNR_WAVES * 64, 3) void gcn_resident_kernel(const 
             x0_store(nrows, 0, XH);  // (nrows = 0 behind the last tile)
             x0_request(XH, XK);  // the second half travels under the readout, the CSR staging and the row sort of the next tile
         }
-        if (ro_gi < g1) out[ro_g] = lds_sum_in_order(s_dot + (ro_n0 - t0), ro_n1 - ro_n0) / (float)(ro_n1 - ro_n0) + pool_bias;
+        if constexpr (RESIDENT_POOL_SUM) {  // (the same chain of adds, the same lane, no division)
+            if (ro_gi < g1) out[ro_g] = lds_sum_in_order(s_dot + (ro_n0 - t0), ro_n1 - ro_n0) + pool_bias;
+        } else {
+            if (ro_gi < g1) out[ro_g] = lds_sum_in_order(s_dot + (ro_n0 - t0), ro_n1 - ro_n0) / (float)(ro_n1 - ro_n0) + pool_bias;
+        }
         if constexpr (RESIDENT_NLOGIT) {
             // the terms the readout is summing, one thread per row of the tile: a graph's rows are consecutive in the tile and in the
             // batch, so the 4-byte stores of a wave fall into a few runs; rows of padding (tid >= rows) are never stored
@@ -1310,8 +1322,10 @@ public:
     bool use_resident(const DeviceBatch& db) const {
         // (graph embeddings, db.emb: the resident kernel folds the head per node and never forms the pooled row -- the per-layer path does;
         // with node embeddings on as well, db.node_emb, the storing instance leaves the rows in HBM and they are pooled from there)
+        // (pooling, db.pooling: the sum has an instance of the resident kernel -- gcn_poolsum.hip; with node embeddings on, rows in HBM, the
+        // sum is taken from them behind the storing instance's launch.  The maximum is taken from the per-layer path's rows)
         return resident_ && table_ok_ && !qmode_ && !keep_h_ && (!db.emb || db.node_emb) && split_ && !exact_ && fused_ && num_tasks_ == 1 && db.gtiles.ok && db.gtiles.n_tiles > 0 &&
-               db.gtiles.fill >= 0.5;
+               db.gtiles.fill >= 0.5 && db.pooling != POOL_OP_MAX;
     }
     // the one-pass front end (gcn_tile_build_kernel + the resident kernel's own encoder): the default; gcn_tile_build = 0 restores the
     // three-launch front end (index build, projected encoder, resident kernel)
@@ -1346,6 +1360,11 @@ public:
                                                                t_row, t_graph, db.b.node_off, db.out, n_tiles, db.range_flag, ablate_,
                                                                reinterpret_cast<const uint8_t*>(desc_.p), reinterpret_cast<const float4*>(d_enc_tab_),
                                                                bp ? db.gtiles.bp_list : nullptr, bp ? db.gtiles.bp_lrow : nullptr, db.node_emb}, s);
+                else if (db.pooling == POOL_OP_SUM)  // ... or the instance whose readout is the sum (gcn_poolsum.hip)
+                    launch_gcn_resident_poolsum(GcnResidentLaunch{true, n_tiles < 256 ? n_tiles : 256, nullptr, nullptr, nullptr, nullptr, nullptr, d_res_, d_pw_, d_pb_,
+                                                                  t_row, t_graph, db.b.node_off, db.out, n_tiles, db.range_flag, ablate_,
+                                                                  reinterpret_cast<const uint8_t*>(desc_.p), reinterpret_cast<const float4*>(d_enc_tab_),
+                                                                  bp ? db.gtiles.bp_list : nullptr, bp ? db.gtiles.bp_lrow : nullptr, nullptr}, s);
                 else if (db.node_logits)  // ... or the instance that stores the per-node readout terms (gcn_nlogit.hip)
                     launch_gcn_resident_nlogit(GcnResidentLaunch{true, n_tiles < 256 ? n_tiles : 256, nullptr, nullptr, nullptr, nullptr, nullptr, d_res_, d_pw_, d_pb_,
                                                                  t_row, t_graph, db.b.node_off, db.out, n_tiles, db.range_flag, ablate_,
@@ -1366,6 +1385,10 @@ public:
                     launch_gcn_resident_rows(GcnResidentLaunch{false, grid, db.h[0], db.csr.row_ptr, db.csr.src, db.csr.ecode, db.csr.out_deg, d_res_, d_pw_, d_pb_,
                                                                db.gtiles.row_start, db.gtiles.graph_start, db.b.node_off, db.out, db.gtiles.n_tiles,
                                                                db.range_flag, ablate_, nullptr, nullptr, nullptr, nullptr, db.node_emb}, s);
+                else if (db.pooling == POOL_OP_SUM)
+                    launch_gcn_resident_poolsum(GcnResidentLaunch{false, grid, db.h[0], db.csr.row_ptr, db.csr.src, db.csr.ecode, db.csr.out_deg, d_res_, d_pw_, d_pb_,
+                                                                  db.gtiles.row_start, db.gtiles.graph_start, db.b.node_off, db.out, db.gtiles.n_tiles,
+                                                                  db.range_flag, ablate_, nullptr, nullptr, nullptr, nullptr, nullptr}, s);
                 else if (db.node_logits)
                     launch_gcn_resident_nlogit(GcnResidentLaunch{false, grid, db.h[0], db.csr.row_ptr, db.csr.src, db.csr.ecode, db.csr.out_deg, d_res_, d_pw_, d_pb_,
                                                                  db.gtiles.row_start, db.gtiles.graph_start, db.b.node_off, db.out, db.gtiles.n_tiles,
@@ -1377,7 +1400,11 @@ public:
             }
             if (db.emb) {  // (only with db.node_emb: use_resident)
                 ProfScope p(prof, "mean_pool_rows", s);
-                mean_pool_rows_kernel<GCN_D><<<(db.b.num_graphs + 3) / 4, 256, 0, s>>>(db.node_emb, db.b.node_off, db.emb, db.b.num_graphs);
+                launch_pool_rows<GCN_D>(db.pooling, db.node_emb, db.b.node_off, db.emb, db.b.num_graphs, s);
+            }
+            if (db.node_emb && db.pooling == POOL_OP_SUM) {  // the storing instance's readout is the mean: the sum from its rows, which are in HBM
+                ProfScope p(prof, "mean_pool_linear", s);
+                launch_pool_linear<GCN_D>(db.pooling, db.node_emb, db.b.node_off, d_pw_, d_pb_, db.out, db.b.num_graphs, s);
             }
             if (db.node_emb && db.node_logits) {  // node embeddings on as well: the rows are in HBM, the terms are taken from them
                 ProfScope p(prof, "node_logits", s);
@@ -1427,7 +1454,8 @@ public:
         }
         db.final_h = cur;
         db.h_valid = true;
-        if (split_ && !exact_ && fused_ && db.b.e_tot > 0 && num_tasks_ == 1 && !db.emb && !db.node_emb) {
+        if (split_ && !exact_ && fused_ && db.b.e_tot > 0 && num_tasks_ == 1 && !db.emb && !db.node_emb && db.pooling != POOL_OP_MAX) {
+            // (the maximum un-folds it: W . max is not a maximum of per-node scores; the sum keeps the fold)
             // last stage: aggregation + BatchNorm with the readout's linear head folded in (per-node scores in db.scratch;
             // flowgnn_get_h returns x_4 = db.h[final_h], which is untouched by this)
             {
@@ -1439,7 +1467,7 @@ public:
                                                                   d_ep_ + (size_t)(GCN_L - 1) * 3 * GCN_D, nullptr, n, db.range_flag, d_pw_);
             }
             ProfScope p(prof, "mean_pool_linear", s);
-            segment_mean_bias_kernel<0><<<(db.b.num_graphs + 255) / 256, 256, 0, s>>>(db.scratch, db.b.node_off, d_pb_, db.out, db.b.num_graphs);
+            if (int rc = launch_segment_bias(db.pooling, db.scratch, db.b.node_off, d_pb_, db.out, db.b.num_graphs, s)) return rc;
             if (db.node_logits) {  // node logits: the per-node scores plus the head's bias
                 ProfScope p2(prof, "node_logits", s);
                 node_logits_bias_kernel<0><<<(n + 255) / 256, 256, 0, s>>>(db.scratch, d_pb_, db.node_logits, n);
@@ -1455,16 +1483,13 @@ public:
         {
             ProfScope p(prof, "mean_pool_linear", s);
             if (num_tasks_ > 1) {  // NUM_TASK outputs per graph (linear_input_stationary over [NUM_TASK][100], GCN/src/finalize.cc:79-113)
-                const int blocks = (db.b.num_graphs + 3) / 4;
-                mean_pool_linear_mt_kernel<GCN_D><<<blocks < 512 ? blocks : 512, 256, 0, s>>>(rows, db.b.node_off, d_pw_, d_pb_, db.out,
-                                                                                              db.b.num_graphs, num_tasks_);
+                launch_pool_linear_mt<GCN_D>(db.pooling, rows, db.b.node_off, d_pw_, d_pb_, db.out, db.b.num_graphs, num_tasks_, s);
             } else
-            mean_pool_linear_kernel<GCN_D><<<(db.b.num_graphs + 3) / 4, 256, 0, s>>>(rows, db.b.node_off, d_pw_, d_pb_,
-                                                                                     db.out, db.b.num_graphs);
+            launch_pool_linear<GCN_D>(db.pooling, rows, db.b.node_off, d_pw_, d_pb_, db.out, db.b.num_graphs, s);
         }
         if (db.emb) {
             ProfScope p(prof, "mean_pool_rows", s);
-            mean_pool_rows_kernel<GCN_D><<<(db.b.num_graphs + 3) / 4, 256, 0, s>>>(rows, db.b.node_off, db.emb, db.b.num_graphs);
+            launch_pool_rows<GCN_D>(db.pooling, rows, db.b.node_off, db.emb, db.b.num_graphs, s);
         }
         if (db.node_logits) {  // node logits from the rows the readout pools, every task
             ProfScope p(prof, "node_logits", s);
@@ -1558,21 +1583,26 @@ Model* make_gcn_model() { return new GcnModel(); }
 
 #ifdef FG_RESIDENT_STORING_TU
 }  // namespace
-#ifdef FG_RESIDENT_NLOGIT_TU
-#define GCN_STORE_ARG a.node_logits
+#if defined(FG_RESIDENT_POOLSUM_TU)
+#define GCN_STORE_ARG /* (no stored output: the kernel's argument list ends with lrow) */
+void launch_gcn_resident_poolsum(const GcnResidentLaunch& a, hipStream_t s) {
+#elif defined(FG_RESIDENT_NLOGIT_TU)
+#define GCN_STORE_ARG , a.node_logits
 void launch_gcn_resident_nlogit(const GcnResidentLaunch& a, hipStream_t s) {
 #else
-#define GCN_STORE_ARG a.node_emb
+#define GCN_STORE_ARG , a.node_emb
 void launch_gcn_resident_rows(const GcnResidentLaunch& a, hipStream_t s) {
 #endif
+    // (GCN_STORE_ARG: ", <the instance's output pointer>" -- it brings its own comma, and is empty for the sum instance, whose argument
+    // list is the default kernel's)
     if (a.onepass)
         gcn_resident_kernel<true><<<a.grid, GCNR_WAVES * 64, 0, s>>>(a.x0, a.row_ptr, a.src, a.ecode, a.out_deg, a.layers, a.pool_w, a.pool_b, a.tile_row,
                                                                      a.tile_graph, a.node_off, a.out, a.n_tiles, a.range_flag, a.ablate, a.desc, a.enc_tab,
-                                                                     a.list, a.lrow, GCN_STORE_ARG);
+                                                                     a.list, a.lrow GCN_STORE_ARG);
     else
         gcn_resident_kernel<false><<<a.grid, GCNR_WAVES * 64, 0, s>>>(a.x0, a.row_ptr, a.src, a.ecode, a.out_deg, a.layers, a.pool_w, a.pool_b, a.tile_row,
                                                                       a.tile_graph, a.node_off, a.out, a.n_tiles, a.range_flag, a.ablate, a.desc, a.enc_tab,
-                                                                      a.list, a.lrow, GCN_STORE_ARG);
+                                                                      a.list, a.lrow GCN_STORE_ARG);
 }
 #endif
 

@@ -770,7 +770,7 @@ public:
     // the batch's half-tiles on gin_pp_kernel, the few graphs beyond the half-tile limits on gin_resident_kernel.  (Decided from the
     // SHARD's own half-tile fill: unlike the shipped kernels' choices this one does not follow the job -- development only.)
     bool use_pingpong(const DeviceBatch& db) const {
-        return pingpong_ && !f16_ && !virtual_node_ && use_resident(db) && !keep_h_ && !db.node_logits && num_tasks_ == 1 && fold_readout_ && head_fold_ && db.gtiles.sub_ok &&
+        return pingpong_ && !f16_ && !virtual_node_ && use_resident(db) && !keep_h_ && !db.node_logits && db.pooling == POOL_OP_MEAN && num_tasks_ == 1 && fold_readout_ && head_fold_ && db.gtiles.sub_ok &&
                db.gtiles.n_sub > 0 && db.gtiles.sub_fill >= resident_min_fill_;
     }
 #endif
@@ -794,7 +794,10 @@ public:
         const bool want = tile_build_ < 0 ? !(pingpong_ && !virtual_node_ && !f16_) : tile_build_ != 0;
         // (graph embeddings, db.emb: the un-folded resident instance pools h_5 on chip; it has the three-kernel front end.  Node
         // embeddings, db.node_emb: the same instance writes its h_5 rows, batch-order tiles)
-        return want && use_resident(db) && !qmode_ && !keep_h_ && !db.emb && !db.node_emb && num_tasks_ == 1 && fold_readout_ && head_fold_ && db.b.edge_attr != nullptr;
+        // (pooling, db.pooling: the sum has instances of the folded kernel with both front ends; the maximum is taken by the un-folded pooling
+        // instance, which has the three-kernel one)
+        return want && use_resident(db) && !qmode_ && !keep_h_ && !db.emb && !db.node_emb && num_tasks_ == 1 && fold_readout_ && head_fold_ && db.b.edge_attr != nullptr &&
+               db.pooling != POOL_OP_MAX;
     }
     bool needs_csr(const DeviceBatch& db) const override { return !one_pass(db); }
     // (asked at flowgnn_set_batch, before the batch is known: the lists are built whenever the one-pass path could take them)
@@ -821,9 +824,10 @@ public:
                 launch_gin_tile_build(tb, t_row, t_graph, reinterpret_cast<uint8_t*>(perm_.p), n_tiles, virtual_node_, resident_order_, s);
             }
             ProfScope p(prof, "gin_resident", s);  // the whole model
-            launch_gin_resident(nullptr, nullptr, nullptr, nullptr, nullptr, d_ecomb_res_, rsplit(), d_pw_, d_pb_, t_row, t_graph,
+            if (int rc = launch_gin_resident(nullptr, nullptr, nullptr, nullptr, nullptr, d_ecomb_res_, rsplit(), d_pw_, d_pb_, t_row, t_graph,
                                 reinterpret_cast<uint8_t*>(perm_.p), db.b.node_off, db.out, n_tiles,
-                                db.range_flag, s, virtual_node_, head(), resident_order_, resident_prof_, &tb, 1, f16_, nullptr, db.node_logits);
+                                db.range_flag, s, virtual_node_, head(), resident_order_, resident_prof_, &tb, 1, f16_, nullptr, db.node_logits, db.pooling))
+                return rc;
             db.final_h = 0;
             db.h_valid = false;
             h0_in_hbm_ = false;  // the tile loader computed h_0 on chip
@@ -862,23 +866,37 @@ public:
             if (int rc = perm_.reserve((size_t)db.gtiles.n_tiles * (GIN_RESIDENT_DESC_BYTES / 4))) return rc;
             // (node logits where the folded instance does not run -- graph embeddings on as well, or un-folded by option: the rows go
             // to HBM and the terms are taken from them, as the pooled rows are)
-            const bool rows = keep_h_ || multi || db.node_emb || (db.node_logits && (db.emb || !(fold_readout_ && head_fold_)));
+            // (pooling: the sum's instances are the folded ones -- with graph embeddings on, or un-folded by option, the rows go to HBM and
+            // the generic kernels pool them; the maximum is taken on chip by the pooling instance unless the rows go to HBM anyway)
+            const bool sum = db.pooling == POOL_OP_SUM, max = db.pooling == POOL_OP_MAX;
+            const bool rows = keep_h_ || multi || db.node_emb || (db.node_logits && (db.emb || !(fold_readout_ && head_fold_))) ||
+                              (sum && (db.emb || !(fold_readout_ && head_fold_)));
             // (node embeddings: the rows go straight into the caller's buffer, and whatever reads h_5 behind the launch reads it there)
             float* const h5 = db.node_emb ? db.node_emb : db.h[1];
             // graph embeddings, single task: the un-folded instance that pools the h_5 rows out of LDS (no row goes to HBM); with the
             // rows in HBM anyway (NUM_TASK > 1, taps) they are pooled from there, behind the launch
             float* pool_emb = rows ? nullptr : db.emb;
+            if (max && !rows && !pool_emb) {  // the maxima with embeddings off: a [G][100] buffer of the model's own
+                if (int rc = pooled_.reserve((size_t)db.b.num_graphs * GIN_D)) return rc;
+                pool_emb = pooled_.p;
+            }
             {
                 ProfScope p(prof, "gin_resident", s);
-                launch_gin_resident(db.h[0], rows ? h5 : nullptr, db.csr.row_ptr, db.csr.src, db.csr.ecode, d_ecomb_res_, rsplit(), d_pw_, d_pb_,
+                if (int rc = launch_gin_resident(db.h[0], rows ? h5 : nullptr, db.csr.row_ptr, db.csr.src, db.csr.ecode, d_ecomb_res_, rsplit(), d_pw_, d_pb_,
                                     db.gtiles.row_start, db.gtiles.graph_start, reinterpret_cast<uint8_t*>(perm_.p), db.b.node_off,
-                                    multi ? nullptr : db.out, db.gtiles.n_tiles, db.range_flag, s, virtual_node_,
+                                    (multi || (rows && !mean_pool(db))) ? nullptr : db.out, db.gtiles.n_tiles, db.range_flag, s, virtual_node_,
                                     (!rows && fold_readout_ && head_fold_) ? head() : nullptr, resident_order_, resident_prof_, nullptr, 1, f16_, pool_emb,
-                                    db.node_logits);
+                                    db.node_logits, rows ? 0 : db.pooling))
+                    return rc;
             }
             db.final_h = rows ? 1 : 0;
             db.h_valid = rows && !db.node_emb;
+            if (max && !rows) {  // the head on the pooled maxima
+                ProfScope p(prof, "pooled_head", s);
+                launch_pooled_head<GIN_D>(pool_emb, d_pw_, d_pb_, db.out, db.b.num_graphs, 1, s);
+            }
             if (multi) launch_readout_mt(db, h5, prof, s);
+            else if (rows && !mean_pool(db)) launch_readout_rows(db, h5, prof, s);  // (the mean: the kernel's own readout wrote the logits)
             if (rows) launch_pool_rows(db, h5, prof, s);
             if (rows) launch_node_logits(db, h5, prof, s);  // (else the folded instance stored them)
             return 0;
@@ -892,7 +910,8 @@ public:
                 ProfScope p(prof, "gin_layer_fused", s);
                 // last layer: the readout's per-node dot product h'[v] . w_pred is taken in the epilogue and only that
                 // leaves the kernel (db.scratch as float[n]); the rows are written only for the flowgnn_get_h tap
-                const bool fold = l == GIN_L - 1 && fold_readout_ && !keep_h_ && !multi && !db.emb && !db.node_emb;
+                // (the maximum un-folds it: W . max is not a maximum of per-node scores; the sum keeps the fold)
+                const bool fold = l == GIN_L - 1 && fold_readout_ && !keep_h_ && !multi && !db.emb && !db.node_emb && db.pooling != POOL_OP_MAX;
                 launch_gin_layer_split(db.h[cur], fold ? db.scratch : hn, db.csr.row_ptr, db.csr.src, db.csr.ecode,
                                        layer_dev(l).ecomb, (f16_ ? d_split16_ : d_split_) + (size_t)l * GS_LAYER_BYTES, n, db.b.e_tot,
                                        l != GIN_L - 1, db.range_flag, split_nt_, s, fold ? d_pw_ : nullptr, f16_);
@@ -942,20 +961,25 @@ public:
         {
             ProfScope p(prof, "mean_pool_linear", s);
             if (folded)
-                segment_mean_bias_kernel<0><<<(db.b.num_graphs + 255) / 256, 256, 0, s>>>(db.scratch, db.b.node_off, d_pb_, db.out,
-                                                                                       db.b.num_graphs);
+                { if (int rc = launch_segment_bias(db.pooling, db.scratch, db.b.node_off, d_pb_, db.out, db.b.num_graphs, s)) return rc; }
             else
-                mean_pool_linear_kernel<GIN_D><<<(db.b.num_graphs + 3) / 4, 256, 0, s>>>(h5, db.b.node_off, d_pw_, d_pb_,
-                                                                                         db.out, db.b.num_graphs);
+                launch_pool_linear<GIN_D>(db.pooling, h5, db.b.node_off, d_pw_, d_pb_, db.out, db.b.num_graphs, s);
         }
         return 0;
+    }
+
+    static bool mean_pool(const DeviceBatch& db) { return db.pooling == POOL_OP_MEAN; }
+    // single-task sum / max readout from h_5 rows that a resident launch left in HBM (its own readout is the mean's)
+    void launch_readout_rows(DeviceBatch& db, const float* h, Profiler& prof, hipStream_t s) {
+        ProfScope p(prof, "mean_pool_linear", s);
+        launch_pool_linear<GIN_D>(db.pooling, h, db.b.node_off, d_pw_, d_pb_, db.out, db.b.num_graphs, s);
     }
 
     // graph embeddings from h_5 rows that are in HBM anyway (per-layer path, NUM_TASK > 1, taps)
     void launch_pool_rows(DeviceBatch& db, const float* h, Profiler& prof, hipStream_t s) {
         if (!db.emb) return;
         ProfScope p(prof, "mean_pool_rows", s);
-        mean_pool_rows_kernel<GIN_D><<<(db.b.num_graphs + 3) / 4, 256, 0, s>>>(h, db.b.node_off, db.emb, db.b.num_graphs);
+        fg::launch_pool_rows<GIN_D>(db.pooling, h, db.b.node_off, db.emb, db.b.num_graphs, s);
     }
 
     // node logits from h_5 rows that are in HBM (per-layer path, NUM_TASK > 1, taps, embeddings on as well): every task
@@ -967,9 +991,7 @@ public:
 
     void launch_readout_mt(DeviceBatch& db, const float* h, Profiler& prof, hipStream_t s) {
         ProfScope p(prof, "mean_pool_linear", s);
-        const int blocks = (db.b.num_graphs + 3) / 4;
-        mean_pool_linear_mt_kernel<GIN_D><<<blocks < 512 ? blocks : 512, 256, 0, s>>>(h, db.b.node_off, d_pw_, d_pb_, db.out, db.b.num_graphs,
-                                                                                      num_tasks_);
+        launch_pool_linear_mt<GIN_D>(db.pooling, h, db.b.node_off, d_pw_, d_pb_, db.out, db.b.num_graphs, num_tasks_, s);
     }
 
     void configure(const Options& o) override {
@@ -1038,6 +1060,7 @@ private:
         if (d_pp_tables_) { (void)hipFree(d_pp_tables_); d_pp_tables_ = nullptr; }
         enc_idx_.release();
         perm_.release();
+        pooled_.release();
         qw_.release();
     }
     bool ready_ = false;
@@ -1060,6 +1083,7 @@ private:
     bool f16_ = false;    // flowgnn_set_numeric_mode(FLOWGNN_NUMERIC_F16): single-product instances of the split kernels
     int num_tasks_ = 1;   // NUM_TASK (GIN/src/dcl.h:25) as a run-time dimension
     GinQWeights qw_;
+    GrowBuf pooled_;  // FLOWGNN_POOL_MAX with graph embeddings off: the [G][100] per-column maxima the resident pooling instance leaves for the head
     GrowBufI perm_;  // graph-resident path: per-tile descriptors (gin_tile_prep_kernel / gin_tile_build_kernel)
     GrowBufI enc_idx_;  // one-pass path: three table-row numbers per node in one word, written by gin_tile_build_kernel
     float* d_enc_tab_ = nullptr;  // ... and the pre-combined encoder table they index

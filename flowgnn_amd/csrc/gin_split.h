@@ -78,13 +78,17 @@ void gin_resident_pack_enc_table(const float* node_embedding /* [173][100] */, f
 // the one-pass front end: descriptors + encoder row numbers of every tile from the caller's arrays (then launch_gin_resident with tb)
 void launch_gin_tile_build(const GinTileBuild& tb, const int* tile_row, const int* tile_graph, uint8_t* tile_desc, int n_tiles, bool hubs,
                            int col_order, hipStream_t s);
-void launch_gin_resident(const float* h0, float* hout, const int* row_ptr, const int* src, const uint8_t* ecode, const float* ecomb_all,
+// Returns 0, or FLOWGNN_ERR_UNSUPPORTED (nothing launched, fg::last_error_text says why) for a `pooling` the arguments leave no instance for.
+int launch_gin_resident(const float* h0, float* hout, const int* row_ptr, const int* src, const uint8_t* ecode, const float* ecomb_all,
                          const uint8_t* chunks_all, const float* pool_w, const float* pool_b, const int* tile_row, const int* tile_graph,
                          uint8_t* tile_desc /* scratch, n_tiles x GIN_RESIDENT_DESC_BYTES */, const int* node_off, float* out, int n_tiles,
                          int* range_flag, hipStream_t s, bool hubs = false, const float* head_u = nullptr, int col_order = 0, bool prof = false,
                          const GinTileBuild* tb = nullptr, int tstride = 1, bool f16 = false /* single-product instances, FLOWGNN_NUMERIC_F16 */,
                          float* emb = nullptr /* [G][100]: the per-graph mean of the h_5 rows, pooled inside the un-folded kernel (out [G] required) */,
-                         float* node_logits = nullptr /* [N]: every node's term of the folded readout, caller order (folded forms only: head_u, out, no hout) */);
+                         float* node_logits = nullptr /* [N]: every node's term of the folded readout, caller order (folded forms only: head_u, out, no hout) */,
+                         int pooling = 0 /* FLOWGNN_POOL_*.  1 (sum): the folded forms' instances whose readout leaves the division out -- the caller
+                                            passes it only with head_u, out and no hout / emb / node_logits.  2 (max): with emb, the pooling instance
+                                            that leaves the per-column maxima of h_5 there and writes no logit -- the caller applies the head to emb */);
 // head_u for launch_gin_resident (GIN_RESIDENT_HEAD_FLOATS floats): the single-task readout folded through the LAST layer's second
 // linear layer -- u = W2^T w_pred divided by the first layer's power-of-two weight scale, padded to 208, then c = b2 . w_pred
 constexpr int GIN_RESIDENT_HEAD_FLOATS = 209;

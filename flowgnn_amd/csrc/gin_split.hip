@@ -56,6 +56,16 @@
 #ifndef GS_NLOGIT_TU
 #define GS_NLOGIT_TU 0
 #endif
+// Pooling modes (flowgnn_set_pooling).  gin_split_poolsum.hip compiles this file once more with GS_POOLSUM_TU = 1, for the folded
+// resident kernel's instances whose readout is the SUM of the graph's terms (gin_resident_poolsum_kernel<HUBS, ENC, F16>: both front
+// ends, both numeric modes); gin_split_poolmax.hip with GS_POOL_TU = 1 and GS_POOL_MAX = 1, for the pooling instances that take the
+// per-column MAXIMUM of the graph's h_5 rows instead of their mean (gin_resident_poolmax_kernel<HUBS, F16>).
+#ifndef GS_POOLSUM_TU
+#define GS_POOLSUM_TU 0
+#endif
+#ifndef GS_POOL_MAX
+#define GS_POOL_MAX 0
+#endif
 
 namespace fg {
 
@@ -1753,7 +1763,7 @@ __device__ __forceinline__ void gr_layer(unsigned long long (&tacc)[6], char* bx
 // requested, all at once as in the prologue: that load is the price of this form (graph embeddings).
 #if GS_POOL_TU
 template <bool HUBS, bool F16>
-#elif GS_NLOGIT_TU
+#elif GS_NLOGIT_TU || GS_POOLSUM_TU
 template <bool HUBS, bool ENC, bool F16>
 #else
 template <bool PROF, bool HUBS, bool FOLD, bool ENC>
@@ -1777,6 +1787,11 @@ __global__ __launch_bounds__(GR_WAVES * 64, 2) void gin_resident_kernel(const fl
                                                                        , float* __restrict__ node_logits) {
     constexpr bool PROF = false, FOLD = true, POOL = false, NLOGIT = true;
     float* const emb = nullptr;
+#elif GS_POOLSUM_TU
+                                                                       ) {
+    constexpr bool PROF = false, FOLD = true, POOL = false, NLOGIT = false;
+    float* const emb = nullptr;
+    float* const node_logits = nullptr;
 #else
                                                                        ) {
     constexpr bool POOL = false, F16 = GS_F16, NLOGIT = false;
@@ -1838,6 +1853,19 @@ __global__ __launch_bounds__(GR_WAVES * 64, 2) void gin_resident_kernel(const fl
                 const int gph = cur.g0 + gl;  // (tiles are ranges of graphs here: bin-packed lists exist in the ENC form only)
                 const int n0 = node_off[gph], n = node_off[gph + 1] - n0;
                 const float* p = s_h + (n0 - cur.t0) * GS_D + col;
+#if GS_POOL_MAX
+                // the maximum (FLOWGNN_POOL_MAX): the chain starts from the graph's FIRST row -- not from 0 (h_5 has no ReLU, pooled maxima
+                // are often negative) and not from anything outside the graph's own rows (the tile's -1.0e30 no-edge row, padding rows):
+                // rows n0 - t0 .. n0 - t0 + n - 1 of the tile are the graph's, n >= 1
+                float mx = p[0];
+                int v = 1;
+                for (; v + 3 < n; v += 4) {  // (four reads in flight)
+                    const float x0 = p[v * GS_D], x1 = p[(v + 1) * GS_D], x2 = p[(v + 2) * GS_D], x3 = p[(v + 3) * GS_D];
+                    mx = __builtin_fmaxf(mx, x0); mx = __builtin_fmaxf(mx, x1); mx = __builtin_fmaxf(mx, x2); mx = __builtin_fmaxf(mx, x3);
+                }
+                for (; v < n; v++) mx = __builtin_fmaxf(mx, p[v * GS_D]);
+                emb[(size_t)gph * GS_D + col] = mx;
+#else
                 float sum = 0.0f;
                 int v = 0;
                 for (; v + 3 < n; v += 4) {  // (four reads in flight; added in node order)
@@ -1846,6 +1874,7 @@ __global__ __launch_bounds__(GR_WAVES * 64, 2) void gin_resident_kernel(const fl
                 }
                 for (; v < n; v++) sum += p[v * GS_D];
                 emb[(size_t)gph * GS_D + col] = sum / (float)n;
+#endif
             }
             if (has_next) {
                 __syncthreads();  // the tile's rows are dead now: the next tile's may land
@@ -1866,7 +1895,12 @@ __global__ __launch_bounds__(GR_WAVES * 64, 2) void gin_resident_kernel(const fl
                     const int gph = list ? list[gi] : gi;
                     const int n0 = node_off[gph], n1 = node_off[gph + 1];
                     const float sum = lds_sum_in_order(s_dot + (list ? lrow[gi] : n0 - cur.t0), n1 - n0);
+#if GS_POOLSUM_TU
+                    // the sum (FLOWGNN_POOL_SUM): no division, and the folded head's constant -- b2 . w, a per-NODE term -- once per node
+                    out[gph] = sum + ((float)(n1 - n0) * head_c + pool_b[0]);
+#else
                     out[gph] = sum / (float)(n1 - n0) + pool_b[0] + head_c;
+#endif
                 }
             }
             if constexpr (NLOGIT) {
@@ -1906,7 +1940,7 @@ __global__ __launch_bounds__(GR_WAVES * 64, 2) void gin_resident_kernel(const fl
 #include "dev/gin_pp_device.inc"  // gin_pp_kernel: the ping-pong form, measured slower -- development builds only
 #endif
 
-#if !GS_POOL_TU && !GS_NLOGIT_TU
+#if !GS_POOL_TU && !GS_NLOGIT_TU && !GS_POOLSUM_TU
 // this translation unit's per-layer kernels (GS_F16: which instance)
 void launch_split_nt(const float* h, float* hout, const int* row_ptr, const int* src, const uint8_t* ecode, const float* ecomb,
                      const uint8_t* chunks, int n_tot, int relu_out, int* range_flag, int nt, hipStream_t s, const float* pool_w) {
@@ -1947,7 +1981,7 @@ void gr_dispatch(bool prof, bool hubs, bool fold, bool enc, int grid, hipStream_
 #undef GR_LAUNCH_FE
 #undef GR_LAUNCH
 }
-#endif  // !GS_POOL_TU && !GS_NLOGIT_TU
+#endif  // !GS_POOL_TU && !GS_NLOGIT_TU && !GS_POOLSUM_TU
 
 #if !GS_SINGLE_PRODUCT
 inline float pow2_scale(const float* w, size_t n) {
@@ -1969,6 +2003,9 @@ inline void put_split(uint8_t* frag, int lane, int e, float v, bool f16 = false)
 }  // namespace
 
 #if GS_POOL_TU
+#if GS_POOL_MAX
+#define gin_resident_pool_dispatch gin_resident_poolmax_dispatch
+#endif
 void gin_resident_pool_dispatch(bool hubs, bool f16, int grid, hipStream_t s, const float* h0, const float* ecomb_all, const uint8_t* chunks_all,
                                 const float* pool_w, const float* pool_b, const int* tile_row, const int* tile_graph, const uint8_t* tile_desc,
                                 const int* node_off, float* out, int n_tiles, int* range_flag, int tstride, float* emb) {
@@ -1979,6 +2016,23 @@ void gin_resident_pool_dispatch(bool hubs, bool f16, int grid, hipStream_t s, co
     if (f16) { if (hubs) GR_LAUNCH_POOL(true, true); else GR_LAUNCH_POOL(false, true); }
     else { if (hubs) GR_LAUNCH_POOL(true, false); else GR_LAUNCH_POOL(false, false); }
 #undef GR_LAUNCH_POOL
+}
+#elif GS_POOLSUM_TU
+void gin_resident_poolsum_dispatch(bool hubs, bool enc, bool f16, int grid, hipStream_t s, const float* h0, const float* ecomb_all,
+                                   const uint8_t* chunks_all, const float* pool_w, const float* pool_b, const int* tile_row, const int* tile_graph,
+                                   const uint8_t* tile_desc, const int* node_off, float* out, int n_tiles, int* range_flag, const float* head_u,
+                                   const uint32_t* eidx, const float4* etab, int tstride, const int* list, const int* lrow) {
+#define GR_LAUNCH_POOLSUM(H, E, F)                                                                                                              \
+    gin_resident_kernel<H, E, F><<<grid, GR_WAVES * 64, 0, s>>>(h0, nullptr, ecomb_all, chunks_all, pool_w, pool_b, tile_row, tile_graph, tile_desc, \
+                                                                node_off, out, n_tiles, range_flag, nullptr, head_u, eidx, etab, tstride, list, lrow)
+#define GR_LAUNCH_POOLSUM_EF(H)                                                                   \
+    do {                                                                                          \
+        if (enc) { if (f16) GR_LAUNCH_POOLSUM(H, true, true); else GR_LAUNCH_POOLSUM(H, true, false); }   \
+        else { if (f16) GR_LAUNCH_POOLSUM(H, false, true); else GR_LAUNCH_POOLSUM(H, false, false); }     \
+    } while (0)
+    if (hubs) GR_LAUNCH_POOLSUM_EF(true); else GR_LAUNCH_POOLSUM_EF(false);
+#undef GR_LAUNCH_POOLSUM_EF
+#undef GR_LAUNCH_POOLSUM
 }
 #elif GS_NLOGIT_TU
 void gin_resident_nlogit_dispatch(bool hubs, bool enc, bool f16, int grid, hipStream_t s, const float* h0, const float* ecomb_all,
@@ -2025,6 +2079,16 @@ void gin_resident_dispatch_f16(bool prof, bool hubs, bool fold, bool enc, int gr
 void gin_resident_pool_dispatch(bool hubs, bool f16, int grid, hipStream_t s, const float* h0, const float* ecomb_all, const uint8_t* chunks_all,
                                 const float* pool_w, const float* pool_b, const int* tile_row, const int* tile_graph, const uint8_t* tile_desc,
                                 const int* node_off, float* out, int n_tiles, int* range_flag, int tstride, float* emb);
+
+// (gin_split_poolmax.hip) the same with the per-column maximum of the h_5 rows in emb (launched with out = null: the head follows from emb)
+void gin_resident_poolmax_dispatch(bool hubs, bool f16, int grid, hipStream_t s, const float* h0, const float* ecomb_all, const uint8_t* chunks_all,
+                                   const float* pool_w, const float* pool_b, const int* tile_row, const int* tile_graph, const uint8_t* tile_desc,
+                                   const int* node_off, float* out, int n_tiles, int* range_flag, int tstride, float* emb);
+// (gin_split_poolsum.hip) the folded instances whose readout is the sum of the graph's terms
+void gin_resident_poolsum_dispatch(bool hubs, bool enc, bool f16, int grid, hipStream_t s, const float* h0, const float* ecomb_all,
+                                   const uint8_t* chunks_all, const float* pool_w, const float* pool_b, const int* tile_row, const int* tile_graph,
+                                   const uint8_t* tile_desc, const int* node_off, float* out, int n_tiles, int* range_flag, const float* head_u,
+                                   const uint32_t* eidx, const float4* etab, int tstride, const int* list, const int* lrow);
 
 // (gin_split_nlogit.hip) the folded instances that also store the per-node readout terms into node_logits [N], caller order
 void gin_resident_nlogit_dispatch(bool hubs, bool enc, bool f16, int grid, hipStream_t s, const float* h0, const float* ecomb_all,
@@ -2188,37 +2252,54 @@ void launch_gin_layer_split(const float* h, float* hout, const int* row_ptr, con
     (f16 ? launch_gin_layer_split_f16 : launch_split_nt)(h, hout, row_ptr, src, ecode, ecomb, chunks, n_tot, relu_out, range_flag, nt, s, pool_w);
 }
 
-void launch_gin_resident(const float* h0, float* hout, const int* row_ptr, const int* src, const uint8_t* ecode, const float* ecomb_all,
+int launch_gin_resident(const float* h0, float* hout, const int* row_ptr, const int* src, const uint8_t* ecode, const float* ecomb_all,
                          const uint8_t* chunks_all, const float* pool_w, const float* pool_b, const int* tile_row, const int* tile_graph,
                          uint8_t* tile_desc, const int* node_off, float* out, int n_tiles, int* range_flag, hipStream_t s, bool hubs,
                          const float* head_u, int col_order, bool prof, const GinTileBuild* tb, int tstride, bool f16, float* emb,
-                         float* node_logits) {
-    if (n_tiles <= 0) return;
+                         float* node_logits, int pooling) {
+    if (n_tiles <= 0) return 0;
     const int order = hubs ? 3 : col_order;
     if (emb != nullptr) { head_u = nullptr; hout = nullptr; prof = false; }  // the pooling instance: un-folded, no tap, no phase stamps
     const bool fold = head_u != nullptr && out != nullptr && hout == nullptr;  // single-task readout, no per-node tap
+    // a mode other than the mean has the instances named below and no other: anything else would be the mean's logits under its name
+    if (pooling != 0 && !(pooling == 1 && fold && node_logits == nullptr && emb == nullptr) && !(pooling == 2 && emb != nullptr)) {
+        set_last_error("launch_gin_resident: pooling 1 (sum) runs the folded instances only (head_u, out, no hout / emb / node_logits), pooling 2 (max) "
+                       "the pooling instance only (emb)");
+        return 8;  // FLOWGNN_ERR_UNSUPPORTED
+    }
     const bool enc = tb != nullptr && fold;  // descriptor + encoder indices straight from the caller's arrays, h_0 computed by the tile loader
     if (!enc) gin_tile_prep_kernel<<<n_tiles, 256, 0, s>>>(row_ptr, src, ecode, tile_row, tile_desc, n_tiles, order, tstride);
     const int grid = n_tiles < 256 ? n_tiles : 256;  // persistent: one 8-wave workgroup per CU (157 KB of LDS)
     unsigned long long* d = nullptr;
     const size_t cnt = (size_t)grid * GR_WAVES * 7;
     if (prof) {  // development aid: phase breakdown from s_memrealtime stamps, printed per launch (synchronises!)
-        if (hipMalloc((void**)&d, cnt * 8) != hipSuccess) return;
+        if (hipMalloc((void**)&d, cnt * 8) != hipSuccess) return 0;
         (void)hipMemsetAsync(d, 0, cnt * 8, s);
     }
     const uint32_t* eidx = enc ? reinterpret_cast<const uint32_t*>(tb->enc_idx) : nullptr;
     const float4* etab = enc ? reinterpret_cast<const float4*>(tb->enc_tab) : nullptr;
+    if (emb != nullptr && pooling == 2) {  // FLOWGNN_POOL_MAX: the per-column maxima go to emb, and the caller applies the head to them (out == null)
+        gin_resident_poolmax_dispatch(hubs, f16, grid, s, h0, ecomb_all, chunks_all, pool_w, pool_b, tile_row, tile_graph, tile_desc, node_off, nullptr,
+                                      n_tiles, range_flag, tstride, emb);
+        return 0;
+    }
+    if (pooling == 1 && fold && node_logits == nullptr) {  // FLOWGNN_POOL_SUM: the folded instance whose readout leaves the division out (no phase stamps)
+        gin_resident_poolsum_dispatch(hubs, enc, f16, grid, s, h0, ecomb_all, chunks_all, pool_w, pool_b, tile_row, tile_graph, tile_desc, node_off,
+                                      out, n_tiles, range_flag, head_u, eidx, etab, tstride, enc ? tb->list : nullptr, enc ? tb->lrow : nullptr);
+        if (d) (void)hipFree(d);
+        return 0;
+    }
     if (emb != nullptr) {
         gin_resident_pool_dispatch(hubs, f16, grid, s, h0, ecomb_all, chunks_all, pool_w, pool_b, tile_row, tile_graph, tile_desc, node_off, out,
                                    n_tiles, range_flag, tstride, emb);
-        return;
+        return 0;
     }
     if (node_logits != nullptr && fold) {  // the folded instance that also stores the per-node terms (no phase stamps)
         gin_resident_nlogit_dispatch(hubs, enc, f16, grid, s, h0, ecomb_all, chunks_all, pool_w, pool_b, tile_row, tile_graph, tile_desc, node_off,
                                      out, n_tiles, range_flag, head_u, eidx, etab, tstride, enc ? tb->list : nullptr, enc ? tb->lrow : nullptr,
                                      node_logits);
         if (d) (void)hipFree(d);
-        return;
+        return 0;
     }
     (f16 ? gin_resident_dispatch_f16 : gr_dispatch)(prof, hubs, fold, enc, grid, s, h0, hout, ecomb_all, chunks_all, pool_w, pool_b, tile_row,
                                                     tile_graph, tile_desc, node_off, out, n_tiles, range_flag, d, head_u, eidx, etab, tstride,
@@ -2257,6 +2338,7 @@ void launch_gin_resident(const float* h0, float* hout, const int* row_ptr, const
             fprintf(stderr, "\n");
         }
     }
+    return 0;
 }
 
 #ifdef FLOWGNN_DEV

@@ -79,7 +79,7 @@ static bool read_eig_txt(const std::string& path, std::vector<float>& eig, size_
 int main(int argc, char** argv) {
     if (argc < 2) {
         fprintf(stderr, "Usage: %s <GIN|GIN-VN|GCN|GAT|PNA|DGN> [--graphs DIR] [--weights DIR] [--num-graphs N] [--trials T] "
-                        "[--out FILE] [--embeddings FILE] [--node-embeddings FILE] [--node-logits FILE] [--attention FILE [--attention-layers MASK]] [--device D | --devices D0,D1,..] [--option key=value] [--numeric f32|q6.10|f16] [--num-tasks T] [XCLBIN File]\n", argv[0]);
+                        "[--out FILE] [--embeddings FILE] [--node-embeddings FILE] [--node-logits FILE] [--attention FILE [--attention-layers MASK]] [--device D | --devices D0,D1,..] [--option key=value] [--numeric f32|q6.10|f16] [--pooling mean|sum|max] [--num-tasks T] [XCLBIN File]\n", argv[0]);
         return EXIT_FAILURE;
     }
     const std::string model = argv[1];
@@ -88,7 +88,7 @@ int main(int argc, char** argv) {
     std::string graphs = "../graphs", wdir = ".", out_path = "HLS_output.txt", eig_dir = "eig", emb_path, nemb_path, nlog_path, attn_path;
     long num_graphs = -1;
     int attn_mask = 16;
-    int trials = 25, numeric = FLOWGNN_NUMERIC_F32, num_tasks = 1;
+    int trials = 25, numeric = FLOWGNN_NUMERIC_F32, num_tasks = 1, pooling = FLOWGNN_POOL_MEAN;
     std::vector<int> devices;
     std::vector<std::pair<std::string, double>> options;
     for (int i = 2; i < argc; i++) {
@@ -128,6 +128,11 @@ int main(int argc, char** argv) {
             const std::string m = next("--numeric");
             numeric = m == "q6.10" ? FLOWGNN_NUMERIC_Q6_10 : m == "f16" ? FLOWGNN_NUMERIC_F16 : FLOWGNN_NUMERIC_F32;
         }
+        else if (a == "--pooling") {  // the readout's pooling (flowgnn_set_pooling; GIN / GIN-VN / GCN / GAT)
+            const std::string m = next("--pooling");
+            if (m != "mean" && m != "sum" && m != "max") { fprintf(stderr, "--pooling wants mean, sum or max\n"); return EXIT_FAILURE; }
+            pooling = m == "sum" ? FLOWGNN_POOL_SUM : m == "max" ? FLOWGNN_POOL_MAX : FLOWGNN_POOL_MEAN;
+        }
         // anything else (e.g. an .xclbin path) is ignored
     }
     if (num_graphs < 0) num_graphs = read_count_file(graphs + "/dataset_size.txt");
@@ -152,6 +157,10 @@ int main(int argc, char** argv) {
     if (numeric != FLOWGNN_NUMERIC_F32) {  // the reference's ap_fixed<16,6> bit patterns, or f16 MLP operands (GIN / GIN-VN)
         rc = flowgnn_group_set_numeric_mode(eng, numeric);
         if (rc) { fprintf(stderr, "numeric mode: %d %s\n", rc, flowgnn_group_last_error(eng)); return EXIT_FAILURE; }
+    }
+    if (pooling != FLOWGNN_POOL_MEAN) {
+        rc = flowgnn_group_set_pooling(eng, pooling);
+        if (rc) { fprintf(stderr, "--pooling: %d %s\n", rc, flowgnn_group_last_error(eng)); return EXIT_FAILURE; }
     }
     printf("\n******* Weights loading done *******\n");
 

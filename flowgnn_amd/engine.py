@@ -17,6 +17,8 @@ from .graphpack import GraphBatch
 
 # flowgnn_set_numeric_mode codes (flowgnn.h: FLOWGNN_NUMERIC_F32 / _Q6_10 / _F16)
 NUMERIC_MODES = {"f32": 0, "q6.10": 1, "f16": 2}
+# flowgnn_set_pooling codes (flowgnn.h: FLOWGNN_POOL_MEAN / _SUM / _MAX)
+POOLING_MODES = {"mean": 0, "sum": 1, "max": 2}
 
 
 class FlowGNNError(RuntimeError):
@@ -476,6 +478,15 @@ class Engine:
         code = NUMERIC_MODES[mode]
         self._check(self.lib.flowgnn_set_numeric_mode(self._h, code), "flowgnn_set_numeric_mode")
 
+    def set_pooling(self, mode: str = "mean"):
+        """The readout's pooling: "mean" (default, the reference's), "sum" or "max" (flowgnn.h: flowgnn_set_pooling; GIN, GIN-VN, GCN,
+        GAT).  The engine's, across batches; `embeddings()` then returns the sum / the maximum, the vector the head is applied to."""
+        self._check(self.lib.flowgnn_set_pooling(self._h, POOLING_MODES[mode]), "flowgnn_set_pooling")
+
+    def pooling(self) -> str:
+        code = int(self.lib.flowgnn_pooling(self._h))
+        return next(k for k, v in POOLING_MODES.items() if v == code)
+
     def exact_reruns(self) -> int:
         """Forward passes repeated on the exact-fp32 kernels (flowgnn.h: flowgnn_exact_reruns)."""
         return int(self.lib.flowgnn_exact_reruns(self._h))
@@ -585,6 +596,10 @@ class EngineGroup:
 
     def set_numeric_mode(self, mode: str = "f32"):
         self._check(self.lib.flowgnn_group_set_numeric_mode(self._h, NUMERIC_MODES[mode]), "flowgnn_group_set_numeric_mode")
+
+    def set_pooling(self, mode: str = "mean"):
+        """Engine.set_pooling on every member (flowgnn.h: flowgnn_group_set_pooling)."""
+        self._check(self.lib.flowgnn_group_set_pooling(self._h, POOLING_MODES[mode]), "flowgnn_group_set_pooling")
 
     def set_batch(self, batch: GraphBatch):
         nn, ne = _i32(batch.nums_of_nodes), _i32(batch.nums_of_edges)
@@ -700,6 +715,13 @@ def entry_set_option(model: str, key: str, value):
     rc = _lib.load().flowgnn_entry_set_option(_lib.MODEL_IDS[model.upper()], key.encode(), option_value(value))
     if rc:
         raise FlowGNNError(rc, f"flowgnn_entry_set_option({key})")
+
+
+def entry_set_pooling(model: str, mode: str = "mean"):
+    """The readout's pooling for the engines behind `model`'s <M>_compute_graphs symbols (flowgnn.h: flowgnn_entry_set_pooling)."""
+    rc = _lib.load().flowgnn_entry_set_pooling(_lib.MODEL_IDS[model.upper()], POOLING_MODES[mode])
+    if rc:
+        raise FlowGNNError(rc, f"flowgnn_entry_set_pooling({mode})")
 
 
 def compute_graphs(model: str, batch: GraphBatch, weight_sets, reload_weights=None, num_tasks: int = 1) -> np.ndarray:

@@ -182,6 +182,7 @@ int GAT_compute_graphs(int num_graphs, int* nums_of_nodes, int* nums_of_edges,
 int flowgnn_entry_set_devices(int n_devices, const int* device_ids);
 int flowgnn_entry_set_pipeline(int chunks_per_engine);
 int flowgnn_entry_set_option(int model, const char* key, double value);
+int flowgnn_entry_set_pooling(int model, int mode);       /* flowgnn_set_pooling (section 2) for the entry points of `model` */
 
 /* =====================================================================
  * (2) Handle API
@@ -539,6 +540,35 @@ int flowgnn_num_tasks(const flowgnn_engine* e);
 int flowgnn_set_numeric_mode(flowgnn_engine* e, int mode);
 
 /*
+ * Pooling of the readout (GIN, GIN-VN, GCN, GAT): how a graph's last node rows r[v] (what
+ * flowgnn_set_node_embeddings returns) become the vector the linear head is applied to.  v runs over every node of the graph --
+ * GIN-VN's virtual node is a node, as it is for the mean.
+ *   FLOWGNN_POOL_MEAN (default, the reference's finalize):  logit[g][t] = b[t] + W[t] . (sum_v r[v]) / n_g
+ *   FLOWGNN_POOL_SUM  (the GIN paper's readout; OGB's graph_pooling = "sum"):  logit[g][t] = b[t] + W[t] . sum_v r[v]
+ *   FLOWGNN_POOL_MAX  (graph_pooling = "max"):  logit[g][t] = b[t] + W[t] . m,  m[d] = max_v r[v][d]
+ * The setting belongs to the engine, like the numeric mode: it may be changed between runs on a resident batch, it holds across
+ * batches, and it drops a recorded launch sequence (option hipgraph).  In the default mode every launch is the one it always was.
+ * Sum keeps the graph-resident kernels (instances whose readout leaves the division out) and the folded per-layer last stage; the
+ * maximum is taken on chip for GIN and GIN-VN (the un-folded pooling instance) and from the rows of the per-layer path for GCN and
+ * GAT, whose last stage is then un-folded (W . max is not a maximum of per-node scores).  A graph's sum has one order per path, as
+ * the mean's has; no float atomics anywhere.  flowgnn_set_embeddings returns the vector the head is applied to, i.e. the sum or
+ * the maximum under those modes; node embeddings and GAT's attention coefficients do not depend on the mode.  A NaN in a row does
+ * not survive the maximum (v_max_f32 returns the other operand).
+ * flowgnn_set_pooling: FLOWGNN_ERR_ARG for a mode outside 0..2.  FLOWGNN_ERR_UNSUPPORTED (flowgnn_last_error says why) for a mode
+ *     other than the mean on PNA and DGN (their MLP heads were trained on the mean), in FLOWGNN_NUMERIC_Q6_10 (the fixed-point
+ *     readout is the reference's), and while node logits are on (their contract is "the mean of the terms is the logit");
+ *     flowgnn_set_numeric_mode and flowgnn_set_node_logits answer the same while a mode other than the mean is set.
+ * flowgnn_pooling: the mode, -1 for a null handle.
+ * flowgnn_group_set_pooling: flowgnn_set_pooling on every member.  flowgnn_entry_set_pooling: for the engines behind the
+ *     <M>_compute_graphs entry points of `model`, as flowgnn_entry_set_option (remembered for engines created later).
+ */
+#define FLOWGNN_POOL_MEAN 0   /* default: the reference's */
+#define FLOWGNN_POOL_SUM  1
+#define FLOWGNN_POOL_MAX  2
+int flowgnn_set_pooling(flowgnn_engine* e, int mode);
+int flowgnn_pooling(const flowgnn_engine* e);            /* -1 for a null handle */
+
+/*
  * Run-time switches, by name (the full list with defaults: the option table in flowgnn_amd/csrc/engine.hip, or
  * flowgnn_option_count / flowgnn_option_name).  They select between kernels that compute the SAME results -- e.g.
  * "gin_resident" 0 = one launch per layer, "gin_mfma" 32 = fp32 matrix pipe instead of three f16 products, "pna_fused" 0 =
@@ -587,6 +617,7 @@ int flowgnn_group_load_weights_dir(flowgnn_group* g, const char* dir);
 int flowgnn_group_set_option(flowgnn_group* g, const char* key, double value);
 int flowgnn_group_set_num_tasks(flowgnn_group* g, int num_tasks);
 int flowgnn_group_set_numeric_mode(flowgnn_group* g, int mode);
+int flowgnn_group_set_pooling(flowgnn_group* g, int mode);
 int flowgnn_group_set_batch(flowgnn_group* g, int num_graphs,
                             const int* nums_of_nodes, const int* nums_of_edges,
                             const int* node_feature, const int* edge_list, const int* edge_attr,
