@@ -171,6 +171,8 @@ struct DeviceBatch {
     int num_tasks;            // NUM_TASK of the readout (1 unless flowgnn_set_num_tasks said otherwise)
     int pooling;              // FLOWGNN_POOL_* (flowgnn_set_pooling; GIN, GIN-VN, GCN, GAT): 0 = mean, every launch is the one it always was; 1 = sum,
                               // 2 = max.  Decides what out and emb hold; node_emb and the attention buffers do not depend on it
+    bool gin_eps_on;          // flowgnn_set_gin_eps (GIN, GIN-VN): false = off, every launch is the one it always was.  A state, not a value: on
+    float gin_self_scale[5];  // with five zeros runs the eps instances too.  s_l = (float)(1.0f + eps[l]) of layer l: a[v] = s_l h_l[v] + m_l[v]
     int final_h;              // which h[] holds the last stage's output (set by forward)
     const float* tap;         // optional debug tap returned by flowgnn_get_h instead of h[final_h]
     int tap_dim;

@@ -12,6 +12,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <cctype>
+#include <cmath>
 #include <thread>
 
 namespace fg {
@@ -708,6 +709,8 @@ static int set_batch_state(flowgnn_engine* e, int num_graphs, const int* nums_of
     db.h[0] = e->d_h0; db.h[1] = e->d_h1; db.scratch = e->d_scratch; db.out = e->d_out;
     db.num_tasks = e->num_tasks;
     db.pooling = e->pooling;
+    db.gin_eps_on = e->gin_eps_on;
+    for (int l = 0; l < 5; l++) db.gin_self_scale[l] = (float)(1.0f + e->gin_eps[l]);
     db.final_h = 0;
     db.tap = nullptr;
     db.tap_dim = 0;
@@ -1291,6 +1294,10 @@ int flowgnn_set_numeric_mode(flowgnn_engine* e, int mode) {
         e->err = "flowgnn_set_numeric_mode: the pooling is not the mean (flowgnn_set_pooling), and the fixed-point readout is the reference's mean";
         return FLOWGNN_ERR_UNSUPPORTED;
     }
+    if (mode == FLOWGNN_NUMERIC_Q6_10 && e->gin_eps_on) {
+        e->err = "flowgnn_set_numeric_mode: a trained eps is on (flowgnn_set_gin_eps), and the fixed-point arithmetic is the reference's, which has no eps";
+        return FLOWGNN_ERR_UNSUPPORTED;
+    }
     e->drop_graph();
     const int rc = e->model->set_numeric_mode(mode);
     if (!rc) e->numeric_mode = mode;
@@ -1325,6 +1332,41 @@ int flowgnn_set_pooling(flowgnn_engine* e, int mode) {
 }
 
 int flowgnn_pooling(const flowgnn_engine* e) { return e ? e->pooling : -1; }
+
+int flowgnn_set_gin_eps(flowgnn_engine* e, const float* eps) {
+    if (!e) return FLOWGNN_ERR_ARG;
+    if (e->model_id != FLOWGNN_MODEL_GIN && e->model_id != FLOWGNN_MODEL_GIN_VN) {
+        e->err = "flowgnn_set_gin_eps: only GIN and GIN-VN have the (1 + eps) self term";
+        return FLOWGNN_ERR_UNSUPPORTED;
+    }
+    if (eps) {
+        for (int l = 0; l < 5; l++)
+            if (!std::isfinite(eps[l])) {
+                e->err = "flowgnn_set_gin_eps: eps[" + std::to_string(l) + "] is not finite";
+                return FLOWGNN_ERR_ARG;
+            }
+        if (e->numeric_mode == FLOWGNN_NUMERIC_Q6_10) {
+            e->err = "flowgnn_set_gin_eps: the fixed-point arithmetic (FLOWGNN_NUMERIC_Q6_10) is the reference's, which has no eps";
+            return FLOWGNN_ERR_UNSUPPORTED;
+        }
+    }
+    ENGINE_TRY(e, use_device(e));
+    e->drop_graph();  // a recorded launch sequence is that of the other state (or carries the other values in its argument blocks)
+    e->gin_eps_on = eps != nullptr;
+    e->db.gin_eps_on = e->gin_eps_on;  // (launches are stream-ordered: the values matter to those enqueued after this call)
+    for (int l = 0; l < 5; l++) {
+        e->gin_eps[l] = eps ? eps[l] : 0.0f;
+        e->db.gin_self_scale[l] = (float)(1.0f + e->gin_eps[l]);
+    }
+    return FLOWGNN_OK;
+}
+
+int flowgnn_gin_eps(const flowgnn_engine* e, float* eps_out) {
+    if (!e) return -1;
+    if (eps_out)
+        for (int l = 0; l < 5; l++) eps_out[l] = e->gin_eps[l];
+    return e->gin_eps_on ? 1 : 0;
+}
 
 int flowgnn_set_option(flowgnn_engine* e, const char* key, double value) {
     if (!e || !key) return FLOWGNN_ERR_ARG;
@@ -1435,6 +1477,7 @@ int flowgnn_profile_read(flowgnn_engine* e, int* count, const char** names, doub
 int flowgnn_run_aggregation_only(flowgnn_engine* e, int layer, int iters, float* avg_ms) {
     if (!e || iters <= 0) return FLOWGNN_ERR_ARG;
     if (!e->ran) { e->err = "flowgnn_run_aggregation_only needs a prior flowgnn_run"; return FLOWGNN_ERR_STATE; }
+    if (e->gin_eps_on) { e->err = "flowgnn_run_aggregation_only: a trained eps is on (flowgnn_set_gin_eps), and the stand-alone aggregation kernel has no eps instance"; return FLOWGNN_ERR_UNSUPPORTED; }
     ENGINE_TRY(e, use_device(e));
     e->drop_graph();
     int rc = e->model->aggregate_dim() > 0 ? ensure_rows(e) : FLOWGNN_OK;  // the kernel's input rows (a resident run left none)
@@ -1465,6 +1508,7 @@ int flowgnn_run_aggregation_only(flowgnn_engine* e, int layer, int iters, float*
 int flowgnn_get_aggregate(flowgnn_engine* e, int layer, float* h_in_host, int* in_dim, float* agg_host, int* agg_dim) {
     if (!e) return FLOWGNN_ERR_ARG;
     if (!e->ran) { e->err = "flowgnn_get_aggregate needs a prior flowgnn_run"; return FLOWGNN_ERR_STATE; }
+    if (e->gin_eps_on) { e->err = "flowgnn_get_aggregate: a trained eps is on (flowgnn_set_gin_eps), and the stand-alone aggregation kernel has no eps instance"; return FLOWGNN_ERR_UNSUPPORTED; }
     int rc = flowgnn_sync(e);
     if (rc) return rc;
     e->drop_graph();

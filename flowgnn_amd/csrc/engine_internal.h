@@ -77,6 +77,8 @@ struct flowgnn_engine {
     bool emb_on = false;
     int numeric_mode = FLOWGNN_NUMERIC_F32;
     int pooling = FLOWGNN_POOL_MEAN;  // flowgnn_set_pooling: the engine's, across batches (db.pooling follows it)
+    bool gin_eps_on = false;          // flowgnn_set_gin_eps: the engine's too, across batches and weight sets (db.gin_eps_on / gin_self_scale follow)
+    float gin_eps[5] = {0, 0, 0, 0, 0};
     fg::GrowBuf emb;                // the engine's own [G][dim] buffer (allocated when first needed, outlives the batch)
     float* emb_user = nullptr;      // flowgnn_set_embeddings_buffer (reset by set_batch)
     float* emb_last = nullptr;      // where the last flowgnn_run put them (null: it ran with embeddings off)

@@ -1,6 +1,7 @@
 // entry.hip -- the reference-compatible entry points: <M>_compute_graphs, their _mt forms and flowgnn_entry_*.
 #include "engine_internal.h"
 #include <atomic>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <limits>
@@ -17,6 +18,8 @@ static std::vector<int> g_entry_devices;  // empty: not decided yet (the environ
 static int g_entry_pipeline = 0;          // flowgnn_entry_set_pipeline: ranges per engine (0: by the size of the host arrays, 1: off)
 static std::vector<std::pair<std::string, double>> g_entry_options[6];
 static int g_entry_pooling[6] = {0, 0, 0, 0, 0, 0};  // flowgnn_entry_set_pooling (FLOWGNN_POOL_MEAN)
+static bool g_entry_eps_on[6] = {false, false, false, false, false, false};  // flowgnn_entry_set_gin_eps: one vector for every weight set
+static float g_entry_eps[6][5] = {};
 // The weight set an entry-point group holds, kept on the host: a caller that reloads the SAME set on every graph
 // (reload_weights = 1 everywhere is legal in the reference and cheap there) must not pay a repack + upload per graph.
 // Compared with memcmp -- no hash, no collision to reason about.
@@ -93,6 +96,28 @@ int flowgnn_entry_set_pooling(int model, int mode) {
     return FLOWGNN_OK;
 }
 
+int flowgnn_entry_set_gin_eps(int model, const float* eps) {
+    if (model < 0 || model >= 6) return FLOWGNN_ERR_ARG;
+    if (model != FLOWGNN_MODEL_GIN && model != FLOWGNN_MODEL_GIN_VN) {
+        fg::set_last_error("flowgnn_entry_set_gin_eps: only GIN and GIN-VN have the (1 + eps) self term");
+        return FLOWGNN_ERR_UNSUPPORTED;
+    }
+    if (eps)
+        for (int l = 0; l < 5; l++)
+            if (!std::isfinite(eps[l])) {
+                fg::set_last_error("flowgnn_entry_set_gin_eps: a value is not finite");
+                return FLOWGNN_ERR_ARG;
+            }
+    std::lock_guard<std::mutex> lock(g_entry_mutex);
+    if (g_entry_group[model]) {  // (remembered only once the engines have accepted it)
+        const int rc = flowgnn_group_set_gin_eps(g_entry_group[model], eps);
+        if (rc) return rc;
+    }
+    g_entry_eps_on[model] = eps != nullptr;
+    for (int l = 0; l < 5; l++) g_entry_eps[model][l] = eps ? eps[l] : 0.0f;
+    return FLOWGNN_OK;
+}
+
 static int compute_graphs_generic(int model, int num_graphs, const int* nums_of_nodes, const int* nums_of_edges,
                                   const int* reload_weights, float* out, const int* node_feature, const float* node_eigen,
                                   const int* edge_list, const int* edge_attr, int ntens, const float* const* tens,
@@ -120,6 +145,10 @@ static int compute_graphs_generic(int model, int num_graphs, const int* nums_of_
         }
         if (g_entry_pooling[model] != FLOWGNN_POOL_MEAN) {
             rc = flowgnn_group_set_pooling(grp, g_entry_pooling[model]);
+            if (rc) return rc;
+        }
+        if (g_entry_eps_on[model]) {
+            rc = flowgnn_group_set_gin_eps(grp, g_entry_eps[model]);
             if (rc) return rc;
         }
         g_entry_wcopy[model].clear();

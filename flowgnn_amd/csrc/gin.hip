@@ -4,6 +4,7 @@
 //   h0[v]   = sum_{k<9} NodeEmb[off_k + feat_k(v)]                          load_inputs.cc:193-212
 //   m_l[v]  = sum_{(u->v)} relu(h_l[u] + sum_{k<3} EdgeEmb_l[off_k+attr_k])  message_passing.cc:136-145
 //   a       = m_l[v] + (1 + eps) h_l[v],  eps == 0 (never loaded)            node_embedding.cc:117
+//             (flowgnn_set_gin_eps: a = m_l[v] + s_l h_l[v], s_l = 1 + eps[l] -- the eps instances)
 //   hid     = b1 + W1 a  (200x100),  h_{l+1} = b2 + W2 relu(hid) (100x200)   node_embedding.cc:124-191
 //   out[g]  = pb + pw . mean_v h_5[v]                                        finalize.cc:36-113
 //
@@ -350,6 +351,8 @@ __device__ inline void gin_issue_chunk(const float* __restrict__ gchunk, char* l
     }
 }
 
+__device__ __forceinline__ float gin_self_scale(float s) { return s; }  // the one element of a kernel's SELF_S pack
+
 #define GIN_MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 
 // One pipeline step c of the node MLP: reads chunk c from `wb`, has already issued chunk c+1 into the
@@ -398,14 +401,16 @@ __device__ inline void gin_mlp_step(const float* wb, int c, int lane, int g, con
     }
 }
 
-template <int NT>
+// SELF_S: empty (the default: a = h[v] + m, today's arguments) or one float, the layer's s_l = 1 + eps[l] (flowgnn_set_gin_eps)
+template <int NT, class... SELF_S>
 __global__ __launch_bounds__(256) void gin_layer_fused_kernel(const float* __restrict__ h, float* __restrict__ hout,
                                                                const int* __restrict__ row_ptr,
                                                                const int* __restrict__ src,
                                                                const uint8_t* __restrict__ ecode,
                                                                const float* __restrict__ ecomb,
                                                                const float* __restrict__ wchunks, int n_tot,
-                                                               int relu_out) {
+                                                               int relu_out, SELF_S... self_s) {
+    static_assert(sizeof...(SELF_S) <= 1, "at most the layer's s_l");
     // Two DISTINCT LDS objects on purpose: the compiler can then prove that the LDS-DMA into one buffer
     // does not alias the ds_reads of the other and keeps the DMA in flight under the MFMAs (with one
     // object and a runtime-selected half it inserts s_waitcnt vmcnt(0) before the first ds_read).
@@ -476,14 +481,25 @@ __global__ __launch_bounds__(256) void gin_layer_fused_kernel(const float* __res
         }
     }
 #pragma unroll
-    for (int nt = 0; nt < NT; nt++) {  // + (1 + eps) h[v], eps == 0
+    for (int nt = 0; nt < NT; nt++) {  // + (1 + eps) h[v], eps == 0 unless SELF_S carries s_l (then: a = fma(h[v], s_l, m), one fp32 rounding)
         const float* hr = h + (size_t)self_row[nt] * GIN_D + 4 * g;
+        if constexpr (sizeof...(SELF_S) > 0) {
+            const float sl = gin_self_scale(self_s...);
+#pragma unroll
+            for (int q = 0; q < 6; q++) {
+                const float4 x = *reinterpret_cast<const float4*>(hr + 16 * q);
+                bq[nt][4 * q + 0] = __builtin_fmaf(x.x, sl, bq[nt][4 * q + 0]); bq[nt][4 * q + 1] = __builtin_fmaf(x.y, sl, bq[nt][4 * q + 1]);
+                bq[nt][4 * q + 2] = __builtin_fmaf(x.z, sl, bq[nt][4 * q + 2]); bq[nt][4 * q + 3] = __builtin_fmaf(x.w, sl, bq[nt][4 * q + 3]);
+            }
+            bq[nt][24] = __builtin_fmaf(h[(size_t)self_row[nt] * GIN_D + 96 + g], sl, bq[nt][24]);
+        } else {
 #pragma unroll
         for (int q = 0; q < 6; q++) {
             const float4 x = *reinterpret_cast<const float4*>(hr + 16 * q);
             bq[nt][4 * q + 0] += x.x; bq[nt][4 * q + 1] += x.y; bq[nt][4 * q + 2] += x.z; bq[nt][4 * q + 3] += x.w;
         }
         bq[nt][24] += h[(size_t)self_row[nt] * GIN_D + 96 + g];
+        }
     }
     __syncthreads();  // every wave is done with the edge-embedding combos: s_a may be overwritten
 
@@ -770,14 +786,20 @@ public:
     // the batch's half-tiles on gin_pp_kernel, the few graphs beyond the half-tile limits on gin_resident_kernel.  (Decided from the
     // SHARD's own half-tile fill: unlike the shipped kernels' choices this one does not follow the job -- development only.)
     bool use_pingpong(const DeviceBatch& db) const {
-        return pingpong_ && !f16_ && !virtual_node_ && use_resident(db) && !keep_h_ && !db.node_logits && db.pooling == POOL_OP_MEAN && num_tasks_ == 1 && fold_readout_ && head_fold_ && db.gtiles.sub_ok &&
+        return pingpong_ && !db.gin_eps_on && !f16_ && !virtual_node_ && use_resident(db) && !keep_h_ && !db.node_logits && db.pooling == POOL_OP_MEAN && num_tasks_ == 1 && fold_readout_ && head_fold_ && db.gtiles.sub_ok &&
                db.gtiles.n_sub > 0 && db.gtiles.sub_fill >= resident_min_fill_;
     }
 #endif
     bool use_resident(const DeviceBatch& db) const {
         // tiles that are mostly empty (graphs of 130..256 nodes, or dense graphs that hit the edge limit first) waste the
         // MFMA columns of the absent rows: below half full the per-layer kernels are the better choice
-        return resident_ && table_ok_ && fused_ && split_ && !exact_ && db.gtiles.ok && db.gtiles.n_tiles > 0 && db.gtiles.fill >= resident_min_fill_;
+        return resident_ && table_ok_ && fused_ && split_ && !exact_ && db.gtiles.ok && db.gtiles.n_tiles > 0 && db.gtiles.fill >= resident_min_fill_ &&
+               (!db.gin_eps_on || eps_resident(db));
+    }
+    // A trained eps (flowgnn_set_gin_eps) has ONE resident instance set, gin_resident_eps_kernel: single task, mean pooling, folded head,
+    // no extra outputs and no taps.  Every other configuration takes the per-layer kernels' eps instances -- never an eps-less kernel.
+    bool eps_resident(const DeviceBatch& db) const {
+        return !keep_h_ && num_tasks_ == 1 && fold_readout_ && head_fold_ && !db.emb && !db.node_emb && !db.node_logits && db.pooling == POOL_OP_MEAN;
     }
 
     // One-pass form of the graph-resident path (default): gin_tile_build_kernel turns the caller's edge list / attributes / node
@@ -809,6 +831,11 @@ public:
         const int n = db.b.n_tot;
         if (n <= 0) return 0;
         if (qmode_) return ginq_forward(qw_, db, prof, s);
+        if (db.gin_eps_on && !fused_) {  // (the engine refuses eps in the fixed-point mode itself)
+            set_last_error("flowgnn_run: gin_unfused 1 (the aggregate + mlp kernels) has no eps instance (flowgnn_set_gin_eps); set gin_unfused 0");
+            return 8;  // FLOWGNN_ERR_UNSUPPORTED
+        }
+        const float* const eps_s = db.gin_eps_on ? db.gin_self_scale : nullptr;  // s_l = 1 + eps[l], or null: every launch as it always was
         if (one_pass(db)) {
             // bin-packed tile lists when flowgnn_set_batch made them (option gin_binpack): fewer, fuller tiles of the same graphs -- everything
             // the resident kernel reads is written by the tile build in tile order, and a row's sums depend on the row alone: the same bits
@@ -826,7 +853,7 @@ public:
             ProfScope p(prof, "gin_resident", s);  // the whole model
             if (int rc = launch_gin_resident(nullptr, nullptr, nullptr, nullptr, nullptr, d_ecomb_res_, rsplit(), d_pw_, d_pb_, t_row, t_graph,
                                 reinterpret_cast<uint8_t*>(perm_.p), db.b.node_off, db.out, n_tiles,
-                                db.range_flag, s, virtual_node_, head(), resident_order_, resident_prof_, &tb, 1, f16_, nullptr, db.node_logits, db.pooling))
+                                db.range_flag, s, virtual_node_, head(), resident_order_, resident_prof_, &tb, 1, f16_, nullptr, db.node_logits, db.pooling, eps_s))
                 return rc;
             db.final_h = 0;
             db.h_valid = false;
@@ -886,7 +913,7 @@ public:
                                     db.gtiles.row_start, db.gtiles.graph_start, reinterpret_cast<uint8_t*>(perm_.p), db.b.node_off,
                                     (multi || (rows && !mean_pool(db))) ? nullptr : db.out, db.gtiles.n_tiles, db.range_flag, s, virtual_node_,
                                     (!rows && fold_readout_ && head_fold_) ? head() : nullptr, resident_order_, resident_prof_, nullptr, 1, f16_, pool_emb,
-                                    db.node_logits, rows ? 0 : db.pooling))
+                                    db.node_logits, rows ? 0 : db.pooling, eps_s))
                     return rc;
             }
             db.final_h = rows ? 1 : 0;
@@ -914,7 +941,7 @@ public:
                 const bool fold = l == GIN_L - 1 && fold_readout_ && !keep_h_ && !multi && !db.emb && !db.node_emb && db.pooling != POOL_OP_MAX;
                 launch_gin_layer_split(db.h[cur], fold ? db.scratch : hn, db.csr.row_ptr, db.csr.src, db.csr.ecode,
                                        layer_dev(l).ecomb, (f16_ ? d_split16_ : d_split_) + (size_t)l * GS_LAYER_BYTES, n, db.b.e_tot,
-                                       l != GIN_L - 1, db.range_flag, split_nt_, s, fold ? d_pw_ : nullptr, f16_);
+                                       l != GIN_L - 1, db.range_flag, split_nt_, s, fold ? d_pw_ : nullptr, f16_, eps_s ? eps_s + l : nullptr);
                 if (fold) {
                     folded = true;
                     break;
@@ -926,6 +953,11 @@ public:
                 ProfScope p(prof, "gin_layer_fused", s);
                 constexpr int NT = 1;
                 const int blocks = (int)ceil_div_ll(n, 64 * NT);
+                if (eps_s)
+                    gin_layer_fused_kernel<NT, float><<<blocks, 256, 0, s>>>(
+                        db.h[cur], hn, db.csr.row_ptr, db.csr.src, db.csr.ecode, layer_dev(l).ecomb,
+                        d_chunks_ + (size_t)l * GIN_CHUNKS * GIN_CHUNK_FLOATS, n, l != GIN_L - 1, eps_s[l]);
+                else
                 gin_layer_fused_kernel<NT><<<blocks, 256, 0, s>>>(
                     db.h[cur], hn, db.csr.row_ptr, db.csr.src, db.csr.ecode, layer_dev(l).ecomb,
                     d_chunks_ + (size_t)l * GIN_CHUNKS * GIN_CHUNK_FLOATS, n, l != GIN_L - 1);

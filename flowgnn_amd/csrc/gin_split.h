@@ -32,7 +32,8 @@ void gin_split_pack_layer(const float* w1, const float* b1, const float* w2, con
 // f16 = true: the single-product instance (FLOWGNN_NUMERIC_F16; chunks packed with f16 = true)
 void launch_gin_layer_split(const float* h, float* hout, const int* row_ptr, const int* src, const uint8_t* ecode,
                             const float* ecomb, const uint8_t* chunks, int n_tot, int e_tot, int relu_out, int* range_flag,
-                            int variant, hipStream_t s, const float* pool_w = nullptr, bool f16 = false);
+                            int variant, hipStream_t s, const float* pool_w = nullptr, bool f16 = false,
+                            const float* self_s = nullptr /* flowgnn_set_gin_eps: the layer's s_l = 1 + eps[l] (host); the eps instance */);
 
 // Graph-resident form (gin_split.hip, gin_resident_kernel): all five layers + readout in one launch; a persistent workgroup
 // keeps a tile of whole graphs (GraphTiles: <= GIN_RESIDENT_ROWS rows, <= GIN_RESIDENT_EDGES in-edges) in LDS across the layers.
@@ -61,6 +62,9 @@ void launch_gin_pp(const float* h0, const int* row_ptr, const int* src, const ui
                    int* range_flag, const float* head_u, hipStream_t s, bool prof = false, int waves = 8);
 #endif
 
+// s_l = 1 + eps[l] of the five layers, by value in a resident eps kernel's argument block (flowgnn_set_gin_eps)
+struct GinSelfScale { float s[5]; };
+
 // what the one-pass tile loader needs (launch_gin_resident, tb != null): the caller's arrays, the per-node table-row numbers it writes
 // (8 B per node) and the pre-combined encoder table (gin_resident_pack_enc_table); err = the engine's validation flag
 struct GinTileBuild {
@@ -88,7 +92,9 @@ int launch_gin_resident(const float* h0, float* hout, const int* row_ptr, const 
                          float* node_logits = nullptr /* [N]: every node's term of the folded readout, caller order (folded forms only: head_u, out, no hout) */,
                          int pooling = 0 /* FLOWGNN_POOL_*.  1 (sum): the folded forms' instances whose readout leaves the division out -- the caller
                                             passes it only with head_u, out and no hout / emb / node_logits.  2 (max): with emb, the pooling instance
-                                            that leaves the per-column maxima of h_5 there and writes no logit -- the caller applies the head to emb */);
+                                            that leaves the per-column maxima of h_5 there and writes no logit -- the caller applies the head to emb */,
+                         const float* self_scale = nullptr /* flowgnn_set_gin_eps: s_l = 1 + eps[l] of the five layers (host).  The eps instances
+                                            (gin_resident_eps_kernel): folded forms only, pooling 0, no hout / emb / node_logits */);
 // head_u for launch_gin_resident (GIN_RESIDENT_HEAD_FLOATS floats): the single-task readout folded through the LAST layer's second
 // linear layer -- u = W2^T w_pred divided by the first layer's power-of-two weight scale, padded to 208, then c = b2 . w_pred
 constexpr int GIN_RESIDENT_HEAD_FLOATS = 209;

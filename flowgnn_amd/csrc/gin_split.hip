@@ -66,6 +66,20 @@
 #ifndef GS_POOL_MAX
 #define GS_POOL_MAX 0
 #endif
+// Trained eps (flowgnn_set_gin_eps): a = s_l h[v] + m[v] with s_l = 1 + eps[l], formed on the host.  GS_EPS = 1 gives the resident kernel
+// of a translation unit the five s_l as one more by-value argument and the multiply in gr_layer's self term; it is orthogonal to
+// GS_POOL_TU / GS_NLOGIT_TU / GS_POOLSUM_TU.  gin_split_eps.hip compiles this file once more with GS_EPS_TU = 1, which selects the folded,
+// single-task, mean-pooling set (gin_resident_eps_kernel<HUBS, ENC, F16>: both front ends, both numeric modes) and sets GS_EPS; an
+// eps x sum or eps x node-logits instance would be one more small file that defines GS_POOLSUM_TU / GS_NLOGIT_TU together with GS_EPS.
+// The same translation unit holds the per-layer kernel's eps instances (gin_layer_split_eps_kernel<NT, WAVES, F16>: s_l as one more
+// argument, the numeric mode a template argument as the resident instances have it) and their launcher -- the default translation
+// units keep the kernels they had, names included (tests/golden/dma_lint.json lists them by name).
+#ifndef GS_EPS_TU
+#define GS_EPS_TU 0
+#endif
+#ifndef GS_EPS
+#define GS_EPS GS_EPS_TU
+#endif
 
 namespace fg {
 
@@ -228,20 +242,32 @@ __device__ __forceinline__ void gs_step(const char* wb, int s, int lane, int g, 
     }
 }
 
+// GS_EPS (gin_split_eps.hip: gin_layer_split_eps_kernel): one more argument, the layer's s_l = 1 + eps[l] by value (flowgnn_set_gin_eps:
+// a = s_l h[v] + m, product and sum in fp32 in both numeric modes), and the numeric mode as a template argument
+#if GS_EPS
+template <int NT, int WAVES, bool F16>
+#else
 template <int NT, int WAVES>
+#endif
 __global__ __launch_bounds__(WAVES * 64) void gin_layer_split_kernel(const float* __restrict__ h, float* __restrict__ hout,
                                                                const int* __restrict__ row_ptr,
                                                                const int* __restrict__ src,
                                                                const uint8_t* __restrict__ ecode,
                                                                const float* __restrict__ ecomb,
                                                                const uint8_t* __restrict__ wchunks, int n_tot, int relu_out,
-                                                               int* __restrict__ range_flag, const float* __restrict__ pool_w) {
+                                                               int* __restrict__ range_flag, const float* __restrict__ pool_w
+#if GS_EPS
+                                                               , float self_s
+#endif
+                                                               ) {
     // two DISTINCT LDS objects: the compiler can then prove that the LDS-DMA into one does not alias the ds_reads
     // of the other and leaves the DMA in flight under the MFMAs (see gin_layer_fused_kernel)
     __shared__ __attribute__((aligned(16))) char s_a[GS_CHUNK_BYTES];  // edge-embedding combos, then odd chunks
     __shared__ __attribute__((aligned(16))) char s_b[GS_CHUNK_BYTES];  // even chunks
     __shared__ float s_hub[NT == 1 ? WAVES * GS_MAXHUB * GS_D : 1];     // parked sums of hub rows
+#if !GS_EPS
     constexpr bool F16 = GS_F16;
+#endif
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // in an SGPR: DMA addresses = scalar base + lane * 16
     const int j = lane & 15, g = lane >> 4;
@@ -393,13 +419,27 @@ __global__ __launch_bounds__(WAVES * 64) void gin_layer_split_kernel(const float
     uint4_t in_hi[NT][3], in_lo[NT][3];
     float in_t[NT];
 #pragma unroll
-    for (int nt = 0; nt < NT; nt++) {  // + (1 + eps) h[v], eps == 0; then split into the MLP1 B operands
+    for (int nt = 0; nt < NT; nt++) {  // + (1 + eps) h[v], eps == 0 (GS_EPS: s_l h[v]); then split into the MLP1 B operands
+#if GS_EPS
+        // a = fma(h[v], s_l, m): one fp32 rounding for product and sum, spelled out (hipcc contracts a separate multiply and add anyway);
+        // hub rows come through here too.  s_l == 1 gives the bits of the default's add -- for the K-tail operand as well, which is kept
+        // from fusing with its rounding to f16 (v_fma_mixlo_f16 would round the sum ONCE, to f16, where the default rounds it to fp32 first)
+#pragma unroll
+        for (int q = 0; q < 6; q++) {
+            const float4 x = self_x[nt][q];
+            bq[nt][4 * q + 0] = __builtin_fmaf(x.x, self_s, bq[nt][4 * q + 0]); bq[nt][4 * q + 1] = __builtin_fmaf(x.y, self_s, bq[nt][4 * q + 1]);
+            bq[nt][4 * q + 2] = __builtin_fmaf(x.z, self_s, bq[nt][4 * q + 2]); bq[nt][4 * q + 3] = __builtin_fmaf(x.w, self_s, bq[nt][4 * q + 3]);
+        }
+        bq[nt][24] = __builtin_fmaf(self_t[nt], self_s, bq[nt][24]);
+        asm volatile("" : "+v"(bq[nt][24]));
+#else
 #pragma unroll
         for (int q = 0; q < 6; q++) {
             const float4 x = self_x[nt][q];
             bq[nt][4 * q + 0] += x.x; bq[nt][4 * q + 1] += x.y; bq[nt][4 * q + 2] += x.z; bq[nt][4 * q + 3] += x.w;
         }
         bq[nt][24] += self_t[nt];
+#endif
 #pragma unroll
         for (int ks = 0; ks < 3; ks++) {
             GS_OPER2(F16, bq[nt][8 * ks + 0], bq[nt][8 * ks + 1], in_hi[nt][ks].x, in_lo[nt][ks].x);
@@ -1271,7 +1311,8 @@ __device__ __forceinline__ void gr_layer(unsigned long long (&tacc)[6], char* bx
                                          const float* __restrict__ h0, const uint8_t* __restrict__ desc, const float* __restrict__ ecomb_all,
                                          const uint8_t* __restrict__ wchunks_all, const float* __restrict__ pool_w,
                                          float* __restrict__ hout, float& vmax, int wave, int lane, const float* s_u,
-                                         const uint32_t* __restrict__ enc_idx, const float4* __restrict__ enc_tab, int (&tile_trips)[2]) {
+                                         const uint32_t* __restrict__ enc_idx, const float4* __restrict__ enc_tab, int (&tile_trips)[2],
+                                         const GinSelfScale* self_scale = nullptr /* GS_EPS: the kernel's argument; read by no other instance */) {
     constexpr int NT = 2;
     // (opaque per layer: what is computed from the lane id -- LDS and global addresses of the fragment reads and DMA pieces, shuffle
     // indices -- is otherwise hoisted out of the tile loop, forty values that live across the whole kernel, spill, and are reloaded inside
@@ -1545,7 +1586,7 @@ __device__ __forceinline__ void gr_layer(unsigned long long (&tacc)[6], char* bx
 #undef GR_MSG2
 #undef GR_MSG1
     uint4_t in_hi[NT][3], in_lo[NT][3], in_tb[NT];
-    {   // + (1 + eps) h[v], eps == 0; rows beyond the tile contribute zeros.  All fourteen reads of the wave's own rows are requested
+    {   // + (1 + eps) h[v], eps == 0 (GS_EPS: s_l h[v]); rows beyond the tile contribute zeros.  All fourteen reads of the wave's own rows are requested
         // before the first add: left to itself hipcc re-uses ONE register quad and serialises them -- ds_read_b128, s_waitcnt
         // lgkmcnt(0), two adds, fourteen times per layer (the walk's read registers are dead here: there is room for all of them)
         float4_t sx[NT][6];
@@ -1559,6 +1600,23 @@ __device__ __forceinline__ void gr_layer(unsigned long long (&tacc)[6], char* bx
             sxt[nt] = s_h[rr * GS_D + 96 + g];
         }
         GR_SB();
+#if GS_EPS
+        // the self rows times s_l = 1 + eps[l], in place and in fp32 (hub rows and rows beyond the tile alike); s_l == 1 leaves every bit.
+        // One scalar load from the argument block per layer, HERE: the index is made opaque so that the load is neither hoisted out of the
+        // tile loop nor, for the last layer's constant index, issued at the kernel's top -- a value that lives across the walk and the MLP
+        // steps costs scalar registers the kernel does not have (ten more scalar spills, which tipped two instances into a vector one)
+        int li = l;
+        asm volatile("" : "+s"(li));
+        const float self_s = self_scale->s[li];
+#pragma unroll
+        for (int nt = 0; nt < NT; nt++) {
+#pragma unroll
+            for (int q = 0; q < 6; q++) sx[nt][q] *= self_s;
+            sxt[nt] *= self_s;
+        }
+#else
+        (void)self_scale;
+#endif
 #pragma unroll
         for (int nt = 0; nt < NT; nt++) {
             // a = h[v] + m = fma(m * 2^-16, 2^16, h[v]): the scaled sums come back exactly.  Rows beyond the tile's last are left to run
@@ -1763,7 +1821,7 @@ __device__ __forceinline__ void gr_layer(unsigned long long (&tacc)[6], char* bx
 // requested, all at once as in the prologue: that load is the price of this form (graph embeddings).
 #if GS_POOL_TU
 template <bool HUBS, bool F16>
-#elif GS_NLOGIT_TU || GS_POOLSUM_TU
+#elif GS_NLOGIT_TU || GS_POOLSUM_TU || GS_EPS_TU
 template <bool HUBS, bool ENC, bool F16>
 #else
 template <bool PROF, bool HUBS, bool FOLD, bool ENC>
@@ -1780,20 +1838,25 @@ __global__ __launch_bounds__(GR_WAVES * 64, 2) void gin_resident_kernel(const fl
                                                                        const float4* __restrict__ enc_tab, int tstride,
                                                                        const int* __restrict__ list, const int* __restrict__ lrow
 #if GS_POOL_TU
-                                                                       , float* __restrict__ emb) {
+                                                                       , float* __restrict__ emb
+#elif GS_NLOGIT_TU
+                                                                       , float* __restrict__ node_logits
+#endif
+#if GS_EPS
+                                                                       , GinSelfScale self_scale  /* s_l = 1 + eps[l], by value */
+#endif
+                                                                       ) {
+#if GS_POOL_TU
     constexpr bool PROF = false, FOLD = false, ENC = false, POOL = true, NLOGIT = false;
     float* const node_logits = nullptr;
 #elif GS_NLOGIT_TU
-                                                                       , float* __restrict__ node_logits) {
     constexpr bool PROF = false, FOLD = true, POOL = false, NLOGIT = true;
     float* const emb = nullptr;
-#elif GS_POOLSUM_TU
-                                                                       ) {
+#elif GS_POOLSUM_TU || GS_EPS_TU
     constexpr bool PROF = false, FOLD = true, POOL = false, NLOGIT = false;
     float* const emb = nullptr;
     float* const node_logits = nullptr;
 #else
-                                                                       ) {
     constexpr bool POOL = false, F16 = GS_F16, NLOGIT = false;
     float* const emb = nullptr;
     float* const node_logits = nullptr;
@@ -1837,15 +1900,20 @@ __global__ __launch_bounds__(GR_WAVES * 64, 2) void gin_resident_kernel(const fl
     __syncthreads();
     float vmax = 0.0f;
     int tile_trips[2] = {0, 0};
+#if GS_EPS
+#define GR_SELF_S(L) , &self_scale
+#else
+#define GR_SELF_S(L)
+#endif
     while (true) {
         const int ntile = tile + gridDim.x;
         const bool has_next = ntile < n_tiles;
         const GrTile nxt = gr_load_tile(tile_row, tile_graph, ntile, n_tiles, tstride);  // used five layers from now
 #pragma unroll 1
         for (int l = 0; l < 4; l++)
-            gr_layer<PROF, HUBS, false, FOLD, ENC, F16>(tacc, s_a, s_b, s_h, s_desc, s_dot, cur, nxt, has_next, ntile, l, h0, desc, ecomb_all, wchunks_all, pool_w, hout, vmax, wave, lane, nullptr, enc_idx, enc_tab, tile_trips);
+            gr_layer<PROF, HUBS, false, FOLD, ENC, F16>(tacc, s_a, s_b, s_h, s_desc, s_dot, cur, nxt, has_next, ntile, l, h0, desc, ecomb_all, wchunks_all, pool_w, hout, vmax, wave, lane, nullptr, enc_idx, enc_tab, tile_trips GR_SELF_S(l));
         // (every layer runs an odd number of MLP steps -- seven -- so the table buffer s_a and the first chunk's buffer s_b keep their roles)
-        gr_layer<PROF, HUBS, true, FOLD, ENC, F16, POOL>(tacc, s_a, s_b, s_h, s_desc, s_dot, cur, nxt, has_next, ntile, 4, h0, desc, ecomb_all, wchunks_all, pool_w, hout, vmax, wave, lane, fold_head ? s_u : nullptr, enc_idx, enc_tab, tile_trips);
+        gr_layer<PROF, HUBS, true, FOLD, ENC, F16, POOL>(tacc, s_a, s_b, s_h, s_desc, s_dot, cur, nxt, has_next, ntile, 4, h0, desc, ecomb_all, wchunks_all, pool_w, hout, vmax, wave, lane, fold_head ? s_u : nullptr, enc_idx, enc_tab, tile_trips GR_SELF_S(4));
         if constexpr (POOL) {  // every row of h_5 is in the tile (the layer's closing barrier)
             const int items = (cur.g1 - cur.g0) * GS_D;
             for (int item = (int)threadIdx.x; item < items; item += GR_WAVES * 64) {
@@ -1927,6 +1995,7 @@ __global__ __launch_bounds__(GR_WAVES * 64, 2) void gin_resident_kernel(const fl
     if (__any(!(vmax < 6.0e4f))) {
         if (lane == 0) atomicOr(range_flag, 1);
     }
+#undef GR_SELF_S
     if constexpr (PROF) {  // per-wave phase totals in 10 ns ticks (s_memrealtime)
         if (lane == 0) {
             for (int i = 0; i < 6; i++) prof_out[((size_t)blockIdx.x * GR_WAVES + wave) * 7 + i] = tacc[i];
@@ -1940,7 +2009,7 @@ __global__ __launch_bounds__(GR_WAVES * 64, 2) void gin_resident_kernel(const fl
 #include "dev/gin_pp_device.inc"  // gin_pp_kernel: the ping-pong form, measured slower -- development builds only
 #endif
 
-#if !GS_POOL_TU && !GS_NLOGIT_TU && !GS_POOLSUM_TU
+#if !GS_POOL_TU && !GS_NLOGIT_TU && !GS_POOLSUM_TU && !GS_EPS_TU
 // this translation unit's per-layer kernels (GS_F16: which instance)
 void launch_split_nt(const float* h, float* hout, const int* row_ptr, const int* src, const uint8_t* ecode, const float* ecomb,
                      const uint8_t* chunks, int n_tot, int relu_out, int* range_flag, int nt, hipStream_t s, const float* pool_w) {
@@ -1981,7 +2050,7 @@ void gr_dispatch(bool prof, bool hubs, bool fold, bool enc, int grid, hipStream_
 #undef GR_LAUNCH_FE
 #undef GR_LAUNCH
 }
-#endif  // !GS_POOL_TU && !GS_NLOGIT_TU && !GS_POOLSUM_TU
+#endif  // !GS_POOL_TU && !GS_NLOGIT_TU && !GS_POOLSUM_TU && !GS_EPS_TU
 
 #if !GS_SINGLE_PRODUCT
 inline float pow2_scale(const float* w, size_t n) {
@@ -2033,6 +2102,39 @@ void gin_resident_poolsum_dispatch(bool hubs, bool enc, bool f16, int grid, hipS
     if (hubs) GR_LAUNCH_POOLSUM_EF(true); else GR_LAUNCH_POOLSUM_EF(false);
 #undef GR_LAUNCH_POOLSUM_EF
 #undef GR_LAUNCH_POOLSUM
+}
+#elif GS_EPS_TU
+// the per-layer kernel's eps instances: the three shapes of launch_split_nt, both numeric modes, s_l as the last argument
+void launch_gin_layer_split_eps(const float* h, float* hout, const int* row_ptr, const int* src, const uint8_t* ecode, const float* ecomb,
+                                const uint8_t* chunks, int n_tot, int relu_out, int* range_flag, int nt, hipStream_t s, const float* pool_w,
+                                bool f16, float self_s) {
+#define GS_LAUNCH_EPS(NT, WAVES, NODES)                                                                                               \
+    do {                                                                                                                              \
+        const int blocks = (int)ceil_div_ll(n_tot, NODES);                                                                            \
+        if (f16) gin_layer_split_kernel<NT, WAVES, true><<<blocks, WAVES * 64, 0, s>>>(h, hout, row_ptr, src, ecode, ecomb, chunks, n_tot, relu_out, range_flag, pool_w, self_s); \
+        else gin_layer_split_kernel<NT, WAVES, false><<<blocks, WAVES * 64, 0, s>>>(h, hout, row_ptr, src, ecode, ecomb, chunks, n_tot, relu_out, range_flag, pool_w, self_s);   \
+    } while (0)
+    if (nt == 4) GS_LAUNCH_EPS(1, 8, 128);  // 8 waves, 128 nodes per workgroup
+    else if (nt == 2) GS_LAUNCH_EPS(2, 4, 128);
+    else GS_LAUNCH_EPS(1, 4, 64);
+#undef GS_LAUNCH_EPS
+}
+void gin_resident_eps_dispatch(bool hubs, bool enc, bool f16, int grid, hipStream_t s, const float* h0, const float* ecomb_all,
+                               const uint8_t* chunks_all, const float* pool_w, const float* pool_b, const int* tile_row, const int* tile_graph,
+                               const uint8_t* tile_desc, const int* node_off, float* out, int n_tiles, int* range_flag, const float* head_u,
+                               const uint32_t* eidx, const float4* etab, int tstride, const int* list, const int* lrow, GinSelfScale self_scale) {
+#define GR_LAUNCH_EPS(H, E, F)                                                                                                              \
+    gin_resident_kernel<H, E, F><<<grid, GR_WAVES * 64, 0, s>>>(h0, nullptr, ecomb_all, chunks_all, pool_w, pool_b, tile_row, tile_graph, tile_desc, \
+                                                                node_off, out, n_tiles, range_flag, nullptr, head_u, eidx, etab, tstride, list, lrow, \
+                                                                self_scale)
+#define GR_LAUNCH_EPS_EF(H)                                                               \
+    do {                                                                                  \
+        if (enc) { if (f16) GR_LAUNCH_EPS(H, true, true); else GR_LAUNCH_EPS(H, true, false); }   \
+        else { if (f16) GR_LAUNCH_EPS(H, false, true); else GR_LAUNCH_EPS(H, false, false); }     \
+    } while (0)
+    if (hubs) GR_LAUNCH_EPS_EF(true); else GR_LAUNCH_EPS_EF(false);
+#undef GR_LAUNCH_EPS_EF
+#undef GR_LAUNCH_EPS
 }
 #elif GS_NLOGIT_TU
 void gin_resident_nlogit_dispatch(bool hubs, bool enc, bool f16, int grid, hipStream_t s, const float* h0, const float* ecomb_all,
@@ -2089,6 +2191,15 @@ void gin_resident_poolsum_dispatch(bool hubs, bool enc, bool f16, int grid, hipS
                                    const uint8_t* chunks_all, const float* pool_w, const float* pool_b, const int* tile_row, const int* tile_graph,
                                    const uint8_t* tile_desc, const int* node_off, float* out, int n_tiles, int* range_flag, const float* head_u,
                                    const uint32_t* eidx, const float4* etab, int tstride, const int* list, const int* lrow);
+
+// (gin_split_eps.hip) the per-layer and the folded resident instances that apply s_l = 1 + eps[l] to the self term (flowgnn_set_gin_eps)
+void launch_gin_layer_split_eps(const float* h, float* hout, const int* row_ptr, const int* src, const uint8_t* ecode, const float* ecomb,
+                                const uint8_t* chunks, int n_tot, int relu_out, int* range_flag, int nt, hipStream_t s, const float* pool_w,
+                                bool f16, float self_s);
+void gin_resident_eps_dispatch(bool hubs, bool enc, bool f16, int grid, hipStream_t s, const float* h0, const float* ecomb_all,
+                               const uint8_t* chunks_all, const float* pool_w, const float* pool_b, const int* tile_row, const int* tile_graph,
+                               const uint8_t* tile_desc, const int* node_off, float* out, int n_tiles, int* range_flag, const float* head_u,
+                               const uint32_t* eidx, const float4* etab, int tstride, const int* list, const int* lrow, GinSelfScale self_scale);
 
 // (gin_split_nlogit.hip) the folded instances that also store the per-node readout terms into node_logits [N], caller order
 void gin_resident_nlogit_dispatch(bool hubs, bool enc, bool f16, int grid, hipStream_t s, const float* h0, const float* ecomb_all,
@@ -2248,7 +2359,11 @@ void gin_resident_pack_layer(const float* w1, const float* b1, const float* w2, 
 
 void launch_gin_layer_split(const float* h, float* hout, const int* row_ptr, const int* src, const uint8_t* ecode,
                             const float* ecomb, const uint8_t* chunks, int n_tot, int e_tot, int relu_out, int* range_flag,
-                            int nt, hipStream_t s, const float* pool_w, bool f16) {
+                            int nt, hipStream_t s, const float* pool_w, bool f16, const float* self_s) {
+    if (self_s != nullptr) {  // eps on: the eps instances (null: the launch it always was)
+        launch_gin_layer_split_eps(h, hout, row_ptr, src, ecode, ecomb, chunks, n_tot, relu_out, range_flag, nt, s, pool_w, f16, *self_s);
+        return;
+    }
     (f16 ? launch_gin_layer_split_f16 : launch_split_nt)(h, hout, row_ptr, src, ecode, ecomb, chunks, n_tot, relu_out, range_flag, nt, s, pool_w);
 }
 
@@ -2256,7 +2371,7 @@ int launch_gin_resident(const float* h0, float* hout, const int* row_ptr, const 
                          const uint8_t* chunks_all, const float* pool_w, const float* pool_b, const int* tile_row, const int* tile_graph,
                          uint8_t* tile_desc, const int* node_off, float* out, int n_tiles, int* range_flag, hipStream_t s, bool hubs,
                          const float* head_u, int col_order, bool prof, const GinTileBuild* tb, int tstride, bool f16, float* emb,
-                         float* node_logits, int pooling) {
+                         float* node_logits, int pooling, const float* self_scale) {
     if (n_tiles <= 0) return 0;
     const int order = hubs ? 3 : col_order;
     if (emb != nullptr) { head_u = nullptr; hout = nullptr; prof = false; }  // the pooling instance: un-folded, no tap, no phase stamps
@@ -2265,6 +2380,11 @@ int launch_gin_resident(const float* h0, float* hout, const int* row_ptr, const 
     if (pooling != 0 && !(pooling == 1 && fold && node_logits == nullptr && emb == nullptr) && !(pooling == 2 && emb != nullptr)) {
         set_last_error("launch_gin_resident: pooling 1 (sum) runs the folded instances only (head_u, out, no hout / emb / node_logits), pooling 2 (max) "
                        "the pooling instance only (emb)");
+        return 8;  // FLOWGNN_ERR_UNSUPPORTED
+    }
+    // eps on: the folded, single-task, mean-pooling instances and no other -- anything else would be the eps-less model under its name
+    if (self_scale != nullptr && !(fold && pooling == 0 && emb == nullptr && node_logits == nullptr && tstride == 1)) {
+        set_last_error("launch_gin_resident: a trained eps runs the folded mean-pooling instances only (head_u, out, no hout / emb / node_logits)");
         return 8;  // FLOWGNN_ERR_UNSUPPORTED
     }
     const bool enc = tb != nullptr && fold;  // descriptor + encoder indices straight from the caller's arrays, h_0 computed by the tile loader
@@ -2278,6 +2398,14 @@ int launch_gin_resident(const float* h0, float* hout, const int* row_ptr, const 
     }
     const uint32_t* eidx = enc ? reinterpret_cast<const uint32_t*>(tb->enc_idx) : nullptr;
     const float4* etab = enc ? reinterpret_cast<const float4*>(tb->enc_tab) : nullptr;
+    if (self_scale != nullptr) {  // flowgnn_set_gin_eps: the folded instance with s_l in its argument block (no phase stamps)
+        GinSelfScale ss;
+        for (int l = 0; l < 5; l++) ss.s[l] = self_scale[l];
+        gin_resident_eps_dispatch(hubs, enc, f16, grid, s, h0, ecomb_all, chunks_all, pool_w, pool_b, tile_row, tile_graph, tile_desc, node_off, out,
+                                  n_tiles, range_flag, head_u, eidx, etab, tstride, enc ? tb->list : nullptr, enc ? tb->lrow : nullptr, ss);
+        if (d) (void)hipFree(d);
+        return 0;
+    }
     if (emb != nullptr && pooling == 2) {  // FLOWGNN_POOL_MAX: the per-column maxima go to emb, and the caller applies the head to them (out == null)
         gin_resident_poolmax_dispatch(hubs, f16, grid, s, h0, ecomb_all, chunks_all, pool_w, pool_b, tile_row, tile_graph, tile_desc, node_off, nullptr,
                                       n_tiles, range_flag, tstride, emb);

@@ -2,7 +2,7 @@
 // OpenCL host (GIN/src/host.cc): load the model's .bin weights, read a graph pack in the reference's on-disk
 // layout, run the whole dataset as ONE batched launch NUM_TRIALS times, write HLS_output.txt.
 //
-//   host <MODEL> [--graphs DIR] [--weights DIR] [--num-graphs N] [--trials T] [--out FILE] [--node-logits FILE] [--attention FILE [--attention-layers MASK]] [--device D | --devices D0,D1,..] [--option key=value] [--numeric f32|q6.10|f16] [XCLBIN]
+//   host <MODEL> [--graphs DIR] [--weights DIR] [--num-graphs N] [--trials T] [--out FILE] [--node-logits FILE] [--attention FILE [--attention-layers MASK]] [--device D | --devices D0,D1,..] [--option key=value] [--numeric f32|q6.10|f16] [--eps] [XCLBIN]
 //
 //   MODEL        GIN | GIN-VN | GCN | GAT | PNA | DGN
 //   --graphs     directory holding graph_info/ and graph_bin/      (default ../graphs, host.cc:14-15)
@@ -14,6 +14,8 @@
 //   --node-logits one more run behind the timed ones, with flowgnn_set_node_logits on: one line per node, NUM_TASK values (GIN, GIN-VN, GCN, GAT)
 //   --attention  one more run behind the timed ones, with flowgnn_set_attention on (GAT): one line per selected layer and edge,
 //                `layer edge h0 h1 h2 h3`, edges in the pack's order; --attention-layers: the layer mask (default 16, the last layer)
+//   --eps        GIN / GIN-VN: read gin_ep1_eps_dim100.bin (five LE float32) from the weights directory and apply it (flowgnn_set_gin_eps);
+//                without the flag the file stays ignored, as in the reference
 //   XCLBIN       accepted and ignored, so `./host <xclbin>`-style command lines keep working
 //
 // Only the C ABI of include/flowgnn.h is used; no HIP or torch types here.
@@ -79,7 +81,7 @@ static bool read_eig_txt(const std::string& path, std::vector<float>& eig, size_
 int main(int argc, char** argv) {
     if (argc < 2) {
         fprintf(stderr, "Usage: %s <GIN|GIN-VN|GCN|GAT|PNA|DGN> [--graphs DIR] [--weights DIR] [--num-graphs N] [--trials T] "
-                        "[--out FILE] [--embeddings FILE] [--node-embeddings FILE] [--node-logits FILE] [--attention FILE [--attention-layers MASK]] [--device D | --devices D0,D1,..] [--option key=value] [--numeric f32|q6.10|f16] [--pooling mean|sum|max] [--num-tasks T] [XCLBIN File]\n", argv[0]);
+                        "[--out FILE] [--embeddings FILE] [--node-embeddings FILE] [--node-logits FILE] [--attention FILE [--attention-layers MASK]] [--device D | --devices D0,D1,..] [--option key=value] [--numeric f32|q6.10|f16] [--pooling mean|sum|max] [--eps] [--num-tasks T] [XCLBIN File]\n", argv[0]);
         return EXIT_FAILURE;
     }
     const std::string model = argv[1];
@@ -89,6 +91,7 @@ int main(int argc, char** argv) {
     long num_graphs = -1;
     int attn_mask = 16;
     int trials = 25, numeric = FLOWGNN_NUMERIC_F32, num_tasks = 1, pooling = FLOWGNN_POOL_MEAN;
+    bool use_eps = false;
     std::vector<int> devices;
     std::vector<std::pair<std::string, double>> options;
     for (int i = 2; i < argc; i++) {
@@ -133,6 +136,7 @@ int main(int argc, char** argv) {
             if (m != "mean" && m != "sum" && m != "max") { fprintf(stderr, "--pooling wants mean, sum or max\n"); return EXIT_FAILURE; }
             pooling = m == "sum" ? FLOWGNN_POOL_SUM : m == "max" ? FLOWGNN_POOL_MAX : FLOWGNN_POOL_MEAN;
         }
+        else if (a == "--eps") use_eps = true;  // the trained eps of the weights directory (flowgnn_set_gin_eps; GIN / GIN-VN)
         // anything else (e.g. an .xclbin path) is ignored
     }
     if (num_graphs < 0) num_graphs = read_count_file(graphs + "/dataset_size.txt");
@@ -161,6 +165,13 @@ int main(int argc, char** argv) {
     if (pooling != FLOWGNN_POOL_MEAN) {
         rc = flowgnn_group_set_pooling(eng, pooling);
         if (rc) { fprintf(stderr, "--pooling: %d %s\n", rc, flowgnn_group_last_error(eng)); return EXIT_FAILURE; }
+    }
+    if (use_eps) {
+        std::vector<float> eps(5);
+        const std::string path = wdir + "/gin_ep1_eps_dim100.bin";
+        if (!read_exact(path, eps, 0, 5)) { fprintf(stderr, "--eps: cannot read five floats from %s\n", path.c_str()); return EXIT_FAILURE; }
+        rc = flowgnn_group_set_gin_eps(eng, eps.data());
+        if (rc) { fprintf(stderr, "--eps: %d %s\n", rc, flowgnn_group_last_error(eng)); return EXIT_FAILURE; }
     }
     printf("\n******* Weights loading done *******\n");
 

@@ -43,6 +43,16 @@ def _pf(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(_lib.p_float)
 
 
+def _eps_arg(eps):
+    """None -> NULL (off); else the five values as a float32 array (ctypes takes its pointer for the duration of the call)."""
+    if eps is None:
+        return None
+    a = np.ascontiguousarray(np.asarray(eps, dtype=np.float32).reshape(-1))
+    if a.size != 5:
+        raise ValueError(f"eps: five values (one per GIN layer), got {a.size}")
+    return (C.c_float * 5)(*a.tolist())
+
+
 def option_value(v) -> float:
     """Option values are numbers; "f32" / "f16" (the *_mfma switches) read as 32 / 16."""
     if isinstance(v, str) and v in ("f32", "f16"):
@@ -146,8 +156,12 @@ class Engine:
         ptrs = (_lib.p_float * len(arrs))(*[_pf(a) for a in arrs])
         self._check(self.lib.flowgnn_set_weights(self._h, len(arrs), ptrs), "flowgnn_set_weights")
 
-    def load_weights_dir(self, directory: str):
+    def load_weights_dir(self, directory: str, eps: bool = False):
+        """eps=True (GIN, GIN-VN): also read the directory's eps file and apply it (set_gin_eps); the C call itself never does."""
         self._check(self.lib.flowgnn_load_weights_dir(self._h, directory.encode()), "flowgnn_load_weights_dir")
+        if eps:
+            from .weights import load_gin_eps
+            self.set_gin_eps(load_gin_eps(directory))
 
     # ---- batch
     def set_job_totals(self, job_nodes: int = -1, job_edges: int = -1):
@@ -487,6 +501,16 @@ class Engine:
         code = int(self.lib.flowgnn_pooling(self._h))
         return next(k for k, v in POOLING_MODES.items() if v == code)
 
+    def set_gin_eps(self, eps=None):
+        """GIN / GIN-VN: apply a trained eps, five values, one per layer -- a[v] = (1 + eps[l]) h[v] + sum of messages (flowgnn.h:
+        flowgnn_set_gin_eps).  None turns it off (the default: the reference has no eps).  The engine's, across batches and weight sets."""
+        self._check(self.lib.flowgnn_set_gin_eps(self._h, _eps_arg(eps)), "flowgnn_set_gin_eps")
+
+    def gin_eps(self):
+        """The five values as float32[5], or None while eps is off (flowgnn.h: flowgnn_gin_eps)."""
+        out = np.zeros(5, np.float32)
+        return out if int(self.lib.flowgnn_gin_eps(self._h, _pf(out))) == 1 else None
+
     def exact_reruns(self) -> int:
         """Forward passes repeated on the exact-fp32 kernels (flowgnn.h: flowgnn_exact_reruns)."""
         return int(self.lib.flowgnn_exact_reruns(self._h))
@@ -600,6 +624,10 @@ class EngineGroup:
     def set_pooling(self, mode: str = "mean"):
         """Engine.set_pooling on every member (flowgnn.h: flowgnn_group_set_pooling)."""
         self._check(self.lib.flowgnn_group_set_pooling(self._h, POOLING_MODES[mode]), "flowgnn_group_set_pooling")
+
+    def set_gin_eps(self, eps=None):
+        """Engine.set_gin_eps on every member (flowgnn.h: flowgnn_group_set_gin_eps)."""
+        self._check(self.lib.flowgnn_group_set_gin_eps(self._h, _eps_arg(eps)), "flowgnn_group_set_gin_eps")
 
     def set_batch(self, batch: GraphBatch):
         nn, ne = _i32(batch.nums_of_nodes), _i32(batch.nums_of_edges)
@@ -722,6 +750,15 @@ def entry_set_pooling(model: str, mode: str = "mean"):
     rc = _lib.load().flowgnn_entry_set_pooling(_lib.MODEL_IDS[model.upper()], POOLING_MODES[mode])
     if rc:
         raise FlowGNNError(rc, f"flowgnn_entry_set_pooling({mode})")
+
+
+def entry_set_gin_eps(model: str, eps=None):
+    """A trained eps for the engines behind `model`'s <M>_compute_graphs symbols, one vector for every weight set; None: off
+    (flowgnn.h: flowgnn_entry_set_gin_eps)."""
+    lib = _lib.load()
+    rc = lib.flowgnn_entry_set_gin_eps(_lib.MODEL_IDS[model.upper()], _eps_arg(eps))
+    if rc:
+        raise FlowGNNError(rc, "flowgnn_entry_set_gin_eps", (lib.flowgnn_last_error(None) or b"").decode())
 
 
 def compute_graphs(model: str, batch: GraphBatch, weight_sets, reload_weights=None, num_tasks: int = 1) -> np.ndarray:

@@ -64,20 +64,35 @@ def _fold_bn(w: np.ndarray, b: np.ndarray, sd: Mapping, prefix: str):
     return w * s[:, None], (b - mean) * s + beta
 
 
-def gin_weights_from_ogb_state_dict(sd: Mapping, num_layers: int = 5, eps_tol: float = 0.0, multi_task: bool = False) -> Dict[str, np.ndarray]:
+def gin_eps_from_ogb_state_dict(sd: Mapping, num_layers: int = 5) -> np.ndarray:
+    """The trained `gnn_node.convs.l.eps` of an OGB GIN state_dict as float32[num_layers] (0 where a layer has none): what
+    Engine.set_gin_eps / flowgnn_set_gin_eps take, and what export_weights(..., keep_eps=True) writes into the eps file."""
+    out = np.zeros(num_layers, np.float32)
+    for l in range(num_layers):
+        k = f"gnn_node.convs.{l}.eps"
+        if k in sd:
+            out[l] = np.float32(_np(sd[k]).ravel()[0])
+    if not np.isfinite(out).all():
+        raise ExportError("eps: non-finite values")
+    return out
+
+
+def gin_weights_from_ogb_state_dict(sd: Mapping, num_layers: int = 5, eps_tol: float = 0.0, multi_task: bool = False,
+                                    keep_eps: bool = False) -> Dict[str, np.ndarray]:
     """OGB `GNN(gnn_type='gin', virtual_node=False, JK='last', residual=False, graph_pooling='mean')` -> the reference's
     GIN weight set.  `convs.l.mlp` may be Linear-BatchNorm-ReLU-Linear (OGB) or Linear-ReLU-Linear; `batch_norms.l`
     (applied to the conv output before the ReLU) is folded into the second linear layer when present.
     multi_task: keep every row of graph_pred_linear (ogbg-molpcba: 128 tasks) -- graph_pred_weights becomes [NUM_TASK][100], for
     an engine with flowgnn_set_num_tasks(NUM_TASK); without it a head with more than one task is refused (the reference's NUM_TASK is 1).
-    The reference ignores GIN's eps (GIN/src/host_load.cc reads it, nothing uses it): a trained |eps| > eps_tol is refused."""
+    The reference ignores GIN's eps (GIN/src/host_load.cc reads it, nothing uses it): a trained |eps| > eps_tol is refused, unless
+    keep_eps says that the engine will apply it (gin_eps_from_ogb_state_dict + flowgnn_set_gin_eps)."""
     p = "gnn_node"
     out = OrderedDict()
     out["node_embedding_weight"] = _tables(sd, f"{p}.atom_encoder.atom_embedding_list", ATOM_DIMS)
     ed, w1s, b1s, w2s, b2s = [], [], [], [], []
     for l in range(num_layers):
         c = f"{p}.convs.{l}"
-        if f"{c}.eps" in sd and abs(float(_np(sd[f"{c}.eps"]).ravel()[0])) > eps_tol:
+        if not keep_eps and f"{c}.eps" in sd and abs(float(_np(sd[f"{c}.eps"]).ravel()[0])) > eps_tol:
             raise ExportError(f"{c}.eps = {float(_np(sd[c + '.eps']).ravel()[0]):g}: the reference's GIN has no eps term")
         ed.append(_tables(sd, f"{c}.bond_encoder.bond_embedding_list", BOND_DIMS))
         w1, b1 = _get(sd, f"{c}.mlp.0.weight"), _get(sd, f"{c}.mlp.0.bias")
@@ -146,13 +161,15 @@ def _checked(w: Dict[str, np.ndarray], spec: Mapping, shape_of) -> Dict[str, np.
     return res
 
 
-def export_weights(model: str, sd: Mapping, directory: str, multi_task: bool = False) -> Dict[str, np.ndarray]:
+def export_weights(model: str, sd: Mapping, directory: str, multi_task: bool = False, keep_eps: bool = False) -> Dict[str, np.ndarray]:
     """Write the `.bin` file(s) `host` / `flowgnn_load_weights_dir` read for `model` ('GIN', 'GIN-VN' or 'GCN').
-    multi_task: keep all rows of the prediction head (the engine then needs flowgnn_set_num_tasks(rows) before loading)."""
+    multi_task: keep all rows of the prediction head (the engine then needs flowgnn_set_num_tasks(rows) before loading).
+    keep_eps (GIN, GIN-VN): a trained eps is not refused; the eps file holds the trained values, for `host --eps` /
+    Engine.load_weights_dir(dir, eps=True) to apply (flowgnn_set_gin_eps)."""
     m = model.upper()
     if m in ("GIN", "GIN-VN"):
-        w = gin_weights_from_ogb_state_dict(sd, multi_task=multi_task)
-        _weights.save_gin_weights(w, directory)
+        w = gin_weights_from_ogb_state_dict(sd, multi_task=multi_task, keep_eps=keep_eps)
+        _weights.save_gin_weights(w, directory, eps=gin_eps_from_ogb_state_dict(sd) if keep_eps else None)
     elif m == "GCN":
         w = gcn_weights_from_ogb_state_dict(sd, multi_task=multi_task)
         _weights.save_gcn_weights(w, directory)

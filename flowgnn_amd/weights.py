@@ -51,12 +51,23 @@ def load_gin_weights(directory: str, num_tasks: int = 1) -> Dict[str, np.ndarray
     return OrderedDict((k, _read(os.path.join(directory, f), _task_shape(k, shp, num_tasks))) for k, (f, shp) in GIN_FILES.items())
 
 
-def save_gin_weights(w: Dict[str, np.ndarray], directory: str) -> None:
+GIN_EPS_FILE = "gin_ep1_eps_dim100.bin"  # five LE float32, one per layer: read by the reference host and never used
+
+
+def load_gin_eps(directory: str) -> np.ndarray:
+    """The five eps values of a GIN / GIN-VN weights directory, float32[5] (for Engine.set_gin_eps: flowgnn_set_gin_eps)."""
+    return _read(os.path.join(directory, GIN_EPS_FILE), (5,))
+
+
+def save_gin_weights(w: Dict[str, np.ndarray], directory: str, eps=None) -> None:
+    """eps: the five trained values for the eps file (None: zeros, what the reference's own sets carry).  Nothing applies the file
+    unless asked to: `host --eps`, Engine.load_weights_dir(dir, eps=True)."""
     os.makedirs(directory, exist_ok=True)
     tasks = int(np.asarray(w["graph_pred_bias"]).size)
     for k, (f, shp) in GIN_FILES.items():
         np.asarray(w[k], dtype="<f4").reshape(_task_shape(k, shp, tasks)).tofile(os.path.join(directory, f))
-    np.zeros(5, dtype="<f4").tofile(os.path.join(directory, "gin_ep1_eps_dim100.bin"))  # read, never used
+    e = np.zeros(5, dtype="<f4") if eps is None else np.asarray(eps, dtype="<f4").reshape(5)
+    e.tofile(os.path.join(directory, GIN_EPS_FILE))  # (zeros: read by the reference, never used)
 
 
 def synth_gin_weights(seed: int = 7, num_tasks: int = 1) -> Dict[str, np.ndarray]:

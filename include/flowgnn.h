@@ -183,6 +183,7 @@ int flowgnn_entry_set_devices(int n_devices, const int* device_ids);
 int flowgnn_entry_set_pipeline(int chunks_per_engine);
 int flowgnn_entry_set_option(int model, const char* key, double value);
 int flowgnn_entry_set_pooling(int model, int mode);       /* flowgnn_set_pooling (section 2) for the entry points of `model` */
+int flowgnn_entry_set_gin_eps(int model, const float* eps); /* flowgnn_set_gin_eps (section 2): one vector for every weight set of the entry points; remembered for engines created later */
 
 /* =====================================================================
  * (2) Handle API
@@ -569,6 +570,31 @@ int flowgnn_set_pooling(flowgnn_engine* e, int mode);
 int flowgnn_pooling(const flowgnn_engine* e);            /* -1 for a null handle */
 
 /*
+ * Trained eps of GIN / GIN-VN.  OGB's GINConv computes mlp((1 + eps) x + propagate(...)) with eps an nn.Parameter; the reference
+ * accelerator reads gin_ep1_eps_dim100.bin and never uses it, and so does this engine by default.  With eps on, layer l computes
+ *     a[v] = s_l h_l[v] + sum_e relu(h_l[src_e] + ecomb_l[code_e]),     s_l = (float)(1.0f + eps[l]), formed once on the host
+ * and everything behind `a` is what it was (operand split, range tracking on a, MLP, ReLU placement, readout).  GIN-VN's virtual node
+ * is a node like any other.  In FLOWGNN_NUMERIC_F16 the product and the sum stay fp32, as the walk is; only the MLP operands are rounded.
+ * "On" and "off" are states, not values: a non-null pointer turns the eps instances of the kernels on even if all five values are zero
+ * (x * 1.0f == x: the same bits as off, through other kernels); NULL turns them off, and then every launch is the one it always was.
+ * The setting belongs to the engine, like the pooling and the numeric mode: it holds across batches and across flowgnn_set_weights,
+ * it may change between runs on a resident batch, and it drops a recorded launch sequence (option hipgraph).
+ * flowgnn_load_weights_dir does not read the eps file; `host --eps` and the Python wrapper's load_weights_dir(dir, eps=True) do.
+ * Kernels: single task, mean pooling, folded readout, no extra outputs -> gin_resident_eps_kernel (both front ends, both numeric
+ * modes); every other configuration, the range fallback included -> the per-layer kernels' eps instances.
+ * flowgnn_set_gin_eps: FLOWGNN_ERR_UNSUPPORTED (flowgnn_last_error says why) for any model but GIN / GIN-VN and in
+ *     FLOWGNN_NUMERIC_Q6_10 (the fixed-point arithmetic is the reference's, which has no eps; flowgnn_set_numeric_mode(Q6_10) answers
+ *     the same while eps is on); FLOWGNN_ERR_ARG for a value that is not finite.  While eps is on, flowgnn_run answers
+ *     FLOWGNN_ERR_UNSUPPORTED under option gin_unfused 1, and so do flowgnn_run_aggregation_only and flowgnn_get_aggregate (the
+ *     stand-alone aggregation kernel has no eps instance).
+ * flowgnn_gin_eps: 1 on, 0 off, -1 for a null handle; eps_out (may be NULL) receives the five values (zeros while off).
+ * flowgnn_group_set_gin_eps: flowgnn_set_gin_eps on every member.  flowgnn_entry_set_gin_eps: for the engines behind the
+ *     GIN / GIN-VN entry points, one vector for every weight set.
+ */
+int flowgnn_set_gin_eps(flowgnn_engine* e, const float* eps /* [5], NULL = off */);
+int flowgnn_gin_eps(const flowgnn_engine* e, float* eps_out /* [5], may be NULL */);   /* 1 on, 0 off, -1 null handle */
+
+/*
  * Run-time switches, by name (the full list with defaults: the option table in flowgnn_amd/csrc/engine.hip, or
  * flowgnn_option_count / flowgnn_option_name).  They select between kernels that compute the SAME results -- e.g.
  * "gin_resident" 0 = one launch per layer, "gin_mfma" 32 = fp32 matrix pipe instead of three f16 products, "pna_fused" 0 =
@@ -618,6 +644,7 @@ int flowgnn_group_set_option(flowgnn_group* g, const char* key, double value);
 int flowgnn_group_set_num_tasks(flowgnn_group* g, int num_tasks);
 int flowgnn_group_set_numeric_mode(flowgnn_group* g, int mode);
 int flowgnn_group_set_pooling(flowgnn_group* g, int mode);
+int flowgnn_group_set_gin_eps(flowgnn_group* g, const float* eps);
 int flowgnn_group_set_batch(flowgnn_group* g, int num_graphs,
                             const int* nums_of_nodes, const int* nums_of_edges,
                             const int* node_feature, const int* edge_list, const int* edge_attr,

@@ -4,7 +4,7 @@
 # The walks' timing variants (csrc/dev/walk_timing_variants.h: GR_CONFLICT_FREE_WALK, GR_ONE_CODE_WALK, GCN_CF_ROWS, GCN_CF_CODES) and the
 # ping-pong kernel live behind -DFLOWGNN_DEV: pass it with them, e.g. variant.sh cf gcn.hip "-DFLOWGNN_DEV -DGCN_CF_ROWS".
 # FILE.hip may be one of the files that compile a model's file once more under a macro (the instances of its resident kernel):
-#   gin_split_f16 gin_split_pool gin_split_nlogit gin_split_poolsum gin_split_poolmax (gin_split.hip), gcn_rows gcn_nlogit gcn_poolsum (gcn.hip),
+#   gin_split_f16 gin_split_pool gin_split_nlogit gin_split_poolsum gin_split_poolmax gin_split_eps (gin_split.hip), gcn_rows gcn_nlogit gcn_poolsum (gcn.hip),
 #   gat_nlogit gat_attn gat_poolsum (gat.hip), pna_emb pna_rows (pna.hip), dgn_emb dgn_rows (dgn.hip)
 # -- a flag that changes the model's file changes them too, and each is recompiled by its own call: variant.sh sum gin_split_poolsum.hip "-D..."
 set -e
