@@ -279,69 +279,70 @@ static void ensure_csr(flowgnn_engine* e) {
     e->db.csr_built = true;
 }
 
-// embeddings on: the engine's own buffer holds the resident batch's [G][dim]; db.emb follows the switch and the caller's buffer
-static int place_embeddings(flowgnn_engine* e) {
-    if (e->emb_on && e->batch_ready && !e->emb_user) {
-        const size_t need = sizeof(float) * (size_t)e->G * (size_t)flowgnn_embedding_dim(e->model_id);
-        if (!e->emb.holds(need)) {
+// The optional per-run outputs (fg::OutSlot, engine_internal.h), in ONE list: everything that treats them alike walks it.
+struct Output {
+    fg::OutSlot flowgnn_engine::*slot;
+    float* DeviceBatch::*field;               // the pointer of the forward's DeviceBatch that the slot feeds
+    bool flowgnn_engine::*on;                 // its switch (null: attn_mask, the switch of both attention slots)
+    size_t (*floats)(const flowgnn_engine*);  // what the resident batch needs of it
+    const char *noun, *setter;                // for the texts of its get and *_device calls
+    const char* no_fixed_point;               // flowgnn_set_numeric_mode's refusal while it is on (null: the row above has said it)
+};
+static size_t emb_dim_of(const flowgnn_engine* e) { return (size_t)flowgnn_embedding_dim(e->model_id); }
+static size_t attn_layers(const flowgnn_engine* e) { return (size_t)__builtin_popcount((unsigned)e->attn_mask); }
+enum { OUT_EMB, OUT_NEMB, OUT_NLOG, OUT_ATTN_E, OUT_ATTN_S };
+static const Output kOutputs[] = {
+    {&flowgnn_engine::emb, &DeviceBatch::emb, &flowgnn_engine::emb_on, [](const flowgnn_engine* e) { return (size_t)e->G * emb_dim_of(e); },
+     "embeddings", "flowgnn_set_embeddings", "flowgnn_set_numeric_mode: graph embeddings are on, and there are no fixed-point embeddings"},
+    {&flowgnn_engine::nemb, &DeviceBatch::node_emb, &flowgnn_engine::nemb_on, [](const flowgnn_engine* e) { return (size_t)e->N * emb_dim_of(e); },
+     "node embeddings", "flowgnn_set_node_embeddings", "flowgnn_set_numeric_mode: node embeddings are on, and there are no fixed-point node embeddings"},
+    {&flowgnn_engine::nlog, &DeviceBatch::node_logits, &flowgnn_engine::nlog_on, [](const flowgnn_engine* e) { return (size_t)e->N * (size_t)e->num_tasks; },
+     "node logits", "flowgnn_set_node_logits", "flowgnn_set_numeric_mode: node logits are on, and there are no fixed-point node logits"},
+    {&flowgnn_engine::attn_e, &DeviceBatch::attn_edge, nullptr, [](const flowgnn_engine* e) { return attn_layers(e) * (size_t)e->E * 4; },
+     "attention", "flowgnn_set_attention", "flowgnn_set_numeric_mode: attention is on, and there are no fixed-point attention coefficients"},
+    {&flowgnn_engine::attn_s, &DeviceBatch::attn_self, nullptr, [](const flowgnn_engine* e) { return attn_layers(e) * (size_t)e->N * 4; },
+     "attention", "flowgnn_set_attention", nullptr},
+};
+static bool is_on(const flowgnn_engine* e, const Output& o) { return o.on ? e->*o.on : e->attn_mask != 0; }
+
+// One output after anything it follows has changed (switch, caller's buffer, batch): with the output on and no caller's buffer, the
+// engine's own buffer holds what the resident batch needs; the DeviceBatch pointer is the target, or null without a batch
+static int place(flowgnn_engine* e, const Output& o) {
+    fg::OutSlot& s = e->*o.slot;
+    const bool on = e->batch_ready && is_on(e, o);
+    if (on && !s.user) {
+        const size_t need = sizeof(float) * o.floats(e);
+        if (!s.own.holds(need)) {
             if (e->stream) EHIP_TRY(e, hipStreamSynchronize(e->stream));  // (a run in flight may still write the old one)
-            if (e->emb_last == e->emb.p) e->emb_last = nullptr;
-            EHIP_TRY(e, e->emb.reserve(need, false));  // no headroom: one batch's size, kept across batches
+            if (s.last == s.own.p) s.last = nullptr;
+            EHIP_TRY(e, s.own.reserve(need, false));  // no headroom: one batch's size, kept across batches
         }
     }
-    e->db.emb = e->batch_ready ? e->emb_target() : nullptr;
+    e->db.*o.field = s.target(on);
     return FLOWGNN_OK;
 }
-// ... and the same for the node embeddings, [N][dim]
-static int place_node_embeddings(flowgnn_engine* e) {
-    if (e->nemb_on && e->batch_ready && !e->nemb_user) {
-        const size_t need = sizeof(float) * (size_t)e->N * (size_t)flowgnn_embedding_dim(e->model_id);
-        if (!e->nemb.holds(need)) {
-            if (e->stream) EHIP_TRY(e, hipStreamSynchronize(e->stream));
-            if (e->nemb_last == e->nemb.p) e->nemb_last = nullptr;
-            EHIP_TRY(e, e->nemb.reserve(need, false));
-        }
-    }
-    e->db.node_emb = e->batch_ready ? e->nemb_target() : nullptr;
-    return FLOWGNN_OK;
-}
-// ... and for the node logits, [N][num_tasks]
-static int place_node_logits(flowgnn_engine* e) {
-    if (e->nlog_on && e->batch_ready && !e->nlog_user) {
-        const size_t need = sizeof(float) * (size_t)e->N * (size_t)e->num_tasks;
-        if (!e->nlog.holds(need)) {
-            if (e->stream) EHIP_TRY(e, hipStreamSynchronize(e->stream));
-            if (e->nlog_last == e->nlog.p) e->nlog_last = nullptr;
-            EHIP_TRY(e, e->nlog.reserve(need, false));
-        }
-    }
-    e->db.node_logits = e->batch_ready ? e->nlog_target() : nullptr;
+// ... and the attention coefficients: two outputs, and the mask the models read
+static int place_attention(flowgnn_engine* e) {
+    if (int rc = place(e, kOutputs[OUT_ATTN_E])) return rc;
+    if (int rc = place(e, kOutputs[OUT_ATTN_S])) return rc;
+    e->db.attn_mask = e->batch_ready ? e->attn_mask : 0;
     return FLOWGNN_OK;
 }
 
-// ... and for the attention coefficients of the selected layers, [n_sel][E][4] and [n_sel][N][4]
-static int place_attention(flowgnn_engine* e) {
-    if (e->attn_mask && e->batch_ready) {
-        const size_t n_sel = (size_t)__builtin_popcount((unsigned)e->attn_mask);
-        const size_t need_e = sizeof(float) * n_sel * (size_t)e->E * 4, need_s = sizeof(float) * n_sel * (size_t)e->N * 4;
-        if ((!e->attn_e_user && !e->attn_e.holds(need_e)) || (!e->attn_s_user && !e->attn_s.holds(need_s))) {
-            if (e->stream) EHIP_TRY(e, hipStreamSynchronize(e->stream));
-            if (!e->attn_e_user && !e->attn_e.holds(need_e)) {
-                if (e->attn_e_last == e->attn_e.p) e->attn_e_last = nullptr;
-                EHIP_TRY(e, e->attn_e.reserve(need_e, false));
-            }
-            if (!e->attn_s_user && !e->attn_s.holds(need_s)) {
-                if (e->attn_s_last == e->attn_s.p) e->attn_s_last = nullptr;
-                EHIP_TRY(e, e->attn_s.reserve(need_s, false));
-            }
-        }
+// The DeviceBatch's output pointers and attention mask as they are, put back when the scope ends: a pass that is to fill other
+// buffers than the next run's (the exact re-run), or none (a tap's pass), installs its own in between
+struct KeepOutputFields {
+    DeviceBatch& db;
+    float* ptr[sizeof(kOutputs) / sizeof(kOutputs[0])];
+    const int mask;
+    explicit KeepOutputFields(DeviceBatch& d) : db(d), mask(d.attn_mask) {
+        for (size_t i = 0; i < sizeof(ptr) / sizeof(ptr[0]); i++) ptr[i] = db.*kOutputs[i].field;
     }
-    const bool on = e->batch_ready && e->attn_mask;
-    e->db.attn_mask = on ? e->attn_mask : 0;
-    e->db.attn_edge = on ? e->attn_e_target() : nullptr;
-    e->db.attn_self = on ? e->attn_s_target() : nullptr;
-    return FLOWGNN_OK;
-}
+    ~KeepOutputFields() {
+        for (size_t i = 0; i < sizeof(ptr) / sizeof(ptr[0]); i++) db.*kOutputs[i].field = ptr[i];
+        db.attn_mask = mask;
+    }
+};
 
 extern "C" {
 
@@ -408,11 +409,7 @@ int flowgnn_destroy(flowgnn_engine* e) {
     if (e->stream) (void)hipStreamSynchronize(e->stream);
     e->drop_graph();
     e->free_batch();
-    e->emb.release();
-    e->nemb.release();
-    e->nlog.release();
-    e->attn_e.release();
-    e->attn_s.release();
+    for (const Output& o : kOutputs) (e->*o.slot).own.release();
     if (e->d_err) (void)hipFree(e->d_err);
     delete e->model;
     if (e->own_stream) (void)hipStreamDestroy(e->own_stream);
@@ -720,19 +717,12 @@ static int set_batch_state(flowgnn_engine* e, int num_graphs, const int* nums_of
     e->db.range_flag = e->d_err + 1;
     e->force_exact = false;
     e->batch_ready = true;
-    e->emb_user = nullptr;
-    e->emb_last = nullptr;
-    e->nemb_user = nullptr;
-    e->nemb_last = nullptr;
-    e->nlog_user = nullptr;
-    e->nlog_last = nullptr;
-    e->attn_e_user = e->attn_s_user = nullptr;
-    e->attn_e_last = e->attn_s_last = nullptr;
+    for (const Output& o : kOutputs) (e->*o.slot).user = (e->*o.slot).last = nullptr;
     e->attn_mask_last = 0;
-    if (int rc = place_embeddings(e)) return rc;
-    if (int rc = place_node_embeddings(e)) return rc;
-    if (int rc = place_node_logits(e)) return rc;
-    return place_attention(e);
+    for (const Output& o : kOutputs)
+        if (int rc = place(e, o)) return rc;
+    e->db.attn_mask = e->attn_mask;
+    return FLOWGNN_OK;
 }
 
 }  // extern "C"
@@ -860,12 +850,8 @@ int flowgnn_run(flowgnn_engine* e) {
         return FLOWGNN_ERR_STATE;
     }
     ENGINE_TRY(e, use_device(e));
-    e->emb_last = e->db.emb;
-    e->nemb_last = e->db.node_emb;
-    e->nlog_last = e->db.node_logits;
+    for (const Output& o : kOutputs) (e->*o.slot).last = e->db.*o.field;
     e->attn_mask_last = e->db.attn_mask;
-    e->attn_e_last = e->db.attn_edge;
-    e->attn_s_last = e->db.attn_self;
     if (e->G == 0) { e->ran = true; return FLOWGNN_OK; }
     const bool want_graph = e->graph_mode != 0 && !e->prof.enabled && (e->graph_mode > 1 || e->N <= (1ll << 20));
     if (want_graph && e->graph_ok) {
@@ -942,28 +928,14 @@ int flowgnn_sync(flowgnn_engine* e) {
         e->drop_graph();  // the captured launches are the split-f16 ones
         EHIP_TRY(e, hipMemsetAsync(e->d_err + 1, 0, sizeof(int), e->stream));
         e->model->set_exact(true);
-        {   // the repeated pass refills what the run filled: the logits, and the embeddings / node embeddings / node logits where that run had them on
-            float* const now = e->db.emb;
-            float* const nnow = e->db.node_emb;
-            float* const lnow = e->db.node_logits;
-            e->db.emb = e->emb_last;
-            e->db.node_emb = e->nemb_last;
-            e->db.node_logits = e->nlog_last;
-            const int anow = e->db.attn_mask;  // ... and the attention coefficients
-            float* const aenow = e->db.attn_edge;
-            float* const asnow = e->db.attn_self;
+        int frc;
+        {   // the repeated pass refills what the run filled: the logits, and every optional output where that run had it on
+            KeepOutputFields keep(e->db);
+            for (const Output& o : kOutputs) e->db.*o.field = (e->*o.slot).last;
             e->db.attn_mask = e->attn_mask_last;
-            e->db.attn_edge = e->attn_e_last;
-            e->db.attn_self = e->attn_s_last;
-            const int frc = engine_forward(e);
-            e->db.emb = now;
-            e->db.node_emb = nnow;
-            e->db.node_logits = lnow;
-            e->db.attn_mask = anow;
-            e->db.attn_edge = aenow;
-            e->db.attn_self = asnow;
-            ENGINE_TRY(e, frc);
+            frc = engine_forward(e);
         }
+        ENGINE_TRY(e, frc);
         he = hipStreamSynchronize(e->stream);
         if (he != hipSuccess) return EHIP_FAIL(e, "hipStreamSynchronize (exact re-run)", he);
         e->prof.collect();
@@ -1003,50 +975,66 @@ int flowgnn_set_results_buffer(flowgnn_engine* e, void* device_ptr) {
     return FLOWGNN_OK;
 }
 
+// ---- the optional outputs (kOutputs): one helper per verb; each ABI function below is its own refusals, then the helper
+static int switch_output(flowgnn_engine* e, const Output& o, int on) {
+    ENGINE_TRY(e, use_device(e));
+    e->drop_graph();  // a recorded launch sequence is that of the other setting
+    e->*o.on = on != 0;
+    return place(e, o);
+}
+
+static int not_the_last_runs(flowgnn_engine* e, const Output& o, const char* api) {
+    e->err = std::string(api) + ": the last flowgnn_run did not have " + o.noun + " on (" + o.setter + ")";
+    return FLOWGNN_ERR_STATE;
+}
+
+// flowgnn_get_*: `count` elements (the batch's graphs, or nodes) are what makes a null out_host an error, and a copy worth making
+static int get_output(flowgnn_engine* e, const Output& o, const char* api, float* out_host, long long flowgnn_engine::*count_of) {
+    if (!e || (!out_host && e->*count_of > 0)) return FLOWGNN_ERR_ARG;
+    const long long count = e->*count_of;
+    const fg::OutSlot& s = e->*o.slot;
+    if (!e->ran || (!s.last && e->G > 0) || (e->G == 0 && !is_on(e, o))) return not_the_last_runs(e, o, api);
+    int rc = flowgnn_sync(e);
+    if (rc) return rc;
+    if (e->G > 0 && count > 0) return d2h_sync(e, out_host, s.last, sizeof(float) * o.floats(e), (std::string("copy ") + o.noun).c_str());
+    return FLOWGNN_OK;
+}
+
+static int output_device(flowgnn_engine* e, const Output& o, const char* api, void** d_out) {
+    if (!e || !d_out) return FLOWGNN_ERR_ARG;
+    if (!e->ran || !(e->*o.slot).last) return not_the_last_runs(e, o, api);
+    *d_out = (e->*o.slot).last;
+    return FLOWGNN_OK;
+}
+
+// as flowgnn_set_results_buffer: no device synchronisation, the pointer matters to the launches enqueued after this call
+static int begin_set_buffer(flowgnn_engine* e) {
+    if (!e) return FLOWGNN_ERR_ARG;
+    if (!e->batch_ready) return FLOWGNN_ERR_STATE;
+    ENGINE_TRY(e, use_device(e));
+    if (e->gexec) e->drop_graph();
+    return FLOWGNN_OK;
+}
+static int set_output_buffer(flowgnn_engine* e, const Output& o, void* device_ptr) {
+    if (int rc = begin_set_buffer(e)) return rc;
+    (e->*o.slot).user = (float*)device_ptr;
+    return place(e, o);
+}
+
 int flowgnn_set_embeddings(flowgnn_engine* e, int on) {
     if (!e) return FLOWGNN_ERR_ARG;
     if (on && e->numeric_mode == FLOWGNN_NUMERIC_Q6_10) {
         e->err = "flowgnn_set_embeddings: there are no fixed-point embeddings (FLOWGNN_NUMERIC_Q6_10)";
         return FLOWGNN_ERR_UNSUPPORTED;
     }
-    ENGINE_TRY(e, use_device(e));
-    e->drop_graph();  // a recorded launch sequence is that of the other setting
-    e->emb_on = on != 0;
-    return place_embeddings(e);
+    return switch_output(e, kOutputs[OUT_EMB], on);
 }
 
-int flowgnn_get_embeddings(flowgnn_engine* e, float* out_host) {
-    if (!e || (!out_host && e->G > 0)) return FLOWGNN_ERR_ARG;
-    if (!e->ran || (!e->emb_last && e->G > 0) || (e->G == 0 && !e->emb_on)) {
-        e->err = "flowgnn_get_embeddings: the last flowgnn_run did not have embeddings on (flowgnn_set_embeddings)";
-        return FLOWGNN_ERR_STATE;
-    }
-    int rc = flowgnn_sync(e);
-    if (rc) return rc;
-    const size_t bytes = sizeof(float) * (size_t)e->G * (size_t)flowgnn_embedding_dim(e->model_id);
-    if (e->G > 0) return d2h_sync(e, out_host, e->emb_last, bytes, "copy embeddings");
-    return FLOWGNN_OK;
-}
+int flowgnn_get_embeddings(flowgnn_engine* e, float* out_host) { return get_output(e, kOutputs[OUT_EMB], "flowgnn_get_embeddings", out_host, &flowgnn_engine::G); }
 
-int flowgnn_embeddings_device(flowgnn_engine* e, void** d_emb) {
-    if (!e || !d_emb) return FLOWGNN_ERR_ARG;
-    if (!e->ran || !e->emb_last) {
-        e->err = "flowgnn_embeddings_device: the last flowgnn_run did not have embeddings on (flowgnn_set_embeddings)";
-        return FLOWGNN_ERR_STATE;
-    }
-    *d_emb = e->emb_last;
-    return FLOWGNN_OK;
-}
+int flowgnn_embeddings_device(flowgnn_engine* e, void** d_emb) { return output_device(e, kOutputs[OUT_EMB], "flowgnn_embeddings_device", d_emb); }
 
-int flowgnn_set_embeddings_buffer(flowgnn_engine* e, void* device_ptr) {
-    if (!e) return FLOWGNN_ERR_ARG;
-    if (!e->batch_ready) return FLOWGNN_ERR_STATE;
-    // as flowgnn_set_results_buffer: no device synchronisation, the pointer matters to the launches enqueued after this call
-    ENGINE_TRY(e, use_device(e));
-    if (e->gexec) e->drop_graph();
-    e->emb_user = (float*)device_ptr;
-    return place_embeddings(e);
-}
+int flowgnn_set_embeddings_buffer(flowgnn_engine* e, void* device_ptr) { return set_output_buffer(e, kOutputs[OUT_EMB], device_ptr); }
 
 int flowgnn_set_node_embeddings(flowgnn_engine* e, int on) {
     if (!e) return FLOWGNN_ERR_ARG;
@@ -1054,44 +1042,14 @@ int flowgnn_set_node_embeddings(flowgnn_engine* e, int on) {
         e->err = "flowgnn_set_node_embeddings: there are no fixed-point node embeddings (FLOWGNN_NUMERIC_Q6_10)";
         return FLOWGNN_ERR_UNSUPPORTED;
     }
-    ENGINE_TRY(e, use_device(e));
-    e->drop_graph();  // a recorded launch sequence is that of the other setting
-    e->nemb_on = on != 0;
-    return place_node_embeddings(e);
+    return switch_output(e, kOutputs[OUT_NEMB], on);
 }
 
-int flowgnn_get_node_embeddings(flowgnn_engine* e, float* out_host) {
-    if (!e || (!out_host && e->N > 0)) return FLOWGNN_ERR_ARG;
-    if (!e->ran || (!e->nemb_last && e->G > 0) || (e->G == 0 && !e->nemb_on)) {
-        e->err = "flowgnn_get_node_embeddings: the last flowgnn_run did not have node embeddings on (flowgnn_set_node_embeddings)";
-        return FLOWGNN_ERR_STATE;
-    }
-    int rc = flowgnn_sync(e);
-    if (rc) return rc;
-    const size_t bytes = sizeof(float) * (size_t)e->N * (size_t)flowgnn_embedding_dim(e->model_id);
-    if (e->G > 0 && e->N > 0) return d2h_sync(e, out_host, e->nemb_last, bytes, "copy node embeddings");
-    return FLOWGNN_OK;
-}
+int flowgnn_get_node_embeddings(flowgnn_engine* e, float* out_host) { return get_output(e, kOutputs[OUT_NEMB], "flowgnn_get_node_embeddings", out_host, &flowgnn_engine::N); }
 
-int flowgnn_node_embeddings_device(flowgnn_engine* e, void** d_rows) {
-    if (!e || !d_rows) return FLOWGNN_ERR_ARG;
-    if (!e->ran || !e->nemb_last) {
-        e->err = "flowgnn_node_embeddings_device: the last flowgnn_run did not have node embeddings on (flowgnn_set_node_embeddings)";
-        return FLOWGNN_ERR_STATE;
-    }
-    *d_rows = e->nemb_last;
-    return FLOWGNN_OK;
-}
+int flowgnn_node_embeddings_device(flowgnn_engine* e, void** d_rows) { return output_device(e, kOutputs[OUT_NEMB], "flowgnn_node_embeddings_device", d_rows); }
 
-int flowgnn_set_node_embeddings_buffer(flowgnn_engine* e, void* device_ptr) {
-    if (!e) return FLOWGNN_ERR_ARG;
-    if (!e->batch_ready) return FLOWGNN_ERR_STATE;
-    // as flowgnn_set_embeddings_buffer: no device synchronisation, the pointer matters to the launches enqueued after this call
-    ENGINE_TRY(e, use_device(e));
-    if (e->gexec) e->drop_graph();
-    e->nemb_user = (float*)device_ptr;
-    return place_node_embeddings(e);
-}
+int flowgnn_set_node_embeddings_buffer(flowgnn_engine* e, void* device_ptr) { return set_output_buffer(e, kOutputs[OUT_NEMB], device_ptr); }
 
 int flowgnn_set_node_logits(flowgnn_engine* e, int on) {
     if (!e) return FLOWGNN_ERR_ARG;
@@ -1107,44 +1065,14 @@ int flowgnn_set_node_logits(flowgnn_engine* e, int on) {
         e->err = "flowgnn_set_node_logits: the pooling is not the mean (flowgnn_set_pooling), and node logits are the terms whose mean is the logit";
         return FLOWGNN_ERR_UNSUPPORTED;
     }
-    ENGINE_TRY(e, use_device(e));
-    e->drop_graph();  // a recorded launch sequence is that of the other setting
-    e->nlog_on = on != 0;
-    return place_node_logits(e);
+    return switch_output(e, kOutputs[OUT_NLOG], on);
 }
 
-int flowgnn_get_node_logits(flowgnn_engine* e, float* out_host) {
-    if (!e || (!out_host && e->N > 0)) return FLOWGNN_ERR_ARG;
-    if (!e->ran || (!e->nlog_last && e->G > 0) || (e->G == 0 && !e->nlog_on)) {
-        e->err = "flowgnn_get_node_logits: the last flowgnn_run did not have node logits on (flowgnn_set_node_logits)";
-        return FLOWGNN_ERR_STATE;
-    }
-    int rc = flowgnn_sync(e);
-    if (rc) return rc;
-    const size_t bytes = sizeof(float) * (size_t)e->N * (size_t)e->num_tasks;
-    if (e->G > 0 && e->N > 0) return d2h_sync(e, out_host, e->nlog_last, bytes, "copy node logits");
-    return FLOWGNN_OK;
-}
+int flowgnn_get_node_logits(flowgnn_engine* e, float* out_host) { return get_output(e, kOutputs[OUT_NLOG], "flowgnn_get_node_logits", out_host, &flowgnn_engine::N); }
 
-int flowgnn_node_logits_device(flowgnn_engine* e, void** d_terms) {
-    if (!e || !d_terms) return FLOWGNN_ERR_ARG;
-    if (!e->ran || !e->nlog_last) {
-        e->err = "flowgnn_node_logits_device: the last flowgnn_run did not have node logits on (flowgnn_set_node_logits)";
-        return FLOWGNN_ERR_STATE;
-    }
-    *d_terms = e->nlog_last;
-    return FLOWGNN_OK;
-}
+int flowgnn_node_logits_device(flowgnn_engine* e, void** d_terms) { return output_device(e, kOutputs[OUT_NLOG], "flowgnn_node_logits_device", d_terms); }
 
-int flowgnn_set_node_logits_buffer(flowgnn_engine* e, void* device_ptr) {
-    if (!e) return FLOWGNN_ERR_ARG;
-    if (!e->batch_ready) return FLOWGNN_ERR_STATE;
-    // as flowgnn_set_embeddings_buffer: no device synchronisation, the pointer matters to the launches enqueued after this call
-    ENGINE_TRY(e, use_device(e));
-    if (e->gexec) e->drop_graph();
-    e->nlog_user = (float*)device_ptr;
-    return place_node_logits(e);
-}
+int flowgnn_set_node_logits_buffer(flowgnn_engine* e, void* device_ptr) { return set_output_buffer(e, kOutputs[OUT_NLOG], device_ptr); }
 
 int flowgnn_attention_shape(int model, int* layers, int* heads) {
     if (model != FLOWGNN_MODEL_GAT) {
@@ -1180,7 +1108,7 @@ int flowgnn_set_attention(flowgnn_engine* e, int layer_mask) {
 int get_attention_strided(flowgnn_engine* e, float* edge_host, size_t edge_stride, float* self_host, size_t self_stride) {
     if (!e) return FLOWGNN_ERR_ARG;
     // (the shapes are those of the mask, so a mask changed since the run is "not the last run's" too: the caller sized its arrays by it)
-    if (!e->ran || !e->attn_mask || e->attn_mask_last != e->attn_mask || (e->G > 0 && (!e->attn_e_last || !e->attn_s_last))) {
+    if (!e->ran || !e->attn_mask || e->attn_mask_last != e->attn_mask || (e->G > 0 && (!e->attn_e.last || !e->attn_s.last))) {
         e->err = "flowgnn_get_attention: the last flowgnn_run did not have attention on with this layer mask (flowgnn_set_attention)";
         return FLOWGNN_ERR_STATE;
     }
@@ -1190,8 +1118,8 @@ int get_attention_strided(flowgnn_engine* e, float* edge_host, size_t edge_strid
     const size_t n_sel = (size_t)__builtin_popcount((unsigned)e->attn_mask_last);
     const size_t le = (size_t)e->E * 4, ls = (size_t)e->N * 4;  // floats per layer
     for (size_t k = 0; k < n_sel; k++) {
-        if (edge_host && le && (rc = d2h_sync(e, edge_host + k * edge_stride, e->attn_e_last + k * le, sizeof(float) * le, "copy attention (edges)"))) return rc;
-        if (self_host && ls && (rc = d2h_sync(e, self_host + k * self_stride, e->attn_s_last + k * ls, sizeof(float) * ls, "copy attention (self)"))) return rc;
+        if (edge_host && le && (rc = d2h_sync(e, edge_host + k * edge_stride, e->attn_e.last + k * le, sizeof(float) * le, "copy attention (edges)"))) return rc;
+        if (self_host && ls && (rc = d2h_sync(e, self_host + k * self_stride, e->attn_s.last + k * ls, sizeof(float) * ls, "copy attention (self)"))) return rc;
     }
     return FLOWGNN_OK;
 }
@@ -1204,23 +1132,19 @@ int flowgnn_get_attention(flowgnn_engine* e, float* edge_host, float* self_host)
 
 int flowgnn_attention_device(flowgnn_engine* e, void** d_edge, void** d_self) {
     if (!e || (!d_edge && !d_self)) return FLOWGNN_ERR_ARG;
-    if (!e->ran || !e->attn_mask || e->attn_mask_last != e->attn_mask || !e->attn_e_last || !e->attn_s_last) {
+    if (!e->ran || !e->attn_mask || e->attn_mask_last != e->attn_mask || !e->attn_e.last || !e->attn_s.last) {
         e->err = "flowgnn_attention_device: the last flowgnn_run did not have attention on with this layer mask (flowgnn_set_attention)";
         return FLOWGNN_ERR_STATE;
     }
-    if (d_edge) *d_edge = e->attn_e_last;
-    if (d_self) *d_self = e->attn_s_last;
+    if (d_edge) *d_edge = e->attn_e.last;
+    if (d_self) *d_self = e->attn_s.last;
     return FLOWGNN_OK;
 }
 
 int flowgnn_set_attention_buffers(flowgnn_engine* e, void* d_edge, void* d_self) {
-    if (!e) return FLOWGNN_ERR_ARG;
-    if (!e->batch_ready) return FLOWGNN_ERR_STATE;
-    // as flowgnn_set_embeddings_buffer: no device synchronisation, the pointers matter to the launches enqueued after this call
-    ENGINE_TRY(e, use_device(e));
-    if (e->gexec) e->drop_graph();
-    e->attn_e_user = (float*)d_edge;
-    e->attn_s_user = (float*)d_self;
+    if (int rc = begin_set_buffer(e)) return rc;
+    e->attn_e.user = (float*)d_edge;
+    e->attn_s.user = (float*)d_self;
     return place_attention(e);
 }
 
@@ -1274,22 +1198,11 @@ int flowgnn_num_tasks(const flowgnn_engine* e) { return e ? e->num_tasks : -1; }
 
 int flowgnn_set_numeric_mode(flowgnn_engine* e, int mode) {
     if (!e) return FLOWGNN_ERR_ARG;
-    if (mode == FLOWGNN_NUMERIC_Q6_10 && e->emb_on) {
-        e->err = "flowgnn_set_numeric_mode: graph embeddings are on, and there are no fixed-point embeddings";
-        return FLOWGNN_ERR_UNSUPPORTED;
-    }
-    if (mode == FLOWGNN_NUMERIC_Q6_10 && e->nemb_on) {
-        e->err = "flowgnn_set_numeric_mode: node embeddings are on, and there are no fixed-point node embeddings";
-        return FLOWGNN_ERR_UNSUPPORTED;
-    }
-    if (mode == FLOWGNN_NUMERIC_Q6_10 && e->nlog_on) {
-        e->err = "flowgnn_set_numeric_mode: node logits are on, and there are no fixed-point node logits";
-        return FLOWGNN_ERR_UNSUPPORTED;
-    }
-    if (mode == FLOWGNN_NUMERIC_Q6_10 && e->attn_mask) {
-        e->err = "flowgnn_set_numeric_mode: attention is on, and there are no fixed-point attention coefficients";
-        return FLOWGNN_ERR_UNSUPPORTED;
-    }
+    for (const Output& o : kOutputs)
+        if (mode == FLOWGNN_NUMERIC_Q6_10 && o.no_fixed_point && is_on(e, o)) {
+            e->err = o.no_fixed_point;
+            return FLOWGNN_ERR_UNSUPPORTED;
+        }
     if (mode == FLOWGNN_NUMERIC_Q6_10 && e->pooling != FLOWGNN_POOL_MEAN) {
         e->err = "flowgnn_set_numeric_mode: the pooling is not the mean (flowgnn_set_pooling), and the fixed-point readout is the reference's mean";
         return FLOWGNN_ERR_UNSUPPORTED;
@@ -1415,19 +1328,13 @@ static int ensure_rows(flowgnn_engine* e) {
     if (e->db.h_valid || e->db.tap) return FLOWGNN_OK;
     e->model->set_keep_h(true);
     e->model->set_exact(e->force_exact);
-    float* const emb = e->db.emb;
-    float* const nemb = e->db.node_emb;
-    float* const nlog = e->db.node_logits;
-    e->db.emb = nullptr;  // a tap's pass leaves the run's embeddings as they are
-    e->db.node_emb = nullptr;
-    e->db.node_logits = nullptr;
-    const int amask = e->db.attn_mask;
-    e->db.attn_mask = 0;  // (the models read the mask alone)
-    rc = engine_forward(e);
-    e->db.emb = emb;
-    e->db.node_emb = nemb;
-    e->db.node_logits = nlog;
-    e->db.attn_mask = amask;
+    {   // a tap's pass leaves the run's outputs as they are (of the attention, the models read the mask alone)
+        KeepOutputFields keep(e->db);
+        for (const Output& o : kOutputs)
+            if (o.on) e->db.*o.field = nullptr;
+        e->db.attn_mask = 0;
+        rc = engine_forward(e);
+    }
     e->model->set_keep_h(false);
     if (rc) { e->err = fg::last_error_text(); return rc; }
     return flowgnn_sync(e);

@@ -35,6 +35,19 @@ struct GrowBuf {
         p = nullptr; cap = 0;
     }
 };
+
+// The engine-side state of ONE optional per-run output (graph embeddings, node embeddings, node logits, GAT's attention
+// coefficients of the edges and of the self edges); its switch is the engine's (*_on, attn_mask).  The rules, for all of them:
+// off by default, and the DeviceBatch pointer it feeds is null then, so every forward is the one it was; `own` is allocated when
+// first needed, to one batch's size, and outlives the batch; `user` is the caller's buffer (flowgnn_set_*_buffer), which
+// flowgnn_set_batch forgets; `last` is where the last flowgnn_run put the result (null: it ran with the output off) -- what a get
+// copies and the *_device calls return.  engine.hip: `place` and the list kOutputs.
+struct OutSlot {
+    GrowBuf own;
+    float* user = nullptr;
+    float* last = nullptr;
+    float* target(bool on) const { return on ? (user ? user : (float*)own.p) : nullptr; }
+};
 }  // namespace fg
 
 struct flowgnn_engine {
@@ -73,37 +86,18 @@ struct flowgnn_engine {
     bool has_attr = false, has_eig = false;
     fg::DeviceBatch db{};
 
-    // graph embeddings (flowgnn_set_embeddings): off by default; db.emb is null then and every forward is the one it was
-    bool emb_on = false;
     int numeric_mode = FLOWGNN_NUMERIC_F32;
     int pooling = FLOWGNN_POOL_MEAN;  // flowgnn_set_pooling: the engine's, across batches (db.pooling follows it)
     bool gin_eps_on = false;          // flowgnn_set_gin_eps: the engine's too, across batches and weight sets (db.gin_eps_on / gin_self_scale follow)
     float gin_eps[5] = {0, 0, 0, 0, 0};
-    fg::GrowBuf emb;                // the engine's own [G][dim] buffer (allocated when first needed, outlives the batch)
-    float* emb_user = nullptr;      // flowgnn_set_embeddings_buffer (reset by set_batch)
-    float* emb_last = nullptr;      // where the last flowgnn_run put them (null: it ran with embeddings off)
-    float* emb_target() const { return emb_on ? (emb_user ? emb_user : (float*)emb.p) : nullptr; }
-    // node embeddings (flowgnn_set_node_embeddings): the same rules, [N][dim]
-    bool nemb_on = false;
-    fg::GrowBuf nemb;
-    float* nemb_user = nullptr;
-    float* nemb_last = nullptr;
-    float* nemb_target() const { return nemb_on ? (nemb_user ? nemb_user : (float*)nemb.p) : nullptr; }
-    // node logits (flowgnn_set_node_logits): the same rules, [N][num_tasks]
-    bool nlog_on = false;
-    fg::GrowBuf nlog;
-    float* nlog_user = nullptr;
-    float* nlog_last = nullptr;
-    float* nlog_target() const { return nlog_on ? (nlog_user ? nlog_user : (float*)nlog.p) : nullptr; }
-    // attention coefficients (flowgnn_set_attention; GAT): the same rules for two buffers, [n_sel][E][4] and [n_sel][N][4], n_sel =
-    // popcount(attn_mask); the mask of the last run is kept beside where it put them (the shapes a get copies are that run's)
-    int attn_mask = 0;
-    fg::GrowBuf attn_e, attn_s;
-    float *attn_e_user = nullptr, *attn_s_user = nullptr;
-    float *attn_e_last = nullptr, *attn_s_last = nullptr;
-    int attn_mask_last = 0;
-    float* attn_e_target() const { return attn_mask ? (attn_e_user ? attn_e_user : (float*)attn_e.p) : nullptr; }
-    float* attn_s_target() const { return attn_mask ? (attn_s_user ? attn_s_user : (float*)attn_s.p) : nullptr; }
+
+    // the optional outputs (fg::OutSlot): graph embeddings [G][dim] (flowgnn_set_embeddings), node embeddings [N][dim]
+    // (flowgnn_set_node_embeddings), node logits [N][num_tasks] (flowgnn_set_node_logits) and, for GAT, the attention coefficients
+    // [n_sel][E][4] and [n_sel][N][4], n_sel = popcount(attn_mask) (flowgnn_set_attention): the mask is the switch of both, and the
+    // mask of the last run is kept beside where it put them (the shapes a get copies are that run's)
+    bool emb_on = false, nemb_on = false, nlog_on = false;
+    int attn_mask = 0, attn_mask_last = 0;
+    fg::OutSlot emb, nemb, nlog, attn_e, attn_s;
 
     // hipGraph replay of the launch sequence (index build + forward), opt-in (FLOWGNN_HIPGRAPH=1; 2 = batches of any size).
     // Measured on this runtime it does not pay: asynchronous launches already pipeline, and a replay of the dozen kernels

@@ -309,71 +309,61 @@ int flowgnn_group_get_results(flowgnn_group* g, float* out_host) {
     });
 }
 
-int flowgnn_group_get_embeddings(flowgnn_group* g, float* out_host) {
+// first[i]: where member i's rows (graphs: &flowgnn_engine::G, nodes: N, edges: E) start in the job, first.back(): the job's
+// (the shards are contiguous graph ranges, so member i's rows start where the rows of members 0 .. i - 1 end)
+static std::vector<size_t> first_rows(const flowgnn_group* g, long long flowgnn_engine::*rows) {
+    std::vector<size_t> first(1, 0);
+    if (g)
+        for (const flowgnn_engine* e : g->eng) first.push_back(first.back() + (size_t)(e->*rows));
+    return first;
+}
+
+// What the group's gets of the optional outputs share: the shards must be those of flowgnn_group_set_batch, `have_out` false is
+// an error when the job has rows (first.back(), as first_rows counts them), and a member with an empty shard only synchronises --
+// if `on` says it has the output on.  get(e, i): the member's own get, into its place of the job's array.
+static int group_get_output(flowgnn_group* g, const char* who, bool have_out, const std::vector<size_t>& first,
+                            const std::function<bool(const flowgnn_engine*)>& on, const std::function<int(flowgnn_engine*, size_t)>& get) {
     if (!g) return FLOWGNN_ERR_ARG;
     g->err.clear();
-    if (!g->batch_valid) return group_fail(g, FLOWGNN_ERR_STATE, "flowgnn_group_get_embeddings: no batch set by flowgnn_group_set_batch (flowgnn_group_compute and the entry points leave none)");
-    if (int rc = group_shards_intact(g, "flowgnn_group_get_embeddings")) return rc;
-    if (!out_host && g->cut.back() > 0) return group_fail(g, FLOWGNN_ERR_ARG, "flowgnn_group_get_embeddings: null output");
-    const size_t dim = (size_t)flowgnn_embedding_dim(g->model_id);
+    if (!g->batch_valid) return group_fail(g, FLOWGNN_ERR_STATE, (std::string(who) + ": no batch set by flowgnn_group_set_batch (flowgnn_group_compute and the entry points leave none)").c_str());
+    if (int rc = group_shards_intact(g, who)) return rc;
+    if (!have_out && first.back() > 0) return group_fail(g, FLOWGNN_ERR_ARG, (std::string(who) + ": null output").c_str());
     return group_each(g, [&](int i) {
         flowgnn_engine* e = g->eng[(size_t)i];
-        if (e->G == 0) return e->emb_on ? flowgnn_sync(e) : (int)FLOWGNN_ERR_STATE;
-        return flowgnn_get_embeddings(e, out_host + (size_t)g->cut[(size_t)i] * dim);
+        if (e->G == 0) return on(e) ? flowgnn_sync(e) : (int)FLOWGNN_ERR_STATE;
+        return get(e, (size_t)i);
     });
 }
 
-// [N_tot][dim] in job order: the shards are contiguous graph ranges, so member i's rows start where the rows of members 0 .. i - 1 end
+int flowgnn_group_get_embeddings(flowgnn_group* g, float* out_host) {
+    const std::vector<size_t> first = first_rows(g, &flowgnn_engine::G);
+    return group_get_output(g, "flowgnn_group_get_embeddings", out_host != nullptr, first, [](const flowgnn_engine* e) { return e->emb_on; },
+                            [&](flowgnn_engine* e, size_t i) { return flowgnn_get_embeddings(e, out_host + first[i] * (size_t)flowgnn_embedding_dim(e->model_id)); });
+}
+
+// [N_tot][dim] in job order
 int flowgnn_group_get_node_embeddings(flowgnn_group* g, float* out_host) {
-    if (!g) return FLOWGNN_ERR_ARG;
-    g->err.clear();
-    if (!g->batch_valid) return group_fail(g, FLOWGNN_ERR_STATE, "flowgnn_group_get_node_embeddings: no batch set by flowgnn_group_set_batch (flowgnn_group_compute and the entry points leave none)");
-    if (int rc = group_shards_intact(g, "flowgnn_group_get_node_embeddings")) return rc;
-    const size_t dim = (size_t)flowgnn_embedding_dim(g->model_id);
-    std::vector<size_t> first(g->eng.size() + 1, 0);
-    for (size_t i = 0; i < g->eng.size(); i++) first[i + 1] = first[i] + (size_t)g->eng[i]->N;
-    if (!out_host && first.back() > 0) return group_fail(g, FLOWGNN_ERR_ARG, "flowgnn_group_get_node_embeddings: null output");
-    return group_each(g, [&](int i) {
-        flowgnn_engine* e = g->eng[(size_t)i];
-        if (e->G == 0) return e->nemb_on ? flowgnn_sync(e) : (int)FLOWGNN_ERR_STATE;
-        return flowgnn_get_node_embeddings(e, out_host + first[(size_t)i] * dim);
-    });
+    const std::vector<size_t> first = first_rows(g, &flowgnn_engine::N);
+    return group_get_output(g, "flowgnn_group_get_node_embeddings", out_host != nullptr, first, [](const flowgnn_engine* e) { return e->nemb_on; },
+                            [&](flowgnn_engine* e, size_t i) { return flowgnn_get_node_embeddings(e, out_host + first[i] * (size_t)flowgnn_embedding_dim(e->model_id)); });
 }
 
 // [N_tot][NUM_TASK] in job order, likewise
 int flowgnn_group_get_node_logits(flowgnn_group* g, float* out_host) {
-    if (!g) return FLOWGNN_ERR_ARG;
-    g->err.clear();
-    if (!g->batch_valid) return group_fail(g, FLOWGNN_ERR_STATE, "flowgnn_group_get_node_logits: no batch set by flowgnn_group_set_batch (flowgnn_group_compute and the entry points leave none)");
-    if (int rc = group_shards_intact(g, "flowgnn_group_get_node_logits")) return rc;
-    std::vector<size_t> first(g->eng.size() + 1, 0);
-    for (size_t i = 0; i < g->eng.size(); i++) first[i + 1] = first[i] + (size_t)g->eng[i]->N;
-    if (!out_host && first.back() > 0) return group_fail(g, FLOWGNN_ERR_ARG, "flowgnn_group_get_node_logits: null output");
-    return group_each(g, [&](int i) {
-        flowgnn_engine* e = g->eng[(size_t)i];
-        if (e->G == 0) return e->nlog_on ? flowgnn_sync(e) : (int)FLOWGNN_ERR_STATE;
-        return flowgnn_get_node_logits(e, out_host + first[(size_t)i] * (size_t)e->num_tasks);
-    });
+    const std::vector<size_t> first = first_rows(g, &flowgnn_engine::N);
+    return group_get_output(g, "flowgnn_group_get_node_logits", out_host != nullptr, first, [](const flowgnn_engine* e) { return e->nlog_on; },
+                            [&](flowgnn_engine* e, size_t i) { return flowgnn_get_node_logits(e, out_host + first[i] * (size_t)e->num_tasks); });
 }
 
 // [n_sel][E_tot][4] and [n_sel][N_tot][4] in job order: per selected layer, member i's edges / nodes start where those of members
-// 0 .. i - 1 end (the shards are contiguous graph ranges; edge indices are the caller's, per graph range)
+// 0 .. i - 1 end (edge indices are the caller's, per graph range); either array may be null
 int flowgnn_group_get_attention(flowgnn_group* g, float* edge_host, float* self_host) {
-    if (!g) return FLOWGNN_ERR_ARG;
-    g->err.clear();
-    if (!g->batch_valid) return group_fail(g, FLOWGNN_ERR_STATE, "flowgnn_group_get_attention: no batch set by flowgnn_group_set_batch (flowgnn_group_compute and the entry points leave none)");
-    if (int rc = group_shards_intact(g, "flowgnn_group_get_attention")) return rc;
-    std::vector<size_t> nfirst(g->eng.size() + 1, 0), efirst(g->eng.size() + 1, 0);
-    for (size_t i = 0; i < g->eng.size(); i++) {
-        nfirst[i + 1] = nfirst[i] + (size_t)g->eng[i]->N;
-        efirst[i + 1] = efirst[i] + (size_t)g->eng[i]->E;
-    }
-    return group_each(g, [&](int i) {
-        flowgnn_engine* e = g->eng[(size_t)i];
-        if (e->G == 0) return e->attn_mask ? flowgnn_sync(e) : (int)FLOWGNN_ERR_STATE;
-        return get_attention_strided(e, edge_host ? edge_host + efirst[(size_t)i] * 4 : nullptr, efirst.back() * 4,
-                                     self_host ? self_host + nfirst[(size_t)i] * 4 : nullptr, nfirst.back() * 4);
-    });
+    const std::vector<size_t> nfirst = first_rows(g, &flowgnn_engine::N), efirst = first_rows(g, &flowgnn_engine::E);
+    return group_get_output(g, "flowgnn_group_get_attention", true, nfirst, [](const flowgnn_engine* e) { return e->attn_mask != 0; },
+                            [&](flowgnn_engine* e, size_t i) {
+                                return get_attention_strided(e, edge_host ? edge_host + efirst[i] * 4 : nullptr, efirst.back() * 4,
+                                                             self_host ? self_host + nfirst[i] * 4 : nullptr, nfirst.back() * 4);
+                            });
 }
 
 // One call for a batch that lives in HOST memory: the job is cut into size x chunks_per_engine ranges (same rule), and engine i

@@ -363,6 +363,16 @@ class Engine:
         self._check(self.lib.flowgnn_set_num_tasks(self._h, int(num_tasks)), "flowgnn_set_num_tasks")
         self.num_tasks = int(num_tasks)
 
+    def _device_ptrs(self, fn: str, count: int = 1):
+        """`count` device addresses (0 = NULL) out of the C function `fn`(engine, void**, ...)."""
+        ps = [C.c_void_p() for _ in range(count)]
+        self._check(getattr(self.lib, fn)(self._h, *(C.byref(p) for p in ps)), fn)
+        return tuple(int(p.value or 0) for p in ps)
+
+    def _set_buffers(self, fn: str, *device_ptrs):
+        """Device addresses into the C function `fn`(engine, void*, ...); None / 0 goes as NULL."""
+        self._check(getattr(self.lib, fn)(self._h, *(C.c_void_p(p) if p else None for p in device_ptrs)), fn)
+
     def results_device_ptr(self) -> int:
         p = C.c_void_p()
         self._check(self.lib.flowgnn_results_device(self._h, C.byref(p)), "flowgnn_results_device")
@@ -405,14 +415,11 @@ class Engine:
         return out
 
     def embeddings_device_ptr(self) -> int:
-        p = C.c_void_p()
-        self._check(self.lib.flowgnn_embeddings_device(self._h, C.byref(p)), "flowgnn_embeddings_device")
-        return int(p.value or 0)
+        return self._device_ptrs("flowgnn_embeddings_device")[0]
 
     def set_embeddings_buffer(self, device_ptr: Optional[int]):
         """Caller-owned device buffer of >= G * embedding_dim floats for the embeddings; None / 0 restores the engine's own."""
-        self._check(self.lib.flowgnn_set_embeddings_buffer(self._h, C.c_void_p(device_ptr) if device_ptr else None),
-                    "flowgnn_set_embeddings_buffer")
+        self._set_buffers("flowgnn_set_embeddings_buffer", device_ptr)
 
     # ---- node embeddings (flowgnn.h: flowgnn_set_node_embeddings)
     def set_node_embeddings(self, on: bool = True):
@@ -426,14 +433,11 @@ class Engine:
         return out
 
     def node_embeddings_device_ptr(self) -> int:
-        p = C.c_void_p()
-        self._check(self.lib.flowgnn_node_embeddings_device(self._h, C.byref(p)), "flowgnn_node_embeddings_device")
-        return int(p.value or 0)
+        return self._device_ptrs("flowgnn_node_embeddings_device")[0]
 
     def set_node_embeddings_buffer(self, device_ptr: Optional[int]):
         """Caller-owned device buffer of >= N * embedding_dim floats for the node embeddings; None / 0 restores the engine's own."""
-        self._check(self.lib.flowgnn_set_node_embeddings_buffer(self._h, C.c_void_p(device_ptr) if device_ptr else None),
-                    "flowgnn_set_node_embeddings_buffer")
+        self._set_buffers("flowgnn_set_node_embeddings_buffer", device_ptr)
 
     # ---- node logits (flowgnn.h: flowgnn_set_node_logits; GIN, GIN-VN, GCN, GAT)
     def set_node_logits(self, on: bool = True):
@@ -448,14 +452,11 @@ class Engine:
         return out
 
     def node_logits_device_ptr(self) -> int:
-        p = C.c_void_p()
-        self._check(self.lib.flowgnn_node_logits_device(self._h, C.byref(p)), "flowgnn_node_logits_device")
-        return int(p.value or 0)
+        return self._device_ptrs("flowgnn_node_logits_device")[0]
 
     def set_node_logits_buffer(self, device_ptr: Optional[int]):
         """Caller-owned device buffer of >= N * num_tasks floats for the node logits; None / 0 restores the engine's own."""
-        self._check(self.lib.flowgnn_set_node_logits_buffer(self._h, C.c_void_p(device_ptr) if device_ptr else None),
-                    "flowgnn_set_node_logits_buffer")
+        self._set_buffers("flowgnn_set_node_logits_buffer", device_ptr)
 
     # ---- attention coefficients (flowgnn.h: flowgnn_set_attention; GAT)
     def set_attention(self, layers="last"):
@@ -476,14 +477,11 @@ class Engine:
 
     def attention_device_ptrs(self):
         """(edge, self) device addresses of the last run's attention coefficients (flowgnn.h: flowgnn_attention_device)."""
-        a, b = C.c_void_p(), C.c_void_p()
-        self._check(self.lib.flowgnn_attention_device(self._h, C.byref(a), C.byref(b)), "flowgnn_attention_device")
-        return int(a.value or 0), int(b.value or 0)
+        return self._device_ptrs("flowgnn_attention_device", 2)
 
     def set_attention_buffers(self, edge_ptr: Optional[int], self_ptr: Optional[int]):
         """Caller-owned device buffers of >= n_sel * E * 4 and n_sel * N * 4 floats; None / 0 restores the engine's own (each)."""
-        self._check(self.lib.flowgnn_set_attention_buffers(self._h, C.c_void_p(edge_ptr) if edge_ptr else None,
-                                                           C.c_void_p(self_ptr) if self_ptr else None), "flowgnn_set_attention_buffers")
+        self._set_buffers("flowgnn_set_attention_buffers", edge_ptr, self_ptr)
 
     # ---- taps
     def set_numeric_mode(self, mode: str = "f32"):
