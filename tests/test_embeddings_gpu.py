@@ -230,26 +230,9 @@ def test_gin_batch_below_the_fill_threshold(oracle, gin_weights):
 
 
 def f16_unfolded(batch, w):
-    """tests/f16_ref.gin_forward(fold=False, rnd="rne") restated to return the pooled h_5 beside the logits (single task)."""
-    r = f16_ref.rounder("rne")
-    nemb, eemb = f64(w["node_embedding_weight"]), f64(w["edge_embedding_weight"])
-    w1, b1, w2, b2 = f64(w["node_mlp_1_weights"]), f64(w["node_mlp_1_bias"]), f64(w["node_mlp_2_weights"]), f64(w["node_mlp_2_bias"])
-    pw, pb = f64(w["graph_pred_weights"]).reshape(-1, 100), f64(w["graph_pred_bias"]).reshape(-1)
-    N = batch.total_nodes
-    ge = batch.global_edges()
-    u, v = ge[:, 0], ge[:, 1]
-    h = nemb[batch.node_feature.astype(np.int64) + ND_OFF[None, :]].sum(axis=1)
-    for l in range(5):
-        ee = eemb[l][batch.edge_attr.astype(np.int64) + ED_OFF[None, :]].sum(axis=1)
-        m = np.zeros((N, 100))
-        np.add.at(m, v, np.maximum(h[u] + ee, 0.0))
-        s1, s2 = f16_ref.pow2_scale(w1[l]), f16_ref.pow2_scale(w2[l])
-        W1, W2 = r(w1[l] * s1) / s1, r(w2[l] * s2) / s2
-        hid = r(np.maximum(r(m + h) @ W1.T + b1[l], 0.0) * s1) / s1
-        hn = hid @ W2.T + b2[l]
-        h = np.maximum(hn, 0.0) if l != 4 else hn
-    emb = pooled(h, batch)
-    return emb @ pw[0] + pb[0], emb
+    """tests/f16_ref.gin_forward(fold=False, rnd="rne"): the logits and the pooled h_5 (single task)."""
+    o = f16_ref.gin_forward(batch, w, fold=False, rnd="rne", outputs=("logits", "pooled"))
+    return o["logits"], o["pooled"]
 
 
 def test_gin_f16_mode(oracle, gin_weights):

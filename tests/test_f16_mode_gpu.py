@@ -21,10 +21,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOST = os.path.join(ROOT, "flowgnn_amd", "host")
 
 
-def probe_weights(seed=5, num_tasks=1):
+def probe_weights(seed=5, num_tasks=1, tight=False):
     """Dyadic weights of few significant bits: all positive MLP weights in {1/4, 1/2} (two per row), embeddings and biases on a
     2^-12 grid with 9..11 significant bits, a readout head of four entries in {+-1, +-1/2}.  Activations then carry bits below
-    their f16 ulp (the roundings matter) while every fp32 sum stays exact (checked per input by f16_ref)."""
+    their f16 ulp (the roundings matter) while every fp32 sum stays exact (checked per input by f16_ref).
+    tight (tests/f16_probe.py): the MLP weights times 1 - 2^-12 + 2^-20 -- after the kernels' power-of-two scale each lies just above
+    the midpoint below a power of two, so rounded to nearest it IS the few-bit value of the plain set (every sum stays exact), while
+    rounded toward zero or left unrounded it is not: the rounding of the weights shows, and through W2 that of the folded u = W2^T w."""
     rng = np.random.default_rng(seed)
     q = 2.0 ** -12
     f = lambda a: np.asarray(a, np.float32)
@@ -38,23 +41,32 @@ def probe_weights(seed=5, num_tasks=1):
     pw = np.zeros((num_tasks, 100))
     for t in range(num_tasks):
         pw[t, rng.choice(100, 4, replace=False)] = [1.0, -1.0, 0.5, -0.5]
+    t = (1.0 - 2.0 ** -12 + 2.0 ** -20) if tight else 1.0
     return {
         "node_embedding_weight": f(rng.integers(2 ** 8, 2 ** 9, (173, 100)) * q),
         "edge_embedding_weight": f(rng.integers(-2 ** 7, 2 ** 7, (5, 13, 100)) * q),
-        "node_mlp_1_weights": f(np.stack([sparse(200, 100, [0.25, 0.5]) for _ in range(5)])),
+        "node_mlp_1_weights": f(np.stack([sparse(200, 100, [0.25, 0.5]) for _ in range(5)]) * t),
         "node_mlp_1_bias": f(rng.integers(2 ** 10, 2 ** 11, (5, 200)) * q),
-        "node_mlp_2_weights": f(np.stack([sparse(100, 200, [0.25]) for _ in range(5)])),
+        "node_mlp_2_weights": f(np.stack([sparse(100, 200, [0.25]) for _ in range(5)]) * t),
         "node_mlp_2_bias": f(rng.integers(2 ** 10, 2 ** 11, (5, 100)) * q),
         "graph_pred_weights": f(pw),
         "graph_pred_bias": f(rng.integers(1, 2 ** 10, (num_tasks,)) * q),
     }
 
 
-def probe_batch(vn):
-    """Molecules whose node count (with GIN-VN's virtual node) is a power of two: the mean pool's division is then exact too."""
+def probe_batch(vn, extra=False):
+    """Molecules whose node count (with GIN-VN's virtual node) is a power of two: the mean pool's division is then exact too.
+    extra (tests/f16_probe.py): a one-node graph in front, one behind, and a four-node graph without edges (three nodes under its
+    virtual node) in the middle -- 1, 2 and 4 are powers of two as well."""
     big = gp.synth_molhiv_batch(1500, seed=11)
     sizes = {7, 15} if vn else {8, 16}
-    b = gp.concat_batches([big.slice(g, g + 1) for g in range(big.num_graphs) if int(big.nums_of_nodes[g]) in sizes])
+    parts = [big.slice(g, g + 1) for g in range(big.num_graphs) if int(big.nums_of_nodes[g]) in sizes]
+    if extra:
+        lone = lambda n, seed: gp.GraphBatch(np.array([n], np.int32), np.array([0], np.int32), big.node_feature[seed:seed + n].copy(),
+                                             np.zeros((0, 2), np.int32), np.zeros((0, 3), np.int32))
+        half = len(parts) // 2
+        parts = [lone(1, 3)] + parts[:half] + [lone(3 if vn else 4, 40)] + parts[half:] + [lone(1, 90)]
+    b = gp.concat_batches(parts)
     return gp.add_virtual_nodes(b) if vn else b
 
 
