@@ -851,10 +851,17 @@ public:
                 launch_gin_tile_build(tb, t_row, t_graph, reinterpret_cast<uint8_t*>(perm_.p), n_tiles, virtual_node_, resident_order_, s);
             }
             ProfScope p(prof, "gin_resident", s);  // the whole model
-            if (int rc = launch_gin_resident(nullptr, nullptr, nullptr, nullptr, nullptr, d_ecomb_res_, rsplit(), d_pw_, d_pb_, t_row, t_graph,
-                                reinterpret_cast<uint8_t*>(perm_.p), db.b.node_off, db.out, n_tiles,
-                                db.range_flag, s, virtual_node_, head(), resident_order_, resident_prof_, &tb, 1, f16_, nullptr, db.node_logits, db.pooling, eps_s))
-                return rc;
+            GinResidentLaunch a = resident_launch(db);  // (no h0, no CSR: the tile loader reads the caller's arrays)
+            a.tile_row = t_row;
+            a.tile_graph = t_graph;
+            a.tile_desc = reinterpret_cast<uint8_t*>(perm_.p);
+            a.n_tiles = n_tiles;
+            a.out = db.out;
+            a.head_u = head();
+            a.prof = resident_prof_;
+            a.tb = &tb;
+            a.pooling = db.pooling;
+            if (int rc = launch_gin_resident(a, s)) return rc;
             db.final_h = 0;
             db.h_valid = false;
             h0_in_hbm_ = false;  // the tile loader computed h_0 on chip
@@ -879,9 +886,21 @@ public:
             }
             if (gt.n_big > 0) {  // graphs of 129..256 nodes (or 641..1280 edges): one full tile each on the eight-wave resident kernel
                 ProfScope p(prof, "gin_resident_big", s);
-                launch_gin_resident(db.h[0], nullptr, db.csr.row_ptr, db.csr.src, db.csr.ecode, d_ecomb_res_, d_rsplit_, d_pw_, d_pb_, gt.big_row,
-                                    gt.big_graph, reinterpret_cast<uint8_t*>(perm_.p + sub_words), db.b.node_off, db.out, gt.n_big,
-                                    db.range_flag, s, false, d_head_, resident_order_, false, nullptr, 2);
+                GinResidentLaunch a = resident_launch(db);
+                a.chunks_all = d_rsplit_;  // (use_pingpong: f32 mode, no virtual node -- and no node logits, no eps)
+                a.hubs = false;
+                a.h0 = db.h[0];
+                a.row_ptr = db.csr.row_ptr;
+                a.src = db.csr.src;
+                a.ecode = db.csr.ecode;
+                a.tile_row = gt.big_row;
+                a.tile_graph = gt.big_graph;
+                a.tstride = 2;  // (start, end) pair lists
+                a.tile_desc = reinterpret_cast<uint8_t*>(perm_.p + sub_words);
+                a.n_tiles = gt.n_big;
+                a.out = db.out;
+                a.head_u = d_head_;
+                launch_gin_resident(a, s);
             }
             db.final_h = 0;
             db.h_valid = false;
@@ -909,12 +928,22 @@ public:
             }
             {
                 ProfScope p(prof, "gin_resident", s);
-                if (int rc = launch_gin_resident(db.h[0], rows ? h5 : nullptr, db.csr.row_ptr, db.csr.src, db.csr.ecode, d_ecomb_res_, rsplit(), d_pw_, d_pb_,
-                                    db.gtiles.row_start, db.gtiles.graph_start, reinterpret_cast<uint8_t*>(perm_.p), db.b.node_off,
-                                    (multi || (rows && !mean_pool(db))) ? nullptr : db.out, db.gtiles.n_tiles, db.range_flag, s, virtual_node_,
-                                    (!rows && fold_readout_ && head_fold_) ? head() : nullptr, resident_order_, resident_prof_, nullptr, 1, f16_, pool_emb,
-                                    db.node_logits, rows ? 0 : db.pooling, eps_s))
-                    return rc;
+                GinResidentLaunch a = resident_launch(db);
+                a.h0 = db.h[0];
+                a.hout = rows ? h5 : nullptr;
+                a.row_ptr = db.csr.row_ptr;
+                a.src = db.csr.src;
+                a.ecode = db.csr.ecode;
+                a.tile_row = db.gtiles.row_start;
+                a.tile_graph = db.gtiles.graph_start;
+                a.tile_desc = reinterpret_cast<uint8_t*>(perm_.p);
+                a.n_tiles = db.gtiles.n_tiles;
+                a.out = (multi || (rows && !mean_pool(db))) ? nullptr : db.out;
+                a.head_u = (!rows && fold_readout_ && head_fold_) ? head() : nullptr;
+                a.prof = resident_prof_;
+                a.emb = pool_emb;
+                a.pooling = rows ? 0 : db.pooling;
+                if (int rc = launch_gin_resident(a, s)) return rc;
             }
             db.final_h = rows ? 1 : 0;
             db.h_valid = rows && !db.node_emb;
@@ -939,9 +968,22 @@ public:
                 // leaves the kernel (db.scratch as float[n]); the rows are written only for the flowgnn_get_h tap
                 // (the maximum un-folds it: W . max is not a maximum of per-node scores; the sum keeps the fold)
                 const bool fold = l == GIN_L - 1 && fold_readout_ && !keep_h_ && !multi && !db.emb && !db.node_emb && db.pooling != POOL_OP_MAX;
-                launch_gin_layer_split(db.h[cur], fold ? db.scratch : hn, db.csr.row_ptr, db.csr.src, db.csr.ecode,
-                                       layer_dev(l).ecomb, (f16_ ? d_split16_ : d_split_) + (size_t)l * GS_LAYER_BYTES, n, db.b.e_tot,
-                                       l != GIN_L - 1, db.range_flag, split_nt_, s, fold ? d_pw_ : nullptr, f16_, eps_s ? eps_s + l : nullptr);
+                GinLayerLaunch a;
+                a.h = db.h[cur];
+                a.hout = fold ? db.scratch : hn;
+                a.row_ptr = db.csr.row_ptr;
+                a.src = db.csr.src;
+                a.ecode = db.csr.ecode;
+                a.ecomb = layer_dev(l).ecomb;
+                a.chunks = (f16_ ? d_split16_ : d_split_) + (size_t)l * GS_LAYER_BYTES;
+                a.n_tot = n;
+                a.relu_out = l != GIN_L - 1;
+                a.range_flag = db.range_flag;
+                a.variant = split_nt_;
+                a.pool_w = fold ? d_pw_ : nullptr;
+                a.f16 = f16_;
+                a.self_s = eps_s ? eps_s + l : nullptr;
+                launch_gin_layer_split(a, s);
                 if (fold) {
                     folded = true;
                     break;
@@ -1076,6 +1118,22 @@ private:
     // the weight streams of the numeric mode: FLOWGNN_NUMERIC_F16 runs the single-product instances of the split kernels on their own
     // streams (the exact re-run and the options that select non-split kernels -- gin_mfma 32, gin_unfused 1 -- read neither)
     const uint8_t* rsplit() const { return f16_ ? d_rsplit16_ : d_rsplit_; }
+    // what every launch_gin_resident call takes from the model and the batch; the tiles, the front end and the outputs are the call site's
+    GinResidentLaunch resident_launch(const DeviceBatch& db) const {
+        GinResidentLaunch a;
+        a.ecomb_all = d_ecomb_res_;
+        a.chunks_all = rsplit();
+        a.pool_w = d_pw_;
+        a.pool_b = d_pb_;
+        a.node_off = db.b.node_off;
+        a.range_flag = db.range_flag;
+        a.hubs = virtual_node_;
+        a.col_order = resident_order_;
+        a.f16 = f16_;
+        a.node_logits = db.node_logits;
+        a.self_scale = db.gin_eps_on ? db.gin_self_scale : nullptr;  // s_l = 1 + eps[l], or null: every launch as it always was
+        return a;
+    }
     const float* head() const { return f16_ ? d_head16_ : d_head_; }
     void free_all() {
         float** ptrs[] = {&d_chunks_, &d_nemb_, &d_pw_, &d_pb_, &d_ecomb_, &d_ecomb_res_, &d_w1f_, &d_w1tail_, &d_b1p_, &d_w2f_, &d_b2p_};

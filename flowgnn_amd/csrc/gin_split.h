@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include "common.h"
+#include "gin_resident_launch.h"
 
 #include <cstddef>
 #include <cstdint>
@@ -25,20 +26,29 @@ constexpr size_t GS_LAYER_BYTES = (size_t)GS_STEPS * GS_CHUNK_STRIDE;
 // even, lo halves 0, the fp32 K-tail fragments rounded the same way
 void gin_split_pack_layer(const float* w1, const float* b1, const float* w2, const float* b2, uint8_t* out, bool f16 = false);
 
-// variant (FLOWGNN_GIN_SPLIT_NT): 4 = eight-wave workgroups of 128 nodes (default), 1 / 2 = four waves x 1 / 2 node tiles
-// pool_w != null (last layer, readout folded in): hout is float[n_tot] and receives h'[v] . pool_w instead of the rows
 // one GIN layer: hout = MLP(h[v] + sum_e relu(h[src_e] + ecomb[code_e])); *range_flag |= 1 if an operand left the
 // range in which the split is fp32-accurate (the caller then repeats the forward pass on the fp32 MFMA kernel)
-// f16 = true: the single-product instance (FLOWGNN_NUMERIC_F16; chunks packed with f16 = true)
-void launch_gin_layer_split(const float* h, float* hout, const int* row_ptr, const int* src, const uint8_t* ecode,
-                            const float* ecomb, const uint8_t* chunks, int n_tot, int e_tot, int relu_out, int* range_flag,
-                            int variant, hipStream_t s, const float* pool_w = nullptr, bool f16 = false,
-                            const float* self_s = nullptr /* flowgnn_set_gin_eps: the layer's s_l = 1 + eps[l] (host); the eps instance */);
+struct GinLayerLaunch {
+    const float* h = nullptr;
+    float* hout = nullptr;
+    const int* row_ptr = nullptr;
+    const int* src = nullptr;
+    const uint8_t* ecode = nullptr;
+    const float* ecomb = nullptr;
+    const uint8_t* chunks = nullptr;
+    int n_tot = 0;
+    int relu_out = 0;
+    int* range_flag = nullptr;
+    int variant = 4;  // FLOWGNN_GIN_SPLIT_NT: 4 = eight-wave workgroups of 128 nodes (default), 1 / 2 = four waves x 1 / 2 node tiles
+    const float* pool_w = nullptr;  // non-null (last layer, readout folded in): hout is float[n_tot] and receives h'[v] . pool_w instead of the rows
+    bool f16 = false;               // the single-product instance (FLOWGNN_NUMERIC_F16; chunks packed with f16 = true)
+    const float* self_s = nullptr;  // flowgnn_set_gin_eps: the layer's s_l = 1 + eps[l] (host); the eps instance
+};
+void launch_gin_layer_split(const GinLayerLaunch& a, hipStream_t s);
 
 // Graph-resident form (gin_split.hip, gin_resident_kernel): all five layers + readout in one launch; a persistent workgroup
 // keeps a tile of whole graphs (GraphTiles: <= GIN_RESIDENT_ROWS rows, <= GIN_RESIDENT_EDGES in-edges) in LDS across the layers.
-// h0 = atom-encoder output [N][100]; ecomb_all [5][60][100]; chunks_all = 5 x gin_resident_layer_bytes(); hout (nullable): h_5 rows for
-// the flowgnn_get_h tap; out [G] receives the logits.
+// Its arguments: GinResidentLaunch (gin_resident_launch.h).
 // weight stream of the resident kernel (its own chunk format: gin_split.hip "GR chunks"); chunks_all = 5 x gin_resident_layer_bytes()
 size_t gin_resident_layer_bytes();
 // f16 = true: the single-product stream (FLOWGNN_NUMERIC_F16): hi halves rounded to nearest even, every lo half (packed K tails included) 0
@@ -82,19 +92,9 @@ void gin_resident_pack_enc_table(const float* node_embedding /* [173][100] */, f
 // the one-pass front end: descriptors + encoder row numbers of every tile from the caller's arrays (then launch_gin_resident with tb)
 void launch_gin_tile_build(const GinTileBuild& tb, const int* tile_row, const int* tile_graph, uint8_t* tile_desc, int n_tiles, bool hubs,
                            int col_order, hipStream_t s);
-// Returns 0, or FLOWGNN_ERR_UNSUPPORTED (nothing launched, fg::last_error_text says why) for a `pooling` the arguments leave no instance for.
-int launch_gin_resident(const float* h0, float* hout, const int* row_ptr, const int* src, const uint8_t* ecode, const float* ecomb_all,
-                         const uint8_t* chunks_all, const float* pool_w, const float* pool_b, const int* tile_row, const int* tile_graph,
-                         uint8_t* tile_desc /* scratch, n_tiles x GIN_RESIDENT_DESC_BYTES */, const int* node_off, float* out, int n_tiles,
-                         int* range_flag, hipStream_t s, bool hubs = false, const float* head_u = nullptr, int col_order = 0, bool prof = false,
-                         const GinTileBuild* tb = nullptr, int tstride = 1, bool f16 = false /* single-product instances, FLOWGNN_NUMERIC_F16 */,
-                         float* emb = nullptr /* [G][100]: the per-graph mean of the h_5 rows, pooled inside the un-folded kernel (out [G] required) */,
-                         float* node_logits = nullptr /* [N]: every node's term of the folded readout, caller order (folded forms only: head_u, out, no hout) */,
-                         int pooling = 0 /* FLOWGNN_POOL_*.  1 (sum): the folded forms' instances whose readout leaves the division out -- the caller
-                                            passes it only with head_u, out and no hout / emb / node_logits.  2 (max): with emb, the pooling instance
-                                            that leaves the per-column maxima of h_5 there and writes no logit -- the caller applies the head to emb */,
-                         const float* self_scale = nullptr /* flowgnn_set_gin_eps: s_l = 1 + eps[l] of the five layers (host).  The eps instances
-                                            (gin_resident_eps_kernel): folded forms only, pooling 0, no hout / emb / node_logits */);
+// Returns 0, or FLOWGNN_ERR_UNSUPPORTED (nothing launched, fg::last_error_text says why) for arguments that leave no instance
+// (gin_resident_launch.h: GinResidentLaunch and gin_resident_pick).
+int launch_gin_resident(const GinResidentLaunch& a, hipStream_t s);
 // head_u for launch_gin_resident (GIN_RESIDENT_HEAD_FLOATS floats): the single-task readout folded through the LAST layer's second
 // linear layer -- u = W2^T w_pred divided by the first layer's power-of-two weight scale, padded to 208, then c = b2 . w_pred
 constexpr int GIN_RESIDENT_HEAD_FLOATS = 209;

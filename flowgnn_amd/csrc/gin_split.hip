@@ -29,8 +29,8 @@
 //   (7 output tiles x 3 = 21 MFMAs per node tile).
 //
 // Single-product instances (FLOWGNN_NUMERIC_F16): gin_split_f16.hip compiles this file once more with GS_SINGLE_PRODUCT = 1 -- the
-// same kernels under their own names (gin_layer_split_f16_kernel, gin_resident_f16_kernel), with GS_F16 = true, behind the launchers'
-// f16 argument.  Everything else (tile builders, weight packing, the launchers themselves) exists in this file's own translation unit only.
+// same kernels under their own names (gin_layer_split_f16_kernel, gin_resident_f16_kernel), with GS_F16 = true, behind the f16 field
+// of the launchers' argument structs.  Everything else (tile builders, weight packing, the launchers themselves) exists in this file's own translation unit only.
 #include "gin_split.h"
 
 #include <cmath>
@@ -82,6 +82,31 @@
 #endif
 
 namespace fg {
+
+// What a launcher of one translation unit gets from launch_gin_resident: the resident kernels' shared arguments (h0 .. lrow, in the
+// kernels' order), the template arguments it picks the kernel by, and the one trailing argument its instance takes.
+struct GrKernelLaunch {
+    int grid;
+    const float* h0; float* hout; const float* ecomb_all; const uint8_t* chunks_all; const float* pool_w; const float* pool_b;
+    const int* tile_row; const int* tile_graph; const uint8_t* tile_desc; const int* node_off; float* out; int n_tiles; int* range_flag;
+    unsigned long long* prof_out; const float* head_u; const uint32_t* eidx; const float4* etab; int tstride; const int* list; const int* lrow;
+    bool prof, hubs, fold, enc, f16;  // (prof, fold: the default instances alone; f16 there: which translation unit)
+    float* emb;               // pool, poolmax
+    float* node_logits;       // nlogit
+    GinSelfScale self_scale;  // eps
+};
+// one per translation unit (gin_split.hip, then gin_split_<name>.hip): every template form of its resident kernel the launcher can pick
+void gin_resident_default_dispatch(const GrKernelLaunch& k, hipStream_t s);
+void gin_resident_f16_dispatch(const GrKernelLaunch& k, hipStream_t s);
+void gin_resident_pool_dispatch(const GrKernelLaunch& k, hipStream_t s);     // h_5 pooled into emb [G][100]: un-folded, rows from HBM
+void gin_resident_poolmax_dispatch(const GrKernelLaunch& k, hipStream_t s);  // the same with the per-column maximum (out = null: the head follows from emb)
+void gin_resident_poolsum_dispatch(const GrKernelLaunch& k, hipStream_t s);  // folded, the readout the sum of the graph's terms
+void gin_resident_eps_dispatch(const GrKernelLaunch& k, hipStream_t s);      // folded, s_l = 1 + eps[l] on the self term (flowgnn_set_gin_eps)
+void gin_resident_nlogit_dispatch(const GrKernelLaunch& k, hipStream_t s);   // folded, the per-node readout terms stored into node_logits [N]
+// the per-layer kernel's three block shapes: gin_split.hip, gin_split_f16.hip, gin_split_eps.hip (both numeric modes, s_l as the last argument)
+void launch_split_nt(const GinLayerLaunch& a, hipStream_t s);
+void launch_gin_layer_split_f16(const GinLayerLaunch& a, hipStream_t s);
+void launch_gin_layer_split_eps(const GinLayerLaunch& a, hipStream_t s);
 
 namespace {
 
@@ -2009,49 +2034,6 @@ __global__ __launch_bounds__(GR_WAVES * 64, 2) void gin_resident_kernel(const fl
 #include "dev/gin_pp_device.inc"  // gin_pp_kernel: the ping-pong form, measured slower -- development builds only
 #endif
 
-#if !GS_POOL_TU && !GS_NLOGIT_TU && !GS_POOLSUM_TU && !GS_EPS_TU
-// this translation unit's per-layer kernels (GS_F16: which instance)
-void launch_split_nt(const float* h, float* hout, const int* row_ptr, const int* src, const uint8_t* ecode, const float* ecomb,
-                     const uint8_t* chunks, int n_tot, int relu_out, int* range_flag, int nt, hipStream_t s, const float* pool_w) {
-    if (nt == 4) {  // 8 waves, 128 nodes per workgroup, 2 workgroups per CU
-        const int blocks = (int)ceil_div_ll(n_tot, 128);
-        gin_layer_split_kernel<1, 8><<<blocks, 512, 0, s>>>(h, hout, row_ptr, src, ecode, ecomb, chunks, n_tot, relu_out, range_flag, pool_w);
-        return;
-    }
-    if (nt == 2) {
-        const int blocks = (int)ceil_div_ll(n_tot, 128);
-        gin_layer_split_kernel<2, 4><<<blocks, 256, 0, s>>>(h, hout, row_ptr, src, ecode, ecomb, chunks, n_tot, relu_out, range_flag, pool_w);
-    } else {
-        const int blocks = (int)ceil_div_ll(n_tot, 64);
-        gin_layer_split_kernel<1, 4><<<blocks, 256, 0, s>>>(h, hout, row_ptr, src, ecode, ecomb, chunks, n_tot, relu_out, range_flag, pool_w);
-    }
-}
-
-// this translation unit's resident kernels (GS_F16: which instance), every PROF / HUBS / FOLD / ENC form the launcher can pick
-void gr_dispatch(bool prof, bool hubs, bool fold, bool enc, int grid, hipStream_t s, const float* h0, float* hout, const float* ecomb_all,
-                 const uint8_t* chunks_all, const float* pool_w, const float* pool_b, const int* tile_row, const int* tile_graph,
-                 const uint8_t* tile_desc, const int* node_off, float* out, int n_tiles, int* range_flag, unsigned long long* d,
-                 const float* head_u, const uint32_t* eidx, const float4* etab, int tstride, const int* list, const int* lrow) {
-#define GR_LAUNCH(P, H, F, E)                                                                                                        \
-    gin_resident_kernel<P, H, F, E><<<grid, GR_WAVES * 64, 0, s>>>(h0, hout, ecomb_all, chunks_all, pool_w, pool_b, tile_row, tile_graph, \
-                                                                   tile_desc, node_off, out, n_tiles, range_flag, d, head_u, eidx, etab, tstride, \
-                                                                   list, lrow)
-#define GR_LAUNCH_FE(P, H)                                    \
-    do {                                                      \
-        if (enc) GR_LAUNCH(P, H, true, true);                 \
-        else if (fold) GR_LAUNCH(P, H, true, false);          \
-        else GR_LAUNCH(P, H, false, false);                   \
-    } while (0)
-    if (prof) {
-        if (hubs) GR_LAUNCH_FE(true, true); else GR_LAUNCH_FE(true, false);
-    } else {
-        if (hubs) GR_LAUNCH_FE(false, true); else GR_LAUNCH_FE(false, false);
-    }
-#undef GR_LAUNCH_FE
-#undef GR_LAUNCH
-}
-#endif  // !GS_POOL_TU && !GS_NLOGIT_TU && !GS_POOLSUM_TU && !GS_EPS_TU
-
 #if !GS_SINGLE_PRODUCT
 inline float pow2_scale(const float* w, size_t n) {
     float m = 0.0f;
@@ -2071,142 +2053,100 @@ inline void put_split(uint8_t* frag, int lane, int e, float v, bool f16 = false)
 #endif
 }  // namespace
 
-#if GS_POOL_TU
-#if GS_POOL_MAX
-#define gin_resident_pool_dispatch gin_resident_poolmax_dispatch
-#endif
-void gin_resident_pool_dispatch(bool hubs, bool f16, int grid, hipStream_t s, const float* h0, const float* ecomb_all, const uint8_t* chunks_all,
-                                const float* pool_w, const float* pool_b, const int* tile_row, const int* tile_graph, const uint8_t* tile_desc,
-                                const int* node_off, float* out, int n_tiles, int* range_flag, int tstride, float* emb) {
-#define GR_LAUNCH_POOL(H, F)                                                                                                              \
-    gin_resident_kernel<H, F><<<grid, GR_WAVES * 64, 0, s>>>(h0, nullptr, ecomb_all, chunks_all, pool_w, pool_b, tile_row, tile_graph, tile_desc, \
-                                                             node_off, out, n_tiles, range_flag, nullptr, nullptr, nullptr, nullptr, tstride,   \
-                                                             nullptr, nullptr, emb)
-    if (f16) { if (hubs) GR_LAUNCH_POOL(true, true); else GR_LAUNCH_POOL(false, true); }
-    else { if (hubs) GR_LAUNCH_POOL(true, false); else GR_LAUNCH_POOL(false, false); }
-#undef GR_LAUNCH_POOL
-}
-#elif GS_POOLSUM_TU
-void gin_resident_poolsum_dispatch(bool hubs, bool enc, bool f16, int grid, hipStream_t s, const float* h0, const float* ecomb_all,
-                                   const uint8_t* chunks_all, const float* pool_w, const float* pool_b, const int* tile_row, const int* tile_graph,
-                                   const uint8_t* tile_desc, const int* node_off, float* out, int n_tiles, int* range_flag, const float* head_u,
-                                   const uint32_t* eidx, const float4* etab, int tstride, const int* list, const int* lrow) {
-#define GR_LAUNCH_POOLSUM(H, E, F)                                                                                                              \
-    gin_resident_kernel<H, E, F><<<grid, GR_WAVES * 64, 0, s>>>(h0, nullptr, ecomb_all, chunks_all, pool_w, pool_b, tile_row, tile_graph, tile_desc, \
-                                                                node_off, out, n_tiles, range_flag, nullptr, head_u, eidx, etab, tstride, list, lrow)
-#define GR_LAUNCH_POOLSUM_EF(H)                                                                   \
-    do {                                                                                          \
-        if (enc) { if (f16) GR_LAUNCH_POOLSUM(H, true, true); else GR_LAUNCH_POOLSUM(H, true, false); }   \
-        else { if (f16) GR_LAUNCH_POOLSUM(H, false, true); else GR_LAUNCH_POOLSUM(H, false, false); }     \
+// This translation unit's per-layer kernels in their three block shapes (the default, the single-product and the eps unit have them)
+#if !(GS_POOL_TU || GS_POOLSUM_TU || GS_NLOGIT_TU)
+#define GS_LAYER_LAUNCH(NODES, WAVES, ...)                                                                                                   \
+    gin_layer_split_kernel<__VA_ARGS__><<<(int)ceil_div_ll(a.n_tot, NODES), WAVES * 64, 0, s>>>(a.h, a.hout, a.row_ptr, a.src, a.ecode, a.ecomb, \
+                                                                                                a.chunks, a.n_tot, a.relu_out, a.range_flag,     \
+                                                                                                a.pool_w GS_LAYER_TRAILER)
+#if GS_EPS_TU  // <NT, WAVES, F16>: both numeric modes, s_l as the last argument
+#define GS_LAYER_LAUNCHER launch_gin_layer_split_eps
+#define GS_LAYER_TRAILER , *a.self_s
+#define GS_LAYER_SHAPE(NT, WAVES, NODES)                                  \
+    do {                                                                  \
+        if (a.f16) GS_LAYER_LAUNCH(NODES, WAVES, NT, WAVES, true);        \
+        else GS_LAYER_LAUNCH(NODES, WAVES, NT, WAVES, false);             \
     } while (0)
-    if (hubs) GR_LAUNCH_POOLSUM_EF(true); else GR_LAUNCH_POOLSUM_EF(false);
-#undef GR_LAUNCH_POOLSUM_EF
-#undef GR_LAUNCH_POOLSUM
-}
-#elif GS_EPS_TU
-// the per-layer kernel's eps instances: the three shapes of launch_split_nt, both numeric modes, s_l as the last argument
-void launch_gin_layer_split_eps(const float* h, float* hout, const int* row_ptr, const int* src, const uint8_t* ecode, const float* ecomb,
-                                const uint8_t* chunks, int n_tot, int relu_out, int* range_flag, int nt, hipStream_t s, const float* pool_w,
-                                bool f16, float self_s) {
-#define GS_LAUNCH_EPS(NT, WAVES, NODES)                                                                                               \
-    do {                                                                                                                              \
-        const int blocks = (int)ceil_div_ll(n_tot, NODES);                                                                            \
-        if (f16) gin_layer_split_kernel<NT, WAVES, true><<<blocks, WAVES * 64, 0, s>>>(h, hout, row_ptr, src, ecode, ecomb, chunks, n_tot, relu_out, range_flag, pool_w, self_s); \
-        else gin_layer_split_kernel<NT, WAVES, false><<<blocks, WAVES * 64, 0, s>>>(h, hout, row_ptr, src, ecode, ecomb, chunks, n_tot, relu_out, range_flag, pool_w, self_s);   \
-    } while (0)
-    if (nt == 4) GS_LAUNCH_EPS(1, 8, 128);  // 8 waves, 128 nodes per workgroup
-    else if (nt == 2) GS_LAUNCH_EPS(2, 4, 128);
-    else GS_LAUNCH_EPS(1, 4, 64);
-#undef GS_LAUNCH_EPS
-}
-void gin_resident_eps_dispatch(bool hubs, bool enc, bool f16, int grid, hipStream_t s, const float* h0, const float* ecomb_all,
-                               const uint8_t* chunks_all, const float* pool_w, const float* pool_b, const int* tile_row, const int* tile_graph,
-                               const uint8_t* tile_desc, const int* node_off, float* out, int n_tiles, int* range_flag, const float* head_u,
-                               const uint32_t* eidx, const float4* etab, int tstride, const int* list, const int* lrow, GinSelfScale self_scale) {
-#define GR_LAUNCH_EPS(H, E, F)                                                                                                              \
-    gin_resident_kernel<H, E, F><<<grid, GR_WAVES * 64, 0, s>>>(h0, nullptr, ecomb_all, chunks_all, pool_w, pool_b, tile_row, tile_graph, tile_desc, \
-                                                                node_off, out, n_tiles, range_flag, nullptr, head_u, eidx, etab, tstride, list, lrow, \
-                                                                self_scale)
-#define GR_LAUNCH_EPS_EF(H)                                                               \
-    do {                                                                                  \
-        if (enc) { if (f16) GR_LAUNCH_EPS(H, true, true); else GR_LAUNCH_EPS(H, true, false); }   \
-        else { if (f16) GR_LAUNCH_EPS(H, false, true); else GR_LAUNCH_EPS(H, false, false); }     \
-    } while (0)
-    if (hubs) GR_LAUNCH_EPS_EF(true); else GR_LAUNCH_EPS_EF(false);
-#undef GR_LAUNCH_EPS_EF
-#undef GR_LAUNCH_EPS
-}
-#elif GS_NLOGIT_TU
-void gin_resident_nlogit_dispatch(bool hubs, bool enc, bool f16, int grid, hipStream_t s, const float* h0, const float* ecomb_all,
-                                  const uint8_t* chunks_all, const float* pool_w, const float* pool_b, const int* tile_row, const int* tile_graph,
-                                  const uint8_t* tile_desc, const int* node_off, float* out, int n_tiles, int* range_flag, const float* head_u,
-                                  const uint32_t* eidx, const float4* etab, int tstride, const int* list, const int* lrow, float* node_logits) {
-#define GR_LAUNCH_NLOGIT(H, E, F)                                                                                                              \
-    gin_resident_kernel<H, E, F><<<grid, GR_WAVES * 64, 0, s>>>(h0, nullptr, ecomb_all, chunks_all, pool_w, pool_b, tile_row, tile_graph, tile_desc, \
-                                                                node_off, out, n_tiles, range_flag, nullptr, head_u, eidx, etab, tstride, list, lrow, \
-                                                                node_logits)
-#define GR_LAUNCH_NLOGIT_EF(H)                                                                  \
-    do {                                                                                        \
-        if (enc) { if (f16) GR_LAUNCH_NLOGIT(H, true, true); else GR_LAUNCH_NLOGIT(H, true, false); }   \
-        else { if (f16) GR_LAUNCH_NLOGIT(H, false, true); else GR_LAUNCH_NLOGIT(H, false, false); }     \
-    } while (0)
-    if (hubs) GR_LAUNCH_NLOGIT_EF(true); else GR_LAUNCH_NLOGIT_EF(false);
-#undef GR_LAUNCH_NLOGIT_EF
-#undef GR_LAUNCH_NLOGIT
-}
-#elif GS_SINGLE_PRODUCT
-// the entry points of the single-product instances (called by the launchers of gin_split.hip's own translation unit)
-void launch_gin_layer_split_f16(const float* h, float* hout, const int* row_ptr, const int* src, const uint8_t* ecode, const float* ecomb,
-                                const uint8_t* chunks, int n_tot, int relu_out, int* range_flag, int nt, hipStream_t s, const float* pool_w) {
-    launch_split_nt(h, hout, row_ptr, src, ecode, ecomb, chunks, n_tot, relu_out, range_flag, nt, s, pool_w);
-}
-void gin_resident_dispatch_f16(bool prof, bool hubs, bool fold, bool enc, int grid, hipStream_t s, const float* h0, float* hout,
-                               const float* ecomb_all, const uint8_t* chunks_all, const float* pool_w, const float* pool_b, const int* tile_row,
-                               const int* tile_graph, const uint8_t* tile_desc, const int* node_off, float* out, int n_tiles, int* range_flag,
-                               unsigned long long* d, const float* head_u, const uint32_t* eidx, const float4* etab, int tstride,
-                               const int* list, const int* lrow) {
-    gr_dispatch(prof, hubs, fold, enc, grid, s, h0, hout, ecomb_all, chunks_all, pool_w, pool_b, tile_row, tile_graph, tile_desc, node_off, out,
-                n_tiles, range_flag, d, head_u, eidx, etab, tstride, list, lrow);
-}
+#else  // <NT, WAVES> (GS_F16: which instance)
+#if GS_SINGLE_PRODUCT
+#define GS_LAYER_LAUNCHER launch_gin_layer_split_f16
 #else
-// (gin_split_f16.hip)
-void launch_gin_layer_split_f16(const float* h, float* hout, const int* row_ptr, const int* src, const uint8_t* ecode, const float* ecomb,
-                                const uint8_t* chunks, int n_tot, int relu_out, int* range_flag, int nt, hipStream_t s, const float* pool_w);
-void gin_resident_dispatch_f16(bool prof, bool hubs, bool fold, bool enc, int grid, hipStream_t s, const float* h0, float* hout,
-                               const float* ecomb_all, const uint8_t* chunks_all, const float* pool_w, const float* pool_b, const int* tile_row,
-                               const int* tile_graph, const uint8_t* tile_desc, const int* node_off, float* out, int n_tiles, int* range_flag,
-                               unsigned long long* d, const float* head_u, const uint32_t* eidx, const float4* etab, int tstride,
-                               const int* list, const int* lrow);
-// (gin_split_pool.hip) the instances that pool h_5 into emb [G][100]: un-folded, rows from HBM, no phase stamps
-void gin_resident_pool_dispatch(bool hubs, bool f16, int grid, hipStream_t s, const float* h0, const float* ecomb_all, const uint8_t* chunks_all,
-                                const float* pool_w, const float* pool_b, const int* tile_row, const int* tile_graph, const uint8_t* tile_desc,
-                                const int* node_off, float* out, int n_tiles, int* range_flag, int tstride, float* emb);
+#define GS_LAYER_LAUNCHER launch_split_nt
+#endif
+#define GS_LAYER_TRAILER
+#define GS_LAYER_SHAPE(NT, WAVES, NODES) GS_LAYER_LAUNCH(NODES, WAVES, NT, WAVES)
+#endif
+void GS_LAYER_LAUNCHER(const GinLayerLaunch& a, hipStream_t s) {
+    if (a.variant == 4) GS_LAYER_SHAPE(1, 8, 128);  // 8 waves, 128 nodes per workgroup, 2 workgroups per CU
+    else if (a.variant == 2) GS_LAYER_SHAPE(2, 4, 128);
+    else GS_LAYER_SHAPE(1, 4, 64);
+}
+#undef GS_LAYER_SHAPE
+#undef GS_LAYER_TRAILER
+#undef GS_LAYER_LAUNCHER
+#undef GS_LAYER_LAUNCH
+#endif
 
-// (gin_split_poolmax.hip) the same with the per-column maximum of the h_5 rows in emb (launched with out = null: the head follows from emb)
-void gin_resident_poolmax_dispatch(bool hubs, bool f16, int grid, hipStream_t s, const float* h0, const float* ecomb_all, const uint8_t* chunks_all,
-                                   const float* pool_w, const float* pool_b, const int* tile_row, const int* tile_graph, const uint8_t* tile_desc,
-                                   const int* node_off, float* out, int n_tiles, int* range_flag, int tstride, float* emb);
-// (gin_split_poolsum.hip) the folded instances whose readout is the sum of the graph's terms
-void gin_resident_poolsum_dispatch(bool hubs, bool enc, bool f16, int grid, hipStream_t s, const float* h0, const float* ecomb_all,
-                                   const uint8_t* chunks_all, const float* pool_w, const float* pool_b, const int* tile_row, const int* tile_graph,
-                                   const uint8_t* tile_desc, const int* node_off, float* out, int n_tiles, int* range_flag, const float* head_u,
-                                   const uint32_t* eidx, const float4* etab, int tstride, const int* list, const int* lrow);
+// Resident kernel: GR_DISPATCHER = this unit's launcher, GR_TRAILER = ", <the instance's own argument>" behind the shared twenty (it
+// brings its own comma, and is empty where the kernel's argument list ends with lrow)
+#if GS_POOL_TU && GS_POOL_MAX
+#define GR_DISPATCHER gin_resident_poolmax_dispatch
+#define GR_TRAILER , k.emb
+#elif GS_POOL_TU
+#define GR_DISPATCHER gin_resident_pool_dispatch
+#define GR_TRAILER , k.emb
+#elif GS_POOLSUM_TU
+#define GR_DISPATCHER gin_resident_poolsum_dispatch
+#define GR_TRAILER
+#elif GS_EPS_TU
+#define GR_DISPATCHER gin_resident_eps_dispatch
+#define GR_TRAILER , k.self_scale
+#elif GS_NLOGIT_TU
+#define GR_DISPATCHER gin_resident_nlogit_dispatch
+#define GR_TRAILER , k.node_logits
+#elif GS_SINGLE_PRODUCT
+#define GR_DISPATCHER gin_resident_f16_dispatch
+#define GR_TRAILER
+#else
+#define GR_DISPATCHER gin_resident_default_dispatch
+#define GR_TRAILER
+#endif
+void GR_DISPATCHER(const GrKernelLaunch& k, hipStream_t s) {
+#define GR_LAUNCH(...)                                                                                                                          \
+    gin_resident_kernel<__VA_ARGS__><<<k.grid, GR_WAVES * 64, 0, s>>>(k.h0, k.hout, k.ecomb_all, k.chunks_all, k.pool_w, k.pool_b, k.tile_row,  \
+                                                                      k.tile_graph, k.tile_desc, k.node_off, k.out, k.n_tiles, k.range_flag,    \
+                                                                      k.prof_out, k.head_u, k.eidx, k.etab, k.tstride, k.list, k.lrow GR_TRAILER)
+#if GS_POOL_TU  // <HUBS, F16>
+    if (k.f16) { if (k.hubs) GR_LAUNCH(true, true); else GR_LAUNCH(false, true); }
+    else { if (k.hubs) GR_LAUNCH(true, false); else GR_LAUNCH(false, false); }
+#elif GS_POOLSUM_TU || GS_EPS_TU || GS_NLOGIT_TU  // <HUBS, ENC, F16>
+#define GR_LAUNCH_EF(H)                                                                               \
+    do {                                                                                              \
+        if (k.enc) { if (k.f16) GR_LAUNCH(H, true, true); else GR_LAUNCH(H, true, false); }           \
+        else { if (k.f16) GR_LAUNCH(H, false, true); else GR_LAUNCH(H, false, false); }               \
+    } while (0)
+    if (k.hubs) GR_LAUNCH_EF(true); else GR_LAUNCH_EF(false);
+#undef GR_LAUNCH_EF
+#else  // <PROF, HUBS, FOLD, ENC> (GS_F16: which instance)
+#define GR_LAUNCH_FE(P, H)                                      \
+    do {                                                        \
+        if (k.enc) GR_LAUNCH(P, H, true, true);                 \
+        else if (k.fold) GR_LAUNCH(P, H, true, false);          \
+        else GR_LAUNCH(P, H, false, false);                     \
+    } while (0)
+    if (k.prof) {
+        if (k.hubs) GR_LAUNCH_FE(true, true); else GR_LAUNCH_FE(true, false);
+    } else {
+        if (k.hubs) GR_LAUNCH_FE(false, true); else GR_LAUNCH_FE(false, false);
+    }
+#undef GR_LAUNCH_FE
+#endif
+#undef GR_LAUNCH
+}
+#undef GR_TRAILER
+#undef GR_DISPATCHER
 
-// (gin_split_eps.hip) the per-layer and the folded resident instances that apply s_l = 1 + eps[l] to the self term (flowgnn_set_gin_eps)
-void launch_gin_layer_split_eps(const float* h, float* hout, const int* row_ptr, const int* src, const uint8_t* ecode, const float* ecomb,
-                                const uint8_t* chunks, int n_tot, int relu_out, int* range_flag, int nt, hipStream_t s, const float* pool_w,
-                                bool f16, float self_s);
-void gin_resident_eps_dispatch(bool hubs, bool enc, bool f16, int grid, hipStream_t s, const float* h0, const float* ecomb_all,
-                               const uint8_t* chunks_all, const float* pool_w, const float* pool_b, const int* tile_row, const int* tile_graph,
-                               const uint8_t* tile_desc, const int* node_off, float* out, int n_tiles, int* range_flag, const float* head_u,
-                               const uint32_t* eidx, const float4* etab, int tstride, const int* list, const int* lrow, GinSelfScale self_scale);
-
-// (gin_split_nlogit.hip) the folded instances that also store the per-node readout terms into node_logits [N], caller order
-void gin_resident_nlogit_dispatch(bool hubs, bool enc, bool f16, int grid, hipStream_t s, const float* h0, const float* ecomb_all,
-                                  const uint8_t* chunks_all, const float* pool_w, const float* pool_b, const int* tile_row, const int* tile_graph,
-                                  const uint8_t* tile_desc, const int* node_off, float* out, int n_tiles, int* range_flag, const float* head_u,
-                                  const uint32_t* eidx, const float4* etab, int tstride, const int* list, const int* lrow, float* node_logits);
-
+#if !GS_SINGLE_PRODUCT
 void gin_split_pack_layer(const float* w1, const float* b1, const float* w2, const float* b2, uint8_t* out, bool f16) {
     std::memset(out, 0, GS_LAYER_BYTES);
     const float s1 = pow2_scale(w1, (size_t)GS_H * GS_D);
@@ -2357,81 +2297,50 @@ void gin_resident_pack_layer(const float* w1, const float* b1, const float* w2, 
     }
 }
 
-void launch_gin_layer_split(const float* h, float* hout, const int* row_ptr, const int* src, const uint8_t* ecode,
-                            const float* ecomb, const uint8_t* chunks, int n_tot, int e_tot, int relu_out, int* range_flag,
-                            int nt, hipStream_t s, const float* pool_w, bool f16, const float* self_s) {
-    if (self_s != nullptr) {  // eps on: the eps instances (null: the launch it always was)
-        launch_gin_layer_split_eps(h, hout, row_ptr, src, ecode, ecomb, chunks, n_tot, relu_out, range_flag, nt, s, pool_w, f16, *self_s);
-        return;
-    }
-    (f16 ? launch_gin_layer_split_f16 : launch_split_nt)(h, hout, row_ptr, src, ecode, ecomb, chunks, n_tot, relu_out, range_flag, nt, s, pool_w);
+void launch_gin_layer_split(const GinLayerLaunch& a, hipStream_t s) {
+    if (a.self_s != nullptr) launch_gin_layer_split_eps(a, s);  // eps on: the eps instances (null: the launch it always was)
+    else (a.f16 ? launch_gin_layer_split_f16 : launch_split_nt)(a, s);
 }
 
-int launch_gin_resident(const float* h0, float* hout, const int* row_ptr, const int* src, const uint8_t* ecode, const float* ecomb_all,
-                         const uint8_t* chunks_all, const float* pool_w, const float* pool_b, const int* tile_row, const int* tile_graph,
-                         uint8_t* tile_desc, const int* node_off, float* out, int n_tiles, int* range_flag, hipStream_t s, bool hubs,
-                         const float* head_u, int col_order, bool prof, const GinTileBuild* tb, int tstride, bool f16, float* emb,
-                         float* node_logits, int pooling, const float* self_scale) {
-    if (n_tiles <= 0) return 0;
-    const int order = hubs ? 3 : col_order;
-    if (emb != nullptr) { head_u = nullptr; hout = nullptr; prof = false; }  // the pooling instance: un-folded, no tap, no phase stamps
-    const bool fold = head_u != nullptr && out != nullptr && hout == nullptr;  // single-task readout, no per-node tap
-    // a mode other than the mean has the instances named below and no other: anything else would be the mean's logits under its name
-    if (pooling != 0 && !(pooling == 1 && fold && node_logits == nullptr && emb == nullptr) && !(pooling == 2 && emb != nullptr)) {
-        set_last_error("launch_gin_resident: pooling 1 (sum) runs the folded instances only (head_u, out, no hout / emb / node_logits), pooling 2 (max) "
-                       "the pooling instance only (emb)");
+int launch_gin_resident(const GinResidentLaunch& a, hipStream_t s) {
+    if (a.n_tiles <= 0) return 0;
+    const GinResidentPick pick = gin_resident_pick(a);
+    if (pick.instance == GinResidentInstance::Refused) {
+        set_last_error(pick.refusal);
         return 8;  // FLOWGNN_ERR_UNSUPPORTED
     }
-    // eps on: the folded, single-task, mean-pooling instances and no other -- anything else would be the eps-less model under its name
-    if (self_scale != nullptr && !(fold && pooling == 0 && emb == nullptr && node_logits == nullptr && tstride == 1)) {
-        set_last_error("launch_gin_resident: a trained eps runs the folded mean-pooling instances only (head_u, out, no hout / emb / node_logits)");
-        return 8;  // FLOWGNN_ERR_UNSUPPORTED
-    }
-    const bool enc = tb != nullptr && fold;  // descriptor + encoder indices straight from the caller's arrays, h_0 computed by the tile loader
-    if (!enc) gin_tile_prep_kernel<<<n_tiles, 256, 0, s>>>(row_ptr, src, ecode, tile_row, tile_desc, n_tiles, order, tstride);
-    const int grid = n_tiles < 256 ? n_tiles : 256;  // persistent: one 8-wave workgroup per CU (157 KB of LDS)
+    const bool fold = pick.fold, enc = pick.enc;
+    if (!enc) gin_tile_prep_kernel<<<a.n_tiles, 256, 0, s>>>(a.row_ptr, a.src, a.ecode, a.tile_row, a.tile_desc, a.n_tiles, a.hubs ? 3 : a.col_order, a.tstride);
+    const int grid = a.n_tiles < 256 ? a.n_tiles : 256;  // persistent: one 8-wave workgroup per CU (157 KB of LDS)
+    // development aid: phase breakdown from s_memrealtime stamps, printed per launch (synchronises!) -- the default instances' kernels
+    // alone write stamps
+    const bool prof = a.prof && pick.instance == GinResidentInstance::Default;
     unsigned long long* d = nullptr;
     const size_t cnt = (size_t)grid * GR_WAVES * 7;
-    if (prof) {  // development aid: phase breakdown from s_memrealtime stamps, printed per launch (synchronises!)
+    if (prof) {
         if (hipMalloc((void**)&d, cnt * 8) != hipSuccess) return 0;
         (void)hipMemsetAsync(d, 0, cnt * 8, s);
     }
-    const uint32_t* eidx = enc ? reinterpret_cast<const uint32_t*>(tb->enc_idx) : nullptr;
-    const float4* etab = enc ? reinterpret_cast<const float4*>(tb->enc_tab) : nullptr;
-    if (self_scale != nullptr) {  // flowgnn_set_gin_eps: the folded instance with s_l in its argument block (no phase stamps)
-        GinSelfScale ss;
-        for (int l = 0; l < 5; l++) ss.s[l] = self_scale[l];
-        gin_resident_eps_dispatch(hubs, enc, f16, grid, s, h0, ecomb_all, chunks_all, pool_w, pool_b, tile_row, tile_graph, tile_desc, node_off, out,
-                                  n_tiles, range_flag, head_u, eidx, etab, tstride, enc ? tb->list : nullptr, enc ? tb->lrow : nullptr, ss);
-        if (d) (void)hipFree(d);
-        return 0;
+    const bool pool = a.emb != nullptr;  // the pooling instances: un-folded, no tap
+    GrKernelLaunch k{grid, a.h0, pool ? nullptr : a.hout, a.ecomb_all, a.chunks_all, a.pool_w, a.pool_b, a.tile_row, a.tile_graph, a.tile_desc,
+                     a.node_off, a.out, a.n_tiles, a.range_flag, d, pool ? nullptr : a.head_u,
+                     enc ? reinterpret_cast<const uint32_t*>(a.tb->enc_idx) : nullptr, enc ? reinterpret_cast<const float4*>(a.tb->enc_tab) : nullptr,
+                     a.tstride, enc ? a.tb->list : nullptr, enc ? a.tb->lrow : nullptr,
+                     prof, a.hubs, fold, enc, a.f16, a.emb, a.node_logits, {}};
+    switch (pick.instance) {
+    case GinResidentInstance::Eps:  // s_l in the argument block
+        for (int l = 0; l < 5; l++) k.self_scale.s[l] = a.self_scale[l];
+        gin_resident_eps_dispatch(k, s);
+        break;
+    case GinResidentInstance::PoolMax:  // FLOWGNN_POOL_MAX: the per-column maxima go to emb, and the caller applies the head to them
+        k.out = nullptr;
+        gin_resident_poolmax_dispatch(k, s);
+        break;
+    case GinResidentInstance::PoolMean: gin_resident_pool_dispatch(k, s); break;
+    case GinResidentInstance::PoolSum: gin_resident_poolsum_dispatch(k, s); break;  // FLOWGNN_POOL_SUM: the readout leaves the division out
+    case GinResidentInstance::NodeLogits: gin_resident_nlogit_dispatch(k, s); break;
+    default: (a.f16 ? gin_resident_f16_dispatch : gin_resident_default_dispatch)(k, s); break;  // Default (Refused has returned)
     }
-    if (emb != nullptr && pooling == 2) {  // FLOWGNN_POOL_MAX: the per-column maxima go to emb, and the caller applies the head to them (out == null)
-        gin_resident_poolmax_dispatch(hubs, f16, grid, s, h0, ecomb_all, chunks_all, pool_w, pool_b, tile_row, tile_graph, tile_desc, node_off, nullptr,
-                                      n_tiles, range_flag, tstride, emb);
-        return 0;
-    }
-    if (pooling == 1 && fold && node_logits == nullptr) {  // FLOWGNN_POOL_SUM: the folded instance whose readout leaves the division out (no phase stamps)
-        gin_resident_poolsum_dispatch(hubs, enc, f16, grid, s, h0, ecomb_all, chunks_all, pool_w, pool_b, tile_row, tile_graph, tile_desc, node_off,
-                                      out, n_tiles, range_flag, head_u, eidx, etab, tstride, enc ? tb->list : nullptr, enc ? tb->lrow : nullptr);
-        if (d) (void)hipFree(d);
-        return 0;
-    }
-    if (emb != nullptr) {
-        gin_resident_pool_dispatch(hubs, f16, grid, s, h0, ecomb_all, chunks_all, pool_w, pool_b, tile_row, tile_graph, tile_desc, node_off, out,
-                                   n_tiles, range_flag, tstride, emb);
-        return 0;
-    }
-    if (node_logits != nullptr && fold) {  // the folded instance that also stores the per-node terms (no phase stamps)
-        gin_resident_nlogit_dispatch(hubs, enc, f16, grid, s, h0, ecomb_all, chunks_all, pool_w, pool_b, tile_row, tile_graph, tile_desc, node_off,
-                                     out, n_tiles, range_flag, head_u, eidx, etab, tstride, enc ? tb->list : nullptr, enc ? tb->lrow : nullptr,
-                                     node_logits);
-        if (d) (void)hipFree(d);
-        return 0;
-    }
-    (f16 ? gin_resident_dispatch_f16 : gr_dispatch)(prof, hubs, fold, enc, grid, s, h0, hout, ecomb_all, chunks_all, pool_w, pool_b, tile_row,
-                                                    tile_graph, tile_desc, node_off, out, n_tiles, range_flag, d, head_u, eidx, etab, tstride,
-                                                    enc ? tb->list : nullptr, enc ? tb->lrow : nullptr);
     if (prof) {
         std::vector<unsigned long long> hbuf(cnt);
         (void)hipStreamSynchronize(s);
@@ -2441,7 +2350,7 @@ int launch_gin_resident(const float* h0, float* hout, const int* row_ptr, const 
         for (size_t i = 0; i < cnt; i++) tot[i % 7] += (double)hbuf[i];
         const double nw = (double)grid * GR_WAVES;
         fprintf(stderr, "[gin_resident prof] tiles %d grid %d | per wave, us: gather %.1f  wait+barrier %.1f  mlp %.1f (of which step-end DMA wait %.1f, barrier %.1f)  epilogue+barrier %.1f  kernel %.1f\n",
-                n_tiles, grid, tot[0] / nw / 100.0, tot[1] / nw / 100.0, tot[2] / nw / 100.0, tot[5] / nw / 100.0, tot[4] / nw / 100.0, tot[3] / nw / 100.0, tot[6] / nw / 100.0);
+                a.n_tiles, grid, tot[0] / nw / 100.0, tot[1] / nw / 100.0, tot[2] / nw / 100.0, tot[5] / nw / 100.0, tot[4] / nw / 100.0, tot[3] / nw / 100.0, tot[6] / nw / 100.0);
         {   // the same by wave index (0..7: which of the eight waves of a workgroup), gather and the wait behind it
             double gw[GR_WAVES] = {0}, ww[GR_WAVES] = {0};
             for (size_t i = 0; i < cnt; i += 7) { const int wi = (int)((i / 7) % GR_WAVES); gw[wi] += (double)hbuf[i]; ww[wi] += (double)hbuf[i + 1]; }
