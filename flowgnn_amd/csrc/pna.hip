@@ -84,8 +84,13 @@ struct PnaAggPolicy {
         const float deg = (float)(indeg == 0 ? 1 : indeg);
         float4 mean, sd;
         mean.x = a.S.x / deg; mean.y = a.S.y / deg; mean.z = a.S.z / deg; mean.w = a.S.w / deg;
-        sd.x = sqrtf(relu1(a.Q.x / deg - mean.x * mean.x)); sd.y = sqrtf(relu1(a.Q.y / deg - mean.y * mean.y));
-        sd.z = sqrtf(relu1(a.Q.z / deg - mean.z * mean.z)); sd.w = sqrtf(relu1(a.Q.w / deg - mean.w * mean.w));
+        // mean^2 rounded on its own: a row with ONE in-edge has Q = fl(x^2) = fl(mean^2), and its std is then exactly 0 as in the
+        // reference -- contracted into fma(-mean, mean, Q / deg) the subtraction leaves fl(x^2) - x^2 there, whose root is up to
+        // 2.4e-4 |x|.  The empty asm keeps hipcc (-ffp-contract=fast) from fusing the squares back into the subtraction.
+        float4 m2 = make_float4(mean.x * mean.x, mean.y * mean.y, mean.z * mean.z, mean.w * mean.w);
+        asm("" : "+v"(m2.x), "+v"(m2.y), "+v"(m2.z), "+v"(m2.w));
+        sd.x = sqrtf(relu1(a.Q.x / deg - m2.x)); sd.y = sqrtf(relu1(a.Q.y / deg - m2.y));
+        sd.z = sqrtf(relu1(a.Q.z / deg - m2.z)); sd.w = sqrtf(relu1(a.Q.w / deg - m2.w));
         float4* o = reinterpret_cast<float4*>(out) + (size_t)v * (PNA_NA * PNA_C) + c;
         stream_store4(o + 0 * PNA_C, mean); stream_store4(o + 1 * PNA_C, a.mn); stream_store4(o + 2 * PNA_C, a.mx); stream_store4(o + 3 * PNA_C, sd);
     }
@@ -542,7 +547,11 @@ __device__ __forceinline__ void pna_slice_finish(const PnaSlice& a, int indeg, d
     // roots per slice are ~60 dependent VALU instructions, and at two waves per SIMD nothing hides their latency
     const float rdeg = __builtin_amdgcn_rcpf((float)(indeg == 0 ? 1 : indeg));
     const float m0 = a.S0 * rdeg, m1 = a.S1 * rdeg;
-    const float sd0 = __builtin_amdgcn_sqrtf(relu1(__builtin_fmaf(-m0, m0, a.Q0 * rdeg))), sd1 = __builtin_amdgcn_sqrtf(relu1(__builtin_fmaf(-m1, m1, a.Q1 * rdeg)));
+    // variance = fl(Q rdeg - fl(m^2)): the square rounded on its own, ONE multiply and one FMA per value as before.  With one in-edge
+    // (rdeg = 1, Q = fl(x^2), m = x) that is exactly 0, the reference's value; fma(-m, m, Q rdeg) left fl(x^2) - x^2 there, whose root
+    // is up to 2.4e-4 |x| (tests/test_split_accuracy_gpu.py found it: 12 x the bound on h_4)
+    // (the squares are operands of an explicit FMA: nothing is left for the compiler to contract them into)
+    const float sd0 = __builtin_amdgcn_sqrtf(relu1(__builtin_fmaf(a.Q0, rdeg, -(m0 * m0)))), sd1 = __builtin_amdgcn_sqrtf(relu1(__builtin_fmaf(a.Q1, rdeg, -(m1 * m1))));
     // K-slots e = 0..7: (feature f0: mean, min, max, std), (feature f0 + 1: the same)
     DS_SPLIT2(m0, a.mn0, b_hi.x, b_lo.x);
     DS_SPLIT2(a.mx0, sd0, b_hi.y, b_lo.y);
