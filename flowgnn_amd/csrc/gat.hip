@@ -18,6 +18,7 @@
 #include "device_common.h"
 #include "dense_split.h"
 #include "modelq.h"
+#include "gat_plan.h"
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -56,11 +57,11 @@ struct GatResidentDev {
 };
 // what a launch of the resident kernel takes, for the storing instance in its own translation unit (gat_nlogit.hip)
 struct GatResidentLaunch {
-    int grid;
-    const int* node_feature; const int* feat_row; const int* row_ptr; const int* src;
-    const int* tile_row; const int* tile_graph; const int* node_off;
-    float* out; int n_tiles; GatResidentDev w; int ablate;
-    float* node_logits;  // [N], caller order (GAT's tiles are ranges of the batch's rows: row r of a tile is node t0 + r)
+    int grid = 0;
+    const int* node_feature = nullptr; const int* feat_row = nullptr; const int* row_ptr = nullptr; const int* src = nullptr;
+    const int* tile_row = nullptr; const int* tile_graph = nullptr; const int* node_off = nullptr;
+    float* out = nullptr; int n_tiles = 0; GatResidentDev w = {}; int ablate = 0;
+    float* node_logits = nullptr;  // [N], caller order (GAT's tiles are ranges of the batch's rows: row r of a tile is node t0 + r)
     // gat_attn.hip only: bit l of the mask selects layer l; [n_sel][e_tot][4] by the caller's edge index (csr.eid), [n_sel][n_tot][4]
     int attn_mask = 0; float* attn_edge = nullptr; float* attn_self = nullptr; const int* eid = nullptr; int e_tot = 0, n_tot = 0;
 };
@@ -983,6 +984,12 @@ __global__ __launch_bounds__(GATR_WAVES * 64, 4) void gat_resident_kernel(const 
 #undef GATR_ABSMAX
 
 #ifndef FG_RESIDENT_INSTANCE_TU  // (host side: the model's own translation unit only)
+// the default instance, launched from the struct the others take: the kernel compiled HERE (see the top of this file)
+static void launch_gat_resident_default(const GatResidentLaunch& a, hipStream_t s) {
+    gat_resident_kernel<<<a.grid, GATR_WAVES * 64, 0, s>>>(a.node_feature, a.feat_row, a.row_ptr, a.src, a.tile_row, a.tile_graph, a.node_off, a.out,
+                                                           a.n_tiles, a.w, a.ablate);
+}
+
 class GatModel : public Model {
 public:
     ~GatModel() override { free_all(); }
@@ -1165,6 +1172,37 @@ public:
     }
     void set_keep_h(bool on) override { keep_h_ = on; }
 
+    // which kernels the next forward of this batch runs: decided in gat_plan.h, from these values and nothing else
+    GatPlan plan(const DeviceBatch& db) const {
+        GatPlanInput in;
+        in.resident = resident_; in.fold_readout = fold_readout_; in.split = split_;
+        in.qmode = qmode_; in.keep_h = keep_h_; in.exact = exact_;
+        in.tiles = db.gtiles.ok && db.gtiles.n_tiles > 0; in.fill = db.gtiles.fill;
+        in.emb = db.emb != nullptr; in.node_emb = db.node_emb != nullptr; in.node_logits = db.node_logits != nullptr;
+        in.attention = db.attn_mask != 0; in.pooling = db.pooling;
+        return gat_plan(in);
+    }
+
+    // the resident path's launch: the plan's instance of gat_resident_kernel
+    void resident_launch(DeviceBatch& db, const GatPlan& plan, const int* feat_row, hipStream_t s) {
+        GatResidentLaunch a;
+        a.grid = db.gtiles.n_tiles < 256 ? db.gtiles.n_tiles : 256;  // persistent: one 16-wave workgroup per CU (118 KB of LDS)
+        a.node_feature = db.b.node_feature; a.feat_row = feat_row; a.row_ptr = db.csr.row_ptr; a.src = db.csr.src;
+        a.tile_row = db.gtiles.row_start; a.tile_graph = db.gtiles.graph_start; a.node_off = db.b.node_off;
+        a.out = db.out; a.n_tiles = db.gtiles.n_tiles; a.ablate = ablate_;
+        a.w.layers = d_res_; a.w.scales = d_scales_; a.w.a_src = d_asrc_; a.w.a_tgt = d_atgt_; a.w.lin0 = d_lin0_;
+        a.w.pool_w = d_pw_; a.w.pool_b = d_pb_; a.w.u4 = d_u4_; a.w.range_flag = db.range_flag;
+        switch (plan.instance) {
+        case GatResidentInstance::PoolSum: launch_gat_resident_poolsum(a, s); break;
+        case GatResidentInstance::Attention:  // (it stores the node logits as well when those are on)
+            a.node_logits = db.node_logits; a.attn_mask = db.attn_mask; a.attn_edge = db.attn_edge; a.attn_self = db.attn_self;
+            a.eid = db.csr.eid; a.e_tot = db.b.e_tot; a.n_tot = db.b.n_tot;
+            launch_gat_resident_attn(a, s); break;
+        case GatResidentInstance::NodeLogits: a.node_logits = db.node_logits; launch_gat_resident_nlogit(a, s); break;
+        case GatResidentInstance::Default: launch_gat_resident_default(a, s); break;
+        }
+    }
+
     int forward(DeviceBatch& db, Profiler& prof, hipStream_t s) override {
         const int n = db.b.n_tot;
         if (n <= 0) return 0;
@@ -1178,42 +1216,11 @@ public:
             feat_row = reinterpret_cast<int*>(db.scratch + (size_t)n * (2 * GAT_F + 16 + GAT_D));
             gat_local_rows_kernel<<<(db.b.num_graphs + 3) / 4, 256, 0, s>>>(db.b.node_off, feat_row, db.b.num_graphs);
         }
-        if (qmode_) return gatq_forward(q_, db, feat_row, prof, s);
-        // all five layers in one launch when the batch packs into graph tiles (tiles under half full, e.g. graphs of 65..128
-        // nodes, waste MFMA columns: the per-layer kernels take those); per-node taps (flowgnn_get_h) come from the per-layer path
-        // (graph embeddings, db.emb: the resident kernel never forms the pooled row -- the per-layer path with the un-folded last stage does)
-        // (node embeddings, db.node_emb: likewise -- the resident kernel folds the last layer's skip contraction into the readout)
-        // (pooling, db.pooling: the sum has an instance of the resident kernel -- gat_poolsum.hip; with attention on as well, and for the
-        // maximum, the per-layer path pools)
-        if (resident_ && !keep_h_ && !db.emb && !db.node_emb && fold_readout_ && split_ && !exact_ && db.gtiles.ok && db.gtiles.n_tiles > 0 && db.gtiles.fill >= 0.5 &&
-            (db.pooling == POOL_OP_MEAN || (db.pooling == POOL_OP_SUM && !db.attn_mask))) {
-            GatResidentDev rw;
-            rw.layers = d_res_;
-            rw.scales = d_scales_;
-            rw.a_src = d_asrc_;
-            rw.a_tgt = d_atgt_;
-            rw.lin0 = d_lin0_;
-            rw.pool_w = d_pw_;
-            rw.pool_b = d_pb_;
-            rw.u4 = d_u4_;
-            rw.range_flag = db.range_flag;
+        const GatPlan plan = this->plan(db);
+        if (plan.path == GatPath::FixedPoint) return gatq_forward(q_, db, feat_row, prof, s);
+        if (plan.path == GatPath::Resident) {
             ProfScope p(prof, "gat_resident", s);
-            const int grid = db.gtiles.n_tiles < 256 ? db.gtiles.n_tiles : 256;  // persistent: one 16-wave workgroup per CU (118 KB of LDS)
-            if (db.pooling == POOL_OP_SUM)  // the instance whose readout is the sum (gat_poolsum.hip)
-                launch_gat_resident_poolsum(GatResidentLaunch{grid, db.b.node_feature, feat_row, db.csr.row_ptr, db.csr.src, db.gtiles.row_start,
-                                                              db.gtiles.graph_start, db.b.node_off, db.out, db.gtiles.n_tiles, rw, ablate_, nullptr}, s);
-            else if (db.attn_mask)  // the instance that also stores the selected layers' attention coefficients, and the node logits if on (gat_attn.hip)
-                launch_gat_resident_attn(GatResidentLaunch{grid, db.b.node_feature, feat_row, db.csr.row_ptr, db.csr.src, db.gtiles.row_start,
-                                                           db.gtiles.graph_start, db.b.node_off, db.out, db.gtiles.n_tiles, rw, ablate_,
-                                                           db.node_logits, db.attn_mask, db.attn_edge, db.attn_self, db.csr.eid, db.b.e_tot, n}, s);
-            else if (db.node_logits)  // the same kernel's instance that also stores the per-node readout terms (gat_nlogit.hip)
-                launch_gat_resident_nlogit(GatResidentLaunch{grid, db.b.node_feature, feat_row, db.csr.row_ptr, db.csr.src, db.gtiles.row_start,
-                                                             db.gtiles.graph_start, db.b.node_off, db.out, db.gtiles.n_tiles, rw, ablate_,
-                                                             db.node_logits}, s);
-            else
-                gat_resident_kernel<<<grid, GATR_WAVES * 64, 0, s>>>(db.b.node_feature, feat_row, db.csr.row_ptr, db.csr.src, db.gtiles.row_start,
-                                                                   db.gtiles.graph_start, db.b.node_off, db.out, db.gtiles.n_tiles, rw,
-                                                                   ablate_);
+            resident_launch(db, plan, feat_row, s);
             db.final_h = 0;
             db.tap = nullptr;
             db.h_valid = false;  // no per-node tensor leaves the kernel: flowgnn_get_h repeats the pass on the per-layer kernels
@@ -1224,8 +1231,6 @@ public:
             ProfScope p(prof, "gat_scores0", s);
             gat_scores0_kernel<<<(n + 255) / 256, 256, 0, s>>>(db.b.node_feature, feat_row, d_lin0_, d_asrc_, d_atgt_, scoreb[0], n);
         }
-        // embeddings pool the `emb` rows themselves; node embeddings are those rows; the maximum needs the rows too (W . max is not a maximum of scores)
-        const bool fold = fold_readout_ && !db.emb && !db.node_emb && db.pooling != POOL_OP_MAX;
         int cur = 0;
         for (int l = 0; l < GAT_L; l++) {
             GatLayerDev w;
@@ -1238,8 +1243,7 @@ public:
             w.wskip_scale = wskip_scale_[l];
             w.wlin_scale = wlin_scale_[l];
             w.range_flag = db.range_flag;
-            const bool sp = split_ && !exact_;
-            if ((db.attn_mask >> l) & 1) {  // this layer's attention coefficients, from the scores its launch below reads (scoreb[cur])
+            if (plan.attention_kernels && ((db.attn_mask >> l) & 1)) {  // this layer's coefficients, from scoreb[cur]
                 ProfScope p(prof, "gat_attention", s);
                 const size_t k = (size_t)__builtin_popcount((unsigned)db.attn_mask & ((1u << l) - 1u));
                 gat_attention_kernel<<<(n + 255) / 256, 256, 0, s>>>(scoreb[cur], db.csr.row_ptr, db.csr.src, db.csr.eid,
@@ -1251,7 +1255,7 @@ public:
             const int layer_grid = n_tiles < 512 ? n_tiles : 512;  // persistent: two 8-wave workgroups per CU (68 KB of LDS each)
 #define GAT_LAUNCH(FIN, FST, ...)                                                              \
     do {                                                                                          \
-        if (sp) gat_layer_kernel<FIN, FST, true><<<layer_grid, 512, 0, s>>>(__VA_ARGS__);         \
+        if (plan.split_products) gat_layer_kernel<FIN, FST, true><<<layer_grid, 512, 0, s>>>(__VA_ARGS__); \
         else gat_layer_kernel<FIN, FST, false><<<layer_grid, 512, 0, s>>>(__VA_ARGS__);           \
     } while (0)
             if (l == 0) {
@@ -1266,7 +1270,7 @@ public:
             } else {
                 GAT_LAUNCH(true, false, db.h[cur], skipb[cur], scoreb[cur], nullptr, nullptr, nullptr, emb,
                                                                         db.csr.row_ptr, db.csr.src, w, n, nullptr, nullptr, w0,
-                                                                        fold ? d_pw_ : nullptr);
+                                                                        plan.fold ? d_pw_ : nullptr);
             }
         }
 #undef GAT_LAUNCH
@@ -1275,19 +1279,18 @@ public:
         db.tap_dim = GAT_F;
         {
             ProfScope p(prof, "mean_pool_linear", s);
-            if (fold)
+            if (plan.fold)
                 { if (int rc = launch_segment_bias(db.pooling, emb, db.b.node_off, d_pb_, db.out, db.b.num_graphs, s)) return rc; }
             else
                 launch_pool_linear<GAT_D>(db.pooling, emb, db.b.node_off, d_pw_, d_pb_, db.out, db.b.num_graphs, s);
         }
-        if (db.emb) {
+        if (plan.pool_rows) {
             ProfScope p(prof, "mean_pool_rows", s);
             launch_pool_rows<GAT_D>(db.pooling, emb, db.b.node_off, db.emb, db.b.num_graphs, s);
         }
-        if (db.node_logits) {
-            // node logits (flowgnn_set_node_logits): the folded last stage left emb[v] . w as float[n], the un-folded one the 16-wide rows
+        if (plan.node_logits_from_scores || plan.node_logits_from_rows) {
             ProfScope p(prof, "node_logits", s);
-            if (fold) node_logits_bias_kernel<0><<<(n + 255) / 256, 256, 0, s>>>(emb, d_pb_, db.node_logits, n);
+            if (plan.node_logits_from_scores) node_logits_bias_kernel<0><<<(n + 255) / 256, 256, 0, s>>>(emb, d_pb_, db.node_logits, n);
             else launch_node_logits_rows<GAT_D>(emb, d_pw_, d_pb_, db.node_logits, n, 1, s);
         }
         return 0;

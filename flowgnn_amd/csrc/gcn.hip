@@ -17,6 +17,7 @@
 #include "modelq.h"
 #include "dense_split.h"
 #include "gin_split.h"  // gin_resident_pack_enc_table: the pre-combined (three rows per node) form of a 173-row table
+#include "gcn_plan.h"
 #include <cmath>
 #include <cstring>
 
@@ -27,14 +28,16 @@ namespace fg {
 // translation unit the host side is left out and the other kernels, with internal linkage and unused, are dropped.
 // what a launch of the resident kernel takes, for the storing instance in its own translation unit (gcn_rows.hip)
 struct GcnResidentLaunch {
-    bool onepass;
-    int grid;
-    const float* x0; const int* row_ptr; const int* src; const uint8_t* ecode; const int* out_deg;
-    const uint8_t* layers; const float* pool_w; const float* pool_b;
-    const int* tile_row; const int* tile_graph; const int* node_off;
-    float* out; int n_tiles; int* range_flag; int ablate;
-    const uint8_t* desc; const float4* enc_tab; const int* list; const int* lrow;
-    float* node_emb;  // [N][100], caller order
+    bool onepass = false;
+    int grid = 0;
+    // the CSR front end: x_0 rows and the index build's arrays (all null with onepass)
+    const float* x0 = nullptr; const int* row_ptr = nullptr; const int* src = nullptr; const uint8_t* ecode = nullptr; const int* out_deg = nullptr;
+    const uint8_t* layers = nullptr; const float* pool_w = nullptr; const float* pool_b = nullptr;
+    const int* tile_row = nullptr; const int* tile_graph = nullptr; const int* node_off = nullptr;
+    float* out = nullptr; int n_tiles = 0; int* range_flag = nullptr; int ablate = 0;
+    // the one-pass front end: gcn_tile_build_kernel's descriptors, the pre-combined encoder table, the bin-packed lists or null
+    const uint8_t* desc = nullptr; const float4* enc_tab = nullptr; const int* list = nullptr; const int* lrow = nullptr;
+    float* node_emb = nullptr;  // [N][100], caller order (launch_gcn_resident_rows)
     float* node_logits = nullptr;  // [N], caller order (launch_gcn_resident_nlogit)
 };
 void launch_gcn_resident_rows(const GcnResidentLaunch& a, hipStream_t s);  // gcn_rows.hip
@@ -1317,108 +1320,96 @@ public:
     }
     void set_keep_h(bool on) override { keep_h_ = on; }
 
-    // x_0 by the encoder, then everything else in one launch when the batch packs into graph tiles (tiles under half full waste MFMA
-    // columns: the per-layer kernels take those; so do per-node taps and the multi-task readout)
-    bool use_resident(const DeviceBatch& db) const {
-        // (graph embeddings, db.emb: the resident kernel folds the head per node and never forms the pooled row -- the per-layer path does;
-        // with node embeddings on as well, db.node_emb, the storing instance leaves the rows in HBM and they are pooled from there)
-        // (pooling, db.pooling: the sum has an instance of the resident kernel -- gcn_poolsum.hip; with node embeddings on, rows in HBM, the
-        // sum is taken from them behind the storing instance's launch.  The maximum is taken from the per-layer path's rows)
-        return resident_ && table_ok_ && !qmode_ && !keep_h_ && (!db.emb || db.node_emb) && split_ && !exact_ && fused_ && num_tasks_ == 1 && db.gtiles.ok && db.gtiles.n_tiles > 0 &&
-               db.gtiles.fill >= 0.5 && db.pooling != POOL_OP_MAX;
+    // which kernels the next forward of this batch runs: decided in gcn_plan.h, from these values and nothing else
+    GcnPlanInput plan_input() const {
+        GcnPlanInput in;
+        in.resident = resident_; in.tile_build = tile_build_; in.binpack = binpack_; in.split = split_; in.fused = fused_;
+        in.table_ok = table_ok_; in.qmode = qmode_; in.keep_h = keep_h_; in.exact = exact_; in.num_tasks = num_tasks_;
+        return in;
     }
-    // the one-pass front end (gcn_tile_build_kernel + the resident kernel's own encoder): the default; gcn_tile_build = 0 restores the
-    // three-launch front end (index build, projected encoder, resident kernel)
-    bool one_pass(const DeviceBatch& db) const { return tile_build_ && use_resident(db) && db.b.edge_attr != nullptr; }
-    bool needs_csr(const DeviceBatch& db) const override { return !one_pass(db); }
-    bool wants_packed_tile_lists() const override { return binpack_ && tile_build_ && resident_ && !qmode_ && num_tasks_ == 1; }
+    GcnPlan plan(const DeviceBatch& db) const {
+        GcnPlanInput in = plan_input();
+        in.tiles = db.gtiles.ok && db.gtiles.n_tiles > 0; in.fill = db.gtiles.fill; in.bp_lists = db.gtiles.bp_tiles > 0;
+        in.edge_attr = db.b.edge_attr != nullptr; in.edges = db.b.e_tot > 0;
+        in.emb = db.emb != nullptr; in.node_emb = db.node_emb != nullptr; in.node_logits = db.node_logits != nullptr;
+        in.pooling = db.pooling;
+        return gcn_plan(in);
+    }
+    bool needs_csr(const DeviceBatch& db) const override { return plan(db).needs_csr; }
+    bool wants_packed_tile_lists() const override { return gcn_wants_packed_tile_lists(plan_input()); }
+
+    // the resident path's launches: the plan's front end, then its instance of gcn_resident_kernel
+    int resident_launch(DeviceBatch& db, const GcnPlan& plan, Profiler& prof, hipStream_t s) {
+        GcnResidentLaunch a;
+        a.onepass = plan.one_pass;
+        a.layers = d_res_; a.pool_w = d_pw_; a.pool_b = d_pb_;
+        a.tile_row = db.gtiles.row_start; a.tile_graph = db.gtiles.graph_start; a.n_tiles = db.gtiles.n_tiles;
+        a.node_off = db.b.node_off; a.out = db.out; a.range_flag = db.range_flag; a.ablate = ablate_;
+        if (plan.one_pass) {  // two launches: descriptors from the caller's arrays, then everything else
+            if (plan.bin_packed) {
+                a.tile_row = db.gtiles.bp_row; a.tile_graph = db.gtiles.bp_graph; a.n_tiles = db.gtiles.bp_tiles;
+                a.list = db.gtiles.bp_list; a.lrow = db.gtiles.bp_lrow;
+            }
+            if (int rc = desc_.reserve(((size_t)a.n_tiles * GCND_BYTES + 3) / 4)) return rc;
+            a.desc = reinterpret_cast<const uint8_t*>(desc_.p);
+            a.enc_tab = reinterpret_cast<const float4*>(d_enc_tab_);
+            // (the kernel templates land in the code object in the order of their first use in this file; naming the one-pass kernel here, ahead
+            // of the encoder below, keeps that order, and so the code object, what it was when forward launched all of them itself)
+            (void)&gcn_resident_kernel<true>;
+            ProfScope p(prof, "gcn_tile_build", s);
+            gcn_tile_build_kernel<<<a.n_tiles, 256, 0, s>>>(db.b, a.tile_row, a.tile_graph, reinterpret_cast<uint8_t*>(desc_.p), a.n_tiles, db.csr.err, a.list);
+        } else {  // three: index build (the engine's), x_0 from the projected table (set_weights), the resident kernel
+            a.x0 = db.h[0]; a.row_ptr = db.csr.row_ptr; a.src = db.csr.src; a.ecode = db.csr.ecode; a.out_deg = db.csr.out_deg;
+            ProfScope p(prof, "gcn_encoder_projected", s);
+            atom_encoder_kernel<GCN_D><<<atom_encoder_grid(db.b.n_tot, GCN_C), 512, 0, s>>>(db.b.node_feature, d_nemb_proj_, db.h[0], db.b.n_tot, db.csr.err);
+        }
+        a.grid = a.n_tiles < 256 ? a.n_tiles : 256;  // persistent: one 12-wave workgroup per CU (153 KB of LDS)
+        ProfScope p(prof, "gcn_resident", s);
+        switch (plan.instance) {
+        case GcnResidentInstance::Rows: a.node_emb = db.node_emb; launch_gcn_resident_rows(a, s); break;
+        case GcnResidentInstance::PoolSum: launch_gcn_resident_poolsum(a, s); break;
+        case GcnResidentInstance::NodeLogits: a.node_logits = db.node_logits; launch_gcn_resident_nlogit(a, s); break;
+        case GcnResidentInstance::Default: launch_gcn_resident_default(a, s); break;
+        }
+        return 0;
+    }
+
+    // the default instance, launched from the struct the others take: the kernel compiled HERE (see the top of this file)
+    static void launch_gcn_resident_default(const GcnResidentLaunch& a, hipStream_t s) {
+        auto* const kernel = a.onepass ? gcn_resident_kernel<true> : gcn_resident_kernel<false>;
+        kernel<<<a.grid, GCNR_WAVES * 64, 0, s>>>(a.x0, a.row_ptr, a.src, a.ecode, a.out_deg, a.layers, a.pool_w, a.pool_b, a.tile_row, a.tile_graph,
+                                                  a.node_off, a.out, a.n_tiles, a.range_flag, a.ablate, a.desc, a.enc_tab, a.list, a.lrow);
+    }
 
     int forward(DeviceBatch& db, Profiler& prof, hipStream_t s) override {
         const int n = db.b.n_tot;
         if (n <= 0) return 0;
+        const GcnPlan plan = this->plan(db);
         agg_ready_ = false;  // tiles_ / esc_ are rebuilt by whichever float path runs below; a fixed-point pass leaves none
-        x0_in_hbm_ = !qmode_ && !(use_resident(db) && one_pass(db));
-        if (qmode_) return gcnq_forward(q_, db, prof, s);
-        if (use_resident(db)) {
-            const int grid = db.gtiles.n_tiles < 256 ? db.gtiles.n_tiles : 256;  // persistent: one 12-wave workgroup per CU (153 KB of LDS)
-            if (one_pass(db)) {  // two launches: descriptors from the caller's arrays, then everything else (no CSR, no x_0 in HBM)
-                // bin-packed tile lists when flowgnn_set_batch made them (option gcn_binpack): fewer, fuller tiles of the same graphs; a
-                // row's sums depend on the row alone, so the logits are the same bits
-                const bool bp = binpack_ && db.gtiles.bp_tiles > 0;
-                const int* t_row = bp ? db.gtiles.bp_row : db.gtiles.row_start;
-                const int* t_graph = bp ? db.gtiles.bp_graph : db.gtiles.graph_start;
-                const int n_tiles = bp ? db.gtiles.bp_tiles : db.gtiles.n_tiles;
-                if (int rc = desc_.reserve(((size_t)n_tiles * GCND_BYTES + 3) / 4)) return rc;
-                {
-                    ProfScope p(prof, "gcn_tile_build", s);
-                    gcn_tile_build_kernel<<<n_tiles, 256, 0, s>>>(db.b, t_row, t_graph, reinterpret_cast<uint8_t*>(desc_.p), n_tiles, db.csr.err,
-                                                                  bp ? db.gtiles.bp_list : nullptr);
-                }
-                ProfScope p(prof, "gcn_resident", s);
-                if (db.node_emb)  // the same kernel's row-storing instance (gcn_rows.hip)
-                    launch_gcn_resident_rows(GcnResidentLaunch{true, n_tiles < 256 ? n_tiles : 256, nullptr, nullptr, nullptr, nullptr, nullptr, d_res_, d_pw_, d_pb_,
-                                                               t_row, t_graph, db.b.node_off, db.out, n_tiles, db.range_flag, ablate_,
-                                                               reinterpret_cast<const uint8_t*>(desc_.p), reinterpret_cast<const float4*>(d_enc_tab_),
-                                                               bp ? db.gtiles.bp_list : nullptr, bp ? db.gtiles.bp_lrow : nullptr, db.node_emb}, s);
-                else if (db.pooling == POOL_OP_SUM)  // ... or the instance whose readout is the sum (gcn_poolsum.hip)
-                    launch_gcn_resident_poolsum(GcnResidentLaunch{true, n_tiles < 256 ? n_tiles : 256, nullptr, nullptr, nullptr, nullptr, nullptr, d_res_, d_pw_, d_pb_,
-                                                                  t_row, t_graph, db.b.node_off, db.out, n_tiles, db.range_flag, ablate_,
-                                                                  reinterpret_cast<const uint8_t*>(desc_.p), reinterpret_cast<const float4*>(d_enc_tab_),
-                                                                  bp ? db.gtiles.bp_list : nullptr, bp ? db.gtiles.bp_lrow : nullptr, nullptr}, s);
-                else if (db.node_logits)  // ... or the instance that stores the per-node readout terms (gcn_nlogit.hip)
-                    launch_gcn_resident_nlogit(GcnResidentLaunch{true, n_tiles < 256 ? n_tiles : 256, nullptr, nullptr, nullptr, nullptr, nullptr, d_res_, d_pw_, d_pb_,
-                                                                 t_row, t_graph, db.b.node_off, db.out, n_tiles, db.range_flag, ablate_,
-                                                                 reinterpret_cast<const uint8_t*>(desc_.p), reinterpret_cast<const float4*>(d_enc_tab_),
-                                                                 bp ? db.gtiles.bp_list : nullptr, bp ? db.gtiles.bp_lrow : nullptr, nullptr, db.node_logits}, s);
-                else
-                gcn_resident_kernel<true><<<n_tiles < 256 ? n_tiles : 256, GCNR_WAVES * 64, 0, s>>>(
-                    nullptr, nullptr, nullptr, nullptr, nullptr, d_res_, d_pw_, d_pb_, t_row, t_graph, db.b.node_off, db.out, n_tiles, db.range_flag,
-                    ablate_, reinterpret_cast<const uint8_t*>(desc_.p), reinterpret_cast<const float4*>(d_enc_tab_), bp ? db.gtiles.bp_list : nullptr,
-                    bp ? db.gtiles.bp_lrow : nullptr);
-            } else {
-                {
-                    ProfScope p(prof, "gcn_encoder_projected", s);  // x_0 from the projected table (set_weights)
-                    atom_encoder_kernel<GCN_D><<<atom_encoder_grid(n, GCN_C), 512, 0, s>>>(db.b.node_feature, d_nemb_proj_, db.h[0], n, db.csr.err);
-                }
-                ProfScope p(prof, "gcn_resident", s);
-                if (db.node_emb)
-                    launch_gcn_resident_rows(GcnResidentLaunch{false, grid, db.h[0], db.csr.row_ptr, db.csr.src, db.csr.ecode, db.csr.out_deg, d_res_, d_pw_, d_pb_,
-                                                               db.gtiles.row_start, db.gtiles.graph_start, db.b.node_off, db.out, db.gtiles.n_tiles,
-                                                               db.range_flag, ablate_, nullptr, nullptr, nullptr, nullptr, db.node_emb}, s);
-                else if (db.pooling == POOL_OP_SUM)
-                    launch_gcn_resident_poolsum(GcnResidentLaunch{false, grid, db.h[0], db.csr.row_ptr, db.csr.src, db.csr.ecode, db.csr.out_deg, d_res_, d_pw_, d_pb_,
-                                                                  db.gtiles.row_start, db.gtiles.graph_start, db.b.node_off, db.out, db.gtiles.n_tiles,
-                                                                  db.range_flag, ablate_, nullptr, nullptr, nullptr, nullptr, nullptr}, s);
-                else if (db.node_logits)
-                    launch_gcn_resident_nlogit(GcnResidentLaunch{false, grid, db.h[0], db.csr.row_ptr, db.csr.src, db.csr.ecode, db.csr.out_deg, d_res_, d_pw_, d_pb_,
-                                                                 db.gtiles.row_start, db.gtiles.graph_start, db.b.node_off, db.out, db.gtiles.n_tiles,
-                                                                 db.range_flag, ablate_, nullptr, nullptr, nullptr, nullptr, nullptr, db.node_logits}, s);
-                else
-                gcn_resident_kernel<false><<<grid, GCNR_WAVES * 64, 0, s>>>(db.h[0], db.csr.row_ptr, db.csr.src, db.csr.ecode, db.csr.out_deg, d_res_, d_pw_,
-                                                                           d_pb_, db.gtiles.row_start, db.gtiles.graph_start, db.b.node_off, db.out,
-                                                                           db.gtiles.n_tiles, db.range_flag, ablate_, nullptr, nullptr, nullptr, nullptr);
-            }
-            if (db.emb) {  // (only with db.node_emb: use_resident)
+        x0_in_hbm_ = plan.path != GcnPath::FixedPoint && !plan.one_pass;
+        if (plan.path == GcnPath::FixedPoint) return gcnq_forward(q_, db, prof, s);
+        if (plan.path == GcnPath::Resident) {
+            if (int rc = resident_launch(db, plan, prof, s)) return rc;
+            if (plan.pool_rows) {
                 ProfScope p(prof, "mean_pool_rows", s);
                 launch_pool_rows<GCN_D>(db.pooling, db.node_emb, db.b.node_off, db.emb, db.b.num_graphs, s);
             }
-            if (db.node_emb && db.pooling == POOL_OP_SUM) {  // the storing instance's readout is the mean: the sum from its rows, which are in HBM
+            if (plan.sum_from_rows) {
                 ProfScope p(prof, "mean_pool_linear", s);
                 launch_pool_linear<GCN_D>(db.pooling, db.node_emb, db.b.node_off, d_pw_, d_pb_, db.out, db.b.num_graphs, s);
             }
-            if (db.node_emb && db.node_logits) {  // node embeddings on as well: the rows are in HBM, the terms are taken from them
+            if (plan.node_logits_from_rows) {
                 ProfScope p(prof, "node_logits", s);
                 launch_node_logits_rows<GCN_D>(db.node_emb, d_pw_, d_pb_, db.node_logits, n, 1, s);
             }
-            agg_ready_ = false;
             db.final_h = 0;
             db.h_valid = false;  // h[0] holds x_0, not x_4: flowgnn_get_h repeats the pass on the per-layer kernels
             return 0;
         }
         if (int rc = prepare_aggregate(db, prof, s)) return rc;
         int cur = 0;
-        if (split_ && !exact_ && fused_) {
-            ProfScope p(prof, "gcn_encoder_dense", s);  // x_0 = W_0 (atom encoder) + b_0 in one kernel
+        if (plan.fused_encoder) {
+            ProfScope p(prof, "gcn_encoder_dense", s);
             const long long wgs = ceil_div_ll(n, 256);
             gcn_encoder_dense_kernel<<<(int)(wgs < 256 ? wgs : 256), 1024, 0, s>>>(db.b.node_feature, d_nemb_, db.h[cur], d_split_, n,
                                                                                    db.csr.err, db.range_flag);
@@ -1431,7 +1422,7 @@ public:
             launch_dense(0, db.scratch, db.h[cur], n, db.range_flag, s);  // x_0 = W_0 h0 + b_0
         }
         for (int l = 1; l < GCN_L; l++) {
-            if (split_ && !exact_ && fused_ && db.b.e_tot > 0) {
+            if (plan.fused_layers) {
                 ProfScope p(prof, "gcn_layer_fused", s);
                 const long long wgs = ceil_div_ll(n, 128);
                 const int grid = (int)(wgs < 512 ? wgs : 512);  // persistent: two 8-wave workgroups per CU (71 KB of LDS each)
@@ -1454,10 +1445,8 @@ public:
         }
         db.final_h = cur;
         db.h_valid = true;
-        if (split_ && !exact_ && fused_ && db.b.e_tot > 0 && num_tasks_ == 1 && !db.emb && !db.node_emb && db.pooling != POOL_OP_MAX) {
-            // (the maximum un-folds it: W . max is not a maximum of per-node scores; the sum keeps the fold)
-            // last stage: aggregation + BatchNorm with the readout's linear head folded in (per-node scores in db.scratch;
-            // flowgnn_get_h returns x_4 = db.h[final_h], which is untouched by this)
+        if (plan.folded_last) {
+            // per-node scores in db.scratch; flowgnn_get_h returns x_4 = db.h[final_h], which is untouched by this
             {
                 ProfScope p(prof, "gcn_layer_fused", s);
                 const long long wgs = ceil_div_ll(n, 128);
@@ -1468,7 +1457,7 @@ public:
             }
             ProfScope p(prof, "mean_pool_linear", s);
             if (int rc = launch_segment_bias(db.pooling, db.scratch, db.b.node_off, d_pb_, db.out, db.b.num_graphs, s)) return rc;
-            if (db.node_logits) {  // node logits: the per-node scores plus the head's bias
+            if (plan.node_logits_from_scores) {
                 ProfScope p2(prof, "node_logits", s);
                 node_logits_bias_kernel<0><<<(n + 255) / 256, 256, 0, s>>>(db.scratch, d_pb_, db.node_logits, n);
             }
@@ -1482,16 +1471,16 @@ public:
         }
         {
             ProfScope p(prof, "mean_pool_linear", s);
-            if (num_tasks_ > 1) {  // NUM_TASK outputs per graph (linear_input_stationary over [NUM_TASK][100], GCN/src/finalize.cc:79-113)
+            if (plan.multi_task)  // linear_input_stationary over [NUM_TASK][100], GCN/src/finalize.cc:79-113
                 launch_pool_linear_mt<GCN_D>(db.pooling, rows, db.b.node_off, d_pw_, d_pb_, db.out, db.b.num_graphs, num_tasks_, s);
-            } else
-            launch_pool_linear<GCN_D>(db.pooling, rows, db.b.node_off, d_pw_, d_pb_, db.out, db.b.num_graphs, s);
+            else
+                launch_pool_linear<GCN_D>(db.pooling, rows, db.b.node_off, d_pw_, d_pb_, db.out, db.b.num_graphs, s);
         }
-        if (db.emb) {
+        if (plan.pool_rows) {
             ProfScope p(prof, "mean_pool_rows", s);
             launch_pool_rows<GCN_D>(db.pooling, rows, db.b.node_off, db.emb, db.b.num_graphs, s);
         }
-        if (db.node_logits) {  // node logits from the rows the readout pools, every task
+        if (plan.node_logits_from_rows) {  // every task
             ProfScope p(prof, "node_logits", s);
             launch_node_logits_rows<GCN_D>(rows, d_pw_, d_pb_, db.node_logits, n, num_tasks_, s);
         }
@@ -1519,7 +1508,7 @@ public:
     void set_exact(bool on) override { exact_ = on; }
 
     int aggregation_only(DeviceBatch& db, int layer, hipStream_t s) override {
-        if (qmode_) return 8;  // FLOWGNN_ERR_UNSUPPORTED: the fixed-point forward never builds the float kernels' inputs (tiles, h rows)
+        if (plan(db).path == GcnPath::FixedPoint) return 8;  // FLOWGNN_ERR_UNSUPPORTED: that forward never builds the float kernels' inputs (tiles, h rows)
         if (layer < 0 || layer >= GCN_L) return 1;
         if (!agg_ready_) {  // the last forward ran the graph-resident kernel
             Profiler none;
