@@ -39,6 +39,9 @@ def _declare(lib):
     lib.flowgnn_load_weights_dir.argtypes = [eng, C.c_char_p]
     lib.flowgnn_set_batch.argtypes = [eng, C.c_int, p_int, p_int, p_int, p_int, p_int, p_float]
     lib.flowgnn_set_batch_device.argtypes = [eng, C.c_int, p_int, p_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.flowgnn_laplacian_eigen_max_nodes.argtypes = []
+    lib.flowgnn_laplacian_eigen.argtypes = [eng, C.c_int, p_int, p_int, p_int, p_float]
+    lib.flowgnn_laplacian_eigen_device.argtypes = [eng, C.c_int, p_int, p_int, C.c_int, C.c_void_p, C.c_void_p]
     lib.flowgnn_set_job_totals.argtypes = [eng, C.c_longlong, C.c_longlong]
     lib.flowgnn_run.argtypes = [eng]
     lib.flowgnn_sync.argtypes = [eng]
@@ -153,6 +156,7 @@ def _declare(lib):
                  "flowgnn_set_attention_buffers", "flowgnn_group_set_attention", "flowgnn_group_get_attention",
                  "flowgnn_set_pooling", "flowgnn_pooling", "flowgnn_group_set_pooling", "flowgnn_entry_set_pooling",
                  "flowgnn_set_gin_eps", "flowgnn_gin_eps", "flowgnn_group_set_gin_eps", "flowgnn_entry_set_gin_eps",
+                 "flowgnn_laplacian_eigen_max_nodes", "flowgnn_laplacian_eigen", "flowgnn_laplacian_eigen_device",
                  "GIN_compute_graphs_mt", "GCN_compute_graphs_mt", "GIN_compute_graphs", "GCN_compute_graphs", "PNA_compute_graphs", "DGN_compute_graphs", "GAT_compute_graphs"):
         getattr(lib, name).restype = C.c_int
 

@@ -189,6 +189,9 @@ void host_parallel_for(int parts, const std::function<void(int)>& fn);
 // ingest.hip
 void launch_ingest_pyg(const long long* x, const long long* ei, const long long* ea, int* nf, int* el, int* ea_out, const int* noff,
                        const int* eoff, int G, long long N, long long E, int* err, int x_err, int device, hipStream_t s);
+// eigen.hip
+void launch_laplacian_eigen(int cls, const int* list, int count, const int* noff, const int* eoff, const void* edges, long long E,
+                            bool pyg, float* out, hipStream_t s);
 
 // the packed arrays back into the reference's int32 layout (what every kernel reads): 255 / 65 535 = "did not fit" -> -1, which the
 // validation on the device refuses as it would have refused the original value
@@ -410,6 +413,9 @@ int flowgnn_destroy(flowgnn_engine* e) {
     e->drop_graph();
     e->free_batch();
     for (const Output& o : kOutputs) (e->*o.slot).own.release();
+    e->eig_plan.release();
+    e->eig_io.release();
+    if (e->eig_done) (void)hipEventDestroy(e->eig_done);
     if (e->d_err) (void)hipFree(e->d_err);
     delete e->model;
     if (e->own_stream) (void)hipStreamDestroy(e->own_stream);
@@ -760,18 +766,18 @@ int flowgnn_set_batch(flowgnn_engine* e, int num_graphs, const int* nums_of_node
 
 // flowgnn_set_batch_device's guard: a non-empty array must be memory of the engine's device, and the bytes the counts imply must lie
 // inside its allocation (with XNACK off, a kernel that reads pageable host memory or runs past an allocation faults the device)
-static int check_device_array(const flowgnn_engine* e, const void* p, size_t bytes, const char* what) {
+static int check_device_array(const flowgnn_engine* e, const void* p, size_t bytes, const char* what, const char* api = "flowgnn_set_batch_device") {
     if (!p || bytes == 0) return 0;
     char msg[256];
     hipPointerAttribute_t a{};
     if (hipPointerGetAttributes(&a, p) != hipSuccess) {
         (void)hipGetLastError();
-        snprintf(msg, sizeof(msg), "flowgnn_set_batch_device: %s is not memory the HIP runtime knows (pageable host memory?)", what);
+        snprintf(msg, sizeof(msg), "%s: %s is not memory the HIP runtime knows (pageable host memory?)", api, what);
         fg::set_last_error(msg);  // (ENGINE_TRY hands it to the engine)
         return FLOWGNN_ERR_ARG;
     }
     if (a.type != hipMemoryTypeDevice || a.device != e->device) {
-        snprintf(msg, sizeof(msg), "flowgnn_set_batch_device: %s is not device memory of device %d (memory type %d, device %d)", what,
+        snprintf(msg, sizeof(msg), "%s: %s is not device memory of device %d (memory type %d, device %d)", api, what,
                  e->device, (int)a.type, a.device);
         fg::set_last_error(msg);  // (ENGINE_TRY hands it to the engine)
         return FLOWGNN_ERR_ARG;
@@ -780,14 +786,14 @@ static int check_device_array(const flowgnn_engine* e, const void* p, size_t byt
     size_t size = 0;
     if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) {
         (void)hipGetLastError();
-        snprintf(msg, sizeof(msg), "flowgnn_set_batch_device: no allocation range for %s", what);
+        snprintf(msg, sizeof(msg), "%s: no allocation range for %s", api, what);
         fg::set_last_error(msg);  // (ENGINE_TRY hands it to the engine)
         return FLOWGNN_ERR_ARG;
     }
     const uintptr_t lo = (uintptr_t)p, end = (uintptr_t)base + size;
     if (lo < (uintptr_t)base || bytes > end - lo) {
-        snprintf(msg, sizeof(msg), "flowgnn_set_batch_device: %s holds %zu bytes from this pointer to the end of its allocation, the counts imply %zu",
-                 what, (size_t)(end > lo ? end - lo : 0), bytes);
+        snprintf(msg, sizeof(msg), "%s: %s holds %zu bytes from this pointer to the end of its allocation, the counts imply %zu",
+                 api, what, (size_t)(end > lo ? end - lo : 0), bytes);
         fg::set_last_error(msg);  // (ENGINE_TRY hands it to the engine)
         return FLOWGNN_ERR_ARG;
     }
@@ -841,6 +847,106 @@ int flowgnn_set_batch_device(flowgnn_engine* e, int num_graphs, const int* nums_
         }
     }
     return FLOWGNN_OK;
+}
+
+// ---- flowgnn_laplacian_eigen*: DGN's node_eigen from the graphs alone (kernels: eigen.hip).  Nothing of the resident batch, the
+// recorded launch sequence or the output slots is touched: the engine lends its device, its launch stream and scratch of its own.
+// The plan both functions share: counts -> offsets and the three size-class lists, one upload, one launch per non-empty class.
+static int laplacian_eigen_classes(flowgnn_engine* e, const char* api, int num_graphs, const int* nums_of_nodes, std::vector<int> (&cls)[3]) {
+    for (int g = 0; g < num_graphs; g++) {
+        const int n = nums_of_nodes[g];
+        if (n > FLOWGNN_EIGEN_MAX_NODES) {
+            char msg[160];
+            snprintf(msg, sizeof(msg), "%s: graph %d has %d nodes, the eigensolver takes up to %d", api, g, n, FLOWGNN_EIGEN_MAX_NODES);
+            e->err = msg;
+            return FLOWGNN_ERR_UNSUPPORTED;
+        }
+        cls[n <= 32 ? 0 : n <= 64 ? 1 : 2].push_back(g);
+    }
+    return FLOWGNN_OK;
+}
+static int laplacian_eigen_launch(flowgnn_engine* e, const char* api, const std::vector<int> (&cls)[3], const BatchCounts& c, bool pyg,
+                                  const void* d_edges, float* d_out) {
+    // the previous call's kernels read eig_plan: wait for them before it is rewritten (or regrown)
+    if (e->eig_done) EHIP_TRY(e, hipEventSynchronize(e->eig_done));
+    else EHIP_TRY(e, hipEventCreateWithFlags(&e->eig_done, hipEventDisableTiming));
+    std::vector<int> plan(c.noff);
+    const size_t at_eoff = plan.size(), at_list = at_eoff + c.eoff.size();
+    ENGINE_TRY(e, upload_concat(e, e->eig_plan, true, plan, {&c.eoff, &cls[0], &cls[1], &cls[2]}));
+    const int* const d_plan = (const int*)e->eig_plan.p;
+    size_t at = at_list;
+    for (int k = 0; k < 3; k++) {
+        fg::launch_laplacian_eigen(k, d_plan + at, (int)cls[k].size(), d_plan, d_plan + at_eoff, d_edges, c.E, pyg, d_out, e->stream);
+        at += cls[k].size();
+    }
+    const hipError_t he = hipGetLastError();
+    if (he != hipSuccess) return EHIP_FAIL(e, api, he);
+    EHIP_TRY(e, hipEventRecord(e->eig_done, e->stream));
+    return FLOWGNN_OK;
+}
+
+int flowgnn_laplacian_eigen_max_nodes(void) { return FLOWGNN_EIGEN_MAX_NODES; }
+
+int flowgnn_laplacian_eigen_device(flowgnn_engine* e, int num_graphs, const int* nums_of_nodes, const int* nums_of_edges, int layout,
+                                   const void* edge_list, float* node_eigen) {
+    static const char* const api = "flowgnn_laplacian_eigen_device";
+    BatchCounts c;
+    const int rc = batch_counts(e, num_graphs, nums_of_nodes, nums_of_edges, &c);
+    if (rc) return rc;
+    if (layout != FLOWGNN_LAYOUT_REFERENCE && layout != FLOWGNN_LAYOUT_PYG) {
+        e->err = "flowgnn_laplacian_eigen_device: unknown layout";
+        return FLOWGNN_ERR_ARG;
+    }
+    if (num_graphs == 0) return FLOWGNN_OK;
+    const size_t N = (size_t)c.N, E = (size_t)c.E;
+    if (!node_eigen || (E > 0 && !edge_list)) {
+        e->err = "flowgnn_laplacian_eigen_device: edge_list or node_eigen is NULL";
+        return FLOWGNN_ERR_ARG;
+    }
+    const size_t w = layout == FLOWGNN_LAYOUT_PYG ? sizeof(long long) : sizeof(int);
+    ENGINE_TRY(e, use_device(e));
+    ENGINE_TRY(e, check_device_array(e, edge_list, w * E * 2, "edge_list", api));
+    ENGINE_TRY(e, check_device_array(e, node_eigen, sizeof(float) * N * 4, "node_eigen", api));
+    std::vector<int> cls[3];
+    if (const int crc = laplacian_eigen_classes(e, api, num_graphs, nums_of_nodes, cls)) return crc;
+    return laplacian_eigen_launch(e, api, cls, c, layout == FLOWGNN_LAYOUT_PYG, edge_list, node_eigen);
+}
+
+int flowgnn_laplacian_eigen(flowgnn_engine* e, int num_graphs, const int* nums_of_nodes, const int* nums_of_edges, const int* edge_list,
+                            float* node_eigen) {
+    static const char* const api = "flowgnn_laplacian_eigen";
+    BatchCounts c;
+    const int rc = batch_counts(e, num_graphs, nums_of_nodes, nums_of_edges, &c);
+    if (rc) return rc;
+    if (num_graphs == 0) return FLOWGNN_OK;
+    const size_t N = (size_t)c.N, E = (size_t)c.E;
+    if (!node_eigen || (E > 0 && !edge_list)) {
+        e->err = "flowgnn_laplacian_eigen: edge_list or node_eigen is NULL";
+        return FLOWGNN_ERR_ARG;
+    }
+    std::vector<int> cls[3];
+    if (const int crc = laplacian_eigen_classes(e, api, num_graphs, nums_of_nodes, cls)) return crc;
+    for (int g = 0; g < num_graphs; g++) {
+        const int n = nums_of_nodes[g];
+        for (int i = c.eoff[g]; i < c.eoff[g + 1]; i++) {
+            const int u = edge_list[2 * (size_t)i], v = edge_list[2 * (size_t)i + 1];
+            if (u < 0 || u >= n || v < 0 || v >= n) {
+                char msg[160];
+                snprintf(msg, sizeof(msg), "%s: edge %d of graph %d is (%d, %d), the graph has %d nodes", api, i - c.eoff[g], g, u, v, n);
+                e->err = msg;
+                return FLOWGNN_ERR_EDGE_RANGE;
+            }
+        }
+    }
+    ENGINE_TRY(e, use_device(e));
+    if (e->eig_done) EHIP_TRY(e, hipEventSynchronize(e->eig_done));  // (eig_io may be regrown: nothing reads it any more)
+    const size_t edge_bytes = (sizeof(int) * E * 2 + 15) / 16 * 16;
+    EHIP_TRY(e, e->eig_io.reserve(edge_bytes + sizeof(float) * N * 4, true));
+    float* const d_out = (float*)((char*)e->eig_io.p + edge_bytes);
+    ENGINE_TRY(e, h2d_sync(e, e->eig_io.p, edge_list, sizeof(int) * E * 2));
+    if (const int lrc = laplacian_eigen_launch(e, api, cls, c, false, e->eig_io.p, d_out)) return lrc;
+    EHIP_TRY(e, hipStreamSynchronize(e->stream));
+    return d2h_sync(e, node_eigen, d_out, sizeof(float) * N * 4, api);
 }
 
 int flowgnn_run(flowgnn_engine* e) {

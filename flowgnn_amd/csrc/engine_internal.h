@@ -86,6 +86,12 @@ struct flowgnn_engine {
     bool has_attr = false, has_eig = false;
     fg::DeviceBatch db{};
 
+    // flowgnn_laplacian_eigen*: no part of the resident batch.  eig_plan: node / edge offsets and the three size-class lists of the
+    // call, in one allocation; eig_io: the host function's edge list and output on the device; eig_done: behind the last call's
+    // kernels on the launch stream (the next call waits for it before it rewrites eig_plan)
+    fg::GrowBuf eig_plan, eig_io;
+    hipEvent_t eig_done = nullptr;
+
     int numeric_mode = FLOWGNN_NUMERIC_F32;
     int pooling = FLOWGNN_POOL_MEAN;  // flowgnn_set_pooling: the engine's, across batches (db.pooling follows it)
     bool gin_eps_on = false;          // flowgnn_set_gin_eps: the engine's too, across batches and weight sets (db.gin_eps_on / gin_self_scale follow)

@@ -2,7 +2,7 @@
 // OpenCL host (GIN/src/host.cc): load the model's .bin weights, read a graph pack in the reference's on-disk
 // layout, run the whole dataset as ONE batched launch NUM_TRIALS times, write HLS_output.txt.
 //
-//   host <MODEL> [--graphs DIR] [--weights DIR] [--num-graphs N] [--trials T] [--out FILE] [--node-logits FILE] [--attention FILE [--attention-layers MASK]] [--device D | --devices D0,D1,..] [--option key=value] [--numeric f32|q6.10|f16] [--eps] [XCLBIN]
+//   host <MODEL> [--graphs DIR] [--weights DIR] [--num-graphs N] [--trials T] [--out FILE] [--node-logits FILE] [--attention FILE [--attention-layers MASK]] [--device D | --devices D0,D1,..] [--option key=value] [--numeric f32|q6.10|f16] [--eps] [--eig DIR | --compute-eig] [XCLBIN]
 //
 //   MODEL        GIN | GIN-VN | GCN | GAT | PNA | DGN
 //   --graphs     directory holding graph_info/ and graph_bin/      (default ../graphs, host.cc:14-15)
@@ -16,6 +16,8 @@
 //                `layer edge h0 h1 h2 h3`, edges in the pack's order; --attention-layers: the layer mask (default 16, the last layer)
 //   --eps        GIN / GIN-VN: read gin_ep1_eps_dim100.bin (five LE float32) from the weights directory and apply it (flowgnn_set_gin_eps);
 //                without the flag the file stays ignored, as in the reference
+//   --eig        DGN: directory holding the eigenvector text files g%d.txt                 (default eig, DGN/src/host_load.cc:178)
+//   --compute-eig DGN: compute node_eigen from the graphs on the GPU (flowgnn_laplacian_eigen, on the first engine) and read no --eig DIR
 //   XCLBIN       accepted and ignored, so `./host <xclbin>`-style command lines keep working
 //
 // Only the C ABI of include/flowgnn.h is used; no HIP or torch types here.
@@ -81,7 +83,7 @@ static bool read_eig_txt(const std::string& path, std::vector<float>& eig, size_
 int main(int argc, char** argv) {
     if (argc < 2) {
         fprintf(stderr, "Usage: %s <GIN|GIN-VN|GCN|GAT|PNA|DGN> [--graphs DIR] [--weights DIR] [--num-graphs N] [--trials T] "
-                        "[--out FILE] [--embeddings FILE] [--node-embeddings FILE] [--node-logits FILE] [--attention FILE [--attention-layers MASK]] [--device D | --devices D0,D1,..] [--option key=value] [--numeric f32|q6.10|f16] [--pooling mean|sum|max] [--eps] [--num-tasks T] [XCLBIN File]\n", argv[0]);
+                        "[--out FILE] [--embeddings FILE] [--node-embeddings FILE] [--node-logits FILE] [--attention FILE [--attention-layers MASK]] [--device D | --devices D0,D1,..] [--option key=value] [--numeric f32|q6.10|f16] [--pooling mean|sum|max] [--eps] [--num-tasks T] [--eig DIR | --compute-eig] [XCLBIN File]\n", argv[0]);
         return EXIT_FAILURE;
     }
     const std::string model = argv[1];
@@ -91,7 +93,7 @@ int main(int argc, char** argv) {
     long num_graphs = -1;
     int attn_mask = 16;
     int trials = 25, numeric = FLOWGNN_NUMERIC_F32, num_tasks = 1, pooling = FLOWGNN_POOL_MEAN;
-    bool use_eps = false;
+    bool use_eps = false, compute_eig = false;
     std::vector<int> devices;
     std::vector<std::pair<std::string, double>> options;
     for (int i = 2; i < argc; i++) {
@@ -136,6 +138,7 @@ int main(int argc, char** argv) {
             if (m != "mean" && m != "sum" && m != "max") { fprintf(stderr, "--pooling wants mean, sum or max\n"); return EXIT_FAILURE; }
             pooling = m == "sum" ? FLOWGNN_POOL_SUM : m == "max" ? FLOWGNN_POOL_MAX : FLOWGNN_POOL_MEAN;
         }
+        else if (a == "--compute-eig") compute_eig = true;  // DGN: node_eigen from the graphs themselves (flowgnn_laplacian_eigen), no --eig DIR
         else if (a == "--eps") use_eps = true;  // the trained eps of the weights directory (flowgnn_set_gin_eps; GIN / GIN-VN)
         // anything else (e.g. an .xclbin path) is ignored
     }
@@ -206,9 +209,11 @@ int main(int argc, char** argv) {
         }
         if (dgn) {
             eig.resize((N + n2) * 4, 0.0f);
-            char ep[512];
-            snprintf(ep, sizeof(ep), "%s/g%ld.txt", eig_dir.c_str(), g);
-            if (!read_eig_txt(ep, eig, N, n)) { fprintf(stderr, "cannot read %s\n", ep); return EXIT_FAILURE; }
+            if (!compute_eig) {
+                char ep[512];
+                snprintf(ep, sizeof(ep), "%s/g%ld.txt", eig_dir.c_str(), g);
+                if (!read_eig_txt(ep, eig, N, n)) { fprintf(stderr, "cannot read %s\n", ep); return EXIT_FAILURE; }
+            }
         }
         nn[g - 1] = n2;
         ne[g - 1] = e2;
@@ -217,6 +222,11 @@ int main(int argc, char** argv) {
         if (g % 1000 == 0 || g == num_graphs) { printf("(%ld/%ld) Loading graphs ...\r", g, num_graphs); fflush(stdout); }
     }
     printf("\n******* Graphs loading done *******\n");
+    if (dgn && compute_eig) {
+        flowgnn_engine* first = flowgnn_group_engine(eng, 0);
+        rc = flowgnn_laplacian_eigen(first, (int)num_graphs, nn.data(), ne.data(), el.data(), eig.data());
+        if (rc) { fprintf(stderr, "--compute-eig: %d %s\n", rc, flowgnn_last_error(first)); return EXIT_FAILURE; }
+    }
 
     rc = flowgnn_group_set_batch(eng, (int)num_graphs, nn.data(), ne.data(), nf.data(), el.data(), ea.data(), dgn ? eig.data() : nullptr);
     if (rc) { fprintf(stderr, "flowgnn_set_batch failed: %d %s\n", rc, flowgnn_group_last_error(eng)); return EXIT_FAILURE; }

@@ -68,6 +68,11 @@ def embedding_dim(model: str) -> int:
     return int(_lib.load().flowgnn_embedding_dim(_lib.MODEL_IDS[model]))
 
 
+def laplacian_eigen_max_nodes() -> int:
+    """The largest graph Engine.laplacian_eigen takes (flowgnn.h: flowgnn_laplacian_eigen_max_nodes); host code only, no GPU needed."""
+    return int(_lib.load().flowgnn_laplacian_eigen_max_nodes())
+
+
 def attention_shape(model: str):
     """(layers, heads) of a model's attention coefficients (flowgnn.h: flowgnn_attention_shape): (5, 4) for GAT, FlowGNNError with
     code 8 for the models that have none; host code only, no GPU needed."""
@@ -242,23 +247,29 @@ class Engine:
                 raise ValueError(f"{name} is not contiguous")
             if shape is not None and (t.dim() != 2 or t.shape[1] != shape[1] or (shape[0] >= 0 and t.shape[0] != shape[0])):
                 raise ValueError(f"{name}: shape {tuple(t.shape)}, expected [{'N' if shape[0] < 0 else shape[0]}][{shape[1]}]")
+        return (layout,) + self._graph_counts(edge_index, layout, n_e, ptr, nums_of_edges, n_rows=x.shape[0])
+
+    def _graph_counts(self, edge_index, layout, n_e, ptr, nums_of_edges, n_rows=None):
+        """(nums_of_nodes, nums_of_edges) as host arrays from `ptr` ([G + 1], any device; it must end at n_rows when that is given)
+        and, when no edge counts are given (PyG layout only), from each edge's source id."""
+        import torch
         if ptr is None:
             raise ValueError("ptr (the node pointer, [G + 1]) is required")
         ptr_h = ptr.detach().to("cpu", torch.int64).numpy() if isinstance(ptr, torch.Tensor) else np.asarray(ptr, dtype=np.int64)
         nn = np.diff(ptr_h)
-        if ptr_h.size < 1 or ptr_h[0] != 0 or ptr_h[-1] != x.shape[0]:
+        if ptr_h.size < 1 or ptr_h[0] != 0 or (n_rows is not None and ptr_h[-1] != n_rows):
             raise ValueError("ptr must run from 0 to N (the rows of x)")
         if nums_of_edges is None:
             if layout != "pyg":
                 raise ValueError("the reference layout holds local ids: pass nums_of_edges")
             # each edge's graph from its source id, bucketed against ptr (the edges of a PyG Batch are grouped by graph)
-            gid = torch.bucketize(edge_index[0], torch.as_tensor(ptr_h[1:], device=dev), right=True)
+            gid = torch.bucketize(edge_index[0], torch.as_tensor(ptr_h[1:], device=edge_index.device), right=True)
             ne = torch.bincount(gid, minlength=len(nn))[: len(nn)].cpu().numpy()
             if int(ne.sum()) != n_e:
                 raise ValueError("edge_index[0] holds ids outside [0, N): pass nums_of_edges")
         else:
             ne = (nums_of_edges.detach().cpu().numpy() if isinstance(nums_of_edges, torch.Tensor) else np.asarray(nums_of_edges))
-        return layout, nn, ne
+        return nn, ne
 
     def set_batch_device(self, x, edge_index, edge_attr=None, node_eigen=None, *, ptr, nums_of_edges=None):
         """A batch whose arrays are torch tensors on the engine's device (flowgnn.h: flowgnn_set_batch_device).  The layout follows
@@ -346,6 +357,54 @@ class Engine:
         ret = (logits,) + ((emb,) if return_embeddings else ()) + ((rows,) if return_node_embeddings else ()) + ((terms,) if return_node_logits else ())
         ret += (attn,) if attn is not None else ()
         return ret if len(ret) > 1 else logits
+
+    # ---- DGN's Laplacian eigenvectors (flowgnn.h: flowgnn_laplacian_eigen)
+    def laplacian_eigen(self, batch: GraphBatch) -> np.ndarray:
+        """node_eigen, float32 [N][4], of a host batch, computed on the GPU: per graph the eigenvectors of the four smallest
+        eigenvalues of its normalised Laplacian (graphpack.laplacian_eigen is the same definition on the CPU).  Graphs of up to
+        laplacian_eigen_max_nodes() nodes; any model's engine will do, and its resident batch is left alone."""
+        nn, ne, el = _i32(batch.nums_of_nodes), _i32(batch.nums_of_edges), _i32(batch.edge_list)
+        out = np.empty((int(nn.sum(dtype=np.int64)), 4), dtype=np.float32)
+        self._check(self.lib.flowgnn_laplacian_eigen(self._h, len(nn), _pi(nn), _pi(ne), _pi(el), _pf(out)), "flowgnn_laplacian_eigen")
+        return out
+
+    def laplacian_eigen_device_ptrs(self, nums_of_nodes, nums_of_edges, layout: str, edge_list: int, node_eigen: int):
+        """flowgnn_laplacian_eigen_device with raw DEVICE addresses (ints), for callers without torch: counts are host arrays,
+        `layout` as in set_batch_device_ptrs; asynchronous on the engine's launch stream (stream_handle())."""
+        nn, ne = _i32(nums_of_nodes), _i32(nums_of_edges)
+        if layout not in _lib.LAYOUT_IDS:
+            raise ValueError(f"unknown layout {layout!r} (pyg / reference)")
+        ptrs = [C.c_void_p(int(p)) if p else None for p in (edge_list, node_eigen)]
+        self._check(self.lib.flowgnn_laplacian_eigen_device(self._h, len(nn), _pi(nn), _pi(ne), _lib.LAYOUT_IDS[layout], *ptrs),
+                    "flowgnn_laplacian_eigen_device")
+
+    def laplacian_eigen_device(self, edge_index, *, ptr, nums_of_edges=None):
+        """node_eigen of a batch whose edges are a torch tensor on the engine's device, into a new float32 [N][4] tensor there:
+        int64 edge_index [2][E] with batch-global ids (a PyG Batch) or int32 edge_list [E][2] with local ids; `ptr` and
+        `nums_of_edges` as for set_batch_device.  Ordered against torch's streams the way set_batch_device is -- the engine's stream
+        after torch's current one, torch's current one after the kernels -- so
+        forward_device(x, ei, None, eng.laplacian_eigen_device(ei, ptr=ptr), ptr=ptr) needs no synchronisation."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if edge_index.dtype == torch.int64 and edge_index.dim() == 2 and edge_index.shape[0] == 2:
+            layout, n_e = "pyg", int(edge_index.shape[1])
+        elif edge_index.dtype == torch.int32 and edge_index.dim() == 2 and edge_index.shape[1] == 2:
+            layout, n_e = "reference", int(edge_index.shape[0])
+        else:
+            raise TypeError("edge_index: int64 [2][E] (PyG layout) or int32 [E][2] (reference layout)")
+        if edge_index.device != dev:
+            raise ValueError(f"edge_index is on {edge_index.device}, the engine on {dev}")
+        if not edge_index.is_contiguous():
+            raise ValueError("edge_index is not contiguous")
+        nn, ne = self._graph_counts(edge_index, layout, n_e, ptr, nums_of_edges)
+        cur = torch.cuda.current_stream(dev)
+        out = torch.empty((int(nn.sum()), 4), dtype=torch.float32, device=dev)
+        es = torch.cuda.ExternalStream(self.stream_handle(), device=dev)
+        es.wait_stream(cur)
+        self.laplacian_eigen_device_ptrs(nn, ne, layout, edge_index.data_ptr(), out.data_ptr())
+        cur.wait_stream(es)  # (and the allocator may recycle edge_index only behind the kernels: see set_batch_device)
+        edge_index.record_stream(cur)
+        return out
 
     def run(self):
         self._check(self.lib.flowgnn_run(self._h), "flowgnn_run")

@@ -311,3 +311,35 @@ def add_virtual_nodes(batch: GraphBatch) -> GraphBatch:
         (batch.nums_of_nodes + 1).astype(np.int32),
         (batch.nums_of_edges + 2 * batch.nums_of_nodes).astype(np.int32),
         np.concatenate(nfs), np.concatenate(els), np.concatenate(eas), None)
+
+
+# --------------------------------------------------------------------------- DGN's Laplacian eigenvectors
+LAPLACIAN_EIGEN_MAX_NODES = 128  # flowgnn.h: FLOWGNN_EIGEN_MAX_NODES (the GPU path's limit; this CPU path has none)
+
+
+def normalized_laplacian(n: int, edges) -> np.ndarray:
+    """L = I - D^-1/2 A D^-1/2 of one graph, float64 [n][n]: A[u][v] = A[v][u] = 1 for every edge (u, v) with u != v (both
+    directions and duplicates collapse to 1, self loops and endpoints outside [0, n) are ignored), d = max(1, row sums of A)."""
+    a = np.zeros((n, n), dtype=np.float64)
+    e = np.asarray(edges, dtype=np.int64).reshape(-1, 2)
+    e = e[(e[:, 0] != e[:, 1]) & (e >= 0).all(axis=1) & (e < n).all(axis=1)]
+    a[e[:, 0], e[:, 1]] = 1.0
+    a[e[:, 1], e[:, 0]] = 1.0
+    dinv = 1.0 / np.sqrt(np.maximum(a.sum(axis=1), 1.0))
+    return np.eye(n) - dinv[:, None] * a * dinv[None, :]
+
+
+def laplacian_eigen(batch: GraphBatch) -> np.ndarray:
+    """DGN's node_eigen, float32 [N_tot][4], from the graphs alone: for each graph the eigenvectors of the four smallest
+    eigenvalues of its normalised Laplacian (normalized_laplacian; numpy.linalg.eigh in float64, ascending, unit 2-norm),
+    node_eigen[noff[g] + i][k] = v_k[i] for k < min(4, n) and 0 for k >= n.  The sign of a vector is whatever eigh leaves (DGN
+    sees neither the sign nor the scale of column 1); inside a repeated eigenvalue the basis is arbitrary but orthonormal.
+    The definition Engine.laplacian_eigen computes on the GPU, and its reference."""
+    no, eo = batch.node_offsets(), batch.edge_offsets()
+    out = np.zeros((batch.total_nodes, 4), dtype=np.float32)
+    for g in range(batch.num_graphs):
+        n = int(batch.nums_of_nodes[g])
+        _, vec = np.linalg.eigh(normalized_laplacian(n, batch.edge_list[eo[g]:eo[g + 1]]))
+        k = min(4, n)
+        out[no[g]:no[g + 1], :k] = vec[:, :k]
+    return out

@@ -595,6 +595,37 @@ int flowgnn_set_gin_eps(flowgnn_engine* e, const float* eps /* [5], NULL = off *
 int flowgnn_gin_eps(const flowgnn_engine* e, float* eps_out /* [5], may be NULL */);   /* 1 on, 0 off, -1 null handle */
 
 /*
+ * Laplacian eigenvectors: DGN's node_eigen from the graphs alone (the reference reads it from DGN/eig/g%d.txt and does not say where it
+ * comes from).  For graph g with n nodes and edges (u, v) in local ids:
+ *     A[u][v] = A[v][u] = 1 for every edge with u != v   (both directions and duplicates collapse to 1, self loops are ignored)
+ *     d[i] = max(1, sum_j A[i][j]),   L = I - D^-1/2 A D^-1/2          (an isolated node has L[i][i] = 1)
+ *     node_eigen[noff[g] + i][k] = v_k[i] for k < min(4, n), 0 for k >= n,   (lambda_k, v_k) the eigenpairs of L, lambda ascending,
+ * every v_k of unit 2-norm -- what the upstream DGN preprocessing computes for a graph that lists both directions of its edges.  The
+ * sign of a vector is whatever the rotations leave (DGN sees neither the sign nor the scale of column 1); inside a repeated
+ * eigenvalue the basis is arbitrary but orthonormal.  fp32: a cyclic Jacobi iteration in on-chip memory, one workgroup per graph
+ * (DESIGN.md section 4.13); residual |L v - lambda v| <= 8 max(n, 8) 2^-24.  A graph's vectors depend on that graph alone: they are
+ * bit-identical whatever the batch order, the slice, the other graphs of the call, or which of the two functions computes them.
+ *  Any model's engine will do: only its device and its launch stream are used.  Neither function touches the resident batch, a
+ *  recorded launch sequence (option hipgraph) or any output.  FLOWGNN_ERR_ARG for nulls and bad counts, as flowgnn_set_batch gives;
+ *  FLOWGNN_ERR_UNSUPPORTED, with a flowgnn_last_error text naming the first such graph, for a graph of more than
+ *  FLOWGNN_EIGEN_MAX_NODES nodes -- nothing is launched or written then.  num_graphs == 0: FLOWGNN_OK, nothing is launched.
+ *  flowgnn_laplacian_eigen_max_nodes: 128.  Needs no GPU.
+ *  flowgnn_laplacian_eigen: host arrays, synchronous (upload, run, copy back); FLOWGNN_ERR_EDGE_RANGE for an endpoint outside [0, n).
+ *  flowgnn_laplacian_eigen_device: flowgnn_set_batch_device's contract -- host counts, DEVICE edge_list in either layout
+ *     (FLOWGNN_LAYOUT_REFERENCE: int32 [E][2], local ids; FLOWGNN_LAYOUT_PYG: int64 [2][E], batch-global ids, made local as
+ *     id - noff[g]) and DEVICE node_eigen (float32 [N][4]), both checked as that function checks its arrays; asynchronous on the
+ *     engine's launch stream, so a following flowgnn_set_batch_device that reads node_eigen needs no event; an edge with an endpoint
+ *     outside its graph is skipped (flowgnn_set_batch_device refuses such a batch afterwards anyway).  Offsets and size-class lists
+ *     live in engine-owned scratch that only grows: no allocation per call in the steady state.
+ */
+#define FLOWGNN_EIGEN_MAX_NODES 128
+int flowgnn_laplacian_eigen_max_nodes(void);
+int flowgnn_laplacian_eigen(flowgnn_engine* e, int num_graphs, const int* nums_of_nodes, const int* nums_of_edges,
+                            const int* edge_list /* host [E][2], local ids */, float* node_eigen /* host [N][4] */);
+int flowgnn_laplacian_eigen_device(flowgnn_engine* e, int num_graphs, const int* nums_of_nodes, const int* nums_of_edges,
+                                   int layout, const void* edge_list /* device */, float* node_eigen /* device [N][4] */);
+
+/*
  * Run-time switches, by name (the full list with defaults: the option table in flowgnn_amd/csrc/engine.hip, or
  * flowgnn_option_count / flowgnn_option_name).  They select between kernels that compute the SAME results -- e.g.
  * "gin_resident" 0 = one launch per layer, "gin_mfma" 32 = fp32 matrix pipe instead of three f16 products, "pna_fused" 0 =
