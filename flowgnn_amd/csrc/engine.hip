@@ -8,6 +8,7 @@
 // Several engines behind one handle: group.hip; the reference's <M>_compute_graphs symbols: entry.hip.
 #include "engine_internal.h"
 #include "tile_pack.h"
+#include "gin_ogbvn.h"
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -415,6 +416,7 @@ int flowgnn_destroy(flowgnn_engine* e) {
     for (const Output& o : kOutputs) (e->*o.slot).own.release();
     e->eig_plan.release();
     e->eig_io.release();
+    e->ogb_vn.release();
     if (e->eig_done) (void)hipEventDestroy(e->eig_done);
     if (e->d_err) (void)hipFree(e->d_err);
     delete e->model;
@@ -714,6 +716,7 @@ static int set_batch_state(flowgnn_engine* e, int num_graphs, const int* nums_of
     db.pooling = e->pooling;
     db.gin_eps_on = e->gin_eps_on;
     for (int l = 0; l < 5; l++) db.gin_self_scale[l] = (float)(1.0f + e->gin_eps[l]);
+    db.ogb_vn = e->ogb_vn_on ? (const float*)e->ogb_vn.p : nullptr;
     db.final_h = 0;
     db.tap = nullptr;
     db.tap_dim = 0;
@@ -1317,6 +1320,10 @@ int flowgnn_set_numeric_mode(flowgnn_engine* e, int mode) {
         e->err = "flowgnn_set_numeric_mode: a trained eps is on (flowgnn_set_gin_eps), and the fixed-point arithmetic is the reference's, which has no eps";
         return FLOWGNN_ERR_UNSUPPORTED;
     }
+    if (mode == FLOWGNN_NUMERIC_Q6_10 && e->ogb_vn_on) {
+        e->err = "flowgnn_set_numeric_mode: OGB's virtual node is on (flowgnn_set_ogb_virtual_node), and the fixed-point arithmetic is the reference's, which has no such model";
+        return FLOWGNN_ERR_UNSUPPORTED;
+    }
     e->drop_graph();
     const int rc = e->model->set_numeric_mode(mode);
     if (!rc) e->numeric_mode = mode;
@@ -1386,6 +1393,53 @@ int flowgnn_gin_eps(const flowgnn_engine* e, float* eps_out) {
         for (int l = 0; l < 5; l++) eps_out[l] = e->gin_eps[l];
     return e->gin_eps_on ? 1 : 0;
 }
+
+int flowgnn_set_ogb_virtual_node(flowgnn_engine* e, const float* vn_embedding, const float* w1, const float* b1, const float* w2, const float* b2) {
+    if (!e) return FLOWGNN_ERR_ARG;
+    if (e->model_id != FLOWGNN_MODEL_GIN) {
+        e->err = "flowgnn_set_ogb_virtual_node: OGB's virtual node exists for GIN only (GIN-VN is the reference's augmentation, a different model)";
+        return FLOWGNN_ERR_UNSUPPORTED;
+    }
+    const float* const t[5] = {vn_embedding, w1, b1, w2, b2};
+    const size_t count[5] = {100, (size_t)FLOWGNN_OGB_VN_LAYERS * FLOWGNN_OGB_VN_HIDDEN * 100, (size_t)FLOWGNN_OGB_VN_LAYERS * FLOWGNN_OGB_VN_HIDDEN,
+                             (size_t)FLOWGNN_OGB_VN_LAYERS * 100 * FLOWGNN_OGB_VN_HIDDEN, (size_t)FLOWGNN_OGB_VN_LAYERS * 100};
+    int given = 0;
+    for (int i = 0; i < 5; i++) given += t[i] != nullptr;
+    if (given != 0 && given != 5) {
+        e->err = "flowgnn_set_ogb_virtual_node: some of the five tensors are NULL and some are not (all five: on, all NULL: off)";
+        return FLOWGNN_ERR_ARG;
+    }
+    const bool on = given == 5;
+    if (on) {
+        static const char* const names[5] = {"vn_embedding", "w1", "b1", "w2", "b2"};
+        for (int i = 0; i < 5; i++)
+            for (size_t k = 0; k < count[i]; k++)
+                if (!std::isfinite(t[i][k])) {
+                    e->err = std::string("flowgnn_set_ogb_virtual_node: ") + names[i] + "[" + std::to_string(k) + "] is not finite";
+                    return FLOWGNN_ERR_ARG;
+                }
+        if (e->numeric_mode == FLOWGNN_NUMERIC_Q6_10) {
+            e->err = "flowgnn_set_ogb_virtual_node: the fixed-point arithmetic (FLOWGNN_NUMERIC_Q6_10) is the reference's, which has no such model";
+            return FLOWGNN_ERR_UNSUPPORTED;
+        }
+    }
+    ENGINE_TRY(e, begin_change(e));  // (an idle stream: a run in flight may still read the tensors this call replaces)
+    if (on) {
+        std::vector<float> packed(fg::GIN_OGBVN_FLOATS);
+        fg::gin_ogbvn_pack(vn_embedding, w1, b1, w2, b2, packed.data());
+        EHIP_TRY(e, e->ogb_vn.reserve(sizeof(float) * packed.size(), false));
+        EHIP_TRY(e, hipMemcpy(e->ogb_vn.p, packed.data(), sizeof(float) * packed.size(), hipMemcpyHostToDevice));
+    }
+    if (int rc = e->model->set_ogb_virtual_node(on)) {
+        e->err = "flowgnn_set_ogb_virtual_node: this model has no such kernel";
+        return rc;
+    }
+    e->ogb_vn_on = on;
+    e->db.ogb_vn = on ? (const float*)e->ogb_vn.p : nullptr;  // (launches are stream-ordered: it matters to those enqueued after this call)
+    return FLOWGNN_OK;
+}
+
+int flowgnn_ogb_virtual_node(const flowgnn_engine* e) { return e ? (e->ogb_vn_on ? 1 : 0) : -1; }
 
 int flowgnn_set_option(flowgnn_engine* e, const char* key, double value) {
     if (!e || !key) return FLOWGNN_ERR_ARG;
@@ -1491,6 +1545,7 @@ int flowgnn_run_aggregation_only(flowgnn_engine* e, int layer, int iters, float*
     if (!e || iters <= 0) return FLOWGNN_ERR_ARG;
     if (!e->ran) { e->err = "flowgnn_run_aggregation_only needs a prior flowgnn_run"; return FLOWGNN_ERR_STATE; }
     if (e->gin_eps_on) { e->err = "flowgnn_run_aggregation_only: a trained eps is on (flowgnn_set_gin_eps), and the stand-alone aggregation kernel has no eps instance"; return FLOWGNN_ERR_UNSUPPORTED; }
+    if (e->ogb_vn_on) { e->err = "flowgnn_run_aggregation_only: OGB's virtual node is on (flowgnn_set_ogb_virtual_node), and the stand-alone aggregation kernel does not add it"; return FLOWGNN_ERR_UNSUPPORTED; }
     ENGINE_TRY(e, use_device(e));
     e->drop_graph();
     int rc = e->model->aggregate_dim() > 0 ? ensure_rows(e) : FLOWGNN_OK;  // the kernel's input rows (a resident run left none)
@@ -1522,6 +1577,7 @@ int flowgnn_get_aggregate(flowgnn_engine* e, int layer, float* h_in_host, int* i
     if (!e) return FLOWGNN_ERR_ARG;
     if (!e->ran) { e->err = "flowgnn_get_aggregate needs a prior flowgnn_run"; return FLOWGNN_ERR_STATE; }
     if (e->gin_eps_on) { e->err = "flowgnn_get_aggregate: a trained eps is on (flowgnn_set_gin_eps), and the stand-alone aggregation kernel has no eps instance"; return FLOWGNN_ERR_UNSUPPORTED; }
+    if (e->ogb_vn_on) { e->err = "flowgnn_get_aggregate: OGB's virtual node is on (flowgnn_set_ogb_virtual_node), and the stand-alone aggregation kernel does not add it"; return FLOWGNN_ERR_UNSUPPORTED; }
     int rc = flowgnn_sync(e);
     if (rc) return rc;
     e->drop_graph();

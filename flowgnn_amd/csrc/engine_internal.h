@@ -96,6 +96,8 @@ struct flowgnn_engine {
     int pooling = FLOWGNN_POOL_MEAN;  // flowgnn_set_pooling: the engine's, across batches (db.pooling follows it)
     bool gin_eps_on = false;          // flowgnn_set_gin_eps: the engine's too, across batches and weight sets (db.gin_eps_on / gin_self_scale follow)
     float gin_eps[5] = {0, 0, 0, 0, 0};
+    bool ogb_vn_on = false;           // flowgnn_set_ogb_virtual_node: the engine's as well (db.ogb_vn follows it)
+    fg::GrowBuf ogb_vn;               // ... and its five tensors on the device (gin_ogbvn.h: GIN_OGBVN_FLOATS)
 
     // the optional outputs (fg::OutSlot): graph embeddings [G][dim] (flowgnn_set_embeddings), node embeddings [N][dim]
     // (flowgnn_set_node_embeddings), node logits [N][num_tasks] (flowgnn_set_node_logits) and, for GAT, the attention coefficients

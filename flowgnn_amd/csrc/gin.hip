@@ -7,6 +7,9 @@
 //             (flowgnn_set_gin_eps: a = m_l[v] + s_l h_l[v], s_l = 1 + eps[l] -- the eps instances)
 //   hid     = b1 + W1 a  (200x100),  h_{l+1} = b2 + W2 relu(hid) (100x200)   node_embedding.cc:124-191
 //   out[g]  = pb + pw . mean_v h_5[v]                                        finalize.cc:36-113
+// OGB's own virtual node (flowgnn_set_ogb_virtual_node, GIN only -- not the reference's GIN-VN, whose virtual node is a node of the
+// batch): h_l[v] += vn_l[g(v)] in front of EVERY layer and a per-graph MLP between layers, one launch per layer in front of the
+// per-layer kernels (gin_ogbvn.hip); the graph-resident kernels are not used then.
 //
 // Here: the whole batch is one super-graph in HBM, h is [N_tot][100] fp32 (row stride
 // 100 floats, rows of a graph contiguous), and per layer there are two kernels:
@@ -17,6 +20,7 @@
 #include "common.h"
 #include "device_common.h"
 #include "gin_split.h"
+#include "gin_ogbvn.h"
 #include "ginq.h"
 #include <cstring>
 #include <cstdio>
@@ -793,8 +797,9 @@ public:
     bool use_resident(const DeviceBatch& db) const {
         // tiles that are mostly empty (graphs of 130..256 nodes, or dense graphs that hit the edge limit first) waste the
         // MFMA columns of the absent rows: below half full the per-layer kernels are the better choice
+        // (OGB's virtual node, db.ogb_vn: the per-layer loop alone has its launch -- and with it one_pass() and use_pingpong() say no)
         return resident_ && table_ok_ && fused_ && split_ && !exact_ && db.gtiles.ok && db.gtiles.n_tiles > 0 && db.gtiles.fill >= resident_min_fill_ &&
-               (!db.gin_eps_on || eps_resident(db));
+               (!db.gin_eps_on || eps_resident(db)) && !db.ogb_vn;
     }
     // A trained eps (flowgnn_set_gin_eps) has ONE resident instance set, gin_resident_eps_kernel: single task, mean pooling, folded head,
     // no extra outputs and no taps.  Every other configuration takes the per-layer kernels' eps instances -- never an eps-less kernel.
@@ -824,12 +829,16 @@ public:
     bool needs_csr(const DeviceBatch& db) const override { return !one_pass(db); }
     // (asked at flowgnn_set_batch, before the batch is known: the lists are built whenever the one-pass path could take them)
     bool wants_packed_tile_lists() const override {
-        return binpack_ && resident_ && !qmode_ && num_tasks_ == 1 && fold_readout_ && head_fold_ && tile_build_ != 0 && (!pingpong_ || f16_);
+        return binpack_ && resident_ && !qmode_ && !ogb_vn_ && num_tasks_ == 1 && fold_readout_ && head_fold_ && tile_build_ != 0 && (!pingpong_ || f16_);
     }
 
     int forward(DeviceBatch& db, Profiler& prof, hipStream_t s) override {
         const int n = db.b.n_tot;
         if (n <= 0) return 0;
+        if (db.ogb_vn && (qmode_ || virtual_node_)) {  // (the engine refuses both itself: no kernel here may run without the vector while it is on)
+            set_last_error("flowgnn_run: OGB's virtual node (flowgnn_set_ogb_virtual_node) exists for GIN in the float modes only");
+            return 8;  // FLOWGNN_ERR_UNSUPPORTED
+        }
         if (qmode_) return ginq_forward(qw_, db, prof, s);
         if (db.gin_eps_on && !fused_) {  // (the engine refuses eps in the fixed-point mode itself)
             set_last_error("flowgnn_run: gin_unfused 1 (the aggregate + mlp kernels) has no eps instance (flowgnn_set_gin_eps); set gin_unfused 0");
@@ -959,7 +968,14 @@ public:
         }
         int cur = 0;
         bool folded = false;
+        // OGB's virtual node: vn_l [G][100] lives in a buffer of the model's own that only grows (vn_0 = E is read from the tensors)
+        if (db.ogb_vn)
+            if (int rc = ogb_vn_state_.reserve((size_t)db.b.num_graphs * GIN_D)) return rc;
         for (int l = 0; l < GIN_L; l++) {
+            if (db.ogb_vn) {  // x_l = h_l + vn_l in place (the last layer too), and vn_{l+1} from the sums of x_l -- whatever form the layer takes
+                ProfScope p(prof, "gin_ogb_vn", s);
+                launch_gin_ogbvn(db.h[cur], db.b.node_off, db.b.num_graphs, db.ogb_vn, ogb_vn_state_.p, l, s);
+            }
             // (node embeddings: the last layer writes h_5 straight into the caller's buffer, and the readout reads it there)
             float* const hn = (l == GIN_L - 1 && db.node_emb) ? db.node_emb : db.h[cur ^ 1];
             if (fused_ && split_ && !exact_) {
@@ -1096,6 +1112,11 @@ public:
         f16_ = mode == 2;
         return 0;
     }
+    int set_ogb_virtual_node(bool on) override {
+        if (on && virtual_node_) return 8;  // GIN-VN is the reference's augmentation: a different model
+        ogb_vn_ = on;
+        return 0;
+    }
     int set_num_tasks(int t) override {
         if (t < 1 || (t != 1 && qmode_)) return 8;
         if (t != num_tasks_) ready_ = false;  // graph_pred_weights / bias change shape: set the weights again
@@ -1104,7 +1125,8 @@ public:
     }
 
     int aggregation_only(DeviceBatch& db, int layer, hipStream_t s) override {
-        if (qmode_) return 8;  // FLOWGNN_ERR_UNSUPPORTED: the fixed-point forward never builds the float kernels' inputs (tiles, h rows)
+        if (qmode_ || ogb_vn_) return 8;  // FLOWGNN_ERR_UNSUPPORTED: the fixed-point forward never builds the float kernels' inputs (tiles, h rows);
+                                          // with OGB's virtual node on, the rows in HBM are x_l of some layer, not an input of `layer`
         if (layer < 0 || layer >= GIN_L) return 1;
         if (!h0_in_hbm_) {  // the last run was the one-pass resident path: the probe's input rows (h_0) were never written to HBM
             atom_encoder_kernel<GIN_D><<<atom_encoder_grid(db.b.n_tot, GIN_C), 512, 0, s>>>(db.b.node_feature, d_nemb_, db.h[0], db.b.n_tot, db.csr.err);
@@ -1151,6 +1173,7 @@ private:
         enc_idx_.release();
         perm_.release();
         pooled_.release();
+        ogb_vn_state_.release();
         qw_.release();
     }
     bool ready_ = false;
@@ -1174,6 +1197,8 @@ private:
     int num_tasks_ = 1;   // NUM_TASK (GIN/src/dcl.h:25) as a run-time dimension
     GinQWeights qw_;
     GrowBuf pooled_;  // FLOWGNN_POOL_MAX with graph embeddings off: the [G][100] per-column maxima the resident pooling instance leaves for the head
+    bool ogb_vn_ = false;    // flowgnn_set_ogb_virtual_node is on (the tensors themselves: DeviceBatch::ogb_vn)
+    GrowBuf ogb_vn_state_;   // ... and the per-graph vectors vn_l [G][100], rewritten in place by each layer's launch
     GrowBufI perm_;  // graph-resident path: per-tile descriptors (gin_tile_prep_kernel / gin_tile_build_kernel)
     GrowBufI enc_idx_;  // one-pass path: three table-row numbers per node in one word, written by gin_tile_build_kernel
     float* d_enc_tab_ = nullptr;  // ... and the pre-combined encoder table they index

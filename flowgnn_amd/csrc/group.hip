@@ -234,6 +234,9 @@ int flowgnn_group_set_num_tasks(flowgnn_group* g, int num_tasks) {
 int flowgnn_group_set_numeric_mode(flowgnn_group* g, int mode) { return group_all(g, [&](flowgnn_engine* e) { return flowgnn_set_numeric_mode(e, mode); }); }
 int flowgnn_group_set_pooling(flowgnn_group* g, int mode) { return group_all(g, [&](flowgnn_engine* e) { return flowgnn_set_pooling(e, mode); }); }
 int flowgnn_group_set_gin_eps(flowgnn_group* g, const float* eps) { return group_all(g, [&](flowgnn_engine* e) { return flowgnn_set_gin_eps(e, eps); }); }
+int flowgnn_group_set_ogb_virtual_node(flowgnn_group* g, const float* vn_embedding, const float* w1, const float* b1, const float* w2, const float* b2) {
+    return group_all(g, [&](flowgnn_engine* e) { return flowgnn_set_ogb_virtual_node(e, vn_embedding, w1, b1, w2, b2); });
+}
 
 int flowgnn_group_set_embeddings(flowgnn_group* g, int on) { return group_all(g, [&](flowgnn_engine* e) { return flowgnn_set_embeddings(e, on); }); }
 int flowgnn_group_set_node_embeddings(flowgnn_group* g, int on) { return group_all(g, [&](flowgnn_engine* e) { return flowgnn_set_node_embeddings(e, on); }); }

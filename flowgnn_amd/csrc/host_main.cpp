@@ -2,7 +2,7 @@
 // OpenCL host (GIN/src/host.cc): load the model's .bin weights, read a graph pack in the reference's on-disk
 // layout, run the whole dataset as ONE batched launch NUM_TRIALS times, write HLS_output.txt.
 //
-//   host <MODEL> [--graphs DIR] [--weights DIR] [--num-graphs N] [--trials T] [--out FILE] [--node-logits FILE] [--attention FILE [--attention-layers MASK]] [--device D | --devices D0,D1,..] [--option key=value] [--numeric f32|q6.10|f16] [--eps] [--eig DIR | --compute-eig] [XCLBIN]
+//   host <MODEL> [--graphs DIR] [--weights DIR] [--num-graphs N] [--trials T] [--out FILE] [--node-logits FILE] [--attention FILE [--attention-layers MASK]] [--device D | --devices D0,D1,..] [--option key=value] [--numeric f32|q6.10|f16] [--eps] [--ogb-vn] [--eig DIR | --compute-eig] [XCLBIN]
 //
 //   MODEL        GIN | GIN-VN | GCN | GAT | PNA | DGN
 //   --graphs     directory holding graph_info/ and graph_bin/      (default ../graphs, host.cc:14-15)
@@ -16,6 +16,8 @@
 //                `layer edge h0 h1 h2 h3`, edges in the pack's order; --attention-layers: the layer mask (default 16, the last layer)
 //   --eps        GIN / GIN-VN: read gin_ep1_eps_dim100.bin (five LE float32) from the weights directory and apply it (flowgnn_set_gin_eps);
 //                without the flag the file stays ignored, as in the reference
+//   --ogb-vn     GIN: read gin_ep1_virtualnode_dim100.bin (161 300 LE float32: vn_embedding, w1, b1, w2, b2) from the weights directory and
+//                run OGB's virtual node (flowgnn_set_ogb_virtual_node) -- an exported gin-virtual checkpoint; usually together with --eps
 //   --eig        DGN: directory holding the eigenvector text files g%d.txt                 (default eig, DGN/src/host_load.cc:178)
 //   --compute-eig DGN: compute node_eigen from the graphs on the GPU (flowgnn_laplacian_eigen, on the first engine) and read no --eig DIR
 //   XCLBIN       accepted and ignored, so `./host <xclbin>`-style command lines keep working
@@ -83,7 +85,7 @@ static bool read_eig_txt(const std::string& path, std::vector<float>& eig, size_
 int main(int argc, char** argv) {
     if (argc < 2) {
         fprintf(stderr, "Usage: %s <GIN|GIN-VN|GCN|GAT|PNA|DGN> [--graphs DIR] [--weights DIR] [--num-graphs N] [--trials T] "
-                        "[--out FILE] [--embeddings FILE] [--node-embeddings FILE] [--node-logits FILE] [--attention FILE [--attention-layers MASK]] [--device D | --devices D0,D1,..] [--option key=value] [--numeric f32|q6.10|f16] [--pooling mean|sum|max] [--eps] [--num-tasks T] [--eig DIR | --compute-eig] [XCLBIN File]\n", argv[0]);
+                        "[--out FILE] [--embeddings FILE] [--node-embeddings FILE] [--node-logits FILE] [--attention FILE [--attention-layers MASK]] [--device D | --devices D0,D1,..] [--option key=value] [--numeric f32|q6.10|f16] [--pooling mean|sum|max] [--eps] [--ogb-vn] [--num-tasks T] [--eig DIR | --compute-eig] [XCLBIN File]\n", argv[0]);
         return EXIT_FAILURE;
     }
     const std::string model = argv[1];
@@ -93,7 +95,7 @@ int main(int argc, char** argv) {
     long num_graphs = -1;
     int attn_mask = 16;
     int trials = 25, numeric = FLOWGNN_NUMERIC_F32, num_tasks = 1, pooling = FLOWGNN_POOL_MEAN;
-    bool use_eps = false, compute_eig = false;
+    bool use_eps = false, use_ogb_vn = false, compute_eig = false;
     std::vector<int> devices;
     std::vector<std::pair<std::string, double>> options;
     for (int i = 2; i < argc; i++) {
@@ -140,6 +142,7 @@ int main(int argc, char** argv) {
         }
         else if (a == "--compute-eig") compute_eig = true;  // DGN: node_eigen from the graphs themselves (flowgnn_laplacian_eigen), no --eig DIR
         else if (a == "--eps") use_eps = true;  // the trained eps of the weights directory (flowgnn_set_gin_eps; GIN / GIN-VN)
+        else if (a == "--ogb-vn") use_ogb_vn = true;  // OGB's virtual node from the weights directory (flowgnn_set_ogb_virtual_node; GIN)
         // anything else (e.g. an .xclbin path) is ignored
     }
     if (num_graphs < 0) num_graphs = read_count_file(graphs + "/dataset_size.txt");
@@ -175,6 +178,15 @@ int main(int argc, char** argv) {
         if (!read_exact(path, eps, 0, 5)) { fprintf(stderr, "--eps: cannot read five floats from %s\n", path.c_str()); return EXIT_FAILURE; }
         rc = flowgnn_group_set_gin_eps(eng, eps.data());
         if (rc) { fprintf(stderr, "--eps: %d %s\n", rc, flowgnn_group_last_error(eng)); return EXIT_FAILURE; }
+    }
+    if (use_ogb_vn) {
+        const size_t H = FLOWGNN_OGB_VN_HIDDEN, L = FLOWGNN_OGB_VN_LAYERS, D = 100;
+        const size_t at[6] = {0, D, D + L * H * D, D + L * H * D + L * H, D + 2 * L * H * D + L * H, D + 2 * L * H * D + L * H + L * D};
+        std::vector<float> vn(at[5]);
+        const std::string path = wdir + "/gin_ep1_virtualnode_dim100.bin";
+        if (!read_exact(path, vn, 0, vn.size())) { fprintf(stderr, "--ogb-vn: cannot read %zu floats from %s\n", vn.size(), path.c_str()); return EXIT_FAILURE; }
+        rc = flowgnn_group_set_ogb_virtual_node(eng, vn.data() + at[0], vn.data() + at[1], vn.data() + at[2], vn.data() + at[3], vn.data() + at[4]);
+        if (rc) { fprintf(stderr, "--ogb-vn: %d %s\n", rc, flowgnn_group_last_error(eng)); return EXIT_FAILURE; }
     }
     printf("\n******* Weights loading done *******\n");
 

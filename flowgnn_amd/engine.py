@@ -53,6 +53,15 @@ def _eps_arg(eps):
     return (C.c_float * 5)(*a.tolist())
 
 
+def _ogb_vn_args(vn):
+    """None -> five NULLs (off); else the dict's five tensors (weights.GIN_VIRTUAL_NODE_SHAPES) as float32 arrays, in the C call's
+    order -- the caller keeps them alive for the duration of the call."""
+    if vn is None:
+        return [None] * 5
+    from .weights import checked_gin_virtual_node
+    return list(checked_gin_virtual_node(vn).values())
+
+
 def option_value(v) -> float:
     """Option values are numbers; "f32" / "f16" (the *_mfma switches) read as 32 / 16."""
     if isinstance(v, str) and v in ("f32", "f16"):
@@ -161,12 +170,16 @@ class Engine:
         ptrs = (_lib.p_float * len(arrs))(*[_pf(a) for a in arrs])
         self._check(self.lib.flowgnn_set_weights(self._h, len(arrs), ptrs), "flowgnn_set_weights")
 
-    def load_weights_dir(self, directory: str, eps: bool = False):
-        """eps=True (GIN, GIN-VN): also read the directory's eps file and apply it (set_gin_eps); the C call itself never does."""
+    def load_weights_dir(self, directory: str, eps: bool = False, virtual_node: bool = False):
+        """eps=True (GIN, GIN-VN): also read the directory's eps file and apply it (set_gin_eps); virtual_node=True (GIN): also read
+        gin_ep1_virtualnode_dim100.bin and apply it (set_ogb_virtual_node).  The C call itself does neither."""
         self._check(self.lib.flowgnn_load_weights_dir(self._h, directory.encode()), "flowgnn_load_weights_dir")
         if eps:
             from .weights import load_gin_eps
             self.set_gin_eps(load_gin_eps(directory))
+        if virtual_node:
+            from .weights import load_gin_virtual_node
+            self.set_ogb_virtual_node(load_gin_virtual_node(directory))
 
     # ---- batch
     def set_job_totals(self, job_nodes: int = -1, job_edges: int = -1):
@@ -568,6 +581,17 @@ class Engine:
         out = np.zeros(5, np.float32)
         return out if int(self.lib.flowgnn_gin_eps(self._h, _pf(out))) == 1 else None
 
+    def set_ogb_virtual_node(self, vn=None):
+        """GIN: run OGB's virtual node (gnn_type='gin-virtual'; flowgnn.h: flowgnn_set_ogb_virtual_node).  `vn`: a dict with the keys
+        vn_embedding [100], w1 [4][200][100], b1 [4][200], w2 [4][100][200], b2 [4][100] (BatchNorms folded:
+        export.gin_virtual_node_from_ogb_state_dict); None turns it off.  The engine's, across batches and weight sets."""
+        a = _ogb_vn_args(vn)
+        self._check(self.lib.flowgnn_set_ogb_virtual_node(self._h, *[_pf(x) for x in a]), "flowgnn_set_ogb_virtual_node")
+
+    def ogb_virtual_node(self) -> bool:
+        """Whether OGB's virtual node is on (flowgnn.h: flowgnn_ogb_virtual_node)."""
+        return int(self.lib.flowgnn_ogb_virtual_node(self._h)) == 1
+
     def exact_reruns(self) -> int:
         """Forward passes repeated on the exact-fp32 kernels (flowgnn.h: flowgnn_exact_reruns)."""
         return int(self.lib.flowgnn_exact_reruns(self._h))
@@ -685,6 +709,11 @@ class EngineGroup:
     def set_gin_eps(self, eps=None):
         """Engine.set_gin_eps on every member (flowgnn.h: flowgnn_group_set_gin_eps)."""
         self._check(self.lib.flowgnn_group_set_gin_eps(self._h, _eps_arg(eps)), "flowgnn_group_set_gin_eps")
+
+    def set_ogb_virtual_node(self, vn=None):
+        """Engine.set_ogb_virtual_node on every member (flowgnn.h: flowgnn_group_set_ogb_virtual_node)."""
+        a = _ogb_vn_args(vn)
+        self._check(self.lib.flowgnn_group_set_ogb_virtual_node(self._h, *[_pf(x) for x in a]), "flowgnn_group_set_ogb_virtual_node")
 
     def set_batch(self, batch: GraphBatch):
         nn, ne = _i32(batch.nums_of_nodes), _i32(batch.nums_of_edges)

@@ -77,16 +77,48 @@ def gin_eps_from_ogb_state_dict(sd: Mapping, num_layers: int = 5) -> np.ndarray:
     return out
 
 
+VN_KEY = "gnn_node.virtualnode_embedding.weight"  # what tells a gin-virtual state_dict from a gin one
+
+
+def gin_virtual_node_from_ogb_state_dict(sd: Mapping, num_layers: int = 5) -> Dict[str, np.ndarray]:
+    """The virtual node of an OGB `GNN(gnn_type='gin-virtual')` state_dict as the five tensors Engine.set_ogb_virtual_node /
+    flowgnn_set_ogb_virtual_node take: `gnn_node.virtualnode_embedding.weight` [1][100] and, per update l < num_layers - 1,
+    `gnn_node.mlp_virtualnode_list.l` = Linear-BatchNorm-ReLU-Linear-BatchNorm-ReLU (OGB: .0 .1 .3 .4) or Linear-ReLU-Linear-ReLU
+    (.0 .2).  Both BatchNorms (inference statistics) sit in front of a ReLU and are folded into the linear layer before them: exact."""
+    emb = _get(sd, VN_KEY).reshape(-1)
+    w1s, b1s, w2s, b2s = [], [], [], []
+    for l in range(num_layers - 1):
+        m = f"gnn_node.mlp_virtualnode_list.{l}"
+        w1, b1 = _get(sd, f"{m}.0.weight"), _get(sd, f"{m}.0.bias")
+        if f"{m}.1.running_mean" in sd:
+            w1, b1 = _fold_bn(w1, b1, sd, f"{m}.1")
+            w2, b2 = _get(sd, f"{m}.3.weight"), _get(sd, f"{m}.3.bias")
+            if f"{m}.4.running_mean" in sd:
+                w2, b2 = _fold_bn(w2, b2, sd, f"{m}.4")
+        else:
+            w2, b2 = _get(sd, f"{m}.2.weight"), _get(sd, f"{m}.2.bias")
+        w1s.append(w1); b1s.append(b1); w2s.append(w2); b2s.append(b2)
+    out = OrderedDict([("vn_embedding", emb), ("w1", np.stack(w1s)), ("b1", np.stack(b1s)), ("w2", np.stack(w2s)), ("b2", np.stack(b2s))])
+    return _checked(out, _weights.GIN_VIRTUAL_NODE_SHAPES, lambda k, v: v)
+
+
 def gin_weights_from_ogb_state_dict(sd: Mapping, num_layers: int = 5, eps_tol: float = 0.0, multi_task: bool = False,
-                                    keep_eps: bool = False) -> Dict[str, np.ndarray]:
+                                    keep_eps: bool = False, virtual_node: bool = False) -> Dict[str, np.ndarray]:
     """OGB `GNN(gnn_type='gin', virtual_node=False, JK='last', residual=False, graph_pooling='mean')` -> the reference's
     GIN weight set.  `convs.l.mlp` may be Linear-BatchNorm-ReLU-Linear (OGB) or Linear-ReLU-Linear; `batch_norms.l`
     (applied to the conv output before the ReLU) is folded into the second linear layer when present.
     multi_task: keep every row of graph_pred_linear (ogbg-molpcba: 128 tasks) -- graph_pred_weights becomes [NUM_TASK][100], for
     an engine with flowgnn_set_num_tasks(NUM_TASK); without it a head with more than one task is refused (the reference's NUM_TASK is 1).
     The reference ignores GIN's eps (GIN/src/host_load.cc reads it, nothing uses it): a trained |eps| > eps_tol is refused, unless
-    keep_eps says that the engine will apply it (gin_eps_from_ogb_state_dict + flowgnn_set_gin_eps)."""
+    keep_eps says that the engine will apply it (gin_eps_from_ogb_state_dict + flowgnn_set_gin_eps).
+    A gin-virtual state_dict (it has `gnn_node.virtualnode_embedding.weight`) is refused -- the weight set alone is a model nobody
+    trained -- unless virtual_node says that the engine will run the virtual node too (gin_virtual_node_from_ogb_state_dict +
+    flowgnn_set_ogb_virtual_node)."""
     p = "gnn_node"
+    if VN_KEY in sd and not virtual_node:
+        raise ExportError(f"the state_dict has '{VN_KEY}': it is OGB's gin-virtual, and these weights without its virtual node are "
+                          f"a model nobody trained; pass virtual_node=True and give the engine gin_virtual_node_from_ogb_state_dict(sd) "
+                          f"(Engine.set_ogb_virtual_node)")
     out = OrderedDict()
     out["node_embedding_weight"] = _tables(sd, f"{p}.atom_encoder.atom_embedding_list", ATOM_DIMS)
     ed, w1s, b1s, w2s, b2s = [], [], [], [], []
@@ -161,15 +193,22 @@ def _checked(w: Dict[str, np.ndarray], spec: Mapping, shape_of) -> Dict[str, np.
     return res
 
 
-def export_weights(model: str, sd: Mapping, directory: str, multi_task: bool = False, keep_eps: bool = False) -> Dict[str, np.ndarray]:
+def export_weights(model: str, sd: Mapping, directory: str, multi_task: bool = False, keep_eps: bool = False,
+                   virtual_node: bool = False) -> Dict[str, np.ndarray]:
     """Write the `.bin` file(s) `host` / `flowgnn_load_weights_dir` read for `model` ('GIN', 'GIN-VN' or 'GCN').
     multi_task: keep all rows of the prediction head (the engine then needs flowgnn_set_num_tasks(rows) before loading).
     keep_eps (GIN, GIN-VN): a trained eps is not refused; the eps file holds the trained values, for `host --eps` /
-    Engine.load_weights_dir(dir, eps=True) to apply (flowgnn_set_gin_eps)."""
+    Engine.load_weights_dir(dir, eps=True) to apply (flowgnn_set_gin_eps).
+    virtual_node (GIN): the state_dict is OGB's gin-virtual; its virtual node goes into gin_ep1_virtualnode_dim100.bin beside the
+    others, for `host GIN --ogb-vn` / Engine.load_weights_dir(dir, virtual_node=True) to apply (flowgnn_set_ogb_virtual_node)."""
     m = model.upper()
+    if virtual_node and m != "GIN":
+        raise ExportError(f"virtual_node=True is OGB's gin-virtual, which the engine runs as GIN (not {model})")
     if m in ("GIN", "GIN-VN"):
-        w = gin_weights_from_ogb_state_dict(sd, multi_task=multi_task, keep_eps=keep_eps)
+        w = gin_weights_from_ogb_state_dict(sd, multi_task=multi_task, keep_eps=keep_eps, virtual_node=virtual_node)
         _weights.save_gin_weights(w, directory, eps=gin_eps_from_ogb_state_dict(sd) if keep_eps else None)
+        if virtual_node:
+            _weights.save_gin_virtual_node(gin_virtual_node_from_ogb_state_dict(sd), directory)
     elif m == "GCN":
         w = gcn_weights_from_ogb_state_dict(sd, multi_task=multi_task)
         _weights.save_gcn_weights(w, directory)

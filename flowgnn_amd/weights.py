@@ -70,6 +70,53 @@ def save_gin_weights(w: Dict[str, np.ndarray], directory: str, eps=None) -> None
     e.tofile(os.path.join(directory, GIN_EPS_FILE))  # (zeros: read by the reference, never used)
 
 
+# OGB's virtual node for GIN (flowgnn.h: flowgnn_set_ogb_virtual_node): one file beside the GIN set, the five tensors in the order of the
+# C call's arguments, BatchNorms folded; name -> shape
+GIN_VIRTUAL_NODE_FILE = "gin_ep1_virtualnode_dim100.bin"
+GIN_VIRTUAL_NODE_SHAPES = OrderedDict([
+    ("vn_embedding", (100,)), ("w1", (4, 200, 100)), ("b1", (4, 200)), ("w2", (4, 100, 200)), ("b2", (4, 100)),
+])
+GIN_VIRTUAL_NODE_FLOATS = sum(int(np.prod(s)) for s in GIN_VIRTUAL_NODE_SHAPES.values())  # 161 300
+
+
+def checked_gin_virtual_node(vn) -> Dict[str, np.ndarray]:
+    """The dict `vn` with exactly the five keys, each as a contiguous float32 array of its shape."""
+    if set(vn) != set(GIN_VIRTUAL_NODE_SHAPES):
+        raise ValueError(f"virtual node: wanted the keys {list(GIN_VIRTUAL_NODE_SHAPES)}, got {sorted(vn)}")
+    out = OrderedDict()
+    for k, shp in GIN_VIRTUAL_NODE_SHAPES.items():
+        a = np.asarray(vn[k], dtype=np.float32)
+        if a.size != int(np.prod(shp)):
+            raise ValueError(f"virtual node: {k} is {a.shape}, wanted {shp}")
+        out[k] = np.ascontiguousarray(a.reshape(shp))
+    return out
+
+
+def save_gin_virtual_node(vn, directory: str) -> None:
+    """Write gin_ep1_virtualnode_dim100.bin: vn_embedding, w1, b1, w2, b2 end to end, little-endian float32.  Nothing applies the
+    file unless asked to: `host GIN --ogb-vn`, Engine.load_weights_dir(dir, virtual_node=True)."""
+    os.makedirs(directory, exist_ok=True)
+    flat = np.concatenate([a.ravel() for a in checked_gin_virtual_node(vn).values()]).astype("<f4")
+    flat.tofile(os.path.join(directory, GIN_VIRTUAL_NODE_FILE))
+
+
+def load_gin_virtual_node(directory: str) -> Dict[str, np.ndarray]:
+    """The five tensors of a directory's virtual-node file (for Engine.set_ogb_virtual_node); a short file is refused."""
+    path = os.path.join(directory, GIN_VIRTUAL_NODE_FILE)
+    out, at = OrderedDict(), 0
+    for k, shp in GIN_VIRTUAL_NODE_SHAPES.items():
+        out[k] = _read(path, shp, at)
+        at += int(np.prod(shp))
+    return out
+
+
+def synth_gin_virtual_node(seed: int = 11, scale: float = 1.0) -> Dict[str, np.ndarray]:
+    """Random virtual-node tensors at the scales of synth_gin_weights' MLP (the virtual node's MLP has the node MLP's shapes)."""
+    rng = np.random.default_rng(seed)
+    s = {"vn_embedding": 0.11, "w1": 0.075, "b1": 0.91, "w2": 0.053, "b2": 0.49}
+    return OrderedDict((k, (rng.standard_normal(shp) * s[k] * scale).astype(np.float32)) for k, shp in GIN_VIRTUAL_NODE_SHAPES.items())
+
+
 def synth_gin_weights(seed: int = 7, num_tasks: int = 1) -> Dict[str, np.ndarray]:
     """Random weights with the measured scales of the shipped GIN set:
     W1 s=0.075, b1 s=0.91, W2 s=0.053, b2 s=0.49, node/edge emb s=0.11/0.14, pred s=0.15."""

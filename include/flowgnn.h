@@ -595,6 +595,40 @@ int flowgnn_set_gin_eps(flowgnn_engine* e, const float* eps /* [5], NULL = off *
 int flowgnn_gin_eps(const flowgnn_engine* e, float* eps_out /* [5], may be NULL */);   /* 1 on, 0 off, -1 null handle */
 
 /*
+ * OGB's virtual node for GIN: the model of ogb/examples/graphproppred/mol with gnn_type = 'gin-virtual'.  It is NOT the reference's
+ * GIN-VN (FLOWGNN_MODEL_GIN_VN), where the host appends an ordinary node joined to every atom: OGB keeps one vector per graph beside
+ * the nodes and updates it with a small MLP between layers.  With D = 100, five GIN layers, and the BatchNorms of the virtual-node MLP
+ * folded into its linear layers (both sit in front of a ReLU, so folding is exact; flowgnn_amd/export.py does it):
+ *     vn_0[g] = vn_embedding                                                      for every graph g
+ *     for l = 0 .. 4:
+ *         x_l[v]  = h_l[v] + vn_l[g(v)]                                           (fp32, one rounding; the last layer too)
+ *         h_{l+1} = GIN layer l applied to x_l                                    (messages, self term with eps if on, MLP, ReLU as ever)
+ *         if l < 4:  t = sum over v in g of x_l[v] + vn_l[g]                      (always a sum, whatever flowgnn_set_pooling says)
+ *                    vn_{l+1}[g] = relu(w2[l] relu(w1[l] t + b1[l]) + b2[l])
+ *     readout: unchanged, on h_5
+ * Tensors (host arrays, copied by the call): vn_embedding [100], w1 [4][200][100], b1 [4][200], w2 [4][100][200], b2 [4][100].
+ * All five NULL turns it off (the default), and then every launch is the one it always was; some but not all NULL, or a value that
+ * is not finite, is FLOWGNN_ERR_ARG.  The setting belongs to the engine, like eps: it holds across batches and flowgnn_set_weights,
+ * it may change between runs on a resident batch, and it drops a recorded launch sequence (option hipgraph).  It combines with eps
+ * (OGB's gin-virtual has both), with every pooling mode, NUM_TASK, the optional outputs, device batches and groups.  In
+ * FLOWGNN_NUMERIC_F16 only the node MLP's operands are rounded, as ever; the virtual node's arithmetic is fp32 FMAs.
+ * Kernels: one launch per layer (profile slot gin_ogb_vn) in front of the per-layer kernels, which every batch takes while it is on
+ * -- the graph-resident kernels do not carry the vector.  A graph's logit has the same bits wherever the
+ * graph stands in a batch, a slice or a group's cut.  flowgnn_get_h returns h_5 as ever; the rows the layers leave in HBM on the way
+ * are x_l (after the add), not h_l.
+ * FLOWGNN_ERR_UNSUPPORTED (flowgnn_last_error says why): any model but FLOWGNN_MODEL_GIN; FLOWGNN_NUMERIC_Q6_10, in both orders of
+ * the two setters; and, while it is on, flowgnn_run_aggregation_only and flowgnn_get_aggregate.
+ * flowgnn_ogb_virtual_node: 1 on, 0 off, -1 for a null handle.  flowgnn_group_set_ogb_virtual_node: the setter on every member.
+ * The reference has no such model, so the reference-compatible <M>_compute_graphs entry points have no form of it.
+ * Files: gin_ep1_virtualnode_dim100.bin beside the GIN set holds the five tensors in this order (161 300 LE float32);
+ * flowgnn_load_weights_dir does not read it; `host GIN --ogb-vn` and the Python wrapper's load_weights_dir(dir, virtual_node=True) do.
+ */
+#define FLOWGNN_OGB_VN_LAYERS 4
+#define FLOWGNN_OGB_VN_HIDDEN 200
+int flowgnn_set_ogb_virtual_node(flowgnn_engine* e, const float* vn_embedding, const float* w1, const float* b1, const float* w2, const float* b2); /* host arrays, copied; all NULL = off */
+int flowgnn_ogb_virtual_node(const flowgnn_engine* e);            /* 1 on, 0 off, -1 null handle */
+
+/*
  * Laplacian eigenvectors: DGN's node_eigen from the graphs alone (the reference reads it from DGN/eig/g%d.txt and does not say where it
  * comes from).  For graph g with n nodes and edges (u, v) in local ids:
  *     A[u][v] = A[v][u] = 1 for every edge with u != v   (both directions and duplicates collapse to 1, self loops are ignored)
@@ -676,6 +710,7 @@ int flowgnn_group_set_num_tasks(flowgnn_group* g, int num_tasks);
 int flowgnn_group_set_numeric_mode(flowgnn_group* g, int mode);
 int flowgnn_group_set_pooling(flowgnn_group* g, int mode);
 int flowgnn_group_set_gin_eps(flowgnn_group* g, const float* eps);
+int flowgnn_group_set_ogb_virtual_node(flowgnn_group* g, const float* vn_embedding, const float* w1, const float* b1, const float* w2, const float* b2);
 int flowgnn_group_set_batch(flowgnn_group* g, int num_graphs,
                             const int* nums_of_nodes, const int* nums_of_edges,
                             const int* node_feature, const int* edge_list, const int* edge_attr,
