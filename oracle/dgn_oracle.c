@@ -1,5 +1,5 @@
 /*
- * dgn_oracle.c -- float restatement of FlowGNN DGN (TEST INFRASTRUCTURE, parity unpinned; see
+ * dgn_oracle.c -- float restatement of FlowGNN DGN (TEST INFRASTRUCTURE, pinned to the reference: DESIGN.md section 2; see
  * flowgnn_oracle.h).  Each block cites the reference lines it follows (paths under /root/reference).
  *
  * Defined deviation: the reference divides the sum aggregate by the node's OUT-degree with no guard

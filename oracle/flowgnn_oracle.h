@@ -1,13 +1,14 @@
 /*
  * flowgnn_oracle.h -- CPU restatement of FlowGNN's NT/MP hot path (TEST INFRASTRUCTURE).
  *
- * PARITY UNPINNED: the reference ships no golden vectors, no tests and no graph
- * packs, and its kernel sources cannot be built
- * in this image without Vitis HLS headers (ap_fixed.h, hls_stream.h, hls_math.h),
- * which are not vendored.  This oracle is therefore a from-reading restatement of
- * the reference algorithm with FM_TYPE = WT_TYPE = float, loop order and
- * summation order preserved; it is cross-checked by an independent float64 NumPy
- * restatement on the batched super-graph (tests/test_oracle_*.py against tests/numpy_ref.py).
+ * The reference ships no golden vectors, no tests and no graph packs (SURVEY.md
+ * section 4, section 8c).  This oracle is a from-reading restatement of the
+ * reference algorithm with FM_TYPE = WT_TYPE = float, loop order and summation
+ * order preserved.  PINNED: the reference's own kernel sources, compiled against
+ * the stand-in headers of oracle/hls_standin (make -C oracle ref), give the same
+ * logits bit for bit (tests/test_reference_pin_cpu.py); it is
+ * also cross-checked by an independent float64 NumPy restatement on the batched
+ * super-graph (tests/test_oracle_*.py against tests/numpy_ref.py).
  *
  * Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may link or
  * call this library.  The product path (flowgnn_amd/) never does.
@@ -77,8 +78,8 @@ int orc_GIN_compute_graphs_mt(int num_graphs, const int* nums_of_nodes, const in
  * (argument order of GCN/src/dcl.h:75-97).  x_dump (optional): [5][N_tot][100], x_l = NT(l) output.
  */
 /*
- * GIN / GIN-VN in the reference's own number format ap_fixed<16,6> (ginq_oracle.c: the rules it assumes, and why
- * it is "parity unpinned").  Float weights are quantised as the reference host does; out_q = 16-bit patterns,
+ * GIN / GIN-VN in the reference's own number format ap_fixed<16,6> (ginq_oracle.c: the rules it assumes, and what
+ * of them is pinned).  Float weights are quantised as the reference host does; out_q = 16-bit patterns,
  * out = out_q / 1024 (either may be NULL); h_dump (optional) int16 [6][N_tot][100].
  */
 #include <stdint.h>
@@ -143,7 +144,7 @@ int orc_GAT_compute_graphs(int num_graphs, const int* nums_of_nodes, const int* 
 
 /*
  * GCN / GAT / PNA (ap_fixed<16,6>) and DGN (ap_fixed<16,3>) in the reference's own number formats: q_oracle.c (the rules it
- * assumes, R0..R8, and why it is "parity unpinned").  model = FLOWGNN_MODEL_* id (2 GCN, 3 GAT, 4 PNA, 5 DGN); tens = the model's
+ * assumes, R0..R8, and what of them is pinned).  model = FLOWGNN_MODEL_* id (2 GCN, 3 GAT, 4 PNA, 5 DGN); tens = the model's
  * float weight tensors in entry-point order ([S] leading), elems[i] = elements of ONE weight set of tensor i; out_q = 16-bit
  * patterns, out = pattern / 2^F (either may be NULL).
  */

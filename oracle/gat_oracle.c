@@ -1,5 +1,5 @@
 /*
- * gat_oracle.c -- float restatement of FlowGNN GAT (TEST INFRASTRUCTURE, parity unpinned; see
+ * gat_oracle.c -- float restatement of FlowGNN GAT (TEST INFRASTRUCTURE, pinned to the reference: DESIGN.md section 2; see
  * flowgnn_oracle.h).  Each block cites the reference lines it follows (paths under /root/reference).
  *
  * Two documented reference quirks:

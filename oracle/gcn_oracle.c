@@ -1,5 +1,5 @@
 /*
- * gcn_oracle.c -- float restatement of FlowGNN GCN (TEST INFRASTRUCTURE, parity unpinned; see
+ * gcn_oracle.c -- float restatement of FlowGNN GCN (TEST INFRASTRUCTURE, pinned to the reference: DESIGN.md section 2; see
  * flowgnn_oracle.h).  Each block cites the reference lines it follows (paths under /root/reference).
  */
 #include "flowgnn_oracle.h"

@@ -1,6 +1,6 @@
 /*
- * gin_oracle.c -- float restatement of FlowGNN GIN (TEST INFRASTRUCTURE, parity
- * unpinned; see flowgnn_oracle.h).  Each block cites the reference lines it follows.
+ * gin_oracle.c -- float restatement of FlowGNN GIN (TEST INFRASTRUCTURE, pinned to the
+ * reference: DESIGN.md section 2; see flowgnn_oracle.h).  Each block cites the reference lines it follows.
  */
 #include "flowgnn_oracle.h"
 #include <stdlib.h>

@@ -3,8 +3,12 @@
  * ap_fixed<16,6> (Q6.10: 16 bits, 10 fractional, truncate toward -inf, wrap on overflow;
  * GIN/src/dcl.h:58-59 with the ap_fixed defaults AP_TRN / AP_WRAP).  TEST INFRASTRUCTURE (see flowgnn_oracle.h).
  *
- * PARITY UNPINNED, doubly: the Vitis ap_fixed.h header is not in this image, so the semantics below are a reading of
- * the published ap_fixed rules, not a run of them:
+ * PINNED to the reference's own sources run in ap_fixed: the kernel sources of GIN/src and GIN-VN/src, compiled against the fixed form of
+ * oracle/hls_standin (make -C oracle ref), give the same 16-bit patterns as this file on every input of
+ * tests/test_reference_pin_cpu.py, so which statement computes and stores what is no longer a reading.  NOT pinned: the
+ * stand-in's ap_fixed is itself written from the published rules (checked against integer formulas, hls_standin/check.cc),
+ * not taken from Vitis, and hls::sqrt / hls::recip (load_inputs.cc:130, whose result GIN never uses) follow R3 / R4 of
+ * q_oracle.c.  The rules, as the stand-in and this file both have them:
  *   - every arithmetic expression is exact in a wider type; quantisation happens only where a value is stored into
  *     an FM_TYPE / WT_TYPE object: floor to a multiple of 2^-10, then keep the low 16 bits (two's complement);
  *   - a float weight becomes WT_TYPE the same way (host buffers are aligned_vector<WT_TYPE> filled from float,

@@ -1,5 +1,5 @@
 /*
- * pna_oracle.c -- float restatement of FlowGNN PNA (TEST INFRASTRUCTURE, parity unpinned; see
+ * pna_oracle.c -- float restatement of FlowGNN PNA (TEST INFRASTRUCTURE, pinned to the reference: DESIGN.md section 2; see
  * flowgnn_oracle.h).  Each block cites the reference lines it follows (paths under /root/reference).
  */
 #include "flowgnn_oracle.h"

@@ -3,8 +3,12 @@
  * PNA/src/dcl.h:74-75) and DGN (ap_fixed<16,3>, Q3.13: DGN/src/dcl.h:54-55) in the reference's own number formats.
  * TEST INFRASTRUCTURE (see flowgnn_oracle.h).  GIN / GIN-VN: ginq_oracle.c.
  *
- * PARITY UNPINNED, doubly (as ginq_oracle.c): the Vitis headers that define ap_fixed, hls::vector and the hls math functions
- * are not in this image, so the rules below are a reading of their published semantics, not a run of them.  F = number of
+ * PINNED, in part: the reference's own sources, compiled against the fixed form of oracle/hls_standin
+ * (make -C oracle ref), give the same 16-bit patterns as this file on every input of tests/test_reference_pin_cpu.py.  That pins
+ * the PROGRAM -- which statement computes and stores what -- under the operator rules R0-R2, R7, R8, which the stand-in takes
+ * from the published ap_fixed result types and hls_standin/check.cc checks against plain integer formulas.  NOT pinned: R3-R6,
+ * the bit rules of hls::sqrt / recip / exp / log / abs -- the stand-in's hls_math.h implements exactly these rules, so the run
+ * says nothing about them; they stay a reading of Vitis -- and Vitis' own C simulation of ap_fixed.  F = number of
  * fractional bits of the format (10 or 13); "pattern" = the 16-bit two's-complement integer, value = pattern / 2^F.
  *
  *  R0  (ginq_oracle.c) every expression is exact in a wider type; a value is quantised only where it is stored into an
