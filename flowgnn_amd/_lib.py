@@ -79,6 +79,8 @@ def _declare(lib):
     lib.flowgnn_gin_eps.argtypes = [eng, p_float]
     lib.flowgnn_set_ogb_virtual_node.argtypes = [eng] + [p_float] * 5
     lib.flowgnn_ogb_virtual_node.argtypes = [eng]
+    lib.flowgnn_set_gcn_virtual_node.argtypes = [eng] + [p_float] * 5
+    lib.flowgnn_gcn_virtual_node.argtypes = [eng]
     lib.flowgnn_set_num_tasks.argtypes = [eng, C.c_int]
     lib.flowgnn_num_tasks.argtypes = [eng]
     lib.flowgnn_get_csr.argtypes = [eng, p_int, p_int, p_int, p_int]
@@ -118,6 +120,7 @@ def _declare(lib):
     lib.flowgnn_group_set_gin_eps.argtypes = [grp, p_float]
     lib.flowgnn_entry_set_gin_eps.argtypes = [C.c_int, p_float]
     lib.flowgnn_group_set_ogb_virtual_node.argtypes = [grp] + [p_float] * 5
+    lib.flowgnn_group_set_gcn_virtual_node.argtypes = [grp] + [p_float] * 5
     lib.flowgnn_group_set_batch.argtypes = [grp, C.c_int, p_int, p_int, p_int, p_int, p_int, p_float]
     lib.flowgnn_group_shards.argtypes = [grp, p_int]
     lib.flowgnn_group_run.argtypes = [grp]
@@ -160,6 +163,7 @@ def _declare(lib):
                  "flowgnn_set_pooling", "flowgnn_pooling", "flowgnn_group_set_pooling", "flowgnn_entry_set_pooling",
                  "flowgnn_set_gin_eps", "flowgnn_gin_eps", "flowgnn_group_set_gin_eps", "flowgnn_entry_set_gin_eps",
                  "flowgnn_set_ogb_virtual_node", "flowgnn_ogb_virtual_node", "flowgnn_group_set_ogb_virtual_node",
+                 "flowgnn_set_gcn_virtual_node", "flowgnn_gcn_virtual_node", "flowgnn_group_set_gcn_virtual_node",
                  "flowgnn_laplacian_eigen_max_nodes", "flowgnn_laplacian_eigen", "flowgnn_laplacian_eigen_device",
                  "GIN_compute_graphs_mt", "GCN_compute_graphs_mt", "GIN_compute_graphs", "GCN_compute_graphs", "PNA_compute_graphs", "DGN_compute_graphs", "GAT_compute_graphs"):
         getattr(lib, name).restype = C.c_int

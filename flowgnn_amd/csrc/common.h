@@ -173,7 +173,7 @@ struct DeviceBatch {
                               // 2 = max.  Decides what out and emb hold; node_emb and the attention buffers do not depend on it
     bool gin_eps_on;          // flowgnn_set_gin_eps (GIN, GIN-VN): false = off, every launch is the one it always was.  A state, not a value: on
     float gin_self_scale[5];  // with five zeros runs the eps instances too.  s_l = (float)(1.0f + eps[l]) of layer l: a[v] = s_l h_l[v] + m_l[v]
-    const float* ogb_vn;      // flowgnn_set_ogb_virtual_node (GIN): the five tensors in the device form of gin_ogbvn.h, or null: off, every
+    const float* ogb_vn;      // flowgnn_set_ogb_virtual_node (GIN) / flowgnn_set_gcn_virtual_node (GCN): the five tensors in the device form of gin_ogbvn.h, or null: off, every
                               // launch is the one it always was.  A forward that finds it set runs OGB's virtual node on every path
     int final_h;              // which h[] holds the last stage's output (set by forward)
     const float* tap;         // optional debug tap returned by flowgnn_get_h instead of h[final_h]
@@ -229,6 +229,9 @@ public:
     // flowgnn_set_ogb_virtual_node: the state alone (the tensors reach forward() through DeviceBatch::ogb_vn), for what a model decides
     // before it sees a batch (wants_packed_tile_lists)
     virtual int set_ogb_virtual_node(bool on) { return on ? 8 : 0; }
+    // flowgnn_set_gcn_virtual_node: the state (null: off) and the embedding row E [100], which GCN folds into layer 0's bias; the
+    // tensors reach forward() through DeviceBatch::ogb_vn as well
+    virtual int set_gcn_virtual_node(const float* vn_embedding) { return vn_embedding ? 8 : 0; }
     // rows > 0: flowgnn_set_batch packs whole graphs into tiles of at most rows rows / edges in-edges (DeviceBatch::gtiles)
     virtual void graph_tile_limits(int& rows, int& edges) const { rows = 0; edges = 0; }
     // rows > 0: flowgnn_set_batch also packs the half-tile lists of GraphTiles (sub / big_*)

@@ -1321,7 +1321,7 @@ int flowgnn_set_numeric_mode(flowgnn_engine* e, int mode) {
         return FLOWGNN_ERR_UNSUPPORTED;
     }
     if (mode == FLOWGNN_NUMERIC_Q6_10 && e->ogb_vn_on) {
-        e->err = "flowgnn_set_numeric_mode: OGB's virtual node is on (flowgnn_set_ogb_virtual_node), and the fixed-point arithmetic is the reference's, which has no such model";
+        e->err = "flowgnn_set_numeric_mode: OGB's virtual node is on (flowgnn_set_ogb_virtual_node / flowgnn_set_gcn_virtual_node), and the fixed-point arithmetic is the reference's, which has no such model";
         return FLOWGNN_ERR_UNSUPPORTED;
     }
     e->drop_graph();
@@ -1394,19 +1394,18 @@ int flowgnn_gin_eps(const flowgnn_engine* e, float* eps_out) {
     return e->gin_eps_on ? 1 : 0;
 }
 
-int flowgnn_set_ogb_virtual_node(flowgnn_engine* e, const float* vn_embedding, const float* w1, const float* b1, const float* w2, const float* b2) {
-    if (!e) return FLOWGNN_ERR_ARG;
-    if (e->model_id != FLOWGNN_MODEL_GIN) {
-        e->err = "flowgnn_set_ogb_virtual_node: OGB's virtual node exists for GIN only (GIN-VN is the reference's augmentation, a different model)";
-        return FLOWGNN_ERR_UNSUPPORTED;
-    }
+// flowgnn_set_ogb_virtual_node (GIN) and flowgnn_set_gcn_virtual_node (GCN): the same five tensors, the same checks, the same device
+// form (gin_ogbvn.h) and the same engine state -- an engine is one model, so one of the two calls is refused on it.  `fn`: the caller.
+static int set_virtual_node(flowgnn_engine* e, const char* fn, const float* vn_embedding, const float* w1, const float* b1, const float* w2,
+                            const float* b2) {
+    const std::string who = std::string(fn) + ": ";
     const float* const t[5] = {vn_embedding, w1, b1, w2, b2};
     const size_t count[5] = {100, (size_t)FLOWGNN_OGB_VN_LAYERS * FLOWGNN_OGB_VN_HIDDEN * 100, (size_t)FLOWGNN_OGB_VN_LAYERS * FLOWGNN_OGB_VN_HIDDEN,
                              (size_t)FLOWGNN_OGB_VN_LAYERS * 100 * FLOWGNN_OGB_VN_HIDDEN, (size_t)FLOWGNN_OGB_VN_LAYERS * 100};
     int given = 0;
     for (int i = 0; i < 5; i++) given += t[i] != nullptr;
     if (given != 0 && given != 5) {
-        e->err = "flowgnn_set_ogb_virtual_node: some of the five tensors are NULL and some are not (all five: on, all NULL: off)";
+        e->err = who + "some of the five tensors are NULL and some are not (all five: on, all NULL: off)";
         return FLOWGNN_ERR_ARG;
     }
     const bool on = given == 5;
@@ -1415,11 +1414,11 @@ int flowgnn_set_ogb_virtual_node(flowgnn_engine* e, const float* vn_embedding, c
         for (int i = 0; i < 5; i++)
             for (size_t k = 0; k < count[i]; k++)
                 if (!std::isfinite(t[i][k])) {
-                    e->err = std::string("flowgnn_set_ogb_virtual_node: ") + names[i] + "[" + std::to_string(k) + "] is not finite";
+                    e->err = who + names[i] + "[" + std::to_string(k) + "] is not finite";
                     return FLOWGNN_ERR_ARG;
                 }
         if (e->numeric_mode == FLOWGNN_NUMERIC_Q6_10) {
-            e->err = "flowgnn_set_ogb_virtual_node: the fixed-point arithmetic (FLOWGNN_NUMERIC_Q6_10) is the reference's, which has no such model";
+            e->err = who + "the fixed-point arithmetic (FLOWGNN_NUMERIC_Q6_10) is the reference's, which has no such model";
             return FLOWGNN_ERR_UNSUPPORTED;
         }
     }
@@ -1430,8 +1429,9 @@ int flowgnn_set_ogb_virtual_node(flowgnn_engine* e, const float* vn_embedding, c
         EHIP_TRY(e, e->ogb_vn.reserve(sizeof(float) * packed.size(), false));
         EHIP_TRY(e, hipMemcpy(e->ogb_vn.p, packed.data(), sizeof(float) * packed.size(), hipMemcpyHostToDevice));
     }
-    if (int rc = e->model->set_ogb_virtual_node(on)) {
-        e->err = "flowgnn_set_ogb_virtual_node: this model has no such kernel";
+    const int rc = e->model_id == FLOWGNN_MODEL_GCN ? e->model->set_gcn_virtual_node(on ? vn_embedding : nullptr) : e->model->set_ogb_virtual_node(on);
+    if (rc) {
+        e->err = who + "this model has no such kernel";
         return rc;
     }
     e->ogb_vn_on = on;
@@ -1439,7 +1439,28 @@ int flowgnn_set_ogb_virtual_node(flowgnn_engine* e, const float* vn_embedding, c
     return FLOWGNN_OK;
 }
 
-int flowgnn_ogb_virtual_node(const flowgnn_engine* e) { return e ? (e->ogb_vn_on ? 1 : 0) : -1; }
+int flowgnn_set_ogb_virtual_node(flowgnn_engine* e, const float* vn_embedding, const float* w1, const float* b1, const float* w2, const float* b2) {
+    if (!e) return FLOWGNN_ERR_ARG;
+    if (e->model_id != FLOWGNN_MODEL_GIN) {
+        e->err = "flowgnn_set_ogb_virtual_node: OGB's virtual node exists for GIN only (GIN-VN is the reference's augmentation, a different model)";
+        if (e->model_id == FLOWGNN_MODEL_GCN) e->err += "; GCN has a call of its own, flowgnn_set_gcn_virtual_node";
+        return FLOWGNN_ERR_UNSUPPORTED;
+    }
+    return set_virtual_node(e, "flowgnn_set_ogb_virtual_node", vn_embedding, w1, b1, w2, b2);
+}
+
+int flowgnn_set_gcn_virtual_node(flowgnn_engine* e, const float* vn_embedding, const float* w1, const float* b1, const float* w2, const float* b2) {
+    if (!e) return FLOWGNN_ERR_ARG;
+    if (e->model_id != FLOWGNN_MODEL_GCN) {
+        e->err = "flowgnn_set_gcn_virtual_node: this call is OGB's gcn-virtual, for GCN only (GIN: flowgnn_set_ogb_virtual_node)";
+        return FLOWGNN_ERR_UNSUPPORTED;
+    }
+    return set_virtual_node(e, "flowgnn_set_gcn_virtual_node", vn_embedding, w1, b1, w2, b2);
+}
+
+int flowgnn_gcn_virtual_node(const flowgnn_engine* e) { return e ? (e->ogb_vn_on && e->model_id == FLOWGNN_MODEL_GCN ? 1 : 0) : -1; }
+
+int flowgnn_ogb_virtual_node(const flowgnn_engine* e) { return e ? (e->ogb_vn_on && e->model_id == FLOWGNN_MODEL_GIN ? 1 : 0) : -1; }
 
 int flowgnn_set_option(flowgnn_engine* e, const char* key, double value) {
     if (!e || !key) return FLOWGNN_ERR_ARG;
@@ -1545,7 +1566,7 @@ int flowgnn_run_aggregation_only(flowgnn_engine* e, int layer, int iters, float*
     if (!e || iters <= 0) return FLOWGNN_ERR_ARG;
     if (!e->ran) { e->err = "flowgnn_run_aggregation_only needs a prior flowgnn_run"; return FLOWGNN_ERR_STATE; }
     if (e->gin_eps_on) { e->err = "flowgnn_run_aggregation_only: a trained eps is on (flowgnn_set_gin_eps), and the stand-alone aggregation kernel has no eps instance"; return FLOWGNN_ERR_UNSUPPORTED; }
-    if (e->ogb_vn_on) { e->err = "flowgnn_run_aggregation_only: OGB's virtual node is on (flowgnn_set_ogb_virtual_node), and the stand-alone aggregation kernel does not add it"; return FLOWGNN_ERR_UNSUPPORTED; }
+    if (e->ogb_vn_on) { e->err = "flowgnn_run_aggregation_only: OGB's virtual node is on (flowgnn_set_ogb_virtual_node / flowgnn_set_gcn_virtual_node), and the stand-alone aggregation kernel does not add it"; return FLOWGNN_ERR_UNSUPPORTED; }
     ENGINE_TRY(e, use_device(e));
     e->drop_graph();
     int rc = e->model->aggregate_dim() > 0 ? ensure_rows(e) : FLOWGNN_OK;  // the kernel's input rows (a resident run left none)
@@ -1577,7 +1598,7 @@ int flowgnn_get_aggregate(flowgnn_engine* e, int layer, float* h_in_host, int* i
     if (!e) return FLOWGNN_ERR_ARG;
     if (!e->ran) { e->err = "flowgnn_get_aggregate needs a prior flowgnn_run"; return FLOWGNN_ERR_STATE; }
     if (e->gin_eps_on) { e->err = "flowgnn_get_aggregate: a trained eps is on (flowgnn_set_gin_eps), and the stand-alone aggregation kernel has no eps instance"; return FLOWGNN_ERR_UNSUPPORTED; }
-    if (e->ogb_vn_on) { e->err = "flowgnn_get_aggregate: OGB's virtual node is on (flowgnn_set_ogb_virtual_node), and the stand-alone aggregation kernel does not add it"; return FLOWGNN_ERR_UNSUPPORTED; }
+    if (e->ogb_vn_on) { e->err = "flowgnn_get_aggregate: OGB's virtual node is on (flowgnn_set_ogb_virtual_node / flowgnn_set_gcn_virtual_node), and the stand-alone aggregation kernel does not add it"; return FLOWGNN_ERR_UNSUPPORTED; }
     int rc = flowgnn_sync(e);
     if (rc) return rc;
     e->drop_graph();

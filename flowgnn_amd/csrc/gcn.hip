@@ -18,8 +18,10 @@
 #include "dense_split.h"
 #include "gin_split.h"  // gin_resident_pack_enc_table: the pre-combined (three rows per node) form of a 173-row table
 #include "gcn_plan.h"
+#include "gcn_ogbvn.h"
 #include <cmath>
 #include <cstring>
+#include <type_traits>
 
 namespace fg {
 // gcn_rows.hip compiles this file once more with FG_RESIDENT_ROWS_TU defined, for ONE kernel: gcn_resident_kernel under the name
@@ -132,9 +134,13 @@ struct GcnAggPolicy {
 // layer's weight fragments (45 KB) both live in LDS, a lane sums the nine table rows of its node for the 25 features it
 // owns (same order as atom_encoder_kernel, so h0 is bit-identical) and feeds them straight to the split MFMAs.  Saves
 // the 2.8 GB write + 2.8 GB read of h0.  One persistent 16-wave workgroup per CU, no barrier after the initial fill.
+// VN (OGB's virtual node, gcn_ogbvn.h): vn_0 = E is a constant and sits in the bias of wpk, so nothing is added here; the instance
+// leaves the per-graph sums of h_0 over the tile as partial rows, from the registers that hold h_0, for the first update.
+template <bool VN = false>
 __global__ __launch_bounds__(1024) void gcn_encoder_dense_kernel(const int* __restrict__ node_feature, const float* __restrict__ table,
                                                                   float* __restrict__ xout, const uint8_t* __restrict__ wpk, int n_tot,
-                                                                  int* __restrict__ err, int* __restrict__ range_flag) {
+                                                                  int* __restrict__ err, int* __restrict__ range_flag,
+                                                                  typename std::conditional<VN, GcnVnArgs, GcnNoVnArgs>::type vna) {
     constexpr int OT = GCN_OT;
     constexpr int WBYTES = (int)dense100_split_bytes(OT);
     constexpr int TAIL_OFF = OT * 6 * 1024, BIAS_OFF = TAIL_OFF + OT * 256, SCALE_OFF = BIAS_OFF + OT * 64;
@@ -162,11 +168,14 @@ __global__ __launch_bounds__(1024) void gcn_encoder_dense_kernel(const int* __re
         long long node = tile * 16 + j;
         const bool valid = node < n_tot;
         if (!valid) node = n_tot - 1;
+        int vg = 0;  // VN: the node's graph
+        if constexpr (VN) vg = vna.node_graph[node];
         int rows[ND_FEATURE];
         int fcur[ND_FEATURE];
 #pragma unroll
         for (int k = 0; k < ND_FEATURE; k++) fcur[k] = fnext[k];
-        {
+        // (VN: the next tile's row is requested behind the partial sums, whose scan needs the nine registers)
+        if constexpr (!VN) {
             const long long tn = tile + (long long)gridDim.x * 16;
             fetch(tn < n_tiles ? tn : tile);
         }
@@ -191,6 +200,11 @@ __global__ __launch_bounds__(1024) void gcn_encoder_dense_kernel(const int* __re
                 a[4 * q + 0] += w.x; a[4 * q + 1] += w.y; a[4 * q + 2] += w.z; a[4 * q + 3] += w.w;
             }
             a[24] += s_tab[rows[k] + 96 + g];
+        }
+        if constexpr (VN) {
+            gcn_ogbvn_tile_partials(a, valid ? vg : -1, j, g, tile, vna.part);
+            const long long tn = tile + (long long)gridDim.x * 16;
+            fetch(tn < n_tiles ? tn : tile);
         }
         ds_uint4_t b_hi[3], b_lo[3];
 #pragma unroll
@@ -239,13 +253,17 @@ __global__ __launch_bounds__(1024) void gcn_encoder_dense_kernel(const int* __re
 // and the sixteen waves of a CU drift freely against each other instead of marching through barrier-delimited steps.
 // FINAL: the last stage has no dense layer and no ReLU; the readout's linear head is applied per node instead
 // (mean_v(a[v]) . w = mean_v(a[v] . w)) and xout is a float[n_tot] of per-node scores for segment_mean_bias_kernel.
-template <bool FINAL>
+// VN (OGB's virtual node, gcn_ogbvn.h; the launch that forms h_l, l = 1..4): x_l = h_l + vn_l[g(v)] is formed in the registers in front
+// of the split, so W_l x_l + b_l costs no row traffic, and for l < 4 the per-graph sums of x_l over the tile go out as partial rows.
+template <bool FINAL, bool VN = false>
 __global__ __launch_bounds__(512) void gcn_layer_fused_kernel(const float* __restrict__ x, float* __restrict__ xout,
                                                                const int* __restrict__ row_ptr, const int* __restrict__ src,
                                                                const uint8_t* __restrict__ ecode, const float* __restrict__ esc,
                                                                const int* __restrict__ out_deg, const float* __restrict__ ecomb,
                                                                const float* __restrict__ ep, const uint8_t* __restrict__ wpk, int n_tot,
-                                                               int* __restrict__ range_flag, const float* __restrict__ pool_w) {
+                                                               int* __restrict__ range_flag, const float* __restrict__ pool_w,
+                                                               typename std::conditional<VN, GcnVnArgs, GcnNoVnArgs>::type vna) {
+    static_assert(!(FINAL && VN), "the last stage reads x_4, which has vn_4 inside already");
     constexpr int OT = GCN_OT;
     constexpr int WBYTES = (int)dense100_split_bytes(OT);
     constexpr int TAIL_OFF = OT * 6 * 1024, BIAS_OFF = TAIL_OFF + OT * 256, SCALE_OFF = BIAS_OFF + OT * 64;
@@ -270,6 +288,8 @@ __global__ __launch_bounds__(512) void gcn_layer_fused_kernel(const float* __res
         int e = row_ptr[node];
         const int e_end = valid ? row_ptr[node + 1] : e;
         const int dv = out_deg[node];
+        int vg = 0;  // VN: the node's graph
+        if constexpr (VN) vg = vna.node_graph[node];
         const float* xr = x + (size_t)node * GCN_D + 4 * g;
         float4 xs[6];
 #pragma unroll
@@ -339,6 +359,16 @@ __global__ __launch_bounds__(512) void gcn_layer_fused_kernel(const float* __res
         }
 #pragma unroll
         for (int k = 0; k < 25; k++) a[k] = relu1(a[k]);
+        if constexpr (VN) {  // x_l = h_l + vn_l[g(v)]: 100 floats per graph out of L2 (a clamped lane: the last node's graph, nothing stored)
+            const float* vr = vna.vn + (size_t)vg * GCN_D;
+#pragma unroll
+            for (int q = 0; q < 6; q++) {
+                const float4 v = *reinterpret_cast<const float4*>(vr + 16 * q + 4 * g);
+                a[4 * q + 0] += v.x; a[4 * q + 1] += v.y; a[4 * q + 2] += v.z; a[4 * q + 3] += v.w;
+            }
+            a[24] += vr[96 + g];
+            if (vna.part) gcn_ogbvn_tile_partials(a, valid ? vg : -1, j, g, tile, vna.part);  // (uniform over the launch)
+        }
         // dense layer on the split operands
         ds_uint4_t b_hi[3], b_lo[3];
 #pragma unroll
@@ -348,8 +378,13 @@ __global__ __launch_bounds__(512) void gcn_layer_fused_kernel(const float* __res
             DS_SPLIT2(a[8 * ks + 4], a[8 * ks + 5], b_hi[ks].z, b_lo[ks].z);
             DS_SPLIT2(a[8 * ks + 6], a[8 * ks + 7], b_hi[ks].w, b_lo[ks].w);
         }
+        if constexpr (VN) {  // relu(a) + vn can be negative: the magnitude
 #pragma unroll
-        for (int k = 0; k < 24; k += 2) vmax = __builtin_fmaxf(__builtin_fmaxf(vmax, a[k]), a[k + 1]);  // a >= 0 (ReLU)
+            for (int k = 0; k < 24; k += 2) vmax = __builtin_fmaxf(__builtin_fmaxf(vmax, __builtin_fabsf(a[k])), __builtin_fabsf(a[k + 1]));
+        } else {
+#pragma unroll
+            for (int k = 0; k < 24; k += 2) vmax = __builtin_fmaxf(__builtin_fmaxf(vmax, a[k]), a[k + 1]);  // a >= 0 (ReLU)
+        }
         asm volatile("" : "+v"(vmax));
 #pragma unroll
         for (int t = 0; t < OT; t++) {
@@ -1238,6 +1273,9 @@ public:
             table_ok_ = emax < 4096.0f && 9.0f * pmax < 6.0e4f;
         }
         if ((rc = upload(&d_split_, split_all))) return rc;
+        w0_.assign(cw, cw + (size_t)GCN_D * GCN_D);
+        b0_.assign(cb, cb + GCN_D);
+        if (ogb_vn_ && (rc = fold_vn_layer0())) return rc;  // the virtual node holds across weight sets: b_0' follows W_0 and b_0
         if ((rc = upload(&d_nemb_, v_nemb))) return rc;
         if ((rc = upload(&d_pw_, v_pw))) return rc;
         if ((rc = upload(&d_pb_, v_pb))) return rc;
@@ -1320,11 +1358,30 @@ public:
     }
     void set_keep_h(bool on) override { keep_h_ = on; }
 
+    // OGB's virtual node (flowgnn_set_gcn_virtual_node, gcn_ogbvn.h): the state, and E for layer 0's folded bias; the five tensors in
+    // their device form reach forward() through DeviceBatch::ogb_vn
+    int set_gcn_virtual_node(const float* vn_embedding) override {
+        if (vn_embedding && qmode_) return 8;
+        ogb_vn_ = vn_embedding != nullptr;
+        if (!ogb_vn_) return 0;
+        vn_e_.assign(vn_embedding, vn_embedding + GCN_D);
+        return ready_ ? fold_vn_layer0() : 0;
+    }
+    // layer 0 with vn_0 = E inside: W_0 (h_0 + E) + b_0 = W_0 h_0 + b_0', a second packed blob for gcn_encoder_dense_kernel
+    int fold_vn_layer0() {
+        std::vector<float> b(GCN_D);
+        gcn_ogbvn_fold_bias(w0_.data(), b0_.data(), vn_e_.data(), b.data());
+        std::vector<uint8_t> blob(dense100_split_bytes(GCN_OT));
+        pack_dense100_split(w0_.data(), b.data(), GCN_D, GCN_OT, blob.data());
+        return upload(&d_split0_vn_, blob);
+    }
+
     // which kernels the next forward of this batch runs: decided in gcn_plan.h, from these values and nothing else
     GcnPlanInput plan_input() const {
         GcnPlanInput in;
         in.resident = resident_; in.tile_build = tile_build_; in.binpack = binpack_; in.split = split_; in.fused = fused_;
         in.table_ok = table_ok_; in.qmode = qmode_; in.keep_h = keep_h_; in.exact = exact_; in.num_tasks = num_tasks_;
+        in.ogb_vn = ogb_vn_;
         return in;
     }
     GcnPlan plan(const DeviceBatch& db) const {
@@ -1407,29 +1464,70 @@ public:
             return 0;
         }
         if (int rc = prepare_aggregate(db, prof, s)) return rc;
+        // OGB's virtual node: the state and the engine's tensors go together (the engine sets both); a forward with one and not the other
+        // would compute another model
+        const bool vn = db.ogb_vn != nullptr;
+        if (vn != ogb_vn_) {
+            set_last_error("flowgnn_run: the GCN model's virtual-node state and the engine's tensors disagree (flowgnn_set_gcn_virtual_node)");
+            return 8;
+        }
+        if (vn) {
+            if (int rc = vn_state_.reserve((size_t)db.b.num_graphs * GCN_D)) return rc;
+            if (plan.vn_fused) {
+                if (int rc = vn_part_.reserve(gcn_ogbvn_part_floats(db.b.num_graphs, n))) return rc;
+                if (int rc = vn_node_graph_.reserve((size_t)n)) return rc;
+            }
+        }
+        // the in-place form (every configuration that does not fuse): x_l = h_l + vn_l on the rows in front of dense l, GIN's launch
+        auto vn_in_place = [&](int l) {
+            if (!vn) return;
+            ProfScope p(prof, "gin_ogb_vn", s);
+            launch_gin_ogbvn(db.scratch, db.b.node_off, db.b.num_graphs, db.ogb_vn, vn_state_.p, l, s);
+        };
         int cur = 0;
+        if (plan.vn_fused) {
+            ProfScope p(prof, "gcn_ogb_vn_map", s);
+            launch_gcn_ogbvn_node_graph(db.b.node_off, db.b.num_graphs, n, vn_node_graph_.p, s);
+        }
         if (plan.fused_encoder) {
             ProfScope p(prof, "gcn_encoder_dense", s);
             const long long wgs = ceil_div_ll(n, 256);
-            gcn_encoder_dense_kernel<<<(int)(wgs < 256 ? wgs : 256), 1024, 0, s>>>(db.b.node_feature, d_nemb_, db.h[cur], d_split_, n,
-                                                                                   db.csr.err, db.range_flag);
+            const int grid = (int)(wgs < 256 ? wgs : 256);
+            if (plan.vn_fused)  // vn_0 = E sits in layer 0's bias; the sums of h_0 go out as partial rows
+                gcn_encoder_dense_kernel<true><<<grid, 1024, 0, s>>>(db.b.node_feature, d_nemb_, db.h[cur], d_split0_vn_, n, db.csr.err, db.range_flag,
+                                                                     GcnVnArgs{vn_node_graph_.p, nullptr, vn_part_.p});
+            else
+                gcn_encoder_dense_kernel<false><<<grid, 1024, 0, s>>>(db.b.node_feature, d_nemb_, db.h[cur], d_split_, n, db.csr.err, db.range_flag,
+                                                                      GcnNoVnArgs{});
         } else {
             {
                 ProfScope p(prof, "atom_encoder", s);
                 atom_encoder_kernel<GCN_D><<<atom_encoder_grid(n, GCN_C), 512, 0, s>>>(db.b.node_feature, d_nemb_, db.scratch, n, db.csr.err);
             }
+            vn_in_place(0);
             ProfScope p(prof, "gcn_dense", s);
             launch_dense(0, db.scratch, db.h[cur], n, db.range_flag, s);  // x_0 = W_0 h0 + b_0
         }
         for (int l = 1; l < GCN_L; l++) {
+            if (plan.vn_fused) {  // vn_l from the sums of x_{l-1}: the partial rows of the launch before (l = 1: the encoder's, of h_0)
+                ProfScope p(prof, "gcn_ogb_vn", s);
+                launch_gcn_ogbvn_update(db.b.node_off, db.b.num_graphs, vn_part_.p, db.ogb_vn, vn_state_.p, l - 1, s);
+            }
             if (plan.fused_layers) {
                 ProfScope p(prof, "gcn_layer_fused", s);
                 const long long wgs = ceil_div_ll(n, 128);
                 const int grid = (int)(wgs < 512 ? wgs : 512);  // persistent: two 8-wave workgroups per CU (71 KB of LDS each)
-                gcn_layer_fused_kernel<false><<<grid, 512, 0, s>>>(db.h[cur], db.h[cur ^ 1], db.csr.row_ptr, db.csr.src, db.csr.ecode, esc_.p,
-                                                            db.csr.out_deg, d_ecomb_ + (size_t)(l - 1) * EDGE_COMBOS * GCN_D,
-                                                            d_ep_ + (size_t)(l - 1) * 3 * GCN_D, d_split_ + (size_t)l * dense100_split_bytes(GCN_OT),
-                                                            n, db.range_flag, nullptr);
+                if (plan.vn_fused)
+                    gcn_layer_fused_kernel<false, true><<<grid, 512, 0, s>>>(
+                        db.h[cur], db.h[cur ^ 1], db.csr.row_ptr, db.csr.src, db.csr.ecode, esc_.p, db.csr.out_deg,
+                        d_ecomb_ + (size_t)(l - 1) * EDGE_COMBOS * GCN_D, d_ep_ + (size_t)(l - 1) * 3 * GCN_D,
+                        d_split_ + (size_t)l * dense100_split_bytes(GCN_OT), n, db.range_flag, nullptr,
+                        GcnVnArgs{vn_node_graph_.p, vn_state_.p, l < GCN_L - 1 ? vn_part_.p : nullptr});
+                else
+                    gcn_layer_fused_kernel<false><<<grid, 512, 0, s>>>(
+                        db.h[cur], db.h[cur ^ 1], db.csr.row_ptr, db.csr.src, db.csr.ecode, esc_.p, db.csr.out_deg,
+                        d_ecomb_ + (size_t)(l - 1) * EDGE_COMBOS * GCN_D, d_ep_ + (size_t)(l - 1) * 3 * GCN_D,
+                        d_split_ + (size_t)l * dense100_split_bytes(GCN_OT), n, db.range_flag, nullptr, GcnNoVnArgs{});
                 cur ^= 1;
                 continue;
             }
@@ -1437,6 +1535,7 @@ public:
                 ProfScope p(prof, "gcn_aggregate", s);
                 launch_aggregate<true>(db, l - 1, db.h[cur], db.scratch, s);  // a_l
             }
+            vn_in_place(l);
             {
                 ProfScope p(prof, "gcn_dense", s);
                 launch_dense(l, db.scratch, db.h[cur ^ 1], n, db.range_flag, s);  // x_l
@@ -1453,7 +1552,8 @@ public:
                 const int grid = (int)(wgs < 512 ? wgs : 512);
                 gcn_layer_fused_kernel<true><<<grid, 512, 0, s>>>(db.h[cur], db.scratch, db.csr.row_ptr, db.csr.src, db.csr.ecode, esc_.p,
                                                                   db.csr.out_deg, d_ecomb_ + (size_t)(GCN_L - 1) * EDGE_COMBOS * GCN_D,
-                                                                  d_ep_ + (size_t)(GCN_L - 1) * 3 * GCN_D, nullptr, n, db.range_flag, d_pw_);
+                                                                  d_ep_ + (size_t)(GCN_L - 1) * 3 * GCN_D, nullptr, n, db.range_flag, d_pw_,
+                                                                  GcnNoVnArgs{});
             }
             ProfScope p(prof, "mean_pool_linear", s);
             if (int rc = launch_segment_bias(db.pooling, db.scratch, db.b.node_off, d_pb_, db.out, db.b.num_graphs, s)) return rc;
@@ -1508,7 +1608,7 @@ public:
     void set_exact(bool on) override { exact_ = on; }
 
     int aggregation_only(DeviceBatch& db, int layer, hipStream_t s) override {
-        if (plan(db).path == GcnPath::FixedPoint) return 8;  // FLOWGNN_ERR_UNSUPPORTED: that forward never builds the float kernels' inputs (tiles, h rows)
+        if (plan(db).path == GcnPath::FixedPoint || ogb_vn_) return 8;  // FLOWGNN_ERR_UNSUPPORTED (the virtual node: the engine refuses it itself): that forward never builds the float kernels' inputs (tiles, h rows)
         if (layer < 0 || layer >= GCN_L) return 1;
         if (!agg_ready_) {  // the last forward ran the graph-resident kernel
             Profiler none;
@@ -1530,6 +1630,10 @@ private:
             if (*p) { (void)hipFree(*p); *p = nullptr; }
         if (d_split_) { (void)hipFree(d_split_); d_split_ = nullptr; }
         if (d_res_) { (void)hipFree(d_res_); d_res_ = nullptr; }
+        if (d_split0_vn_) { (void)hipFree(d_split0_vn_); d_split0_vn_ = nullptr; }
+        vn_state_.release();
+        vn_part_.release();
+        vn_node_graph_.release();
         esc_.release();
         tiles_.release();
         desc_.release();
@@ -1537,6 +1641,11 @@ private:
     }
     bool ready_ = false;
     bool qmode_ = false;  // flowgnn_set_numeric_mode(FLOWGNN_NUMERIC_Q6_10)
+    bool ogb_vn_ = false;              // flowgnn_set_gcn_virtual_node is on (the tensors themselves: DeviceBatch::ogb_vn)
+    std::vector<float> vn_e_, w0_, b0_;  // ... its embedding row, and layer 0's W and b (host copies), for b_0' = b_0 + W_0 E
+    uint8_t* d_split0_vn_ = nullptr;   // ... layer 0's split blob with b_0' (fold_vn_layer0)
+    GrowBuf vn_state_, vn_part_;       // ... the per-graph vectors vn_l [G][100]; the partial rows of x_l (gcn_ogbvn_part_floats)
+    GrowBufI vn_node_graph_;           // ... the graph of every node of the batch
     QPack q_;
     GrowBufI desc_;               // gcn_tile_build_kernel: GCND_BYTES per graph tile
     float* d_enc_tab_ = nullptr;  // the projected table pre-combined into three rows per node (gin_resident_pack_enc_table)

@@ -27,6 +27,8 @@ struct GcnPlanInput {
     // outputs asked for
     bool emb = false, node_emb = false, node_logits = false;
     int pooling = 0;  // FLOWGNN_POOL_*: 0 mean, 1 sum, 2 max
+    // model state, again (the last field: an initialiser list written before it existed means what it meant)
+    bool ogb_vn = false;  // OGB's virtual node is on (flowgnn_set_gcn_virtual_node)
 };
 
 enum class GcnPath { FixedPoint, Resident, PerLayer };
@@ -52,6 +54,10 @@ struct GcnPlan {
     bool folded_last = false;
     bool multi_task = false;              // NUM_TASK outputs per graph from the un-folded rows
     bool node_logits_from_scores = false; // the folded last stage's scores plus the head's bias
+    // OGB's virtual node, on the per-layer path alone (the resident kernel has no instance with it).  true: vn_l is added in the fused
+    // kernels' registers and pooled from there (gcn_ogbvn.h); false with the virtual node on: in place on the rows in front of each
+    // dense launch, which needs the rows in HBM -- so the encoder fuses only where the layers do
+    bool vn_fused = false;
     // ---- either path, from rows in HBM (the storing instance's, or the un-folded last stage's)
     bool pool_rows = false;              // graph embeddings
     bool node_logits_from_rows = false;  // node logits
@@ -59,7 +65,7 @@ struct GcnPlan {
 
 // flowgnn_set_batch also bin-packs the graphs into tile lists: asked before there is a batch, so from the options and the model state alone
 inline bool gcn_wants_packed_tile_lists(const GcnPlanInput& in) {
-    return in.binpack && in.tile_build && in.resident && !in.qmode && in.num_tasks == 1;
+    return in.binpack && in.tile_build && in.resident && !in.qmode && !in.ogb_vn && in.num_tasks == 1;
 }
 
 inline GcnPlan gcn_plan(const GcnPlanInput& in) {
@@ -69,7 +75,7 @@ inline GcnPlan gcn_plan(const GcnPlanInput& in) {
         return p;
     }
     const bool fast = in.split && !in.exact && in.fused;
-    if (in.resident && in.table_ok && !in.keep_h && (!in.emb || in.node_emb) && fast && in.num_tasks == 1 && in.tiles && in.fill >= 0.5 &&
+    if (in.resident && !in.ogb_vn && in.table_ok && !in.keep_h && (!in.emb || in.node_emb) && fast && in.num_tasks == 1 && in.tiles && in.fill >= 0.5 &&
         in.pooling != 2) {
         p.path = GcnPath::Resident;
         p.one_pass = in.tile_build && in.edge_attr;
@@ -84,8 +90,9 @@ inline GcnPlan gcn_plan(const GcnPlanInput& in) {
         p.node_logits_from_rows = in.node_emb && in.node_logits;
         return p;
     }
-    p.fused_encoder = fast;
     p.fused_layers = fast && in.edges;
+    p.fused_encoder = fast && (!in.ogb_vn || p.fused_layers);
+    p.vn_fused = in.ogb_vn && p.fused_encoder && p.fused_layers;
     p.folded_last = p.fused_layers && in.num_tasks == 1 && !in.emb && !in.node_emb && in.pooling != 2;
     p.multi_task = !p.folded_last && in.num_tasks > 1;
     p.node_logits_from_scores = p.folded_last && in.node_logits;

@@ -18,6 +18,7 @@
 //                without the flag the file stays ignored, as in the reference
 //   --ogb-vn     GIN: read gin_ep1_virtualnode_dim100.bin (161 300 LE float32: vn_embedding, w1, b1, w2, b2) from the weights directory and
 //                run OGB's virtual node (flowgnn_set_ogb_virtual_node) -- an exported gin-virtual checkpoint; usually together with --eps
+//                GCN: the same from gcn_ep1_virtualnode_dim100.bin (flowgnn_set_gcn_virtual_node) -- an exported gcn-virtual checkpoint
 //   --eig        DGN: directory holding the eigenvector text files g%d.txt                 (default eig, DGN/src/host_load.cc:178)
 //   --compute-eig DGN: compute node_eigen from the graphs on the GPU (flowgnn_laplacian_eigen, on the first engine) and read no --eig DIR
 //   XCLBIN       accepted and ignored, so `./host <xclbin>`-style command lines keep working
@@ -142,7 +143,7 @@ int main(int argc, char** argv) {
         }
         else if (a == "--compute-eig") compute_eig = true;  // DGN: node_eigen from the graphs themselves (flowgnn_laplacian_eigen), no --eig DIR
         else if (a == "--eps") use_eps = true;  // the trained eps of the weights directory (flowgnn_set_gin_eps; GIN / GIN-VN)
-        else if (a == "--ogb-vn") use_ogb_vn = true;  // OGB's virtual node from the weights directory (flowgnn_set_ogb_virtual_node; GIN)
+        else if (a == "--ogb-vn") use_ogb_vn = true;  // OGB's virtual node from the weights directory (GIN: flowgnn_set_ogb_virtual_node, GCN: flowgnn_set_gcn_virtual_node)
         // anything else (e.g. an .xclbin path) is ignored
     }
     if (num_graphs < 0) num_graphs = read_count_file(graphs + "/dataset_size.txt");
@@ -183,9 +184,11 @@ int main(int argc, char** argv) {
         const size_t H = FLOWGNN_OGB_VN_HIDDEN, L = FLOWGNN_OGB_VN_LAYERS, D = 100;
         const size_t at[6] = {0, D, D + L * H * D, D + L * H * D + L * H, D + 2 * L * H * D + L * H, D + 2 * L * H * D + L * H + L * D};
         std::vector<float> vn(at[5]);
-        const std::string path = wdir + "/gin_ep1_virtualnode_dim100.bin";
+        const bool gcn = mid == FLOWGNN_MODEL_GCN;
+        const std::string path = wdir + (gcn ? "/gcn_ep1_virtualnode_dim100.bin" : "/gin_ep1_virtualnode_dim100.bin");
         if (!read_exact(path, vn, 0, vn.size())) { fprintf(stderr, "--ogb-vn: cannot read %zu floats from %s\n", vn.size(), path.c_str()); return EXIT_FAILURE; }
-        rc = flowgnn_group_set_ogb_virtual_node(eng, vn.data() + at[0], vn.data() + at[1], vn.data() + at[2], vn.data() + at[3], vn.data() + at[4]);
+        rc = (gcn ? flowgnn_group_set_gcn_virtual_node : flowgnn_group_set_ogb_virtual_node)(eng, vn.data() + at[0], vn.data() + at[1], vn.data() + at[2],
+                                                                                             vn.data() + at[3], vn.data() + at[4]);
         if (rc) { fprintf(stderr, "--ogb-vn: %d %s\n", rc, flowgnn_group_last_error(eng)); return EXIT_FAILURE; }
     }
     printf("\n******* Weights loading done *******\n");

@@ -171,13 +171,17 @@ class Engine:
         self._check(self.lib.flowgnn_set_weights(self._h, len(arrs), ptrs), "flowgnn_set_weights")
 
     def load_weights_dir(self, directory: str, eps: bool = False, virtual_node: bool = False):
-        """eps=True (GIN, GIN-VN): also read the directory's eps file and apply it (set_gin_eps); virtual_node=True (GIN): also read
-        gin_ep1_virtualnode_dim100.bin and apply it (set_ogb_virtual_node).  The C call itself does neither."""
+        """eps=True (GIN, GIN-VN): also read the directory's eps file and apply it (set_gin_eps); virtual_node=True: also read
+        gin_ep1_virtualnode_dim100.bin and apply it (GIN: set_ogb_virtual_node), or gcn_ep1_virtualnode_dim100.bin on a GCN engine
+        (set_gcn_virtual_node).  The C call itself does neither."""
         self._check(self.lib.flowgnn_load_weights_dir(self._h, directory.encode()), "flowgnn_load_weights_dir")
         if eps:
             from .weights import load_gin_eps
             self.set_gin_eps(load_gin_eps(directory))
-        if virtual_node:
+        if virtual_node and self.model == "GCN":
+            from .weights import load_gcn_virtual_node
+            self.set_gcn_virtual_node(load_gcn_virtual_node(directory))
+        elif virtual_node:
             from .weights import load_gin_virtual_node
             self.set_ogb_virtual_node(load_gin_virtual_node(directory))
 
@@ -592,6 +596,17 @@ class Engine:
         """Whether OGB's virtual node is on (flowgnn.h: flowgnn_ogb_virtual_node)."""
         return int(self.lib.flowgnn_ogb_virtual_node(self._h)) == 1
 
+    def set_gcn_virtual_node(self, vn=None):
+        """GCN: run OGB's virtual node (gnn_type='gcn-virtual'; flowgnn.h: flowgnn_set_gcn_virtual_node).  `vn`: the dict of
+        set_ogb_virtual_node (export.gcn_virtual_node_from_ogb_state_dict); None turns it off.  The engine's, across batches and
+        weight sets."""
+        a = _ogb_vn_args(vn)
+        self._check(self.lib.flowgnn_set_gcn_virtual_node(self._h, *[_pf(x) for x in a]), "flowgnn_set_gcn_virtual_node")
+
+    def gcn_virtual_node(self) -> bool:
+        """Whether GCN's virtual node is on (flowgnn.h: flowgnn_gcn_virtual_node)."""
+        return int(self.lib.flowgnn_gcn_virtual_node(self._h)) == 1
+
     def exact_reruns(self) -> int:
         """Forward passes repeated on the exact-fp32 kernels (flowgnn.h: flowgnn_exact_reruns)."""
         return int(self.lib.flowgnn_exact_reruns(self._h))
@@ -714,6 +729,11 @@ class EngineGroup:
         """Engine.set_ogb_virtual_node on every member (flowgnn.h: flowgnn_group_set_ogb_virtual_node)."""
         a = _ogb_vn_args(vn)
         self._check(self.lib.flowgnn_group_set_ogb_virtual_node(self._h, *[_pf(x) for x in a]), "flowgnn_group_set_ogb_virtual_node")
+
+    def set_gcn_virtual_node(self, vn=None):
+        """Engine.set_gcn_virtual_node on every member (flowgnn.h: flowgnn_group_set_gcn_virtual_node)."""
+        a = _ogb_vn_args(vn)
+        self._check(self.lib.flowgnn_group_set_gcn_virtual_node(self._h, *[_pf(x) for x in a]), "flowgnn_group_set_gcn_virtual_node")
 
     def set_batch(self, batch: GraphBatch):
         nn, ne = _i32(batch.nums_of_nodes), _i32(batch.nums_of_edges)

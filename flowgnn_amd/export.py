@@ -80,11 +80,8 @@ def gin_eps_from_ogb_state_dict(sd: Mapping, num_layers: int = 5) -> np.ndarray:
 VN_KEY = "gnn_node.virtualnode_embedding.weight"  # what tells a gin-virtual state_dict from a gin one
 
 
-def gin_virtual_node_from_ogb_state_dict(sd: Mapping, num_layers: int = 5) -> Dict[str, np.ndarray]:
-    """The virtual node of an OGB `GNN(gnn_type='gin-virtual')` state_dict as the five tensors Engine.set_ogb_virtual_node /
-    flowgnn_set_ogb_virtual_node take: `gnn_node.virtualnode_embedding.weight` [1][100] and, per update l < num_layers - 1,
-    `gnn_node.mlp_virtualnode_list.l` = Linear-BatchNorm-ReLU-Linear-BatchNorm-ReLU (OGB: .0 .1 .3 .4) or Linear-ReLU-Linear-ReLU
-    (.0 .2).  Both BatchNorms (inference statistics) sit in front of a ReLU and are folded into the linear layer before them: exact."""
+def _virtual_node_from_ogb_state_dict(sd: Mapping, num_layers: int) -> Dict[str, np.ndarray]:
+    """GNN_node_Virtualnode's own keys are the same whatever gnn_type the convolutions have: the folding of both exporters below."""
     emb = _get(sd, VN_KEY).reshape(-1)
     w1s, b1s, w2s, b2s = [], [], [], []
     for l in range(num_layers - 1):
@@ -100,6 +97,20 @@ def gin_virtual_node_from_ogb_state_dict(sd: Mapping, num_layers: int = 5) -> Di
         w1s.append(w1); b1s.append(b1); w2s.append(w2); b2s.append(b2)
     out = OrderedDict([("vn_embedding", emb), ("w1", np.stack(w1s)), ("b1", np.stack(b1s)), ("w2", np.stack(w2s)), ("b2", np.stack(b2s))])
     return _checked(out, _weights.GIN_VIRTUAL_NODE_SHAPES, lambda k, v: v)
+
+
+def gin_virtual_node_from_ogb_state_dict(sd: Mapping, num_layers: int = 5) -> Dict[str, np.ndarray]:
+    """The virtual node of an OGB `GNN(gnn_type='gin-virtual')` state_dict as the five tensors Engine.set_ogb_virtual_node /
+    flowgnn_set_ogb_virtual_node take: `gnn_node.virtualnode_embedding.weight` [1][100] and, per update l < num_layers - 1,
+    `gnn_node.mlp_virtualnode_list.l` = Linear-BatchNorm-ReLU-Linear-BatchNorm-ReLU (OGB: .0 .1 .3 .4) or Linear-ReLU-Linear-ReLU
+    (.0 .2).  Both BatchNorms (inference statistics) sit in front of a ReLU and are folded into the linear layer before them: exact."""
+    return _virtual_node_from_ogb_state_dict(sd, num_layers)
+
+
+def gcn_virtual_node_from_ogb_state_dict(sd: Mapping, num_layers: int = 5) -> Dict[str, np.ndarray]:
+    """The same five tensors of an OGB `GNN(gnn_type='gcn-virtual')` state_dict, for Engine.set_gcn_virtual_node /
+    flowgnn_set_gcn_virtual_node (the virtual node's keys and its MLP do not depend on the convolution)."""
+    return _virtual_node_from_ogb_state_dict(sd, num_layers)
 
 
 def gin_weights_from_ogb_state_dict(sd: Mapping, num_layers: int = 5, eps_tol: float = 0.0, multi_task: bool = False,
@@ -147,11 +158,19 @@ def gin_weights_from_ogb_state_dict(sd: Mapping, num_layers: int = 5, eps_tol: f
     return _checked(out, _weights.GIN_FILES, lambda k, v: _weights._task_shape(k, v[1], pw.shape[0]))
 
 
-def gcn_weights_from_ogb_state_dict(sd: Mapping, num_layers: int = 5, multi_task: bool = False) -> Dict[str, np.ndarray]:
+def gcn_weights_from_ogb_state_dict(sd: Mapping, num_layers: int = 5, multi_task: bool = False,
+                                    virtual_node: bool = False) -> Dict[str, np.ndarray]:
     """OGB `GNN(gnn_type='gcn', ...)` -> the reference's GCN weight set.  BatchNorm stays a separate step in the
     reference (GCN/src/node_embedding.cc:123-138) but with 2^-10 added to the variance instead of torch's 1e-5
-    (GCN/src/load_inputs.cc:32): the exported variance is shifted by the difference so that both normalise alike."""
+    (GCN/src/load_inputs.cc:32): the exported variance is shifted by the difference so that both normalise alike.
+    A gcn-virtual state_dict (it has `gnn_node.virtualnode_embedding.weight`) is refused -- the weight set alone is a model nobody
+    trained -- unless virtual_node says that the engine will run the virtual node too (gcn_virtual_node_from_ogb_state_dict +
+    flowgnn_set_gcn_virtual_node)."""
     p = "gnn_node"
+    if VN_KEY in sd and not virtual_node:
+        raise ExportError(f"the state_dict has '{VN_KEY}': it is OGB's gcn-virtual, and these weights without its virtual node are "
+                          f"a model nobody trained; pass virtual_node=True and give the engine gcn_virtual_node_from_ogb_state_dict(sd) "
+                          f"(Engine.set_gcn_virtual_node)")
     out = OrderedDict()
     out["node_embedding_weight"] = _tables(sd, f"{p}.atom_encoder.atom_embedding_list", ATOM_DIMS)
     cols = {k: [] for k in ("edge_embedding_weight", "convs_weight", "convs_bias", "convs_root_emb_weight", "bn_weight", "bn_bias",
@@ -200,18 +219,21 @@ def export_weights(model: str, sd: Mapping, directory: str, multi_task: bool = F
     keep_eps (GIN, GIN-VN): a trained eps is not refused; the eps file holds the trained values, for `host --eps` /
     Engine.load_weights_dir(dir, eps=True) to apply (flowgnn_set_gin_eps).
     virtual_node (GIN): the state_dict is OGB's gin-virtual; its virtual node goes into gin_ep1_virtualnode_dim100.bin beside the
-    others, for `host GIN --ogb-vn` / Engine.load_weights_dir(dir, virtual_node=True) to apply (flowgnn_set_ogb_virtual_node)."""
+    others, for `host GIN --ogb-vn` / Engine.load_weights_dir(dir, virtual_node=True) to apply (flowgnn_set_ogb_virtual_node).
+    virtual_node (GCN): likewise OGB's gcn-virtual, into gcn_ep1_virtualnode_dim100.bin (flowgnn_set_gcn_virtual_node)."""
     m = model.upper()
-    if virtual_node and m != "GIN":
-        raise ExportError(f"virtual_node=True is OGB's gin-virtual, which the engine runs as GIN (not {model})")
+    if virtual_node and m not in ("GIN", "GCN"):
+        raise ExportError(f"virtual_node=True is OGB's gin-virtual or gcn-virtual, which the engine runs as GIN or GCN (not {model})")
     if m in ("GIN", "GIN-VN"):
         w = gin_weights_from_ogb_state_dict(sd, multi_task=multi_task, keep_eps=keep_eps, virtual_node=virtual_node)
         _weights.save_gin_weights(w, directory, eps=gin_eps_from_ogb_state_dict(sd) if keep_eps else None)
         if virtual_node:
             _weights.save_gin_virtual_node(gin_virtual_node_from_ogb_state_dict(sd), directory)
     elif m == "GCN":
-        w = gcn_weights_from_ogb_state_dict(sd, multi_task=multi_task)
+        w = gcn_weights_from_ogb_state_dict(sd, multi_task=multi_task, virtual_node=virtual_node)
         _weights.save_gcn_weights(w, directory)
+        if virtual_node:
+            _weights.save_gcn_virtual_node(gcn_virtual_node_from_ogb_state_dict(sd), directory)
     else:
         raise ExportError(f"no OGB example model corresponds to the reference's {model} (its PNA/DGN/GAT checkpoints are already "
                           f"flat files: use flowgnn_amd.weights.save_*_weights)")

@@ -117,6 +117,33 @@ def synth_gin_virtual_node(seed: int = 11, scale: float = 1.0) -> Dict[str, np.n
     return OrderedDict((k, (rng.standard_normal(shp) * s[k] * scale).astype(np.float32)) for k, shp in GIN_VIRTUAL_NODE_SHAPES.items())
 
 
+# ... and for GCN (flowgnn.h: flowgnn_set_gcn_virtual_node): the same five tensors in the same order, one file beside the GCN file
+GCN_VIRTUAL_NODE_FILE = "gcn_ep1_virtualnode_dim100.bin"
+
+
+def save_gcn_virtual_node(vn, directory: str) -> None:
+    """Write gcn_ep1_virtualnode_dim100.bin, as save_gin_virtual_node writes GIN's.  Nothing applies the file unless asked to:
+    `host GCN --ogb-vn`, Engine.load_weights_dir(dir, virtual_node=True)."""
+    os.makedirs(directory, exist_ok=True)
+    flat = np.concatenate([a.ravel() for a in checked_gin_virtual_node(vn).values()]).astype("<f4")
+    flat.tofile(os.path.join(directory, GCN_VIRTUAL_NODE_FILE))
+
+
+def load_gcn_virtual_node(directory: str) -> Dict[str, np.ndarray]:
+    """The five tensors of a directory's GCN virtual-node file (for Engine.set_gcn_virtual_node); a short file is refused."""
+    path = os.path.join(directory, GCN_VIRTUAL_NODE_FILE)
+    out, at = OrderedDict(), 0
+    for k, shp in GIN_VIRTUAL_NODE_SHAPES.items():
+        out[k] = _read(path, shp, at)
+        at += int(np.prod(shp))
+    return out
+
+
+def synth_gcn_virtual_node(seed: int = 13, scale: float = 1.0) -> Dict[str, np.ndarray]:
+    """Random virtual-node tensors for GCN: synth_gin_virtual_node's scales (the MLP is the same), another seed."""
+    return synth_gin_virtual_node(seed=seed, scale=scale)
+
+
 def synth_gin_weights(seed: int = 7, num_tasks: int = 1) -> Dict[str, np.ndarray]:
     """Random weights with the measured scales of the shipped GIN set:
     W1 s=0.075, b1 s=0.91, W2 s=0.053, b2 s=0.49, node/edge emb s=0.11/0.14, pred s=0.15."""

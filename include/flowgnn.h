@@ -616,7 +616,7 @@ int flowgnn_gin_eps(const flowgnn_engine* e, float* eps_out /* [5], may be NULL 
  * -- the graph-resident kernels do not carry the vector.  A graph's logit has the same bits wherever the
  * graph stands in a batch, a slice or a group's cut.  flowgnn_get_h returns h_5 as ever; the rows the layers leave in HBM on the way
  * are x_l (after the add), not h_l.
- * FLOWGNN_ERR_UNSUPPORTED (flowgnn_last_error says why): any model but FLOWGNN_MODEL_GIN; FLOWGNN_NUMERIC_Q6_10, in both orders of
+ * FLOWGNN_ERR_UNSUPPORTED (flowgnn_last_error says why): any model but FLOWGNN_MODEL_GIN (GCN has flowgnn_set_gcn_virtual_node below); FLOWGNN_NUMERIC_Q6_10, in both orders of
  * the two setters; and, while it is on, flowgnn_run_aggregation_only and flowgnn_get_aggregate.
  * flowgnn_ogb_virtual_node: 1 on, 0 off, -1 for a null handle.  flowgnn_group_set_ogb_virtual_node: the setter on every member.
  * The reference has no such model, so the reference-compatible <M>_compute_graphs entry points have no form of it.
@@ -627,6 +627,40 @@ int flowgnn_gin_eps(const flowgnn_engine* e, float* eps_out /* [5], may be NULL 
 #define FLOWGNN_OGB_VN_HIDDEN 200
 int flowgnn_set_ogb_virtual_node(flowgnn_engine* e, const float* vn_embedding, const float* w1, const float* b1, const float* w2, const float* b2); /* host arrays, copied; all NULL = off */
 int flowgnn_ogb_virtual_node(const flowgnn_engine* e);            /* 1 on, 0 off, -1 null handle */
+
+/*
+ * OGB's virtual node for GCN: gnn_type = 'gcn-virtual' of the same example.  The five tensors, their shapes, the folding and the
+ * device form are those of flowgnn_set_ogb_virtual_node above; the definition differs where GCN does -- the layer's linear map comes
+ * first, so the vector passes through it:
+ *     vn_0[g] = vn_embedding
+ *     for l = 0 .. 4:
+ *         x_l[v]  = h_l[v] + vn_l[g(v)]                                           (the last layer too; h_0 = the atom encoder's rows)
+ *         h_{l+1} = GCN layer l applied to x_l                                    (W_l x_l + b_l FIRST, then messages, root term, BatchNorm, ReLU
+ *                                                                                  but after layer 4 -- all as ever)
+ *         if l < 4:  t = sum over v in g of x_l[v] + vn_l[g]                      (always a sum, whatever flowgnn_set_pooling says)
+ *                    vn_{l+1}[g] = relu(w2[l] relu(w1[l] t + b1[l]) + b2[l])
+ *     readout: unchanged
+ * Calls of its own, because flowgnn_set_ogb_virtual_node on a GCN engine is refused and stays so.  All five NULL turns it off (the
+ * default), and then every launch is the one it always was; some but not all NULL, a value that is not finite, or a null handle is
+ * FLOWGNN_ERR_ARG.  The setting holds across batches and flowgnn_set_weights, may change between runs on a resident batch, and drops
+ * a recorded launch sequence (option hipgraph).  It combines with every pooling mode, NUM_TASK, the optional outputs, device batches
+ * and groups.  flowgnn_get_h returns x_4 as ever, now with vn_4 inside.
+ * Kernels: while it is on every batch takes the per-layer kernels.  In the default configuration the add and
+ * the per-graph sums happen in the registers of the fused layer kernels and one small launch per update (profile slot gcn_ogb_vn,
+ * four per run) forms vn_{l+1}; the sums are cut at the batch's 16-node tiles, so a graph's logit has the same bits from run to run
+ * and between a host batch and the same batch given on the device, and agrees within fp32 rounding when the graph stands elsewhere
+ * (a permuted batch, a slice, a group's cut).  The configurations that do not fuse (gcn_mfma 32, gcn_unfused 1, the exact re-run
+ * behind the range flag, a batch without edges) add the vector in place in front of each dense launch (profile slot gin_ogb_vn, five
+ * per run), with GIN's bit invariance.
+ * FLOWGNN_ERR_UNSUPPORTED (flowgnn_last_error says why): any model but FLOWGNN_MODEL_GCN; FLOWGNN_NUMERIC_Q6_10, in both orders of
+ * the two setters; and, while it is on, flowgnn_run_aggregation_only and flowgnn_get_aggregate.
+ * flowgnn_gcn_virtual_node: 1 on, 0 off, -1 for a null handle.  flowgnn_group_set_gcn_virtual_node: the setter on every member.
+ * GCN_compute_graphs has no form of it.
+ * Files: gcn_ep1_virtualnode_dim100.bin beside the GCN file holds the five tensors in this order (161 300 LE float32);
+ * flowgnn_load_weights_dir does not read it; `host GCN --ogb-vn` and the Python wrapper's load_weights_dir(dir, virtual_node=True) do.
+ */
+int flowgnn_set_gcn_virtual_node(flowgnn_engine* e, const float* vn_embedding, const float* w1, const float* b1, const float* w2, const float* b2); /* host arrays, copied; all NULL = off */
+int flowgnn_gcn_virtual_node(const flowgnn_engine* e);            /* 1 on, 0 off, -1 null handle */
 
 /*
  * Laplacian eigenvectors: DGN's node_eigen from the graphs alone (the reference reads it from DGN/eig/g%d.txt and does not say where it
@@ -711,6 +745,7 @@ int flowgnn_group_set_numeric_mode(flowgnn_group* g, int mode);
 int flowgnn_group_set_pooling(flowgnn_group* g, int mode);
 int flowgnn_group_set_gin_eps(flowgnn_group* g, const float* eps);
 int flowgnn_group_set_ogb_virtual_node(flowgnn_group* g, const float* vn_embedding, const float* w1, const float* b1, const float* w2, const float* b2);
+int flowgnn_group_set_gcn_virtual_node(flowgnn_group* g, const float* vn_embedding, const float* w1, const float* b1, const float* w2, const float* b2);
 int flowgnn_group_set_batch(flowgnn_group* g, int num_graphs,
                             const int* nums_of_nodes, const int* nums_of_edges,
                             const int* node_feature, const int* edge_list, const int* edge_attr,
