@@ -292,7 +292,7 @@ struct Output {
     const char *noun, *setter;                // for the texts of its get and *_device calls
     const char* no_fixed_point;               // flowgnn_set_numeric_mode's refusal while it is on (null: the row above has said it)
 };
-static size_t emb_dim_of(const flowgnn_engine* e) { return (size_t)flowgnn_embedding_dim(e->model_id); }
+static size_t emb_dim_of(const flowgnn_engine* e) { return (size_t)e->emb_dim; }  // the ENGINE's width (flowgnn_set_emb_dim), not the model's default
 static size_t attn_layers(const flowgnn_engine* e) { return (size_t)__builtin_popcount((unsigned)e->attn_mask); }
 enum { OUT_EMB, OUT_NEMB, OUT_NLOG, OUT_ATTN_E, OUT_ATTN_S };
 static const Output kOutputs[] = {
@@ -376,6 +376,7 @@ int flowgnn_create(int model, int device_id, flowgnn_engine** out) {
     e->model_id = model;
     e->device = device_id;
     e->model = m;
+    e->emb_dim = flowgnn_embedding_dim(model);  // (the embeddings' width: GAT's rows in HBM, Model::emb_dim(), are its four heads side by side)
     e->graph_mode = e->opts.i("hipgraph");
     m->configure(e->opts);
     int rc = use_device(e);
@@ -1305,6 +1306,55 @@ int flowgnn_set_num_tasks(flowgnn_engine* e, int num_tasks) {
 
 int flowgnn_num_tasks(const flowgnn_engine* e) { return e ? e->num_tasks : -1; }
 
+// The width is the model OBJECT: GinModel (gin.hip) at 100, the per-layer model of gin_wide.hip at 300.  The call swaps it; everything
+// the old object held (weights) goes with it, and everything sized by the width (h, the embeddings, the node embeddings) with the batch.
+int flowgnn_set_emb_dim(flowgnn_engine* e, int emb_dim) {
+    if (!e) return FLOWGNN_ERR_ARG;
+    if (emb_dim != FLOWGNN_EMB_DIM_REFERENCE && emb_dim != FLOWGNN_EMB_DIM_OGB) {
+        e->err = "flowgnn_set_emb_dim: the widths are FLOWGNN_EMB_DIM_REFERENCE (100) and FLOWGNN_EMB_DIM_OGB (300)";
+        return FLOWGNN_ERR_ARG;
+    }
+    if (e->model_id != FLOWGNN_MODEL_GIN) {
+        e->err = "flowgnn_set_emb_dim: the width is a choice of FLOWGNN_MODEL_GIN alone (GIN-VN, GCN and the other models have the reference's width only)";
+        return FLOWGNN_ERR_UNSUPPORTED;
+    }
+    if (emb_dim == e->emb_dim) return FLOWGNN_OK;
+    if (emb_dim != FLOWGNN_EMB_DIM_REFERENCE) {
+        if (e->numeric_mode != FLOWGNN_NUMERIC_F32) {
+            e->err = "flowgnn_set_emb_dim: a numeric mode other than FLOWGNN_NUMERIC_F32 is on (flowgnn_set_numeric_mode), and width 300 has neither fixed-point nor f16 kernels";
+            return FLOWGNN_ERR_UNSUPPORTED;
+        }
+        if (e->ogb_vn_on) {
+            e->err = "flowgnn_set_emb_dim: OGB's virtual node is on (flowgnn_set_ogb_virtual_node), and its tensors are 100 wide";
+            return FLOWGNN_ERR_UNSUPPORTED;
+        }
+    }
+    ENGINE_TRY(e, begin_change(e));
+    Model* m = emb_dim == FLOWGNN_EMB_DIM_REFERENCE ? make_gin_model(false) : make_gin_wide_model(emb_dim);
+    if (!m) { e->err = "flowgnn_set_emb_dim: no model of this width"; return FLOWGNN_ERR_UNSUPPORTED; }
+    m->configure(e->opts);
+    if (int rc = m->set_num_tasks(e->num_tasks)) {
+        delete m;
+        e->err = "flowgnn_set_emb_dim: the model of this width does not take the engine's NUM_TASK";
+        return rc;
+    }
+    delete e->model;  // (the stream is idle: begin_change)
+    e->model = m;
+    e->emb_dim = emb_dim;
+    e->free_batch();  // h, scratch and the outputs are sized by the width: the batch has to be set again, and so have the weights
+    e->batch_ready = false;
+    e->ran = false;
+    e->force_exact = false;
+    e->db.tap = nullptr;
+    for (const Output& o : kOutputs) {
+        (e->*o.slot).user = (e->*o.slot).last = nullptr;
+        e->db.*o.field = nullptr;
+    }
+    return FLOWGNN_OK;
+}
+
+int flowgnn_emb_dim(const flowgnn_engine* e) { return e ? e->emb_dim : -1; }
+
 int flowgnn_set_numeric_mode(flowgnn_engine* e, int mode) {
     if (!e) return FLOWGNN_ERR_ARG;
     for (const Output& o : kOutputs)
@@ -1312,6 +1362,10 @@ int flowgnn_set_numeric_mode(flowgnn_engine* e, int mode) {
             e->err = o.no_fixed_point;
             return FLOWGNN_ERR_UNSUPPORTED;
         }
+    if (mode != FLOWGNN_NUMERIC_F32 && e->model_id == FLOWGNN_MODEL_GIN && e->emb_dim != FLOWGNN_EMB_DIM_REFERENCE) {
+        e->err = "flowgnn_set_numeric_mode: the engine's width is 300 (flowgnn_set_emb_dim), which has neither fixed-point nor f16 kernels";
+        return FLOWGNN_ERR_UNSUPPORTED;
+    }
     if (mode == FLOWGNN_NUMERIC_Q6_10 && e->pooling != FLOWGNN_POOL_MEAN) {
         e->err = "flowgnn_set_numeric_mode: the pooling is not the mean (flowgnn_set_pooling), and the fixed-point readout is the reference's mean";
         return FLOWGNN_ERR_UNSUPPORTED;
@@ -1446,6 +1500,10 @@ int flowgnn_set_ogb_virtual_node(flowgnn_engine* e, const float* vn_embedding, c
         if (e->model_id == FLOWGNN_MODEL_GCN) e->err += "; GCN has a call of its own, flowgnn_set_gcn_virtual_node";
         return FLOWGNN_ERR_UNSUPPORTED;
     }
+    if (e->emb_dim != FLOWGNN_EMB_DIM_REFERENCE && (vn_embedding || w1 || b1 || w2 || b2)) {
+        e->err = "flowgnn_set_ogb_virtual_node: the engine's width is 300 (flowgnn_set_emb_dim), and the virtual node's tensors are 100 wide";
+        return FLOWGNN_ERR_UNSUPPORTED;
+    }
     return set_virtual_node(e, "flowgnn_set_ogb_virtual_node", vn_embedding, w1, b1, w2, b2);
 }
 
@@ -1564,6 +1622,7 @@ int flowgnn_profile_read(flowgnn_engine* e, int* count, const char** names, doub
 
 int flowgnn_run_aggregation_only(flowgnn_engine* e, int layer, int iters, float* avg_ms) {
     if (!e || iters <= 0) return FLOWGNN_ERR_ARG;
+    if (e->model_id == FLOWGNN_MODEL_GIN && e->emb_dim != FLOWGNN_EMB_DIM_REFERENCE) { e->err = "flowgnn_run_aggregation_only: the engine's width is 300 (flowgnn_set_emb_dim), which has no stand-alone aggregation kernel"; return FLOWGNN_ERR_UNSUPPORTED; }
     if (!e->ran) { e->err = "flowgnn_run_aggregation_only needs a prior flowgnn_run"; return FLOWGNN_ERR_STATE; }
     if (e->gin_eps_on) { e->err = "flowgnn_run_aggregation_only: a trained eps is on (flowgnn_set_gin_eps), and the stand-alone aggregation kernel has no eps instance"; return FLOWGNN_ERR_UNSUPPORTED; }
     if (e->ogb_vn_on) { e->err = "flowgnn_run_aggregation_only: OGB's virtual node is on (flowgnn_set_ogb_virtual_node / flowgnn_set_gcn_virtual_node), and the stand-alone aggregation kernel does not add it"; return FLOWGNN_ERR_UNSUPPORTED; }
@@ -1596,6 +1655,7 @@ int flowgnn_run_aggregation_only(flowgnn_engine* e, int layer, int iters, float*
 
 int flowgnn_get_aggregate(flowgnn_engine* e, int layer, float* h_in_host, int* in_dim, float* agg_host, int* agg_dim) {
     if (!e) return FLOWGNN_ERR_ARG;
+    if (e->model_id == FLOWGNN_MODEL_GIN && e->emb_dim != FLOWGNN_EMB_DIM_REFERENCE) { e->err = "flowgnn_get_aggregate: the engine's width is 300 (flowgnn_set_emb_dim), which has no stand-alone aggregation kernel"; return FLOWGNN_ERR_UNSUPPORTED; }
     if (!e->ran) { e->err = "flowgnn_get_aggregate needs a prior flowgnn_run"; return FLOWGNN_ERR_STATE; }
     if (e->gin_eps_on) { e->err = "flowgnn_get_aggregate: a trained eps is on (flowgnn_set_gin_eps), and the stand-alone aggregation kernel has no eps instance"; return FLOWGNN_ERR_UNSUPPORTED; }
     if (e->ogb_vn_on) { e->err = "flowgnn_get_aggregate: OGB's virtual node is on (flowgnn_set_ogb_virtual_node / flowgnn_set_gcn_virtual_node), and the stand-alone aggregation kernel does not add it"; return FLOWGNN_ERR_UNSUPPORTED; }

@@ -1,0 +1,586 @@
+// GIN at OGB's default width (emb_dim 300, hidden 600): flowgnn_set_emb_dim(e, FLOWGNN_EMB_DIM_OGB).  DESIGN.md section 4.16.
+//
+// A model of its own beside GinModel (gin.hip): the graph-resident kernel keeps 256 rows x 100 floats on chip and cannot be widened, so
+// this width runs one launch per layer, where a tile is a run of consecutive rows and nothing depends on a graph fitting on chip.
+//
+// Layer kernel (gw_layer_kernel<D>, H = 2 D): the scheme of gin_layer_split_kernel (gin_split.hip) -- a wave owns one 16-node column
+// tile, gathers a[v] = s_l h[v] + sum_e relu(h[src_e] + ecomb[code_e]) straight into the B-operand layout of the f16 matrix pipe, and
+// runs both dense products as three f16 MFMAs per product (w_hi x_hi + w_hi x_lo + w_lo x_hi, fp32 accumulate, weights pre-scaled by a
+// power of two and split on the host, activations split by DS_SPLIT2).  Per step it runs MLP1 of two hidden tiles and feeds them as ONE
+// K-step of MLP2 into the T2 row accumulators: the C layout of one MFMA is the B layout of the next (the K permutation of
+// dense_split.h), so the hidden layer never leaves the wave.  K is padded with zero weights (D -> 32 KS1, H -> 16 T1): no fp32 K tail.
+// The weight stream (STEPS chunks per layer) goes L2 -> LDS by LDS-DMA, double buffered in two distinct LDS objects and shared by the
+// eight waves of a 128-row workgroup; the only synchronisation is s_waitcnt vmcnt(0) + a workgroup barrier per step.
+//   lane (j = lane & 15, g = lane >> 4); B operand of K-step ks, slot e (0..7): feature 16 (2 ks + (e >> 2)) + 4 g + (e & 3).
+// Operands beyond the f16 range raise *range_flag; the engine then repeats the pass with set_exact(true), which runs the fp32 form of
+// the layer (gw_aggregate_kernel + gw_dense_f32_kernel twice, plain FMAs, the same row order).
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "common.h"
+#include "dense_split.h"
+
+namespace fg {
+namespace {
+
+constexpr int GW_L = 5;
+constexpr int GW_WAVES = 8;
+constexpr int GW_ROWS = GW_WAVES * 16;  // rows of a workgroup
+
+template <int D>
+struct GwDims {
+    static_assert(D % 4 == 0, "rows are read as float4 pieces");
+    static constexpr int H = 2 * D;
+    static constexpr int C = D / 4;               // float4 pieces of a row
+    static constexpr int KS1 = (D + 31) / 32;     // K-steps of the first product (K padded to 32 KS1)
+    static constexpr int Q = 2 * KS1;             // 16-feature pieces a lane holds four floats of
+    static constexpr int KS2 = (H + 31) / 32;     // K-steps of the second product
+    static constexpr int T1 = 2 * KS2;            // 16-row tiles of the hidden layer (K of the second product padded to 16 T1)
+    static constexpr int T2 = (D + 15) / 16;      // 16-row tiles of the output, the last one masked at column D
+    static constexpr int STEPS = KS2 + 1;         // step s: MLP1 of hidden tiles 2s, 2s + 1 (s < KS2) and K-step s - 1 of MLP2 (s > 0)
+    static_assert(STEPS % 2 == 0, "the step loop alternates two LDS buffers");
+    // chunk s of the weight stream, in 1 KiB fragments (64 lanes x 8 halves):
+    //   [0, W2_OFF): W1 of hidden tiles 2s, 2s + 1: fragment ((ks * 2 + tl) * 2 + p), p = 0 hi, 1 lo          (absent for s = KS2)
+    //   [W2_OFF, B1_OFF): W2 of K-step s - 1: fragment (t2 * 2 + p)                                          (absent for s = 0)
+    //   [B1_OFF, CHUNK_BYTES): b1 of the two hidden tiles, pre-scaled: 2 x 16 floats
+    static constexpr int W2_OFF = KS1 * 2 * 2 * 1024;
+    static constexpr int B1_OFF = W2_OFF + T2 * 2 * 1024;
+    static constexpr int CHUNK_BYTES = B1_OFF + 2 * 16 * 4;
+    static constexpr int PIECES = (CHUNK_BYTES + 1023) / 1024;   // DMA pieces of 1 KiB, the last one partial
+    static constexpr int LAST_LANES = (CHUNK_BYTES - (PIECES - 1) * 1024) / 16;
+    static constexpr int CHUNK_STRIDE = PIECES * 1024;           // in global memory
+    static constexpr size_t LAYER_BYTES = (size_t)STEPS * CHUNK_STRIDE;
+    static constexpr int ECOMB_BYTES = EDGE_COMBOS * D * 4;      // the layer's 60 combined edge rows: in buffer A until the first odd chunk
+    static constexpr int ECOMB_PIECES = (ECOMB_BYTES + 1023) / 1024;
+    static constexpr int ECOMB_LAST_LANES = (ECOMB_BYTES - (ECOMB_PIECES - 1) * 1024) / 16;
+    static_assert(ECOMB_BYTES <= CHUNK_BYTES && ECOMB_BYTES % 16 == 0, "the combined edge table shares buffer A");
+    static_assert(2 * CHUNK_BYTES <= 160 * 1024, "two weight buffers must fit the CU's LDS");
+    static constexpr int TAIL_FLOATS = T2 * 16 + 4;  // per layer, read from global memory: b2 pre-scaled and padded, then 1 / (s1 s2)
+};
+
+__device__ __forceinline__ float gw_relu(float x) {  // max(x, 0) as one integer max (gin_split.hip: gs_relu)
+    const int b = __builtin_bit_cast(int, x);
+    return __builtin_bit_cast(float, b > 0 ? b : 0);
+}
+
+template <int D>
+__device__ __forceinline__ void gw_issue(const uint8_t* __restrict__ gsrc, char* lds_buf, int pieces, int last_lanes, int wave, int lane) {
+#pragma unroll
+    for (int p = 0; p < (GwDims<D>::PIECES + GW_WAVES - 1) / GW_WAVES; p++) {
+        const int piece = wave + GW_WAVES * p;
+        if (piece < pieces - 1 || (piece == pieces - 1 && lane < last_lanes)) {
+            const uint8_t* g = gsrc + piece * 1024 + lane * 16;
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
+                                             (__attribute__((address_space(3))) void*)(lds_buf + piece * 1024), 16, 0, 0);
+        }
+    }
+}
+
+// one step from the chunk in `wb`: MLP1 of hidden tiles 2s, 2s + 1 (their ReLU'd, split values become h_hi / h_lo for the next step),
+// and K-step s - 1 of MLP2 from the h_hi / h_lo the previous step left
+template <int D>
+__device__ __forceinline__ void gw_step(const char* wb, int s, int lane, int g, const ds_uint4_t (&in_hi)[GwDims<D>::KS1],
+                                        const ds_uint4_t (&in_lo)[GwDims<D>::KS1], ds_uint4_t& h_hi, ds_uint4_t& h_lo,
+                                        float4_t (&acc2)[GwDims<D>::T2], float& vmax) {
+    using M = GwDims<D>;
+    ds_uint4_t n_hi = {0, 0, 0, 0}, n_lo = {0, 0, 0, 0};
+    if (s < M::KS2) {
+        float4_t acc1[2];
+#pragma unroll
+        for (int tl = 0; tl < 2; tl++) {
+            const float4 b = *reinterpret_cast<const float4*>(wb + M::B1_OFF + tl * 64 + g * 16);
+            acc1[tl] = (float4_t){b.x, b.y, b.z, b.w};
+        }
+#pragma unroll
+        for (int ks = 0; ks < M::KS1; ks++) {
+            ds_uint4_t a[2][2];
+#pragma unroll
+            for (int tl = 0; tl < 2; tl++)
+#pragma unroll
+                for (int p = 0; p < 2; p++) a[tl][p] = *reinterpret_cast<const ds_uint4_t*>(wb + ((ks * 2 + tl) * 2 + p) * 1024 + lane * 16);
+#pragma unroll
+            for (int tl = 0; tl < 2; tl++) acc1[tl] = DS_MFMA16(a[tl][0], in_hi[ks], acc1[tl]);
+#pragma unroll
+            for (int tl = 0; tl < 2; tl++) acc1[tl] = DS_MFMA16(a[tl][0], in_lo[ks], acc1[tl]);
+#pragma unroll
+            for (int tl = 0; tl < 2; tl++) acc1[tl] = DS_MFMA16(a[tl][1], in_hi[ks], acc1[tl]);
+        }
+        float4_t r0 = acc1[0], r1 = acc1[1];
+        r0.x = gw_relu(r0.x); r0.y = gw_relu(r0.y); r0.z = gw_relu(r0.z); r0.w = gw_relu(r0.w);
+        r1.x = gw_relu(r1.x); r1.y = gw_relu(r1.y); r1.z = gw_relu(r1.z); r1.w = gw_relu(r1.w);
+        vmax = __builtin_fmaxf(__builtin_fmaxf(vmax, r0.x), r0.y);
+        vmax = __builtin_fmaxf(__builtin_fmaxf(vmax, r0.z), r0.w);
+        vmax = __builtin_fmaxf(__builtin_fmaxf(vmax, r1.x), r1.y);
+        vmax = __builtin_fmaxf(__builtin_fmaxf(vmax, r1.z), r1.w);
+        asm volatile("" : "+v"(vmax));
+        DS_SPLIT2(r0.x, r0.y, n_hi.x, n_lo.x);
+        DS_SPLIT2(r0.z, r0.w, n_hi.y, n_lo.y);
+        DS_SPLIT2(r1.x, r1.y, n_hi.z, n_lo.z);
+        DS_SPLIT2(r1.z, r1.w, n_hi.w, n_lo.w);
+    }
+    if (s > 0) {
+#pragma unroll
+        for (int t2 = 0; t2 < M::T2; t2++) {
+            const ds_uint4_t a_hi = *reinterpret_cast<const ds_uint4_t*>(wb + M::W2_OFF + (t2 * 2 + 0) * 1024 + lane * 16);
+            const ds_uint4_t a_lo = *reinterpret_cast<const ds_uint4_t*>(wb + M::W2_OFF + (t2 * 2 + 1) * 1024 + lane * 16);
+            acc2[t2] = DS_MFMA16(a_hi, h_hi, acc2[t2]);
+            acc2[t2] = DS_MFMA16(a_hi, h_lo, acc2[t2]);
+            acc2[t2] = DS_MFMA16(a_lo, h_hi, acc2[t2]);
+        }
+    }
+    h_hi = n_hi;
+    h_lo = n_lo;
+}
+
+// hout[v] = W2 relu(W1 a[v] + b1) + b2 (ReLU'd if relu_out), a[v] = fma(h[v], self_s, sum over v's in-edges, in CSR order)
+template <int D>
+__global__ __launch_bounds__(GW_WAVES * 64) void gw_layer_kernel(const float* __restrict__ h, float* __restrict__ hout,
+                                                                 const int* __restrict__ row_ptr, const int* __restrict__ src,
+                                                                 const uint8_t* __restrict__ ecode, const float* __restrict__ ecomb,
+                                                                 const uint8_t* __restrict__ wchunks, const float* __restrict__ tailp,
+                                                                 int n_tot, int relu_out, float self_s, int* __restrict__ range_flag) {
+    using M = GwDims<D>;
+    // two DISTINCT LDS objects, as in gin_layer_split_kernel: the DMA into one does not alias the reads of the other
+    __shared__ __attribute__((aligned(16))) char s_a[M::CHUNK_BYTES];  // the combined edge table, then the odd chunks
+    __shared__ __attribute__((aligned(16))) char s_b[M::CHUNK_BYTES];  // the even chunks
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int j = lane & 15, g = lane >> 4;
+    const long long node0 = (long long)blockIdx.x * GW_ROWS + wave * 16 + j;
+    const bool valid = node0 < n_tot;
+    const long long node = valid ? node0 : (long long)n_tot - 1;
+
+    int e_cur = row_ptr[node];
+    const int e_end = valid ? row_ptr[node + 1] : e_cur;
+    gw_issue<D>(wchunks, s_b, M::PIECES, M::LAST_LANES, wave, lane);                                                  // chunk 0
+    gw_issue<D>(reinterpret_cast<const uint8_t*>(ecomb), s_a, M::ECOMB_PIECES, M::ECOMB_LAST_LANES, wave, lane);      // the edge table
+    float bq[4 * M::Q];
+#pragma unroll
+    for (int k = 0; k < 4 * M::Q; k++) bq[k] = 0.0f;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    const float* s_ecomb = reinterpret_cast<const float*>(s_a);
+
+    // ---- gather: one in-edge per trip, in CSR order (a row's sum depends on the row alone); pieces at or beyond column D stay zero
+    while (__any(e_cur < e_end)) {
+        if (e_cur < e_end) {
+            const int u = src[e_cur];
+            const int code = ecode[e_cur];
+            e_cur++;
+            const float* hr = h + (size_t)u * D + 4 * g;
+            const float* er = s_ecomb + code * D + 4 * g;
+#pragma unroll
+            for (int q0 = 0; q0 < M::Q; q0 += M::KS1) {
+                float4 x[M::KS1];
+#pragma unroll
+                for (int q = 0; q < M::KS1; q++)
+                    if (16 * (q0 + q) + 4 * g < D) x[q] = *reinterpret_cast<const float4*>(hr + 16 * (q0 + q));
+#pragma unroll
+                for (int q = 0; q < M::KS1; q++)
+                    if (16 * (q0 + q) + 4 * g < D) {
+                        const float4 w = *reinterpret_cast<const float4*>(er + 16 * (q0 + q));
+                        bq[4 * (q0 + q) + 0] += relu1(w.x + x[q].x);
+                        bq[4 * (q0 + q) + 1] += relu1(w.y + x[q].y);
+                        bq[4 * (q0 + q) + 2] += relu1(w.z + x[q].z);
+                        bq[4 * (q0 + q) + 3] += relu1(w.w + x[q].w);
+                    }
+            }
+        }
+    }
+    // ---- a = fma(h[v], s_l, m): one fp32 rounding (s_l = 1: the bits of the plain sum), then split into the B operands of MLP1
+    float vmax = 0.0f;
+    ds_uint4_t in_hi[M::KS1], in_lo[M::KS1];
+    {
+        const float* hr = h + (size_t)node * D + 4 * g;
+#pragma unroll
+        for (int q = 0; q < M::Q; q++)
+            if (16 * q + 4 * g < D) {
+                const float4 x = *reinterpret_cast<const float4*>(hr + 16 * q);
+                bq[4 * q + 0] = __builtin_fmaf(x.x, self_s, bq[4 * q + 0]);
+                bq[4 * q + 1] = __builtin_fmaf(x.y, self_s, bq[4 * q + 1]);
+                bq[4 * q + 2] = __builtin_fmaf(x.z, self_s, bq[4 * q + 2]);
+                bq[4 * q + 3] = __builtin_fmaf(x.w, self_s, bq[4 * q + 3]);
+            }
+#pragma unroll
+        for (int k = 0; k < 4 * M::Q; k += 2) vmax = __builtin_fmaxf(__builtin_fmaxf(vmax, __builtin_fabsf(bq[k])), __builtin_fabsf(bq[k + 1]));
+#pragma unroll
+        for (int ks = 0; ks < M::KS1; ks++) {
+            DS_SPLIT2(bq[8 * ks + 0], bq[8 * ks + 1], in_hi[ks].x, in_lo[ks].x);
+            DS_SPLIT2(bq[8 * ks + 2], bq[8 * ks + 3], in_hi[ks].y, in_lo[ks].y);
+            DS_SPLIT2(bq[8 * ks + 4], bq[8 * ks + 5], in_hi[ks].z, in_lo[ks].z);
+            DS_SPLIT2(bq[8 * ks + 6], bq[8 * ks + 7], in_hi[ks].w, in_lo[ks].w);
+        }
+    }
+    float4_t acc2[M::T2];
+#pragma unroll
+    for (int t2 = 0; t2 < M::T2; t2++) {
+        const float4 b = *reinterpret_cast<const float4*>(tailp + 16 * t2 + 4 * g);
+        acc2[t2] = (float4_t){b.x, b.y, b.z, b.w};
+    }
+    const float oscale = tailp[M::T2 * 16];
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();  // every wave is done with the edge table: s_a may be overwritten (chunk 0 has been resident since the first barrier)
+
+    // ---- node MLP, weights streamed through LDS
+    ds_uint4_t h_hi = {0, 0, 0, 0}, h_lo = {0, 0, 0, 0};
+#pragma unroll 1
+    for (int c = 0; c < M::STEPS; c += 2) {
+        gw_issue<D>(wchunks + (size_t)(c + 1) * M::CHUNK_STRIDE, s_a, M::PIECES, M::LAST_LANES, wave, lane);
+        gw_step<D>(s_b, c, lane, g, in_hi, in_lo, h_hi, h_lo, acc2, vmax);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's pieces of chunk c + 1 have landed
+        __syncthreads();                                  // everyone's have; everyone is done with s_b
+        if (c + 2 < M::STEPS) gw_issue<D>(wchunks + (size_t)(c + 2) * M::CHUNK_STRIDE, s_b, M::PIECES, M::LAST_LANES, wave, lane);
+        gw_step<D>(s_a, c + 1, lane, g, in_hi, in_lo, h_hi, h_lo, acc2, vmax);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+    }
+
+    if (valid) {
+        float* row = hout + (size_t)node * D;
+#pragma unroll
+        for (int t2 = 0; t2 < M::T2; t2++) {
+            const int col = 16 * t2 + 4 * g;
+            if (col < D) {
+                float4_t r = acc2[t2] * oscale;
+                if (relu_out) { r.x = gw_relu(r.x); r.y = gw_relu(r.y); r.z = gw_relu(r.z); r.w = gw_relu(r.w); }
+                *reinterpret_cast<float4*>(row + col) = make_float4(r.x, r.y, r.z, r.w);
+            }
+        }
+    }
+    if (__any(!(vmax < 6.0e4f))) {
+        if (lane == 0) atomicOr(range_flag, 1);
+    }
+}
+
+// ---------------------------------------------------------------- the exact (fp32) form of the layer: the same sums, plain FMAs
+// a[v] = fma(h[v], s_l, m[v]), m[v] the in-edge sum in CSR order; one lane per (node, float4 piece)
+template <int D>
+__global__ __launch_bounds__(256) void gw_aggregate_kernel(const float* __restrict__ h, float* __restrict__ a, const int* __restrict__ row_ptr,
+                                                           const int* __restrict__ src, const uint8_t* __restrict__ ecode,
+                                                           const float* __restrict__ ecomb, int n_tot, float self_s) {
+    constexpr int C = D / 4;
+    const long long items = (long long)n_tot * C;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < items; i += (long long)gridDim.x * 256) {
+        const long long v = i / C;
+        const int c = (int)(i - v * C);
+        float4 m = make_float4(0.f, 0.f, 0.f, 0.f);
+        const int e1 = row_ptr[v + 1];
+        for (int e = row_ptr[v]; e < e1; e++) {
+            const float4 x = reinterpret_cast<const float4*>(h)[(size_t)src[e] * C + c];
+            const float4 w = reinterpret_cast<const float4*>(ecomb)[(size_t)ecode[e] * C + c];
+            m.x += relu1(w.x + x.x); m.y += relu1(w.y + x.y); m.z += relu1(w.z + x.z); m.w += relu1(w.w + x.w);
+        }
+        const float4 x = reinterpret_cast<const float4*>(h)[(size_t)v * C + c];
+        reinterpret_cast<float4*>(a)[(size_t)v * C + c] =
+            make_float4(__builtin_fmaf(x.x, self_s, m.x), __builtin_fmaf(x.y, self_s, m.y), __builtin_fmaf(x.z, self_s, m.z), __builtin_fmaf(x.w, self_s, m.w));
+    }
+}
+
+// out[v][o] = act(b[o] + sum_k in[v][k] wt[k][o]), k ascending; eight rows per workgroup staged in LDS, a thread owns output columns
+template <int K, int O>
+__global__ __launch_bounds__(256) void gw_dense_f32_kernel(const float* __restrict__ in, const float* __restrict__ wt, const float* __restrict__ b,
+                                                           float* __restrict__ out, int n_tot, int relu_out) {
+    constexpr int RB = 8;
+    __shared__ float s_in[RB][K];
+    const long long v0 = (long long)blockIdx.x * RB;
+    for (int i = threadIdx.x; i < RB * K; i += 256) {
+        const int r = i / K, k = i - r * K;
+        s_in[r][k] = v0 + r < n_tot ? in[(size_t)(v0 + r) * K + k] : 0.0f;
+    }
+    __syncthreads();
+    for (int o = threadIdx.x; o < O; o += 256) {
+        float acc[RB];
+        const float bo = b[o];
+#pragma unroll
+        for (int r = 0; r < RB; r++) acc[r] = bo;
+        for (int k = 0; k < K; k++) {
+            const float w = wt[(size_t)k * O + o];
+#pragma unroll
+            for (int r = 0; r < RB; r++) acc[r] = __builtin_fmaf(s_in[r][k], w, acc[r]);
+        }
+#pragma unroll
+        for (int r = 0; r < RB; r++)
+            if (v0 + r < n_tot) out[(size_t)(v0 + r) * O + o] = relu_out ? relu1(acc[r]) : acc[r];
+    }
+}
+
+// ---------------------------------------------------------------- atom encoder and pooling at this width
+// (atom_encoder_kernel<D> stages the 173-row table in LDS, and the readout kernels of device_common.h hold a row in half a wavefront:
+// neither fits 75 float4 pieces.)  One lane per (node, float4 piece), the table read through the caches; summation order k = 0..8.
+template <int D>
+__global__ __launch_bounds__(256) void gw_atom_encoder_kernel(const int* __restrict__ node_feature, const float* __restrict__ table,
+                                                              float* __restrict__ h, int n_tot, int* __restrict__ err) {
+    constexpr int C = D / 4;
+    const long long items = (long long)n_tot * C;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < items; i += (long long)gridDim.x * 256) {
+        const long long v = i / C;
+        const int c = (int)(i - v * C);
+        float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (int k = 0; k < ND_FEATURE; k++) {
+            int f = node_feature[v * ND_FEATURE + k];
+            if (f < 0 || f >= c_nd_card[k]) {
+                atomicMax(err, ERR_NODE_FEAT);
+                f = 0;
+            }
+            const float4 w = reinterpret_cast<const float4*>(table)[(size_t)(c_nd_off[k] + f) * C + c];
+            s.x += w.x; s.y += w.y; s.z += w.z; s.w += w.w;
+        }
+        reinterpret_cast<float4*>(h)[i] = s;
+    }
+}
+
+// emb[g][:] = pool over the rows of graph g, in node order: one wavefront per graph, a lane owns the float4 pieces lane, lane + 64, ...
+// -- every column is one chain in node order, so the value depends on the graph alone
+template <int D, int OP>
+__global__ __launch_bounds__(256) void gw_pool_rows_kernel(const float* __restrict__ rows, const int* __restrict__ node_off, float* __restrict__ emb,
+                                                           int num_graphs) {
+    constexpr int C = D / 4;
+    const int lane = threadIdx.x & 63;
+    const int gi = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (gi >= num_graphs) return;
+    const int n0 = node_off[gi], n1 = node_off[gi + 1];
+    const float n = (float)(n1 - n0);
+    for (int c = lane; c < C; c += 64) {
+        float4 acc = make_float4(pool_init<OP>(), pool_init<OP>(), pool_init<OP>(), pool_init<OP>());
+        for (int v = n0; v < n1; v++) pool_fold4<OP>(acc, reinterpret_cast<const float4*>(rows)[(size_t)v * C + c]);
+        reinterpret_cast<float4*>(emb)[(size_t)gi * C + c] =
+            make_float4(pool_finish<OP>(acc.x, n), pool_finish<OP>(acc.y, n), pool_finish<OP>(acc.z, n), pool_finish<OP>(acc.w, n));
+    }
+}
+
+inline float gw_pow2_scale(const float* w, size_t n) {
+    float m = 0.0f;
+    for (size_t i = 0; i < n; i++) m = std::fmax(m, std::fabs(w[i]));
+    if (!(m > 0.0f) || !std::isfinite(m)) return 1.0f;
+    return std::ldexp(1.0f, -std::ilogb(m));  // m * scale in [1, 2)
+}
+
+inline void gw_put_split(uint8_t* frag, int lane, int e, float v) {
+    const _Float16 hi = (_Float16)v;  // to nearest even
+    const _Float16 lo = (_Float16)(v - (float)hi);
+    std::memcpy(frag + lane * 16 + e * 2, &hi, 2);
+    std::memcpy(frag + 1024 + lane * 16 + e * 2, &lo, 2);
+}
+
+// w1 [H][D], b1 [H], w2 [D][H], b2 [D] (row-major, host) -> LAYER_BYTES of chunks and TAIL_FLOATS floats
+template <int D>
+void gw_pack_layer(const float* w1, const float* b1, const float* w2, const float* b2, uint8_t* out, float* tail) {
+    using M = GwDims<D>;
+    std::memset(out, 0, M::LAYER_BYTES);
+    const float s1 = gw_pow2_scale(w1, (size_t)M::H * D);
+    const float s2 = gw_pow2_scale(w2, (size_t)D * M::H);
+    for (int s = 0; s < M::STEPS; s++) {
+        uint8_t* ck = out + (size_t)s * M::CHUNK_STRIDE;
+        if (s < M::KS2)
+            for (int tl = 0; tl < 2; tl++) {
+                const int t = 2 * s + tl;
+                for (int lane = 0; lane < 64; lane++) {
+                    const int i = lane & 15, gk = lane >> 4, o = 16 * t + i;
+                    for (int ks = 0; ks < M::KS1; ks++)
+                        for (int e = 0; e < 8; e++) {
+                            const int f = 16 * (2 * ks + (e >> 2)) + 4 * gk + (e & 3);
+                            gw_put_split(ck + (size_t)((ks * 2 + tl) * 2) * 1024, lane, e, (o < M::H && f < D) ? w1[(size_t)o * D + f] * s1 : 0.0f);
+                        }
+                }
+                for (int x = 0; x < 16; x++) {
+                    const int o = 16 * t + x;
+                    const float b = o < M::H ? b1[o] * s1 : 0.0f;
+                    std::memcpy(ck + M::B1_OFF + tl * 64 + x * 4, &b, 4);
+                }
+            }
+        if (s > 0) {
+            const int ks = s - 1;
+            for (int t2 = 0; t2 < M::T2; t2++)
+                for (int lane = 0; lane < 64; lane++) {
+                    const int i = lane & 15, gk = lane >> 4, d = 16 * t2 + i;
+                    for (int e = 0; e < 8; e++) {
+                        const int k = 16 * (2 * ks + (e >> 2)) + 4 * gk + (e & 3);
+                        gw_put_split(ck + M::W2_OFF + (size_t)(t2 * 2) * 1024, lane, e, (d < D && k < M::H) ? w2[(size_t)d * M::H + k] * s2 : 0.0f);
+                    }
+                }
+        }
+    }
+    for (int x = 0; x < M::TAIL_FLOATS; x++) tail[x] = 0.0f;
+    for (int x = 0; x < D; x++) tail[x] = b2[x] * s1 * s2;
+    tail[M::T2 * 16] = 1.0f / (s1 * s2);
+}
+
+template <int D>
+class GinWideModel : public Model {
+    using M = GwDims<D>;
+    static constexpr int H = M::H;
+
+public:
+    ~GinWideModel() override { free_all(); }
+    int emb_dim() const override { return D; }
+    int scratch_dim() const override { return D; }
+    bool has_edge_attr() const override { return true; }
+    int num_weight_tensors() const override { return 8; }
+    bool weights_ready() const override { return ready_; }
+    void set_exact(bool on) override { exact_ = on; }
+    int set_num_tasks(int t) override {
+        if (t < 1) return 8;
+        if (t != num_tasks_) ready_ = false;  // graph_pred_weights / bias change shape: set the weights again
+        num_tasks_ = t;
+        return 0;
+    }
+
+    // host tensors: node_emb[173][D], edge_emb[5][13][D], w1[5][H][D], b1[5][H], w2[5][D][H], b2[5][D], pred_w[NUM_TASK][D], pred_b[NUM_TASK]
+    int set_weights(const float* const* t) override {
+        const float *nemb = t[0], *eemb = t[1], *w1 = t[2], *b1 = t[3], *w2 = t[4], *b2 = t[5], *pw = t[6], *pb = t[7];
+        std::vector<float> v_nemb(nemb, nemb + (size_t)ND_FEATURE_TOTAL * D);
+        std::vector<float> v_pw(pw, pw + (size_t)num_tasks_ * D), v_pb(pb, pb + num_tasks_);
+        std::vector<float> v_b1(b1, b1 + (size_t)GW_L * H), v_b2(b2, b2 + (size_t)GW_L * D);
+        std::vector<float> ecomb((size_t)GW_L * EDGE_COMBOS * D);
+        std::vector<float> w1t((size_t)GW_L * D * H), w2t((size_t)GW_L * H * D);  // the exact form's [K][O] copies
+        std::vector<uint8_t> chunks((size_t)GW_L * M::LAYER_BYTES);
+        std::vector<float> tails((size_t)GW_L * M::TAIL_FLOATS);
+        static const int ed_off[3] = {0, 5, 11};
+        for (int l = 0; l < GW_L; l++) {
+            const float* E = eemb + (size_t)l * ED_FEATURE_PER_LAYER * D;
+            for (int a0 = 0; a0 < 5; a0++)
+                for (int a1 = 0; a1 < 6; a1++)
+                    for (int a2 = 0; a2 < 2; a2++) {
+                        const int code = (a0 * 6 + a1) * 2 + a2;
+                        for (int d = 0; d < D; d++) {
+                            float s = 0.0f;  // the order of GinModel::set_weights
+                            s += E[(ed_off[0] + a0) * D + d];
+                            s += E[(ed_off[1] + a1) * D + d];
+                            s += E[(ed_off[2] + a2) * D + d];
+                            ecomb[((size_t)l * EDGE_COMBOS + code) * D + d] = s;
+                        }
+                    }
+            const float* W1 = w1 + (size_t)l * H * D;
+            const float* W2 = w2 + (size_t)l * D * H;
+            for (int o = 0; o < H; o++)
+                for (int k = 0; k < D; k++) w1t[(size_t)l * D * H + (size_t)k * H + o] = W1[(size_t)o * D + k];
+            for (int o = 0; o < D; o++)
+                for (int k = 0; k < H; k++) w2t[(size_t)l * H * D + (size_t)k * D + o] = W2[(size_t)o * H + k];
+            gw_pack_layer<D>(W1, b1 + (size_t)l * H, W2, b2 + (size_t)l * D, chunks.data() + (size_t)l * M::LAYER_BYTES,
+                             tails.data() + (size_t)l * M::TAIL_FLOATS);
+        }
+        int rc;
+        if ((rc = upload(&d_chunks_, chunks))) return rc;
+        if ((rc = upload(&d_tails_, tails))) return rc;
+        if ((rc = upload(&d_nemb_, v_nemb))) return rc;
+        if ((rc = upload(&d_pw_, v_pw))) return rc;
+        if ((rc = upload(&d_pb_, v_pb))) return rc;
+        if ((rc = upload(&d_ecomb_, ecomb))) return rc;
+        if ((rc = upload(&d_w1t_, w1t))) return rc;
+        if ((rc = upload(&d_w2t_, w2t))) return rc;
+        if ((rc = upload(&d_b1_, v_b1))) return rc;
+        if ((rc = upload(&d_b2_, v_b2))) return rc;
+        ready_ = true;
+        return 0;
+    }
+
+    // the reference's file names (GIN/src/host_load.cc:24-58) with this width in place of 100
+    int load_weights_dir(const char* dir) override {
+        std::vector<float> w1((size_t)GW_L * H * D), b1((size_t)GW_L * H), w2((size_t)GW_L * D * H), b2((size_t)GW_L * D),
+            nemb((size_t)ND_FEATURE_TOTAL * D), eemb((size_t)GW_L * ED_FEATURE_PER_LAYER * D), pw((size_t)num_tasks_ * D), pb(num_tasks_);
+        const std::string sfx = "_dim" + std::to_string(D) + ".bin";
+        int rc;
+        if ((rc = read_floats(dir, ("gin_ep1_mlp_1_weights" + sfx).c_str(), 0, w1.size(), w1.data()))) return rc;
+        if ((rc = read_floats(dir, ("gin_ep1_mlp_1_bias" + sfx).c_str(), 0, b1.size(), b1.data()))) return rc;
+        if ((rc = read_floats(dir, ("gin_ep1_mlp_2_weights" + sfx).c_str(), 0, w2.size(), w2.data()))) return rc;
+        if ((rc = read_floats(dir, ("gin_ep1_mlp_2_bias" + sfx).c_str(), 0, b2.size(), b2.data()))) return rc;
+        if ((rc = read_floats(dir, ("gin_ep1_nd_embed" + sfx).c_str(), 0, nemb.size(), nemb.data()))) return rc;
+        if ((rc = read_floats(dir, ("gin_ep1_ed_embed" + sfx).c_str(), 0, eemb.size(), eemb.data()))) return rc;
+        if ((rc = read_floats(dir, ("gin_ep1_pred_weights" + sfx).c_str(), 0, pw.size(), pw.data()))) return rc;
+        if ((rc = read_floats(dir, ("gin_ep1_pred_bias" + sfx).c_str(), 0, pb.size(), pb.data()))) return rc;
+        const float* t[8] = {nemb.data(), eemb.data(), w1.data(), b1.data(), w2.data(), b2.data(), pw.data(), pb.data()};
+        return set_weights(t);
+    }
+
+    int forward(DeviceBatch& db, Profiler& prof, hipStream_t s) override {
+        const int n = db.b.n_tot;
+        if (n <= 0) return 0;
+        if (db.ogb_vn) {  // (the engine refuses it itself)
+            set_last_error("flowgnn_run: OGB's virtual node (flowgnn_set_ogb_virtual_node) has 100-wide tensors; this engine's width is not 100");
+            return 8;  // FLOWGNN_ERR_UNSUPPORTED
+        }
+        {
+            ProfScope p(prof, "atom_encoder", s);
+            gw_atom_encoder_kernel<D><<<grid_for((long long)n * M::C, 256, 256 * 8), 256, 0, s>>>(db.b.node_feature, d_nemb_, db.h[0], n, db.csr.err);
+        }
+        if (exact_)
+            if (int rc = hid_.reserve((size_t)n * H)) return rc;
+        int cur = 0;
+        for (int l = 0; l < GW_L; l++) {
+            // (node embeddings: the last layer writes h_5 straight into the caller's buffer, and the readout reads it there)
+            float* const hn = (l == GW_L - 1 && db.node_emb) ? db.node_emb : db.h[cur ^ 1];
+            const float self_s = db.gin_eps_on ? db.gin_self_scale[l] : 1.0f;
+            const float* ecomb = d_ecomb_ + (size_t)l * EDGE_COMBOS * D;
+            const int relu_out = l != GW_L - 1;
+            if (!exact_) {
+                ProfScope p(prof, "gin_wide_layer", s);
+                gw_layer_kernel<D><<<(int)ceil_div_ll(n, GW_ROWS), GW_WAVES * 64, 0, s>>>(
+                    db.h[cur], hn, db.csr.row_ptr, db.csr.src, db.csr.ecode, ecomb, d_chunks_ + (size_t)l * M::LAYER_BYTES,
+                    d_tails_ + (size_t)l * M::TAIL_FLOATS, n, relu_out, self_s, db.range_flag);
+            } else {
+                ProfScope p(prof, "gin_wide_layer_f32", s);
+                gw_aggregate_kernel<D><<<grid_for((long long)n * M::C, 256, 256 * 8), 256, 0, s>>>(db.h[cur], db.scratch, db.csr.row_ptr, db.csr.src,
+                                                                                                   db.csr.ecode, ecomb, n, self_s);
+                const int blocks = (int)ceil_div_ll(n, 8);
+                gw_dense_f32_kernel<D, H><<<blocks, 256, 0, s>>>(db.scratch, d_w1t_ + (size_t)l * D * H, d_b1_ + (size_t)l * H, hid_.p, n, 1);
+                gw_dense_f32_kernel<H, D><<<blocks, 256, 0, s>>>(hid_.p, d_w2t_ + (size_t)l * H * D, d_b2_ + (size_t)l * D, hn, n, relu_out);
+            }
+            cur ^= 1;
+        }
+        db.final_h = cur;
+        db.h_valid = !db.node_emb;
+        const float* const h5 = db.node_emb ? db.node_emb : db.h[cur];
+        // readout: the pooled rows (the caller's graph embeddings when they are on), then the head on them -- every NUM_TASK, every pooling
+        float* pooled = db.emb;
+        if (!pooled) {
+            if (int rc = pooled_.reserve((size_t)db.b.num_graphs * D)) return rc;
+            pooled = pooled_.p;
+        }
+        {
+            ProfScope p(prof, "mean_pool_rows", s);
+            const int grid = (db.b.num_graphs + 3) / 4;
+            if (db.pooling == POOL_OP_SUM) gw_pool_rows_kernel<D, POOL_OP_SUM><<<grid, 256, 0, s>>>(h5, db.b.node_off, pooled, db.b.num_graphs);
+            else if (db.pooling == POOL_OP_MAX) gw_pool_rows_kernel<D, POOL_OP_MAX><<<grid, 256, 0, s>>>(h5, db.b.node_off, pooled, db.b.num_graphs);
+            else gw_pool_rows_kernel<D, POOL_OP_MEAN><<<grid, 256, 0, s>>>(h5, db.b.node_off, pooled, db.b.num_graphs);
+        }
+        {
+            ProfScope p(prof, "pooled_head", s);
+            launch_pooled_head<D>(pooled, d_pw_, d_pb_, db.out, db.b.num_graphs, num_tasks_, s);
+        }
+        if (db.node_logits) {
+            ProfScope p(prof, "node_logits", s);
+            launch_node_logits_rows<D>(h5, d_pw_, d_pb_, db.node_logits, n, num_tasks_, s);
+        }
+        return 0;
+    }
+
+private:
+    void free_all() {
+        float** ptrs[] = {&d_tails_, &d_nemb_, &d_pw_, &d_pb_, &d_ecomb_, &d_w1t_, &d_w2t_, &d_b1_, &d_b2_};
+        for (auto p : ptrs)
+            if (*p) { (void)hipFree(*p); *p = nullptr; }
+        if (d_chunks_) { (void)hipFree(d_chunks_); d_chunks_ = nullptr; }
+        hid_.release();
+        pooled_.release();
+    }
+    bool ready_ = false;
+    bool exact_ = false;
+    int num_tasks_ = 1;
+    uint8_t* d_chunks_ = nullptr;  // the weight stream of gw_layer_kernel: GW_L x LAYER_BYTES
+    float* d_tails_ = nullptr;     // ... and per layer b2 (pre-scaled, padded) and the output scale
+    float *d_nemb_ = nullptr, *d_pw_ = nullptr, *d_pb_ = nullptr, *d_ecomb_ = nullptr;
+    float *d_w1t_ = nullptr, *d_w2t_ = nullptr, *d_b1_ = nullptr, *d_b2_ = nullptr;  // the exact form's weights, [K][O]
+    GrowBuf hid_;     // the exact form's hidden rows [N][H]
+    GrowBuf pooled_;  // the pooled rows [G][D] when graph embeddings are off
+};
+
+}  // namespace
+
+Model* make_gin_wide_model(int emb_dim) {
+    if (emb_dim == 300) return new GinWideModel<300>();  // FLOWGNN_EMB_DIM_OGB: the one instantiation
+    return nullptr;
+}
+
+}  // namespace fg

@@ -231,6 +231,13 @@ int flowgnn_group_set_num_tasks(flowgnn_group* g, int num_tasks) {
     if (!rc) g->num_tasks = num_tasks;
     return rc;
 }
+int flowgnn_group_set_emb_dim(flowgnn_group* g, int emb_dim) {
+    if (!g) return FLOWGNN_ERR_ARG;
+    g->err.clear();
+    for (flowgnn_engine* e : g->eng)
+        if (e->emb_dim != emb_dim) g->batch_valid = false;  // (a member that changes its width drops its shard with it)
+    return group_each(g, [&](int i) { return flowgnn_set_emb_dim(g->eng[(size_t)i], emb_dim); });
+}
 int flowgnn_group_set_numeric_mode(flowgnn_group* g, int mode) { return group_all(g, [&](flowgnn_engine* e) { return flowgnn_set_numeric_mode(e, mode); }); }
 int flowgnn_group_set_pooling(flowgnn_group* g, int mode) { return group_all(g, [&](flowgnn_engine* e) { return flowgnn_set_pooling(e, mode); }); }
 int flowgnn_group_set_gin_eps(flowgnn_group* g, const float* eps) { return group_all(g, [&](flowgnn_engine* e) { return flowgnn_set_gin_eps(e, eps); }); }
@@ -345,14 +352,14 @@ static int group_get_output(flowgnn_group* g, const char* who, bool have_out, co
 int flowgnn_group_get_embeddings(flowgnn_group* g, float* out_host) {
     const std::vector<size_t> first = first_rows(g, &flowgnn_engine::G);
     return group_get_output(g, "flowgnn_group_get_embeddings", out_host != nullptr, first, [](const flowgnn_engine* e) { return e->emb_on; },
-                            [&](flowgnn_engine* e, size_t i) { return flowgnn_get_embeddings(e, out_host + first[i] * (size_t)flowgnn_embedding_dim(e->model_id)); });
+                            [&](flowgnn_engine* e, size_t i) { return flowgnn_get_embeddings(e, out_host + first[i] * (size_t)flowgnn_emb_dim(e)); });
 }
 
 // [N_tot][dim] in job order
 int flowgnn_group_get_node_embeddings(flowgnn_group* g, float* out_host) {
     const std::vector<size_t> first = first_rows(g, &flowgnn_engine::N);
     return group_get_output(g, "flowgnn_group_get_node_embeddings", out_host != nullptr, first, [](const flowgnn_engine* e) { return e->nemb_on; },
-                            [&](flowgnn_engine* e, size_t i) { return flowgnn_get_node_embeddings(e, out_host + first[i] * (size_t)flowgnn_embedding_dim(e->model_id)); });
+                            [&](flowgnn_engine* e, size_t i) { return flowgnn_get_node_embeddings(e, out_host + first[i] * (size_t)flowgnn_emb_dim(e)); });
 }
 
 // [N_tot][NUM_TASK] in job order, likewise

@@ -2,7 +2,7 @@
 // OpenCL host (GIN/src/host.cc): load the model's .bin weights, read a graph pack in the reference's on-disk
 // layout, run the whole dataset as ONE batched launch NUM_TRIALS times, write HLS_output.txt.
 //
-//   host <MODEL> [--graphs DIR] [--weights DIR] [--num-graphs N] [--trials T] [--out FILE] [--node-logits FILE] [--attention FILE [--attention-layers MASK]] [--device D | --devices D0,D1,..] [--option key=value] [--numeric f32|q6.10|f16] [--eps] [--ogb-vn] [--eig DIR | --compute-eig] [XCLBIN]
+//   host <MODEL> [--graphs DIR] [--weights DIR] [--num-graphs N] [--trials T] [--out FILE] [--node-logits FILE] [--attention FILE [--attention-layers MASK]] [--device D | --devices D0,D1,..] [--option key=value] [--numeric f32|q6.10|f16] [--eps] [--ogb-vn] [--emb-dim 100|300] [--eig DIR | --compute-eig] [XCLBIN]
 //
 //   MODEL        GIN | GIN-VN | GCN | GAT | PNA | DGN
 //   --graphs     directory holding graph_info/ and graph_bin/      (default ../graphs, host.cc:14-15)
@@ -19,6 +19,8 @@
 //   --ogb-vn     GIN: read gin_ep1_virtualnode_dim100.bin (161 300 LE float32: vn_embedding, w1, b1, w2, b2) from the weights directory and
 //                run OGB's virtual node (flowgnn_set_ogb_virtual_node) -- an exported gin-virtual checkpoint; usually together with --eps
 //                GCN: the same from gcn_ep1_virtualnode_dim100.bin (flowgnn_set_gcn_virtual_node) -- an exported gcn-virtual checkpoint
+//   --emb-dim    GIN: 300 = OGB's default width (flowgnn_set_emb_dim): the weights directory's dim300 files are read (with --eps,
+//                gin_ep1_eps_dim300.bin); 100 (default) = the reference's width
 //   --eig        DGN: directory holding the eigenvector text files g%d.txt                 (default eig, DGN/src/host_load.cc:178)
 //   --compute-eig DGN: compute node_eigen from the graphs on the GPU (flowgnn_laplacian_eigen, on the first engine) and read no --eig DIR
 //   XCLBIN       accepted and ignored, so `./host <xclbin>`-style command lines keep working
@@ -86,7 +88,7 @@ static bool read_eig_txt(const std::string& path, std::vector<float>& eig, size_
 int main(int argc, char** argv) {
     if (argc < 2) {
         fprintf(stderr, "Usage: %s <GIN|GIN-VN|GCN|GAT|PNA|DGN> [--graphs DIR] [--weights DIR] [--num-graphs N] [--trials T] "
-                        "[--out FILE] [--embeddings FILE] [--node-embeddings FILE] [--node-logits FILE] [--attention FILE [--attention-layers MASK]] [--device D | --devices D0,D1,..] [--option key=value] [--numeric f32|q6.10|f16] [--pooling mean|sum|max] [--eps] [--ogb-vn] [--num-tasks T] [--eig DIR | --compute-eig] [XCLBIN File]\n", argv[0]);
+                        "[--out FILE] [--embeddings FILE] [--node-embeddings FILE] [--node-logits FILE] [--attention FILE [--attention-layers MASK]] [--device D | --devices D0,D1,..] [--option key=value] [--numeric f32|q6.10|f16] [--pooling mean|sum|max] [--eps] [--ogb-vn] [--emb-dim 100|300] [--num-tasks T] [--eig DIR | --compute-eig] [XCLBIN File]\n", argv[0]);
         return EXIT_FAILURE;
     }
     const std::string model = argv[1];
@@ -95,7 +97,7 @@ int main(int argc, char** argv) {
     std::string graphs = "../graphs", wdir = ".", out_path = "HLS_output.txt", eig_dir = "eig", emb_path, nemb_path, nlog_path, attn_path;
     long num_graphs = -1;
     int attn_mask = 16;
-    int trials = 25, numeric = FLOWGNN_NUMERIC_F32, num_tasks = 1, pooling = FLOWGNN_POOL_MEAN;
+    int trials = 25, numeric = FLOWGNN_NUMERIC_F32, num_tasks = 1, pooling = FLOWGNN_POOL_MEAN, emb_dim = FLOWGNN_EMB_DIM_REFERENCE;
     bool use_eps = false, use_ogb_vn = false, compute_eig = false;
     std::vector<int> devices;
     std::vector<std::pair<std::string, double>> options;
@@ -132,6 +134,7 @@ int main(int argc, char** argv) {
             options.emplace_back(kv.substr(0, eq), atof(kv.c_str() + eq + 1));
         }
         else if (a == "--num-tasks") num_tasks = atoi(next("--num-tasks"));  // NUM_TASK of the readout (GIN/src/dcl.h:25), GIN / GIN-VN / GCN
+        else if (a == "--emb-dim") emb_dim = atoi(next("--emb-dim"));  // GIN: 300 = OGB's default width (flowgnn_set_emb_dim), the dim300 files of the weights directory
         else if (a == "--numeric") {
             const std::string m = next("--numeric");
             numeric = m == "q6.10" ? FLOWGNN_NUMERIC_Q6_10 : m == "f16" ? FLOWGNN_NUMERIC_F16 : FLOWGNN_NUMERIC_F32;
@@ -163,6 +166,10 @@ int main(int argc, char** argv) {
         rc = flowgnn_group_set_num_tasks(eng, num_tasks);
         if (rc) { fprintf(stderr, "--num-tasks %d: %d %s\n", num_tasks, rc, flowgnn_group_last_error(eng)); return EXIT_FAILURE; }
     }
+    if (emb_dim != FLOWGNN_EMB_DIM_REFERENCE) {
+        rc = flowgnn_group_set_emb_dim(eng, emb_dim);
+        if (rc) { fprintf(stderr, "--emb-dim %d: %d %s\n", emb_dim, rc, flowgnn_group_last_error(eng)); return EXIT_FAILURE; }
+    }
     rc = flowgnn_group_load_weights_dir(eng, wdir.c_str());
     if (rc) { fprintf(stderr, "loading weights failed: %d %s\n", rc, flowgnn_group_last_error(eng)); return EXIT_FAILURE; }
     if (numeric != FLOWGNN_NUMERIC_F32) {  // the reference's ap_fixed<16,6> bit patterns, or f16 MLP operands (GIN / GIN-VN)
@@ -175,7 +182,7 @@ int main(int argc, char** argv) {
     }
     if (use_eps) {
         std::vector<float> eps(5);
-        const std::string path = wdir + "/gin_ep1_eps_dim100.bin";
+        const std::string path = wdir + "/gin_ep1_eps_dim" + std::to_string(emb_dim) + ".bin";
         if (!read_exact(path, eps, 0, 5)) { fprintf(stderr, "--eps: cannot read five floats from %s\n", path.c_str()); return EXIT_FAILURE; }
         rc = flowgnn_group_set_gin_eps(eng, eps.data());
         if (rc) { fprintf(stderr, "--eps: %d %s\n", rc, flowgnn_group_last_error(eng)); return EXIT_FAILURE; }
@@ -274,7 +281,7 @@ int main(int argc, char** argv) {
     fclose(o);
     if (!emb_path.empty()) {
         // one more run with embeddings on, behind the timed ones: the figures and the logits above are those of a run without the flag
-        const int dim = flowgnn_embedding_dim(mid);
+        const int dim = flowgnn_emb_dim(flowgnn_group_engine(eng, 0));
         std::vector<float> emb((size_t)num_graphs * dim);
         rc = flowgnn_group_set_embeddings(eng, 1);
         if (!rc) rc = flowgnn_group_run(eng);
@@ -288,7 +295,7 @@ int main(int argc, char** argv) {
     }
     if (!nemb_path.empty()) {
         // likewise one more run, with node embeddings on (and graph embeddings off again)
-        const int dim = flowgnn_embedding_dim(mid);
+        const int dim = flowgnn_emb_dim(flowgnn_group_engine(eng, 0));
         const size_t n_tot = N;
         std::vector<float> rows(n_tot * dim);
         rc = flowgnn_group_set_embeddings(eng, 0);

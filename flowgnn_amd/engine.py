@@ -173,11 +173,12 @@ class Engine:
     def load_weights_dir(self, directory: str, eps: bool = False, virtual_node: bool = False):
         """eps=True (GIN, GIN-VN): also read the directory's eps file and apply it (set_gin_eps); virtual_node=True: also read
         gin_ep1_virtualnode_dim100.bin and apply it (GIN: set_ogb_virtual_node), or gcn_ep1_virtualnode_dim100.bin on a GCN engine
-        (set_gcn_virtual_node).  The C call itself does neither."""
+        (set_gcn_virtual_node).  The C call itself does neither.  A GIN engine at width 300 (set_emb_dim) reads the dim300 set, its eps
+        file included."""
         self._check(self.lib.flowgnn_load_weights_dir(self._h, directory.encode()), "flowgnn_load_weights_dir")
         if eps:
             from .weights import load_gin_eps
-            self.set_gin_eps(load_gin_eps(directory))
+            self.set_gin_eps(load_gin_eps(directory, emb_dim=self.emb_dim if self.model == "GIN" else 100))
         if virtual_node and self.model == "GCN":
             from .weights import load_gcn_virtual_node
             self.set_gcn_virtual_node(load_gcn_virtual_node(directory))
@@ -333,11 +334,11 @@ class Engine:
         out = torch.empty(G * self.num_tasks, dtype=torch.float32, device=dev)  # (before the engine's stream waits for torch's)
         emb = None
         if return_embeddings:
-            emb = torch.empty((G, embedding_dim(self.model)), dtype=torch.float32, device=dev)
+            emb = torch.empty((G, self.emb_dim), dtype=torch.float32, device=dev)
             self.set_embeddings(True)
         rows = None
         if return_node_embeddings:
-            rows = torch.empty((int(x.shape[0]), embedding_dim(self.model)), dtype=torch.float32, device=dev)
+            rows = torch.empty((int(x.shape[0]), self.emb_dim), dtype=torch.float32, device=dev)
             self.set_node_embeddings(True)
         terms = None
         if return_node_logits:
@@ -439,6 +440,16 @@ class Engine:
         self._check(self.lib.flowgnn_set_num_tasks(self._h, int(num_tasks)), "flowgnn_set_num_tasks")
         self.num_tasks = int(num_tasks)
 
+    def set_emb_dim(self, emb_dim: int):
+        """GIN's width (flowgnn.h: flowgnn_set_emb_dim): 100, the reference's, or 300, OGB's default; set before weights and batch
+        (both have to be set again afterwards)."""
+        self._check(self.lib.flowgnn_set_emb_dim(self._h, int(emb_dim)), "flowgnn_set_emb_dim")
+
+    @property
+    def emb_dim(self) -> int:
+        """The engine's width: what its embeddings, node embeddings and get_h rows are wide (flowgnn.h: flowgnn_emb_dim)."""
+        return int(self.lib.flowgnn_emb_dim(self._h))
+
     def _device_ptrs(self, fn: str, count: int = 1):
         """`count` device addresses (0 = NULL) out of the C function `fn`(engine, void**, ...)."""
         ps = [C.c_void_p() for _ in range(count)]
@@ -486,7 +497,7 @@ class Engine:
 
     def embeddings(self) -> np.ndarray:
         """[G][embedding_dim(model)] of the last run (synchronises); FLOWGNN_ERR_STATE if that run had embeddings off."""
-        out = np.empty((self.num_graphs, embedding_dim(self.model)), dtype=np.float32)
+        out = np.empty((self.num_graphs, self.emb_dim), dtype=np.float32)
         self._check(self.lib.flowgnn_get_embeddings(self._h, _pf(out)), "flowgnn_get_embeddings")
         return out
 
@@ -504,7 +515,7 @@ class Engine:
 
     def node_embeddings(self) -> np.ndarray:
         """[N][embedding_dim(model)] of the last run (synchronises); FLOWGNN_ERR_STATE if that run had node embeddings off."""
-        out = np.empty((self.total_nodes, embedding_dim(self.model)), dtype=np.float32)
+        out = np.empty((self.total_nodes, self.emb_dim), dtype=np.float32)
         self._check(self.lib.flowgnn_get_node_embeddings(self._h, _pf(out)), "flowgnn_get_node_embeddings")
         return out
 
@@ -714,6 +725,15 @@ class EngineGroup:
         self._check(self.lib.flowgnn_group_set_num_tasks(self._h, int(num_tasks)), "flowgnn_group_set_num_tasks")
         self.num_tasks = int(num_tasks)
 
+    def set_emb_dim(self, emb_dim: int):
+        """GIN's width on every member (flowgnn.h: flowgnn_group_set_emb_dim); weights and batch have to be set again afterwards."""
+        self._check(self.lib.flowgnn_group_set_emb_dim(self._h, int(emb_dim)), "flowgnn_group_set_emb_dim")
+
+    @property
+    def emb_dim(self) -> int:
+        """The members' width (they are one model with one setting: the first member answers)."""
+        return int(self.lib.flowgnn_emb_dim(self.lib.flowgnn_group_engine(self._h, 0)))
+
     def set_numeric_mode(self, mode: str = "f32"):
         self._check(self.lib.flowgnn_group_set_numeric_mode(self._h, NUMERIC_MODES[mode]), "flowgnn_group_set_numeric_mode")
 
@@ -766,7 +786,7 @@ class EngineGroup:
 
     def embeddings(self) -> np.ndarray:
         """[G][embedding_dim(model)] of the last run, in job order (flowgnn.h: flowgnn_group_get_embeddings)."""
-        out = np.empty((self.num_graphs, embedding_dim(self.model)), dtype=np.float32)
+        out = np.empty((self.num_graphs, self.emb_dim), dtype=np.float32)
         self._check(self.lib.flowgnn_group_get_embeddings(self._h, _pf(out)), "flowgnn_group_get_embeddings")
         return out
 
@@ -775,7 +795,7 @@ class EngineGroup:
 
     def node_embeddings(self) -> np.ndarray:
         """[N][embedding_dim(model)] of the last run, in job order (flowgnn.h: flowgnn_group_get_node_embeddings)."""
-        out = np.empty((self.total_nodes, embedding_dim(self.model)), dtype=np.float32)
+        out = np.empty((self.total_nodes, self.emb_dim), dtype=np.float32)
         self._check(self.lib.flowgnn_group_get_node_embeddings(self._h, _pf(out)), "flowgnn_group_get_node_embeddings")
         return out
 

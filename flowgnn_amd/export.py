@@ -124,8 +124,18 @@ def gin_weights_from_ogb_state_dict(sd: Mapping, num_layers: int = 5, eps_tol: f
     keep_eps says that the engine will apply it (gin_eps_from_ogb_state_dict + flowgnn_set_gin_eps).
     A gin-virtual state_dict (it has `gnn_node.virtualnode_embedding.weight`) is refused -- the weight set alone is a model nobody
     trained -- unless virtual_node says that the engine will run the virtual node too (gin_virtual_node_from_ogb_state_dict +
-    flowgnn_set_ogb_virtual_node)."""
+    flowgnn_set_ogb_virtual_node).
+    The width is read off `atom_embedding_list.0.weight`: 100 (the reference's) or 300 (OGB's default; the tensors are then the
+    300-wide set of flowgnn_set_emb_dim(FLOWGNN_EMB_DIM_OGB)).  A 300-wide gin-virtual state_dict is refused even with virtual_node:
+    the engine's virtual node has 100-wide tensors."""
     p = "gnn_node"
+    width = int(_get(sd, f"{p}.atom_encoder.atom_embedding_list.0.weight").shape[-1])
+    if width not in _weights.GIN_EMB_DIMS:
+        raise ExportError(f"atom_embedding_list.0.weight is {width} wide: the engine runs GIN at emb_dim 100 (the reference's width) "
+                          f"and at emb_dim 300 (OGB's default), no other")
+    if VN_KEY in sd and width != 100:
+        raise ExportError(f"the state_dict has '{VN_KEY}' and is {width} wide: the engine's virtual node (flowgnn_set_ogb_virtual_node) "
+                          f"has 100-wide tensors, so a {width}-wide gin-virtual model cannot run, with or without virtual_node=True")
     if VN_KEY in sd and not virtual_node:
         raise ExportError(f"the state_dict has '{VN_KEY}': it is OGB's gin-virtual, and these weights without its virtual node are "
                           f"a model nobody trained; pass virtual_node=True and give the engine gin_virtual_node_from_ogb_state_dict(sd) "
@@ -155,7 +165,7 @@ def gin_weights_from_ogb_state_dict(sd: Mapping, num_layers: int = 5, eps_tol: f
         raise ExportError(f"graph_pred_linear has {pw.shape[0]} tasks; the reference is built with NUM_TASK = 1 (GIN/src/dcl.h:25): "
                           f"pass multi_task=True for an engine with flowgnn_set_num_tasks({pw.shape[0]})")
     out["graph_pred_weights"], out["graph_pred_bias"] = pw, pb
-    return _checked(out, _weights.GIN_FILES, lambda k, v: _weights._task_shape(k, v[1], pw.shape[0]))
+    return _checked(out, _weights.gin_files(width), lambda k, v: _weights._task_shape(k, v[1], pw.shape[0]))
 
 
 def gcn_weights_from_ogb_state_dict(sd: Mapping, num_layers: int = 5, multi_task: bool = False,
@@ -217,7 +227,8 @@ def export_weights(model: str, sd: Mapping, directory: str, multi_task: bool = F
     """Write the `.bin` file(s) `host` / `flowgnn_load_weights_dir` read for `model` ('GIN', 'GIN-VN' or 'GCN').
     multi_task: keep all rows of the prediction head (the engine then needs flowgnn_set_num_tasks(rows) before loading).
     keep_eps (GIN, GIN-VN): a trained eps is not refused; the eps file holds the trained values, for `host --eps` /
-    Engine.load_weights_dir(dir, eps=True) to apply (flowgnn_set_gin_eps).
+    Engine.load_weights_dir(dir, eps=True) to apply (flowgnn_set_gin_eps).  A 300-wide GIN state_dict (OGB's default emb_dim) gives the
+    dim300 file set, for an engine with flowgnn_set_emb_dim(300) / `host GIN --emb-dim 300`.
     virtual_node (GIN): the state_dict is OGB's gin-virtual; its virtual node goes into gin_ep1_virtualnode_dim100.bin beside the
     others, for `host GIN --ogb-vn` / Engine.load_weights_dir(dir, virtual_node=True) to apply (flowgnn_set_ogb_virtual_node).
     virtual_node (GCN): likewise OGB's gcn-virtual, into gcn_ep1_virtualnode_dim100.bin (flowgnn_set_gcn_virtual_node)."""

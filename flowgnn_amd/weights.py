@@ -47,27 +47,50 @@ def _task_shape(k: str, shp, num_tasks: int):
     return tuple(shp)
 
 
-def load_gin_weights(directory: str, num_tasks: int = 1) -> Dict[str, np.ndarray]:
-    return OrderedDict((k, _read(os.path.join(directory, f), _task_shape(k, shp, num_tasks))) for k, (f, shp) in GIN_FILES.items())
+GIN_EMB_DIMS = (100, 300)  # the reference's width, and OGB's default (flowgnn_set_emb_dim: FLOWGNN_EMB_DIM_REFERENCE / _OGB)
+
+
+def gin_files(emb_dim: int = 100):
+    """GIN_FILES at width emb_dim: the reference's names with dim<emb_dim> in place of dim100, the shapes with 100 -> D, 200 -> 2 D."""
+    d = int(emb_dim)
+    if d not in GIN_EMB_DIMS:
+        raise ValueError(f"GIN: emb_dim {emb_dim} is not one of {GIN_EMB_DIMS}")
+    grow = {100: d, 200: 2 * d}
+    return OrderedDict((k, (f.replace("dim100", f"dim{d}"), tuple(grow.get(n, n) for n in shp))) for k, (f, shp) in GIN_FILES.items())
+
+
+def gin_emb_dim_of(w) -> int:
+    """The width of a GIN weight set: the row length of its atom-embedding table."""
+    return int(np.asarray(w["node_embedding_weight"]).shape[-1])
+
+
+def load_gin_weights(directory: str, num_tasks: int = 1, emb_dim: int = 100) -> Dict[str, np.ndarray]:
+    return OrderedDict((k, _read(os.path.join(directory, f), _task_shape(k, shp, num_tasks))) for k, (f, shp) in gin_files(emb_dim).items())
 
 
 GIN_EPS_FILE = "gin_ep1_eps_dim100.bin"  # five LE float32, one per layer: read by the reference host and never used
 
 
-def load_gin_eps(directory: str) -> np.ndarray:
+def gin_eps_file(emb_dim: int = 100) -> str:
+    return GIN_EPS_FILE.replace("dim100", f"dim{int(emb_dim)}")
+
+
+def load_gin_eps(directory: str, emb_dim: int = 100) -> np.ndarray:
     """The five eps values of a GIN / GIN-VN weights directory, float32[5] (for Engine.set_gin_eps: flowgnn_set_gin_eps)."""
-    return _read(os.path.join(directory, GIN_EPS_FILE), (5,))
+    return _read(os.path.join(directory, gin_eps_file(emb_dim)), (5,))
 
 
-def save_gin_weights(w: Dict[str, np.ndarray], directory: str, eps=None) -> None:
+def save_gin_weights(w: Dict[str, np.ndarray], directory: str, eps=None, emb_dim=None) -> None:
     """eps: the five trained values for the eps file (None: zeros, what the reference's own sets carry).  Nothing applies the file
-    unless asked to: `host --eps`, Engine.load_weights_dir(dir, eps=True)."""
+    unless asked to: `host --eps`, Engine.load_weights_dir(dir, eps=True).  emb_dim: None = the arrays' own width (which names the
+    files: dim100 / dim300)."""
     os.makedirs(directory, exist_ok=True)
     tasks = int(np.asarray(w["graph_pred_bias"]).size)
-    for k, (f, shp) in GIN_FILES.items():
+    d = gin_emb_dim_of(w) if emb_dim is None else int(emb_dim)
+    for k, (f, shp) in gin_files(d).items():
         np.asarray(w[k], dtype="<f4").reshape(_task_shape(k, shp, tasks)).tofile(os.path.join(directory, f))
     e = np.zeros(5, dtype="<f4") if eps is None else np.asarray(eps, dtype="<f4").reshape(5)
-    e.tofile(os.path.join(directory, GIN_EPS_FILE))  # (zeros: read by the reference, never used)
+    e.tofile(os.path.join(directory, gin_eps_file(d)))  # (zeros: read by the reference, never used)
 
 
 # OGB's virtual node for GIN (flowgnn.h: flowgnn_set_ogb_virtual_node): one file beside the GIN set, the five tensors in the order of the
@@ -144,9 +167,11 @@ def synth_gcn_virtual_node(seed: int = 13, scale: float = 1.0) -> Dict[str, np.n
     return synth_gin_virtual_node(seed=seed, scale=scale)
 
 
-def synth_gin_weights(seed: int = 7, num_tasks: int = 1) -> Dict[str, np.ndarray]:
+def synth_gin_weights(seed: int = 7, num_tasks: int = 1, emb_dim: int = 100) -> Dict[str, np.ndarray]:
     """Random weights with the measured scales of the shipped GIN set:
-    W1 s=0.075, b1 s=0.91, W2 s=0.053, b2 s=0.49, node/edge emb s=0.11/0.14, pred s=0.15."""
+    W1 s=0.075, b1 s=0.91, W2 s=0.053, b2 s=0.49, node/edge emb s=0.11/0.14, pred s=0.15.
+    emb_dim 300: the same scales at OGB's default width, the matrices' scales shrunk by sqrt(100 / emb_dim) so that the activations
+    keep their size (the draws, and at 100 the values, are what they always were)."""
     rng = np.random.default_rng(seed)
     scale = {
         "node_embedding_weight": 0.11, "edge_embedding_weight": 0.14,
@@ -154,8 +179,11 @@ def synth_gin_weights(seed: int = 7, num_tasks: int = 1) -> Dict[str, np.ndarray
         "node_mlp_2_weights": 0.053, "node_mlp_2_bias": 0.49,
         "graph_pred_weights": 0.15, "graph_pred_bias": 0.12,
     }
+    if emb_dim != 100:
+        for k in ("node_mlp_1_weights", "node_mlp_2_weights", "graph_pred_weights"):
+            scale[k] = scale[k] * float(np.sqrt(100.0 / emb_dim))
     return OrderedDict((k, (rng.standard_normal(_task_shape(k, shp, num_tasks)) * scale[k]).astype(np.float32))
-                       for k, (_, shp) in GIN_FILES.items())
+                       for k, (_, shp) in gin_files(emb_dim).items())
 
 
 # --------------------------------------------------------------------------- GCN

@@ -504,6 +504,26 @@ int flowgnn_set_num_tasks(flowgnn_engine* e, int num_tasks);
 int flowgnn_num_tasks(const flowgnn_engine* e);
 
 /*
+ * EMB_DIM of GIN as a run-time choice between two widths (a compile-time constant in the reference, GIN/src/dcl.h:19, 100 as
+ * shipped; OGB's own training script defaults to --emb_dim 300, and the GIN results quoted for ogbg-molhiv / ogbg-molpcba are
+ * 300-wide models).  At FLOWGNN_EMB_DIM_OGB the eight GIN tensors are node_emb [173][300], edge_emb [5][13][300], w1 [5][600][300],
+ * b1 [5][600], w2 [5][300][600], b2 [5][300], pred_w [NUM_TASK][300], pred_b [NUM_TASK]; flowgnn_load_weights_dir reads the
+ * reference's file names with dim300 in place of dim100; embeddings, node embeddings and flowgnn_get_h are 300 wide.  The width runs
+ * on kernels of its own, one launch per layer: split-f16 MFMA products with the fp32 re-run of flowgnn_exact_reruns.
+ * Call it before setting weights and batch (both must be set again afterwards: weights set before are dropped); drops a recorded
+ * launch sequence; setting the width the engine has is a no-op.  FLOWGNN_MODEL_GIN only: every other model, GIN-VN included, returns
+ * FLOWGNN_ERR_UNSUPPORTED.  At 300, FLOWGNN_NUMERIC_Q6_10 / FLOWGNN_NUMERIC_F16, flowgnn_set_ogb_virtual_node (its tensors are 100
+ * wide) and flowgnn_run_aggregation_only / flowgnn_get_aggregate return FLOWGNN_ERR_UNSUPPORTED, and so does this call while one
+ * of the first three is on.  A width other than the two: FLOWGNN_ERR_ARG.  flowgnn_embedding_dim(model) keeps answering for the
+ * model's default width; flowgnn_emb_dim(e) is the engine's (-1 for a null handle).  The <M>_compute_graphs entry points have no
+ * 300-wide form.
+ */
+#define FLOWGNN_EMB_DIM_REFERENCE 100
+#define FLOWGNN_EMB_DIM_OGB       300
+int flowgnn_set_emb_dim(flowgnn_engine* e, int emb_dim);   /* 100 (default) or 300 */
+int flowgnn_emb_dim(const flowgnn_engine* e);              /* -1 for a null handle */
+
+/*
  * Numeric mode of the engine.  FLOWGNN_NUMERIC_F32 (default): fp32 storage and accumulation.
  * FLOWGNN_NUMERIC_Q6_10: every value is the bit pattern of the reference's own number format -- ap_fixed<16,6> for GIN,
  * GIN-VN, GCN, GAT and PNA (GIN/src/dcl.h:58-59: 10 fractional bits, truncation toward -inf, wrap on overflow), ap_fixed<16,3>
@@ -741,6 +761,7 @@ int flowgnn_group_set_weights(flowgnn_group* g, int count, const float* const* t
 int flowgnn_group_load_weights_dir(flowgnn_group* g, const char* dir);
 int flowgnn_group_set_option(flowgnn_group* g, const char* key, double value);
 int flowgnn_group_set_num_tasks(flowgnn_group* g, int num_tasks);
+int flowgnn_group_set_emb_dim(flowgnn_group* g, int emb_dim);
 int flowgnn_group_set_numeric_mode(flowgnn_group* g, int mode);
 int flowgnn_group_set_pooling(flowgnn_group* g, int mode);
 int flowgnn_group_set_gin_eps(flowgnn_group* g, const float* eps);
