@@ -1324,10 +1324,11 @@ int flowgnn_set_emb_dim(flowgnn_engine* e, int emb_dim) {
             e->err = "flowgnn_set_emb_dim: a numeric mode other than FLOWGNN_NUMERIC_F32 is on (flowgnn_set_numeric_mode), and width 300 has neither fixed-point nor f16 kernels";
             return FLOWGNN_ERR_UNSUPPORTED;
         }
-        if (e->ogb_vn_on) {
-            e->err = "flowgnn_set_emb_dim: OGB's virtual node is on (flowgnn_set_ogb_virtual_node), and its tensors are 100 wide";
-            return FLOWGNN_ERR_UNSUPPORTED;
-        }
+    }
+    if (e->ogb_vn_on) {  // (either direction: the tensors belong to a width -- turn it off, change the width, set it again)
+        e->err = "flowgnn_set_emb_dim: OGB's virtual node is on (flowgnn_set_ogb_virtual_node / flowgnn_set_ogb_virtual_node_dim), and its tensors are " +
+                 std::to_string(e->emb_dim) + " wide";
+        return FLOWGNN_ERR_UNSUPPORTED;
     }
     ENGINE_TRY(e, begin_change(e));
     Model* m = emb_dim == FLOWGNN_EMB_DIM_REFERENCE ? make_gin_model(false) : make_gin_wide_model(emb_dim);
@@ -1450,12 +1451,15 @@ int flowgnn_gin_eps(const flowgnn_engine* e, float* eps_out) {
 
 // flowgnn_set_ogb_virtual_node (GIN) and flowgnn_set_gcn_virtual_node (GCN): the same five tensors, the same checks, the same device
 // form (gin_ogbvn.h) and the same engine state -- an engine is one model, so one of the two calls is refused on it.  `fn`: the caller.
+// `dim`: the tensors' width D (hidden width 2 D) -- 100 in the two calls without a width argument; 300 (flowgnn_set_ogb_virtual_node_dim)
+// packs into gin_wide.hip's own device form instead.
 static int set_virtual_node(flowgnn_engine* e, const char* fn, const float* vn_embedding, const float* w1, const float* b1, const float* w2,
-                            const float* b2) {
+                            const float* b2, int dim = FLOWGNN_EMB_DIM_REFERENCE) {
     const std::string who = std::string(fn) + ": ";
     const float* const t[5] = {vn_embedding, w1, b1, w2, b2};
-    const size_t count[5] = {100, (size_t)FLOWGNN_OGB_VN_LAYERS * FLOWGNN_OGB_VN_HIDDEN * 100, (size_t)FLOWGNN_OGB_VN_LAYERS * FLOWGNN_OGB_VN_HIDDEN,
-                             (size_t)FLOWGNN_OGB_VN_LAYERS * 100 * FLOWGNN_OGB_VN_HIDDEN, (size_t)FLOWGNN_OGB_VN_LAYERS * 100};
+    const size_t D = (size_t)dim, H = 2 * D;
+    const size_t count[5] = {D, (size_t)FLOWGNN_OGB_VN_LAYERS * H * D, (size_t)FLOWGNN_OGB_VN_LAYERS * H, (size_t)FLOWGNN_OGB_VN_LAYERS * D * H,
+                             (size_t)FLOWGNN_OGB_VN_LAYERS * D};
     int given = 0;
     for (int i = 0; i < 5; i++) given += t[i] != nullptr;
     if (given != 0 && given != 5) {
@@ -1475,11 +1479,21 @@ static int set_virtual_node(flowgnn_engine* e, const char* fn, const float* vn_e
             e->err = who + "the fixed-point arithmetic (FLOWGNN_NUMERIC_Q6_10) is the reference's, which has no such model";
             return FLOWGNN_ERR_UNSUPPORTED;
         }
+        // (a width other than 100 needs a model object of that width with a device form of its own; refused before anything changes)
+        if (dim != FLOWGNN_EMB_DIM_REFERENCE && (e->model->emb_dim() != dim || e->model->ogb_vn_blob_bytes() == 0)) {
+            e->err = who + "this model has no such kernel";
+            return FLOWGNN_ERR_UNSUPPORTED;
+        }
     }
     ENGINE_TRY(e, begin_change(e));  // (an idle stream: a run in flight may still read the tensors this call replaces)
-    if (on) {
+    if (on && dim == FLOWGNN_EMB_DIM_REFERENCE) {
         std::vector<float> packed(fg::GIN_OGBVN_FLOATS);
         fg::gin_ogbvn_pack(vn_embedding, w1, b1, w2, b2, packed.data());
+        EHIP_TRY(e, e->ogb_vn.reserve(sizeof(float) * packed.size(), false));
+        EHIP_TRY(e, hipMemcpy(e->ogb_vn.p, packed.data(), sizeof(float) * packed.size(), hipMemcpyHostToDevice));
+    } else if (on) {
+        std::vector<float> packed(e->model->ogb_vn_blob_bytes() / sizeof(float));  // (floats: the parts are read as float4 pieces)
+        e->model->ogb_vn_pack(vn_embedding, w1, b1, w2, b2, packed.data());
         EHIP_TRY(e, e->ogb_vn.reserve(sizeof(float) * packed.size(), false));
         EHIP_TRY(e, hipMemcpy(e->ogb_vn.p, packed.data(), sizeof(float) * packed.size(), hipMemcpyHostToDevice));
     }
@@ -1501,10 +1515,37 @@ int flowgnn_set_ogb_virtual_node(flowgnn_engine* e, const float* vn_embedding, c
         return FLOWGNN_ERR_UNSUPPORTED;
     }
     if (e->emb_dim != FLOWGNN_EMB_DIM_REFERENCE && (vn_embedding || w1 || b1 || w2 || b2)) {
-        e->err = "flowgnn_set_ogb_virtual_node: the engine's width is 300 (flowgnn_set_emb_dim), and the virtual node's tensors are 100 wide";
+        e->err = "flowgnn_set_ogb_virtual_node: the engine's width is 300 (flowgnn_set_emb_dim), and the virtual node's tensors are 100 wide "
+                 "in this call; 300-wide tensors go through flowgnn_set_ogb_virtual_node_dim";
         return FLOWGNN_ERR_UNSUPPORTED;
     }
     return set_virtual_node(e, "flowgnn_set_ogb_virtual_node", vn_embedding, w1, b1, w2, b2);
+}
+
+// The call that carries the width.  emb_dim 100 IS the call above (the same state, kernels and bits); 300 is gin_wide.hip's virtual
+// node.  All five NULL: off, whatever the engine's width.
+int flowgnn_set_ogb_virtual_node_dim(flowgnn_engine* e, int emb_dim, const float* vn_embedding, const float* w1, const float* b1, const float* w2,
+                                     const float* b2) {
+    if (!e) return FLOWGNN_ERR_ARG;
+    if (emb_dim != FLOWGNN_EMB_DIM_REFERENCE && emb_dim != FLOWGNN_EMB_DIM_OGB) {
+        e->err = "flowgnn_set_ogb_virtual_node_dim: emb_dim is " + std::to_string(emb_dim) +
+                 "; the widths are FLOWGNN_EMB_DIM_REFERENCE (100) and FLOWGNN_EMB_DIM_OGB (300)";
+        return FLOWGNN_ERR_ARG;
+    }
+    if (e->model_id != FLOWGNN_MODEL_GIN) {
+        e->err = "flowgnn_set_ogb_virtual_node_dim: OGB's virtual node exists for GIN only (GIN-VN is the reference's augmentation, a different model)";
+        if (e->model_id == FLOWGNN_MODEL_GCN) e->err += "; GCN has a call of its own, flowgnn_set_gcn_virtual_node";
+        return FLOWGNN_ERR_UNSUPPORTED;
+    }
+    const bool any = vn_embedding || w1 || b1 || w2 || b2;
+    if (any && emb_dim != e->emb_dim) {
+        e->err = "flowgnn_set_ogb_virtual_node_dim: the tensors are " + std::to_string(emb_dim) + " wide and the engine's width is " +
+                 std::to_string(e->emb_dim) + " (flowgnn_set_emb_dim)";
+        return FLOWGNN_ERR_ARG;
+    }
+    if (!any || emb_dim == FLOWGNN_EMB_DIM_REFERENCE)  // off at any width (no tensor is read), or exactly the 100-wide call
+        return set_virtual_node(e, "flowgnn_set_ogb_virtual_node_dim", vn_embedding, w1, b1, w2, b2);
+    return set_virtual_node(e, "flowgnn_set_ogb_virtual_node_dim", vn_embedding, w1, b1, w2, b2, emb_dim);
 }
 
 int flowgnn_set_gcn_virtual_node(flowgnn_engine* e, const float* vn_embedding, const float* w1, const float* b1, const float* w2, const float* b2) {

@@ -14,6 +14,11 @@
 //   lane (j = lane & 15, g = lane >> 4); B operand of K-step ks, slot e (0..7): feature 16 (2 ks + (e >> 2)) + 4 g + (e & 3).
 // Operands beyond the f16 range raise *range_flag; the engine then repeats the pass with set_exact(true), which runs the fp32 form of
 // the layer (gw_aggregate_kernel + gw_dense_f32_kernel twice, plain FMAs, the same row order).
+//
+// OGB's virtual node at this width (flowgnn_set_ogb_virtual_node_dim): no launch rewrites the rows to add a
+// vector.  x_0 = h_0 + E is formed by the encoder's VN instance, x_{l+1} = relu(layer l) + vn_{l+1}[g(v)] in the epilogue of the layer
+// kernel's VN instance (vn_{l+1} depends on x_l alone, so it is complete before layer l is launched), t by gw_vn_pool_kernel (one read of
+// the rows) and the update MLP by the layer kernel's own MLP on G "rows" t (gw_vn_update_kernel: the body with the gather compiled out).
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -134,12 +139,20 @@ __device__ __forceinline__ void gw_step(const char* wb, int s, int lane, int g, 
 }
 
 // hout[v] = W2 relu(W1 a[v] + b1) + b2 (ReLU'd if relu_out), a[v] = fma(h[v], self_s, sum over v's in-edges, in CSR order)
-template <int D>
-__global__ __launch_bounds__(GW_WAVES * 64) void gw_layer_kernel(const float* __restrict__ h, float* __restrict__ hout,
-                                                                 const int* __restrict__ row_ptr, const int* __restrict__ src,
-                                                                 const uint8_t* __restrict__ ecode, const float* __restrict__ ecomb,
-                                                                 const uint8_t* __restrict__ wchunks, const float* __restrict__ tailp,
-                                                                 int n_tot, int relu_out, float self_s, int* __restrict__ range_flag) {
+// The body of the layer's three kernels (below); MODE is a compile-time constant in each, and GW_PLAIN compiles to what the one
+// kernel was before the other two existed.
+//   GW_PLAIN   the layer
+//   GW_VN      the layer, and OGB's virtual node of the NEXT layer added in the epilogue: hout[v] = relu(..) + vn_add[node_graph[v]],
+//              one fp32 add just before the store (section 4.17) -- the 16 rows of a tile may belong to 16 different graphs
+//   GW_UPDATE  the virtual node's update MLP: the "rows" are the per-graph sums t, nothing has in-edges (no gather, no edge table)
+enum { GW_PLAIN = 0, GW_VN = 1, GW_UPDATE = 2 };
+
+template <int D, int MODE>
+__device__ __forceinline__ void gw_layer_body(const float* __restrict__ h, float* __restrict__ hout, const int* __restrict__ row_ptr,
+                                              const int* __restrict__ src, const uint8_t* __restrict__ ecode, const float* __restrict__ ecomb,
+                                              const uint8_t* __restrict__ wchunks, const float* __restrict__ tailp, int n_tot, int relu_out,
+                                              float self_s, int* __restrict__ range_flag, const int* __restrict__ node_graph,
+                                              const float* __restrict__ vn_add) {
     using M = GwDims<D>;
     // two DISTINCT LDS objects, as in gin_layer_split_kernel: the DMA into one does not alias the reads of the other
     __shared__ __attribute__((aligned(16))) char s_a[M::CHUNK_BYTES];  // the combined edge table, then the odd chunks
@@ -151,10 +164,11 @@ __global__ __launch_bounds__(GW_WAVES * 64) void gw_layer_kernel(const float* __
     const bool valid = node0 < n_tot;
     const long long node = valid ? node0 : (long long)n_tot - 1;
 
-    int e_cur = row_ptr[node];
-    const int e_end = valid ? row_ptr[node + 1] : e_cur;
+    int e_cur = MODE == GW_UPDATE ? 0 : row_ptr[node];
+    const int e_end = MODE == GW_UPDATE ? 0 : (valid ? row_ptr[node + 1] : e_cur);
     gw_issue<D>(wchunks, s_b, M::PIECES, M::LAST_LANES, wave, lane);                                                  // chunk 0
-    gw_issue<D>(reinterpret_cast<const uint8_t*>(ecomb), s_a, M::ECOMB_PIECES, M::ECOMB_LAST_LANES, wave, lane);      // the edge table
+    if (MODE != GW_UPDATE)
+        gw_issue<D>(reinterpret_cast<const uint8_t*>(ecomb), s_a, M::ECOMB_PIECES, M::ECOMB_LAST_LANES, wave, lane);  // the edge table
     float bq[4 * M::Q];
 #pragma unroll
     for (int k = 0; k < 4 * M::Q; k++) bq[k] = 0.0f;
@@ -163,7 +177,7 @@ __global__ __launch_bounds__(GW_WAVES * 64) void gw_layer_kernel(const float* __
     const float* s_ecomb = reinterpret_cast<const float*>(s_a);
 
     // ---- gather: one in-edge per trip, in CSR order (a row's sum depends on the row alone); pieces at or beyond column D stay zero
-    while (__any(e_cur < e_end)) {
+    while (MODE != GW_UPDATE && __any(e_cur < e_end)) {
         if (e_cur < e_end) {
             const int u = src[e_cur];
             const int code = ecode[e_cur];
@@ -238,12 +252,18 @@ __global__ __launch_bounds__(GW_WAVES * 64) void gw_layer_kernel(const float* __
 
     if (valid) {
         float* row = hout + (size_t)node * D;
+        // (GW_VN: in_hi / in_lo are dead here; the lane's node decides the vector, lane by lane)
+        const float* vrow = MODE == GW_VN ? vn_add + (size_t)node_graph[node] * D : nullptr;
 #pragma unroll
         for (int t2 = 0; t2 < M::T2; t2++) {
             const int col = 16 * t2 + 4 * g;
             if (col < D) {
                 float4_t r = acc2[t2] * oscale;
                 if (relu_out) { r.x = gw_relu(r.x); r.y = gw_relu(r.y); r.z = gw_relu(r.z); r.w = gw_relu(r.w); }
+                if (MODE == GW_VN) {
+                    const float4 a = *reinterpret_cast<const float4*>(vrow + col);
+                    r.x += a.x; r.y += a.y; r.z += a.z; r.w += a.w;
+                }
                 *reinterpret_cast<float4*>(row + col) = make_float4(r.x, r.y, r.z, r.w);
             }
         }
@@ -251,6 +271,34 @@ __global__ __launch_bounds__(GW_WAVES * 64) void gw_layer_kernel(const float* __
     if (__any(!(vmax < 6.0e4f))) {
         if (lane == 0) atomicOr(range_flag, 1);
     }
+}
+
+template <int D>
+__global__ __launch_bounds__(GW_WAVES * 64) void gw_layer_kernel(const float* __restrict__ h, float* __restrict__ hout,
+                                                                 const int* __restrict__ row_ptr, const int* __restrict__ src,
+                                                                 const uint8_t* __restrict__ ecode, const float* __restrict__ ecomb,
+                                                                 const uint8_t* __restrict__ wchunks, const float* __restrict__ tailp,
+                                                                 int n_tot, int relu_out, float self_s, int* __restrict__ range_flag) {
+    gw_layer_body<D, GW_PLAIN>(h, hout, row_ptr, src, ecode, ecomb, wchunks, tailp, n_tot, relu_out, self_s, range_flag, nullptr, nullptr);
+}
+
+// the VN instance: x_{l+1}[v] = relu(layer l of x_l)[v] + vn_{l+1}[node_graph[v]] (always ReLU'd: layers 0..3)
+template <int D>
+__global__ __launch_bounds__(GW_WAVES * 64) void gw_layer_vn_kernel(const float* __restrict__ h, float* __restrict__ hout,
+                                                                    const int* __restrict__ row_ptr, const int* __restrict__ src,
+                                                                    const uint8_t* __restrict__ ecode, const float* __restrict__ ecomb,
+                                                                    const uint8_t* __restrict__ wchunks, const float* __restrict__ tailp,
+                                                                    int n_tot, float self_s, int* __restrict__ range_flag,
+                                                                    const int* __restrict__ node_graph, const float* __restrict__ vn_add) {
+    gw_layer_body<D, GW_VN>(h, hout, row_ptr, src, ecode, ecomb, wchunks, tailp, n_tot, 1, self_s, range_flag, node_graph, vn_add);
+}
+
+// the update instance: vn_next[g] = relu(W2 relu(W1 t[g] + b1) + b2) for num_graphs "rows" t; a = fma(t, 1, 0) = t exactly
+template <int D>
+__global__ __launch_bounds__(GW_WAVES * 64) void gw_vn_update_kernel(const float* __restrict__ t, float* __restrict__ vn_next,
+                                                                     const uint8_t* __restrict__ wchunks, const float* __restrict__ tailp,
+                                                                     int num_graphs, int* __restrict__ range_flag) {
+    gw_layer_body<D, GW_UPDATE>(t, vn_next, nullptr, nullptr, nullptr, nullptr, wchunks, tailp, num_graphs, 1, 1.0f, range_flag, nullptr, nullptr);
 }
 
 // ---------------------------------------------------------------- the exact (fp32) form of the layer: the same sums, plain FMAs
@@ -308,9 +356,10 @@ __global__ __launch_bounds__(256) void gw_dense_f32_kernel(const float* __restri
 // ---------------------------------------------------------------- atom encoder and pooling at this width
 // (atom_encoder_kernel<D> stages the 173-row table in LDS, and the readout kernels of device_common.h hold a row in half a wavefront:
 // neither fits 75 float4 pieces.)  One lane per (node, float4 piece), the table read through the caches; summation order k = 0..8.
-template <int D>
-__global__ __launch_bounds__(256) void gw_atom_encoder_kernel(const int* __restrict__ node_feature, const float* __restrict__ table,
-                                                              float* __restrict__ h, int n_tot, int* __restrict__ err) {
+// VN: x_0 = h_0 + E, E's piece added after the nine table rows -- the bits of a separate add (section 4.17)
+template <int D, bool VN>
+__device__ __forceinline__ void gw_atom_encoder_body(const int* __restrict__ node_feature, const float* __restrict__ table,
+                                                     float* __restrict__ h, int n_tot, int* __restrict__ err, const float* __restrict__ vn_e) {
     constexpr int C = D / 4;
     const long long items = (long long)n_tot * C;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < items; i += (long long)gridDim.x * 256) {
@@ -327,7 +376,76 @@ __global__ __launch_bounds__(256) void gw_atom_encoder_kernel(const int* __restr
             const float4 w = reinterpret_cast<const float4*>(table)[(size_t)(c_nd_off[k] + f) * C + c];
             s.x += w.x; s.y += w.y; s.z += w.z; s.w += w.w;
         }
+        if (VN) {
+            const float4 w = reinterpret_cast<const float4*>(vn_e)[c];
+            s.x += w.x; s.y += w.y; s.z += w.z; s.w += w.w;
+        }
         reinterpret_cast<float4*>(h)[i] = s;
+    }
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void gw_atom_encoder_kernel(const int* __restrict__ node_feature, const float* __restrict__ table,
+                                                              float* __restrict__ h, int n_tot, int* __restrict__ err) {
+    gw_atom_encoder_body<D, false>(node_feature, table, h, n_tot, err, nullptr);
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void gw_atom_encoder_vn_kernel(const int* __restrict__ node_feature, const float* __restrict__ table,
+                                                                 float* __restrict__ h, int n_tot, int* __restrict__ err,
+                                                                 const float* __restrict__ vn_e) {
+    gw_atom_encoder_body<D, true>(node_feature, table, h, n_tot, err, vn_e);
+}
+
+// ---------------------------------------------------------------- OGB's virtual node at this width (section 4.17)
+// t[g] = (the rows of graph g summed in node order, one chain per column as in gw_pool_rows_kernel) + vn[g]: one lane per (graph,
+// float4 piece), four rows in flight, the adds in node order -- the value depends on the graph alone.  Reads the rows once, writes
+// [G][D]; no atomics.  vn_stride (floats): D, or 0 for layer 0, where every graph's vector is E.  node_graph non-null (layer 0's
+// launch): also writes the node -> graph array the VN layer instances and gw_vn_add_kernel read.
+template <int D>
+__global__ __launch_bounds__(256) void gw_vn_pool_kernel(const float* __restrict__ rows, const int* __restrict__ node_off,
+                                                         const float* __restrict__ vn, int vn_stride, float* __restrict__ t,
+                                                         int* __restrict__ node_graph, int num_graphs) {
+    constexpr int C = D / 4;
+    const long long items = (long long)num_graphs * C;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < items; i += (long long)gridDim.x * 256) {
+        const int gi = (int)(i / C);
+        const int c = (int)(i - (long long)gi * C);
+        const int n0 = node_off[gi], n1 = node_off[gi + 1];
+        const float4* p = reinterpret_cast<const float4*>(rows) + (size_t)n0 * C + c;
+        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+        int v = n0;
+        for (; v + 3 < n1; v += 4, p += 4 * C) {
+            const float4 x0 = p[0], x1 = p[C], x2 = p[2 * C], x3 = p[3 * C];
+            acc.x += x0.x; acc.y += x0.y; acc.z += x0.z; acc.w += x0.w;
+            acc.x += x1.x; acc.y += x1.y; acc.z += x1.z; acc.w += x1.w;
+            acc.x += x2.x; acc.y += x2.y; acc.z += x2.z; acc.w += x2.w;
+            acc.x += x3.x; acc.y += x3.y; acc.z += x3.z; acc.w += x3.w;
+        }
+        for (; v < n1; v++, p += C) {
+            const float4 x = p[0];
+            acc.x += x.x; acc.y += x.y; acc.z += x.z; acc.w += x.w;
+        }
+        const float4 w = reinterpret_cast<const float4*>(vn + (size_t)gi * vn_stride)[c];
+        reinterpret_cast<float4*>(t)[i] = make_float4(acc.x + w.x, acc.y + w.y, acc.z + w.z, acc.w + w.w);
+        if (node_graph)
+            for (int u = n0 + c; u < n1; u += C) node_graph[u] = gi;
+    }
+}
+
+// rows[v] += vn[node_graph[v]]: the exact (fp32) re-run's add on the dense kernel's output -- its speed is no goal
+template <int D>
+__global__ __launch_bounds__(256) void gw_vn_add_kernel(float* __restrict__ rows, const int* __restrict__ node_graph,
+                                                        const float* __restrict__ vn, int n_tot) {
+    constexpr int C = D / 4;
+    const long long items = (long long)n_tot * C;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < items; i += (long long)gridDim.x * 256) {
+        const long long v = i / C;
+        const int c = (int)(i - v * C);
+        const float4 w = reinterpret_cast<const float4*>(vn)[(size_t)node_graph[v] * C + c];
+        float4 x = reinterpret_cast<float4*>(rows)[i];
+        x.x += w.x; x.y += w.y; x.z += w.z; x.w += w.w;
+        reinterpret_cast<float4*>(rows)[i] = x;
     }
 }
 
@@ -407,6 +525,47 @@ void gw_pack_layer(const float* w1, const float* b1, const float* w2, const floa
     tail[M::T2 * 16] = 1.0f / (s1 * s2);
 }
 
+// OGB's virtual node at this width (flowgnn_set_ogb_virtual_node_dim, section 4.17): the device form of the five tensors, a layout
+// of this file's own (gin_ogbvn.h's is the 100-wide one).  In bytes, every part a multiple of 16:
+//   E [D] floats | per update l (0..3): the weight stream of gw_pack_layer<D> (LAYER_BYTES) | its tail (TAIL_FLOATS floats)
+//                                       | W1^T [D][H] | W2^T [H][D] | b1 [H] | b2 [D]     (the four fp32 parts: the exact form)
+constexpr int GW_VN_LAYERS = GW_L - 1;
+template <int D>
+struct GwVnBlob {
+    using M = GwDims<D>;
+    static constexpr size_t E_BYTES = (size_t)D * 4;
+    static constexpr size_t TAIL_OFF = M::LAYER_BYTES;
+    static constexpr size_t W1T_OFF = TAIL_OFF + (size_t)M::TAIL_FLOATS * 4;
+    static constexpr size_t W2T_OFF = W1T_OFF + (size_t)D * M::H * 4;
+    static constexpr size_t B1_OFF = W2T_OFF + (size_t)M::H * D * 4;
+    static constexpr size_t B2_OFF = B1_OFF + (size_t)M::H * 4;
+    static constexpr size_t LAYER_STRIDE = B2_OFF + (size_t)D * 4;
+    static constexpr size_t BYTES = E_BYTES + GW_VN_LAYERS * LAYER_STRIDE;
+    static_assert(E_BYTES % 16 == 0 && TAIL_OFF % 16 == 0 && W1T_OFF % 16 == 0 && LAYER_STRIDE % 16 == 0, "the weight stream is read in 16-byte pieces");
+};
+
+// host tensors E [D], w1 [4][H][D], b1 [4][H], w2 [4][D][H], b2 [4][D] -> GwVnBlob<D>::BYTES bytes
+template <int D>
+void gw_vn_pack(const float* vn_embedding, const float* w1, const float* b1, const float* w2, const float* b2, uint8_t* out) {
+    using B = GwVnBlob<D>;
+    constexpr int H = 2 * D;
+    std::memcpy(out, vn_embedding, B::E_BYTES);
+    for (int l = 0; l < GW_VN_LAYERS; l++) {
+        uint8_t* o = out + B::E_BYTES + (size_t)l * B::LAYER_STRIDE;
+        const float* W1 = w1 + (size_t)l * H * D;
+        const float* W2 = w2 + (size_t)l * D * H;
+        gw_pack_layer<D>(W1, b1 + (size_t)l * H, W2, b2 + (size_t)l * D, o, reinterpret_cast<float*>(o + B::TAIL_OFF));
+        float* w1t = reinterpret_cast<float*>(o + B::W1T_OFF);
+        float* w2t = reinterpret_cast<float*>(o + B::W2T_OFF);
+        for (int u = 0; u < H; u++)
+            for (int k = 0; k < D; k++) w1t[(size_t)k * H + u] = W1[(size_t)u * D + k];
+        for (int d = 0; d < D; d++)
+            for (int k = 0; k < H; k++) w2t[(size_t)k * D + d] = W2[(size_t)d * H + k];
+        std::memcpy(o + B::B1_OFF, b1 + (size_t)l * H, (size_t)H * 4);
+        std::memcpy(o + B::B2_OFF, b2 + (size_t)l * D, (size_t)D * 4);
+    }
+}
+
 template <int D>
 class GinWideModel : public Model {
     using M = GwDims<D>;
@@ -414,6 +573,11 @@ class GinWideModel : public Model {
 
 public:
     ~GinWideModel() override { free_all(); }
+    int set_ogb_virtual_node(bool) override { return 0; }  // (the tensors: DeviceBatch::ogb_vn, in GwVnBlob's form)
+    size_t ogb_vn_blob_bytes() const override { return GwVnBlob<D>::BYTES; }
+    void ogb_vn_pack(const float* vn_embedding, const float* w1, const float* b1, const float* w2, const float* b2, void* out) const override {
+        gw_vn_pack<D>(vn_embedding, w1, b1, w2, b2, static_cast<uint8_t*>(out));
+    }
     int emb_dim() const override { return D; }
     int scratch_dim() const override { return D; }
     bool has_edge_attr() const override { return true; }
@@ -497,16 +661,28 @@ public:
     int forward(DeviceBatch& db, Profiler& prof, hipStream_t s) override {
         const int n = db.b.n_tot;
         if (n <= 0) return 0;
-        if (db.ogb_vn) {  // (the engine refuses it itself)
-            set_last_error("flowgnn_run: OGB's virtual node (flowgnn_set_ogb_virtual_node) has 100-wide tensors; this engine's width is not 100");
-            return 8;  // FLOWGNN_ERR_UNSUPPORTED
+        // OGB's virtual node (section 4.17): no launch rewrites the rows to add a vector -- x_0 = h_0 + E in the encoder, x_{l+1} in layer
+        // l's epilogue; vn_{l+1} depends on x_l alone, so it is complete before layer l is launched
+        using VB = GwVnBlob<D>;
+        const uint8_t* const vnb = reinterpret_cast<const uint8_t*>(db.ogb_vn);
+        const bool vn_on = vnb != nullptr;
+        const int G = db.b.num_graphs;
+        if (vn_on) {
+            if (int rc = vn_t_.reserve((size_t)G * D)) return rc;
+            if (int rc = vn_vec_[0].reserve((size_t)G * D)) return rc;
+            if (int rc = vn_vec_[1].reserve((size_t)G * D)) return rc;
+            if (int rc = node_graph_.reserve((size_t)n)) return rc;
         }
         {
             ProfScope p(prof, "atom_encoder", s);
-            gw_atom_encoder_kernel<D><<<grid_for((long long)n * M::C, 256, 256 * 8), 256, 0, s>>>(db.b.node_feature, d_nemb_, db.h[0], n, db.csr.err);
+            const int grid = grid_for((long long)n * M::C, 256, 256 * 8);
+            if (vn_on)
+                gw_atom_encoder_vn_kernel<D><<<grid, 256, 0, s>>>(db.b.node_feature, d_nemb_, db.h[0], n, db.csr.err, reinterpret_cast<const float*>(vnb));
+            else
+                gw_atom_encoder_kernel<D><<<grid, 256, 0, s>>>(db.b.node_feature, d_nemb_, db.h[0], n, db.csr.err);
         }
         if (exact_)
-            if (int rc = hid_.reserve((size_t)n * H)) return rc;
+            if (int rc = hid_.reserve((size_t)(n > G ? n : G) * H)) return rc;
         int cur = 0;
         for (int l = 0; l < GW_L; l++) {
             // (node embeddings: the last layer writes h_5 straight into the caller's buffer, and the readout reads it there)
@@ -514,11 +690,39 @@ public:
             const float self_s = db.gin_eps_on ? db.gin_self_scale[l] : 1.0f;
             const float* ecomb = d_ecomb_ + (size_t)l * EDGE_COMBOS * D;
             const int relu_out = l != GW_L - 1;
+            const bool vn_next = vn_on && l < GW_VN_LAYERS;  // this layer's output rows get vn_{l+1} added
+            float* const vnn = vn_vec_[l & 1].p;            // vn_{l+1}; vn_l is vn_vec_[(l - 1) & 1] (l = 0: E, stride 0)
+            if (vn_next) {
+                const uint8_t* const wl = vnb + VB::E_BYTES + (size_t)l * VB::LAYER_STRIDE;
+                {
+                    ProfScope p(prof, "gin_wide_vn_pool", s);  // t = sum of x_l's rows + vn_l (a sum whatever the readout's pooling is)
+                    gw_vn_pool_kernel<D><<<grid_for((long long)G * M::C, 256, 256 * 8), 256, 0, s>>>(
+                        db.h[cur], db.b.node_off, l == 0 ? reinterpret_cast<const float*>(vnb) : vn_vec_[(l - 1) & 1].p, l == 0 ? 0 : D, vn_t_.p,
+                        l == 0 ? node_graph_.p : nullptr, G);
+                }
+                ProfScope p(prof, "gin_wide_vn_update", s);
+                if (!exact_) {
+                    gw_vn_update_kernel<D><<<(int)ceil_div_ll(G, GW_ROWS), GW_WAVES * 64, 0, s>>>(
+                        vn_t_.p, vnn, wl, reinterpret_cast<const float*>(wl + VB::TAIL_OFF), G, db.range_flag);
+                } else {
+                    const int blocks = (int)ceil_div_ll(G, 8);
+                    gw_dense_f32_kernel<D, H><<<blocks, 256, 0, s>>>(vn_t_.p, reinterpret_cast<const float*>(wl + VB::W1T_OFF),
+                                                                    reinterpret_cast<const float*>(wl + VB::B1_OFF), hid_.p, G, 1);
+                    gw_dense_f32_kernel<H, D><<<blocks, 256, 0, s>>>(hid_.p, reinterpret_cast<const float*>(wl + VB::W2T_OFF),
+                                                                    reinterpret_cast<const float*>(wl + VB::B2_OFF), vnn, G, 1);
+                }
+            }
             if (!exact_) {
                 ProfScope p(prof, "gin_wide_layer", s);
-                gw_layer_kernel<D><<<(int)ceil_div_ll(n, GW_ROWS), GW_WAVES * 64, 0, s>>>(
-                    db.h[cur], hn, db.csr.row_ptr, db.csr.src, db.csr.ecode, ecomb, d_chunks_ + (size_t)l * M::LAYER_BYTES,
-                    d_tails_ + (size_t)l * M::TAIL_FLOATS, n, relu_out, self_s, db.range_flag);
+                const int grid = (int)ceil_div_ll(n, GW_ROWS);
+                if (vn_next)
+                    gw_layer_vn_kernel<D><<<grid, GW_WAVES * 64, 0, s>>>(
+                        db.h[cur], hn, db.csr.row_ptr, db.csr.src, db.csr.ecode, ecomb, d_chunks_ + (size_t)l * M::LAYER_BYTES,
+                        d_tails_ + (size_t)l * M::TAIL_FLOATS, n, self_s, db.range_flag, node_graph_.p, vnn);
+                else
+                    gw_layer_kernel<D><<<grid, GW_WAVES * 64, 0, s>>>(
+                        db.h[cur], hn, db.csr.row_ptr, db.csr.src, db.csr.ecode, ecomb, d_chunks_ + (size_t)l * M::LAYER_BYTES,
+                        d_tails_ + (size_t)l * M::TAIL_FLOATS, n, relu_out, self_s, db.range_flag);
             } else {
                 ProfScope p(prof, "gin_wide_layer_f32", s);
                 gw_aggregate_kernel<D><<<grid_for((long long)n * M::C, 256, 256 * 8), 256, 0, s>>>(db.h[cur], db.scratch, db.csr.row_ptr, db.csr.src,
@@ -526,6 +730,7 @@ public:
                 const int blocks = (int)ceil_div_ll(n, 8);
                 gw_dense_f32_kernel<D, H><<<blocks, 256, 0, s>>>(db.scratch, d_w1t_ + (size_t)l * D * H, d_b1_ + (size_t)l * H, hid_.p, n, 1);
                 gw_dense_f32_kernel<H, D><<<blocks, 256, 0, s>>>(hid_.p, d_w2t_ + (size_t)l * H * D, d_b2_ + (size_t)l * D, hn, n, relu_out);
+                if (vn_next) gw_vn_add_kernel<D><<<grid_for((long long)n * M::C, 256, 256 * 8), 256, 0, s>>>(hn, node_graph_.p, vnn, n);
             }
             cur ^= 1;
         }
@@ -564,6 +769,10 @@ private:
         if (d_chunks_) { (void)hipFree(d_chunks_); d_chunks_ = nullptr; }
         hid_.release();
         pooled_.release();
+        vn_t_.release();
+        vn_vec_[0].release();
+        vn_vec_[1].release();
+        node_graph_.release();
     }
     bool ready_ = false;
     bool exact_ = false;
@@ -574,6 +783,9 @@ private:
     float *d_w1t_ = nullptr, *d_w2t_ = nullptr, *d_b1_ = nullptr, *d_b2_ = nullptr;  // the exact form's weights, [K][O]
     GrowBuf hid_;     // the exact form's hidden rows [N][H]
     GrowBuf pooled_;  // the pooled rows [G][D] when graph embeddings are off
+    GrowBuf vn_t_;         // OGB's virtual node: t [G][D], the update's input
+    GrowBuf vn_vec_[2];    // ... vn_l and vn_{l+1} [G][D], alternating (both are live while layer l's update runs)
+    GrowBufI node_graph_;  // ... and node -> graph [N], written by layer 0's pool launch of every pass
 };
 
 }  // namespace

@@ -53,13 +53,18 @@ def _eps_arg(eps):
     return (C.c_float * 5)(*a.tolist())
 
 
-def _ogb_vn_args(vn):
+def _ogb_vn_args(vn, emb_dims=(100, 300)):
     """None -> five NULLs (off); else the dict's five tensors (weights.GIN_VIRTUAL_NODE_SHAPES) as float32 arrays, in the C call's
     order -- the caller keeps them alive for the duration of the call."""
     if vn is None:
         return [None] * 5
     from .weights import checked_gin_virtual_node
-    return list(checked_gin_virtual_node(vn).values())
+    return list(checked_gin_virtual_node(vn, emb_dims=emb_dims).values())
+
+
+def _ogb_vn_dim(a) -> int:
+    """The width of _ogb_vn_args' tensors (the embedding row's length); 100 for the five NULLs."""
+    return 100 if a[0] is None else int(a[0].size)
 
 
 def option_value(v) -> float:
@@ -174,7 +179,7 @@ class Engine:
         """eps=True (GIN, GIN-VN): also read the directory's eps file and apply it (set_gin_eps); virtual_node=True: also read
         gin_ep1_virtualnode_dim100.bin and apply it (GIN: set_ogb_virtual_node), or gcn_ep1_virtualnode_dim100.bin on a GCN engine
         (set_gcn_virtual_node).  The C call itself does neither.  A GIN engine at width 300 (set_emb_dim) reads the dim300 set, its eps
-        file included."""
+        file and its virtual-node file (gin_ep1_virtualnode_dim300.bin, through flowgnn_set_ogb_virtual_node_dim) included."""
         self._check(self.lib.flowgnn_load_weights_dir(self._h, directory.encode()), "flowgnn_load_weights_dir")
         if eps:
             from .weights import load_gin_eps
@@ -184,7 +189,7 @@ class Engine:
             self.set_gcn_virtual_node(load_gcn_virtual_node(directory))
         elif virtual_node:
             from .weights import load_gin_virtual_node
-            self.set_ogb_virtual_node(load_gin_virtual_node(directory))
+            self.set_ogb_virtual_node(load_gin_virtual_node(directory, emb_dim=self.emb_dim))
 
     # ---- batch
     def set_job_totals(self, job_nodes: int = -1, job_edges: int = -1):
@@ -599,9 +604,14 @@ class Engine:
     def set_ogb_virtual_node(self, vn=None):
         """GIN: run OGB's virtual node (gnn_type='gin-virtual'; flowgnn.h: flowgnn_set_ogb_virtual_node).  `vn`: a dict with the keys
         vn_embedding [100], w1 [4][200][100], b1 [4][200], w2 [4][100][200], b2 [4][100] (BatchNorms folded:
-        export.gin_virtual_node_from_ogb_state_dict); None turns it off.  The engine's, across batches and weight sets."""
+        export.gin_virtual_node_from_ogb_state_dict); None turns it off.  The engine's, across batches and weight sets.
+        300-wide tensors ([300], [4][600][300], ...: weights.gin_virtual_node_shapes(300)) go through the call that carries the width,
+        flowgnn_set_ogb_virtual_node_dim, for an engine at set_emb_dim(300); 100-wide ones through the call that has none."""
         a = _ogb_vn_args(vn)
-        self._check(self.lib.flowgnn_set_ogb_virtual_node(self._h, *[_pf(x) for x in a]), "flowgnn_set_ogb_virtual_node")
+        if _ogb_vn_dim(a) == 100:  # (at width 300 that is the call's own refusal: it has no width argument)
+            self._check(self.lib.flowgnn_set_ogb_virtual_node(self._h, *[_pf(x) for x in a]), "flowgnn_set_ogb_virtual_node")
+        else:
+            self._check(self.lib.flowgnn_set_ogb_virtual_node_dim(self._h, _ogb_vn_dim(a), *[_pf(x) for x in a]), "flowgnn_set_ogb_virtual_node_dim")
 
     def ogb_virtual_node(self) -> bool:
         """Whether OGB's virtual node is on (flowgnn.h: flowgnn_ogb_virtual_node)."""
@@ -611,7 +621,7 @@ class Engine:
         """GCN: run OGB's virtual node (gnn_type='gcn-virtual'; flowgnn.h: flowgnn_set_gcn_virtual_node).  `vn`: the dict of
         set_ogb_virtual_node (export.gcn_virtual_node_from_ogb_state_dict); None turns it off.  The engine's, across batches and
         weight sets."""
-        a = _ogb_vn_args(vn)
+        a = _ogb_vn_args(vn, emb_dims=(100,))
         self._check(self.lib.flowgnn_set_gcn_virtual_node(self._h, *[_pf(x) for x in a]), "flowgnn_set_gcn_virtual_node")
 
     def gcn_virtual_node(self) -> bool:
@@ -748,11 +758,15 @@ class EngineGroup:
     def set_ogb_virtual_node(self, vn=None):
         """Engine.set_ogb_virtual_node on every member (flowgnn.h: flowgnn_group_set_ogb_virtual_node)."""
         a = _ogb_vn_args(vn)
-        self._check(self.lib.flowgnn_group_set_ogb_virtual_node(self._h, *[_pf(x) for x in a]), "flowgnn_group_set_ogb_virtual_node")
+        if _ogb_vn_dim(a) == 100:
+            self._check(self.lib.flowgnn_group_set_ogb_virtual_node(self._h, *[_pf(x) for x in a]), "flowgnn_group_set_ogb_virtual_node")
+        else:
+            self._check(self.lib.flowgnn_group_set_ogb_virtual_node_dim(self._h, _ogb_vn_dim(a), *[_pf(x) for x in a]),
+                        "flowgnn_group_set_ogb_virtual_node_dim")
 
     def set_gcn_virtual_node(self, vn=None):
         """Engine.set_gcn_virtual_node on every member (flowgnn.h: flowgnn_group_set_gcn_virtual_node)."""
-        a = _ogb_vn_args(vn)
+        a = _ogb_vn_args(vn, emb_dims=(100,))
         self._check(self.lib.flowgnn_group_set_gcn_virtual_node(self._h, *[_pf(x) for x in a]), "flowgnn_group_set_gcn_virtual_node")
 
     def set_batch(self, batch: GraphBatch):

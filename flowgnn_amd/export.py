@@ -80,9 +80,19 @@ def gin_eps_from_ogb_state_dict(sd: Mapping, num_layers: int = 5) -> np.ndarray:
 VN_KEY = "gnn_node.virtualnode_embedding.weight"  # what tells a gin-virtual state_dict from a gin one
 
 
-def _virtual_node_from_ogb_state_dict(sd: Mapping, num_layers: int) -> Dict[str, np.ndarray]:
+def _vn_dim(virtual_node_dim) -> int:
+    d = int(virtual_node_dim)
+    if d not in _weights.GIN_EMB_DIMS:
+        raise ExportError(f"virtual_node_dim {virtual_node_dim}: the engine's virtual node is {_weights.GIN_EMB_DIMS[0]} or {_weights.GIN_EMB_DIMS[1]} wide")
+    return d
+
+
+def _virtual_node_from_ogb_state_dict(sd: Mapping, num_layers: int, dim: int = 100) -> Dict[str, np.ndarray]:
     """GNN_node_Virtualnode's own keys are the same whatever gnn_type the convolutions have: the folding of both exporters below."""
     emb = _get(sd, VN_KEY).reshape(-1)
+    if emb.size != dim:
+        raise ExportError(f"'{VN_KEY}' is {emb.size} wide and virtual_node_dim is {dim}" +
+                          (": the virtual node's tensors are 100-wide unless virtual_node_dim=300 says otherwise" if dim == 100 else ""))
     w1s, b1s, w2s, b2s = [], [], [], []
     for l in range(num_layers - 1):
         m = f"gnn_node.mlp_virtualnode_list.{l}"
@@ -96,15 +106,16 @@ def _virtual_node_from_ogb_state_dict(sd: Mapping, num_layers: int) -> Dict[str,
             w2, b2 = _get(sd, f"{m}.2.weight"), _get(sd, f"{m}.2.bias")
         w1s.append(w1); b1s.append(b1); w2s.append(w2); b2s.append(b2)
     out = OrderedDict([("vn_embedding", emb), ("w1", np.stack(w1s)), ("b1", np.stack(b1s)), ("w2", np.stack(w2s)), ("b2", np.stack(b2s))])
-    return _checked(out, _weights.GIN_VIRTUAL_NODE_SHAPES, lambda k, v: v)
+    return _checked(out, _weights.gin_virtual_node_shapes(dim), lambda k, v: v)
 
 
-def gin_virtual_node_from_ogb_state_dict(sd: Mapping, num_layers: int = 5) -> Dict[str, np.ndarray]:
+def gin_virtual_node_from_ogb_state_dict(sd: Mapping, num_layers: int = 5, virtual_node_dim: int = 100) -> Dict[str, np.ndarray]:
     """The virtual node of an OGB `GNN(gnn_type='gin-virtual')` state_dict as the five tensors Engine.set_ogb_virtual_node /
     flowgnn_set_ogb_virtual_node take: `gnn_node.virtualnode_embedding.weight` [1][100] and, per update l < num_layers - 1,
     `gnn_node.mlp_virtualnode_list.l` = Linear-BatchNorm-ReLU-Linear-BatchNorm-ReLU (OGB: .0 .1 .3 .4) or Linear-ReLU-Linear-ReLU
-    (.0 .2).  Both BatchNorms (inference statistics) sit in front of a ReLU and are folded into the linear layer before them: exact."""
-    return _virtual_node_from_ogb_state_dict(sd, num_layers)
+    (.0 .2).  Both BatchNorms (inference statistics) sit in front of a ReLU and are folded into the linear layer before them: exact.
+    virtual_node_dim: the width the caller expects, 100 or 300 (flowgnn_set_ogb_virtual_node_dim); a state_dict of another width is refused."""
+    return _virtual_node_from_ogb_state_dict(sd, num_layers, _vn_dim(virtual_node_dim))
 
 
 def gcn_virtual_node_from_ogb_state_dict(sd: Mapping, num_layers: int = 5) -> Dict[str, np.ndarray]:
@@ -114,7 +125,7 @@ def gcn_virtual_node_from_ogb_state_dict(sd: Mapping, num_layers: int = 5) -> Di
 
 
 def gin_weights_from_ogb_state_dict(sd: Mapping, num_layers: int = 5, eps_tol: float = 0.0, multi_task: bool = False,
-                                    keep_eps: bool = False, virtual_node: bool = False) -> Dict[str, np.ndarray]:
+                                    keep_eps: bool = False, virtual_node: bool = False, virtual_node_dim: int = 100) -> Dict[str, np.ndarray]:
     """OGB `GNN(gnn_type='gin', virtual_node=False, JK='last', residual=False, graph_pooling='mean')` -> the reference's
     GIN weight set.  `convs.l.mlp` may be Linear-BatchNorm-ReLU-Linear (OGB) or Linear-ReLU-Linear; `batch_norms.l`
     (applied to the conv output before the ReLU) is folded into the second linear layer when present.
@@ -126,16 +137,22 @@ def gin_weights_from_ogb_state_dict(sd: Mapping, num_layers: int = 5, eps_tol: f
     trained -- unless virtual_node says that the engine will run the virtual node too (gin_virtual_node_from_ogb_state_dict +
     flowgnn_set_ogb_virtual_node).
     The width is read off `atom_embedding_list.0.weight`: 100 (the reference's) or 300 (OGB's default; the tensors are then the
-    300-wide set of flowgnn_set_emb_dim(FLOWGNN_EMB_DIM_OGB)).  A 300-wide gin-virtual state_dict is refused even with virtual_node:
-    the engine's virtual node has 100-wide tensors."""
+    300-wide set of flowgnn_set_emb_dim(FLOWGNN_EMB_DIM_OGB)).  A 300-wide gin-virtual state_dict exports only with virtual_node=True
+    AND virtual_node_dim=300 (the engine then takes its virtual node through flowgnn_set_ogb_virtual_node_dim); without the keyword
+    the virtual node's tensors are 100-wide and the state_dict is refused.  A virtual_node_dim other than the state_dict's width is
+    refused too."""
+    vdim = _vn_dim(virtual_node_dim)
     p = "gnn_node"
     width = int(_get(sd, f"{p}.atom_encoder.atom_embedding_list.0.weight").shape[-1])
     if width not in _weights.GIN_EMB_DIMS:
         raise ExportError(f"atom_embedding_list.0.weight is {width} wide: the engine runs GIN at emb_dim 100 (the reference's width) "
                           f"and at emb_dim 300 (OGB's default), no other")
-    if VN_KEY in sd and width != 100:
+    if vdim != 100 and vdim != width:
+        raise ExportError(f"virtual_node_dim is {vdim} and the state_dict is {width} wide")
+    if VN_KEY in sd and width != vdim:
         raise ExportError(f"the state_dict has '{VN_KEY}' and is {width} wide: the engine's virtual node (flowgnn_set_ogb_virtual_node) "
-                          f"has 100-wide tensors, so a {width}-wide gin-virtual model cannot run, with or without virtual_node=True")
+                          f"has 100-wide tensors unless told otherwise, so a {width}-wide gin-virtual model exports only with "
+                          f"virtual_node=True, virtual_node_dim={width} (flowgnn_set_ogb_virtual_node_dim)")
     if VN_KEY in sd and not virtual_node:
         raise ExportError(f"the state_dict has '{VN_KEY}': it is OGB's gin-virtual, and these weights without its virtual node are "
                           f"a model nobody trained; pass virtual_node=True and give the engine gin_virtual_node_from_ogb_state_dict(sd) "
@@ -223,7 +240,7 @@ def _checked(w: Dict[str, np.ndarray], spec: Mapping, shape_of) -> Dict[str, np.
 
 
 def export_weights(model: str, sd: Mapping, directory: str, multi_task: bool = False, keep_eps: bool = False,
-                   virtual_node: bool = False) -> Dict[str, np.ndarray]:
+                   virtual_node: bool = False, virtual_node_dim: int = 100) -> Dict[str, np.ndarray]:
     """Write the `.bin` file(s) `host` / `flowgnn_load_weights_dir` read for `model` ('GIN', 'GIN-VN' or 'GCN').
     multi_task: keep all rows of the prediction head (the engine then needs flowgnn_set_num_tasks(rows) before loading).
     keep_eps (GIN, GIN-VN): a trained eps is not refused; the eps file holds the trained values, for `host --eps` /
@@ -231,15 +248,21 @@ def export_weights(model: str, sd: Mapping, directory: str, multi_task: bool = F
     dim300 file set, for an engine with flowgnn_set_emb_dim(300) / `host GIN --emb-dim 300`.
     virtual_node (GIN): the state_dict is OGB's gin-virtual; its virtual node goes into gin_ep1_virtualnode_dim100.bin beside the
     others, for `host GIN --ogb-vn` / Engine.load_weights_dir(dir, virtual_node=True) to apply (flowgnn_set_ogb_virtual_node).
+    virtual_node_dim (GIN): 300 for a 300-wide gin-virtual state_dict, whose virtual node goes into gin_ep1_virtualnode_dim300.bin
+    (flowgnn_set_ogb_virtual_node_dim; `host GIN --emb-dim 300 --eps --ogb-vn`); without it such a state_dict is refused.
     virtual_node (GCN): likewise OGB's gcn-virtual, into gcn_ep1_virtualnode_dim100.bin (flowgnn_set_gcn_virtual_node)."""
     m = model.upper()
+    if _vn_dim(virtual_node_dim) != 100 and m != "GIN":
+        raise ExportError(f"virtual_node_dim={virtual_node_dim} is GIN's (flowgnn_set_ogb_virtual_node_dim); {model} has the 100-wide virtual node only")
     if virtual_node and m not in ("GIN", "GCN"):
         raise ExportError(f"virtual_node=True is OGB's gin-virtual or gcn-virtual, which the engine runs as GIN or GCN (not {model})")
     if m in ("GIN", "GIN-VN"):
-        w = gin_weights_from_ogb_state_dict(sd, multi_task=multi_task, keep_eps=keep_eps, virtual_node=virtual_node)
+        w = gin_weights_from_ogb_state_dict(sd, multi_task=multi_task, keep_eps=keep_eps, virtual_node=virtual_node,
+                                            virtual_node_dim=virtual_node_dim)
+        vn = gin_virtual_node_from_ogb_state_dict(sd, virtual_node_dim=virtual_node_dim) if virtual_node else None  # (before any file is written)
         _weights.save_gin_weights(w, directory, eps=gin_eps_from_ogb_state_dict(sd) if keep_eps else None)
         if virtual_node:
-            _weights.save_gin_virtual_node(gin_virtual_node_from_ogb_state_dict(sd), directory)
+            _weights.save_gin_virtual_node(vn, directory)
     elif m == "GCN":
         w = gcn_weights_from_ogb_state_dict(sd, multi_task=multi_task, virtual_node=virtual_node)
         _weights.save_gcn_weights(w, directory)

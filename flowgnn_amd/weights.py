@@ -102,12 +102,36 @@ GIN_VIRTUAL_NODE_SHAPES = OrderedDict([
 GIN_VIRTUAL_NODE_FLOATS = sum(int(np.prod(s)) for s in GIN_VIRTUAL_NODE_SHAPES.values())  # 161 300
 
 
-def checked_gin_virtual_node(vn) -> Dict[str, np.ndarray]:
-    """The dict `vn` with exactly the five keys, each as a contiguous float32 array of its shape."""
+def gin_virtual_node_shapes(emb_dim: int = 100):
+    """GIN_VIRTUAL_NODE_SHAPES at width emb_dim (flowgnn_set_ogb_virtual_node_dim): 100 -> D, 200 -> 2 D."""
+    d = int(emb_dim)
+    if d not in GIN_EMB_DIMS:
+        raise ValueError(f"virtual node: emb_dim {emb_dim} is not one of {GIN_EMB_DIMS}")
+    grow = {100: d, 200: 2 * d}
+    return OrderedDict((k, tuple(grow.get(n, n) for n in shp)) for k, shp in GIN_VIRTUAL_NODE_SHAPES.items())
+
+
+def gin_virtual_node_file(emb_dim: int = 100) -> str:
+    """gin_ep1_virtualnode_dim<emb_dim>.bin"""
+    gin_virtual_node_shapes(emb_dim)  # (refuses a width that does not exist)
+    return GIN_VIRTUAL_NODE_FILE.replace("dim100", f"dim{int(emb_dim)}")
+
+
+def gin_virtual_node_dim_of(vn) -> int:
+    """The width of a virtual node's tensors: the size of its embedding row."""
+    return int(np.asarray(vn["vn_embedding"]).size)
+
+
+def checked_gin_virtual_node(vn, emb_dims=GIN_EMB_DIMS) -> Dict[str, np.ndarray]:
+    """The dict `vn` with exactly the five keys, each as a contiguous float32 array of its shape at the width read off vn_embedding's
+    size, which must be one of emb_dims (GCN's callers pass (100,): its call has no wider form)."""
     if set(vn) != set(GIN_VIRTUAL_NODE_SHAPES):
         raise ValueError(f"virtual node: wanted the keys {list(GIN_VIRTUAL_NODE_SHAPES)}, got {sorted(vn)}")
+    d = gin_virtual_node_dim_of(vn)
+    if d not in tuple(emb_dims):
+        raise ValueError(f"virtual node: vn_embedding is {np.asarray(vn['vn_embedding']).shape}, wanted a row of one of the widths {tuple(emb_dims)}")
     out = OrderedDict()
-    for k, shp in GIN_VIRTUAL_NODE_SHAPES.items():
+    for k, shp in gin_virtual_node_shapes(d).items():
         a = np.asarray(vn[k], dtype=np.float32)
         if a.size != int(np.prod(shp)):
             raise ValueError(f"virtual node: {k} is {a.shape}, wanted {shp}")
@@ -115,29 +139,39 @@ def checked_gin_virtual_node(vn) -> Dict[str, np.ndarray]:
     return out
 
 
-def save_gin_virtual_node(vn, directory: str) -> None:
-    """Write gin_ep1_virtualnode_dim100.bin: vn_embedding, w1, b1, w2, b2 end to end, little-endian float32.  Nothing applies the
-    file unless asked to: `host GIN --ogb-vn`, Engine.load_weights_dir(dir, virtual_node=True)."""
+def save_gin_virtual_node(vn, directory: str, emb_dim=None) -> None:
+    """Write gin_ep1_virtualnode_dim<D>.bin: vn_embedding, w1, b1, w2, b2 end to end, little-endian float32.  emb_dim: None = the
+    tensors' own width (which names the file); a width the tensors do not have is refused.  Nothing applies the file unless asked to:
+    `host GIN --ogb-vn`, Engine.load_weights_dir(dir, virtual_node=True)."""
+    vn = checked_gin_virtual_node(vn)
+    d = gin_virtual_node_dim_of(vn)
+    if emb_dim is not None and int(emb_dim) != d:
+        raise ValueError(f"virtual node: the tensors are {d} wide, emb_dim says {emb_dim}")
     os.makedirs(directory, exist_ok=True)
-    flat = np.concatenate([a.ravel() for a in checked_gin_virtual_node(vn).values()]).astype("<f4")
-    flat.tofile(os.path.join(directory, GIN_VIRTUAL_NODE_FILE))
+    flat = np.concatenate([a.ravel() for a in vn.values()]).astype("<f4")
+    flat.tofile(os.path.join(directory, gin_virtual_node_file(d)))
 
 
-def load_gin_virtual_node(directory: str) -> Dict[str, np.ndarray]:
-    """The five tensors of a directory's virtual-node file (for Engine.set_ogb_virtual_node); a short file is refused."""
-    path = os.path.join(directory, GIN_VIRTUAL_NODE_FILE)
+def load_gin_virtual_node(directory: str, emb_dim: int = 100) -> Dict[str, np.ndarray]:
+    """The five tensors of a directory's virtual-node file of width emb_dim (for Engine.set_ogb_virtual_node); a short file is refused."""
+    path = os.path.join(directory, gin_virtual_node_file(emb_dim))
     out, at = OrderedDict(), 0
-    for k, shp in GIN_VIRTUAL_NODE_SHAPES.items():
+    for k, shp in gin_virtual_node_shapes(emb_dim).items():
         out[k] = _read(path, shp, at)
         at += int(np.prod(shp))
     return out
 
 
-def synth_gin_virtual_node(seed: int = 11, scale: float = 1.0) -> Dict[str, np.ndarray]:
-    """Random virtual-node tensors at the scales of synth_gin_weights' MLP (the virtual node's MLP has the node MLP's shapes)."""
+def synth_gin_virtual_node(seed: int = 11, scale: float = 1.0, emb_dim: int = 100) -> Dict[str, np.ndarray]:
+    """Random virtual-node tensors at the scales of synth_gin_weights' MLP (the virtual node's MLP has the node MLP's shapes).
+    emb_dim 300: the matrices' scales shrink with sqrt(100 / emb_dim), as synth_gin_weights' do (at 100 the values are what they
+    always were)."""
     rng = np.random.default_rng(seed)
     s = {"vn_embedding": 0.11, "w1": 0.075, "b1": 0.91, "w2": 0.053, "b2": 0.49}
-    return OrderedDict((k, (rng.standard_normal(shp) * s[k] * scale).astype(np.float32)) for k, shp in GIN_VIRTUAL_NODE_SHAPES.items())
+    if emb_dim != 100:
+        for k in ("w1", "w2"):
+            s[k] = s[k] * float(np.sqrt(100.0 / emb_dim))
+    return OrderedDict((k, (rng.standard_normal(shp) * s[k] * scale).astype(np.float32)) for k, shp in gin_virtual_node_shapes(emb_dim).items())
 
 
 # ... and for GCN (flowgnn.h: flowgnn_set_gcn_virtual_node): the same five tensors in the same order, one file beside the GCN file
@@ -147,8 +181,8 @@ GCN_VIRTUAL_NODE_FILE = "gcn_ep1_virtualnode_dim100.bin"
 def save_gcn_virtual_node(vn, directory: str) -> None:
     """Write gcn_ep1_virtualnode_dim100.bin, as save_gin_virtual_node writes GIN's.  Nothing applies the file unless asked to:
     `host GCN --ogb-vn`, Engine.load_weights_dir(dir, virtual_node=True)."""
+    flat = np.concatenate([a.ravel() for a in checked_gin_virtual_node(vn, emb_dims=(100,)).values()]).astype("<f4")  # (refused before anything is created)
     os.makedirs(directory, exist_ok=True)
-    flat = np.concatenate([a.ravel() for a in checked_gin_virtual_node(vn).values()]).astype("<f4")
     flat.tofile(os.path.join(directory, GCN_VIRTUAL_NODE_FILE))
 
 

@@ -513,7 +513,7 @@ int flowgnn_num_tasks(const flowgnn_engine* e);
  * Call it before setting weights and batch (both must be set again afterwards: weights set before are dropped); drops a recorded
  * launch sequence; setting the width the engine has is a no-op.  FLOWGNN_MODEL_GIN only: every other model, GIN-VN included, returns
  * FLOWGNN_ERR_UNSUPPORTED.  At 300, FLOWGNN_NUMERIC_Q6_10 / FLOWGNN_NUMERIC_F16, flowgnn_set_ogb_virtual_node (its tensors are 100
- * wide) and flowgnn_run_aggregation_only / flowgnn_get_aggregate return FLOWGNN_ERR_UNSUPPORTED, and so does this call while one
+ * wide; 300-wide ones go through flowgnn_set_ogb_virtual_node_dim) and flowgnn_run_aggregation_only / flowgnn_get_aggregate return FLOWGNN_ERR_UNSUPPORTED, and so does this call while one
  * of the first three is on.  A width other than the two: FLOWGNN_ERR_ARG.  flowgnn_embedding_dim(model) keeps answering for the
  * model's default width; flowgnn_emb_dim(e) is the engine's (-1 for a null handle).  The <M>_compute_graphs entry points have no
  * 300-wide form.
@@ -649,6 +649,29 @@ int flowgnn_set_ogb_virtual_node(flowgnn_engine* e, const float* vn_embedding, c
 int flowgnn_ogb_virtual_node(const flowgnn_engine* e);            /* 1 on, 0 off, -1 null handle */
 
 /*
+ * The same model through a call that carries the tensors' width, which is how OGB's gin-virtual at its default emb_dim 300 runs
+ * (flowgnn_set_emb_dim(e, FLOWGNN_EMB_DIM_OGB) first).  With D = emb_dim: vn_embedding [D], w1 [4][2D][D], b1 [4][2D], w2 [4][D][2D],
+ * b2 [4][D]; the definition is the one above with that D.
+ *   emb_dim == 100: exactly flowgnn_set_ogb_virtual_node -- the same state, the same kernels, the same bits.
+ *   emb_dim == 300: kernels of gin_wide.hip.  No launch rewrites the rows to add a vector: x_0 = h_0 + E is
+ *       formed in the atom encoder, x_{l+1} in the epilogue of layer l's kernel, t by one read of the rows (profile slot
+ *       gin_wide_vn_pool) and the update MLP by the layer kernel's own split-f16 products on G rows (gin_wide_vn_update), with the
+ *       fp32 re-run of flowgnn_exact_reruns when t or a hidden value leaves the f16 range.  It combines with eps, NUM_TASK, every
+ *       pooling mode, the optional outputs, flowgnn_get_h, device batches and groups; the bits of a graph's result do not depend on
+ *       where the graph stands in a batch.
+ * FLOWGNN_ERR_ARG: emb_dim other than 100 or 300; tensors given and emb_dim != flowgnn_emb_dim(e) (flowgnn_last_error names both);
+ * some of the five NULL and some not; a value that is not finite.  FLOWGNN_ERR_UNSUPPORTED: any model but FLOWGNN_MODEL_GIN.  All five
+ * NULL turns the virtual node off at any width.  flowgnn_set_ogb_virtual_node itself has no width argument, so its tensors are 100
+ * wide by contract and it keeps refusing at width 300.  flowgnn_ogb_virtual_node reports 1 for either width.  While a virtual node of
+ * either width is on, flowgnn_set_emb_dim to the other width is FLOWGNN_ERR_UNSUPPORTED: the tensors belong to a width -- turn it off,
+ * change the width, set it again.  State handling is that of the call above.
+ * Files: gin_ep1_virtualnode_dim300.bin holds the five tensors in this order (1 443 900 LE float32); `host GIN --emb-dim 300 --ogb-vn`
+ * and the Python wrapper's load_weights_dir(dir, virtual_node=True) read the file of the engine's width.
+ */
+int flowgnn_set_ogb_virtual_node_dim(flowgnn_engine* e, int emb_dim, const float* vn_embedding, const float* w1, const float* b1,
+                                     const float* w2, const float* b2); /* host arrays, copied; all NULL = off */
+
+/*
  * OGB's virtual node for GCN: gnn_type = 'gcn-virtual' of the same example.  The five tensors, their shapes, the folding and the
  * device form are those of flowgnn_set_ogb_virtual_node above; the definition differs where GCN does -- the layer's linear map comes
  * first, so the vector passes through it:
@@ -766,6 +789,8 @@ int flowgnn_group_set_numeric_mode(flowgnn_group* g, int mode);
 int flowgnn_group_set_pooling(flowgnn_group* g, int mode);
 int flowgnn_group_set_gin_eps(flowgnn_group* g, const float* eps);
 int flowgnn_group_set_ogb_virtual_node(flowgnn_group* g, const float* vn_embedding, const float* w1, const float* b1, const float* w2, const float* b2);
+int flowgnn_group_set_ogb_virtual_node_dim(flowgnn_group* g, int emb_dim, const float* vn_embedding, const float* w1, const float* b1,
+                                           const float* w2, const float* b2);
 int flowgnn_group_set_gcn_virtual_node(flowgnn_group* g, const float* vn_embedding, const float* w1, const float* b1, const float* w2, const float* b2);
 int flowgnn_group_set_batch(flowgnn_group* g, int num_graphs,
                             const int* nums_of_nodes, const int* nums_of_edges,
