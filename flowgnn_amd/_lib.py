@@ -86,6 +86,7 @@ def _declare(lib):
     lib.flowgnn_num_tasks.argtypes = [eng]
     lib.flowgnn_set_emb_dim.argtypes = [eng, C.c_int]
     lib.flowgnn_emb_dim.argtypes = [eng]
+    lib.flowgnn_set_model_emb_dim.argtypes = [eng, C.c_int]
     lib.flowgnn_get_csr.argtypes = [eng, p_int, p_int, p_int, p_int]
     lib.flowgnn_get_h.argtypes = [eng, p_float, p_int]
     lib.flowgnn_profile_enable.argtypes = [eng, C.c_int]
@@ -118,6 +119,7 @@ def _declare(lib):
     lib.flowgnn_group_set_option.argtypes = [grp, C.c_char_p, C.c_double]
     lib.flowgnn_group_set_num_tasks.argtypes = [grp, C.c_int]
     lib.flowgnn_group_set_emb_dim.argtypes = [grp, C.c_int]
+    lib.flowgnn_group_set_model_emb_dim.argtypes = [grp, C.c_int]
     lib.flowgnn_group_set_numeric_mode.argtypes = [grp, C.c_int]
     lib.flowgnn_group_set_pooling.argtypes = [grp, C.c_int]
     lib.flowgnn_entry_set_pooling.argtypes = [C.c_int, C.c_int]
@@ -149,7 +151,7 @@ def _declare(lib):
     lib.GCN_compute_graphs.argtypes = [C.c_int, p_int, p_int, p_int, p_float, p_int, p_int, p_int] + [p_float] * 11
     for name in ("flowgnn_create", "flowgnn_destroy", "flowgnn_set_weights_gin", "flowgnn_set_weights", "flowgnn_load_weights_dir",
                  "flowgnn_set_batch", "flowgnn_set_batch_device", "flowgnn_set_job_totals", "flowgnn_graph_tile_fill", "flowgnn_set_job_tile_fill", "flowgnn_run", "flowgnn_sync", "flowgnn_get_results",
-                 "flowgnn_results_device", "flowgnn_set_results_buffer", "flowgnn_stream", "flowgnn_batch_info", "flowgnn_batch_tiles", "flowgnn_exact_reruns", "flowgnn_set_numeric_mode", "flowgnn_set_num_tasks", "flowgnn_num_tasks", "flowgnn_set_emb_dim", "flowgnn_emb_dim", "flowgnn_group_set_emb_dim", "flowgnn_get_csr",
+                 "flowgnn_results_device", "flowgnn_set_results_buffer", "flowgnn_stream", "flowgnn_batch_info", "flowgnn_batch_tiles", "flowgnn_exact_reruns", "flowgnn_set_numeric_mode", "flowgnn_set_num_tasks", "flowgnn_num_tasks", "flowgnn_set_emb_dim", "flowgnn_emb_dim", "flowgnn_group_set_emb_dim", "flowgnn_set_model_emb_dim", "flowgnn_group_set_model_emb_dim", "flowgnn_get_csr",
                  "flowgnn_get_h", "flowgnn_profile_enable", "flowgnn_profile_read",
                  "flowgnn_run_aggregation_only", "flowgnn_get_aggregate", "flowgnn_set_stream",
                  "flowgnn_set_option", "flowgnn_get_option", "flowgnn_option_count", "flowgnn_entry_set_devices", "flowgnn_entry_set_option",

@@ -262,6 +262,7 @@ public:
 Model* make_gin_model(bool virtual_node);
 Model* make_gin_wide_model(int emb_dim);  // gin_wide.hip: GIN at OGB's default width (flowgnn_set_emb_dim); null: no such width
 Model* make_gcn_model();
+Model* make_gcn_wide_model(int emb_dim);  // gcn_wide.hip: GCN at OGB's default width (flowgnn_set_model_emb_dim); null: no such width
 Model* make_pna_model();
 Model* make_dgn_model();
 Model* make_gat_model();

@@ -1306,37 +1306,35 @@ int flowgnn_set_num_tasks(flowgnn_engine* e, int num_tasks) {
 
 int flowgnn_num_tasks(const flowgnn_engine* e) { return e ? e->num_tasks : -1; }
 
-// The width is the model OBJECT: GinModel (gin.hip) at 100, the per-layer model of gin_wide.hip at 300.  The call swaps it; everything
-// the old object held (weights) goes with it, and everything sized by the width (h, the embeddings, the node embeddings) with the batch.
-int flowgnn_set_emb_dim(flowgnn_engine* e, int emb_dim) {
-    if (!e) return FLOWGNN_ERR_ARG;
-    if (emb_dim != FLOWGNN_EMB_DIM_REFERENCE && emb_dim != FLOWGNN_EMB_DIM_OGB) {
-        e->err = "flowgnn_set_emb_dim: the widths are FLOWGNN_EMB_DIM_REFERENCE (100) and FLOWGNN_EMB_DIM_OGB (300)";
-        return FLOWGNN_ERR_ARG;
-    }
-    if (e->model_id != FLOWGNN_MODEL_GIN) {
-        e->err = "flowgnn_set_emb_dim: the width is a choice of FLOWGNN_MODEL_GIN alone (GIN-VN, GCN and the other models have the reference's width only)";
-        return FLOWGNN_ERR_UNSUPPORTED;
-    }
+// The width is the model OBJECT: GinModel (gin.hip) / GcnModel (gcn.hip) at 100, the per-layer models of gin_wide.hip / gcn_wide.hip at
+// 300.  The call swaps it; everything the old object held (weights) goes with it, and everything sized by the width (h, the embeddings,
+// the node embeddings) with the batch.  `fn`: the caller (flowgnn_set_emb_dim: GIN; flowgnn_set_model_emb_dim: GIN and GCN).
+static bool off_default_width(const flowgnn_engine* e) { return e->emb_dim != flowgnn_embedding_dim(e->model_id); }
+
+static int set_width(flowgnn_engine* e, const char* fn, int emb_dim) {
+    const std::string who = std::string(fn) + ": ";
+    const bool gcn = e->model_id == FLOWGNN_MODEL_GCN;
     if (emb_dim == e->emb_dim) return FLOWGNN_OK;
     if (emb_dim != FLOWGNN_EMB_DIM_REFERENCE) {
         if (e->numeric_mode != FLOWGNN_NUMERIC_F32) {
-            e->err = "flowgnn_set_emb_dim: a numeric mode other than FLOWGNN_NUMERIC_F32 is on (flowgnn_set_numeric_mode), and width 300 has neither fixed-point nor f16 kernels";
+            e->err = who + "a numeric mode other than FLOWGNN_NUMERIC_F32 is on (flowgnn_set_numeric_mode), and width 300 has neither fixed-point nor f16 kernels";
             return FLOWGNN_ERR_UNSUPPORTED;
         }
     }
     if (e->ogb_vn_on) {  // (either direction: the tensors belong to a width -- turn it off, change the width, set it again)
-        e->err = "flowgnn_set_emb_dim: OGB's virtual node is on (flowgnn_set_ogb_virtual_node / flowgnn_set_ogb_virtual_node_dim), and its tensors are " +
-                 std::to_string(e->emb_dim) + " wide";
+        e->err = who + "OGB's virtual node is on (" + (gcn ? "flowgnn_set_gcn_virtual_node" : "flowgnn_set_ogb_virtual_node / flowgnn_set_ogb_virtual_node_dim") +
+                 "), and its tensors are " + std::to_string(e->emb_dim) + " wide";
+        if (gcn) e->err += " (gcn-virtual has no 300-wide form)";
         return FLOWGNN_ERR_UNSUPPORTED;
     }
     ENGINE_TRY(e, begin_change(e));
-    Model* m = emb_dim == FLOWGNN_EMB_DIM_REFERENCE ? make_gin_model(false) : make_gin_wide_model(emb_dim);
-    if (!m) { e->err = "flowgnn_set_emb_dim: no model of this width"; return FLOWGNN_ERR_UNSUPPORTED; }
+    Model* m = gcn ? (emb_dim == FLOWGNN_EMB_DIM_REFERENCE ? make_gcn_model() : make_gcn_wide_model(emb_dim))
+                   : (emb_dim == FLOWGNN_EMB_DIM_REFERENCE ? make_gin_model(false) : make_gin_wide_model(emb_dim));
+    if (!m) { e->err = who + "no model of this width"; return FLOWGNN_ERR_UNSUPPORTED; }
     m->configure(e->opts);
     if (int rc = m->set_num_tasks(e->num_tasks)) {
         delete m;
-        e->err = "flowgnn_set_emb_dim: the model of this width does not take the engine's NUM_TASK";
+        e->err = who + "the model of this width does not take the engine's NUM_TASK";
         return rc;
     }
     delete e->model;  // (the stream is idle: begin_change)
@@ -1354,6 +1352,35 @@ int flowgnn_set_emb_dim(flowgnn_engine* e, int emb_dim) {
     return FLOWGNN_OK;
 }
 
+int flowgnn_set_emb_dim(flowgnn_engine* e, int emb_dim) {
+    if (!e) return FLOWGNN_ERR_ARG;
+    if (emb_dim != FLOWGNN_EMB_DIM_REFERENCE && emb_dim != FLOWGNN_EMB_DIM_OGB) {
+        e->err = "flowgnn_set_emb_dim: the widths are FLOWGNN_EMB_DIM_REFERENCE (100) and FLOWGNN_EMB_DIM_OGB (300)";
+        return FLOWGNN_ERR_ARG;
+    }
+    if (e->model_id != FLOWGNN_MODEL_GIN) {
+        e->err = "flowgnn_set_emb_dim: the width is a choice of FLOWGNN_MODEL_GIN alone in this call (GIN-VN and the other models have the reference's width only; "
+                 "GCN's width goes through flowgnn_set_model_emb_dim)";
+        return FLOWGNN_ERR_UNSUPPORTED;
+    }
+    return set_width(e, "flowgnn_set_emb_dim", emb_dim);
+}
+
+// The call that names no model: GIN exactly as flowgnn_set_emb_dim (the same code path, state and bits), GCN between GcnModel and
+// gcn_wide.hip's model.
+int flowgnn_set_model_emb_dim(flowgnn_engine* e, int emb_dim) {
+    if (!e) return FLOWGNN_ERR_ARG;
+    if (emb_dim != FLOWGNN_EMB_DIM_REFERENCE && emb_dim != FLOWGNN_EMB_DIM_OGB) {
+        e->err = "flowgnn_set_model_emb_dim: the widths are FLOWGNN_EMB_DIM_REFERENCE (100) and FLOWGNN_EMB_DIM_OGB (300)";
+        return FLOWGNN_ERR_ARG;
+    }
+    if (e->model_id != FLOWGNN_MODEL_GIN && e->model_id != FLOWGNN_MODEL_GCN) {
+        e->err = "flowgnn_set_model_emb_dim: the width is a choice of FLOWGNN_MODEL_GIN and FLOWGNN_MODEL_GCN (the other models have the reference's width only)";
+        return FLOWGNN_ERR_UNSUPPORTED;
+    }
+    return set_width(e, e->model_id == FLOWGNN_MODEL_GIN ? "flowgnn_set_emb_dim" : "flowgnn_set_model_emb_dim", emb_dim);
+}
+
 int flowgnn_emb_dim(const flowgnn_engine* e) { return e ? e->emb_dim : -1; }
 
 int flowgnn_set_numeric_mode(flowgnn_engine* e, int mode) {
@@ -1363,8 +1390,8 @@ int flowgnn_set_numeric_mode(flowgnn_engine* e, int mode) {
             e->err = o.no_fixed_point;
             return FLOWGNN_ERR_UNSUPPORTED;
         }
-    if (mode != FLOWGNN_NUMERIC_F32 && e->model_id == FLOWGNN_MODEL_GIN && e->emb_dim != FLOWGNN_EMB_DIM_REFERENCE) {
-        e->err = "flowgnn_set_numeric_mode: the engine's width is 300 (flowgnn_set_emb_dim), which has neither fixed-point nor f16 kernels";
+    if (mode != FLOWGNN_NUMERIC_F32 && off_default_width(e)) {
+        e->err = "flowgnn_set_numeric_mode: the engine's width is 300 (flowgnn_set_emb_dim / flowgnn_set_model_emb_dim), which has neither fixed-point nor f16 kernels";
         return FLOWGNN_ERR_UNSUPPORTED;
     }
     if (mode == FLOWGNN_NUMERIC_Q6_10 && e->pooling != FLOWGNN_POOL_MEAN) {
@@ -1554,6 +1581,10 @@ int flowgnn_set_gcn_virtual_node(flowgnn_engine* e, const float* vn_embedding, c
         e->err = "flowgnn_set_gcn_virtual_node: this call is OGB's gcn-virtual, for GCN only (GIN: flowgnn_set_ogb_virtual_node)";
         return FLOWGNN_ERR_UNSUPPORTED;
     }
+    if (off_default_width(e) && (vn_embedding || w1 || b1 || w2 || b2)) {
+        e->err = "flowgnn_set_gcn_virtual_node: the engine's width is 300 (flowgnn_set_model_emb_dim), the virtual node's tensors are 100 wide, and gcn-virtual has no 300-wide form";
+        return FLOWGNN_ERR_UNSUPPORTED;
+    }
     return set_virtual_node(e, "flowgnn_set_gcn_virtual_node", vn_embedding, w1, b1, w2, b2);
 }
 
@@ -1663,7 +1694,7 @@ int flowgnn_profile_read(flowgnn_engine* e, int* count, const char** names, doub
 
 int flowgnn_run_aggregation_only(flowgnn_engine* e, int layer, int iters, float* avg_ms) {
     if (!e || iters <= 0) return FLOWGNN_ERR_ARG;
-    if (e->model_id == FLOWGNN_MODEL_GIN && e->emb_dim != FLOWGNN_EMB_DIM_REFERENCE) { e->err = "flowgnn_run_aggregation_only: the engine's width is 300 (flowgnn_set_emb_dim), which has no stand-alone aggregation kernel"; return FLOWGNN_ERR_UNSUPPORTED; }
+    if (off_default_width(e)) { e->err = "flowgnn_run_aggregation_only: the engine's width is 300 (flowgnn_set_emb_dim / flowgnn_set_model_emb_dim), which has no stand-alone aggregation kernel"; return FLOWGNN_ERR_UNSUPPORTED; }
     if (!e->ran) { e->err = "flowgnn_run_aggregation_only needs a prior flowgnn_run"; return FLOWGNN_ERR_STATE; }
     if (e->gin_eps_on) { e->err = "flowgnn_run_aggregation_only: a trained eps is on (flowgnn_set_gin_eps), and the stand-alone aggregation kernel has no eps instance"; return FLOWGNN_ERR_UNSUPPORTED; }
     if (e->ogb_vn_on) { e->err = "flowgnn_run_aggregation_only: OGB's virtual node is on (flowgnn_set_ogb_virtual_node / flowgnn_set_gcn_virtual_node), and the stand-alone aggregation kernel does not add it"; return FLOWGNN_ERR_UNSUPPORTED; }
@@ -1696,7 +1727,7 @@ int flowgnn_run_aggregation_only(flowgnn_engine* e, int layer, int iters, float*
 
 int flowgnn_get_aggregate(flowgnn_engine* e, int layer, float* h_in_host, int* in_dim, float* agg_host, int* agg_dim) {
     if (!e) return FLOWGNN_ERR_ARG;
-    if (e->model_id == FLOWGNN_MODEL_GIN && e->emb_dim != FLOWGNN_EMB_DIM_REFERENCE) { e->err = "flowgnn_get_aggregate: the engine's width is 300 (flowgnn_set_emb_dim), which has no stand-alone aggregation kernel"; return FLOWGNN_ERR_UNSUPPORTED; }
+    if (off_default_width(e)) { e->err = "flowgnn_get_aggregate: the engine's width is 300 (flowgnn_set_emb_dim / flowgnn_set_model_emb_dim), which has no stand-alone aggregation kernel"; return FLOWGNN_ERR_UNSUPPORTED; }
     if (!e->ran) { e->err = "flowgnn_get_aggregate needs a prior flowgnn_run"; return FLOWGNN_ERR_STATE; }
     if (e->gin_eps_on) { e->err = "flowgnn_get_aggregate: a trained eps is on (flowgnn_set_gin_eps), and the stand-alone aggregation kernel has no eps instance"; return FLOWGNN_ERR_UNSUPPORTED; }
     if (e->ogb_vn_on) { e->err = "flowgnn_get_aggregate: OGB's virtual node is on (flowgnn_set_ogb_virtual_node / flowgnn_set_gcn_virtual_node), and the stand-alone aggregation kernel does not add it"; return FLOWGNN_ERR_UNSUPPORTED; }

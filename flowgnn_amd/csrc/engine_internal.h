@@ -65,7 +65,7 @@ struct flowgnn_engine {
     bool batch_ready = false;
     bool ran = false;
     int num_tasks = 1;          // NUM_TASK of the readout: results are [G][num_tasks]
-    int emb_dim = 0;            // the width of the engine's embeddings: flowgnn_embedding_dim(model) at flowgnn_create, then what flowgnn_set_emb_dim said (GIN)
+    int emb_dim = 0;            // the width of the engine's embeddings: flowgnn_embedding_dim(model) at flowgnn_create, then what flowgnn_set_emb_dim (GIN) / flowgnn_set_model_emb_dim (GIN, GCN) said
     bool force_exact = false;   // the resident batch tripped the range flag once: run it on the exact kernels
     int exact_reruns = 0;
     long long G = 0, N = 0, E = 0;

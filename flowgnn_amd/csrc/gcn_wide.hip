@@ -1,0 +1,535 @@
+// GCN at OGB's default width (emb_dim 300): flowgnn_set_model_emb_dim(e, FLOWGNN_EMB_DIM_OGB) on a GCN engine.  DESIGN.md section 4.18.
+//
+// The model of gcn.hip's header with D in place of 100 (x_l = W_l a_l + b_l is ONE D x D product per layer):
+//   x_0     = b_0 + W_0 h0, h0[v] = sum_{k<9} NodeEmb[off_k + feat_k(v)]
+//   m_l[v]  = sum_{(u->v)} dinv[u] dinv[v] relu(x_l[u] + ecomb_l[code_e]), CSR order; dinv[i] = outdeg(i) > 0 ? 1/sqrt(outdeg(i)+1) : 0
+//   pre_l   = BN_l(m_l + relu(x_l + root_l) / (outdeg + 1)), BN eval mode with sqrt(var + 2^-10), folded to one scale and one shift
+//   a_{l+1} = relu(pre_l), x_{l+1} = W_{l+1} a_{l+1} + b_{l+1} (l < 4); readout: pool(pre_4), graph_pred_linear
+//
+// A model object of its own beside GcnModel, as GinWideModel is beside GinModel: one launch per stage, a tile is a run of rows.
+//   x_0        the first product is linear in the nine looked-up rows: W_0 is applied to the 173-row table once (set_weights, in double)
+//              and x_0 is the wide atom encoder on that table with b_0 as a tenth row (gw_atom_encoder_vn_kernel) -- no dense launch
+//   l = 0..3   gcw_layer_kernel<D>: the scheme of gcn_layer_fused_kernel<false> (gcn.hip) carried to this width the way gw_layer_body
+//              (gin_wide.hip) carried gin_layer_split_kernel.  A wave owns a 16-node column tile, walks its in-edges in CSR order into
+//              the B-operand layout (lane (j, g) holds features 16 q + 4 g + r, q < Q; pieces at or beyond column D stay zero), loads
+//              the node's own row after the walk, applies root, 1 / (deg + 1), the folded BatchNorm and ReLU in registers, splits with
+//              DS_SPLIT2 and runs x_{l+1} as three f16 MFMAs per product.  K is padded with zero weights to whole K-steps: no fp32 tail.
+//              The split weights (T output tiles x KS K-steps x hi/lo KiB) do not fit LDS: they stream L2 -> LDS by LDS-DMA as chunks of
+//              TPC whole output tiles into two distinct LDS objects; s_waitcnt vmcnt(0) + a workgroup barrier per step, nothing counted.
+//              A chunk's output tiles are stored as soon as its MFMAs are done, so TPC accumulators are live, not T.  The combined edge
+//              table and the three epilogue vectors have LDS of their own beside the two buffers (the budget: GcwDims).
+//   l = 4      gcw_final_kernel<D>: the walk and the epilogue without ReLU and without a product; rows pre_4
+//   readout    gw_pool_rows_kernel, launch_pooled_head, launch_node_logits_rows, as GinWideModel::forward
+// a beyond the f16 range raises *range_flag; the engine then repeats the pass with set_exact(true): gcw_aggregate_kernel (the same
+// CSR order, the same FMAs, the same epilogue, one lane per node and float4 piece) and gw_dense_f32_kernel<D, D> once per stage.
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "common.h"
+#include "dense_split.h"
+#include "wide_common.h"
+
+namespace fg {
+namespace {
+
+constexpr int GCW_L = 5;
+
+template <int D>
+struct GcwDims {
+    static_assert(D % 4 == 0, "rows are read as float4 pieces");
+    static constexpr int C = D / 4;               // float4 pieces of a row
+    static constexpr int KS = (D + 31) / 32;      // K-steps of the product (K padded to 32 KS)
+    static constexpr int Q = 2 * KS;              // 16-feature pieces a lane holds four floats of
+    static constexpr int T = (D + 15) / 16;       // 16-row output tiles, the last one masked at column D
+    static constexpr int TPC = 2;                 // output tiles of a chunk of the weight stream
+    static constexpr int STEPS = (T + TPC - 1) / TPC;
+    static_assert(STEPS % 2 == 0, "the step loop alternates two LDS buffers");
+    // chunk c, in 1 KiB fragments (64 lanes x 8 halves): output tile TPC c + tl, K-step ks, p = 0 hi, 1 lo: fragment (tl KS + ks) 2 + p;
+    // tiles at or beyond T are zeros (their products are computed and dropped)
+    static constexpr int TILE_BYTES = KS * 2 * 1024;
+    static constexpr int CHUNK_BYTES = TPC * TILE_BYTES;
+    static constexpr int PIECES = CHUNK_BYTES / 1024;
+    static constexpr size_t LAYER_BYTES = (size_t)STEPS * CHUNK_BYTES;
+    // per layer, contiguous in global memory and in LDS: the 60 combined edge rows | root | folded BN scale | folded BN shift
+    static constexpr int ECOMB_FLOATS = EDGE_COMBOS * D;
+    static constexpr int TAB_FLOATS = ECOMB_FLOATS + 3 * D;
+    static constexpr int TAB_BYTES = TAB_FLOATS * 4;
+    static constexpr int TAB_PIECES = (TAB_BYTES + 1023) / 1024;
+    static constexpr int TAB_LAST_LANES = (TAB_BYTES - (TAB_PIECES - 1) * 1024) / 16;
+    static_assert(TAB_BYTES % 16 == 0, "the table is copied in 16-byte pieces");
+    static_assert(2 * CHUNK_BYTES + TAB_BYTES <= 160 * 1024, "two weight buffers and the table must fit the CU's LDS");
+    static constexpr int SCALE_AT = STEPS * TPC * 16;  // per layer, read from global memory: b pre-scaled and padded, then 1 / s
+    static constexpr int TAIL_FLOATS = SCALE_AT + 4;
+};
+
+// dinv[src_e] per CSR entry (edge_scalar_kernel, device_common.h), the per-layer path's policy of gcn.hip restated: GcnAggPolicy
+// itself lives in gcn.hip's translation units
+struct GcwScalarPolicy {
+    struct Params { const int* out_deg; };
+    __device__ static float src_scalar(const Params& p, int u) {
+        const int d = p.out_deg[u];
+        return d > 0 ? 1.0f / sqrtf((float)(d + 1)) : 0.0f;
+    }
+};
+
+// a[v] = act(BN(m[v] + relu(x[v] + root) / (deg(v) + 1))) of this lane's node in the B-operand layout; s_tab: the layer's table in LDS.
+// The accumulate is an explicit fma at every place this is inlined (GcnAggPolicy::edge says why), and so is the epilogue.
+template <int D, bool RELU_OUT>
+__device__ __forceinline__ void gcw_walk(const float* __restrict__ x, const int* __restrict__ row_ptr, const int* __restrict__ src,
+                                         const uint8_t* __restrict__ ecode, const float* __restrict__ esc, const int* __restrict__ out_deg,
+                                         const float* s_tab, long long node, bool valid, int g, float (&a)[4 * GcwDims<D>::Q]) {
+    using M = GcwDims<D>;
+    int e = row_ptr[node];
+    const int e_end = valid ? row_ptr[node + 1] : e;
+    const int dv = out_deg[node];
+    const float dinv_v = dv > 0 ? 1.0f / sqrtf((float)(dv + 1)) : 0.0f;
+    const float idp1 = 1.0f / (float)(dv + 1);
+#pragma unroll
+    for (int k = 0; k < 4 * M::Q; k++) a[k] = 0.0f;
+    int u_nx = 0, c_nx = 0;
+    float n_nx = 0.0f;
+    if (e < e_end) { u_nx = src[e]; c_nx = ecode[e]; n_nx = esc[e]; }
+    // Piece q of a row is columns 16 q + 4 g .. + 3.  The one piece that straddles column D (D % 16 != 0) is read by the lanes beyond D
+    // from the row's last four columns instead -- in bounds, and no branch inside the walk; what those lanes hold of it is zeroed
+    // at the end, so pieces at or beyond column D stay zero.  NQ: the pieces that exist.
+    constexpr int NQ = M::T;
+    const int o_last = 16 * (NQ - 1) < D - 4 - 4 * g ? 16 * (NQ - 1) : D - 4 - 4 * g;
+#define GCW_OFF(q) (16 * (q) + 16 > D ? o_last : 16 * (q))
+    // ---- one in-edge per trip, in CSR order (a row's sum depends on the row alone); the CSR entry one edge ahead of the row loads
+    // (a lane whose row is done runs the trip with norm 0 on the entry it read last, or on row 0: fma(0, finite, a) is a, and the 4 Q
+    // accumulators are updated on one path -- under `if (e < e_end)` they were copied to and fro on every trip)
+    while (__any(e < e_end)) {
+        const int u = u_nx, code = c_nx;
+        const float norm = e < e_end ? n_nx * dinv_v : 0.0f;
+        e += e < e_end;
+        if (e < e_end) { u_nx = src[e]; c_nx = ecode[e]; n_nx = esc[e]; }
+        const float* hr = x + (size_t)u * D + 4 * g;
+        const float* er = s_tab + code * D + 4 * g;
+#pragma unroll
+        for (int q0 = 0; q0 < NQ; q0 += M::KS) {
+            if (q0) __builtin_amdgcn_sched_barrier(0);  // (one half row in flight, not both)
+            float4 xv[M::KS];
+#pragma unroll
+            for (int q = 0; q < M::KS; q++)
+                if (q0 + q < NQ) xv[q] = *reinterpret_cast<const float4*>(hr + GCW_OFF(q0 + q));
+#pragma unroll
+            for (int q = 0; q < M::KS; q++)
+                if (q0 + q < NQ) {
+                    const float4 w = *reinterpret_cast<const float4*>(er + GCW_OFF(q0 + q));
+                    float r0 = __builtin_fmaf(norm, relu1(w.x + xv[q].x), a[4 * (q0 + q) + 0]);
+                    float r1 = __builtin_fmaf(norm, relu1(w.y + xv[q].y), a[4 * (q0 + q) + 1]);
+                    float r2 = __builtin_fmaf(norm, relu1(w.z + xv[q].z), a[4 * (q0 + q) + 2]);
+                    float r3 = __builtin_fmaf(norm, relu1(w.w + xv[q].w), a[4 * (q0 + q) + 3]);
+                    asm volatile("" : "+v"(r0), "+v"(r1), "+v"(r2), "+v"(r3));  // (computed in this trip, not carried into the next)
+                    a[4 * (q0 + q) + 0] = r0; a[4 * (q0 + q) + 1] = r1; a[4 * (q0 + q) + 2] = r2; a[4 * (q0 + q) + 3] = r3;
+                }
+        }
+    }
+    // ---- the node's own row, after the walk (another 4 Q registers before it), and the epilogue: root, 1 / (deg + 1), folded BatchNorm
+    const float* xr = x + (size_t)node * D + 4 * g;
+    const float* ep = s_tab + M::ECOMB_FLOATS + 4 * g;
+    // (a fence every four pieces: left alone, the scheduler hoists all 4 Q row loads and 12 Q table reads above the first FMA, and spills)
+#pragma unroll
+    for (int q = 0; q < NQ; q++) {
+        if (q % 4 == 0) __builtin_amdgcn_sched_barrier(0);
+        const float4 xs = *reinterpret_cast<const float4*>(xr + GCW_OFF(q));
+        const float4 rt = *reinterpret_cast<const float4*>(ep + GCW_OFF(q));
+        const float4 sc = *reinterpret_cast<const float4*>(ep + D + GCW_OFF(q));
+        const float4 sh = *reinterpret_cast<const float4*>(ep + 2 * D + GCW_OFF(q));
+        float r0 = __builtin_fmaf(__builtin_fmaf(relu1(xs.x + rt.x), idp1, a[4 * q + 0]), sc.x, sh.x);
+        float r1 = __builtin_fmaf(__builtin_fmaf(relu1(xs.y + rt.y), idp1, a[4 * q + 1]), sc.y, sh.y);
+        float r2 = __builtin_fmaf(__builtin_fmaf(relu1(xs.z + rt.z), idp1, a[4 * q + 2]), sc.z, sh.z);
+        float r3 = __builtin_fmaf(__builtin_fmaf(relu1(xs.w + rt.w), idp1, a[4 * q + 3]), sc.w, sh.w);
+        if (RELU_OUT) { r0 = relu1(r0); r1 = relu1(r1); r2 = relu1(r2); r3 = relu1(r3); }
+        if (16 * q + 16 > D && 16 * q + 4 * g >= D) r0 = r1 = r2 = r3 = 0.0f;  // the straddling piece, beyond column D
+        asm volatile("" : "+v"(r0), "+v"(r1), "+v"(r2), "+v"(r3));  // (computed here, not sunk to where the value is used)
+        a[4 * q + 0] = r0; a[4 * q + 1] = r1; a[4 * q + 2] = r2; a[4 * q + 3] = r3;
+    }
+#undef GCW_OFF
+}
+
+// the TPC output tiles of chunk c from the fragments in `wb`: three f16 MFMAs per product, stored as soon as they are done
+template <int D>
+__device__ __forceinline__ void gcw_step(const char* wb, int c, int lane, int g, const ds_uint4_t (&in_hi)[GcwDims<D>::KS],
+                                         const ds_uint4_t (&in_lo)[GcwDims<D>::KS], const float* __restrict__ tailp, float oscale,
+                                         float* __restrict__ row, bool valid) {
+    using M = GcwDims<D>;
+    float4_t acc[M::TPC];
+#pragma unroll
+    for (int tl = 0; tl < M::TPC; tl++) {
+        const float4 b = *reinterpret_cast<const float4*>(tailp + 16 * (c * M::TPC + tl) + 4 * g);
+        acc[tl] = (float4_t){b.x, b.y, b.z, b.w};
+    }
+#pragma unroll
+    for (int ks = 0; ks < M::KS; ks++) {
+        ds_uint4_t w[M::TPC][2];
+#pragma unroll
+        for (int tl = 0; tl < M::TPC; tl++)
+#pragma unroll
+            for (int p = 0; p < 2; p++) w[tl][p] = *reinterpret_cast<const ds_uint4_t*>(wb + ((tl * M::KS + ks) * 2 + p) * 1024 + lane * 16);
+#pragma unroll
+        for (int tl = 0; tl < M::TPC; tl++) acc[tl] = DS_MFMA16(w[tl][0], in_hi[ks], acc[tl]);
+#pragma unroll
+        for (int tl = 0; tl < M::TPC; tl++) acc[tl] = DS_MFMA16(w[tl][0], in_lo[ks], acc[tl]);
+#pragma unroll
+        for (int tl = 0; tl < M::TPC; tl++) acc[tl] = DS_MFMA16(w[tl][1], in_hi[ks], acc[tl]);
+    }
+#pragma unroll
+    for (int tl = 0; tl < M::TPC; tl++) {
+        const int col = 16 * (c * M::TPC + tl) + 4 * g;
+        if (col < D && valid) {
+            const float4_t r = acc[tl] * oscale;
+            *reinterpret_cast<float4*>(row + col) = make_float4(r.x, r.y, r.z, r.w);
+        }
+    }
+}
+
+// xout[v] = W relu(pre[v]) + b: stages l = 0..3.  tab: the layer's table; wchunks / tailp: the NEXT layer's product (gcw_pack_layer)
+template <int D>
+__global__ __launch_bounds__(GW_WAVES * 64) void gcw_layer_kernel(const float* __restrict__ x, float* __restrict__ xout,
+                                                                  const int* __restrict__ row_ptr, const int* __restrict__ src,
+                                                                  const uint8_t* __restrict__ ecode, const float* __restrict__ esc,
+                                                                  const int* __restrict__ out_deg, const float* __restrict__ tab,
+                                                                  const uint8_t* __restrict__ wchunks, const float* __restrict__ tailp,
+                                                                  int n_tot, int* __restrict__ range_flag) {
+    using M = GcwDims<D>;
+    // three DISTINCT LDS objects: the DMA into one weight buffer does not alias the reads of the other, and the table stays
+    __shared__ __attribute__((aligned(16))) char s_tab[M::TAB_BYTES];
+    __shared__ __attribute__((aligned(16))) char s_w0[M::CHUNK_BYTES];  // the even chunks
+    __shared__ __attribute__((aligned(16))) char s_w1[M::CHUNK_BYTES];  // the odd chunks
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int j = lane & 15, g = lane >> 4;
+    const long long node0 = (long long)blockIdx.x * GW_ROWS + wave * 16 + j;
+    const bool valid = node0 < n_tot;
+    const long long node = valid ? node0 : (long long)n_tot - 1;
+
+    gw_issue_pieces<M::TAB_PIECES>(reinterpret_cast<const uint8_t*>(tab), s_tab, M::TAB_PIECES, M::TAB_LAST_LANES, wave, lane);
+    gw_issue_pieces<M::PIECES>(wchunks, s_w0, M::PIECES, 64, wave, lane);  // chunk 0
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+
+    float a[4 * M::Q];
+    gcw_walk<D, true>(x, row_ptr, src, ecode, esc, out_deg, reinterpret_cast<const float*>(s_tab), node, valid, g, a);
+    float vmax = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 4 * M::Q; k += 2) vmax = __builtin_fmaxf(__builtin_fmaxf(vmax, __builtin_fabsf(a[k])), __builtin_fabsf(a[k + 1]));
+    ds_uint4_t in_hi[M::KS], in_lo[M::KS];
+#pragma unroll
+    for (int ks = 0; ks < M::KS; ks++) {
+        DS_SPLIT2(a[8 * ks + 0], a[8 * ks + 1], in_hi[ks].x, in_lo[ks].x);
+        DS_SPLIT2(a[8 * ks + 2], a[8 * ks + 3], in_hi[ks].y, in_lo[ks].y);
+        DS_SPLIT2(a[8 * ks + 4], a[8 * ks + 5], in_hi[ks].z, in_lo[ks].z);
+        DS_SPLIT2(a[8 * ks + 6], a[8 * ks + 7], in_hi[ks].w, in_lo[ks].w);
+    }
+    const float oscale = tailp[M::SCALE_AT];
+    float* const row = xout + (size_t)node * D;
+
+    // ---- the product, weights streamed through LDS (chunk 0 has been resident since the first barrier; nobody has touched s_w1)
+#pragma unroll 1
+    for (int c = 0; c < M::STEPS; c += 2) {
+        gw_issue_pieces<M::PIECES>(wchunks + (size_t)(c + 1) * M::CHUNK_BYTES, s_w1, M::PIECES, 64, wave, lane);
+        gcw_step<D>(s_w0, c, lane, g, in_hi, in_lo, tailp, oscale, row, valid);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's pieces of chunk c + 1 have landed
+        __syncthreads();                                  // everyone's have; everyone is done with s_w0
+        if (c + 2 < M::STEPS) gw_issue_pieces<M::PIECES>(wchunks + (size_t)(c + 2) * M::CHUNK_BYTES, s_w0, M::PIECES, 64, wave, lane);
+        gcw_step<D>(s_w1, c + 1, lane, g, in_hi, in_lo, tailp, oscale, row, valid);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+    }
+    if (__any(!(vmax < 6.0e4f))) {
+        if (lane == 0) atomicOr(range_flag, 1);
+    }
+}
+
+// out[v] = pre_4[v]: stage 4, the walk and the epilogue without ReLU and without a product
+template <int D>
+__global__ __launch_bounds__(GW_WAVES * 64) void gcw_final_kernel(const float* __restrict__ x, float* __restrict__ out,
+                                                                  const int* __restrict__ row_ptr, const int* __restrict__ src,
+                                                                  const uint8_t* __restrict__ ecode, const float* __restrict__ esc,
+                                                                  const int* __restrict__ out_deg, const float* __restrict__ tab, int n_tot) {
+    using M = GcwDims<D>;
+    __shared__ __attribute__((aligned(16))) char s_tab[M::TAB_BYTES];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int j = lane & 15, g = lane >> 4;
+    const long long node0 = (long long)blockIdx.x * GW_ROWS + wave * 16 + j;
+    const bool valid = node0 < n_tot;
+    const long long node = valid ? node0 : (long long)n_tot - 1;
+    gw_issue_pieces<M::TAB_PIECES>(reinterpret_cast<const uint8_t*>(tab), s_tab, M::TAB_PIECES, M::TAB_LAST_LANES, wave, lane);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    float a[4 * M::Q];
+    gcw_walk<D, false>(x, row_ptr, src, ecode, esc, out_deg, reinterpret_cast<const float*>(s_tab), node, valid, g, a);
+    if (valid) {
+        float* row = out + (size_t)node * D + 4 * g;
+#pragma unroll
+        for (int q = 0; q < M::Q; q++)
+            if (16 * q + 4 * g < D) *reinterpret_cast<float4*>(row + 16 * q) = make_float4(a[4 * q + 0], a[4 * q + 1], a[4 * q + 2], a[4 * q + 3]);
+    }
+}
+
+// ---------------------------------------------------------------- the exact (fp32) form of a stage: the same sums, plain FMAs
+// a[v] = act(BN(m[v] + relu(x[v] + root) / (deg(v) + 1))), m[v] in CSR order; one lane per (node, float4 piece); tab in global memory
+template <int D>
+__global__ __launch_bounds__(256) void gcw_aggregate_kernel(const float* __restrict__ x, float* __restrict__ a, const int* __restrict__ row_ptr,
+                                                            const int* __restrict__ src, const uint8_t* __restrict__ ecode,
+                                                            const float* __restrict__ esc, const int* __restrict__ out_deg,
+                                                            const float* __restrict__ tab, int n_tot, int relu_out) {
+    using M = GcwDims<D>;
+    constexpr int C = M::C;
+    const float4* const ep = reinterpret_cast<const float4*>(tab + M::ECOMB_FLOATS);
+    const long long items = (long long)n_tot * C;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < items; i += (long long)gridDim.x * 256) {
+        const long long v = i / C;
+        const int c = (int)(i - v * C);
+        const int dv = out_deg[v];
+        const float dinv_v = dv > 0 ? 1.0f / sqrtf((float)(dv + 1)) : 0.0f;
+        const float idp1 = 1.0f / (float)(dv + 1);
+        float4 m = make_float4(0.f, 0.f, 0.f, 0.f);
+        const int e1 = row_ptr[v + 1];
+        for (int e = row_ptr[v]; e < e1; e++) {
+            const float norm = esc[e] * dinv_v;
+            const float4 xv = reinterpret_cast<const float4*>(x)[(size_t)src[e] * C + c];
+            const float4 w = reinterpret_cast<const float4*>(tab)[(size_t)ecode[e] * C + c];
+            m.x = __builtin_fmaf(norm, relu1(w.x + xv.x), m.x); m.y = __builtin_fmaf(norm, relu1(w.y + xv.y), m.y);
+            m.z = __builtin_fmaf(norm, relu1(w.z + xv.z), m.z); m.w = __builtin_fmaf(norm, relu1(w.w + xv.w), m.w);
+        }
+        const float4 xs = reinterpret_cast<const float4*>(x)[(size_t)v * C + c];
+        const float4 rt = ep[c], sc = ep[C + c], sh = ep[2 * C + c];
+        float4 r;
+        r.x = __builtin_fmaf(__builtin_fmaf(relu1(xs.x + rt.x), idp1, m.x), sc.x, sh.x);
+        r.y = __builtin_fmaf(__builtin_fmaf(relu1(xs.y + rt.y), idp1, m.y), sc.y, sh.y);
+        r.z = __builtin_fmaf(__builtin_fmaf(relu1(xs.z + rt.z), idp1, m.z), sc.z, sh.z);
+        r.w = __builtin_fmaf(__builtin_fmaf(relu1(xs.w + rt.w), idp1, m.w), sc.w, sh.w);
+        if (relu_out) { r.x = relu1(r.x); r.y = relu1(r.y); r.z = relu1(r.z); r.w = relu1(r.w); }
+        reinterpret_cast<float4*>(a)[(size_t)v * C + c] = r;
+    }
+}
+
+// w [D][D] (row-major [o][k], host), b [D] -> LAYER_BYTES of chunks and TAIL_FLOATS floats
+template <int D>
+void gcw_pack_layer(const float* w, const float* b, uint8_t* out, float* tail) {
+    using M = GcwDims<D>;
+    std::memset(out, 0, M::LAYER_BYTES);
+    const float s = gw_pow2_scale(w, (size_t)D * D);
+    for (int t = 0; t < M::T; t++) {
+        uint8_t* tile = out + (size_t)(t / M::TPC) * M::CHUNK_BYTES + (size_t)(t % M::TPC) * M::TILE_BYTES;
+        for (int lane = 0; lane < 64; lane++) {
+            const int i = lane & 15, gk = lane >> 4, o = 16 * t + i;
+            for (int ks = 0; ks < M::KS; ks++)
+                for (int e = 0; e < 8; e++) {
+                    const int k = 16 * (2 * ks + (e >> 2)) + 4 * gk + (e & 3);
+                    gw_put_split(tile + (size_t)(ks * 2) * 1024, lane, e, (o < D && k < D) ? w[(size_t)o * D + k] * s : 0.0f);
+                }
+        }
+    }
+    for (int i = 0; i < M::TAIL_FLOATS; i++) tail[i] = 0.0f;
+    for (int o = 0; o < D; o++) tail[o] = b[o] * s;
+    tail[M::SCALE_AT] = 1.0f / s;
+}
+
+template <int D>
+class GcnWideModel : public Model {
+    using M = GcwDims<D>;
+
+public:
+    ~GcnWideModel() override { free_all(); }
+    int emb_dim() const override { return D; }
+    int scratch_dim() const override { return D; }
+    bool has_edge_attr() const override { return true; }
+    int num_weight_tensors() const override { return 11; }
+    bool weights_ready() const override { return ready_; }
+    void set_exact(bool on) override { exact_ = on; }
+    int set_num_tasks(int t) override {
+        if (t < 1) return 8;
+        if (t != num_tasks_) ready_ = false;  // graph_pred_weights / bias change shape: set the weights again
+        num_tasks_ = t;
+        return 0;
+    }
+
+    // host tensors, GcnModel's with D for 100: node_emb[173][D], edge_emb[5][13][D], convs_weight[5][D][D], convs_bias[5][D], root_emb[5][D],
+    // bn_weight/bias/mean/var[5][D], pred_w[NUM_TASK][D], pred_b[NUM_TASK]
+    int set_weights(const float* const* t) override {
+        const float *nemb = t[0], *eemb = t[1], *cw = t[2], *cb = t[3], *root = t[4], *bnw = t[5], *bnb = t[6], *bnm = t[7], *bnv = t[8],
+                    *pw = t[9], *pb = t[10];
+        std::vector<float> v_pw(pw, pw + (size_t)num_tasks_ * D), v_pb(pb, pb + num_tasks_), v_b0(cb, cb + D);
+        std::vector<float> tab((size_t)GCW_L * M::TAB_FLOATS);
+        std::vector<float> wt((size_t)(GCW_L - 1) * D * D), v_b(cb + D, cb + (size_t)GCW_L * D);  // the exact form: [K][O] copies of W_1..W_4
+        std::vector<uint8_t> chunks((size_t)(GCW_L - 1) * M::LAYER_BYTES);
+        std::vector<float> tails((size_t)(GCW_L - 1) * M::TAIL_FLOATS);
+        static const int ed_off[3] = {0, 5, 11};
+        for (int l = 0; l < GCW_L; l++) {
+            const float* E = eemb + (size_t)l * ED_FEATURE_PER_LAYER * D;
+            float* tl = &tab[(size_t)l * M::TAB_FLOATS];
+            for (int a0 = 0; a0 < 5; a0++)
+                for (int a1 = 0; a1 < 6; a1++)
+                    for (int a2 = 0; a2 < 2; a2++)
+                        for (int d = 0; d < D; d++) {
+                            float s = 0.0f;  // the order of GcnModel::set_weights
+                            s += E[(ed_off[0] + a0) * D + d];
+                            s += E[(ed_off[1] + a1) * D + d];
+                            s += E[(ed_off[2] + a2) * D + d];
+                            tl[(size_t)((a0 * 6 + a1) * 2 + a2) * D + d] = s;
+                        }
+            float* e = tl + M::ECOMB_FLOATS;
+            for (int d = 0; d < D; d++) {
+                const double sv = std::sqrt((double)(bnv[l * D + d] + 1.0f / 1024.0f));
+                const double scale = (double)bnw[l * D + d] / sv;
+                e[0 * D + d] = root[l * D + d];
+                e[1 * D + d] = (float)scale;
+                e[2 * D + d] = (float)((double)bnb[l * D + d] - (double)bnm[l * D + d] * scale);
+            }
+            if (l == 0) continue;
+            const float* W = cw + (size_t)l * D * D;
+            for (int o = 0; o < D; o++)
+                for (int k = 0; k < D; k++) wt[(size_t)(l - 1) * D * D + (size_t)k * D + o] = W[(size_t)o * D + k];
+            gcw_pack_layer<D>(W, cb + (size_t)l * D, chunks.data() + (size_t)(l - 1) * M::LAYER_BYTES, tails.data() + (size_t)(l - 1) * M::TAIL_FLOATS);
+        }
+        // x_0 = b_0 + W_0 (sum_k NodeEmb[off_k + f_k]) = sum_k (W_0 NodeEmb[off_k + f_k]) + b_0: W_0 applied to the table once, in double
+        // (GcnModel::set_weights); b_0 is the encoder's tenth row
+        std::vector<float> proj((size_t)ND_FEATURE_TOTAL * D);
+        for (int r = 0; r < ND_FEATURE_TOTAL; r++)
+            for (int o = 0; o < D; o++) {
+                double acc = 0.0;
+                for (int i = 0; i < D; i++) acc += (double)cw[(size_t)o * D + i] * (double)nemb[(size_t)r * D + i];
+                proj[(size_t)r * D + o] = (float)acc;
+            }
+        int rc;
+        if ((rc = upload(&d_chunks_, chunks))) return rc;
+        if ((rc = upload(&d_tails_, tails))) return rc;
+        if ((rc = upload(&d_tab_, tab))) return rc;
+        if ((rc = upload(&d_proj_, proj))) return rc;
+        if ((rc = upload(&d_b0_, v_b0))) return rc;
+        if ((rc = upload(&d_wt_, wt))) return rc;
+        if ((rc = upload(&d_b_, v_b))) return rc;
+        if ((rc = upload(&d_pw_, v_pw))) return rc;
+        if ((rc = upload(&d_pb_, v_pb))) return rc;
+        ready_ = true;
+        return 0;
+    }
+
+    // the reference's one file (GCN/src/host_load.cc) with this width in place of 100: node table at 0, layer l at 173 D + l (D^2 + 15 D)
+    // (W, b, root, the 13 edge rows), BatchNorm l at 173 D + 5 (D^2 + 15 D) + l (4 D + 1), the head behind the fifth
+    int load_weights_dir(const char* dir) override {
+        const std::string name = "gcn_ep1_dim" + std::to_string(D) + ".weights.all.bin";
+        const char* f = name.c_str();
+        const size_t d = D, layer = d * d + 15 * d, bn0 = ND_FEATURE_TOTAL * d + GCW_L * layer, head = bn0 + GCW_L * (4 * d + 1);
+        std::vector<float> nemb(ND_FEATURE_TOTAL * d), eemb(GCW_L * ED_FEATURE_PER_LAYER * d), cw(GCW_L * d * d), cb(GCW_L * d), root(GCW_L * d),
+            bnw(GCW_L * d), bnb(GCW_L * d), bnm(GCW_L * d), bnv(GCW_L * d), pw((size_t)num_tasks_ * d), pb(num_tasks_);
+        int rc;
+        if ((rc = read_floats(dir, f, 0, nemb.size(), nemb.data()))) return rc;
+        for (int l = 0; l < GCW_L; l++) {
+            const size_t base = ND_FEATURE_TOTAL * d + layer * (size_t)l;
+            if ((rc = read_floats(dir, f, base, d * d, &cw[(size_t)l * d * d]))) return rc;
+            if ((rc = read_floats(dir, f, base + d * d, d, &cb[l * d]))) return rc;
+            if ((rc = read_floats(dir, f, base + d * d + d, d, &root[l * d]))) return rc;
+            if ((rc = read_floats(dir, f, base + d * d + 2 * d, ED_FEATURE_PER_LAYER * d, &eemb[(size_t)l * ED_FEATURE_PER_LAYER * d]))) return rc;
+            const size_t bn = bn0 + (4 * d + 1) * (size_t)l;  // 4 x D floats + one skipped counter per layer
+            if ((rc = read_floats(dir, f, bn, d, &bnw[l * d]))) return rc;
+            if ((rc = read_floats(dir, f, bn + d, d, &bnb[l * d]))) return rc;
+            if ((rc = read_floats(dir, f, bn + 2 * d, d, &bnm[l * d]))) return rc;
+            if ((rc = read_floats(dir, f, bn + 3 * d, d, &bnv[l * d]))) return rc;
+        }
+        if ((rc = read_floats(dir, f, head, pw.size(), pw.data()))) return rc;
+        if ((rc = read_floats(dir, f, head + pw.size(), pb.size(), pb.data()))) return rc;
+        const float* t[11] = {nemb.data(), eemb.data(), cw.data(), cb.data(), root.data(), bnw.data(), bnb.data(), bnm.data(), bnv.data(), pw.data(), pb.data()};
+        return set_weights(t);
+    }
+
+    int forward(DeviceBatch& db, Profiler& prof, hipStream_t s) override {
+        const int n = db.b.n_tot;
+        if (n <= 0) return 0;
+        if (db.b.e_tot > 0) {  // dinv[src_e] per CSR entry, once per pass, as on the 100-wide per-layer path
+            if (int rc = esc_.reserve((size_t)db.b.e_tot)) return rc;
+            ProfScope p(prof, "edge_scalar", s);
+            GcwScalarPolicy::Params prm{db.csr.out_deg};
+            edge_scalar_kernel<GcwScalarPolicy><<<grid_for(db.b.e_tot, 256, 256 * 8), 256, 0, s>>>(prm, db.csr.src, esc_.p, db.b.e_tot);
+        }
+        {
+            ProfScope p(prof, "atom_encoder", s);  // x_0: nine rows of the projected table and b_0
+            gw_atom_encoder_vn_kernel<D><<<grid_for((long long)n * M::C, 256, 256 * 8), 256, 0, s>>>(db.b.node_feature, d_proj_, db.h[0], n, db.csr.err, d_b0_);
+        }
+        int cur = 0;
+        for (int l = 0; l < GCW_L; l++) {
+            const bool last = l == GCW_L - 1;
+            // (node embeddings: the last stage writes pre_4 straight into the caller's buffer, and the readout reads it there)
+            float* const hn = (last && db.node_emb) ? db.node_emb : db.h[cur ^ 1];
+            const float* tab = d_tab_ + (size_t)l * M::TAB_FLOATS;
+            if (!exact_) {
+                ProfScope p(prof, "gcn_wide_layer", s);
+                const int grid = (int)ceil_div_ll(n, GW_ROWS);
+                if (!last)
+                    gcw_layer_kernel<D><<<grid, GW_WAVES * 64, 0, s>>>(db.h[cur], hn, db.csr.row_ptr, db.csr.src, db.csr.ecode, esc_.p, db.csr.out_deg, tab,
+                                                                       d_chunks_ + (size_t)l * M::LAYER_BYTES, d_tails_ + (size_t)l * M::TAIL_FLOATS, n,
+                                                                       db.range_flag);
+                else
+                    gcw_final_kernel<D><<<grid, GW_WAVES * 64, 0, s>>>(db.h[cur], hn, db.csr.row_ptr, db.csr.src, db.csr.ecode, esc_.p, db.csr.out_deg, tab, n);
+            } else {
+                ProfScope p(prof, "gcn_wide_layer_f32", s);
+                gcw_aggregate_kernel<D><<<grid_for((long long)n * M::C, 256, 256 * 8), 256, 0, s>>>(
+                    db.h[cur], last ? hn : db.scratch, db.csr.row_ptr, db.csr.src, db.csr.ecode, esc_.p, db.csr.out_deg, tab, n, last ? 0 : 1);
+                if (!last)
+                    gw_dense_f32_kernel<D, D><<<(int)ceil_div_ll(n, 8), 256, 0, s>>>(db.scratch, d_wt_ + (size_t)l * D * D, d_b_ + (size_t)l * D, hn, n, 0);
+            }
+            cur ^= 1;
+        }
+        db.final_h = cur;
+        db.h_valid = !db.node_emb;
+        const float* const h5 = db.node_emb ? db.node_emb : db.h[cur];
+        // readout: the pooled rows (the caller's graph embeddings when they are on), then the head on them -- every NUM_TASK, every pooling
+        float* pooled = db.emb;
+        if (!pooled) {
+            if (int rc = pooled_.reserve((size_t)db.b.num_graphs * D)) return rc;
+            pooled = pooled_.p;
+        }
+        {
+            ProfScope p(prof, "mean_pool_rows", s);
+            const int grid = (db.b.num_graphs + 3) / 4;
+            if (db.pooling == POOL_OP_SUM) gw_pool_rows_kernel<D, POOL_OP_SUM><<<grid, 256, 0, s>>>(h5, db.b.node_off, pooled, db.b.num_graphs);
+            else if (db.pooling == POOL_OP_MAX) gw_pool_rows_kernel<D, POOL_OP_MAX><<<grid, 256, 0, s>>>(h5, db.b.node_off, pooled, db.b.num_graphs);
+            else gw_pool_rows_kernel<D, POOL_OP_MEAN><<<grid, 256, 0, s>>>(h5, db.b.node_off, pooled, db.b.num_graphs);
+        }
+        {
+            ProfScope p(prof, "pooled_head", s);
+            launch_pooled_head<D>(pooled, d_pw_, d_pb_, db.out, db.b.num_graphs, num_tasks_, s);
+        }
+        if (db.node_logits) {
+            ProfScope p(prof, "node_logits", s);
+            launch_node_logits_rows<D>(h5, d_pw_, d_pb_, db.node_logits, n, num_tasks_, s);
+        }
+        return 0;
+    }
+
+private:
+    void free_all() {
+        float** ptrs[] = {&d_tails_, &d_tab_, &d_proj_, &d_b0_, &d_wt_, &d_b_, &d_pw_, &d_pb_};
+        for (auto p : ptrs)
+            if (*p) { (void)hipFree(*p); *p = nullptr; }
+        if (d_chunks_) { (void)hipFree(d_chunks_); d_chunks_ = nullptr; }
+        esc_.release();
+        pooled_.release();
+    }
+    bool ready_ = false;
+    bool exact_ = false;
+    int num_tasks_ = 1;
+    uint8_t* d_chunks_ = nullptr;  // the weight streams of gcw_layer_kernel: W_1 .. W_4, LAYER_BYTES each
+    float* d_tails_ = nullptr;     // ... and per product b (pre-scaled, padded) and the output scale
+    float* d_tab_ = nullptr;       // per layer: ecomb | root | BN scale | BN shift
+    float *d_proj_ = nullptr, *d_b0_ = nullptr;  // W_0 applied to the node table, and b_0
+    float *d_wt_ = nullptr, *d_b_ = nullptr;     // the exact form's W_1 .. W_4 as [K][O], and b_1 .. b_4
+    float *d_pw_ = nullptr, *d_pb_ = nullptr;
+    GrowBuf esc_;     // [E] dinv[src_e] in CSR order
+    GrowBuf pooled_;  // the pooled rows [G][D] when graph embeddings are off
+};
+
+}  // namespace
+
+Model* make_gcn_wide_model(int emb_dim) {
+    if (emb_dim == 300) return new GcnWideModel<300>();  // FLOWGNN_EMB_DIM_OGB: the one instantiation
+    return nullptr;
+}
+
+}  // namespace fg

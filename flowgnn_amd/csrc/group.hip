@@ -238,6 +238,13 @@ int flowgnn_group_set_emb_dim(flowgnn_group* g, int emb_dim) {
         if (e->emb_dim != emb_dim) g->batch_valid = false;  // (a member that changes its width drops its shard with it)
     return group_each(g, [&](int i) { return flowgnn_set_emb_dim(g->eng[(size_t)i], emb_dim); });
 }
+int flowgnn_group_set_model_emb_dim(flowgnn_group* g, int emb_dim) {
+    if (!g) return FLOWGNN_ERR_ARG;
+    g->err.clear();
+    for (flowgnn_engine* e : g->eng)
+        if (e->emb_dim != emb_dim) g->batch_valid = false;  // (as above)
+    return group_each(g, [&](int i) { return flowgnn_set_model_emb_dim(g->eng[(size_t)i], emb_dim); });
+}
 int flowgnn_group_set_numeric_mode(flowgnn_group* g, int mode) { return group_all(g, [&](flowgnn_engine* e) { return flowgnn_set_numeric_mode(e, mode); }); }
 int flowgnn_group_set_pooling(flowgnn_group* g, int mode) { return group_all(g, [&](flowgnn_engine* e) { return flowgnn_set_pooling(e, mode); }); }
 int flowgnn_group_set_gin_eps(flowgnn_group* g, const float* eps) { return group_all(g, [&](flowgnn_engine* e) { return flowgnn_set_gin_eps(e, eps); }); }

@@ -20,7 +20,8 @@
 //                run OGB's virtual node (flowgnn_set_ogb_virtual_node) -- an exported gin-virtual checkpoint; usually together with --eps
 //                (with --emb-dim 300: gin_ep1_virtualnode_dim300.bin, 1 443 900 floats, through flowgnn_set_ogb_virtual_node_dim);
 //                GCN: the same from gcn_ep1_virtualnode_dim100.bin (flowgnn_set_gcn_virtual_node) -- an exported gcn-virtual checkpoint
-//   --emb-dim    GIN: 300 = OGB's default width (flowgnn_set_emb_dim): the weights directory's dim300 files are read (with --eps,
+//   --emb-dim    GCN: 300 = OGB's default width (flowgnn_set_model_emb_dim), gcn_ep1_dim300.weights.all.bin is read.
+//                GIN: 300 = OGB's default width (flowgnn_set_emb_dim): the weights directory's dim300 files are read (with --eps,
 //                gin_ep1_eps_dim300.bin); 100 (default) = the reference's width
 //   --eig        DGN: directory holding the eigenvector text files g%d.txt                 (default eig, DGN/src/host_load.cc:178)
 //   --compute-eig DGN: compute node_eigen from the graphs on the GPU (flowgnn_laplacian_eigen, on the first engine) and read no --eig DIR
@@ -168,7 +169,8 @@ int main(int argc, char** argv) {
         if (rc) { fprintf(stderr, "--num-tasks %d: %d %s\n", num_tasks, rc, flowgnn_group_last_error(eng)); return EXIT_FAILURE; }
     }
     if (emb_dim != FLOWGNN_EMB_DIM_REFERENCE) {
-        rc = flowgnn_group_set_emb_dim(eng, emb_dim);
+        // GCN's width goes through the call that names no model (flowgnn.h); GIN keeps the call it had
+        rc = mid == FLOWGNN_MODEL_GCN ? flowgnn_group_set_model_emb_dim(eng, emb_dim) : flowgnn_group_set_emb_dim(eng, emb_dim);
         if (rc) { fprintf(stderr, "--emb-dim %d: %d %s\n", emb_dim, rc, flowgnn_group_last_error(eng)); return EXIT_FAILURE; }
     }
     rc = flowgnn_group_load_weights_dir(eng, wdir.c_str());
@@ -195,7 +197,9 @@ int main(int argc, char** argv) {
         const size_t at[6] = {0, D, D + L * H * D, D + L * H * D + L * H, D + 2 * L * H * D + L * H, D + 2 * L * H * D + L * H + L * D};
         std::vector<float> vn(at[5]);
         const std::string path = wdir + (gcn ? "/gcn_ep1_virtualnode_dim100.bin" : "/gin_ep1_virtualnode_dim" + std::to_string(D) + ".bin");
-        if (!read_exact(path, vn, 0, vn.size())) { fprintf(stderr, "--ogb-vn: cannot read %zu floats from %s\n", vn.size(), path.c_str()); return EXIT_FAILURE; }
+        // (GCN at --emb-dim 300 has no such file: the engine refuses the tensors before it reads them, and its text is the answer)
+        const bool refused = gcn && emb_dim != FLOWGNN_EMB_DIM_REFERENCE;
+        if (!refused && !read_exact(path, vn, 0, vn.size())) { fprintf(stderr, "--ogb-vn: cannot read %zu floats from %s\n", vn.size(), path.c_str()); return EXIT_FAILURE; }
         if (wide)
             rc = flowgnn_group_set_ogb_virtual_node_dim(eng, emb_dim, vn.data() + at[0], vn.data() + at[1], vn.data() + at[2], vn.data() + at[3], vn.data() + at[4]);
         else

@@ -450,6 +450,11 @@ class Engine:
         (both have to be set again afterwards)."""
         self._check(self.lib.flowgnn_set_emb_dim(self._h, int(emb_dim)), "flowgnn_set_emb_dim")
 
+    def set_model_emb_dim(self, emb_dim: int):
+        """GIN's or GCN's width (flowgnn.h: flowgnn_set_model_emb_dim): on a GIN engine exactly set_emb_dim, on a GCN engine 100 or
+        300 (OGB's default, gcn_ep1_dim300.weights.all.bin); set before weights and batch (both have to be set again afterwards)."""
+        self._check(self.lib.flowgnn_set_model_emb_dim(self._h, int(emb_dim)), "flowgnn_set_model_emb_dim")
+
     @property
     def emb_dim(self) -> int:
         """The engine's width: what its embeddings, node embeddings and get_h rows are wide (flowgnn.h: flowgnn_emb_dim)."""
@@ -738,6 +743,10 @@ class EngineGroup:
     def set_emb_dim(self, emb_dim: int):
         """GIN's width on every member (flowgnn.h: flowgnn_group_set_emb_dim); weights and batch have to be set again afterwards."""
         self._check(self.lib.flowgnn_group_set_emb_dim(self._h, int(emb_dim)), "flowgnn_group_set_emb_dim")
+
+    def set_model_emb_dim(self, emb_dim: int):
+        """GIN's or GCN's width on every member (flowgnn.h: flowgnn_group_set_model_emb_dim)."""
+        self._check(self.lib.flowgnn_group_set_model_emb_dim(self._h, int(emb_dim)), "flowgnn_group_set_model_emb_dim")
 
     @property
     def emb_dim(self) -> int:

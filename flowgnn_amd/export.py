@@ -186,14 +186,27 @@ def gin_weights_from_ogb_state_dict(sd: Mapping, num_layers: int = 5, eps_tol: f
 
 
 def gcn_weights_from_ogb_state_dict(sd: Mapping, num_layers: int = 5, multi_task: bool = False,
-                                    virtual_node: bool = False) -> Dict[str, np.ndarray]:
+                                    virtual_node: bool = False, emb_dim: int = 100) -> Dict[str, np.ndarray]:
     """OGB `GNN(gnn_type='gcn', ...)` -> the reference's GCN weight set.  BatchNorm stays a separate step in the
     reference (GCN/src/node_embedding.cc:123-138) but with 2^-10 added to the variance instead of torch's 1e-5
     (GCN/src/load_inputs.cc:32): the exported variance is shifted by the difference so that both normalise alike.
     A gcn-virtual state_dict (it has `gnn_node.virtualnode_embedding.weight`) is refused -- the weight set alone is a model nobody
     trained -- unless virtual_node says that the engine will run the virtual node too (gcn_virtual_node_from_ogb_state_dict +
-    flowgnn_set_gcn_virtual_node)."""
+    flowgnn_set_gcn_virtual_node).
+    emb_dim: the width the caller expects, 100 or 300 (OGB's default, for an engine with flowgnn_set_model_emb_dim(300)); a state_dict
+    of another width is refused, and so is gcn-virtual at 300, which the engine does not run."""
     p = "gnn_node"
+    if int(emb_dim) not in _weights.GCN_EMB_DIMS:
+        raise ExportError(f"emb_dim {emb_dim}: the engine runs GCN at emb_dim {_weights.GCN_EMB_DIMS[0]} (the reference's width) and "
+                          f"{_weights.GCN_EMB_DIMS[1]} (OGB's default), no other")
+    emb_dim = int(emb_dim)
+    shapes = _weights.gcn_shapes(emb_dim)
+    if emb_dim != 100:
+        if virtual_node:
+            raise ExportError(f"virtual_node=True at emb_dim {emb_dim}: the engine runs gcn-virtual at emb_dim 100 only")
+        width = int(_get(sd, f"{p}.atom_encoder.atom_embedding_list.0.weight").shape[-1])
+        if width != emb_dim:
+            raise ExportError(f"atom_embedding_list.0.weight is {width} wide and emb_dim is {emb_dim}")
     if VN_KEY in sd and not virtual_node:
         raise ExportError(f"the state_dict has '{VN_KEY}': it is OGB's gcn-virtual, and these weights without its virtual node are "
                           f"a model nobody trained; pass virtual_node=True and give the engine gcn_virtual_node_from_ogb_state_dict(sd) "
@@ -222,8 +235,8 @@ def gcn_weights_from_ogb_state_dict(sd: Mapping, num_layers: int = 5, multi_task
         raise ExportError(f"graph_pred_linear has {pw.shape[0]} tasks; the reference is built with NUM_TASK = 1 (GCN/src/dcl.h): "
                           f"pass multi_task=True for an engine with flowgnn_set_num_tasks({pw.shape[0]})")
     out["graph_pred_weights"], out["graph_pred_bias"] = pw, pb
-    ordered = OrderedDict((k, out[k]) for k in _weights.GCN_SHAPES)
-    return _checked(ordered, _weights.GCN_SHAPES, lambda k, v: _weights._task_shape(k, v, pw.shape[0]))
+    ordered = OrderedDict((k, out[k]) for k in shapes)
+    return _checked(ordered, shapes, lambda k, v: _weights._task_shape(k, v, pw.shape[0]))
 
 
 def _checked(w: Dict[str, np.ndarray], spec: Mapping, shape_of) -> Dict[str, np.ndarray]:
@@ -240,7 +253,7 @@ def _checked(w: Dict[str, np.ndarray], spec: Mapping, shape_of) -> Dict[str, np.
 
 
 def export_weights(model: str, sd: Mapping, directory: str, multi_task: bool = False, keep_eps: bool = False,
-                   virtual_node: bool = False, virtual_node_dim: int = 100) -> Dict[str, np.ndarray]:
+                   virtual_node: bool = False, virtual_node_dim: int = 100, emb_dim: int = 100) -> Dict[str, np.ndarray]:
     """Write the `.bin` file(s) `host` / `flowgnn_load_weights_dir` read for `model` ('GIN', 'GIN-VN' or 'GCN').
     multi_task: keep all rows of the prediction head (the engine then needs flowgnn_set_num_tasks(rows) before loading).
     keep_eps (GIN, GIN-VN): a trained eps is not refused; the eps file holds the trained values, for `host --eps` /
@@ -250,8 +263,13 @@ def export_weights(model: str, sd: Mapping, directory: str, multi_task: bool = F
     others, for `host GIN --ogb-vn` / Engine.load_weights_dir(dir, virtual_node=True) to apply (flowgnn_set_ogb_virtual_node).
     virtual_node_dim (GIN): 300 for a 300-wide gin-virtual state_dict, whose virtual node goes into gin_ep1_virtualnode_dim300.bin
     (flowgnn_set_ogb_virtual_node_dim; `host GIN --emb-dim 300 --eps --ogb-vn`); without it such a state_dict is refused.
-    virtual_node (GCN): likewise OGB's gcn-virtual, into gcn_ep1_virtualnode_dim100.bin (flowgnn_set_gcn_virtual_node)."""
+    virtual_node (GCN): likewise OGB's gcn-virtual, into gcn_ep1_virtualnode_dim100.bin (flowgnn_set_gcn_virtual_node).
+    emb_dim (GCN): 300 for a 300-wide gcn state_dict, which goes into gcn_ep1_dim300.weights.all.bin, for an engine with
+    flowgnn_set_model_emb_dim(300) / `host GCN --emb-dim 300`; without it such a state_dict is refused.  (GIN reads its width off the
+    state_dict and takes no emb_dim.)"""
     m = model.upper()
+    if int(emb_dim) != 100 and m != "GCN":
+        raise ExportError(f"emb_dim={emb_dim} is GCN's keyword; {model} reads its width off the state_dict")
     if _vn_dim(virtual_node_dim) != 100 and m != "GIN":
         raise ExportError(f"virtual_node_dim={virtual_node_dim} is GIN's (flowgnn_set_ogb_virtual_node_dim); {model} has the 100-wide virtual node only")
     if virtual_node and m not in ("GIN", "GCN"):
@@ -264,7 +282,7 @@ def export_weights(model: str, sd: Mapping, directory: str, multi_task: bool = F
         if virtual_node:
             _weights.save_gin_virtual_node(vn, directory)
     elif m == "GCN":
-        w = gcn_weights_from_ogb_state_dict(sd, multi_task=multi_task, virtual_node=virtual_node)
+        w = gcn_weights_from_ogb_state_dict(sd, multi_task=multi_task, virtual_node=virtual_node, emb_dim=emb_dim)
         _weights.save_gcn_weights(w, directory)
         if virtual_node:
             _weights.save_gcn_virtual_node(gcn_virtual_node_from_ogb_state_dict(sd), directory)

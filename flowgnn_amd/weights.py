@@ -228,31 +228,61 @@ GCN_SHAPES = OrderedDict([
     ("bn_weight", (5, 100)), ("bn_bias", (5, 100)), ("bn_mean", (5, 100)), ("bn_var", (5, 100)),
     ("graph_pred_weights", (1, 100)), ("graph_pred_bias", (1,)),
 ])
+GCN_EMB_DIMS = (100, 300)  # the reference's width, and OGB's default (flowgnn_set_model_emb_dim: FLOWGNN_EMB_DIM_REFERENCE / _OGB)
 
 
-def _gcn_offsets(num_tasks: int = 1):
-    """(name, layer or None) -> float offset in the .all.bin (GCN/src/host_load.cc:34-170); the head is the last tensor pair of
-    the flattened state_dict: weight [NUM_TASK][100] at 76805, bias [NUM_TASK] right behind it (76905 for NUM_TASK = 1)."""
-    off = {("node_embedding_weight", None): 0, ("graph_pred_weights", None): 76805, ("graph_pred_bias", None): 76805 + 100 * num_tasks}
+def _gcn_dim(emb_dim) -> int:
+    d = int(emb_dim)
+    if d not in GCN_EMB_DIMS:
+        raise ValueError(f"GCN: emb_dim {emb_dim} is not one of {GCN_EMB_DIMS}")
+    return d
+
+
+def gcn_file(emb_dim: int = 100) -> str:
+    """gcn_ep1_dim<emb_dim>.weights.all.bin: the reference's one file, with D for 100 in every offset."""
+    return GCN_FILE.replace("dim100", f"dim{_gcn_dim(emb_dim)}")
+
+
+def gcn_shapes(emb_dim: int = 100):
+    """GCN_SHAPES at width emb_dim: 100 -> D."""
+    d = _gcn_dim(emb_dim)
+    return OrderedDict((k, tuple(d if x == 100 else x for x in shp)) for k, shp in GCN_SHAPES.items())
+
+
+def gcn_emb_dim_of(w) -> int:
+    """The width of a GCN weight set: the node table's second dimension."""
+    return int(np.asarray(w["node_embedding_weight"]).shape[-1])
+
+
+def _gcn_offsets(num_tasks: int = 1, emb_dim: int = 100):
+    """(name, layer or None) -> float offset in the .all.bin (GCN/src/host_load.cc:34-170, D for 100): node table at 0, layer l at
+    173 D + l (D^2 + 15 D), BatchNorm l at 173 D + 5 (D^2 + 15 D) + l (4 D + 1); the head is the last tensor pair of the flattened
+    state_dict: weight [NUM_TASK][D] at 173 D + 5 (D^2 + 15 D) + 5 (4 D + 1), bias [NUM_TASK] right behind it.  At D = 100 these are
+    17300, 11500, 74800 and 76805."""
+    d = int(emb_dim)
+    layer = d * d + 15 * d
+    bn0 = 173 * d + 5 * layer
+    head = bn0 + 5 * (4 * d + 1)
+    off = {("node_embedding_weight", None): 0, ("graph_pred_weights", None): head, ("graph_pred_bias", None): head + d * num_tasks}
     for l in range(5):
-        base = 17300 + 11500 * l
+        base = 173 * d + layer * l
         off[("convs_weight", l)] = base
-        off[("convs_bias", l)] = base + 10000
-        off[("convs_root_emb_weight", l)] = base + 10100
-        off[("edge_embedding_weight", l)] = base + 10200
-        bn = 74800 + 401 * l  # 4 x 100 floats, then one skipped counter (num_batches_tracked)
+        off[("convs_bias", l)] = base + d * d
+        off[("convs_root_emb_weight", l)] = base + d * d + d
+        off[("edge_embedding_weight", l)] = base + d * d + 2 * d
+        bn = bn0 + (4 * d + 1) * l  # 4 x D floats, then one skipped counter (num_batches_tracked)
         off[("bn_weight", l)] = bn
-        off[("bn_bias", l)] = bn + 100
-        off[("bn_mean", l)] = bn + 200
-        off[("bn_var", l)] = bn + 300
+        off[("bn_bias", l)] = bn + d
+        off[("bn_mean", l)] = bn + 2 * d
+        off[("bn_var", l)] = bn + 3 * d
     return off
 
 
-def load_gcn_weights(directory: str, num_tasks: int = 1) -> Dict[str, np.ndarray]:
-    path = os.path.join(directory, GCN_FILE)
-    off = _gcn_offsets(num_tasks)
+def load_gcn_weights(directory: str, num_tasks: int = 1, emb_dim: int = 100) -> Dict[str, np.ndarray]:
+    path = os.path.join(directory, gcn_file(emb_dim))
+    off = _gcn_offsets(num_tasks, emb_dim)
     w = OrderedDict()
-    for k, shp in GCN_SHAPES.items():
+    for k, shp in gcn_shapes(emb_dim).items():
         if (k, None) in off:
             w[k] = _read(path, _task_shape(k, shp, num_tasks), off[(k, None)])
         else:
@@ -260,28 +290,36 @@ def load_gcn_weights(directory: str, num_tasks: int = 1) -> Dict[str, np.ndarray
     return w
 
 
-def save_gcn_weights(w: Dict[str, np.ndarray], directory: str) -> None:
+def save_gcn_weights(w: Dict[str, np.ndarray], directory: str, emb_dim=None) -> None:
+    """emb_dim: None = the arrays' own width (which names the file); a number must agree with it."""
+    d = gcn_emb_dim_of(w)
+    if emb_dim is not None and int(emb_dim) != d:
+        raise ValueError(f"GCN: the tensors are {d} wide, emb_dim says {emb_dim}")
     os.makedirs(directory, exist_ok=True)
     tasks = int(np.asarray(w["graph_pred_bias"]).size)
-    buf = np.zeros(76805 + 101 * tasks, dtype="<f4")
-    off = _gcn_offsets(tasks)
-    for k, shp in GCN_SHAPES.items():
+    off = _gcn_offsets(tasks, d)
+    buf = np.zeros(off[("graph_pred_weights", None)] + (d + 1) * tasks, dtype="<f4")
+    for k, shp in gcn_shapes(d).items():
         a = np.asarray(w[k], dtype=np.float32).reshape(_task_shape(k, shp, tasks))
         if (k, None) in off:
             buf[off[(k, None)]:off[(k, None)] + a.size] = a.ravel()
         else:
             for l in range(5):
                 buf[off[(k, l)]:off[(k, l)] + a[l].size] = a[l].ravel()
-    buf.tofile(os.path.join(directory, GCN_FILE))
+    buf.tofile(os.path.join(directory, gcn_file(d)))
 
 
-def synth_gcn_weights(seed: int = 7, num_tasks: int = 1) -> Dict[str, np.ndarray]:
+def synth_gcn_weights(seed: int = 7, num_tasks: int = 1, emb_dim: int = 100) -> Dict[str, np.ndarray]:
+    """emb_dim 300: the same scales at OGB's default width, convs_weight shrunk by sqrt(100 / emb_dim) so that the activations keep
+    the size they have at 100 (at 100 the values are what they always were)."""
     rng = np.random.default_rng(seed)
     scale = {"node_embedding_weight": 0.11, "edge_embedding_weight": 0.14, "convs_weight": 0.09, "convs_bias": 0.1,
              "convs_root_emb_weight": 0.3, "bn_weight": 0.2, "bn_bias": 0.2, "bn_mean": 0.3,
              "graph_pred_weights": 0.15, "graph_pred_bias": 0.12}
+    if emb_dim != 100:
+        scale["convs_weight"] = scale["convs_weight"] * float(np.sqrt(100.0 / emb_dim))
     w = OrderedDict()
-    for k, shp in GCN_SHAPES.items():
+    for k, shp in gcn_shapes(emb_dim).items():
         shp = _task_shape(k, shp, num_tasks)
         if k == "bn_var":
             w[k] = rng.uniform(0.3, 1.5, shp).astype(np.float32)

@@ -512,7 +512,7 @@ int flowgnn_num_tasks(const flowgnn_engine* e);
  * on kernels of its own, one launch per layer: split-f16 MFMA products with the fp32 re-run of flowgnn_exact_reruns.
  * Call it before setting weights and batch (both must be set again afterwards: weights set before are dropped); drops a recorded
  * launch sequence; setting the width the engine has is a no-op.  FLOWGNN_MODEL_GIN only: every other model, GIN-VN included, returns
- * FLOWGNN_ERR_UNSUPPORTED.  At 300, FLOWGNN_NUMERIC_Q6_10 / FLOWGNN_NUMERIC_F16, flowgnn_set_ogb_virtual_node (its tensors are 100
+ * FLOWGNN_ERR_UNSUPPORTED (GCN's width goes through flowgnn_set_model_emb_dim below, and the error text says so).  At 300, FLOWGNN_NUMERIC_Q6_10 / FLOWGNN_NUMERIC_F16, flowgnn_set_ogb_virtual_node (its tensors are 100
  * wide; 300-wide ones go through flowgnn_set_ogb_virtual_node_dim) and flowgnn_run_aggregation_only / flowgnn_get_aggregate return FLOWGNN_ERR_UNSUPPORTED, and so does this call while one
  * of the first three is on.  A width other than the two: FLOWGNN_ERR_ARG.  flowgnn_embedding_dim(model) keeps answering for the
  * model's default width; flowgnn_emb_dim(e) is the engine's (-1 for a null handle).  The <M>_compute_graphs entry points have no
@@ -522,6 +522,26 @@ int flowgnn_num_tasks(const flowgnn_engine* e);
 #define FLOWGNN_EMB_DIM_OGB       300
 int flowgnn_set_emb_dim(flowgnn_engine* e, int emb_dim);   /* 100 (default) or 300 */
 int flowgnn_emb_dim(const flowgnn_engine* e);              /* -1 for a null handle */
+
+/*
+ * The width of GIN or GCN: the call that names no model.  On a GIN engine it is exactly flowgnn_set_emb_dim (the same code path, state
+ * and bits).  On a GCN engine it chooses between the reference's width and OGB's default, the width of a GNN(gnn_type='gcn')
+ * checkpoint trained with OGB's own script: at FLOWGNN_EMB_DIM_OGB the eleven GCN tensors are node_emb [173][300], edge_emb
+ * [5][13][300], convs_weight [5][300][300], convs_bias / root_emb / bn_weight / bn_bias / bn_mean / bn_var [5][300], pred_w
+ * [NUM_TASK][300], pred_b [NUM_TASK]; flowgnn_load_weights_dir reads gcn_ep1_dim300.weights.all.bin, the reference's one file with
+ * 300 for 100 in every offset; embeddings, node embeddings and flowgnn_get_h (the rows the readout pools) are 300 wide.  The width
+ * runs on kernels of its own (gcn_wide.hip): one fused launch per layer with split-f16 MFMA products and the fp32
+ * re-run of flowgnn_exact_reruns.  NUM_TASK, the three poolings, graph embeddings, node embeddings, node logits, host and device
+ * batches and groups work as at 100.  flowgnn_set_option values that choose among the 100-wide GCN paths (gcn_resident, gcn_binpack,
+ * gcn_tile_build, gcn_unfused, gcn_mfma) are accepted and have no effect at 300.
+ * The same sequence as flowgnn_set_emb_dim: weights and batch must be set again after a change, and the width the engine has is a
+ * no-op.  Any other model: FLOWGNN_ERR_UNSUPPORTED; a width other than the two: FLOWGNN_ERR_ARG.  On a GCN engine at 300,
+ * FLOWGNN_NUMERIC_Q6_10, flowgnn_set_gcn_virtual_node with tensors (they are 100 wide, and gcn-virtual has no 300-wide form; all five
+ * NULL stays accepted), flowgnn_run_aggregation_only and flowgnn_get_aggregate return FLOWGNN_ERR_UNSUPPORTED, and so does this call
+ * while the fixed-point mode or GCN's virtual node is on.  flowgnn_set_emb_dim on a GCN engine stays FLOWGNN_ERR_UNSUPPORTED and
+ * names this call.  flowgnn_embedding_dim(FLOWGNN_MODEL_GCN) stays 100.
+ */
+int flowgnn_set_model_emb_dim(flowgnn_engine* e, int emb_dim);   /* GIN, GCN: 100 (default) or 300 */
 
 /*
  * Numeric mode of the engine.  FLOWGNN_NUMERIC_F32 (default): fp32 storage and accumulation.
@@ -785,6 +805,7 @@ int flowgnn_group_load_weights_dir(flowgnn_group* g, const char* dir);
 int flowgnn_group_set_option(flowgnn_group* g, const char* key, double value);
 int flowgnn_group_set_num_tasks(flowgnn_group* g, int num_tasks);
 int flowgnn_group_set_emb_dim(flowgnn_group* g, int emb_dim);
+int flowgnn_group_set_model_emb_dim(flowgnn_group* g, int emb_dim);
 int flowgnn_group_set_numeric_mode(flowgnn_group* g, int mode);
 int flowgnn_group_set_pooling(flowgnn_group* g, int mode);
 int flowgnn_group_set_gin_eps(flowgnn_group* g, const float* eps);
