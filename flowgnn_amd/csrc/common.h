@@ -234,8 +234,8 @@ public:
     // (E [D], w1 [4][2D][D], b1 [4][2D], w2 [4][D][2D], b2 [4][D], D = emb_dim()) into it; DeviceBatch::ogb_vn then points at a copy
     virtual size_t ogb_vn_blob_bytes() const { return 0; }
     virtual void ogb_vn_pack(const float*, const float*, const float*, const float*, const float*, void*) const {}
-    // flowgnn_set_gcn_virtual_node: the state (null: off) and the embedding row E [100], which GCN folds into layer 0's bias; the
-    // tensors reach forward() through DeviceBatch::ogb_vn as well
+    // flowgnn_set_gcn_virtual_node / _dim: the state (null: off) and the embedding row E [emb_dim()], which GCN folds into layer 0's
+    // bias; the tensors reach forward() through DeviceBatch::ogb_vn as well (at width 300 in the form of ogb_vn_pack)
     virtual int set_gcn_virtual_node(const float* vn_embedding) { return vn_embedding ? 8 : 0; }
     // rows > 0: flowgnn_set_batch packs whole graphs into tiles of at most rows rows / edges in-edges (DeviceBatch::gtiles)
     virtual void graph_tile_limits(int& rows, int& edges) const { rows = 0; edges = 0; }

@@ -1322,9 +1322,9 @@ static int set_width(flowgnn_engine* e, const char* fn, int emb_dim) {
         }
     }
     if (e->ogb_vn_on) {  // (either direction: the tensors belong to a width -- turn it off, change the width, set it again)
-        e->err = who + "OGB's virtual node is on (" + (gcn ? "flowgnn_set_gcn_virtual_node" : "flowgnn_set_ogb_virtual_node / flowgnn_set_ogb_virtual_node_dim") +
-                 "), and its tensors are " + std::to_string(e->emb_dim) + " wide";
-        if (gcn) e->err += " (gcn-virtual has no 300-wide form)";
+        e->err = who + "OGB's virtual node is on (" + (gcn ? "flowgnn_set_gcn_virtual_node / flowgnn_set_gcn_virtual_node_dim" : "flowgnn_set_ogb_virtual_node / flowgnn_set_ogb_virtual_node_dim") +
+                 "), and its tensors are " + std::to_string(e->emb_dim) + " wide, not " + std::to_string(emb_dim) +
+                 ": turn it off, change the width, set it again";
         return FLOWGNN_ERR_UNSUPPORTED;
     }
     ENGINE_TRY(e, begin_change(e));
@@ -1478,8 +1478,8 @@ int flowgnn_gin_eps(const flowgnn_engine* e, float* eps_out) {
 
 // flowgnn_set_ogb_virtual_node (GIN) and flowgnn_set_gcn_virtual_node (GCN): the same five tensors, the same checks, the same device
 // form (gin_ogbvn.h) and the same engine state -- an engine is one model, so one of the two calls is refused on it.  `fn`: the caller.
-// `dim`: the tensors' width D (hidden width 2 D) -- 100 in the two calls without a width argument; 300 (flowgnn_set_ogb_virtual_node_dim)
-// packs into gin_wide.hip's own device form instead.
+// `dim`: the tensors' width D (hidden width 2 D) -- 100 in the two calls without a width argument; 300 (flowgnn_set_ogb_virtual_node_dim,
+// flowgnn_set_gcn_virtual_node_dim) packs into gin_wide.hip's own device form instead, through the model object of that width.
 static int set_virtual_node(flowgnn_engine* e, const char* fn, const float* vn_embedding, const float* w1, const float* b1, const float* w2,
                             const float* b2, int dim = FLOWGNN_EMB_DIM_REFERENCE) {
     const std::string who = std::string(fn) + ": ";
@@ -1582,10 +1582,36 @@ int flowgnn_set_gcn_virtual_node(flowgnn_engine* e, const float* vn_embedding, c
         return FLOWGNN_ERR_UNSUPPORTED;
     }
     if (off_default_width(e) && (vn_embedding || w1 || b1 || w2 || b2)) {
-        e->err = "flowgnn_set_gcn_virtual_node: the engine's width is 300 (flowgnn_set_model_emb_dim), the virtual node's tensors are 100 wide, and gcn-virtual has no 300-wide form";
+        e->err = "flowgnn_set_gcn_virtual_node: the engine's width is 300 (flowgnn_set_model_emb_dim), and the virtual node's tensors are 100 wide "
+                 "in this call; 300-wide tensors go through flowgnn_set_gcn_virtual_node_dim";
         return FLOWGNN_ERR_UNSUPPORTED;
     }
     return set_virtual_node(e, "flowgnn_set_gcn_virtual_node", vn_embedding, w1, b1, w2, b2);
+}
+
+// The call that carries the width, the mirror of flowgnn_set_ogb_virtual_node_dim.  emb_dim 100 IS the call above (the same state,
+// kernels and bits); 300 is gcn_wide.hip's virtual node.  All five NULL: off, whatever the engine's width.
+int flowgnn_set_gcn_virtual_node_dim(flowgnn_engine* e, int emb_dim, const float* vn_embedding, const float* w1, const float* b1, const float* w2,
+                                     const float* b2) {
+    if (!e) return FLOWGNN_ERR_ARG;
+    if (emb_dim != FLOWGNN_EMB_DIM_REFERENCE && emb_dim != FLOWGNN_EMB_DIM_OGB) {
+        e->err = "flowgnn_set_gcn_virtual_node_dim: emb_dim is " + std::to_string(emb_dim) +
+                 "; the widths are FLOWGNN_EMB_DIM_REFERENCE (100) and FLOWGNN_EMB_DIM_OGB (300)";
+        return FLOWGNN_ERR_ARG;
+    }
+    if (e->model_id != FLOWGNN_MODEL_GCN) {
+        e->err = "flowgnn_set_gcn_virtual_node_dim: this call is OGB's gcn-virtual, for GCN only (GIN: flowgnn_set_ogb_virtual_node_dim)";
+        return FLOWGNN_ERR_UNSUPPORTED;
+    }
+    const bool any = vn_embedding || w1 || b1 || w2 || b2;
+    if (any && emb_dim != e->emb_dim) {
+        e->err = "flowgnn_set_gcn_virtual_node_dim: the tensors are " + std::to_string(emb_dim) + " wide and the engine's width is " +
+                 std::to_string(e->emb_dim) + " (flowgnn_set_model_emb_dim)";
+        return FLOWGNN_ERR_ARG;
+    }
+    if (!any || emb_dim == FLOWGNN_EMB_DIM_REFERENCE)  // off at any width (no tensor is read), or exactly the 100-wide call
+        return set_virtual_node(e, "flowgnn_set_gcn_virtual_node_dim", vn_embedding, w1, b1, w2, b2);
+    return set_virtual_node(e, "flowgnn_set_gcn_virtual_node_dim", vn_embedding, w1, b1, w2, b2, emb_dim);
 }
 
 int flowgnn_gcn_virtual_node(const flowgnn_engine* e) { return e ? (e->ogb_vn_on && e->model_id == FLOWGNN_MODEL_GCN ? 1 : 0) : -1; }

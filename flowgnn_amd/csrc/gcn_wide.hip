@@ -22,13 +22,28 @@
 //   readout    gw_pool_rows_kernel, launch_pooled_head, launch_node_logits_rows, as GinWideModel::forward
 // a beyond the f16 range raises *range_flag; the engine then repeats the pass with set_exact(true): gcw_aggregate_kernel (the same
 // CSR order, the same FMAs, the same epilogue, one lane per node and float4 piece) and gw_dense_f32_kernel<D, D> once per stage.
+//
+// OGB's virtual node at this width (gcn-virtual; flowgnn_set_gcn_virtual_node_dim): the definition of
+// gcn_ogbvn.h with D = 300.  The row the vector is added to and pooled over, a_l = relu(pre_{l-1}), exists in gcw_layer_kernel's
+// registers alone, so the add and the per-graph sums are in that kernel's VN instance (gcw_layer_vn_kernel), as section 4.15 put them
+// into gcn_layer_fused_kernel:
+//   layer 0    vn_0 = E is a constant: b_0' = b_0 + W_0 E on the host, in double -- the encoder's tenth row, no new encoder kernel
+//   t_0        gcw_vn_t0_kernel: sum_v h_0[v] + (n + 1) E from the unprojected table (this path never forms h_0), and node -> graph
+//   s = 0..3   behind the walk a lane adds its pieces of vn_{s+1}[g(node)], in front of the range tracking and the split; s < 3: a
+//              segmented scan along the 16 lanes of a tile, 16 columns at a time, leaves the partial rows of xin_{s+1}, one per
+//              (16-node tile, graph) at slot graph + tile (gcn_ogbvn.h's rule); gcw_vn_t_kernel adds a graph's slots in order and vn
+//   update     gin_wide.hip's gw_vn_update_kernel on the G rows t, its blob and its launcher (gin_wide_vn.h)
+// The exact re-run adds and pools on the scratch rows between gcw_aggregate_kernel and the dense launch (gin_wide.hip's two kernels).
 #include <cmath>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "common.h"
 #include "dense_split.h"
+#include "gcn_ogbvn.h"
+#include "gin_wide_vn.h"
 #include "wide_common.h"
 
 namespace fg {
@@ -186,14 +201,80 @@ __device__ __forceinline__ void gcw_step(const char* wb, int c, int lane, int g,
     }
 }
 
-// xout[v] = W relu(pre[v]) + b: stages l = 0..3.  tab: the layer's table; wchunks / tailp: the NEXT layer's product (gcw_pack_layer)
+// what the VN instance of the layer kernel takes besides the layer's own arguments (GcnVnArgs of gcn_ogbvn.h at this width)
+struct GcwVnArgs {
+    const int* node_graph;  // [N] the graph of every node (gcw_vn_t0_kernel)
+    const float* vn;        // [G][D] vn_{s+1}
+    float* part;            // [(G + n_tiles)][D] partial sums of xin_{s+1}, or null: stage 3, which feeds no update
+};
+struct GcwNoVnArgs {};
+
+// slots of the partial rows: gcn_ogbvn_part_floats's rule (slot = graph + tile) with rows of D floats
+inline size_t gcw_vn_part_floats(int num_graphs, long long n_tot, int d) { return ((size_t)num_graphs + (size_t)((n_tot + 15) / 16)) * (size_t)d; }
+
+// Lane (j, g) holds a[4 q + r], columns 16 q + 4 g + r of node j of 16-node tile `tile`; gi is that node's graph, or -1 for a clamped
+// lane behind the batch's last node (it adds nothing and stores nothing).  a += vn[gi]; with `part`, the column sums of the sum over
+// the lanes of every graph present in the tile go to the partial row of slot gi + tile: gcn_ogbvn_tile_partials's segmented scan
+// (row_shr 1 / 2 / 4 / 8 along the 16 lanes of a row, the graph's last lane stores), run per 16-column piece -- four live values at a
+// time, not 4 Q.  Every cross-lane read is made by every lane of the wave, outside any test that differs between lanes (gcn_ogbvn.h
+// records the bug).  Pieces at or beyond column D are neither added to nor stored: they stay zero.
 template <int D>
-__global__ __launch_bounds__(GW_WAVES * 64) void gcw_layer_kernel(const float* __restrict__ x, float* __restrict__ xout,
-                                                                  const int* __restrict__ row_ptr, const int* __restrict__ src,
-                                                                  const uint8_t* __restrict__ ecode, const float* __restrict__ esc,
-                                                                  const int* __restrict__ out_deg, const float* __restrict__ tab,
-                                                                  const uint8_t* __restrict__ wchunks, const float* __restrict__ tailp,
-                                                                  int n_tot, int* __restrict__ range_flag) {
+__device__ __forceinline__ void gcw_vn_add_partials(float (&a)[4 * GcwDims<D>::Q], const float* __restrict__ vn, int gi, int j, int g,
+                                                    long long tile, float* __restrict__ part) {
+    using M = GcwDims<D>;
+    const size_t gr = (size_t)(gi >= 0 ? gi : 0);
+    const float* const vr = vn + gr * D + 4 * g;
+    const bool take1 = gcn_ogbvn_row_shr<1>(gi, -2) == gi, take2 = gcn_ogbvn_row_shr<2>(gi, -2) == gi;
+    const bool take4 = gcn_ogbvn_row_shr<4>(gi, -2) == gi, take8 = gcn_ogbvn_row_shr<8>(gi, -2) == gi;
+    const int next_gi = gcn_ogbvn_row_shl1(gi, -2);
+    const bool store = gi >= 0 && (j == 15 || next_gi != gi);
+    float* const pr = part ? part + (gr + (size_t)tile) * D + 4 * g : nullptr;  // (formed by every lane, followed by the storing ones alone)
+#pragma unroll
+    for (int q = 0; q < M::T; q++) {
+        const bool in = 16 * q + 16 <= D || 16 * q + 4 * g < D;
+        float4 w = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (gi >= 0 && in) w = *reinterpret_cast<const float4*>(vr + 16 * q);
+        a[4 * q + 0] += w.x; a[4 * q + 1] += w.y; a[4 * q + 2] += w.z; a[4 * q + 3] += w.w;
+        if (part) {  // (uniform over the launch)
+            float s[4];
+#pragma unroll
+            for (int r = 0; r < 4; r++) s[r] = gi >= 0 ? a[4 * q + r] : 0.0f;
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const float y = __builtin_bit_cast(float, gcn_ogbvn_row_shr<1>(__builtin_bit_cast(int, s[r]), 0));
+                s[r] = take1 ? s[r] + y : s[r];
+            }
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const float y = __builtin_bit_cast(float, gcn_ogbvn_row_shr<2>(__builtin_bit_cast(int, s[r]), 0));
+                s[r] = take2 ? s[r] + y : s[r];
+            }
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const float y = __builtin_bit_cast(float, gcn_ogbvn_row_shr<4>(__builtin_bit_cast(int, s[r]), 0));
+                s[r] = take4 ? s[r] + y : s[r];
+            }
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const float y = __builtin_bit_cast(float, gcn_ogbvn_row_shr<8>(__builtin_bit_cast(int, s[r]), 0));
+                s[r] = take8 ? s[r] + y : s[r];
+            }
+            if (store && in) *reinterpret_cast<float4*>(pr + 16 * q) = make_float4(s[0], s[1], s[2], s[3]);
+        }
+    }
+}
+
+// xout[v] = W relu(pre[v]) + b: stages l = 0..3.  tab: the layer's table; wchunks / tailp: the NEXT layer's product (gcw_pack_layer).
+// The body of the layer's two kernels (below); VN is a compile-time constant in each, and without it this compiles to what the one
+// kernel was before the other existed.  VN: xout[v] = W (relu(pre[v]) + vn[g(v)]) + b, and the partial rows (gcw_vn_add_partials).
+template <int D, bool VN>
+__device__ __forceinline__ void gcw_layer_body(const float* __restrict__ x, float* __restrict__ xout,
+                                               const int* __restrict__ row_ptr, const int* __restrict__ src,
+                                               const uint8_t* __restrict__ ecode, const float* __restrict__ esc,
+                                               const int* __restrict__ out_deg, const float* __restrict__ tab,
+                                               const uint8_t* __restrict__ wchunks, const float* __restrict__ tailp,
+                                               int n_tot, int* __restrict__ range_flag,
+                                               typename std::conditional<VN, GcwVnArgs, GcwNoVnArgs>::type vna) {
     using M = GcwDims<D>;
     // three DISTINCT LDS objects: the DMA into one weight buffer does not alias the reads of the other, and the table stays
     __shared__ __attribute__((aligned(16))) char s_tab[M::TAB_BYTES];
@@ -213,6 +294,10 @@ __global__ __launch_bounds__(GW_WAVES * 64) void gcw_layer_kernel(const float* _
 
     float a[4 * M::Q];
     gcw_walk<D, true>(x, row_ptr, src, ecode, esc, out_deg, reinterpret_cast<const float*>(s_tab), node, valid, g, a);
+    if constexpr (VN) {
+        const int gi = valid ? vna.node_graph[node] : -1;
+        gcw_vn_add_partials<D>(a, vna.vn, gi, j, g, (long long)blockIdx.x * GW_WAVES + wave, vna.part);
+    }
     float vmax = 0.0f;
 #pragma unroll
     for (int k = 0; k < 4 * M::Q; k += 2) vmax = __builtin_fmaxf(__builtin_fmaxf(vmax, __builtin_fabsf(a[k])), __builtin_fabsf(a[k + 1]));
@@ -241,6 +326,84 @@ __global__ __launch_bounds__(GW_WAVES * 64) void gcw_layer_kernel(const float* _
     }
     if (__any(!(vmax < 6.0e4f))) {
         if (lane == 0) atomicOr(range_flag, 1);
+    }
+}
+
+template <int D>
+__global__ __launch_bounds__(GW_WAVES * 64) void gcw_layer_kernel(const float* __restrict__ x, float* __restrict__ xout,
+                                                                  const int* __restrict__ row_ptr, const int* __restrict__ src,
+                                                                  const uint8_t* __restrict__ ecode, const float* __restrict__ esc,
+                                                                  const int* __restrict__ out_deg, const float* __restrict__ tab,
+                                                                  const uint8_t* __restrict__ wchunks, const float* __restrict__ tailp,
+                                                                  int n_tot, int* __restrict__ range_flag) {
+    gcw_layer_body<D, false>(x, xout, row_ptr, src, ecode, esc, out_deg, tab, wchunks, tailp, n_tot, range_flag, GcwNoVnArgs{});
+}
+
+// the VN instance: stage s adds vn_{s+1} behind the walk and (s < 3) leaves the partial rows of xin_{s+1}
+template <int D>
+__global__ __launch_bounds__(GW_WAVES * 64) void gcw_layer_vn_kernel(const float* __restrict__ x, float* __restrict__ xout,
+                                                                     const int* __restrict__ row_ptr, const int* __restrict__ src,
+                                                                     const uint8_t* __restrict__ ecode, const float* __restrict__ esc,
+                                                                     const int* __restrict__ out_deg, const float* __restrict__ tab,
+                                                                     const uint8_t* __restrict__ wchunks, const float* __restrict__ tailp,
+                                                                     int n_tot, int* __restrict__ range_flag, GcwVnArgs vna) {
+    gcw_layer_body<D, true>(x, xout, row_ptr, src, ecode, esc, out_deg, tab, wchunks, tailp, n_tot, range_flag, vna);
+}
+
+// t_0[g] = sum_{v in g} h_0[v] + (n + 1) E, h_0[v] the nine rows of the UNPROJECTED table in the encoder's order (every node's
+// xin_0 = h_0 + E, and vn_0 = E once more): one lane per (graph, float4 piece), one chain per column in node order, so the value
+// depends on the graph alone.  Also writes node_graph [N], for every forward, as gw_vn_pool_kernel does.  (A feature out of range
+// reads row 0 here; the encoder of the same pass reports it.)
+template <int D>
+__global__ __launch_bounds__(256) void gcw_vn_t0_kernel(const int* __restrict__ node_feature, const float* __restrict__ table,
+                                                        const int* __restrict__ node_off, const float* __restrict__ vn_e,
+                                                        float* __restrict__ t, int* __restrict__ node_graph, int num_graphs) {
+    constexpr int C = D / 4;
+    const long long items = (long long)num_graphs * C;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < items; i += (long long)gridDim.x * 256) {
+        const int gi = (int)(i / C);
+        const int c = (int)(i - (long long)gi * C);
+        const int n0 = node_off[gi], n1 = node_off[gi + 1];
+        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int v = n0; v < n1; v++) {
+            float4 h = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+            for (int k = 0; k < ND_FEATURE; k++) {
+                int f = node_feature[(long long)v * ND_FEATURE + k];
+                if (f < 0 || f >= c_nd_card[k]) f = 0;
+                const float4 w = reinterpret_cast<const float4*>(table)[(size_t)(c_nd_off[k] + f) * C + c];
+                h.x += w.x; h.y += w.y; h.z += w.z; h.w += w.w;
+            }
+            acc.x += h.x; acc.y += h.y; acc.z += h.z; acc.w += h.w;
+        }
+        const float4 e = reinterpret_cast<const float4*>(vn_e)[c];
+        const float m = (float)(n1 - n0 + 1);
+        reinterpret_cast<float4*>(t)[i] =
+            make_float4(__builtin_fmaf(e.x, m, acc.x), __builtin_fmaf(e.y, m, acc.y), __builtin_fmaf(e.z, m, acc.z), __builtin_fmaf(e.w, m, acc.w));
+        for (int u = n0 + c; u < n1; u += C) node_graph[u] = gi;
+    }
+}
+
+// t[g] = (the graph's partial rows, added in slot order) + vn[g]: one lane per (graph, float4 piece).  The rows are cut at the batch's
+// 16-node tiles, so t is a function of the graph AND of where it stands in the batch (section 4.15)
+template <int D>
+__global__ __launch_bounds__(256) void gcw_vn_t_kernel(const float* __restrict__ part, const int* __restrict__ node_off,
+                                                       const float* __restrict__ vn, float* __restrict__ t, int num_graphs) {
+    constexpr int C = D / 4;
+    const long long items = (long long)num_graphs * C;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < items; i += (long long)gridDim.x * 256) {
+        const int gi = (int)(i / C);
+        const int c = (int)(i - (long long)gi * C);
+        const int n0 = node_off[gi], n1 = node_off[gi + 1];
+        const long long lo = (long long)gi + (n0 >> 4), hi = (long long)gi + ((n1 - 1) >> 4);  // (a graph without nodes: hi < lo)
+        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (n1 > n0)
+            for (long long p = lo; p <= hi; p++) {
+                const float4 x = reinterpret_cast<const float4*>(part)[(size_t)p * C + c];
+                acc.x += x.x; acc.y += x.y; acc.z += x.z; acc.w += x.w;
+            }
+        const float4 w = reinterpret_cast<const float4*>(vn)[i];
+        reinterpret_cast<float4*>(t)[i] = make_float4(acc.x + w.x, acc.y + w.y, acc.z + w.z, acc.w + w.w);
     }
 }
 
@@ -349,13 +512,29 @@ public:
         num_tasks_ = t;
         return 0;
     }
+    // OGB's virtual node (flowgnn_set_gcn_virtual_node_dim, section 4.19): the tensors' device form is gin_wide.hip's (gin_wide_vn.h) and
+    // reaches forward() through DeviceBatch::ogb_vn; here the state, and E [D] for layer 0's folded bias -- in either order with
+    // set_weights, and it holds across weight sets
+    size_t ogb_vn_blob_bytes() const override { return gw_vn_blob_bytes(D); }
+    void ogb_vn_pack(const float* vn_embedding, const float* w1, const float* b1, const float* w2, const float* b2, void* out) const override {
+        gw_vn_blob_pack(D, vn_embedding, w1, b1, w2, b2, out);
+    }
+    int set_gcn_virtual_node(const float* vn_embedding) override {
+        if (vn_embedding && gw_vn_blob_bytes(D) == 0) return 8;
+        vn_on_ = vn_embedding != nullptr;
+        if (vn_on_) vn_e_.assign(vn_embedding, vn_embedding + D);
+        return ready_ ? upload_b0() : 0;
+    }
 
     // host tensors, GcnModel's with D for 100: node_emb[173][D], edge_emb[5][13][D], convs_weight[5][D][D], convs_bias[5][D], root_emb[5][D],
     // bn_weight/bias/mean/var[5][D], pred_w[NUM_TASK][D], pred_b[NUM_TASK]
     int set_weights(const float* const* t) override {
         const float *nemb = t[0], *eemb = t[1], *cw = t[2], *cb = t[3], *root = t[4], *bnw = t[5], *bnb = t[6], *bnm = t[7], *bnv = t[8],
                     *pw = t[9], *pb = t[10];
-        std::vector<float> v_pw(pw, pw + (size_t)num_tasks_ * D), v_pb(pb, pb + num_tasks_), v_b0(cb, cb + D);
+        std::vector<float> v_pw(pw, pw + (size_t)num_tasks_ * D), v_pb(pb, pb + num_tasks_);
+        std::vector<float> v_nemb(nemb, nemb + (size_t)ND_FEATURE_TOTAL * D);  // the virtual node's t_0 reads the unprojected table
+        w0_.assign(cw, cw + (size_t)D * D);
+        b0_.assign(cb, cb + D);
         std::vector<float> tab((size_t)GCW_L * M::TAB_FLOATS);
         std::vector<float> wt((size_t)(GCW_L - 1) * D * D), v_b(cb + D, cb + (size_t)GCW_L * D);  // the exact form: [K][O] copies of W_1..W_4
         std::vector<uint8_t> chunks((size_t)(GCW_L - 1) * M::LAYER_BYTES);
@@ -402,7 +581,8 @@ public:
         if ((rc = upload(&d_tails_, tails))) return rc;
         if ((rc = upload(&d_tab_, tab))) return rc;
         if ((rc = upload(&d_proj_, proj))) return rc;
-        if ((rc = upload(&d_b0_, v_b0))) return rc;
+        if ((rc = upload_b0())) return rc;
+        if ((rc = upload(&d_nemb_, v_nemb))) return rc;
         if ((rc = upload(&d_wt_, wt))) return rc;
         if ((rc = upload(&d_b_, v_b))) return rc;
         if ((rc = upload(&d_pw_, v_pw))) return rc;
@@ -442,6 +622,23 @@ public:
     int forward(DeviceBatch& db, Profiler& prof, hipStream_t s) override {
         const int n = db.b.n_tot;
         if (n <= 0) return 0;
+        const int G = db.b.num_graphs;
+        const bool vn = db.ogb_vn != nullptr;
+        if (vn != vn_on_) {
+            set_last_error("flowgnn_run: the GCN model's virtual-node state and the engine's tensors disagree (flowgnn_set_gcn_virtual_node_dim)");
+            return 8;
+        }
+        if (vn) {
+            if (int rc = vn_t_.reserve((size_t)G * D)) return rc;
+            if (int rc = vn_vec_[0].reserve((size_t)G * D)) return rc;
+            if (int rc = vn_vec_[1].reserve((size_t)G * D)) return rc;
+            if (int rc = node_graph_.reserve((size_t)n)) return rc;
+            if (!exact_) {
+                if (int rc = vn_part_.reserve(gcw_vn_part_floats(G, n, D))) return rc;
+            } else {
+                if (int rc = hid_.reserve((size_t)G * 2 * D)) return rc;
+            }
+        }
         if (db.b.e_tot > 0) {  // dinv[src_e] per CSR entry, once per pass, as on the 100-wide per-layer path
             if (int rc = esc_.reserve((size_t)db.b.e_tot)) return rc;
             ProfScope p(prof, "edge_scalar", s);
@@ -452,6 +649,16 @@ public:
             ProfScope p(prof, "atom_encoder", s);  // x_0: nine rows of the projected table and b_0
             gw_atom_encoder_vn_kernel<D><<<grid_for((long long)n * M::C, 256, 256 * 8), 256, 0, s>>>(db.b.node_feature, d_proj_, db.h[0], n, db.csr.err, d_b0_);
         }
+        // the virtual node: vn_{l+1} (vn_vec_[l & 1]) is complete before stage l is launched -- vn_1 from t_0 here, vn_{l+2} behind stage l
+        if (vn) {
+            {
+                ProfScope p(prof, "gcn_wide_vn_t0", s);
+                gcw_vn_t0_kernel<D><<<grid_for((long long)G * M::C, 256, 256 * 8), 256, 0, s>>>(db.b.node_feature, d_nemb_, db.b.node_off, db.ogb_vn, vn_t_.p,
+                                                                                                node_graph_.p, G);
+            }
+            ProfScope p(prof, "gcn_wide_vn_update", s);
+            if (int rc = launch_gw_vn_update(D, db.ogb_vn, 0, vn_t_.p, vn_vec_[0].p, hid_.p, G, exact_, db.range_flag, s)) return rc;
+        }
         int cur = 0;
         for (int l = 0; l < GCW_L; l++) {
             const bool last = l == GCW_L - 1;
@@ -461,7 +668,12 @@ public:
             if (!exact_) {
                 ProfScope p(prof, "gcn_wide_layer", s);
                 const int grid = (int)ceil_div_ll(n, GW_ROWS);
-                if (!last)
+                if (!last && vn)
+                    gcw_layer_vn_kernel<D><<<grid, GW_WAVES * 64, 0, s>>>(db.h[cur], hn, db.csr.row_ptr, db.csr.src, db.csr.ecode, esc_.p, db.csr.out_deg, tab,
+                                                                          d_chunks_ + (size_t)l * M::LAYER_BYTES, d_tails_ + (size_t)l * M::TAIL_FLOATS,
+                                                                          n, db.range_flag,
+                                                                          GcwVnArgs{node_graph_.p, vn_vec_[l & 1].p, feeds_update(l) ? vn_part_.p : nullptr});
+                else if (!last)
                     gcw_layer_kernel<D><<<grid, GW_WAVES * 64, 0, s>>>(db.h[cur], hn, db.csr.row_ptr, db.csr.src, db.csr.ecode, esc_.p, db.csr.out_deg, tab,
                                                                        d_chunks_ + (size_t)l * M::LAYER_BYTES, d_tails_ + (size_t)l * M::TAIL_FLOATS, n,
                                                                        db.range_flag);
@@ -471,8 +683,21 @@ public:
                 ProfScope p(prof, "gcn_wide_layer_f32", s);
                 gcw_aggregate_kernel<D><<<grid_for((long long)n * M::C, 256, 256 * 8), 256, 0, s>>>(
                     db.h[cur], last ? hn : db.scratch, db.csr.row_ptr, db.csr.src, db.csr.ecode, esc_.p, db.csr.out_deg, tab, n, last ? 0 : 1);
+                if (!last && vn) {  // xin_{l+1} = a_{l+1} + vn_{l+1} on the scratch rows, and their per-graph sums
+                    if (int rc = launch_gw_vn_add(D, db.scratch, node_graph_.p, vn_vec_[l & 1].p, n, s)) return rc;
+                    if (feeds_update(l))
+                        if (int rc = launch_gw_vn_pool(D, db.scratch, db.b.node_off, vn_vec_[l & 1].p, D, vn_t_.p, nullptr, G, s)) return rc;
+                }
                 if (!last)
                     gw_dense_f32_kernel<D, D><<<(int)ceil_div_ll(n, 8), 256, 0, s>>>(db.scratch, d_wt_ + (size_t)l * D * D, d_b_ + (size_t)l * D, hn, n, 0);
+            }
+            if (vn && feeds_update(l)) {  // t_{l+1} (the split form: from the partial rows stage l left) and vn_{l+2}
+                if (!exact_) {
+                    ProfScope p(prof, "gcn_wide_vn_t", s);
+                    gcw_vn_t_kernel<D><<<grid_for((long long)G * M::C, 256, 256 * 8), 256, 0, s>>>(vn_part_.p, db.b.node_off, vn_vec_[l & 1].p, vn_t_.p, G);
+                }
+                ProfScope p(prof, "gcn_wide_vn_update", s);
+                if (int rc = launch_gw_vn_update(D, db.ogb_vn, l + 1, vn_t_.p, vn_vec_[(l + 1) & 1].p, hid_.p, G, exact_, db.range_flag, s)) return rc;
             }
             cur ^= 1;
         }
@@ -504,8 +729,27 @@ public:
     }
 
 private:
+    // stage l (0..3) adds vn_{l+1}; its rows xin_{l+1} feed update l + 1, which exists for l + 1 < 4
+    static bool feeds_update(int l) { return l + 1 < GCW_L - 1; }
+    // the encoder's tenth row: b_0, or with the virtual node on b_0' = b_0 + W_0 E, in double
+    int upload_b0() {
+        std::vector<float> b(b0_);
+        if (vn_on_)
+            for (int o = 0; o < D; o++) {
+                double acc = (double)b0_[o];
+                for (int i = 0; i < D; i++) acc += (double)w0_[(size_t)o * D + i] * (double)vn_e_[i];
+                b[o] = (float)acc;
+            }
+        return upload(&d_b0_, b);
+    }
     void free_all() {
-        float** ptrs[] = {&d_tails_, &d_tab_, &d_proj_, &d_b0_, &d_wt_, &d_b_, &d_pw_, &d_pb_};
+        vn_t_.release();
+        vn_vec_[0].release();
+        vn_vec_[1].release();
+        vn_part_.release();
+        hid_.release();
+        node_graph_.release();
+        float** ptrs[] = {&d_tails_, &d_tab_, &d_proj_, &d_b0_, &d_nemb_, &d_wt_, &d_b_, &d_pw_, &d_pb_};
         for (auto p : ptrs)
             if (*p) { (void)hipFree(*p); *p = nullptr; }
         if (d_chunks_) { (void)hipFree(d_chunks_); d_chunks_ = nullptr; }
@@ -523,6 +767,15 @@ private:
     float *d_pw_ = nullptr, *d_pb_ = nullptr;
     GrowBuf esc_;     // [E] dinv[src_e] in CSR order
     GrowBuf pooled_;  // the pooled rows [G][D] when graph embeddings are off
+    // OGB's virtual node (section 4.19)
+    bool vn_on_ = false;              // flowgnn_set_gcn_virtual_node_dim is on (the tensors themselves: DeviceBatch::ogb_vn)
+    std::vector<float> w0_, b0_, vn_e_;  // ... W_0, b_0 and E on the host, for b_0'
+    float* d_nemb_ = nullptr;         // ... the unprojected node table [173][D] (gcw_vn_t0_kernel)
+    GrowBuf vn_t_;                    // ... t [G][D], the update's input
+    GrowBuf vn_vec_[2];               // ... vn_{l+1} and vn_{l+2} [G][D], alternating
+    GrowBuf vn_part_;                 // ... the partial rows of xin (gcw_vn_part_floats)
+    GrowBuf hid_;                     // ... the exact form's hidden rows of the update [G][2 D]
+    GrowBufI node_graph_;             // ... node -> graph [N], written by the t_0 launch of every pass
 };
 
 }  // namespace

@@ -679,3 +679,63 @@ Model* make_gin_wide_model(int emb_dim) {
 }
 
 }  // namespace fg
+
+// ---------------------------------------------------------------- gin_wide_vn.h: the virtual node's launches, for gcn_wide.hip as well
+// (section 4.19).  The kernels above exist once, in this translation unit; GinWideModel::forward launches them itself, and these
+// launch the same instances.  They stand behind everything else so that the model's own kernels are compiled as they always were.
+// The width is the public constant's: the literal stays in make_gin_wide_model alone.
+#include "../../include/flowgnn.h"
+#include "gin_wide_vn.h"
+
+namespace fg {
+
+namespace {
+constexpr int GW_VN_D = FLOWGNN_EMB_DIM_OGB;
+template class GinWideModel<GW_VN_D>;  // (its members, and through forward() its kernels, are instantiated here, in front of the uses below)
+}  // namespace
+
+size_t gw_vn_blob_bytes(int emb_dim) { return emb_dim == GW_VN_D ? GwVnBlob<GW_VN_D>::BYTES : 0; }
+
+void gw_vn_blob_pack(int emb_dim, const float* vn_embedding, const float* w1, const float* b1, const float* w2, const float* b2, void* out) {
+    if (emb_dim == GW_VN_D) gw_vn_pack<GW_VN_D>(vn_embedding, w1, b1, w2, b2, static_cast<uint8_t*>(out));
+}
+
+int launch_gw_vn_update(int emb_dim, const void* blob, int l, const float* t, float* vn_next, float* hid, int num_graphs, bool exact,
+                        int* range_flag, hipStream_t s) {
+    if (emb_dim != GW_VN_D || l < 0 || l >= GW_VN_LAYERS) return FLOWGNN_ERR_UNSUPPORTED;
+    if (num_graphs <= 0) return 0;
+    constexpr int D = GW_VN_D, H = 2 * D;
+    using VB = GwVnBlob<D>;
+    const uint8_t* const wl = static_cast<const uint8_t*>(blob) + VB::E_BYTES + (size_t)l * VB::LAYER_STRIDE;
+    if (!exact) {
+        gw_vn_update_kernel<D><<<(int)ceil_div_ll(num_graphs, GW_ROWS), GW_WAVES * 64, 0, s>>>(
+            t, vn_next, wl, reinterpret_cast<const float*>(wl + VB::TAIL_OFF), num_graphs, range_flag);
+    } else {
+        const int blocks = (int)ceil_div_ll(num_graphs, 8);
+        gw_dense_f32_kernel<D, H><<<blocks, 256, 0, s>>>(t, reinterpret_cast<const float*>(wl + VB::W1T_OFF),
+                                                        reinterpret_cast<const float*>(wl + VB::B1_OFF), hid, num_graphs, 1);
+        gw_dense_f32_kernel<H, D><<<blocks, 256, 0, s>>>(hid, reinterpret_cast<const float*>(wl + VB::W2T_OFF),
+                                                        reinterpret_cast<const float*>(wl + VB::B2_OFF), vn_next, num_graphs, 1);
+    }
+    return 0;
+}
+
+int launch_gw_vn_pool(int emb_dim, const float* rows, const int* node_off, const float* vn, int vn_stride, float* t, int* node_graph,
+                      int num_graphs, hipStream_t s) {
+    if (emb_dim != GW_VN_D) return FLOWGNN_ERR_UNSUPPORTED;
+    if (num_graphs <= 0) return 0;
+    constexpr int D = GW_VN_D;
+    gw_vn_pool_kernel<D><<<grid_for((long long)num_graphs * GwDims<D>::C, 256, 256 * 8), 256, 0, s>>>(rows, node_off, vn, vn_stride, t, node_graph,
+                                                                                                      num_graphs);
+    return 0;
+}
+
+int launch_gw_vn_add(int emb_dim, float* rows, const int* node_graph, const float* vn, int n_tot, hipStream_t s) {
+    if (emb_dim != GW_VN_D) return FLOWGNN_ERR_UNSUPPORTED;
+    if (n_tot <= 0) return 0;
+    constexpr int D = GW_VN_D;
+    gw_vn_add_kernel<D><<<grid_for((long long)n_tot * GwDims<D>::C, 256, 256 * 8), 256, 0, s>>>(rows, node_graph, vn, n_tot);
+    return 0;
+}
+
+}  // namespace fg

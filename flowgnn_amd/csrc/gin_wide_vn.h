@@ -1,0 +1,24 @@
+// gin_wide_vn.h -- OGB's virtual node at width 300, the parts that gcn_wide.hip runs as well (section 4.19):
+// the device form of the five tensors (GwVnBlob, gin_wide.hip), the update MLP on G rows t, and the exact re-run's pool and add on
+// rows.  The device code exists once, in gin_wide.hip's translation unit; these are its launchers.  emb_dim: 300, the one
+// instantiation (anything else: 0 bytes / FLOWGNN_ERR_UNSUPPORTED).
+#pragma once
+#include "common.h"
+
+namespace fg {
+
+size_t gw_vn_blob_bytes(int emb_dim);
+// host tensors E [D], w1 [4][2D][D], b1 [4][2D], w2 [4][D][2D], b2 [4][D] -> gw_vn_blob_bytes(emb_dim) bytes at out
+void gw_vn_blob_pack(int emb_dim, const float* vn_embedding, const float* w1, const float* b1, const float* w2, const float* b2, void* out);
+
+// vn_next[g] = relu(W2[l] relu(W1[l] t[g] + b1[l]) + b2[l]) for num_graphs rows t; blob: the device form.  exact: the fp32 form
+// (gw_dense_f32_kernel twice; hid [num_graphs][2D] is its hidden rows), else gw_vn_update_kernel, which raises *range_flag itself
+int launch_gw_vn_update(int emb_dim, const void* blob, int l, const float* t, float* vn_next, float* hid, int num_graphs, bool exact,
+                        int* range_flag, hipStream_t s);
+// t[g] = (the rows of graph g in node order) + vn[g * vn_stride]; node_graph non-null: also the node -> graph array (gw_vn_pool_kernel)
+int launch_gw_vn_pool(int emb_dim, const float* rows, const int* node_off, const float* vn, int vn_stride, float* t, int* node_graph,
+                      int num_graphs, hipStream_t s);
+// rows[v] += vn[node_graph[v]] (gw_vn_add_kernel)
+int launch_gw_vn_add(int emb_dim, float* rows, const int* node_graph, const float* vn, int n_tot, hipStream_t s);
+
+}  // namespace fg

@@ -20,6 +20,7 @@
 //                run OGB's virtual node (flowgnn_set_ogb_virtual_node) -- an exported gin-virtual checkpoint; usually together with --eps
 //                (with --emb-dim 300: gin_ep1_virtualnode_dim300.bin, 1 443 900 floats, through flowgnn_set_ogb_virtual_node_dim);
 //                GCN: the same from gcn_ep1_virtualnode_dim100.bin (flowgnn_set_gcn_virtual_node) -- an exported gcn-virtual checkpoint
+//                (with --emb-dim 300: gcn_ep1_virtualnode_dim300.bin, through flowgnn_set_gcn_virtual_node_dim)
 //   --emb-dim    GCN: 300 = OGB's default width (flowgnn_set_model_emb_dim), gcn_ep1_dim300.weights.all.bin is read.
 //                GIN: 300 = OGB's default width (flowgnn_set_emb_dim): the weights directory's dim300 files are read (with --eps,
 //                gin_ep1_eps_dim300.bin); 100 (default) = the reference's width
@@ -192,16 +193,20 @@ int main(int argc, char** argv) {
     }
     if (use_ogb_vn) {
         const bool gcn = mid == FLOWGNN_MODEL_GCN;
-        const bool wide = !gcn && emb_dim != FLOWGNN_EMB_DIM_REFERENCE;  // GIN at --emb-dim 300: the file of that width, through the call that carries it
+        const bool wide = emb_dim != FLOWGNN_EMB_DIM_REFERENCE;  // --emb-dim 300: the file of that width, through the call that carries it
         const size_t L = FLOWGNN_OGB_VN_LAYERS, D = wide ? (size_t)emb_dim : 100, H = 2 * D;
         const size_t at[6] = {0, D, D + L * H * D, D + L * H * D + L * H, D + 2 * L * H * D + L * H, D + 2 * L * H * D + L * H + L * D};
         std::vector<float> vn(at[5]);
-        const std::string path = wdir + (gcn ? "/gcn_ep1_virtualnode_dim100.bin" : "/gin_ep1_virtualnode_dim" + std::to_string(D) + ".bin");
-        // (GCN at --emb-dim 300 has no such file: the engine refuses the tensors before it reads them, and its text is the answer)
-        const bool refused = gcn && emb_dim != FLOWGNN_EMB_DIM_REFERENCE;
-        if (!refused && !read_exact(path, vn, 0, vn.size())) { fprintf(stderr, "--ogb-vn: cannot read %zu floats from %s\n", vn.size(), path.c_str()); return EXIT_FAILURE; }
+        const std::string path = wdir + (gcn ? "/gcn_ep1_virtualnode_dim" : "/gin_ep1_virtualnode_dim") + std::to_string(D) + ".bin";
+        const char* const call = wide ? (gcn ? "flowgnn_set_gcn_virtual_node_dim" : "flowgnn_set_ogb_virtual_node_dim")
+                                      : (gcn ? "flowgnn_set_gcn_virtual_node" : "flowgnn_set_ogb_virtual_node");
+        if (!read_exact(path, vn, 0, vn.size())) {
+            fprintf(stderr, "--ogb-vn: cannot read %zu floats from %s (the tensors of %s)\n", vn.size(), path.c_str(), call);
+            return EXIT_FAILURE;
+        }
         if (wide)
-            rc = flowgnn_group_set_ogb_virtual_node_dim(eng, emb_dim, vn.data() + at[0], vn.data() + at[1], vn.data() + at[2], vn.data() + at[3], vn.data() + at[4]);
+            rc = (gcn ? flowgnn_group_set_gcn_virtual_node_dim : flowgnn_group_set_ogb_virtual_node_dim)(eng, emb_dim, vn.data() + at[0], vn.data() + at[1],
+                                                                                                         vn.data() + at[2], vn.data() + at[3], vn.data() + at[4]);
         else
             rc = (gcn ? flowgnn_group_set_gcn_virtual_node : flowgnn_group_set_ogb_virtual_node)(eng, vn.data() + at[0], vn.data() + at[1], vn.data() + at[2],
                                                                                                  vn.data() + at[3], vn.data() + at[4]);

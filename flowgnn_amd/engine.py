@@ -67,6 +67,16 @@ def _ogb_vn_dim(a) -> int:
     return 100 if a[0] is None else int(a[0].size)
 
 
+def _gcn_vn_args(vn, engine_dim):
+    """_ogb_vn_args for GCN's two calls: 300-wide tensors are for an engine at set_model_emb_dim(300) alone -- on any other they
+    are refused here, before a C call sees a pointer."""
+    a = _ogb_vn_args(vn)
+    if _ogb_vn_dim(a) != 100 and _ogb_vn_dim(a) != int(engine_dim):
+        raise ValueError(f"set_gcn_virtual_node: the tensors are {_ogb_vn_dim(a)} wide and the engine's width is {int(engine_dim)} "
+                         "(set_model_emb_dim(300) first)")
+    return a
+
+
 def option_value(v) -> float:
     """Option values are numbers; "f32" / "f16" (the *_mfma switches) read as 32 / 16."""
     if isinstance(v, str) and v in ("f32", "f16"):
@@ -178,7 +188,7 @@ class Engine:
     def load_weights_dir(self, directory: str, eps: bool = False, virtual_node: bool = False):
         """eps=True (GIN, GIN-VN): also read the directory's eps file and apply it (set_gin_eps); virtual_node=True: also read
         gin_ep1_virtualnode_dim100.bin and apply it (GIN: set_ogb_virtual_node), or gcn_ep1_virtualnode_dim100.bin on a GCN engine
-        (set_gcn_virtual_node).  The C call itself does neither.  A GIN engine at width 300 (set_emb_dim) reads the dim300 set, its eps
+        (set_gcn_virtual_node; at width 300 gcn_ep1_virtualnode_dim300.bin, through flowgnn_set_gcn_virtual_node_dim).  The C call itself does neither.  A GIN engine at width 300 (set_emb_dim) reads the dim300 set, its eps
         file and its virtual-node file (gin_ep1_virtualnode_dim300.bin, through flowgnn_set_ogb_virtual_node_dim) included."""
         self._check(self.lib.flowgnn_load_weights_dir(self._h, directory.encode()), "flowgnn_load_weights_dir")
         if eps:
@@ -186,7 +196,7 @@ class Engine:
             self.set_gin_eps(load_gin_eps(directory, emb_dim=self.emb_dim if self.model == "GIN" else 100))
         if virtual_node and self.model == "GCN":
             from .weights import load_gcn_virtual_node
-            self.set_gcn_virtual_node(load_gcn_virtual_node(directory))
+            self.set_gcn_virtual_node(load_gcn_virtual_node(directory, emb_dim=self.emb_dim))
         elif virtual_node:
             from .weights import load_gin_virtual_node
             self.set_ogb_virtual_node(load_gin_virtual_node(directory, emb_dim=self.emb_dim))
@@ -625,9 +635,13 @@ class Engine:
     def set_gcn_virtual_node(self, vn=None):
         """GCN: run OGB's virtual node (gnn_type='gcn-virtual'; flowgnn.h: flowgnn_set_gcn_virtual_node).  `vn`: the dict of
         set_ogb_virtual_node (export.gcn_virtual_node_from_ogb_state_dict); None turns it off.  The engine's, across batches and
-        weight sets."""
-        a = _ogb_vn_args(vn, emb_dims=(100,))
-        self._check(self.lib.flowgnn_set_gcn_virtual_node(self._h, *[_pf(x) for x in a]), "flowgnn_set_gcn_virtual_node")
+        weight sets.  300-wide tensors go through the call that carries the width, flowgnn_set_gcn_virtual_node_dim, for an engine at
+        set_model_emb_dim(300) (on any other: ValueError); 100-wide ones through the call that has none."""
+        a = _gcn_vn_args(vn, self.emb_dim)
+        if _ogb_vn_dim(a) == 100:  # (at width 300 that is the call's own refusal: it has no width argument)
+            self._check(self.lib.flowgnn_set_gcn_virtual_node(self._h, *[_pf(x) for x in a]), "flowgnn_set_gcn_virtual_node")
+        else:
+            self._check(self.lib.flowgnn_set_gcn_virtual_node_dim(self._h, _ogb_vn_dim(a), *[_pf(x) for x in a]), "flowgnn_set_gcn_virtual_node_dim")
 
     def gcn_virtual_node(self) -> bool:
         """Whether GCN's virtual node is on (flowgnn.h: flowgnn_gcn_virtual_node)."""
@@ -775,8 +789,12 @@ class EngineGroup:
 
     def set_gcn_virtual_node(self, vn=None):
         """Engine.set_gcn_virtual_node on every member (flowgnn.h: flowgnn_group_set_gcn_virtual_node)."""
-        a = _ogb_vn_args(vn, emb_dims=(100,))
-        self._check(self.lib.flowgnn_group_set_gcn_virtual_node(self._h, *[_pf(x) for x in a]), "flowgnn_group_set_gcn_virtual_node")
+        a = _gcn_vn_args(vn, self.emb_dim)
+        if _ogb_vn_dim(a) == 100:
+            self._check(self.lib.flowgnn_group_set_gcn_virtual_node(self._h, *[_pf(x) for x in a]), "flowgnn_group_set_gcn_virtual_node")
+        else:
+            self._check(self.lib.flowgnn_group_set_gcn_virtual_node_dim(self._h, _ogb_vn_dim(a), *[_pf(x) for x in a]),
+                        "flowgnn_group_set_gcn_virtual_node_dim")
 
     def set_batch(self, batch: GraphBatch):
         nn, ne = _i32(batch.nums_of_nodes), _i32(batch.nums_of_edges)

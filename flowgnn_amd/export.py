@@ -118,10 +118,11 @@ def gin_virtual_node_from_ogb_state_dict(sd: Mapping, num_layers: int = 5, virtu
     return _virtual_node_from_ogb_state_dict(sd, num_layers, _vn_dim(virtual_node_dim))
 
 
-def gcn_virtual_node_from_ogb_state_dict(sd: Mapping, num_layers: int = 5) -> Dict[str, np.ndarray]:
+def gcn_virtual_node_from_ogb_state_dict(sd: Mapping, num_layers: int = 5, virtual_node_dim: int = 100) -> Dict[str, np.ndarray]:
     """The same five tensors of an OGB `GNN(gnn_type='gcn-virtual')` state_dict, for Engine.set_gcn_virtual_node /
-    flowgnn_set_gcn_virtual_node (the virtual node's keys and its MLP do not depend on the convolution)."""
-    return _virtual_node_from_ogb_state_dict(sd, num_layers)
+    flowgnn_set_gcn_virtual_node (the virtual node's keys and its MLP do not depend on the convolution).
+    virtual_node_dim: the width the caller expects, 100 or 300 (flowgnn_set_gcn_virtual_node_dim); a state_dict of another width is refused."""
+    return _virtual_node_from_ogb_state_dict(sd, num_layers, _vn_dim(virtual_node_dim))
 
 
 def gin_weights_from_ogb_state_dict(sd: Mapping, num_layers: int = 5, eps_tol: float = 0.0, multi_task: bool = False,
@@ -186,7 +187,7 @@ def gin_weights_from_ogb_state_dict(sd: Mapping, num_layers: int = 5, eps_tol: f
 
 
 def gcn_weights_from_ogb_state_dict(sd: Mapping, num_layers: int = 5, multi_task: bool = False,
-                                    virtual_node: bool = False, emb_dim: int = 100) -> Dict[str, np.ndarray]:
+                                    virtual_node: bool = False, emb_dim: int = 100, virtual_node_dim: int = 100) -> Dict[str, np.ndarray]:
     """OGB `GNN(gnn_type='gcn', ...)` -> the reference's GCN weight set.  BatchNorm stays a separate step in the
     reference (GCN/src/node_embedding.cc:123-138) but with 2^-10 added to the variance instead of torch's 1e-5
     (GCN/src/load_inputs.cc:32): the exported variance is shifted by the difference so that both normalise alike.
@@ -194,16 +195,23 @@ def gcn_weights_from_ogb_state_dict(sd: Mapping, num_layers: int = 5, multi_task
     trained -- unless virtual_node says that the engine will run the virtual node too (gcn_virtual_node_from_ogb_state_dict +
     flowgnn_set_gcn_virtual_node).
     emb_dim: the width the caller expects, 100 or 300 (OGB's default, for an engine with flowgnn_set_model_emb_dim(300)); a state_dict
-    of another width is refused, and so is gcn-virtual at 300, which the engine does not run."""
+    of another width is refused.  A 300-wide gcn-virtual state_dict exports only with virtual_node=True, emb_dim=300 AND
+    virtual_node_dim=300 (the engine then takes its virtual node through flowgnn_set_gcn_virtual_node_dim); without that keyword the
+    virtual node's tensors are 100 wide and the state_dict is refused.  A virtual_node_dim other than emb_dim is refused too."""
     p = "gnn_node"
+    vdim = _vn_dim(virtual_node_dim)
     if int(emb_dim) not in _weights.GCN_EMB_DIMS:
         raise ExportError(f"emb_dim {emb_dim}: the engine runs GCN at emb_dim {_weights.GCN_EMB_DIMS[0]} (the reference's width) and "
                           f"{_weights.GCN_EMB_DIMS[1]} (OGB's default), no other")
     emb_dim = int(emb_dim)
     shapes = _weights.gcn_shapes(emb_dim)
+    if vdim != 100 and vdim != emb_dim:
+        raise ExportError(f"virtual_node_dim is {vdim} and emb_dim is {emb_dim}: the virtual node has the model's width")
     if emb_dim != 100:
-        if virtual_node:
-            raise ExportError(f"virtual_node=True at emb_dim {emb_dim}: the engine runs gcn-virtual at emb_dim 100 only")
+        if virtual_node and vdim != emb_dim:
+            raise ExportError(f"virtual_node=True at emb_dim {emb_dim}: the virtual node's tensors are 100 wide unless told otherwise, and the "
+                              f"engine runs those at emb_dim 100 only; a {emb_dim}-wide gcn-virtual model exports with "
+                              f"virtual_node_dim={emb_dim} beside emb_dim={emb_dim} (flowgnn_set_gcn_virtual_node_dim)")
         width = int(_get(sd, f"{p}.atom_encoder.atom_embedding_list.0.weight").shape[-1])
         if width != emb_dim:
             raise ExportError(f"atom_embedding_list.0.weight is {width} wide and emb_dim is {emb_dim}")
@@ -264,14 +272,18 @@ def export_weights(model: str, sd: Mapping, directory: str, multi_task: bool = F
     virtual_node_dim (GIN): 300 for a 300-wide gin-virtual state_dict, whose virtual node goes into gin_ep1_virtualnode_dim300.bin
     (flowgnn_set_ogb_virtual_node_dim; `host GIN --emb-dim 300 --eps --ogb-vn`); without it such a state_dict is refused.
     virtual_node (GCN): likewise OGB's gcn-virtual, into gcn_ep1_virtualnode_dim100.bin (flowgnn_set_gcn_virtual_node).
+    virtual_node_dim (GCN): 300 beside emb_dim=300 for a 300-wide gcn-virtual state_dict, whose virtual node goes into
+    gcn_ep1_virtualnode_dim300.bin (flowgnn_set_gcn_virtual_node_dim; `host GCN --emb-dim 300 --ogb-vn`); without it such a
+    state_dict is refused, and so is a virtual_node_dim other than emb_dim.
     emb_dim (GCN): 300 for a 300-wide gcn state_dict, which goes into gcn_ep1_dim300.weights.all.bin, for an engine with
     flowgnn_set_model_emb_dim(300) / `host GCN --emb-dim 300`; without it such a state_dict is refused.  (GIN reads its width off the
     state_dict and takes no emb_dim.)"""
     m = model.upper()
     if int(emb_dim) != 100 and m != "GCN":
         raise ExportError(f"emb_dim={emb_dim} is GCN's keyword; {model} reads its width off the state_dict")
-    if _vn_dim(virtual_node_dim) != 100 and m != "GIN":
-        raise ExportError(f"virtual_node_dim={virtual_node_dim} is GIN's (flowgnn_set_ogb_virtual_node_dim); {model} has the 100-wide virtual node only")
+    if _vn_dim(virtual_node_dim) != 100 and m not in ("GIN", "GCN"):
+        raise ExportError(f"virtual_node_dim={virtual_node_dim} is GIN's and GCN's (flowgnn_set_ogb_virtual_node_dim, "
+                          f"flowgnn_set_gcn_virtual_node_dim); {model} has no such virtual node")
     if virtual_node and m not in ("GIN", "GCN"):
         raise ExportError(f"virtual_node=True is OGB's gin-virtual or gcn-virtual, which the engine runs as GIN or GCN (not {model})")
     if m in ("GIN", "GIN-VN"):
@@ -282,10 +294,11 @@ def export_weights(model: str, sd: Mapping, directory: str, multi_task: bool = F
         if virtual_node:
             _weights.save_gin_virtual_node(vn, directory)
     elif m == "GCN":
-        w = gcn_weights_from_ogb_state_dict(sd, multi_task=multi_task, virtual_node=virtual_node, emb_dim=emb_dim)
+        w = gcn_weights_from_ogb_state_dict(sd, multi_task=multi_task, virtual_node=virtual_node, emb_dim=emb_dim, virtual_node_dim=virtual_node_dim)
+        vn = gcn_virtual_node_from_ogb_state_dict(sd, virtual_node_dim=virtual_node_dim) if virtual_node else None  # (before any file is written)
         _weights.save_gcn_weights(w, directory)
         if virtual_node:
-            _weights.save_gcn_virtual_node(gcn_virtual_node_from_ogb_state_dict(sd), directory)
+            _weights.save_gcn_virtual_node(vn, directory, emb_dim=int(virtual_node_dim))
     else:
         raise ExportError(f"no OGB example model corresponds to the reference's {model} (its PNA/DGN/GAT checkpoints are already "
                           f"flat files: use flowgnn_amd.weights.save_*_weights)")

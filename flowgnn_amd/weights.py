@@ -178,27 +178,35 @@ def synth_gin_virtual_node(seed: int = 11, scale: float = 1.0, emb_dim: int = 10
 GCN_VIRTUAL_NODE_FILE = "gcn_ep1_virtualnode_dim100.bin"
 
 
-def save_gcn_virtual_node(vn, directory: str) -> None:
-    """Write gcn_ep1_virtualnode_dim100.bin, as save_gin_virtual_node writes GIN's.  Nothing applies the file unless asked to:
-    `host GCN --ogb-vn`, Engine.load_weights_dir(dir, virtual_node=True)."""
-    flat = np.concatenate([a.ravel() for a in checked_gin_virtual_node(vn, emb_dims=(100,)).values()]).astype("<f4")  # (refused before anything is created)
+def gcn_virtual_node_file(emb_dim: int = 100) -> str:
+    """gcn_ep1_virtualnode_dim<emb_dim>.bin"""
+    gin_virtual_node_shapes(emb_dim)  # (refuses a width that does not exist)
+    return GCN_VIRTUAL_NODE_FILE.replace("dim100", f"dim{int(emb_dim)}")
+
+
+def save_gcn_virtual_node(vn, directory: str, emb_dim: int = 100) -> None:
+    """Write gcn_ep1_virtualnode_dim<emb_dim>.bin, as save_gin_virtual_node writes GIN's.  The width is the keyword's, 100 unless it
+    says 300 (flowgnn_set_gcn_virtual_node_dim): tensors of another width are refused before anything is created.  Nothing applies
+    the file unless asked to: `host GCN --ogb-vn`, Engine.load_weights_dir(dir, virtual_node=True)."""
+    name = gcn_virtual_node_file(emb_dim)
+    flat = np.concatenate([a.ravel() for a in checked_gin_virtual_node(vn, emb_dims=(int(emb_dim),)).values()]).astype("<f4")  # (refused before anything is created)
     os.makedirs(directory, exist_ok=True)
-    flat.tofile(os.path.join(directory, GCN_VIRTUAL_NODE_FILE))
+    flat.tofile(os.path.join(directory, name))
 
 
-def load_gcn_virtual_node(directory: str) -> Dict[str, np.ndarray]:
-    """The five tensors of a directory's GCN virtual-node file (for Engine.set_gcn_virtual_node); a short file is refused."""
-    path = os.path.join(directory, GCN_VIRTUAL_NODE_FILE)
+def load_gcn_virtual_node(directory: str, emb_dim: int = 100) -> Dict[str, np.ndarray]:
+    """The five tensors of a directory's GCN virtual-node file of width emb_dim (for Engine.set_gcn_virtual_node); a short file is refused."""
+    path = os.path.join(directory, gcn_virtual_node_file(emb_dim))
     out, at = OrderedDict(), 0
-    for k, shp in GIN_VIRTUAL_NODE_SHAPES.items():
+    for k, shp in gin_virtual_node_shapes(emb_dim).items():
         out[k] = _read(path, shp, at)
         at += int(np.prod(shp))
     return out
 
 
-def synth_gcn_virtual_node(seed: int = 13, scale: float = 1.0) -> Dict[str, np.ndarray]:
+def synth_gcn_virtual_node(seed: int = 13, scale: float = 1.0, emb_dim: int = 100) -> Dict[str, np.ndarray]:
     """Random virtual-node tensors for GCN: synth_gin_virtual_node's scales (the MLP is the same), another seed."""
-    return synth_gin_virtual_node(seed=seed, scale=scale)
+    return synth_gin_virtual_node(seed=seed, scale=scale, emb_dim=emb_dim)
 
 
 def synth_gin_weights(seed: int = 7, num_tasks: int = 1, emb_dim: int = 100) -> Dict[str, np.ndarray]:

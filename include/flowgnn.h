@@ -536,9 +536,9 @@ int flowgnn_emb_dim(const flowgnn_engine* e);              /* -1 for a null hand
  * gcn_tile_build, gcn_unfused, gcn_mfma) are accepted and have no effect at 300.
  * The same sequence as flowgnn_set_emb_dim: weights and batch must be set again after a change, and the width the engine has is a
  * no-op.  Any other model: FLOWGNN_ERR_UNSUPPORTED; a width other than the two: FLOWGNN_ERR_ARG.  On a GCN engine at 300,
- * FLOWGNN_NUMERIC_Q6_10, flowgnn_set_gcn_virtual_node with tensors (they are 100 wide, and gcn-virtual has no 300-wide form; all five
- * NULL stays accepted), flowgnn_run_aggregation_only and flowgnn_get_aggregate return FLOWGNN_ERR_UNSUPPORTED, and so does this call
- * while the fixed-point mode or GCN's virtual node is on.  flowgnn_set_emb_dim on a GCN engine stays FLOWGNN_ERR_UNSUPPORTED and
+ * FLOWGNN_NUMERIC_Q6_10, flowgnn_set_gcn_virtual_node with tensors (they are 100 wide; 300-wide ones go through
+ * flowgnn_set_gcn_virtual_node_dim; all five NULL stays accepted), flowgnn_run_aggregation_only and flowgnn_get_aggregate return
+ * FLOWGNN_ERR_UNSUPPORTED, and so does this call while the fixed-point mode or GCN's virtual node of the other width is on.  flowgnn_set_emb_dim on a GCN engine stays FLOWGNN_ERR_UNSUPPORTED and
  * names this call.  flowgnn_embedding_dim(FLOWGNN_MODEL_GCN) stays 100.
  */
 int flowgnn_set_model_emb_dim(flowgnn_engine* e, int emb_dim);   /* GIN, GCN: 100 (default) or 300 */
@@ -726,6 +726,31 @@ int flowgnn_set_gcn_virtual_node(flowgnn_engine* e, const float* vn_embedding, c
 int flowgnn_gcn_virtual_node(const flowgnn_engine* e);            /* 1 on, 0 off, -1 null handle */
 
 /*
+ * gcn-virtual through a call that carries the tensors' width, which is how it runs at OGB's default emb_dim 300
+ * (flowgnn_set_model_emb_dim(e, FLOWGNN_EMB_DIM_OGB) first): the mirror of flowgnn_set_ogb_virtual_node_dim.  With D = emb_dim:
+ * vn_embedding [D], w1 [4][2D][D], b1 [4][2D], w2 [4][D][2D], b2 [4][D]; the definition is the one above with that D.
+ *   emb_dim == 100: exactly flowgnn_set_gcn_virtual_node -- the same state, the same kernels, the same bits.
+ *   emb_dim == 300: kernels of gcn_wide.hip.  The row the vector is added to exists only in the registers
+ *       of the fused layer kernel, so its VN instance adds vn there, in front of the f16 split, and leaves the per-graph sums as
+ *       partial rows cut at the batch's 16-node tiles (section 4.15's scheme); vn_0 = E sits in layer 0's bias.  Profile slots:
+ *       gcn_wide_vn_t0 (sum of the atom rows, once), gcn_wide_vn_t (three) and gcn_wide_vn_update (four, gin_wide.hip's split-f16
+ *       update MLP), with the fp32 re-run of flowgnn_exact_reruns when a row, t or a hidden value leaves the f16 range.  It combines
+ *       with NUM_TASK, every pooling mode, the optional outputs, flowgnn_get_h, device batches and groups.  A graph's result has the
+ *       same bits from run to run and between a host batch and the same batch given on the device, and agrees within fp32 rounding
+ *       when the graph stands elsewhere (a permuted batch, a slice, a group's cut).
+ * FLOWGNN_ERR_ARG: emb_dim other than 100 or 300; tensors given and emb_dim != flowgnn_emb_dim(e) (flowgnn_last_error names both);
+ * some of the five NULL and some not; a value that is not finite; a null handle.  FLOWGNN_ERR_UNSUPPORTED: any model but
+ * FLOWGNN_MODEL_GCN; FLOWGNN_NUMERIC_Q6_10.  All five NULL turns the virtual node off at any width.  flowgnn_set_gcn_virtual_node
+ * itself has no width argument, so its tensors are 100 wide by contract and it keeps refusing at width 300.
+ * flowgnn_gcn_virtual_node reports 1 for either width.  While a virtual node of either width is on, flowgnn_set_model_emb_dim to the
+ * other width is FLOWGNN_ERR_UNSUPPORTED: turn it off, change the width, set it again.  State handling is that of the call above.
+ * Files: gcn_ep1_virtualnode_dim300.bin holds the five tensors in this order (1 443 900 LE float32); `host GCN --emb-dim 300 --ogb-vn`
+ * and the Python wrapper's load_weights_dir(dir, virtual_node=True) read the file of the engine's width.
+ */
+int flowgnn_set_gcn_virtual_node_dim(flowgnn_engine* e, int emb_dim, const float* vn_embedding, const float* w1, const float* b1,
+                                     const float* w2, const float* b2); /* host arrays, copied; all NULL = off */
+
+/*
  * Laplacian eigenvectors: DGN's node_eigen from the graphs alone (the reference reads it from DGN/eig/g%d.txt and does not say where it
  * comes from).  For graph g with n nodes and edges (u, v) in local ids:
  *     A[u][v] = A[v][u] = 1 for every edge with u != v   (both directions and duplicates collapse to 1, self loops are ignored)
@@ -813,6 +838,8 @@ int flowgnn_group_set_ogb_virtual_node(flowgnn_group* g, const float* vn_embeddi
 int flowgnn_group_set_ogb_virtual_node_dim(flowgnn_group* g, int emb_dim, const float* vn_embedding, const float* w1, const float* b1,
                                            const float* w2, const float* b2);
 int flowgnn_group_set_gcn_virtual_node(flowgnn_group* g, const float* vn_embedding, const float* w1, const float* b1, const float* w2, const float* b2);
+int flowgnn_group_set_gcn_virtual_node_dim(flowgnn_group* g, int emb_dim, const float* vn_embedding, const float* w1, const float* b1,
+                                           const float* w2, const float* b2);
 int flowgnn_group_set_batch(flowgnn_group* g, int num_graphs,
                             const int* nums_of_nodes, const int* nums_of_edges,
                             const int* node_feature, const int* edge_list, const int* edge_attr,
