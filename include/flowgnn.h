@@ -540,6 +540,9 @@ int flowgnn_emb_dim(const flowgnn_engine* e);              /* -1 for a null hand
  * flowgnn_set_gcn_virtual_node_dim; all five NULL stays accepted), flowgnn_run_aggregation_only and flowgnn_get_aggregate return
  * FLOWGNN_ERR_UNSUPPORTED, and so does this call while the fixed-point mode or GCN's virtual node of the other width is on.  flowgnn_set_emb_dim on a GCN engine stays FLOWGNN_ERR_UNSUPPORTED and
  * names this call.  flowgnn_embedding_dim(FLOWGNN_MODEL_GCN) stays 100.
+ * Where the engine's GCN is OGB's GCNConv (either width): on batches that list both directions of every edge, as every OGB molecule
+ * dataset does.  The engine follows the reference, whose normalisation is 0 at a node without out-edges; OGB takes
+ * (out-degree + 1)^-1/2 there, so a message into such a node is dropped here and delivered there.
  */
 int flowgnn_set_model_emb_dim(flowgnn_engine* e, int emb_dim);   /* GIN, GCN: 100 (default) or 300 */
 
