@@ -175,6 +175,8 @@ struct DeviceBatch {
     float gin_self_scale[5];  // with five zeros runs the eps instances too.  s_l = (float)(1.0f + eps[l]) of layer l: a[v] = s_l h_l[v] + m_l[v]
     const float* ogb_vn;      // flowgnn_set_ogb_virtual_node (GIN) / flowgnn_set_gcn_virtual_node (GCN): the five tensors in the device form of gin_ogbvn.h, or null: off, every
                               // launch is the one it always was.  A forward that finds it set runs OGB's virtual node on every path
+    const void* attn_pool;    // flowgnn_set_attention_pooling (GIN, GCN at width 300): the gate's tensors in the device form of wide_attn.h, or null: off,
+                              // every launch is the one it always was.  A forward that finds it set pools by the softmax of the gates
     int final_h;              // which h[] holds the last stage's output (set by forward)
     const float* tap;         // optional debug tap returned by flowgnn_get_h instead of h[final_h]
     int tap_dim;

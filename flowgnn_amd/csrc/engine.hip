@@ -9,6 +9,7 @@
 #include "engine_internal.h"
 #include "tile_pack.h"
 #include "gin_ogbvn.h"
+#include "wide_attn.h"
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -418,6 +419,7 @@ int flowgnn_destroy(flowgnn_engine* e) {
     e->eig_plan.release();
     e->eig_io.release();
     e->ogb_vn.release();
+    e->attn_pool.release();
     if (e->eig_done) (void)hipEventDestroy(e->eig_done);
     if (e->d_err) (void)hipFree(e->d_err);
     delete e->model;
@@ -718,6 +720,7 @@ static int set_batch_state(flowgnn_engine* e, int num_graphs, const int* nums_of
     db.gin_eps_on = e->gin_eps_on;
     for (int l = 0; l < 5; l++) db.gin_self_scale[l] = (float)(1.0f + e->gin_eps[l]);
     db.ogb_vn = e->ogb_vn_on ? (const float*)e->ogb_vn.p : nullptr;
+    db.attn_pool = e->attn_pool_on ? e->attn_pool.p : nullptr;
     db.final_h = 0;
     db.tap = nullptr;
     db.tap_dim = 0;
@@ -1175,6 +1178,10 @@ int flowgnn_set_node_logits(flowgnn_engine* e, int on) {
         e->err = "flowgnn_set_node_logits: the pooling is not the mean (flowgnn_set_pooling), and node logits are the terms whose mean is the logit";
         return FLOWGNN_ERR_UNSUPPORTED;
     }
+    if (on && e->attn_pool_on) {
+        e->err = "flowgnn_set_node_logits: the attention pooling is on (flowgnn_set_attention_pooling), and under it a graph's logit is no mean of per-node terms: there are no node logits";
+        return FLOWGNN_ERR_UNSUPPORTED;
+    }
     return switch_output(e, kOutputs[OUT_NLOG], on);
 }
 
@@ -1327,6 +1334,11 @@ static int set_width(flowgnn_engine* e, const char* fn, int emb_dim) {
                  ": turn it off, change the width, set it again";
         return FLOWGNN_ERR_UNSUPPORTED;
     }
+    if (e->attn_pool_on) {  // (the same rule: the gate's tensors belong to a width)
+        e->err = who + "the attention pooling is on (flowgnn_set_attention_pooling), and its tensors are " + std::to_string(e->emb_dim) + " wide, not " +
+                 std::to_string(emb_dim) + ": turn it off, change the width, set it again";
+        return FLOWGNN_ERR_UNSUPPORTED;
+    }
     ENGINE_TRY(e, begin_change(e));
     Model* m = gcn ? (emb_dim == FLOWGNN_EMB_DIM_REFERENCE ? make_gcn_model() : make_gcn_wide_model(emb_dim))
                    : (emb_dim == FLOWGNN_EMB_DIM_REFERENCE ? make_gin_model(false) : make_gin_wide_model(emb_dim));
@@ -1430,6 +1442,10 @@ int flowgnn_set_pooling(flowgnn_engine* e, int mode) {
     }
     if (mode != FLOWGNN_POOL_MEAN && e->nlog_on) {
         e->err = "flowgnn_set_pooling: node logits are on, and they are the terms whose mean is the logit";
+        return FLOWGNN_ERR_UNSUPPORTED;
+    }
+    if (mode != FLOWGNN_POOL_MEAN && e->attn_pool_on) {
+        e->err = "flowgnn_set_pooling: the attention pooling is on (flowgnn_set_attention_pooling), a readout of its own; beside it the mean is the only accepted value";
         return FLOWGNN_ERR_UNSUPPORTED;
     }
     ENGINE_TRY(e, use_device(e));
@@ -1617,6 +1633,70 @@ int flowgnn_set_gcn_virtual_node_dim(flowgnn_engine* e, int emb_dim, const float
 int flowgnn_gcn_virtual_node(const flowgnn_engine* e) { return e ? (e->ogb_vn_on && e->model_id == FLOWGNN_MODEL_GCN ? 1 : 0) : -1; }
 
 int flowgnn_ogb_virtual_node(const flowgnn_engine* e) { return e ? (e->ogb_vn_on && e->model_id == FLOWGNN_MODEL_GIN ? 1 : 0) : -1; }
+
+// OGB's graph_pooling="attention" readout: the state handling of set_virtual_node above -- checks first, then
+// an idle stream, the tensors packed on the host into the device form of wide_attn.h, one device buffer owned by the engine.  All three
+// NULL: off, at any width and for any model.
+int flowgnn_set_attention_pooling(flowgnn_engine* e, int emb_dim, const float* w1, const float* b1, const float* w2) {
+    if (!e) return FLOWGNN_ERR_ARG;
+    const std::string who = "flowgnn_set_attention_pooling: ";
+    if (emb_dim != FLOWGNN_EMB_DIM_REFERENCE && emb_dim != FLOWGNN_EMB_DIM_OGB) {
+        e->err = who + "emb_dim is " + std::to_string(emb_dim) + "; the widths are FLOWGNN_EMB_DIM_REFERENCE (100) and FLOWGNN_EMB_DIM_OGB (300)";
+        return FLOWGNN_ERR_ARG;
+    }
+    const int given = (w1 != nullptr) + (b1 != nullptr) + (w2 != nullptr);
+    if (given != 0 && given != 3) {
+        e->err = who + "some of the three tensors are NULL and some are not (all three: on, all NULL: off)";
+        return FLOWGNN_ERR_ARG;
+    }
+    const bool on = given == 3;
+    if (on) {
+        const size_t D = (size_t)emb_dim, H = 2 * D;
+        const float* const t[3] = {w1, b1, w2};
+        const size_t count[3] = {H * D, H, H};
+        static const char* const names[3] = {"w1", "b1", "w2"};
+        for (int i = 0; i < 3; i++)
+            for (size_t k = 0; k < count[i]; k++)
+                if (!std::isfinite(t[i][k])) {
+                    e->err = who + names[i] + "[" + std::to_string(k) + "] is not finite";
+                    return FLOWGNN_ERR_ARG;
+                }
+        if (e->model_id != FLOWGNN_MODEL_GIN && e->model_id != FLOWGNN_MODEL_GCN) {
+            e->err = who + "the attention pooling exists for FLOWGNN_MODEL_GIN and FLOWGNN_MODEL_GCN only (OGB's gin, gin-virtual, gcn, gcn-virtual)";
+            return FLOWGNN_ERR_UNSUPPORTED;
+        }
+        if (emb_dim != e->emb_dim) {
+            e->err = who + "the tensors are " + std::to_string(emb_dim) + " wide and the engine's width is " + std::to_string(e->emb_dim) +
+                     " (flowgnn_set_emb_dim / flowgnn_set_model_emb_dim)";
+            return FLOWGNN_ERR_ARG;
+        }
+        if (emb_dim != FLOWGNN_EMB_DIM_OGB || fg::attn_pool_blob_bytes(emb_dim) == 0) {
+            e->err = who + "only the 300-wide models have this readout (the 100-wide graph-resident kernels fold the mean into their last layer): "
+                           "flowgnn_set_emb_dim / flowgnn_set_model_emb_dim(e, 300) first";
+            return FLOWGNN_ERR_UNSUPPORTED;
+        }
+        if (e->pooling != FLOWGNN_POOL_MEAN) {
+            e->err = who + "the pooling is not the mean (flowgnn_set_pooling), and this readout replaces the pooling: set FLOWGNN_POOL_MEAN first";
+            return FLOWGNN_ERR_UNSUPPORTED;
+        }
+        if (e->nlog_on) {
+            e->err = who + "node logits are on (flowgnn_set_node_logits), and under this readout a graph's logit is no mean of per-node terms";
+            return FLOWGNN_ERR_UNSUPPORTED;
+        }
+    }
+    ENGINE_TRY(e, begin_change(e));  // (an idle stream: a run in flight may still read the tensors this call replaces)
+    if (on) {
+        std::vector<float> packed(fg::attn_pool_blob_bytes(emb_dim) / sizeof(float));  // (floats: the parts are read as float4 pieces)
+        fg::attn_pool_blob_pack(emb_dim, w1, b1, w2, packed.data());
+        EHIP_TRY(e, e->attn_pool.reserve(sizeof(float) * packed.size(), false));
+        EHIP_TRY(e, hipMemcpy(e->attn_pool.p, packed.data(), sizeof(float) * packed.size(), hipMemcpyHostToDevice));
+    }
+    e->attn_pool_on = on;
+    e->db.attn_pool = on ? e->attn_pool.p : nullptr;  // (launches are stream-ordered: it matters to those enqueued after this call)
+    return FLOWGNN_OK;
+}
+
+int flowgnn_attention_pooling(const flowgnn_engine* e) { return e ? (e->attn_pool_on ? 1 : 0) : -1; }
 
 int flowgnn_set_option(flowgnn_engine* e, const char* key, double value) {
     if (!e || !key) return FLOWGNN_ERR_ARG;

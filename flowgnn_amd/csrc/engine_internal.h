@@ -99,6 +99,8 @@ struct flowgnn_engine {
     float gin_eps[5] = {0, 0, 0, 0, 0};
     bool ogb_vn_on = false;           // flowgnn_set_ogb_virtual_node: the engine's as well (db.ogb_vn follows it)
     fg::GrowBuf ogb_vn;               // ... and its five tensors on the device (gin_ogbvn.h: GIN_OGBVN_FLOATS)
+    bool attn_pool_on = false;        // flowgnn_set_attention_pooling: the engine's as well (db.attn_pool follows it)
+    fg::GrowBuf attn_pool;            // ... and the gate's three tensors on the device (wide_attn.h)
 
     // the optional outputs (fg::OutSlot): graph embeddings [G][dim] (flowgnn_set_embeddings), node embeddings [N][dim]
     // (flowgnn_set_node_embeddings), node logits [N][num_tasks] (flowgnn_set_node_logits) and, for GAT, the attention coefficients

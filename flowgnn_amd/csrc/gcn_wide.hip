@@ -44,6 +44,7 @@
 #include "dense_split.h"
 #include "gcn_ogbvn.h"
 #include "gin_wide_vn.h"
+#include "wide_attn.h"
 #include "wide_common.h"
 
 namespace fg {
@@ -639,6 +640,11 @@ public:
                 if (int rc = hid_.reserve((size_t)G * 2 * D)) return rc;
             }
         }
+        if (db.attn_pool) {  // the attention readout (section 4.20): the gates [N], and the exact form's hidden rows [N][2 D]
+            if (int rc = attn_s_.reserve((size_t)n)) return rc;
+            if (exact_)
+                if (int rc = hid_.reserve((size_t)(n > G ? n : G) * 2 * D)) return rc;
+        }
         if (db.b.e_tot > 0) {  // dinv[src_e] per CSR entry, once per pass, as on the 100-wide per-layer path
             if (int rc = esc_.reserve((size_t)db.b.e_tot)) return rc;
             ProfScope p(prof, "edge_scalar", s);
@@ -710,7 +716,14 @@ public:
             if (int rc = pooled_.reserve((size_t)db.b.num_graphs * D)) return rc;
             pooled = pooled_.p;
         }
-        {
+        if (db.attn_pool) {  // OGB's attention readout (section 4.20): the gates of the rows, then their softmax-weighted sum per graph
+            {
+                ProfScope p(prof, "attn_gate", s);
+                if (int rc = launch_attn_gate(D, db.attn_pool, h5, attn_s_.p, hid_.p, n, exact_, db.range_flag, s)) return rc;
+            }
+            ProfScope p(prof, "attn_pool_rows", s);
+            if (int rc = launch_attn_pool_rows(D, h5, attn_s_.p, db.b.node_off, pooled, db.b.num_graphs, s)) return rc;
+        } else {
             ProfScope p(prof, "mean_pool_rows", s);
             const int grid = (db.b.num_graphs + 3) / 4;
             if (db.pooling == POOL_OP_SUM) gw_pool_rows_kernel<D, POOL_OP_SUM><<<grid, 256, 0, s>>>(h5, db.b.node_off, pooled, db.b.num_graphs);
@@ -755,6 +768,7 @@ private:
         if (d_chunks_) { (void)hipFree(d_chunks_); d_chunks_ = nullptr; }
         esc_.release();
         pooled_.release();
+        attn_s_.release();
     }
     bool ready_ = false;
     bool exact_ = false;
@@ -767,6 +781,7 @@ private:
     float *d_pw_ = nullptr, *d_pb_ = nullptr;
     GrowBuf esc_;     // [E] dinv[src_e] in CSR order
     GrowBuf pooled_;  // the pooled rows [G][D] when graph embeddings are off
+    GrowBuf attn_s_;  // the attention readout's gates [N] (section 4.20)
     // OGB's virtual node (section 4.19)
     bool vn_on_ = false;              // flowgnn_set_gcn_virtual_node_dim is on (the tensors themselves: DeviceBatch::ogb_vn)
     std::vector<float> w0_, b0_, vn_e_;  // ... W_0, b_0 and E on the host, for b_0'

@@ -25,6 +25,7 @@
 
 #include "common.h"
 #include "dense_split.h"
+#include "wide_attn.h"    // the attention readout's two launches (section 4.20)
 #include "wide_common.h"  // GW_WAVES / GW_ROWS, gw_relu, the LDS-DMA issue, the encoder, pooling and fp32 dense kernels (shared with gcn_wide.hip)
 
 namespace fg {
@@ -626,7 +627,15 @@ public:
             if (int rc = pooled_.reserve((size_t)db.b.num_graphs * D)) return rc;
             pooled = pooled_.p;
         }
-        {
+        if (db.attn_pool) {  // OGB's attention readout (section 4.20): the gates of the rows, then their softmax-weighted sum per graph
+            if (int rc = attn_s_.reserve((size_t)n)) return rc;
+            {
+                ProfScope p(prof, "attn_gate", s);
+                if (int rc = launch_attn_gate(D, db.attn_pool, h5, attn_s_.p, hid_.p, n, exact_, db.range_flag, s)) return rc;
+            }
+            ProfScope p(prof, "attn_pool_rows", s);
+            if (int rc = launch_attn_pool_rows(D, h5, attn_s_.p, db.b.node_off, pooled, db.b.num_graphs, s)) return rc;
+        } else {
             ProfScope p(prof, "mean_pool_rows", s);
             const int grid = (db.b.num_graphs + 3) / 4;
             if (db.pooling == POOL_OP_SUM) gw_pool_rows_kernel<D, POOL_OP_SUM><<<grid, 256, 0, s>>>(h5, db.b.node_off, pooled, db.b.num_graphs);
@@ -652,6 +661,7 @@ private:
         if (d_chunks_) { (void)hipFree(d_chunks_); d_chunks_ = nullptr; }
         hid_.release();
         pooled_.release();
+        attn_s_.release();
         vn_t_.release();
         vn_vec_[0].release();
         vn_vec_[1].release();
@@ -666,6 +676,7 @@ private:
     float *d_w1t_ = nullptr, *d_w2t_ = nullptr, *d_b1_ = nullptr, *d_b2_ = nullptr;  // the exact form's weights, [K][O]
     GrowBuf hid_;     // the exact form's hidden rows [N][H]
     GrowBuf pooled_;  // the pooled rows [G][D] when graph embeddings are off
+    GrowBuf attn_s_;  // the attention readout's gates [N] (section 4.20)
     GrowBuf vn_t_;         // OGB's virtual node: t [G][D], the update's input
     GrowBuf vn_vec_[2];    // ... vn_l and vn_{l+1} [G][D], alternating (both are live while layer l's update runs)
     GrowBufI node_graph_;  // ... and node -> graph [N], written by layer 0's pool launch of every pass

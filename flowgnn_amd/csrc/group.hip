@@ -266,6 +266,10 @@ int flowgnn_group_set_gcn_virtual_node_dim(flowgnn_group* g, int emb_dim, const 
     return group_all(g, [&](flowgnn_engine* e) { return flowgnn_set_gcn_virtual_node_dim(e, emb_dim, vn_embedding, w1, b1, w2, b2); });
 }
 
+int flowgnn_group_set_attention_pooling(flowgnn_group* g, int emb_dim, const float* w1, const float* b1, const float* w2) {
+    return group_all(g, [&](flowgnn_engine* e) { return flowgnn_set_attention_pooling(e, emb_dim, w1, b1, w2); });
+}
+
 int flowgnn_group_set_embeddings(flowgnn_group* g, int on) { return group_all(g, [&](flowgnn_engine* e) { return flowgnn_set_embeddings(e, on); }); }
 int flowgnn_group_set_node_embeddings(flowgnn_group* g, int on) { return group_all(g, [&](flowgnn_engine* e) { return flowgnn_set_node_embeddings(e, on); }); }
 int flowgnn_group_set_node_logits(flowgnn_group* g, int on) { return group_all(g, [&](flowgnn_engine* e) { return flowgnn_set_node_logits(e, on); }); }

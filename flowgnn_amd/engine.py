@@ -62,6 +62,16 @@ def _ogb_vn_args(vn, emb_dims=(100, 300)):
     return list(checked_gin_virtual_node(vn, emb_dims=emb_dims).values())
 
 
+def _attn_pool_args(gate):
+    """None -> (300, three NULLs) (off); else the width read off w1 and the dict's three tensors (weights.ATTENTION_POOLING_KEYS) as
+    float32 arrays, in the C call's order -- the caller keeps them alive for the duration of the call."""
+    if gate is None:
+        return 300, [None] * 3
+    from .weights import checked_attention_pooling
+    a = list(checked_attention_pooling(gate).values())
+    return int(a[0].shape[1]), a
+
+
 def _ogb_vn_dim(a) -> int:
     """The width of _ogb_vn_args' tensors (the embedding row's length); 100 for the five NULLs."""
     return 100 if a[0] is None else int(a[0].size)
@@ -185,11 +195,13 @@ class Engine:
         ptrs = (_lib.p_float * len(arrs))(*[_pf(a) for a in arrs])
         self._check(self.lib.flowgnn_set_weights(self._h, len(arrs), ptrs), "flowgnn_set_weights")
 
-    def load_weights_dir(self, directory: str, eps: bool = False, virtual_node: bool = False):
+    def load_weights_dir(self, directory: str, eps: bool = False, virtual_node: bool = False, attention_pooling: bool = False):
         """eps=True (GIN, GIN-VN): also read the directory's eps file and apply it (set_gin_eps); virtual_node=True: also read
         gin_ep1_virtualnode_dim100.bin and apply it (GIN: set_ogb_virtual_node), or gcn_ep1_virtualnode_dim100.bin on a GCN engine
         (set_gcn_virtual_node; at width 300 gcn_ep1_virtualnode_dim300.bin, through flowgnn_set_gcn_virtual_node_dim).  The C call itself does neither.  A GIN engine at width 300 (set_emb_dim) reads the dim300 set, its eps
-        file and its virtual-node file (gin_ep1_virtualnode_dim300.bin, through flowgnn_set_ogb_virtual_node_dim) included."""
+        file and its virtual-node file (gin_ep1_virtualnode_dim300.bin, through flowgnn_set_ogb_virtual_node_dim) included.
+        attention_pooling=True (GIN, GCN at width 300): also read gin_ep1_attnpool_dim300.bin / gcn_ep1_attnpool_dim300.bin and apply it
+        (set_attention_pooling)."""
         self._check(self.lib.flowgnn_load_weights_dir(self._h, directory.encode()), "flowgnn_load_weights_dir")
         if eps:
             from .weights import load_gin_eps
@@ -200,6 +212,9 @@ class Engine:
         elif virtual_node:
             from .weights import load_gin_virtual_node
             self.set_ogb_virtual_node(load_gin_virtual_node(directory, emb_dim=self.emb_dim))
+        if attention_pooling:
+            from .weights import load_attention_pooling
+            self.set_attention_pooling(load_attention_pooling(directory, model=self.model, emb_dim=self.emb_dim))
 
     # ---- batch
     def set_job_totals(self, job_nodes: int = -1, job_edges: int = -1):
@@ -647,6 +662,18 @@ class Engine:
         """Whether GCN's virtual node is on (flowgnn.h: flowgnn_gcn_virtual_node)."""
         return int(self.lib.flowgnn_gcn_virtual_node(self._h)) == 1
 
+    def set_attention_pooling(self, gate=None):
+        """GIN, GCN at width 300: OGB's graph_pooling="attention" readout (flowgnn.h: flowgnn_set_attention_pooling).  `gate`: a dict
+        with the keys w1 [600][300], b1 [600], w2 [600] (the gate's BatchNorm folded, its last bias dropped:
+        export.attention_pooling_from_ogb_state_dict); the width is read off w1.  None turns it off.  The engine's, across batches and
+        weight sets; `embeddings()` then returns the softmax-weighted sums, the vectors the head is applied to."""
+        d, a = _attn_pool_args(gate)
+        self._check(self.lib.flowgnn_set_attention_pooling(self._h, d, *[_pf(x) for x in a]), "flowgnn_set_attention_pooling")
+
+    def attention_pooling(self) -> bool:
+        """Whether the attention readout is on (flowgnn.h: flowgnn_attention_pooling)."""
+        return int(self.lib.flowgnn_attention_pooling(self._h)) == 1
+
     def exact_reruns(self) -> int:
         """Forward passes repeated on the exact-fp32 kernels (flowgnn.h: flowgnn_exact_reruns)."""
         return int(self.lib.flowgnn_exact_reruns(self._h))
@@ -795,6 +822,11 @@ class EngineGroup:
         else:
             self._check(self.lib.flowgnn_group_set_gcn_virtual_node_dim(self._h, _ogb_vn_dim(a), *[_pf(x) for x in a]),
                         "flowgnn_group_set_gcn_virtual_node_dim")
+
+    def set_attention_pooling(self, gate=None):
+        """Engine.set_attention_pooling on every member (flowgnn.h: flowgnn_group_set_attention_pooling)."""
+        d, a = _attn_pool_args(gate)
+        self._check(self.lib.flowgnn_group_set_attention_pooling(self._h, d, *[_pf(x) for x in a]), "flowgnn_group_set_attention_pooling")
 
     def set_batch(self, batch: GraphBatch):
         nn, ne = _i32(batch.nums_of_nodes), _i32(batch.nums_of_edges)

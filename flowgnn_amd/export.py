@@ -125,6 +125,41 @@ def gcn_virtual_node_from_ogb_state_dict(sd: Mapping, num_layers: int = 5, virtu
     return _virtual_node_from_ogb_state_dict(sd, num_layers, _vn_dim(virtual_node_dim))
 
 
+ATTN_KEY = "pool.gate_nn.0.weight"  # what tells a graph_pooling="attention" state_dict from the others
+
+
+def attention_pooling_from_ogb_state_dict(sd: Mapping, emb_dim: int = 300) -> Dict[str, np.ndarray]:
+    """The gate of an OGB `GNN(graph_pooling='attention')` state_dict as the three tensors Engine.set_attention_pooling /
+    flowgnn_set_attention_pooling take: `pool.gate_nn` = Linear(D, 2D)-BatchNorm1d(2D)-ReLU-Linear(2D, 1) (OGB: .0 .1 .3).  The
+    BatchNorm (inference statistics) sits in front of the ReLU and is folded into the first linear layer: exact.  `pool.gate_nn.3.bias`
+    adds the same number to every gate of a graph and cancels in the softmax: it is dropped, here and in the engine.
+    emb_dim: the width the caller expects (300: only the 300-wide models have this readout); a state_dict of another width is refused."""
+    try:
+        shapes = _weights.attention_pooling_shapes(emb_dim)
+    except ValueError as e:
+        raise ExportError(str(e))
+    d = int(emb_dim)
+    if ATTN_KEY not in sd:
+        raise ExportError(f"state_dict has no '{ATTN_KEY}': it is not a graph_pooling='attention' model (its keys are pool.gate_nn.*)")
+    w1, b1 = _get(sd, "pool.gate_nn.0.weight"), _get(sd, "pool.gate_nn.0.bias")
+    if w1.shape != (2 * d, d):
+        raise ExportError(f"'pool.gate_nn.0.weight' is {w1.shape} and emb_dim is {d}: wanted ({2 * d}, {d})")
+    if b1.shape != (2 * d,):
+        raise ExportError(f"'pool.gate_nn.0.bias' is {b1.shape}, wanted ({2 * d},)")
+    for k in ("weight", "bias", "running_mean", "running_var"):
+        t = _get(sd, f"pool.gate_nn.1.{k}")
+        if t.shape != (2 * d,):
+            raise ExportError(f"'pool.gate_nn.1.{k}' is {t.shape}, wanted ({2 * d},)")
+    if (_get(sd, "pool.gate_nn.1.running_var") + BN_EPS <= 0).any():
+        raise ExportError("'pool.gate_nn.1.running_var' is not positive")
+    w1, b1 = _fold_bn(w1, b1, sd, "pool.gate_nn.1")
+    w2 = _get(sd, "pool.gate_nn.3.weight")
+    if w2.size != 2 * d or w2.shape[0] != 1:
+        raise ExportError(f"'pool.gate_nn.3.weight' is {w2.shape}, wanted (1, {2 * d})")
+    out = OrderedDict([("w1", w1), ("b1", b1), ("w2", w2.reshape(-1))])
+    return _checked(out, shapes, lambda k, v: v)
+
+
 def gin_weights_from_ogb_state_dict(sd: Mapping, num_layers: int = 5, eps_tol: float = 0.0, multi_task: bool = False,
                                     keep_eps: bool = False, virtual_node: bool = False, virtual_node_dim: int = 100) -> Dict[str, np.ndarray]:
     """OGB `GNN(gnn_type='gin', virtual_node=False, JK='last', residual=False, graph_pooling='mean')` -> the reference's
@@ -261,7 +296,8 @@ def _checked(w: Dict[str, np.ndarray], spec: Mapping, shape_of) -> Dict[str, np.
 
 
 def export_weights(model: str, sd: Mapping, directory: str, multi_task: bool = False, keep_eps: bool = False,
-                   virtual_node: bool = False, virtual_node_dim: int = 100, emb_dim: int = 100) -> Dict[str, np.ndarray]:
+                   virtual_node: bool = False, virtual_node_dim: int = 100, emb_dim: int = 100,
+                   attention_pooling: bool = False) -> Dict[str, np.ndarray]:
     """Write the `.bin` file(s) `host` / `flowgnn_load_weights_dir` read for `model` ('GIN', 'GIN-VN' or 'GCN').
     multi_task: keep all rows of the prediction head (the engine then needs flowgnn_set_num_tasks(rows) before loading).
     keep_eps (GIN, GIN-VN): a trained eps is not refused; the eps file holds the trained values, for `host --eps` /
@@ -277,8 +313,17 @@ def export_weights(model: str, sd: Mapping, directory: str, multi_task: bool = F
     state_dict is refused, and so is a virtual_node_dim other than emb_dim.
     emb_dim (GCN): 300 for a 300-wide gcn state_dict, which goes into gcn_ep1_dim300.weights.all.bin, for an engine with
     flowgnn_set_model_emb_dim(300) / `host GCN --emb-dim 300`; without it such a state_dict is refused.  (GIN reads its width off the
-    state_dict and takes no emb_dim.)"""
+    state_dict and takes no emb_dim.)
+    attention_pooling (GIN, GCN at width 300): the state_dict was trained with graph_pooling='attention'; its gate goes into
+    gin_ep1_attnpool_dim300.bin / gcn_ep1_attnpool_dim300.bin beside the others (attention_pooling_from_ogb_state_dict), for
+    `host GIN|GCN --emb-dim 300 --attn-pool` / Engine.load_weights_dir(dir, attention_pooling=True) to apply
+    (flowgnn_set_attention_pooling).  Without the keyword such a state_dict is refused: its head was never trained on the mean."""
     m = model.upper()
+    if attention_pooling and m not in ("GIN", "GCN"):
+        raise ExportError(f"attention_pooling=True is GIN's and GCN's (flowgnn_set_attention_pooling); {model} has no such readout")
+    if ATTN_KEY in sd and not attention_pooling:
+        raise ExportError(f"the state_dict has '{ATTN_KEY}': it was trained with graph_pooling='attention', and its head on a mean readout "
+                          f"is a model nobody trained; pass attention_pooling=True (flowgnn_set_attention_pooling; 300-wide GIN and GCN)")
     if int(emb_dim) != 100 and m != "GCN":
         raise ExportError(f"emb_dim={emb_dim} is GCN's keyword; {model} reads its width off the state_dict")
     if _vn_dim(virtual_node_dim) != 100 and m not in ("GIN", "GCN"):
@@ -290,15 +335,21 @@ def export_weights(model: str, sd: Mapping, directory: str, multi_task: bool = F
         w = gin_weights_from_ogb_state_dict(sd, multi_task=multi_task, keep_eps=keep_eps, virtual_node=virtual_node,
                                             virtual_node_dim=virtual_node_dim)
         vn = gin_virtual_node_from_ogb_state_dict(sd, virtual_node_dim=virtual_node_dim) if virtual_node else None  # (before any file is written)
+        gate = attention_pooling_from_ogb_state_dict(sd, emb_dim=_weights.gin_emb_dim_of(w)) if attention_pooling else None  # (likewise)
         _weights.save_gin_weights(w, directory, eps=gin_eps_from_ogb_state_dict(sd) if keep_eps else None)
         if virtual_node:
             _weights.save_gin_virtual_node(vn, directory)
+        if attention_pooling:
+            _weights.save_attention_pooling(gate, directory, model="GIN")
     elif m == "GCN":
         w = gcn_weights_from_ogb_state_dict(sd, multi_task=multi_task, virtual_node=virtual_node, emb_dim=emb_dim, virtual_node_dim=virtual_node_dim)
         vn = gcn_virtual_node_from_ogb_state_dict(sd, virtual_node_dim=virtual_node_dim) if virtual_node else None  # (before any file is written)
+        gate = attention_pooling_from_ogb_state_dict(sd, emb_dim=int(emb_dim)) if attention_pooling else None  # (likewise)
         _weights.save_gcn_weights(w, directory)
         if virtual_node:
             _weights.save_gcn_virtual_node(vn, directory, emb_dim=int(virtual_node_dim))
+        if attention_pooling:
+            _weights.save_attention_pooling(gate, directory, model="GCN")
     else:
         raise ExportError(f"no OGB example model corresponds to the reference's {model} (its PNA/DGN/GAT checkpoints are already "
                           f"flat files: use flowgnn_amd.weights.save_*_weights)")

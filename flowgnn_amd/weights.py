@@ -209,6 +209,77 @@ def synth_gcn_virtual_node(seed: int = 13, scale: float = 1.0, emb_dim: int = 10
     return synth_gin_virtual_node(seed=seed, scale=scale, emb_dim=emb_dim)
 
 
+# OGB's attention readout for GIN and GCN at width 300 (flowgnn.h: flowgnn_set_attention_pooling): one file beside the model's set, the
+# gate's three tensors in the order of the C call's arguments, its BatchNorm folded; the last Linear's bias cancels in the softmax and
+# is not stored
+ATTENTION_POOLING_KEYS = ("w1", "b1", "w2")
+ATTENTION_POOLING_EMB_DIMS = (300,)
+_ATTENTION_POOLING_PREFIX = {"GIN": "gin", "GCN": "gcn"}
+
+
+def attention_pooling_shapes(emb_dim: int = 300, emb_dims=ATTENTION_POOLING_EMB_DIMS):
+    """w1 [2D][D], b1 [2D], w2 [2D] at D = emb_dim, one of emb_dims (the files exist at 300 alone; the C call takes 100-wide tensors
+    too, to refuse them by name)."""
+    d = int(emb_dim)
+    if d not in tuple(emb_dims):
+        raise ValueError(f"attention pooling: emb_dim {emb_dim} is not one of {tuple(emb_dims)} (only the 300-wide models have this readout)")
+    return OrderedDict([("w1", (2 * d, d)), ("b1", (2 * d,)), ("w2", (2 * d,))])
+
+
+def attention_pooling_file(model: str = "GIN", emb_dim: int = 300) -> str:
+    """gin_ep1_attnpool_dim<emb_dim>.bin / gcn_ep1_attnpool_dim<emb_dim>.bin"""
+    attention_pooling_shapes(emb_dim)  # (refuses a width that does not exist)
+    if model not in _ATTENTION_POOLING_PREFIX:
+        raise ValueError(f"attention pooling: model {model!r} is not one of {sorted(_ATTENTION_POOLING_PREFIX)}")
+    return f"{_ATTENTION_POOLING_PREFIX[model]}_ep1_attnpool_dim{int(emb_dim)}.bin"
+
+
+def checked_attention_pooling(gate) -> Dict[str, np.ndarray]:
+    """The dict `gate` with exactly the keys w1, b1, w2, each as a contiguous float32 array of its shape at the width read off w1."""
+    if set(gate) != set(ATTENTION_POOLING_KEYS):
+        raise ValueError(f"attention pooling: wanted the keys {list(ATTENTION_POOLING_KEYS)}, got {sorted(gate)}")
+    w1 = np.asarray(gate["w1"])
+    if w1.ndim != 2 or w1.shape[0] != 2 * w1.shape[1]:
+        raise ValueError(f"attention pooling: w1 is {w1.shape}, wanted [2D][D]")
+    out = OrderedDict()
+    for k, shp in attention_pooling_shapes(w1.shape[1], emb_dims=GIN_EMB_DIMS).items():
+        a = np.asarray(gate[k], dtype=np.float32)
+        if a.size != int(np.prod(shp)):
+            raise ValueError(f"attention pooling: {k} is {a.shape}, wanted {shp}")
+        out[k] = np.ascontiguousarray(a.reshape(shp))
+    return out
+
+
+def save_attention_pooling(gate, directory: str, model: str = "GIN") -> None:
+    """Write <model>_ep1_attnpool_dim300.bin: w1, b1, w2 end to end, little-endian float32 (181 200 of them).  Nothing applies the file
+    unless asked to: `host GIN|GCN --emb-dim 300 --attn-pool`, Engine.load_weights_dir(dir, attention_pooling=True)."""
+    gate = checked_attention_pooling(gate)
+    name = attention_pooling_file(model, gate["w1"].shape[1])  # (refused before anything is created)
+    os.makedirs(directory, exist_ok=True)
+    np.concatenate([a.ravel() for a in gate.values()]).astype("<f4").tofile(os.path.join(directory, name))
+
+
+def load_attention_pooling(directory: str, model: str = "GIN", emb_dim: int = 300) -> Dict[str, np.ndarray]:
+    """The three tensors of a directory's attention-pooling file (for Engine.set_attention_pooling); a short file is refused."""
+    path = os.path.join(directory, attention_pooling_file(model, emb_dim))
+    out, at = OrderedDict(), 0
+    for k, shp in attention_pooling_shapes(emb_dim).items():
+        out[k] = _read(path, shp, at)
+        at += int(np.prod(shp))
+    return out
+
+
+def synth_attention_pooling(seed: int = 11, emb_dim: int = 300) -> Dict[str, np.ndarray]:
+    """Random gate tensors: w1 = N(0,1) / sqrt(D), b1 = 0.5 N(0,1), w2 = 8 N(0,1) / sqrt(2D), drawn in this order from one
+    default_rng(seed) -- gates that spread by a few units inside a molecule, so that the softmax is far from the mean."""
+    d = int(emb_dim)
+    rng = np.random.default_rng(seed)
+    w1 = (rng.standard_normal((2 * d, d)) / np.sqrt(d)).astype(np.float32)
+    b1 = (0.5 * rng.standard_normal(2 * d)).astype(np.float32)
+    w2 = (8.0 * rng.standard_normal(2 * d) / np.sqrt(2 * d)).astype(np.float32)
+    return OrderedDict([("w1", w1), ("b1", b1), ("w2", w2)])
+
+
 def synth_gin_weights(seed: int = 7, num_tasks: int = 1, emb_dim: int = 100) -> Dict[str, np.ndarray]:
     """Random weights with the measured scales of the shipped GIN set:
     W1 s=0.075, b1 s=0.91, W2 s=0.053, b2 s=0.49, node/edge emb s=0.11/0.14, pred s=0.15.

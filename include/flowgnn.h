@@ -601,7 +601,8 @@ int flowgnn_set_numeric_mode(flowgnn_engine* e, int mode);
  * flowgnn_set_pooling: FLOWGNN_ERR_ARG for a mode outside 0..2.  FLOWGNN_ERR_UNSUPPORTED (flowgnn_last_error says why) for a mode
  *     other than the mean on PNA and DGN (their MLP heads were trained on the mean), in FLOWGNN_NUMERIC_Q6_10 (the fixed-point
  *     readout is the reference's), and while node logits are on (their contract is "the mean of the terms is the logit");
- *     flowgnn_set_numeric_mode and flowgnn_set_node_logits answer the same while a mode other than the mean is set.
+ *     flowgnn_set_numeric_mode and flowgnn_set_node_logits answer the same while a mode other than the mean is set.  Also while
+ *     OGB's attention readout is on (flowgnn_set_attention_pooling, a readout of its own with a call of its own: there is no fourth mode).
  * flowgnn_pooling: the mode, -1 for a null handle.
  * flowgnn_group_set_pooling: flowgnn_set_pooling on every member.  flowgnn_entry_set_pooling: for the engines behind the
  *     <M>_compute_graphs entry points of `model`, as flowgnn_entry_set_option (remembered for engines created later).
@@ -754,6 +755,41 @@ int flowgnn_set_gcn_virtual_node_dim(flowgnn_engine* e, int emb_dim, const float
                                      const float* w2, const float* b2); /* host arrays, copied; all NULL = off */
 
 /*
+ * OGB's graph_pooling="attention" readout for GIN and GCN at width 300, with or without OGB's virtual node:
+ *     GlobalAttention(gate_nn = Sequential(Linear(D, 2D), BatchNorm1d(2D), ReLU(), Linear(2D, 1)))
+ * With D = emb_dim = 300, H = 2D and r[v] the rows the readout pools (h_5 of GIN, GCN's final rows: exactly what
+ * flowgnn_set_node_embeddings returns):
+ *     s[v]        = w2 . relu(W1 r[v] + b1)                  W1 [H][D], b1 [H], w2 [H]; the BatchNorm folded into W1, b1 by the exporter
+ *     m_g         = max over v in g of s[v]
+ *     e[v]        = exp(s[v] - m_g)
+ *     pooled[g]   = (sum over v in g of e[v] r[v]) / (sum over v in g of e[v])     both sums in node order, one chain per column
+ *     logit[g][t] = b[t] + W[t] . pooled[g]                  the model's own head, every NUM_TASK
+ * The bias of the gate's last Linear (OGB's pool.gate_nn.3.bias) cancels in the softmax: it is neither taken nor stored.  A one-node
+ * graph gets pooled = r[v] exactly (e = 1, Z = 1), so its logit has the bits of the mean readout's.  A graph without nodes gets zeros.
+ * Arithmetic: the first product is fp32-accurate on the f16 matrix pipe (three split-f16 MFMAs, W1 pre-scaled by a power of two and
+ * split on the host), with the fp32 re-run of flowgnn_exact_reruns when a row or a hidden value leaves the f16 range; everything else
+ * is fp32.  The bits of a graph's result depend on that graph alone (profile slots attn_gate, attn_pool_rows).
+ * The tensors are host arrays and are copied.  All three NULL turns the readout off (the default) at any width and for any model, and
+ * then every launch is the one it always was.  The setting holds across batches and flowgnn_set_weights, may change between runs on a
+ * resident batch, and drops a recorded launch sequence (option hipgraph).  It combines with eps, NUM_TASK, OGB's virtual node, graph
+ * embeddings (they return pooled), node embeddings, flowgnn_get_h, host and device batches, groups and option hipgraph.
+ * FLOWGNN_ERR_ARG: a null handle; emb_dim other than 100 or 300; some of the three NULL and some not; a value that is not finite;
+ * tensors given and emb_dim != flowgnn_emb_dim(e) (flowgnn_last_error names both widths).
+ * FLOWGNN_ERR_UNSUPPORTED (flowgnn_last_error says why): any model but FLOWGNN_MODEL_GIN and FLOWGNN_MODEL_GCN; emb_dim == 100 (only
+ * the 300-wide models have this readout: flowgnn_set_emb_dim / flowgnn_set_model_emb_dim first); in both orders of the two calls,
+ * flowgnn_set_pooling other than the mean (while the readout is on the mean is the only accepted value, and flowgnn_pooling keeps
+ * reporting what flowgnn_set_pooling said) and flowgnn_set_node_logits (the logit is no longer a mean of per-node terms); and, while it
+ * is on, a change of width: the tensors belong to a width -- turn it off, change the width, set it again.
+ * flowgnn_attention_pooling: 1 on, 0 off, -1 for a null handle.  flowgnn_group_set_attention_pooling: the setter on every member.
+ * The <M>_compute_graphs entry points have no form of it, as they have none at width 300.
+ * Files: gin_ep1_attnpool_dim300.bin / gcn_ep1_attnpool_dim300.bin beside the model's set hold w1, b1, w2 in this order (181 200 LE
+ * float32); flowgnn_load_weights_dir does not read it; `host GIN|GCN --emb-dim 300 --attn-pool` and the Python wrapper's
+ * load_weights_dir(dir, attention_pooling=True) do.
+ */
+int flowgnn_set_attention_pooling(flowgnn_engine* e, int emb_dim, const float* w1, const float* b1, const float* w2); /* host arrays, copied; all NULL = off */
+int flowgnn_attention_pooling(const flowgnn_engine* e);   /* 1 on, 0 off, -1 null handle */
+
+/*
  * Laplacian eigenvectors: DGN's node_eigen from the graphs alone (the reference reads it from DGN/eig/g%d.txt and does not say where it
  * comes from).  For graph g with n nodes and edges (u, v) in local ids:
  *     A[u][v] = A[v][u] = 1 for every edge with u != v   (both directions and duplicates collapse to 1, self loops are ignored)
@@ -843,6 +879,7 @@ int flowgnn_group_set_ogb_virtual_node_dim(flowgnn_group* g, int emb_dim, const 
 int flowgnn_group_set_gcn_virtual_node(flowgnn_group* g, const float* vn_embedding, const float* w1, const float* b1, const float* w2, const float* b2);
 int flowgnn_group_set_gcn_virtual_node_dim(flowgnn_group* g, int emb_dim, const float* vn_embedding, const float* w1, const float* b1,
                                            const float* w2, const float* b2);
+int flowgnn_group_set_attention_pooling(flowgnn_group* g, int emb_dim, const float* w1, const float* b1, const float* w2);
 int flowgnn_group_set_batch(flowgnn_group* g, int num_graphs,
                             const int* nums_of_nodes, const int* nums_of_edges,
                             const int* node_feature, const int* edge_list, const int* edge_attr,
