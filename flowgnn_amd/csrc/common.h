@@ -231,8 +231,8 @@ public:
     // flowgnn_set_ogb_virtual_node: the state alone (the tensors reach forward() through DeviceBatch::ogb_vn), for what a model decides
     // before it sees a batch (wants_packed_tile_lists)
     virtual int set_ogb_virtual_node(bool on) { return on ? 8 : 0; }
-    // flowgnn_set_ogb_virtual_node_dim at a width other than 100: a model that runs the virtual node from a device form of its own says
-    // how many bytes that form has (0: none -- the 100-wide form of gin_ogbvn.h is the engine's) and packs the five host tensors
+    // flowgnn_set_ogb_virtual_node / flowgnn_set_gcn_virtual_node and their _dim forms: a model that runs the virtual node says how many
+    // bytes the device form of its tensors has (0: no such kernel; the 100-wide models: gin_ogbvn.h's) and packs the five host tensors
     // (E [D], w1 [4][2D][D], b1 [4][2D], w2 [4][D][2D], b2 [4][D], D = emb_dim()) into it; DeviceBatch::ogb_vn then points at a copy
     virtual size_t ogb_vn_blob_bytes() const { return 0; }
     virtual void ogb_vn_pack(const float*, const float*, const float*, const float*, const float*, void*) const {}

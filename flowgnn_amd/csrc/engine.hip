@@ -1492,12 +1492,12 @@ int flowgnn_gin_eps(const flowgnn_engine* e, float* eps_out) {
     return e->gin_eps_on ? 1 : 0;
 }
 
-// flowgnn_set_ogb_virtual_node (GIN) and flowgnn_set_gcn_virtual_node (GCN): the same five tensors, the same checks, the same device
-// form (gin_ogbvn.h) and the same engine state -- an engine is one model, so one of the two calls is refused on it.  `fn`: the caller.
-// `dim`: the tensors' width D (hidden width 2 D) -- 100 in the two calls without a width argument; 300 (flowgnn_set_ogb_virtual_node_dim,
-// flowgnn_set_gcn_virtual_node_dim) packs into gin_wide.hip's own device form instead, through the model object of that width.
+// flowgnn_set_ogb_virtual_node (GIN) and flowgnn_set_gcn_virtual_node (GCN): the same five tensors, the same checks and the same engine
+// state -- an engine is one model, so one of the two calls is refused on it.  `fn`: the caller.  `dim`: the tensors' width D (hidden
+// width 2 D) -- 100 in the two calls without a width argument.  The device form is the model object's (Model::ogb_vn_pack): gin_ogbvn.h's
+// at width 100, gin_wide.hip's own at 300.
 static int set_virtual_node(flowgnn_engine* e, const char* fn, const float* vn_embedding, const float* w1, const float* b1, const float* w2,
-                            const float* b2, int dim = FLOWGNN_EMB_DIM_REFERENCE) {
+                            const float* b2, int dim) {
     const std::string who = std::string(fn) + ": ";
     const float* const t[5] = {vn_embedding, w1, b1, w2, b2};
     const size_t D = (size_t)dim, H = 2 * D;
@@ -1522,19 +1522,14 @@ static int set_virtual_node(flowgnn_engine* e, const char* fn, const float* vn_e
             e->err = who + "the fixed-point arithmetic (FLOWGNN_NUMERIC_Q6_10) is the reference's, which has no such model";
             return FLOWGNN_ERR_UNSUPPORTED;
         }
-        // (a width other than 100 needs a model object of that width with a device form of its own; refused before anything changes)
-        if (dim != FLOWGNN_EMB_DIM_REFERENCE && (e->model->emb_dim() != dim || e->model->ogb_vn_blob_bytes() == 0)) {
+        // (the model object has this width and a device form for the tensors; refused before anything changes)
+        if (e->model->emb_dim() != dim || e->model->ogb_vn_blob_bytes() == 0) {
             e->err = who + "this model has no such kernel";
             return FLOWGNN_ERR_UNSUPPORTED;
         }
     }
     ENGINE_TRY(e, begin_change(e));  // (an idle stream: a run in flight may still read the tensors this call replaces)
-    if (on && dim == FLOWGNN_EMB_DIM_REFERENCE) {
-        std::vector<float> packed(fg::GIN_OGBVN_FLOATS);
-        fg::gin_ogbvn_pack(vn_embedding, w1, b1, w2, b2, packed.data());
-        EHIP_TRY(e, e->ogb_vn.reserve(sizeof(float) * packed.size(), false));
-        EHIP_TRY(e, hipMemcpy(e->ogb_vn.p, packed.data(), sizeof(float) * packed.size(), hipMemcpyHostToDevice));
-    } else if (on) {
+    if (on) {
         std::vector<float> packed(e->model->ogb_vn_blob_bytes() / sizeof(float));  // (floats: the parts are read as float4 pieces)
         e->model->ogb_vn_pack(vn_embedding, w1, b1, w2, b2, packed.data());
         EHIP_TRY(e, e->ogb_vn.reserve(sizeof(float) * packed.size(), false));
@@ -1550,84 +1545,81 @@ static int set_virtual_node(flowgnn_engine* e, const char* fn, const float* vn_e
     return FLOWGNN_OK;
 }
 
-int flowgnn_set_ogb_virtual_node(flowgnn_engine* e, const float* vn_embedding, const float* w1, const float* b1, const float* w2, const float* b2) {
-    if (!e) return FLOWGNN_ERR_ARG;
-    if (e->model_id != FLOWGNN_MODEL_GIN) {
-        e->err = "flowgnn_set_ogb_virtual_node: OGB's virtual node exists for GIN only (GIN-VN is the reference's augmentation, a different model)";
-        if (e->model_id == FLOWGNN_MODEL_GCN) e->err += "; GCN has a call of its own, flowgnn_set_gcn_virtual_node";
-        return FLOWGNN_ERR_UNSUPPORTED;
-    }
-    if (e->emb_dim != FLOWGNN_EMB_DIM_REFERENCE && (vn_embedding || w1 || b1 || w2 || b2)) {
-        e->err = "flowgnn_set_ogb_virtual_node: the engine's width is 300 (flowgnn_set_emb_dim), and the virtual node's tensors are 100 wide "
-                 "in this call; 300-wide tensors go through flowgnn_set_ogb_virtual_node_dim";
-        return FLOWGNN_ERR_UNSUPPORTED;
-    }
-    return set_virtual_node(e, "flowgnn_set_ogb_virtual_node", vn_embedding, w1, b1, w2, b2);
+// What tells GIN's pair of calls from GCN's: the checks in front of set_virtual_node are the same, in the same order.
+struct VnCalls {
+    int model_id;                // the one model the calls serve
+    const char* fn[2];           // the call without a width, and the one that carries it
+    const char* width_call;      // what sets that model's width
+    const char* wrong_model[2];  // the refusal on an engine of another model, per call ...
+    const char* gcn_hint;        // ... and what a GCN engine is told besides
+};
+static const VnCalls kVnGin = {FLOWGNN_MODEL_GIN,
+                               {"flowgnn_set_ogb_virtual_node", "flowgnn_set_ogb_virtual_node_dim"},
+                               "flowgnn_set_emb_dim",
+                               {": OGB's virtual node exists for GIN only (GIN-VN is the reference's augmentation, a different model)",
+                                ": OGB's virtual node exists for GIN only (GIN-VN is the reference's augmentation, a different model)"},
+                               "; GCN has a call of its own, flowgnn_set_gcn_virtual_node"};
+static const VnCalls kVnGcn = {FLOWGNN_MODEL_GCN,
+                               {"flowgnn_set_gcn_virtual_node", "flowgnn_set_gcn_virtual_node_dim"},
+                               "flowgnn_set_model_emb_dim",
+                               {": this call is OGB's gcn-virtual, for GCN only (GIN: flowgnn_set_ogb_virtual_node)",
+                                ": this call is OGB's gcn-virtual, for GCN only (GIN: flowgnn_set_ogb_virtual_node_dim)"},
+                               ""};
+
+static int vn_wrong_model(flowgnn_engine* e, const VnCalls& c, int with_dim) {
+    e->err = std::string(c.fn[with_dim]) + c.wrong_model[with_dim];
+    if (e->model_id == FLOWGNN_MODEL_GCN) e->err += c.gcn_hint;
+    return FLOWGNN_ERR_UNSUPPORTED;
 }
 
-// The call that carries the width.  emb_dim 100 IS the call above (the same state, kernels and bits); 300 is gin_wide.hip's virtual
-// node.  All five NULL: off, whatever the engine's width.
-int flowgnn_set_ogb_virtual_node_dim(flowgnn_engine* e, int emb_dim, const float* vn_embedding, const float* w1, const float* b1, const float* w2,
-                                     const float* b2) {
+// the calls without a width: the tensors are 100 wide
+static int set_virtual_node_ref(flowgnn_engine* e, const VnCalls& c, const float* vn_embedding, const float* w1, const float* b1, const float* w2,
+                                const float* b2) {
     if (!e) return FLOWGNN_ERR_ARG;
-    if (emb_dim != FLOWGNN_EMB_DIM_REFERENCE && emb_dim != FLOWGNN_EMB_DIM_OGB) {
-        e->err = "flowgnn_set_ogb_virtual_node_dim: emb_dim is " + std::to_string(emb_dim) +
-                 "; the widths are FLOWGNN_EMB_DIM_REFERENCE (100) and FLOWGNN_EMB_DIM_OGB (300)";
-        return FLOWGNN_ERR_ARG;
-    }
-    if (e->model_id != FLOWGNN_MODEL_GIN) {
-        e->err = "flowgnn_set_ogb_virtual_node_dim: OGB's virtual node exists for GIN only (GIN-VN is the reference's augmentation, a different model)";
-        if (e->model_id == FLOWGNN_MODEL_GCN) e->err += "; GCN has a call of its own, flowgnn_set_gcn_virtual_node";
+    if (e->model_id != c.model_id) return vn_wrong_model(e, c, 0);
+    if (off_default_width(e) && (vn_embedding || w1 || b1 || w2 || b2)) {
+        e->err = std::string(c.fn[0]) + ": the engine's width is 300 (" + c.width_call + "), and the virtual node's tensors are 100 wide "
+                 "in this call; 300-wide tensors go through " + c.fn[1];
         return FLOWGNN_ERR_UNSUPPORTED;
     }
-    const bool any = vn_embedding || w1 || b1 || w2 || b2;
-    if (any && emb_dim != e->emb_dim) {
-        e->err = "flowgnn_set_ogb_virtual_node_dim: the tensors are " + std::to_string(emb_dim) + " wide and the engine's width is " +
-                 std::to_string(e->emb_dim) + " (flowgnn_set_emb_dim)";
+    return set_virtual_node(e, c.fn[0], vn_embedding, w1, b1, w2, b2, FLOWGNN_EMB_DIM_REFERENCE);
+}
+
+// The calls that carry the width.  emb_dim 100 IS the call above (the same state, kernels and bits); 300 is gin_wide.hip's virtual node
+//  or gcn_wide.hip's (section 4.19).  All five NULL: off, whatever the engine's width (no tensor is read).
+static int set_virtual_node_dim(flowgnn_engine* e, const VnCalls& c, int emb_dim, const float* vn_embedding, const float* w1, const float* b1,
+                                const float* w2, const float* b2) {
+    if (!e) return FLOWGNN_ERR_ARG;
+    const std::string who = std::string(c.fn[1]) + ": ";
+    if (emb_dim != FLOWGNN_EMB_DIM_REFERENCE && emb_dim != FLOWGNN_EMB_DIM_OGB) {
+        e->err = who + "emb_dim is " + std::to_string(emb_dim) + "; the widths are FLOWGNN_EMB_DIM_REFERENCE (100) and FLOWGNN_EMB_DIM_OGB (300)";
         return FLOWGNN_ERR_ARG;
     }
-    if (!any || emb_dim == FLOWGNN_EMB_DIM_REFERENCE)  // off at any width (no tensor is read), or exactly the 100-wide call
-        return set_virtual_node(e, "flowgnn_set_ogb_virtual_node_dim", vn_embedding, w1, b1, w2, b2);
-    return set_virtual_node(e, "flowgnn_set_ogb_virtual_node_dim", vn_embedding, w1, b1, w2, b2, emb_dim);
+    if (e->model_id != c.model_id) return vn_wrong_model(e, c, 1);
+    if ((vn_embedding || w1 || b1 || w2 || b2) && emb_dim != e->emb_dim) {
+        e->err = who + "the tensors are " + std::to_string(emb_dim) + " wide and the engine's width is " + std::to_string(e->emb_dim) + " (" +
+                 c.width_call + ")";
+        return FLOWGNN_ERR_ARG;
+    }
+    return set_virtual_node(e, c.fn[1], vn_embedding, w1, b1, w2, b2, emb_dim);
+}
+
+int flowgnn_set_ogb_virtual_node(flowgnn_engine* e, const float* vn_embedding, const float* w1, const float* b1, const float* w2, const float* b2) {
+    return set_virtual_node_ref(e, kVnGin, vn_embedding, w1, b1, w2, b2);
+}
+
+int flowgnn_set_ogb_virtual_node_dim(flowgnn_engine* e, int emb_dim, const float* vn_embedding, const float* w1, const float* b1, const float* w2,
+                                     const float* b2) {
+    return set_virtual_node_dim(e, kVnGin, emb_dim, vn_embedding, w1, b1, w2, b2);
 }
 
 int flowgnn_set_gcn_virtual_node(flowgnn_engine* e, const float* vn_embedding, const float* w1, const float* b1, const float* w2, const float* b2) {
-    if (!e) return FLOWGNN_ERR_ARG;
-    if (e->model_id != FLOWGNN_MODEL_GCN) {
-        e->err = "flowgnn_set_gcn_virtual_node: this call is OGB's gcn-virtual, for GCN only (GIN: flowgnn_set_ogb_virtual_node)";
-        return FLOWGNN_ERR_UNSUPPORTED;
-    }
-    if (off_default_width(e) && (vn_embedding || w1 || b1 || w2 || b2)) {
-        e->err = "flowgnn_set_gcn_virtual_node: the engine's width is 300 (flowgnn_set_model_emb_dim), and the virtual node's tensors are 100 wide "
-                 "in this call; 300-wide tensors go through flowgnn_set_gcn_virtual_node_dim";
-        return FLOWGNN_ERR_UNSUPPORTED;
-    }
-    return set_virtual_node(e, "flowgnn_set_gcn_virtual_node", vn_embedding, w1, b1, w2, b2);
+    return set_virtual_node_ref(e, kVnGcn, vn_embedding, w1, b1, w2, b2);
 }
 
-// The call that carries the width, the mirror of flowgnn_set_ogb_virtual_node_dim.  emb_dim 100 IS the call above (the same state,
-// kernels and bits); 300 is gcn_wide.hip's virtual node.  All five NULL: off, whatever the engine's width.
 int flowgnn_set_gcn_virtual_node_dim(flowgnn_engine* e, int emb_dim, const float* vn_embedding, const float* w1, const float* b1, const float* w2,
                                      const float* b2) {
-    if (!e) return FLOWGNN_ERR_ARG;
-    if (emb_dim != FLOWGNN_EMB_DIM_REFERENCE && emb_dim != FLOWGNN_EMB_DIM_OGB) {
-        e->err = "flowgnn_set_gcn_virtual_node_dim: emb_dim is " + std::to_string(emb_dim) +
-                 "; the widths are FLOWGNN_EMB_DIM_REFERENCE (100) and FLOWGNN_EMB_DIM_OGB (300)";
-        return FLOWGNN_ERR_ARG;
-    }
-    if (e->model_id != FLOWGNN_MODEL_GCN) {
-        e->err = "flowgnn_set_gcn_virtual_node_dim: this call is OGB's gcn-virtual, for GCN only (GIN: flowgnn_set_ogb_virtual_node_dim)";
-        return FLOWGNN_ERR_UNSUPPORTED;
-    }
-    const bool any = vn_embedding || w1 || b1 || w2 || b2;
-    if (any && emb_dim != e->emb_dim) {
-        e->err = "flowgnn_set_gcn_virtual_node_dim: the tensors are " + std::to_string(emb_dim) + " wide and the engine's width is " +
-                 std::to_string(e->emb_dim) + " (flowgnn_set_model_emb_dim)";
-        return FLOWGNN_ERR_ARG;
-    }
-    if (!any || emb_dim == FLOWGNN_EMB_DIM_REFERENCE)  // off at any width (no tensor is read), or exactly the 100-wide call
-        return set_virtual_node(e, "flowgnn_set_gcn_virtual_node_dim", vn_embedding, w1, b1, w2, b2);
-    return set_virtual_node(e, "flowgnn_set_gcn_virtual_node_dim", vn_embedding, w1, b1, w2, b2, emb_dim);
+    return set_virtual_node_dim(e, kVnGcn, emb_dim, vn_embedding, w1, b1, w2, b2);
 }
 
 int flowgnn_gcn_virtual_node(const flowgnn_engine* e) { return e ? (e->ogb_vn_on && e->model_id == FLOWGNN_MODEL_GCN ? 1 : 0) : -1; }

@@ -1367,6 +1367,10 @@ public:
         vn_e_.assign(vn_embedding, vn_embedding + GCN_D);
         return ready_ ? fold_vn_layer0() : 0;
     }
+    size_t ogb_vn_blob_bytes() const override { return GIN_OGBVN_FLOATS * sizeof(float); }  // (GIN's device form: gin_ogbvn.h)
+    void ogb_vn_pack(const float* vn_embedding, const float* w1, const float* b1, const float* w2, const float* b2, void* out) const override {
+        gin_ogbvn_pack(vn_embedding, w1, b1, w2, b2, static_cast<float*>(out));
+    }
     // layer 0 with vn_0 = E inside: W_0 (h_0 + E) + b_0 = W_0 h_0 + b_0', a second packed blob for gcn_encoder_dense_kernel
     int fold_vn_layer0() {
         std::vector<float> b(GCN_D);

@@ -19,7 +19,8 @@
 //              A chunk's output tiles are stored as soon as its MFMAs are done, so TPC accumulators are live, not T.  The combined edge
 //              table and the three epilogue vectors have LDS of their own beside the two buffers (the budget: GcwDims).
 //   l = 4      gcw_final_kernel<D>: the walk and the epilogue without ReLU and without a product; rows pre_4
-//   readout    gw_pool_rows_kernel, launch_pooled_head, launch_node_logits_rows, as GinWideModel::forward
+//   readout    GwReadout (wide_common.h), the one GinWideModel::forward ends in; set_weights packs with wide_common.h's gw_pack_tile,
+//              gw_transpose and gw_edge_combos (DESIGN.md section 4.21 says what is shared and what is not)
 // a beyond the f16 range raises *range_flag; the engine then repeats the pass with set_exact(true): gcw_aggregate_kernel (the same
 // CSR order, the same FMAs, the same epilogue, one lane per node and float4 piece) and gw_dense_f32_kernel<D, D> once per stage.
 //
@@ -44,7 +45,6 @@
 #include "dense_split.h"
 #include "gcn_ogbvn.h"
 #include "gin_wide_vn.h"
-#include "wide_attn.h"
 #include "wide_common.h"
 
 namespace fg {
@@ -481,14 +481,7 @@ void gcw_pack_layer(const float* w, const float* b, uint8_t* out, float* tail) {
     const float s = gw_pow2_scale(w, (size_t)D * D);
     for (int t = 0; t < M::T; t++) {
         uint8_t* tile = out + (size_t)(t / M::TPC) * M::CHUNK_BYTES + (size_t)(t % M::TPC) * M::TILE_BYTES;
-        for (int lane = 0; lane < 64; lane++) {
-            const int i = lane & 15, gk = lane >> 4, o = 16 * t + i;
-            for (int ks = 0; ks < M::KS; ks++)
-                for (int e = 0; e < 8; e++) {
-                    const int k = 16 * (2 * ks + (e >> 2)) + 4 * gk + (e & 3);
-                    gw_put_split(tile + (size_t)(ks * 2) * 1024, lane, e, (o < D && k < D) ? w[(size_t)o * D + k] * s : 0.0f);
-                }
-        }
+        gw_pack_tile(w, D, D, 16 * t, s, 0, M::KS, tile, 2048);
     }
     for (int i = 0; i < M::TAIL_FLOATS; i++) tail[i] = 0.0f;
     for (int o = 0; o < D; o++) tail[o] = b[o] * s;
@@ -507,12 +500,7 @@ public:
     int num_weight_tensors() const override { return 11; }
     bool weights_ready() const override { return ready_; }
     void set_exact(bool on) override { exact_ = on; }
-    int set_num_tasks(int t) override {
-        if (t < 1) return 8;
-        if (t != num_tasks_) ready_ = false;  // graph_pred_weights / bias change shape: set the weights again
-        num_tasks_ = t;
-        return 0;
-    }
+    int set_num_tasks(int t) override { return readout_.set_num_tasks(t, ready_); }
     // OGB's virtual node (flowgnn_set_gcn_virtual_node_dim, section 4.19): the tensors' device form is gin_wide.hip's (gin_wide_vn.h) and
     // reaches forward() through DeviceBatch::ogb_vn; here the state, and E [D] for layer 0's folded bias -- in either order with
     // set_weights, and it holds across weight sets
@@ -532,7 +520,6 @@ public:
     int set_weights(const float* const* t) override {
         const float *nemb = t[0], *eemb = t[1], *cw = t[2], *cb = t[3], *root = t[4], *bnw = t[5], *bnb = t[6], *bnm = t[7], *bnv = t[8],
                     *pw = t[9], *pb = t[10];
-        std::vector<float> v_pw(pw, pw + (size_t)num_tasks_ * D), v_pb(pb, pb + num_tasks_);
         std::vector<float> v_nemb(nemb, nemb + (size_t)ND_FEATURE_TOTAL * D);  // the virtual node's t_0 reads the unprojected table
         w0_.assign(cw, cw + (size_t)D * D);
         b0_.assign(cb, cb + D);
@@ -540,20 +527,9 @@ public:
         std::vector<float> wt((size_t)(GCW_L - 1) * D * D), v_b(cb + D, cb + (size_t)GCW_L * D);  // the exact form: [K][O] copies of W_1..W_4
         std::vector<uint8_t> chunks((size_t)(GCW_L - 1) * M::LAYER_BYTES);
         std::vector<float> tails((size_t)(GCW_L - 1) * M::TAIL_FLOATS);
-        static const int ed_off[3] = {0, 5, 11};
         for (int l = 0; l < GCW_L; l++) {
-            const float* E = eemb + (size_t)l * ED_FEATURE_PER_LAYER * D;
             float* tl = &tab[(size_t)l * M::TAB_FLOATS];
-            for (int a0 = 0; a0 < 5; a0++)
-                for (int a1 = 0; a1 < 6; a1++)
-                    for (int a2 = 0; a2 < 2; a2++)
-                        for (int d = 0; d < D; d++) {
-                            float s = 0.0f;  // the order of GcnModel::set_weights
-                            s += E[(ed_off[0] + a0) * D + d];
-                            s += E[(ed_off[1] + a1) * D + d];
-                            s += E[(ed_off[2] + a2) * D + d];
-                            tl[(size_t)((a0 * 6 + a1) * 2 + a2) * D + d] = s;
-                        }
+            gw_edge_combos(eemb + (size_t)l * ED_FEATURE_PER_LAYER * D, D, tl);
             float* e = tl + M::ECOMB_FLOATS;
             for (int d = 0; d < D; d++) {
                 const double sv = std::sqrt((double)(bnv[l * D + d] + 1.0f / 1024.0f));
@@ -564,8 +540,7 @@ public:
             }
             if (l == 0) continue;
             const float* W = cw + (size_t)l * D * D;
-            for (int o = 0; o < D; o++)
-                for (int k = 0; k < D; k++) wt[(size_t)(l - 1) * D * D + (size_t)k * D + o] = W[(size_t)o * D + k];
+            gw_transpose(W, D, D, &wt[(size_t)(l - 1) * D * D]);
             gcw_pack_layer<D>(W, cb + (size_t)l * D, chunks.data() + (size_t)(l - 1) * M::LAYER_BYTES, tails.data() + (size_t)(l - 1) * M::TAIL_FLOATS);
         }
         // x_0 = b_0 + W_0 (sum_k NodeEmb[off_k + f_k]) = sum_k (W_0 NodeEmb[off_k + f_k]) + b_0: W_0 applied to the table once, in double
@@ -586,8 +561,7 @@ public:
         if ((rc = upload(&d_nemb_, v_nemb))) return rc;
         if ((rc = upload(&d_wt_, wt))) return rc;
         if ((rc = upload(&d_b_, v_b))) return rc;
-        if ((rc = upload(&d_pw_, v_pw))) return rc;
-        if ((rc = upload(&d_pb_, v_pb))) return rc;
+        if ((rc = readout_.upload_head(pw, pb))) return rc;
         ready_ = true;
         return 0;
     }
@@ -599,7 +573,7 @@ public:
         const char* f = name.c_str();
         const size_t d = D, layer = d * d + 15 * d, bn0 = ND_FEATURE_TOTAL * d + GCW_L * layer, head = bn0 + GCW_L * (4 * d + 1);
         std::vector<float> nemb(ND_FEATURE_TOTAL * d), eemb(GCW_L * ED_FEATURE_PER_LAYER * d), cw(GCW_L * d * d), cb(GCW_L * d), root(GCW_L * d),
-            bnw(GCW_L * d), bnb(GCW_L * d), bnm(GCW_L * d), bnv(GCW_L * d), pw((size_t)num_tasks_ * d), pb(num_tasks_);
+            bnw(GCW_L * d), bnb(GCW_L * d), bnm(GCW_L * d), bnv(GCW_L * d), pw((size_t)readout_.num_tasks * d), pb(readout_.num_tasks);
         int rc;
         if ((rc = read_floats(dir, f, 0, nemb.size(), nemb.data()))) return rc;
         for (int l = 0; l < GCW_L; l++) {
@@ -640,11 +614,9 @@ public:
                 if (int rc = hid_.reserve((size_t)G * 2 * D)) return rc;
             }
         }
-        if (db.attn_pool) {  // the attention readout (section 4.20): the gates [N], and the exact form's hidden rows [N][2 D]
-            if (int rc = attn_s_.reserve((size_t)n)) return rc;
-            if (exact_)
-                if (int rc = hid_.reserve((size_t)(n > G ? n : G) * 2 * D)) return rc;
-        }
+        if (int rc = readout_.reserve(db)) return rc;  // the attention readout (section 4.20): the gates [N] ...
+        if (db.attn_pool && exact_)                    // ... and the exact form's hidden rows [N][2 D]
+            if (int rc = hid_.reserve((size_t)(n > G ? n : G) * 2 * D)) return rc;
         if (db.b.e_tot > 0) {  // dinv[src_e] per CSR entry, once per pass, as on the 100-wide per-layer path
             if (int rc = esc_.reserve((size_t)db.b.e_tot)) return rc;
             ProfScope p(prof, "edge_scalar", s);
@@ -694,8 +666,7 @@ public:
                     if (feeds_update(l))
                         if (int rc = launch_gw_vn_pool(D, db.scratch, db.b.node_off, vn_vec_[l & 1].p, D, vn_t_.p, nullptr, G, s)) return rc;
                 }
-                if (!last)
-                    gw_dense_f32_kernel<D, D><<<(int)ceil_div_ll(n, 8), 256, 0, s>>>(db.scratch, d_wt_ + (size_t)l * D * D, d_b_ + (size_t)l * D, hn, n, 0);
+                if (!last) launch_gw_dense_f32<D, D>(db.scratch, d_wt_ + (size_t)l * D * D, d_b_ + (size_t)l * D, hn, n, 0, s);
             }
             if (vn && feeds_update(l)) {  // t_{l+1} (the split form: from the partial rows stage l left) and vn_{l+2}
                 if (!exact_) {
@@ -709,36 +680,7 @@ public:
         }
         db.final_h = cur;
         db.h_valid = !db.node_emb;
-        const float* const h5 = db.node_emb ? db.node_emb : db.h[cur];
-        // readout: the pooled rows (the caller's graph embeddings when they are on), then the head on them -- every NUM_TASK, every pooling
-        float* pooled = db.emb;
-        if (!pooled) {
-            if (int rc = pooled_.reserve((size_t)db.b.num_graphs * D)) return rc;
-            pooled = pooled_.p;
-        }
-        if (db.attn_pool) {  // OGB's attention readout (section 4.20): the gates of the rows, then their softmax-weighted sum per graph
-            {
-                ProfScope p(prof, "attn_gate", s);
-                if (int rc = launch_attn_gate(D, db.attn_pool, h5, attn_s_.p, hid_.p, n, exact_, db.range_flag, s)) return rc;
-            }
-            ProfScope p(prof, "attn_pool_rows", s);
-            if (int rc = launch_attn_pool_rows(D, h5, attn_s_.p, db.b.node_off, pooled, db.b.num_graphs, s)) return rc;
-        } else {
-            ProfScope p(prof, "mean_pool_rows", s);
-            const int grid = (db.b.num_graphs + 3) / 4;
-            if (db.pooling == POOL_OP_SUM) gw_pool_rows_kernel<D, POOL_OP_SUM><<<grid, 256, 0, s>>>(h5, db.b.node_off, pooled, db.b.num_graphs);
-            else if (db.pooling == POOL_OP_MAX) gw_pool_rows_kernel<D, POOL_OP_MAX><<<grid, 256, 0, s>>>(h5, db.b.node_off, pooled, db.b.num_graphs);
-            else gw_pool_rows_kernel<D, POOL_OP_MEAN><<<grid, 256, 0, s>>>(h5, db.b.node_off, pooled, db.b.num_graphs);
-        }
-        {
-            ProfScope p(prof, "pooled_head", s);
-            launch_pooled_head<D>(pooled, d_pw_, d_pb_, db.out, db.b.num_graphs, num_tasks_, s);
-        }
-        if (db.node_logits) {
-            ProfScope p(prof, "node_logits", s);
-            launch_node_logits_rows<D>(h5, d_pw_, d_pb_, db.node_logits, n, num_tasks_, s);
-        }
-        return 0;
+        return readout_.run(db, prof, s, db.node_emb ? db.node_emb : db.h[cur], exact_, hid_.p);
     }
 
 private:
@@ -762,26 +704,22 @@ private:
         vn_part_.release();
         hid_.release();
         node_graph_.release();
-        float** ptrs[] = {&d_tails_, &d_tab_, &d_proj_, &d_b0_, &d_nemb_, &d_wt_, &d_b_, &d_pw_, &d_pb_};
+        float** ptrs[] = {&d_tails_, &d_tab_, &d_proj_, &d_b0_, &d_nemb_, &d_wt_, &d_b_};
         for (auto p : ptrs)
             if (*p) { (void)hipFree(*p); *p = nullptr; }
         if (d_chunks_) { (void)hipFree(d_chunks_); d_chunks_ = nullptr; }
         esc_.release();
-        pooled_.release();
-        attn_s_.release();
+        readout_.release();
     }
     bool ready_ = false;
     bool exact_ = false;
-    int num_tasks_ = 1;
+    GwReadout<D> readout_;         // the head's weights, NUM_TASK, the pooled rows and the gates (wide_common.h)
     uint8_t* d_chunks_ = nullptr;  // the weight streams of gcw_layer_kernel: W_1 .. W_4, LAYER_BYTES each
     float* d_tails_ = nullptr;     // ... and per product b (pre-scaled, padded) and the output scale
     float* d_tab_ = nullptr;       // per layer: ecomb | root | BN scale | BN shift
     float *d_proj_ = nullptr, *d_b0_ = nullptr;  // W_0 applied to the node table, and b_0
     float *d_wt_ = nullptr, *d_b_ = nullptr;     // the exact form's W_1 .. W_4 as [K][O], and b_1 .. b_4
-    float *d_pw_ = nullptr, *d_pb_ = nullptr;
     GrowBuf esc_;     // [E] dinv[src_e] in CSR order
-    GrowBuf pooled_;  // the pooled rows [G][D] when graph embeddings are off
-    GrowBuf attn_s_;  // the attention readout's gates [N] (section 4.20)
     // OGB's virtual node (section 4.19)
     bool vn_on_ = false;              // flowgnn_set_gcn_virtual_node_dim is on (the tensors themselves: DeviceBatch::ogb_vn)
     std::vector<float> w0_, b0_, vn_e_;  // ... W_0, b_0 and E on the host, for b_0'

@@ -1117,6 +1117,10 @@ public:
         ogb_vn_ = on;
         return 0;
     }
+    size_t ogb_vn_blob_bytes() const override { return GIN_OGBVN_FLOATS * sizeof(float); }
+    void ogb_vn_pack(const float* vn_embedding, const float* w1, const float* b1, const float* w2, const float* b2, void* out) const override {
+        gin_ogbvn_pack(vn_embedding, w1, b1, w2, b2, static_cast<float*>(out));
+    }
     int set_num_tasks(int t) override {
         if (t < 1 || (t != 1 && qmode_)) return 8;
         if (t != num_tasks_) ready_ = false;  // graph_pred_weights / bias change shape: set the weights again

@@ -19,14 +19,19 @@
 // vector.  x_0 = h_0 + E is formed by the encoder's VN instance, x_{l+1} = relu(layer l) + vn_{l+1}[g(v)] in the epilogue of the layer
 // kernel's VN instance (vn_{l+1} depends on x_l alone, so it is complete before layer l is launched), t by gw_vn_pool_kernel (one read of
 // the rows) and the update MLP by the layer kernel's own MLP on G "rows" t (gw_vn_update_kernel: the body with the gather compiled out).
+//
+// Where things live: this file has the layer's kernels, the virtual node's kernels and their three launchers
+// (gin_wide_vn.h; forward() and gcn_wide.hip call the same ones), the weight stream's layout and the model object.  The readout, the
+// fragment packer, the transpose, the edge table and the fp32 MLP launch are wide_common.h's, shared with gcn_wide.hip and wide_attn.hip.
 #include <cmath>
 #include <cstring>
 #include <vector>
 
+#include "../../include/flowgnn.h"
 #include "common.h"
 #include "dense_split.h"
-#include "wide_attn.h"    // the attention readout's two launches (section 4.20)
-#include "wide_common.h"  // GW_WAVES / GW_ROWS, gw_relu, the LDS-DMA issue, the encoder, pooling and fp32 dense kernels (shared with gcn_wide.hip)
+#include "gin_wide_vn.h"  // the virtual node's launches, defined at the end of this file: forward() and gcn_wide.hip call them
+#include "wide_common.h"  // GW_WAVES / GW_ROWS, gw_relu, the LDS-DMA issue, the encoder, pooling and fp32 dense kernels, the packer, the readout
 
 namespace fg {
 namespace {
@@ -378,31 +383,15 @@ void gw_pack_layer(const float* w1, const float* b1, const float* w2, const floa
         if (s < M::KS2)
             for (int tl = 0; tl < 2; tl++) {
                 const int t = 2 * s + tl;
-                for (int lane = 0; lane < 64; lane++) {
-                    const int i = lane & 15, gk = lane >> 4, o = 16 * t + i;
-                    for (int ks = 0; ks < M::KS1; ks++)
-                        for (int e = 0; e < 8; e++) {
-                            const int f = 16 * (2 * ks + (e >> 2)) + 4 * gk + (e & 3);
-                            gw_put_split(ck + (size_t)((ks * 2 + tl) * 2) * 1024, lane, e, (o < M::H && f < D) ? w1[(size_t)o * D + f] * s1 : 0.0f);
-                        }
-                }
+                gw_pack_tile(w1, M::H, D, 16 * t, s1, 0, M::KS1, ck + tl * 2048, 4096);
                 for (int x = 0; x < 16; x++) {
                     const int o = 16 * t + x;
                     const float b = o < M::H ? b1[o] * s1 : 0.0f;
                     std::memcpy(ck + M::B1_OFF + tl * 64 + x * 4, &b, 4);
                 }
             }
-        if (s > 0) {
-            const int ks = s - 1;
-            for (int t2 = 0; t2 < M::T2; t2++)
-                for (int lane = 0; lane < 64; lane++) {
-                    const int i = lane & 15, gk = lane >> 4, d = 16 * t2 + i;
-                    for (int e = 0; e < 8; e++) {
-                        const int k = 16 * (2 * ks + (e >> 2)) + 4 * gk + (e & 3);
-                        gw_put_split(ck + M::W2_OFF + (size_t)(t2 * 2) * 1024, lane, e, (d < D && k < M::H) ? w2[(size_t)d * M::H + k] * s2 : 0.0f);
-                    }
-                }
-        }
+        if (s > 0)
+            for (int t2 = 0; t2 < M::T2; t2++) gw_pack_tile(w2, D, M::H, 16 * t2, s2, s - 1, 1, ck + M::W2_OFF + t2 * 2048, 0);
     }
     for (int x = 0; x < M::TAIL_FLOATS; x++) tail[x] = 0.0f;
     for (int x = 0; x < D; x++) tail[x] = b2[x] * s1 * s2;
@@ -439,12 +428,8 @@ void gw_vn_pack(const float* vn_embedding, const float* w1, const float* b1, con
         const float* W1 = w1 + (size_t)l * H * D;
         const float* W2 = w2 + (size_t)l * D * H;
         gw_pack_layer<D>(W1, b1 + (size_t)l * H, W2, b2 + (size_t)l * D, o, reinterpret_cast<float*>(o + B::TAIL_OFF));
-        float* w1t = reinterpret_cast<float*>(o + B::W1T_OFF);
-        float* w2t = reinterpret_cast<float*>(o + B::W2T_OFF);
-        for (int u = 0; u < H; u++)
-            for (int k = 0; k < D; k++) w1t[(size_t)k * H + u] = W1[(size_t)u * D + k];
-        for (int d = 0; d < D; d++)
-            for (int k = 0; k < H; k++) w2t[(size_t)k * D + d] = W2[(size_t)d * H + k];
+        gw_transpose(W1, H, D, reinterpret_cast<float*>(o + B::W1T_OFF));
+        gw_transpose(W2, D, H, reinterpret_cast<float*>(o + B::W2T_OFF));
         std::memcpy(o + B::B1_OFF, b1 + (size_t)l * H, (size_t)H * 4);
         std::memcpy(o + B::B2_OFF, b2 + (size_t)l * D, (size_t)D * 4);
     }
@@ -468,44 +453,23 @@ public:
     int num_weight_tensors() const override { return 8; }
     bool weights_ready() const override { return ready_; }
     void set_exact(bool on) override { exact_ = on; }
-    int set_num_tasks(int t) override {
-        if (t < 1) return 8;
-        if (t != num_tasks_) ready_ = false;  // graph_pred_weights / bias change shape: set the weights again
-        num_tasks_ = t;
-        return 0;
-    }
+    int set_num_tasks(int t) override { return readout_.set_num_tasks(t, ready_); }
 
     // host tensors: node_emb[173][D], edge_emb[5][13][D], w1[5][H][D], b1[5][H], w2[5][D][H], b2[5][D], pred_w[NUM_TASK][D], pred_b[NUM_TASK]
     int set_weights(const float* const* t) override {
         const float *nemb = t[0], *eemb = t[1], *w1 = t[2], *b1 = t[3], *w2 = t[4], *b2 = t[5], *pw = t[6], *pb = t[7];
         std::vector<float> v_nemb(nemb, nemb + (size_t)ND_FEATURE_TOTAL * D);
-        std::vector<float> v_pw(pw, pw + (size_t)num_tasks_ * D), v_pb(pb, pb + num_tasks_);
         std::vector<float> v_b1(b1, b1 + (size_t)GW_L * H), v_b2(b2, b2 + (size_t)GW_L * D);
         std::vector<float> ecomb((size_t)GW_L * EDGE_COMBOS * D);
         std::vector<float> w1t((size_t)GW_L * D * H), w2t((size_t)GW_L * H * D);  // the exact form's [K][O] copies
         std::vector<uint8_t> chunks((size_t)GW_L * M::LAYER_BYTES);
         std::vector<float> tails((size_t)GW_L * M::TAIL_FLOATS);
-        static const int ed_off[3] = {0, 5, 11};
         for (int l = 0; l < GW_L; l++) {
-            const float* E = eemb + (size_t)l * ED_FEATURE_PER_LAYER * D;
-            for (int a0 = 0; a0 < 5; a0++)
-                for (int a1 = 0; a1 < 6; a1++)
-                    for (int a2 = 0; a2 < 2; a2++) {
-                        const int code = (a0 * 6 + a1) * 2 + a2;
-                        for (int d = 0; d < D; d++) {
-                            float s = 0.0f;  // the order of GinModel::set_weights
-                            s += E[(ed_off[0] + a0) * D + d];
-                            s += E[(ed_off[1] + a1) * D + d];
-                            s += E[(ed_off[2] + a2) * D + d];
-                            ecomb[((size_t)l * EDGE_COMBOS + code) * D + d] = s;
-                        }
-                    }
+            gw_edge_combos(eemb + (size_t)l * ED_FEATURE_PER_LAYER * D, D, &ecomb[(size_t)l * EDGE_COMBOS * D]);
             const float* W1 = w1 + (size_t)l * H * D;
             const float* W2 = w2 + (size_t)l * D * H;
-            for (int o = 0; o < H; o++)
-                for (int k = 0; k < D; k++) w1t[(size_t)l * D * H + (size_t)k * H + o] = W1[(size_t)o * D + k];
-            for (int o = 0; o < D; o++)
-                for (int k = 0; k < H; k++) w2t[(size_t)l * H * D + (size_t)k * D + o] = W2[(size_t)o * H + k];
+            gw_transpose(W1, H, D, &w1t[(size_t)l * D * H]);
+            gw_transpose(W2, D, H, &w2t[(size_t)l * H * D]);
             gw_pack_layer<D>(W1, b1 + (size_t)l * H, W2, b2 + (size_t)l * D, chunks.data() + (size_t)l * M::LAYER_BYTES,
                              tails.data() + (size_t)l * M::TAIL_FLOATS);
         }
@@ -513,8 +477,7 @@ public:
         if ((rc = upload(&d_chunks_, chunks))) return rc;
         if ((rc = upload(&d_tails_, tails))) return rc;
         if ((rc = upload(&d_nemb_, v_nemb))) return rc;
-        if ((rc = upload(&d_pw_, v_pw))) return rc;
-        if ((rc = upload(&d_pb_, v_pb))) return rc;
+        if ((rc = readout_.upload_head(pw, pb))) return rc;
         if ((rc = upload(&d_ecomb_, ecomb))) return rc;
         if ((rc = upload(&d_w1t_, w1t))) return rc;
         if ((rc = upload(&d_w2t_, w2t))) return rc;
@@ -527,7 +490,7 @@ public:
     // the reference's file names (GIN/src/host_load.cc:24-58) with this width in place of 100
     int load_weights_dir(const char* dir) override {
         std::vector<float> w1((size_t)GW_L * H * D), b1((size_t)GW_L * H), w2((size_t)GW_L * D * H), b2((size_t)GW_L * D),
-            nemb((size_t)ND_FEATURE_TOTAL * D), eemb((size_t)GW_L * ED_FEATURE_PER_LAYER * D), pw((size_t)num_tasks_ * D), pb(num_tasks_);
+            nemb((size_t)ND_FEATURE_TOTAL * D), eemb((size_t)GW_L * ED_FEATURE_PER_LAYER * D), pw((size_t)readout_.num_tasks * D), pb(readout_.num_tasks);
         const std::string sfx = "_dim" + std::to_string(D) + ".bin";
         int rc;
         if ((rc = read_floats(dir, ("gin_ep1_mlp_1_weights" + sfx).c_str(), 0, w1.size(), w1.data()))) return rc;
@@ -546,9 +509,8 @@ public:
         const int n = db.b.n_tot;
         if (n <= 0) return 0;
         // OGB's virtual node (section 4.17): no launch rewrites the rows to add a vector -- x_0 = h_0 + E in the encoder, x_{l+1} in layer
-        // l's epilogue; vn_{l+1} depends on x_l alone, so it is complete before layer l is launched
-        using VB = GwVnBlob<D>;
-        const uint8_t* const vnb = reinterpret_cast<const uint8_t*>(db.ogb_vn);
+        // l's epilogue; vn_{l+1} depends on x_l alone, so it is complete before layer l is launched (the launches: gin_wide_vn.h)
+        const float* const vnb = db.ogb_vn;  // GwVnBlob's form; E is its first part
         const bool vn_on = vnb != nullptr;
         const int G = db.b.num_graphs;
         if (vn_on) {
@@ -557,11 +519,12 @@ public:
             if (int rc = vn_vec_[1].reserve((size_t)G * D)) return rc;
             if (int rc = node_graph_.reserve((size_t)n)) return rc;
         }
+        if (int rc = readout_.reserve(db)) return rc;
         {
             ProfScope p(prof, "atom_encoder", s);
             const int grid = grid_for((long long)n * M::C, 256, 256 * 8);
             if (vn_on)
-                gw_atom_encoder_vn_kernel<D><<<grid, 256, 0, s>>>(db.b.node_feature, d_nemb_, db.h[0], n, db.csr.err, reinterpret_cast<const float*>(vnb));
+                gw_atom_encoder_vn_kernel<D><<<grid, 256, 0, s>>>(db.b.node_feature, d_nemb_, db.h[0], n, db.csr.err, vnb);
             else
                 gw_atom_encoder_kernel<D><<<grid, 256, 0, s>>>(db.b.node_feature, d_nemb_, db.h[0], n, db.csr.err);
         }
@@ -577,24 +540,14 @@ public:
             const bool vn_next = vn_on && l < GW_VN_LAYERS;  // this layer's output rows get vn_{l+1} added
             float* const vnn = vn_vec_[l & 1].p;            // vn_{l+1}; vn_l is vn_vec_[(l - 1) & 1] (l = 0: E, stride 0)
             if (vn_next) {
-                const uint8_t* const wl = vnb + VB::E_BYTES + (size_t)l * VB::LAYER_STRIDE;
                 {
                     ProfScope p(prof, "gin_wide_vn_pool", s);  // t = sum of x_l's rows + vn_l (a sum whatever the readout's pooling is)
-                    gw_vn_pool_kernel<D><<<grid_for((long long)G * M::C, 256, 256 * 8), 256, 0, s>>>(
-                        db.h[cur], db.b.node_off, l == 0 ? reinterpret_cast<const float*>(vnb) : vn_vec_[(l - 1) & 1].p, l == 0 ? 0 : D, vn_t_.p,
-                        l == 0 ? node_graph_.p : nullptr, G);
+                    if (int rc = launch_gw_vn_pool(D, db.h[cur], db.b.node_off, l == 0 ? vnb : vn_vec_[(l - 1) & 1].p, l == 0 ? 0 : D, vn_t_.p,
+                                                   l == 0 ? node_graph_.p : nullptr, G, s))
+                        return rc;
                 }
                 ProfScope p(prof, "gin_wide_vn_update", s);
-                if (!exact_) {
-                    gw_vn_update_kernel<D><<<(int)ceil_div_ll(G, GW_ROWS), GW_WAVES * 64, 0, s>>>(
-                        vn_t_.p, vnn, wl, reinterpret_cast<const float*>(wl + VB::TAIL_OFF), G, db.range_flag);
-                } else {
-                    const int blocks = (int)ceil_div_ll(G, 8);
-                    gw_dense_f32_kernel<D, H><<<blocks, 256, 0, s>>>(vn_t_.p, reinterpret_cast<const float*>(wl + VB::W1T_OFF),
-                                                                    reinterpret_cast<const float*>(wl + VB::B1_OFF), hid_.p, G, 1);
-                    gw_dense_f32_kernel<H, D><<<blocks, 256, 0, s>>>(hid_.p, reinterpret_cast<const float*>(wl + VB::W2T_OFF),
-                                                                    reinterpret_cast<const float*>(wl + VB::B2_OFF), vnn, G, 1);
-                }
+                if (int rc = launch_gw_vn_update(D, vnb, l, vn_t_.p, vnn, hid_.p, G, exact_, db.range_flag, s)) return rc;
             }
             if (!exact_) {
                 ProfScope p(prof, "gin_wide_layer", s);
@@ -611,57 +564,26 @@ public:
                 ProfScope p(prof, "gin_wide_layer_f32", s);
                 gw_aggregate_kernel<D><<<grid_for((long long)n * M::C, 256, 256 * 8), 256, 0, s>>>(db.h[cur], db.scratch, db.csr.row_ptr, db.csr.src,
                                                                                                    db.csr.ecode, ecomb, n, self_s);
-                const int blocks = (int)ceil_div_ll(n, 8);
-                gw_dense_f32_kernel<D, H><<<blocks, 256, 0, s>>>(db.scratch, d_w1t_ + (size_t)l * D * H, d_b1_ + (size_t)l * H, hid_.p, n, 1);
-                gw_dense_f32_kernel<H, D><<<blocks, 256, 0, s>>>(hid_.p, d_w2t_ + (size_t)l * H * D, d_b2_ + (size_t)l * D, hn, n, relu_out);
-                if (vn_next) gw_vn_add_kernel<D><<<grid_for((long long)n * M::C, 256, 256 * 8), 256, 0, s>>>(hn, node_graph_.p, vnn, n);
+                launch_gw_mlp_f32<D>(db.scratch, d_w1t_ + (size_t)l * D * H, d_b1_ + (size_t)l * H, d_w2t_ + (size_t)l * H * D, d_b2_ + (size_t)l * D,
+                                     hid_.p, hn, n, relu_out, s);
+                if (vn_next)
+                    if (int rc = launch_gw_vn_add(D, hn, node_graph_.p, vnn, n, s)) return rc;
             }
             cur ^= 1;
         }
         db.final_h = cur;
         db.h_valid = !db.node_emb;
-        const float* const h5 = db.node_emb ? db.node_emb : db.h[cur];
-        // readout: the pooled rows (the caller's graph embeddings when they are on), then the head on them -- every NUM_TASK, every pooling
-        float* pooled = db.emb;
-        if (!pooled) {
-            if (int rc = pooled_.reserve((size_t)db.b.num_graphs * D)) return rc;
-            pooled = pooled_.p;
-        }
-        if (db.attn_pool) {  // OGB's attention readout (section 4.20): the gates of the rows, then their softmax-weighted sum per graph
-            if (int rc = attn_s_.reserve((size_t)n)) return rc;
-            {
-                ProfScope p(prof, "attn_gate", s);
-                if (int rc = launch_attn_gate(D, db.attn_pool, h5, attn_s_.p, hid_.p, n, exact_, db.range_flag, s)) return rc;
-            }
-            ProfScope p(prof, "attn_pool_rows", s);
-            if (int rc = launch_attn_pool_rows(D, h5, attn_s_.p, db.b.node_off, pooled, db.b.num_graphs, s)) return rc;
-        } else {
-            ProfScope p(prof, "mean_pool_rows", s);
-            const int grid = (db.b.num_graphs + 3) / 4;
-            if (db.pooling == POOL_OP_SUM) gw_pool_rows_kernel<D, POOL_OP_SUM><<<grid, 256, 0, s>>>(h5, db.b.node_off, pooled, db.b.num_graphs);
-            else if (db.pooling == POOL_OP_MAX) gw_pool_rows_kernel<D, POOL_OP_MAX><<<grid, 256, 0, s>>>(h5, db.b.node_off, pooled, db.b.num_graphs);
-            else gw_pool_rows_kernel<D, POOL_OP_MEAN><<<grid, 256, 0, s>>>(h5, db.b.node_off, pooled, db.b.num_graphs);
-        }
-        {
-            ProfScope p(prof, "pooled_head", s);
-            launch_pooled_head<D>(pooled, d_pw_, d_pb_, db.out, db.b.num_graphs, num_tasks_, s);
-        }
-        if (db.node_logits) {
-            ProfScope p(prof, "node_logits", s);
-            launch_node_logits_rows<D>(h5, d_pw_, d_pb_, db.node_logits, n, num_tasks_, s);
-        }
-        return 0;
+        return readout_.run(db, prof, s, db.node_emb ? db.node_emb : db.h[cur], exact_, hid_.p);
     }
 
 private:
     void free_all() {
-        float** ptrs[] = {&d_tails_, &d_nemb_, &d_pw_, &d_pb_, &d_ecomb_, &d_w1t_, &d_w2t_, &d_b1_, &d_b2_};
+        float** ptrs[] = {&d_tails_, &d_nemb_, &d_ecomb_, &d_w1t_, &d_w2t_, &d_b1_, &d_b2_};
         for (auto p : ptrs)
             if (*p) { (void)hipFree(*p); *p = nullptr; }
         if (d_chunks_) { (void)hipFree(d_chunks_); d_chunks_ = nullptr; }
         hid_.release();
-        pooled_.release();
-        attn_s_.release();
+        readout_.release();
         vn_t_.release();
         vn_vec_[0].release();
         vn_vec_[1].release();
@@ -669,18 +591,18 @@ private:
     }
     bool ready_ = false;
     bool exact_ = false;
-    int num_tasks_ = 1;
+    GwReadout<D> readout_;         // the head's weights, NUM_TASK, the pooled rows and the gates (wide_common.h)
     uint8_t* d_chunks_ = nullptr;  // the weight stream of gw_layer_kernel: GW_L x LAYER_BYTES
     float* d_tails_ = nullptr;     // ... and per layer b2 (pre-scaled, padded) and the output scale
-    float *d_nemb_ = nullptr, *d_pw_ = nullptr, *d_pb_ = nullptr, *d_ecomb_ = nullptr;
+    float *d_nemb_ = nullptr, *d_ecomb_ = nullptr;
     float *d_w1t_ = nullptr, *d_w2t_ = nullptr, *d_b1_ = nullptr, *d_b2_ = nullptr;  // the exact form's weights, [K][O]
     GrowBuf hid_;     // the exact form's hidden rows [N][H]
-    GrowBuf pooled_;  // the pooled rows [G][D] when graph embeddings are off
-    GrowBuf attn_s_;  // the attention readout's gates [N] (section 4.20)
-    GrowBuf vn_t_;         // OGB's virtual node: t [G][D], the update's input
+    GrowBuf vn_t_;        // OGB's virtual node: t [G][D], the update's input
     GrowBuf vn_vec_[2];    // ... vn_l and vn_{l+1} [G][D], alternating (both are live while layer l's update runs)
     GrowBufI node_graph_;  // ... and node -> graph [N], written by layer 0's pool launch of every pass
 };
+
+constexpr int GW_VN_D = FLOWGNN_EMB_DIM_OGB;  // the launchers' one width: the public constant's (the literal stays in make_gin_wide_model)
 
 }  // namespace
 
@@ -689,22 +611,8 @@ Model* make_gin_wide_model(int emb_dim) {
     return nullptr;
 }
 
-}  // namespace fg
-
-// ---------------------------------------------------------------- gin_wide_vn.h: the virtual node's launches, for gcn_wide.hip as well
-// (section 4.19).  The kernels above exist once, in this translation unit; GinWideModel::forward launches them itself, and these
-// launch the same instances.  They stand behind everything else so that the model's own kernels are compiled as they always were.
-// The width is the public constant's: the literal stays in make_gin_wide_model alone.
-#include "../../include/flowgnn.h"
-#include "gin_wide_vn.h"
-
-namespace fg {
-
-namespace {
-constexpr int GW_VN_D = FLOWGNN_EMB_DIM_OGB;
-template class GinWideModel<GW_VN_D>;  // (its members, and through forward() its kernels, are instantiated here, in front of the uses below)
-}  // namespace
-
+// ---------------------------------------------------------------- gin_wide_vn.h: the virtual node's launches, the only ones in this
+// file -- GinWideModel::forward goes through them, and so does gcn_wide.hip (section 4.19)
 size_t gw_vn_blob_bytes(int emb_dim) { return emb_dim == GW_VN_D ? GwVnBlob<GW_VN_D>::BYTES : 0; }
 
 void gw_vn_blob_pack(int emb_dim, const float* vn_embedding, const float* w1, const float* b1, const float* w2, const float* b2, void* out) {
@@ -715,19 +623,16 @@ int launch_gw_vn_update(int emb_dim, const void* blob, int l, const float* t, fl
                         int* range_flag, hipStream_t s) {
     if (emb_dim != GW_VN_D || l < 0 || l >= GW_VN_LAYERS) return FLOWGNN_ERR_UNSUPPORTED;
     if (num_graphs <= 0) return 0;
-    constexpr int D = GW_VN_D, H = 2 * D;
+    constexpr int D = GW_VN_D;
     using VB = GwVnBlob<D>;
     const uint8_t* const wl = static_cast<const uint8_t*>(blob) + VB::E_BYTES + (size_t)l * VB::LAYER_STRIDE;
-    if (!exact) {
+    if (!exact)
         gw_vn_update_kernel<D><<<(int)ceil_div_ll(num_graphs, GW_ROWS), GW_WAVES * 64, 0, s>>>(
             t, vn_next, wl, reinterpret_cast<const float*>(wl + VB::TAIL_OFF), num_graphs, range_flag);
-    } else {
-        const int blocks = (int)ceil_div_ll(num_graphs, 8);
-        gw_dense_f32_kernel<D, H><<<blocks, 256, 0, s>>>(t, reinterpret_cast<const float*>(wl + VB::W1T_OFF),
-                                                        reinterpret_cast<const float*>(wl + VB::B1_OFF), hid, num_graphs, 1);
-        gw_dense_f32_kernel<H, D><<<blocks, 256, 0, s>>>(hid, reinterpret_cast<const float*>(wl + VB::W2T_OFF),
-                                                        reinterpret_cast<const float*>(wl + VB::B2_OFF), vn_next, num_graphs, 1);
-    }
+    else
+        launch_gw_mlp_f32<D>(t, reinterpret_cast<const float*>(wl + VB::W1T_OFF), reinterpret_cast<const float*>(wl + VB::B1_OFF),
+                             reinterpret_cast<const float*>(wl + VB::W2T_OFF), reinterpret_cast<const float*>(wl + VB::B2_OFF), hid, vn_next,
+                             num_graphs, 1, s);
     return 0;
 }
 

@@ -1,7 +1,8 @@
 // gin_wide_vn.h -- OGB's virtual node at width 300, the parts that gcn_wide.hip runs as well (section 4.19):
-// the device form of the five tensors (GwVnBlob, gin_wide.hip), the update MLP on G rows t, and the exact re-run's pool and add on
-// rows.  The device code exists once, in gin_wide.hip's translation unit; these are its launchers.  emb_dim: 300, the one
-// instantiation (anything else: 0 bytes / FLOWGNN_ERR_UNSUPPORTED).
+// the device form of the five tensors (GwVnBlob, gin_wide.hip), the update MLP on G rows t, and the pool and add on rows.  The
+// device code exists once, in gin_wide.hip's translation unit; these are its only launchers -- GinWideModel::forward calls them as
+// gcn_wide.hip does, each under the caller's own profiler slot.  emb_dim: 300, the one instantiation (anything else: 0 bytes /
+// FLOWGNN_ERR_UNSUPPORTED).
 #pragma once
 #include "common.h"
 

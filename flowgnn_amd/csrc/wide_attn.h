@@ -1,5 +1,6 @@
 // wide_attn.h -- OGB's graph_pooling="attention" readout at width 300 (flowgnn_set_attention_pooling): the
-// gate's device form and the two launches that stand in for gw_pool_rows_kernel in gin_wide.hip's and gcn_wide.hip's forward.
+// gate's device form and the two launches that stand in for gw_pool_rows_kernel in the readout of gin_wide.hip and gcn_wide.hip
+// (GwReadout, wide_common.h).
 //   s[v] = w2 . relu(W1 r[v] + b1);  pooled[g] = sum_v softmax_g(s)[v] r[v], the sums in node order
 // The kernels exist once, in wide_attn.hip; the engine packs the blob through attn_pool_blob_pack and DeviceBatch::attn_pool points
 // at its device copy.

@@ -1,5 +1,6 @@
 // OGB's graph_pooling="attention" readout at width 300 (flowgnn_set_attention_pooling), for gin_wide.hip and
-// gcn_wide.hip alike: both call the two launch functions of wide_attn.h in place of their gw_pool_rows_kernel launch.
+// gcn_wide.hip alike: their one readout (GwReadout, wide_common.h) calls the two launch functions of wide_attn.h in place of its
+// gw_pool_rows_kernel launch.  The gate's stream is packed with wide_common.h's gw_pack_tile, as the layers' streams are.
 //   s[v]      = w2 . relu(W1 r[v] + b1)            W1 [H][D], b1 [H], w2 [H], H = 2 D (the gate's BatchNorm folded in by the exporter)
 //   pooled[g] = (sum_v e[v] r[v]) / (sum_v e[v]),  e[v] = exp(s[v] - max_{u in g} s[u]), both sums in node order
 //
@@ -12,15 +13,8 @@
 //   lane (j = lane & 15, g = lane >> 4): row j of the wave's tile; B operand of K-step ks, slot e: feature 16 (2 ks + (e >> 2)) + 4 g + (e & 3);
 //   C layout of hidden tile t, slot r: hidden unit 16 t + 4 g + r -- the four lane groups g of a row are summed once, at the end.
 // attn_pool_rows_kernel<D>: the shape of gw_pool_rows_kernel (wide_common.h), one wavefront per graph, no atomics.
-#include <cmath>
-#include <cstring>
-#include <vector>
-
-#include "common.h"
-#include "dense_split.h"
-#include "wide_common.h"
-#include "wide_attn.h"
 #include "../../include/flowgnn.h"
+#include "wide_common.h"  // (common.h, dense_split.h, wide_attn.h)
 
 namespace fg {
 namespace {
@@ -233,14 +227,7 @@ void ag_pack(const float* w1, const float* b1, const float* w2, uint8_t* out) {
         uint8_t* ck = out + (size_t)s * M::CHUNK_STRIDE;
         for (int tl = 0; tl < 2; tl++) {
             const int t = 2 * s + tl;
-            for (int lane = 0; lane < 64; lane++) {
-                const int i = lane & 15, gk = lane >> 4, o = 16 * t + i;
-                for (int ks = 0; ks < M::KS1; ks++)
-                    for (int e = 0; e < 8; e++) {
-                        const int f = 16 * (2 * ks + (e >> 2)) + 4 * gk + (e & 3);
-                        gw_put_split(ck + (size_t)((ks * 2 + tl) * 2) * 1024, lane, e, (o < H && f < D) ? w1[(size_t)o * D + f] * s1 : 0.0f);
-                    }
-            }
+            gw_pack_tile(w1, H, D, 16 * t, s1, 0, M::KS1, ck + tl * 2048, 4096);
             for (int x = 0; x < 16; x++) {
                 const int o = 16 * t + x;
                 const float b = o < H ? b1[o] * s1 : 0.0f;
@@ -250,9 +237,7 @@ void ag_pack(const float* w1, const float* b1, const float* w2, uint8_t* out) {
             }
         }
     }
-    float* w1t = reinterpret_cast<float*>(out + M::W1T_OFF);
-    for (int u = 0; u < H; u++)
-        for (int k = 0; k < D; k++) w1t[(size_t)k * H + u] = w1[(size_t)u * D + k];
+    gw_transpose(w1, H, D, reinterpret_cast<float*>(out + M::W1T_OFF));
     std::memcpy(out + M::B1F_OFF, b1, (size_t)H * 4);
     std::memcpy(out + M::W2F_OFF, w2, (size_t)H * 4);
 }
@@ -277,8 +262,7 @@ int launch_attn_gate(int emb_dim, const void* blob, const float* rows, float* s_
     if (!exact) {
         attn_gate_kernel<D><<<(int)ceil_div_ll(n_tot, GW_ROWS), GW_WAVES * 64, 0, s>>>(rows, s_out, b, n_tot, range_flag);
     } else {
-        gw_dense_f32_kernel<D, H><<<(int)ceil_div_ll(n_tot, 8), 256, 0, s>>>(rows, reinterpret_cast<const float*>(b + M::W1T_OFF),
-                                                                            reinterpret_cast<const float*>(b + M::B1F_OFF), hid, n_tot, 1);
+        launch_gw_dense_f32<D, H>(rows, reinterpret_cast<const float*>(b + M::W1T_OFF), reinterpret_cast<const float*>(b + M::B1F_OFF), hid, n_tot, 1, s);
         attn_dot_kernel<H><<<(int)ceil_div_ll(n_tot, 16), 256, 0, s>>>(hid, reinterpret_cast<const float*>(b + M::W2F_OFF), s_out, n_tot);
     }
     return 0;

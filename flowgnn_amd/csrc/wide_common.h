@@ -1,9 +1,16 @@
-// wide_common.h -- device code shared by the per-layer models of OGB's default width: gin_wide.hip (DESIGN.md sections 4.16, 4.17)
-// and gcn_wide.hip (section 4.18).  Templates on the width D; every kernel here has internal linkage, so each of the two translation
-// units compiles the instances it launches and nothing else.
+// wide_common.h -- what the per-layer models of OGB's default width share: gin_wide.hip (DESIGN.md sections 4.16, 4.17), gcn_wide.hip
+// (sections 4.18, 4.19) and wide_attn.hip (section 4.20).  Device side: the LDS-DMA issue, the fp32 dense kernel, the atom encoder and
+// the pooling kernel.  Host side: the fp32 launches, the split-f16 fragment packer, the transpose and the edge table of set_weights,
+// and the readout (GwReadout).  Templates on the width D; every kernel here has internal linkage, so each translation unit compiles
+// the instances it launches and nothing else.  The layer kernels' own bodies are NOT shared: section 4.21 says why.
 #pragma once
+#include <cmath>
+#include <cstring>
+#include <vector>
+
 #include "common.h"
 #include "dense_split.h"
+#include "wide_attn.h"  // the attention readout's two launches
 
 namespace fg {
 namespace {
@@ -123,6 +130,20 @@ __global__ __launch_bounds__(256) void gw_pool_rows_kernel(const float* __restri
     }
 }
 
+// ---------------------------------------------------------------- host side: launches, packing, the readout
+template <int K, int O>
+inline void launch_gw_dense_f32(const float* in, const float* wt, const float* b, float* out, int rows, int relu_out, hipStream_t s) {
+    gw_dense_f32_kernel<K, O><<<(int)ceil_div_ll(rows, 8), 256, 0, s>>>(in, wt, b, out, rows, relu_out);
+}
+
+// the fp32 MLP of the exact forms: out = act(W2 relu(W1 in + b1) + b2), D -> 2 D -> D, through hid [rows][2 D]; w1t / w2t are [K][O]
+template <int D>
+inline void launch_gw_mlp_f32(const float* in, const float* w1t, const float* b1, const float* w2t, const float* b2, float* hid, float* out,
+                              int rows, int relu_out, hipStream_t s) {
+    launch_gw_dense_f32<D, 2 * D>(in, w1t, b1, hid, rows, 1, s);
+    launch_gw_dense_f32<2 * D, D>(hid, w2t, b2, out, rows, relu_out, s);
+}
+
 inline float gw_pow2_scale(const float* w, size_t n) {
     float m = 0.0f;
     for (size_t i = 0; i < n; i++) m = std::fmax(m, std::fabs(w[i]));
@@ -136,6 +157,102 @@ inline void gw_put_split(uint8_t* frag, int lane, int e, float v) {
     std::memcpy(frag + lane * 16 + e * 2, &hi, 2);
     std::memcpy(frag + 1024 + lane * 16 + e * 2, &lo, 2);
 }
+
+// The A operand of the split-f16 products: rows row0 .. row0 + 15 of the row-major w [rows][cols], times `scale`, as `nks` hi/lo
+// fragment pairs (2 KiB each; K-steps ks0 .. ks0 + nks - 1) `stride` bytes apart from `base`.  Lane (i = lane & 15, gk = lane >> 4),
+// slot e of K-step ks holds w[row0 + i][16 (2 ks + (e >> 2)) + 4 gk + (e & 3)]; what lies outside the matrix is zero.
+inline void gw_pack_tile(const float* w, int rows, int cols, int row0, float scale, int ks0, int nks, uint8_t* base, size_t stride) {
+    for (int lane = 0; lane < 64; lane++) {
+        const int o = row0 + (lane & 15), gk = lane >> 4;
+        for (int ks = ks0; ks < ks0 + nks; ks++)
+            for (int e = 0; e < 8; e++) {
+                const int k = 16 * (2 * ks + (e >> 2)) + 4 * gk + (e & 3);
+                gw_put_split(base + (size_t)(ks - ks0) * stride, lane, e, (o < rows && k < cols) ? w[(size_t)o * cols + k] * scale : 0.0f);
+            }
+    }
+}
+
+// wt [K][O] = w [O][K] transposed: the exact forms read a weight row per k
+inline void gw_transpose(const float* w, int O, int K, float* wt) {
+    for (int o = 0; o < O; o++)
+        for (int k = 0; k < K; k++) wt[(size_t)k * O + o] = w[(size_t)o * K + k];
+}
+
+// out [60][d]: a layer's combined edge rows, row (a0 * 6 + a1) * 2 + a2 = E[a0] + E[5 + a1] + E[11 + a2] of its 13 edge rows E
+inline void gw_edge_combos(const float* E, int d, float* out) {
+    static const int ed_off[3] = {0, 5, 11};
+    for (int a0 = 0; a0 < 5; a0++)
+        for (int a1 = 0; a1 < 6; a1++)
+            for (int a2 = 0; a2 < 2; a2++)
+                for (int k = 0; k < d; k++) {
+                    float s = 0.0f;  // the order of GinModel::set_weights (GcnModel's is the same)
+                    s += E[(ed_off[0] + a0) * d + k];
+                    s += E[(ed_off[1] + a1) * d + k];
+                    s += E[(ed_off[2] + a2) * d + k];
+                    out[(size_t)((a0 * 6 + a1) * 2 + a2) * d + k] = s;
+                }
+}
+
+// The readout of both models: the pooled rows (the caller's graph embeddings when they are on), then the head on them -- every
+// NUM_TASK, every pooling -- and the per-node logit terms.  Owns the head's weights and the two buffers; a member of the model.
+template <int D>
+struct GwReadout {
+    int num_tasks = 1;
+    float *d_pw = nullptr, *d_pb = nullptr;  // graph_pred_weights [NUM_TASK][D], bias [NUM_TASK]
+    GrowBuf pooled;                          // the pooled rows [G][D] when graph embeddings are off
+    GrowBuf attn_s;                          // the attention readout's gates [N] (section 4.20)
+
+    int set_num_tasks(int t, bool& ready) {
+        if (t < 1) return 8;
+        if (t != num_tasks) ready = false;  // graph_pred_weights / bias change shape: set the weights again
+        num_tasks = t;
+        return 0;
+    }
+    int upload_head(const float* pw, const float* pb) {
+        if (int rc = upload(&d_pw, std::vector<float>(pw, pw + (size_t)num_tasks * D))) return rc;
+        return upload(&d_pb, std::vector<float>(pb, pb + num_tasks));
+    }
+    // in front of a forward's first launch: the gates [N], when the attention readout is on
+    int reserve(const DeviceBatch& db) { return db.attn_pool ? attn_s.reserve((size_t)db.b.n_tot) : 0; }
+    // h5: the rows the pool is taken over; hid: the exact attention gate's hidden rows [N][2 D]
+    int run(DeviceBatch& db, Profiler& prof, hipStream_t s, const float* h5, bool exact, float* hid) {
+        const int n = db.b.n_tot, G = db.b.num_graphs;
+        float* out = db.emb;
+        if (!out) {
+            if (int rc = pooled.reserve((size_t)G * D)) return rc;
+            out = pooled.p;
+        }
+        if (db.attn_pool) {  // OGB's attention readout (section 4.20): the gates of the rows, then their softmax-weighted sum per graph
+            {
+                ProfScope p(prof, "attn_gate", s);
+                if (int rc = launch_attn_gate(D, db.attn_pool, h5, attn_s.p, hid, n, exact, db.range_flag, s)) return rc;
+            }
+            ProfScope p(prof, "attn_pool_rows", s);
+            if (int rc = launch_attn_pool_rows(D, h5, attn_s.p, db.b.node_off, out, G, s)) return rc;
+        } else {
+            ProfScope p(prof, "mean_pool_rows", s);
+            const int grid = (G + 3) / 4;
+            if (db.pooling == POOL_OP_SUM) gw_pool_rows_kernel<D, POOL_OP_SUM><<<grid, 256, 0, s>>>(h5, db.b.node_off, out, G);
+            else if (db.pooling == POOL_OP_MAX) gw_pool_rows_kernel<D, POOL_OP_MAX><<<grid, 256, 0, s>>>(h5, db.b.node_off, out, G);
+            else gw_pool_rows_kernel<D, POOL_OP_MEAN><<<grid, 256, 0, s>>>(h5, db.b.node_off, out, G);
+        }
+        {
+            ProfScope p(prof, "pooled_head", s);
+            launch_pooled_head<D>(out, d_pw, d_pb, db.out, G, num_tasks, s);
+        }
+        if (db.node_logits) {
+            ProfScope p(prof, "node_logits", s);
+            launch_node_logits_rows<D>(h5, d_pw, d_pb, db.node_logits, n, num_tasks, s);
+        }
+        return 0;
+    }
+    void release() {
+        if (d_pw) { (void)hipFree(d_pw); d_pw = nullptr; }
+        if (d_pb) { (void)hipFree(d_pb); d_pb = nullptr; }
+        pooled.release();
+        attn_s.release();
+    }
+};
 
 }  // namespace
 }  // namespace fg
