@@ -145,6 +145,11 @@ struct GraphTiles {
     const int* bp_graph = nullptr;     // device [bp_tiles + 1]
     const int* bp_row = nullptr;       // device [bp_tiles + 1]
     int bp_tiles = 0;                  // 0: not built
+    // what a resident kernel and its tile build take (host side): the batch-order ranges (list / lrow null), or the bin-packed lists
+    struct Tiles { const int *row, *graph, *list, *lrow; int n_tiles; };
+    Tiles tiles(bool bin_packed) const {
+        return bin_packed ? Tiles{bp_row, bp_graph, bp_list, bp_lrow, bp_tiles} : Tiles{row_start, graph_start, nullptr, nullptr, n_tiles};
+    }
 };
 
 // Everything a model's forward needs about the resident batch.

@@ -16,6 +16,7 @@
 #include "device_common.h"
 #include "modelq.h"
 #include "dense_split.h"
+#include "dgn_plan.h"
 #include <cmath>
 #include <cstring>
 
@@ -24,10 +25,28 @@ namespace fg {
 // dgn_resident_emb_kernel, the instance that also stores every graph's pooled row (flowgnn_set_embeddings).  A second instance in
 // this translation unit or a pointer tested at run time both cost the default kernel registers (and 0.4 - 1.7 % of its time); this way
 // the default kernel is the code it was.  In that translation unit the host side is left out and the other kernels, with internal linkage and unused, are dropped.
-void launch_dgn_resident_emb(const void* resident_args, int grid, hipStream_t s);  // dgn_emb.hip
 // ... and dgn_rows.hip with FG_RESIDENT_ROWS_TU, for dgn_resident_rows_kernel: the instance that also stores every node's h_4 row, in
 // the caller's node order (flowgnn_set_node_embeddings).  That one tests the embeddings pointer at run time, to serve both at once.
-void launch_dgn_resident_rows(const void* resident_args, int grid, hipStream_t s);  // dgn_rows.hip
+// what a launch of the resident kernel takes, the ONE type of the three translation units: the kernel's DgnResidentArgs (below) adds nothing
+struct DgnResidentLaunch {
+    const uint32_t* rec;      // [n_tot + 128][12] (dgn_tile_build_kernel<true>)
+    const float* table;       // [173][100]
+    const uint8_t* wpk;       // 4 x DGN_FT_LAYER_BYTES (dgn_pack_fused_layer)
+    const int* tile_row;      // GraphTiles::row_start, or bp_row (the tile's first row in the record space)
+    const int* tile_graph;    // GraphTiles::graph_start, or bp_graph
+    const int* list;          // GraphTiles::bp_list (tile t = the graphs list[tile_graph[t]] ..), or null (tile t = graphs tile_graph[t] ..)
+    BatchView b;              // node counts for the readout; the edge list for rows with duplicate in-edges
+    const float* head;        // DGN_HEAD_BYTES: w1 [100][50] and w2 [50][25] transposed ([in][out]: unit along the lanes), b1, b2, w3, b3
+    float* out;               // [G]
+    float* emb;               // [G][100]: the pooled rows the head reads (flowgnn_set_embeddings), or null
+    int* range_flag;
+    int n_tiles;
+    float* node_emb;          // [N][100]: every node's h_4 row in the caller's node order (flowgnn_set_node_embeddings;
+                              // dgn_resident_rows_kernel stores them), or null.  Last: the other members keep their places
+};
+void launch_dgn_resident_default(const DgnResidentLaunch& a, int grid, hipStream_t s);  // dgn.hip
+void launch_dgn_resident_emb(const DgnResidentLaunch& a, int grid, hipStream_t s);      // dgn_emb.hip
+void launch_dgn_resident_rows(const DgnResidentLaunch& a, int grid, hipStream_t s);     // dgn_rows.hip
 #if defined(FG_RESIDENT_EMB_TU) || defined(FG_RESIDENT_ROWS_TU)
 #define FG_RESIDENT_KERNEL_TU 1
 namespace {
@@ -1087,22 +1106,7 @@ static_assert((DGN_HEAD_B3 + 1) * 4 <= DGN_HEAD_BYTES && DGN_HEAD_BYTES <= 2 * D
 #define DGNR_SKIP(bit) false
 #endif
 
-struct DgnResidentArgs {
-    const uint32_t* rec;      // [n_tot + 128][12] (dgn_tile_build_kernel<true>)
-    const float* table;       // [173][100]
-    const uint8_t* wpk;       // 4 x DGN_FT_LAYER_BYTES (dgn_pack_fused_layer)
-    const int* tile_row;      // GraphTiles::row_start, or bp_row (the tile's first row in the record space)
-    const int* tile_graph;    // GraphTiles::graph_start, or bp_graph
-    const int* list;          // GraphTiles::bp_list (tile t = the graphs list[tile_graph[t]] ..), or null (tile t = graphs tile_graph[t] ..)
-    BatchView b;              // node counts for the readout; the edge list for rows with duplicate in-edges
-    const float* head;        // DGN_HEAD_BYTES: w1 [100][50] and w2 [50][25] transposed ([in][out]: unit along the lanes), b1, b2, w3, b3
-    float* out;               // [G]
-    float* emb;               // [G][100]: the pooled rows the head reads (flowgnn_set_embeddings), or null
-    int* range_flag;
-    int n_tiles;
-    float* node_emb;          // [N][100]: every node's h_4 row in the caller's node order (flowgnn_set_node_embeddings;
-                              // dgn_resident_rows_kernel stores them), or null.  Last: the other members keep their places
-};
+struct DgnResidentArgs : DgnResidentLaunch {};  // the kernel's parameter: the same, in the namespace of this translation unit's kernel
 
 __global__ __launch_bounds__(512, 2) void dgn_resident_kernel(const DgnResidentArgs a) {
     constexpr int OFF_W = 2 * DGN_HT_BYTES, OFF_TAB = OFF_W + 2 * DGN_CHUNK, OFF_REC = OFF_TAB + ND_FEATURE_TOTAL * DGN_D * 4,
@@ -1655,11 +1659,11 @@ public:
         return set_weights(t);
     }
 
-    // row tiles + eig1[src_e] per CSR entry of the standalone aggregation kernel, once per batch pass
-    int prepare_aggregate(DeviceBatch& db, Profiler& prof, hipStream_t s) {
+    // row tiles + (edge_scalar: the batch has an edge) eig1[src_e] per CSR entry of the standalone aggregation kernel, once per batch pass
+    int prepare_aggregate(DeviceBatch& db, bool edge_scalar, Profiler& prof, hipStream_t s) {
         const int n = db.b.n_tot;
         if (int rc = make_tile_bounds(tiles_, db.b.node_off, db.b.num_graphs, n, tile_nominal_, tile_slack_, s)) return rc;
-        if (db.b.e_tot > 0) {
+        if (edge_scalar) {
             if (int rc = esc_.reserve((size_t)db.b.e_tot)) return rc;
             ProfScope p(prof, "edge_scalar", s);
             DgnAggPolicy::Params prm{db.node_eigen, db.csr.out_deg, nullptr};
@@ -1679,57 +1683,49 @@ public:
         rows = fused_ ? DGN_FT_ROWS : 0;
         edges = fused_ ? DGN_FT_EDGES : 0;
     }
-    bool wants_packed_tile_lists() const override { return fused_ && resident_ != 0 && binpack_ && !qmode_; }
 
-    bool use_fused(const DeviceBatch& db) const {
-        // tiles that are mostly empty (graphs of 65..128 nodes) waste MFMA columns: below 40 % full the two-kernel layer is used
-        return fused_ && split_ && !exact_ && db.gtiles.ok && db.gtiles.n_tiles > 0 && db.gtiles.fill >= 0.4;
+    // which kernels the next forward of this batch runs: decided in dgn_plan.h, from these values and nothing else
+    DgnPlanInput plan_input() const {
+        DgnPlanInput in;
+        in.fused = fused_; in.split = split_; in.mfma_agg = mfma_agg_; in.fold_readout = fold_readout_; in.rowinfo_direct = rowinfo_direct_;
+        in.resident = resident_; in.binpack = binpack_;
+        in.qmode = qmode_; in.keep_h = keep_h_; in.exact = exact_;
+        return in;
     }
-    bool use_mfma_agg(const DeviceBatch& db) const {
-        return mfma_agg_ < 0 ? (double)db.job_e >= 8.0 * (double)db.job_n : mfma_agg_ != 0;  // the JOB's density: every shard of a job takes the same path
+    DgnPlan plan(const DeviceBatch& db) const {
+        DgnPlanInput in = plan_input();
+        in.nonempty = db.b.n_tot > 0; in.eigen = db.node_eigen != nullptr;
+        in.tiles = db.gtiles.ok && db.gtiles.n_tiles > 0; in.fill = db.gtiles.fill; in.bp_lists = db.gtiles.bp_tiles > 0;
+        in.edges = db.b.e_tot > 0; in.job_n = db.job_n; in.job_e = db.job_e; in.csr_built = db.csr_built;
+        in.emb = db.emb != nullptr; in.node_emb = db.node_emb != nullptr;
+        return dgn_plan(in);
     }
-    // the graph-resident kernel: every layer's h stays on chip, nothing per node is written (flowgnn_get_h repeats the pass per layer).
-    // dgn_resident = 1: where the per-layer path would aggregate on the matrix pipe (dense tiles); 2: for every batch that tiles
-    bool use_resident(const DeviceBatch& db) const {
-        return resident_ != 0 && !keep_h_ && !qmode_ && db.node_eigen && use_fused(db) && (resident_ == 2 || use_mfma_agg(db));
-    }
-    // the matrix-pipe paths take what they need of the graph structure from the caller's edge list (dgn_rowinfo_kernel): no index build
-    bool needs_csr(const DeviceBatch& db) const override {
-        if (db.b.n_tot > 0 && use_resident(db)) return false;
-        return !(rowinfo_direct_ && !qmode_ && db.b.n_tot > 0 && db.node_eigen && use_fused(db) && use_mfma_agg(db));
-    }
+    bool needs_csr(const DeviceBatch& db) const override { return plan(db).needs_csr; }
+    bool wants_packed_tile_lists() const override { return dgn_wants_packed_tile_lists(plan_input()); }
 
     // two launches per step: per-row records from the caller's arrays, then everything else
-    int forward_resident(DeviceBatch& db, Profiler& prof, hipStream_t s) {
-        const int n = db.b.n_tot;
-        if (int rc = rec_.reserve(((size_t)n + DGN_FT_ROWS) * DGN_REC_DW)) return rc;  // (a tile's DMA reads 128 records whatever its rows)
+    int forward_resident(DeviceBatch& db, const DgnPlan& plan, Profiler& prof, hipStream_t s) {
+        if (int rc = rec_.reserve(((size_t)db.b.n_tot + DGN_FT_ROWS) * DGN_REC_DW)) return rc;  // (a tile's DMA reads 128 records whatever its rows)
         // bin-packed tile lists when flowgnn_set_batch made them (option dgn_binpack): fewer, fuller tiles of the same graphs
-        const bool bp = binpack_ && db.gtiles.bp_tiles > 0;
-        const int* t_row = bp ? db.gtiles.bp_row : db.gtiles.row_start;
-        const int* t_graph = bp ? db.gtiles.bp_graph : db.gtiles.graph_start;
-        const int* t_list = bp ? db.gtiles.bp_list : nullptr;
-        const int n_tiles = bp ? db.gtiles.bp_tiles : db.gtiles.n_tiles;
+        const GraphTiles::Tiles t = db.gtiles.tiles(plan.bin_packed);
         {
             ProfScope p(prof, "dgn_tile_build", s);
-            dgn_rowinfo_kernel<true><<<n_tiles, 256, 0, s>>>(db.b, t_row, t_graph, n_tiles, db.node_eigen, reinterpret_cast<uint32_t*>(rec_.p),
-                                                             nullptr, db.csr.err, nullptr, t_list);
+            dgn_rowinfo_kernel<true><<<t.n_tiles, 256, 0, s>>>(db.b, t.row, t.graph, t.n_tiles, db.node_eigen, reinterpret_cast<uint32_t*>(rec_.p),
+                                                               nullptr, db.csr.err, nullptr, t.list);
         }
-        DgnResidentArgs a;
-        a.rec = reinterpret_cast<const uint32_t*>(rec_.p);
-        a.table = d_emb_;
-        a.wpk = d_fused_;
-        a.tile_row = t_row; a.tile_graph = t_graph; a.list = t_list;
+        DgnResidentLaunch a;
+        a.rec = reinterpret_cast<const uint32_t*>(rec_.p); a.table = d_emb_; a.wpk = d_fused_; a.head = d_head_;
+        a.tile_row = t.row; a.tile_graph = t.graph; a.list = t.list; a.n_tiles = t.n_tiles;
         a.b = db.b;
-        a.head = d_head_;
-        a.out = db.out; a.emb = db.emb; a.range_flag = db.range_flag;
-        a.n_tiles = n_tiles;
-        a.node_emb = db.node_emb;
-        const int grid = n_tiles < 256 ? n_tiles : 256;  // persistent: one 8-wave workgroup per CU (157 KB of LDS)
+        a.out = db.out; a.emb = db.emb; a.node_emb = db.node_emb; a.range_flag = db.range_flag;
+        const int grid = t.n_tiles < 256 ? t.n_tiles : 256;  // persistent: one 8-wave workgroup per CU (157 KB of LDS)
         {
             ProfScope p(prof, "dgn_resident", s);
-            if (a.node_emb) launch_dgn_resident_rows(&a, grid, s);  // the row-storing instance (dgn_rows.hip), embeddings or not
-            else if (a.emb) launch_dgn_resident_emb(&a, grid, s);  // the same kernel's storing instance (dgn_emb.hip)
-            else dgn_resident_kernel<<<grid, 512, 0, s>>>(a);
+            switch (plan.instance) {
+            case DgnResidentInstance::Rows: launch_dgn_resident_rows(a, grid, s); break;  // the row-storing instance, embeddings or not
+            case DgnResidentInstance::Emb: launch_dgn_resident_emb(a, grid, s); break;
+            case DgnResidentInstance::Default: launch_dgn_resident_default(a, grid, s); break;
+            }
         }
         db.final_h = 0;
         db.h_valid = false;  // no per-node tensor leaves the kernel: flowgnn_get_h repeats the pass on the per-layer kernels
@@ -1740,24 +1736,21 @@ public:
         const int n = db.b.n_tot;
         if (n <= 0) return 0;
         if (!db.node_eigen) return 1;
-        agg_ready_ = false;  // tiles_ / esc_ are rebuilt by whichever float path runs below; a fixed-point pass leaves none
-        if (qmode_) return dgnq_forward(q_, db, prof, s);
+        const DgnPlan plan = this->plan(db);
+        agg_ready_ = false;  // tiles_ / esc_ are rebuilt where the plan prepares the two-kernel layer; every other pass leaves none
+        if (plan.path == DgnPath::FixedPoint) return dgnq_forward(q_, db, prof, s);
         db.h_valid = true;
-        if (use_resident(db)) return forward_resident(db, prof, s);
+        if (plan.path == DgnPath::Resident) return forward_resident(db, plan, prof, s);
         {
             ProfScope p(prof, "atom_encoder", s);
             atom_encoder_kernel<DGN_D><<<atom_encoder_grid(n, DGN_C), 512, 0, s>>>(db.b.node_feature, d_emb_, db.h[0], n, db.csr.err);
         }
-        const bool fused = use_fused(db);
-        agg_ready_ = false;
-        if (!fused)  // the fused layer takes eig1[src] from its own LDS tile: only the two-kernel layer needs these
-            if (int rc = prepare_aggregate(db, prof, s)) return rc;
+        if (plan.prepare_aggregate)  // the fused layer takes eig1[src] from its own LDS tile: only the two-kernel layer needs these
+            if (int rc = prepare_aggregate(db, plan.edge_scalar, prof, s)) return rc;
         int cur = 0;
-        bool pooled = false;  // the last layer left per-wave partial sums instead of its rows
         // matrix-pipe path without a CSR of this batch: the in-edge pass (adjacency masks, wsum, abssum, out-degrees) from the caller's
         // edge list, once per forward
-        const bool direct = fused && use_mfma_agg(db) && rowinfo_direct_ && !db.csr_built;
-        if (direct) {
+        if (plan.rowinfo_from_edge_list) {
             if (int rc = rowinfo_.reserve((size_t)n * 8)) return rc;
             if (int rc = dupflag_.reserve(1)) return rc;
             ProfScope p(prof, "dgn_rowinfo", s);
@@ -1770,16 +1763,14 @@ public:
         for (int l = 0; l < DGN_L; l++) {
             // (node embeddings: the last layer writes h_4 straight into the caller's buffer, and the readout pools it from there)
             float* const hn = (l == DGN_L - 1 && db.node_emb) ? db.node_emb : db.h[cur ^ 1];
-            if (fused) {
+            if (plan.fused_layers) {
                 ProfScope p(prof, "dgn_layer_fused", s);
                 const int grid = db.gtiles.n_tiles < 256 ? db.gtiles.n_tiles : 256;  // persistent: one 8-wave workgroup per CU (153 KB of LDS)
                 // dense tiles (kNN graphs: 16 in-edges per row, a third of a graph's block filled): both aggregates as MFMAs with the
                 // tile's adjacency; sparse ones (molecules, ~2 in-edges per row): the in-edge walk is cheaper than 20 MFMAs per K-step
-                const bool mfma_agg = use_mfma_agg(db);
-                if (mfma_agg) {
+                if (plan.mfma_aggregation) {
                     if (int rc = rowinfo_.reserve((size_t)n * 8)) return rc;
                     uint32_t* ri = reinterpret_cast<uint32_t*>(rowinfo_.p);
-                    const bool stored = direct || l > 0;  // rowinfo of this batch exists: every layer loads it
 #define DGN_MFMA_LAUNCH(I, P)                                                                                                                 \
     dgn_layer_mfma_kernel<I, P><<<grid, 512, 0, s>>>(db.h[cur], hn, db.csr.row_ptr, db.csr.src, db.csr.out_deg, db.node_eigen,       \
                                                      d_fused_ + (size_t)l * DGN_FT_LAYER_BYTES, db.gtiles.row_start, db.gtiles.n_tiles,       \
@@ -1788,16 +1779,15 @@ public:
                     // without a stored pass the first layer's launch makes and stores it (adjacency mask, wsum, abssum per row), the
                     // others load it; the last one keeps h' on chip and hands the readout per-wave partial sums (POOL) unless the rows
                     // are asked for
-                    const bool pool = l == DGN_L - 1 && fold_readout_ && !keep_h_ && !db.node_emb && DGN_L > 1;
+                    const bool pool = l == DGN_L - 1 && plan.pooled_last;
                     if (pool) {
                         if (int rc = ginfo_.reserve((size_t)n * 2)) return rc;
                         if (int rc = pool_part_.reserve((size_t)db.b.num_graphs * 8 * DGN_D)) return rc;
                         if (int rc = pool_cnt_.reserve((size_t)db.b.num_graphs)) return rc;
                         dgn_graph_info_kernel<<<(db.b.num_graphs + 255) / 256, 256, 0, s>>>(db.b.node_off, db.b.num_graphs,
                                                                                           reinterpret_cast<int2*>(ginfo_.p));
-                        pooled = true;
                     }
-                    if (!stored) DGN_MFMA_LAUNCH(1, false); else if (pool) DGN_MFMA_LAUNCH(2, true); else DGN_MFMA_LAUNCH(2, false);
+                    if (l == 0 && plan.first_layer_makes_rowinfo) DGN_MFMA_LAUNCH(1, false); else if (pool) DGN_MFMA_LAUNCH(2, true); else DGN_MFMA_LAUNCH(2, false);
 #undef DGN_MFMA_LAUNCH
                     cur ^= 1;
                     continue;
@@ -1815,7 +1805,7 @@ public:
             {
                 ProfScope p(prof, "dgn_dense", s);
                 const int waves = (int)ceil_div_ll(n, 16);
-                if (split_ && !exact_) {
+                if (plan.split_dense) {
                     const long long wgs = ceil_div_ll(n, 256);
                     dense200_res_relu_split_kernel<DGN_OT><<<(int)(wgs < 256 ? wgs : 256), 1024, 0, s>>>(
                         db.scratch, db.h[cur], hn, d_split_ + (size_t)l * dense200_split_bytes(DGN_OT), n, DGN_D, db.range_flag);
@@ -1827,22 +1817,17 @@ public:
             cur ^= 1;
         }
         db.final_h = cur;
-        db.h_valid = !pooled && !db.node_emb;  // pooled: h[cur] was never written; flowgnn_get_h repeats the pass with the rows kept
-        const float* const h4 = db.node_emb ? db.node_emb : db.h[cur];
+        db.h_valid = !plan.pooled_last && !db.node_emb;  // pooled: h[cur] was never written; flowgnn_get_h repeats the pass with the rows kept
+        // the readout: from the last layer's per-wave partial sums, or from its rows; with the pooled rows stored too, or not
+        using Readout = void (*)(const float*, const int*, const int*, const float*, const float*, const float*, const float*, const float*, const float*,
+                                 float*, int, float*);
+        static const Readout readout[2][2] = {{dgn_pool_part_mlp3_kernel<true, true>, dgn_pool_part_mlp3_kernel<false, true>},
+                                              {dgn_pool_part_mlp3_kernel<true>, dgn_pool_part_mlp3_kernel<false>}};  // [!emb_readout][!pooled_last]
+        const float* const rows = plan.pooled_last ? pool_part_.p : db.node_emb ? db.node_emb : db.h[cur];
         {
             ProfScope p(prof, "pool_mlp3", s);
-            if (pooled && db.emb)
-                dgn_pool_part_mlp3_kernel<true, true><<<grid_for(db.b.num_graphs, 4, 256 * 4), 256, 0, s>>>(pool_part_.p, pool_cnt_.p, db.b.node_off, d_w0_, d_b0_, d_w1_,
-                                                                                                d_b1_, d_w2_, d_b2_, db.out, db.b.num_graphs, db.emb);
-            else if (db.emb)
-                dgn_pool_part_mlp3_kernel<false, true><<<grid_for(db.b.num_graphs, 4, 256 * 4), 256, 0, s>>>(h4, nullptr, db.b.node_off, d_w0_, d_b0_, d_w1_,
-                                                                                                 d_b1_, d_w2_, d_b2_, db.out, db.b.num_graphs, db.emb);
-            else if (pooled)
-                dgn_pool_part_mlp3_kernel<true><<<grid_for(db.b.num_graphs, 4, 256 * 4), 256, 0, s>>>(pool_part_.p, pool_cnt_.p, db.b.node_off, d_w0_, d_b0_, d_w1_,
-                                                                                          d_b1_, d_w2_, d_b2_, db.out, db.b.num_graphs);
-            else
-                dgn_pool_part_mlp3_kernel<false><<<grid_for(db.b.num_graphs, 4, 256 * 4), 256, 0, s>>>(h4, nullptr, db.b.node_off, d_w0_, d_b0_, d_w1_,
-                                                                                           d_b1_, d_w2_, d_b2_, db.out, db.b.num_graphs);
+            readout[!plan.emb_readout][!plan.pooled_last]<<<grid_for(db.b.num_graphs, 4, 256 * 4), 256, 0, s>>>(
+                rows, plan.pooled_last ? pool_cnt_.p : nullptr, db.b.node_off, d_w0_, d_b0_, d_w1_, d_b1_, d_w2_, d_b2_, db.out, db.b.num_graphs, db.emb);
         }
         return 0;
     }
@@ -1868,7 +1853,7 @@ public:
         if (layer < 0 || layer >= DGN_L) return 1;
         if (!agg_ready_) {  // the last forward ran the fused layers
             Profiler none;
-            if (int rc = prepare_aggregate(db, none, s)) return rc;
+            if (int rc = prepare_aggregate(db, db.b.e_tot > 0, none, s)) return rc;
         }
         launch_aggregate(db, db.h[db.final_h], s);
         return 0;
@@ -1928,15 +1913,16 @@ Model* make_dgn_model() { return new DgnModel(); }
 #ifdef FG_RESIDENT_KERNEL_TU
 }  // namespace
 #endif
-#ifdef FG_RESIDENT_EMB_TU
-void launch_dgn_resident_emb(const void* resident_args, int grid, hipStream_t s) {
-    dgn_resident_kernel<<<grid, 512, 0, s>>>(*static_cast<const DgnResidentArgs*>(resident_args));
-}
+// this translation unit's instance of dgn_resident_kernel, under the launcher's name that goes with it
+#if defined(FG_RESIDENT_EMB_TU)
+void launch_dgn_resident_emb(
+#elif defined(FG_RESIDENT_ROWS_TU)
+void launch_dgn_resident_rows(
+#else
+void launch_dgn_resident_default(
 #endif
-#ifdef FG_RESIDENT_ROWS_TU
-void launch_dgn_resident_rows(const void* resident_args, int grid, hipStream_t s) {
-    dgn_resident_kernel<<<grid, 512, 0, s>>>(*static_cast<const DgnResidentArgs*>(resident_args));
+    const DgnResidentLaunch& a, int grid, hipStream_t s) {
+    dgn_resident_kernel<<<grid, 512, 0, s>>>(DgnResidentArgs{a});
 }
-#endif
 
 }  // namespace fg

@@ -1404,13 +1404,10 @@ public:
         GcnResidentLaunch a;
         a.onepass = plan.one_pass;
         a.layers = d_res_; a.pool_w = d_pw_; a.pool_b = d_pb_;
-        a.tile_row = db.gtiles.row_start; a.tile_graph = db.gtiles.graph_start; a.n_tiles = db.gtiles.n_tiles;
+        const GraphTiles::Tiles t = db.gtiles.tiles(plan.bin_packed);  // (bin-packed: behind the one-pass front end alone)
+        a.tile_row = t.row; a.tile_graph = t.graph; a.n_tiles = t.n_tiles; a.list = t.list; a.lrow = t.lrow;
         a.node_off = db.b.node_off; a.out = db.out; a.range_flag = db.range_flag; a.ablate = ablate_;
         if (plan.one_pass) {  // two launches: descriptors from the caller's arrays, then everything else
-            if (plan.bin_packed) {
-                a.tile_row = db.gtiles.bp_row; a.tile_graph = db.gtiles.bp_graph; a.n_tiles = db.gtiles.bp_tiles;
-                a.list = db.gtiles.bp_list; a.lrow = db.gtiles.bp_lrow;
-            }
             if (int rc = desc_.reserve(((size_t)a.n_tiles * GCND_BYTES + 3) / 4)) return rc;
             a.desc = reinterpret_cast<const uint8_t*>(desc_.p);
             a.enc_tab = reinterpret_cast<const float4*>(d_enc_tab_);

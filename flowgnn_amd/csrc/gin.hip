@@ -848,21 +848,19 @@ public:
         if (one_pass(db)) {
             // bin-packed tile lists when flowgnn_set_batch made them (option gin_binpack): fewer, fuller tiles of the same graphs -- everything
             // the resident kernel reads is written by the tile build in tile order, and a row's sums depend on the row alone: the same bits
-            const bool bp = binpack_ && db.gtiles.bp_tiles > 0;
-            const int* t_row = bp ? db.gtiles.bp_row : db.gtiles.row_start;
-            const int* t_graph = bp ? db.gtiles.bp_graph : db.gtiles.graph_start;
-            const int n_tiles = bp ? db.gtiles.bp_tiles : db.gtiles.n_tiles;
+            const GraphTiles::Tiles t = db.gtiles.tiles(binpack_ && db.gtiles.bp_tiles > 0);
+            const int n_tiles = t.n_tiles;
             if (int rc = perm_.reserve((size_t)n_tiles * (GIN_RESIDENT_DESC_BYTES / 4))) return rc;
             if (int rc = enc_idx_.reserve((size_t)n)) return rc;
-            GinTileBuild tb{db.b, enc_idx_.p, d_enc_tab_, db.csr.err, bp ? db.gtiles.bp_list : nullptr, bp ? db.gtiles.bp_lrow : nullptr};
+            GinTileBuild tb{db.b, enc_idx_.p, d_enc_tab_, db.csr.err, t.list, t.lrow};
             {
                 ProfScope p(prof, "gin_tile_build", s);
-                launch_gin_tile_build(tb, t_row, t_graph, reinterpret_cast<uint8_t*>(perm_.p), n_tiles, virtual_node_, resident_order_, s);
+                launch_gin_tile_build(tb, t.row, t.graph, reinterpret_cast<uint8_t*>(perm_.p), n_tiles, virtual_node_, resident_order_, s);
             }
             ProfScope p(prof, "gin_resident", s);  // the whole model
             GinResidentLaunch a = resident_launch(db);  // (no h0, no CSR: the tile loader reads the caller's arrays)
-            a.tile_row = t_row;
-            a.tile_graph = t_graph;
+            a.tile_row = t.row;
+            a.tile_graph = t.graph;
             a.tile_desc = reinterpret_cast<uint8_t*>(perm_.p);
             a.n_tiles = n_tiles;
             a.out = db.out;

@@ -18,6 +18,7 @@
 #include "device_common.h"
 #include "modelq.h"
 #include "dense_split.h"
+#include "pna_plan.h"
 #include <cmath>
 #include <cstring>
 
@@ -26,10 +27,36 @@ namespace fg {
 // pna_resident_emb_kernel, the instance that also stores every graph's pooled row (flowgnn_set_embeddings).  A second instance in
 // this translation unit or a pointer tested at run time both cost the default kernel registers (and 0.4 - 1.7 % of its time); this way
 // the default kernel is the code it was.  In that translation unit the host side is left out and the other kernels, with internal linkage and unused, are dropped.
-void launch_pna_resident_emb(const void* resident_args, int grid, hipStream_t s);  // pna_emb.hip
 // ... and pna_rows.hip with FG_RESIDENT_ROWS_TU, for pna_resident_rows_kernel: the instance that also stores every node's h_4 row, in
 // the caller's node order (flowgnn_set_node_embeddings).  That one tests the embeddings pointer at run time, to serve both at once.
-void launch_pna_resident_rows(const void* resident_args, int grid, hipStream_t s);  // pna_rows.hip
+constexpr int PNA_L = 4;
+// what a launch of the resident kernel takes, the ONE type of the three translation units: the kernel's PnaResidentArgs (below) adds nothing
+struct PnaResidentLaunch {
+    const uint32_t* fidx;      // [rows][3]: nine encoder table rows per row as bytes, tile order (pna_tile_build_kernel), or null: ...
+    const int* node_feature;   // ... [N][9], the caller's features (batch-order tiles only)
+    const int* list;           // GraphTiles::bp_list / bp_lrow (bin-packed tiles), or null: tile t = the graphs tile_graph[t] ..
+    const int* lrow;
+    const float* nemb;         // [173][80]
+    const uint8_t* desc;       // pna_tile_build_kernel / pna_tile_desc_kernel
+    const uint8_t* wpk;        // feature-major weight stream, 4 layers x 10 chunks
+    const float* bias;         // [4][80]
+    const int* tile_row;       // GraphTiles::row_start
+    const int* tile_graph;     // GraphTiles::graph_start
+    const int* node_off;       // [G + 1]
+    const float *w1t, *b1, *w2t, *b2, *w3, *b3;  // head, w1 / w2 transposed ([in][out]: coalesced over the output lanes)
+    float* out;                // [G]
+    float* emb;                // [G][80]: the pooled rows the head reads (flowgnn_set_embeddings; pna_resident_emb_kernel stores them), or null
+    int* range_flag;
+    int* err;
+    float avg_deg;
+    float oscale[PNA_L];
+    int n_tiles;
+    float* node_emb;           // [N][80]: every node's h_4 row in the caller's node order (flowgnn_set_node_embeddings;
+                               // pna_resident_rows_kernel stores them), or null.  Last: the other members keep their places
+};
+void launch_pna_resident_default(const PnaResidentLaunch& a, int grid, hipStream_t s);  // pna.hip
+void launch_pna_resident_emb(const PnaResidentLaunch& a, int grid, hipStream_t s);      // pna_emb.hip
+void launch_pna_resident_rows(const PnaResidentLaunch& a, int grid, hipStream_t s);     // pna_rows.hip
 #if defined(FG_RESIDENT_EMB_TU) || defined(FG_RESIDENT_ROWS_TU)
 #define FG_RESIDENT_KERNEL_TU 1
 namespace {
@@ -46,7 +73,6 @@ constexpr bool RESIDENT_ROWS = false;
 #endif
 
 constexpr int PNA_D = 80;
-constexpr int PNA_L = 4;
 constexpr int PNA_C = PNA_D / 4;   // 20 float4 chunks per row
 constexpr int PNA_OT = 5;          // 16-row output tiles
 constexpr int PNA_NA = 4;          // aggregators, reference enum order: mean, min, max, std
@@ -808,29 +834,7 @@ __global__ __launch_bounds__(PNA_FT_WAVES * 64, 4) void pna_layer_fused_kernel(c
 //             pool_mlp3_kernel (even rows | odd rows, then the two halves).
 // HBM traffic per tile: 36 B of node features per row, the 6 KiB descriptor (CSR slice + out-degrees), one logit per graph.
 // Same bits as the per-layer path (atom_encoder + 4 x pna_layer_fused + pool_mlp3): same operations in the same order.
-struct PnaResidentArgs {
-    const uint32_t* fidx;      // [rows][3]: nine encoder table rows per row as bytes, tile order (pna_tile_build_kernel), or null: ...
-    const int* node_feature;   // ... [N][9], the caller's features (batch-order tiles only)
-    const int* list;           // GraphTiles::bp_list / bp_lrow (bin-packed tiles), or null: tile t = the graphs tile_graph[t] ..
-    const int* lrow;
-    const float* nemb;         // [173][80]
-    const uint8_t* desc;       // pna_tile_build_kernel / pna_tile_desc_kernel
-    const uint8_t* wpk;        // feature-major weight stream, 4 layers x 10 chunks
-    const float* bias;         // [4][80]
-    const int* tile_row;       // GraphTiles::row_start
-    const int* tile_graph;     // GraphTiles::graph_start
-    const int* node_off;       // [G + 1]
-    const float *w1t, *b1, *w2t, *b2, *w3, *b3;  // head, w1 / w2 transposed ([in][out]: coalesced over the output lanes)
-    float* out;                // [G]
-    float* emb;                // [G][80]: the pooled rows the head reads (flowgnn_set_embeddings; pna_resident_emb_kernel stores them), or null
-    int* range_flag;
-    int* err;
-    float avg_deg;
-    float oscale[PNA_L];
-    int n_tiles;
-    float* node_emb;           // [N][80]: every node's h_4 row in the caller's node order (flowgnn_set_node_embeddings;
-                               // pna_resident_rows_kernel stores them), or null.  Last: the other members keep their places
-};
+struct PnaResidentArgs : PnaResidentLaunch {};  // the kernel's parameter: the same, in the namespace of this translation unit's kernel
 
 // development only (-DFLOWGNN_DEV -DPNAR_TIMING=<bits>, scripts/dev/variant.sh): TIMING variants that leave a phase out and compute wrong
 // results on purpose -- 1 no encoder (h_0 = 0), 2 no readout, 4 no gathers, 8 no MFMAs.  Never part of the shipped library.
@@ -1189,53 +1193,56 @@ public:
         edges = fused_ ? PNA_FT_EDGES : 0;
     }
 
-    // tiles that are mostly empty (graphs of 65..128 nodes) waste MFMA columns: below 40 % full the two-kernel layer is used
-    bool use_fused(const DeviceBatch& db) const {
-        return fused_ && !qmode_ && split_ && !exact_ && db.gtiles.ok && db.gtiles.n_tiles > 0 && db.gtiles.fill >= 0.4;
+    // which kernels the next forward of this batch runs: decided in pna_plan.h, from these values and nothing else
+    PnaPlanInput plan_input() const {
+        PnaPlanInput in;
+        in.fused = fused_; in.split = split_; in.resident = resident_; in.tile_build = tile_build_; in.binpack = binpack_;
+        in.qmode = qmode_; in.keep_h = keep_h_; in.exact = exact_;
+        return in;
     }
-    // the graph-resident kernel: every layer's h stays in LDS, nothing per node is written (flowgnn_get_h repeats the pass per layer)
-    bool use_resident(const DeviceBatch& db) const { return resident_ && !keep_h_ && use_fused(db); }
-    // pna_tile_build=0 keeps the index build + pna_tile_desc_kernel in front of the resident kernel
-    bool needs_csr(const DeviceBatch& db) const override { return !(tile_build_ && use_resident(db)); }
+    PnaPlan plan(const DeviceBatch& db) const {
+        PnaPlanInput in = plan_input();
+        in.tiles = db.gtiles.ok && db.gtiles.n_tiles > 0; in.fill = db.gtiles.fill; in.bp_lists = db.gtiles.bp_tiles > 0;
+        in.emb = db.emb != nullptr; in.node_emb = db.node_emb != nullptr;
+        return pna_plan(in);
+    }
+    bool needs_csr(const DeviceBatch& db) const override { return plan(db).needs_csr; }
     void set_keep_h(bool on) override { keep_h_ = on; }
-    bool wants_packed_tile_lists() const override { return binpack_ && tile_build_ && resident_ && fused_ && !qmode_; }
+    bool wants_packed_tile_lists() const override { return pna_wants_packed_tile_lists(plan_input()); }
 
-    int forward_resident(DeviceBatch& db, Profiler& prof, hipStream_t s) {
+    int forward_resident(DeviceBatch& db, const PnaPlan& plan, Profiler& prof, hipStream_t s) {
         // bin-packed tile lists when flowgnn_set_batch made them (option pna_binpack; tile-build path only): fewer, fuller tiles of the
         // same graphs.  A row's aggregates and a graph's pooling depend on the row / the graph alone: the same bits.
-        const bool bp = binpack_ && tile_build_ && db.gtiles.bp_tiles > 0;
-        const int* t_row = bp ? db.gtiles.bp_row : db.gtiles.row_start;
-        const int* t_graph = bp ? db.gtiles.bp_graph : db.gtiles.graph_start;
-        const int n_tiles = bp ? db.gtiles.bp_tiles : db.gtiles.n_tiles;
-        if (int rc = desc_.reserve(((size_t)n_tiles * PNA_DESC_BYTES + 3) / 4)) return rc;
-        if (tile_build_) {  // two launches per step: descriptors from the caller's arrays, then everything else (no CSR in HBM)
+        const GraphTiles::Tiles t = db.gtiles.tiles(plan.bin_packed);
+        if (int rc = desc_.reserve(((size_t)t.n_tiles * PNA_DESC_BYTES + 3) / 4)) return rc;
+        if (plan.one_pass) {  // two launches per step: descriptors from the caller's arrays, then everything else (no CSR in HBM)
             if (int rc = fidx_.reserve((size_t)db.b.n_tot * 3)) return rc;
             ProfScope p(prof, "pna_tile_build", s);
-            pna_tile_build_kernel<<<n_tiles, 256, 0, s>>>(db.b, t_row, t_graph, n_tiles, reinterpret_cast<uint8_t*>(desc_.p), db.csr.err,
-                                                          bp ? db.gtiles.bp_list : nullptr, reinterpret_cast<uint32_t*>(fidx_.p));
-        } else {
+            pna_tile_build_kernel<<<t.n_tiles, 256, 0, s>>>(db.b, t.row, t.graph, t.n_tiles, reinterpret_cast<uint8_t*>(desc_.p), db.csr.err, t.list,
+                                                          reinterpret_cast<uint32_t*>(fidx_.p));
+        } else {  // pna_tile_build=0 keeps the index build + pna_tile_desc_kernel in front of the resident kernel
             ProfScope p(prof, "pna_tile_desc", s);
-            pna_tile_desc_kernel<<<n_tiles, 256, 0, s>>>(db.csr.row_ptr, db.csr.src, db.csr.out_deg, t_row, reinterpret_cast<uint8_t*>(desc_.p), n_tiles);
+            pna_tile_desc_kernel<<<t.n_tiles, 256, 0, s>>>(db.csr.row_ptr, db.csr.src, db.csr.out_deg, t.row, reinterpret_cast<uint8_t*>(desc_.p), t.n_tiles);
         }
-        PnaResidentArgs a;
-        a.fidx = tile_build_ ? reinterpret_cast<const uint32_t*>(fidx_.p) : nullptr;
-        a.list = bp ? db.gtiles.bp_list : nullptr;
-        a.lrow = bp ? db.gtiles.bp_lrow : nullptr;
+        PnaResidentLaunch a;
+        a.fidx = plan.one_pass ? reinterpret_cast<const uint32_t*>(fidx_.p) : nullptr;
+        a.list = t.list; a.lrow = t.lrow;
         a.node_feature = db.b.node_feature; a.nemb = d_nemb_; a.desc = reinterpret_cast<const uint8_t*>(desc_.p);
         a.wpk = d_stream_; a.bias = d_cb_;
-        a.tile_row = t_row; a.tile_graph = t_graph; a.node_off = db.b.node_off;
+        a.tile_row = t.row; a.tile_graph = t.graph; a.node_off = db.b.node_off;
         a.w1t = d_w1t_; a.b1 = d_b1_; a.w2t = d_w2t_; a.b2 = d_b2_; a.w3 = d_w3_; a.b3 = d_b3_;
         a.out = db.out; a.emb = db.emb; a.range_flag = db.range_flag; a.err = db.csr.err;
         a.avg_deg = avg_deg_;
         for (int l = 0; l < PNA_L; l++) a.oscale[l] = oscale_[l];
-        a.n_tiles = n_tiles;
-        a.node_emb = db.node_emb;
-        const int grid = n_tiles < 256 ? n_tiles : 256;  // persistent: one 16-wave workgroup per CU
+        a.n_tiles = t.n_tiles; a.node_emb = db.node_emb;
+        const int grid = t.n_tiles < 256 ? t.n_tiles : 256;  // persistent: one 16-wave workgroup per CU
         {
             ProfScope p(prof, "pna_resident", s);
-            if (a.node_emb) launch_pna_resident_rows(&a, grid, s);  // the row-storing instance (pna_rows.hip), embeddings or not
-            else if (a.emb) launch_pna_resident_emb(&a, grid, s);  // the same kernel's storing instance (pna_emb.hip)
-            else pna_resident_kernel<<<grid, PNA_FT_WAVES * 64, 0, s>>>(a);
+            switch (plan.instance) {
+            case PnaResidentInstance::Rows: launch_pna_resident_rows(a, grid, s); break;  // the row-storing instance, embeddings or not
+            case PnaResidentInstance::Emb: launch_pna_resident_emb(a, grid, s); break;
+            case PnaResidentInstance::Default: launch_pna_resident_default(a, grid, s); break;
+            }
         }
         db.final_h = 0;
         db.h_valid = false;  // no per-node tensor leaves the kernel: flowgnn_get_h repeats the pass on the per-layer kernels
@@ -1245,9 +1252,10 @@ public:
     int forward(DeviceBatch& db, Profiler& prof, hipStream_t s) override {
         const int n = db.b.n_tot;
         if (n <= 0) return 0;
-        if (qmode_) return pnaq_forward(q_, db, prof, s);
+        const PnaPlan plan = this->plan(db);
+        if (plan.path == PnaPath::FixedPoint) return pnaq_forward(q_, db, prof, s);
         db.h_valid = true;
-        if (use_resident(db)) return forward_resident(db, prof, s);
+        if (plan.path == PnaPath::Resident) return forward_resident(db, plan, prof, s);
         {
             ProfScope p(prof, "atom_encoder", s);
             atom_encoder_kernel<PNA_D><<<atom_encoder_grid(n, PNA_C), 512, 0, s>>>(db.b.node_feature, d_nemb_,
@@ -1255,11 +1263,10 @@ public:
         }
         if (int rc = make_tile_bounds(tiles_, db.b.node_off, db.b.num_graphs, n, tile_nominal_, tile_slack_, s)) return rc;
         int cur = 0;
-        const bool fused = use_fused(db);
         for (int l = 0; l < PNA_L; l++) {
             // (node embeddings: the last layer writes h_4 straight into the caller's buffer, and the readout pools it from there)
             float* const hn = (l == PNA_L - 1 && db.node_emb) ? db.node_emb : db.h[cur ^ 1];
-            if (fused) {
+            if (plan.fused_layers) {
                 ProfScope p(prof, "pna_layer_fused", s);
                 const int grid = db.gtiles.n_tiles < 256 ? db.gtiles.n_tiles : 256;  // persistent: one 16-wave workgroup per CU (151 KB of LDS)
                 if (l == 0) {  // the tiles' CSR slices as the layer kernel stages them, once for the four layers
@@ -1281,7 +1288,7 @@ public:
             {
                 ProfScope p(prof, "pna_dense", s);
                 const int waves = (int)ceil_div_ll(n, 16);
-                if (split_ && !exact_) {
+                if (plan.split_dense) {
                     pna_dense_split_kernel<<<(int)ceil_div_ll(n, 128), 512, 0, s>>>(db.scratch, db.h[cur], hn, db.csr.out_deg,
                                                                                     d_split_ + (size_t)l * PNA_SPLIT_LAYER_BYTES,
                                                                                     d_cb_ + (size_t)l * PNA_D, avg_deg_, oscale_[l], n,
@@ -1298,7 +1305,7 @@ public:
         db.h_valid = !db.node_emb;  // (a tap repeats the pass with the rows in h[])
         {
             ProfScope p(prof, "pool_mlp3", s);
-            if (db.emb)
+            if (plan.emb_readout)
                 pool_mlp3_kernel<PNA_D, 40, 20, true><<<(db.b.num_graphs + 3) / 4, 256, 0, s>>>(h4, db.b.node_off, d_w1_, d_b1_, d_w2_, d_b2_,
                                                                                                 d_w3_, d_b3_, db.out, db.b.num_graphs, db.emb);
             else
@@ -1406,15 +1413,16 @@ Model* make_pna_model() { return new PnaModel(); }
 #ifdef FG_RESIDENT_KERNEL_TU
 }  // namespace
 #endif
-#ifdef FG_RESIDENT_EMB_TU
-void launch_pna_resident_emb(const void* resident_args, int grid, hipStream_t s) {
-    pna_resident_kernel<<<grid, PNA_FT_WAVES * 64, 0, s>>>(*static_cast<const PnaResidentArgs*>(resident_args));
-}
+// this translation unit's instance of pna_resident_kernel, under the launcher's name that goes with it
+#if defined(FG_RESIDENT_EMB_TU)
+void launch_pna_resident_emb(
+#elif defined(FG_RESIDENT_ROWS_TU)
+void launch_pna_resident_rows(
+#else
+void launch_pna_resident_default(
 #endif
-#ifdef FG_RESIDENT_ROWS_TU
-void launch_pna_resident_rows(const void* resident_args, int grid, hipStream_t s) {
-    pna_resident_kernel<<<grid, PNA_FT_WAVES * 64, 0, s>>>(*static_cast<const PnaResidentArgs*>(resident_args));
+    const PnaResidentLaunch& a, int grid, hipStream_t s) {
+    pna_resident_kernel<<<grid, PNA_FT_WAVES * 64, 0, s>>>(PnaResidentArgs{a});
 }
-#endif
 
 }  // namespace fg

@@ -178,7 +178,7 @@ def plans(tmp_path_factory):
 
     def run(ogb_vn):
         out = np.zeros(n, np.uint32)
-        lib.gvp_gcn_bulk(words.ctypes.data_as(C.POINTER(C.c_uint32)), n, rp.FILLS.ctypes.data_as(C.POINTER(C.c_double)), ogb_vn,
+        lib.gvp_gcn_bulk(words.ctypes.data_as(C.POINTER(C.c_uint32)), n, rp.FILLS["GCN"].ctypes.data_as(C.POINTER(C.c_double)), ogb_vn,
                          out.ctypes.data_as(C.POINTER(C.c_uint32)))
         res, at = {}, 0
         for k, bits in fields:
