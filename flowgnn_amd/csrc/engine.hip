@@ -1322,11 +1322,15 @@ static int set_width(flowgnn_engine* e, const char* fn, int emb_dim) {
     const std::string who = std::string(fn) + ": ";
     const bool gcn = e->model_id == FLOWGNN_MODEL_GCN;
     if (emb_dim == e->emb_dim) return FLOWGNN_OK;
-    if (emb_dim != FLOWGNN_EMB_DIM_REFERENCE) {
-        if (e->numeric_mode != FLOWGNN_NUMERIC_F32) {
-            e->err = who + "a numeric mode other than FLOWGNN_NUMERIC_F32 is on (flowgnn_set_numeric_mode), and width 300 has neither fixed-point nor f16 kernels";
-            return FLOWGNN_ERR_UNSUPPORTED;
-        }
+    if (e->numeric_mode != FLOWGNN_NUMERIC_F32) {  // (either direction: the mode is the model object's, and the call swaps the object)
+        if (emb_dim != FLOWGNN_EMB_DIM_REFERENCE)
+            e->err = who + "a numeric mode other than FLOWGNN_NUMERIC_F32 is on (flowgnn_set_numeric_mode), and the width changes in "
+                     "FLOWGNN_NUMERIC_F32 only: width 300 has no fixed-point kernels, and GIN's f16 mode at width 300 is set at that width, through "
+                     "flowgnn_set_numeric_mode_dim";
+        else
+            e->err = who + "a numeric mode other than FLOWGNN_NUMERIC_F32 is on at width 300 (flowgnn_set_numeric_mode_dim), and the width changes "
+                     "in FLOWGNN_NUMERIC_F32 only: set that mode, change the width, set the numeric mode again";
+        return FLOWGNN_ERR_UNSUPPORTED;
     }
     if (e->ogb_vn_on) {  // (either direction: the tensors belong to a width -- turn it off, change the width, set it again)
         e->err = who + "OGB's virtual node is on (" + (gcn ? "flowgnn_set_gcn_virtual_node / flowgnn_set_gcn_virtual_node_dim" : "flowgnn_set_ogb_virtual_node / flowgnn_set_ogb_virtual_node_dim") +
@@ -1395,16 +1399,26 @@ int flowgnn_set_model_emb_dim(flowgnn_engine* e, int emb_dim) {
 
 int flowgnn_emb_dim(const flowgnn_engine* e) { return e ? e->emb_dim : -1; }
 
-int flowgnn_set_numeric_mode(flowgnn_engine* e, int mode) {
-    if (!e) return FLOWGNN_ERR_ARG;
+// flowgnn_set_numeric_mode and flowgnn_set_numeric_mode_dim at the engine's width.  with_dim: the call carried the width -- what lets
+// a GIN engine at width 300 take FLOWGNN_NUMERIC_F16 (gin_wide_f16.hip); the call without it keeps refusing
+// every mode but F32 there.  At width 100 the two are one.
+static int set_numeric_mode(flowgnn_engine* e, int mode, bool with_dim) {
     for (const Output& o : kOutputs)
         if (mode == FLOWGNN_NUMERIC_Q6_10 && o.no_fixed_point && is_on(e, o)) {
             e->err = o.no_fixed_point;
             return FLOWGNN_ERR_UNSUPPORTED;
         }
     if (mode != FLOWGNN_NUMERIC_F32 && off_default_width(e)) {
-        e->err = "flowgnn_set_numeric_mode: the engine's width is 300 (flowgnn_set_emb_dim / flowgnn_set_model_emb_dim), which has neither fixed-point nor f16 kernels";
-        return FLOWGNN_ERR_UNSUPPORTED;
+        if (!with_dim) {
+            e->err = "flowgnn_set_numeric_mode: the engine's width is 300 (flowgnn_set_emb_dim / flowgnn_set_model_emb_dim), which has no fixed-point "
+                     "kernels; GIN's f16 mode at that width goes through flowgnn_set_numeric_mode_dim";
+            return FLOWGNN_ERR_UNSUPPORTED;
+        }
+        if (mode != FLOWGNN_NUMERIC_F16 || e->model_id != FLOWGNN_MODEL_GIN) {
+            e->err = "flowgnn_set_numeric_mode_dim: at width 300 the modes are FLOWGNN_NUMERIC_F32 and, for FLOWGNN_MODEL_GIN, FLOWGNN_NUMERIC_F16; "
+                     "there are no fixed-point kernels at that width, and GCN has no f16 kernels";
+            return FLOWGNN_ERR_UNSUPPORTED;
+        }
     }
     if (mode == FLOWGNN_NUMERIC_Q6_10 && e->pooling != FLOWGNN_POOL_MEAN) {
         e->err = "flowgnn_set_numeric_mode: the pooling is not the mean (flowgnn_set_pooling), and the fixed-point readout is the reference's mean";
@@ -1424,6 +1438,34 @@ int flowgnn_set_numeric_mode(flowgnn_engine* e, int mode) {
     if (rc) e->err = "flowgnn_set_numeric_mode: unknown mode, a mode this model does not have (f16: GIN / GIN-VN only), or the fixed-point "
                      "readout is single-task and NUM_TASK != 1";
     return rc;
+}
+
+int flowgnn_set_numeric_mode(flowgnn_engine* e, int mode) {
+    if (!e) return FLOWGNN_ERR_ARG;
+    return set_numeric_mode(e, mode, false);
+}
+
+// The call that carries the width: emb_dim 100 IS the call above (the same state, kernels and bits); 300 reaches gin_wide_f16.hip's
+// kernels on a GIN engine.  emb_dim must be the engine's width.
+int flowgnn_set_numeric_mode_dim(flowgnn_engine* e, int emb_dim, int mode) {
+    if (!e) return FLOWGNN_ERR_ARG;
+    const std::string who = "flowgnn_set_numeric_mode_dim: ";
+    if (emb_dim != FLOWGNN_EMB_DIM_REFERENCE && emb_dim != FLOWGNN_EMB_DIM_OGB) {
+        e->err = who + "emb_dim is " + std::to_string(emb_dim) + "; the widths are FLOWGNN_EMB_DIM_REFERENCE (100) and FLOWGNN_EMB_DIM_OGB (300)";
+        return FLOWGNN_ERR_ARG;
+    }
+    if (mode != FLOWGNN_NUMERIC_F32 && mode != FLOWGNN_NUMERIC_Q6_10 && mode != FLOWGNN_NUMERIC_F16) {
+        e->err = who + "mode is " + std::to_string(mode) + "; the modes are FLOWGNN_NUMERIC_F32 (0), FLOWGNN_NUMERIC_Q6_10 (1) and FLOWGNN_NUMERIC_F16 (2)";
+        return FLOWGNN_ERR_ARG;
+    }
+    // (flowgnn_emb_dim is the model's own figure for the models without a choice of width -- GAT's 16; their width here is 100)
+    const int width = off_default_width(e) ? e->emb_dim : FLOWGNN_EMB_DIM_REFERENCE;
+    if (emb_dim != width) {
+        e->err = who + "emb_dim is " + std::to_string(emb_dim) + " and the engine's width is " + std::to_string(width) +
+                 " (flowgnn_set_emb_dim / flowgnn_set_model_emb_dim)";
+        return FLOWGNN_ERR_ARG;
+    }
+    return set_numeric_mode(e, mode, true);
 }
 
 int flowgnn_set_pooling(flowgnn_engine* e, int mode) {

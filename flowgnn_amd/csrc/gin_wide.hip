@@ -23,6 +23,8 @@
 // Where things live: this file has the layer's kernels, the virtual node's kernels and their three launchers
 // (gin_wide_vn.h; forward() and gcn_wide.hip call the same ones), the weight stream's layout and the model object.  The readout, the
 // fragment packer, the transpose, the edge table and the fp32 MLP launch are wide_common.h's, shared with gcn_wide.hip and wide_attn.hip.
+// FLOWGNN_NUMERIC_F16 at this width (flowgnn_set_numeric_mode_dim, section 4.22): the layer's two single-product kernels live in
+// gin_wide_f16.hip behind gin_wide_f16.h's launcher; this file packs their hi-only weight stream and chooses between the launches.
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -30,6 +32,7 @@
 #include "../../include/flowgnn.h"
 #include "common.h"
 #include "dense_split.h"
+#include "gin_wide_f16.h"  // FLOWGNN_NUMERIC_F16 at this width: the hi-only stream's layout and the launcher of gin_wide_f16.hip's kernels
 #include "gin_wide_vn.h"  // the virtual node's launches, defined at the end of this file: forward() and gcn_wide.hip call them
 #include "wide_common.h"  // GW_WAVES / GW_ROWS, gw_relu, the LDS-DMA issue, the encoder, pooling and fp32 dense kernels, the packer, the readout
 
@@ -398,6 +401,23 @@ void gw_pack_layer(const float* w1, const float* b1, const float* w2, const floa
     tail[M::T2 * 16] = 1.0f / (s1 * s2);
 }
 
+// FLOWGNN_NUMERIC_F16 (section 4.22): a layer's hi-only stream (GwF16Dims, gin_wide_f16.h) out of its split stream -- the hi fragments
+// r(W s) and the pre-scaled b1 as gw_pack_layer left them, the lo fragments dropped; the tail is shared as it is
+template <int D>
+void gw_pack_layer_f16(const uint8_t* split, uint8_t* out) {
+    using M = GwDims<D>;
+    using F = GwF16Dims<D>;
+    static_assert(F::STEPS == M::STEPS && F::KS1 == M::KS1 && F::T2 == M::T2, "the two streams cut a layer into the same steps");
+    std::memset(out, 0, F::LAYER_BYTES);
+    for (int s = 0; s < M::STEPS; s++) {
+        const uint8_t* ck = split + (size_t)s * M::CHUNK_STRIDE;
+        uint8_t* o = out + (size_t)s * F::CHUNK_STRIDE;
+        for (int f = 0; f < M::KS1 * 2; f++) std::memcpy(o + f * 1024, ck + f * 2048, 1024);
+        for (int t2 = 0; t2 < M::T2; t2++) std::memcpy(o + F::W2_OFF + t2 * 1024, ck + M::W2_OFF + t2 * 2048, 1024);
+        std::memcpy(o + F::B1_OFF, ck + M::B1_OFF, 2 * 16 * 4);
+    }
+}
+
 // OGB's virtual node at this width (flowgnn_set_ogb_virtual_node_dim, section 4.17): the device form of the five tensors, a layout
 // of this file's own (gin_ogbvn.h's is the 100-wide one).  In bytes, every part a multiple of 16:
 //   E [D] floats | per update l (0..3): the weight stream of gw_pack_layer<D> (LAYER_BYTES) | its tail (TAIL_FLOATS floats)
@@ -438,6 +458,7 @@ void gw_vn_pack(const float* vn_embedding, const float* w1, const float* b1, con
 template <int D>
 class GinWideModel : public Model {
     using M = GwDims<D>;
+    using F16 = GwF16Dims<D>;
     static constexpr int H = M::H;
 
 public:
@@ -453,6 +474,13 @@ public:
     int num_weight_tensors() const override { return 8; }
     bool weights_ready() const override { return ready_; }
     void set_exact(bool on) override { exact_ = on; }
+    // FLOWGNN_NUMERIC_F16 (flowgnn_set_numeric_mode_dim, section 4.22): the five layers run gin_wide_f16.hip's kernels on the hi-only
+    // stream, which set_weights packs beside the split one whatever the mode is -- so the two calls come in either order
+    int set_numeric_mode(int mode) override {
+        if (mode != FLOWGNN_NUMERIC_F32 && mode != FLOWGNN_NUMERIC_F16) return FLOWGNN_ERR_UNSUPPORTED;
+        f16_ = mode == FLOWGNN_NUMERIC_F16;
+        return 0;
+    }
     int set_num_tasks(int t) override { return readout_.set_num_tasks(t, ready_); }
 
     // host tensors: node_emb[173][D], edge_emb[5][13][D], w1[5][H][D], b1[5][H], w2[5][D][H], b2[5][D], pred_w[NUM_TASK][D], pred_b[NUM_TASK]
@@ -463,6 +491,7 @@ public:
         std::vector<float> ecomb((size_t)GW_L * EDGE_COMBOS * D);
         std::vector<float> w1t((size_t)GW_L * D * H), w2t((size_t)GW_L * H * D);  // the exact form's [K][O] copies
         std::vector<uint8_t> chunks((size_t)GW_L * M::LAYER_BYTES);
+        std::vector<uint8_t> chunks16((size_t)GW_L * F16::LAYER_BYTES);
         std::vector<float> tails((size_t)GW_L * M::TAIL_FLOATS);
         for (int l = 0; l < GW_L; l++) {
             gw_edge_combos(eemb + (size_t)l * ED_FEATURE_PER_LAYER * D, D, &ecomb[(size_t)l * EDGE_COMBOS * D]);
@@ -472,9 +501,11 @@ public:
             gw_transpose(W2, D, H, &w2t[(size_t)l * H * D]);
             gw_pack_layer<D>(W1, b1 + (size_t)l * H, W2, b2 + (size_t)l * D, chunks.data() + (size_t)l * M::LAYER_BYTES,
                              tails.data() + (size_t)l * M::TAIL_FLOATS);
+            gw_pack_layer_f16<D>(chunks.data() + (size_t)l * M::LAYER_BYTES, chunks16.data() + (size_t)l * F16::LAYER_BYTES);
         }
         int rc;
         if ((rc = upload(&d_chunks_, chunks))) return rc;
+        if ((rc = upload(&d_chunks16_, chunks16))) return rc;
         if ((rc = upload(&d_tails_, tails))) return rc;
         if ((rc = upload(&d_nemb_, v_nemb))) return rc;
         if ((rc = readout_.upload_head(pw, pb))) return rc;
@@ -549,7 +580,13 @@ public:
                 ProfScope p(prof, "gin_wide_vn_update", s);
                 if (int rc = launch_gw_vn_update(D, vnb, l, vn_t_.p, vnn, hid_.p, G, exact_, db.range_flag, s)) return rc;
             }
-            if (!exact_) {
+            if (!exact_ && f16_) {
+                ProfScope p(prof, "gin_wide_layer_f16", s);
+                if (int rc = launch_gw_layer_f16(D, db.h[cur], hn, db.csr.row_ptr, db.csr.src, db.csr.ecode, ecomb,
+                                                 d_chunks16_ + (size_t)l * F16::LAYER_BYTES, d_tails_ + (size_t)l * M::TAIL_FLOATS, n, relu_out,
+                                                 self_s, db.range_flag, vn_next ? node_graph_.p : nullptr, vn_next ? vnn : nullptr, s))
+                    return rc;
+            } else if (!exact_) {
                 ProfScope p(prof, "gin_wide_layer", s);
                 const int grid = (int)ceil_div_ll(n, GW_ROWS);
                 if (vn_next)
@@ -582,6 +619,7 @@ private:
         for (auto p : ptrs)
             if (*p) { (void)hipFree(*p); *p = nullptr; }
         if (d_chunks_) { (void)hipFree(d_chunks_); d_chunks_ = nullptr; }
+        if (d_chunks16_) { (void)hipFree(d_chunks16_); d_chunks16_ = nullptr; }
         hid_.release();
         readout_.release();
         vn_t_.release();
@@ -591,9 +629,11 @@ private:
     }
     bool ready_ = false;
     bool exact_ = false;
+    bool f16_ = false;  // flowgnn_set_numeric_mode_dim(FLOWGNN_NUMERIC_F16)
     GwReadout<D> readout_;         // the head's weights, NUM_TASK, the pooled rows and the gates (wide_common.h)
     uint8_t* d_chunks_ = nullptr;  // the weight stream of gw_layer_kernel: GW_L x LAYER_BYTES
-    float* d_tails_ = nullptr;     // ... and per layer b2 (pre-scaled, padded) and the output scale
+    uint8_t* d_chunks16_ = nullptr;  // the hi-only stream of gin_wide_f16.hip's kernels: GW_L x GwF16Dims::LAYER_BYTES
+    float* d_tails_ = nullptr;     // ... and per layer b2 (pre-scaled, padded) and the output scale (both streams)
     float *d_nemb_ = nullptr, *d_ecomb_ = nullptr;
     float *d_w1t_ = nullptr, *d_w2t_ = nullptr, *d_b1_ = nullptr, *d_b2_ = nullptr;  // the exact form's weights, [K][O]
     GrowBuf hid_;     // the exact form's hidden rows [N][H]

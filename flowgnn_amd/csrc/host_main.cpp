@@ -25,7 +25,8 @@
 //                from the weights directory and run OGB's graph_pooling="attention" readout (flowgnn_set_attention_pooling)
 //   --emb-dim    GCN: 300 = OGB's default width (flowgnn_set_model_emb_dim), gcn_ep1_dim300.weights.all.bin is read.
 //                GIN: 300 = OGB's default width (flowgnn_set_emb_dim): the weights directory's dim300 files are read (with --eps,
-//                gin_ep1_eps_dim300.bin); 100 (default) = the reference's width
+//                gin_ep1_eps_dim300.bin); 100 (default) = the reference's width.  With --numeric, 300 sends the mode through
+//                flowgnn_group_set_numeric_mode_dim: GIN takes f16 at that width (beside --eps, --ogb-vn and --attn-pool as before)
 //   --eig        DGN: directory holding the eigenvector text files g%d.txt                 (default eig, DGN/src/host_load.cc:178)
 //   --compute-eig DGN: compute node_eigen from the graphs on the GPU (flowgnn_laplacian_eigen, on the first engine) and read no --eig DIR
 //   XCLBIN       accepted and ignored, so `./host <xclbin>`-style command lines keep working
@@ -180,7 +181,8 @@ int main(int argc, char** argv) {
     rc = flowgnn_group_load_weights_dir(eng, wdir.c_str());
     if (rc) { fprintf(stderr, "loading weights failed: %d %s\n", rc, flowgnn_group_last_error(eng)); return EXIT_FAILURE; }
     if (numeric != FLOWGNN_NUMERIC_F32) {  // the reference's ap_fixed<16,6> bit patterns, or f16 MLP operands (GIN / GIN-VN)
-        rc = flowgnn_group_set_numeric_mode(eng, numeric);
+        // --emb-dim 300: through the call that carries the width (GIN's f16 mode at that width, gin_wide_f16.hip)
+        rc = emb_dim != FLOWGNN_EMB_DIM_REFERENCE ? flowgnn_group_set_numeric_mode_dim(eng, emb_dim, numeric) : flowgnn_group_set_numeric_mode(eng, numeric);
         if (rc) { fprintf(stderr, "numeric mode: %d %s\n", rc, flowgnn_group_last_error(eng)); return EXIT_FAILURE; }
     }
     if (pooling != FLOWGNN_POOL_MEAN) {

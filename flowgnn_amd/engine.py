@@ -606,11 +606,16 @@ class Engine:
         self._set_buffers("flowgnn_set_attention_buffers", edge_ptr, self_ptr)
 
     # ---- taps
-    def set_numeric_mode(self, mode: str = "f32"):
+    def set_numeric_mode(self, mode: str = "f32", emb_dim: Optional[int] = None):
         """"f32" (default), "q6.10": the bit patterns of the reference's own fixed-point format (ap_fixed<16,6>; DGN: ap_fixed<16,3>),
-        or "f16" (GIN / GIN-VN): MLP operands rounded to f16, fp32 accumulation (flowgnn.h: FLOWGNN_NUMERIC_F16)."""
+        or "f16" (GIN / GIN-VN): MLP operands rounded to f16, fp32 accumulation (flowgnn.h: FLOWGNN_NUMERIC_F16).
+        emb_dim: the engine's width, which sends the call through flowgnn_set_numeric_mode_dim -- the way to "f16" on a GIN engine at
+        set_emb_dim(300); without it the call is flowgnn_set_numeric_mode, which refuses every mode but "f32" at that width."""
         code = NUMERIC_MODES[mode]
-        self._check(self.lib.flowgnn_set_numeric_mode(self._h, code), "flowgnn_set_numeric_mode")
+        if emb_dim is None:
+            self._check(self.lib.flowgnn_set_numeric_mode(self._h, code), "flowgnn_set_numeric_mode")
+        else:
+            self._check(self.lib.flowgnn_set_numeric_mode_dim(self._h, int(emb_dim), code), "flowgnn_set_numeric_mode_dim")
 
     def set_pooling(self, mode: str = "mean"):
         """The readout's pooling: "mean" (default, the reference's), "sum" or "max" (flowgnn.h: flowgnn_set_pooling; GIN, GIN-VN, GCN,
@@ -794,8 +799,12 @@ class EngineGroup:
         """The members' width (they are one model with one setting: the first member answers)."""
         return int(self.lib.flowgnn_emb_dim(self.lib.flowgnn_group_engine(self._h, 0)))
 
-    def set_numeric_mode(self, mode: str = "f32"):
-        self._check(self.lib.flowgnn_group_set_numeric_mode(self._h, NUMERIC_MODES[mode]), "flowgnn_group_set_numeric_mode")
+    def set_numeric_mode(self, mode: str = "f32", emb_dim: Optional[int] = None):
+        """Engine.set_numeric_mode on every member (flowgnn.h: flowgnn_group_set_numeric_mode; with emb_dim: ..._dim)."""
+        if emb_dim is None:
+            self._check(self.lib.flowgnn_group_set_numeric_mode(self._h, NUMERIC_MODES[mode]), "flowgnn_group_set_numeric_mode")
+        else:
+            self._check(self.lib.flowgnn_group_set_numeric_mode_dim(self._h, int(emb_dim), NUMERIC_MODES[mode]), "flowgnn_group_set_numeric_mode_dim")
 
     def set_pooling(self, mode: str = "mean"):
         """Engine.set_pooling on every member (flowgnn.h: flowgnn_group_set_pooling)."""

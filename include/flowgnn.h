@@ -512,7 +512,8 @@ int flowgnn_num_tasks(const flowgnn_engine* e);
  * on kernels of its own, one launch per layer: split-f16 MFMA products with the fp32 re-run of flowgnn_exact_reruns.
  * Call it before setting weights and batch (both must be set again afterwards: weights set before are dropped); drops a recorded
  * launch sequence; setting the width the engine has is a no-op.  FLOWGNN_MODEL_GIN only: every other model, GIN-VN included, returns
- * FLOWGNN_ERR_UNSUPPORTED (GCN's width goes through flowgnn_set_model_emb_dim below, and the error text says so).  At 300, FLOWGNN_NUMERIC_Q6_10 / FLOWGNN_NUMERIC_F16, flowgnn_set_ogb_virtual_node (its tensors are 100
+ * FLOWGNN_ERR_UNSUPPORTED (GCN's width goes through flowgnn_set_model_emb_dim below, and the error text says so).  At 300, FLOWGNN_NUMERIC_Q6_10 / FLOWGNN_NUMERIC_F16 through flowgnn_set_numeric_mode (F16 at
+ * that width goes through flowgnn_set_numeric_mode_dim), flowgnn_set_ogb_virtual_node (its tensors are 100
  * wide; 300-wide ones go through flowgnn_set_ogb_virtual_node_dim) and flowgnn_run_aggregation_only / flowgnn_get_aggregate return FLOWGNN_ERR_UNSUPPORTED, and so does this call while one
  * of the first three is on.  A width other than the two: FLOWGNN_ERR_ARG.  flowgnn_embedding_dim(model) keeps answering for the
  * model's default width; flowgnn_emb_dim(e) is the engine's (-1 for a null handle).  The <M>_compute_graphs entry points have no
@@ -582,6 +583,25 @@ int flowgnn_set_model_emb_dim(flowgnn_engine* e, int emb_dim);   /* GIN, GCN: 10
  */
 #define FLOWGNN_NUMERIC_F16 2
 int flowgnn_set_numeric_mode(flowgnn_engine* e, int mode);
+/*
+ * The numeric mode with the width it is meant for: emb_dim must be the engine's width (FLOWGNN_ERR_ARG otherwise, the text names both
+ * numbers; also for a width that is neither 100 nor 300 and for an unknown mode).  With emb_dim FLOWGNN_EMB_DIM_REFERENCE the call IS
+ * flowgnn_set_numeric_mode.  With FLOWGNN_EMB_DIM_OGB, on a FLOWGNN_MODEL_GIN engine at that width (flowgnn_set_emb_dim), it accepts
+ * FLOWGNN_NUMERIC_F32 and FLOWGNN_NUMERIC_F16; FLOWGNN_NUMERIC_Q6_10, and any mode but F32 on a GCN engine at that width, return
+ * FLOWGNN_ERR_UNSUPPORTED.  flowgnn_set_numeric_mode itself keeps answering FLOWGNN_ERR_UNSUPPORTED to every mode but F32 at width 300.
+ * FLOWGNN_NUMERIC_F16 at width 300, with D = 300, H = 600, the un-folded rule of the text above:
+ *   a[v] = fma(h[v], s_l, sum_e relu(h[src_e] + ecomb_l[code_e])) in fp32, in CSR order, as in the default mode; then a, the ReLU'd
+ *   hidden units (in the kernels' scaled domain, r(hid s1) / s1) and both weight matrices after their power-of-two scale (r(W s) / s)
+ *   are rounded to f16, to nearest even, and each product is ONE f16 x f16 MFMA with fp32 accumulation; biases and 1 / (s1 s2) as in
+ *   the default mode.  fp32 and unchanged: the encoder, the walk, eps, OGB's virtual node (only the node MLP's operands are rounded;
+ *   the virtual node's add and its update MLP are the default mode's), the pooling, the attention readout's gate, the head and the
+ *   node logits.  Range fallback as above: beyond 6e4 the pass is repeated on the fp32 kernels of the default mode's exact path.
+ * The mode is the engine's: it survives flowgnn_set_weights, new batches, eps, pooling, NUM_TASK and the virtual-node and attention
+ * readout setters, in either order with them.  While it is not FLOWGNN_NUMERIC_F32 at width 300, flowgnn_set_emb_dim /
+ * flowgnn_set_model_emb_dim to width 100 return FLOWGNN_ERR_UNSUPPORTED (set F32, change the width, set the mode again); the same
+ * width again stays a no-op.
+ */
+int flowgnn_set_numeric_mode_dim(flowgnn_engine* e, int emb_dim, int mode);
 
 /*
  * Pooling of the readout (GIN, GIN-VN, GCN, GAT): how a graph's last node rows r[v] (what
@@ -871,6 +891,7 @@ int flowgnn_group_set_num_tasks(flowgnn_group* g, int num_tasks);
 int flowgnn_group_set_emb_dim(flowgnn_group* g, int emb_dim);
 int flowgnn_group_set_model_emb_dim(flowgnn_group* g, int emb_dim);
 int flowgnn_group_set_numeric_mode(flowgnn_group* g, int mode);
+int flowgnn_group_set_numeric_mode_dim(flowgnn_group* g, int emb_dim, int mode);
 int flowgnn_group_set_pooling(flowgnn_group* g, int mode);
 int flowgnn_group_set_gin_eps(flowgnn_group* g, const float* eps);
 int flowgnn_group_set_ogb_virtual_node(flowgnn_group* g, const float* vn_embedding, const float* w1, const float* b1, const float* w2, const float* b2);
