@@ -182,6 +182,8 @@ struct DeviceBatch {
                               // launch is the one it always was.  A forward that finds it set runs OGB's virtual node on every path
     const void* attn_pool;    // flowgnn_set_attention_pooling (GIN, GCN at width 300): the gate's tensors in the device form of wide_attn.h, or null: off,
                               // every launch is the one it always was.  A forward that finds it set pools by the softmax of the gates
+    const void* s2s;          // flowgnn_set_set2set_pooling (GIN, GCN at width 300): the six tensors in the device form of wide_s2s.h, or null: off, every
+    int s2s_steps;            // launch is the one it always was.  A forward that finds it set runs s2s_steps set2set steps and the readout's own head
     int final_h;              // which h[] holds the last stage's output (set by forward)
     const float* tap;         // optional debug tap returned by flowgnn_get_h instead of h[final_h]
     int tap_dim;

@@ -10,6 +10,7 @@
 #include "tile_pack.h"
 #include "gin_ogbvn.h"
 #include "wide_attn.h"
+#include "wide_s2s.h"
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -420,6 +421,7 @@ int flowgnn_destroy(flowgnn_engine* e) {
     e->eig_io.release();
     e->ogb_vn.release();
     e->attn_pool.release();
+    e->s2s.release();
     if (e->eig_done) (void)hipEventDestroy(e->eig_done);
     if (e->d_err) (void)hipFree(e->d_err);
     delete e->model;
@@ -721,6 +723,8 @@ static int set_batch_state(flowgnn_engine* e, int num_graphs, const int* nums_of
     for (int l = 0; l < 5; l++) db.gin_self_scale[l] = (float)(1.0f + e->gin_eps[l]);
     db.ogb_vn = e->ogb_vn_on ? (const float*)e->ogb_vn.p : nullptr;
     db.attn_pool = e->attn_pool_on ? e->attn_pool.p : nullptr;
+    db.s2s = e->s2s_steps ? e->s2s.p : nullptr;
+    db.s2s_steps = e->s2s_steps;
     db.final_h = 0;
     db.tap = nullptr;
     db.tap_dim = 0;
@@ -1140,6 +1144,11 @@ int flowgnn_set_embeddings(flowgnn_engine* e, int on) {
         e->err = "flowgnn_set_embeddings: there are no fixed-point embeddings (FLOWGNN_NUMERIC_Q6_10)";
         return FLOWGNN_ERR_UNSUPPORTED;
     }
+    if (on && e->s2s_steps) {
+        e->err = "flowgnn_set_embeddings: the set2set pooling is on (flowgnn_set_set2set_pooling), and the vector its head reads is " +
+                 std::to_string(2 * e->emb_dim) + " wide where every embeddings buffer is " + std::to_string(e->emb_dim) + " wide: there are no graph embeddings";
+        return FLOWGNN_ERR_UNSUPPORTED;
+    }
     return switch_output(e, kOutputs[OUT_EMB], on);
 }
 
@@ -1180,6 +1189,10 @@ int flowgnn_set_node_logits(flowgnn_engine* e, int on) {
     }
     if (on && e->attn_pool_on) {
         e->err = "flowgnn_set_node_logits: the attention pooling is on (flowgnn_set_attention_pooling), and under it a graph's logit is no mean of per-node terms: there are no node logits";
+        return FLOWGNN_ERR_UNSUPPORTED;
+    }
+    if (on && e->s2s_steps) {
+        e->err = "flowgnn_set_node_logits: the set2set pooling is on (flowgnn_set_set2set_pooling), and under it a graph's logit is no mean of per-node terms: there are no node logits";
         return FLOWGNN_ERR_UNSUPPORTED;
     }
     return switch_output(e, kOutputs[OUT_NLOG], on);
@@ -1302,6 +1315,11 @@ long long flowgnn_graph_replays(const flowgnn_engine* e) { return e ? e->graph_r
 
 int flowgnn_set_num_tasks(flowgnn_engine* e, int num_tasks) {
     if (!e || num_tasks < 1) return FLOWGNN_ERR_ARG;
+    if (e->s2s_steps && num_tasks != e->num_tasks) {  // (the readout's own head has NUM_TASK rows)
+        e->err = "flowgnn_set_num_tasks: the set2set pooling is on (flowgnn_set_set2set_pooling), and its head has " + std::to_string(e->num_tasks) +
+                 " tasks, not " + std::to_string(num_tasks) + ": turn it off, change NUM_TASK, set it again";
+        return FLOWGNN_ERR_UNSUPPORTED;
+    }
     ENGINE_TRY(e, begin_change(e));
     const int rc = e->model->set_num_tasks(num_tasks);
     if (rc) { e->err = "flowgnn_set_num_tasks: this model's readout has a single task (multi-task readout exists for GIN / GIN-VN / GCN)"; return rc; }
@@ -1340,6 +1358,11 @@ static int set_width(flowgnn_engine* e, const char* fn, int emb_dim) {
     }
     if (e->attn_pool_on) {  // (the same rule: the gate's tensors belong to a width)
         e->err = who + "the attention pooling is on (flowgnn_set_attention_pooling), and its tensors are " + std::to_string(e->emb_dim) + " wide, not " +
+                 std::to_string(emb_dim) + ": turn it off, change the width, set it again";
+        return FLOWGNN_ERR_UNSUPPORTED;
+    }
+    if (e->s2s_steps) {  // (and the same again)
+        e->err = who + "the set2set pooling is on (flowgnn_set_set2set_pooling), and its tensors are " + std::to_string(e->emb_dim) + " wide, not " +
                  std::to_string(emb_dim) + ": turn it off, change the width, set it again";
         return FLOWGNN_ERR_UNSUPPORTED;
     }
@@ -1488,6 +1511,10 @@ int flowgnn_set_pooling(flowgnn_engine* e, int mode) {
     }
     if (mode != FLOWGNN_POOL_MEAN && e->attn_pool_on) {
         e->err = "flowgnn_set_pooling: the attention pooling is on (flowgnn_set_attention_pooling), a readout of its own; beside it the mean is the only accepted value";
+        return FLOWGNN_ERR_UNSUPPORTED;
+    }
+    if (mode != FLOWGNN_POOL_MEAN && e->s2s_steps) {
+        e->err = "flowgnn_set_pooling: the set2set pooling is on (flowgnn_set_set2set_pooling), a readout of its own; beside it the mean is the only accepted value";
         return FLOWGNN_ERR_UNSUPPORTED;
     }
     ENGINE_TRY(e, use_device(e));
@@ -1717,6 +1744,10 @@ int flowgnn_set_attention_pooling(flowgnn_engine* e, int emb_dim, const float* w
             e->err = who + "node logits are on (flowgnn_set_node_logits), and under this readout a graph's logit is no mean of per-node terms";
             return FLOWGNN_ERR_UNSUPPORTED;
         }
+        if (e->s2s_steps) {
+            e->err = who + "the set2set pooling is on (flowgnn_set_set2set_pooling), and the two readouts exclude each other: turn that one off first";
+            return FLOWGNN_ERR_UNSUPPORTED;
+        }
     }
     ENGINE_TRY(e, begin_change(e));  // (an idle stream: a run in flight may still read the tensors this call replaces)
     if (on) {
@@ -1731,6 +1762,91 @@ int flowgnn_set_attention_pooling(flowgnn_engine* e, int emb_dim, const float* w
 }
 
 int flowgnn_attention_pooling(const flowgnn_engine* e) { return e ? (e->attn_pool_on ? 1 : 0) : -1; }
+
+// OGB's graph_pooling="set2set" readout: the state handling of the attention readout above -- checks first,
+// then an idle stream, the six tensors packed on the host into the device form of wide_s2s.h, one device buffer owned by the engine.
+// All six NULL: off, at any width and for any model.
+int flowgnn_set_set2set_pooling(flowgnn_engine* e, int emb_dim, int steps, int num_tasks, const float* w_ih, const float* w_hh, const float* b_ih,
+                                const float* b_hh, const float* head_w, const float* head_b) {
+    if (!e) return FLOWGNN_ERR_ARG;
+    const std::string who = "flowgnn_set_set2set_pooling: ";
+    if (emb_dim != FLOWGNN_EMB_DIM_REFERENCE && emb_dim != FLOWGNN_EMB_DIM_OGB) {
+        e->err = who + "emb_dim is " + std::to_string(emb_dim) + "; the widths are FLOWGNN_EMB_DIM_REFERENCE (100) and FLOWGNN_EMB_DIM_OGB (300)";
+        return FLOWGNN_ERR_ARG;
+    }
+    const float* const t[6] = {w_ih, w_hh, b_ih, b_hh, head_w, head_b};
+    int given = 0;
+    for (const float* p : t) given += p != nullptr;
+    if (given != 0 && given != 6) {
+        e->err = who + "some of the six tensors are NULL and some are not (all six: on, all NULL: off)";
+        return FLOWGNN_ERR_ARG;
+    }
+    const bool on = given == 6;
+    if (on) {
+        if (steps < 1 || steps > FLOWGNN_SET2SET_MAX_STEPS) {
+            e->err = who + "steps is " + std::to_string(steps) + "; the processing steps are 1 .. " + std::to_string(FLOWGNN_SET2SET_MAX_STEPS) + " (OGB: 2)";
+            return FLOWGNN_ERR_ARG;
+        }
+        if (num_tasks < 1 || num_tasks != e->num_tasks) {
+            e->err = who + "head_w has " + std::to_string(num_tasks) + " tasks and the engine's NUM_TASK is " + std::to_string(e->num_tasks) +
+                     " (flowgnn_set_num_tasks)";
+            return FLOWGNN_ERR_ARG;
+        }
+        const size_t D = (size_t)emb_dim, T = (size_t)num_tasks;
+        const size_t count[6] = {4 * D * 2 * D, 4 * D * D, 4 * D, 4 * D, T * 2 * D, T};
+        static const char* const names[6] = {"w_ih", "w_hh", "b_ih", "b_hh", "head_w", "head_b"};
+        for (int i = 0; i < 6; i++)
+            for (size_t k = 0; k < count[i]; k++)
+                if (!std::isfinite(t[i][k])) {
+                    e->err = who + names[i] + "[" + std::to_string(k) + "] is not finite";
+                    return FLOWGNN_ERR_ARG;
+                }
+        if (e->model_id != FLOWGNN_MODEL_GIN && e->model_id != FLOWGNN_MODEL_GCN) {
+            e->err = who + "the set2set pooling exists for FLOWGNN_MODEL_GIN and FLOWGNN_MODEL_GCN only (OGB's gin, gin-virtual, gcn, gcn-virtual)";
+            return FLOWGNN_ERR_UNSUPPORTED;
+        }
+        if (emb_dim != e->emb_dim) {
+            e->err = who + "the tensors are " + std::to_string(emb_dim) + " wide and the engine's width is " + std::to_string(e->emb_dim) +
+                     " (flowgnn_set_emb_dim / flowgnn_set_model_emb_dim)";
+            return FLOWGNN_ERR_ARG;
+        }
+        if (emb_dim != FLOWGNN_EMB_DIM_OGB || fg::s2s_blob_bytes(emb_dim, num_tasks) == 0) {
+            e->err = who + "only the 300-wide models have this readout (the 100-wide graph-resident kernels fold the mean into their last layer): "
+                           "flowgnn_set_emb_dim / flowgnn_set_model_emb_dim(e, 300) first";
+            return FLOWGNN_ERR_UNSUPPORTED;
+        }
+        if (e->pooling != FLOWGNN_POOL_MEAN) {
+            e->err = who + "the pooling is not the mean (flowgnn_set_pooling), and this readout replaces the pooling: set FLOWGNN_POOL_MEAN first";
+            return FLOWGNN_ERR_UNSUPPORTED;
+        }
+        if (e->nlog_on) {
+            e->err = who + "node logits are on (flowgnn_set_node_logits), and under this readout a graph's logit is no mean of per-node terms";
+            return FLOWGNN_ERR_UNSUPPORTED;
+        }
+        if (e->attn_pool_on) {
+            e->err = who + "the attention pooling is on (flowgnn_set_attention_pooling), and the two readouts exclude each other: turn that one off first";
+            return FLOWGNN_ERR_UNSUPPORTED;
+        }
+        if (e->emb_on) {
+            e->err = who + "graph embeddings are on (flowgnn_set_embeddings), and the vector this readout's head reads is " + std::to_string(2 * emb_dim) +
+                     " wide where every embeddings buffer is " + std::to_string(emb_dim) + " wide";
+            return FLOWGNN_ERR_UNSUPPORTED;
+        }
+    }
+    ENGINE_TRY(e, begin_change(e));  // (an idle stream: a run in flight may still read the tensors this call replaces)
+    if (on) {
+        std::vector<float> packed(fg::s2s_blob_bytes(emb_dim, num_tasks) / sizeof(float));  // (floats: the parts are read as float4 pieces)
+        fg::s2s_blob_pack(emb_dim, num_tasks, w_ih, w_hh, b_ih, b_hh, head_w, head_b, packed.data());
+        EHIP_TRY(e, e->s2s.reserve(sizeof(float) * packed.size(), false));
+        EHIP_TRY(e, hipMemcpy(e->s2s.p, packed.data(), sizeof(float) * packed.size(), hipMemcpyHostToDevice));
+    }
+    e->s2s_steps = on ? steps : 0;
+    e->db.s2s = on ? e->s2s.p : nullptr;  // (launches are stream-ordered: it matters to those enqueued after this call)
+    e->db.s2s_steps = e->s2s_steps;
+    return FLOWGNN_OK;
+}
+
+int flowgnn_set2set_pooling(const flowgnn_engine* e) { return e ? e->s2s_steps : -1; }
 
 int flowgnn_set_option(flowgnn_engine* e, const char* key, double value) {
     if (!e || !key) return FLOWGNN_ERR_ARG;

@@ -101,6 +101,8 @@ struct flowgnn_engine {
     fg::GrowBuf ogb_vn;               // ... and its five tensors on the device (gin_ogbvn.h: GIN_OGBVN_FLOATS)
     bool attn_pool_on = false;        // flowgnn_set_attention_pooling: the engine's as well (db.attn_pool follows it)
     fg::GrowBuf attn_pool;            // ... and the gate's three tensors on the device (wide_attn.h)
+    int s2s_steps = 0;                // flowgnn_set_set2set_pooling: the engine's as well, 0 = off (db.s2s / db.s2s_steps follow it)
+    fg::GrowBuf s2s;                  // ... and its six tensors on the device (wide_s2s.h)
 
     // the optional outputs (fg::OutSlot): graph embeddings [G][dim] (flowgnn_set_embeddings), node embeddings [N][dim]
     // (flowgnn_set_node_embeddings), node logits [N][num_tasks] (flowgnn_set_node_logits) and, for GAT, the attention coefficients

@@ -614,7 +614,7 @@ public:
                 if (int rc = hid_.reserve((size_t)G * 2 * D)) return rc;
             }
         }
-        if (int rc = readout_.reserve(db)) return rc;  // the attention readout (section 4.20): the gates [N] ...
+        if (int rc = readout_.reserve(db, exact_)) return rc;  // the attention readout (section 4.20): the gates [N] ...
         if (db.attn_pool && exact_)                    // ... and the exact form's hidden rows [N][2 D]
             if (int rc = hid_.reserve((size_t)(n > G ? n : G) * 2 * D)) return rc;
         if (db.b.e_tot > 0) {  // dinv[src_e] per CSR entry, once per pass, as on the 100-wide per-layer path

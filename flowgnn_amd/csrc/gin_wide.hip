@@ -550,7 +550,7 @@ public:
             if (int rc = vn_vec_[1].reserve((size_t)G * D)) return rc;
             if (int rc = node_graph_.reserve((size_t)n)) return rc;
         }
-        if (int rc = readout_.reserve(db)) return rc;
+        if (int rc = readout_.reserve(db, exact_)) return rc;
         {
             ProfScope p(prof, "atom_encoder", s);
             const int grid = grid_for((long long)n * M::C, 256, 256 * 8);

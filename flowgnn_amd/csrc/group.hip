@@ -273,6 +273,11 @@ int flowgnn_group_set_attention_pooling(flowgnn_group* g, int emb_dim, const flo
     return group_all(g, [&](flowgnn_engine* e) { return flowgnn_set_attention_pooling(e, emb_dim, w1, b1, w2); });
 }
 
+int flowgnn_group_set_set2set_pooling(flowgnn_group* g, int emb_dim, int steps, int num_tasks, const float* w_ih, const float* w_hh,
+                                      const float* b_ih, const float* b_hh, const float* head_w, const float* head_b) {
+    return group_all(g, [&](flowgnn_engine* e) { return flowgnn_set_set2set_pooling(e, emb_dim, steps, num_tasks, w_ih, w_hh, b_ih, b_hh, head_w, head_b); });
+}
+
 int flowgnn_group_set_embeddings(flowgnn_group* g, int on) { return group_all(g, [&](flowgnn_engine* e) { return flowgnn_set_embeddings(e, on); }); }
 int flowgnn_group_set_node_embeddings(flowgnn_group* g, int on) { return group_all(g, [&](flowgnn_engine* e) { return flowgnn_set_node_embeddings(e, on); }); }
 int flowgnn_group_set_node_logits(flowgnn_group* g, int on) { return group_all(g, [&](flowgnn_engine* e) { return flowgnn_set_node_logits(e, on); }); }

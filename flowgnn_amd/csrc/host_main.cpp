@@ -2,7 +2,7 @@
 // OpenCL host (GIN/src/host.cc): load the model's .bin weights, read a graph pack in the reference's on-disk
 // layout, run the whole dataset as ONE batched launch NUM_TRIALS times, write HLS_output.txt.
 //
-//   host <MODEL> [--graphs DIR] [--weights DIR] [--num-graphs N] [--trials T] [--out FILE] [--node-logits FILE] [--attention FILE [--attention-layers MASK]] [--device D | --devices D0,D1,..] [--option key=value] [--numeric f32|q6.10|f16] [--eps] [--ogb-vn] [--attn-pool] [--emb-dim 100|300] [--eig DIR | --compute-eig] [XCLBIN]
+//   host <MODEL> [--graphs DIR] [--weights DIR] [--num-graphs N] [--trials T] [--out FILE] [--node-logits FILE] [--attention FILE [--attention-layers MASK]] [--device D | --devices D0,D1,..] [--option key=value] [--numeric f32|q6.10|f16] [--eps] [--ogb-vn] [--attn-pool] [--set2set [--set2set-steps N]] [--emb-dim 100|300] [--eig DIR | --compute-eig] [XCLBIN]
 //
 //   MODEL        GIN | GIN-VN | GCN | GAT | PNA | DGN
 //   --graphs     directory holding graph_info/ and graph_bin/      (default ../graphs, host.cc:14-15)
@@ -23,6 +23,9 @@
 //                (with --emb-dim 300: gcn_ep1_virtualnode_dim300.bin, through flowgnn_set_gcn_virtual_node_dim)
 //   --attn-pool  GIN, GCN with --emb-dim 300: read gin_ep1_attnpool_dim300.bin / gcn_ep1_attnpool_dim300.bin (181 200 LE float32: w1, b1, w2)
 //                from the weights directory and run OGB's graph_pooling="attention" readout (flowgnn_set_attention_pooling)
+//   --set2set    GIN, GCN with --emb-dim 300: read gin_ep1_set2set_dim300.bin / gcn_ep1_set2set_dim300.bin (LE float32: w_ih, w_hh, b_ih, b_hh,
+//                head_w, head_b; 1 082 400 + 601 per task of --num-tasks) from the weights directory and run OGB's graph_pooling="set2set"
+//                readout (flowgnn_set_set2set_pooling) with --set2set-steps processing steps (default 2, OGB's); refused with --attn-pool
 //   --emb-dim    GCN: 300 = OGB's default width (flowgnn_set_model_emb_dim), gcn_ep1_dim300.weights.all.bin is read.
 //                GIN: 300 = OGB's default width (flowgnn_set_emb_dim): the weights directory's dim300 files are read (with --eps,
 //                gin_ep1_eps_dim300.bin); 100 (default) = the reference's width.  With --numeric, 300 sends the mode through
@@ -94,7 +97,7 @@ static bool read_eig_txt(const std::string& path, std::vector<float>& eig, size_
 int main(int argc, char** argv) {
     if (argc < 2) {
         fprintf(stderr, "Usage: %s <GIN|GIN-VN|GCN|GAT|PNA|DGN> [--graphs DIR] [--weights DIR] [--num-graphs N] [--trials T] "
-                        "[--out FILE] [--embeddings FILE] [--node-embeddings FILE] [--node-logits FILE] [--attention FILE [--attention-layers MASK]] [--device D | --devices D0,D1,..] [--option key=value] [--numeric f32|q6.10|f16] [--pooling mean|sum|max] [--eps] [--ogb-vn] [--attn-pool] [--emb-dim 100|300] [--num-tasks T] [--eig DIR | --compute-eig] [XCLBIN File]\n", argv[0]);
+                        "[--out FILE] [--embeddings FILE] [--node-embeddings FILE] [--node-logits FILE] [--attention FILE [--attention-layers MASK]] [--device D | --devices D0,D1,..] [--option key=value] [--numeric f32|q6.10|f16] [--pooling mean|sum|max] [--eps] [--ogb-vn] [--attn-pool] [--set2set [--set2set-steps N]] [--emb-dim 100|300] [--num-tasks T] [--eig DIR | --compute-eig] [XCLBIN File]\n", argv[0]);
         return EXIT_FAILURE;
     }
     const std::string model = argv[1];
@@ -104,7 +107,8 @@ int main(int argc, char** argv) {
     long num_graphs = -1;
     int attn_mask = 16;
     int trials = 25, numeric = FLOWGNN_NUMERIC_F32, num_tasks = 1, pooling = FLOWGNN_POOL_MEAN, emb_dim = FLOWGNN_EMB_DIM_REFERENCE;
-    bool use_eps = false, use_ogb_vn = false, use_attn_pool = false, compute_eig = false;
+    bool use_eps = false, use_ogb_vn = false, use_attn_pool = false, use_set2set = false, compute_eig = false;
+    int set2set_steps = 2;
     std::vector<int> devices;
     std::vector<std::pair<std::string, double>> options;
     for (int i = 2; i < argc; i++) {
@@ -153,9 +157,12 @@ int main(int argc, char** argv) {
         else if (a == "--compute-eig") compute_eig = true;  // DGN: node_eigen from the graphs themselves (flowgnn_laplacian_eigen), no --eig DIR
         else if (a == "--eps") use_eps = true;  // the trained eps of the weights directory (flowgnn_set_gin_eps; GIN / GIN-VN)
         else if (a == "--attn-pool") use_attn_pool = true;  // OGB's attention readout from the weights directory (flowgnn_set_attention_pooling)
+        else if (a == "--set2set") use_set2set = true;  // OGB's set2set readout from the weights directory (flowgnn_set_set2set_pooling)
+        else if (a == "--set2set-steps") set2set_steps = atoi(next("--set2set-steps"));
         else if (a == "--ogb-vn") use_ogb_vn = true;  // OGB's virtual node from the weights directory (GIN: flowgnn_set_ogb_virtual_node, GCN: flowgnn_set_gcn_virtual_node)
         // anything else (e.g. an .xclbin path) is ignored
     }
+    if (use_set2set && use_attn_pool) { fprintf(stderr, "--set2set and --attn-pool: a model has one readout\n"); return EXIT_FAILURE; }
     if (num_graphs < 0) num_graphs = read_count_file(graphs + "/dataset_size.txt");
     if (num_graphs < 0) num_graphs = read_count_file("../common/includes/dataset/dataset_size.txt");
     if (num_graphs < 0) { fprintf(stderr, "graph count unknown: pass --num-graphs or provide dataset_size.txt\n"); return EXIT_FAILURE; }
@@ -227,6 +234,19 @@ int main(int argc, char** argv) {
         }
         rc = flowgnn_group_set_attention_pooling(eng, emb_dim, gate.data(), gate.data() + H * D, gate.data() + H * D + H);
         if (rc) { fprintf(stderr, "--attn-pool: %d %s\n", rc, flowgnn_group_last_error(eng)); return EXIT_FAILURE; }
+    }
+    if (use_set2set) {
+        const size_t D = (size_t)emb_dim, T = (size_t)(num_tasks > 0 ? num_tasks : 1);
+        const size_t at[7] = {0, 8 * D * D, 12 * D * D, 12 * D * D + 4 * D, 12 * D * D + 8 * D, 12 * D * D + 8 * D + T * 2 * D, 12 * D * D + 8 * D + T * (2 * D + 1)};
+        std::vector<float> t(at[6]);
+        const std::string path = wdir + (mid == FLOWGNN_MODEL_GCN ? "/gcn_ep1_set2set_dim" : "/gin_ep1_set2set_dim") + std::to_string(D) + ".bin";
+        if (!read_exact(path, t, 0, t.size())) {
+            fprintf(stderr, "--set2set: cannot read %zu floats from %s (the tensors of flowgnn_set_set2set_pooling at --num-tasks %zu)\n", t.size(), path.c_str(), T);
+            return EXIT_FAILURE;
+        }
+        rc = flowgnn_group_set_set2set_pooling(eng, emb_dim, set2set_steps, (int)T, t.data() + at[0], t.data() + at[1], t.data() + at[2], t.data() + at[3],
+                                               t.data() + at[4], t.data() + at[5]);
+        if (rc) { fprintf(stderr, "--set2set: %d %s\n", rc, flowgnn_group_last_error(eng)); return EXIT_FAILURE; }
     }
     printf("\n******* Weights loading done *******\n");
 

@@ -1,5 +1,5 @@
 // wide_common.h -- what the per-layer models of OGB's default width share: gin_wide.hip (DESIGN.md sections 4.16, 4.17), gcn_wide.hip
-// (sections 4.18, 4.19) and wide_attn.hip (section 4.20).  Device side: the LDS-DMA issue, the fp32 dense kernel, the atom encoder and
+// (sections 4.18, 4.19), wide_attn.hip (section 4.20) and wide_s2s.hip (section 4.23).  Device side: the LDS-DMA issue, the fp32 dense kernel, the atom encoder and
 // the pooling kernel.  Host side: the fp32 launches, the split-f16 fragment packer, the transpose and the edge table of set_weights,
 // and the readout (GwReadout).  Templates on the width D; every kernel here has internal linkage, so each translation unit compiles
 // the instances it launches and nothing else.  The layer kernels' own bodies are NOT shared: section 4.21 says why.
@@ -11,6 +11,7 @@
 #include "common.h"
 #include "dense_split.h"
 #include "wide_attn.h"  // the attention readout's two launches
+#include "wide_s2s.h"   // the set2set readout's launches
 
 namespace fg {
 namespace {
@@ -194,13 +195,16 @@ inline void gw_edge_combos(const float* E, int d, float* out) {
 }
 
 // The readout of both models: the pooled rows (the caller's graph embeddings when they are on), then the head on them -- every
-// NUM_TASK, every pooling -- and the per-node logit terms.  Owns the head's weights and the two buffers; a member of the model.
+// NUM_TASK, every pooling -- and the per-node logit terms; or, in its place, the set2set readout with its own head (section 4.23).
+// Owns the head's weights and the readouts' buffers; a member of the model.
 template <int D>
 struct GwReadout {
     int num_tasks = 1;
     float *d_pw = nullptr, *d_pb = nullptr;  // graph_pred_weights [NUM_TASK][D], bias [NUM_TASK]
     GrowBuf pooled;                          // the pooled rows [G][D] when graph embeddings are off
     GrowBuf attn_s;                          // the attention readout's gates [N] (section 4.20)
+    GrowBuf s2s_h, s2s_c, s2s_r, s2s_e;      // the set2set readout's h_t, c_t, r_t [G][D] and dots e [N] (section 4.23)
+    GrowBuf s2s_q, s2s_z;                    // ... and its exact form's q* [G][2 D] and z [G][4 D]
 
     int set_num_tasks(int t, bool& ready) {
         if (t < 1) return 8;
@@ -212,11 +216,41 @@ struct GwReadout {
         if (int rc = upload(&d_pw, std::vector<float>(pw, pw + (size_t)num_tasks * D))) return rc;
         return upload(&d_pb, std::vector<float>(pb, pb + num_tasks));
     }
-    // in front of a forward's first launch: the gates [N], when the attention readout is on
-    int reserve(const DeviceBatch& db) { return db.attn_pool ? attn_s.reserve((size_t)db.b.n_tot) : 0; }
+    // in front of a forward's first launch: the gates [N], when the attention readout is on; the set2set readout's state, when that is
+    int reserve(const DeviceBatch& db, bool exact) {
+        if (db.s2s) {
+            const size_t G = (size_t)db.b.num_graphs;
+            if (int rc = s2s_h.reserve(G * D)) return rc;
+            if (int rc = s2s_c.reserve(G * D)) return rc;
+            if (int rc = s2s_r.reserve(G * D)) return rc;
+            if (int rc = s2s_e.reserve((size_t)db.b.n_tot)) return rc;
+            if (exact) {
+                if (int rc = s2s_q.reserve(G * 2 * D)) return rc;
+                if (int rc = s2s_z.reserve(G * 4 * D)) return rc;
+            }
+        }
+        return db.attn_pool ? attn_s.reserve((size_t)db.b.n_tot) : 0;
+    }
     // h5: the rows the pool is taken over; hid: the exact attention gate's hidden rows [N][2 D]
     int run(DeviceBatch& db, Profiler& prof, hipStream_t s, const float* h5, bool exact, float* hid) {
         const int n = db.b.n_tot, G = db.b.num_graphs;
+        if (db.s2s) {  // OGB's set2set readout (section 4.23): per step the LSTM on the graphs' q*, the rows' dots with h_t, their softmax-weighted
+                       // sum; then its own head on [h, r].  No graph embeddings and no node logits beside it (the engine refuses both)
+            for (int t = 0; t < db.s2s_steps; t++) {
+                {
+                    ProfScope p(prof, "s2s_lstm", s);
+                    if (int rc = launch_s2s_lstm(D, db.s2s, s2s_h.p, s2s_c.p, s2s_r.p, s2s_q.p, s2s_z.p, G, t == 0, exact, db.range_flag, s)) return rc;
+                }
+                {
+                    ProfScope p(prof, "s2s_dot_rows", s);
+                    if (int rc = launch_s2s_dot_rows(D, h5, s2s_h.p, db.b.node_off, s2s_e.p, G, s)) return rc;
+                }
+                ProfScope p(prof, "s2s_pool_rows", s);
+                if (int rc = launch_attn_pool_rows(D, h5, s2s_e.p, db.b.node_off, s2s_r.p, G, s)) return rc;
+            }
+            ProfScope p(prof, "s2s_head", s);
+            return launch_s2s_head(D, db.s2s, s2s_h.p, s2s_r.p, db.out, G, num_tasks, s);
+        }
         float* out = db.emb;
         if (!out) {
             if (int rc = pooled.reserve((size_t)G * D)) return rc;
@@ -251,6 +285,7 @@ struct GwReadout {
         if (d_pb) { (void)hipFree(d_pb); d_pb = nullptr; }
         pooled.release();
         attn_s.release();
+        for (GrowBuf* b : {&s2s_h, &s2s_c, &s2s_r, &s2s_e, &s2s_q, &s2s_z}) b->release();
     }
 };
 

@@ -72,6 +72,16 @@ def _attn_pool_args(gate):
     return int(a[0].shape[1]), a
 
 
+def _s2s_args(s2s):
+    """None -> (300, 1, six NULLs) (off); else the width read off w_hh, NUM_TASK off head_b and the dict's six tensors
+    (weights.SET2SET_KEYS) as float32 arrays, in the C call's order -- the caller keeps them alive for the duration of the call."""
+    if s2s is None:
+        return 300, 1, [None] * 6
+    from .weights import checked_set2set
+    a = list(checked_set2set(s2s).values())
+    return int(a[1].shape[1]), int(a[5].size), a
+
+
 def _ogb_vn_dim(a) -> int:
     """The width of _ogb_vn_args' tensors (the embedding row's length); 100 for the five NULLs."""
     return 100 if a[0] is None else int(a[0].size)
@@ -195,13 +205,16 @@ class Engine:
         ptrs = (_lib.p_float * len(arrs))(*[_pf(a) for a in arrs])
         self._check(self.lib.flowgnn_set_weights(self._h, len(arrs), ptrs), "flowgnn_set_weights")
 
-    def load_weights_dir(self, directory: str, eps: bool = False, virtual_node: bool = False, attention_pooling: bool = False):
+    def load_weights_dir(self, directory: str, eps: bool = False, virtual_node: bool = False, attention_pooling: bool = False,
+                         set2set: bool = False, set2set_steps: int = 2):
         """eps=True (GIN, GIN-VN): also read the directory's eps file and apply it (set_gin_eps); virtual_node=True: also read
         gin_ep1_virtualnode_dim100.bin and apply it (GIN: set_ogb_virtual_node), or gcn_ep1_virtualnode_dim100.bin on a GCN engine
         (set_gcn_virtual_node; at width 300 gcn_ep1_virtualnode_dim300.bin, through flowgnn_set_gcn_virtual_node_dim).  The C call itself does neither.  A GIN engine at width 300 (set_emb_dim) reads the dim300 set, its eps
         file and its virtual-node file (gin_ep1_virtualnode_dim300.bin, through flowgnn_set_ogb_virtual_node_dim) included.
         attention_pooling=True (GIN, GCN at width 300): also read gin_ep1_attnpool_dim300.bin / gcn_ep1_attnpool_dim300.bin and apply it
-        (set_attention_pooling)."""
+        (set_attention_pooling).
+        set2set=True (GIN, GCN at width 300): also read gin_ep1_set2set_dim300.bin / gcn_ep1_set2set_dim300.bin and apply it with
+        set2set_steps processing steps (set_set2set_pooling; OGB: 2)."""
         self._check(self.lib.flowgnn_load_weights_dir(self._h, directory.encode()), "flowgnn_load_weights_dir")
         if eps:
             from .weights import load_gin_eps
@@ -215,6 +228,9 @@ class Engine:
         if attention_pooling:
             from .weights import load_attention_pooling
             self.set_attention_pooling(load_attention_pooling(directory, model=self.model, emb_dim=self.emb_dim))
+        if set2set:
+            from .weights import load_set2set
+            self.set_set2set_pooling(load_set2set(directory, model=self.model, emb_dim=self.emb_dim), steps=set2set_steps)
 
     # ---- batch
     def set_job_totals(self, job_nodes: int = -1, job_edges: int = -1):
@@ -679,6 +695,18 @@ class Engine:
         """Whether the attention readout is on (flowgnn.h: flowgnn_attention_pooling)."""
         return int(self.lib.flowgnn_attention_pooling(self._h)) == 1
 
+    def set_set2set_pooling(self, s2s=None, steps: int = 2):
+        """GIN, GCN at width 300: OGB's graph_pooling="set2set" readout (flowgnn.h: flowgnn_set_set2set_pooling).  `s2s`: a dict with the
+        keys of weights.SET2SET_KEYS (weights.load_set2set, weights.synth_set2set, export.set2set_from_ogb_state_dict); the width is
+        read off w_hh and NUM_TASK off head_b.  steps: the processing steps, 1 .. 8 (OGB: 2).  None turns it off.  The engine's, across
+        batches and weight sets; while it is on the model's own head is not read."""
+        d, t, a = _s2s_args(s2s)
+        self._check(self.lib.flowgnn_set_set2set_pooling(self._h, d, int(steps), t, *[_pf(x) for x in a]), "flowgnn_set_set2set_pooling")
+
+    def set2set_pooling(self) -> int:
+        """The set2set readout's processing steps, 0 when it is off (flowgnn.h: flowgnn_set2set_pooling)."""
+        return int(self.lib.flowgnn_set2set_pooling(self._h))
+
     def exact_reruns(self) -> int:
         """Forward passes repeated on the exact-fp32 kernels (flowgnn.h: flowgnn_exact_reruns)."""
         return int(self.lib.flowgnn_exact_reruns(self._h))
@@ -836,6 +864,11 @@ class EngineGroup:
         """Engine.set_attention_pooling on every member (flowgnn.h: flowgnn_group_set_attention_pooling)."""
         d, a = _attn_pool_args(gate)
         self._check(self.lib.flowgnn_group_set_attention_pooling(self._h, d, *[_pf(x) for x in a]), "flowgnn_group_set_attention_pooling")
+
+    def set_set2set_pooling(self, s2s=None, steps: int = 2):
+        """Engine.set_set2set_pooling on every member (flowgnn.h: flowgnn_group_set_set2set_pooling)."""
+        d, t, a = _s2s_args(s2s)
+        self._check(self.lib.flowgnn_group_set_set2set_pooling(self._h, d, int(steps), t, *[_pf(x) for x in a]), "flowgnn_group_set_set2set_pooling")
 
     def set_batch(self, batch: GraphBatch):
         nn, ne = _i32(batch.nums_of_nodes), _i32(batch.nums_of_edges)

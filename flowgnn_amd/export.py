@@ -160,6 +160,41 @@ def attention_pooling_from_ogb_state_dict(sd: Mapping, emb_dim: int = 300) -> Di
     return _checked(out, shapes, lambda k, v: v)
 
 
+S2S_KEY = "pool.lstm.weight_ih_l0"  # what tells a graph_pooling="set2set" state_dict from the others
+_S2S_SD_KEYS = OrderedDict([("w_ih", "pool.lstm.weight_ih_l0"), ("w_hh", "pool.lstm.weight_hh_l0"), ("b_ih", "pool.lstm.bias_ih_l0"),
+                            ("b_hh", "pool.lstm.bias_hh_l0"), ("head_w", "graph_pred_linear.weight"), ("head_b", "graph_pred_linear.bias")])
+
+
+def set2set_from_ogb_state_dict(sd: Mapping, emb_dim: int = 300) -> Dict[str, np.ndarray]:
+    """The readout of an OGB `GNN(graph_pooling='set2set')` state_dict as the six tensors Engine.set_set2set_pooling /
+    flowgnn_set_set2set_pooling take: PyG's `pool.lstm` = torch.nn.LSTM(2D, D) (weight_ih_l0 [4D][2D], weight_hh_l0 [4D][D], bias_ih_l0,
+    bias_hh_l0 [4D]; gate order i, f, g, o) and OGB's `graph_pred_linear` = Linear(2D, NUM_TASK), every row of it.  The tensors are taken
+    as they are; the number of processing steps is no tensor (OGB: 2) and is given to the engine.
+    emb_dim: the width the caller expects (300: only the 300-wide models have this readout); a state_dict of another width is refused."""
+    d = int(emb_dim)
+    if S2S_KEY not in sd:
+        raise ExportError(f"state_dict has no '{S2S_KEY}': it is not a graph_pooling='set2set' model (its keys are pool.lstm.*)")
+    out = OrderedDict((k, _get(sd, name)) for k, name in _S2S_SD_KEYS.items())
+    t = out["head_w"].shape[0] if out["head_w"].ndim == 2 else 0
+    try:
+        shapes = _weights.set2set_shapes(d, max(1, t))
+    except ValueError as e:
+        raise ExportError(str(e))
+    for k, shp in shapes.items():
+        if out[k].shape != shp:
+            raise ExportError(f"'{_S2S_SD_KEYS[k]}' is {out[k].shape} and emb_dim is {d}: wanted {shp}")
+    return _checked(out, shapes, lambda k, v: v)
+
+
+def _mean_head_zeroed(sd: Mapping, emb_dim: int) -> Dict:
+    """`sd` with graph_pred_linear replaced by an all-zero [T][D] head and bias: what the model's own set carries beside a set2set file"""
+    t = _get(sd, "graph_pred_linear.weight").shape[0]
+    out = dict(sd)
+    out["graph_pred_linear.weight"] = np.zeros((t, int(emb_dim)), np.float32)
+    out["graph_pred_linear.bias"] = np.zeros(t, np.float32)
+    return out
+
+
 def gin_weights_from_ogb_state_dict(sd: Mapping, num_layers: int = 5, eps_tol: float = 0.0, multi_task: bool = False,
                                     keep_eps: bool = False, virtual_node: bool = False, virtual_node_dim: int = 100) -> Dict[str, np.ndarray]:
     """OGB `GNN(gnn_type='gin', virtual_node=False, JK='last', residual=False, graph_pooling='mean')` -> the reference's
@@ -297,7 +332,7 @@ def _checked(w: Dict[str, np.ndarray], spec: Mapping, shape_of) -> Dict[str, np.
 
 def export_weights(model: str, sd: Mapping, directory: str, multi_task: bool = False, keep_eps: bool = False,
                    virtual_node: bool = False, virtual_node_dim: int = 100, emb_dim: int = 100,
-                   attention_pooling: bool = False) -> Dict[str, np.ndarray]:
+                   attention_pooling: bool = False, set2set: bool = False) -> Dict[str, np.ndarray]:
     """Write the `.bin` file(s) `host` / `flowgnn_load_weights_dir` read for `model` ('GIN', 'GIN-VN' or 'GCN').
     multi_task: keep all rows of the prediction head (the engine then needs flowgnn_set_num_tasks(rows) before loading).
     keep_eps (GIN, GIN-VN): a trained eps is not refused; the eps file holds the trained values, for `host --eps` /
@@ -317,8 +352,22 @@ def export_weights(model: str, sd: Mapping, directory: str, multi_task: bool = F
     attention_pooling (GIN, GCN at width 300): the state_dict was trained with graph_pooling='attention'; its gate goes into
     gin_ep1_attnpool_dim300.bin / gcn_ep1_attnpool_dim300.bin beside the others (attention_pooling_from_ogb_state_dict), for
     `host GIN|GCN --emb-dim 300 --attn-pool` / Engine.load_weights_dir(dir, attention_pooling=True) to apply
-    (flowgnn_set_attention_pooling).  Without the keyword such a state_dict is refused: its head was never trained on the mean."""
+    (flowgnn_set_attention_pooling).  Without the keyword such a state_dict is refused: its head was never trained on the mean.
+    set2set (GIN, GCN at width 300): the state_dict was trained with graph_pooling='set2set'; its LSTM and its Linear(2D, NUM_TASK) head
+    go into gin_ep1_set2set_dim300.bin / gcn_ep1_set2set_dim300.bin beside the others (set2set_from_ogb_state_dict), for
+    `host GIN|GCN --emb-dim 300 --set2set` / Engine.load_weights_dir(dir, set2set=True) to apply (flowgnn_set_set2set_pooling).  The
+    model's own set then carries an all-zero [NUM_TASK][D] head and bias -- the 2D-wide head does not fit it -- so a run that forgets the
+    flag gives zeros, not plausible numbers.  Without the keyword such a state_dict is refused, and so is set2set together with
+    attention_pooling."""
     m = model.upper()
+    if set2set and m not in ("GIN", "GCN"):
+        raise ExportError(f"set2set=True is GIN's and GCN's (flowgnn_set_set2set_pooling); {model} has no such readout")
+    if set2set and attention_pooling:
+        raise ExportError("set2set=True and attention_pooling=True: a model has one readout (flowgnn_set_set2set_pooling and "
+                          "flowgnn_set_attention_pooling exclude each other)")
+    if S2S_KEY in sd and not set2set:
+        raise ExportError(f"the state_dict has '{S2S_KEY}': it was trained with graph_pooling='set2set', and its head is 2 x emb_dim wide, "
+                          f"on the LSTM's query vector; pass set2set=True (flowgnn_set_set2set_pooling; 300-wide GIN and GCN)")
     if attention_pooling and m not in ("GIN", "GCN"):
         raise ExportError(f"attention_pooling=True is GIN's and GCN's (flowgnn_set_attention_pooling); {model} has no such readout")
     if ATTN_KEY in sd and not attention_pooling:
@@ -331,6 +380,10 @@ def export_weights(model: str, sd: Mapping, directory: str, multi_task: bool = F
                           f"flowgnn_set_gcn_virtual_node_dim); {model} has no such virtual node")
     if virtual_node and m not in ("GIN", "GCN"):
         raise ExportError(f"virtual_node=True is OGB's gin-virtual or gcn-virtual, which the engine runs as GIN or GCN (not {model})")
+    s2s = None
+    if set2set:  # (before any file is written; the width: GIN's own, read off the state_dict as gin_weights_from_ogb_state_dict reads it)
+        s2s = set2set_from_ogb_state_dict(sd, emb_dim=_get(sd, "gnn_node.atom_encoder.atom_embedding_list.0.weight").shape[1] if m == "GIN" else int(emb_dim))
+        sd = _mean_head_zeroed(sd, s2s["w_hh"].shape[1])
     if m in ("GIN", "GIN-VN"):
         w = gin_weights_from_ogb_state_dict(sd, multi_task=multi_task, keep_eps=keep_eps, virtual_node=virtual_node,
                                             virtual_node_dim=virtual_node_dim)
@@ -341,6 +394,8 @@ def export_weights(model: str, sd: Mapping, directory: str, multi_task: bool = F
             _weights.save_gin_virtual_node(vn, directory)
         if attention_pooling:
             _weights.save_attention_pooling(gate, directory, model="GIN")
+        if set2set:
+            _weights.save_set2set(s2s, directory, model="GIN")
     elif m == "GCN":
         w = gcn_weights_from_ogb_state_dict(sd, multi_task=multi_task, virtual_node=virtual_node, emb_dim=emb_dim, virtual_node_dim=virtual_node_dim)
         vn = gcn_virtual_node_from_ogb_state_dict(sd, virtual_node_dim=virtual_node_dim) if virtual_node else None  # (before any file is written)
@@ -350,6 +405,8 @@ def export_weights(model: str, sd: Mapping, directory: str, multi_task: bool = F
             _weights.save_gcn_virtual_node(vn, directory, emb_dim=int(virtual_node_dim))
         if attention_pooling:
             _weights.save_attention_pooling(gate, directory, model="GCN")
+        if set2set:
+            _weights.save_set2set(s2s, directory, model="GCN")
     else:
         raise ExportError(f"no OGB example model corresponds to the reference's {model} (its PNA/DGN/GAT checkpoints are already "
                           f"flat files: use flowgnn_amd.weights.save_*_weights)")

@@ -280,6 +280,91 @@ def synth_attention_pooling(seed: int = 11, emb_dim: int = 300) -> Dict[str, np.
     return OrderedDict([("w1", w1), ("b1", b1), ("w2", w2)])
 
 
+# OGB's set2set readout for GIN and GCN at width 300 (flowgnn.h: flowgnn_set_set2set_pooling): one file beside the model's set, PyG's
+# Set2Set LSTM (pool.lstm.weight_ih_l0, weight_hh_l0, bias_ih_l0, bias_hh_l0; gate order i, f, g, o) and OGB's Linear(2D, NUM_TASK) head,
+# in the order of the C call's arguments.  The number of processing steps is no tensor: it is given where the file is applied
+SET2SET_KEYS = ("w_ih", "w_hh", "b_ih", "b_hh", "head_w", "head_b")
+SET2SET_EMB_DIMS = (300,)
+_SET2SET_PREFIX = {"GIN": "gin", "GCN": "gcn"}
+
+
+def set2set_shapes(emb_dim: int = 300, num_tasks: int = 1, emb_dims=SET2SET_EMB_DIMS):
+    """w_ih [4D][2D], w_hh [4D][D], b_ih [4D], b_hh [4D], head_w [T][2D], head_b [T] at D = emb_dim, one of emb_dims (the files exist
+    at 300 alone; the C call takes 100-wide tensors too, to refuse them by name), T = num_tasks."""
+    d, t = int(emb_dim), int(num_tasks)
+    if d not in tuple(emb_dims):
+        raise ValueError(f"set2set: emb_dim {emb_dim} is not one of {tuple(emb_dims)} (only the 300-wide models have this readout)")
+    if t < 1:
+        raise ValueError(f"set2set: num_tasks is {num_tasks}, wanted at least 1")
+    return OrderedDict([("w_ih", (4 * d, 2 * d)), ("w_hh", (4 * d, d)), ("b_ih", (4 * d,)), ("b_hh", (4 * d,)), ("head_w", (t, 2 * d)), ("head_b", (t,))])
+
+
+def set2set_file(model: str = "GIN", emb_dim: int = 300) -> str:
+    """gin_ep1_set2set_dim<emb_dim>.bin / gcn_ep1_set2set_dim<emb_dim>.bin"""
+    set2set_shapes(emb_dim)  # (refuses a width that does not exist)
+    if model not in _SET2SET_PREFIX:
+        raise ValueError(f"set2set: model {model!r} is not one of {sorted(_SET2SET_PREFIX)}")
+    return f"{_SET2SET_PREFIX[model]}_ep1_set2set_dim{int(emb_dim)}.bin"
+
+
+def checked_set2set(s2s) -> Dict[str, np.ndarray]:
+    """The dict `s2s` with exactly the keys of SET2SET_KEYS, each as a contiguous float32 array of its shape, the width read off w_hh
+    and NUM_TASK off head_b."""
+    if set(s2s) != set(SET2SET_KEYS):
+        raise ValueError(f"set2set: wanted the keys {list(SET2SET_KEYS)}, got {sorted(s2s)}")
+    w_hh = np.asarray(s2s["w_hh"])
+    if w_hh.ndim != 2 or w_hh.shape[0] != 4 * w_hh.shape[1]:
+        raise ValueError(f"set2set: w_hh is {w_hh.shape}, wanted [4D][D]")
+    out = OrderedDict()
+    for k, shp in set2set_shapes(w_hh.shape[1], max(1, np.asarray(s2s["head_b"]).size), emb_dims=GIN_EMB_DIMS).items():
+        a = np.asarray(s2s[k], dtype=np.float32)
+        if a.size != int(np.prod(shp)):
+            raise ValueError(f"set2set: {k} is {a.shape}, wanted {shp}")
+        out[k] = np.ascontiguousarray(a.reshape(shp))
+    return out
+
+
+def save_set2set(s2s, directory: str, model: str = "GIN") -> None:
+    """Write <model>_ep1_set2set_dim300.bin: the six tensors end to end, little-endian float32.  Nothing applies the file unless asked
+    to: `host GIN|GCN --emb-dim 300 --set2set`, Engine.load_weights_dir(dir, set2set=True)."""
+    s2s = checked_set2set(s2s)
+    name = set2set_file(model, s2s["w_hh"].shape[1])  # (refused before anything is created)
+    os.makedirs(directory, exist_ok=True)
+    np.concatenate([a.ravel() for a in s2s.values()]).astype("<f4").tofile(os.path.join(directory, name))
+
+
+def load_set2set(directory: str, model: str = "GIN", emb_dim: int = 300) -> Dict[str, np.ndarray]:
+    """The six tensors of a directory's set2set file (for Engine.set_set2set_pooling).  NUM_TASK is read off the file's length: the
+    LSTM takes 4D (3D + 2) floats and every task 2D + 1 more; another length is refused."""
+    path = os.path.join(directory, set2set_file(model, emb_dim))
+    d = int(emb_dim)
+    floats, lstm = os.path.getsize(path) // 4, 4 * d * (3 * d + 2)
+    t = (floats - lstm) // (2 * d + 1)
+    if os.path.getsize(path) % 4 or t < 1 or lstm + t * (2 * d + 1) != floats:
+        raise ValueError(f"{path}: {os.path.getsize(path)} bytes are not {lstm} + NUM_TASK x {2 * d + 1} little-endian float32")
+    out, at = OrderedDict(), 0
+    for k, shp in set2set_shapes(d, t).items():
+        out[k] = _read(path, shp, at)
+        at += int(np.prod(shp))
+    return out
+
+
+def synth_set2set(seed: int = 17, emb_dim: int = 300, num_tasks: int = 1) -> Dict[str, np.ndarray]:
+    """Random set2set tensors, drawn in the order of SET2SET_KEYS from one default_rng(seed): the two matrices U(-1/sqrt(D), 1/sqrt(D)),
+    torch's initialisation of an LSTM; both biases U(-1/sqrt(D), 1/sqrt(D)) + 0.3 N(0, 1), so that the gates are not all near 1/2;
+    head_w = 0.15 N(0, 1) sqrt(100 / D) and head_b = 0.12 N(0, 1), the scales of synth_gin_weights' head."""
+    d, t = int(emb_dim), int(num_tasks)
+    rng = np.random.default_rng(seed)
+    k = 1.0 / np.sqrt(d)
+    w_ih = rng.uniform(-k, k, (4 * d, 2 * d)).astype(np.float32)
+    w_hh = rng.uniform(-k, k, (4 * d, d)).astype(np.float32)
+    b_ih = (rng.uniform(-k, k, 4 * d) + 0.3 * rng.standard_normal(4 * d)).astype(np.float32)
+    b_hh = (rng.uniform(-k, k, 4 * d) + 0.3 * rng.standard_normal(4 * d)).astype(np.float32)
+    head_w = (0.15 * rng.standard_normal((t, 2 * d)) * np.sqrt(100.0 / d)).astype(np.float32)
+    head_b = (0.12 * rng.standard_normal(t)).astype(np.float32)
+    return OrderedDict([("w_ih", w_ih), ("w_hh", w_hh), ("b_ih", b_ih), ("b_hh", b_hh), ("head_w", head_w), ("head_b", head_b)])
+
+
 def synth_gin_weights(seed: int = 7, num_tasks: int = 1, emb_dim: int = 100) -> Dict[str, np.ndarray]:
     """Random weights with the measured scales of the shipped GIN set:
     W1 s=0.075, b1 s=0.91, W2 s=0.053, b2 s=0.49, node/edge emb s=0.11/0.14, pred s=0.15.

@@ -810,6 +810,52 @@ int flowgnn_set_attention_pooling(flowgnn_engine* e, int emb_dim, const float* w
 int flowgnn_attention_pooling(const flowgnn_engine* e);   /* 1 on, 0 off, -1 null handle */
 
 /*
+ * OGB's graph_pooling="set2set" readout for GIN and GCN at width 300 (gin, gin-virtual, gcn, gcn-virtual): OGB pools with PyG's
+ * Set2Set(emb_dim, processing_steps) -- an LSTM(2D, D) over the graphs' query vectors -- and reads a head of its own, Linear(2D, NUM_TASK).
+ * With D = emb_dim = 300, r[v] the rows the readout pools (exactly what flowgnn_set_node_embeddings returns) and g(v) the graph of v:
+ *     h_0 = c_0 = 0 [G][D];  q*_0 = 0 [G][2D]
+ *     for t = 1 .. steps:
+ *         z      = W_ih q*_{t-1} + b_ih + W_hh h_{t-1} + b_hh        [G][4D] = (z_i, z_f, z_g, z_o): torch.nn.LSTM's gate order
+ *         c_t    = sigmoid(z_f) c_{t-1} + sigmoid(z_i) tanh(z_g)
+ *         h_t    = sigmoid(z_o) tanh(c_t)
+ *         e[v]   = r[v] . h_t[g(v)]
+ *         m_g    = max over v in g of e[v];  a[v] = exp(e[v] - m_g)
+ *         r_t[g] = (sum over v in g of a[v] r[v]) / (sum over v in g of a[v])    both sums in node order, one chain per column
+ *         q*_t   = [h_t, r_t]
+ *     logit[g][k] = head_b[k] + head_w[k] . q*_steps[g]
+ * w_ih [4D][2D], w_hh [4D][D], b_ih [4D], b_hh [4D] are PyG's pool.lstm.weight_ih_l0, weight_hh_l0, bias_ih_l0, bias_hh_l0; head_w
+ * [num_tasks][2D] and head_b [num_tasks] are OGB's graph_pred_linear.  While the readout is on the model's own [NUM_TASK][D] head is not
+ * read.  A graph without nodes has r_t = 0 and still gets a logit from h_t; a one-node graph has r_t = r[v] exactly.  q*'s first half
+ * is h_{t-1}, so the engine folds w_hh into w_ih's first D columns and the two biases into one, in float64, rounded once; at t = 1 the
+ * product is skipped (z is the bias).  Arithmetic: the product is fp32-accurate on the f16 matrix pipe (three split-f16 MFMAs, the
+ * weights pre-scaled by a power of two and split on the host), with the fp32 re-run of flowgnn_exact_reruns when a value of q* leaves
+ * the f16 range; the cell, the dots, the softmax and the head are fp32, the cell safe at saturation.  Every sum has a fixed order, there
+ * are no atomics, and the bits of a graph's logit depend on that graph alone (profile slots s2s_lstm,
+ * s2s_dot_rows, s2s_pool_rows, s2s_head).
+ * The tensors are host arrays and are copied.  All six NULL turns the readout off (the default) at any width and for any model, and
+ * then every launch is the one it always was.  The setting holds across batches and flowgnn_set_weights, may change between runs on a
+ * resident batch, and drops a recorded launch sequence (option hipgraph).  It combines with eps, NUM_TASK, OGB's virtual node, GIN's f16
+ * numeric mode at width 300 (the readout stays fp32-accurate), node embeddings, flowgnn_get_h, host and device batches, groups and
+ * option hipgraph.
+ * FLOWGNN_ERR_ARG: a null handle; emb_dim other than 100 or 300; some of the six NULL and some not; and, with tensors given: steps
+ * outside 1 .. FLOWGNN_SET2SET_MAX_STEPS; num_tasks < 1 or != flowgnn_num_tasks(e) (flowgnn_last_error names both numbers); a value
+ * that is not finite; emb_dim != flowgnn_emb_dim(e) (flowgnn_last_error names both widths).
+ * FLOWGNN_ERR_UNSUPPORTED (flowgnn_last_error says why): any model but FLOWGNN_MODEL_GIN and FLOWGNN_MODEL_GCN; emb_dim == 100; in
+ * both orders of the two calls, flowgnn_set_pooling other than the mean, flowgnn_set_node_logits, flowgnn_set_attention_pooling (the
+ * two readouts exclude each other) and flowgnn_set_embeddings (the vector the head reads is 2D wide and every embeddings buffer is D
+ * wide); and, while it is on, a change of width and a change of NUM_TASK: turn it off, change, set it again.
+ * flowgnn_set2set_pooling: the steps when on, 0 off, -1 for a null handle.  flowgnn_group_set_set2set_pooling: the setter on every
+ * member.  The <M>_compute_graphs entry points have no form of it.
+ * Files: gin_ep1_set2set_dim300.bin / gcn_ep1_set2set_dim300.bin beside the model's set hold w_ih, w_hh, b_ih, b_hh, head_w, head_b in
+ * this order as LE float32 (NUM_TASK follows from the length); flowgnn_load_weights_dir does not read it; `host GIN|GCN --emb-dim 300
+ * --set2set [--set2set-steps N]` and the Python wrapper's load_weights_dir(dir, set2set=True, set2set_steps=N) do.
+ */
+#define FLOWGNN_SET2SET_MAX_STEPS 8
+int flowgnn_set_set2set_pooling(flowgnn_engine* e, int emb_dim, int steps, int num_tasks, const float* w_ih, const float* w_hh,
+                                const float* b_ih, const float* b_hh, const float* head_w, const float* head_b); /* host arrays, copied; all six NULL = off */
+int flowgnn_set2set_pooling(const flowgnn_engine* e);   /* steps when on, 0 off, -1 null handle */
+
+/*
  * Laplacian eigenvectors: DGN's node_eigen from the graphs alone (the reference reads it from DGN/eig/g%d.txt and does not say where it
  * comes from).  For graph g with n nodes and edges (u, v) in local ids:
  *     A[u][v] = A[v][u] = 1 for every edge with u != v   (both directions and duplicates collapse to 1, self loops are ignored)
@@ -901,6 +947,8 @@ int flowgnn_group_set_gcn_virtual_node(flowgnn_group* g, const float* vn_embeddi
 int flowgnn_group_set_gcn_virtual_node_dim(flowgnn_group* g, int emb_dim, const float* vn_embedding, const float* w1, const float* b1,
                                            const float* w2, const float* b2);
 int flowgnn_group_set_attention_pooling(flowgnn_group* g, int emb_dim, const float* w1, const float* b1, const float* w2);
+int flowgnn_group_set_set2set_pooling(flowgnn_group* g, int emb_dim, int steps, int num_tasks, const float* w_ih, const float* w_hh,
+                                      const float* b_ih, const float* b_hh, const float* head_w, const float* head_b);
 int flowgnn_group_set_batch(flowgnn_group* g, int num_graphs,
                             const int* nums_of_nodes, const int* nums_of_edges,
                             const int* node_feature, const int* edge_list, const int* edge_attr,
