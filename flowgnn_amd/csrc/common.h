@@ -184,6 +184,8 @@ struct DeviceBatch {
                               // every launch is the one it always was.  A forward that finds it set pools by the softmax of the gates
     const void* s2s;          // flowgnn_set_set2set_pooling (GIN, GCN at width 300): the six tensors in the device form of wide_s2s.h, or null: off, every
     int s2s_steps;            // launch is the one it always was.  A forward that finds it set runs s2s_steps set2set steps and the readout's own head
+    int jk;                   // flowgnn_set_jk_residual (GIN at width 300): FLOWGNN_JK_LAST / FLOWGNN_JK_SUM and OGB's residual flag; (0, 0): off, every
+    int residual;             // launch is the one it always was.  Under JK sum the rows the readout pools (and node_emb) are the sum, h[final_h] stays h_5
     int final_h;              // which h[] holds the last stage's output (set by forward)
     const float* tap;         // optional debug tap returned by flowgnn_get_h instead of h[final_h]
     int tap_dim;

@@ -725,6 +725,8 @@ static int set_batch_state(flowgnn_engine* e, int num_graphs, const int* nums_of
     db.attn_pool = e->attn_pool_on ? e->attn_pool.p : nullptr;
     db.s2s = e->s2s_steps ? e->s2s.p : nullptr;
     db.s2s_steps = e->s2s_steps;
+    db.jk = e->jk;
+    db.residual = e->residual;
     db.final_h = 0;
     db.tap = nullptr;
     db.tap_dim = 0;
@@ -1366,6 +1368,11 @@ static int set_width(flowgnn_engine* e, const char* fn, int emb_dim) {
                  std::to_string(emb_dim) + ": turn it off, change the width, set it again";
         return FLOWGNN_ERR_UNSUPPORTED;
     }
+    if (e->jk != FLOWGNN_JK_LAST || e->residual) {  // (on means width 300: the call asks for 100, which has no instance)
+        e->err = who + "JK sum or the residual is on (flowgnn_set_jk_residual), and only the 300-wide GIN has those instances, not width " +
+                 std::to_string(emb_dim) + ": turn it off (FLOWGNN_JK_LAST, 0), then change the width";
+        return FLOWGNN_ERR_UNSUPPORTED;
+    }
     ENGINE_TRY(e, begin_change(e));
     Model* m = gcn ? (emb_dim == FLOWGNN_EMB_DIM_REFERENCE ? make_gcn_model() : make_gcn_wide_model(emb_dim))
                    : (emb_dim == FLOWGNN_EMB_DIM_REFERENCE ? make_gin_model(false) : make_gin_wide_model(emb_dim));
@@ -1847,6 +1854,61 @@ int flowgnn_set_set2set_pooling(flowgnn_engine* e, int emb_dim, int steps, int n
 }
 
 int flowgnn_set2set_pooling(const flowgnn_engine* e) { return e ? e->s2s_steps : -1; }
+
+// OGB's JK="sum" and residual=True for GIN at width 300.  No tensors: the setting is two integers of the
+// engine's, like the pooling mode, and db.jk / db.residual carry it to GinWideModel::forward.  (FLOWGNN_JK_LAST, 0) is the default state
+// and is accepted wherever a handle is valid.
+int flowgnn_set_jk_residual(flowgnn_engine* e, int emb_dim, int jk, int residual) {
+    if (!e) return FLOWGNN_ERR_ARG;
+    const std::string who = "flowgnn_set_jk_residual: ";
+    if (jk != FLOWGNN_JK_LAST && jk != FLOWGNN_JK_SUM) {
+        e->err = who + "jk is " + std::to_string(jk) + "; the values are FLOWGNN_JK_LAST (0) and FLOWGNN_JK_SUM (1)";
+        return FLOWGNN_ERR_ARG;
+    }
+    if (residual != 0 && residual != 1) {
+        e->err = who + "residual is " + std::to_string(residual) + "; the values are 0 (off) and 1 (on)";
+        return FLOWGNN_ERR_ARG;
+    }
+    if (emb_dim != FLOWGNN_EMB_DIM_REFERENCE && emb_dim != FLOWGNN_EMB_DIM_OGB) {
+        e->err = who + "emb_dim is " + std::to_string(emb_dim) + "; the widths are FLOWGNN_EMB_DIM_REFERENCE (100) and FLOWGNN_EMB_DIM_OGB (300)";
+        return FLOWGNN_ERR_ARG;
+    }
+    if (jk != FLOWGNN_JK_LAST || residual) {
+        if (e->model_id == FLOWGNN_MODEL_GCN) {
+            e->err = who + "GCN's rows in HBM are post-linear (W_l a_l + b_l, not h_l), so a residual needs a second row stream through its layer "
+                           "kernel: that form does not exist yet (FLOWGNN_MODEL_GIN only)";
+            return FLOWGNN_ERR_UNSUPPORTED;
+        }
+        if (e->model_id != FLOWGNN_MODEL_GIN) {
+            e->err = who + "JK sum and the residual exist for FLOWGNN_MODEL_GIN only (OGB's gin and gin-virtual at width 300)";
+            return FLOWGNN_ERR_UNSUPPORTED;
+        }
+        if (emb_dim != e->emb_dim) {
+            e->err = who + "emb_dim is " + std::to_string(emb_dim) + " and the engine's width is " + std::to_string(e->emb_dim) +
+                     " (flowgnn_set_emb_dim / flowgnn_set_model_emb_dim)";
+            return FLOWGNN_ERR_ARG;
+        }
+        if (emb_dim != FLOWGNN_EMB_DIM_OGB) {
+            e->err = who + "only the 300-wide GIN has these instances (the 100-wide graph-resident kernels and the 100-wide per-layer path have "
+                           "none): flowgnn_set_emb_dim(e, 300) first";
+            return FLOWGNN_ERR_UNSUPPORTED;
+        }
+    }
+    ENGINE_TRY(e, use_device(e));
+    e->drop_graph();  // a recorded launch sequence is that of the other setting
+    e->jk = jk;
+    e->residual = residual;
+    e->db.jk = jk;  // (launches are stream-ordered: the setting matters to those enqueued after this call)
+    e->db.residual = residual;
+    return FLOWGNN_OK;
+}
+
+int flowgnn_jk_residual(const flowgnn_engine* e, int* jk_out, int* residual_out) {
+    if (!e) return -1;
+    if (jk_out) *jk_out = e->jk;
+    if (residual_out) *residual_out = e->residual;
+    return (e->jk != FLOWGNN_JK_LAST || e->residual) ? 1 : 0;
+}
 
 int flowgnn_set_option(flowgnn_engine* e, const char* key, double value) {
     if (!e || !key) return FLOWGNN_ERR_ARG;

@@ -103,6 +103,8 @@ struct flowgnn_engine {
     fg::GrowBuf attn_pool;            // ... and the gate's three tensors on the device (wide_attn.h)
     int s2s_steps = 0;                // flowgnn_set_set2set_pooling: the engine's as well, 0 = off (db.s2s / db.s2s_steps follow it)
     fg::GrowBuf s2s;                  // ... and its six tensors on the device (wide_s2s.h)
+    int jk = FLOWGNN_JK_LAST;         // flowgnn_set_jk_residual: the engine's as well, across batches and weight sets (db.jk / db.residual follow)
+    int residual = 0;
 
     // the optional outputs (fg::OutSlot): graph embeddings [G][dim] (flowgnn_set_embeddings), node embeddings [N][dim]
     // (flowgnn_set_node_embeddings), node logits [N][num_tasks] (flowgnn_set_node_logits) and, for GAT, the attention coefficients

@@ -635,7 +635,7 @@ public:
                                                                                                 node_graph_.p, G);
             }
             ProfScope p(prof, "gcn_wide_vn_update", s);
-            if (int rc = launch_gw_vn_update(D, db.ogb_vn, 0, vn_t_.p, vn_vec_[0].p, hid_.p, G, exact_, db.range_flag, s)) return rc;
+            if (int rc = launch_gw_vn_update(D, db.ogb_vn, 0, vn_t_.p, vn_vec_[0].p, hid_.p, G, exact_, db.range_flag, nullptr, 0, s)) return rc;
         }
         int cur = 0;
         for (int l = 0; l < GCW_L; l++) {
@@ -674,7 +674,7 @@ public:
                     gcw_vn_t_kernel<D><<<grid_for((long long)G * M::C, 256, 256 * 8), 256, 0, s>>>(vn_part_.p, db.b.node_off, vn_vec_[l & 1].p, vn_t_.p, G);
                 }
                 ProfScope p(prof, "gcn_wide_vn_update", s);
-                if (int rc = launch_gw_vn_update(D, db.ogb_vn, l + 1, vn_t_.p, vn_vec_[(l + 1) & 1].p, hid_.p, G, exact_, db.range_flag, s)) return rc;
+                if (int rc = launch_gw_vn_update(D, db.ogb_vn, l + 1, vn_t_.p, vn_vec_[(l + 1) & 1].p, hid_.p, G, exact_, db.range_flag, nullptr, 0, s)) return rc;
             }
             cur ^= 1;
         }

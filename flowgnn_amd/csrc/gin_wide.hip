@@ -23,6 +23,9 @@
 // Where things live: this file has the layer's kernels, the virtual node's kernels and their three launchers
 // (gin_wide_vn.h; forward() and gcn_wide.hip call the same ones), the weight stream's layout and the model object.  The readout, the
 // fragment packer, the transpose, the edge table and the fp32 MLP launch are wide_common.h's, shared with gcn_wide.hip and wide_attn.hip.
+// The layer kernel's body (GwDims, gw_step, gw_layer_body) is gin_wide_body.h's: gin_wide_jk.hip compiles it once more with OGB's
+// residual=True and JK="sum" in the epilogue (flowgnn_set_jk_residual, section 4.24); forward() launches those instances while the
+// setting is on and the ones below otherwise.
 // FLOWGNN_NUMERIC_F16 at this width (flowgnn_set_numeric_mode_dim, section 4.22): the layer's two single-product kernels live in
 // gin_wide_f16.hip behind gin_wide_f16.h's launcher; this file packs their hi-only weight stream and chooses between the launches.
 #include <cmath>
@@ -32,7 +35,9 @@
 #include "../../include/flowgnn.h"
 #include "common.h"
 #include "dense_split.h"
+#include "gin_wide_body.h"  // GwDims, gw_step and gw_layer_body: the layer kernel's body, which gin_wide_jk.hip instantiates as well (section 4.24)
 #include "gin_wide_f16.h"  // FLOWGNN_NUMERIC_F16 at this width: the hi-only stream's layout and the launcher of gin_wide_f16.hip's kernels
+#include "gin_wide_jk.h"  // flowgnn_set_jk_residual (section 4.24): the launchers of gin_wide_jk.hip's instances
 #include "gin_wide_vn.h"  // the virtual node's launches, defined at the end of this file: forward() and gcn_wide.hip call them
 #include "wide_common.h"  // GW_WAVES / GW_ROWS, gw_relu, the LDS-DMA issue, the encoder, pooling and fp32 dense kernels, the packer, the readout
 
@@ -40,233 +45,6 @@ namespace fg {
 namespace {
 
 constexpr int GW_L = 5;
-
-template <int D>
-struct GwDims {
-    static_assert(D % 4 == 0, "rows are read as float4 pieces");
-    static constexpr int H = 2 * D;
-    static constexpr int C = D / 4;               // float4 pieces of a row
-    static constexpr int KS1 = (D + 31) / 32;     // K-steps of the first product (K padded to 32 KS1)
-    static constexpr int Q = 2 * KS1;             // 16-feature pieces a lane holds four floats of
-    static constexpr int KS2 = (H + 31) / 32;     // K-steps of the second product
-    static constexpr int T1 = 2 * KS2;            // 16-row tiles of the hidden layer (K of the second product padded to 16 T1)
-    static constexpr int T2 = (D + 15) / 16;      // 16-row tiles of the output, the last one masked at column D
-    static constexpr int STEPS = KS2 + 1;         // step s: MLP1 of hidden tiles 2s, 2s + 1 (s < KS2) and K-step s - 1 of MLP2 (s > 0)
-    static_assert(STEPS % 2 == 0, "the step loop alternates two LDS buffers");
-    // chunk s of the weight stream, in 1 KiB fragments (64 lanes x 8 halves):
-    //   [0, W2_OFF): W1 of hidden tiles 2s, 2s + 1: fragment ((ks * 2 + tl) * 2 + p), p = 0 hi, 1 lo          (absent for s = KS2)
-    //   [W2_OFF, B1_OFF): W2 of K-step s - 1: fragment (t2 * 2 + p)                                          (absent for s = 0)
-    //   [B1_OFF, CHUNK_BYTES): b1 of the two hidden tiles, pre-scaled: 2 x 16 floats
-    static constexpr int W2_OFF = KS1 * 2 * 2 * 1024;
-    static constexpr int B1_OFF = W2_OFF + T2 * 2 * 1024;
-    static constexpr int CHUNK_BYTES = B1_OFF + 2 * 16 * 4;
-    static constexpr int PIECES = (CHUNK_BYTES + 1023) / 1024;   // DMA pieces of 1 KiB, the last one partial
-    static constexpr int LAST_LANES = (CHUNK_BYTES - (PIECES - 1) * 1024) / 16;
-    static constexpr int CHUNK_STRIDE = PIECES * 1024;           // in global memory
-    static constexpr size_t LAYER_BYTES = (size_t)STEPS * CHUNK_STRIDE;
-    static constexpr int ECOMB_BYTES = EDGE_COMBOS * D * 4;      // the layer's 60 combined edge rows: in buffer A until the first odd chunk
-    static constexpr int ECOMB_PIECES = (ECOMB_BYTES + 1023) / 1024;
-    static constexpr int ECOMB_LAST_LANES = (ECOMB_BYTES - (ECOMB_PIECES - 1) * 1024) / 16;
-    static_assert(ECOMB_BYTES <= CHUNK_BYTES && ECOMB_BYTES % 16 == 0, "the combined edge table shares buffer A");
-    static_assert(2 * CHUNK_BYTES <= 160 * 1024, "two weight buffers must fit the CU's LDS");
-    static constexpr int TAIL_FLOATS = T2 * 16 + 4;  // per layer, read from global memory: b2 pre-scaled and padded, then 1 / (s1 s2)
-};
-
-template <int D>
-__device__ __forceinline__ void gw_issue(const uint8_t* __restrict__ gsrc, char* lds_buf, int pieces, int last_lanes, int wave, int lane) {
-    gw_issue_pieces<GwDims<D>::PIECES>(gsrc, lds_buf, pieces, last_lanes, wave, lane);  // (wide_common.h)
-}
-
-// one step from the chunk in `wb`: MLP1 of hidden tiles 2s, 2s + 1 (their ReLU'd, split values become h_hi / h_lo for the next step),
-// and K-step s - 1 of MLP2 from the h_hi / h_lo the previous step left
-template <int D>
-__device__ __forceinline__ void gw_step(const char* wb, int s, int lane, int g, const ds_uint4_t (&in_hi)[GwDims<D>::KS1],
-                                        const ds_uint4_t (&in_lo)[GwDims<D>::KS1], ds_uint4_t& h_hi, ds_uint4_t& h_lo,
-                                        float4_t (&acc2)[GwDims<D>::T2], float& vmax) {
-    using M = GwDims<D>;
-    ds_uint4_t n_hi = {0, 0, 0, 0}, n_lo = {0, 0, 0, 0};
-    if (s < M::KS2) {
-        float4_t acc1[2];
-#pragma unroll
-        for (int tl = 0; tl < 2; tl++) {
-            const float4 b = *reinterpret_cast<const float4*>(wb + M::B1_OFF + tl * 64 + g * 16);
-            acc1[tl] = (float4_t){b.x, b.y, b.z, b.w};
-        }
-#pragma unroll
-        for (int ks = 0; ks < M::KS1; ks++) {
-            ds_uint4_t a[2][2];
-#pragma unroll
-            for (int tl = 0; tl < 2; tl++)
-#pragma unroll
-                for (int p = 0; p < 2; p++) a[tl][p] = *reinterpret_cast<const ds_uint4_t*>(wb + ((ks * 2 + tl) * 2 + p) * 1024 + lane * 16);
-#pragma unroll
-            for (int tl = 0; tl < 2; tl++) acc1[tl] = DS_MFMA16(a[tl][0], in_hi[ks], acc1[tl]);
-#pragma unroll
-            for (int tl = 0; tl < 2; tl++) acc1[tl] = DS_MFMA16(a[tl][0], in_lo[ks], acc1[tl]);
-#pragma unroll
-            for (int tl = 0; tl < 2; tl++) acc1[tl] = DS_MFMA16(a[tl][1], in_hi[ks], acc1[tl]);
-        }
-        float4_t r0 = acc1[0], r1 = acc1[1];
-        r0.x = gw_relu(r0.x); r0.y = gw_relu(r0.y); r0.z = gw_relu(r0.z); r0.w = gw_relu(r0.w);
-        r1.x = gw_relu(r1.x); r1.y = gw_relu(r1.y); r1.z = gw_relu(r1.z); r1.w = gw_relu(r1.w);
-        vmax = __builtin_fmaxf(__builtin_fmaxf(vmax, r0.x), r0.y);
-        vmax = __builtin_fmaxf(__builtin_fmaxf(vmax, r0.z), r0.w);
-        vmax = __builtin_fmaxf(__builtin_fmaxf(vmax, r1.x), r1.y);
-        vmax = __builtin_fmaxf(__builtin_fmaxf(vmax, r1.z), r1.w);
-        asm volatile("" : "+v"(vmax));
-        DS_SPLIT2(r0.x, r0.y, n_hi.x, n_lo.x);
-        DS_SPLIT2(r0.z, r0.w, n_hi.y, n_lo.y);
-        DS_SPLIT2(r1.x, r1.y, n_hi.z, n_lo.z);
-        DS_SPLIT2(r1.z, r1.w, n_hi.w, n_lo.w);
-    }
-    if (s > 0) {
-#pragma unroll
-        for (int t2 = 0; t2 < M::T2; t2++) {
-            const ds_uint4_t a_hi = *reinterpret_cast<const ds_uint4_t*>(wb + M::W2_OFF + (t2 * 2 + 0) * 1024 + lane * 16);
-            const ds_uint4_t a_lo = *reinterpret_cast<const ds_uint4_t*>(wb + M::W2_OFF + (t2 * 2 + 1) * 1024 + lane * 16);
-            acc2[t2] = DS_MFMA16(a_hi, h_hi, acc2[t2]);
-            acc2[t2] = DS_MFMA16(a_hi, h_lo, acc2[t2]);
-            acc2[t2] = DS_MFMA16(a_lo, h_hi, acc2[t2]);
-        }
-    }
-    h_hi = n_hi;
-    h_lo = n_lo;
-}
-
-// hout[v] = W2 relu(W1 a[v] + b1) + b2 (ReLU'd if relu_out), a[v] = fma(h[v], self_s, sum over v's in-edges, in CSR order)
-// The body of the layer's three kernels (below); MODE is a compile-time constant in each, and GW_PLAIN compiles to what the one
-// kernel was before the other two existed.
-//   GW_PLAIN   the layer
-//   GW_VN      the layer, and OGB's virtual node of the NEXT layer added in the epilogue: hout[v] = relu(..) + vn_add[node_graph[v]],
-//              one fp32 add just before the store (section 4.17) -- the 16 rows of a tile may belong to 16 different graphs
-//   GW_UPDATE  the virtual node's update MLP: the "rows" are the per-graph sums t, nothing has in-edges (no gather, no edge table)
-enum { GW_PLAIN = 0, GW_VN = 1, GW_UPDATE = 2 };
-
-template <int D, int MODE>
-__device__ __forceinline__ void gw_layer_body(const float* __restrict__ h, float* __restrict__ hout, const int* __restrict__ row_ptr,
-                                              const int* __restrict__ src, const uint8_t* __restrict__ ecode, const float* __restrict__ ecomb,
-                                              const uint8_t* __restrict__ wchunks, const float* __restrict__ tailp, int n_tot, int relu_out,
-                                              float self_s, int* __restrict__ range_flag, const int* __restrict__ node_graph,
-                                              const float* __restrict__ vn_add) {
-    using M = GwDims<D>;
-    // two DISTINCT LDS objects, as in gin_layer_split_kernel: the DMA into one does not alias the reads of the other
-    __shared__ __attribute__((aligned(16))) char s_a[M::CHUNK_BYTES];  // the combined edge table, then the odd chunks
-    __shared__ __attribute__((aligned(16))) char s_b[M::CHUNK_BYTES];  // the even chunks
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int j = lane & 15, g = lane >> 4;
-    const long long node0 = (long long)blockIdx.x * GW_ROWS + wave * 16 + j;
-    const bool valid = node0 < n_tot;
-    const long long node = valid ? node0 : (long long)n_tot - 1;
-
-    int e_cur = MODE == GW_UPDATE ? 0 : row_ptr[node];
-    const int e_end = MODE == GW_UPDATE ? 0 : (valid ? row_ptr[node + 1] : e_cur);
-    gw_issue<D>(wchunks, s_b, M::PIECES, M::LAST_LANES, wave, lane);                                                  // chunk 0
-    if (MODE != GW_UPDATE)
-        gw_issue<D>(reinterpret_cast<const uint8_t*>(ecomb), s_a, M::ECOMB_PIECES, M::ECOMB_LAST_LANES, wave, lane);  // the edge table
-    float bq[4 * M::Q];
-#pragma unroll
-    for (int k = 0; k < 4 * M::Q; k++) bq[k] = 0.0f;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    const float* s_ecomb = reinterpret_cast<const float*>(s_a);
-
-    // ---- gather: one in-edge per trip, in CSR order (a row's sum depends on the row alone); pieces at or beyond column D stay zero
-    while (MODE != GW_UPDATE && __any(e_cur < e_end)) {
-        if (e_cur < e_end) {
-            const int u = src[e_cur];
-            const int code = ecode[e_cur];
-            e_cur++;
-            const float* hr = h + (size_t)u * D + 4 * g;
-            const float* er = s_ecomb + code * D + 4 * g;
-#pragma unroll
-            for (int q0 = 0; q0 < M::Q; q0 += M::KS1) {
-                float4 x[M::KS1];
-#pragma unroll
-                for (int q = 0; q < M::KS1; q++)
-                    if (16 * (q0 + q) + 4 * g < D) x[q] = *reinterpret_cast<const float4*>(hr + 16 * (q0 + q));
-#pragma unroll
-                for (int q = 0; q < M::KS1; q++)
-                    if (16 * (q0 + q) + 4 * g < D) {
-                        const float4 w = *reinterpret_cast<const float4*>(er + 16 * (q0 + q));
-                        bq[4 * (q0 + q) + 0] += relu1(w.x + x[q].x);
-                        bq[4 * (q0 + q) + 1] += relu1(w.y + x[q].y);
-                        bq[4 * (q0 + q) + 2] += relu1(w.z + x[q].z);
-                        bq[4 * (q0 + q) + 3] += relu1(w.w + x[q].w);
-                    }
-            }
-        }
-    }
-    // ---- a = fma(h[v], s_l, m): one fp32 rounding (s_l = 1: the bits of the plain sum), then split into the B operands of MLP1
-    float vmax = 0.0f;
-    ds_uint4_t in_hi[M::KS1], in_lo[M::KS1];
-    {
-        const float* hr = h + (size_t)node * D + 4 * g;
-#pragma unroll
-        for (int q = 0; q < M::Q; q++)
-            if (16 * q + 4 * g < D) {
-                const float4 x = *reinterpret_cast<const float4*>(hr + 16 * q);
-                bq[4 * q + 0] = __builtin_fmaf(x.x, self_s, bq[4 * q + 0]);
-                bq[4 * q + 1] = __builtin_fmaf(x.y, self_s, bq[4 * q + 1]);
-                bq[4 * q + 2] = __builtin_fmaf(x.z, self_s, bq[4 * q + 2]);
-                bq[4 * q + 3] = __builtin_fmaf(x.w, self_s, bq[4 * q + 3]);
-            }
-#pragma unroll
-        for (int k = 0; k < 4 * M::Q; k += 2) vmax = __builtin_fmaxf(__builtin_fmaxf(vmax, __builtin_fabsf(bq[k])), __builtin_fabsf(bq[k + 1]));
-#pragma unroll
-        for (int ks = 0; ks < M::KS1; ks++) {
-            DS_SPLIT2(bq[8 * ks + 0], bq[8 * ks + 1], in_hi[ks].x, in_lo[ks].x);
-            DS_SPLIT2(bq[8 * ks + 2], bq[8 * ks + 3], in_hi[ks].y, in_lo[ks].y);
-            DS_SPLIT2(bq[8 * ks + 4], bq[8 * ks + 5], in_hi[ks].z, in_lo[ks].z);
-            DS_SPLIT2(bq[8 * ks + 6], bq[8 * ks + 7], in_hi[ks].w, in_lo[ks].w);
-        }
-    }
-    float4_t acc2[M::T2];
-#pragma unroll
-    for (int t2 = 0; t2 < M::T2; t2++) {
-        const float4 b = *reinterpret_cast<const float4*>(tailp + 16 * t2 + 4 * g);
-        acc2[t2] = (float4_t){b.x, b.y, b.z, b.w};
-    }
-    const float oscale = tailp[M::T2 * 16];
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();  // every wave is done with the edge table: s_a may be overwritten (chunk 0 has been resident since the first barrier)
-
-    // ---- node MLP, weights streamed through LDS
-    ds_uint4_t h_hi = {0, 0, 0, 0}, h_lo = {0, 0, 0, 0};
-#pragma unroll 1
-    for (int c = 0; c < M::STEPS; c += 2) {
-        gw_issue<D>(wchunks + (size_t)(c + 1) * M::CHUNK_STRIDE, s_a, M::PIECES, M::LAST_LANES, wave, lane);
-        gw_step<D>(s_b, c, lane, g, in_hi, in_lo, h_hi, h_lo, acc2, vmax);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's pieces of chunk c + 1 have landed
-        __syncthreads();                                  // everyone's have; everyone is done with s_b
-        if (c + 2 < M::STEPS) gw_issue<D>(wchunks + (size_t)(c + 2) * M::CHUNK_STRIDE, s_b, M::PIECES, M::LAST_LANES, wave, lane);
-        gw_step<D>(s_a, c + 1, lane, g, in_hi, in_lo, h_hi, h_lo, acc2, vmax);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-    }
-
-    if (valid) {
-        float* row = hout + (size_t)node * D;
-        // (GW_VN: in_hi / in_lo are dead here; the lane's node decides the vector, lane by lane)
-        const float* vrow = MODE == GW_VN ? vn_add + (size_t)node_graph[node] * D : nullptr;
-#pragma unroll
-        for (int t2 = 0; t2 < M::T2; t2++) {
-            const int col = 16 * t2 + 4 * g;
-            if (col < D) {
-                float4_t r = acc2[t2] * oscale;
-                if (relu_out) { r.x = gw_relu(r.x); r.y = gw_relu(r.y); r.z = gw_relu(r.z); r.w = gw_relu(r.w); }
-                if (MODE == GW_VN) {
-                    const float4 a = *reinterpret_cast<const float4*>(vrow + col);
-                    r.x += a.x; r.y += a.y; r.z += a.z; r.w += a.w;
-                }
-                *reinterpret_cast<float4*>(row + col) = make_float4(r.x, r.y, r.z, r.w);
-            }
-        }
-    }
-    if (__any(!(vmax < 6.0e4f))) {
-        if (lane == 0) atomicOr(range_flag, 1);
-    }
-}
 
 template <int D>
 __global__ __launch_bounds__(GW_WAVES * 64) void gw_layer_kernel(const float* __restrict__ h, float* __restrict__ hout,
@@ -550,6 +328,11 @@ public:
             if (int rc = vn_vec_[1].reserve((size_t)G * D)) return rc;
             if (int rc = node_graph_.reserve((size_t)n)) return rc;
         }
+        // OGB's residual=True and JK="sum" (flowgnn_set_jk_residual, section 4.24): with either on, the fast paths' launches are
+        // gin_wide_jk.hip's instances, under the slots of the ones they stand in for; in the default state nothing below differs
+        const bool res_on = db.residual != 0, jk_on = db.jk == FLOWGNN_JK_SUM;
+        if (jk_on)
+            if (int rc = jk_.reserve((size_t)n * D)) return rc;
         if (int rc = readout_.reserve(db, exact_)) return rc;
         {
             ProfScope p(prof, "atom_encoder", s);
@@ -564,7 +347,11 @@ public:
         int cur = 0;
         for (int l = 0; l < GW_L; l++) {
             // (node embeddings: the last layer writes h_5 straight into the caller's buffer, and the readout reads it there)
-            float* const hn = (l == GW_L - 1 && db.node_emb) ? db.node_emb : db.h[cur ^ 1];
+            // (under JK sum the reverse: the rows the pool is taken over are the sum's, so the last layer's sum goes into the caller's
+            // buffer and h_5 into the ping-pong buffer)
+            float* const hn = (l == GW_L - 1 && db.node_emb && !jk_on) ? db.node_emb : db.h[cur ^ 1];
+            const float* const jk_in = !jk_on ? nullptr : l == 0 ? db.h[cur] : jk_.p;  // x_0 is layer 0's input
+            float* const jk_out = !jk_on ? nullptr : (l == GW_L - 1 && db.node_emb) ? db.node_emb : jk_.p;
             const float self_s = db.gin_eps_on ? db.gin_self_scale[l] : 1.0f;
             const float* ecomb = d_ecomb_ + (size_t)l * EDGE_COMBOS * D;
             const int relu_out = l != GW_L - 1;
@@ -578,9 +365,18 @@ public:
                         return rc;
                 }
                 ProfScope p(prof, "gin_wide_vn_update", s);
-                if (int rc = launch_gw_vn_update(D, vnb, l, vn_t_.p, vnn, hid_.p, G, exact_, db.range_flag, s)) return rc;
+                if (int rc = launch_gw_vn_update(D, vnb, l, vn_t_.p, vnn, hid_.p, G, exact_, db.range_flag,
+                                                 !res_on ? nullptr : l == 0 ? vnb : vn_vec_[(l - 1) & 1].p, l == 0 ? 0 : D, s))
+                    return rc;
             }
-            if (!exact_ && f16_) {
+            if (!exact_ && (res_on || jk_on)) {
+                ProfScope p(prof, f16_ ? "gin_wide_layer_f16" : "gin_wide_layer", s);
+                if (int rc = launch_gw_layer_jk(D, f16_, db.h[cur], hn, db.csr.row_ptr, db.csr.src, db.csr.ecode, ecomb,
+                                                f16_ ? d_chunks16_ + (size_t)l * F16::LAYER_BYTES : d_chunks_ + (size_t)l * M::LAYER_BYTES,
+                                                d_tails_ + (size_t)l * M::TAIL_FLOATS, n, relu_out, self_s, db.range_flag,
+                                                vn_next ? node_graph_.p : nullptr, vn_next ? vnn : nullptr, res_on, jk_in, jk_out, s))
+                    return rc;
+            } else if (!exact_ && f16_) {
                 ProfScope p(prof, "gin_wide_layer_f16", s);
                 if (int rc = launch_gw_layer_f16(D, db.h[cur], hn, db.csr.row_ptr, db.csr.src, db.csr.ecode, ecomb,
                                                  d_chunks16_ + (size_t)l * F16::LAYER_BYTES, d_tails_ + (size_t)l * M::TAIL_FLOATS, n, relu_out,
@@ -603,14 +399,19 @@ public:
                                                                                                    db.csr.ecode, ecomb, n, self_s);
                 launch_gw_mlp_f32<D>(db.scratch, d_w1t_ + (size_t)l * D * H, d_b1_ + (size_t)l * H, d_w2t_ + (size_t)l * H * D, d_b2_ + (size_t)l * D,
                                      hid_.p, hn, n, relu_out, s);
+                // (the adds in the fast path's order: the residual, the virtual node's vector, the JK sum)
+                if (res_on)
+                    if (int rc = launch_gw_add_rows(D, hn, hn, db.h[cur], D, n, s)) return rc;
                 if (vn_next)
                     if (int rc = launch_gw_vn_add(D, hn, node_graph_.p, vnn, n, s)) return rc;
+                if (jk_on)
+                    if (int rc = launch_gw_add_rows(D, jk_out, jk_in, hn, D, n, s)) return rc;
             }
             cur ^= 1;
         }
         db.final_h = cur;
-        db.h_valid = !db.node_emb;
-        return readout_.run(db, prof, s, db.node_emb ? db.node_emb : db.h[cur], exact_, hid_.p);
+        db.h_valid = jk_on || !db.node_emb;
+        return readout_.run(db, prof, s, db.node_emb ? db.node_emb : jk_on ? jk_.p : db.h[cur], exact_, hid_.p);
     }
 
 private:
@@ -626,6 +427,7 @@ private:
         vn_vec_[0].release();
         vn_vec_[1].release();
         node_graph_.release();
+        jk_.release();
     }
     bool ready_ = false;
     bool exact_ = false;
@@ -640,6 +442,7 @@ private:
     GrowBuf vn_t_;        // OGB's virtual node: t [G][D], the update's input
     GrowBuf vn_vec_[2];    // ... vn_l and vn_{l+1} [G][D], alternating (both are live while layer l's update runs)
     GrowBufI node_graph_;  // ... and node -> graph [N], written by layer 0's pool launch of every pass
+    GrowBuf jk_;           // JK sum (section 4.24): the running sum of the rows [N][D], reserved only while it is on; neither ping-pong buffer
 };
 
 constexpr int GW_VN_D = FLOWGNN_EMB_DIM_OGB;  // the launchers' one width: the public constant's (the literal stays in make_gin_wide_model)
@@ -660,12 +463,15 @@ void gw_vn_blob_pack(int emb_dim, const float* vn_embedding, const float* w1, co
 }
 
 int launch_gw_vn_update(int emb_dim, const void* blob, int l, const float* t, float* vn_next, float* hid, int num_graphs, bool exact,
-                        int* range_flag, hipStream_t s) {
+                        int* range_flag, const float* vn_prev, int vn_prev_stride, hipStream_t s) {
     if (emb_dim != GW_VN_D || l < 0 || l >= GW_VN_LAYERS) return FLOWGNN_ERR_UNSUPPORTED;
     if (num_graphs <= 0) return 0;
     constexpr int D = GW_VN_D;
     using VB = GwVnBlob<D>;
     const uint8_t* const wl = static_cast<const uint8_t*>(blob) + VB::E_BYTES + (size_t)l * VB::LAYER_STRIDE;
+    if (!exact && vn_prev)  // residual=True (section 4.24): the update instance of gin_wide_jk.hip, the add in its epilogue
+        return launch_gw_vn_update_res(D, t, vn_next, wl, reinterpret_cast<const float*>(wl + VB::TAIL_OFF), num_graphs, range_flag, vn_prev,
+                                       vn_prev_stride, s);
     if (!exact)
         gw_vn_update_kernel<D><<<(int)ceil_div_ll(num_graphs, GW_ROWS), GW_WAVES * 64, 0, s>>>(
             t, vn_next, wl, reinterpret_cast<const float*>(wl + VB::TAIL_OFF), num_graphs, range_flag);
@@ -673,6 +479,7 @@ int launch_gw_vn_update(int emb_dim, const void* blob, int l, const float* t, fl
         launch_gw_mlp_f32<D>(t, reinterpret_cast<const float*>(wl + VB::W1T_OFF), reinterpret_cast<const float*>(wl + VB::B1_OFF),
                              reinterpret_cast<const float*>(wl + VB::W2T_OFF), reinterpret_cast<const float*>(wl + VB::B2_OFF), hid, vn_next,
                              num_graphs, 1, s);
+    if (exact && vn_prev) return launch_gw_add_rows(D, vn_next, vn_next, vn_prev, vn_prev_stride, num_graphs, s);
     return 0;
 }
 

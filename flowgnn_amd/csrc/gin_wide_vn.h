@@ -13,9 +13,11 @@ size_t gw_vn_blob_bytes(int emb_dim);
 void gw_vn_blob_pack(int emb_dim, const float* vn_embedding, const float* w1, const float* b1, const float* w2, const float* b2, void* out);
 
 // vn_next[g] = relu(W2[l] relu(W1[l] t[g] + b1[l]) + b2[l]) for num_graphs rows t; blob: the device form.  exact: the fp32 form
-// (gw_dense_f32_kernel twice; hid [num_graphs][2D] is its hidden rows), else gw_vn_update_kernel, which raises *range_flag itself
+// (gw_dense_f32_kernel twice; hid [num_graphs][2D] is its hidden rows), else gw_vn_update_kernel, which raises *range_flag itself.
+// vn_prev non-null (GIN under residual=True, section 4.24; gcn_wide.hip passes null): vn_next[g] = vn_prev[g * vn_prev_stride] + that,
+// one fp32 add, by gin_wide_jk.hip's instance of the update kernel (exact: by its element-wise add); stride in floats, 0 for E
 int launch_gw_vn_update(int emb_dim, const void* blob, int l, const float* t, float* vn_next, float* hid, int num_graphs, bool exact,
-                        int* range_flag, hipStream_t s);
+                        int* range_flag, const float* vn_prev, int vn_prev_stride, hipStream_t s);
 // t[g] = (the rows of graph g in node order) + vn[g * vn_stride]; node_graph non-null: also the node -> graph array (gw_vn_pool_kernel)
 int launch_gw_vn_pool(int emb_dim, const float* rows, const int* node_off, const float* vn, int vn_stride, float* t, int* node_graph,
                       int num_graphs, hipStream_t s);

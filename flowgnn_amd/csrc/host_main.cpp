@@ -2,7 +2,7 @@
 // OpenCL host (GIN/src/host.cc): load the model's .bin weights, read a graph pack in the reference's on-disk
 // layout, run the whole dataset as ONE batched launch NUM_TRIALS times, write HLS_output.txt.
 //
-//   host <MODEL> [--graphs DIR] [--weights DIR] [--num-graphs N] [--trials T] [--out FILE] [--node-logits FILE] [--attention FILE [--attention-layers MASK]] [--device D | --devices D0,D1,..] [--option key=value] [--numeric f32|q6.10|f16] [--eps] [--ogb-vn] [--attn-pool] [--set2set [--set2set-steps N]] [--emb-dim 100|300] [--eig DIR | --compute-eig] [XCLBIN]
+//   host <MODEL> [--graphs DIR] [--weights DIR] [--num-graphs N] [--trials T] [--out FILE] [--node-logits FILE] [--attention FILE [--attention-layers MASK]] [--device D | --devices D0,D1,..] [--option key=value] [--numeric f32|q6.10|f16] [--eps] [--ogb-vn] [--attn-pool] [--set2set [--set2set-steps N]] [--jk last|sum] [--residual] [--emb-dim 100|300] [--eig DIR | --compute-eig] [XCLBIN]
 //
 //   MODEL        GIN | GIN-VN | GCN | GAT | PNA | DGN
 //   --graphs     directory holding graph_info/ and graph_bin/      (default ../graphs, host.cc:14-15)
@@ -26,6 +26,8 @@
 //   --set2set    GIN, GCN with --emb-dim 300: read gin_ep1_set2set_dim300.bin / gcn_ep1_set2set_dim300.bin (LE float32: w_ih, w_hh, b_ih, b_hh,
 //                head_w, head_b; 1 082 400 + 601 per task of --num-tasks) from the weights directory and run OGB's graph_pooling="set2set"
 //                readout (flowgnn_set_set2set_pooling) with --set2set-steps processing steps (default 2, OGB's); refused with --attn-pool
+//   --jk, --residual   GIN with --emb-dim 300: OGB's GNN(JK="sum") and GNN(residual=True) (flowgnn_set_jk_residual).  Neither is in the weights
+//                directory -- they add no parameter -- so they are given here: the flags the checkpoint was trained with
 //   --emb-dim    GCN: 300 = OGB's default width (flowgnn_set_model_emb_dim), gcn_ep1_dim300.weights.all.bin is read.
 //                GIN: 300 = OGB's default width (flowgnn_set_emb_dim): the weights directory's dim300 files are read (with --eps,
 //                gin_ep1_eps_dim300.bin); 100 (default) = the reference's width.  With --numeric, 300 sends the mode through
@@ -97,7 +99,7 @@ static bool read_eig_txt(const std::string& path, std::vector<float>& eig, size_
 int main(int argc, char** argv) {
     if (argc < 2) {
         fprintf(stderr, "Usage: %s <GIN|GIN-VN|GCN|GAT|PNA|DGN> [--graphs DIR] [--weights DIR] [--num-graphs N] [--trials T] "
-                        "[--out FILE] [--embeddings FILE] [--node-embeddings FILE] [--node-logits FILE] [--attention FILE [--attention-layers MASK]] [--device D | --devices D0,D1,..] [--option key=value] [--numeric f32|q6.10|f16] [--pooling mean|sum|max] [--eps] [--ogb-vn] [--attn-pool] [--set2set [--set2set-steps N]] [--emb-dim 100|300] [--num-tasks T] [--eig DIR | --compute-eig] [XCLBIN File]\n", argv[0]);
+                        "[--out FILE] [--embeddings FILE] [--node-embeddings FILE] [--node-logits FILE] [--attention FILE [--attention-layers MASK]] [--device D | --devices D0,D1,..] [--option key=value] [--numeric f32|q6.10|f16] [--pooling mean|sum|max] [--eps] [--ogb-vn] [--attn-pool] [--set2set [--set2set-steps N]] [--jk last|sum] [--residual] [--emb-dim 100|300] [--num-tasks T] [--eig DIR | --compute-eig] [XCLBIN File]\n", argv[0]);
         return EXIT_FAILURE;
     }
     const std::string model = argv[1];
@@ -108,7 +110,7 @@ int main(int argc, char** argv) {
     int attn_mask = 16;
     int trials = 25, numeric = FLOWGNN_NUMERIC_F32, num_tasks = 1, pooling = FLOWGNN_POOL_MEAN, emb_dim = FLOWGNN_EMB_DIM_REFERENCE;
     bool use_eps = false, use_ogb_vn = false, use_attn_pool = false, use_set2set = false, compute_eig = false;
-    int set2set_steps = 2;
+    int set2set_steps = 2, jk = FLOWGNN_JK_LAST, residual = 0;
     std::vector<int> devices;
     std::vector<std::pair<std::string, double>> options;
     for (int i = 2; i < argc; i++) {
@@ -159,6 +161,12 @@ int main(int argc, char** argv) {
         else if (a == "--attn-pool") use_attn_pool = true;  // OGB's attention readout from the weights directory (flowgnn_set_attention_pooling)
         else if (a == "--set2set") use_set2set = true;  // OGB's set2set readout from the weights directory (flowgnn_set_set2set_pooling)
         else if (a == "--set2set-steps") set2set_steps = atoi(next("--set2set-steps"));
+        else if (a == "--jk") {  // OGB's JK (flowgnn_set_jk_residual; GIN at --emb-dim 300)
+            const std::string m = next("--jk");
+            if (m != "last" && m != "sum") { fprintf(stderr, "--jk wants last or sum\n"); return EXIT_FAILURE; }
+            jk = m == "sum" ? FLOWGNN_JK_SUM : FLOWGNN_JK_LAST;
+        }
+        else if (a == "--residual") residual = 1;  // OGB's residual=True (flowgnn_set_jk_residual; GIN at --emb-dim 300)
         else if (a == "--ogb-vn") use_ogb_vn = true;  // OGB's virtual node from the weights directory (GIN: flowgnn_set_ogb_virtual_node, GCN: flowgnn_set_gcn_virtual_node)
         // anything else (e.g. an .xclbin path) is ignored
     }
@@ -247,6 +255,10 @@ int main(int argc, char** argv) {
         rc = flowgnn_group_set_set2set_pooling(eng, emb_dim, set2set_steps, (int)T, t.data() + at[0], t.data() + at[1], t.data() + at[2], t.data() + at[3],
                                                t.data() + at[4], t.data() + at[5]);
         if (rc) { fprintf(stderr, "--set2set: %d %s\n", rc, flowgnn_group_last_error(eng)); return EXIT_FAILURE; }
+    }
+    if (jk != FLOWGNN_JK_LAST || residual) {
+        rc = flowgnn_group_set_jk_residual(eng, emb_dim, jk, residual);
+        if (rc) { fprintf(stderr, "--jk / --residual: %d %s\n", rc, flowgnn_group_last_error(eng)); return EXIT_FAILURE; }
     }
     printf("\n******* Weights loading done *******\n");
 

@@ -19,6 +19,18 @@ from .graphpack import GraphBatch
 NUMERIC_MODES = {"f32": 0, "q6.10": 1, "f16": 2}
 # flowgnn_set_pooling codes (flowgnn.h: FLOWGNN_POOL_MEAN / _SUM / _MAX)
 POOLING_MODES = {"mean": 0, "sum": 1, "max": 2}
+# flowgnn_set_jk_residual codes (flowgnn.h: FLOWGNN_JK_LAST / _SUM)
+JK_MODES = {"last": 0, "sum": 1}
+JK_NAMES = {v: k for k, v in JK_MODES.items()}
+
+
+def _jk_code(jk) -> int:
+    """OGB's JK names; an integer goes to the library as it is, which judges it"""
+    if isinstance(jk, str):
+        if jk not in JK_MODES:
+            raise ValueError(f"jk is {jk!r}, wanted one of {sorted(JK_MODES)}")
+        return JK_MODES[jk]
+    return int(jk)
 
 
 class FlowGNNError(RuntimeError):
@@ -707,6 +719,19 @@ class Engine:
         """The set2set readout's processing steps, 0 when it is off (flowgnn.h: flowgnn_set2set_pooling)."""
         return int(self.lib.flowgnn_set2set_pooling(self._h))
 
+    def set_jk_residual(self, jk: str = "last", residual: bool = False, emb_dim: int = 300):
+        """GIN at width 300: OGB's GNN(JK=..., residual=...) (flowgnn.h: flowgnn_set_jk_residual).  jk: "last" or "sum"; under "sum" the
+        rows the readout pools, node embeddings and node logits are the sum of the encoder's rows and every layer's rows, while
+        final_h() stays the last layer's output.  Neither flag is in a state_dict: the caller passes what the model was trained with.
+        The engine's, across batches and weight sets; ("last", False) is the default state."""
+        self._check(self.lib.flowgnn_set_jk_residual(self._h, int(emb_dim), _jk_code(jk), int(residual)), "flowgnn_set_jk_residual")
+
+    def jk_residual(self):
+        """(jk, residual) as set_jk_residual takes them (flowgnn.h: flowgnn_jk_residual)."""
+        jk, res = C.c_int(0), C.c_int(0)
+        self.lib.flowgnn_jk_residual(self._h, C.byref(jk), C.byref(res))
+        return JK_NAMES[jk.value], bool(res.value)
+
     def exact_reruns(self) -> int:
         """Forward passes repeated on the exact-fp32 kernels (flowgnn.h: flowgnn_exact_reruns)."""
         return int(self.lib.flowgnn_exact_reruns(self._h))
@@ -864,6 +889,10 @@ class EngineGroup:
         """Engine.set_attention_pooling on every member (flowgnn.h: flowgnn_group_set_attention_pooling)."""
         d, a = _attn_pool_args(gate)
         self._check(self.lib.flowgnn_group_set_attention_pooling(self._h, d, *[_pf(x) for x in a]), "flowgnn_group_set_attention_pooling")
+
+    def set_jk_residual(self, jk: str = "last", residual: bool = False, emb_dim: int = 300):
+        """Engine.set_jk_residual on every member (flowgnn.h: flowgnn_group_set_jk_residual)."""
+        self._check(self.lib.flowgnn_group_set_jk_residual(self._h, int(emb_dim), _jk_code(jk), int(residual)), "flowgnn_group_set_jk_residual")
 
     def set_set2set_pooling(self, s2s=None, steps: int = 2):
         """Engine.set_set2set_pooling on every member (flowgnn.h: flowgnn_group_set_set2set_pooling)."""

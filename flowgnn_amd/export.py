@@ -358,7 +358,10 @@ def export_weights(model: str, sd: Mapping, directory: str, multi_task: bool = F
     `host GIN|GCN --emb-dim 300 --set2set` / Engine.load_weights_dir(dir, set2set=True) to apply (flowgnn_set_set2set_pooling).  The
     model's own set then carries an all-zero [NUM_TASK][D] head and bias -- the 2D-wide head does not fit it -- so a run that forgets the
     flag gives zeros, not plausible numbers.  Without the keyword such a state_dict is refused, and so is set2set together with
-    attention_pooling."""
+    attention_pooling.
+    OGB's GNN(JK=..., residual=...) need nothing here: neither flag adds a parameter, so neither is in a state_dict and the files of
+    such a model are those of a JK='last', residual=False one.  The CALLER passes the flags the model was trained with to the engine
+    (Engine.set_jk_residual / flowgnn_set_jk_residual; `host GIN --emb-dim 300 --jk sum --residual`); nothing can check them."""
     m = model.upper()
     if set2set and m not in ("GIN", "GCN"):
         raise ExportError(f"set2set=True is GIN's and GCN's (flowgnn_set_set2set_pooling); {model} has no such readout")

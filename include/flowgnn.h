@@ -856,6 +856,38 @@ int flowgnn_set_set2set_pooling(flowgnn_engine* e, int emb_dim, int steps, int n
 int flowgnn_set2set_pooling(const flowgnn_engine* e);   /* steps when on, 0 off, -1 null handle */
 
 /*
+ * OGB's JK="sum" and residual=True for GIN at width 300 (gin and gin-virtual): the two arguments of OGB's
+ * GNN(...) that change the forward pass without adding a parameter.  A state_dict of such a model goes through the exporter
+ * unchanged, so the CALLER passes the flags; without this call a checkpoint trained with either runs as JK="last", residual=False.
+ * In the notation of flowgnn_set_ogb_virtual_node_dim (y_l: GIN layer l of its input rows x_l, ReLU'd for l < 4; x_l = h_l without
+ * the virtual node), every add fp32 in every numeric mode:
+ *     h_{l+1}[v] = y_l[v] + x_l[v]                     residual: one add after the ReLU, the last layer included
+ *     x_{l+1}[v] = h_{l+1}[v] + vn_{l+1}[g(v)]         virtual node, l < 4: after the residual's add
+ *     vn_{l+1}[g] = vn_l[g] + relu(w2 relu(w1 t + b1) + b2)      residual with the virtual node (vn_0 = E)
+ *     r[v] = ((((x_0[v] + x_1[v]) + x_2[v]) + x_3[v]) + x_4[v]) + h_5[v]      JK sum: six terms, left to right
+ * so the residual and the JK sum see the rows with the virtual node's vector inside, as OGB's GNN_node_Virtualnode has them.  The six
+ * terms are those of OGB's current source (range(num_layer + 1)); older releases summed range(num_layer), five terms.
+ * r is what the readout pools (every pooling, the attention and set2set readouts, every NUM_TASK), what node embeddings return (their
+ * contract is "the rows the pool is taken over") and what node logits are computed from.  flowgnn_get_h keeps returning the last
+ * layer's output h_5 (with the residual when it is on): under JK sum that is NOT what the readout pools.
+ * The setting is the engine's, like the pooling mode: it holds across batches and flowgnn_set_weights, may change between runs on a
+ * resident batch, and drops a recorded launch sequence (option hipgraph).  (FLOWGNN_JK_LAST, 0) is the default: every launch is the one
+ * it always was, setting it is the same as never calling, and it is accepted wherever the handle is valid.  It combines with a trained
+ * eps, the virtual node, FLOWGNN_NUMERIC_F16 at width 300 and its exact re-run, host and device batches and groups.
+ * FLOWGNN_ERR_ARG: a null handle; jk outside 0..1; residual outside 0..1; emb_dim other than 100 or 300; a non-default setting with
+ * emb_dim != flowgnn_emb_dim(e) (flowgnn_last_error names both widths).
+ * FLOWGNN_ERR_UNSUPPORTED (flowgnn_last_error says why), for a non-default setting: any model but FLOWGNN_MODEL_GIN (GCN's rows in HBM
+ * are post-linear: that form does not exist yet); width 100 (the graph-resident kernels and the 100-wide per-layer path have no
+ * instance); and, while it is on, flowgnn_set_emb_dim / flowgnn_set_model_emb_dim to 100: turn it off, then change the width.
+ * flowgnn_jk_residual: 1 if either is on, 0 off, -1 for a null handle; the outs may be NULL.  flowgnn_group_set_jk_residual: the setter
+ * on every member.  The <M>_compute_graphs entry points have no form of it.  `host GIN --emb-dim 300 --jk sum --residual`.
+ */
+#define FLOWGNN_JK_LAST 0
+#define FLOWGNN_JK_SUM  1
+int flowgnn_set_jk_residual(flowgnn_engine* e, int emb_dim, int jk, int residual);   /* (LAST, 0) = off, the default */
+int flowgnn_jk_residual(const flowgnn_engine* e, int* jk_out, int* residual_out);    /* 1 if either is on, 0 off, -1 null handle; outs may be NULL */
+
+/*
  * Laplacian eigenvectors: DGN's node_eigen from the graphs alone (the reference reads it from DGN/eig/g%d.txt and does not say where it
  * comes from).  For graph g with n nodes and edges (u, v) in local ids:
  *     A[u][v] = A[v][u] = 1 for every edge with u != v   (both directions and duplicates collapse to 1, self loops are ignored)
@@ -949,6 +981,7 @@ int flowgnn_group_set_gcn_virtual_node_dim(flowgnn_group* g, int emb_dim, const 
 int flowgnn_group_set_attention_pooling(flowgnn_group* g, int emb_dim, const float* w1, const float* b1, const float* w2);
 int flowgnn_group_set_set2set_pooling(flowgnn_group* g, int emb_dim, int steps, int num_tasks, const float* w_ih, const float* w_hh,
                                       const float* b_ih, const float* b_hh, const float* head_w, const float* head_b);
+int flowgnn_group_set_jk_residual(flowgnn_group* g, int emb_dim, int jk, int residual);
 int flowgnn_group_set_batch(flowgnn_group* g, int num_graphs,
                             const int* nums_of_nodes, const int* nums_of_edges,
                             const int* node_feature, const int* edge_list, const int* edge_attr,
