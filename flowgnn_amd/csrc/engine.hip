@@ -1369,8 +1369,9 @@ static int set_width(flowgnn_engine* e, const char* fn, int emb_dim) {
         return FLOWGNN_ERR_UNSUPPORTED;
     }
     if (e->jk != FLOWGNN_JK_LAST || e->residual) {  // (on means width 300: the call asks for 100, which has no instance)
-        e->err = who + "JK sum or the residual is on (flowgnn_set_jk_residual), and only the 300-wide GIN has those instances, not width " +
-                 std::to_string(emb_dim) + ": turn it off (FLOWGNN_JK_LAST, 0), then change the width";
+        e->err = who + "JK sum or the residual is on (" + (gcn ? "flowgnn_set_model_jk_residual" : "flowgnn_set_jk_residual") + "), and only the 300-wide " +
+                 (gcn ? "GCN" : "GIN") + " has those instances, not width " + std::to_string(emb_dim) +
+                 ": turn it off (FLOWGNN_JK_LAST, 0), then change the width";
         return FLOWGNN_ERR_UNSUPPORTED;
     }
     ENGINE_TRY(e, begin_change(e));
@@ -1855,12 +1856,12 @@ int flowgnn_set_set2set_pooling(flowgnn_engine* e, int emb_dim, int steps, int n
 
 int flowgnn_set2set_pooling(const flowgnn_engine* e) { return e ? e->s2s_steps : -1; }
 
-// OGB's JK="sum" and residual=True for GIN at width 300.  No tensors: the setting is two integers of the
-// engine's, like the pooling mode, and db.jk / db.residual carry it to GinWideModel::forward.  (FLOWGNN_JK_LAST, 0) is the default state
-// and is accepted wherever a handle is valid.
-int flowgnn_set_jk_residual(flowgnn_engine* e, int emb_dim, int jk, int residual) {
-    if (!e) return FLOWGNN_ERR_ARG;
-    const std::string who = "flowgnn_set_jk_residual: ";
+// OGB's JK="sum" and residual=True at width 300: GIN and, through the model form of the call, GCN (section
+// 4.25).  No tensors: the setting is two integers of the engine's, like the pooling mode, and db.jk / db.residual carry it to
+// GinWideModel::forward / GcnWideModel::forward.  (FLOWGNN_JK_LAST, 0) is the default state and is accepted wherever a handle is valid.
+// `fn`: the caller.  model_form: flowgnn_set_model_jk_residual, which a GCN engine accepts; on a GIN engine the two calls are one.
+static int set_jk_residual(flowgnn_engine* e, const char* fn, bool model_form, int emb_dim, int jk, int residual) {
+    const std::string who = std::string(fn) + ": ";
     if (jk != FLOWGNN_JK_LAST && jk != FLOWGNN_JK_SUM) {
         e->err = who + "jk is " + std::to_string(jk) + "; the values are FLOWGNN_JK_LAST (0) and FLOWGNN_JK_SUM (1)";
         return FLOWGNN_ERR_ARG;
@@ -1874,13 +1875,17 @@ int flowgnn_set_jk_residual(flowgnn_engine* e, int emb_dim, int jk, int residual
         return FLOWGNN_ERR_ARG;
     }
     if (jk != FLOWGNN_JK_LAST || residual) {
-        if (e->model_id == FLOWGNN_MODEL_GCN) {
+        const bool gcn = e->model_id == FLOWGNN_MODEL_GCN;
+        if (gcn && !model_form) {
             e->err = who + "GCN's rows in HBM are post-linear (W_l a_l + b_l, not h_l), so a residual needs a second row stream through its layer "
-                           "kernel: that form does not exist yet (FLOWGNN_MODEL_GIN only)";
+                           "kernel: that form does not exist yet (FLOWGNN_MODEL_GIN only) under this call -- it is "
+                           "flowgnn_set_model_jk_residual that carries it for FLOWGNN_MODEL_GCN at width 300";
             return FLOWGNN_ERR_UNSUPPORTED;
         }
-        if (e->model_id != FLOWGNN_MODEL_GIN) {
-            e->err = who + "JK sum and the residual exist for FLOWGNN_MODEL_GIN only (OGB's gin and gin-virtual at width 300)";
+        if (!gcn && e->model_id != FLOWGNN_MODEL_GIN) {
+            e->err = who + (model_form ? "JK sum and the residual exist for FLOWGNN_MODEL_GIN and FLOWGNN_MODEL_GCN only (OGB's gin, gin-virtual, gcn "
+                                         "and gcn-virtual at width 300)"
+                                       : "JK sum and the residual exist for FLOWGNN_MODEL_GIN only (OGB's gin and gin-virtual at width 300)");
             return FLOWGNN_ERR_UNSUPPORTED;
         }
         if (emb_dim != e->emb_dim) {
@@ -1889,8 +1894,12 @@ int flowgnn_set_jk_residual(flowgnn_engine* e, int emb_dim, int jk, int residual
             return FLOWGNN_ERR_ARG;
         }
         if (emb_dim != FLOWGNN_EMB_DIM_OGB) {
-            e->err = who + "only the 300-wide GIN has these instances (the 100-wide graph-resident kernels and the 100-wide per-layer path have "
-                           "none): flowgnn_set_emb_dim(e, 300) first";
+            if (gcn)
+                e->err = who + "only the 300-wide GCN has these instances (the 100-wide graph-resident kernels and the 100-wide per-layer path have "
+                               "none): flowgnn_set_model_emb_dim(e, 300) first";
+            else
+                e->err = who + "only the 300-wide GIN has these instances (the 100-wide graph-resident kernels and the 100-wide per-layer path have "
+                               "none): flowgnn_set_emb_dim(e, 300) first";
             return FLOWGNN_ERR_UNSUPPORTED;
         }
     }
@@ -1901,6 +1910,16 @@ int flowgnn_set_jk_residual(flowgnn_engine* e, int emb_dim, int jk, int residual
     e->db.jk = jk;  // (launches are stream-ordered: the setting matters to those enqueued after this call)
     e->db.residual = residual;
     return FLOWGNN_OK;
+}
+
+int flowgnn_set_jk_residual(flowgnn_engine* e, int emb_dim, int jk, int residual) {
+    if (!e) return FLOWGNN_ERR_ARG;
+    return set_jk_residual(e, "flowgnn_set_jk_residual", false, emb_dim, jk, residual);
+}
+
+int flowgnn_set_model_jk_residual(flowgnn_engine* e, int emb_dim, int jk, int residual) {
+    if (!e) return FLOWGNN_ERR_ARG;
+    return set_jk_residual(e, "flowgnn_set_model_jk_residual", true, emb_dim, jk, residual);
 }
 
 int flowgnn_jk_residual(const flowgnn_engine* e, int* jk_out, int* residual_out) {

@@ -14,7 +14,7 @@ void gw_vn_blob_pack(int emb_dim, const float* vn_embedding, const float* w1, co
 
 // vn_next[g] = relu(W2[l] relu(W1[l] t[g] + b1[l]) + b2[l]) for num_graphs rows t; blob: the device form.  exact: the fp32 form
 // (gw_dense_f32_kernel twice; hid [num_graphs][2D] is its hidden rows), else gw_vn_update_kernel, which raises *range_flag itself.
-// vn_prev non-null (GIN under residual=True, section 4.24; gcn_wide.hip passes null): vn_next[g] = vn_prev[g * vn_prev_stride] + that,
+// vn_prev non-null (residual=True: GIN, section 4.24, and GCN, section 4.25; null otherwise): vn_next[g] = vn_prev[g * vn_prev_stride] + that,
 // one fp32 add, by gin_wide_jk.hip's instance of the update kernel (exact: by its element-wise add); stride in floats, 0 for E
 int launch_gw_vn_update(int emb_dim, const void* blob, int l, const float* t, float* vn_next, float* hid, int num_graphs, bool exact,
                         int* range_flag, const float* vn_prev, int vn_prev_stride, hipStream_t s);

@@ -282,6 +282,10 @@ int flowgnn_group_set_jk_residual(flowgnn_group* g, int emb_dim, int jk, int res
     return group_all(g, [&](flowgnn_engine* e) { return flowgnn_set_jk_residual(e, emb_dim, jk, residual); });
 }
 
+int flowgnn_group_set_model_jk_residual(flowgnn_group* g, int emb_dim, int jk, int residual) {
+    return group_all(g, [&](flowgnn_engine* e) { return flowgnn_set_model_jk_residual(e, emb_dim, jk, residual); });
+}
+
 int flowgnn_group_set_embeddings(flowgnn_group* g, int on) { return group_all(g, [&](flowgnn_engine* e) { return flowgnn_set_embeddings(e, on); }); }
 int flowgnn_group_set_node_embeddings(flowgnn_group* g, int on) { return group_all(g, [&](flowgnn_engine* e) { return flowgnn_set_node_embeddings(e, on); }); }
 int flowgnn_group_set_node_logits(flowgnn_group* g, int on) { return group_all(g, [&](flowgnn_engine* e) { return flowgnn_set_node_logits(e, on); }); }

@@ -26,7 +26,7 @@
 //   --set2set    GIN, GCN with --emb-dim 300: read gin_ep1_set2set_dim300.bin / gcn_ep1_set2set_dim300.bin (LE float32: w_ih, w_hh, b_ih, b_hh,
 //                head_w, head_b; 1 082 400 + 601 per task of --num-tasks) from the weights directory and run OGB's graph_pooling="set2set"
 //                readout (flowgnn_set_set2set_pooling) with --set2set-steps processing steps (default 2, OGB's); refused with --attn-pool
-//   --jk, --residual   GIN with --emb-dim 300: OGB's GNN(JK="sum") and GNN(residual=True) (flowgnn_set_jk_residual).  Neither is in the weights
+//   --jk, --residual   GIN or GCN with --emb-dim 300: OGB's GNN(JK="sum") and GNN(residual=True) (flowgnn_set_jk_residual; GCN: flowgnn_set_model_jk_residual).  Neither is in the weights
 //                directory -- they add no parameter -- so they are given here: the flags the checkpoint was trained with
 //   --emb-dim    GCN: 300 = OGB's default width (flowgnn_set_model_emb_dim), gcn_ep1_dim300.weights.all.bin is read.
 //                GIN: 300 = OGB's default width (flowgnn_set_emb_dim): the weights directory's dim300 files are read (with --eps,
@@ -161,12 +161,12 @@ int main(int argc, char** argv) {
         else if (a == "--attn-pool") use_attn_pool = true;  // OGB's attention readout from the weights directory (flowgnn_set_attention_pooling)
         else if (a == "--set2set") use_set2set = true;  // OGB's set2set readout from the weights directory (flowgnn_set_set2set_pooling)
         else if (a == "--set2set-steps") set2set_steps = atoi(next("--set2set-steps"));
-        else if (a == "--jk") {  // OGB's JK (flowgnn_set_jk_residual; GIN at --emb-dim 300)
+        else if (a == "--jk") {  // OGB's JK (flowgnn_set_jk_residual / flowgnn_set_model_jk_residual; GIN, GCN at --emb-dim 300)
             const std::string m = next("--jk");
             if (m != "last" && m != "sum") { fprintf(stderr, "--jk wants last or sum\n"); return EXIT_FAILURE; }
             jk = m == "sum" ? FLOWGNN_JK_SUM : FLOWGNN_JK_LAST;
         }
-        else if (a == "--residual") residual = 1;  // OGB's residual=True (flowgnn_set_jk_residual; GIN at --emb-dim 300)
+        else if (a == "--residual") residual = 1;  // OGB's residual=True (the same calls; GIN, GCN at --emb-dim 300)
         else if (a == "--ogb-vn") use_ogb_vn = true;  // OGB's virtual node from the weights directory (GIN: flowgnn_set_ogb_virtual_node, GCN: flowgnn_set_gcn_virtual_node)
         // anything else (e.g. an .xclbin path) is ignored
     }
@@ -257,7 +257,8 @@ int main(int argc, char** argv) {
         if (rc) { fprintf(stderr, "--set2set: %d %s\n", rc, flowgnn_group_last_error(eng)); return EXIT_FAILURE; }
     }
     if (jk != FLOWGNN_JK_LAST || residual) {
-        rc = flowgnn_group_set_jk_residual(eng, emb_dim, jk, residual);
+        // (GCN: the model form of the call, as with --emb-dim; on a GIN engine the two are one)
+        rc = model == "GCN" ? flowgnn_group_set_model_jk_residual(eng, emb_dim, jk, residual) : flowgnn_group_set_jk_residual(eng, emb_dim, jk, residual);
         if (rc) { fprintf(stderr, "--jk / --residual: %d %s\n", rc, flowgnn_group_last_error(eng)); return EXIT_FAILURE; }
     }
     printf("\n******* Weights loading done *******\n");

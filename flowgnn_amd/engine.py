@@ -720,11 +720,15 @@ class Engine:
         return int(self.lib.flowgnn_set2set_pooling(self._h))
 
     def set_jk_residual(self, jk: str = "last", residual: bool = False, emb_dim: int = 300):
-        """GIN at width 300: OGB's GNN(JK=..., residual=...) (flowgnn.h: flowgnn_set_jk_residual).  jk: "last" or "sum"; under "sum" the
-        rows the readout pools, node embeddings and node logits are the sum of the encoder's rows and every layer's rows, while
-        final_h() stays the last layer's output.  Neither flag is in a state_dict: the caller passes what the model was trained with.
-        The engine's, across batches and weight sets; ("last", False) is the default state."""
-        self._check(self.lib.flowgnn_set_jk_residual(self._h, int(emb_dim), _jk_code(jk), int(residual)), "flowgnn_set_jk_residual")
+        """GIN and GCN at width 300: OGB's GNN(JK=..., residual=...) (flowgnn.h: flowgnn_set_jk_residual, and for a GCN engine the model
+        form of the call, flowgnn_set_model_jk_residual).  jk: "last" or "sum"; under "sum" the rows the readout pools, node embeddings
+        and node logits are the sum of the encoder's rows and every layer's rows, while final_h() stays the last layer's output.
+        Neither flag is in a state_dict: the caller passes what the model was trained with.  The engine's, across batches and weight
+        sets; ("last", False) is the default state."""
+        if self.model == "GCN":
+            self._check(self.lib.flowgnn_set_model_jk_residual(self._h, int(emb_dim), _jk_code(jk), int(residual)), "flowgnn_set_model_jk_residual")
+        else:
+            self._check(self.lib.flowgnn_set_jk_residual(self._h, int(emb_dim), _jk_code(jk), int(residual)), "flowgnn_set_jk_residual")
 
     def jk_residual(self):
         """(jk, residual) as set_jk_residual takes them (flowgnn.h: flowgnn_jk_residual)."""
@@ -891,8 +895,12 @@ class EngineGroup:
         self._check(self.lib.flowgnn_group_set_attention_pooling(self._h, d, *[_pf(x) for x in a]), "flowgnn_group_set_attention_pooling")
 
     def set_jk_residual(self, jk: str = "last", residual: bool = False, emb_dim: int = 300):
-        """Engine.set_jk_residual on every member (flowgnn.h: flowgnn_group_set_jk_residual)."""
-        self._check(self.lib.flowgnn_group_set_jk_residual(self._h, int(emb_dim), _jk_code(jk), int(residual)), "flowgnn_group_set_jk_residual")
+        """Engine.set_jk_residual on every member (flowgnn.h: flowgnn_group_set_jk_residual; GCN: flowgnn_group_set_model_jk_residual)."""
+        if self.model == "GCN":
+            self._check(self.lib.flowgnn_group_set_model_jk_residual(self._h, int(emb_dim), _jk_code(jk), int(residual)),
+                        "flowgnn_group_set_model_jk_residual")
+        else:
+            self._check(self.lib.flowgnn_group_set_jk_residual(self._h, int(emb_dim), _jk_code(jk), int(residual)), "flowgnn_group_set_jk_residual")
 
     def set_set2set_pooling(self, s2s=None, steps: int = 2):
         """Engine.set_set2set_pooling on every member (flowgnn.h: flowgnn_group_set_set2set_pooling)."""

@@ -361,7 +361,9 @@ def export_weights(model: str, sd: Mapping, directory: str, multi_task: bool = F
     attention_pooling.
     OGB's GNN(JK=..., residual=...) need nothing here: neither flag adds a parameter, so neither is in a state_dict and the files of
     such a model are those of a JK='last', residual=False one.  The CALLER passes the flags the model was trained with to the engine
-    (Engine.set_jk_residual / flowgnn_set_jk_residual; `host GIN --emb-dim 300 --jk sum --residual`); nothing can check them."""
+    (Engine.set_jk_residual / flowgnn_set_jk_residual; `host GIN --emb-dim 300 --jk sum --residual`); nothing can check them.  That
+    holds for GCN too (gcn and gcn-virtual at width 300): Engine.set_jk_residual / flowgnn_set_model_jk_residual;
+    `host GCN --emb-dim 300 [--ogb-vn] --jk sum --residual`."""
     m = model.upper()
     if set2set and m not in ("GIN", "GCN"):
         raise ExportError(f"set2set=True is GIN's and GCN's (flowgnn_set_set2set_pooling); {model} has no such readout")

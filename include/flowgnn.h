@@ -877,8 +877,9 @@ int flowgnn_set2set_pooling(const flowgnn_engine* e);   /* steps when on, 0 off,
  * FLOWGNN_ERR_ARG: a null handle; jk outside 0..1; residual outside 0..1; emb_dim other than 100 or 300; a non-default setting with
  * emb_dim != flowgnn_emb_dim(e) (flowgnn_last_error names both widths).
  * FLOWGNN_ERR_UNSUPPORTED (flowgnn_last_error says why), for a non-default setting: any model but FLOWGNN_MODEL_GIN (GCN's rows in HBM
- * are post-linear: that form does not exist yet); width 100 (the graph-resident kernels and the 100-wide per-layer path have no
- * instance); and, while it is on, flowgnn_set_emb_dim / flowgnn_set_model_emb_dim to 100: turn it off, then change the width.
+ * are post-linear: that form does not exist yet under this call -- it is flowgnn_set_model_jk_residual, below, that carries it);
+ * width 100 (the graph-resident kernels and the 100-wide per-layer path have no instance); and, while it is on, flowgnn_set_emb_dim /
+ * flowgnn_set_model_emb_dim to 100: turn it off, then change the width.
  * flowgnn_jk_residual: 1 if either is on, 0 off, -1 for a null handle; the outs may be NULL.  flowgnn_group_set_jk_residual: the setter
  * on every member.  The <M>_compute_graphs entry points have no form of it.  `host GIN --emb-dim 300 --jk sum --residual`.
  */
@@ -886,6 +887,26 @@ int flowgnn_set2set_pooling(const flowgnn_engine* e);   /* steps when on, 0 off,
 #define FLOWGNN_JK_SUM  1
 int flowgnn_set_jk_residual(flowgnn_engine* e, int emb_dim, int jk, int residual);   /* (LAST, 0) = off, the default */
 int flowgnn_jk_residual(const flowgnn_engine* e, int* jk_out, int* residual_out);    /* 1 if either is on, 0 off, -1 null handle; outs may be NULL */
+
+/*
+ * The same two options for GCN at width 300 (OGB's gcn and gcn-virtual), through a call that carries the model
+ * as flowgnn_set_model_emb_dim does beside flowgnn_set_emb_dim: flowgnn_set_jk_residual keeps refusing FLOWGNN_MODEL_GCN.  On a GIN
+ * engine this call IS that one (same state, same codes); flowgnn_jk_residual serves both.  conv.py's GNN_node / GNN_node_Virtualnode
+ * with gnn_type="gcn", in the notation above with conv_l GCN layer l (the product W_l x + b_l, the walk, root, 1 / (deg + 1) and the
+ * folded BatchNorm) and y_l = relu(conv_l(x_l)) for l < 4, y_4 = conv_4(x_4):
+ *     x_0[v] = h_0[v] (+ E)                            h_0: the UNPROJECTED atom-encoder rows
+ *     h_{l+1}[v] = y_l[v] + x_l[v]                     residual: one fp32 add after the ReLU, the last layer included
+ *     x_{l+1}[v] = h_{l+1}[v] + vn_{l+1}[g(v)]         virtual node, l < 4: one fp32 add after the residual's
+ *     vn_{l+1}[g] = vn_l[g] + relu(w2 relu(w1 t + b1) + b2),  t = sum_{v in g} x_l[v] + vn_l[g]     (vn_0 = E)
+ *     r[v] = ((((x_0[v] + x_1[v]) + x_2[v]) + x_3[v]) + x_4[v]) + h_5[v]      JK sum: six terms, left to right
+ * r, flowgnn_get_h (h_5, with the residual when it is on), the state and the default are as above.  It combines with
+ * flowgnn_set_gcn_virtual_node_dim, the three poolings, the attention and set2set readouts, NUM_TASK, every optional output, host and
+ * device batches, groups, option hipgraph and the exact re-run.
+ * FLOWGNN_ERR_ARG: as above.  FLOWGNN_ERR_UNSUPPORTED for a non-default setting: any model but FLOWGNN_MODEL_GIN and FLOWGNN_MODEL_GCN;
+ * GCN at width 100 (flowgnn_set_model_emb_dim(e, 300) first); and, while it is on, flowgnn_set_model_emb_dim to 100.
+ * flowgnn_group_set_model_jk_residual: on every member.  `host GCN --emb-dim 300 [--ogb-vn] --jk sum --residual`.
+ */
+int flowgnn_set_model_jk_residual(flowgnn_engine* e, int emb_dim, int jk, int residual);   /* (LAST, 0) = off, the default */
 
 /*
  * Laplacian eigenvectors: DGN's node_eigen from the graphs alone (the reference reads it from DGN/eig/g%d.txt and does not say where it
@@ -982,6 +1003,7 @@ int flowgnn_group_set_attention_pooling(flowgnn_group* g, int emb_dim, const flo
 int flowgnn_group_set_set2set_pooling(flowgnn_group* g, int emb_dim, int steps, int num_tasks, const float* w_ih, const float* w_hh,
                                       const float* b_ih, const float* b_hh, const float* head_w, const float* head_b);
 int flowgnn_group_set_jk_residual(flowgnn_group* g, int emb_dim, int jk, int residual);
+int flowgnn_group_set_model_jk_residual(flowgnn_group* g, int emb_dim, int jk, int residual);
 int flowgnn_group_set_batch(flowgnn_group* g, int num_graphs,
                             const int* nums_of_nodes, const int* nums_of_edges,
                             const int* node_feature, const int* edge_list, const int* edge_attr,
