@@ -123,13 +123,17 @@ def load(directory, virtual_node, num_tasks=1):
     return w, (weights.load_gcn_virtual_node(directory, emb_dim=WIDE) if virtual_node else None)
 
 
-def forward(batch, w, vn=None, jk="last", residual=False, pooling="mean", bn_eps=2.0 ** -10):
+def forward(batch, w, vn=None, jk="last", residual=False, pooling="mean", bn_eps=2.0 ** -10, drop=None):
     """Ref(logits, r [N][D], pooled [G][D], h_5 [N][D], scale, operands) in float64, flowgnn.h's definition line by line:
         x_0 = h_0 (+ E);  h_{l+1} = y_l (+ x_l);  x_{l+1} = h_{l+1} (+ vn_{l+1}[g]);  vn_{l+1} = (vn_l +) relu(w2 relu(w1 t + b1) + b2)
         r = h_5, or ((((x_0 + x_1) + x_2) + x_3) + x_4) + h_5
     y_l = relu(conv_l(x_l)) for l < 4 and conv_4(x_4), conv_l as tests/gcn_wide_ref.forward has it: the product W_l x + b_l, the walk,
-    root, 1 / (deg + 1) and the layer's BatchNorm (bn_eps: the engine's 2^-10 for the exported files, torch's 1e-5 for a state_dict)."""
+    root, 1 / (deg + 1) and the layer's BatchNorm (bn_eps: the engine's 2^-10 for the exported files, torch's 1e-5 for a state_dict).
+    drop: a WRONG form for tests/test_wide_shapes_cpu.py, as tests/ogb_jk_torch.forward takes it."""
     assert jk in JKS, jk
+    assert drop is None or (drop[0] == "residual" and residual) or (drop[0] == "jk" and jk == "sum"), drop
+    keep_res = 1.0 - drop[1] if drop is not None and drop[0] == "residual" else 1.0
+    keep_jk = 1.0 - drop[1] if drop is not None and drop[0] == "jk" else 1.0
     c = lambda a: np.asarray(a, dtype=np.float64)
     nemb, eemb = c(w["node_embedding_weight"]), c(w["edge_embedding_weight"])
     cw, cb, root = c(w["convs_weight"]), c(w["convs_bias"]), c(w["convs_root_emb_weight"])
@@ -164,7 +168,7 @@ def forward(batch, w, vn=None, jk="last", residual=False, pooling="mean", bn_eps
         np.add.at(m, v, norm[:, None] * np.maximum(z[u] + ee, 0.0))
         pre = bn(m + np.maximum(z + root[l], 0.0) / (outdeg[:, None] + 1.0), l)
         y = np.maximum(pre, 0.0) if l != L - 1 else pre
-        h = y + x if residual else y
+        h = y + keep_res * x if residual else y
         big.extend([float(np.abs(x).max()), float(np.abs(z).max()), float(np.abs(m).max()), float(np.abs(pre).max()), float(np.abs(h).max())])
         if vn is not None and l < L - 1:
             t = seg(x) + vec
@@ -179,7 +183,7 @@ def forward(batch, w, vn=None, jk="last", residual=False, pooling="mean", bn_eps
         if l < L - 1:
             ops.append(float(np.abs(x_next).max()))  # a of stage l: what DS_SPLIT2 splits
         if jk == "sum":
-            r = x + x_next if l == 0 else r + x_next  # (x_next of the last layer is h_5)
+            r = keep_jk * (x if l == 0 else r) + x_next  # (x_next of the last layer is h_5)
         x = x_next
     if jk == "last":
         r = h

@@ -14,6 +14,9 @@ values of tests/test_jk_residual_cpu.py and tests/test_jk_residual_gpu.py.  No G
   forward      a NumPy float64 restatement in the ENGINE's terms -- x_l, h_{l+1}, vn_l, r and the add order of flowgnn.h -- in the
                form of tests/gin_wide_vn_ref.forward, on the exported weights (BatchNorms folded, eps as (float)(1.0f + eps)); with
                f16=True the node MLP's operands are rounded as tests/gin_wide_f16_ref.forward rounds them.
+               `operands`, Ref's last field: the largest value the range guards of the split-f16 / f16 kernels watch (gin_wide_body.h,
+               gin_wide_f16_body.h: |a| and the ReLU'd hidden units times the first matrix's power-of-two pre-scale, per layer and
+               per update), as tests/ogb_gcn_jk_torch.forward has it for GCN.
   load         the exported files of a directory, as forward takes them.
 """
 import copy
@@ -26,7 +29,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from flowgnn_amd import weights
-from tests import f16_ref, gin_wide_vn_ref as V, numpy_ref, ogb_torch as T
+from tests import f16_ref, gin_wide_vn_ref as V, numpy_ref, ogb_torch as T, split_ref
 from tests.test_gin_eps import self_scale
 
 JKS = ("last", "sum")
@@ -219,7 +222,7 @@ def variant_rows(virtual_node, jk, residual, variant):
 
 
 # ---------------------------------------------------------------- the engine's terms, in NumPy
-Ref = namedtuple("Ref", "logits rows pooled h5 scale")
+Ref = namedtuple("Ref", "logits rows pooled h5 scale operands")
 ND_OFF, ED_OFF = numpy_ref.ND_OFF, numpy_ref.ED_OFF
 
 
@@ -230,14 +233,19 @@ def load(directory, virtual_node, num_tasks=1):
     return w, vn, weights.load_gin_eps(directory, emb_dim=WIDE)
 
 
-def forward(batch, w, vn=None, eps=None, jk="last", residual=False, pooling="mean", f16=False, eps_f64=False):
-    """Ref(logits, r [N][D], pooled [G][D], h_5 [N][D], scale) in float64, flowgnn.h's definition line by line:
+def forward(batch, w, vn=None, eps=None, jk="last", residual=False, pooling="mean", f16=False, eps_f64=False, drop=None):
+    """Ref(logits, r [N][D], pooled [G][D], h_5 [N][D], scale, operands) in float64, flowgnn.h's definition line by line:
         x_0 = h_0 (+ E);  h_{l+1} = y_l (+ x_l);  x_{l+1} = h_{l+1} (+ vn_{l+1}[g]);  vn_{l+1} = (vn_l +) relu(w2 relu(w1 t + b1) + b2)
         r = h_5, or ((((x_0 + x_1) + x_2) + x_3) + x_4) + h_5
     f16: a, the ReLU'd hidden units (in the scaled domain) and both matrices of the NODE MLP rounded to f16, to nearest even, as
     tests/gin_wide_f16_ref.forward does; the residual, the JK sum and the virtual node's update stay unrounded.
-    eps: s_l = (float)(1.0f + eps[l]) as the engine forms it; eps_f64: 1 + eps[l] in float64, as OGB's own forward has it."""
+    eps: s_l = (float)(1.0f + eps[l]) as the engine forms it; eps_f64: 1 + eps[l] in float64, as OGB's own forward has it.
+    drop: None, or (term, mask [N][D] of bool) -- a WRONG form for tests/test_wide_shapes_cpu.py: where mask is set, every layer leaves
+    out the residual's x_l (term "residual") or the JK store, so that r stays the layer's input sum there (term "jk": r = h_5)."""
     assert jk in JKS, jk
+    assert drop is None or (drop[0] == "residual" and residual) or (drop[0] == "jk" and jk == "sum"), drop
+    keep_res = 1.0 - drop[1] if drop is not None and drop[0] == "residual" else 1.0
+    keep_jk = 1.0 - drop[1] if drop is not None and drop[0] == "jk" else 1.0
     c = lambda a: np.asarray(a, dtype=np.float64)
     rnd = f16_ref.rounder("rne") if f16 else (lambda a: a)
     nemb, eemb = c(w["node_embedding_weight"]), c(w["edge_embedding_weight"])
@@ -252,7 +260,7 @@ def forward(batch, w, vn=None, eps=None, jk="last", residual=False, pooling="mea
     gid = np.repeat(np.arange(G), batch.nums_of_nodes)
     seg = lambda rows: np.add.reduceat(rows, off[:-1], axis=0)
     h = nemb[batch.node_feature.astype(np.int64) + ND_OFF[None, :]].sum(axis=1)
-    big = [1.0, float(np.abs(h).max())]
+    big, ops = [1.0, float(np.abs(h).max())], [0.0]
     if vn is not None:
         E = c(vn["vn_embedding"]).reshape(-1)
         v1, c1, v2, c2 = c(vn["w1"]), c(vn["b1"]), c(vn["w2"]), c(vn["b2"])
@@ -276,19 +284,21 @@ def forward(batch, w, vn=None, eps=None, jk="last", residual=False, pooling="mea
         y = hid @ W2.T + b2[l]
         if l != L - 1:
             y = np.maximum(y, 0.0)
-        h = y + x if residual else y
+        h = y + keep_res * x if residual else y
         big.extend([float(np.abs(x).max()), float(np.abs(a).max()), float(hid.max()), float(np.abs(h).max())])
+        ops.extend([float(np.abs(a).max()), split_ref.pow2_scale(np.asarray(w["node_mlp_1_weights"], np.float32)[l]) * float(hid.max())])
         if vn is not None and l < L - 1:
             t = seg(x) + vec
             uh = np.maximum(t @ v1[l].T + c1[l], 0.0)
             upd = np.maximum(uh @ v2[l].T + c2[l], 0.0)
             vec = vec + upd if residual else upd
             big.extend([float(np.abs(t).max()), float(uh.max()), float(vec.max())])
+            ops.extend([float(np.abs(t).max()), split_ref.pow2_scale(np.asarray(vn["w1"], np.float32)[l]) * float(uh.max())])
             x_next = h + vec[gid]
         else:
             x_next = h
         if jk == "sum":
-            r = x + x_next if l == 0 else r + x_next  # (x_next of the last layer is h_5)
+            r = keep_jk * (x if l == 0 else r) + x_next  # (x_next of the last layer is h_5)
         x = x_next
     if jk == "last":
         r = h
@@ -302,7 +312,7 @@ def forward(batch, w, vn=None, eps=None, jk="last", residual=False, pooling="mea
         pooled = np.maximum.reduceat(r, off[:-1], axis=0)
     big.append(float(np.abs(pooled).max()))
     out = pooled @ pw.T + pb
-    return Ref(out[:, 0] if out.shape[1] == 1 else out, r, pooled, h, max(big))
+    return Ref(out[:, 0] if out.shape[1] == 1 else out, r, pooled, h, max(big), max(ops))
 
 
 def node_logits(w, rows):

@@ -15,6 +15,7 @@ from flowgnn_amd import Engine, EngineGroup, export, graphpack as gp, weights
 from tests import gin_wide_ref as R, split_ref
 from tests.parity import REL, assert_close, err_ratio
 from tests.test_embeddings_gpu import launched
+from tests.wide_cases import CARDS, EDGE_COUNTS, graph, hub, isolated, path  # noqa: F401  (the builders live there; others import them from here)
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -22,8 +23,6 @@ HOST = os.path.join(ROOT, "flowgnn_amd", "host")
 WIDE_SLOT = "gin_wide_layer"
 EXACT_SLOT = "gin_wide_layer_f32"
 EPS = np.asarray(R.TRAINED_EPS, np.float32)
-EDGE_COUNTS = [1, 15, 16, 17, 31, 32, 33, 63, 64, 65, 127, 128, 129, 255, 256, 257]  # every power-of-two row tile up to 256 at its edge and one past it
-CARDS = (119, 4, 12, 12, 10, 6, 6, 2, 2)
 f64 = lambda a: np.asarray(a, dtype=np.float64)
 
 
@@ -36,31 +35,6 @@ def torch_context_first():
         return
     if torch.cuda.is_available():
         torch.cuda.init()
-
-
-def graph(n, edges, seed):
-    """One graph of n nodes with the directed edges [(src, dst)]; the edge attributes walk through all 60 (a0, a1, a2) codes."""
-    rng = np.random.default_rng(seed)
-    nf = np.stack([rng.integers(0, c, n) for c in CARDS], 1).astype(np.int32)
-    el = np.asarray(edges, np.int32).reshape(-1, 2)
-    code = (np.arange(len(el)) + seed) % 60
-    ea = np.stack([code // 12, (code // 2) % 6, code % 2], 1).astype(np.int32)
-    return gp.GraphBatch(np.array([n], np.int32), np.array([len(el)], np.int32), nf, el, ea)
-
-
-def path(n, seed):
-    fwd = [(i, i + 1) for i in range(n - 1)]
-    return graph(n, fwd + [(b, a) for a, b in fwd], seed)
-
-
-def isolated(n, seed):
-    return graph(n, [], seed)
-
-
-def hub(leaves, seed):
-    """Node 0 has `leaves` in-edges and no out-edge: with edges back to the leaves the activations grow by `leaves` every two layers and
-    leave the split's range at 300 leaves (the exact re-run would then compute the result, not the kernel under test)."""
-    return graph(leaves + 1, [(i, 0) for i in range(1, leaves + 1)], seed)
 
 
 def in_range(ref, w):
