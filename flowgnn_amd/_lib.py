@@ -74,6 +74,7 @@ def _declare(lib):
     lib.flowgnn_graph_replays.restype = C.c_longlong
     lib.flowgnn_set_numeric_mode.argtypes = [eng, C.c_int]
     lib.flowgnn_set_numeric_mode_dim.argtypes = [eng, C.c_int, C.c_int]
+    lib.flowgnn_set_model_numeric_mode_dim.argtypes = [eng, C.c_int, C.c_int]
     lib.flowgnn_set_pooling.argtypes = [eng, C.c_int]
     lib.flowgnn_pooling.argtypes = [eng]
     lib.flowgnn_set_gin_eps.argtypes = [eng, p_float]
@@ -131,6 +132,7 @@ def _declare(lib):
     lib.flowgnn_group_set_model_emb_dim.argtypes = [grp, C.c_int]
     lib.flowgnn_group_set_numeric_mode.argtypes = [grp, C.c_int]
     lib.flowgnn_group_set_numeric_mode_dim.argtypes = [grp, C.c_int, C.c_int]
+    lib.flowgnn_group_set_model_numeric_mode_dim.argtypes = [grp, C.c_int, C.c_int]
     lib.flowgnn_group_set_pooling.argtypes = [grp, C.c_int]
     lib.flowgnn_entry_set_pooling.argtypes = [C.c_int, C.c_int]
     lib.flowgnn_group_set_gin_eps.argtypes = [grp, p_float]
@@ -187,6 +189,7 @@ def _declare(lib):
                  "flowgnn_set_ogb_virtual_node", "flowgnn_ogb_virtual_node", "flowgnn_group_set_ogb_virtual_node",
                  "flowgnn_set_ogb_virtual_node_dim", "flowgnn_group_set_ogb_virtual_node_dim",
                  "flowgnn_set_numeric_mode_dim", "flowgnn_group_set_numeric_mode_dim",
+                 "flowgnn_set_model_numeric_mode_dim", "flowgnn_group_set_model_numeric_mode_dim",
                  "flowgnn_set_gcn_virtual_node", "flowgnn_gcn_virtual_node", "flowgnn_group_set_gcn_virtual_node",
                  "flowgnn_set_gcn_virtual_node_dim", "flowgnn_group_set_gcn_virtual_node_dim",
                  "flowgnn_set_attention_pooling", "flowgnn_attention_pooling", "flowgnn_group_set_attention_pooling",

@@ -1345,10 +1345,10 @@ static int set_width(flowgnn_engine* e, const char* fn, int emb_dim) {
     if (e->numeric_mode != FLOWGNN_NUMERIC_F32) {  // (either direction: the mode is the model object's, and the call swaps the object)
         if (emb_dim != FLOWGNN_EMB_DIM_REFERENCE)
             e->err = who + "a numeric mode other than FLOWGNN_NUMERIC_F32 is on (flowgnn_set_numeric_mode), and the width changes in "
-                     "FLOWGNN_NUMERIC_F32 only: width 300 has no fixed-point kernels, and GIN's f16 mode at width 300 is set at that width, through "
-                     "flowgnn_set_numeric_mode_dim";
+                     "FLOWGNN_NUMERIC_F32 only: width 300 has no fixed-point kernels, and the f16 mode at width 300 is set at that width, through "
+                     "flowgnn_set_numeric_mode_dim (GIN) or flowgnn_set_model_numeric_mode_dim (GCN)";
         else
-            e->err = who + "a numeric mode other than FLOWGNN_NUMERIC_F32 is on at width 300 (flowgnn_set_numeric_mode_dim), and the width changes "
+            e->err = who + "a numeric mode other than FLOWGNN_NUMERIC_F32 is on at width 300 (flowgnn_set_numeric_mode_dim / flowgnn_set_model_numeric_mode_dim), and the width changes "
                      "in FLOWGNN_NUMERIC_F32 only: set that mode, change the width, set the numeric mode again";
         return FLOWGNN_ERR_UNSUPPORTED;
     }
@@ -1432,8 +1432,10 @@ int flowgnn_emb_dim(const flowgnn_engine* e) { return e ? e->emb_dim : -1; }
 
 // flowgnn_set_numeric_mode and flowgnn_set_numeric_mode_dim at the engine's width.  with_dim: the call carried the width -- what lets
 // a GIN engine at width 300 take FLOWGNN_NUMERIC_F16 (gin_wide_f16.hip); the call without it keeps refusing
-// every mode but F32 there.  At width 100 the two are one.
-static int set_numeric_mode(flowgnn_engine* e, int mode, bool with_dim) {
+// every mode but F32 there.  At width 100 the two are one.  model_form: the call was flowgnn_set_model_numeric_mode_dim on a GCN engine --
+// what lets a GCN engine at width 300 take FLOWGNN_NUMERIC_F16 (gcn_wide_f16.hip); flowgnn_set_numeric_mode_dim
+// keeps refusing it there.
+static int set_numeric_mode(flowgnn_engine* e, int mode, bool with_dim, bool model_form = false) {
     for (const Output& o : kOutputs)
         if (mode == FLOWGNN_NUMERIC_Q6_10 && o.no_fixed_point && is_on(e, o)) {
             e->err = o.no_fixed_point;
@@ -1442,12 +1444,18 @@ static int set_numeric_mode(flowgnn_engine* e, int mode, bool with_dim) {
     if (mode != FLOWGNN_NUMERIC_F32 && off_default_width(e)) {
         if (!with_dim) {
             e->err = "flowgnn_set_numeric_mode: the engine's width is 300 (flowgnn_set_emb_dim / flowgnn_set_model_emb_dim), which has no fixed-point "
-                     "kernels; GIN's f16 mode at that width goes through flowgnn_set_numeric_mode_dim";
+                     "kernels; GIN's f16 mode at that width goes through flowgnn_set_numeric_mode_dim, GCN's through flowgnn_set_model_numeric_mode_dim";
             return FLOWGNN_ERR_UNSUPPORTED;
         }
-        if (mode != FLOWGNN_NUMERIC_F16 || e->model_id != FLOWGNN_MODEL_GIN) {
+        if (model_form && mode != FLOWGNN_NUMERIC_F16) {
+            e->err = "flowgnn_set_model_numeric_mode_dim: at width 300 the modes are FLOWGNN_NUMERIC_F32 and FLOWGNN_NUMERIC_F16; there are no "
+                     "fixed-point kernels at that width";
+            return FLOWGNN_ERR_UNSUPPORTED;
+        }
+        if (!model_form && (mode != FLOWGNN_NUMERIC_F16 || e->model_id != FLOWGNN_MODEL_GIN)) {
             e->err = "flowgnn_set_numeric_mode_dim: at width 300 the modes are FLOWGNN_NUMERIC_F32 and, for FLOWGNN_MODEL_GIN, FLOWGNN_NUMERIC_F16; "
-                     "there are no fixed-point kernels at that width, and GCN has no f16 kernels";
+                     "there are no fixed-point kernels at that width, and GCN's f16 mode at that width goes through "
+                     "flowgnn_set_model_numeric_mode_dim";
             return FLOWGNN_ERR_UNSUPPORTED;
         }
     }
@@ -1478,9 +1486,8 @@ int flowgnn_set_numeric_mode(flowgnn_engine* e, int mode) {
 
 // The call that carries the width: emb_dim 100 IS the call above (the same state, kernels and bits); 300 reaches gin_wide_f16.hip's
 // kernels on a GIN engine.  emb_dim must be the engine's width.
-int flowgnn_set_numeric_mode_dim(flowgnn_engine* e, int emb_dim, int mode) {
-    if (!e) return FLOWGNN_ERR_ARG;
-    const std::string who = "flowgnn_set_numeric_mode_dim: ";
+static int set_numeric_mode_dim(flowgnn_engine* e, const char* fn, int emb_dim, int mode, bool model_form) {
+    const std::string who = std::string(fn) + ": ";
     if (emb_dim != FLOWGNN_EMB_DIM_REFERENCE && emb_dim != FLOWGNN_EMB_DIM_OGB) {
         e->err = who + "emb_dim is " + std::to_string(emb_dim) + "; the widths are FLOWGNN_EMB_DIM_REFERENCE (100) and FLOWGNN_EMB_DIM_OGB (300)";
         return FLOWGNN_ERR_ARG;
@@ -1496,7 +1503,20 @@ int flowgnn_set_numeric_mode_dim(flowgnn_engine* e, int emb_dim, int mode) {
                  " (flowgnn_set_emb_dim / flowgnn_set_model_emb_dim)";
         return FLOWGNN_ERR_ARG;
     }
-    return set_numeric_mode(e, mode, true);
+    return set_numeric_mode(e, mode, true, model_form);
+}
+
+int flowgnn_set_numeric_mode_dim(flowgnn_engine* e, int emb_dim, int mode) {
+    if (!e) return FLOWGNN_ERR_ARG;
+    return set_numeric_mode_dim(e, "flowgnn_set_numeric_mode_dim", emb_dim, mode, false);
+}
+
+// The call that names no model, as flowgnn_set_model_emb_dim is for the width: on a GCN engine at width 300 it reaches
+// gcn_wide_f16.hip's kernels; on every other engine, and at width 100, it is the call above.
+int flowgnn_set_model_numeric_mode_dim(flowgnn_engine* e, int emb_dim, int mode) {
+    if (!e) return FLOWGNN_ERR_ARG;
+    if (e->model_id != FLOWGNN_MODEL_GCN) return flowgnn_set_numeric_mode_dim(e, emb_dim, mode);
+    return set_numeric_mode_dim(e, "flowgnn_set_model_numeric_mode_dim", emb_dim, mode, true);
 }
 
 int flowgnn_set_pooling(flowgnn_engine* e, int mode) {

@@ -45,6 +45,10 @@
 //   s = 4      h_5 = pre_4 (+ x_4) to the ping-pong buffer, the sum (+ h_5) to the rows the readout pools
 //   update     vn_{l+1} = vn_l + relu(..) under the residual (launch_gw_vn_update's vn_prev)
 // With both flags off none of it exists: forward() takes the branches it took, and no launch comes from the new file.
+//
+// FLOWGNN_NUMERIC_F16 at this width (flowgnn_set_model_numeric_mode_dim): stages 0..3 run gcn_wide_f16.hip's
+// kernels (one rounding of a and of W s to f16, one MFMA per product) on a hi-only stream that set_weights packs beside the split one
+// whatever the mode is; stage 4, the virtual node's update, the readout and the exact re-run are the ones above.
 #include <cmath>
 #include <cstring>
 #include <string>
@@ -56,6 +60,7 @@
 #include "dense_split.h"
 #include "gcn_ogbvn.h"
 #include "gcn_wide_body.h"  // GcwDims, gcw_walk, gcw_step, gcw_vn_add_partials and the layer kernel's body, which gcn_wide_jk.hip instantiates as well (section 4.25)
+#include "gcn_wide_f16.h"   // FLOWGNN_NUMERIC_F16 (section 4.27): the hi-only stream's layout and the launcher of gcn_wide_f16.hip's kernels
 #include "gcn_wide_jk.h"    // flowgnn_set_model_jk_residual (section 4.25): the launchers of gcn_wide_jk.hip's instances
 #include "gin_wide_jk.h"    // ... and the exact re-run's element-wise add (launch_gw_add_rows)
 #include "gin_wide_vn.h"
@@ -237,9 +242,25 @@ void gcw_pack_layer(const float* w, const float* b, uint8_t* out, float* tail) {
     tail[M::SCALE_AT] = 1.0f / s;
 }
 
+// FLOWGNN_NUMERIC_F16 (section 4.27): a layer's hi-only stream (GcwF16Dims, gcn_wide_f16.h) out of its split stream -- the hi
+// fragments r(W s) as gcw_pack_layer left them, the lo fragments dropped; the tail is shared as it is
+template <int D>
+void gcw_pack_layer_f16(const uint8_t* split, uint8_t* out) {
+    using M = GcwDims<D>;
+    using F = GcwF16Dims<D>;
+    static_assert(F::KS == M::KS && F::T == M::T && F::SCALE_AT == M::SCALE_AT, "the two streams cut a product into the same tiles, and share the tail");
+    std::memset(out, 0, F::LAYER_BYTES);
+    for (int t = 0; t < M::T; t++) {
+        const uint8_t* tile = split + (size_t)(t / M::TPC) * M::CHUNK_BYTES + (size_t)(t % M::TPC) * M::TILE_BYTES;
+        uint8_t* o = out + (size_t)(t / F::TPC) * F::CHUNK_BYTES + (size_t)(t % F::TPC) * F::TILE_BYTES;
+        for (int ks = 0; ks < M::KS; ks++) std::memcpy(o + ks * 1024, tile + ks * 2048, 1024);
+    }
+}
+
 template <int D>
 class GcnWideModel : public Model {
     using M = GcwDims<D>;
+    using F16 = GcwF16Dims<D>;
 
 public:
     ~GcnWideModel() override { free_all(); }
@@ -250,6 +271,13 @@ public:
     bool weights_ready() const override { return ready_; }
     void set_exact(bool on) override { exact_ = on; }
     int set_num_tasks(int t) override { return readout_.set_num_tasks(t, ready_); }
+    // FLOWGNN_NUMERIC_F16 (flowgnn_set_model_numeric_mode_dim, section 4.27): stages 0..3 run gcn_wide_f16.hip's kernels on the hi-only
+    // stream, which set_weights packs beside the split one whatever the mode is -- so the two calls come in either order
+    int set_numeric_mode(int mode) override {
+        if (mode != FLOWGNN_NUMERIC_F32 && mode != FLOWGNN_NUMERIC_F16) return FLOWGNN_ERR_UNSUPPORTED;
+        f16_ = mode == FLOWGNN_NUMERIC_F16;
+        return 0;
+    }
     // OGB's virtual node (flowgnn_set_gcn_virtual_node_dim, section 4.19): the tensors' device form is gin_wide.hip's (gin_wide_vn.h) and
     // reaches forward() through DeviceBatch::ogb_vn; here the state, and E [D] for layer 0's folded bias -- in either order with
     // set_weights, and it holds across weight sets
@@ -275,6 +303,7 @@ public:
         std::vector<float> tab((size_t)GCW_L * M::TAB_FLOATS);
         std::vector<float> wt((size_t)(GCW_L - 1) * D * D), v_b(cb + D, cb + (size_t)GCW_L * D);  // the exact form: [K][O] copies of W_1..W_4
         std::vector<uint8_t> chunks((size_t)(GCW_L - 1) * M::LAYER_BYTES);
+        std::vector<uint8_t> chunks16((size_t)(GCW_L - 1) * F16::LAYER_BYTES);
         std::vector<float> tails((size_t)(GCW_L - 1) * M::TAIL_FLOATS);
         for (int l = 0; l < GCW_L; l++) {
             float* tl = &tab[(size_t)l * M::TAB_FLOATS];
@@ -291,6 +320,7 @@ public:
             const float* W = cw + (size_t)l * D * D;
             gw_transpose(W, D, D, &wt[(size_t)(l - 1) * D * D]);
             gcw_pack_layer<D>(W, cb + (size_t)l * D, chunks.data() + (size_t)(l - 1) * M::LAYER_BYTES, tails.data() + (size_t)(l - 1) * M::TAIL_FLOATS);
+            gcw_pack_layer_f16<D>(chunks.data() + (size_t)(l - 1) * M::LAYER_BYTES, chunks16.data() + (size_t)(l - 1) * F16::LAYER_BYTES);
         }
         // x_0 = b_0 + W_0 (sum_k NodeEmb[off_k + f_k]) = sum_k (W_0 NodeEmb[off_k + f_k]) + b_0: W_0 applied to the table once, in double
         // (GcnModel::set_weights); b_0 is the encoder's tenth row
@@ -303,6 +333,7 @@ public:
             }
         int rc;
         if ((rc = upload(&d_chunks_, chunks))) return rc;
+        if ((rc = upload(&d_chunks16_, chunks16))) return rc;
         if ((rc = upload(&d_tails_, tails))) return rc;
         if ((rc = upload(&d_tab_, tab))) return rc;
         if ((rc = upload(&d_proj_, proj))) return rc;
@@ -414,7 +445,14 @@ public:
             float* const rres = res_on ? res_.p : nullptr;
             const float* const jk_in = !jk_on ? nullptr : (l == 0 && res_on) ? res_.p : jk_.p;
             float* const jk_out = !jk_on ? nullptr : (last && db.node_emb) ? db.node_emb : jk_.p;
-            if (!exact_ && ext_on) {
+            if (!exact_ && f16_ && !last) {  // FLOWGNN_NUMERIC_F16 (section 4.27): the four instances of gcn_wide_f16.hip, a slot of their own
+                ProfScope p(prof, "gcn_wide_layer_f16", s);
+                if (int rc = launch_gcw_layer_f16(D, db.h[cur], hn, db.csr.row_ptr, db.csr.src, db.csr.ecode, esc_.p, db.csr.out_deg, tab,
+                                                  d_chunks16_ + (size_t)l * F16::LAYER_BYTES, d_tails_ + (size_t)l * M::TAIL_FLOATS, n, db.range_flag,
+                                                  vn ? node_graph_.p : nullptr, vn ? vn_vec_[l & 1].p : nullptr,
+                                                  vn && feeds_update(l) ? vn_part_.p : nullptr, rres, rres, jk_in, jk_out, s))
+                    return rc;
+            } else if (!exact_ && ext_on) {
                 ProfScope p(prof, "gcn_wide_layer", s);
                 int rc;
                 if (!last)
@@ -502,13 +540,16 @@ private:
         for (auto p : ptrs)
             if (*p) { (void)hipFree(*p); *p = nullptr; }
         if (d_chunks_) { (void)hipFree(d_chunks_); d_chunks_ = nullptr; }
+        if (d_chunks16_) { (void)hipFree(d_chunks16_); d_chunks16_ = nullptr; }
         esc_.release();
         readout_.release();
     }
     bool ready_ = false;
     bool exact_ = false;
+    bool f16_ = false;  // flowgnn_set_model_numeric_mode_dim(FLOWGNN_NUMERIC_F16)
     GwReadout<D> readout_;         // the head's weights, NUM_TASK, the pooled rows and the gates (wide_common.h)
     uint8_t* d_chunks_ = nullptr;  // the weight streams of gcw_layer_kernel: W_1 .. W_4, LAYER_BYTES each
+    uint8_t* d_chunks16_ = nullptr;  // FLOWGNN_NUMERIC_F16: the same four products as hi-only streams, F16::LAYER_BYTES each
     float* d_tails_ = nullptr;     // ... and per product b (pre-scaled, padded) and the output scale
     float* d_tab_ = nullptr;       // per layer: ecomb | root | BN scale | BN shift
     float *d_proj_ = nullptr, *d_b0_ = nullptr;  // W_0 applied to the node table, and b_0

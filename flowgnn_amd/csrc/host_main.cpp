@@ -31,7 +31,9 @@
 //   --emb-dim    GCN: 300 = OGB's default width (flowgnn_set_model_emb_dim), gcn_ep1_dim300.weights.all.bin is read.
 //                GIN: 300 = OGB's default width (flowgnn_set_emb_dim): the weights directory's dim300 files are read (with --eps,
 //                gin_ep1_eps_dim300.bin); 100 (default) = the reference's width.  With --numeric, 300 sends the mode through
-//                flowgnn_group_set_numeric_mode_dim: GIN takes f16 at that width (beside --eps, --ogb-vn and --attn-pool as before)
+//                flowgnn_group_set_numeric_mode_dim: GIN takes f16 at that width (beside --eps, --ogb-vn and --attn-pool as before);
+//                GCN: through flowgnn_group_set_model_numeric_mode_dim, `host GCN --emb-dim 300 --numeric f16 [--ogb-vn] [--jk sum]
+//                [--residual]` -- stages 0..3 with one f16 rounding of each operand of the layer's product
 //   --eig        DGN: directory holding the eigenvector text files g%d.txt                 (default eig, DGN/src/host_load.cc:178)
 //   --compute-eig DGN: compute node_eigen from the graphs on the GPU (flowgnn_laplacian_eigen, on the first engine) and read no --eig DIR
 //   XCLBIN       accepted and ignored, so `./host <xclbin>`-style command lines keep working
@@ -196,8 +198,10 @@ int main(int argc, char** argv) {
     rc = flowgnn_group_load_weights_dir(eng, wdir.c_str());
     if (rc) { fprintf(stderr, "loading weights failed: %d %s\n", rc, flowgnn_group_last_error(eng)); return EXIT_FAILURE; }
     if (numeric != FLOWGNN_NUMERIC_F32) {  // the reference's ap_fixed<16,6> bit patterns, or f16 MLP operands (GIN / GIN-VN)
-        // --emb-dim 300: through the call that carries the width (GIN's f16 mode at that width, gin_wide_f16.hip)
-        rc = emb_dim != FLOWGNN_EMB_DIM_REFERENCE ? flowgnn_group_set_numeric_mode_dim(eng, emb_dim, numeric) : flowgnn_group_set_numeric_mode(eng, numeric);
+        // --emb-dim 300: through the call that carries the width (GIN's f16 mode at that width, gin_wide_f16.hip); GCN's goes through
+        // the call that names no model (gcn_wide_f16.hip), as its width did
+        if (mid == FLOWGNN_MODEL_GCN && emb_dim != FLOWGNN_EMB_DIM_REFERENCE) rc = flowgnn_group_set_model_numeric_mode_dim(eng, emb_dim, numeric);
+        else rc = emb_dim != FLOWGNN_EMB_DIM_REFERENCE ? flowgnn_group_set_numeric_mode_dim(eng, emb_dim, numeric) : flowgnn_group_set_numeric_mode(eng, numeric);
         if (rc) { fprintf(stderr, "numeric mode: %d %s\n", rc, flowgnn_group_last_error(eng)); return EXIT_FAILURE; }
     }
     if (pooling != FLOWGNN_POOL_MEAN) {

@@ -638,10 +638,14 @@ class Engine:
         """"f32" (default), "q6.10": the bit patterns of the reference's own fixed-point format (ap_fixed<16,6>; DGN: ap_fixed<16,3>),
         or "f16" (GIN / GIN-VN): MLP operands rounded to f16, fp32 accumulation (flowgnn.h: FLOWGNN_NUMERIC_F16).
         emb_dim: the engine's width, which sends the call through flowgnn_set_numeric_mode_dim -- the way to "f16" on a GIN engine at
-        set_emb_dim(300); without it the call is flowgnn_set_numeric_mode, which refuses every mode but "f32" at that width."""
+        set_emb_dim(300); without it the call is flowgnn_set_numeric_mode, which refuses every mode but "f32" at that width.
+        A GCN engine takes the model form of the call, flowgnn_set_model_numeric_mode_dim, as set_jk_residual does: the way to "f16" for
+        gcn and gcn-virtual at width 300 (stages 0..3 with one f16 rounding of each operand of the layer's product)."""
         code = NUMERIC_MODES[mode]
         if emb_dim is None:
             self._check(self.lib.flowgnn_set_numeric_mode(self._h, code), "flowgnn_set_numeric_mode")
+        elif self.model == "GCN":
+            self._check(self.lib.flowgnn_set_model_numeric_mode_dim(self._h, int(emb_dim), code), "flowgnn_set_model_numeric_mode_dim")
         else:
             self._check(self.lib.flowgnn_set_numeric_mode_dim(self._h, int(emb_dim), code), "flowgnn_set_numeric_mode_dim")
 
@@ -857,9 +861,13 @@ class EngineGroup:
         return int(self.lib.flowgnn_emb_dim(self.lib.flowgnn_group_engine(self._h, 0)))
 
     def set_numeric_mode(self, mode: str = "f32", emb_dim: Optional[int] = None):
-        """Engine.set_numeric_mode on every member (flowgnn.h: flowgnn_group_set_numeric_mode; with emb_dim: ..._dim)."""
+        """Engine.set_numeric_mode on every member (flowgnn.h: flowgnn_group_set_numeric_mode; with emb_dim: ..._dim; GCN:
+        flowgnn_group_set_model_numeric_mode_dim)."""
         if emb_dim is None:
             self._check(self.lib.flowgnn_group_set_numeric_mode(self._h, NUMERIC_MODES[mode]), "flowgnn_group_set_numeric_mode")
+        elif self.model == "GCN":
+            self._check(self.lib.flowgnn_group_set_model_numeric_mode_dim(self._h, int(emb_dim), NUMERIC_MODES[mode]),
+                        "flowgnn_group_set_model_numeric_mode_dim")
         else:
             self._check(self.lib.flowgnn_group_set_numeric_mode_dim(self._h, int(emb_dim), NUMERIC_MODES[mode]), "flowgnn_group_set_numeric_mode_dim")
 

@@ -602,6 +602,29 @@ int flowgnn_set_numeric_mode(flowgnn_engine* e, int mode);
  * width again stays a no-op.
  */
 int flowgnn_set_numeric_mode_dim(flowgnn_engine* e, int emb_dim, int mode);
+/*
+ * The same call in the form that names no model, as flowgnn_set_model_emb_dim is for the width.  On a FLOWGNN_MODEL_GIN engine it IS
+ * flowgnn_set_numeric_mode_dim; at emb_dim FLOWGNN_EMB_DIM_REFERENCE on any engine it IS flowgnn_set_numeric_mode (GCN's F16 at width
+ * 100 stays FLOWGNN_ERR_UNSUPPORTED).  On a FLOWGNN_MODEL_GCN engine at FLOWGNN_EMB_DIM_OGB (flowgnn_set_model_emb_dim) it accepts
+ * FLOWGNN_NUMERIC_F32 and FLOWGNN_NUMERIC_F16; FLOWGNN_NUMERIC_Q6_10 returns FLOWGNN_ERR_UNSUPPORTED.  emb_dim other than the engine's
+ * width, a width that is neither 100 nor 300, an unknown mode and a null handle: FLOWGNN_ERR_ARG, as above.  flowgnn_set_numeric_mode
+ * and flowgnn_set_numeric_mode_dim keep answering FLOWGNN_ERR_UNSUPPORTED to F16 on a GCN engine at width 300; their texts name this call.
+ * FLOWGNN_NUMERIC_F16 for GCN / gcn-virtual at width 300, with D = 300: in stages s = 0..3 the two operands of
+ * the layer's one product x_{s+1} = W_{s+1} a_{s+1} + b_{s+1} are rounded to f16, to nearest even --
+ *   a_{s+1}, what the kernel holds behind the walk, the epilogue (root, 1 / (deg + 1), the folded BatchNorm, ReLU), the residual add and
+ *   the virtual node's add, at the point where the default mode splits it into two halves;
+ *   the weight matrix after its power-of-two scale, r(W s) / s: the hi halves of the default mode's split stream
+ * -- and the product is ONE f16 x f16 MFMA per K-step and output tile, with fp32 accumulation, the pre-scaled bias and 1 / s as in the
+ * default mode.  fp32 and unchanged: the encoder and x_0, the walk, root, 1 / (deg + 1) and the folded BatchNorm, the residual add and the
+ * virtual node's add, the partial rows and the rows of flowgnn_set_model_jk_residual (they hold the unrounded a), stage 4, the virtual
+ * node's sums and its update MLP, the pools, every readout (mean, sum, max, attention, set2set), the head and the node logits.  Range
+ * fallback as above: a beyond 6e4 raises the flag and the pass is repeated on the default mode's exact fp32 path.
+ * The mode is the engine's: it survives flowgnn_set_weights, new batches, pooling, NUM_TASK, flowgnn_set_gcn_virtual_node_dim,
+ * flowgnn_set_model_jk_residual and the attention and set2set readout setters, in either order with them.  While it is not
+ * FLOWGNN_NUMERIC_F32, flowgnn_set_model_emb_dim(e, 100) returns FLOWGNN_ERR_UNSUPPORTED and leaves the mode as it was (set F32, change
+ * the width, set the mode again); the same width again stays a no-op.  flowgnn_set_numeric_mode(e, FLOWGNN_NUMERIC_F32) always goes back.
+ */
+int flowgnn_set_model_numeric_mode_dim(flowgnn_engine* e, int emb_dim, int mode);
 
 /*
  * Pooling of the readout (GIN, GIN-VN, GCN, GAT): how a graph's last node rows r[v] (what
@@ -991,6 +1014,7 @@ int flowgnn_group_set_emb_dim(flowgnn_group* g, int emb_dim);
 int flowgnn_group_set_model_emb_dim(flowgnn_group* g, int emb_dim);
 int flowgnn_group_set_numeric_mode(flowgnn_group* g, int mode);
 int flowgnn_group_set_numeric_mode_dim(flowgnn_group* g, int emb_dim, int mode);
+int flowgnn_group_set_model_numeric_mode_dim(flowgnn_group* g, int emb_dim, int mode);
 int flowgnn_group_set_pooling(flowgnn_group* g, int mode);
 int flowgnn_group_set_gin_eps(flowgnn_group* g, const float* eps);
 int flowgnn_group_set_ogb_virtual_node(flowgnn_group* g, const float* vn_embedding, const float* w1, const float* b1, const float* w2, const float* b2);
