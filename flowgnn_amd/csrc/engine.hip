@@ -1435,7 +1435,14 @@ int flowgnn_emb_dim(const flowgnn_engine* e) { return e ? e->emb_dim : -1; }
 // every mode but F32 there.  At width 100 the two are one.  model_form: the call was flowgnn_set_model_numeric_mode_dim on a GCN engine --
 // what lets a GCN engine at width 300 take FLOWGNN_NUMERIC_F16 (gcn_wide_f16.hip); flowgnn_set_numeric_mode_dim
 // keeps refusing it there.
-static int set_numeric_mode(flowgnn_engine* e, int mode, bool with_dim, bool model_form = false) {
+// pna_form: the call was flowgnn_set_model_numeric_mode_dim(e, FLOWGNN_EMB_DIM_PNA, ..) on a PNA engine -- the one way to PNA's
+// FLOWGNN_NUMERIC_F16 (pna_f16.hip); every other call keeps refusing it there.
+static int set_numeric_mode(flowgnn_engine* e, int mode, bool with_dim, bool model_form = false, bool pna_form = false) {
+    if (mode == FLOWGNN_NUMERIC_F16 && e->model_id == FLOWGNN_MODEL_PNA && !pna_form) {
+        e->err = "flowgnn_set_numeric_mode: PNA's f16 mode goes through the call that carries the model, with the model's true width: "
+                 "flowgnn_set_model_numeric_mode_dim(e, FLOWGNN_EMB_DIM_PNA (80), FLOWGNN_NUMERIC_F16)";
+        return FLOWGNN_ERR_UNSUPPORTED;
+    }
     for (const Output& o : kOutputs)
         if (mode == FLOWGNN_NUMERIC_Q6_10 && o.no_fixed_point && is_on(e, o)) {
             e->err = o.no_fixed_point;
@@ -1490,6 +1497,8 @@ static int set_numeric_mode_dim(flowgnn_engine* e, const char* fn, int emb_dim, 
     const std::string who = std::string(fn) + ": ";
     if (emb_dim != FLOWGNN_EMB_DIM_REFERENCE && emb_dim != FLOWGNN_EMB_DIM_OGB) {
         e->err = who + "emb_dim is " + std::to_string(emb_dim) + "; the widths are FLOWGNN_EMB_DIM_REFERENCE (100) and FLOWGNN_EMB_DIM_OGB (300)";
+        if (emb_dim == FLOWGNN_EMB_DIM_PNA)
+            e->err += "; FLOWGNN_EMB_DIM_PNA (80) is a width of the model form alone, flowgnn_set_model_numeric_mode_dim on a FLOWGNN_MODEL_PNA engine";
         return FLOWGNN_ERR_ARG;
     }
     if (mode != FLOWGNN_NUMERIC_F32 && mode != FLOWGNN_NUMERIC_Q6_10 && mode != FLOWGNN_NUMERIC_F16) {
@@ -1515,6 +1524,14 @@ int flowgnn_set_numeric_mode_dim(flowgnn_engine* e, int emb_dim, int mode) {
 // gcn_wide_f16.hip's kernels; on every other engine, and at width 100, it is the call above.
 int flowgnn_set_model_numeric_mode_dim(flowgnn_engine* e, int emb_dim, int mode) {
     if (!e) return FLOWGNN_ERR_ARG;
+    if (e->model_id == FLOWGNN_MODEL_PNA && emb_dim == FLOWGNN_EMB_DIM_PNA) {  // PNA at its true width: F32, Q6_10 (the plain call's), F16
+        if (mode != FLOWGNN_NUMERIC_F32 && mode != FLOWGNN_NUMERIC_Q6_10 && mode != FLOWGNN_NUMERIC_F16) {
+            e->err = "flowgnn_set_model_numeric_mode_dim: mode is " + std::to_string(mode) +
+                     "; the modes are FLOWGNN_NUMERIC_F32 (0), FLOWGNN_NUMERIC_Q6_10 (1) and FLOWGNN_NUMERIC_F16 (2)";
+            return FLOWGNN_ERR_ARG;
+        }
+        return set_numeric_mode(e, mode, true, true, true);
+    }
     if (e->model_id != FLOWGNN_MODEL_GCN) return flowgnn_set_numeric_mode_dim(e, emb_dim, mode);
     return set_numeric_mode_dim(e, "flowgnn_set_model_numeric_mode_dim", emb_dim, mode, true);
 }

@@ -57,10 +57,27 @@ struct PnaResidentLaunch {
 void launch_pna_resident_default(const PnaResidentLaunch& a, int grid, hipStream_t s);  // pna.hip
 void launch_pna_resident_emb(const PnaResidentLaunch& a, int grid, hipStream_t s);      // pna_emb.hip
 void launch_pna_resident_rows(const PnaResidentLaunch& a, int grid, hipStream_t s);     // pna_rows.hip
-#if defined(FG_RESIDENT_EMB_TU) || defined(FG_RESIDENT_ROWS_TU)
+// Single-product instances (FLOWGNN_NUMERIC_F16): pna_f16.hip, pna_emb_f16.hip and pna_rows_f16.hip compile this
+// file once more with PNA_SINGLE_PRODUCT = 1 -- the same kernels under their own names, every operand of the layer's 320 -> 3 x 80
+// contraction one f16 value (round to nearest even) and every product ONE f16 MFMA (fp32 accumulate).  wpk is then the hi-halves-only
+// stream (15 KiB chunks).  Host side and tile builders exist in this file's own translation unit only.
+#ifndef PNA_SINGLE_PRODUCT
+#define PNA_SINGLE_PRODUCT 0
+#endif
+void launch_pna_resident_f16_default(const PnaResidentLaunch& a, int grid, hipStream_t s);  // pna_f16.hip
+void launch_pna_resident_f16_emb(const PnaResidentLaunch& a, int grid, hipStream_t s);      // pna_emb_f16.hip
+void launch_pna_resident_f16_rows(const PnaResidentLaunch& a, int grid, hipStream_t s);     // pna_rows_f16.hip
+// the per-layer kernels' single-product instances (pna_f16.hip): the arguments of pna_layer_fused_kernel / pna_dense_split_kernel
+void launch_pna_layer_fused_f16(const float* h, float* hout, const uint8_t* desc, const int* out_deg, const uint8_t* wpk, const float* bias,
+                                float avg_deg, float oscale, const int* tile_row, int n_tiles, int* range_flag, int ablate, unsigned long long* prof_out, int grid,
+                                hipStream_t s);
+void launch_pna_dense_split_f16(const float* agg, const float* h, float* hout, const int* out_deg, const uint8_t* wpk, const float* bias,
+                                float avg_deg, float oscale, int n_tot, int* range_flag, hipStream_t s);
+#if defined(FG_RESIDENT_EMB_TU) || defined(FG_RESIDENT_ROWS_TU) || PNA_SINGLE_PRODUCT
 #define FG_RESIDENT_KERNEL_TU 1
 namespace {
 #endif
+constexpr bool PNA_F16 = PNA_SINGLE_PRODUCT != 0;
 #ifdef FG_RESIDENT_EMB_TU
 constexpr bool RESIDENT_EMB = true;
 #else
@@ -200,8 +217,10 @@ __global__ __launch_bounds__(256) void pna_dense_kernel(const float* __restrict_
 // K = 320 = 10 K-steps exactly: slot e of K-step ks is aggregate feature [a][16 q + 4 g + (e & 3)] with
 // 5 a + q = 2 ks + (e >> 2).  The scalers are applied to the accumulators in the epilogue, in the oracle's order.
 constexpr int PNA_KS = 10;
-constexpr int PNA_CHUNK = PNA_NS * PNA_OT * 2 * 1024;  // 30 KiB
+constexpr int PNA_FRAGS = PNA_F16 ? 1 : 2;                         // fragments per accumulator and K-step: hi and lo, or (single product) hi alone
+constexpr int PNA_CHUNK = PNA_NS * PNA_OT * PNA_FRAGS * 1024;  // 30 KiB (single product: 15 KiB)
 constexpr size_t PNA_SPLIT_LAYER_BYTES = (size_t)PNA_KS * PNA_CHUNK;
+constexpr size_t PNA_F16_LAYER_BYTES = (size_t)PNA_KS * PNA_NS * PNA_OT * 1024;  // the single-product stream of a layer: 10 x 15 360 B
 
 __device__ __forceinline__ void pna_issue_chunk(const uint8_t* __restrict__ gchunk, char* lds_buf, int wave, int lane) {
 #pragma unroll
@@ -215,13 +234,22 @@ __device__ __forceinline__ void pna_issue_chunk(const uint8_t* __restrict__ gchu
     }
 }
 
+// the B operands of a pair: split (hi + lo) or, single product, the pair rounded to f16 once, to nearest even (LO is left alone)
+typedef _Float16 pna_half2_t __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint32_t pna_pack_rne(float a, float b) { return __builtin_bit_cast(uint32_t, (pna_half2_t){(_Float16)a, (_Float16)b}); }
+#define PNA_OPER2(a, b, HI, LO)                                 \
+    do {                                                        \
+        if constexpr (PNA_F16) { (HI) = pna_pack_rne((a), (b)); } \
+        else { DS_SPLIT2(a, b, HI, LO); }                       \
+    } while (0)
+
 __device__ __forceinline__ void pna_split_step(const char* wb, int lane, const float4& x0, const float4& x1, float4_t (&y)[PNA_NS * PNA_OT],
                                                float& vmax) {
-    ds_uint4_t b_hi, b_lo;
-    DS_SPLIT2(x0.x, x0.y, b_hi.x, b_lo.x);
-    DS_SPLIT2(x0.z, x0.w, b_hi.y, b_lo.y);
-    DS_SPLIT2(x1.x, x1.y, b_hi.z, b_lo.z);
-    DS_SPLIT2(x1.z, x1.w, b_hi.w, b_lo.w);
+    ds_uint4_t b_hi, b_lo = {0, 0, 0, 0};
+    PNA_OPER2(x0.x, x0.y, b_hi.x, b_lo.x);
+    PNA_OPER2(x0.z, x0.w, b_hi.y, b_lo.y);
+    PNA_OPER2(x1.x, x1.y, b_hi.z, b_lo.z);
+    PNA_OPER2(x1.z, x1.w, b_hi.w, b_lo.w);
     vmax = __builtin_fmaxf(__builtin_fmaxf(vmax, __builtin_fabsf(x0.x)), __builtin_fabsf(x0.y));
     vmax = __builtin_fmaxf(__builtin_fmaxf(vmax, __builtin_fabsf(x0.z)), __builtin_fabsf(x0.w));
     vmax = __builtin_fmaxf(__builtin_fmaxf(vmax, __builtin_fabsf(x1.x)), __builtin_fabsf(x1.y));
@@ -229,6 +257,10 @@ __device__ __forceinline__ void pna_split_step(const char* wb, int lane, const f
     asm volatile("" : "+v"(vmax));  // computed here, not sunk to the kernel's end with all its inputs kept alive
 #pragma unroll
     for (int st = 0; st < PNA_NS * PNA_OT; st++) {
+        if constexpr (PNA_F16) {  // one fragment, one product
+            y[st] = DS_MFMA16(*reinterpret_cast<const ds_uint4_t*>(wb + st * 1024 + lane * 16), b_hi, y[st]);
+            continue;
+        }
         const ds_uint4_t a_hi = *reinterpret_cast<const ds_uint4_t*>(wb + (st * 2 + 0) * 1024 + lane * 16);
         const ds_uint4_t a_lo = *reinterpret_cast<const ds_uint4_t*>(wb + (st * 2 + 1) * 1024 + lane * 16);
         y[st] = DS_MFMA16(a_hi, b_hi, y[st]);
@@ -518,6 +550,19 @@ __device__ __forceinline__ void pna_issue_rows(const float* __restrict__ h, int 
 // its predecessor's accumulator).  Four waves per SIMD: the fragment reads of one wave hide under the MFMAs and gathers of the others.
 __device__ __forceinline__ void pna_stream_mfma(const char* wb, int lane, const ds_uint4_t& b_hi, const ds_uint4_t& b_lo,
                                                 float4_t (&y)[PNA_NS * PNA_OT]) {
+    if constexpr (PNA_F16) {  // single product: fifteen fragments, fifteen MFMAs, in groups of four accumulators (the last has three)
+        constexpr int NST = PNA_NS * PNA_OT, PNA_F16_GROUP = 4;  // (groups of 2, 3 and 5 compile to the same register figures)
+#pragma unroll
+        for (int G = 0; G < NST; G += PNA_F16_GROUP) {
+            const int n = G + PNA_F16_GROUP <= NST ? PNA_F16_GROUP : NST - G;
+            ds_uint4_t f[PNA_F16_GROUP];
+#pragma unroll
+            for (int i = 0; i < n; i++) f[i] = *reinterpret_cast<const ds_uint4_t*>(wb + (G + i) * 1024 + lane * 16);
+#pragma unroll
+            for (int i = 0; i < n; i++) y[G + i] = DS_MFMA16(f[i], b_hi, y[G + i]);
+        }
+        return;
+    }
 #pragma unroll
     for (int G = 0; G < 8; G++) {  // pairs of accumulators (the last group has one): four fragment registers sets live at a time
         constexpr int NST = PNA_NS * PNA_OT;
@@ -579,10 +624,10 @@ __device__ __forceinline__ void pna_slice_finish(const PnaSlice& a, int indeg, d
     // (the squares are operands of an explicit FMA: nothing is left for the compiler to contract them into)
     const float sd0 = __builtin_amdgcn_sqrtf(relu1(__builtin_fmaf(a.Q0, rdeg, -(m0 * m0)))), sd1 = __builtin_amdgcn_sqrtf(relu1(__builtin_fmaf(a.Q1, rdeg, -(m1 * m1))));
     // K-slots e = 0..7: (feature f0: mean, min, max, std), (feature f0 + 1: the same)
-    DS_SPLIT2(m0, a.mn0, b_hi.x, b_lo.x);
-    DS_SPLIT2(a.mx0, sd0, b_hi.y, b_lo.y);
-    DS_SPLIT2(m1, a.mn1, b_hi.z, b_lo.z);
-    DS_SPLIT2(a.mx1, sd1, b_hi.w, b_lo.w);
+    PNA_OPER2(m0, a.mn0, b_hi.x, b_lo.x);
+    PNA_OPER2(a.mx0, sd0, b_hi.y, b_lo.y);
+    PNA_OPER2(m1, a.mn1, b_hi.z, b_lo.z);
+    PNA_OPER2(a.mx1, sd1, b_hi.w, b_lo.w);
     asm("v_max3_f32 %0, |%1|, |%2|, %0" : "+v"(vmax) : "v"(m0), "v"(m1));
     asm("v_max3_f32 %0, |%1|, |%2|, %0" : "+v"(vmax) : "v"(sd0), "v"(sd1));
     asm("v_max3_f32 %0, |%1|, |%2|, %0" : "+v"(vmax) : "v"(a.mn0), "v"(a.mn1));
@@ -1044,7 +1089,10 @@ __global__ __launch_bounds__(PNA_FT_WAVES * 64, 4) void pna_resident_kernel(cons
 // pna_pack_split_layer: chunk ks = fragments of the 15 (scaler, output tile) pairs, hi then lo, 1 KiB each); K-slot e of lane
 // group gk in K-step ks is (feature 8 ks + 2 gk + (e >> 2), aggregator e & 3).  The scale is the one pna_pack_split_layer returns.
 #ifndef FG_RESIDENT_KERNEL_TU  // (host side: the model's own translation unit only)
-static void pna_pack_stream_layer(const float* cw, uint8_t* out) {
+// f16 (FLOWGNN_NUMERIC_F16): the stream of the single-product kernels -- r(W s) alone, rounded to nearest even, in chunks of 15 fragments
+static void pna_pack_stream_layer(const float* cw, uint8_t* out, bool f16 = false) {
+    const size_t chunk = f16 ? PNA_CHUNK / 2 : PNA_CHUNK;
+    const int frags = f16 ? 1 : 2;
     float m = 0.0f;
     for (size_t i = 0; i < (size_t)PNA_D * PNA_NS * PNA_NA * PNA_D; i++) m = std::fmax(m, std::fabs(cw[i]));
     const float sc = (m > 0.0f && std::isfinite(m)) ? std::ldexp(1.0f, -std::ilogb(m)) : 1.0f;
@@ -1053,20 +1101,22 @@ static void pna_pack_stream_layer(const float* cw, uint8_t* out) {
             for (int t = 0; t < PNA_OT; t++)
                 for (int lane = 0; lane < 64; lane++) {
                     const int i = lane & 15, gk = lane >> 4, o = 16 * t + i;
-                    uint8_t* f = out + (size_t)ks * PNA_CHUNK + (size_t)((s * PNA_OT + t) * 2) * 1024;
+                    uint8_t* f = out + (size_t)ks * chunk + (size_t)((s * PNA_OT + t) * frags) * 1024;
                     for (int e = 0; e < 8; e++) {
                         const int feat = 8 * ks + 2 * gk + (e >> 2), a = e & 3;
                         const float v = cw[(((size_t)o * PNA_NS + s) * PNA_NA + a) * PNA_D + feat] * sc;
                         const _Float16 hi = (_Float16)v;
                         const _Float16 lo = (_Float16)(v - (float)hi);
                         std::memcpy(f + lane * 16 + e * 2, &hi, 2);
-                        std::memcpy(f + 1024 + lane * 16 + e * 2, &lo, 2);
+                        if (!f16) std::memcpy(f + 1024 + lane * 16 + e * 2, &lo, 2);
                     }
                 }
 }
 
 // host: conv_w of one layer [80][3][4][80] -> PNA_SPLIT_LAYER_BYTES; returns 1 / scale
-static float pna_pack_split_layer(const float* cw, uint8_t* out) {
+static float pna_pack_split_layer(const float* cw, uint8_t* out, bool f16 = false) {
+    const size_t chunk = f16 ? PNA_CHUNK / 2 : PNA_CHUNK;
+    const int frags = f16 ? 1 : 2;
     float m = 0.0f;
     for (size_t i = 0; i < (size_t)PNA_D * PNA_NS * PNA_NA * PNA_D; i++) m = std::fmax(m, std::fabs(cw[i]));
     const float sc = (m > 0.0f && std::isfinite(m)) ? std::ldexp(1.0f, -std::ilogb(m)) : 1.0f;
@@ -1075,14 +1125,14 @@ static float pna_pack_split_layer(const float* cw, uint8_t* out) {
             for (int t = 0; t < PNA_OT; t++)
                 for (int lane = 0; lane < 64; lane++) {
                     const int i = lane & 15, gk = lane >> 4, o = 16 * t + i;
-                    uint8_t* f = out + (size_t)ks * PNA_CHUNK + (size_t)((s * PNA_OT + t) * 2) * 1024;
+                    uint8_t* f = out + (size_t)ks * chunk + (size_t)((s * PNA_OT + t) * frags) * 1024;
                     for (int e = 0; e < 8; e++) {
                         const int Q = 2 * ks + (e >> 2), a = Q / 5, q = Q % 5, k = 16 * q + 4 * gk + (e & 3);
                         const float v = cw[(((size_t)o * PNA_NS + s) * PNA_NA + a) * PNA_D + k] * sc;
                         const _Float16 hi = (_Float16)v;
                         const _Float16 lo = (_Float16)(v - (float)hi);
                         std::memcpy(f + lane * 16 + e * 2, &hi, 2);
-                        std::memcpy(f + 1024 + lane * 16 + e * 2, &lo, 2);
+                        if (!f16) std::memcpy(f + 1024 + lane * 16 + e * 2, &lo, 2);
                     }
                 }
     return 1.0f / sc;
@@ -1101,8 +1151,10 @@ public:
     // host tensors (PNA/src/dcl.h:98-110): node_emb[173][80], conv_w[4][80][3][4][80] (out, scaler, aggr, in),
     // conv_b[4][80], mlp1_w[40][80], mlp1_b[40], mlp2_w[20][40], mlp2_b[20], mlp3_w[1][20], mlp3_b[1], avg_deg[1]
     int set_numeric_mode(int mode) override {
-        if (mode != 0 && mode != 1) return 8;
+        // mode 2 (FLOWGNN_NUMERIC_F16): the engine lets it through for flowgnn_set_model_numeric_mode_dim at width 80 alone
+        if (mode != 0 && mode != 1 && mode != 2) return 8;
         qmode_ = mode == 1;
+        f16_ = mode == 2;
         return 0;
     }
 
@@ -1135,9 +1187,17 @@ public:
         std::vector<uint8_t> stream((size_t)PNA_L * PNA_SPLIT_LAYER_BYTES);
         for (int l = 0; l < PNA_L; l++)
             pna_pack_stream_layer(cw + (size_t)l * PNA_D * PNA_NS * PNA_NA * PNA_D, stream.data() + (size_t)l * PNA_SPLIT_LAYER_BYTES);
+        // ... and beside them the single-product streams (FLOWGNN_NUMERIC_F16): hi halves alone, half the bytes, in both K orders
+        std::vector<uint8_t> split16((size_t)PNA_L * PNA_F16_LAYER_BYTES), stream16((size_t)PNA_L * PNA_F16_LAYER_BYTES);
+        for (int l = 0; l < PNA_L; l++) {
+            pna_pack_split_layer(cw + (size_t)l * PNA_D * PNA_NS * PNA_NA * PNA_D, split16.data() + (size_t)l * PNA_F16_LAYER_BYTES, true);
+            pna_pack_stream_layer(cw + (size_t)l * PNA_D * PNA_NS * PNA_NA * PNA_D, stream16.data() + (size_t)l * PNA_F16_LAYER_BYTES, true);
+        }
         int rc;
         if ((rc = upload(&d_split_, split))) return rc;
         if ((rc = upload(&d_stream_, stream))) return rc;
+        if ((rc = upload(&d_split16_, split16))) return rc;
+        if ((rc = upload(&d_stream16_, stream16))) return rc;
         if ((rc = upload(&d_nemb_, v_nemb))) return rc;
         if ((rc = upload(&d_wf_, wf))) return rc;
         if ((rc = upload(&d_cb_, v_cb))) return rc;
@@ -1197,7 +1257,7 @@ public:
     PnaPlanInput plan_input() const {
         PnaPlanInput in;
         in.fused = fused_; in.split = split_; in.resident = resident_; in.tile_build = tile_build_; in.binpack = binpack_;
-        in.qmode = qmode_; in.keep_h = keep_h_; in.exact = exact_;
+        in.qmode = qmode_; in.keep_h = keep_h_; in.exact = exact_; in.f16 = f16_;
         return in;
     }
     PnaPlan plan(const DeviceBatch& db) const {
@@ -1228,7 +1288,7 @@ public:
         a.fidx = plan.one_pass ? reinterpret_cast<const uint32_t*>(fidx_.p) : nullptr;
         a.list = t.list; a.lrow = t.lrow;
         a.node_feature = db.b.node_feature; a.nemb = d_nemb_; a.desc = reinterpret_cast<const uint8_t*>(desc_.p);
-        a.wpk = d_stream_; a.bias = d_cb_;
+        a.wpk = plan.single_product ? d_stream16_ : d_stream_; a.bias = d_cb_;
         a.tile_row = t.row; a.tile_graph = t.graph; a.node_off = db.b.node_off;
         a.w1t = d_w1t_; a.b1 = d_b1_; a.w2t = d_w2t_; a.b2 = d_b2_; a.w3 = d_w3_; a.b3 = d_b3_;
         a.out = db.out; a.emb = db.emb; a.range_flag = db.range_flag; a.err = db.csr.err;
@@ -1236,7 +1296,14 @@ public:
         for (int l = 0; l < PNA_L; l++) a.oscale[l] = oscale_[l];
         a.n_tiles = t.n_tiles; a.node_emb = db.node_emb;
         const int grid = t.n_tiles < 256 ? t.n_tiles : 256;  // persistent: one 16-wave workgroup per CU
-        {
+        if (plan.single_product) {  // FLOWGNN_NUMERIC_F16: the single-product instances, in a slot of their own
+            ProfScope p(prof, "pna_resident_f16", s);
+            switch (plan.instance) {
+            case PnaResidentInstance::Rows: launch_pna_resident_f16_rows(a, grid, s); break;
+            case PnaResidentInstance::Emb: launch_pna_resident_f16_emb(a, grid, s); break;
+            case PnaResidentInstance::Default: launch_pna_resident_f16_default(a, grid, s); break;
+            }
+        } else {
             ProfScope p(prof, "pna_resident", s);
             switch (plan.instance) {
             case PnaResidentInstance::Rows: launch_pna_resident_rows(a, grid, s); break;  // the row-storing instance, embeddings or not
@@ -1267,13 +1334,18 @@ public:
             // (node embeddings: the last layer writes h_4 straight into the caller's buffer, and the readout pools it from there)
             float* const hn = (l == PNA_L - 1 && db.node_emb) ? db.node_emb : db.h[cur ^ 1];
             if (plan.fused_layers) {
-                ProfScope p(prof, "pna_layer_fused", s);
+                ProfScope p(prof, plan.single_product ? "pna_layer_fused_f16" : "pna_layer_fused", s);
                 const int grid = db.gtiles.n_tiles < 256 ? db.gtiles.n_tiles : 256;  // persistent: one 16-wave workgroup per CU (151 KB of LDS)
                 if (l == 0) {  // the tiles' CSR slices as the layer kernel stages them, once for the four layers
                     if (int rc = desc_.reserve(((size_t)db.gtiles.n_tiles * PNA_DESC_BYTES + 3) / 4)) return rc;
                     pna_tile_desc_kernel<<<db.gtiles.n_tiles, 256, 0, s>>>(db.csr.row_ptr, db.csr.src, db.csr.out_deg, db.gtiles.row_start,
                                                                           reinterpret_cast<uint8_t*>(desc_.p), db.gtiles.n_tiles);
                 }
+                if (plan.single_product)
+                    launch_pna_layer_fused_f16(db.h[cur], hn, reinterpret_cast<const uint8_t*>(desc_.p), db.csr.out_deg,
+                                               d_stream16_ + (size_t)l * PNA_F16_LAYER_BYTES, d_cb_ + (size_t)l * PNA_D, avg_deg_, oscale_[l],
+                                               db.gtiles.row_start, db.gtiles.n_tiles, db.range_flag, ablate_, prof_buf(grid, l), grid, s);
+                else
                 pna_layer_fused_kernel<<<grid, PNA_FT_WAVES * 64, 0, s>>>(db.h[cur], hn, reinterpret_cast<const uint8_t*>(desc_.p), db.csr.out_deg,
                                                             d_stream_ + (size_t)l * PNA_SPLIT_LAYER_BYTES, d_cb_ + (size_t)l * PNA_D, avg_deg_,
                                                             oscale_[l], db.gtiles.row_start, db.gtiles.n_tiles, db.range_flag,
@@ -1286,9 +1358,12 @@ public:
                 launch_aggregate(db, db.h[cur], s);
             }
             {
-                ProfScope p(prof, "pna_dense", s);
+                ProfScope p(prof, plan.single_product ? "pna_dense_f16" : "pna_dense", s);
                 const int waves = (int)ceil_div_ll(n, 16);
-                if (plan.split_dense) {
+                if (plan.single_product) {
+                    launch_pna_dense_split_f16(db.scratch, db.h[cur], hn, db.csr.out_deg, d_split16_ + (size_t)l * PNA_F16_LAYER_BYTES,
+                                               d_cb_ + (size_t)l * PNA_D, avg_deg_, oscale_[l], n, db.range_flag, s);
+                } else if (plan.split_dense) {
                     pna_dense_split_kernel<<<(int)ceil_div_ll(n, 128), 512, 0, s>>>(db.scratch, db.h[cur], hn, db.csr.out_deg,
                                                                                     d_split_ + (size_t)l * PNA_SPLIT_LAYER_BYTES,
                                                                                     d_cb_ + (size_t)l * PNA_D, avg_deg_, oscale_[l], n,
@@ -1377,6 +1452,8 @@ private:
             if (*p) { (void)hipFree(*p); *p = nullptr; }
         if (d_split_) { (void)hipFree(d_split_); d_split_ = nullptr; }
         if (d_stream_) { (void)hipFree(d_stream_); d_stream_ = nullptr; }
+        if (d_split16_) { (void)hipFree(d_split16_); d_split16_ = nullptr; }
+        if (d_stream16_) { (void)hipFree(d_stream16_); d_stream16_ = nullptr; }
         tiles_.release();
         desc_.release();
         fidx_.release();
@@ -1384,6 +1461,7 @@ private:
     }
     bool ready_ = false;
     bool qmode_ = false;  // flowgnn_set_numeric_mode(FLOWGNN_NUMERIC_Q6_10)
+    bool f16_ = false;    // flowgnn_set_model_numeric_mode_dim(e, 80, FLOWGNN_NUMERIC_F16): the single-product kernels (pna_f16.hip)
     QPack q_;
     GrowBufI tiles_;  // graph-aligned tile starts of the resident batch (tile_bounds_kernel)
     GrowBufI desc_;   // pna_tile_desc_kernel: 5.5 KiB per graph tile
@@ -1401,6 +1479,7 @@ private:
     bool exact_ = false;
     uint8_t* d_split_ = nullptr;
     uint8_t* d_stream_ = nullptr;  // feature-major weight stream of the fused layer kernel
+    uint8_t *d_split16_ = nullptr, *d_stream16_ = nullptr;  // the same two as hi halves alone (FLOWGNN_NUMERIC_F16)
     float oscale_[PNA_L] = {1.f, 1.f, 1.f, 1.f};
     float avg_deg_ = 1.0f;
     float *d_nemb_ = nullptr, *d_wf_ = nullptr, *d_cb_ = nullptr, *d_w1_ = nullptr, *d_b1_ = nullptr, *d_w2_ = nullptr,
@@ -1413,8 +1492,26 @@ Model* make_pna_model() { return new PnaModel(); }
 #ifdef FG_RESIDENT_KERNEL_TU
 }  // namespace
 #endif
+#if PNA_SINGLE_PRODUCT && !defined(FG_RESIDENT_EMB_TU) && !defined(FG_RESIDENT_ROWS_TU)
+// pna_f16.hip: the per-layer kernels' single-product instances
+void launch_pna_layer_fused_f16(const float* h, float* hout, const uint8_t* desc, const int* out_deg, const uint8_t* wpk, const float* bias,
+                                float avg_deg, float oscale, const int* tile_row, int n_tiles, int* range_flag, int ablate, unsigned long long* prof_out, int grid,
+                                hipStream_t s) {
+    pna_layer_fused_kernel<<<grid, PNA_FT_WAVES * 64, 0, s>>>(h, hout, desc, out_deg, wpk, bias, avg_deg, oscale, tile_row, n_tiles, range_flag, ablate, prof_out);
+}
+void launch_pna_dense_split_f16(const float* agg, const float* h, float* hout, const int* out_deg, const uint8_t* wpk, const float* bias,
+                                float avg_deg, float oscale, int n_tot, int* range_flag, hipStream_t s) {
+    pna_dense_split_kernel<<<(int)ceil_div_ll(n_tot, 128), 512, 0, s>>>(agg, h, hout, out_deg, wpk, bias, avg_deg, oscale, n_tot, range_flag);
+}
+#endif
 // this translation unit's instance of pna_resident_kernel, under the launcher's name that goes with it
-#if defined(FG_RESIDENT_EMB_TU)
+#if PNA_SINGLE_PRODUCT && defined(FG_RESIDENT_EMB_TU)
+void launch_pna_resident_f16_emb(
+#elif PNA_SINGLE_PRODUCT && defined(FG_RESIDENT_ROWS_TU)
+void launch_pna_resident_f16_rows(
+#elif PNA_SINGLE_PRODUCT
+void launch_pna_resident_f16_default(
+#elif defined(FG_RESIDENT_EMB_TU)
 void launch_pna_resident_emb(
 #elif defined(FG_RESIDENT_ROWS_TU)
 void launch_pna_resident_rows(

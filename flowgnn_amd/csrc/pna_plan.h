@@ -14,6 +14,7 @@ struct PnaPlanInput {
     bool binpack = true;     // pna_binpack
     // model state
     bool qmode = false;   // FLOWGNN_NUMERIC_Q6_10
+    bool f16 = false;     // FLOWGNN_NUMERIC_F16: the single-product instances of the split kernels (pna_f16.hip)
     bool keep_h = false;  // a per-node tap wants h_4 in HBM (flowgnn_get_h)
     bool exact = false;   // the engine asked for the fp32 pipe after the range flag tripped
     // batch
@@ -39,6 +40,9 @@ struct PnaPlan {
     bool fused_layers = false;  // one graph-tile kernel per layer; else aggregate + dense, two kernels ...
     bool split_dense = false;   // ... the dense one as split-f16 products, else on the fp32 pipe
     bool emb_readout = false;   // the readout also stores the pooled rows
+    // ---- either path: the split kernels it runs are their single-product instances (FLOWGNN_NUMERIC_F16).  The path itself is the one
+    // the same input takes with f16 off; the fp32 pipe (pna_mfma=32, the exact re-run) has no such instance and runs as it is
+    bool single_product = false;
 };
 
 // flowgnn_set_batch also bin-packs the graphs into tile lists: asked before there is a batch, so from the options and the model state alone
@@ -52,6 +56,7 @@ inline PnaPlan pna_plan(const PnaPlanInput& in) {
     }
     // tiles that are mostly empty (graphs of 65..128 nodes) waste MFMA columns: below 40 % full the two-kernel layer is used
     const bool tile_kernels = in.fused && in.split && !in.exact && in.tiles && in.fill >= 0.4;
+    p.single_product = in.f16 && in.split && !in.exact;  // (qmode has returned above: it wins over f16)
     // the graph-resident kernel: every layer's h stays in LDS, nothing per node is written (flowgnn_get_h repeats the pass per layer)
     if (in.resident && !in.keep_h && tile_kernels) {
         p.path = PnaPath::Resident;

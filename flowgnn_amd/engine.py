@@ -640,11 +640,16 @@ class Engine:
         emb_dim: the engine's width, which sends the call through flowgnn_set_numeric_mode_dim -- the way to "f16" on a GIN engine at
         set_emb_dim(300); without it the call is flowgnn_set_numeric_mode, which refuses every mode but "f32" at that width.
         A GCN engine takes the model form of the call, flowgnn_set_model_numeric_mode_dim, as set_jk_residual does: the way to "f16" for
-        gcn and gcn-virtual at width 300 (stages 0..3 with one f16 rounding of each operand of the layer's product)."""
+        gcn and gcn-virtual at width 300 (stages 0..3 with one f16 rounding of each operand of the layer's product).
+        A PNA engine takes the model form too: set_numeric_mode("f16", emb_dim=80) -- 80 is PNA's own width, FLOWGNN_EMB_DIM_PNA -- is
+        the one way to PNA's "f16" (each operand of the layer's 320 -> 3 x 80 contraction rounded to f16 once, one MFMA per product);
+        without emb_dim, or with 100, "f16" stays refused on PNA."""
         code = NUMERIC_MODES[mode]
         if emb_dim is None:
             self._check(self.lib.flowgnn_set_numeric_mode(self._h, code), "flowgnn_set_numeric_mode")
         elif self.model == "GCN":
+            self._check(self.lib.flowgnn_set_model_numeric_mode_dim(self._h, int(emb_dim), code), "flowgnn_set_model_numeric_mode_dim")
+        elif self.model == "PNA":  # (emb_dim=80: the one way to PNA's "f16")
             self._check(self.lib.flowgnn_set_model_numeric_mode_dim(self._h, int(emb_dim), code), "flowgnn_set_model_numeric_mode_dim")
         else:
             self._check(self.lib.flowgnn_set_numeric_mode_dim(self._h, int(emb_dim), code), "flowgnn_set_numeric_mode_dim")
@@ -861,11 +866,14 @@ class EngineGroup:
         return int(self.lib.flowgnn_emb_dim(self.lib.flowgnn_group_engine(self._h, 0)))
 
     def set_numeric_mode(self, mode: str = "f32", emb_dim: Optional[int] = None):
-        """Engine.set_numeric_mode on every member (flowgnn.h: flowgnn_group_set_numeric_mode; with emb_dim: ..._dim; GCN:
-        flowgnn_group_set_model_numeric_mode_dim)."""
+        """Engine.set_numeric_mode on every member (flowgnn.h: flowgnn_group_set_numeric_mode; with emb_dim: ..._dim; GCN, and PNA
+        with emb_dim=80: flowgnn_group_set_model_numeric_mode_dim)."""
         if emb_dim is None:
             self._check(self.lib.flowgnn_group_set_numeric_mode(self._h, NUMERIC_MODES[mode]), "flowgnn_group_set_numeric_mode")
         elif self.model == "GCN":
+            self._check(self.lib.flowgnn_group_set_model_numeric_mode_dim(self._h, int(emb_dim), NUMERIC_MODES[mode]),
+                        "flowgnn_group_set_model_numeric_mode_dim")
+        elif self.model == "PNA":
             self._check(self.lib.flowgnn_group_set_model_numeric_mode_dim(self._h, int(emb_dim), NUMERIC_MODES[mode]),
                         "flowgnn_group_set_model_numeric_mode_dim")
         else:

@@ -521,6 +521,9 @@ int flowgnn_num_tasks(const flowgnn_engine* e);
  */
 #define FLOWGNN_EMB_DIM_REFERENCE 100
 #define FLOWGNN_EMB_DIM_OGB       300
+/* PNA's own width, flowgnn_embedding_dim(FLOWGNN_MODEL_PNA): no choice of width, but the argument that flowgnn_set_model_numeric_mode_dim
+ * takes on a FLOWGNN_MODEL_PNA engine (below). */
+#define FLOWGNN_EMB_DIM_PNA       80
 int flowgnn_set_emb_dim(flowgnn_engine* e, int emb_dim);   /* 100 (default) or 300 */
 int flowgnn_emb_dim(const flowgnn_engine* e);              /* -1 for a null handle */
 
@@ -562,7 +565,8 @@ int flowgnn_set_model_emb_dim(flowgnn_engine* e, int emb_dim);   /* GIN, GCN: 10
 #define FLOWGNN_NUMERIC_F32 0
 #define FLOWGNN_NUMERIC_Q6_10 1
 /*
- * FLOWGNN_NUMERIC_F16 (GIN and GIN-VN only, NUM_TASK 1 or more; every other model returns FLOWGNN_ERR_UNSUPPORTED): the
+ * FLOWGNN_NUMERIC_F16 (through this call: GIN and GIN-VN only, NUM_TASK 1 or more; every other model returns FLOWGNN_ERR_UNSUPPORTED --
+ * GIN and GCN at width 300 and PNA have theirs behind flowgnn_set_numeric_mode_dim / flowgnn_set_model_numeric_mode_dim below): the
  * 16-bit operand speed of the matrix pipe.  Every operand of the node MLP's two linear layers -- the weights and the
  * activation each of them multiplies -- is rounded to f16 (round to nearest even), and each product is ONE f16 x f16 MFMA
  * with fp32 accumulation (the default mode forms every product from three).  The weights are rounded after the exact
@@ -625,6 +629,25 @@ int flowgnn_set_numeric_mode_dim(flowgnn_engine* e, int emb_dim, int mode);
  * the width, set the mode again); the same width again stays a no-op.  flowgnn_set_numeric_mode(e, FLOWGNN_NUMERIC_F32) always goes back.
  */
 int flowgnn_set_model_numeric_mode_dim(flowgnn_engine* e, int emb_dim, int mode);
+/*
+ * flowgnn_set_model_numeric_mode_dim on a FLOWGNN_MODEL_PNA engine: the call above also takes the model's true width, FLOWGNN_EMB_DIM_PNA (80, what
+ * flowgnn_embedding_dim(FLOWGNN_MODEL_PNA) returns), and there it accepts FLOWGNN_NUMERIC_F32, FLOWGNN_NUMERIC_Q6_10 (both as
+ * flowgnn_set_numeric_mode has them) and FLOWGNN_NUMERIC_F16: the one way to PNA's f16 mode.  Every other call keeps its answer on a
+ * PNA engine -- flowgnn_set_numeric_mode, flowgnn_set_numeric_mode_dim and this call at emb_dim 100 return FLOWGNN_ERR_UNSUPPORTED for
+ * F16, and the text names this form; flowgnn_set_numeric_mode_dim(e, 80, ..) is FLOWGNN_ERR_ARG, and its text names this form too.  On
+ * every other engine emb_dim 80 stays FLOWGNN_ERR_ARG.
+ * FLOWGNN_NUMERIC_F16 for PNA changes the layer's 320 -> 3 x 80 contraction and nothing else:
+ *   each of a node's 320 aggregates (mean, min, max, std of 80 features, as the walk forms them in fp32 -- the sentinels
+ *   31.9990234375 and -32 of a row without in-edges included: the first rounds to 32) is rounded to f16 ONCE, to nearest even, at the
+ *   point where the default mode splits it into two halves; the conv weights are rounded after the layer's power-of-two scale, r(W s);
+ *   each product is ONE f16 x f16 MFMA with fp32 accumulation, in the default mode's accumulator order.
+ * fp32 and unchanged: the encoder sum, the walk (sums, squares, min, max, 1 / indeg, the square root), the scalers t and scale and the
+ * update h + relu(b + Y_0 + t Y_1 + scale Y_2), the rows (on chip and in HBM), the mean pool and the 80 -> 40 -> 20 -> 1 head.  Range
+ * fallback as above: an aggregate beyond 6e4 raises the flag and the pass is repeated on the fp32 path -- that batch's results are the
+ * f32 mode's bytes.  pna_mfma=32 keeps the fp32 pipe, and with it f32-mode results.  The mode is the engine's: it survives
+ * flowgnn_set_weights and new batches, and runs with embeddings, node embeddings, flowgnn_get_h, device batches, groups and option
+ * hipgraph; sum and max pooling stay refused for PNA.  DGN is the one model left without an f16 mode.
+ */
 
 /*
  * Pooling of the readout (GIN, GIN-VN, GCN, GAT): how a graph's last node rows r[v] (what
