@@ -75,6 +75,7 @@ def _declare(lib):
     lib.flowgnn_set_numeric_mode.argtypes = [eng, C.c_int]
     lib.flowgnn_set_numeric_mode_dim.argtypes = [eng, C.c_int, C.c_int]
     lib.flowgnn_set_model_numeric_mode_dim.argtypes = [eng, C.c_int, C.c_int]
+    lib.flowgnn_set_model_numeric_mode.argtypes = [eng, C.c_int, C.c_int]
     lib.flowgnn_set_pooling.argtypes = [eng, C.c_int]
     lib.flowgnn_pooling.argtypes = [eng]
     lib.flowgnn_set_gin_eps.argtypes = [eng, p_float]
@@ -133,6 +134,7 @@ def _declare(lib):
     lib.flowgnn_group_set_numeric_mode.argtypes = [grp, C.c_int]
     lib.flowgnn_group_set_numeric_mode_dim.argtypes = [grp, C.c_int, C.c_int]
     lib.flowgnn_group_set_model_numeric_mode_dim.argtypes = [grp, C.c_int, C.c_int]
+    lib.flowgnn_group_set_model_numeric_mode.argtypes = [grp, C.c_int, C.c_int]
     lib.flowgnn_group_set_pooling.argtypes = [grp, C.c_int]
     lib.flowgnn_entry_set_pooling.argtypes = [C.c_int, C.c_int]
     lib.flowgnn_group_set_gin_eps.argtypes = [grp, p_float]
@@ -190,6 +192,7 @@ def _declare(lib):
                  "flowgnn_set_ogb_virtual_node_dim", "flowgnn_group_set_ogb_virtual_node_dim",
                  "flowgnn_set_numeric_mode_dim", "flowgnn_group_set_numeric_mode_dim",
                  "flowgnn_set_model_numeric_mode_dim", "flowgnn_group_set_model_numeric_mode_dim",
+                 "flowgnn_set_model_numeric_mode", "flowgnn_group_set_model_numeric_mode",
                  "flowgnn_set_gcn_virtual_node", "flowgnn_gcn_virtual_node", "flowgnn_group_set_gcn_virtual_node",
                  "flowgnn_set_gcn_virtual_node_dim", "flowgnn_group_set_gcn_virtual_node_dim",
                  "flowgnn_set_attention_pooling", "flowgnn_attention_pooling", "flowgnn_group_set_attention_pooling",

@@ -47,10 +47,39 @@ struct DgnResidentLaunch {
 void launch_dgn_resident_default(const DgnResidentLaunch& a, int grid, hipStream_t s);  // dgn.hip
 void launch_dgn_resident_emb(const DgnResidentLaunch& a, int grid, hipStream_t s);      // dgn_emb.hip
 void launch_dgn_resident_rows(const DgnResidentLaunch& a, int grid, hipStream_t s);     // dgn_rows.hip
-#if defined(FG_RESIDENT_EMB_TU) || defined(FG_RESIDENT_ROWS_TU)
+// Single-product instances (FLOWGNN_NUMERIC_F16): dgn_f16.hip, dgn_emb_f16.hip and dgn_rows_f16.hip compile this
+// file once more with DGN_SINGLE_PRODUCT = 1 -- dgn_resident_kernel and dgn_layer_mfma_kernel under names of their own, every operand of
+// the matrix-pipe products (transposed source rows, directional weights, a1 / a2, the scaled update weights) ONE f16 value, rounded to
+// nearest even, and every product ONE f16 MFMA (fp32 accumulate).  wpk is then the hi-halves-only stream (7 KiB per K-step, bias block
+// behind it).  Host side and the other kernels exist in this file's own translation unit only.
+#ifndef DGN_SINGLE_PRODUCT
+#define DGN_SINGLE_PRODUCT 0
+#endif
+void launch_dgn_resident_f16_default(const DgnResidentLaunch& a, int grid, hipStream_t s);  // dgn_f16.hip
+void launch_dgn_resident_f16_emb(const DgnResidentLaunch& a, int grid, hipStream_t s);      // dgn_emb_f16.hip
+void launch_dgn_resident_f16_rows(const DgnResidentLaunch& a, int grid, hipStream_t s);     // dgn_rows_f16.hip
+// the per-layer matrix-pipe kernel's single-product instances (dgn_f16.hip): dgn_layer_mfma_kernel<info, pool>'s arguments; (info, pool) is
+// one of (1, false), (2, false), (2, true)
+struct DgnLayerMfmaLaunch {
+    const float* h; float* hout;
+    const int *row_ptr, *src, *out_deg;
+    const float* eig4;
+    const uint8_t* wpk;
+    const int* tile_row;
+    int n_tiles;
+    int* range_flag;
+    int ablate;
+    uint32_t* rowinfo;
+    const int2* ginfo;
+    float* pool_part;
+    int* pool_cnt;
+};
+void launch_dgn_layer_mfma_f16(const DgnLayerMfmaLaunch& a, int info, bool pool, int grid, hipStream_t s);
+#if defined(FG_RESIDENT_EMB_TU) || defined(FG_RESIDENT_ROWS_TU) || DGN_SINGLE_PRODUCT
 #define FG_RESIDENT_KERNEL_TU 1
 namespace {
 #endif
+constexpr bool DGN_F16 = DGN_SINGLE_PRODUCT != 0;
 #ifdef FG_RESIDENT_EMB_TU
 constexpr bool RESIDENT_EMB = true;
 #else
@@ -185,6 +214,22 @@ constexpr int DGN_FT_KS = 7;
 constexpr int DGN_FT_WBYTES = DGN_FT_KS * DGN_OT * 2 * 1024;  // 100 352: [k][t][hi, lo] fragments
 constexpr int DGN_FT_BIAS = DGN_FT_WBYTES;                     // then bias[112] (pre-scaled) and 1 / scale
 constexpr size_t DGN_FT_LAYER_BYTES = DGN_FT_WBYTES + 512;
+// what the matrix-pipe kernels (dgn_layer_mfma_kernel, dgn_resident_kernel) read: the same, or (single product) the hi fragments alone,
+// [k][t] x 1 KiB, with the same bias block and 1 / scale behind them
+constexpr int DGN_FRAGS = DGN_F16 ? 1 : 2;  // fragments per output tile and K-step: hi and lo, or hi alone
+constexpr int DGN_MP_WBYTES = DGN_FT_KS * DGN_OT * DGN_FRAGS * 1024;
+constexpr int DGN_MP_BIAS = DGN_MP_WBYTES;
+constexpr size_t DGN_MP_LAYER_BYTES = DGN_MP_WBYTES + 512;
+constexpr size_t DGN_F16_LAYER_BYTES = (size_t)DGN_FT_KS * DGN_OT * 1024 + 512;  // the single-product stream of a layer: 50 176 + 512 B
+
+// an operand pair of a matrix-pipe product: split (hi + lo) or, single product, the pair rounded to f16 once, to nearest even (LO is left alone)
+typedef _Float16 dgn_half2_t __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint32_t dgn_pack_rne(float a, float b) { return __builtin_bit_cast(uint32_t, (dgn_half2_t){(_Float16)a, (_Float16)b}); }
+#define DGN_OPER2(a, b, HI, LO)                                   \
+    do {                                                          \
+        if constexpr (DGN_F16) { (HI) = dgn_pack_rne((a), (b)); } \
+        else { DS_SPLIT2(a, b, HI, LO); }                         \
+    } while (0)
 
 __global__ __launch_bounds__(512, 2) void dgn_layer_fused_kernel(const float* __restrict__ h, float* __restrict__ hout,
                                                                   const int* __restrict__ row_ptr, const int* __restrict__ src,
@@ -443,7 +488,7 @@ __global__ __launch_bounds__(512, 2) void dgn_layer_mfma_kernel(const float* __r
                                                                  int* __restrict__ pool_cnt) {
     const int ablate = FG_ABLATE(ablate_arg);  // development aid (dgn_ablate, -DFLOWGNN_DEV builds): 1 no aggregation MFMAs, 2 no dense
     (void)ablate_arg;                          // MFMAs, 4 no transposing stores of the next tile, 8 no in-edge pass, 16 no h[v] loads
-    constexpr int OFF_W = 2 * DGN_HT_BYTES, OFF_SRC = OFF_W + (int)DGN_FT_LAYER_BYTES, OFF_RP = OFF_SRC + DGN_FT_EDGES,
+    constexpr int OFF_W = (DGN_F16 ? 1 : 2) * DGN_HT_BYTES, OFF_SRC = OFF_W + (int)DGN_MP_LAYER_BYTES, OFF_RP = OFF_SRC + DGN_FT_EDGES,  // (single product: one s_ht half)
                   OFF_EIG = OFF_RP + 2 * (DGN_FT_ROWS + 8), LDS_TOTAL = OFF_EIG + 4 * DGN_FT_ROWS;
     static_assert(OFF_W % 16 == 0 && OFF_SRC % 16 == 0 && OFF_RP % 4 == 0 && OFF_EIG % 16 == 0, "alignment");
     __shared__ __attribute__((aligned(16))) char s_all[LDS_TOTAL];
@@ -458,15 +503,24 @@ __global__ __launch_bounds__(512, 2) void dgn_layer_mfma_kernel(const float* __r
     const int j = lane & 15, g = lane >> 4;
     int tile = blockIdx.x;
     if (tile >= n_tiles) return;
-    for (int i = tid; i < (int)(DGN_FT_LAYER_BYTES / 16); i += 512)
+    for (int i = tid; i < (int)(DGN_MP_LAYER_BYTES / 16); i += 512)
         reinterpret_cast<uint4*>(s_w)[i] = reinterpret_cast<const uint4*>(wpk)[i];
     // loader geometry: wave w owns rows 16 w .. 16 w + 15; its p-th load covers chunks 4 p .. 4 p + 3 of them -- lane = (row lane & 15,
     // chunk lane >> 4): a wave instruction reads sixteen 64-byte row segments (lanes along rows alone would touch 64 different lines
     // per instruction: measured +0.23 ms per layer), and the 2-byte stores of the transposition fall into 32 different banks
     const int lr = 16 * wave + (lane & 15), cg = lane >> 4;
+    float hmax = 0.0f;  // single product: the largest |h| rounded into s_ht (joins vmax at the end: beyond 6e4 the range flag trips)
     auto put_row_piece = [&](int c, const float4& v, bool real) {
         if (c >= DGN_C) return;
         const float4 x = real ? v : make_float4(0.f, 0.f, 0.f, 0.f);  // rows beyond the tile's last: zeros (never NaN under a zero mask)
+        if constexpr (DGN_F16) {  // one rounding to nearest even per feature, no lo half
+            const uint32_t r01 = dgn_pack_rne(x.x, x.y), r23 = dgn_pack_rne(x.z, x.w);
+            hmax = __builtin_fmaxf(__builtin_fmaxf(hmax, __builtin_fabsf(x.x)), __builtin_fabsf(x.y));
+            hmax = __builtin_fmaxf(__builtin_fmaxf(hmax, __builtin_fabsf(x.z)), __builtin_fabsf(x.w));
+            uint16_t* pr = s_ht_hi + (4 * c) * DGN_HT_STRIDE + lr;
+            pr[0] = (uint16_t)r01; pr[DGN_HT_STRIDE] = (uint16_t)(r01 >> 16); pr[2 * DGN_HT_STRIDE] = (uint16_t)r23; pr[3 * DGN_HT_STRIDE] = (uint16_t)(r23 >> 16);
+            return;
+        }
         uint32_t h01, l01, h23, l23;
         DS_SPLIT2(x.x, x.y, h01, l01);
         DS_SPLIT2(x.z, x.w, h23, l23);
@@ -495,7 +549,7 @@ __global__ __launch_bounds__(512, 2) void dgn_layer_mfma_kernel(const float* __r
     }
     if (tid < DGN_FT_ROWS) put_eig(tid, eig4[(size_t)(t0 + (tid < rows ? tid : 0)) * 4 + 1], tid < rows);
     __syncthreads();
-    const float oscale = *reinterpret_cast<const float*>(s_w + DGN_FT_BIAS + 112 * 4);
+    const float oscale = *reinterpret_cast<const float*>(s_w + DGN_MP_BIAS + 112 * 4);
     float vmax = 0.0f;
     uint32_t cur_bits = 0;
     uint4 cur_info = make_uint4(0u, 0u, 0u, 0u);
@@ -627,11 +681,11 @@ __global__ __launch_bounds__(512, 2) void dgn_layer_mfma_kernel(const float* __r
             b_el[sb] = b_eh[sb];
             if (blk[sb]) {  // (block diagonal: a 16-row group sees two or three of the four blocks)
                 const float4 ea = *reinterpret_cast<const float4*>(s_eig + 32 * sb + 8 * g), eb = *reinterpret_cast<const float4*>(s_eig + 32 * sb + 8 * g + 4);
-                ds_uint4_t eh, el;
-                DS_SPLIT2((ea.x - eig_v) * wscale, (ea.y - eig_v) * wscale, eh.x, el.x);
-                DS_SPLIT2((ea.z - eig_v) * wscale, (ea.w - eig_v) * wscale, eh.y, el.y);
-                DS_SPLIT2((eb.x - eig_v) * wscale, (eb.y - eig_v) * wscale, eh.z, el.z);
-                DS_SPLIT2((eb.z - eig_v) * wscale, (eb.w - eig_v) * wscale, eh.w, el.w);
+                ds_uint4_t eh, el = {0u, 0u, 0u, 0u};  // (single product: the one rounded weight, d_uv = rne_f16((eig[u] - eig[v]) wscale); no lo half)
+                DGN_OPER2((ea.x - eig_v) * wscale, (ea.y - eig_v) * wscale, eh.x, el.x);
+                DGN_OPER2((ea.z - eig_v) * wscale, (ea.w - eig_v) * wscale, eh.y, el.y);
+                DGN_OPER2((eb.x - eig_v) * wscale, (eb.y - eig_v) * wscale, eh.z, el.z);
+                DGN_OPER2((eb.z - eig_v) * wscale, (eb.w - eig_v) * wscale, eh.w, el.w);
                 b_eh[sb] = m & eh;
                 b_el[sb] = m & el;
             }
@@ -639,7 +693,7 @@ __global__ __launch_bounds__(512, 2) void dgn_layer_mfma_kernel(const float* __r
         float4_t acc[DGN_OT];
 #pragma unroll
         for (int t = 0; t < DGN_OT; t++) {
-            const float4 bv = *reinterpret_cast<const float4*>(s_w + DGN_FT_BIAS + (16 * t + 4 * g) * 4);
+            const float4 bv = *reinterpret_cast<const float4*>(s_w + DGN_MP_BIAS + (16 * t + 4 * g) * 4);
             acc[t] = (float4_t){bv.x, bv.y, bv.z, bv.w};
         }
         const float* hrow = h + (size_t)node * DGN_D;  // the row itself: from HBM / L2 (the tile's fp32 rows are not kept in LDS)
@@ -660,6 +714,12 @@ __global__ __launch_bounds__(512, 2) void dgn_layer_mfma_kernel(const float* __r
 #pragma unroll
             for (int sb = 0; sb < 4; sb++) {
                 if (blk[sb] && !(ablate & 1)) {
+                    if constexpr (DGN_F16) {  // one product per aggregate and block
+                        const ds_uint4_t fx = *reinterpret_cast<const ds_uint4_t*>(ah + 32 * sb);
+                        m1 = DS_MFMA16(fx, b_one[sb], m1);
+                        pp = DS_MFMA16(fx, b_eh[sb], pp);
+                        continue;
+                    }
                     const ds_uint4_t fh = *reinterpret_cast<const ds_uint4_t*>(ah + 32 * sb);
                     const ds_uint4_t fl = *reinterpret_cast<const ds_uint4_t*>(al + 32 * sb);
                     m1 = DS_MFMA16(fh, b_one[sb], m1);
@@ -677,12 +737,13 @@ __global__ __launch_bounds__(512, 2) void dgn_layer_mfma_kernel(const float* __r
                     if (e < cnt) {
                         const int u = STAGE_CSR ? (int)s_src[e_base + e] : ((src[gb + e] - t0) & 127);
                         if (u == prev && real) {
-                            const float eu = (s_eig[u] - eig_v) * wscale;  // the copy's (scaled) weight
+                            float eu = (s_eig[u] - eig_v) * wscale;  // the copy's (scaled) weight
+                            if constexpr (DGN_F16) eu = (float)(_Float16)eu;  // ... as the first copy's: rounded once
 #pragma unroll
                             for (int c = 0; c < 4; c++) {
                                 const int f = (k < 6 ? 16 * k : 96) + 4 * g + c;
-                                const float x = (float)__builtin_bit_cast(_Float16, s_ht_hi[f * DGN_HT_STRIDE + u]) +
-                                                (float)__builtin_bit_cast(_Float16, s_ht_lo[f * DGN_HT_STRIDE + u]);
+                                float x = (float)__builtin_bit_cast(_Float16, s_ht_hi[f * DGN_HT_STRIDE + u]);
+                                if constexpr (!DGN_F16) x += (float)__builtin_bit_cast(_Float16, s_ht_lo[f * DGN_HT_STRIDE + u]);
                                 m1[c] += x;
                                 pp[c] = __builtin_fmaf(x, eu, pp[c]);
                             }
@@ -698,17 +759,27 @@ __global__ __launch_bounds__(512, 2) void dgn_layer_mfma_kernel(const float* __r
             a2.z = fabsf(__builtin_fmaf(-wsum_s, hv.z, pp.z) * inv_abs_s);
             a2.w = fabsf(__builtin_fmaf(-wsum_s, hv.w, pp.w) * inv_abs_s);
             if (!real || !valid) { a1 = make_float4(0.f, 0.f, 0.f, 0.f); a2 = a1; }
-            ds_uint4_t b_hi, b_lo;
-            DS_SPLIT2(a1.x, a1.y, b_hi.x, b_lo.x);
-            DS_SPLIT2(a1.z, a1.w, b_hi.y, b_lo.y);
-            DS_SPLIT2(a2.x, a2.y, b_hi.z, b_lo.z);
-            DS_SPLIT2(a2.z, a2.w, b_hi.w, b_lo.w);
+            ds_uint4_t b_hi, b_lo = {0u, 0u, 0u, 0u};
+            DGN_OPER2(a1.x, a1.y, b_hi.x, b_lo.x);
+            DGN_OPER2(a1.z, a1.w, b_hi.y, b_lo.y);
+            DGN_OPER2(a2.x, a2.y, b_hi.z, b_lo.z);
+            DGN_OPER2(a2.z, a2.w, b_hi.w, b_lo.w);
             asm("v_max3_f32 %0, |%1|, |%2|, %0" : "+v"(vmax) : "v"(a1.x), "v"(a1.y));
             asm("v_max3_f32 %0, |%1|, |%2|, %0" : "+v"(vmax) : "v"(a1.z), "v"(a1.w));
             asm("v_max3_f32 %0, |%1|, |%2|, %0" : "+v"(vmax) : "v"(a2.x), "v"(a2.y));
             asm("v_max3_f32 %0, |%1|, |%2|, %0" : "+v"(vmax) : "v"(a2.z), "v"(a2.w));
             asm volatile("" : "+v"(vmax));
-            const char* wb = s_w + (size_t)k * (DGN_OT * 2 * 1024);
+            const char* wb = s_w + (size_t)k * (DGN_OT * DGN_FRAGS * 1024);
+            if constexpr (DGN_F16) {  // single product: seven fragments, seven MFMAs, one per accumulator
+                if (!(ablate & 2)) {
+                    ds_uint4_t f7[DGN_OT];
+#pragma unroll
+                    for (int t = 0; t < DGN_OT; t++) f7[t] = *reinterpret_cast<const ds_uint4_t*>(wb + t * 1024 + lane * 16);
+#pragma unroll
+                    for (int t = 0; t < DGN_OT; t++) acc[t] = DS_MFMA16(f7[t], b_hi, acc[t]);
+                } else { acc[0].x += b_hi.x; }
+                continue;
+            }
             if (!(ablate & 2)) {
             ds_uint4_t ff[2][4];  // the fragments of the NEXT pair of output tiles are requested before this pair's MFMAs issue
 #pragma unroll
@@ -822,6 +893,7 @@ __global__ __launch_bounds__(512, 2) void dgn_layer_mfma_kernel(const float* __r
         tile = ntile; t0 = nt0; rows = nrows; e0 = ne0; ne = nne;
         cur_bits = nx_bits; cur_info = nx_info;
     }
+    if constexpr (DGN_F16) vmax = __builtin_fmaxf(vmax, hmax);
     if (__any(!(vmax < 6.0e4f))) {
         if (lane == 0) atomicOr(range_flag, 1);
     }
@@ -1094,11 +1166,13 @@ __global__ __launch_bounds__(256) void dgn_pool_part_mlp3_kernel(const float* __
 // order of a row's in-edge sum depends on where its graph sits in the tile: toleranced under batch splits, tests/test_dgn_gpu.py.)
 // Rows with duplicate in-edges (the mask has no multiplicities) add the extra copies from the caller's edge list: slow and rare.
 constexpr int DGN_REC_TILE_BYTES = DGN_FT_ROWS * DGN_REC_DW * 4;  // 6 144: six DMA pieces
-constexpr int DGN_CHUNK = DGN_OT * 2 * 1024;                      // 14 336: the fragments of one K-step
+constexpr int DGN_CHUNK = DGN_OT * DGN_FRAGS * 1024;              // 14 336: the fragments of one K-step (single product: 7 168)
 // the readout's head in one block (25 DMA pieces into the two weight slots, which are idle by then)
 constexpr int DGN_HEAD_W2 = 100 * 50, DGN_HEAD_B1 = DGN_HEAD_W2 + 50 * 25, DGN_HEAD_B2 = DGN_HEAD_B1 + 50, DGN_HEAD_W3 = DGN_HEAD_B2 + 25,
               DGN_HEAD_B3 = DGN_HEAD_W3 + 25, DGN_HEAD_BYTES = 25 * 1024;
-static_assert((DGN_HEAD_B3 + 1) * 4 <= DGN_HEAD_BYTES && DGN_HEAD_BYTES <= 2 * DGN_CHUNK, "the head fits the two slots");
+// the two weight slots; single product: two 7 KiB chunks are smaller than the head block that follows them there, so the region keeps the head's size
+constexpr int DGN_WSLOT_BYTES = 2 * DGN_CHUNK < DGN_HEAD_BYTES ? DGN_HEAD_BYTES : 2 * DGN_CHUNK;
+static_assert((DGN_HEAD_B3 + 1) * 4 <= DGN_HEAD_BYTES && DGN_HEAD_BYTES <= DGN_WSLOT_BYTES, "the head fits the two slots");
 
 #ifdef FLOWGNN_DEV
 #include "dev/dgn_timing_variants.h"  // development: timing variants (wrong results on purpose), selected by -DDGNR_TIMING=<bits>
@@ -1109,7 +1183,7 @@ static_assert((DGN_HEAD_B3 + 1) * 4 <= DGN_HEAD_BYTES && DGN_HEAD_BYTES <= 2 * D
 struct DgnResidentArgs : DgnResidentLaunch {};  // the kernel's parameter: the same, in the namespace of this translation unit's kernel
 
 __global__ __launch_bounds__(512, 2) void dgn_resident_kernel(const DgnResidentArgs a) {
-    constexpr int OFF_W = 2 * DGN_HT_BYTES, OFF_TAB = OFF_W + 2 * DGN_CHUNK, OFF_REC = OFF_TAB + ND_FEATURE_TOTAL * DGN_D * 4,
+    constexpr int OFF_W = 2 * DGN_HT_BYTES, OFF_TAB = OFF_W + DGN_WSLOT_BYTES, OFF_REC = OFF_TAB + ND_FEATURE_TOTAL * DGN_D * 4,
                   OFF_BIAS = OFF_REC + DGN_REC_TILE_BYTES, OFF_EIG = OFF_BIAS + DGN_L * 512, LDS_TOTAL = OFF_EIG + 4 * DGN_FT_ROWS;
     static_assert(OFF_W % 16 == 0 && OFF_TAB % 16 == 0 && OFF_REC % 16 == 0 && OFF_BIAS % 16 == 0 && OFF_EIG % 16 == 0, "alignment");
     static_assert(LDS_TOTAL <= 160 * 1024, "LDS of one CU");
@@ -1128,8 +1202,12 @@ __global__ __launch_bounds__(512, 2) void dgn_resident_kernel(const DgnResidentA
     int tile = blockIdx.x;
     if (tile >= a.n_tiles) return;
     auto issue_chunk = [&](int l, int k) {  // K-step k of layer l -> slot (l + k) & 1: fourteen 1 KiB pieces over eight waves
-        const uint8_t* gsrc = a.wpk + (size_t)l * DGN_FT_LAYER_BYTES + (size_t)k * DGN_CHUNK;
+        const uint8_t* gsrc = a.wpk + (size_t)l * DGN_MP_LAYER_BYTES + (size_t)k * DGN_CHUNK;
         const uint32_t lb = lds_addr_of(s_w) + (uint32_t)(((l + k) & 1) * DGN_CHUNK);
+        if constexpr (DGN_F16) {  // seven 1 KiB pieces: one each on waves 0..6
+            if (wave < DGN_OT) lds_dma16(gsrc + wave * 1024, (uint32_t)lane * 16u, lb + wave * 1024);
+            return;
+        }
         lds_dma16(gsrc + wave * 1024, (uint32_t)lane * 16u, lb + wave * 1024);
         if (wave < 6) lds_dma16(gsrc + (wave + 8) * 1024, (uint32_t)lane * 16u, lb + (wave + 8) * 1024);
     };
@@ -1152,10 +1230,19 @@ __global__ __launch_bounds__(512, 2) void dgn_resident_kernel(const DgnResidentA
     // once per workgroup: the encoder table and the four layers' bias vectors (pre-scaled, 112 floats + 1 / scale each)
     for (int i = tid; i < ND_FEATURE_TOTAL * DGN_C; i += 512)
         reinterpret_cast<float4*>(s_all + OFF_TAB)[i] = reinterpret_cast<const float4*>(a.table)[i];
-    if (tid < DGN_L * 128) s_bias[tid] = *reinterpret_cast<const float*>(a.wpk + (size_t)(tid >> 7) * DGN_FT_LAYER_BYTES + DGN_FT_BIAS + (tid & 127) * 4);
+    if (tid < DGN_L * 128) s_bias[tid] = *reinterpret_cast<const float*>(a.wpk + (size_t)(tid >> 7) * DGN_MP_LAYER_BYTES + DGN_MP_BIAS + (tid & 127) * 4);
     const int lr = 16 * wave + j;  // this lane's row of the tile (the four lanes g of a row share it)
+    float hmax = 0.0f;  // single product: the largest |h| rounded into s_ht (joins vmax at the end: beyond 6e4 the range flag trips)
     auto put_row_piece = [&](int c, const float4_t& x) {  // features 4 c .. 4 c + 3 of row lr -> the transposed split rows
         if (c >= DGN_C) return;
+        if constexpr (DGN_F16) {  // one rounding to nearest even per feature, no lo half
+            const uint32_t r01 = dgn_pack_rne(x.x, x.y), r23 = dgn_pack_rne(x.z, x.w);
+            hmax = __builtin_fmaxf(__builtin_fmaxf(hmax, __builtin_fabsf(x.x)), __builtin_fabsf(x.y));
+            hmax = __builtin_fmaxf(__builtin_fmaxf(hmax, __builtin_fabsf(x.z)), __builtin_fabsf(x.w));
+            uint16_t* pr = s_ht_hi + (4 * c) * DGN_HT_STRIDE + lr;
+            pr[0] = (uint16_t)r01; pr[DGN_HT_STRIDE] = (uint16_t)(r01 >> 16); pr[2 * DGN_HT_STRIDE] = (uint16_t)r23; pr[3 * DGN_HT_STRIDE] = (uint16_t)(r23 >> 16);
+            return;
+        }
         uint32_t h01, l01, h23, l23;
         DS_SPLIT2(x.x, x.y, h01, l01);
         DS_SPLIT2(x.z, x.w, h23, l23);
@@ -1234,11 +1321,11 @@ __global__ __launch_bounds__(512, 2) void dgn_resident_kernel(const DgnResidentA
                 float es[8];  // eig1 of sources 32 sb + 8 g .. + 7 (records of rows beyond the tile's last are never under a set bit)
 #pragma unroll
                 for (int i = 0; i < 8; i++) es[i] = __builtin_bit_cast(float, s_rec[(32 * sb + 8 * g + i) * DGN_REC_DW + 8]);
-                ds_uint4_t eh, el;
-                DS_SPLIT2((es[0] - eig_v) * wscale, (es[1] - eig_v) * wscale, eh.x, el.x);
-                DS_SPLIT2((es[2] - eig_v) * wscale, (es[3] - eig_v) * wscale, eh.y, el.y);
-                DS_SPLIT2((es[4] - eig_v) * wscale, (es[5] - eig_v) * wscale, eh.z, el.z);
-                DS_SPLIT2((es[6] - eig_v) * wscale, (es[7] - eig_v) * wscale, eh.w, el.w);
+                ds_uint4_t eh, el = {0u, 0u, 0u, 0u};  // (single product: the one rounded weight, d_uv = rne_f16((eig[u] - eig[v]) wscale); no lo half)
+                DGN_OPER2((es[0] - eig_v) * wscale, (es[1] - eig_v) * wscale, eh.x, el.x);
+                DGN_OPER2((es[2] - eig_v) * wscale, (es[3] - eig_v) * wscale, eh.y, el.y);
+                DGN_OPER2((es[4] - eig_v) * wscale, (es[5] - eig_v) * wscale, eh.z, el.z);
+                DGN_OPER2((es[6] - eig_v) * wscale, (es[7] - eig_v) * wscale, eh.w, el.w);
                 b_eh[sb] = m & eh;
                 b_el[sb] = m & el;
             }
@@ -1310,6 +1397,12 @@ __global__ __launch_bounds__(512, 2) void dgn_resident_kernel(const DgnResidentA
 #pragma unroll
                 for (int sb = 0; sb < 4; sb++) {
                     if (blk[sb] && !DGNR_SKIP(4)) {
+                        if constexpr (DGN_F16) {  // one product per aggregate and block
+                            const ds_uint4_t fx = *reinterpret_cast<const ds_uint4_t*>(ah + 32 * sb);
+                            m1 = DS_MFMA16(fx, b_one[sb], m1);
+                            pp = DS_MFMA16(fx, b_eh[sb], pp);
+                            continue;
+                        }
                         const ds_uint4_t fh = *reinterpret_cast<const ds_uint4_t*>(ah + 32 * sb);
                         const ds_uint4_t fl = *reinterpret_cast<const ds_uint4_t*>(al + 32 * sb);
                         m1 = DS_MFMA16(fh, b_one[sb], m1);
@@ -1338,12 +1431,13 @@ __global__ __launch_bounds__(512, 2) void dgn_resident_kernel(const DgnResidentA
                                 const int wi = u >> 5;
                                 const uint32_t cur = wi == 0 ? seen0 : (wi == 1 ? seen1 : (wi == 2 ? seen2 : seen3));
                                 if (cur & bit) {
-                                    const float eu = (s_eig[u] - eig_v) * wscale;  // the copy's (scaled) weight
+                                    float eu = (s_eig[u] - eig_v) * wscale;  // the copy's (scaled) weight
+                                    if constexpr (DGN_F16) eu = (float)(_Float16)eu;  // ... as the first copy's: rounded once
 #pragma unroll
                                     for (int c = 0; c < 4; c++) {
                                         const int f = (k < 6 ? 16 * k : 96) + 4 * g + c;
-                                        const float x = (float)__builtin_bit_cast(_Float16, s_ht_hi[f * DGN_HT_STRIDE + u]) +
-                                                        (float)__builtin_bit_cast(_Float16, s_ht_lo[f * DGN_HT_STRIDE + u]);
+                                        float x = (float)__builtin_bit_cast(_Float16, s_ht_hi[f * DGN_HT_STRIDE + u]);
+                                        if constexpr (!DGN_F16) x += (float)__builtin_bit_cast(_Float16, s_ht_lo[f * DGN_HT_STRIDE + u]);
                                         m1[c] += x;
                                         pp[c] = __builtin_fmaf(x, eu, pp[c]);
                                     }
@@ -1365,11 +1459,11 @@ __global__ __launch_bounds__(512, 2) void dgn_resident_kernel(const DgnResidentA
                 // mask spelled out for every K-step hipcc kept an exec-mask region and eight v_mov per K-step: others-per-MFMA is what
                 // this kernel is bound by, tools/coissue6.hip)
                 if (!real) { a1 = make_float4(0.f, 0.f, 0.f, 0.f); a2 = a1; }
-                ds_uint4_t b_hi, b_lo;
-                DS_SPLIT2(a1.x, a1.y, b_hi.x, b_lo.x);
-                DS_SPLIT2(a1.z, a1.w, b_hi.y, b_lo.y);
-                DS_SPLIT2(a2.x, a2.y, b_hi.z, b_lo.z);
-                DS_SPLIT2(a2.z, a2.w, b_hi.w, b_lo.w);
+                ds_uint4_t b_hi, b_lo = {0u, 0u, 0u, 0u};
+                DGN_OPER2(a1.x, a1.y, b_hi.x, b_lo.x);
+                DGN_OPER2(a1.z, a1.w, b_hi.y, b_lo.y);
+                DGN_OPER2(a2.x, a2.y, b_hi.z, b_lo.z);
+                DGN_OPER2(a2.z, a2.w, b_hi.w, b_lo.w);
                 asm("v_max3_f32 %0, |%1|, |%2|, %0" : "+v"(vmax) : "v"(a1.x), "v"(a1.y));
                 asm("v_max3_f32 %0, |%1|, |%2|, %0" : "+v"(vmax) : "v"(a1.z), "v"(a1.w));
                 asm("v_max3_f32 %0, |%1|, |%2|, %0" : "+v"(vmax) : "v"(a2.x), "v"(a2.y));
@@ -1378,6 +1472,14 @@ __global__ __launch_bounds__(512, 2) void dgn_resident_kernel(const DgnResidentA
                 // ---- dense update, K-step k: 21 MFMAs on the chunk in slot (l + k) & 1
                 const char* wb = s_w + ((l + k) & 1) * DGN_CHUNK;
                 if (DGNR_SKIP(8)) { acc[0].x += __builtin_bit_cast(float, b_hi.x ^ b_lo.y); continue; }
+                if constexpr (DGN_F16) {  // single product: seven fragments, seven MFMAs, one per accumulator
+                    ds_uint4_t f7[DGN_OT];
+#pragma unroll
+                    for (int t = 0; t < DGN_OT; t++) f7[t] = *reinterpret_cast<const ds_uint4_t*>(wb + t * 1024 + lane * 16);
+#pragma unroll
+                    for (int t = 0; t < DGN_OT; t++) acc[t] = DS_MFMA16(f7[t], b_hi, acc[t]);
+                    continue;
+                }
                 ds_uint4_t ff[2][4];  // the fragments of the NEXT pair of output tiles are requested before this pair's MFMAs issue
 #pragma unroll
                 for (int i = 0; i < 4; i++) ff[0][i] = *reinterpret_cast<const ds_uint4_t*>(wb + i * 1024 + lane * 16);
@@ -1507,6 +1609,7 @@ __global__ __launch_bounds__(512, 2) void dgn_resident_kernel(const DgnResidentA
         if (!has_next) break;
         tile = ntile;
     }
+    if constexpr (DGN_F16) vmax = __builtin_fmaxf(vmax, hmax);
     if (__any(!(vmax < 6.0e4f)) && !DGNR_SKIP(63)) {  // (a timing variant's garbage must not send the engine to the exact kernels)
         if (lane == 0) atomicOr(a.range_flag, 1);
     }
@@ -1514,8 +1617,12 @@ __global__ __launch_bounds__(512, 2) void dgn_resident_kernel(const DgnResidentA
 
 // host: W [100][2][100] (out, block, in), b [100] -> DGN_FT_LAYER_BYTES in the feature-major K order of dgn_layer_fused_kernel
 #ifndef FG_RESIDENT_KERNEL_TU  // (host side: the model's own translation unit only)
-static void dgn_pack_fused_layer(const float* W, const float* b, uint8_t* out) {
-    std::memset(out, 0, DGN_FT_LAYER_BYTES);
+// f16 (FLOWGNN_NUMERIC_F16): the stream of the single-product kernels -- the hi halves r(W s) alone (round to nearest even), [k][t] x 1 KiB,
+// with the same bias block and 1 / scale behind them: DGN_F16_LAYER_BYTES
+static void dgn_pack_fused_layer(const float* W, const float* b, uint8_t* out, bool f16 = false) {
+    const int frags = f16 ? 1 : 2;
+    const size_t bias_off = f16 ? DGN_F16_LAYER_BYTES - 512 : (size_t)DGN_FT_BIAS;
+    std::memset(out, 0, f16 ? DGN_F16_LAYER_BYTES : DGN_FT_LAYER_BYTES);
     float m = 0.0f;
     for (size_t i = 0; i < (size_t)DGN_D * 2 * DGN_D; i++) m = std::fmax(m, std::fabs(W[i]));
     const float sc = (m > 0.0f && std::isfinite(m)) ? std::ldexp(1.0f, -std::ilogb(m)) : 1.0f;
@@ -1523,22 +1630,22 @@ static void dgn_pack_fused_layer(const float* W, const float* b, uint8_t* out) {
         for (int t = 0; t < DGN_OT; t++)
             for (int lane = 0; lane < 64; lane++) {
                 const int i = lane & 15, gk = lane >> 4, o = 16 * t + i;
-                uint8_t* f = out + (size_t)((k * DGN_OT + t) * 2) * 1024;
+                uint8_t* f = out + (size_t)((k * DGN_OT + t) * frags) * 1024;
                 for (int e = 0; e < 8; e++) {
                     const int feat = 16 * k + 4 * gk + (e & 3), blk = e >> 2;
                     const float v = (o < DGN_D && feat < DGN_D) ? W[((size_t)o * 2 + blk) * DGN_D + feat] * sc : 0.0f;
                     const _Float16 hi = (_Float16)v;
                     const _Float16 lo = (_Float16)(v - (float)hi);
                     std::memcpy(f + lane * 16 + e * 2, &hi, 2);
-                    std::memcpy(f + 1024 + lane * 16 + e * 2, &lo, 2);
+                    if (!f16) std::memcpy(f + 1024 + lane * 16 + e * 2, &lo, 2);
                 }
             }
     for (int x = 0; x < 16 * DGN_OT; x++) {
         const float bb = x < DGN_D ? b[x] * sc : 0.0f;
-        std::memcpy(out + DGN_FT_BIAS + (size_t)x * 4, &bb, 4);
+        std::memcpy(out + bias_off + (size_t)x * 4, &bb, 4);
     }
     const float os = 1.0f / sc;
-    std::memcpy(out + DGN_FT_BIAS + 112 * 4, &os, 4);
+    std::memcpy(out + bias_off + 112 * 4, &os, 4);
 }
 
 class DgnModel : public Model {
@@ -1554,8 +1661,10 @@ public:
     // host tensors (DGN/src/dcl.h:81-90): atom tables [9][119][100], layer W [4][100][200], b [4][100],
     // FC0 w [50][100] b [50], FC1 w [25][50] b [25], FC2 w [1][25] b [1]
     int set_numeric_mode(int mode) override {  // mode 1 = "the reference's own format": ap_fixed<16,3> for DGN (DGN/src/dcl.h:54-55)
-        if (mode != 0 && mode != 1) return 8;
+        // mode 2 (FLOWGNN_NUMERIC_F16): the engine lets it through for flowgnn_set_model_numeric_mode alone
+        if (mode != 0 && mode != 1 && mode != 2) return 8;
         qmode_ = mode == 1;
+        f16_ = mode == 2;
         return 0;
     }
 
@@ -1577,6 +1686,7 @@ public:
             v_w2(t[7], t[7] + 25), v_b2(t[8], t[8] + 1);
         std::vector<float> wf_all, wt_all, bp_all;
         std::vector<uint8_t> split_all, fused_all;
+        std::vector<uint8_t> fused16_all((size_t)DGN_L * DGN_F16_LAYER_BYTES);  // beside them the single-product streams (FLOWGNN_NUMERIC_F16)
         std::vector<float> Wb((size_t)DGN_D * DGN_D), zero(DGN_D, 0.0f);
         for (int l = 0; l < DGN_L; l++) {
             const float* W = t[1] + (size_t)l * DGN_D * 2 * DGN_D;  // [out][2][in]
@@ -1600,10 +1710,12 @@ public:
             const size_t foff = fused_all.size();
             fused_all.resize(foff + DGN_FT_LAYER_BYTES);
             dgn_pack_fused_layer(W, t[2] + (size_t)l * DGN_D, fused_all.data() + foff);
+            dgn_pack_fused_layer(W, t[2] + (size_t)l * DGN_D, fused16_all.data() + (size_t)l * DGN_F16_LAYER_BYTES, true);
         }
         int rc;
         if ((rc = upload(&d_split_, split_all))) return rc;
         if ((rc = upload(&d_fused_, fused_all))) return rc;
+        if ((rc = upload(&d_fused16_, fused16_all))) return rc;
         if ((rc = upload(&d_emb_, v_emb))) return rc;
         if ((rc = upload(&d_wf_, wf_all))) return rc;
         if ((rc = upload(&d_wt_, wt_all))) return rc;
@@ -1689,7 +1801,7 @@ public:
         DgnPlanInput in;
         in.fused = fused_; in.split = split_; in.mfma_agg = mfma_agg_; in.fold_readout = fold_readout_; in.rowinfo_direct = rowinfo_direct_;
         in.resident = resident_; in.binpack = binpack_;
-        in.qmode = qmode_; in.keep_h = keep_h_; in.exact = exact_;
+        in.qmode = qmode_; in.keep_h = keep_h_; in.exact = exact_; in.f16 = f16_;
         return in;
     }
     DgnPlan plan(const DeviceBatch& db) const {
@@ -1714,12 +1826,19 @@ public:
                                                                nullptr, db.csr.err, nullptr, t.list);
         }
         DgnResidentLaunch a;
-        a.rec = reinterpret_cast<const uint32_t*>(rec_.p); a.table = d_emb_; a.wpk = d_fused_; a.head = d_head_;
+        a.rec = reinterpret_cast<const uint32_t*>(rec_.p); a.table = d_emb_; a.wpk = plan.single_product ? d_fused16_ : d_fused_; a.head = d_head_;
         a.tile_row = t.row; a.tile_graph = t.graph; a.list = t.list; a.n_tiles = t.n_tiles;
         a.b = db.b;
         a.out = db.out; a.emb = db.emb; a.node_emb = db.node_emb; a.range_flag = db.range_flag;
         const int grid = t.n_tiles < 256 ? t.n_tiles : 256;  // persistent: one 8-wave workgroup per CU (157 KB of LDS)
-        {
+        if (plan.single_product) {  // FLOWGNN_NUMERIC_F16: the single-product instances, in a slot of their own
+            ProfScope p(prof, "dgn_resident_f16", s);
+            switch (plan.instance) {
+            case DgnResidentInstance::Rows: launch_dgn_resident_f16_rows(a, grid, s); break;
+            case DgnResidentInstance::Emb: launch_dgn_resident_f16_emb(a, grid, s); break;
+            case DgnResidentInstance::Default: launch_dgn_resident_f16_default(a, grid, s); break;
+            }
+        } else {
             ProfScope p(prof, "dgn_resident", s);
             switch (plan.instance) {
             case DgnResidentInstance::Rows: launch_dgn_resident_rows(a, grid, s); break;  // the row-storing instance, embeddings or not
@@ -1764,7 +1883,7 @@ public:
             // (node embeddings: the last layer writes h_4 straight into the caller's buffer, and the readout pools it from there)
             float* const hn = (l == DGN_L - 1 && db.node_emb) ? db.node_emb : db.h[cur ^ 1];
             if (plan.fused_layers) {
-                ProfScope p(prof, "dgn_layer_fused", s);
+                ProfScope p(prof, plan.single_product ? "dgn_layer_mfma_f16" : "dgn_layer_fused", s);
                 const int grid = db.gtiles.n_tiles < 256 ? db.gtiles.n_tiles : 256;  // persistent: one 8-wave workgroup per CU (153 KB of LDS)
                 // dense tiles (kNN graphs: 16 in-edges per row, a third of a graph's block filled): both aggregates as MFMAs with the
                 // tile's adjacency; sparse ones (molecules, ~2 in-edges per row): the in-edge walk is cheaper than 20 MFMAs per K-step
@@ -1787,6 +1906,12 @@ public:
                         dgn_graph_info_kernel<<<(db.b.num_graphs + 255) / 256, 256, 0, s>>>(db.b.node_off, db.b.num_graphs,
                                                                                           reinterpret_cast<int2*>(ginfo_.p));
                     }
+                    if (plan.single_product) {  // FLOWGNN_NUMERIC_F16: the same three instances as single products, on the hi-only stream
+                        const DgnLayerMfmaLaunch a{db.h[cur], hn, db.csr.row_ptr, db.csr.src, db.csr.out_deg, db.node_eigen,
+                                                   d_fused16_ + (size_t)l * DGN_F16_LAYER_BYTES, db.gtiles.row_start, db.gtiles.n_tiles, db.range_flag,
+                                                   ablate_, ri, reinterpret_cast<const int2*>(ginfo_.p), pool_part_.p, pool_cnt_.p};
+                        launch_dgn_layer_mfma_f16(a, (l == 0 && plan.first_layer_makes_rowinfo) ? 1 : 2, pool, grid, s);
+                    } else
                     if (l == 0 && plan.first_layer_makes_rowinfo) DGN_MFMA_LAUNCH(1, false); else if (pool) DGN_MFMA_LAUNCH(2, true); else DGN_MFMA_LAUNCH(2, false);
 #undef DGN_MFMA_LAUNCH
                     cur ^= 1;
@@ -1875,9 +2000,11 @@ private:
         q_.release();
         if (d_split_) { (void)hipFree(d_split_); d_split_ = nullptr; }
         if (d_fused_) { (void)hipFree(d_fused_); d_fused_ = nullptr; }
+        if (d_fused16_) { (void)hipFree(d_fused16_); d_fused16_ = nullptr; }
     }
     bool ready_ = false;
     bool qmode_ = false;  // flowgnn_set_numeric_mode(FLOWGNN_NUMERIC_Q6_10): ap_fixed<16,3> arithmetic
+    bool f16_ = false;    // flowgnn_set_model_numeric_mode(e, FLOWGNN_MODEL_DGN, FLOWGNN_NUMERIC_F16): the single-product kernels (dgn_f16.hip)
     QPack q_;
     GrowBufI tiles_;  // graph-aligned tile starts of the resident batch (tile_bounds_kernel)
     static constexpr int kTileNominal = 64, kTileSlack = 64;  // the model's defaults of the options tile_nominal / tile_slack
@@ -1900,6 +2027,7 @@ private:
     int ablate_ = 0;  // development aid (-DFLOWGNN_DEV builds only, option dgn_ablate): per-phase timing (scripts/dev/pna_ablate.sh)
     bool fused_ = true;
     uint8_t* d_fused_ = nullptr;  // feature-major weights of the fused layer kernel
+    uint8_t* d_fused16_ = nullptr;  // the same as hi halves alone (FLOWGNN_NUMERIC_F16)
     bool exact_ = false;
     uint8_t* d_split_ = nullptr;
     GrowBuf esc_;
@@ -1913,8 +2041,24 @@ Model* make_dgn_model() { return new DgnModel(); }
 #ifdef FG_RESIDENT_KERNEL_TU
 }  // namespace
 #endif
+#if DGN_SINGLE_PRODUCT && !defined(FG_RESIDENT_EMB_TU) && !defined(FG_RESIDENT_ROWS_TU)
+// dgn_f16.hip: the per-layer matrix-pipe kernel's single-product instances
+void launch_dgn_layer_mfma_f16(const DgnLayerMfmaLaunch& a, int info, bool pool, int grid, hipStream_t s) {
+#define DGN_MFMA_F16_LAUNCH(I, P)                                                                                                            \
+    dgn_layer_mfma_kernel<I, P><<<grid, 512, 0, s>>>(a.h, a.hout, a.row_ptr, a.src, a.out_deg, a.eig4, a.wpk, a.tile_row, a.n_tiles, a.range_flag, \
+                                                     a.ablate, a.rowinfo, a.ginfo, a.pool_part, a.pool_cnt)
+    if (info == 1) DGN_MFMA_F16_LAUNCH(1, false); else if (pool) DGN_MFMA_F16_LAUNCH(2, true); else DGN_MFMA_F16_LAUNCH(2, false);
+#undef DGN_MFMA_F16_LAUNCH
+}
+#endif
 // this translation unit's instance of dgn_resident_kernel, under the launcher's name that goes with it
-#if defined(FG_RESIDENT_EMB_TU)
+#if DGN_SINGLE_PRODUCT && defined(FG_RESIDENT_EMB_TU)
+void launch_dgn_resident_f16_emb(
+#elif DGN_SINGLE_PRODUCT && defined(FG_RESIDENT_ROWS_TU)
+void launch_dgn_resident_f16_rows(
+#elif DGN_SINGLE_PRODUCT
+void launch_dgn_resident_f16_default(
+#elif defined(FG_RESIDENT_EMB_TU)
 void launch_dgn_resident_emb(
 #elif defined(FG_RESIDENT_ROWS_TU)
 void launch_dgn_resident_rows(

@@ -16,6 +16,7 @@ struct DgnPlanInput {
     bool binpack = true;         // dgn_binpack
     // model state
     bool qmode = false;   // FLOWGNN_NUMERIC_Q6_10
+    bool f16 = false;     // FLOWGNN_NUMERIC_F16: the single-product instances of the matrix-pipe kernels (dgn_f16.hip)
     bool keep_h = false;  // a per-node tap wants h_4 in HBM (flowgnn_get_h)
     bool exact = false;   // the engine asked for the fp32 pipe after the range flag tripped
     // batch
@@ -56,6 +57,10 @@ struct DgnPlan {
     bool edge_scalar = false;        // ... and eig1[src] per CSR entry (needs an edge)
     bool split_dense = false;        // the two-kernel layer's dense one as split-f16 products, else on the fp32 pipe
     bool emb_readout = false;        // the readout also stores the pooled rows
+    // ---- either path: the matrix-pipe kernels it runs (dgn_resident_kernel, dgn_layer_mfma_kernel) are their single-product instances
+    // (FLOWGNN_NUMERIC_F16).  Path, instance and every other flag are the ones the same input gets with f16 off; the in-edge walk
+    // (dgn_layer_fused_kernel), the two-kernel layer and the fp32 pipe (dgn_mfma=32, the exact re-run) have no such instance and run as they are
+    bool single_product = false;
 };
 
 // flowgnn_set_batch also bin-packs the graphs into tile lists: asked before there is a batch, so from the options and the model state alone
@@ -78,6 +83,7 @@ inline DgnPlan dgn_plan(const DgnPlanInput& in) {
         p.needs_csr = false;
         p.bin_packed = in.binpack && in.bp_lists;
         p.instance = in.node_emb ? DgnResidentInstance::Rows : in.emb ? DgnResidentInstance::Emb : DgnResidentInstance::Default;
+        p.single_product = in.f16;  // (qmode has returned above: it wins over f16; tile_kernels holds split && !exact)
         return p;
     }
     p.fused_layers = tile_kernels;
@@ -90,6 +96,7 @@ inline DgnPlan dgn_plan(const DgnPlanInput& in) {
     p.edge_scalar = p.prepare_aggregate && in.edges;
     p.split_dense = p.prepare_aggregate && in.split && !in.exact;
     p.emb_readout = in.emb;
+    p.single_product = in.f16 && p.fused_layers && p.mfma_aggregation;
     return p;
 }
 

@@ -1437,7 +1437,14 @@ int flowgnn_emb_dim(const flowgnn_engine* e) { return e ? e->emb_dim : -1; }
 // keeps refusing it there.
 // pna_form: the call was flowgnn_set_model_numeric_mode_dim(e, FLOWGNN_EMB_DIM_PNA, ..) on a PNA engine -- the one way to PNA's
 // FLOWGNN_NUMERIC_F16 (pna_f16.hip); every other call keeps refusing it there.
-static int set_numeric_mode(flowgnn_engine* e, int mode, bool with_dim, bool model_form = false, bool pna_form = false) {
+// dgn_form: the call was flowgnn_set_model_numeric_mode(e, FLOWGNN_MODEL_DGN, ..) on a DGN engine -- the one way to DGN's
+// FLOWGNN_NUMERIC_F16 (dgn_f16.hip); every other call keeps refusing it there.
+static int set_numeric_mode(flowgnn_engine* e, int mode, bool with_dim, bool model_form = false, bool pna_form = false, bool dgn_form = false) {
+    if (mode == FLOWGNN_NUMERIC_F16 && e->model_id == FLOWGNN_MODEL_DGN && !dgn_form) {
+        e->err = "flowgnn_set_numeric_mode: DGN's f16 mode goes through the call that names the model: "
+                 "flowgnn_set_model_numeric_mode(e, FLOWGNN_MODEL_DGN, FLOWGNN_NUMERIC_F16)";
+        return FLOWGNN_ERR_UNSUPPORTED;
+    }
     if (mode == FLOWGNN_NUMERIC_F16 && e->model_id == FLOWGNN_MODEL_PNA && !pna_form) {
         e->err = "flowgnn_set_numeric_mode: PNA's f16 mode goes through the call that carries the model, with the model's true width: "
                  "flowgnn_set_model_numeric_mode_dim(e, FLOWGNN_EMB_DIM_PNA (80), FLOWGNN_NUMERIC_F16)";
@@ -1534,6 +1541,30 @@ int flowgnn_set_model_numeric_mode_dim(flowgnn_engine* e, int emb_dim, int mode)
     }
     if (e->model_id != FLOWGNN_MODEL_GCN) return flowgnn_set_numeric_mode_dim(e, emb_dim, mode);
     return set_numeric_mode_dim(e, "flowgnn_set_model_numeric_mode_dim", emb_dim, mode, true);
+}
+
+// The call that names the model: one call that reaches every mode any engine has.  On a DGN engine (whose width is the reference's 100,
+// so no width of its own to enter through) it takes F32, Q6_10 and F16 -- dgn_f16.hip's kernels; on every other
+// engine it is flowgnn_set_model_numeric_mode_dim at that engine's own current width.
+int flowgnn_set_model_numeric_mode(flowgnn_engine* e, int model_id, int mode) {
+    if (!e) return FLOWGNN_ERR_ARG;
+    static const char* const names[] = {"FLOWGNN_MODEL_GIN", "FLOWGNN_MODEL_GIN_VN", "FLOWGNN_MODEL_GCN", "FLOWGNN_MODEL_GAT", "FLOWGNN_MODEL_PNA", "FLOWGNN_MODEL_DGN"};
+    auto name = [&](int m) { return std::to_string(m) + " (" + ((m >= 0 && m < 6) ? names[m] : "no model") + ")"; };
+    if (model_id != e->model_id) {
+        e->err = "flowgnn_set_model_numeric_mode: model_id is " + name(model_id) + " and the engine's model is " + name(e->model_id);
+        return FLOWGNN_ERR_ARG;
+    }
+    if (e->model_id == FLOWGNN_MODEL_DGN) {
+        if (mode != FLOWGNN_NUMERIC_F32 && mode != FLOWGNN_NUMERIC_Q6_10 && mode != FLOWGNN_NUMERIC_F16) {
+            e->err = "flowgnn_set_model_numeric_mode: mode is " + std::to_string(mode) +
+                     "; the modes are FLOWGNN_NUMERIC_F32 (0), FLOWGNN_NUMERIC_Q6_10 (1) and FLOWGNN_NUMERIC_F16 (2)";
+            return FLOWGNN_ERR_ARG;
+        }
+        return set_numeric_mode(e, mode, true, true, false, true);
+    }
+    // (flowgnn_emb_dim is the model's own figure for the models without a choice of width -- GAT's 16; their width for these calls is 100)
+    const int width = e->model_id == FLOWGNN_MODEL_PNA ? FLOWGNN_EMB_DIM_PNA : off_default_width(e) ? e->emb_dim : FLOWGNN_EMB_DIM_REFERENCE;
+    return flowgnn_set_model_numeric_mode_dim(e, width, mode);
 }
 
 int flowgnn_set_pooling(flowgnn_engine* e, int mode) {

@@ -252,6 +252,9 @@ int flowgnn_group_set_numeric_mode_dim(flowgnn_group* g, int emb_dim, int mode) 
 int flowgnn_group_set_model_numeric_mode_dim(flowgnn_group* g, int emb_dim, int mode) {
     return group_all(g, [&](flowgnn_engine* e) { return flowgnn_set_model_numeric_mode_dim(e, emb_dim, mode); });
 }
+int flowgnn_group_set_model_numeric_mode(flowgnn_group* g, int model_id, int mode) {
+    return group_all(g, [&](flowgnn_engine* e) { return flowgnn_set_model_numeric_mode(e, model_id, mode); });
+}
 int flowgnn_group_set_pooling(flowgnn_group* g, int mode) { return group_all(g, [&](flowgnn_engine* e) { return flowgnn_set_pooling(e, mode); }); }
 int flowgnn_group_set_gin_eps(flowgnn_group* g, const float* eps) { return group_all(g, [&](flowgnn_engine* e) { return flowgnn_set_gin_eps(e, eps); }); }
 int flowgnn_group_set_ogb_virtual_node(flowgnn_group* g, const float* vn_embedding, const float* w1, const float* b1, const float* w2, const float* b2) {

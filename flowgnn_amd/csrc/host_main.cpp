@@ -37,6 +37,8 @@
 //   --numeric    f32 (default), q6.10 or f16.  `host PNA --numeric f16` sends PNA's f16 mode through
 //                flowgnn_group_set_model_numeric_mode_dim at FLOWGNN_EMB_DIM_PNA (80): one f16 rounding of each operand of the layer's
 //                320 -> 3 x 80 contraction, one MFMA per product
+//                `host DGN --numeric f16` sends DGN's f16 mode through flowgnn_group_set_model_numeric_mode, the call that names the model:
+//                one f16 rounding of each operand of the matrix-pipe products (both aggregates and the 200 -> 100 update), one MFMA each
 //   --eig        DGN: directory holding the eigenvector text files g%d.txt                 (default eig, DGN/src/host_load.cc:178)
 //   --compute-eig DGN: compute node_eigen from the graphs on the GPU (flowgnn_laplacian_eigen, on the first engine) and read no --eig DIR
 //   XCLBIN       accepted and ignored, so `./host <xclbin>`-style command lines keep working
@@ -204,7 +206,9 @@ int main(int argc, char** argv) {
         // --emb-dim 300: through the call that carries the width (GIN's f16 mode at that width, gin_wide_f16.hip); GCN's goes through
         // the call that names no model (gcn_wide_f16.hip), as its width did
         // PNA's f16 mode: the group's model form at the model's true width (pna_f16.hip)
-        if (mid == FLOWGNN_MODEL_PNA && numeric == FLOWGNN_NUMERIC_F16) rc = flowgnn_group_set_model_numeric_mode_dim(eng, FLOWGNN_EMB_DIM_PNA, numeric);
+        // DGN's f16 mode: the group's call that names the model (dgn_f16.hip)
+        if (mid == FLOWGNN_MODEL_DGN && numeric == FLOWGNN_NUMERIC_F16) rc = flowgnn_group_set_model_numeric_mode(eng, FLOWGNN_MODEL_DGN, numeric);
+        else if (mid == FLOWGNN_MODEL_PNA && numeric == FLOWGNN_NUMERIC_F16) rc = flowgnn_group_set_model_numeric_mode_dim(eng, FLOWGNN_EMB_DIM_PNA, numeric);
         else if (mid == FLOWGNN_MODEL_GCN && emb_dim != FLOWGNN_EMB_DIM_REFERENCE) rc = flowgnn_group_set_model_numeric_mode_dim(eng, emb_dim, numeric);
         else rc = emb_dim != FLOWGNN_EMB_DIM_REFERENCE ? flowgnn_group_set_numeric_mode_dim(eng, emb_dim, numeric) : flowgnn_group_set_numeric_mode(eng, numeric);
         if (rc) { fprintf(stderr, "numeric mode: %d %s\n", rc, flowgnn_group_last_error(eng)); return EXIT_FAILURE; }

@@ -643,10 +643,17 @@ class Engine:
         gcn and gcn-virtual at width 300 (stages 0..3 with one f16 rounding of each operand of the layer's product).
         A PNA engine takes the model form too: set_numeric_mode("f16", emb_dim=80) -- 80 is PNA's own width, FLOWGNN_EMB_DIM_PNA -- is
         the one way to PNA's "f16" (each operand of the layer's 320 -> 3 x 80 contraction rounded to f16 once, one MFMA per product);
-        without emb_dim, or with 100, "f16" stays refused on PNA."""
+        without emb_dim, or with 100, "f16" stays refused on PNA.
+        A DGN engine with emb_dim (100, DGN's width) takes the call that names the model, flowgnn_set_model_numeric_mode:
+        set_numeric_mode("f16", emb_dim=100) is the one way to DGN's "f16" (each operand of the matrix-pipe products -- both aggregates
+        and the 200 -> 100 update -- rounded to f16 once, one MFMA per product); without emb_dim "f16" stays refused on DGN."""
         code = NUMERIC_MODES[mode]
         if emb_dim is None:
             self._check(self.lib.flowgnn_set_numeric_mode(self._h, code), "flowgnn_set_numeric_mode")
+        elif self.model == "DGN":
+            if int(emb_dim) != 100:
+                raise ValueError(f"DGN's width is 100, not {emb_dim}")
+            self._check(self.lib.flowgnn_set_model_numeric_mode(self._h, _lib.MODEL_IDS["DGN"], code), "flowgnn_set_model_numeric_mode")
         elif self.model == "GCN":
             self._check(self.lib.flowgnn_set_model_numeric_mode_dim(self._h, int(emb_dim), code), "flowgnn_set_model_numeric_mode_dim")
         elif self.model == "PNA":  # (emb_dim=80: the one way to PNA's "f16")
@@ -867,9 +874,14 @@ class EngineGroup:
 
     def set_numeric_mode(self, mode: str = "f32", emb_dim: Optional[int] = None):
         """Engine.set_numeric_mode on every member (flowgnn.h: flowgnn_group_set_numeric_mode; with emb_dim: ..._dim; GCN, and PNA
-        with emb_dim=80: flowgnn_group_set_model_numeric_mode_dim)."""
+        with emb_dim=80: flowgnn_group_set_model_numeric_mode_dim; DGN with emb_dim=100: flowgnn_group_set_model_numeric_mode)."""
         if emb_dim is None:
             self._check(self.lib.flowgnn_group_set_numeric_mode(self._h, NUMERIC_MODES[mode]), "flowgnn_group_set_numeric_mode")
+        elif self.model == "DGN":
+            if int(emb_dim) != 100:
+                raise ValueError(f"DGN's width is 100, not {emb_dim}")
+            self._check(self.lib.flowgnn_group_set_model_numeric_mode(self._h, _lib.MODEL_IDS["DGN"], NUMERIC_MODES[mode]),
+                        "flowgnn_group_set_model_numeric_mode")
         elif self.model == "GCN":
             self._check(self.lib.flowgnn_group_set_model_numeric_mode_dim(self._h, int(emb_dim), NUMERIC_MODES[mode]),
                         "flowgnn_group_set_model_numeric_mode_dim")

@@ -566,7 +566,8 @@ int flowgnn_set_model_emb_dim(flowgnn_engine* e, int emb_dim);   /* GIN, GCN: 10
 #define FLOWGNN_NUMERIC_Q6_10 1
 /*
  * FLOWGNN_NUMERIC_F16 (through this call: GIN and GIN-VN only, NUM_TASK 1 or more; every other model returns FLOWGNN_ERR_UNSUPPORTED --
- * GIN and GCN at width 300 and PNA have theirs behind flowgnn_set_numeric_mode_dim / flowgnn_set_model_numeric_mode_dim below): the
+ * GIN and GCN at width 300 and PNA have theirs behind flowgnn_set_numeric_mode_dim / flowgnn_set_model_numeric_mode_dim below, DGN
+ * behind flowgnn_set_model_numeric_mode, the call that names the model and reaches every mode any engine has): the
  * 16-bit operand speed of the matrix pipe.  Every operand of the node MLP's two linear layers -- the weights and the
  * activation each of them multiplies -- is rounded to f16 (round to nearest even), and each product is ONE f16 x f16 MFMA
  * with fp32 accumulation (the default mode forms every product from three).  The weights are rounded after the exact
@@ -646,8 +647,40 @@ int flowgnn_set_model_numeric_mode_dim(flowgnn_engine* e, int emb_dim, int mode)
  * fallback as above: an aggregate beyond 6e4 raises the flag and the pass is repeated on the fp32 path -- that batch's results are the
  * f32 mode's bytes.  pna_mfma=32 keeps the fp32 pipe, and with it f32-mode results.  The mode is the engine's: it survives
  * flowgnn_set_weights and new batches, and runs with embeddings, node embeddings, flowgnn_get_h, device batches, groups and option
- * hipgraph; sum and max pooling stay refused for PNA.  DGN is the one model left without an f16 mode.
+ * hipgraph; sum and max pooling stay refused for PNA.  (DGN's f16 mode: flowgnn_set_model_numeric_mode, below.)
  */
+/*
+ * The numeric mode through the call that names the MODEL: model_id must be the engine's own model (FLOWGNN_ERR_ARG otherwise; the text
+ * names both models; a null handle: FLOWGNN_ERR_ARG).  One call then reaches every mode any engine has:
+ *   on a FLOWGNN_MODEL_DGN engine it accepts FLOWGNN_NUMERIC_F32, FLOWGNN_NUMERIC_Q6_10 (both as flowgnn_set_numeric_mode has them; Q6_10
+ *   stays refused beside embeddings and the other outputs without a fixed-point form) and FLOWGNN_NUMERIC_F16: the one way to DGN's f16
+ *   mode.  DGN's width is the reference's 100, so it has no width of its own to enter through as PNA has: flowgnn_set_numeric_mode,
+ *   flowgnn_set_numeric_mode_dim and flowgnn_set_model_numeric_mode_dim(e, 100, FLOWGNN_NUMERIC_F16) keep returning
+ *   FLOWGNN_ERR_UNSUPPORTED on a DGN engine, and the text names this call;
+ *   on every other engine it IS flowgnn_set_model_numeric_mode_dim at that engine's own current width: FLOWGNN_EMB_DIM_PNA for PNA, the
+ *   engine's width (flowgnn_set_emb_dim / flowgnn_set_model_emb_dim) for GIN and GCN, 100 for GIN-VN and GAT -- return code for return code.
+ * FLOWGNN_NUMERIC_F16 for DGN changes the operands of the matrix-pipe products and nothing else.  Per layer:
+ *   each feature of a source row h[u] is rounded to f16 ONCE, to nearest even (x_u; the default mode keeps a hi and a lo half);
+ *   m1[v] = sum_{u->v} x_u is one MFMA per 32-source block, fp32 accumulation;
+ *   the directional weight is d_uv = rne_f16((eig1[u] - eig1[v]) wscale_v) -- the fp32 subtraction and the exact power-of-two scale of
+ *   the row first, then one rounding -- and pp[v] = sum x_u d_uv one MFMA per block; every further copy of a duplicate edge adds the
+ *   same product x_u d_uv as its first;
+ *   a1 = m1 / outdeg and a2 = |fma(-wsum wscale, h[v], pp) / (abssum wscale)| in fp32 as in the default mode, with h[v] unrounded;
+ *   the dense update: a1 and a2 rounded to f16 once, to nearest even, the weights r(W s) (the hi halves of the default mode's split
+ *   stream), ONE f16 x f16 MFMA per product in the default mode's accumulator order, the pre-scaled fp32 bias first;
+ *   h' = h + relu(acc / s) in fp32.
+ * fp32 and unchanged: the encoder, the row records (masks, wsum, abssum, out-degree), the residual, the rows and pooled rows that leave
+ * the kernels, the mean pool and the 100 -> 50 -> 25 -> 1 head.  Range fallback as above: an a1, an a2 or -- in this mode -- any value of
+ * h that is rounded as a source row beyond 6e4 raises the flag and the pass is repeated on the exact fp32 path: that batch's results are
+ * the f32 mode's bytes (flowgnn_exact_reruns counts it).
+ * The mode lives on the matrix-pipe kernels (the graph-resident kernel and the per-layer matrix-pipe kernel that flowgnn_get_h runs: their
+ * taps are the mode's values, and the two agree in every byte on the same tiles, as in the default mode).  A job whose plan picks the
+ * in-edge walk, the two-kernel layer or the fp32 pipe -- sparse jobs with E < 8 N, tiles under 0.4 fill, dgn_mfma=32, the exact re-run --
+ * runs the default kernels and returns the f32 mode's bytes, as PNA's mode does under pna_mfma=32.  The mode is the engine's: it survives
+ * flowgnn_set_weights and new batches, and runs with embeddings, node embeddings, flowgnn_get_h, device batches, groups and option
+ * hipgraph (a recorded launch sequence is dropped on the switch); sum and max pooling stay refused for DGN.
+ */
+int flowgnn_set_model_numeric_mode(flowgnn_engine* e, int model_id, int mode);
 
 /*
  * Pooling of the readout (GIN, GIN-VN, GCN, GAT): how a graph's last node rows r[v] (what
@@ -1038,6 +1071,7 @@ int flowgnn_group_set_model_emb_dim(flowgnn_group* g, int emb_dim);
 int flowgnn_group_set_numeric_mode(flowgnn_group* g, int mode);
 int flowgnn_group_set_numeric_mode_dim(flowgnn_group* g, int emb_dim, int mode);
 int flowgnn_group_set_model_numeric_mode_dim(flowgnn_group* g, int emb_dim, int mode);
+int flowgnn_group_set_model_numeric_mode(flowgnn_group* g, int model_id, int mode);   /* flowgnn_set_model_numeric_mode on every member */
 int flowgnn_group_set_pooling(flowgnn_group* g, int mode);
 int flowgnn_group_set_gin_eps(flowgnn_group* g, const float* eps);
 int flowgnn_group_set_ogb_virtual_node(flowgnn_group* g, const float* vn_embedding, const float* w1, const float* b1, const float* w2, const float* b2);

@@ -5,7 +5,7 @@
 # ping-pong kernel live behind -DFLOWGNN_DEV: pass it with them, e.g. variant.sh cf gcn.hip "-DFLOWGNN_DEV -DGCN_CF_ROWS".
 # FILE.hip may be one of the files that compile a model's file once more under a macro (the instances of its resident kernel):
 #   gin_split_f16 gin_split_pool gin_split_nlogit gin_split_poolsum gin_split_poolmax gin_split_eps (gin_split.hip), gcn_rows gcn_nlogit gcn_poolsum (gcn.hip),
-#   gat_nlogit gat_attn gat_poolsum (gat.hip), pna_emb pna_rows pna_f16 pna_emb_f16 pna_rows_f16 (pna.hip), dgn_emb dgn_rows (dgn.hip)
+#   gat_nlogit gat_attn gat_poolsum (gat.hip), pna_emb pna_rows pna_f16 pna_emb_f16 pna_rows_f16 (pna.hip), dgn_emb dgn_rows dgn_f16 dgn_emb_f16 dgn_rows_f16 (dgn.hip)
 # -- a flag that changes the model's file changes them too, and each is recompiled by its own call: variant.sh sum gin_split_poolsum.hip "-D..."
 set -e
 name=$1; file=$2; flags=$3
