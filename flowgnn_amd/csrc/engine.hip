@@ -6,11 +6,9 @@
 //   flowgnn_create -> flowgnn_set_weights_* / flowgnn_load_weights_dir -> flowgnn_set_batch
 //   -> N x flowgnn_run -> flowgnn_get_results.
 // Several engines behind one handle: group.hip; the reference's <M>_compute_graphs symbols: entry.hip.
+// The calls that configure an engine (width, numeric mode, pooling, eps, virtual nodes, readouts, JK / residual): engine_config.hip.
 #include "engine_internal.h"
 #include "tile_pack.h"
-#include "gin_ogbvn.h"
-#include "wide_attn.h"
-#include "wide_s2s.h"
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -254,13 +252,13 @@ static int host_threads(int want) {
 }  // namespace fg
 
 // ------------------------------------------------------------------ engine object (struct flowgnn_engine: engine_internal.h)
-static int use_device(flowgnn_engine* e) {
+int use_device(flowgnn_engine* e) {
     FG_HIP_TRY(hipSetDevice(e->device));
     return 0;
 }
 
 // what every call that changes what the launched kernels read starts with: the engine's device, no recorded launch sequence, an idle stream
-static int begin_change(flowgnn_engine* e) {
+int begin_change(flowgnn_engine* e) {
     ENGINE_TRY(e, use_device(e));
     e->drop_graph();
     if (e->stream) EHIP_TRY(e, hipStreamSynchronize(e->stream));
@@ -285,31 +283,7 @@ static void ensure_csr(flowgnn_engine* e) {
     e->db.csr_built = true;
 }
 
-// The optional per-run outputs (fg::OutSlot, engine_internal.h), in ONE list: everything that treats them alike walks it.
-struct Output {
-    fg::OutSlot flowgnn_engine::*slot;
-    float* DeviceBatch::*field;               // the pointer of the forward's DeviceBatch that the slot feeds
-    bool flowgnn_engine::*on;                 // its switch (null: attn_mask, the switch of both attention slots)
-    size_t (*floats)(const flowgnn_engine*);  // what the resident batch needs of it
-    const char *noun, *setter;                // for the texts of its get and *_device calls
-    const char* no_fixed_point;               // flowgnn_set_numeric_mode's refusal while it is on (null: the row above has said it)
-};
-static size_t emb_dim_of(const flowgnn_engine* e) { return (size_t)e->emb_dim; }  // the ENGINE's width (flowgnn_set_emb_dim), not the model's default
-static size_t attn_layers(const flowgnn_engine* e) { return (size_t)__builtin_popcount((unsigned)e->attn_mask); }
-enum { OUT_EMB, OUT_NEMB, OUT_NLOG, OUT_ATTN_E, OUT_ATTN_S };
-static const Output kOutputs[] = {
-    {&flowgnn_engine::emb, &DeviceBatch::emb, &flowgnn_engine::emb_on, [](const flowgnn_engine* e) { return (size_t)e->G * emb_dim_of(e); },
-     "embeddings", "flowgnn_set_embeddings", "flowgnn_set_numeric_mode: graph embeddings are on, and there are no fixed-point embeddings"},
-    {&flowgnn_engine::nemb, &DeviceBatch::node_emb, &flowgnn_engine::nemb_on, [](const flowgnn_engine* e) { return (size_t)e->N * emb_dim_of(e); },
-     "node embeddings", "flowgnn_set_node_embeddings", "flowgnn_set_numeric_mode: node embeddings are on, and there are no fixed-point node embeddings"},
-    {&flowgnn_engine::nlog, &DeviceBatch::node_logits, &flowgnn_engine::nlog_on, [](const flowgnn_engine* e) { return (size_t)e->N * (size_t)e->num_tasks; },
-     "node logits", "flowgnn_set_node_logits", "flowgnn_set_numeric_mode: node logits are on, and there are no fixed-point node logits"},
-    {&flowgnn_engine::attn_e, &DeviceBatch::attn_edge, nullptr, [](const flowgnn_engine* e) { return attn_layers(e) * (size_t)e->E * 4; },
-     "attention", "flowgnn_set_attention", "flowgnn_set_numeric_mode: attention is on, and there are no fixed-point attention coefficients"},
-    {&flowgnn_engine::attn_s, &DeviceBatch::attn_self, nullptr, [](const flowgnn_engine* e) { return attn_layers(e) * (size_t)e->N * 4; },
-     "attention", "flowgnn_set_attention", nullptr},
-};
-static bool is_on(const flowgnn_engine* e, const Output& o) { return o.on ? e->*o.on : e->attn_mask != 0; }
+// (The optional per-run outputs, fg::OutSlot, and the ONE list of them, kOutputs: engine_internal.h.)
 
 // One output after anything it follows has changed (switch, caller's buffer, batch): with the output on and no caller's buffer, the
 // engine's own buffer holds what the resident batch needs; the DeviceBatch pointer is the target, or null without a batch
@@ -1314,688 +1288,6 @@ int flowgnn_batch_tiles(const flowgnn_engine* e, int* batch_order, int* packed) 
 int flowgnn_exact_reruns(const flowgnn_engine* e) { return e ? e->exact_reruns : -1; }
 
 long long flowgnn_graph_replays(const flowgnn_engine* e) { return e ? e->graph_replays : -1; }
-
-int flowgnn_set_num_tasks(flowgnn_engine* e, int num_tasks) {
-    if (!e || num_tasks < 1) return FLOWGNN_ERR_ARG;
-    if (e->s2s_steps && num_tasks != e->num_tasks) {  // (the readout's own head has NUM_TASK rows)
-        e->err = "flowgnn_set_num_tasks: the set2set pooling is on (flowgnn_set_set2set_pooling), and its head has " + std::to_string(e->num_tasks) +
-                 " tasks, not " + std::to_string(num_tasks) + ": turn it off, change NUM_TASK, set it again";
-        return FLOWGNN_ERR_UNSUPPORTED;
-    }
-    ENGINE_TRY(e, begin_change(e));
-    const int rc = e->model->set_num_tasks(num_tasks);
-    if (rc) { e->err = "flowgnn_set_num_tasks: this model's readout has a single task (multi-task readout exists for GIN / GIN-VN / GCN)"; return rc; }
-    e->num_tasks = num_tasks;
-    e->batch_ready = false;  // the result buffer is sized by the batch: set the batch again
-    e->ran = false;
-    return FLOWGNN_OK;
-}
-
-int flowgnn_num_tasks(const flowgnn_engine* e) { return e ? e->num_tasks : -1; }
-
-// The width is the model OBJECT: GinModel (gin.hip) / GcnModel (gcn.hip) at 100, the per-layer models of gin_wide.hip / gcn_wide.hip at
-// 300.  The call swaps it; everything the old object held (weights) goes with it, and everything sized by the width (h, the embeddings,
-// the node embeddings) with the batch.  `fn`: the caller (flowgnn_set_emb_dim: GIN; flowgnn_set_model_emb_dim: GIN and GCN).
-static bool off_default_width(const flowgnn_engine* e) { return e->emb_dim != flowgnn_embedding_dim(e->model_id); }
-
-static int set_width(flowgnn_engine* e, const char* fn, int emb_dim) {
-    const std::string who = std::string(fn) + ": ";
-    const bool gcn = e->model_id == FLOWGNN_MODEL_GCN;
-    if (emb_dim == e->emb_dim) return FLOWGNN_OK;
-    if (e->numeric_mode != FLOWGNN_NUMERIC_F32) {  // (either direction: the mode is the model object's, and the call swaps the object)
-        if (emb_dim != FLOWGNN_EMB_DIM_REFERENCE)
-            e->err = who + "a numeric mode other than FLOWGNN_NUMERIC_F32 is on (flowgnn_set_numeric_mode), and the width changes in "
-                     "FLOWGNN_NUMERIC_F32 only: width 300 has no fixed-point kernels, and the f16 mode at width 300 is set at that width, through "
-                     "flowgnn_set_numeric_mode_dim (GIN) or flowgnn_set_model_numeric_mode_dim (GCN)";
-        else
-            e->err = who + "a numeric mode other than FLOWGNN_NUMERIC_F32 is on at width 300 (flowgnn_set_numeric_mode_dim / flowgnn_set_model_numeric_mode_dim), and the width changes "
-                     "in FLOWGNN_NUMERIC_F32 only: set that mode, change the width, set the numeric mode again";
-        return FLOWGNN_ERR_UNSUPPORTED;
-    }
-    if (e->ogb_vn_on) {  // (either direction: the tensors belong to a width -- turn it off, change the width, set it again)
-        e->err = who + "OGB's virtual node is on (" + (gcn ? "flowgnn_set_gcn_virtual_node / flowgnn_set_gcn_virtual_node_dim" : "flowgnn_set_ogb_virtual_node / flowgnn_set_ogb_virtual_node_dim") +
-                 "), and its tensors are " + std::to_string(e->emb_dim) + " wide, not " + std::to_string(emb_dim) +
-                 ": turn it off, change the width, set it again";
-        return FLOWGNN_ERR_UNSUPPORTED;
-    }
-    if (e->attn_pool_on) {  // (the same rule: the gate's tensors belong to a width)
-        e->err = who + "the attention pooling is on (flowgnn_set_attention_pooling), and its tensors are " + std::to_string(e->emb_dim) + " wide, not " +
-                 std::to_string(emb_dim) + ": turn it off, change the width, set it again";
-        return FLOWGNN_ERR_UNSUPPORTED;
-    }
-    if (e->s2s_steps) {  // (and the same again)
-        e->err = who + "the set2set pooling is on (flowgnn_set_set2set_pooling), and its tensors are " + std::to_string(e->emb_dim) + " wide, not " +
-                 std::to_string(emb_dim) + ": turn it off, change the width, set it again";
-        return FLOWGNN_ERR_UNSUPPORTED;
-    }
-    if (e->jk != FLOWGNN_JK_LAST || e->residual) {  // (on means width 300: the call asks for 100, which has no instance)
-        e->err = who + "JK sum or the residual is on (" + (gcn ? "flowgnn_set_model_jk_residual" : "flowgnn_set_jk_residual") + "), and only the 300-wide " +
-                 (gcn ? "GCN" : "GIN") + " has those instances, not width " + std::to_string(emb_dim) +
-                 ": turn it off (FLOWGNN_JK_LAST, 0), then change the width";
-        return FLOWGNN_ERR_UNSUPPORTED;
-    }
-    ENGINE_TRY(e, begin_change(e));
-    Model* m = gcn ? (emb_dim == FLOWGNN_EMB_DIM_REFERENCE ? make_gcn_model() : make_gcn_wide_model(emb_dim))
-                   : (emb_dim == FLOWGNN_EMB_DIM_REFERENCE ? make_gin_model(false) : make_gin_wide_model(emb_dim));
-    if (!m) { e->err = who + "no model of this width"; return FLOWGNN_ERR_UNSUPPORTED; }
-    m->configure(e->opts);
-    if (int rc = m->set_num_tasks(e->num_tasks)) {
-        delete m;
-        e->err = who + "the model of this width does not take the engine's NUM_TASK";
-        return rc;
-    }
-    delete e->model;  // (the stream is idle: begin_change)
-    e->model = m;
-    e->emb_dim = emb_dim;
-    e->free_batch();  // h, scratch and the outputs are sized by the width: the batch has to be set again, and so have the weights
-    e->batch_ready = false;
-    e->ran = false;
-    e->force_exact = false;
-    e->db.tap = nullptr;
-    for (const Output& o : kOutputs) {
-        (e->*o.slot).user = (e->*o.slot).last = nullptr;
-        e->db.*o.field = nullptr;
-    }
-    return FLOWGNN_OK;
-}
-
-int flowgnn_set_emb_dim(flowgnn_engine* e, int emb_dim) {
-    if (!e) return FLOWGNN_ERR_ARG;
-    if (emb_dim != FLOWGNN_EMB_DIM_REFERENCE && emb_dim != FLOWGNN_EMB_DIM_OGB) {
-        e->err = "flowgnn_set_emb_dim: the widths are FLOWGNN_EMB_DIM_REFERENCE (100) and FLOWGNN_EMB_DIM_OGB (300)";
-        return FLOWGNN_ERR_ARG;
-    }
-    if (e->model_id != FLOWGNN_MODEL_GIN) {
-        e->err = "flowgnn_set_emb_dim: the width is a choice of FLOWGNN_MODEL_GIN alone in this call (GIN-VN and the other models have the reference's width only; "
-                 "GCN's width goes through flowgnn_set_model_emb_dim)";
-        return FLOWGNN_ERR_UNSUPPORTED;
-    }
-    return set_width(e, "flowgnn_set_emb_dim", emb_dim);
-}
-
-// The call that names no model: GIN exactly as flowgnn_set_emb_dim (the same code path, state and bits), GCN between GcnModel and
-// gcn_wide.hip's model.
-int flowgnn_set_model_emb_dim(flowgnn_engine* e, int emb_dim) {
-    if (!e) return FLOWGNN_ERR_ARG;
-    if (emb_dim != FLOWGNN_EMB_DIM_REFERENCE && emb_dim != FLOWGNN_EMB_DIM_OGB) {
-        e->err = "flowgnn_set_model_emb_dim: the widths are FLOWGNN_EMB_DIM_REFERENCE (100) and FLOWGNN_EMB_DIM_OGB (300)";
-        return FLOWGNN_ERR_ARG;
-    }
-    if (e->model_id != FLOWGNN_MODEL_GIN && e->model_id != FLOWGNN_MODEL_GCN) {
-        e->err = "flowgnn_set_model_emb_dim: the width is a choice of FLOWGNN_MODEL_GIN and FLOWGNN_MODEL_GCN (the other models have the reference's width only)";
-        return FLOWGNN_ERR_UNSUPPORTED;
-    }
-    return set_width(e, e->model_id == FLOWGNN_MODEL_GIN ? "flowgnn_set_emb_dim" : "flowgnn_set_model_emb_dim", emb_dim);
-}
-
-int flowgnn_emb_dim(const flowgnn_engine* e) { return e ? e->emb_dim : -1; }
-
-// flowgnn_set_numeric_mode and flowgnn_set_numeric_mode_dim at the engine's width.  with_dim: the call carried the width -- what lets
-// a GIN engine at width 300 take FLOWGNN_NUMERIC_F16 (gin_wide_f16.hip); the call without it keeps refusing
-// every mode but F32 there.  At width 100 the two are one.  model_form: the call was flowgnn_set_model_numeric_mode_dim on a GCN engine --
-// what lets a GCN engine at width 300 take FLOWGNN_NUMERIC_F16 (gcn_wide_f16.hip); flowgnn_set_numeric_mode_dim
-// keeps refusing it there.
-// pna_form: the call was flowgnn_set_model_numeric_mode_dim(e, FLOWGNN_EMB_DIM_PNA, ..) on a PNA engine -- the one way to PNA's
-// FLOWGNN_NUMERIC_F16 (pna_f16.hip); every other call keeps refusing it there.
-// dgn_form: the call was flowgnn_set_model_numeric_mode(e, FLOWGNN_MODEL_DGN, ..) on a DGN engine -- the one way to DGN's
-// FLOWGNN_NUMERIC_F16 (dgn_f16.hip); every other call keeps refusing it there.
-static int set_numeric_mode(flowgnn_engine* e, int mode, bool with_dim, bool model_form = false, bool pna_form = false, bool dgn_form = false) {
-    if (mode == FLOWGNN_NUMERIC_F16 && e->model_id == FLOWGNN_MODEL_DGN && !dgn_form) {
-        e->err = "flowgnn_set_numeric_mode: DGN's f16 mode goes through the call that names the model: "
-                 "flowgnn_set_model_numeric_mode(e, FLOWGNN_MODEL_DGN, FLOWGNN_NUMERIC_F16)";
-        return FLOWGNN_ERR_UNSUPPORTED;
-    }
-    if (mode == FLOWGNN_NUMERIC_F16 && e->model_id == FLOWGNN_MODEL_PNA && !pna_form) {
-        e->err = "flowgnn_set_numeric_mode: PNA's f16 mode goes through the call that carries the model, with the model's true width: "
-                 "flowgnn_set_model_numeric_mode_dim(e, FLOWGNN_EMB_DIM_PNA (80), FLOWGNN_NUMERIC_F16)";
-        return FLOWGNN_ERR_UNSUPPORTED;
-    }
-    for (const Output& o : kOutputs)
-        if (mode == FLOWGNN_NUMERIC_Q6_10 && o.no_fixed_point && is_on(e, o)) {
-            e->err = o.no_fixed_point;
-            return FLOWGNN_ERR_UNSUPPORTED;
-        }
-    if (mode != FLOWGNN_NUMERIC_F32 && off_default_width(e)) {
-        if (!with_dim) {
-            e->err = "flowgnn_set_numeric_mode: the engine's width is 300 (flowgnn_set_emb_dim / flowgnn_set_model_emb_dim), which has no fixed-point "
-                     "kernels; GIN's f16 mode at that width goes through flowgnn_set_numeric_mode_dim, GCN's through flowgnn_set_model_numeric_mode_dim";
-            return FLOWGNN_ERR_UNSUPPORTED;
-        }
-        if (model_form && mode != FLOWGNN_NUMERIC_F16) {
-            e->err = "flowgnn_set_model_numeric_mode_dim: at width 300 the modes are FLOWGNN_NUMERIC_F32 and FLOWGNN_NUMERIC_F16; there are no "
-                     "fixed-point kernels at that width";
-            return FLOWGNN_ERR_UNSUPPORTED;
-        }
-        if (!model_form && (mode != FLOWGNN_NUMERIC_F16 || e->model_id != FLOWGNN_MODEL_GIN)) {
-            e->err = "flowgnn_set_numeric_mode_dim: at width 300 the modes are FLOWGNN_NUMERIC_F32 and, for FLOWGNN_MODEL_GIN, FLOWGNN_NUMERIC_F16; "
-                     "there are no fixed-point kernels at that width, and GCN's f16 mode at that width goes through "
-                     "flowgnn_set_model_numeric_mode_dim";
-            return FLOWGNN_ERR_UNSUPPORTED;
-        }
-    }
-    if (mode == FLOWGNN_NUMERIC_Q6_10 && e->pooling != FLOWGNN_POOL_MEAN) {
-        e->err = "flowgnn_set_numeric_mode: the pooling is not the mean (flowgnn_set_pooling), and the fixed-point readout is the reference's mean";
-        return FLOWGNN_ERR_UNSUPPORTED;
-    }
-    if (mode == FLOWGNN_NUMERIC_Q6_10 && e->gin_eps_on) {
-        e->err = "flowgnn_set_numeric_mode: a trained eps is on (flowgnn_set_gin_eps), and the fixed-point arithmetic is the reference's, which has no eps";
-        return FLOWGNN_ERR_UNSUPPORTED;
-    }
-    if (mode == FLOWGNN_NUMERIC_Q6_10 && e->ogb_vn_on) {
-        e->err = "flowgnn_set_numeric_mode: OGB's virtual node is on (flowgnn_set_ogb_virtual_node / flowgnn_set_gcn_virtual_node), and the fixed-point arithmetic is the reference's, which has no such model";
-        return FLOWGNN_ERR_UNSUPPORTED;
-    }
-    e->drop_graph();
-    const int rc = e->model->set_numeric_mode(mode);
-    if (!rc) e->numeric_mode = mode;
-    if (rc) e->err = "flowgnn_set_numeric_mode: unknown mode, a mode this model does not have (f16: GIN / GIN-VN only), or the fixed-point "
-                     "readout is single-task and NUM_TASK != 1";
-    return rc;
-}
-
-int flowgnn_set_numeric_mode(flowgnn_engine* e, int mode) {
-    if (!e) return FLOWGNN_ERR_ARG;
-    return set_numeric_mode(e, mode, false);
-}
-
-// The call that carries the width: emb_dim 100 IS the call above (the same state, kernels and bits); 300 reaches gin_wide_f16.hip's
-// kernels on a GIN engine.  emb_dim must be the engine's width.
-static int set_numeric_mode_dim(flowgnn_engine* e, const char* fn, int emb_dim, int mode, bool model_form) {
-    const std::string who = std::string(fn) + ": ";
-    if (emb_dim != FLOWGNN_EMB_DIM_REFERENCE && emb_dim != FLOWGNN_EMB_DIM_OGB) {
-        e->err = who + "emb_dim is " + std::to_string(emb_dim) + "; the widths are FLOWGNN_EMB_DIM_REFERENCE (100) and FLOWGNN_EMB_DIM_OGB (300)";
-        if (emb_dim == FLOWGNN_EMB_DIM_PNA)
-            e->err += "; FLOWGNN_EMB_DIM_PNA (80) is a width of the model form alone, flowgnn_set_model_numeric_mode_dim on a FLOWGNN_MODEL_PNA engine";
-        return FLOWGNN_ERR_ARG;
-    }
-    if (mode != FLOWGNN_NUMERIC_F32 && mode != FLOWGNN_NUMERIC_Q6_10 && mode != FLOWGNN_NUMERIC_F16) {
-        e->err = who + "mode is " + std::to_string(mode) + "; the modes are FLOWGNN_NUMERIC_F32 (0), FLOWGNN_NUMERIC_Q6_10 (1) and FLOWGNN_NUMERIC_F16 (2)";
-        return FLOWGNN_ERR_ARG;
-    }
-    // (flowgnn_emb_dim is the model's own figure for the models without a choice of width -- GAT's 16; their width here is 100)
-    const int width = off_default_width(e) ? e->emb_dim : FLOWGNN_EMB_DIM_REFERENCE;
-    if (emb_dim != width) {
-        e->err = who + "emb_dim is " + std::to_string(emb_dim) + " and the engine's width is " + std::to_string(width) +
-                 " (flowgnn_set_emb_dim / flowgnn_set_model_emb_dim)";
-        return FLOWGNN_ERR_ARG;
-    }
-    return set_numeric_mode(e, mode, true, model_form);
-}
-
-int flowgnn_set_numeric_mode_dim(flowgnn_engine* e, int emb_dim, int mode) {
-    if (!e) return FLOWGNN_ERR_ARG;
-    return set_numeric_mode_dim(e, "flowgnn_set_numeric_mode_dim", emb_dim, mode, false);
-}
-
-// The call that names no model, as flowgnn_set_model_emb_dim is for the width: on a GCN engine at width 300 it reaches
-// gcn_wide_f16.hip's kernels; on every other engine, and at width 100, it is the call above.
-int flowgnn_set_model_numeric_mode_dim(flowgnn_engine* e, int emb_dim, int mode) {
-    if (!e) return FLOWGNN_ERR_ARG;
-    if (e->model_id == FLOWGNN_MODEL_PNA && emb_dim == FLOWGNN_EMB_DIM_PNA) {  // PNA at its true width: F32, Q6_10 (the plain call's), F16
-        if (mode != FLOWGNN_NUMERIC_F32 && mode != FLOWGNN_NUMERIC_Q6_10 && mode != FLOWGNN_NUMERIC_F16) {
-            e->err = "flowgnn_set_model_numeric_mode_dim: mode is " + std::to_string(mode) +
-                     "; the modes are FLOWGNN_NUMERIC_F32 (0), FLOWGNN_NUMERIC_Q6_10 (1) and FLOWGNN_NUMERIC_F16 (2)";
-            return FLOWGNN_ERR_ARG;
-        }
-        return set_numeric_mode(e, mode, true, true, true);
-    }
-    if (e->model_id != FLOWGNN_MODEL_GCN) return flowgnn_set_numeric_mode_dim(e, emb_dim, mode);
-    return set_numeric_mode_dim(e, "flowgnn_set_model_numeric_mode_dim", emb_dim, mode, true);
-}
-
-// The call that names the model: one call that reaches every mode any engine has.  On a DGN engine (whose width is the reference's 100,
-// so no width of its own to enter through) it takes F32, Q6_10 and F16 -- dgn_f16.hip's kernels; on every other
-// engine it is flowgnn_set_model_numeric_mode_dim at that engine's own current width.
-int flowgnn_set_model_numeric_mode(flowgnn_engine* e, int model_id, int mode) {
-    if (!e) return FLOWGNN_ERR_ARG;
-    static const char* const names[] = {"FLOWGNN_MODEL_GIN", "FLOWGNN_MODEL_GIN_VN", "FLOWGNN_MODEL_GCN", "FLOWGNN_MODEL_GAT", "FLOWGNN_MODEL_PNA", "FLOWGNN_MODEL_DGN"};
-    auto name = [&](int m) { return std::to_string(m) + " (" + ((m >= 0 && m < 6) ? names[m] : "no model") + ")"; };
-    if (model_id != e->model_id) {
-        e->err = "flowgnn_set_model_numeric_mode: model_id is " + name(model_id) + " and the engine's model is " + name(e->model_id);
-        return FLOWGNN_ERR_ARG;
-    }
-    if (e->model_id == FLOWGNN_MODEL_DGN) {
-        if (mode != FLOWGNN_NUMERIC_F32 && mode != FLOWGNN_NUMERIC_Q6_10 && mode != FLOWGNN_NUMERIC_F16) {
-            e->err = "flowgnn_set_model_numeric_mode: mode is " + std::to_string(mode) +
-                     "; the modes are FLOWGNN_NUMERIC_F32 (0), FLOWGNN_NUMERIC_Q6_10 (1) and FLOWGNN_NUMERIC_F16 (2)";
-            return FLOWGNN_ERR_ARG;
-        }
-        return set_numeric_mode(e, mode, true, true, false, true);
-    }
-    // (flowgnn_emb_dim is the model's own figure for the models without a choice of width -- GAT's 16; their width for these calls is 100)
-    const int width = e->model_id == FLOWGNN_MODEL_PNA ? FLOWGNN_EMB_DIM_PNA : off_default_width(e) ? e->emb_dim : FLOWGNN_EMB_DIM_REFERENCE;
-    return flowgnn_set_model_numeric_mode_dim(e, width, mode);
-}
-
-int flowgnn_set_pooling(flowgnn_engine* e, int mode) {
-    if (!e) return FLOWGNN_ERR_ARG;
-    if (mode != FLOWGNN_POOL_MEAN && mode != FLOWGNN_POOL_SUM && mode != FLOWGNN_POOL_MAX) {
-        e->err = "flowgnn_set_pooling: the modes are FLOWGNN_POOL_MEAN (0), FLOWGNN_POOL_SUM (1) and FLOWGNN_POOL_MAX (2)";
-        return FLOWGNN_ERR_ARG;
-    }
-    if (mode != FLOWGNN_POOL_MEAN && (e->model_id == FLOWGNN_MODEL_PNA || e->model_id == FLOWGNN_MODEL_DGN)) {
-        e->err = "flowgnn_set_pooling: PNA and DGN read the pooled vector through an MLP head that was trained on the mean";
-        return FLOWGNN_ERR_UNSUPPORTED;
-    }
-    if (mode != FLOWGNN_POOL_MEAN && e->numeric_mode == FLOWGNN_NUMERIC_Q6_10) {
-        e->err = "flowgnn_set_pooling: the fixed-point readout (FLOWGNN_NUMERIC_Q6_10) is the reference's mean";
-        return FLOWGNN_ERR_UNSUPPORTED;
-    }
-    if (mode != FLOWGNN_POOL_MEAN && e->nlog_on) {
-        e->err = "flowgnn_set_pooling: node logits are on, and they are the terms whose mean is the logit";
-        return FLOWGNN_ERR_UNSUPPORTED;
-    }
-    if (mode != FLOWGNN_POOL_MEAN && e->attn_pool_on) {
-        e->err = "flowgnn_set_pooling: the attention pooling is on (flowgnn_set_attention_pooling), a readout of its own; beside it the mean is the only accepted value";
-        return FLOWGNN_ERR_UNSUPPORTED;
-    }
-    if (mode != FLOWGNN_POOL_MEAN && e->s2s_steps) {
-        e->err = "flowgnn_set_pooling: the set2set pooling is on (flowgnn_set_set2set_pooling), a readout of its own; beside it the mean is the only accepted value";
-        return FLOWGNN_ERR_UNSUPPORTED;
-    }
-    ENGINE_TRY(e, use_device(e));
-    e->drop_graph();  // a recorded launch sequence is that of the other mode
-    e->pooling = mode;
-    e->db.pooling = mode;  // (launches are stream-ordered: the mode matters to those enqueued after this call)
-    return FLOWGNN_OK;
-}
-
-int flowgnn_pooling(const flowgnn_engine* e) { return e ? e->pooling : -1; }
-
-int flowgnn_set_gin_eps(flowgnn_engine* e, const float* eps) {
-    if (!e) return FLOWGNN_ERR_ARG;
-    if (e->model_id != FLOWGNN_MODEL_GIN && e->model_id != FLOWGNN_MODEL_GIN_VN) {
-        e->err = "flowgnn_set_gin_eps: only GIN and GIN-VN have the (1 + eps) self term";
-        return FLOWGNN_ERR_UNSUPPORTED;
-    }
-    if (eps) {
-        for (int l = 0; l < 5; l++)
-            if (!std::isfinite(eps[l])) {
-                e->err = "flowgnn_set_gin_eps: eps[" + std::to_string(l) + "] is not finite";
-                return FLOWGNN_ERR_ARG;
-            }
-        if (e->numeric_mode == FLOWGNN_NUMERIC_Q6_10) {
-            e->err = "flowgnn_set_gin_eps: the fixed-point arithmetic (FLOWGNN_NUMERIC_Q6_10) is the reference's, which has no eps";
-            return FLOWGNN_ERR_UNSUPPORTED;
-        }
-    }
-    ENGINE_TRY(e, use_device(e));
-    e->drop_graph();  // a recorded launch sequence is that of the other state (or carries the other values in its argument blocks)
-    e->gin_eps_on = eps != nullptr;
-    e->db.gin_eps_on = e->gin_eps_on;  // (launches are stream-ordered: the values matter to those enqueued after this call)
-    for (int l = 0; l < 5; l++) {
-        e->gin_eps[l] = eps ? eps[l] : 0.0f;
-        e->db.gin_self_scale[l] = (float)(1.0f + e->gin_eps[l]);
-    }
-    return FLOWGNN_OK;
-}
-
-int flowgnn_gin_eps(const flowgnn_engine* e, float* eps_out) {
-    if (!e) return -1;
-    if (eps_out)
-        for (int l = 0; l < 5; l++) eps_out[l] = e->gin_eps[l];
-    return e->gin_eps_on ? 1 : 0;
-}
-
-// flowgnn_set_ogb_virtual_node (GIN) and flowgnn_set_gcn_virtual_node (GCN): the same five tensors, the same checks and the same engine
-// state -- an engine is one model, so one of the two calls is refused on it.  `fn`: the caller.  `dim`: the tensors' width D (hidden
-// width 2 D) -- 100 in the two calls without a width argument.  The device form is the model object's (Model::ogb_vn_pack): gin_ogbvn.h's
-// at width 100, gin_wide.hip's own at 300.
-static int set_virtual_node(flowgnn_engine* e, const char* fn, const float* vn_embedding, const float* w1, const float* b1, const float* w2,
-                            const float* b2, int dim) {
-    const std::string who = std::string(fn) + ": ";
-    const float* const t[5] = {vn_embedding, w1, b1, w2, b2};
-    const size_t D = (size_t)dim, H = 2 * D;
-    const size_t count[5] = {D, (size_t)FLOWGNN_OGB_VN_LAYERS * H * D, (size_t)FLOWGNN_OGB_VN_LAYERS * H, (size_t)FLOWGNN_OGB_VN_LAYERS * D * H,
-                             (size_t)FLOWGNN_OGB_VN_LAYERS * D};
-    int given = 0;
-    for (int i = 0; i < 5; i++) given += t[i] != nullptr;
-    if (given != 0 && given != 5) {
-        e->err = who + "some of the five tensors are NULL and some are not (all five: on, all NULL: off)";
-        return FLOWGNN_ERR_ARG;
-    }
-    const bool on = given == 5;
-    if (on) {
-        static const char* const names[5] = {"vn_embedding", "w1", "b1", "w2", "b2"};
-        for (int i = 0; i < 5; i++)
-            for (size_t k = 0; k < count[i]; k++)
-                if (!std::isfinite(t[i][k])) {
-                    e->err = who + names[i] + "[" + std::to_string(k) + "] is not finite";
-                    return FLOWGNN_ERR_ARG;
-                }
-        if (e->numeric_mode == FLOWGNN_NUMERIC_Q6_10) {
-            e->err = who + "the fixed-point arithmetic (FLOWGNN_NUMERIC_Q6_10) is the reference's, which has no such model";
-            return FLOWGNN_ERR_UNSUPPORTED;
-        }
-        // (the model object has this width and a device form for the tensors; refused before anything changes)
-        if (e->model->emb_dim() != dim || e->model->ogb_vn_blob_bytes() == 0) {
-            e->err = who + "this model has no such kernel";
-            return FLOWGNN_ERR_UNSUPPORTED;
-        }
-    }
-    ENGINE_TRY(e, begin_change(e));  // (an idle stream: a run in flight may still read the tensors this call replaces)
-    if (on) {
-        std::vector<float> packed(e->model->ogb_vn_blob_bytes() / sizeof(float));  // (floats: the parts are read as float4 pieces)
-        e->model->ogb_vn_pack(vn_embedding, w1, b1, w2, b2, packed.data());
-        EHIP_TRY(e, e->ogb_vn.reserve(sizeof(float) * packed.size(), false));
-        EHIP_TRY(e, hipMemcpy(e->ogb_vn.p, packed.data(), sizeof(float) * packed.size(), hipMemcpyHostToDevice));
-    }
-    const int rc = e->model_id == FLOWGNN_MODEL_GCN ? e->model->set_gcn_virtual_node(on ? vn_embedding : nullptr) : e->model->set_ogb_virtual_node(on);
-    if (rc) {
-        e->err = who + "this model has no such kernel";
-        return rc;
-    }
-    e->ogb_vn_on = on;
-    e->db.ogb_vn = on ? (const float*)e->ogb_vn.p : nullptr;  // (launches are stream-ordered: it matters to those enqueued after this call)
-    return FLOWGNN_OK;
-}
-
-// What tells GIN's pair of calls from GCN's: the checks in front of set_virtual_node are the same, in the same order.
-struct VnCalls {
-    int model_id;                // the one model the calls serve
-    const char* fn[2];           // the call without a width, and the one that carries it
-    const char* width_call;      // what sets that model's width
-    const char* wrong_model[2];  // the refusal on an engine of another model, per call ...
-    const char* gcn_hint;        // ... and what a GCN engine is told besides
-};
-static const VnCalls kVnGin = {FLOWGNN_MODEL_GIN,
-                               {"flowgnn_set_ogb_virtual_node", "flowgnn_set_ogb_virtual_node_dim"},
-                               "flowgnn_set_emb_dim",
-                               {": OGB's virtual node exists for GIN only (GIN-VN is the reference's augmentation, a different model)",
-                                ": OGB's virtual node exists for GIN only (GIN-VN is the reference's augmentation, a different model)"},
-                               "; GCN has a call of its own, flowgnn_set_gcn_virtual_node"};
-static const VnCalls kVnGcn = {FLOWGNN_MODEL_GCN,
-                               {"flowgnn_set_gcn_virtual_node", "flowgnn_set_gcn_virtual_node_dim"},
-                               "flowgnn_set_model_emb_dim",
-                               {": this call is OGB's gcn-virtual, for GCN only (GIN: flowgnn_set_ogb_virtual_node)",
-                                ": this call is OGB's gcn-virtual, for GCN only (GIN: flowgnn_set_ogb_virtual_node_dim)"},
-                               ""};
-
-static int vn_wrong_model(flowgnn_engine* e, const VnCalls& c, int with_dim) {
-    e->err = std::string(c.fn[with_dim]) + c.wrong_model[with_dim];
-    if (e->model_id == FLOWGNN_MODEL_GCN) e->err += c.gcn_hint;
-    return FLOWGNN_ERR_UNSUPPORTED;
-}
-
-// the calls without a width: the tensors are 100 wide
-static int set_virtual_node_ref(flowgnn_engine* e, const VnCalls& c, const float* vn_embedding, const float* w1, const float* b1, const float* w2,
-                                const float* b2) {
-    if (!e) return FLOWGNN_ERR_ARG;
-    if (e->model_id != c.model_id) return vn_wrong_model(e, c, 0);
-    if (off_default_width(e) && (vn_embedding || w1 || b1 || w2 || b2)) {
-        e->err = std::string(c.fn[0]) + ": the engine's width is 300 (" + c.width_call + "), and the virtual node's tensors are 100 wide "
-                 "in this call; 300-wide tensors go through " + c.fn[1];
-        return FLOWGNN_ERR_UNSUPPORTED;
-    }
-    return set_virtual_node(e, c.fn[0], vn_embedding, w1, b1, w2, b2, FLOWGNN_EMB_DIM_REFERENCE);
-}
-
-// The calls that carry the width.  emb_dim 100 IS the call above (the same state, kernels and bits); 300 is gin_wide.hip's virtual node
-//  or gcn_wide.hip's (section 4.19).  All five NULL: off, whatever the engine's width (no tensor is read).
-static int set_virtual_node_dim(flowgnn_engine* e, const VnCalls& c, int emb_dim, const float* vn_embedding, const float* w1, const float* b1,
-                                const float* w2, const float* b2) {
-    if (!e) return FLOWGNN_ERR_ARG;
-    const std::string who = std::string(c.fn[1]) + ": ";
-    if (emb_dim != FLOWGNN_EMB_DIM_REFERENCE && emb_dim != FLOWGNN_EMB_DIM_OGB) {
-        e->err = who + "emb_dim is " + std::to_string(emb_dim) + "; the widths are FLOWGNN_EMB_DIM_REFERENCE (100) and FLOWGNN_EMB_DIM_OGB (300)";
-        return FLOWGNN_ERR_ARG;
-    }
-    if (e->model_id != c.model_id) return vn_wrong_model(e, c, 1);
-    if ((vn_embedding || w1 || b1 || w2 || b2) && emb_dim != e->emb_dim) {
-        e->err = who + "the tensors are " + std::to_string(emb_dim) + " wide and the engine's width is " + std::to_string(e->emb_dim) + " (" +
-                 c.width_call + ")";
-        return FLOWGNN_ERR_ARG;
-    }
-    return set_virtual_node(e, c.fn[1], vn_embedding, w1, b1, w2, b2, emb_dim);
-}
-
-int flowgnn_set_ogb_virtual_node(flowgnn_engine* e, const float* vn_embedding, const float* w1, const float* b1, const float* w2, const float* b2) {
-    return set_virtual_node_ref(e, kVnGin, vn_embedding, w1, b1, w2, b2);
-}
-
-int flowgnn_set_ogb_virtual_node_dim(flowgnn_engine* e, int emb_dim, const float* vn_embedding, const float* w1, const float* b1, const float* w2,
-                                     const float* b2) {
-    return set_virtual_node_dim(e, kVnGin, emb_dim, vn_embedding, w1, b1, w2, b2);
-}
-
-int flowgnn_set_gcn_virtual_node(flowgnn_engine* e, const float* vn_embedding, const float* w1, const float* b1, const float* w2, const float* b2) {
-    return set_virtual_node_ref(e, kVnGcn, vn_embedding, w1, b1, w2, b2);
-}
-
-int flowgnn_set_gcn_virtual_node_dim(flowgnn_engine* e, int emb_dim, const float* vn_embedding, const float* w1, const float* b1, const float* w2,
-                                     const float* b2) {
-    return set_virtual_node_dim(e, kVnGcn, emb_dim, vn_embedding, w1, b1, w2, b2);
-}
-
-int flowgnn_gcn_virtual_node(const flowgnn_engine* e) { return e ? (e->ogb_vn_on && e->model_id == FLOWGNN_MODEL_GCN ? 1 : 0) : -1; }
-
-int flowgnn_ogb_virtual_node(const flowgnn_engine* e) { return e ? (e->ogb_vn_on && e->model_id == FLOWGNN_MODEL_GIN ? 1 : 0) : -1; }
-
-// OGB's graph_pooling="attention" readout: the state handling of set_virtual_node above -- checks first, then
-// an idle stream, the tensors packed on the host into the device form of wide_attn.h, one device buffer owned by the engine.  All three
-// NULL: off, at any width and for any model.
-int flowgnn_set_attention_pooling(flowgnn_engine* e, int emb_dim, const float* w1, const float* b1, const float* w2) {
-    if (!e) return FLOWGNN_ERR_ARG;
-    const std::string who = "flowgnn_set_attention_pooling: ";
-    if (emb_dim != FLOWGNN_EMB_DIM_REFERENCE && emb_dim != FLOWGNN_EMB_DIM_OGB) {
-        e->err = who + "emb_dim is " + std::to_string(emb_dim) + "; the widths are FLOWGNN_EMB_DIM_REFERENCE (100) and FLOWGNN_EMB_DIM_OGB (300)";
-        return FLOWGNN_ERR_ARG;
-    }
-    const int given = (w1 != nullptr) + (b1 != nullptr) + (w2 != nullptr);
-    if (given != 0 && given != 3) {
-        e->err = who + "some of the three tensors are NULL and some are not (all three: on, all NULL: off)";
-        return FLOWGNN_ERR_ARG;
-    }
-    const bool on = given == 3;
-    if (on) {
-        const size_t D = (size_t)emb_dim, H = 2 * D;
-        const float* const t[3] = {w1, b1, w2};
-        const size_t count[3] = {H * D, H, H};
-        static const char* const names[3] = {"w1", "b1", "w2"};
-        for (int i = 0; i < 3; i++)
-            for (size_t k = 0; k < count[i]; k++)
-                if (!std::isfinite(t[i][k])) {
-                    e->err = who + names[i] + "[" + std::to_string(k) + "] is not finite";
-                    return FLOWGNN_ERR_ARG;
-                }
-        if (e->model_id != FLOWGNN_MODEL_GIN && e->model_id != FLOWGNN_MODEL_GCN) {
-            e->err = who + "the attention pooling exists for FLOWGNN_MODEL_GIN and FLOWGNN_MODEL_GCN only (OGB's gin, gin-virtual, gcn, gcn-virtual)";
-            return FLOWGNN_ERR_UNSUPPORTED;
-        }
-        if (emb_dim != e->emb_dim) {
-            e->err = who + "the tensors are " + std::to_string(emb_dim) + " wide and the engine's width is " + std::to_string(e->emb_dim) +
-                     " (flowgnn_set_emb_dim / flowgnn_set_model_emb_dim)";
-            return FLOWGNN_ERR_ARG;
-        }
-        if (emb_dim != FLOWGNN_EMB_DIM_OGB || fg::attn_pool_blob_bytes(emb_dim) == 0) {
-            e->err = who + "only the 300-wide models have this readout (the 100-wide graph-resident kernels fold the mean into their last layer): "
-                           "flowgnn_set_emb_dim / flowgnn_set_model_emb_dim(e, 300) first";
-            return FLOWGNN_ERR_UNSUPPORTED;
-        }
-        if (e->pooling != FLOWGNN_POOL_MEAN) {
-            e->err = who + "the pooling is not the mean (flowgnn_set_pooling), and this readout replaces the pooling: set FLOWGNN_POOL_MEAN first";
-            return FLOWGNN_ERR_UNSUPPORTED;
-        }
-        if (e->nlog_on) {
-            e->err = who + "node logits are on (flowgnn_set_node_logits), and under this readout a graph's logit is no mean of per-node terms";
-            return FLOWGNN_ERR_UNSUPPORTED;
-        }
-        if (e->s2s_steps) {
-            e->err = who + "the set2set pooling is on (flowgnn_set_set2set_pooling), and the two readouts exclude each other: turn that one off first";
-            return FLOWGNN_ERR_UNSUPPORTED;
-        }
-    }
-    ENGINE_TRY(e, begin_change(e));  // (an idle stream: a run in flight may still read the tensors this call replaces)
-    if (on) {
-        std::vector<float> packed(fg::attn_pool_blob_bytes(emb_dim) / sizeof(float));  // (floats: the parts are read as float4 pieces)
-        fg::attn_pool_blob_pack(emb_dim, w1, b1, w2, packed.data());
-        EHIP_TRY(e, e->attn_pool.reserve(sizeof(float) * packed.size(), false));
-        EHIP_TRY(e, hipMemcpy(e->attn_pool.p, packed.data(), sizeof(float) * packed.size(), hipMemcpyHostToDevice));
-    }
-    e->attn_pool_on = on;
-    e->db.attn_pool = on ? e->attn_pool.p : nullptr;  // (launches are stream-ordered: it matters to those enqueued after this call)
-    return FLOWGNN_OK;
-}
-
-int flowgnn_attention_pooling(const flowgnn_engine* e) { return e ? (e->attn_pool_on ? 1 : 0) : -1; }
-
-// OGB's graph_pooling="set2set" readout: the state handling of the attention readout above -- checks first,
-// then an idle stream, the six tensors packed on the host into the device form of wide_s2s.h, one device buffer owned by the engine.
-// All six NULL: off, at any width and for any model.
-int flowgnn_set_set2set_pooling(flowgnn_engine* e, int emb_dim, int steps, int num_tasks, const float* w_ih, const float* w_hh, const float* b_ih,
-                                const float* b_hh, const float* head_w, const float* head_b) {
-    if (!e) return FLOWGNN_ERR_ARG;
-    const std::string who = "flowgnn_set_set2set_pooling: ";
-    if (emb_dim != FLOWGNN_EMB_DIM_REFERENCE && emb_dim != FLOWGNN_EMB_DIM_OGB) {
-        e->err = who + "emb_dim is " + std::to_string(emb_dim) + "; the widths are FLOWGNN_EMB_DIM_REFERENCE (100) and FLOWGNN_EMB_DIM_OGB (300)";
-        return FLOWGNN_ERR_ARG;
-    }
-    const float* const t[6] = {w_ih, w_hh, b_ih, b_hh, head_w, head_b};
-    int given = 0;
-    for (const float* p : t) given += p != nullptr;
-    if (given != 0 && given != 6) {
-        e->err = who + "some of the six tensors are NULL and some are not (all six: on, all NULL: off)";
-        return FLOWGNN_ERR_ARG;
-    }
-    const bool on = given == 6;
-    if (on) {
-        if (steps < 1 || steps > FLOWGNN_SET2SET_MAX_STEPS) {
-            e->err = who + "steps is " + std::to_string(steps) + "; the processing steps are 1 .. " + std::to_string(FLOWGNN_SET2SET_MAX_STEPS) + " (OGB: 2)";
-            return FLOWGNN_ERR_ARG;
-        }
-        if (num_tasks < 1 || num_tasks != e->num_tasks) {
-            e->err = who + "head_w has " + std::to_string(num_tasks) + " tasks and the engine's NUM_TASK is " + std::to_string(e->num_tasks) +
-                     " (flowgnn_set_num_tasks)";
-            return FLOWGNN_ERR_ARG;
-        }
-        const size_t D = (size_t)emb_dim, T = (size_t)num_tasks;
-        const size_t count[6] = {4 * D * 2 * D, 4 * D * D, 4 * D, 4 * D, T * 2 * D, T};
-        static const char* const names[6] = {"w_ih", "w_hh", "b_ih", "b_hh", "head_w", "head_b"};
-        for (int i = 0; i < 6; i++)
-            for (size_t k = 0; k < count[i]; k++)
-                if (!std::isfinite(t[i][k])) {
-                    e->err = who + names[i] + "[" + std::to_string(k) + "] is not finite";
-                    return FLOWGNN_ERR_ARG;
-                }
-        if (e->model_id != FLOWGNN_MODEL_GIN && e->model_id != FLOWGNN_MODEL_GCN) {
-            e->err = who + "the set2set pooling exists for FLOWGNN_MODEL_GIN and FLOWGNN_MODEL_GCN only (OGB's gin, gin-virtual, gcn, gcn-virtual)";
-            return FLOWGNN_ERR_UNSUPPORTED;
-        }
-        if (emb_dim != e->emb_dim) {
-            e->err = who + "the tensors are " + std::to_string(emb_dim) + " wide and the engine's width is " + std::to_string(e->emb_dim) +
-                     " (flowgnn_set_emb_dim / flowgnn_set_model_emb_dim)";
-            return FLOWGNN_ERR_ARG;
-        }
-        if (emb_dim != FLOWGNN_EMB_DIM_OGB || fg::s2s_blob_bytes(emb_dim, num_tasks) == 0) {
-            e->err = who + "only the 300-wide models have this readout (the 100-wide graph-resident kernels fold the mean into their last layer): "
-                           "flowgnn_set_emb_dim / flowgnn_set_model_emb_dim(e, 300) first";
-            return FLOWGNN_ERR_UNSUPPORTED;
-        }
-        if (e->pooling != FLOWGNN_POOL_MEAN) {
-            e->err = who + "the pooling is not the mean (flowgnn_set_pooling), and this readout replaces the pooling: set FLOWGNN_POOL_MEAN first";
-            return FLOWGNN_ERR_UNSUPPORTED;
-        }
-        if (e->nlog_on) {
-            e->err = who + "node logits are on (flowgnn_set_node_logits), and under this readout a graph's logit is no mean of per-node terms";
-            return FLOWGNN_ERR_UNSUPPORTED;
-        }
-        if (e->attn_pool_on) {
-            e->err = who + "the attention pooling is on (flowgnn_set_attention_pooling), and the two readouts exclude each other: turn that one off first";
-            return FLOWGNN_ERR_UNSUPPORTED;
-        }
-        if (e->emb_on) {
-            e->err = who + "graph embeddings are on (flowgnn_set_embeddings), and the vector this readout's head reads is " + std::to_string(2 * emb_dim) +
-                     " wide where every embeddings buffer is " + std::to_string(emb_dim) + " wide";
-            return FLOWGNN_ERR_UNSUPPORTED;
-        }
-    }
-    ENGINE_TRY(e, begin_change(e));  // (an idle stream: a run in flight may still read the tensors this call replaces)
-    if (on) {
-        std::vector<float> packed(fg::s2s_blob_bytes(emb_dim, num_tasks) / sizeof(float));  // (floats: the parts are read as float4 pieces)
-        fg::s2s_blob_pack(emb_dim, num_tasks, w_ih, w_hh, b_ih, b_hh, head_w, head_b, packed.data());
-        EHIP_TRY(e, e->s2s.reserve(sizeof(float) * packed.size(), false));
-        EHIP_TRY(e, hipMemcpy(e->s2s.p, packed.data(), sizeof(float) * packed.size(), hipMemcpyHostToDevice));
-    }
-    e->s2s_steps = on ? steps : 0;
-    e->db.s2s = on ? e->s2s.p : nullptr;  // (launches are stream-ordered: it matters to those enqueued after this call)
-    e->db.s2s_steps = e->s2s_steps;
-    return FLOWGNN_OK;
-}
-
-int flowgnn_set2set_pooling(const flowgnn_engine* e) { return e ? e->s2s_steps : -1; }
-
-// OGB's JK="sum" and residual=True at width 300: GIN and, through the model form of the call, GCN (section
-// 4.25).  No tensors: the setting is two integers of the engine's, like the pooling mode, and db.jk / db.residual carry it to
-// GinWideModel::forward / GcnWideModel::forward.  (FLOWGNN_JK_LAST, 0) is the default state and is accepted wherever a handle is valid.
-// `fn`: the caller.  model_form: flowgnn_set_model_jk_residual, which a GCN engine accepts; on a GIN engine the two calls are one.
-static int set_jk_residual(flowgnn_engine* e, const char* fn, bool model_form, int emb_dim, int jk, int residual) {
-    const std::string who = std::string(fn) + ": ";
-    if (jk != FLOWGNN_JK_LAST && jk != FLOWGNN_JK_SUM) {
-        e->err = who + "jk is " + std::to_string(jk) + "; the values are FLOWGNN_JK_LAST (0) and FLOWGNN_JK_SUM (1)";
-        return FLOWGNN_ERR_ARG;
-    }
-    if (residual != 0 && residual != 1) {
-        e->err = who + "residual is " + std::to_string(residual) + "; the values are 0 (off) and 1 (on)";
-        return FLOWGNN_ERR_ARG;
-    }
-    if (emb_dim != FLOWGNN_EMB_DIM_REFERENCE && emb_dim != FLOWGNN_EMB_DIM_OGB) {
-        e->err = who + "emb_dim is " + std::to_string(emb_dim) + "; the widths are FLOWGNN_EMB_DIM_REFERENCE (100) and FLOWGNN_EMB_DIM_OGB (300)";
-        return FLOWGNN_ERR_ARG;
-    }
-    if (jk != FLOWGNN_JK_LAST || residual) {
-        const bool gcn = e->model_id == FLOWGNN_MODEL_GCN;
-        if (gcn && !model_form) {
-            e->err = who + "GCN's rows in HBM are post-linear (W_l a_l + b_l, not h_l), so a residual needs a second row stream through its layer "
-                           "kernel: that form does not exist yet (FLOWGNN_MODEL_GIN only) under this call -- it is "
-                           "flowgnn_set_model_jk_residual that carries it for FLOWGNN_MODEL_GCN at width 300";
-            return FLOWGNN_ERR_UNSUPPORTED;
-        }
-        if (!gcn && e->model_id != FLOWGNN_MODEL_GIN) {
-            e->err = who + (model_form ? "JK sum and the residual exist for FLOWGNN_MODEL_GIN and FLOWGNN_MODEL_GCN only (OGB's gin, gin-virtual, gcn "
-                                         "and gcn-virtual at width 300)"
-                                       : "JK sum and the residual exist for FLOWGNN_MODEL_GIN only (OGB's gin and gin-virtual at width 300)");
-            return FLOWGNN_ERR_UNSUPPORTED;
-        }
-        if (emb_dim != e->emb_dim) {
-            e->err = who + "emb_dim is " + std::to_string(emb_dim) + " and the engine's width is " + std::to_string(e->emb_dim) +
-                     " (flowgnn_set_emb_dim / flowgnn_set_model_emb_dim)";
-            return FLOWGNN_ERR_ARG;
-        }
-        if (emb_dim != FLOWGNN_EMB_DIM_OGB) {
-            if (gcn)
-                e->err = who + "only the 300-wide GCN has these instances (the 100-wide graph-resident kernels and the 100-wide per-layer path have "
-                               "none): flowgnn_set_model_emb_dim(e, 300) first";
-            else
-                e->err = who + "only the 300-wide GIN has these instances (the 100-wide graph-resident kernels and the 100-wide per-layer path have "
-                               "none): flowgnn_set_emb_dim(e, 300) first";
-            return FLOWGNN_ERR_UNSUPPORTED;
-        }
-    }
-    ENGINE_TRY(e, use_device(e));
-    e->drop_graph();  // a recorded launch sequence is that of the other setting
-    e->jk = jk;
-    e->residual = residual;
-    e->db.jk = jk;  // (launches are stream-ordered: the setting matters to those enqueued after this call)
-    e->db.residual = residual;
-    return FLOWGNN_OK;
-}
-
-int flowgnn_set_jk_residual(flowgnn_engine* e, int emb_dim, int jk, int residual) {
-    if (!e) return FLOWGNN_ERR_ARG;
-    return set_jk_residual(e, "flowgnn_set_jk_residual", false, emb_dim, jk, residual);
-}
-
-int flowgnn_set_model_jk_residual(flowgnn_engine* e, int emb_dim, int jk, int residual) {
-    if (!e) return FLOWGNN_ERR_ARG;
-    return set_jk_residual(e, "flowgnn_set_model_jk_residual", true, emb_dim, jk, residual);
-}
-
-int flowgnn_jk_residual(const flowgnn_engine* e, int* jk_out, int* residual_out) {
-    if (!e) return -1;
-    if (jk_out) *jk_out = e->jk;
-    if (residual_out) *residual_out = e->residual;
-    return (e->jk != FLOWGNN_JK_LAST || e->residual) ? 1 : 0;
-}
 
 int flowgnn_set_option(flowgnn_engine* e, const char* key, double value) {
     if (!e || !key) return FLOWGNN_ERR_ARG;

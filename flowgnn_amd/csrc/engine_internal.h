@@ -1,4 +1,7 @@
-// engine_internal.h -- what engine.hip, group.hip and entry.hip share beyond the C ABI of include/flowgnn.h.
+// engine_internal.h -- what engine.hip, engine_config.hip, group.hip and entry.hip share beyond the C ABI of include/flowgnn.h: the
+// engine and group objects, the buffer helper and the slot type of the optional outputs, the macros that carry a failure's text to the
+// engine, the list of the optional outputs (kOutputs), and the few functions of engine.hip that the other files call (for
+// engine_config.hip: use_device, begin_change).
 #pragma once
 #include "common.h"
 #include "../../include/flowgnn.h"
@@ -41,7 +44,7 @@ struct GrowBuf {
 // off by default, and the DeviceBatch pointer it feeds is null then, so every forward is the one it was; `own` is allocated when
 // first needed, to one batch's size, and outlives the batch; `user` is the caller's buffer (flowgnn_set_*_buffer), which
 // flowgnn_set_batch forgets; `last` is where the last flowgnn_run put the result (null: it ran with the output off) -- what a get
-// copies and the *_device calls return.  engine.hip: `place` and the list kOutputs.
+// copies and the *_device calls return.  engine.hip: `place`; the list kOutputs is below.
 struct OutSlot {
     GrowBuf own;
     float* user = nullptr;
@@ -149,6 +152,40 @@ struct flowgnn_engine {
         capG = capN = capE = 0;
     }
 };
+
+// ---- engine.hip, for engine_config.hip
+int use_device(flowgnn_engine* e);
+// what every call that changes what the launched kernels read starts with: the engine's device, no recorded launch sequence, an idle stream
+int begin_change(flowgnn_engine* e);
+// the engine is GIN or GCN at width 300 (flowgnn_emb_dim is the model's own figure otherwise: 100, GAT's 16, PNA's 80)
+inline bool off_default_width(const flowgnn_engine* e) { return e->emb_dim != flowgnn_embedding_dim(e->model_id); }
+
+// The optional per-run outputs (fg::OutSlot above), in ONE list: everything that treats them alike walks it.  (static: a list with
+// external linkage would be compiled for the device as well, where the functions it points to do not exist.)
+struct Output {
+    fg::OutSlot flowgnn_engine::*slot;
+    float* fg::DeviceBatch::*field;           // the pointer of the forward's DeviceBatch that the slot feeds
+    bool flowgnn_engine::*on;                 // its switch (null: attn_mask, the switch of both attention slots)
+    size_t (*floats)(const flowgnn_engine*);  // what the resident batch needs of it
+    const char *noun, *setter;                // for the texts of its get and *_device calls
+    const char* no_fixed_point;               // flowgnn_set_numeric_mode's refusal while it is on (null: the row above has said it)
+};
+inline size_t emb_dim_of(const flowgnn_engine* e) { return (size_t)e->emb_dim; }  // the ENGINE's width (flowgnn_set_emb_dim), not the model's default
+inline size_t attn_layers(const flowgnn_engine* e) { return (size_t)__builtin_popcount((unsigned)e->attn_mask); }
+enum { OUT_EMB, OUT_NEMB, OUT_NLOG, OUT_ATTN_E, OUT_ATTN_S };
+static const Output kOutputs[] = {
+    {&flowgnn_engine::emb, &fg::DeviceBatch::emb, &flowgnn_engine::emb_on, [](const flowgnn_engine* e) { return (size_t)e->G * emb_dim_of(e); },
+     "embeddings", "flowgnn_set_embeddings", "flowgnn_set_numeric_mode: graph embeddings are on, and there are no fixed-point embeddings"},
+    {&flowgnn_engine::nemb, &fg::DeviceBatch::node_emb, &flowgnn_engine::nemb_on, [](const flowgnn_engine* e) { return (size_t)e->N * emb_dim_of(e); },
+     "node embeddings", "flowgnn_set_node_embeddings", "flowgnn_set_numeric_mode: node embeddings are on, and there are no fixed-point node embeddings"},
+    {&flowgnn_engine::nlog, &fg::DeviceBatch::node_logits, &flowgnn_engine::nlog_on, [](const flowgnn_engine* e) { return (size_t)e->N * (size_t)e->num_tasks; },
+     "node logits", "flowgnn_set_node_logits", "flowgnn_set_numeric_mode: node logits are on, and there are no fixed-point node logits"},
+    {&flowgnn_engine::attn_e, &fg::DeviceBatch::attn_edge, nullptr, [](const flowgnn_engine* e) { return attn_layers(e) * (size_t)e->E * 4; },
+     "attention", "flowgnn_set_attention", "flowgnn_set_numeric_mode: attention is on, and there are no fixed-point attention coefficients"},
+    {&flowgnn_engine::attn_s, &fg::DeviceBatch::attn_self, nullptr, [](const flowgnn_engine* e) { return attn_layers(e) * (size_t)e->N * 4; },
+     "attention", "flowgnn_set_attention", nullptr},
+};
+inline bool is_on(const flowgnn_engine* e, const Output& o) { return o.on ? e->*o.on : e->attn_mask != 0; }
 
 #define ENGINE_TRY(e, expr)                                     \
     do {                                                        \

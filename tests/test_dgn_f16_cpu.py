@@ -215,14 +215,20 @@ def test_null_handles_are_argument_errors_and_the_bindings_declare_the_calls():
 
 
 def test_engine_source_keeps_the_three_old_refusals_and_names_the_new_call():
-    src = open(os.path.join(ROOT, "flowgnn_amd", "csrc", "engine.hip")).read()
-    m = re.search(r"if \(mode == FLOWGNN_NUMERIC_F16 && e->model_id == FLOWGNN_MODEL_DGN && !dgn_form\) \{(.*?)\}", src, re.S)
-    assert m and "flowgnn_set_model_numeric_mode(e, FLOWGNN_MODEL_DGN, FLOWGNN_NUMERIC_F16)" in m.group(1) and "FLOWGNN_ERR_UNSUPPORTED" in m.group(1)
+    src = open(os.path.join(ROOT, "flowgnn_amd", "csrc", "engine_config.hip")).read()
+    # on a DGN engine only the route of the call that names the model reaches f16 ...
+    assert re.search(r"case FLOWGNN_MODEL_DGN: return route == ModeRoute::ModelNumericMode;", src)
+    # ... and every other route is refused, FLOWGNN_ERR_UNSUPPORTED, with a text that names that call
+    m = re.search(r"if \(mode == FLOWGNN_NUMERIC_F16 && !route_reaches_f16\(e, route\)\)\n\s*return refuse\(e, FLOWGNN_ERR_UNSUPPORTED,\s*e->model_id == FLOWGNN_MODEL_DGN \?(.*?)\n\s*: e->model_id", src, re.S)
+    assert m and "flowgnn_set_model_numeric_mode(e, FLOWGNN_MODEL_DGN, FLOWGNN_NUMERIC_F16)" in m.group(1)
     body = src[src.index("int flowgnn_set_model_numeric_mode(flowgnn_engine* e, int model_id, int mode)"):]
     body = body[:body.index("\n}\n")]
     assert "model_id != e->model_id" in body and "FLOWGNN_ERR_ARG" in body and "return flowgnn_set_model_numeric_mode_dim(e, width, mode);" in body
-    # the three old calls never pass dgn_form
-    assert len(re.findall(r"set_numeric_mode\(e, mode, true, true, false, true\)", src)) == 1
+    assert re.search(r"if \(model_id != e->model_id\)\s*return refuse\(e, FLOWGNN_ERR_ARG,", body)
+    assert body.index("model_id != e->model_id") < body.index("ModeRoute::ModelNumericMode")
+    # the three old calls never pass that route: its one call site is in the call that names the model
+    assert len(re.findall(r"set_numeric_mode\(e, mode, ModeRoute::ModelNumericMode\)", src)) == 1 and "set_numeric_mode(e, mode, ModeRoute::ModelNumericMode)" in body
+    assert len(re.findall(r"ModeRoute::ModelNumericMode\b", src)) == 2  # (the rule above and that call site)
 
 
 def test_python_and_cli_route_dgn_to_the_new_call():
