@@ -93,6 +93,8 @@ def _declare(lib):
     lib.flowgnn_set_jk_residual.argtypes = [eng, C.c_int, C.c_int, C.c_int]
     lib.flowgnn_set_model_jk_residual.argtypes = [eng, C.c_int, C.c_int, C.c_int]
     lib.flowgnn_jk_residual.argtypes = [eng, p_int, p_int]
+    lib.flowgnn_set_num_layers.argtypes = [eng, C.c_int, C.c_int]
+    lib.flowgnn_num_layers.argtypes = [eng]
     lib.flowgnn_set_num_tasks.argtypes = [eng, C.c_int]
     lib.flowgnn_num_tasks.argtypes = [eng]
     lib.flowgnn_set_emb_dim.argtypes = [eng, C.c_int]
@@ -147,6 +149,7 @@ def _declare(lib):
     lib.flowgnn_group_set_set2set_pooling.argtypes = [grp, C.c_int, C.c_int, C.c_int] + [p_float] * 6
     lib.flowgnn_group_set_jk_residual.argtypes = [grp, C.c_int, C.c_int, C.c_int]
     lib.flowgnn_group_set_model_jk_residual.argtypes = [grp, C.c_int, C.c_int, C.c_int]
+    lib.flowgnn_group_set_num_layers.argtypes = [grp, C.c_int, C.c_int]
     lib.flowgnn_group_set_batch.argtypes = [grp, C.c_int, p_int, p_int, p_int, p_int, p_int, p_float]
     lib.flowgnn_group_shards.argtypes = [grp, p_int]
     lib.flowgnn_group_run.argtypes = [grp]
@@ -198,6 +201,7 @@ def _declare(lib):
                  "flowgnn_set_attention_pooling", "flowgnn_attention_pooling", "flowgnn_group_set_attention_pooling",
                  "flowgnn_set_set2set_pooling", "flowgnn_set2set_pooling", "flowgnn_group_set_set2set_pooling",
                  "flowgnn_set_jk_residual", "flowgnn_jk_residual", "flowgnn_group_set_jk_residual", "flowgnn_set_model_jk_residual", "flowgnn_group_set_model_jk_residual",
+                 "flowgnn_set_num_layers", "flowgnn_num_layers", "flowgnn_group_set_num_layers",
                  "flowgnn_laplacian_eigen_max_nodes", "flowgnn_laplacian_eigen", "flowgnn_laplacian_eigen_device",
                  "GIN_compute_graphs_mt", "GCN_compute_graphs_mt", "GIN_compute_graphs", "GCN_compute_graphs", "PNA_compute_graphs", "DGN_compute_graphs", "GAT_compute_graphs"):
         getattr(lib, name).restype = C.c_int

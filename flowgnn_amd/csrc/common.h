@@ -13,6 +13,8 @@ constexpr int EDGE_ATTR = 3;
 constexpr int ED_FEATURE_PER_LAYER = 13;
 constexpr int EDGE_COMBOS = 60;  // 5 * 6 * 2 distinct (attr0, attr1, attr2) triples
 constexpr int WAVE = 64;
+constexpr int NUM_LAYERS_DEFAULT = 5;  // the reference's depth (flowgnn.h: FLOWGNN_NUM_LAYERS_DEFAULT)
+constexpr int MAX_NUM_LAYERS = 8;      // flowgnn_set_num_layers' cap: the size of the per-layer arrays below (flowgnn.h: FLOWGNN_MAX_NUM_LAYERS)
 
 // error flag values written by validation code on the device (match flowgnn.h)
 constexpr int ERR_EDGE_RANGE = 2;
@@ -177,7 +179,7 @@ struct DeviceBatch {
     int pooling;              // FLOWGNN_POOL_* (flowgnn_set_pooling; GIN, GIN-VN, GCN, GAT): 0 = mean, every launch is the one it always was; 1 = sum,
                               // 2 = max.  Decides what out and emb hold; node_emb and the attention buffers do not depend on it
     bool gin_eps_on;          // flowgnn_set_gin_eps (GIN, GIN-VN): false = off, every launch is the one it always was.  A state, not a value: on
-    float gin_self_scale[5];  // with five zeros runs the eps instances too.  s_l = (float)(1.0f + eps[l]) of layer l: a[v] = s_l h_l[v] + m_l[v]
+    float gin_self_scale[MAX_NUM_LAYERS];  // with five zeros runs the eps instances too.  s_l = (float)(1.0f + eps[l]) of layer l: a[v] = s_l h_l[v] + m_l[v]
     const float* ogb_vn;      // flowgnn_set_ogb_virtual_node (GIN) / flowgnn_set_gcn_virtual_node (GCN): the five tensors in the device form of gin_ogbvn.h, or null: off, every
                               // launch is the one it always was.  A forward that finds it set runs OGB's virtual node on every path
     const void* attn_pool;    // flowgnn_set_attention_pooling (GIN, GCN at width 300): the gate's tensors in the device form of wide_attn.h, or null: off,
@@ -237,12 +239,15 @@ public:
     virtual int set_numeric_mode(int mode) { return mode == 0 ? 0 : 8 /* FLOWGNN_ERR_UNSUPPORTED */; }
     // NUM_TASK of the readout (graph_pred_weights [NUM_TASK][EMB_DIM], out [G][NUM_TASK]); takes effect at the next set_weights
     virtual int set_num_tasks(int t) { return t == 1 ? 0 : 8; }
+    // OGB's num_layer (flowgnn_set_num_layers): the models whose layers are a host-side loop of launches take 2 .. MAX_NUM_LAYERS and
+    // drop their weights on a change; every other model is five layers deep at compile time
+    virtual int set_num_layers(int n) { return n == NUM_LAYERS_DEFAULT ? 0 : 8; }
     // flowgnn_set_ogb_virtual_node: the state alone (the tensors reach forward() through DeviceBatch::ogb_vn), for what a model decides
     // before it sees a batch (wants_packed_tile_lists)
     virtual int set_ogb_virtual_node(bool on) { return on ? 8 : 0; }
     // flowgnn_set_ogb_virtual_node / flowgnn_set_gcn_virtual_node and their _dim forms: a model that runs the virtual node says how many
     // bytes the device form of its tensors has (0: no such kernel; the 100-wide models: gin_ogbvn.h's) and packs the five host tensors
-    // (E [D], w1 [4][2D][D], b1 [4][2D], w2 [4][D][2D], b2 [4][D], D = emb_dim()) into it; DeviceBatch::ogb_vn then points at a copy
+    // (E [D], w1 [4][2D][D], b1 [4][2D], w2 [4][D][2D], b2 [4][D], D = emb_dim(); 4 = the model's depth - 1) into it; DeviceBatch::ogb_vn then points at a copy
     virtual size_t ogb_vn_blob_bytes() const { return 0; }
     virtual void ogb_vn_pack(const float*, const float*, const float*, const float*, const float*, void*) const {}
     // flowgnn_set_gcn_virtual_node / _dim: the state (null: off) and the embedding row E [emb_dim()], which GCN folds into layer 0's
@@ -280,6 +285,11 @@ Model* make_gat_model();
 
 // helpers
 int read_floats(const char* dir, const char* file, size_t offset_floats, size_t count, float* dst);
+// A weight file that holds fixed_floats + layers * per_layer_floats floats (flowgnn_set_num_layers): FLOWGNN_ERR_IO, with both depths in
+// the text, when its size is that of another depth in 2 .. MAX_NUM_LAYERS; 0 otherwise (read_floats reports what else is wrong with it)
+int check_layer_file(const char* dir, const char* file, size_t fixed_floats, size_t per_layer_floats, int layers);
+// ... and the whole of a file that is layers blocks of per_layer_floats
+int read_layer_floats(const char* dir, const char* file, int layers, size_t per_layer_floats, float* dst);
 template <typename T>
 int upload(T** dptr, const std::vector<T>& host) {
     const size_t want = sizeof(T) * (host.empty() ? 1 : host.size());

@@ -42,6 +42,29 @@ int read_floats(const char* dir, const char* file, size_t offset_floats, size_t 
     return rc;
 }
 
+int check_layer_file(const char* dir, const char* file, size_t fixed_floats, size_t per_layer_floats, int layers) {
+    const std::string path = std::string(dir) + "/" + file;
+    FILE* f = fopen(path.c_str(), "rb");
+    if (!f) return 0;  // (read_floats says so)
+    long bytes = -1;
+    if (fseek(f, 0, SEEK_END) == 0) bytes = ftell(f);
+    fclose(f);
+    if (bytes < 0 || bytes % (long)sizeof(float) != 0) return 0;
+    const size_t have = (size_t)bytes / sizeof(float);
+    if (have == fixed_floats + (size_t)layers * per_layer_floats) return 0;
+    for (int k = 2; k <= MAX_NUM_LAYERS; k++)
+        if (have == fixed_floats + (size_t)k * per_layer_floats) {
+            snprintf(g_err, sizeof(g_err), "%s holds the tensors of a model %d layers deep, and the engine's depth is %d (flowgnn_set_num_layers)", path.c_str(), k, layers);
+            return FLOWGNN_ERR_IO;
+        }
+    return 0;
+}
+
+int read_layer_floats(const char* dir, const char* file, int layers, size_t per_layer_floats, float* dst) {
+    if (int rc = check_layer_file(dir, file, 0, per_layer_floats, layers)) return rc;
+    return read_floats(dir, file, 0, (size_t)layers * per_layer_floats, dst);
+}
+
 // ------------------------------------------------------------------ profiler
 Profiler::~Profiler() {
     for (auto& p : pending_) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
@@ -694,7 +717,7 @@ static int set_batch_state(flowgnn_engine* e, int num_graphs, const int* nums_of
     db.num_tasks = e->num_tasks;
     db.pooling = e->pooling;
     db.gin_eps_on = e->gin_eps_on;
-    for (int l = 0; l < 5; l++) db.gin_self_scale[l] = (float)(1.0f + e->gin_eps[l]);
+    for (int l = 0; l < FLOWGNN_MAX_NUM_LAYERS; l++) db.gin_self_scale[l] = (float)(1.0f + e->gin_eps[l]);
     db.ogb_vn = e->ogb_vn_on ? (const float*)e->ogb_vn.p : nullptr;
     db.attn_pool = e->attn_pool_on ? e->attn_pool.p : nullptr;
     db.s2s = e->s2s_steps ? e->s2s.p : nullptr;

@@ -1,5 +1,5 @@
 // engine_config.hip -- the calls that configure an engine (include/flowgnn.h): NUM_TASK, width, numeric mode, pooling, eps, the two
-// virtual nodes, the attention and set2set readouts, JK / residual, and their getters.  Host code only; what it shares with engine.hip
+// virtual nodes, the attention and set2set readouts, JK / residual, the depth, and their getters.  Host code only; what it shares with engine.hip
 // (begin_change, use_device, kOutputs) is declared in engine_internal.h.
 //
 // Every setter is: its argument checks, its state checks, begin_change (or use_device + drop_graph where no device memory changes
@@ -146,6 +146,9 @@ static int set_width(flowgnn_engine* e, const char* fn, int emb_dim) {
         return refuse(e, FLOWGNN_ERR_UNSUPPORTED, who + "JK sum or the residual is on (" + (gcn ? "flowgnn_set_model_jk_residual" : "flowgnn_set_jk_residual") + "), and only the 300-wide " +
                                                   (gcn ? "GCN" : "GIN") + " has those instances, not width " + std::to_string(emb_dim) +
                                                   ": turn it off (FLOWGNN_JK_LAST, 0), then change the width");
+    if (e->num_layers != FLOWGNN_NUM_LAYERS_DEFAULT)  // (not 5 means width 300: the call asks for 100, whose kernels are five layers deep)
+        return refuse(e, FLOWGNN_ERR_UNSUPPORTED, who + "the depth is " + std::to_string(e->num_layers) + " (flowgnn_set_num_layers), and the " + std::to_string(emb_dim) +
+                                                  "-wide kernels are five layers deep: flowgnn_set_num_layers(e, " + std::to_string(e->emb_dim) + ", 5) first, then change the width");
     ENGINE_TRY(e, begin_change(e));
     Model* m = gcn ? (emb_dim == FLOWGNN_EMB_DIM_REFERENCE ? make_gcn_model() : make_gcn_wide_model(emb_dim))
                    : (emb_dim == FLOWGNN_EMB_DIM_REFERENCE ? make_gin_model(false) : make_gin_wide_model(emb_dim));
@@ -347,7 +350,7 @@ int flowgnn_set_gin_eps(flowgnn_engine* e, const float* eps) {
     if (e->model_id != FLOWGNN_MODEL_GIN && e->model_id != FLOWGNN_MODEL_GIN_VN)
         return refuse(e, FLOWGNN_ERR_UNSUPPORTED, "flowgnn_set_gin_eps: only GIN and GIN-VN have the (1 + eps) self term");
     if (eps) {
-        for (int l = 0; l < 5; l++)
+        for (int l = 0; l < e->num_layers; l++)
             if (!std::isfinite(eps[l]))
                 return refuse(e, FLOWGNN_ERR_ARG, "flowgnn_set_gin_eps: eps[" + std::to_string(l) + "] is not finite");
         if (e->numeric_mode == FLOWGNN_NUMERIC_Q6_10)
@@ -357,8 +360,8 @@ int flowgnn_set_gin_eps(flowgnn_engine* e, const float* eps) {
     e->drop_graph();  // a recorded launch sequence is that of the other state (or carries the other values in its argument blocks)
     e->gin_eps_on = eps != nullptr;
     e->db.gin_eps_on = e->gin_eps_on;  // (launches are stream-ordered: the values matter to those enqueued after this call)
-    for (int l = 0; l < 5; l++) {
-        e->gin_eps[l] = eps ? eps[l] : 0.0f;
+    for (int l = 0; l < FLOWGNN_MAX_NUM_LAYERS; l++) {  // (the caller's array has flowgnn_num_layers(e) floats; beyond them: zeros)
+        e->gin_eps[l] = (eps && l < e->num_layers) ? eps[l] : 0.0f;
         e->db.gin_self_scale[l] = (float)(1.0f + e->gin_eps[l]);
     }
     return FLOWGNN_OK;
@@ -367,7 +370,7 @@ int flowgnn_set_gin_eps(flowgnn_engine* e, const float* eps) {
 int flowgnn_gin_eps(const flowgnn_engine* e, float* eps_out) {
     if (!e) return -1;
     if (eps_out)
-        for (int l = 0; l < 5; l++) eps_out[l] = e->gin_eps[l];
+        for (int l = 0; l < e->num_layers; l++) eps_out[l] = e->gin_eps[l];
     return e->gin_eps_on ? 1 : 0;
 }
 }  // extern "C"
@@ -380,7 +383,7 @@ int flowgnn_gin_eps(const flowgnn_engine* e, float* eps_out) {
 static int set_virtual_node(flowgnn_engine* e, const char* fn, const float* vn_embedding, const float* w1, const float* b1, const float* w2,
                             const float* b2, int dim) {
     const std::string who = std::string(fn) + ": ";
-    const size_t D = (size_t)dim, H = 2 * D, L = FLOWGNN_OGB_VN_LAYERS;
+    const size_t D = (size_t)dim, H = 2 * D, L = (size_t)e->num_layers - 1;  // (FLOWGNN_OGB_VN_LAYERS unless flowgnn_set_num_layers said otherwise)
     const TensorArg t[5] = {{"vn_embedding", vn_embedding, D}, {"w1", w1, L * H * D}, {"b1", b1, L * H}, {"w2", w2, L * D * H}, {"b2", b2, L * D}};
     bool on;
     if (int rc = tensor_set_on(e, who, t, &on)) return rc;
@@ -541,6 +544,49 @@ int flowgnn_set_set2set_pooling(flowgnn_engine* e, int emb_dim, int steps, int n
 }
 
 int flowgnn_set2set_pooling(const flowgnn_engine* e) { return e ? e->s2s_steps : -1; }
+}  // extern "C"
+
+// ------------------------------------------------------------------ the depth
+// OGB's num_layer for GIN and GCN at width 300: the model object's loop bound.  The sequence of
+// flowgnn_set_num_tasks: begin_change, the model drops its weights, the batch has to be set again.
+extern "C" {
+
+int flowgnn_set_num_layers(flowgnn_engine* e, int emb_dim, int num_layers) {
+    if (!e) return FLOWGNN_ERR_ARG;
+    const std::string who = "flowgnn_set_num_layers: ";
+    if (num_layers < FLOWGNN_MIN_NUM_LAYERS || num_layers > FLOWGNN_MAX_NUM_LAYERS)
+        return refuse(e, FLOWGNN_ERR_ARG, who + "num_layers is " + std::to_string(num_layers) + "; the depths are " + std::to_string(FLOWGNN_MIN_NUM_LAYERS) + " .. " +
+                                              std::to_string(FLOWGNN_MAX_NUM_LAYERS) + " (OGB's GNN_node raises below 2; FLOWGNN_MAX_NUM_LAYERS is the size of this ABI's per-layer arrays)");
+    if (int rc = width_argument(e, who, emb_dim)) return rc;
+    if (e->model_id != FLOWGNN_MODEL_GIN && e->model_id != FLOWGNN_MODEL_GCN) {
+        if (num_layers == e->num_layers) return FLOWGNN_OK;  // (5: what every engine is)
+        return refuse(e, FLOWGNN_ERR_UNSUPPORTED, who + "the depth is a choice of FLOWGNN_MODEL_GIN and FLOWGNN_MODEL_GCN at width 300 (OGB's gin, gin-virtual, gcn, gcn-virtual); "
+                                                        "every other model is five layers deep");
+    }
+    if (int rc = width_matches(e, who, false, emb_dim, e->emb_dim)) return rc;
+    if (num_layers == e->num_layers) return FLOWGNN_OK;
+    if (e->numeric_mode == FLOWGNN_NUMERIC_Q6_10)
+        return refuse(e, FLOWGNN_ERR_UNSUPPORTED, who + "the fixed-point arithmetic (FLOWGNN_NUMERIC_Q6_10) is the reference's, which is five layers deep");
+    if (emb_dim != FLOWGNN_EMB_DIM_OGB)
+        return refuse(e, FLOWGNN_ERR_UNSUPPORTED, who + "only the 300-wide models have a depth other than 5 (the graph-resident and the 100-wide per-layer kernels are five layers deep): "
+                                                        "flowgnn_set_emb_dim / flowgnn_set_model_emb_dim(e, 300) first");
+    const std::string not_that_deep = std::to_string(e->num_layers) + " layers, not " + std::to_string(num_layers) + ": turn it off, change the depth, set it again";
+    if (e->gin_eps_on)  // (the tensors belong to a depth, as the virtual node's belong to a width in set_width)
+        return refuse(e, FLOWGNN_ERR_UNSUPPORTED, who + "a trained eps is on (flowgnn_set_gin_eps), and its values are those of " + not_that_deep);
+    if (e->ogb_vn_on)
+        return refuse(e, FLOWGNN_ERR_UNSUPPORTED, who + "OGB's virtual node is on (" + (e->model_id == FLOWGNN_MODEL_GCN ? "flowgnn_set_gcn_virtual_node_dim" : "flowgnn_set_ogb_virtual_node_dim") +
+                                                  "), and its tensors are those of " + not_that_deep);
+    ENGINE_TRY(e, begin_change(e));
+    const int rc = e->model->set_num_layers(num_layers);
+    if (rc) return refuse(e, rc, who + "this model is five layers deep");
+    e->num_layers = num_layers;
+    e->batch_ready = false;  // as flowgnn_set_num_tasks: weights and batch are set again
+    e->ran = false;
+    e->force_exact = false;
+    return FLOWGNN_OK;
+}
+
+int flowgnn_num_layers(const flowgnn_engine* e) { return e ? e->num_layers : -1; }
 }  // extern "C"
 
 // ------------------------------------------------------------------ JK / residual

@@ -99,7 +99,7 @@ struct flowgnn_engine {
     int numeric_mode = FLOWGNN_NUMERIC_F32;
     int pooling = FLOWGNN_POOL_MEAN;  // flowgnn_set_pooling: the engine's, across batches (db.pooling follows it)
     bool gin_eps_on = false;          // flowgnn_set_gin_eps: the engine's too, across batches and weight sets (db.gin_eps_on / gin_self_scale follow)
-    float gin_eps[5] = {0, 0, 0, 0, 0};
+    float gin_eps[FLOWGNN_MAX_NUM_LAYERS] = {};
     bool ogb_vn_on = false;           // flowgnn_set_ogb_virtual_node: the engine's as well (db.ogb_vn follows it)
     fg::GrowBuf ogb_vn;               // ... and its five tensors on the device (gin_ogbvn.h: GIN_OGBVN_FLOATS)
     bool attn_pool_on = false;        // flowgnn_set_attention_pooling: the engine's as well (db.attn_pool follows it)
@@ -108,6 +108,8 @@ struct flowgnn_engine {
     fg::GrowBuf s2s;                  // ... and its six tensors on the device (wide_s2s.h)
     int jk = FLOWGNN_JK_LAST;         // flowgnn_set_jk_residual: the engine's as well, across batches and weight sets (db.jk / db.residual follow)
     int residual = 0;
+    int num_layers = FLOWGNN_NUM_LAYERS_DEFAULT;  // flowgnn_set_num_layers: the model's depth (GIN, GCN at width 300: 2 .. 8); sizes eps and the virtual node's tensors
+    static_assert(FLOWGNN_MAX_NUM_LAYERS == fg::MAX_NUM_LAYERS && FLOWGNN_NUM_LAYERS_DEFAULT == fg::NUM_LAYERS_DEFAULT, "common.h restates the header's two depths");
 
     // the optional outputs (fg::OutSlot): graph embeddings [G][dim] (flowgnn_set_embeddings), node embeddings [N][dim]
     // (flowgnn_set_node_embeddings), node logits [N][num_tasks] (flowgnn_set_node_logits) and, for GAT, the attention coefficients

@@ -69,7 +69,7 @@
 namespace fg {
 namespace {
 
-constexpr int GCW_L = 5;
+// (the depth: GcnWideModel::layers_, 5 unless flowgnn_set_num_layers said otherwise -- DESIGN.md section 4.30; no kernel knows it)
 
 // dinv[src_e] per CSR entry (edge_scalar_kernel, device_common.h), the per-layer path's policy of gcn.hip restated: GcnAggPolicy
 // itself lives in gcn.hip's translation units
@@ -271,6 +271,14 @@ public:
     bool weights_ready() const override { return ready_; }
     void set_exact(bool on) override { exact_ = on; }
     int set_num_tasks(int t) override { return readout_.set_num_tasks(t, ready_); }
+    // OGB's num_layer (flowgnn_set_num_layers, section 4.30): the bound of forward()'s stage loop and the leading dimension of the
+    // per-layer tensors.  The weights are those of a depth: a change drops them, as a change of NUM_TASK does
+    int set_num_layers(int n) override {
+        if (n < FLOWGNN_MIN_NUM_LAYERS || n > FLOWGNN_MAX_NUM_LAYERS) return FLOWGNN_ERR_UNSUPPORTED;
+        if (n != layers_) ready_ = false;
+        layers_ = n;
+        return 0;
+    }
     // FLOWGNN_NUMERIC_F16 (flowgnn_set_model_numeric_mode_dim, section 4.27): stages 0..3 run gcn_wide_f16.hip's kernels on the hi-only
     // stream, which set_weights packs beside the split one whatever the mode is -- so the two calls come in either order
     int set_numeric_mode(int mode) override {
@@ -281,31 +289,32 @@ public:
     // OGB's virtual node (flowgnn_set_gcn_virtual_node_dim, section 4.19): the tensors' device form is gin_wide.hip's (gin_wide_vn.h) and
     // reaches forward() through DeviceBatch::ogb_vn; here the state, and E [D] for layer 0's folded bias -- in either order with
     // set_weights, and it holds across weight sets
-    size_t ogb_vn_blob_bytes() const override { return gw_vn_blob_bytes(D); }
+    size_t ogb_vn_blob_bytes() const override { return gw_vn_blob_bytes(D, layers_ - 1); }
     void ogb_vn_pack(const float* vn_embedding, const float* w1, const float* b1, const float* w2, const float* b2, void* out) const override {
-        gw_vn_blob_pack(D, vn_embedding, w1, b1, w2, b2, out);
+        gw_vn_blob_pack(D, layers_ - 1, vn_embedding, w1, b1, w2, b2, out);
     }
     int set_gcn_virtual_node(const float* vn_embedding) override {
-        if (vn_embedding && gw_vn_blob_bytes(D) == 0) return 8;
+        if (vn_embedding && gw_vn_blob_bytes(D, layers_ - 1) == 0) return 8;
         vn_on_ = vn_embedding != nullptr;
         if (vn_on_) vn_e_.assign(vn_embedding, vn_embedding + D);
         return ready_ ? upload_b0() : 0;
     }
 
-    // host tensors, GcnModel's with D for 100: node_emb[173][D], edge_emb[5][13][D], convs_weight[5][D][D], convs_bias[5][D], root_emb[5][D],
-    // bn_weight/bias/mean/var[5][D], pred_w[NUM_TASK][D], pred_b[NUM_TASK]
+    // host tensors, GcnModel's with D for 100 and the depth L for 5: node_emb[173][D], edge_emb[L][13][D], convs_weight[L][D][D],
+    // convs_bias[L][D], root_emb[L][D], bn_weight/bias/mean/var[L][D], pred_w[NUM_TASK][D], pred_b[NUM_TASK]
     int set_weights(const float* const* t) override {
+        const int L = layers_;
         const float *nemb = t[0], *eemb = t[1], *cw = t[2], *cb = t[3], *root = t[4], *bnw = t[5], *bnb = t[6], *bnm = t[7], *bnv = t[8],
                     *pw = t[9], *pb = t[10];
         std::vector<float> v_nemb(nemb, nemb + (size_t)ND_FEATURE_TOTAL * D);  // the virtual node's t_0 reads the unprojected table
         w0_.assign(cw, cw + (size_t)D * D);
         b0_.assign(cb, cb + D);
-        std::vector<float> tab((size_t)GCW_L * M::TAB_FLOATS);
-        std::vector<float> wt((size_t)(GCW_L - 1) * D * D), v_b(cb + D, cb + (size_t)GCW_L * D);  // the exact form: [K][O] copies of W_1..W_4
-        std::vector<uint8_t> chunks((size_t)(GCW_L - 1) * M::LAYER_BYTES);
-        std::vector<uint8_t> chunks16((size_t)(GCW_L - 1) * F16::LAYER_BYTES);
-        std::vector<float> tails((size_t)(GCW_L - 1) * M::TAIL_FLOATS);
-        for (int l = 0; l < GCW_L; l++) {
+        std::vector<float> tab((size_t)L * M::TAB_FLOATS);
+        std::vector<float> wt((size_t)(L - 1) * D * D), v_b(cb + D, cb + (size_t)L * D);  // the exact form: [K][O] copies of W_1 .. W_{L-1}
+        std::vector<uint8_t> chunks((size_t)(L - 1) * M::LAYER_BYTES);
+        std::vector<uint8_t> chunks16((size_t)(L - 1) * F16::LAYER_BYTES);
+        std::vector<float> tails((size_t)(L - 1) * M::TAIL_FLOATS);
+        for (int l = 0; l < L; l++) {
             float* tl = &tab[(size_t)l * M::TAB_FLOATS];
             gw_edge_combos(eemb + (size_t)l * ED_FEATURE_PER_LAYER * D, D, tl);
             float* e = tl + M::ECOMB_FLOATS;
@@ -348,16 +357,19 @@ public:
     }
 
     // the reference's one file (GCN/src/host_load.cc) with this width in place of 100: node table at 0, layer l at 173 D + l (D^2 + 15 D)
-    // (W, b, root, the 13 edge rows), BatchNorm l at 173 D + 5 (D^2 + 15 D) + l (4 D + 1), the head behind the fifth
+    // (W, b, root, the 13 edge rows), BatchNorm l at 173 D + L (D^2 + 15 D) + l (4 D + 1), the head behind the last -- L the depth, the
+    // reference's 5: every offset behind the layers moves with it, so a file of another depth is refused by its size, not read
     int load_weights_dir(const char* dir) override {
+        const int L = layers_;
         const std::string name = "gcn_ep1_dim" + std::to_string(D) + ".weights.all.bin";
         const char* f = name.c_str();
-        const size_t d = D, layer = d * d + 15 * d, bn0 = ND_FEATURE_TOTAL * d + GCW_L * layer, head = bn0 + GCW_L * (4 * d + 1);
-        std::vector<float> nemb(ND_FEATURE_TOTAL * d), eemb(GCW_L * ED_FEATURE_PER_LAYER * d), cw(GCW_L * d * d), cb(GCW_L * d), root(GCW_L * d),
-            bnw(GCW_L * d), bnb(GCW_L * d), bnm(GCW_L * d), bnv(GCW_L * d), pw((size_t)readout_.num_tasks * d), pb(readout_.num_tasks);
+        const size_t d = D, layer = d * d + 15 * d, bn0 = ND_FEATURE_TOTAL * d + L * layer, head = bn0 + L * (4 * d + 1);
+        std::vector<float> nemb(ND_FEATURE_TOTAL * d), eemb(L * ED_FEATURE_PER_LAYER * d), cw(L * d * d), cb(L * d), root(L * d),
+            bnw(L * d), bnb(L * d), bnm(L * d), bnv(L * d), pw((size_t)readout_.num_tasks * d), pb(readout_.num_tasks);
         int rc;
+        if ((rc = check_layer_file(dir, f, nemb.size() + pw.size() + pb.size(), layer + 4 * d + 1, L))) return rc;
         if ((rc = read_floats(dir, f, 0, nemb.size(), nemb.data()))) return rc;
-        for (int l = 0; l < GCW_L; l++) {
+        for (int l = 0; l < L; l++) {
             const size_t base = ND_FEATURE_TOTAL * d + layer * (size_t)l;
             if ((rc = read_floats(dir, f, base, d * d, &cw[(size_t)l * d * d]))) return rc;
             if ((rc = read_floats(dir, f, base + d * d, d, &cb[l * d]))) return rc;
@@ -379,6 +391,7 @@ public:
         const int n = db.b.n_tot;
         if (n <= 0) return 0;
         const int G = db.b.num_graphs;
+        const int L = layers_;  // (the depth: flowgnn_set_num_layers)
         const bool vn = db.ogb_vn != nullptr;
         if (vn != vn_on_) {
             set_last_error("flowgnn_run: the GCN model's virtual-node state and the engine's tensors disagree (flowgnn_set_gcn_virtual_node_dim)");
@@ -429,12 +442,12 @@ public:
                                                                                                 node_graph_.p, G);
             }
             ProfScope p(prof, "gcn_wide_vn_update", s);
-            if (int rc = launch_gw_vn_update(D, db.ogb_vn, 0, vn_t_.p, vn_vec_[0].p, hid_.p, G, exact_, db.range_flag, res_on ? db.ogb_vn : nullptr, 0, s))
+            if (int rc = launch_gw_vn_update(D, db.ogb_vn, L - 1, 0, vn_t_.p, vn_vec_[0].p, hid_.p, G, exact_, db.range_flag, res_on ? db.ogb_vn : nullptr, 0, s))
                 return rc;
         }
         int cur = 0;
-        for (int l = 0; l < GCW_L; l++) {
-            const bool last = l == GCW_L - 1;
+        for (int l = 0; l < L; l++) {
+            const bool last = l == L - 1;
             // (node embeddings: the last stage writes pre_4 straight into the caller's buffer, and the readout reads it there)
             // (under JK sum the reverse: the rows the pool is taken over are the sum's, so the last stage's sum goes into the caller's
             // buffer and h_5 into the ping-pong buffer)
@@ -502,7 +515,7 @@ public:
                     gcw_vn_t_kernel<D><<<grid_for((long long)G * M::C, 256, 256 * 8), 256, 0, s>>>(vn_part_.p, db.b.node_off, vn_vec_[l & 1].p, vn_t_.p, G);
                 }
                 ProfScope p(prof, "gcn_wide_vn_update", s);
-                if (int rc = launch_gw_vn_update(D, db.ogb_vn, l + 1, vn_t_.p, vn_vec_[(l + 1) & 1].p, hid_.p, G, exact_, db.range_flag,
+                if (int rc = launch_gw_vn_update(D, db.ogb_vn, L - 1, l + 1, vn_t_.p, vn_vec_[(l + 1) & 1].p, hid_.p, G, exact_, db.range_flag,
                                                  res_on ? vn_vec_[l & 1].p : nullptr, res_on ? D : 0, s))
                     return rc;
             }
@@ -514,8 +527,8 @@ public:
     }
 
 private:
-    // stage l (0..3) adds vn_{l+1}; its rows xin_{l+1} feed update l + 1, which exists for l + 1 < 4
-    static bool feeds_update(int l) { return l + 1 < GCW_L - 1; }
+    // stage l (0 .. L - 2) adds vn_{l+1}; its rows xin_{l+1} feed update l + 1, which exists for l + 1 < L - 1 (at L = 2: for no stage)
+    bool feeds_update(int l) const { return l + 1 < layers_ - 1; }
     // the encoder's tenth row: b_0, or with the virtual node on b_0' = b_0 + W_0 E, in double
     int upload_b0() {
         std::vector<float> b(b0_);
@@ -547,13 +560,14 @@ private:
     bool ready_ = false;
     bool exact_ = false;
     bool f16_ = false;  // flowgnn_set_model_numeric_mode_dim(FLOWGNN_NUMERIC_F16)
+    int layers_ = FLOWGNN_NUM_LAYERS_DEFAULT;  // flowgnn_set_num_layers: L, what the per-layer buffers below were packed for while ready_
     GwReadout<D> readout_;         // the head's weights, NUM_TASK, the pooled rows and the gates (wide_common.h)
-    uint8_t* d_chunks_ = nullptr;  // the weight streams of gcw_layer_kernel: W_1 .. W_4, LAYER_BYTES each
-    uint8_t* d_chunks16_ = nullptr;  // FLOWGNN_NUMERIC_F16: the same four products as hi-only streams, F16::LAYER_BYTES each
+    uint8_t* d_chunks_ = nullptr;  // the weight streams of gcw_layer_kernel: W_1 .. W_{L-1}, LAYER_BYTES each
+    uint8_t* d_chunks16_ = nullptr;  // FLOWGNN_NUMERIC_F16: the same L - 1 products as hi-only streams, F16::LAYER_BYTES each
     float* d_tails_ = nullptr;     // ... and per product b (pre-scaled, padded) and the output scale
     float* d_tab_ = nullptr;       // per layer: ecomb | root | BN scale | BN shift
     float *d_proj_ = nullptr, *d_b0_ = nullptr;  // W_0 applied to the node table, and b_0
-    float *d_wt_ = nullptr, *d_b_ = nullptr;     // the exact form's W_1 .. W_4 as [K][O], and b_1 .. b_4
+    float *d_wt_ = nullptr, *d_b_ = nullptr;     // the exact form's W_1 .. W_{L-1} as [K][O], and b_1 .. b_{L-1}
     GrowBuf esc_;     // [E] dinv[src_e] in CSR order
     // OGB's virtual node (section 4.19)
     bool vn_on_ = false;              // flowgnn_set_gcn_virtual_node_dim is on (the tensors themselves: DeviceBatch::ogb_vn)

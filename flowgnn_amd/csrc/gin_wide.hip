@@ -44,7 +44,7 @@
 namespace fg {
 namespace {
 
-constexpr int GW_L = 5;
+// (the depth: GinWideModel::layers_, 5 unless flowgnn_set_num_layers said otherwise -- DESIGN.md section 4.30; no kernel knows it)
 
 template <int D>
 __global__ __launch_bounds__(GW_WAVES * 64) void gw_layer_kernel(const float* __restrict__ h, float* __restrict__ hout,
@@ -55,7 +55,7 @@ __global__ __launch_bounds__(GW_WAVES * 64) void gw_layer_kernel(const float* __
     gw_layer_body<D, GW_PLAIN>(h, hout, row_ptr, src, ecode, ecomb, wchunks, tailp, n_tot, relu_out, self_s, range_flag, nullptr, nullptr);
 }
 
-// the VN instance: x_{l+1}[v] = relu(layer l of x_l)[v] + vn_{l+1}[node_graph[v]] (always ReLU'd: layers 0..3)
+// the VN instance: x_{l+1}[v] = relu(layer l of x_l)[v] + vn_{l+1}[node_graph[v]] (always ReLU'd: every layer but the last)
 template <int D>
 __global__ __launch_bounds__(GW_WAVES * 64) void gw_layer_vn_kernel(const float* __restrict__ h, float* __restrict__ hout,
                                                                     const int* __restrict__ row_ptr, const int* __restrict__ src,
@@ -198,9 +198,8 @@ void gw_pack_layer_f16(const uint8_t* split, uint8_t* out) {
 
 // OGB's virtual node at this width (flowgnn_set_ogb_virtual_node_dim, section 4.17): the device form of the five tensors, a layout
 // of this file's own (gin_ogbvn.h's is the 100-wide one).  In bytes, every part a multiple of 16:
-//   E [D] floats | per update l (0..3): the weight stream of gw_pack_layer<D> (LAYER_BYTES) | its tail (TAIL_FLOATS floats)
+//   E [D] floats | per update l (0 .. depth - 2): the weight stream of gw_pack_layer<D> (LAYER_BYTES) | its tail (TAIL_FLOATS floats)
 //                                       | W1^T [D][H] | W2^T [H][D] | b1 [H] | b2 [D]     (the four fp32 parts: the exact form)
-constexpr int GW_VN_LAYERS = GW_L - 1;
 template <int D>
 struct GwVnBlob {
     using M = GwDims<D>;
@@ -211,17 +210,17 @@ struct GwVnBlob {
     static constexpr size_t B1_OFF = W2T_OFF + (size_t)M::H * D * 4;
     static constexpr size_t B2_OFF = B1_OFF + (size_t)M::H * 4;
     static constexpr size_t LAYER_STRIDE = B2_OFF + (size_t)D * 4;
-    static constexpr size_t BYTES = E_BYTES + GW_VN_LAYERS * LAYER_STRIDE;
+    static constexpr size_t bytes(int n_updates) { return E_BYTES + (size_t)n_updates * LAYER_STRIDE; }
     static_assert(E_BYTES % 16 == 0 && TAIL_OFF % 16 == 0 && W1T_OFF % 16 == 0 && LAYER_STRIDE % 16 == 0, "the weight stream is read in 16-byte pieces");
 };
 
-// host tensors E [D], w1 [4][H][D], b1 [4][H], w2 [4][D][H], b2 [4][D] -> GwVnBlob<D>::BYTES bytes
+// host tensors E [D], w1 [U][H][D], b1 [U][H], w2 [U][D][H], b2 [U][D], U = n_updates -> GwVnBlob<D>::bytes(U) bytes
 template <int D>
-void gw_vn_pack(const float* vn_embedding, const float* w1, const float* b1, const float* w2, const float* b2, uint8_t* out) {
+void gw_vn_pack(int n_updates, const float* vn_embedding, const float* w1, const float* b1, const float* w2, const float* b2, uint8_t* out) {
     using B = GwVnBlob<D>;
     constexpr int H = 2 * D;
     std::memcpy(out, vn_embedding, B::E_BYTES);
-    for (int l = 0; l < GW_VN_LAYERS; l++) {
+    for (int l = 0; l < n_updates; l++) {
         uint8_t* o = out + B::E_BYTES + (size_t)l * B::LAYER_STRIDE;
         const float* W1 = w1 + (size_t)l * H * D;
         const float* W2 = w2 + (size_t)l * D * H;
@@ -242,9 +241,9 @@ class GinWideModel : public Model {
 public:
     ~GinWideModel() override { free_all(); }
     int set_ogb_virtual_node(bool) override { return 0; }  // (the tensors: DeviceBatch::ogb_vn, in GwVnBlob's form)
-    size_t ogb_vn_blob_bytes() const override { return GwVnBlob<D>::BYTES; }
+    size_t ogb_vn_blob_bytes() const override { return GwVnBlob<D>::bytes(layers_ - 1); }
     void ogb_vn_pack(const float* vn_embedding, const float* w1, const float* b1, const float* w2, const float* b2, void* out) const override {
-        gw_vn_pack<D>(vn_embedding, w1, b1, w2, b2, static_cast<uint8_t*>(out));
+        gw_vn_pack<D>(layers_ - 1, vn_embedding, w1, b1, w2, b2, static_cast<uint8_t*>(out));
     }
     int emb_dim() const override { return D; }
     int scratch_dim() const override { return D; }
@@ -260,18 +259,27 @@ public:
         return 0;
     }
     int set_num_tasks(int t) override { return readout_.set_num_tasks(t, ready_); }
+    // OGB's num_layer (flowgnn_set_num_layers, section 4.30): the bound of forward()'s loop and the leading dimension of the per-layer
+    // tensors.  The weights are those of a depth: a change drops them, as a change of NUM_TASK does
+    int set_num_layers(int n) override {
+        if (n < FLOWGNN_MIN_NUM_LAYERS || n > FLOWGNN_MAX_NUM_LAYERS) return FLOWGNN_ERR_UNSUPPORTED;
+        if (n != layers_) ready_ = false;
+        layers_ = n;
+        return 0;
+    }
 
-    // host tensors: node_emb[173][D], edge_emb[5][13][D], w1[5][H][D], b1[5][H], w2[5][D][H], b2[5][D], pred_w[NUM_TASK][D], pred_b[NUM_TASK]
+    // host tensors, L = the depth: node_emb[173][D], edge_emb[L][13][D], w1[L][H][D], b1[L][H], w2[L][D][H], b2[L][D], pred_w[NUM_TASK][D], pred_b[NUM_TASK]
     int set_weights(const float* const* t) override {
+        const int L = layers_;
         const float *nemb = t[0], *eemb = t[1], *w1 = t[2], *b1 = t[3], *w2 = t[4], *b2 = t[5], *pw = t[6], *pb = t[7];
         std::vector<float> v_nemb(nemb, nemb + (size_t)ND_FEATURE_TOTAL * D);
-        std::vector<float> v_b1(b1, b1 + (size_t)GW_L * H), v_b2(b2, b2 + (size_t)GW_L * D);
-        std::vector<float> ecomb((size_t)GW_L * EDGE_COMBOS * D);
-        std::vector<float> w1t((size_t)GW_L * D * H), w2t((size_t)GW_L * H * D);  // the exact form's [K][O] copies
-        std::vector<uint8_t> chunks((size_t)GW_L * M::LAYER_BYTES);
-        std::vector<uint8_t> chunks16((size_t)GW_L * F16::LAYER_BYTES);
-        std::vector<float> tails((size_t)GW_L * M::TAIL_FLOATS);
-        for (int l = 0; l < GW_L; l++) {
+        std::vector<float> v_b1(b1, b1 + (size_t)L * H), v_b2(b2, b2 + (size_t)L * D);
+        std::vector<float> ecomb((size_t)L * EDGE_COMBOS * D);
+        std::vector<float> w1t((size_t)L * D * H), w2t((size_t)L * H * D);  // the exact form's [K][O] copies
+        std::vector<uint8_t> chunks((size_t)L * M::LAYER_BYTES);
+        std::vector<uint8_t> chunks16((size_t)L * F16::LAYER_BYTES);
+        std::vector<float> tails((size_t)L * M::TAIL_FLOATS);
+        for (int l = 0; l < L; l++) {
             gw_edge_combos(eemb + (size_t)l * ED_FEATURE_PER_LAYER * D, D, &ecomb[(size_t)l * EDGE_COMBOS * D]);
             const float* W1 = w1 + (size_t)l * H * D;
             const float* W2 = w2 + (size_t)l * D * H;
@@ -298,16 +306,17 @@ public:
 
     // the reference's file names (GIN/src/host_load.cc:24-58) with this width in place of 100
     int load_weights_dir(const char* dir) override {
-        std::vector<float> w1((size_t)GW_L * H * D), b1((size_t)GW_L * H), w2((size_t)GW_L * D * H), b2((size_t)GW_L * D),
-            nemb((size_t)ND_FEATURE_TOTAL * D), eemb((size_t)GW_L * ED_FEATURE_PER_LAYER * D), pw((size_t)readout_.num_tasks * D), pb(readout_.num_tasks);
+        const int L = layers_;
+        std::vector<float> w1((size_t)L * H * D), b1((size_t)L * H), w2((size_t)L * D * H), b2((size_t)L * D),
+            nemb((size_t)ND_FEATURE_TOTAL * D), eemb((size_t)L * ED_FEATURE_PER_LAYER * D), pw((size_t)readout_.num_tasks * D), pb(readout_.num_tasks);
         const std::string sfx = "_dim" + std::to_string(D) + ".bin";
         int rc;
-        if ((rc = read_floats(dir, ("gin_ep1_mlp_1_weights" + sfx).c_str(), 0, w1.size(), w1.data()))) return rc;
-        if ((rc = read_floats(dir, ("gin_ep1_mlp_1_bias" + sfx).c_str(), 0, b1.size(), b1.data()))) return rc;
-        if ((rc = read_floats(dir, ("gin_ep1_mlp_2_weights" + sfx).c_str(), 0, w2.size(), w2.data()))) return rc;
-        if ((rc = read_floats(dir, ("gin_ep1_mlp_2_bias" + sfx).c_str(), 0, b2.size(), b2.data()))) return rc;
+        if ((rc = read_layer_floats(dir, ("gin_ep1_mlp_1_weights" + sfx).c_str(), L, w1.size() / L, w1.data()))) return rc;
+        if ((rc = read_layer_floats(dir, ("gin_ep1_mlp_1_bias" + sfx).c_str(), L, b1.size() / L, b1.data()))) return rc;
+        if ((rc = read_layer_floats(dir, ("gin_ep1_mlp_2_weights" + sfx).c_str(), L, w2.size() / L, w2.data()))) return rc;
+        if ((rc = read_layer_floats(dir, ("gin_ep1_mlp_2_bias" + sfx).c_str(), L, b2.size() / L, b2.data()))) return rc;
         if ((rc = read_floats(dir, ("gin_ep1_nd_embed" + sfx).c_str(), 0, nemb.size(), nemb.data()))) return rc;
-        if ((rc = read_floats(dir, ("gin_ep1_ed_embed" + sfx).c_str(), 0, eemb.size(), eemb.data()))) return rc;
+        if ((rc = read_layer_floats(dir, ("gin_ep1_ed_embed" + sfx).c_str(), L, eemb.size() / L, eemb.data()))) return rc;
         if ((rc = read_floats(dir, ("gin_ep1_pred_weights" + sfx).c_str(), 0, pw.size(), pw.data()))) return rc;
         if ((rc = read_floats(dir, ("gin_ep1_pred_bias" + sfx).c_str(), 0, pb.size(), pb.data()))) return rc;
         const float* t[8] = {nemb.data(), eemb.data(), w1.data(), b1.data(), w2.data(), b2.data(), pw.data(), pb.data()};
@@ -322,6 +331,7 @@ public:
         const float* const vnb = db.ogb_vn;  // GwVnBlob's form; E is its first part
         const bool vn_on = vnb != nullptr;
         const int G = db.b.num_graphs;
+        const int L = layers_;  // (the depth: flowgnn_set_num_layers)
         if (vn_on) {
             if (int rc = vn_t_.reserve((size_t)G * D)) return rc;
             if (int rc = vn_vec_[0].reserve((size_t)G * D)) return rc;
@@ -345,17 +355,17 @@ public:
         if (exact_)
             if (int rc = hid_.reserve((size_t)(n > G ? n : G) * H)) return rc;
         int cur = 0;
-        for (int l = 0; l < GW_L; l++) {
-            // (node embeddings: the last layer writes h_5 straight into the caller's buffer, and the readout reads it there)
+        for (int l = 0; l < L; l++) {
+            // (node embeddings: the last layer writes h_L straight into the caller's buffer, and the readout reads it there)
             // (under JK sum the reverse: the rows the pool is taken over are the sum's, so the last layer's sum goes into the caller's
             // buffer and h_5 into the ping-pong buffer)
-            float* const hn = (l == GW_L - 1 && db.node_emb && !jk_on) ? db.node_emb : db.h[cur ^ 1];
+            float* const hn = (l == L - 1 && db.node_emb && !jk_on) ? db.node_emb : db.h[cur ^ 1];
             const float* const jk_in = !jk_on ? nullptr : l == 0 ? db.h[cur] : jk_.p;  // x_0 is layer 0's input
-            float* const jk_out = !jk_on ? nullptr : (l == GW_L - 1 && db.node_emb) ? db.node_emb : jk_.p;
+            float* const jk_out = !jk_on ? nullptr : (l == L - 1 && db.node_emb) ? db.node_emb : jk_.p;
             const float self_s = db.gin_eps_on ? db.gin_self_scale[l] : 1.0f;
             const float* ecomb = d_ecomb_ + (size_t)l * EDGE_COMBOS * D;
-            const int relu_out = l != GW_L - 1;
-            const bool vn_next = vn_on && l < GW_VN_LAYERS;  // this layer's output rows get vn_{l+1} added
+            const int relu_out = l != L - 1;
+            const bool vn_next = vn_on && l < L - 1;  // this layer's output rows get vn_{l+1} added
             float* const vnn = vn_vec_[l & 1].p;            // vn_{l+1}; vn_l is vn_vec_[(l - 1) & 1] (l = 0: E, stride 0)
             if (vn_next) {
                 {
@@ -365,7 +375,7 @@ public:
                         return rc;
                 }
                 ProfScope p(prof, "gin_wide_vn_update", s);
-                if (int rc = launch_gw_vn_update(D, vnb, l, vn_t_.p, vnn, hid_.p, G, exact_, db.range_flag,
+                if (int rc = launch_gw_vn_update(D, vnb, L - 1, l, vn_t_.p, vnn, hid_.p, G, exact_, db.range_flag,
                                                  !res_on ? nullptr : l == 0 ? vnb : vn_vec_[(l - 1) & 1].p, l == 0 ? 0 : D, s))
                     return rc;
             }
@@ -432,9 +442,10 @@ private:
     bool ready_ = false;
     bool exact_ = false;
     bool f16_ = false;  // flowgnn_set_numeric_mode_dim(FLOWGNN_NUMERIC_F16)
+    int layers_ = FLOWGNN_NUM_LAYERS_DEFAULT;  // flowgnn_set_num_layers: L, what the per-layer buffers below were packed for while ready_
     GwReadout<D> readout_;         // the head's weights, NUM_TASK, the pooled rows and the gates (wide_common.h)
-    uint8_t* d_chunks_ = nullptr;  // the weight stream of gw_layer_kernel: GW_L x LAYER_BYTES
-    uint8_t* d_chunks16_ = nullptr;  // the hi-only stream of gin_wide_f16.hip's kernels: GW_L x GwF16Dims::LAYER_BYTES
+    uint8_t* d_chunks_ = nullptr;  // the weight stream of gw_layer_kernel: L x LAYER_BYTES
+    uint8_t* d_chunks16_ = nullptr;  // the hi-only stream of gin_wide_f16.hip's kernels: L x GwF16Dims::LAYER_BYTES
     float* d_tails_ = nullptr;     // ... and per layer b2 (pre-scaled, padded) and the output scale (both streams)
     float *d_nemb_ = nullptr, *d_ecomb_ = nullptr;
     float *d_w1t_ = nullptr, *d_w2t_ = nullptr, *d_b1_ = nullptr, *d_b2_ = nullptr;  // the exact form's weights, [K][O]
@@ -456,15 +467,15 @@ Model* make_gin_wide_model(int emb_dim) {
 
 // ---------------------------------------------------------------- gin_wide_vn.h: the virtual node's launches, the only ones in this
 // file -- GinWideModel::forward goes through them, and so does gcn_wide.hip (section 4.19)
-size_t gw_vn_blob_bytes(int emb_dim) { return emb_dim == GW_VN_D ? GwVnBlob<GW_VN_D>::BYTES : 0; }
+size_t gw_vn_blob_bytes(int emb_dim, int n_updates) { return emb_dim == GW_VN_D && n_updates > 0 ? GwVnBlob<GW_VN_D>::bytes(n_updates) : 0; }
 
-void gw_vn_blob_pack(int emb_dim, const float* vn_embedding, const float* w1, const float* b1, const float* w2, const float* b2, void* out) {
-    if (emb_dim == GW_VN_D) gw_vn_pack<GW_VN_D>(vn_embedding, w1, b1, w2, b2, static_cast<uint8_t*>(out));
+void gw_vn_blob_pack(int emb_dim, int n_updates, const float* vn_embedding, const float* w1, const float* b1, const float* w2, const float* b2, void* out) {
+    if (emb_dim == GW_VN_D) gw_vn_pack<GW_VN_D>(n_updates, vn_embedding, w1, b1, w2, b2, static_cast<uint8_t*>(out));
 }
 
-int launch_gw_vn_update(int emb_dim, const void* blob, int l, const float* t, float* vn_next, float* hid, int num_graphs, bool exact,
+int launch_gw_vn_update(int emb_dim, const void* blob, int n_updates, int l, const float* t, float* vn_next, float* hid, int num_graphs, bool exact,
                         int* range_flag, const float* vn_prev, int vn_prev_stride, hipStream_t s) {
-    if (emb_dim != GW_VN_D || l < 0 || l >= GW_VN_LAYERS) return FLOWGNN_ERR_UNSUPPORTED;
+    if (emb_dim != GW_VN_D || l < 0 || l >= n_updates) return FLOWGNN_ERR_UNSUPPORTED;
     if (num_graphs <= 0) return 0;
     constexpr int D = GW_VN_D;
     using VB = GwVnBlob<D>;

@@ -292,6 +292,15 @@ int flowgnn_group_set_model_jk_residual(flowgnn_group* g, int emb_dim, int jk, i
     return group_all(g, [&](flowgnn_engine* e) { return flowgnn_set_model_jk_residual(e, emb_dim, jk, residual); });
 }
 
+// (a member that changes its depth drops its shard with it, as with the width)
+int flowgnn_group_set_num_layers(flowgnn_group* g, int emb_dim, int num_layers) {
+    if (!g) return FLOWGNN_ERR_ARG;
+    g->err.clear();
+    for (flowgnn_engine* e : g->eng)
+        if (e->num_layers != num_layers) g->batch_valid = false;
+    return group_each(g, [&](int i) { return flowgnn_set_num_layers(g->eng[(size_t)i], emb_dim, num_layers); });
+}
+
 int flowgnn_group_set_embeddings(flowgnn_group* g, int on) { return group_all(g, [&](flowgnn_engine* e) { return flowgnn_set_embeddings(e, on); }); }
 int flowgnn_group_set_node_embeddings(flowgnn_group* g, int on) { return group_all(g, [&](flowgnn_engine* e) { return flowgnn_set_node_embeddings(e, on); }); }
 int flowgnn_group_set_node_logits(flowgnn_group* g, int on) { return group_all(g, [&](flowgnn_engine* e) { return flowgnn_set_node_logits(e, on); }); }

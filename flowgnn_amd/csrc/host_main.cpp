@@ -2,7 +2,7 @@
 // OpenCL host (GIN/src/host.cc): load the model's .bin weights, read a graph pack in the reference's on-disk
 // layout, run the whole dataset as ONE batched launch NUM_TRIALS times, write HLS_output.txt.
 //
-//   host <MODEL> [--graphs DIR] [--weights DIR] [--num-graphs N] [--trials T] [--out FILE] [--node-logits FILE] [--attention FILE [--attention-layers MASK]] [--device D | --devices D0,D1,..] [--option key=value] [--numeric f32|q6.10|f16] [--eps] [--ogb-vn] [--attn-pool] [--set2set [--set2set-steps N]] [--jk last|sum] [--residual] [--emb-dim 100|300] [--eig DIR | --compute-eig] [XCLBIN]
+//   host <MODEL> [--graphs DIR] [--weights DIR] [--num-graphs N] [--trials T] [--out FILE] [--node-logits FILE] [--attention FILE [--attention-layers MASK]] [--device D | --devices D0,D1,..] [--option key=value] [--numeric f32|q6.10|f16] [--eps] [--ogb-vn] [--attn-pool] [--set2set [--set2set-steps N]] [--jk last|sum] [--residual] [--emb-dim 100|300] [--num-layer N] [--eig DIR | --compute-eig] [XCLBIN]
 //
 //   MODEL        GIN | GIN-VN | GCN | GAT | PNA | DGN
 //   --graphs     directory holding graph_info/ and graph_bin/      (default ../graphs, host.cc:14-15)
@@ -34,6 +34,8 @@
 //                flowgnn_group_set_numeric_mode_dim: GIN takes f16 at that width (beside --eps, --ogb-vn and --attn-pool as before);
 //                GCN: through flowgnn_group_set_model_numeric_mode_dim, `host GCN --emb-dim 300 --numeric f16 [--ogb-vn] [--jk sum]
 //                [--residual]` -- stages 0..3 with one f16 rounding of each operand of the layer's product
+//   --num-layer  GIN or GCN with --emb-dim 300: OGB's num_layer, 2 .. 8 (flowgnn_set_num_layers; default 5).  The weights directory's files
+//                keep their names and hold N layers (with --eps N floats, with --ogb-vn N - 1 updates); a file of another depth is refused
 //   --numeric    f32 (default), q6.10 or f16.  `host PNA --numeric f16` sends PNA's f16 mode through
 //                flowgnn_group_set_model_numeric_mode_dim at FLOWGNN_EMB_DIM_PNA (80): one f16 rounding of each operand of the layer's
 //                320 -> 3 x 80 contraction, one MFMA per product
@@ -71,6 +73,16 @@ static bool read_exact(const std::string& path, std::vector<T>& dst, size_t star
     return ok;
 }
 
+// floats in a file, -1: it cannot be opened
+static long file_floats(const std::string& path) {
+    FILE* f = fopen(path.c_str(), "rb");
+    if (!f) return -1;
+    long n = -1;
+    if (fseek(f, 0, SEEK_END) == 0) n = ftell(f) / (long)sizeof(float);
+    fclose(f);
+    return n;
+}
+
 static long read_count_file(const std::string& path) {
     FILE* f = fopen(path.c_str(), "r");
     if (!f) return -1;
@@ -106,7 +118,7 @@ static bool read_eig_txt(const std::string& path, std::vector<float>& eig, size_
 int main(int argc, char** argv) {
     if (argc < 2) {
         fprintf(stderr, "Usage: %s <GIN|GIN-VN|GCN|GAT|PNA|DGN> [--graphs DIR] [--weights DIR] [--num-graphs N] [--trials T] "
-                        "[--out FILE] [--embeddings FILE] [--node-embeddings FILE] [--node-logits FILE] [--attention FILE [--attention-layers MASK]] [--device D | --devices D0,D1,..] [--option key=value] [--numeric f32|q6.10|f16] [--pooling mean|sum|max] [--eps] [--ogb-vn] [--attn-pool] [--set2set [--set2set-steps N]] [--jk last|sum] [--residual] [--emb-dim 100|300] [--num-tasks T] [--eig DIR | --compute-eig] [XCLBIN File]\n", argv[0]);
+                        "[--out FILE] [--embeddings FILE] [--node-embeddings FILE] [--node-logits FILE] [--attention FILE [--attention-layers MASK]] [--device D | --devices D0,D1,..] [--option key=value] [--numeric f32|q6.10|f16] [--pooling mean|sum|max] [--eps] [--ogb-vn] [--attn-pool] [--set2set [--set2set-steps N]] [--jk last|sum] [--residual] [--emb-dim 100|300] [--num-layer N] [--num-tasks T] [--eig DIR | --compute-eig] [XCLBIN File]\n", argv[0]);
         return EXIT_FAILURE;
     }
     const std::string model = argv[1];
@@ -117,7 +129,7 @@ int main(int argc, char** argv) {
     int attn_mask = 16;
     int trials = 25, numeric = FLOWGNN_NUMERIC_F32, num_tasks = 1, pooling = FLOWGNN_POOL_MEAN, emb_dim = FLOWGNN_EMB_DIM_REFERENCE;
     bool use_eps = false, use_ogb_vn = false, use_attn_pool = false, use_set2set = false, compute_eig = false;
-    int set2set_steps = 2, jk = FLOWGNN_JK_LAST, residual = 0;
+    int set2set_steps = 2, jk = FLOWGNN_JK_LAST, residual = 0, num_layer = FLOWGNN_NUM_LAYERS_DEFAULT;
     std::vector<int> devices;
     std::vector<std::pair<std::string, double>> options;
     for (int i = 2; i < argc; i++) {
@@ -154,6 +166,7 @@ int main(int argc, char** argv) {
         }
         else if (a == "--num-tasks") num_tasks = atoi(next("--num-tasks"));  // NUM_TASK of the readout (GIN/src/dcl.h:25), GIN / GIN-VN / GCN
         else if (a == "--emb-dim") emb_dim = atoi(next("--emb-dim"));  // GIN: 300 = OGB's default width (flowgnn_set_emb_dim), the dim300 files of the weights directory
+        else if (a == "--num-layer") num_layer = atoi(next("--num-layer"));  // OGB's num_layer (flowgnn_set_num_layers; GIN, GCN at --emb-dim 300)
         else if (a == "--numeric") {
             const std::string m = next("--numeric");
             numeric = m == "q6.10" ? FLOWGNN_NUMERIC_Q6_10 : m == "f16" ? FLOWGNN_NUMERIC_F16 : FLOWGNN_NUMERIC_F32;
@@ -200,6 +213,10 @@ int main(int argc, char** argv) {
         rc = mid == FLOWGNN_MODEL_GCN ? flowgnn_group_set_model_emb_dim(eng, emb_dim) : flowgnn_group_set_emb_dim(eng, emb_dim);
         if (rc) { fprintf(stderr, "--emb-dim %d: %d %s\n", emb_dim, rc, flowgnn_group_last_error(eng)); return EXIT_FAILURE; }
     }
+    if (num_layer != FLOWGNN_NUM_LAYERS_DEFAULT) {  // behind the width (the depth is a choice at 300), in front of the weights (they are a depth's)
+        rc = flowgnn_group_set_num_layers(eng, emb_dim, num_layer);
+        if (rc) { fprintf(stderr, "--num-layer %d: %d %s\n", num_layer, rc, flowgnn_group_last_error(eng)); return EXIT_FAILURE; }
+    }
     rc = flowgnn_group_load_weights_dir(eng, wdir.c_str());
     if (rc) { fprintf(stderr, "loading weights failed: %d %s\n", rc, flowgnn_group_last_error(eng)); return EXIT_FAILURE; }
     if (numeric != FLOWGNN_NUMERIC_F32) {  // the reference's ap_fixed<16,6> bit patterns, or f16 MLP operands (GIN / GIN-VN)
@@ -218,21 +235,32 @@ int main(int argc, char** argv) {
         if (rc) { fprintf(stderr, "--pooling: %d %s\n", rc, flowgnn_group_last_error(eng)); return EXIT_FAILURE; }
     }
     if (use_eps) {
-        std::vector<float> eps(5);
+        std::vector<float> eps((size_t)num_layer);
         const std::string path = wdir + "/gin_ep1_eps_dim" + std::to_string(emb_dim) + ".bin";
-        if (!read_exact(path, eps, 0, 5)) { fprintf(stderr, "--eps: cannot read five floats from %s\n", path.c_str()); return EXIT_FAILURE; }
+        const long have = file_floats(path);
+        if (num_layer != FLOWGNN_NUM_LAYERS_DEFAULT && have >= 0 && have != num_layer) {
+            fprintf(stderr, "--eps: %s holds the eps of %ld layers, and --num-layer is %d\n", path.c_str(), have, num_layer);
+            return EXIT_FAILURE;
+        }
+        if (!read_exact(path, eps, 0, eps.size())) { fprintf(stderr, "--eps: cannot read %s floats from %s\n", num_layer == 5 ? "five" : std::to_string(num_layer).c_str(), path.c_str()); return EXIT_FAILURE; }
         rc = flowgnn_group_set_gin_eps(eng, eps.data());
         if (rc) { fprintf(stderr, "--eps: %d %s\n", rc, flowgnn_group_last_error(eng)); return EXIT_FAILURE; }
     }
     if (use_ogb_vn) {
         const bool gcn = mid == FLOWGNN_MODEL_GCN;
         const bool wide = emb_dim != FLOWGNN_EMB_DIM_REFERENCE;  // --emb-dim 300: the file of that width, through the call that carries it
-        const size_t L = FLOWGNN_OGB_VN_LAYERS, D = wide ? (size_t)emb_dim : 100, H = 2 * D;
+        const size_t L = (size_t)num_layer - 1 /* FLOWGNN_OGB_VN_LAYERS at the default depth */, D = wide ? (size_t)emb_dim : 100, H = 2 * D;
         const size_t at[6] = {0, D, D + L * H * D, D + L * H * D + L * H, D + 2 * L * H * D + L * H, D + 2 * L * H * D + L * H + L * D};
         std::vector<float> vn(at[5]);
         const std::string path = wdir + (gcn ? "/gcn_ep1_virtualnode_dim" : "/gin_ep1_virtualnode_dim") + std::to_string(D) + ".bin";
         const char* const call = wide ? (gcn ? "flowgnn_set_gcn_virtual_node_dim" : "flowgnn_set_ogb_virtual_node_dim")
                                       : (gcn ? "flowgnn_set_gcn_virtual_node" : "flowgnn_set_ogb_virtual_node");
+        const long have = file_floats(path);
+        if (num_layer != FLOWGNN_NUM_LAYERS_DEFAULT && have >= 0 && (size_t)have != vn.size()) {
+            fprintf(stderr, "--ogb-vn: %s holds %ld floats, and the tensors of %d updates (--num-layer %d) are %zu\n", path.c_str(), have, num_layer - 1,
+                    num_layer, vn.size());
+            return EXIT_FAILURE;
+        }
         if (!read_exact(path, vn, 0, vn.size())) {
             fprintf(stderr, "--ogb-vn: cannot read %zu floats from %s (the tensors of %s)\n", vn.size(), path.c_str(), call);
             return EXIT_FAILURE;

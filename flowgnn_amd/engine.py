@@ -55,23 +55,26 @@ def _pf(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(_lib.p_float)
 
 
-def _eps_arg(eps):
-    """None -> NULL (off); else the five values as a float32 array (ctypes takes its pointer for the duration of the call)."""
+def _eps_arg(eps, num_layers: int = 5):
+    """None -> NULL (off); else the five values as a float32 array (ctypes takes its pointer for the duration of the call).  "Five" is
+    the engine's depth (flowgnn_num_layers): the C call reads that many."""
     if eps is None:
         return None
     a = np.ascontiguousarray(np.asarray(eps, dtype=np.float32).reshape(-1))
-    if a.size != 5:
-        raise ValueError(f"eps: five values (one per GIN layer), got {a.size}")
-    return (C.c_float * 5)(*a.tolist())
+    n = int(num_layers)
+    if a.size != n:
+        raise ValueError(f"eps: {'five' if n == 5 else n} values (one per GIN layer), got {a.size}")
+    return (C.c_float * n)(*a.tolist())
 
 
-def _ogb_vn_args(vn, emb_dims=(100, 300)):
+def _ogb_vn_args(vn, emb_dims=(100, 300), num_layers: int = 5):
     """None -> five NULLs (off); else the dict's five tensors (weights.GIN_VIRTUAL_NODE_SHAPES) as float32 arrays, in the C call's
-    order -- the caller keeps them alive for the duration of the call."""
+    order -- the caller keeps them alive for the duration of the call.  num_layers: the engine's depth (flowgnn_num_layers): the C call
+    reads num_layers - 1 updates, so tensors of another depth are refused here, before it sees a pointer."""
     if vn is None:
         return [None] * 5
     from .weights import checked_gin_virtual_node
-    return list(checked_gin_virtual_node(vn, emb_dims=emb_dims).values())
+    return list(checked_gin_virtual_node(vn, emb_dims=emb_dims, num_layers=int(num_layers)).values())
 
 
 def _attn_pool_args(gate):
@@ -99,14 +102,27 @@ def _ogb_vn_dim(a) -> int:
     return 100 if a[0] is None else int(a[0].size)
 
 
-def _gcn_vn_args(vn, engine_dim):
+def _gcn_vn_args(vn, engine_dim, num_layers: int = 5):
     """_ogb_vn_args for GCN's two calls: 300-wide tensors are for an engine at set_model_emb_dim(300) alone -- on any other they
     are refused here, before a C call sees a pointer."""
-    a = _ogb_vn_args(vn)
+    a = _ogb_vn_args(vn, num_layers=num_layers)
     if _ogb_vn_dim(a) != 100 and _ogb_vn_dim(a) != int(engine_dim):
         raise ValueError(f"set_gcn_virtual_node: the tensors are {_ogb_vn_dim(a)} wide and the engine's width is {int(engine_dim)} "
                          "(set_model_emb_dim(300) first)")
     return a
+
+
+def _check_weights_depth(model: str, w, num_layers: int) -> None:
+    """GIN / GIN-VN / GCN: the C call reads num_layers blocks of every per-layer tensor through a bare pointer, so a weight set of
+    another depth (flowgnn_set_num_layers) is refused here, before it sees one.  The depth is read off the per-layer edge table,
+    [L][13][D] with D the row length of the node table; a set without those two names is left to the C call as ever."""
+    if model not in ("GIN", "GIN-VN", "GCN") or not hasattr(w, "keys") or not {"node_embedding_weight", "edge_embedding_weight"} <= set(w.keys()):
+        return
+    d = np.asarray(w["node_embedding_weight"]).size // 173
+    have = np.asarray(w["edge_embedding_weight"]).size
+    if d and have != int(num_layers) * 13 * d:
+        raise ValueError(f"set_weights: edge_embedding_weight holds {have / (13 * d):g} layers of {d}-wide rows and the engine's depth is "
+                         f"{int(num_layers)} (set_num_layers / flowgnn_set_num_layers)")
 
 
 def option_value(v) -> float:
@@ -213,6 +229,7 @@ class Engine:
     # ---- weights
     def set_weights(self, w: Dict[str, np.ndarray]):
         """`w`: OrderedDict in the argument order of the model's <M>_compute_graphs entry point."""
+        _check_weights_depth(self.model, w, self.num_layers)
         arrs = [_f32(v) for v in w.values()]
         ptrs = (_lib.p_float * len(arrs))(*[_pf(a) for a in arrs])
         self._check(self.lib.flowgnn_set_weights(self._h, len(arrs), ptrs), "flowgnn_set_weights")
@@ -226,17 +243,19 @@ class Engine:
         attention_pooling=True (GIN, GCN at width 300): also read gin_ep1_attnpool_dim300.bin / gcn_ep1_attnpool_dim300.bin and apply it
         (set_attention_pooling).
         set2set=True (GIN, GCN at width 300): also read gin_ep1_set2set_dim300.bin / gcn_ep1_set2set_dim300.bin and apply it with
-        set2set_steps processing steps (set_set2set_pooling; OGB: 2)."""
+        set2set_steps processing steps (set_set2set_pooling; OGB: 2).
+        After set_num_layers the files are read at the engine's depth: the per-layer tensors, num_layers eps values, num_layers - 1
+        updates of the virtual node; a file of another depth is refused."""
         self._check(self.lib.flowgnn_load_weights_dir(self._h, directory.encode()), "flowgnn_load_weights_dir")
         if eps:
             from .weights import load_gin_eps
-            self.set_gin_eps(load_gin_eps(directory, emb_dim=self.emb_dim if self.model == "GIN" else 100))
+            self.set_gin_eps(load_gin_eps(directory, emb_dim=self.emb_dim if self.model == "GIN" else 100, num_layers=self.num_layers))
         if virtual_node and self.model == "GCN":
             from .weights import load_gcn_virtual_node
-            self.set_gcn_virtual_node(load_gcn_virtual_node(directory, emb_dim=self.emb_dim))
+            self.set_gcn_virtual_node(load_gcn_virtual_node(directory, emb_dim=self.emb_dim, num_layers=self.num_layers))
         elif virtual_node:
             from .weights import load_gin_virtual_node
-            self.set_ogb_virtual_node(load_gin_virtual_node(directory, emb_dim=self.emb_dim))
+            self.set_ogb_virtual_node(load_gin_virtual_node(directory, emb_dim=self.emb_dim, num_layers=self.num_layers))
         if attention_pooling:
             from .weights import load_attention_pooling
             self.set_attention_pooling(load_attention_pooling(directory, model=self.model, emb_dim=self.emb_dim))
@@ -498,6 +517,17 @@ class Engine:
         self._check(self.lib.flowgnn_set_num_tasks(self._h, int(num_tasks)), "flowgnn_set_num_tasks")
         self.num_tasks = int(num_tasks)
 
+    def set_num_layers(self, n: int, emb_dim: int = 300):
+        """GIN's or GCN's depth at width 300, OGB's num_layer (flowgnn.h: flowgnn_set_num_layers): 2 .. 8, 5 by default; set behind the
+        width and before weights and batch (both have to be set again after a change).  eps and the virtual node must be off while it
+        changes: their tensors are a depth's."""
+        self._check(self.lib.flowgnn_set_num_layers(self._h, int(emb_dim), int(n)), "flowgnn_set_num_layers")
+
+    @property
+    def num_layers(self) -> int:
+        """The engine's depth (flowgnn.h: flowgnn_num_layers): 5 unless set_num_layers said otherwise."""
+        return int(self.lib.flowgnn_num_layers(self._h))
+
     def set_emb_dim(self, emb_dim: int):
         """GIN's width (flowgnn.h: flowgnn_set_emb_dim): 100, the reference's, or 300, OGB's default; set before weights and batch
         (both have to be set again afterwards)."""
@@ -673,11 +703,11 @@ class Engine:
     def set_gin_eps(self, eps=None):
         """GIN / GIN-VN: apply a trained eps, five values, one per layer -- a[v] = (1 + eps[l]) h[v] + sum of messages (flowgnn.h:
         flowgnn_set_gin_eps).  None turns it off (the default: the reference has no eps).  The engine's, across batches and weight sets."""
-        self._check(self.lib.flowgnn_set_gin_eps(self._h, _eps_arg(eps)), "flowgnn_set_gin_eps")
+        self._check(self.lib.flowgnn_set_gin_eps(self._h, _eps_arg(eps, self.num_layers)), "flowgnn_set_gin_eps")
 
     def gin_eps(self):
-        """The five values as float32[5], or None while eps is off (flowgnn.h: flowgnn_gin_eps)."""
-        out = np.zeros(5, np.float32)
+        """The five values as float32[5] (float32[num_layers] after set_num_layers), or None while eps is off (flowgnn.h: flowgnn_gin_eps)."""
+        out = np.zeros(self.num_layers, np.float32)
         return out if int(self.lib.flowgnn_gin_eps(self._h, _pf(out))) == 1 else None
 
     def set_ogb_virtual_node(self, vn=None):
@@ -686,7 +716,7 @@ class Engine:
         export.gin_virtual_node_from_ogb_state_dict); None turns it off.  The engine's, across batches and weight sets.
         300-wide tensors ([300], [4][600][300], ...: weights.gin_virtual_node_shapes(300)) go through the call that carries the width,
         flowgnn_set_ogb_virtual_node_dim, for an engine at set_emb_dim(300); 100-wide ones through the call that has none."""
-        a = _ogb_vn_args(vn)
+        a = _ogb_vn_args(vn, num_layers=self.num_layers)
         if _ogb_vn_dim(a) == 100:  # (at width 300 that is the call's own refusal: it has no width argument)
             self._check(self.lib.flowgnn_set_ogb_virtual_node(self._h, *[_pf(x) for x in a]), "flowgnn_set_ogb_virtual_node")
         else:
@@ -701,7 +731,7 @@ class Engine:
         set_ogb_virtual_node (export.gcn_virtual_node_from_ogb_state_dict); None turns it off.  The engine's, across batches and
         weight sets.  300-wide tensors go through the call that carries the width, flowgnn_set_gcn_virtual_node_dim, for an engine at
         set_model_emb_dim(300) (on any other: ValueError); 100-wide ones through the call that has none."""
-        a = _gcn_vn_args(vn, self.emb_dim)
+        a = _gcn_vn_args(vn, self.emb_dim, self.num_layers)
         if _ogb_vn_dim(a) == 100:  # (at width 300 that is the call's own refusal: it has no width argument)
             self._check(self.lib.flowgnn_set_gcn_virtual_node(self._h, *[_pf(x) for x in a]), "flowgnn_set_gcn_virtual_node")
         else:
@@ -848,6 +878,7 @@ class EngineGroup:
             pass
 
     def set_weights(self, w: Dict[str, np.ndarray]):
+        _check_weights_depth(self.model, w, self.num_layers)
         arrs = [_f32(v) for v in w.values()]
         ptrs = (_lib.p_float * len(arrs))(*[_pf(a) for a in arrs])
         self._check(self.lib.flowgnn_group_set_weights(self._h, len(arrs), ptrs), "flowgnn_group_set_weights")
@@ -866,6 +897,15 @@ class EngineGroup:
     def set_model_emb_dim(self, emb_dim: int):
         """GIN's or GCN's width on every member (flowgnn.h: flowgnn_group_set_model_emb_dim)."""
         self._check(self.lib.flowgnn_group_set_model_emb_dim(self._h, int(emb_dim)), "flowgnn_group_set_model_emb_dim")
+
+    def set_num_layers(self, n: int, emb_dim: int = 300):
+        """Engine.set_num_layers on every member (flowgnn.h: flowgnn_group_set_num_layers); weights and batch have to be set again afterwards."""
+        self._check(self.lib.flowgnn_group_set_num_layers(self._h, int(emb_dim), int(n)), "flowgnn_group_set_num_layers")
+
+    @property
+    def num_layers(self) -> int:
+        """The members' depth (the first member answers, as for the width)."""
+        return int(self.lib.flowgnn_num_layers(self.lib.flowgnn_group_engine(self._h, 0)))
 
     @property
     def emb_dim(self) -> int:
@@ -897,11 +937,11 @@ class EngineGroup:
 
     def set_gin_eps(self, eps=None):
         """Engine.set_gin_eps on every member (flowgnn.h: flowgnn_group_set_gin_eps)."""
-        self._check(self.lib.flowgnn_group_set_gin_eps(self._h, _eps_arg(eps)), "flowgnn_group_set_gin_eps")
+        self._check(self.lib.flowgnn_group_set_gin_eps(self._h, _eps_arg(eps, self.num_layers)), "flowgnn_group_set_gin_eps")
 
     def set_ogb_virtual_node(self, vn=None):
         """Engine.set_ogb_virtual_node on every member (flowgnn.h: flowgnn_group_set_ogb_virtual_node)."""
-        a = _ogb_vn_args(vn)
+        a = _ogb_vn_args(vn, num_layers=self.num_layers)
         if _ogb_vn_dim(a) == 100:
             self._check(self.lib.flowgnn_group_set_ogb_virtual_node(self._h, *[_pf(x) for x in a]), "flowgnn_group_set_ogb_virtual_node")
         else:
@@ -910,7 +950,7 @@ class EngineGroup:
 
     def set_gcn_virtual_node(self, vn=None):
         """Engine.set_gcn_virtual_node on every member (flowgnn.h: flowgnn_group_set_gcn_virtual_node)."""
-        a = _gcn_vn_args(vn, self.emb_dim)
+        a = _gcn_vn_args(vn, self.emb_dim, self.num_layers)
         if _ogb_vn_dim(a) == 100:
             self._check(self.lib.flowgnn_group_set_gcn_virtual_node(self._h, *[_pf(x) for x in a]), "flowgnn_group_set_gcn_virtual_node")
         else:

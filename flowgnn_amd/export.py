@@ -77,6 +77,28 @@ def gin_eps_from_ogb_state_dict(sd: Mapping, num_layers: int = 5) -> np.ndarray:
     return out
 
 
+def num_layers_of_ogb_state_dict(sd: Mapping) -> int:
+    """OGB's num_layer read off a GNN(...) state_dict: the number of `gnn_node.convs.<l>` blocks, which must be numbered 0 .. L - 1."""
+    idx = set()
+    for k in sd:
+        parts = str(k).split(".")
+        if len(parts) > 3 and parts[0] == "gnn_node" and parts[1] == "convs" and parts[2].isdigit():
+            idx.add(int(parts[2]))
+    if not idx:
+        raise ExportError("state_dict has no 'gnn_node.convs.<l>.*' keys: not an OGB GNN(...) model")
+    if idx != set(range(len(idx))):
+        raise ExportError(f"'gnn_node.convs' has the layers {sorted(idx)}: wanted 0 .. {len(idx) - 1}")
+    return len(idx)
+
+
+def _checked_depth(num_layers: int, width: int) -> int:
+    """The depths the engine runs (flowgnn_set_num_layers): 2 .. 8 at width 300, 5 alone at width 100."""
+    try:
+        return _weights._depth(num_layers, width)
+    except ValueError as e:
+        raise ExportError(f"{e}: the state_dict is {num_layers} layers deep and {width} wide")
+
+
 VN_KEY = "gnn_node.virtualnode_embedding.weight"  # what tells a gin-virtual state_dict from a gin one
 
 
@@ -106,7 +128,7 @@ def _virtual_node_from_ogb_state_dict(sd: Mapping, num_layers: int, dim: int = 1
             w2, b2 = _get(sd, f"{m}.2.weight"), _get(sd, f"{m}.2.bias")
         w1s.append(w1); b1s.append(b1); w2s.append(w2); b2s.append(b2)
     out = OrderedDict([("vn_embedding", emb), ("w1", np.stack(w1s)), ("b1", np.stack(b1s)), ("w2", np.stack(w2s)), ("b2", np.stack(b2s))])
-    return _checked(out, _weights.gin_virtual_node_shapes(dim), lambda k, v: v)
+    return _checked(out, _weights.gin_virtual_node_shapes(dim, _checked_depth(num_layers, dim)), lambda k, v: v)
 
 
 def gin_virtual_node_from_ogb_state_dict(sd: Mapping, num_layers: int = 5, virtual_node_dim: int = 100) -> Dict[str, np.ndarray]:
@@ -253,7 +275,7 @@ def gin_weights_from_ogb_state_dict(sd: Mapping, num_layers: int = 5, eps_tol: f
         raise ExportError(f"graph_pred_linear has {pw.shape[0]} tasks; the reference is built with NUM_TASK = 1 (GIN/src/dcl.h:25): "
                           f"pass multi_task=True for an engine with flowgnn_set_num_tasks({pw.shape[0]})")
     out["graph_pred_weights"], out["graph_pred_bias"] = pw, pb
-    return _checked(out, _weights.gin_files(width), lambda k, v: _weights._task_shape(k, v[1], pw.shape[0]))
+    return _checked(out, _weights.gin_files(width, _checked_depth(num_layers, width)), lambda k, v: _weights._task_shape(k, v[1], pw.shape[0]))
 
 
 def gcn_weights_from_ogb_state_dict(sd: Mapping, num_layers: int = 5, multi_task: bool = False,
@@ -274,7 +296,7 @@ def gcn_weights_from_ogb_state_dict(sd: Mapping, num_layers: int = 5, multi_task
         raise ExportError(f"emb_dim {emb_dim}: the engine runs GCN at emb_dim {_weights.GCN_EMB_DIMS[0]} (the reference's width) and "
                           f"{_weights.GCN_EMB_DIMS[1]} (OGB's default), no other")
     emb_dim = int(emb_dim)
-    shapes = _weights.gcn_shapes(emb_dim)
+    shapes = _weights.gcn_shapes(emb_dim, _checked_depth(num_layers, emb_dim))
     if vdim != 100 and vdim != emb_dim:
         raise ExportError(f"virtual_node_dim is {vdim} and emb_dim is {emb_dim}: the virtual node has the model's width")
     if emb_dim != 100:
@@ -363,7 +385,11 @@ def export_weights(model: str, sd: Mapping, directory: str, multi_task: bool = F
     such a model are those of a JK='last', residual=False one.  The CALLER passes the flags the model was trained with to the engine
     (Engine.set_jk_residual / flowgnn_set_jk_residual; `host GIN --emb-dim 300 --jk sum --residual`); nothing can check them.  That
     holds for GCN too (gcn and gcn-virtual at width 300): Engine.set_jk_residual / flowgnn_set_model_jk_residual;
-    `host GCN --emb-dim 300 [--ogb-vn] --jk sum --residual`."""
+    `host GCN --emb-dim 300 [--ogb-vn] --jk sum --residual`.
+    OGB's num_layer is read off the state_dict (num_layers_of_ogb_state_dict: the `gnn_node.convs.<l>` blocks) and sizes every per-layer
+    tensor, the eps file and the virtual node's file; the file names stay the same.  A depth other than 5 is for an engine with
+    flowgnn_set_num_layers(300, depth) / Engine.set_num_layers(depth) / `host GIN|GCN --emb-dim 300 --num-layer depth`; a depth outside
+    2 .. 8, and a depth other than 5 at width 100, are refused before any file is written."""
     m = model.upper()
     if set2set and m not in ("GIN", "GCN"):
         raise ExportError(f"set2set=True is GIN's and GCN's (flowgnn_set_set2set_pooling); {model} has no such readout")
@@ -385,16 +411,25 @@ def export_weights(model: str, sd: Mapping, directory: str, multi_task: bool = F
                           f"flowgnn_set_gcn_virtual_node_dim); {model} has no such virtual node")
     if virtual_node and m not in ("GIN", "GCN"):
         raise ExportError(f"virtual_node=True is OGB's gin-virtual or gcn-virtual, which the engine runs as GIN or GCN (not {model})")
+    depth = num_layers_of_ogb_state_dict(sd) if m in ("GIN", "GIN-VN", "GCN") else 5
+    if m in ("GIN", "GIN-VN", "GCN"):  # (before any file is written; the width as the two exporters below read it)
+        width = int(emb_dim) if m == "GCN" else int(_get(sd, "gnn_node.atom_encoder.atom_embedding_list.0.weight").shape[-1])
+        if not _weights.MIN_NUM_LAYERS <= depth <= _weights.MAX_NUM_LAYERS:
+            raise ExportError(f"the state_dict is {depth} layers deep (gnn_node.convs.*): flowgnn_set_num_layers takes "
+                              f"{_weights.MIN_NUM_LAYERS} .. {_weights.MAX_NUM_LAYERS}")
+        if depth != 5 and (width == 100 or m == "GIN-VN"):
+            raise ExportError(f"the state_dict is {depth} layers deep (gnn_node.convs.*) and {'GIN-VN' if m == 'GIN-VN' else '100 wide'}: only the 300-wide GIN and GCN "
+                              f"run a depth other than 5 (flowgnn_set_num_layers)")
     s2s = None
     if set2set:  # (before any file is written; the width: GIN's own, read off the state_dict as gin_weights_from_ogb_state_dict reads it)
         s2s = set2set_from_ogb_state_dict(sd, emb_dim=_get(sd, "gnn_node.atom_encoder.atom_embedding_list.0.weight").shape[1] if m == "GIN" else int(emb_dim))
         sd = _mean_head_zeroed(sd, s2s["w_hh"].shape[1])
     if m in ("GIN", "GIN-VN"):
-        w = gin_weights_from_ogb_state_dict(sd, multi_task=multi_task, keep_eps=keep_eps, virtual_node=virtual_node,
+        w = gin_weights_from_ogb_state_dict(sd, num_layers=depth, multi_task=multi_task, keep_eps=keep_eps, virtual_node=virtual_node,
                                             virtual_node_dim=virtual_node_dim)
-        vn = gin_virtual_node_from_ogb_state_dict(sd, virtual_node_dim=virtual_node_dim) if virtual_node else None  # (before any file is written)
+        vn = gin_virtual_node_from_ogb_state_dict(sd, num_layers=depth, virtual_node_dim=virtual_node_dim) if virtual_node else None  # (before any file is written)
         gate = attention_pooling_from_ogb_state_dict(sd, emb_dim=_weights.gin_emb_dim_of(w)) if attention_pooling else None  # (likewise)
-        _weights.save_gin_weights(w, directory, eps=gin_eps_from_ogb_state_dict(sd) if keep_eps else None)
+        _weights.save_gin_weights(w, directory, eps=gin_eps_from_ogb_state_dict(sd, num_layers=depth) if keep_eps else None)
         if virtual_node:
             _weights.save_gin_virtual_node(vn, directory)
         if attention_pooling:
@@ -402,8 +437,8 @@ def export_weights(model: str, sd: Mapping, directory: str, multi_task: bool = F
         if set2set:
             _weights.save_set2set(s2s, directory, model="GIN")
     elif m == "GCN":
-        w = gcn_weights_from_ogb_state_dict(sd, multi_task=multi_task, virtual_node=virtual_node, emb_dim=emb_dim, virtual_node_dim=virtual_node_dim)
-        vn = gcn_virtual_node_from_ogb_state_dict(sd, virtual_node_dim=virtual_node_dim) if virtual_node else None  # (before any file is written)
+        w = gcn_weights_from_ogb_state_dict(sd, num_layers=depth, multi_task=multi_task, virtual_node=virtual_node, emb_dim=emb_dim, virtual_node_dim=virtual_node_dim)
+        vn = gcn_virtual_node_from_ogb_state_dict(sd, num_layers=depth, virtual_node_dim=virtual_node_dim) if virtual_node else None  # (before any file is written)
         gate = attention_pooling_from_ogb_state_dict(sd, emb_dim=int(emb_dim)) if attention_pooling else None  # (likewise)
         _weights.save_gcn_weights(w, directory)
         if virtual_node:

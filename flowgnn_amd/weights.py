@@ -47,16 +47,57 @@ def _task_shape(k: str, shp, num_tasks: int):
     return tuple(shp)
 
 
+NUM_LAYERS_DEFAULT, MIN_NUM_LAYERS, MAX_NUM_LAYERS = 5, 2, 8  # flowgnn.h: FLOWGNN_NUM_LAYERS_DEFAULT, FLOWGNN_MIN_NUM_LAYERS, FLOWGNN_MAX_NUM_LAYERS
+
+
+def _depth(num_layers, emb_dim) -> int:
+    """OGB's num_layer as the loaders and savers take it (flowgnn_set_num_layers): 2 .. 8, and 5 alone at width 100."""
+    n = int(num_layers)
+    if not MIN_NUM_LAYERS <= n <= MAX_NUM_LAYERS:
+        raise ValueError(f"num_layers {num_layers} is outside {MIN_NUM_LAYERS} .. {MAX_NUM_LAYERS} (flowgnn_set_num_layers)")
+    if n != NUM_LAYERS_DEFAULT and int(emb_dim) == 100:
+        raise ValueError(f"num_layers {n} at emb_dim 100: the 100-wide kernels are five layers deep; only the 300-wide models have a "
+                         f"depth other than 5 (flowgnn_set_num_layers)")
+    return n
+
+
+def _check_depth_of_file(path: str, fixed: int, per_layer: int, num_layers: int, shift: int = 0) -> None:
+    """Refuse a file whose size is fixed + (k + shift) per_layer floats for a depth k other than num_layers: both depths are named.
+    (Any other size is left to the reads, which refuse a short file.)  shift: -1 for the virtual node's files, one block per update."""
+    if not os.path.exists(path) or os.path.getsize(path) % 4:
+        return
+    floats = os.path.getsize(path) // 4
+    if floats == fixed + (num_layers + shift) * per_layer:
+        return
+    for k in range(MIN_NUM_LAYERS, MAX_NUM_LAYERS + 1):
+        if floats == fixed + (k + shift) * per_layer:
+            raise ValueError(f"{path} holds the tensors of a model {k} layers deep, and num_layers is {num_layers} (flowgnn_set_num_layers)")
+
+
 GIN_EMB_DIMS = (100, 300)  # the reference's width, and OGB's default (flowgnn_set_emb_dim: FLOWGNN_EMB_DIM_REFERENCE / _OGB)
 
 
-def gin_files(emb_dim: int = 100):
-    """GIN_FILES at width emb_dim: the reference's names with dim<emb_dim> in place of dim100, the shapes with 100 -> D, 200 -> 2 D."""
+_GIN_PER_LAYER = ("edge_embedding_weight", "node_mlp_1_weights", "node_mlp_1_bias", "node_mlp_2_weights", "node_mlp_2_bias")
+
+
+def gin_files(emb_dim: int = 100, num_layers: int = 5):
+    """GIN_FILES at width emb_dim and depth num_layers: the reference's names with dim<emb_dim> in place of dim100 (the depth is not in
+    a name), the shapes with 100 -> D, 200 -> 2 D and the leading 5 of the per-layer tensors -> num_layers."""
     d = int(emb_dim)
     if d not in GIN_EMB_DIMS:
         raise ValueError(f"GIN: emb_dim {emb_dim} is not one of {GIN_EMB_DIMS}")
+    n = _depth(num_layers, d)
     grow = {100: d, 200: 2 * d}
-    return OrderedDict((k, (f.replace("dim100", f"dim{d}"), tuple(grow.get(n, n) for n in shp))) for k, (f, shp) in GIN_FILES.items())
+    out = OrderedDict()
+    for k, (f, shp) in GIN_FILES.items():
+        wide = tuple(grow.get(x, x) for x in shp)
+        out[k] = (f.replace("dim100", f"dim{d}"), (n,) + wide[1:] if k in _GIN_PER_LAYER else wide)
+    return out
+
+
+def gin_num_layers_of(w) -> int:
+    """The depth of a GIN or GCN weight set: the leading dimension of its per-layer edge table."""
+    return int(np.asarray(w["edge_embedding_weight"]).shape[0])
 
 
 def gin_emb_dim_of(w) -> int:
@@ -64,8 +105,12 @@ def gin_emb_dim_of(w) -> int:
     return int(np.asarray(w["node_embedding_weight"]).shape[-1])
 
 
-def load_gin_weights(directory: str, num_tasks: int = 1, emb_dim: int = 100) -> Dict[str, np.ndarray]:
-    return OrderedDict((k, _read(os.path.join(directory, f), _task_shape(k, shp, num_tasks))) for k, (f, shp) in gin_files(emb_dim).items())
+def load_gin_weights(directory: str, num_tasks: int = 1, emb_dim: int = 100, num_layers: int = 5) -> Dict[str, np.ndarray]:
+    """num_layers: the depth the files were written for (flowgnn_set_num_layers); a per-layer file of another depth is refused."""
+    files = gin_files(emb_dim, num_layers)
+    for k in _GIN_PER_LAYER:
+        _check_depth_of_file(os.path.join(directory, files[k][0]), 0, int(np.prod(files[k][1][1:])), int(num_layers))
+    return OrderedDict((k, _read(os.path.join(directory, f), _task_shape(k, shp, num_tasks))) for k, (f, shp) in files.items())
 
 
 GIN_EPS_FILE = "gin_ep1_eps_dim100.bin"  # five LE float32, one per layer: read by the reference host and never used
@@ -75,21 +120,29 @@ def gin_eps_file(emb_dim: int = 100) -> str:
     return GIN_EPS_FILE.replace("dim100", f"dim{int(emb_dim)}")
 
 
-def load_gin_eps(directory: str, emb_dim: int = 100) -> np.ndarray:
-    """The five eps values of a GIN / GIN-VN weights directory, float32[5] (for Engine.set_gin_eps: flowgnn_set_gin_eps)."""
-    return _read(os.path.join(directory, gin_eps_file(emb_dim)), (5,))
+def load_gin_eps(directory: str, emb_dim: int = 100, num_layers: int = 5) -> np.ndarray:
+    """The eps values of a GIN / GIN-VN weights directory, float32[num_layers] -- five unless the depth says otherwise (for
+    Engine.set_gin_eps: flowgnn_set_gin_eps); a file of another depth is refused."""
+    n = _depth(num_layers, emb_dim)
+    path = os.path.join(directory, gin_eps_file(emb_dim))
+    _check_depth_of_file(path, 0, 1, n)
+    return _read(path, (n,))
 
 
-def save_gin_weights(w: Dict[str, np.ndarray], directory: str, eps=None, emb_dim=None) -> None:
-    """eps: the five trained values for the eps file (None: zeros, what the reference's own sets carry).  Nothing applies the file
-    unless asked to: `host --eps`, Engine.load_weights_dir(dir, eps=True).  emb_dim: None = the arrays' own width (which names the
-    files: dim100 / dim300)."""
-    os.makedirs(directory, exist_ok=True)
+def save_gin_weights(w: Dict[str, np.ndarray], directory: str, eps=None, emb_dim=None, num_layers=None) -> None:
+    """eps: the trained values, one per layer, for the eps file (None: zeros, what the reference's own sets carry).  Nothing applies the
+    file unless asked to: `host --eps`, Engine.load_weights_dir(dir, eps=True).  emb_dim: None = the arrays' own width (which names the
+    files: dim100 / dim300).  num_layers: None = the arrays' own depth; a number must agree with it."""
     tasks = int(np.asarray(w["graph_pred_bias"]).size)
     d = gin_emb_dim_of(w) if emb_dim is None else int(emb_dim)
-    for k, (f, shp) in gin_files(d).items():
+    n = gin_num_layers_of(w)
+    if num_layers is not None and int(num_layers) != n:
+        raise ValueError(f"GIN: the tensors are {n} layers deep, num_layers says {num_layers}")
+    files = gin_files(d, n)  # (a depth that does not exist is refused before anything is created)
+    os.makedirs(directory, exist_ok=True)
+    for k, (f, shp) in files.items():
         np.asarray(w[k], dtype="<f4").reshape(_task_shape(k, shp, tasks)).tofile(os.path.join(directory, f))
-    e = np.zeros(5, dtype="<f4") if eps is None else np.asarray(eps, dtype="<f4").reshape(5)
+    e = np.zeros(n, dtype="<f4") if eps is None else np.asarray(eps, dtype="<f4").reshape(n)
     e.tofile(os.path.join(directory, gin_eps_file(d)))  # (zeros: read by the reference, never used)
 
 
@@ -102,13 +155,21 @@ GIN_VIRTUAL_NODE_SHAPES = OrderedDict([
 GIN_VIRTUAL_NODE_FLOATS = sum(int(np.prod(s)) for s in GIN_VIRTUAL_NODE_SHAPES.values())  # 161 300
 
 
-def gin_virtual_node_shapes(emb_dim: int = 100):
-    """GIN_VIRTUAL_NODE_SHAPES at width emb_dim (flowgnn_set_ogb_virtual_node_dim): 100 -> D, 200 -> 2 D."""
+def gin_virtual_node_shapes(emb_dim: int = 100, num_layers: int = 5):
+    """GIN_VIRTUAL_NODE_SHAPES at width emb_dim (flowgnn_set_ogb_virtual_node_dim): 100 -> D, 200 -> 2 D; and at depth num_layers
+    (flowgnn_set_num_layers): the leading 4 of the four per-update tensors -> num_layers - 1."""
     d = int(emb_dim)
     if d not in GIN_EMB_DIMS:
         raise ValueError(f"virtual node: emb_dim {emb_dim} is not one of {GIN_EMB_DIMS}")
+    u = _depth(num_layers, d) - 1
     grow = {100: d, 200: 2 * d}
-    return OrderedDict((k, tuple(grow.get(n, n) for n in shp)) for k, shp in GIN_VIRTUAL_NODE_SHAPES.items())
+    return OrderedDict((k, tuple(grow.get(n, n) for n in shp) if k == "vn_embedding" else (u,) + tuple(grow.get(n, n) for n in shp[1:]))
+                       for k, shp in GIN_VIRTUAL_NODE_SHAPES.items())
+
+
+def gin_virtual_node_num_layers_of(vn) -> int:
+    """The depth a virtual node's tensors belong to: its updates (the rows of b2) + 1."""
+    return int(np.asarray(vn["b2"]).size) // gin_virtual_node_dim_of(vn) + 1
 
 
 def gin_virtual_node_file(emb_dim: int = 100) -> str:
@@ -122,16 +183,17 @@ def gin_virtual_node_dim_of(vn) -> int:
     return int(np.asarray(vn["vn_embedding"]).size)
 
 
-def checked_gin_virtual_node(vn, emb_dims=GIN_EMB_DIMS) -> Dict[str, np.ndarray]:
+def checked_gin_virtual_node(vn, emb_dims=GIN_EMB_DIMS, num_layers=None) -> Dict[str, np.ndarray]:
     """The dict `vn` with exactly the five keys, each as a contiguous float32 array of its shape at the width read off vn_embedding's
-    size, which must be one of emb_dims (GCN's callers pass (100,): its call has no wider form)."""
+    size, which must be one of emb_dims (GCN's callers pass (100,): its call has no wider form).  num_layers: the depth the tensors
+    must have (the engine's: it reads num_layers - 1 updates); None = the tensors' own, read off b2."""
     if set(vn) != set(GIN_VIRTUAL_NODE_SHAPES):
         raise ValueError(f"virtual node: wanted the keys {list(GIN_VIRTUAL_NODE_SHAPES)}, got {sorted(vn)}")
     d = gin_virtual_node_dim_of(vn)
     if d not in tuple(emb_dims):
         raise ValueError(f"virtual node: vn_embedding is {np.asarray(vn['vn_embedding']).shape}, wanted a row of one of the widths {tuple(emb_dims)}")
     out = OrderedDict()
-    for k, shp in gin_virtual_node_shapes(d).items():
+    for k, shp in gin_virtual_node_shapes(d, gin_virtual_node_num_layers_of(vn) if num_layers is None else num_layers).items():
         a = np.asarray(vn[k], dtype=np.float32)
         if a.size != int(np.prod(shp)):
             raise ValueError(f"virtual node: {k} is {a.shape}, wanted {shp}")
@@ -152,17 +214,19 @@ def save_gin_virtual_node(vn, directory: str, emb_dim=None) -> None:
     flat.tofile(os.path.join(directory, gin_virtual_node_file(d)))
 
 
-def load_gin_virtual_node(directory: str, emb_dim: int = 100) -> Dict[str, np.ndarray]:
+def load_gin_virtual_node(directory: str, emb_dim: int = 100, num_layers: int = 5) -> Dict[str, np.ndarray]:
     """The five tensors of a directory's virtual-node file of width emb_dim (for Engine.set_ogb_virtual_node); a short file is refused."""
     path = os.path.join(directory, gin_virtual_node_file(emb_dim))
+    d = int(emb_dim)
+    _check_depth_of_file(path, d, 4 * d * d + 3 * d, _depth(num_layers, d), shift=-1)  # (per update: w1, w2, b1, b2; a file of another depth is refused)
     out, at = OrderedDict(), 0
-    for k, shp in gin_virtual_node_shapes(emb_dim).items():
+    for k, shp in gin_virtual_node_shapes(emb_dim, num_layers).items():
         out[k] = _read(path, shp, at)
         at += int(np.prod(shp))
     return out
 
 
-def synth_gin_virtual_node(seed: int = 11, scale: float = 1.0, emb_dim: int = 100) -> Dict[str, np.ndarray]:
+def synth_gin_virtual_node(seed: int = 11, scale: float = 1.0, emb_dim: int = 100, num_layers: int = 5) -> Dict[str, np.ndarray]:
     """Random virtual-node tensors at the scales of synth_gin_weights' MLP (the virtual node's MLP has the node MLP's shapes).
     emb_dim 300: the matrices' scales shrink with sqrt(100 / emb_dim), as synth_gin_weights' do (at 100 the values are what they
     always were)."""
@@ -171,7 +235,7 @@ def synth_gin_virtual_node(seed: int = 11, scale: float = 1.0, emb_dim: int = 10
     if emb_dim != 100:
         for k in ("w1", "w2"):
             s[k] = s[k] * float(np.sqrt(100.0 / emb_dim))
-    return OrderedDict((k, (rng.standard_normal(shp) * s[k] * scale).astype(np.float32)) for k, shp in gin_virtual_node_shapes(emb_dim).items())
+    return OrderedDict((k, (rng.standard_normal(shp) * s[k] * scale).astype(np.float32)) for k, shp in gin_virtual_node_shapes(emb_dim, num_layers).items())
 
 
 # ... and for GCN (flowgnn.h: flowgnn_set_gcn_virtual_node): the same five tensors in the same order, one file beside the GCN file
@@ -194,19 +258,21 @@ def save_gcn_virtual_node(vn, directory: str, emb_dim: int = 100) -> None:
     flat.tofile(os.path.join(directory, name))
 
 
-def load_gcn_virtual_node(directory: str, emb_dim: int = 100) -> Dict[str, np.ndarray]:
+def load_gcn_virtual_node(directory: str, emb_dim: int = 100, num_layers: int = 5) -> Dict[str, np.ndarray]:
     """The five tensors of a directory's GCN virtual-node file of width emb_dim (for Engine.set_gcn_virtual_node); a short file is refused."""
     path = os.path.join(directory, gcn_virtual_node_file(emb_dim))
+    d = int(emb_dim)
+    _check_depth_of_file(path, d, 4 * d * d + 3 * d, _depth(num_layers, d), shift=-1)  # (per update: w1, w2, b1, b2; a file of another depth is refused)
     out, at = OrderedDict(), 0
-    for k, shp in gin_virtual_node_shapes(emb_dim).items():
+    for k, shp in gin_virtual_node_shapes(emb_dim, num_layers).items():
         out[k] = _read(path, shp, at)
         at += int(np.prod(shp))
     return out
 
 
-def synth_gcn_virtual_node(seed: int = 13, scale: float = 1.0, emb_dim: int = 100) -> Dict[str, np.ndarray]:
+def synth_gcn_virtual_node(seed: int = 13, scale: float = 1.0, emb_dim: int = 100, num_layers: int = 5) -> Dict[str, np.ndarray]:
     """Random virtual-node tensors for GCN: synth_gin_virtual_node's scales (the MLP is the same), another seed."""
-    return synth_gin_virtual_node(seed=seed, scale=scale, emb_dim=emb_dim)
+    return synth_gin_virtual_node(seed=seed, scale=scale, emb_dim=emb_dim, num_layers=num_layers)
 
 
 # OGB's attention readout for GIN and GCN at width 300 (flowgnn.h: flowgnn_set_attention_pooling): one file beside the model's set, the
@@ -365,7 +431,7 @@ def synth_set2set(seed: int = 17, emb_dim: int = 300, num_tasks: int = 1) -> Dic
     return OrderedDict([("w_ih", w_ih), ("w_hh", w_hh), ("b_ih", b_ih), ("b_hh", b_hh), ("head_w", head_w), ("head_b", head_b)])
 
 
-def synth_gin_weights(seed: int = 7, num_tasks: int = 1, emb_dim: int = 100) -> Dict[str, np.ndarray]:
+def synth_gin_weights(seed: int = 7, num_tasks: int = 1, emb_dim: int = 100, num_layers: int = 5) -> Dict[str, np.ndarray]:
     """Random weights with the measured scales of the shipped GIN set:
     W1 s=0.075, b1 s=0.91, W2 s=0.053, b2 s=0.49, node/edge emb s=0.11/0.14, pred s=0.15.
     emb_dim 300: the same scales at OGB's default width, the matrices' scales shrunk by sqrt(100 / emb_dim) so that the activations
@@ -381,7 +447,7 @@ def synth_gin_weights(seed: int = 7, num_tasks: int = 1, emb_dim: int = 100) -> 
         for k in ("node_mlp_1_weights", "node_mlp_2_weights", "graph_pred_weights"):
             scale[k] = scale[k] * float(np.sqrt(100.0 / emb_dim))
     return OrderedDict((k, (rng.standard_normal(_task_shape(k, shp, num_tasks)) * scale[k]).astype(np.float32))
-                       for k, (_, shp) in gin_files(emb_dim).items())
+                       for k, (_, shp) in gin_files(emb_dim, num_layers).items())
 
 
 # --------------------------------------------------------------------------- GCN
@@ -407,10 +473,15 @@ def gcn_file(emb_dim: int = 100) -> str:
     return GCN_FILE.replace("dim100", f"dim{_gcn_dim(emb_dim)}")
 
 
-def gcn_shapes(emb_dim: int = 100):
-    """GCN_SHAPES at width emb_dim: 100 -> D."""
+_GCN_WHOLE = ("node_embedding_weight", "graph_pred_weights", "graph_pred_bias")  # every other tensor is per layer
+
+
+def gcn_shapes(emb_dim: int = 100, num_layers: int = 5):
+    """GCN_SHAPES at width emb_dim: 100 -> D; and at depth num_layers (flowgnn_set_num_layers): the leading 5 of the per-layer tensors."""
     d = _gcn_dim(emb_dim)
-    return OrderedDict((k, tuple(d if x == 100 else x for x in shp)) for k, shp in GCN_SHAPES.items())
+    n = _depth(num_layers, d)
+    return OrderedDict((k, tuple(d if x == 100 else x for x in shp) if k in _GCN_WHOLE else (n,) + tuple(d if x == 100 else x for x in shp[1:]))
+                       for k, shp in GCN_SHAPES.items())
 
 
 def gcn_emb_dim_of(w) -> int:
@@ -418,17 +489,17 @@ def gcn_emb_dim_of(w) -> int:
     return int(np.asarray(w["node_embedding_weight"]).shape[-1])
 
 
-def _gcn_offsets(num_tasks: int = 1, emb_dim: int = 100):
+def _gcn_offsets(num_tasks: int = 1, emb_dim: int = 100, num_layers: int = 5):
     """(name, layer or None) -> float offset in the .all.bin (GCN/src/host_load.cc:34-170, D for 100): node table at 0, layer l at
     173 D + l (D^2 + 15 D), BatchNorm l at 173 D + 5 (D^2 + 15 D) + l (4 D + 1); the head is the last tensor pair of the flattened
     state_dict: weight [NUM_TASK][D] at 173 D + 5 (D^2 + 15 D) + 5 (4 D + 1), bias [NUM_TASK] right behind it.  At D = 100 these are
-    17300, 11500, 74800 and 76805."""
-    d = int(emb_dim)
+    17300, 11500, 74800 and 76805.  num_layers: L for every 5 above (flowgnn_set_num_layers) -- the BatchNorm blocks and the head move."""
+    d, L = int(emb_dim), int(num_layers)
     layer = d * d + 15 * d
-    bn0 = 173 * d + 5 * layer
-    head = bn0 + 5 * (4 * d + 1)
+    bn0 = 173 * d + L * layer
+    head = bn0 + L * (4 * d + 1)
     off = {("node_embedding_weight", None): 0, ("graph_pred_weights", None): head, ("graph_pred_bias", None): head + d * num_tasks}
-    for l in range(5):
+    for l in range(L):
         base = 173 * d + layer * l
         off[("convs_weight", l)] = base
         off[("convs_bias", l)] = base + d * d
@@ -442,38 +513,46 @@ def _gcn_offsets(num_tasks: int = 1, emb_dim: int = 100):
     return off
 
 
-def load_gcn_weights(directory: str, num_tasks: int = 1, emb_dim: int = 100) -> Dict[str, np.ndarray]:
+def load_gcn_weights(directory: str, num_tasks: int = 1, emb_dim: int = 100, num_layers: int = 5) -> Dict[str, np.ndarray]:
+    """num_layers: the depth the file was written for (flowgnn_set_num_layers): every offset behind the layers depends on it, so a file
+    whose size is that of another depth is refused."""
     path = os.path.join(directory, gcn_file(emb_dim))
-    off = _gcn_offsets(num_tasks, emb_dim)
+    d, n = _gcn_dim(emb_dim), _depth(num_layers, emb_dim)
+    _check_depth_of_file(path, 173 * d + (d + 1) * int(num_tasks), d * d + 15 * d + 4 * d + 1, n)
+    off = _gcn_offsets(num_tasks, emb_dim, n)
     w = OrderedDict()
-    for k, shp in gcn_shapes(emb_dim).items():
+    for k, shp in gcn_shapes(emb_dim, n).items():
         if (k, None) in off:
             w[k] = _read(path, _task_shape(k, shp, num_tasks), off[(k, None)])
         else:
-            w[k] = np.stack([_read(path, shp[1:], off[(k, l)]) for l in range(5)])
+            w[k] = np.stack([_read(path, shp[1:], off[(k, l)]) for l in range(n)])
     return w
 
 
-def save_gcn_weights(w: Dict[str, np.ndarray], directory: str, emb_dim=None) -> None:
-    """emb_dim: None = the arrays' own width (which names the file); a number must agree with it."""
+def save_gcn_weights(w: Dict[str, np.ndarray], directory: str, emb_dim=None, num_layers=None) -> None:
+    """emb_dim: None = the arrays' own width (which names the file); a number must agree with it.  num_layers: likewise the depth."""
     d = gcn_emb_dim_of(w)
     if emb_dim is not None and int(emb_dim) != d:
         raise ValueError(f"GCN: the tensors are {d} wide, emb_dim says {emb_dim}")
+    n = gin_num_layers_of(w)
+    if num_layers is not None and int(num_layers) != n:
+        raise ValueError(f"GCN: the tensors are {n} layers deep, num_layers says {num_layers}")
+    shapes = gcn_shapes(d, n)  # (a depth that does not exist is refused before anything is created)
     os.makedirs(directory, exist_ok=True)
     tasks = int(np.asarray(w["graph_pred_bias"]).size)
-    off = _gcn_offsets(tasks, d)
+    off = _gcn_offsets(tasks, d, n)
     buf = np.zeros(off[("graph_pred_weights", None)] + (d + 1) * tasks, dtype="<f4")
-    for k, shp in gcn_shapes(d).items():
+    for k, shp in shapes.items():
         a = np.asarray(w[k], dtype=np.float32).reshape(_task_shape(k, shp, tasks))
         if (k, None) in off:
             buf[off[(k, None)]:off[(k, None)] + a.size] = a.ravel()
         else:
-            for l in range(5):
+            for l in range(n):
                 buf[off[(k, l)]:off[(k, l)] + a[l].size] = a[l].ravel()
     buf.tofile(os.path.join(directory, gcn_file(d)))
 
 
-def synth_gcn_weights(seed: int = 7, num_tasks: int = 1, emb_dim: int = 100) -> Dict[str, np.ndarray]:
+def synth_gcn_weights(seed: int = 7, num_tasks: int = 1, emb_dim: int = 100, num_layers: int = 5) -> Dict[str, np.ndarray]:
     """emb_dim 300: the same scales at OGB's default width, convs_weight shrunk by sqrt(100 / emb_dim) so that the activations keep
     the size they have at 100 (at 100 the values are what they always were)."""
     rng = np.random.default_rng(seed)
@@ -483,7 +562,7 @@ def synth_gcn_weights(seed: int = 7, num_tasks: int = 1, emb_dim: int = 100) -> 
     if emb_dim != 100:
         scale["convs_weight"] = scale["convs_weight"] * float(np.sqrt(100.0 / emb_dim))
     w = OrderedDict()
-    for k, shp in gcn_shapes(emb_dim).items():
+    for k, shp in gcn_shapes(emb_dim, num_layers).items():
         shp = _task_shape(k, shp, num_tasks)
         if k == "bn_var":
             w[k] = rng.uniform(0.3, 1.5, shp).astype(np.float32)

@@ -507,7 +507,8 @@ int flowgnn_num_tasks(const flowgnn_engine* e);
  * EMB_DIM of GIN as a run-time choice between two widths (a compile-time constant in the reference, GIN/src/dcl.h:19, 100 as
  * shipped; OGB's own training script defaults to --emb_dim 300, and the GIN results quoted for ogbg-molhiv / ogbg-molpcba are
  * 300-wide models).  At FLOWGNN_EMB_DIM_OGB the eight GIN tensors are node_emb [173][300], edge_emb [5][13][300], w1 [5][600][300],
- * b1 [5][600], w2 [5][300][600], b2 [5][300], pred_w [NUM_TASK][300], pred_b [NUM_TASK]; flowgnn_load_weights_dir reads the
+ * b1 [5][600], w2 [5][300][600], b2 [5][300], pred_w [NUM_TASK][300], pred_b [NUM_TASK] (every leading 5 is flowgnn_num_layers(e),
+ * which flowgnn_set_num_layers below changes at this width); flowgnn_load_weights_dir reads the
  * reference's file names with dim300 in place of dim100; embeddings, node embeddings and flowgnn_get_h are 300 wide.  The width runs
  * on kernels of its own, one launch per layer: split-f16 MFMA products with the fp32 re-run of flowgnn_exact_reruns.
  * Call it before setting weights and batch (both must be set again afterwards: weights set before are dropped); drops a recorded
@@ -532,7 +533,7 @@ int flowgnn_emb_dim(const flowgnn_engine* e);              /* -1 for a null hand
  * and bits).  On a GCN engine it chooses between the reference's width and OGB's default, the width of a GNN(gnn_type='gcn')
  * checkpoint trained with OGB's own script: at FLOWGNN_EMB_DIM_OGB the eleven GCN tensors are node_emb [173][300], edge_emb
  * [5][13][300], convs_weight [5][300][300], convs_bias / root_emb / bn_weight / bn_bias / bn_mean / bn_var [5][300], pred_w
- * [NUM_TASK][300], pred_b [NUM_TASK]; flowgnn_load_weights_dir reads gcn_ep1_dim300.weights.all.bin, the reference's one file with
+ * [NUM_TASK][300], pred_b [NUM_TASK] (every leading 5 is flowgnn_num_layers(e), flowgnn_set_num_layers below); flowgnn_load_weights_dir reads gcn_ep1_dim300.weights.all.bin, the reference's one file with
  * 300 for 100 in every offset; embeddings, node embeddings and flowgnn_get_h (the rows the readout pools) are 300 wide.  The width
  * runs on kernels of its own (gcn_wide.hip): one fused launch per layer with split-f16 MFMA products and the fp32
  * re-run of flowgnn_exact_reruns.  NUM_TASK, the three poolings, graph embeddings, node embeddings, node logits, host and device
@@ -731,11 +732,12 @@ int flowgnn_pooling(const flowgnn_engine* e);            /* -1 for a null handle
  *     FLOWGNN_ERR_UNSUPPORTED under option gin_unfused 1, and so do flowgnn_run_aggregation_only and flowgnn_get_aggregate (the
  *     stand-alone aggregation kernel has no eps instance).
  * flowgnn_gin_eps: 1 on, 0 off, -1 for a null handle; eps_out (may be NULL) receives the five values (zeros while off).
+ * "Five" is flowgnn_num_layers(e): after flowgnn_set_num_layers (below) both calls read and write that many floats.
  * flowgnn_group_set_gin_eps: flowgnn_set_gin_eps on every member.  flowgnn_entry_set_gin_eps: for the engines behind the
  *     GIN / GIN-VN entry points, one vector for every weight set.
  */
-int flowgnn_set_gin_eps(flowgnn_engine* e, const float* eps /* [5], NULL = off */);
-int flowgnn_gin_eps(const flowgnn_engine* e, float* eps_out /* [5], may be NULL */);   /* 1 on, 0 off, -1 null handle */
+int flowgnn_set_gin_eps(flowgnn_engine* e, const float* eps /* [flowgnn_num_layers(e)] (5 unless flowgnn_set_num_layers said otherwise), NULL = off */);
+int flowgnn_gin_eps(const flowgnn_engine* e, float* eps_out /* [flowgnn_num_layers(e)], may be NULL */);   /* 1 on, 0 off, -1 null handle */
 
 /*
  * OGB's virtual node for GIN: the model of ogb/examples/graphproppred/mol with gnn_type = 'gin-virtual'.  It is NOT the reference's
@@ -774,7 +776,8 @@ int flowgnn_ogb_virtual_node(const flowgnn_engine* e);            /* 1 on, 0 off
 /*
  * The same model through a call that carries the tensors' width, which is how OGB's gin-virtual at its default emb_dim 300 runs
  * (flowgnn_set_emb_dim(e, FLOWGNN_EMB_DIM_OGB) first).  With D = emb_dim: vn_embedding [D], w1 [4][2D][D], b1 [4][2D], w2 [4][D][2D],
- * b2 [4][D]; the definition is the one above with that D.
+ * b2 [4][D]; the definition is the one above with that D.  The leading 4 is flowgnn_num_layers(e) - 1: after flowgnn_set_num_layers
+ * (below) the call reads that many updates, and the definition's "l = 0 .. 4" and "l < 4" run over the engine's depth.
  *   emb_dim == 100: exactly flowgnn_set_ogb_virtual_node -- the same state, the same kernels, the same bits.
  *   emb_dim == 300: kernels of gin_wide.hip.  No launch rewrites the rows to add a vector: x_0 = h_0 + E is
  *       formed in the atom encoder, x_{l+1} in the epilogue of layer l's kernel, t by one read of the rows (profile slot
@@ -831,7 +834,8 @@ int flowgnn_gcn_virtual_node(const flowgnn_engine* e);            /* 1 on, 0 off
 /*
  * gcn-virtual through a call that carries the tensors' width, which is how it runs at OGB's default emb_dim 300
  * (flowgnn_set_model_emb_dim(e, FLOWGNN_EMB_DIM_OGB) first): the mirror of flowgnn_set_ogb_virtual_node_dim.  With D = emb_dim:
- * vn_embedding [D], w1 [4][2D][D], b1 [4][2D], w2 [4][D][2D], b2 [4][D]; the definition is the one above with that D.
+ * vn_embedding [D], w1 [4][2D][D], b1 [4][2D], w2 [4][D][2D], b2 [4][D]; the definition is the one above with that D.  The leading 4 is
+ * flowgnn_num_layers(e) - 1, as in flowgnn_set_ogb_virtual_node_dim.
  *   emb_dim == 100: exactly flowgnn_set_gcn_virtual_node -- the same state, the same kernels, the same bits.
  *   emb_dim == 300: kernels of gcn_wide.hip.  The row the vector is added to exists only in the registers
  *       of the fused layer kernel, so its VN instance adds vn there, in front of the f16 split, and leaves the per-graph sums as
@@ -988,6 +992,39 @@ int flowgnn_jk_residual(const flowgnn_engine* e, int* jk_out, int* residual_out)
 int flowgnn_set_model_jk_residual(flowgnn_engine* e, int emb_dim, int jk, int residual);   /* (LAST, 0) = off, the default */
 
 /*
+ * OGB's num_layer for GIN and GCN at width 300 (gin, gin-virtual, gcn, gcn-virtual): the depth of the model as
+ * a run-time property of the engine, 5 by default as in the reference (a compile-time constant there).  The 300-wide paths launch one
+ * kernel per layer, so the depth is the bound of a host-side loop: the layer kernels are the ones every depth-5 run launches, L times.
+ * With L = num_layers every "5" of the tensors above is L and every "4" of the virtual node's is L - 1:
+ *     GIN  edge_emb [L][13][300], w1 [L][600][300], b1 [L][600], w2 [L][300][600], b2 [L][300]
+ *     GCN  edge_emb [L][13][300], convs_weight [L][300][300], convs_bias / root_emb / bn_* [L][300]
+ *     flowgnn_set_gin_eps reads and flowgnn_gin_eps writes L floats; the virtual-node setters read L - 1 updates
+ *     JK sum has L + 1 terms; flowgnn_get_h returns h_L, the last layer's output
+ * flowgnn_load_weights_dir reads the same file names, sized by L, and refuses a file whose size is that of another depth (the text
+ * names both depths) instead of reading short or past its end.
+ * The range is FLOWGNN_MIN_NUM_LAYERS .. FLOWGNN_MAX_NUM_LAYERS: OGB's GNN_node raises below 2, and 8 is the size of the arrays this
+ * ABI keeps per layer (eps, the self scales).
+ * A change follows flowgnn_set_num_tasks: the model drops its weights, the batch has to be set again, a recorded launch sequence is
+ * dropped.  The numeric mode, the pooling, the attention / set2set readouts and JK / residual survive it: none is sized by the depth.
+ * The depth the engine has is a no-op (FLOWGNN_OK before any state changes), so flowgnn_set_num_layers(e, w, 5) on an engine that
+ * never called it changes nothing, at either width.
+ * FLOWGNN_ERR_ARG: a null handle; num_layers outside 2 .. 8; emb_dim other than 100 or 300; emb_dim != flowgnn_emb_dim(e)
+ * (flowgnn_last_error names both widths).
+ * FLOWGNN_ERR_UNSUPPORTED (flowgnn_last_error says why): any model but FLOWGNN_MODEL_GIN and FLOWGNN_MODEL_GCN; width 100 with a depth
+ * other than 5 (the graph-resident and the 100-wide per-layer kernels are five layers deep); while a trained eps or OGB's virtual node
+ * is on (their tensors belong to a depth: turn it off, change the depth, set it again); FLOWGNN_NUMERIC_Q6_10; and, while the depth is
+ * not 5, flowgnn_set_emb_dim / flowgnn_set_model_emb_dim to 100 (set the depth back to 5 first).
+ * flowgnn_num_layers: the engine's depth, 5 on every engine that never called the setter, -1 for a null handle.
+ * flowgnn_group_set_num_layers: the setter on every member.  The <M>_compute_graphs entry points have no form of it.
+ * `host GIN|GCN --emb-dim 300 --num-layer N`.
+ */
+#define FLOWGNN_NUM_LAYERS_DEFAULT 5
+#define FLOWGNN_MIN_NUM_LAYERS 2
+#define FLOWGNN_MAX_NUM_LAYERS 8
+int flowgnn_set_num_layers(flowgnn_engine* e, int emb_dim, int num_layers);   /* GIN, GCN at width 300: 2 .. 8; 5 = the default */
+int flowgnn_num_layers(const flowgnn_engine* e);                              /* -1 for a null handle */
+
+/*
  * Laplacian eigenvectors: DGN's node_eigen from the graphs alone (the reference reads it from DGN/eig/g%d.txt and does not say where it
  * comes from).  For graph g with n nodes and edges (u, v) in local ids:
  *     A[u][v] = A[v][u] = 1 for every edge with u != v   (both directions and duplicates collapse to 1, self loops are ignored)
@@ -1085,6 +1122,7 @@ int flowgnn_group_set_set2set_pooling(flowgnn_group* g, int emb_dim, int steps, 
                                       const float* b_ih, const float* b_hh, const float* head_w, const float* head_b);
 int flowgnn_group_set_jk_residual(flowgnn_group* g, int emb_dim, int jk, int residual);
 int flowgnn_group_set_model_jk_residual(flowgnn_group* g, int emb_dim, int jk, int residual);
+int flowgnn_group_set_num_layers(flowgnn_group* g, int emb_dim, int num_layers);   /* flowgnn_set_num_layers on every member */
 int flowgnn_group_set_batch(flowgnn_group* g, int num_graphs,
                             const int* nums_of_nodes, const int* nums_of_edges,
                             const int* node_feature, const int* edge_list, const int* edge_attr,
