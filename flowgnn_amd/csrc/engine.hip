@@ -419,6 +419,8 @@ int flowgnn_destroy(flowgnn_engine* e) {
     e->ogb_vn.release();
     e->attn_pool.release();
     e->s2s.release();
+    e->edge_lin.release();
+    e->edge_feat.release();
     if (e->eig_done) (void)hipEventDestroy(e->eig_done);
     if (e->d_err) (void)hipFree(e->d_err);
     delete e->model;
@@ -586,12 +588,18 @@ static int d2h_sync(flowgnn_engine* e, void* dst, const void* src, size_t bytes,
     return he == hipSuccess ? 0 : EHIP_FAIL(e, what, he);
 }
 
+// The batch carries edge attributes: the model reads them, unless OGB's linear edge encoder is on (flowgnn_set_edge_linear) and the
+// caller passed none -- the edge term then comes from the float features of flowgnn_set_edge_features, and no edge code is built
+static bool batch_has_attr(const flowgnn_engine* e, const void* edge_attr) {
+    return e->model->has_edge_attr() && !(e->edge_lin_dim && !edge_attr);
+}
+
 // the bulk arrays of flowgnn_set_batch, host -> d_nf / d_el / d_ea / d_eig.
 // copy_mu (flowgnn_group_compute): held around the large host -> device copies only -- one copier per DEVICE at a time, while another
 // engine of the same device packs its next range on the host or packs its tiles
 static int upload_host_arrays(flowgnn_engine* e, const BatchCounts& c, const int* node_feature, const int* edge_list, const int* edge_attr,
                               const float* node_eigen, std::mutex* copy_mu) {
-    const bool attr = e->model->has_edge_attr();
+    const bool attr = batch_has_attr(e, edge_attr);
     const bool eig = (e->model_id == FLOWGNN_MODEL_DGN);
     const long long N = c.N, E = c.E;
     // The three int32 arrays narrowed on the host (9 B per node, 5 B per edge: a quarter of the bytes), copied from pinned memory and
@@ -638,8 +646,7 @@ static int upload_concat(flowgnn_engine* e, fg::GrowBuf& buf, bool headroom, std
 // always copied them (after the buffers, before the tiles); nullptr: the caller enqueues that transfer itself once this returns
 // (flowgnn_set_batch_device: after the reset of the error word, so that what its ingest reports survives until the next batch).
 static int set_batch_state(flowgnn_engine* e, int num_graphs, const int* nums_of_nodes, const int* nums_of_edges, const BatchCounts& c,
-                           const std::function<int()>& upload) {
-    const bool attr = e->model->has_edge_attr();
+                           bool attr, const std::function<int()>& upload) {
     const bool eig = (e->model_id == FLOWGNN_MODEL_DGN);
     const long long N = c.N, E = c.E;
     const int mx_n = c.mx_n, mx_e = c.mx_e;
@@ -724,6 +731,10 @@ static int set_batch_state(flowgnn_engine* e, int num_graphs, const int* nums_of
     db.s2s_steps = e->s2s_steps;
     db.jk = e->jk;
     db.residual = e->residual;
+    db.edge_lin = e->edge_lin_dim ? e->edge_lin.p : nullptr;
+    db.edge_lin_dim = e->edge_lin_dim;
+    e->edge_feat_dim = 0;  // flowgnn_set_edge_features: the features were the previous batch's
+    db.edge_feat = nullptr;
     db.final_h = 0;
     db.tap = nullptr;
     db.tap_dim = 0;
@@ -758,12 +769,12 @@ int set_batch_impl(flowgnn_engine* e, int num_graphs, const int* nums_of_nodes, 
     BatchCounts c;
     const int rc = batch_counts(e, num_graphs, nums_of_nodes, nums_of_edges, &c);
     if (rc) return rc;
-    const bool attr = e->model->has_edge_attr();
+    const bool attr = batch_has_attr(e, edge_attr);
     const bool eig = (e->model_id == FLOWGNN_MODEL_DGN);
     if (c.N > 0 && !node_feature) return FLOWGNN_ERR_ARG;
     if (c.E > 0 && (!edge_list || (attr && !edge_attr))) return FLOWGNN_ERR_ARG;
     if (eig && c.N > 0 && !node_eigen) return FLOWGNN_ERR_ARG;
-    return set_batch_state(e, num_graphs, nums_of_nodes, nums_of_edges, c,
+    return set_batch_state(e, num_graphs, nums_of_nodes, nums_of_edges, c, attr,
                            [&]() { return upload_host_arrays(e, c, node_feature, edge_list, edge_attr, node_eigen, copy_mu); });
 }
 
@@ -819,7 +830,7 @@ int flowgnn_set_batch_device(flowgnn_engine* e, int num_graphs, const int* nums_
         e->err = "flowgnn_set_batch_device: unknown layout";
         return FLOWGNN_ERR_ARG;
     }
-    const bool attr = e->model->has_edge_attr();
+    const bool attr = batch_has_attr(e, edge_attr);
     const bool eig = (e->model_id == FLOWGNN_MODEL_DGN);
     const size_t N = (size_t)c.N, E = (size_t)c.E;
     if ((N > 0 && !node_feature) || (E > 0 && (!edge_list || (attr && !edge_attr))) || (eig && N > 0 && !node_eigen)) {
@@ -833,7 +844,7 @@ int flowgnn_set_batch_device(flowgnn_engine* e, int num_graphs, const int* nums_
     ENGINE_TRY(e, check_device_array(e, edge_list, w * E * 2, "edge_list"));
     ENGINE_TRY(e, check_device_array(e, edge_attr, w * E * EDGE_ATTR, "edge_attr"));
     ENGINE_TRY(e, check_device_array(e, node_eigen, sizeof(float) * N * 4, "node_eigen"));
-    rc = set_batch_state(e, num_graphs, nums_of_nodes, nums_of_edges, c, nullptr);
+    rc = set_batch_state(e, num_graphs, nums_of_nodes, nums_of_edges, c, attr, nullptr);
     if (rc) return rc;
     // the ingest, on the launch stream: ordered after the caller's work on it, before the next flowgnn_run; nothing waits for it
     {
@@ -856,6 +867,40 @@ int flowgnn_set_batch_device(flowgnn_engine* e, int num_graphs, const int* nums_
             return EHIP_FAIL(e, "flowgnn_set_batch_device: ingest", he);
         }
     }
+    return FLOWGNN_OK;
+}
+
+// The float edge features of the resident batch, for OGB's linear edge encoder (flowgnn_set_edge_linear): the
+// engine's own copy, made on the launch stream, so it is ordered behind the caller's work there and in front of the next run
+int flowgnn_set_edge_features(flowgnn_engine* e, int edge_dim, const float* ef, int on_device) {
+    if (!e) return FLOWGNN_ERR_ARG;
+    static const char* const api = "flowgnn_set_edge_features";
+    if (edge_dim < 1 || edge_dim > FLOWGNN_MAX_EDGE_DIM) {
+        e->err = std::string(api) + ": edge_dim is " + std::to_string(edge_dim) + "; an edge has 1 .. " + std::to_string(FLOWGNN_MAX_EDGE_DIM) + " features";
+        return FLOWGNN_ERR_ARG;
+    }
+    if (!e->batch_ready) {
+        e->err = std::string(api) + ": no batch is set, and the features are a batch's (flowgnn_set_batch first)";
+        return FLOWGNN_ERR_STATE;
+    }
+    const size_t bytes = sizeof(float) * (size_t)e->E * (size_t)edge_dim;
+    if (bytes && !ef) {
+        e->err = std::string(api) + ": ef is NULL and the batch has edges";
+        return FLOWGNN_ERR_ARG;
+    }
+    ENGINE_TRY(e, use_device(e));
+    if (on_device) ENGINE_TRY(e, check_device_array(e, ef, bytes, "ef", api));
+    e->drop_graph();  // a recorded launch sequence reads the buffer as it was
+    if (!e->edge_feat.holds(bytes)) {
+        if (e->stream) EHIP_TRY(e, hipStreamSynchronize(e->stream));  // (a run in flight may still read the old one)
+        EHIP_TRY(e, e->edge_feat.reserve(bytes, true));
+    }
+    if (bytes) {
+        EHIP_TRY(e, hipMemcpyAsync(e->edge_feat.p, ef, bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, e->stream));
+        if (!on_device) EHIP_TRY(e, hipStreamSynchronize(e->stream));  // the caller's host array is its own again when the call returns
+    }
+    e->edge_feat_dim = edge_dim;
+    e->db.edge_feat = (const float*)e->edge_feat.p;
     return FLOWGNN_OK;
 }
 
@@ -963,6 +1008,13 @@ int flowgnn_run(flowgnn_engine* e) {
     if (!e) return FLOWGNN_ERR_ARG;
     if (!e->batch_ready || !e->model->weights_ready()) {
         e->err = "flowgnn_run: weights or batch not set";
+        return FLOWGNN_ERR_STATE;
+    }
+    if (e->edge_lin_dim && e->edge_feat_dim != e->edge_lin_dim) {  // OGB's linear edge encoder reads the batch's float edge features
+        e->err = e->edge_feat_dim ? "flowgnn_run: the edge encoder (flowgnn_set_edge_linear) takes " + std::to_string(e->edge_lin_dim) +
+                                        " features per edge and the batch's (flowgnn_set_edge_features) have " + std::to_string(e->edge_feat_dim)
+                                  : std::string("flowgnn_run: the edge encoder is on (flowgnn_set_edge_linear) and the batch has no edge features: "
+                                                "flowgnn_set_edge_features after flowgnn_set_batch");
         return FLOWGNN_ERR_STATE;
     }
     ENGINE_TRY(e, use_device(e));

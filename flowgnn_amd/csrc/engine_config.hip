@@ -8,6 +8,7 @@
 // holds that order.  A new option that carries tensors follows flowgnn_set_attention_pooling: width_argument, tensor_set_on, its own
 // argument checks, tensor_set_finite, its state checks, begin_change, upload_packed, its own fields.
 #include "engine_internal.h"
+#include "gin_wide_el.h"
 #include "wide_attn.h"
 #include "wide_s2s.h"
 #include <cmath>
@@ -146,6 +147,8 @@ static int set_width(flowgnn_engine* e, const char* fn, int emb_dim) {
         return refuse(e, FLOWGNN_ERR_UNSUPPORTED, who + "JK sum or the residual is on (" + (gcn ? "flowgnn_set_model_jk_residual" : "flowgnn_set_jk_residual") + "), and only the 300-wide " +
                                                   (gcn ? "GCN" : "GIN") + " has those instances, not width " + std::to_string(emb_dim) +
                                                   ": turn it off (FLOWGNN_JK_LAST, 0), then change the width");
+    if (e->edge_lin_dim)  // (on means width 300: the call asks for 100, which has no such kernel)
+        return refuse(e, FLOWGNN_ERR_UNSUPPORTED, who + "OGB's linear edge encoder is on (flowgnn_set_edge_linear), and only the 300-wide GIN has it: turn it off, then change the width");
     if (e->num_layers != FLOWGNN_NUM_LAYERS_DEFAULT)  // (not 5 means width 300: the call asks for 100, whose kernels are five layers deep)
         return refuse(e, FLOWGNN_ERR_UNSUPPORTED, who + "the depth is " + std::to_string(e->num_layers) + " (flowgnn_set_num_layers), and the " + std::to_string(emb_dim) +
                                                   "-wide kernels are five layers deep: flowgnn_set_num_layers(e, " + std::to_string(e->emb_dim) + ", 5) first, then change the width");
@@ -260,6 +263,9 @@ static int set_numeric_mode(flowgnn_engine* e, int mode, ModeRoute route) {
         return refuse(e, FLOWGNN_ERR_UNSUPPORTED, "flowgnn_set_numeric_mode: a trained eps is on (flowgnn_set_gin_eps), and the fixed-point arithmetic is the reference's, which has no eps");
     if (mode == FLOWGNN_NUMERIC_Q6_10 && e->ogb_vn_on)
         return refuse(e, FLOWGNN_ERR_UNSUPPORTED, "flowgnn_set_numeric_mode: OGB's virtual node is on (flowgnn_set_ogb_virtual_node / flowgnn_set_gcn_virtual_node), and the fixed-point arithmetic is the reference's, which has no such model");
+    if (mode == FLOWGNN_NUMERIC_F16 && e->edge_lin_dim)
+        return refuse(e, FLOWGNN_ERR_STATE, "flowgnn_set_numeric_mode: OGB's linear edge encoder is on (flowgnn_set_edge_linear), and the f16 instances of the layer have no encoder: "
+                                            "turn one of the two off");
     e->drop_graph();
     const int rc = e->model->set_numeric_mode(mode);
     if (!rc) e->numeric_mode = mode;
@@ -580,6 +586,9 @@ int flowgnn_set_num_layers(flowgnn_engine* e, int emb_dim, int num_layers) {
     const int rc = e->model->set_num_layers(num_layers);
     if (rc) return refuse(e, rc, who + "this model is five layers deep");
     e->num_layers = num_layers;
+    e->edge_lin_dim = 0;  // OGB's linear edge encoder (flowgnn_set_edge_linear): its tensors were the other depth's -- off, to be set again
+    e->db.edge_lin = nullptr;
+    e->db.edge_lin_dim = 0;
     e->batch_ready = false;  // as flowgnn_set_num_tasks: weights and batch are set again
     e->ran = false;
     e->force_exact = false;
@@ -587,6 +596,50 @@ int flowgnn_set_num_layers(flowgnn_engine* e, int emb_dim, int num_layers) {
 }
 
 int flowgnn_num_layers(const flowgnn_engine* e) { return e ? e->num_layers : -1; }
+
+// ------------------------------------------------------------------ OGB's linear edge encoder
+// GIN at width 300: the encoder's two tensors in the device form of gin_wide_el.h, one device buffer owned by
+// the engine; db.edge_lin / db.edge_lin_dim carry it to GinWideModel::forward.  Both NULL: off, at any width and for any model.
+int flowgnn_set_edge_linear(flowgnn_engine* e, int emb_dim, int edge_dim, const float* w, const float* b) {
+    if (!e) return FLOWGNN_ERR_ARG;
+    const std::string who = "flowgnn_set_edge_linear: ";
+    if (int rc = width_argument(e, who, emb_dim)) return rc;
+    const bool given = w || b;
+    if (given && (edge_dim < 1 || edge_dim > FLOWGNN_MAX_EDGE_DIM))
+        return refuse(e, FLOWGNN_ERR_ARG, who + "edge_dim is " + std::to_string(edge_dim) + "; the encoder takes 1 .. " + std::to_string(FLOWGNN_MAX_EDGE_DIM) +
+                                              " features per edge (3 edge_dim + 2 K slots of one 32-deep MFMA; ogbg-ppa: 7)");
+    const size_t D = (size_t)emb_dim, L = (size_t)e->num_layers, F = (size_t)(given ? edge_dim : 0);
+    const TensorArg t[2] = {{"w", w, L * D * F}, {"b", b, L * D}};
+    bool on;
+    if (int rc = tensor_set_on(e, who, t, &on)) return rc;
+    if (on) {
+        if (int rc = tensor_set_finite(e, who, t)) return rc;
+        if (e->model_id != FLOWGNN_MODEL_GIN)
+            return refuse(e, FLOWGNN_ERR_UNSUPPORTED, who + "the linear edge encoder exists for FLOWGNN_MODEL_GIN only (OGB's gin and gin-virtual of ogbg-ppa; its GCNConv has no kernel here)");
+        if (int rc = width_matches(e, who, true, emb_dim, e->emb_dim, "flowgnn_set_emb_dim")) return rc;
+        if (fg::gw_el_blob_bytes(emb_dim, e->num_layers, edge_dim) == 0)
+            return refuse(e, FLOWGNN_ERR_UNSUPPORTED, who + "only the 300-wide GIN has this layer (the 100-wide kernels look the edge's row up in their table): flowgnn_set_emb_dim(e, 300) first");
+        if (e->numeric_mode != FLOWGNN_NUMERIC_F32)
+            return refuse(e, FLOWGNN_ERR_STATE, who + "FLOWGNN_NUMERIC_F16 is on (flowgnn_set_numeric_mode_dim), and the f16 instances of the layer have no encoder: turn one of the two off");
+        if (e->jk != FLOWGNN_JK_LAST || e->residual)
+            return refuse(e, FLOWGNN_ERR_STATE, who + "JK sum or the residual is on (flowgnn_set_jk_residual), and those instances of the layer have no encoder: turn one of the two off");
+    }
+    ENGINE_TRY(e, begin_change(e));
+    if (on)
+        if (int rc = upload_packed(e, e->edge_lin, fg::gw_el_blob_bytes(emb_dim, e->num_layers, edge_dim),
+                                   [&](float* dst) { fg::gw_el_blob_pack(emb_dim, e->num_layers, edge_dim, w, b, dst); }))
+            return rc;
+    e->edge_lin_dim = on ? edge_dim : 0;
+    e->db.edge_lin = on ? e->edge_lin.p : nullptr;  // (launches are stream-ordered: it matters to those enqueued after this call)
+    e->db.edge_lin_dim = e->edge_lin_dim;
+    if (!on && e->batch_ready && !e->has_attr && e->model->has_edge_attr()) {
+        e->batch_ready = false;  // the batch was set without edge_attr, which the table path reads: set it again
+        e->ran = false;
+    }
+    return FLOWGNN_OK;
+}
+
+int flowgnn_edge_linear(const flowgnn_engine* e) { return e ? e->edge_lin_dim : -1; }
 }  // extern "C"
 
 // ------------------------------------------------------------------ JK / residual
@@ -617,6 +670,9 @@ static int set_jk_residual(flowgnn_engine* e, const char* fn, bool model_form, i
                            "none): " + (gcn ? "flowgnn_set_model_emb_dim" : "flowgnn_set_emb_dim") + "(e, 300) first");
     }
     ENGINE_TRY(e, use_device(e));
+    if ((jk != FLOWGNN_JK_LAST || residual) && e->edge_lin_dim)
+        return refuse(e, FLOWGNN_ERR_STATE, who + "OGB's linear edge encoder is on (flowgnn_set_edge_linear), and the JK / residual instances of the layer have no encoder: "
+                                                  "turn one of the two off");
     e->drop_graph();  // a recorded launch sequence is that of the other setting
     e->jk = jk;
     e->residual = residual;

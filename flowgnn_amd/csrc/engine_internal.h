@@ -108,6 +108,10 @@ struct flowgnn_engine {
     fg::GrowBuf s2s;                  // ... and its six tensors on the device (wide_s2s.h)
     int jk = FLOWGNN_JK_LAST;         // flowgnn_set_jk_residual: the engine's as well, across batches and weight sets (db.jk / db.residual follow)
     int residual = 0;
+    int edge_lin_dim = 0;             // flowgnn_set_edge_linear: the engine's as well, 0 = off (db.edge_lin / db.edge_lin_dim follow it)
+    fg::GrowBuf edge_lin;             // ... and its tensors on the device (gin_wide_el.h)
+    int edge_feat_dim = 0;            // flowgnn_set_edge_features: the resident BATCH's, 0 = none attached (db.edge_feat follows it) ...
+    fg::GrowBuf edge_feat;            // ... and the engine's copy of them [E][edge_feat_dim]
     int num_layers = FLOWGNN_NUM_LAYERS_DEFAULT;  // flowgnn_set_num_layers: the model's depth (GIN, GCN at width 300: 2 .. 8); sizes eps and the virtual node's tensors
     static_assert(FLOWGNN_MAX_NUM_LAYERS == fg::MAX_NUM_LAYERS && FLOWGNN_NUM_LAYERS_DEFAULT == fg::NUM_LAYERS_DEFAULT, "common.h restates the header's two depths");
 

@@ -35,6 +35,7 @@
 #include "../../include/flowgnn.h"
 #include "common.h"
 #include "dense_split.h"
+#include "gin_wide_el.h"  // flowgnn_set_edge_linear (section 4.31): the launchers of gin_wide_el.hip's kernels
 #include "gin_wide_body.h"  // GwDims, gw_step and gw_layer_body: the layer kernel's body, which gin_wide_jk.hip instantiates as well (section 4.24)
 #include "gin_wide_f16.h"  // FLOWGNN_NUMERIC_F16 at this width: the hi-only stream's layout and the launcher of gin_wide_f16.hip's kernels
 #include "gin_wide_jk.h"  // flowgnn_set_jk_residual (section 4.24): the launchers of gin_wide_jk.hip's instances
@@ -343,6 +344,10 @@ public:
         const bool res_on = db.residual != 0, jk_on = db.jk == FLOWGNN_JK_SUM;
         if (jk_on)
             if (int rc = jk_.reserve((size_t)n * D)) return rc;
+        // OGB's linear edge encoder (flowgnn_set_edge_linear, section 4.31): the layer's launches are gin_wide_el.hip's, under slots of
+        // their own; the engine keeps it apart from the f16 mode and JK / residual, whose instances have no encoder
+        const bool el_on = db.edge_lin != nullptr;
+        if (el_on && (f16_ || res_on || jk_on || (db.b.e_tot > 0 && !db.edge_feat))) return FLOWGNN_ERR_STATE;
         if (int rc = readout_.reserve(db, exact_)) return rc;
         {
             ProfScope p(prof, "atom_encoder", s);
@@ -379,7 +384,13 @@ public:
                                                  !res_on ? nullptr : l == 0 ? vnb : vn_vec_[(l - 1) & 1].p, l == 0 ? 0 : D, s))
                     return rc;
             }
-            if (!exact_ && (res_on || jk_on)) {
+            if (!exact_ && el_on) {
+                ProfScope p(prof, "gin_wide_layer_el", s);
+                if (int rc = launch_gw_layer_el(D, db.edge_lin, db.edge_lin_dim, l, db.h[cur], hn, db.csr.row_ptr, db.csr.src, db.csr.eid, db.edge_feat,
+                                                d_chunks_ + (size_t)l * M::LAYER_BYTES, d_tails_ + (size_t)l * M::TAIL_FLOATS, n, relu_out, self_s,
+                                                db.range_flag, vn_next ? node_graph_.p : nullptr, vn_next ? vnn : nullptr, s))
+                    return rc;
+            } else if (!exact_ && (res_on || jk_on)) {
                 ProfScope p(prof, f16_ ? "gin_wide_layer_f16" : "gin_wide_layer", s);
                 if (int rc = launch_gw_layer_jk(D, f16_, db.h[cur], hn, db.csr.row_ptr, db.csr.src, db.csr.ecode, ecomb,
                                                 f16_ ? d_chunks16_ + (size_t)l * F16::LAYER_BYTES : d_chunks_ + (size_t)l * M::LAYER_BYTES,
@@ -404,9 +415,16 @@ public:
                         db.h[cur], hn, db.csr.row_ptr, db.csr.src, db.csr.ecode, ecomb, d_chunks_ + (size_t)l * M::LAYER_BYTES,
                         d_tails_ + (size_t)l * M::TAIL_FLOATS, n, relu_out, self_s, db.range_flag);
             } else {
+                if (el_on) {  // (the exact form of the encoder: the aggregate under a slot of its own, the MLP as ever)
+                    ProfScope p(prof, "gin_wide_aggregate_el", s);
+                    if (int rc = launch_gw_aggregate_el(D, db.edge_lin, db.edge_lin_dim, l, db.h[cur], db.scratch, db.csr.row_ptr, db.csr.src,
+                                                        db.csr.eid, db.edge_feat, n, self_s, s))
+                        return rc;
+                }
                 ProfScope p(prof, "gin_wide_layer_f32", s);
-                gw_aggregate_kernel<D><<<grid_for((long long)n * M::C, 256, 256 * 8), 256, 0, s>>>(db.h[cur], db.scratch, db.csr.row_ptr, db.csr.src,
-                                                                                                   db.csr.ecode, ecomb, n, self_s);
+                if (!el_on)
+                    gw_aggregate_kernel<D><<<grid_for((long long)n * M::C, 256, 256 * 8), 256, 0, s>>>(db.h[cur], db.scratch, db.csr.row_ptr, db.csr.src,
+                                                                                                       db.csr.ecode, ecomb, n, self_s);
                 launch_gw_mlp_f32<D>(db.scratch, d_w1t_ + (size_t)l * D * H, d_b1_ + (size_t)l * H, d_w2t_ + (size_t)l * H * D, d_b2_ + (size_t)l * D,
                                      hid_.p, hn, n, relu_out, s);
                 // (the adds in the fast path's order: the residual, the virtual node's vector, the JK sum)

@@ -3,6 +3,8 @@
 // three it always had (EXT = false: the layer, its virtual-node instance, the virtual node's update), gin_wide_jk.hip the three with
 // OGB's residual=True and JK="sum" in their epilogues (EXT = true; flowgnn_set_jk_residual, section 4.24).  EXT is a compile-time
 // constant: with it false the epilogue's extra code does not exist and a kernel is the one it was before this header did.
+// gin_wide_el.hip has the two with OGB's linear edge encoder in the walk (EL = true; flowgnn_set_edge_linear, section 4.31): compile
+// time as well, and with it false the walk is the table's, instruction for instruction.
 #pragma once
 #include "common.h"
 #include "dense_split.h"
@@ -118,14 +120,24 @@ __device__ __forceinline__ void gw_step(const char* wb, int s, int lane, int g, 
 //                   or workgroup touches them
 enum { GW_PLAIN = 0, GW_VN = 1, GW_UPDATE = 2 };
 
-template <int D, int MODE, bool EXT = false>
+// EL (section 4.31, OGB's linear edge encoder): the walk of gin_wide_el.hip, the one translation unit with EL = true, which defines it
+// in front of this header's body; in every other instance the call below is discarded and nothing of it exists
+template <int D>
+__device__ __forceinline__ void gw_el_walk(const float* __restrict__ h, const int* __restrict__ src, const int* __restrict__ eid,
+                                           const float* __restrict__ ef, int el_f, float el_inv, const char* s_frag, int e_cur, int e_end,
+                                           int lane, float (&bq)[4 * GwDims<D>::Q], float& vmax);
+
+template <int D, int MODE, bool EXT = false, bool EL = false>
 __device__ __forceinline__ void gw_layer_body(const float* __restrict__ h, float* __restrict__ hout, const int* __restrict__ row_ptr,
                                               const int* __restrict__ src, const uint8_t* __restrict__ ecode, const float* __restrict__ ecomb,
                                               const uint8_t* __restrict__ wchunks, const float* __restrict__ tailp, int n_tot, int relu_out,
                                               float self_s, int* __restrict__ range_flag, const int* __restrict__ node_graph,
                                               const float* __restrict__ vn_add, const float* __restrict__ xres = nullptr,
-                                              int xres_stride = 0, const float* jk_in = nullptr, float* jk_out = nullptr) {
+                                              int xres_stride = 0, const float* jk_in = nullptr, float* jk_out = nullptr,
+                                              const int* __restrict__ eid = nullptr, const float* __restrict__ ef = nullptr, int el_f = 0,
+                                              float el_inv = 0.0f) {
     using M = GwDims<D>;
+    static_assert(!EL || MODE != GW_UPDATE, "the update has no edges");
     // two DISTINCT LDS objects, as in gin_layer_split_kernel: the DMA into one does not alias the reads of the other
     __shared__ __attribute__((aligned(16))) char s_a[M::CHUNK_BYTES];  // the combined edge table, then the odd chunks
     __shared__ __attribute__((aligned(16))) char s_b[M::CHUNK_BYTES];  // the even chunks
@@ -139,7 +151,9 @@ __device__ __forceinline__ void gw_layer_body(const float* __restrict__ h, float
     int e_cur = MODE == GW_UPDATE ? 0 : row_ptr[node];
     const int e_end = MODE == GW_UPDATE ? 0 : (valid ? row_ptr[node + 1] : e_cur);
     gw_issue<D>(wchunks, s_b, M::PIECES, M::LAST_LANES, wave, lane);                                                  // chunk 0
-    if (MODE != GW_UPDATE)
+    if (EL)  // (ecomb: the layer's T2 fragments of W_e and b_e, 1 KiB each, where the edge table goes otherwise)
+        gw_issue<D>(reinterpret_cast<const uint8_t*>(ecomb), s_a, M::T2, 64, wave, lane);
+    else if (MODE != GW_UPDATE)
         gw_issue<D>(reinterpret_cast<const uint8_t*>(ecomb), s_a, M::ECOMB_PIECES, M::ECOMB_LAST_LANES, wave, lane);  // the edge table
     float bq[4 * M::Q];
 #pragma unroll
@@ -149,7 +163,9 @@ __device__ __forceinline__ void gw_layer_body(const float* __restrict__ h, float
     const float* s_ecomb = reinterpret_cast<const float*>(s_a);
 
     // ---- gather: one in-edge per trip, in CSR order (a row's sum depends on the row alone); pieces at or beyond column D stay zero
-    while (MODE != GW_UPDATE && __any(e_cur < e_end)) {
+    float el_vmax = 0.0f;
+    if constexpr (EL) gw_el_walk<D>(h, src, eid, ef, el_f, el_inv, s_a, e_cur, e_end, lane, bq, el_vmax);
+    while (!EL && MODE != GW_UPDATE && __any(e_cur < e_end)) {
         if (e_cur < e_end) {
             const int u = src[e_cur];
             const int code = ecode[e_cur];
@@ -175,7 +191,7 @@ __device__ __forceinline__ void gw_layer_body(const float* __restrict__ h, float
         }
     }
     // ---- a = fma(h[v], s_l, m): one fp32 rounding (s_l = 1: the bits of the plain sum), then split into the B operands of MLP1
-    float vmax = 0.0f;
+    float vmax = EL ? el_vmax : 0.0f;
     ds_uint4_t in_hi[M::KS1], in_lo[M::KS1];
     {
         const float* hr = h + (size_t)node * D + 4 * g;

@@ -235,7 +235,7 @@ class Engine:
         self._check(self.lib.flowgnn_set_weights(self._h, len(arrs), ptrs), "flowgnn_set_weights")
 
     def load_weights_dir(self, directory: str, eps: bool = False, virtual_node: bool = False, attention_pooling: bool = False,
-                         set2set: bool = False, set2set_steps: int = 2):
+                         set2set: bool = False, set2set_steps: int = 2, edge_linear: bool = False):
         """eps=True (GIN, GIN-VN): also read the directory's eps file and apply it (set_gin_eps); virtual_node=True: also read
         gin_ep1_virtualnode_dim100.bin and apply it (GIN: set_ogb_virtual_node), or gcn_ep1_virtualnode_dim100.bin on a GCN engine
         (set_gcn_virtual_node; at width 300 gcn_ep1_virtualnode_dim300.bin, through flowgnn_set_gcn_virtual_node_dim).  The C call itself does neither.  A GIN engine at width 300 (set_emb_dim) reads the dim300 set, its eps
@@ -262,6 +262,10 @@ class Engine:
         if set2set:
             from .weights import load_set2set
             self.set_set2set_pooling(load_set2set(directory, model=self.model, emb_dim=self.emb_dim), steps=set2set_steps)
+        if edge_linear:  # (GIN at width 300: gin_ep1_edgelin_dim300.bin, OGB's linear edge encoder of ogbg-ppa, through set_edge_linear)
+            from .weights import load_edge_linear
+            el = load_edge_linear(directory, emb_dim=self.emb_dim, num_layers=self.num_layers)
+            self.set_edge_linear(el["w"], el["b"])
 
     # ---- batch
     def set_job_totals(self, job_nodes: int = -1, job_edges: int = -1):
@@ -562,8 +566,9 @@ class Engine:
         self._check(self.lib.flowgnn_set_results_buffer(self._h, C.c_void_p(device_ptr)), "flowgnn_set_results_buffer")
 
     def forward(self, batch: GraphBatch, return_embeddings: bool = False, return_node_embeddings: bool = False,
-                return_node_logits: bool = False, return_attention=None):
+                return_node_logits: bool = False, return_attention=None, edge_features=None):
         """set_batch + run + results; return_embeddings: (logits, embeddings) -- embeddings stay on for later runs;
+        edge_features: what set_edge_features takes, attached behind set_batch (the batch's float edge features, for set_edge_linear);
         return_node_embeddings: the node embeddings [N][embedding_dim] appended to the tuple (they stay on likewise);
         return_node_logits: the per-node readout terms [N] or [N][num_tasks] appended last (likewise);
         return_attention (GAT): what set_attention takes; the pair attention() returns is appended after everything else (likewise)."""
@@ -577,6 +582,8 @@ class Engine:
         if return_node_logits:
             self.set_node_logits(True)
         self.set_batch(batch)
+        if edge_features is not None:
+            self.set_edge_features(edge_features)
         self.run()
         ret = (self.results(),) + ((self.embeddings(),) if return_embeddings else ()) + ((self.node_embeddings(),) if return_node_embeddings else ())
         ret += (self.node_logits(),) if return_node_logits else ()
@@ -781,6 +788,44 @@ class Engine:
         jk, res = C.c_int(0), C.c_int(0)
         self.lib.flowgnn_jk_residual(self._h, C.byref(jk), C.byref(res))
         return JK_NAMES[jk.value], bool(res.value)
+
+    def set_edge_linear(self, w=None, b=None):
+        """GIN at width 300: OGB's linear edge encoder, the layer of ogbg-ppa (flowgnn.h: flowgnn_set_edge_linear).  w [L][300][F],
+        b [L][300] with L = num_layers and F edge features per edge, 1 .. 10 (weights.load_edge_linear,
+        export.edge_linear_from_ogb_state_dict); (None, None) turns it off.  Set behind the depth; the engine's, across batches and
+        weight sets.  While it is on every batch needs set_edge_features (or forward(..., edge_features=...))."""
+        if w is None and b is None:
+            self._check(self.lib.flowgnn_set_edge_linear(self._h, 300, 0, None, None), "flowgnn_set_edge_linear")
+            return
+        w, b = _f32(w), _f32(b)
+        if w.ndim != 3 or b.shape != w.shape[:2] or w.shape[0] != self.num_layers:
+            raise ValueError(f"edge encoder: w is {w.shape} and b is {b.shape}; wanted [L][D][F] and [L][D] with L = {self.num_layers}")
+        self._check(self.lib.flowgnn_set_edge_linear(self._h, w.shape[1], w.shape[2], _pf(w), _pf(b)), "flowgnn_set_edge_linear")
+
+    @property
+    def edge_linear(self) -> int:
+        """The edge encoder's features per edge, 0 while it is off (flowgnn.h: flowgnn_edge_linear)."""
+        return int(self.lib.flowgnn_edge_linear(self._h))
+
+    def set_edge_features(self, ef):
+        """The float edge features [E][F] of the batch set last, in its edge order (flowgnn.h: flowgnn_set_edge_features): a NumPy
+        array, or a float32 torch tensor on the engine's device, which is copied on the engine's launch stream.  The next set_batch
+        drops them."""
+        if hasattr(ef, "data_ptr"):  # a torch tensor
+            if not ef.is_cuda or ef.device.index != self.device or str(ef.dtype) != "torch.float32" or ef.dim() != 2:
+                raise ValueError(f"edge features: wanted a 2-d float32 tensor on device {self.device}, got {ef.dtype} {tuple(ef.shape)} on {ef.device}")
+            import torch
+            ef = ef.contiguous()
+            es = torch.cuda.ExternalStream(self.stream_handle(), device=ef.device)
+            es.wait_stream(torch.cuda.current_stream(ef.device))  # what produced the tensor is done before the engine's copy reads it
+            self._check(self.lib.flowgnn_set_edge_features(self._h, int(ef.shape[1]), C.cast(C.c_void_p(ef.data_ptr() if ef.numel() else 0), _lib.p_float), 1),
+                        "flowgnn_set_edge_features")
+            ef.record_stream(es)
+            return
+        ef = _f32(ef)
+        if ef.ndim != 2:
+            raise ValueError(f"edge features: wanted [E][F], got {ef.shape}")
+        self._check(self.lib.flowgnn_set_edge_features(self._h, ef.shape[1], _pf(ef), 0), "flowgnn_set_edge_features")
 
     def exact_reruns(self) -> int:
         """Forward passes repeated on the exact-fp32 kernels (flowgnn.h: flowgnn_exact_reruns)."""

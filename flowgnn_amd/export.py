@@ -208,6 +208,42 @@ def set2set_from_ogb_state_dict(sd: Mapping, emb_dim: int = 300) -> Dict[str, np
     return _checked(out, shapes, lambda k, v: v)
 
 
+EDGE_LIN_KEY = "gnn_node.convs.0.edge_encoder.weight"  # what tells an ogbg-ppa state_dict (ppa/conv.py) from a molecular one
+
+
+def edge_linear_from_ogb_state_dict(sd: Mapping, num_layers: int = 5) -> Dict[str, np.ndarray]:
+    """The edge encoders of an ogbg-ppa `GNN(gnn_type='gin' | 'gin-virtual')` state_dict, `gnn_node.convs.l.edge_encoder.weight` [D][F]
+    and `.bias` [D] per layer, as the two tensors Engine.set_edge_linear / flowgnn_set_edge_linear take: w [L][D][F], b [L][D]."""
+    w = np.stack([_get(sd, f"gnn_node.convs.{l}.edge_encoder.weight") for l in range(num_layers)])
+    b = np.stack([_get(sd, f"gnn_node.convs.{l}.edge_encoder.bias") for l in range(num_layers)])
+    if w.ndim != 3 or b.shape != w.shape[:2] or not 1 <= w.shape[2] <= _weights.EDGE_LINEAR_MAX_DIM:
+        raise ExportError(f"edge_encoder: weight {w.shape[1:]} and bias {b.shape[1:]} per layer; wanted [D][F] and [D] with F in 1 .. "
+                          f"{_weights.EDGE_LINEAR_MAX_DIM} (flowgnn_set_edge_linear)")
+    if not (np.isfinite(w).all() and np.isfinite(b).all()):
+        raise ExportError("edge_encoder: non-finite values")
+    return OrderedDict([("w", w.astype(np.float32)), ("b", b.astype(np.float32))])
+
+
+def _ppa_as_molecular(sd: Mapping, num_layers: int) -> Dict:
+    """An ogbg-ppa state_dict with the keys of a molecular one where the two differ, so that the rest of the export is one path:
+    node_encoder = Embedding(1, D) becomes the atom tables with its row as the row of feature 0, value 0, and every other row zero (an
+    all-zero node_feature, which is what ppa's x is, then sums to exactly that row); the bond tables, which the engine does not read
+    while the edge encoder is on, are zero.  The edge encoders themselves go through edge_linear_from_ogb_state_dict."""
+    row = _get(sd, "gnn_node.node_encoder.weight")
+    if row.ndim != 2 or row.shape[0] != 1:
+        raise ExportError(f"gnn_node.node_encoder.weight is {row.shape}: ogbg-ppa's is Embedding(1, emb_dim)")
+    out = {k: v for k, v in sd.items() if ".edge_encoder." not in str(k) and k != "gnn_node.node_encoder.weight"}
+    for k, n in enumerate(ATOM_DIMS):
+        t = np.zeros((n, row.shape[1]))
+        if k == 0:
+            t[0] = row[0]
+        out[f"gnn_node.atom_encoder.atom_embedding_list.{k}.weight"] = t
+    for l in range(num_layers):
+        for k, n in enumerate(BOND_DIMS):
+            out[f"gnn_node.convs.{l}.bond_encoder.bond_embedding_list.{k}.weight"] = np.zeros((n, row.shape[1]))
+    return out
+
+
 def _mean_head_zeroed(sd: Mapping, emb_dim: int) -> Dict:
     """`sd` with graph_pred_linear replaced by an all-zero [T][D] head and bias: what the model's own set carries beside a set2set file"""
     t = _get(sd, "graph_pred_linear.weight").shape[0]
@@ -389,7 +425,11 @@ def export_weights(model: str, sd: Mapping, directory: str, multi_task: bool = F
     OGB's num_layer is read off the state_dict (num_layers_of_ogb_state_dict: the `gnn_node.convs.<l>` blocks) and sizes every per-layer
     tensor, the eps file and the virtual node's file; the file names stay the same.  A depth other than 5 is for an engine with
     flowgnn_set_num_layers(300, depth) / Engine.set_num_layers(depth) / `host GIN|GCN --emb-dim 300 --num-layer depth`; a depth outside
-    2 .. 8, and a depth other than 5 at width 100, are refused before any file is written."""
+    2 .. 8, and a depth other than 5 at width 100, are refused before any file is written.
+    An ogbg-ppa state_dict (GIN, 300 wide) is recognised by `gnn_node.convs.0.edge_encoder.weight`: its per-layer Linear(F, D) edge
+    encoders go into gin_ep1_edgelin_dim300.bin (w [L][D][F], then b [L][D]) for Engine.load_weights_dir(dir, edge_linear=True) to apply
+    (flowgnn_set_edge_linear); its node_encoder = Embedding(1, D) becomes the atom table's row of feature 0, value 0, with every other
+    row zero, so ppa's all-zero x reproduces it; the bond tables are written as zeros, which the engine does not read then."""
     m = model.upper()
     if set2set and m not in ("GIN", "GCN"):
         raise ExportError(f"set2set=True is GIN's and GCN's (flowgnn_set_set2set_pooling); {model} has no such readout")
@@ -412,6 +452,15 @@ def export_weights(model: str, sd: Mapping, directory: str, multi_task: bool = F
     if virtual_node and m not in ("GIN", "GCN"):
         raise ExportError(f"virtual_node=True is OGB's gin-virtual or gcn-virtual, which the engine runs as GIN or GCN (not {model})")
     depth = num_layers_of_ogb_state_dict(sd) if m in ("GIN", "GIN-VN", "GCN") else 5
+    edge_lin = None
+    if EDGE_LIN_KEY in sd:  # an ogbg-ppa model (before any file is written): its edge encoders, then the molecular keys for the rest
+        if m != "GIN":
+            raise ExportError(f"the state_dict has '{EDGE_LIN_KEY}': it is an ogbg-ppa model, which the engine runs as GIN at width 300 "
+                              f"(flowgnn_set_edge_linear), not as {model}")
+        edge_lin = edge_linear_from_ogb_state_dict(sd, num_layers=depth)
+        if edge_lin["w"].shape[1] != 300:
+            raise ExportError(f"the ogbg-ppa state_dict is {edge_lin['w'].shape[1]} wide: only the 300-wide GIN has the linear edge encoder")
+        sd = _ppa_as_molecular(sd, depth)
     if m in ("GIN", "GIN-VN", "GCN"):  # (before any file is written; the width as the two exporters below read it)
         width = int(emb_dim) if m == "GCN" else int(_get(sd, "gnn_node.atom_encoder.atom_embedding_list.0.weight").shape[-1])
         if not _weights.MIN_NUM_LAYERS <= depth <= _weights.MAX_NUM_LAYERS:
@@ -436,6 +485,8 @@ def export_weights(model: str, sd: Mapping, directory: str, multi_task: bool = F
             _weights.save_attention_pooling(gate, directory, model="GIN")
         if set2set:
             _weights.save_set2set(s2s, directory, model="GIN")
+        if edge_lin is not None:  # gin_ep1_edgelin_dim300.bin, for Engine.load_weights_dir(dir, edge_linear=True)
+            _weights.save_edge_linear(edge_lin, directory)
     elif m == "GCN":
         w = gcn_weights_from_ogb_state_dict(sd, num_layers=depth, multi_task=multi_task, virtual_node=virtual_node, emb_dim=emb_dim, virtual_node_dim=virtual_node_dim)
         vn = gcn_virtual_node_from_ogb_state_dict(sd, num_layers=depth, virtual_node_dim=virtual_node_dim) if virtual_node else None  # (before any file is written)

@@ -346,6 +346,43 @@ def synth_attention_pooling(seed: int = 11, emb_dim: int = 300) -> Dict[str, np.
     return OrderedDict([("w1", w1), ("b1", b1), ("w2", w2)])
 
 
+# OGB's linear edge encoder for GIN at width 300, the layer of ogbg-ppa (flowgnn.h: flowgnn_set_edge_linear): one file beside the model's
+# set, w [L][D][F] then b [L][D].  F, the features per edge, is no part of the name: it is recovered from the file's size and L
+EDGE_LINEAR_MAX_DIM = 10  # flowgnn.h: FLOWGNN_MAX_EDGE_DIM
+
+
+def edge_linear_file(emb_dim: int = 300) -> str:
+    """gin_ep1_edgelin_dim<emb_dim>.bin"""
+    if int(emb_dim) != 300:
+        raise ValueError(f"edge encoder: emb_dim {emb_dim} is not 300 (only the 300-wide GIN has this layer)")
+    return f"gin_ep1_edgelin_dim{int(emb_dim)}.bin"
+
+
+def save_edge_linear(el, directory: str) -> None:
+    """Write gin_ep1_edgelin_dim300.bin from {"w": [L][D][F], "b": [L][D]}: w, then b, little-endian float32.  Nothing applies the file
+    unless asked to: Engine.load_weights_dir(dir, edge_linear=True)."""
+    w, b = np.asarray(el["w"], dtype=np.float32), np.asarray(el["b"], dtype=np.float32)
+    if w.ndim != 3 or b.shape != w.shape[:2] or not 1 <= w.shape[2] <= EDGE_LINEAR_MAX_DIM:
+        raise ValueError(f"edge encoder: w is {w.shape} and b is {b.shape}; wanted [L][D][F] and [L][D], F in 1 .. {EDGE_LINEAR_MAX_DIM}")
+    name = edge_linear_file(w.shape[1])  # (refused before anything is created)
+    _depth(w.shape[0], w.shape[1])
+    os.makedirs(directory, exist_ok=True)
+    np.concatenate([w.ravel(), b.ravel()]).astype("<f4").tofile(os.path.join(directory, name))
+
+
+def load_edge_linear(directory: str, emb_dim: int = 300, num_layers: int = 5) -> Dict[str, np.ndarray]:
+    """The two tensors of a directory's edge-encoder file (for Engine.set_edge_linear) at the depth num_layers; a file whose size
+    fits no F in 1 .. 10 at that depth is refused."""
+    path = os.path.join(directory, edge_linear_file(emb_dim))
+    d, n = int(emb_dim), _depth(num_layers, emb_dim)
+    size = os.path.getsize(path)
+    f = size // (4 * n * d) - 1
+    if size != 4 * n * d * (f + 1) or not 1 <= f <= EDGE_LINEAR_MAX_DIM:
+        raise ValueError(f"{path} holds {size} bytes: not w [{n}][{d}][F] and b [{n}][{d}] for any F in 1 .. {EDGE_LINEAR_MAX_DIM} "
+                         f"(num_layers is {n}: flowgnn_set_num_layers)")
+    return OrderedDict([("w", _read(path, (n, d, f))), ("b", _read(path, (n, d), n * d * f))])
+
+
 # OGB's set2set readout for GIN and GCN at width 300 (flowgnn.h: flowgnn_set_set2set_pooling): one file beside the model's set, PyG's
 # Set2Set LSTM (pool.lstm.weight_ih_l0, weight_hh_l0, bias_ih_l0, bias_hh_l0; gate order i, f, g, o) and OGB's Linear(2D, NUM_TASK) head,
 # in the order of the C call's arguments.  The number of processing steps is no tensor: it is given where the file is applied

@@ -1025,6 +1025,39 @@ int flowgnn_set_num_layers(flowgnn_engine* e, int emb_dim, int num_layers);   /*
 int flowgnn_num_layers(const flowgnn_engine* e);                              /* -1 for a null handle */
 
 /*
+ * OGB's linear edge encoder for GIN at width 300, the layer of ogbg-ppa (examples/graphproppred/ppa/conv.py):
+ * edge_encoder = Linear(F, 300) per layer on F FLOAT edge features, the message of an edge relu(x_u + W_e e_uv + b_e), where the
+ * molecular models look the edge's row up in a table of 60.  Everything else of the model is what it was: the GIN MLP, eps, the virtual
+ * node (flowgnn_set_ogb_virtual_node_dim), the poolings and the attention / set2set readouts, NUM_TASK, the depth, graph and node
+ * embeddings, node logits, option hipgraph.  The layer runs gin_wide_el.hip's kernels: the encoder is one f16 MFMA per 16-column tile
+ * and trip of the in-edge walk, fp32-accurate by the split scheme; a feature at or beyond 6e4 or not finite repeats the pass on the
+ * exact fp32 kernels, as any operand out of range does (flowgnn_exact_reruns).
+ *   flowgnn_set_edge_linear   w [L][300][edge_dim], b [L][300], host arrays, copied; L = flowgnn_num_layers(e), so it is set behind the
+ *       depth, like eps, and a change of depth turns it off.  Both NULL: off.  edge_dim is 1 .. FLOWGNN_MAX_EDGE_DIM (ppa: 7).
+ *       ppa's node_encoder = Embedding(1, 300) needs no call: its row as the atom table's row of feature 0, value 0, every other row
+ *       zero, with an all-zero node_feature (what flowgnn_amd.export writes for a ppa state_dict).
+ *   flowgnn_set_edge_features  ef [E_tot][edge_dim] float32 in the edge order of the batch set last, a host array (on_device 0) or
+ *       memory of the engine's device (on_device 1, checked as flowgnn_set_batch_device checks its arrays); copied into a buffer of the
+ *       engine's own on its launch stream.  They belong to the batch: the next flowgnn_set_batch / _device drops them.  Drops a
+ *       recorded launch sequence.  Single engines only: groups and the <M>_compute_graphs entry points have no form of it.
+ * While the encoder is on, flowgnn_set_batch / _device accept edge_attr == NULL on this engine (a non-null one is validated as ever
+ * and not read), and flowgnn_run returns FLOWGNN_ERR_STATE without attached features or with features of another edge_dim.  While it
+ * is off every path, launch and bit is what it was; a batch that was set without edge_attr has to be set again then.
+ * FLOWGNN_ERR_ARG: a null handle; one of w, b NULL and not the other; edge_dim outside 1 .. 10; emb_dim other than the engine's width;
+ * a non-finite weight; ef NULL with edges in the batch; a device pointer that fails the check.
+ * FLOWGNN_ERR_UNSUPPORTED: any engine but FLOWGNN_MODEL_GIN at width 300 (GCN's ppa layer, width 100 and groups do not exist); and,
+ * while it is on, flowgnn_set_emb_dim to 100.
+ * FLOWGNN_ERR_STATE, from whichever call comes second: the encoder beside FLOWGNN_NUMERIC_F16 and beside JK sum or the residual
+ * (flowgnn_set_numeric_mode_dim, flowgnn_set_jk_residual) -- those instances of the layer have no encoder; flowgnn_set_edge_features
+ * without a batch.
+ * flowgnn_edge_linear: edge_dim while on, 0 while off, -1 for a null handle.
+ */
+#define FLOWGNN_MAX_EDGE_DIM 10
+int flowgnn_set_edge_linear(flowgnn_engine* e, int emb_dim, int edge_dim, const float* w /* [L][300][edge_dim] */, const float* b /* [L][300] */);
+int flowgnn_edge_linear(const flowgnn_engine* e);
+int flowgnn_set_edge_features(flowgnn_engine* e, int edge_dim, const float* ef /* [E_tot][edge_dim] */, int on_device);
+
+/*
  * Laplacian eigenvectors: DGN's node_eigen from the graphs alone (the reference reads it from DGN/eig/g%d.txt and does not say where it
  * comes from).  For graph g with n nodes and edges (u, v) in local ids:
  *     A[u][v] = A[v][u] = 1 for every edge with u != v   (both directions and duplicates collapse to 1, self loops are ignored)
