@@ -96,6 +96,7 @@ def _declare(lib):
     lib.flowgnn_set_num_layers.argtypes = [eng, C.c_int, C.c_int]
     lib.flowgnn_num_layers.argtypes = [eng]
     lib.flowgnn_set_edge_linear.argtypes = [eng, C.c_int, C.c_int, p_float, p_float]
+    lib.flowgnn_set_model_edge_linear.argtypes = [eng, C.c_int, C.c_int, p_float, p_float]
     lib.flowgnn_edge_linear.argtypes = [eng]
     lib.flowgnn_set_edge_features.argtypes = [eng, C.c_int, p_float, C.c_int]
     lib.flowgnn_set_num_tasks.argtypes = [eng, C.c_int]
@@ -205,7 +206,7 @@ def _declare(lib):
                  "flowgnn_set_set2set_pooling", "flowgnn_set2set_pooling", "flowgnn_group_set_set2set_pooling",
                  "flowgnn_set_jk_residual", "flowgnn_jk_residual", "flowgnn_group_set_jk_residual", "flowgnn_set_model_jk_residual", "flowgnn_group_set_model_jk_residual",
                  "flowgnn_set_num_layers", "flowgnn_num_layers", "flowgnn_group_set_num_layers",
-                 "flowgnn_set_edge_linear", "flowgnn_edge_linear", "flowgnn_set_edge_features",
+                 "flowgnn_set_edge_linear", "flowgnn_set_model_edge_linear", "flowgnn_edge_linear", "flowgnn_set_edge_features",
                  "flowgnn_laplacian_eigen_max_nodes", "flowgnn_laplacian_eigen", "flowgnn_laplacian_eigen_device",
                  "GIN_compute_graphs_mt", "GCN_compute_graphs_mt", "GIN_compute_graphs", "GCN_compute_graphs", "PNA_compute_graphs", "DGN_compute_graphs", "GAT_compute_graphs"):
         getattr(lib, name).restype = C.c_int

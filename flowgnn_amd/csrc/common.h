@@ -188,7 +188,7 @@ struct DeviceBatch {
     int s2s_steps;            // launch is the one it always was.  A forward that finds it set runs s2s_steps set2set steps and the readout's own head
     int jk;                   // flowgnn_set_jk_residual (GIN at width 300): FLOWGNN_JK_LAST / FLOWGNN_JK_SUM and OGB's residual flag; (0, 0): off, every
     int residual;             // launch is the one it always was.  Under JK sum the rows the readout pools (and node_emb) are the sum, h[final_h] stays h_5
-    const void* edge_lin;     // flowgnn_set_edge_linear (GIN at width 300): the encoder's tensors in the device form of gin_wide_el.h, or null: off, every
+    const void* edge_lin;     // flowgnn_set_edge_linear / _model_edge_linear (GIN, GCN at width 300): the encoder's tensors (gin_wide_el.h), or null: off, every
     int edge_lin_dim;         // launch is the one it always was; its edge_dim; and the batch's float edge features [E][edge_lin_dim] in the caller's
     const float* edge_feat;   // edge order (flowgnn_set_edge_features; flowgnn_run refuses the run while the encoder is on and they are missing)
     int final_h;              // which h[] holds the last stage's output (set by forward)

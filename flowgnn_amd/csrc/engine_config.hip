@@ -8,6 +8,7 @@
 // holds that order.  A new option that carries tensors follows flowgnn_set_attention_pooling: width_argument, tensor_set_on, its own
 // argument checks, tensor_set_finite, its state checks, begin_change, upload_packed, its own fields.
 #include "engine_internal.h"
+#include "gcn_wide_el.h"
 #include "gin_wide_el.h"
 #include "wide_attn.h"
 #include "wide_s2s.h"
@@ -148,7 +149,7 @@ static int set_width(flowgnn_engine* e, const char* fn, int emb_dim) {
                                                   (gcn ? "GCN" : "GIN") + " has those instances, not width " + std::to_string(emb_dim) +
                                                   ": turn it off (FLOWGNN_JK_LAST, 0), then change the width");
     if (e->edge_lin_dim)  // (on means width 300: the call asks for 100, which has no such kernel)
-        return refuse(e, FLOWGNN_ERR_UNSUPPORTED, who + "OGB's linear edge encoder is on (flowgnn_set_edge_linear), and only the 300-wide GIN has it: turn it off, then change the width");
+        return refuse(e, FLOWGNN_ERR_UNSUPPORTED, who + "OGB's linear edge encoder is on (flowgnn_set_edge_linear / flowgnn_set_model_edge_linear), and only the 300-wide GIN and GCN have it: turn it off, then change the width");
     if (e->num_layers != FLOWGNN_NUM_LAYERS_DEFAULT)  // (not 5 means width 300: the call asks for 100, whose kernels are five layers deep)
         return refuse(e, FLOWGNN_ERR_UNSUPPORTED, who + "the depth is " + std::to_string(e->num_layers) + " (flowgnn_set_num_layers), and the " + std::to_string(emb_dim) +
                                                   "-wide kernels are five layers deep: flowgnn_set_num_layers(e, " + std::to_string(e->emb_dim) + ", 5) first, then change the width");
@@ -264,7 +265,7 @@ static int set_numeric_mode(flowgnn_engine* e, int mode, ModeRoute route) {
     if (mode == FLOWGNN_NUMERIC_Q6_10 && e->ogb_vn_on)
         return refuse(e, FLOWGNN_ERR_UNSUPPORTED, "flowgnn_set_numeric_mode: OGB's virtual node is on (flowgnn_set_ogb_virtual_node / flowgnn_set_gcn_virtual_node), and the fixed-point arithmetic is the reference's, which has no such model");
     if (mode == FLOWGNN_NUMERIC_F16 && e->edge_lin_dim)
-        return refuse(e, FLOWGNN_ERR_STATE, "flowgnn_set_numeric_mode: OGB's linear edge encoder is on (flowgnn_set_edge_linear), and the f16 instances of the layer have no encoder: "
+        return refuse(e, FLOWGNN_ERR_STATE, "flowgnn_set_numeric_mode: OGB's linear edge encoder is on (flowgnn_set_edge_linear / flowgnn_set_model_edge_linear), and the f16 instances of the layer have no encoder: "
                                             "turn one of the two off");
     e->drop_graph();
     const int rc = e->model->set_numeric_mode(mode);
@@ -596,13 +597,16 @@ int flowgnn_set_num_layers(flowgnn_engine* e, int emb_dim, int num_layers) {
 }
 
 int flowgnn_num_layers(const flowgnn_engine* e) { return e ? e->num_layers : -1; }
+}  // extern "C"
 
 // ------------------------------------------------------------------ OGB's linear edge encoder
-// GIN at width 300: the encoder's two tensors in the device form of gin_wide_el.h, one device buffer owned by
-// the engine; db.edge_lin / db.edge_lin_dim carry it to GinWideModel::forward.  Both NULL: off, at any width and for any model.
-int flowgnn_set_edge_linear(flowgnn_engine* e, int emb_dim, int edge_dim, const float* w, const float* b) {
-    if (!e) return FLOWGNN_ERR_ARG;
-    const std::string who = "flowgnn_set_edge_linear: ";
+// GIN and, through the model form of the call, GCN (section 4.32) at width 300: the encoder's two tensors in
+// the device form of gin_wide_el.h / gcn_wide_el.h, one device buffer owned by the engine; db.edge_lin / db.edge_lin_dim carry it to
+// GinWideModel::forward / GcnWideModel::forward.  Both NULL: off, at any width and for any model.
+// `fn`: the caller.  model_form: flowgnn_set_model_edge_linear, which a GCN engine accepts; on a GIN engine the two calls are one.
+static int set_edge_linear(flowgnn_engine* e, const char* fn, bool model_form, int emb_dim, int edge_dim, const float* w, const float* b) {
+    const std::string who = std::string(fn) + ": ";
+    const bool gcn = e->model_id == FLOWGNN_MODEL_GCN;
     if (int rc = width_argument(e, who, emb_dim)) return rc;
     const bool given = w || b;
     if (given && (edge_dim < 1 || edge_dim > FLOWGNN_MAX_EDGE_DIM))
@@ -614,20 +618,31 @@ int flowgnn_set_edge_linear(flowgnn_engine* e, int emb_dim, int edge_dim, const 
     if (int rc = tensor_set_on(e, who, t, &on)) return rc;
     if (on) {
         if (int rc = tensor_set_finite(e, who, t)) return rc;
-        if (e->model_id != FLOWGNN_MODEL_GIN)
-            return refuse(e, FLOWGNN_ERR_UNSUPPORTED, who + "the linear edge encoder exists for FLOWGNN_MODEL_GIN only (OGB's gin and gin-virtual of ogbg-ppa; its GCNConv has no kernel here)");
-        if (int rc = width_matches(e, who, true, emb_dim, e->emb_dim, "flowgnn_set_emb_dim")) return rc;
-        if (fg::gw_el_blob_bytes(emb_dim, e->num_layers, edge_dim) == 0)
-            return refuse(e, FLOWGNN_ERR_UNSUPPORTED, who + "only the 300-wide GIN has this layer (the 100-wide kernels look the edge's row up in their table): flowgnn_set_emb_dim(e, 300) first");
+        if (gcn && !model_form)
+            return refuse(e, FLOWGNN_ERR_UNSUPPORTED, who + "the linear edge encoder exists for FLOWGNN_MODEL_GIN only under this call (OGB's gin and gin-virtual of ogbg-ppa) -- it is "
+                                                            "flowgnn_set_model_edge_linear that carries it for FLOWGNN_MODEL_GCN at width 300");
+        if (!gcn && e->model_id != FLOWGNN_MODEL_GIN)
+            return refuse(e, FLOWGNN_ERR_UNSUPPORTED, who + (model_form ? "the linear edge encoder exists for FLOWGNN_MODEL_GIN and FLOWGNN_MODEL_GCN only (OGB's gin, gin-virtual, gcn and "
+                                                                          "gcn-virtual of ogbg-ppa)"
+                                                                        : "the linear edge encoder exists for FLOWGNN_MODEL_GIN only (OGB's gin and gin-virtual of ogbg-ppa)"));
+        if (int rc = width_matches(e, who, true, emb_dim, e->emb_dim, gcn ? "flowgnn_set_model_emb_dim" : "flowgnn_set_emb_dim")) return rc;
+        if ((gcn ? fg::gcw_el_blob_bytes(emb_dim, e->num_layers, edge_dim) : fg::gw_el_blob_bytes(emb_dim, e->num_layers, edge_dim)) == 0)
+            return refuse(e, FLOWGNN_ERR_UNSUPPORTED, who + "only the 300-wide " + (gcn ? "GCN" : "GIN") + " has this layer (the 100-wide kernels look the edge's row up in their table): " +
+                                                            (gcn ? "flowgnn_set_model_emb_dim" : "flowgnn_set_emb_dim") + "(e, 300) first");
         if (e->numeric_mode != FLOWGNN_NUMERIC_F32)
-            return refuse(e, FLOWGNN_ERR_STATE, who + "FLOWGNN_NUMERIC_F16 is on (flowgnn_set_numeric_mode_dim), and the f16 instances of the layer have no encoder: turn one of the two off");
+            return refuse(e, FLOWGNN_ERR_STATE, who + "FLOWGNN_NUMERIC_F16 is on (" + (gcn ? "flowgnn_set_model_numeric_mode_dim" : "flowgnn_set_numeric_mode_dim") +
+                                                      "), and the f16 instances of the layer have no encoder: turn one of the two off");
         if (e->jk != FLOWGNN_JK_LAST || e->residual)
-            return refuse(e, FLOWGNN_ERR_STATE, who + "JK sum or the residual is on (flowgnn_set_jk_residual), and those instances of the layer have no encoder: turn one of the two off");
+            return refuse(e, FLOWGNN_ERR_STATE, who + "JK sum or the residual is on (" + (gcn ? "flowgnn_set_model_jk_residual" : "flowgnn_set_jk_residual") +
+                                                      "), and those instances of the layer have no encoder: turn one of the two off");
     }
     ENGINE_TRY(e, begin_change(e));
     if (on)
-        if (int rc = upload_packed(e, e->edge_lin, fg::gw_el_blob_bytes(emb_dim, e->num_layers, edge_dim),
-                                   [&](float* dst) { fg::gw_el_blob_pack(emb_dim, e->num_layers, edge_dim, w, b, dst); }))
+        if (int rc = upload_packed(e, e->edge_lin, gcn ? fg::gcw_el_blob_bytes(emb_dim, e->num_layers, edge_dim) : fg::gw_el_blob_bytes(emb_dim, e->num_layers, edge_dim),
+                                   [&](float* dst) {
+                                       if (gcn) fg::gcw_el_blob_pack(emb_dim, e->num_layers, edge_dim, w, b, dst);
+                                       else fg::gw_el_blob_pack(emb_dim, e->num_layers, edge_dim, w, b, dst);
+                                   }))
             return rc;
     e->edge_lin_dim = on ? edge_dim : 0;
     e->db.edge_lin = on ? e->edge_lin.p : nullptr;  // (launches are stream-ordered: it matters to those enqueued after this call)
@@ -637,6 +652,18 @@ int flowgnn_set_edge_linear(flowgnn_engine* e, int emb_dim, int edge_dim, const 
         e->ran = false;
     }
     return FLOWGNN_OK;
+}
+
+extern "C" {
+
+int flowgnn_set_edge_linear(flowgnn_engine* e, int emb_dim, int edge_dim, const float* w, const float* b) {
+    if (!e) return FLOWGNN_ERR_ARG;
+    return set_edge_linear(e, "flowgnn_set_edge_linear", false, emb_dim, edge_dim, w, b);
+}
+
+int flowgnn_set_model_edge_linear(flowgnn_engine* e, int emb_dim, int edge_dim, const float* w, const float* b) {
+    if (!e) return FLOWGNN_ERR_ARG;
+    return set_edge_linear(e, "flowgnn_set_model_edge_linear", true, emb_dim, edge_dim, w, b);
 }
 
 int flowgnn_edge_linear(const flowgnn_engine* e) { return e ? e->edge_lin_dim : -1; }
@@ -671,7 +698,7 @@ static int set_jk_residual(flowgnn_engine* e, const char* fn, bool model_form, i
     }
     ENGINE_TRY(e, use_device(e));
     if ((jk != FLOWGNN_JK_LAST || residual) && e->edge_lin_dim)
-        return refuse(e, FLOWGNN_ERR_STATE, who + "OGB's linear edge encoder is on (flowgnn_set_edge_linear), and the JK / residual instances of the layer have no encoder: "
+        return refuse(e, FLOWGNN_ERR_STATE, who + "OGB's linear edge encoder is on (flowgnn_set_edge_linear / flowgnn_set_model_edge_linear), and the JK / residual instances of the layer have no encoder: "
                                                   "turn one of the two off");
     e->drop_graph();  // a recorded launch sequence is that of the other setting
     e->jk = jk;

@@ -108,7 +108,7 @@ struct flowgnn_engine {
     fg::GrowBuf s2s;                  // ... and its six tensors on the device (wide_s2s.h)
     int jk = FLOWGNN_JK_LAST;         // flowgnn_set_jk_residual: the engine's as well, across batches and weight sets (db.jk / db.residual follow)
     int residual = 0;
-    int edge_lin_dim = 0;             // flowgnn_set_edge_linear: the engine's as well, 0 = off (db.edge_lin / db.edge_lin_dim follow it)
+    int edge_lin_dim = 0;             // flowgnn_set_edge_linear / flowgnn_set_model_edge_linear: the engine's, 0 = off (db.edge_lin / db.edge_lin_dim follow it)
     fg::GrowBuf edge_lin;             // ... and its tensors on the device (gin_wide_el.h)
     int edge_feat_dim = 0;            // flowgnn_set_edge_features: the resident BATCH's, 0 = none attached (db.edge_feat follows it) ...
     fg::GrowBuf edge_feat;            // ... and the engine's copy of them [E][edge_feat_dim]

@@ -49,6 +49,10 @@
 // FLOWGNN_NUMERIC_F16 at this width (flowgnn_set_model_numeric_mode_dim): stages 0..3 run gcn_wide_f16.hip's
 // kernels (one rounding of a and of W s to f16, one MFMA per product) on a hi-only stream that set_weights packs beside the split one
 // whatever the mode is; stage 4, the virtual node's update, the readout and the exact re-run are the ones above.
+//
+// OGB's linear edge encoder (flowgnn_set_model_edge_linear), the GCNConv of ogbg-ppa: the edge term inside
+// the relu is W_e e_uv + b_e from the edge's float features.  Every stage then runs gcn_wide_el.hip's kernels (the encoder on the
+// matrix pipe inside the walk; the exact re-run: gcw_aggregate_el_kernel) under slots of their own; the rest of the pass is the same.
 #include <cmath>
 #include <cstring>
 #include <string>
@@ -59,6 +63,7 @@
 #include "common.h"
 #include "dense_split.h"
 #include "gcn_ogbvn.h"
+#include "gcn_wide_el.h"    // flowgnn_set_model_edge_linear (section 4.32): the launchers of gcn_wide_el.hip's kernels
 #include "gcn_wide_body.h"  // GcwDims, gcw_walk, gcw_step, gcw_vn_add_partials and the layer kernel's body, which gcn_wide_jk.hip instantiates as well (section 4.25)
 #include "gcn_wide_f16.h"   // FLOWGNN_NUMERIC_F16 (section 4.27): the hi-only stream's layout and the launcher of gcn_wide_f16.hip's kernels
 #include "gcn_wide_jk.h"    // flowgnn_set_model_jk_residual (section 4.25): the launchers of gcn_wide_jk.hip's instances
@@ -415,6 +420,10 @@ public:
             if (int rc = res_.reserve((size_t)n * D)) return rc;
         if (jk_on)
             if (int rc = jk_.reserve((size_t)n * D)) return rc;
+        // OGB's linear edge encoder (flowgnn_set_model_edge_linear, section 4.32): every stage's launch is gcn_wide_el.hip's, under slots
+        // of their own; the engine keeps it apart from the f16 mode and JK / residual, whose instances have no encoder
+        const bool el_on = db.edge_lin != nullptr;
+        if (el_on && (f16_ || ext_on || (db.b.e_tot > 0 && !db.edge_feat))) return FLOWGNN_ERR_STATE;
         if (int rc = readout_.reserve(db, exact_)) return rc;  // the attention readout (section 4.20): the gates [N] ...
         if (db.attn_pool && exact_)                    // ... and the exact form's hidden rows [N][2 D]
             if (int rc = hid_.reserve((size_t)(n > G ? n : G) * 2 * D)) return rc;
@@ -458,7 +467,19 @@ public:
             float* const rres = res_on ? res_.p : nullptr;
             const float* const jk_in = !jk_on ? nullptr : (l == 0 && res_on) ? res_.p : jk_.p;
             float* const jk_out = !jk_on ? nullptr : (last && db.node_emb) ? db.node_emb : jk_.p;
-            if (!exact_ && f16_ && !last) {  // FLOWGNN_NUMERIC_F16 (section 4.27): the four instances of gcn_wide_f16.hip, a slot of their own
+            if (!exact_ && el_on) {
+                ProfScope p(prof, "gcn_wide_layer_el", s);
+                int rc;
+                if (!last)
+                    rc = launch_gcw_layer_el(D, db.edge_lin, db.edge_lin_dim, l, db.h[cur], hn, db.csr.row_ptr, db.csr.src, db.csr.eid, db.edge_feat, esc_.p,
+                                             db.csr.out_deg, tab, d_chunks_ + (size_t)l * M::LAYER_BYTES, d_tails_ + (size_t)l * M::TAIL_FLOATS, n,
+                                             db.range_flag, vn ? node_graph_.p : nullptr, vn ? vn_vec_[l & 1].p : nullptr,
+                                             vn && feeds_update(l) ? vn_part_.p : nullptr, s);
+                else
+                    rc = launch_gcw_final_el(D, db.edge_lin, db.edge_lin_dim, l, db.h[cur], hn, db.csr.row_ptr, db.csr.src, db.csr.eid, db.edge_feat, esc_.p,
+                                             db.csr.out_deg, tab, n, db.range_flag, s);
+                if (rc) return rc;
+            } else if (!exact_ && f16_ && !last) {  // FLOWGNN_NUMERIC_F16 (section 4.27): the four instances of gcn_wide_f16.hip, a slot of their own
                 ProfScope p(prof, "gcn_wide_layer_f16", s);
                 if (int rc = launch_gcw_layer_f16(D, db.h[cur], hn, db.csr.row_ptr, db.csr.src, db.csr.ecode, esc_.p, db.csr.out_deg, tab,
                                                   d_chunks16_ + (size_t)l * F16::LAYER_BYTES, d_tails_ + (size_t)l * M::TAIL_FLOATS, n, db.range_flag,
@@ -492,9 +513,16 @@ public:
                 else
                     gcw_final_kernel<D><<<grid, GW_WAVES * 64, 0, s>>>(db.h[cur], hn, db.csr.row_ptr, db.csr.src, db.csr.ecode, esc_.p, db.csr.out_deg, tab, n);
             } else {
+                if (el_on) {  // (the exact form of the encoder: the aggregate under a slot of its own, the rest as ever)
+                    ProfScope p(prof, "gcn_wide_aggregate_el", s);
+                    if (int rc = launch_gcw_aggregate_el(D, db.edge_lin, db.edge_lin_dim, l, db.h[cur], last ? hn : db.scratch, db.csr.row_ptr, db.csr.src,
+                                                         db.csr.eid, db.edge_feat, esc_.p, db.csr.out_deg, tab, n, last ? 0 : 1, s))
+                        return rc;
+                }
                 ProfScope p(prof, "gcn_wide_layer_f32", s);
-                gcw_aggregate_kernel<D><<<grid_for((long long)n * M::C, 256, 256 * 8), 256, 0, s>>>(
-                    db.h[cur], last ? hn : db.scratch, db.csr.row_ptr, db.csr.src, db.csr.ecode, esc_.p, db.csr.out_deg, tab, n, last ? 0 : 1);
+                if (!el_on)
+                    gcw_aggregate_kernel<D><<<grid_for((long long)n * M::C, 256, 256 * 8), 256, 0, s>>>(
+                        db.h[cur], last ? hn : db.scratch, db.csr.row_ptr, db.csr.src, db.csr.ecode, esc_.p, db.csr.out_deg, tab, n, last ? 0 : 1);
                 // (the adds in the fast path's order: the residual, the virtual node's vector, the JK sum -- then the pool and the product)
                 float* const rows = last ? hn : db.scratch;
                 if (res_on)

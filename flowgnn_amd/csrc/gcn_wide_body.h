@@ -4,6 +4,8 @@
 // the layer and its virtual-node instance), gcn_wide_jk.hip the two with OGB's residual=True and JK="sum" behind the walk (EXT = true;
 // flowgnn_set_model_jk_residual, section 4.25) and the final stage with them (gcw_final_jk_body).  EXT is a compile-time constant:
 // with it false the extra code does not exist and a kernel is the one it was before this header did.
+// gcn_wide_el.hip has the instances with OGB's linear edge encoder in the walk (EL = true; flowgnn_set_model_edge_linear, section
+// 4.32): compile time as well, and with it false the walk is the table's, instruction for instruction.
 #pragma once
 #include <type_traits>
 
@@ -43,12 +45,52 @@ struct GcwDims {
     static constexpr int TAIL_FLOATS = SCALE_AT + 4;
 };
 
+// EL (section 4.32, OGB's linear edge encoder): what the walk reads where the edge codes go, and the layer's block in LDS where the
+// table goes -- the T fragments of W_e and b_e (wide_el_pack.h) | 1 / scale, padded to 16 bytes | root | BN scale | BN shift
+struct GcwElArgs {
+    const int* eid;    // CSR position -> the caller's edge
+    const float* ef;   // [E][el_f] float features in the caller's edge order
+    int el_f;
+    float* vmax;       // the lane's range tracker: inf once a feature is beyond the f16 range or not finite
+};
+struct GcwNoElArgs {};
+template <int D>
+struct GcwElLds {
+    static constexpr int FRAG_BYTES = GcwDims<D>::T * 1024 + 16;  // fragments and 1 / scale: contiguous in the encoder's blob as well
+    static constexpr int FRAG_PIECES = (FRAG_BYTES + 1023) / 1024;
+    static constexpr int FRAG_LAST_LANES = (FRAG_BYTES - (FRAG_PIECES - 1) * 1024) / 16;
+    static constexpr int INV_FLOAT = GcwDims<D>::T * 256;
+    static constexpr int EP_FLOAT = FRAG_BYTES / 4;  // root | BN scale | BN shift, from the layer's table in global memory
+    static constexpr int EP_BYTES = 3 * D * 4;
+    static constexpr int EP_PIECES = (EP_BYTES + 1023) / 1024;
+    static constexpr int EP_LAST_LANES = (EP_BYTES - (EP_PIECES - 1) * 1024) / 16;
+    static constexpr int BYTES = FRAG_BYTES + EP_BYTES;
+    static_assert(EP_BYTES % 16 == 0 && FRAG_BYTES % 16 == 0, "both parts are copied in 16-byte pieces");
+};
+
+// the layer's block, LDS-DMA'd: the fragments and 1 / scale from the encoder's blob, root | BN scale | BN shift from the layer's table
+template <int D>
+__device__ __forceinline__ void gcw_el_issue_block(const uint8_t* __restrict__ lblob, const float* __restrict__ tab, char* s_blk, int wave, int lane) {
+    using E = GcwElLds<D>;
+    gw_issue_pieces<E::FRAG_PIECES>(lblob, s_blk, E::FRAG_PIECES, E::FRAG_LAST_LANES, wave, lane);
+    gw_issue_pieces<E::EP_PIECES>(reinterpret_cast<const uint8_t*>(tab + GcwDims<D>::ECOMB_FLOATS), s_blk + E::FRAG_BYTES, E::EP_PIECES, E::EP_LAST_LANES,
+                                  wave, lane);
+}
+
+// the trips of the EL walk: gcn_wide_el.hip, the one translation unit with EL = true, defines it in front of its kernels; in every
+// other instance the call in gcw_walk is discarded and nothing of it exists
+template <int D>
+__device__ __forceinline__ void gcw_el_trips(const float* __restrict__ x, const int* __restrict__ src, const float* __restrict__ esc,
+                                             const GcwElArgs& el, const float* s_blk, int e, int e_end, float dinv_v, int g,
+                                             float (&a)[4 * GcwDims<D>::Q]);
+
 // a[v] = act(BN(m[v] + relu(x[v] + root) / (deg(v) + 1))) of this lane's node in the B-operand layout; s_tab: the layer's table in LDS.
 // The accumulate is an explicit fma at every place this is inlined (GcnAggPolicy::edge says why), and so is the epilogue.
-template <int D, bool RELU_OUT>
+template <int D, bool RELU_OUT, bool EL = false>
 __device__ __forceinline__ void gcw_walk(const float* __restrict__ x, const int* __restrict__ row_ptr, const int* __restrict__ src,
                                          const uint8_t* __restrict__ ecode, const float* __restrict__ esc, const int* __restrict__ out_deg,
-                                         const float* s_tab, long long node, bool valid, int g, float (&a)[4 * GcwDims<D>::Q]) {
+                                         const float* s_tab, long long node, bool valid, int g, float (&a)[4 * GcwDims<D>::Q],
+                                         typename std::conditional<EL, GcwElArgs, GcwNoElArgs>::type el = {}) {
     using M = GcwDims<D>;
     int e = row_ptr[node];
     const int e_end = valid ? row_ptr[node + 1] : e;
@@ -57,9 +99,10 @@ __device__ __forceinline__ void gcw_walk(const float* __restrict__ x, const int*
     const float idp1 = 1.0f / (float)(dv + 1);
 #pragma unroll
     for (int k = 0; k < 4 * M::Q; k++) a[k] = 0.0f;
+    if constexpr (EL) gcw_el_trips<D>(x, src, esc, el, s_tab, e, e_end, dinv_v, g, a);
     int u_nx = 0, c_nx = 0;
     float n_nx = 0.0f;
-    if (e < e_end) { u_nx = src[e]; c_nx = ecode[e]; n_nx = esc[e]; }
+    if (!EL && e < e_end) { u_nx = src[e]; c_nx = ecode[e]; n_nx = esc[e]; }
     // Piece q of a row is columns 16 q + 4 g .. + 3.  The one piece that straddles column D (D % 16 != 0) is read by the lanes beyond D
     // from the row's last four columns instead -- in bounds, and no branch inside the walk; what those lanes hold of it is zeroed
     // at the end, so pieces at or beyond column D stay zero.  NQ: the pieces that exist.
@@ -69,7 +112,7 @@ __device__ __forceinline__ void gcw_walk(const float* __restrict__ x, const int*
     // ---- one in-edge per trip, in CSR order (a row's sum depends on the row alone); the CSR entry one edge ahead of the row loads
     // (a lane whose row is done runs the trip with norm 0 on the entry it read last, or on row 0: fma(0, finite, a) is a, and the 4 Q
     // accumulators are updated on one path -- under `if (e < e_end)` they were copied to and fro on every trip)
-    while (__any(e < e_end)) {
+    while (!EL && __any(e < e_end)) {
         const int u = u_nx, code = c_nx;
         const float norm = e < e_end ? n_nx * dinv_v : 0.0f;
         e += e < e_end;
@@ -98,7 +141,7 @@ __device__ __forceinline__ void gcw_walk(const float* __restrict__ x, const int*
     }
     // ---- the node's own row, after the walk (another 4 Q registers before it), and the epilogue: root, 1 / (deg + 1), folded BatchNorm
     const float* xr = x + (size_t)node * D + 4 * g;
-    const float* ep = s_tab + M::ECOMB_FLOATS + 4 * g;
+    const float* ep = s_tab + (EL ? GcwElLds<D>::EP_FLOAT : M::ECOMB_FLOATS) + 4 * g;
     // (a fence every four pieces: left alone, the scheduler hoists all 4 Q row loads and 12 Q table reads above the first FMA, and spills)
 #pragma unroll
     for (int q = 0; q < NQ; q++) {
@@ -273,7 +316,7 @@ __device__ __forceinline__ void gcw_ext_store(const float (&a)[4 * GcwDims<D>::Q
 // kernel was before the other existed.  VN: xout[v] = W (relu(pre[v]) + vn[g(v)]) + b, and the partial rows (gcw_vn_add_partials).
 // EXT (gcn_wide_jk.hip): the residual in front of the virtual node's add, so that the partial rows hold it (OGB's order), and the
 // stores of x_{s+1} and of the JK sum behind the range tracking, in front of the split.
-template <int D, bool VN, bool EXT = false>
+template <int D, bool VN, bool EXT = false, bool EL = false>
 __device__ __forceinline__ void gcw_layer_body(const float* __restrict__ x, float* __restrict__ xout,
                                                const int* __restrict__ row_ptr, const int* __restrict__ src,
                                                const uint8_t* __restrict__ ecode, const float* __restrict__ esc,
@@ -281,10 +324,13 @@ __device__ __forceinline__ void gcw_layer_body(const float* __restrict__ x, floa
                                                const uint8_t* __restrict__ wchunks, const float* __restrict__ tailp,
                                                int n_tot, int* __restrict__ range_flag,
                                                typename std::conditional<VN, GcwVnArgs, GcwNoVnArgs>::type vna,
-                                               typename std::conditional<EXT, GcwExtArgs, GcwNoExtArgs>::type ext = {}) {
+                                               typename std::conditional<EXT, GcwExtArgs, GcwNoExtArgs>::type ext = {},
+                                               typename std::conditional<EL, GcwElArgs, GcwNoElArgs>::type el = {}) {
     using M = GcwDims<D>;
+    static_assert(!(EL && EXT), "the JK / residual instances have no encoder");
     // three DISTINCT LDS objects: the DMA into one weight buffer does not alias the reads of the other, and the table stays
-    __shared__ __attribute__((aligned(16))) char s_tab[M::TAB_BYTES];
+    // (EL: the encoder's block where the table goes; ecode is then the layer's fragments in the encoder's blob)
+    __shared__ __attribute__((aligned(16))) char s_tab[EL ? GcwElLds<D>::BYTES : M::TAB_BYTES];
     __shared__ __attribute__((aligned(16))) char s_w0[M::CHUNK_BYTES];  // the even chunks
     __shared__ __attribute__((aligned(16))) char s_w1[M::CHUNK_BYTES];  // the odd chunks
     const int lane = threadIdx.x & 63;
@@ -294,13 +340,22 @@ __device__ __forceinline__ void gcw_layer_body(const float* __restrict__ x, floa
     const bool valid = node0 < n_tot;
     const long long node = valid ? node0 : (long long)n_tot - 1;
 
-    gw_issue_pieces<M::TAB_PIECES>(reinterpret_cast<const uint8_t*>(tab), s_tab, M::TAB_PIECES, M::TAB_LAST_LANES, wave, lane);
+    if constexpr (EL)
+        gcw_el_issue_block<D>(ecode, tab, s_tab, wave, lane);
+    else
+        gw_issue_pieces<M::TAB_PIECES>(reinterpret_cast<const uint8_t*>(tab), s_tab, M::TAB_PIECES, M::TAB_LAST_LANES, wave, lane);
     gw_issue_pieces<M::PIECES>(wchunks, s_w0, M::PIECES, 64, wave, lane);  // chunk 0
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 
     float a[4 * M::Q];
-    gcw_walk<D, true>(x, row_ptr, src, ecode, esc, out_deg, reinterpret_cast<const float*>(s_tab), node, valid, g, a);
+    float vmax = 0.0f;
+    if constexpr (EL) {
+        el.vmax = &vmax;
+        gcw_walk<D, true, true>(x, row_ptr, src, nullptr, esc, out_deg, reinterpret_cast<const float*>(s_tab), node, valid, g, a, el);
+    } else {
+        gcw_walk<D, true>(x, row_ptr, src, ecode, esc, out_deg, reinterpret_cast<const float*>(s_tab), node, valid, g, a);
+    }
     if constexpr (EXT) {
         if (ext.rin) gcw_ext_residual<D>(a, ext.rin, node, valid, g);  // (uniform over the launch)
     }
@@ -308,7 +363,6 @@ __device__ __forceinline__ void gcw_layer_body(const float* __restrict__ x, floa
         const int gi = valid ? vna.node_graph[node] : -1;
         gcw_vn_add_partials<D>(a, vna.vn, gi, j, g, (long long)blockIdx.x * GW_WAVES + wave, vna.part);
     }
-    float vmax = 0.0f;
 #pragma unroll
     for (int k = 0; k < 4 * M::Q; k += 2) vmax = __builtin_fmaxf(__builtin_fmaxf(vmax, __builtin_fabsf(a[k])), __builtin_fabsf(a[k + 1]));
     if constexpr (EXT) gcw_ext_store<D>(a, ext.rout, ext.jk_in, ext.jk_out, node, valid, g);

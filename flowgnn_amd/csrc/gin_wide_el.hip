@@ -21,8 +21,6 @@
 // This file defines the walk (gw_el_walk, declared in gin_wide_body.h) and is the one translation unit that instantiates the body
 // with EL = true; gin_wide.hip's, gin_wide_jk.hip's and gin_wide_f16.hip's kernels do not contain it.
 #include <cmath>
-#include <cstring>
-#include <vector>
 
 #include "../../include/flowgnn.h"
 #include "common.h"
@@ -30,6 +28,7 @@
 #include "gin_wide_body.h"
 #include "gin_wide_el.h"
 #include "wide_common.h"
+#include "wide_el_pack.h"  // GwElBlob and the host packer, which gcn_wide_el.hip shares (section 4.32)
 
 namespace fg {
 namespace {
@@ -110,16 +109,6 @@ __device__ __forceinline__ void gw_el_walk(const float* __restrict__ h, const in
 }
 
 template <int D>
-struct GwElBlob {
-    using M = GwDims<D>;
-    static constexpr size_t INV_OFF = (size_t)M::T2 * 1024;
-    static constexpr size_t W_OFF = INV_OFF + 16;
-    static constexpr size_t b_off(int F) { return W_OFF + (size_t)D * F * 4; }
-    static constexpr size_t layer_stride(int F) { return b_off(F) + (size_t)D * 4; }
-    static_assert((D * 4) % 16 == 0, "every part is read in 16-byte pieces");
-};
-
-template <int D>
 __global__ __launch_bounds__(GW_WAVES * 64) void gw_layer_el_kernel(const float* __restrict__ h, float* __restrict__ hout,
                                                                     const int* __restrict__ row_ptr, const int* __restrict__ src,
                                                                     const int* __restrict__ eid, const float* __restrict__ ef,
@@ -178,46 +167,6 @@ __global__ __launch_bounds__(256) void gw_aggregate_el_kernel(const float* __res
         reinterpret_cast<float4*>(a)[(size_t)v * C + c] =
             make_float4(__builtin_fmaf(x.x, self_s, m.x), __builtin_fmaf(x.y, self_s, m.y), __builtin_fmaf(x.z, self_s, m.z), __builtin_fmaf(x.w, self_s, m.w));
     }
-}
-
-inline void gw_el_put(uint8_t* frag, int lane, int e, float v) {
-    const _Float16 hv = (_Float16)v;
-    std::memcpy(frag + lane * 16 + e * 2, &hv, 2);
-}
-
-// one layer: w [D][F], b [D] (row-major, host) -> the T2 fragments (the slot table at the head of this file), 1 / scale, and the fp32 copies
-template <int D>
-void gw_el_pack_layer(int F, const float* w, const float* b, uint8_t* out) {
-    using B = GwElBlob<D>;
-    using M = GwDims<D>;
-    std::memset(out, 0, B::layer_stride(F));
-    // one power of two for the weights and the bias: they share the accumulator (max |.| times scale in [1, 2), far inside f16)
-    std::vector<float> wb(w, w + (size_t)D * F);
-    wb.insert(wb.end(), b, b + D);
-    const float scale = gw_pow2_scale(wb.data(), wb.size());
-    for (int t = 0; t < M::T2; t++)
-        for (int lane = 0; lane < 64; lane++) {
-            const int o = 16 * t + (lane & 15), gk = lane >> 4;
-            if (o >= D) continue;
-            for (int e = 0; e < 8; e++) {
-                const int kk = 16 * (e >> 2) + 4 * gk + (e & 3);
-                float val = 0.0f;
-                if (kk < 3 * F) {
-                    const float ws = w[(size_t)o * F + kk % F] * scale;
-                    const float hi = (float)(_Float16)ws;
-                    val = kk < 2 * F ? hi : ws - hi;
-                } else if (kk < 3 * F + 2) {
-                    const float bs = b[o] * scale;
-                    const float hi = (float)(_Float16)bs;
-                    val = kk == 3 * F ? hi : bs - hi;
-                }
-                gw_el_put(out + (size_t)t * 1024, lane, e, val);
-            }
-        }
-    const float inv = 1.0f / scale;
-    std::memcpy(out + B::INV_OFF, &inv, 4);
-    std::memcpy(out + B::W_OFF, w, (size_t)D * F * 4);
-    std::memcpy(out + B::b_off(F), b, (size_t)D * 4);
 }
 
 constexpr int GWE_D = FLOWGNN_EMB_DIM_OGB;  // the launchers' one width: the public constant's

@@ -262,10 +262,10 @@ class Engine:
         if set2set:
             from .weights import load_set2set
             self.set_set2set_pooling(load_set2set(directory, model=self.model, emb_dim=self.emb_dim), steps=set2set_steps)
-        if edge_linear:  # (GIN at width 300: gin_ep1_edgelin_dim300.bin, OGB's linear edge encoder of ogbg-ppa, through set_edge_linear)
+        if edge_linear:  # (GIN, GCN at width 300: gin_ep1_edgelin_dim300.bin / gcn_ep1_edgelin_dim300.bin, OGB's linear edge encoder of ogbg-ppa)
             from .weights import load_edge_linear
-            el = load_edge_linear(directory, emb_dim=self.emb_dim, num_layers=self.num_layers)
-            self.set_edge_linear(el["w"], el["b"])
+            el = load_edge_linear(directory, emb_dim=self.emb_dim, num_layers=self.num_layers, model=self.model)
+            self.set_model_edge_linear(el["w"], el["b"])
 
     # ---- batch
     def set_job_totals(self, job_nodes: int = -1, job_edges: int = -1):
@@ -789,18 +789,24 @@ class Engine:
         self.lib.flowgnn_jk_residual(self._h, C.byref(jk), C.byref(res))
         return JK_NAMES[jk.value], bool(res.value)
 
-    def set_edge_linear(self, w=None, b=None):
+    def set_edge_linear(self, w=None, b=None, _call="flowgnn_set_edge_linear"):
         """GIN at width 300: OGB's linear edge encoder, the layer of ogbg-ppa (flowgnn.h: flowgnn_set_edge_linear).  w [L][300][F],
         b [L][300] with L = num_layers and F edge features per edge, 1 .. 10 (weights.load_edge_linear,
         export.edge_linear_from_ogb_state_dict); (None, None) turns it off.  Set behind the depth; the engine's, across batches and
         weight sets.  While it is on every batch needs set_edge_features (or forward(..., edge_features=...))."""
+        fn = getattr(self.lib, _call)
         if w is None and b is None:
-            self._check(self.lib.flowgnn_set_edge_linear(self._h, 300, 0, None, None), "flowgnn_set_edge_linear")
+            self._check(fn(self._h, 300, 0, None, None), _call)
             return
         w, b = _f32(w), _f32(b)
         if w.ndim != 3 or b.shape != w.shape[:2] or w.shape[0] != self.num_layers:
             raise ValueError(f"edge encoder: w is {w.shape} and b is {b.shape}; wanted [L][D][F] and [L][D] with L = {self.num_layers}")
-        self._check(self.lib.flowgnn_set_edge_linear(self._h, w.shape[1], w.shape[2], _pf(w), _pf(b)), "flowgnn_set_edge_linear")
+        self._check(fn(self._h, w.shape[1], w.shape[2], _pf(w), _pf(b)), _call)
+
+    def set_model_edge_linear(self, w=None, b=None):
+        """The model form of set_edge_linear (flowgnn.h: flowgnn_set_model_edge_linear): the same on a GIN engine, and on a GCN engine
+        at width 300 ppa's GCNConv (gcn and gcn-virtual), which set_edge_linear refuses."""
+        self.set_edge_linear(w, b, _call="flowgnn_set_model_edge_linear")
 
     @property
     def edge_linear(self) -> int:

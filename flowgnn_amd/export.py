@@ -212,7 +212,7 @@ EDGE_LIN_KEY = "gnn_node.convs.0.edge_encoder.weight"  # what tells an ogbg-ppa 
 
 
 def edge_linear_from_ogb_state_dict(sd: Mapping, num_layers: int = 5) -> Dict[str, np.ndarray]:
-    """The edge encoders of an ogbg-ppa `GNN(gnn_type='gin' | 'gin-virtual')` state_dict, `gnn_node.convs.l.edge_encoder.weight` [D][F]
+    """The edge encoders of an ogbg-ppa `GNN(gnn_type='gin' | 'gin-virtual' | 'gcn' | 'gcn-virtual')` state_dict, `gnn_node.convs.l.edge_encoder.weight` [D][F]
     and `.bias` [D] per layer, as the two tensors Engine.set_edge_linear / flowgnn_set_edge_linear take: w [L][D][F], b [L][D]."""
     w = np.stack([_get(sd, f"gnn_node.convs.{l}.edge_encoder.weight") for l in range(num_layers)])
     b = np.stack([_get(sd, f"gnn_node.convs.{l}.edge_encoder.bias") for l in range(num_layers)])
@@ -426,9 +426,9 @@ def export_weights(model: str, sd: Mapping, directory: str, multi_task: bool = F
     tensor, the eps file and the virtual node's file; the file names stay the same.  A depth other than 5 is for an engine with
     flowgnn_set_num_layers(300, depth) / Engine.set_num_layers(depth) / `host GIN|GCN --emb-dim 300 --num-layer depth`; a depth outside
     2 .. 8, and a depth other than 5 at width 100, are refused before any file is written.
-    An ogbg-ppa state_dict (GIN, 300 wide) is recognised by `gnn_node.convs.0.edge_encoder.weight`: its per-layer Linear(F, D) edge
-    encoders go into gin_ep1_edgelin_dim300.bin (w [L][D][F], then b [L][D]) for Engine.load_weights_dir(dir, edge_linear=True) to apply
-    (flowgnn_set_edge_linear); its node_encoder = Embedding(1, D) becomes the atom table's row of feature 0, value 0, with every other
+    An ogbg-ppa state_dict (GIN or GCN with emb_dim=300; 300 wide) is recognised by `gnn_node.convs.0.edge_encoder.weight`: its per-layer Linear(F, D) edge
+    encoders go into gin_ep1_edgelin_dim300.bin / gcn_ep1_edgelin_dim300.bin (w [L][D][F], then b [L][D]) for
+    Engine.load_weights_dir(dir, edge_linear=True) to apply (flowgnn_set_edge_linear / flowgnn_set_model_edge_linear); its node_encoder = Embedding(1, D) becomes the atom table's row of feature 0, value 0, with every other
     row zero, so ppa's all-zero x reproduces it; the bond tables are written as zeros, which the engine does not read then."""
     m = model.upper()
     if set2set and m not in ("GIN", "GCN"):
@@ -454,12 +454,13 @@ def export_weights(model: str, sd: Mapping, directory: str, multi_task: bool = F
     depth = num_layers_of_ogb_state_dict(sd) if m in ("GIN", "GIN-VN", "GCN") else 5
     edge_lin = None
     if EDGE_LIN_KEY in sd:  # an ogbg-ppa model (before any file is written): its edge encoders, then the molecular keys for the rest
-        if m != "GIN":
-            raise ExportError(f"the state_dict has '{EDGE_LIN_KEY}': it is an ogbg-ppa model, which the engine runs as GIN at width 300 "
-                              f"(flowgnn_set_edge_linear), not as {model}")
+        if m not in ("GIN", "GCN"):
+            raise ExportError(f"the state_dict has '{EDGE_LIN_KEY}': it is an ogbg-ppa model, which the engine runs as GIN or GCN at width 300 "
+                              f"(flowgnn_set_edge_linear / flowgnn_set_model_edge_linear), not as {model}")
         edge_lin = edge_linear_from_ogb_state_dict(sd, num_layers=depth)
-        if edge_lin["w"].shape[1] != 300:
-            raise ExportError(f"the ogbg-ppa state_dict is {edge_lin['w'].shape[1]} wide: only the 300-wide GIN has the linear edge encoder")
+        if edge_lin["w"].shape[1] != 300 or (m == "GCN" and int(emb_dim) != 300):
+            raise ExportError(f"the ogbg-ppa state_dict is {edge_lin['w'].shape[1]} wide (emb_dim={emb_dim}): only the 300-wide GIN and GCN have the "
+                              f"linear edge encoder")
         sd = _ppa_as_molecular(sd, depth)
     if m in ("GIN", "GIN-VN", "GCN"):  # (before any file is written; the width as the two exporters below read it)
         width = int(emb_dim) if m == "GCN" else int(_get(sd, "gnn_node.atom_encoder.atom_embedding_list.0.weight").shape[-1])
@@ -498,6 +499,8 @@ def export_weights(model: str, sd: Mapping, directory: str, multi_task: bool = F
             _weights.save_attention_pooling(gate, directory, model="GCN")
         if set2set:
             _weights.save_set2set(s2s, directory, model="GCN")
+        if edge_lin is not None:  # gcn_ep1_edgelin_dim300.bin, for Engine.load_weights_dir(dir, edge_linear=True)
+            _weights.save_edge_linear(edge_lin, directory, model="GCN")
     else:
         raise ExportError(f"no OGB example model corresponds to the reference's {model} (its PNA/DGN/GAT checkpoints are already "
                           f"flat files: use flowgnn_amd.weights.save_*_weights)")

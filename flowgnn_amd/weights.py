@@ -346,34 +346,39 @@ def synth_attention_pooling(seed: int = 11, emb_dim: int = 300) -> Dict[str, np.
     return OrderedDict([("w1", w1), ("b1", b1), ("w2", w2)])
 
 
-# OGB's linear edge encoder for GIN at width 300, the layer of ogbg-ppa (flowgnn.h: flowgnn_set_edge_linear): one file beside the model's
-# set, w [L][D][F] then b [L][D].  F, the features per edge, is no part of the name: it is recovered from the file's size and L
+# OGB's linear edge encoder for GIN and GCN at width 300, the layer of ogbg-ppa (flowgnn.h: flowgnn_set_edge_linear,
+# flowgnn_set_model_edge_linear): one file beside the model's set, gin_... or gcn_..., w [L][D][F] then b [L][D].  F, the features per edge, is no part of the name: it is recovered from the file's size and L
 EDGE_LINEAR_MAX_DIM = 10  # flowgnn.h: FLOWGNN_MAX_EDGE_DIM
 
 
-def edge_linear_file(emb_dim: int = 300) -> str:
-    """gin_ep1_edgelin_dim<emb_dim>.bin"""
+_EDGE_LINEAR_PREFIX = {"GIN": "gin", "GCN": "gcn"}
+
+
+def edge_linear_file(emb_dim: int = 300, model: str = "GIN") -> str:
+    """gin_ep1_edgelin_dim<emb_dim>.bin; for the model "GCN": gcn_ep1_edgelin_dim<emb_dim>.bin"""
+    if model.upper() not in _EDGE_LINEAR_PREFIX:
+        raise ValueError(f"edge encoder: {model} has no such layer (GIN and GCN at width 300)")
     if int(emb_dim) != 300:
-        raise ValueError(f"edge encoder: emb_dim {emb_dim} is not 300 (only the 300-wide GIN has this layer)")
-    return f"gin_ep1_edgelin_dim{int(emb_dim)}.bin"
+        raise ValueError(f"edge encoder: emb_dim {emb_dim} is not 300 (only the 300-wide GIN and GCN have this layer)")
+    return f"{_EDGE_LINEAR_PREFIX[model.upper()]}_ep1_edgelin_dim{int(emb_dim)}.bin"
 
 
-def save_edge_linear(el, directory: str) -> None:
-    """Write gin_ep1_edgelin_dim300.bin from {"w": [L][D][F], "b": [L][D]}: w, then b, little-endian float32.  Nothing applies the file
+def save_edge_linear(el, directory: str, model: str = "GIN") -> None:
+    """Write gin_ep1_edgelin_dim300.bin (model="GCN": gcn_ep1_edgelin_dim300.bin) from {"w": [L][D][F], "b": [L][D]}: w, then b, little-endian float32.  Nothing applies the file
     unless asked to: Engine.load_weights_dir(dir, edge_linear=True)."""
     w, b = np.asarray(el["w"], dtype=np.float32), np.asarray(el["b"], dtype=np.float32)
     if w.ndim != 3 or b.shape != w.shape[:2] or not 1 <= w.shape[2] <= EDGE_LINEAR_MAX_DIM:
         raise ValueError(f"edge encoder: w is {w.shape} and b is {b.shape}; wanted [L][D][F] and [L][D], F in 1 .. {EDGE_LINEAR_MAX_DIM}")
-    name = edge_linear_file(w.shape[1])  # (refused before anything is created)
+    name = edge_linear_file(w.shape[1], model)  # (refused before anything is created)
     _depth(w.shape[0], w.shape[1])
     os.makedirs(directory, exist_ok=True)
     np.concatenate([w.ravel(), b.ravel()]).astype("<f4").tofile(os.path.join(directory, name))
 
 
-def load_edge_linear(directory: str, emb_dim: int = 300, num_layers: int = 5) -> Dict[str, np.ndarray]:
-    """The two tensors of a directory's edge-encoder file (for Engine.set_edge_linear) at the depth num_layers; a file whose size
-    fits no F in 1 .. 10 at that depth is refused."""
-    path = os.path.join(directory, edge_linear_file(emb_dim))
+def load_edge_linear(directory: str, emb_dim: int = 300, num_layers: int = 5, model: str = "GIN") -> Dict[str, np.ndarray]:
+    """The two tensors of a directory's edge-encoder file (for Engine.set_edge_linear / set_model_edge_linear) at the depth
+    num_layers; a file whose size fits no F in 1 .. 10 at that depth is refused."""
+    path = os.path.join(directory, edge_linear_file(emb_dim, model))
     d, n = int(emb_dim), _depth(num_layers, emb_dim)
     size = os.path.getsize(path)
     f = size // (4 * n * d) - 1

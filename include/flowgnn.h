@@ -1045,8 +1045,8 @@ int flowgnn_num_layers(const flowgnn_engine* e);                              /*
  * is off every path, launch and bit is what it was; a batch that was set without edge_attr has to be set again then.
  * FLOWGNN_ERR_ARG: a null handle; one of w, b NULL and not the other; edge_dim outside 1 .. 10; emb_dim other than the engine's width;
  * a non-finite weight; ef NULL with edges in the batch; a device pointer that fails the check.
- * FLOWGNN_ERR_UNSUPPORTED: any engine but FLOWGNN_MODEL_GIN at width 300 (GCN's ppa layer, width 100 and groups do not exist); and,
- * while it is on, flowgnn_set_emb_dim to 100.
+ * FLOWGNN_ERR_UNSUPPORTED: any engine but FLOWGNN_MODEL_GIN at width 300 (GCN's ppa layer goes through flowgnn_set_model_edge_linear,
+ * below; width 100 and groups do not exist); and, while it is on, flowgnn_set_emb_dim to 100.
  * FLOWGNN_ERR_STATE, from whichever call comes second: the encoder beside FLOWGNN_NUMERIC_F16 and beside JK sum or the residual
  * (flowgnn_set_numeric_mode_dim, flowgnn_set_jk_residual) -- those instances of the layer have no encoder; flowgnn_set_edge_features
  * without a batch.
@@ -1056,6 +1056,20 @@ int flowgnn_num_layers(const flowgnn_engine* e);                              /*
 int flowgnn_set_edge_linear(flowgnn_engine* e, int emb_dim, int edge_dim, const float* w /* [L][300][edge_dim] */, const float* b /* [L][300] */);
 int flowgnn_edge_linear(const flowgnn_engine* e);
 int flowgnn_set_edge_features(flowgnn_engine* e, int edge_dim, const float* ef /* [E_tot][edge_dim] */, int on_device);
+
+/*
+ * The model form of the call, like flowgnn_set_model_emb_dim and flowgnn_set_model_jk_residual: on a FLOWGNN_MODEL_GIN engine it is
+ * flowgnn_set_edge_linear; on a FLOWGNN_MODEL_GCN engine at width 300 it turns on ppa's GCNConv,
+ *   m[v] = sum over (u, v) of dinv[u] dinv[v] relu(x_u + W_e e_uv + b_e),   pre = BN(m + relu(x + root) / (deg + 1)),
+ * OGB mol's GCNConv with edge_encoder = Linear(F, 300) in place of the bond encoder: gcn and gcn-virtual
+ * (flowgnn_set_gcn_virtual_node_dim), depths 2 .. 8, every pooling and readout, NUM_TASK, graph and node embeddings, node logits.
+ * Every stage runs gcn_wide_el.hip's kernels, the encoder on the matrix pipe inside the in-edge walk as for GIN.  The tensors, the
+ * features (flowgnn_set_edge_features), flowgnn_edge_linear, the edge_attr == NULL rule and the status codes are those above, with
+ * GCN's own calls in the refusals: FLOWGNN_ERR_STATE beside flowgnn_set_model_numeric_mode_dim's FLOWGNN_NUMERIC_F16 and beside
+ * flowgnn_set_model_jk_residual's JK sum or residual, from whichever call comes second; FLOWGNN_ERR_UNSUPPORTED at width 100 and on
+ * any other model.  flowgnn_set_edge_linear itself keeps refusing a GCN engine, as the other GIN-only forms do.
+ */
+int flowgnn_set_model_edge_linear(flowgnn_engine* e, int emb_dim, int edge_dim, const float* w /* [L][300][edge_dim] */, const float* b /* [L][300] */);
 
 /*
  * Laplacian eigenvectors: DGN's node_eigen from the graphs alone (the reference reads it from DGN/eig/g%d.txt and does not say where it
