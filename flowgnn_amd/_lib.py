@@ -97,6 +97,14 @@ def _declare(lib):
     lib.flowgnn_num_layers.argtypes = [eng]
     lib.flowgnn_set_edge_linear.argtypes = [eng, C.c_int, C.c_int, p_float, p_float]
     lib.flowgnn_set_model_edge_linear.argtypes = [eng, C.c_int, C.c_int, p_float, p_float]
+    lib.flowgnn_set_vocab_head.argtypes = [eng, C.c_int, C.c_int, C.c_int, p_float, p_float]
+    lib.flowgnn_vocab_head.argtypes = [eng]
+    lib.flowgnn_get_tokens.argtypes = [eng, p_int, p_float]
+    lib.flowgnn_tokens_device.argtypes = [eng, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    lib.flowgnn_tokens_positions.argtypes = [eng]
+    lib.flowgnn_set_ast_encoder.argtypes = [eng, C.c_int, C.c_int, C.c_int, C.c_int, p_float, p_float, p_float]
+    lib.flowgnn_ast_encoder.argtypes = [eng]
+    lib.flowgnn_set_ast_nodes.argtypes = [eng, p_int, p_int, C.c_int]
     lib.flowgnn_edge_linear.argtypes = [eng]
     lib.flowgnn_set_edge_features.argtypes = [eng, C.c_int, p_float, C.c_int]
     lib.flowgnn_set_num_tasks.argtypes = [eng, C.c_int]
@@ -207,6 +215,8 @@ def _declare(lib):
                  "flowgnn_set_jk_residual", "flowgnn_jk_residual", "flowgnn_group_set_jk_residual", "flowgnn_set_model_jk_residual", "flowgnn_group_set_model_jk_residual",
                  "flowgnn_set_num_layers", "flowgnn_num_layers", "flowgnn_group_set_num_layers",
                  "flowgnn_set_edge_linear", "flowgnn_set_model_edge_linear", "flowgnn_edge_linear", "flowgnn_set_edge_features",
+                 "flowgnn_set_vocab_head", "flowgnn_vocab_head", "flowgnn_get_tokens", "flowgnn_tokens_device", "flowgnn_tokens_positions",
+                 "flowgnn_set_ast_encoder", "flowgnn_ast_encoder", "flowgnn_set_ast_nodes",
                  "flowgnn_laplacian_eigen_max_nodes", "flowgnn_laplacian_eigen", "flowgnn_laplacian_eigen_device",
                  "GIN_compute_graphs_mt", "GCN_compute_graphs_mt", "GIN_compute_graphs", "GCN_compute_graphs", "PNA_compute_graphs", "DGN_compute_graphs", "GAT_compute_graphs"):
         getattr(lib, name).restype = C.c_int

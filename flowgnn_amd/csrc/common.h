@@ -191,6 +191,13 @@ struct DeviceBatch {
     const void* edge_lin;     // flowgnn_set_edge_linear / _model_edge_linear (GIN, GCN at width 300): the encoder's tensors (gin_wide_el.h), or null: off, every
     int edge_lin_dim;         // launch is the one it always was; its edge_dim; and the batch's float edge features [E][edge_lin_dim] in the caller's
     const float* edge_feat;   // edge order (flowgnn_set_edge_features; flowgnn_run refuses the run while the encoder is on and they are missing)
+    const void* vocab;        // flowgnn_set_vocab_head (GIN at width 300): the head's tensors in the device form of wide_vocab.h, or null: off, every
+    int vocab_p, vocab_v;     // launch is the one it always was; its positions P and vocabulary V; where a forward that finds it set leaves
+    int* tokens;              // argmax_v [G][P] and
+    float* scores;            // the maxima [G][P] (the engine's buffers)
+    const void* ast_enc;      // flowgnn_set_ast_encoder (GIN at width 300): the three tables (wide_vocab.h), or null: off, the atom encoder runs;
+    int ast_types, ast_attrs, ast_max_depth;  // their sizes; and the batch's x [N][2] and depth [N] (flowgnn_set_ast_nodes; flowgnn_run
+    const int *ast_x, *ast_depth;             // refuses the run while the encoder is on and they are missing)
     int final_h;              // which h[] holds the last stage's output (set by forward)
     const float* tap;         // optional debug tap returned by flowgnn_get_h instead of h[final_h]
     int tap_dim;

@@ -421,6 +421,7 @@ int flowgnn_destroy(flowgnn_engine* e) {
     e->s2s.release();
     e->edge_lin.release();
     e->edge_feat.release();
+    for (fg::GrowBuf* b : {&e->vocab, &e->tokens, &e->ast_enc, &e->ast_nodes}) b->release();
     if (e->eig_done) (void)hipEventDestroy(e->eig_done);
     if (e->d_err) (void)hipFree(e->d_err);
     delete e->model;
@@ -735,6 +736,14 @@ static int set_batch_state(flowgnn_engine* e, int num_graphs, const int* nums_of
     db.edge_lin_dim = e->edge_lin_dim;
     e->edge_feat_dim = 0;  // flowgnn_set_edge_features: the features were the previous batch's
     db.edge_feat = nullptr;
+    db.vocab = e->vocab_p ? e->vocab.p : nullptr;
+    db.vocab_p = e->vocab_p;
+    db.vocab_v = e->vocab_v;
+    db.ast_enc = e->ast_on ? e->ast_enc.p : nullptr;
+    db.ast_types = e->ast_types; db.ast_attrs = e->ast_attrs; db.ast_max_depth = e->ast_max_depth;
+    e->ast_nodes_set = false;  // flowgnn_set_ast_nodes: the nodes were the previous batch's
+    db.ast_x = db.ast_depth = nullptr;
+    e->tokens_p = 0;
     db.final_h = 0;
     db.tap = nullptr;
     db.tap_dim = 0;
@@ -749,10 +758,25 @@ static int set_batch_state(flowgnn_engine* e, int num_graphs, const int* nums_of
     for (const Output& o : kOutputs)
         if (int rc = place(e, o)) return rc;
     e->db.attn_mask = e->attn_mask;
-    return FLOWGNN_OK;
+    return place_tokens(e);
 }
 
 }  // extern "C"
+
+// flowgnn_set_vocab_head's outputs of the resident batch: tokens [G][P] | scores [G][P] in one buffer of the engine's, behind a change of
+// the batch or of the head (both leave the stream idle and no recorded launch sequence).  Either change moves or frees what the last run
+// wrote, so that run's tokens are gone with it: flowgnn_get_tokens / flowgnn_tokens_device answer FLOWGNN_ERR_STATE until the next run
+int place_tokens(flowgnn_engine* e) {
+    e->tokens_p = 0;
+    e->db.tokens = nullptr;
+    e->db.scores = nullptr;
+    if (!e->vocab_p || !e->batch_ready) return FLOWGNN_OK;
+    const size_t items = (size_t)e->G * (size_t)e->vocab_p;
+    EHIP_TRY(e, e->tokens.reserve(items * (sizeof(int) + sizeof(float)), false));
+    e->db.tokens = (int*)e->tokens.p;
+    e->db.scores = (float*)e->tokens.p + items;
+    return FLOWGNN_OK;
+}
 
 // fill of the model's graph tiles when `num_graphs` graphs are packed greedily in order (the packing flowgnn_set_batch does), without
 // the last tile; 1 for a one-tile batch, 0 when a graph exceeds the tile limits (no resident path), -1 when the model has no tiles
@@ -904,6 +928,43 @@ int flowgnn_set_edge_features(flowgnn_engine* e, int edge_dim, const float* ef, 
     return FLOWGNN_OK;
 }
 
+// The AST nodes of the resident batch, for OGB's ASTNodeEncoder (flowgnn_set_ast_encoder): attached as
+// flowgnn_set_edge_features attaches the edge features -- the engine's own copy, made on the launch stream
+int flowgnn_set_ast_nodes(flowgnn_engine* e, const int* x, const int* depth, int on_device) {
+    if (!e) return FLOWGNN_ERR_ARG;
+    static const char* const api = "flowgnn_set_ast_nodes";
+    if (!e->batch_ready) {
+        e->err = std::string(api) + ": no batch is set, and the nodes are a batch's (flowgnn_set_batch first)";
+        return FLOWGNN_ERR_STATE;
+    }
+    const size_t N = (size_t)e->N, bytes = sizeof(int) * N * 3;
+    if (N && (!x || !depth)) {
+        e->err = std::string(api) + ": x or depth is NULL and the batch has nodes";
+        return FLOWGNN_ERR_ARG;
+    }
+    ENGINE_TRY(e, use_device(e));
+    if (on_device) {
+        ENGINE_TRY(e, check_device_array(e, x, sizeof(int) * N * 2, "x", api));
+        ENGINE_TRY(e, check_device_array(e, depth, sizeof(int) * N, "depth", api));
+    }
+    e->drop_graph();  // a recorded launch sequence reads the buffer as it was
+    if (!e->ast_nodes.holds(bytes)) {
+        if (e->stream) EHIP_TRY(e, hipStreamSynchronize(e->stream));  // (a run in flight may still read the old one)
+        EHIP_TRY(e, e->ast_nodes.reserve(bytes, true));
+    }
+    int* const d_x = (int*)e->ast_nodes.p;
+    if (N) {
+        const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+        EHIP_TRY(e, hipMemcpyAsync(d_x, x, sizeof(int) * N * 2, kind, e->stream));
+        EHIP_TRY(e, hipMemcpyAsync(d_x + 2 * N, depth, sizeof(int) * N, kind, e->stream));
+        if (!on_device) EHIP_TRY(e, hipStreamSynchronize(e->stream));  // the caller's host arrays are its own again when the call returns
+    }
+    e->ast_nodes_set = true;
+    e->db.ast_x = d_x;
+    e->db.ast_depth = d_x + 2 * N;
+    return FLOWGNN_OK;
+}
+
 // ---- flowgnn_laplacian_eigen*: DGN's node_eigen from the graphs alone (kernels: eigen.hip).  Nothing of the resident batch, the
 // recorded launch sequence or the output slots is touched: the engine lends its device, its launch stream and scratch of its own.
 // The plan both functions share: counts -> offsets and the three size-class lists, one upload, one launch per non-empty class.
@@ -1017,7 +1078,12 @@ int flowgnn_run(flowgnn_engine* e) {
                                                 "flowgnn_set_edge_features after flowgnn_set_batch");
         return FLOWGNN_ERR_STATE;
     }
+    if (e->ast_on && !e->ast_nodes_set) {  // OGB's ASTNodeEncoder reads the batch's x and depth
+        e->err = "flowgnn_run: the AST node encoder is on (flowgnn_set_ast_encoder) and the batch has no AST nodes: flowgnn_set_ast_nodes after flowgnn_set_batch";
+        return FLOWGNN_ERR_STATE;
+    }
     ENGINE_TRY(e, use_device(e));
+    e->tokens_p = e->db.vocab ? e->db.vocab_p : 0;
     for (const Output& o : kOutputs) (e->*o.slot).last = e->db.*o.field;
     e->attn_mask_last = e->db.attn_mask;
     if (e->G == 0) { e->ran = true; return FLOWGNN_OK; }
@@ -1123,6 +1189,32 @@ int flowgnn_get_results(flowgnn_engine* e, float* out_host) {
     int rc = flowgnn_sync(e);
     if (rc) return rc;
     if (e->G > 0) return d2h_sync(e, out_host, e->db.out, sizeof(float) * (size_t)e->G * e->num_tasks, "copy results");
+    return FLOWGNN_OK;
+}
+
+// flowgnn_set_vocab_head's outputs of the last run
+static int no_tokens(flowgnn_engine* e, const char* api) {
+    e->err = std::string(api) + ": the last flowgnn_run did not have the vocabulary head on, or the batch or the head has changed since (flowgnn_set_vocab_head)";
+    return FLOWGNN_ERR_STATE;
+}
+
+int flowgnn_get_tokens(flowgnn_engine* e, int* tokens_host, float* scores_host) {
+    if (!e || (!tokens_host && e->G > 0)) return FLOWGNN_ERR_ARG;
+    if (!e->ran || !e->tokens_p) return no_tokens(e, "flowgnn_get_tokens");
+    if (int rc = flowgnn_sync(e)) return rc;
+    if (e->G == 0) return FLOWGNN_OK;
+    const size_t items = (size_t)e->G * (size_t)e->tokens_p;
+    if (int rc = d2h_sync(e, tokens_host, e->db.tokens, sizeof(int) * items, "copy tokens")) return rc;
+    return scores_host ? d2h_sync(e, scores_host, e->db.scores, sizeof(float) * items, "copy scores") : FLOWGNN_OK;
+}
+
+int flowgnn_tokens_positions(const flowgnn_engine* e) { return e ? (e->ran ? e->tokens_p : 0) : -1; }
+
+int flowgnn_tokens_device(flowgnn_engine* e, void** d_tokens, void** d_scores) {
+    if (!e) return FLOWGNN_ERR_ARG;
+    if (!e->ran || !e->tokens_p) return no_tokens(e, "flowgnn_tokens_device");
+    if (d_tokens) *d_tokens = e->db.tokens;
+    if (d_scores) *d_scores = e->db.scores;
     return FLOWGNN_OK;
 }
 

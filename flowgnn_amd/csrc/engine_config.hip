@@ -1,5 +1,5 @@
 // engine_config.hip -- the calls that configure an engine (include/flowgnn.h): NUM_TASK, width, numeric mode, pooling, eps, the two
-// virtual nodes, the attention and set2set readouts, JK / residual, the depth, and their getters.  Host code only; what it shares with engine.hip
+// virtual nodes, the attention and set2set readouts, JK / residual, the depth, the edge encoder, code2's head and node encoder, and their getters.  Host code only; what it shares with engine.hip
 // (begin_change, use_device, kOutputs) is declared in engine_internal.h.
 //
 // Every setter is: its argument checks, its state checks, begin_change (or use_device + drop_graph where no device memory changes
@@ -12,6 +12,7 @@
 #include "gin_wide_el.h"
 #include "wide_attn.h"
 #include "wide_s2s.h"
+#include "wide_vocab.h"
 #include <cmath>
 
 using namespace fg;
@@ -153,6 +154,9 @@ static int set_width(flowgnn_engine* e, const char* fn, int emb_dim) {
     if (e->num_layers != FLOWGNN_NUM_LAYERS_DEFAULT)  // (not 5 means width 300: the call asks for 100, whose kernels are five layers deep)
         return refuse(e, FLOWGNN_ERR_UNSUPPORTED, who + "the depth is " + std::to_string(e->num_layers) + " (flowgnn_set_num_layers), and the " + std::to_string(emb_dim) +
                                                   "-wide kernels are five layers deep: flowgnn_set_num_layers(e, " + std::to_string(e->emb_dim) + ", 5) first, then change the width");
+    if (e->vocab_p || e->ast_on)  // (on means width 300, as for the edge encoder)
+        return refuse(e, FLOWGNN_ERR_UNSUPPORTED, who + (e->vocab_p ? "the vocabulary head is on (flowgnn_set_vocab_head)" : "the AST node encoder is on (flowgnn_set_ast_encoder)") +
+                                                  ", and only the 300-wide GIN has it: turn it off, then change the width");
     ENGINE_TRY(e, begin_change(e));
     Model* m = gcn ? (emb_dim == FLOWGNN_EMB_DIM_REFERENCE ? make_gcn_model() : make_gcn_wide_model(emb_dim))
                    : (emb_dim == FLOWGNN_EMB_DIM_REFERENCE ? make_gin_model(false) : make_gin_wide_model(emb_dim));
@@ -538,6 +542,9 @@ int flowgnn_set_set2set_pooling(flowgnn_engine* e, int emb_dim, int steps, int n
         if (e->emb_on)
             return refuse(e, FLOWGNN_ERR_UNSUPPORTED, who + "graph embeddings are on (flowgnn_set_embeddings), and the vector this readout's head reads is " + std::to_string(2 * emb_dim) +
                      " wide where every embeddings buffer is " + std::to_string(emb_dim) + " wide");
+        if (e->vocab_p)
+            return refuse(e, FLOWGNN_ERR_STATE, who + "the vocabulary head is on (flowgnn_set_vocab_head), and it reads a pooled row " + std::to_string(emb_dim) + " wide where this readout's is " +
+                                                      std::to_string(2 * emb_dim) + " wide: turn one of the two off");
     }
     ENGINE_TRY(e, begin_change(e));
     if (on)
@@ -667,6 +674,94 @@ int flowgnn_set_model_edge_linear(flowgnn_engine* e, int emb_dim, int edge_dim, 
 }
 
 int flowgnn_edge_linear(const flowgnn_engine* e) { return e ? e->edge_lin_dim : -1; }
+}  // extern "C"
+
+// ------------------------------------------------------------------ ogbg-code2: the vocabulary head and the AST node encoder
+// GIN at width 300.  Each is a tensor set in the device form of wide_vocab.h, one device buffer owned by the
+// engine; db.vocab / db.ast_enc and their sizes carry them to GwReadout::run and GinWideModel::forward.  All NULL: off, at any width
+// and for any model.
+// what both calls refuse alike once their tensors are known to be sound; blob_bytes: the size of the device form (0: none at this width)
+static int code2_state(flowgnn_engine* e, const std::string& who, const char* name, int emb_dim, size_t blob_bytes) {
+    if (e->model_id != FLOWGNN_MODEL_GIN)
+        return refuse(e, FLOWGNN_ERR_UNSUPPORTED, who + "the " + name + " exists for FLOWGNN_MODEL_GIN only (OGB's gin and gin-virtual of ogbg-code2; GCN's form is not built)");
+    if (int rc = width_matches(e, who, true, emb_dim, e->emb_dim, "flowgnn_set_emb_dim")) return rc;
+    if (blob_bytes == 0)
+        return refuse(e, FLOWGNN_ERR_UNSUPPORTED, who + "only the 300-wide GIN has the " + name + ": flowgnn_set_emb_dim(e, 300) first");
+    return FLOWGNN_OK;
+}
+
+extern "C" {
+
+int flowgnn_set_vocab_head(flowgnn_engine* e, int emb_dim, int positions, int vocab, const float* w, const float* b) {
+    if (!e) return FLOWGNN_ERR_ARG;
+    const std::string who = "flowgnn_set_vocab_head: ";
+    if (int rc = width_argument(e, who, emb_dim)) return rc;
+    const bool given = w || b;
+    if (given && (positions < 1 || positions > FLOWGNN_MAX_VOCAB_POSITIONS))
+        return refuse(e, FLOWGNN_ERR_ARG, who + "positions is " + std::to_string(positions) + "; the head has 1 .. " + std::to_string(FLOWGNN_MAX_VOCAB_POSITIONS) + " positions (ogbg-code2: 5)");
+    if (given && (vocab < 1 || vocab > FLOWGNN_MAX_VOCAB))
+        return refuse(e, FLOWGNN_ERR_ARG, who + "vocab is " + std::to_string(vocab) + "; the vocabulary has 1 .. " + std::to_string(FLOWGNN_MAX_VOCAB) + " entries (ogbg-code2: 5002)");
+    const size_t D = (size_t)emb_dim, PV = given ? (size_t)positions * (size_t)vocab : 0;
+    const TensorArg t[2] = {{"w", w, PV * D}, {"b", b, PV}};
+    bool on;
+    if (int rc = tensor_set_on(e, who, t, &on)) return rc;
+    if (on) {
+        if (int rc = tensor_set_finite(e, who, t)) return rc;
+        if (int rc = code2_state(e, who, "vocabulary head", emb_dim, fg::vocab_head_blob_bytes(emb_dim, positions, vocab))) return rc;
+        if (e->s2s_steps)
+            return refuse(e, FLOWGNN_ERR_STATE, who + "the set2set pooling is on (flowgnn_set_set2set_pooling), and its pooled vector is " + std::to_string(2 * emb_dim) + " wide where the head reads " +
+                                                      std::to_string(emb_dim) + ": turn one of the two off");
+    }
+    ENGINE_TRY(e, begin_change(e));
+    if (on)
+        if (int rc = upload_packed(e, e->vocab, fg::vocab_head_blob_bytes(emb_dim, positions, vocab),
+                                   [&](float* dst) { fg::vocab_head_blob_pack(emb_dim, positions, vocab, w, b, dst); }))
+            return rc;
+    e->vocab_p = on ? positions : 0;
+    e->vocab_v = on ? vocab : 0;
+    e->db.vocab = on ? e->vocab.p : nullptr;  // (launches are stream-ordered: it matters to those enqueued after this call)
+    e->db.vocab_p = e->vocab_p;
+    e->db.vocab_v = e->vocab_v;
+    return place_tokens(e);
+}
+
+int flowgnn_vocab_head(const flowgnn_engine* e) { return e ? e->vocab_p : -1; }
+
+int flowgnn_set_ast_encoder(flowgnn_engine* e, int emb_dim, int n_types, int n_attrs, int max_depth, const float* type_tab, const float* attr_tab,
+                            const float* depth_tab) {
+    if (!e) return FLOWGNN_ERR_ARG;
+    const std::string who = "flowgnn_set_ast_encoder: ";
+    if (int rc = width_argument(e, who, emb_dim)) return rc;
+    const bool given = type_tab || attr_tab || depth_tab;
+    if (given && (n_types < 1 || n_attrs < 1 || max_depth < 0))
+        return refuse(e, FLOWGNN_ERR_ARG, who + "n_types is " + std::to_string(n_types) + ", n_attrs " + std::to_string(n_attrs) + ", max_depth " + std::to_string(max_depth) +
+                                              "; the tables have at least one row each (ogbg-code2: 98, 10030, 20)");
+    const size_t D = (size_t)emb_dim;
+    const TensorArg t[3] = {{"type_tab", type_tab, given ? (size_t)n_types * D : 0}, {"attr_tab", attr_tab, given ? (size_t)n_attrs * D : 0},
+                            {"depth_tab", depth_tab, given ? ((size_t)max_depth + 1) * D : 0}};
+    bool on;
+    if (int rc = tensor_set_on(e, who, t, &on)) return rc;
+    if (on) {
+        if (int rc = tensor_set_finite(e, who, t)) return rc;
+        if (int rc = code2_state(e, who, "AST node encoder", emb_dim, fg::ast_encoder_blob_bytes(emb_dim, n_types, n_attrs, max_depth))) return rc;
+    }
+    ENGINE_TRY(e, begin_change(e));
+    if (on)
+        if (int rc = upload_packed(e, e->ast_enc, fg::ast_encoder_blob_bytes(emb_dim, n_types, n_attrs, max_depth),
+                                   [&](float* dst) { fg::ast_encoder_blob_pack(emb_dim, n_types, n_attrs, max_depth, type_tab, attr_tab, depth_tab, dst); }))
+            return rc;
+    e->ast_on = on;
+    e->ast_types = on ? n_types : 0;
+    e->ast_attrs = on ? n_attrs : 0;
+    e->ast_max_depth = on ? max_depth : 0;
+    e->db.ast_enc = on ? e->ast_enc.p : nullptr;  // (launches are stream-ordered: it matters to those enqueued after this call)
+    e->db.ast_types = e->ast_types;
+    e->db.ast_attrs = e->ast_attrs;
+    e->db.ast_max_depth = e->ast_max_depth;
+    return FLOWGNN_OK;
+}
+
+int flowgnn_ast_encoder(const flowgnn_engine* e) { return e ? (e->ast_on ? 1 : 0) : -1; }
 }  // extern "C"
 
 // ------------------------------------------------------------------ JK / residual

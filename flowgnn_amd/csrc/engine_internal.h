@@ -112,6 +112,15 @@ struct flowgnn_engine {
     fg::GrowBuf edge_lin;             // ... and its tensors on the device (gin_wide_el.h)
     int edge_feat_dim = 0;            // flowgnn_set_edge_features: the resident BATCH's, 0 = none attached (db.edge_feat follows it) ...
     fg::GrowBuf edge_feat;            // ... and the engine's copy of them [E][edge_feat_dim]
+    int vocab_p = 0, vocab_v = 0;     // flowgnn_set_vocab_head: the engine's, vocab_p 0 = off (db.vocab / vocab_p / vocab_v follow it)
+    fg::GrowBuf vocab;                // ... its tensors on the device (wide_vocab.h) ...
+    fg::GrowBuf tokens;               // ... and tokens [G][P] int32 | scores [G][P] of the resident batch (db.tokens / db.scores)
+    int tokens_p = 0;                 // the P of the last flowgnn_run (0: it ran with the head off): what flowgnn_get_tokens copies
+    bool ast_on = false;              // flowgnn_set_ast_encoder: the engine's as well (db.ast_enc and the three sizes follow it)
+    int ast_types = 0, ast_attrs = 0, ast_max_depth = 0;
+    fg::GrowBuf ast_enc;              // ... and its three tables on the device (wide_vocab.h)
+    bool ast_nodes_set = false;       // flowgnn_set_ast_nodes: the resident BATCH's (db.ast_x / db.ast_depth follow it) ...
+    fg::GrowBuf ast_nodes;            // ... and the engine's copy of them: x [N][2] | depth [N]
     int num_layers = FLOWGNN_NUM_LAYERS_DEFAULT;  // flowgnn_set_num_layers: the model's depth (GIN, GCN at width 300: 2 .. 8); sizes eps and the virtual node's tensors
     static_assert(FLOWGNN_MAX_NUM_LAYERS == fg::MAX_NUM_LAYERS && FLOWGNN_NUM_LAYERS_DEFAULT == fg::NUM_LAYERS_DEFAULT, "common.h restates the header's two depths");
 
@@ -163,6 +172,8 @@ struct flowgnn_engine {
 int use_device(flowgnn_engine* e);
 // what every call that changes what the launched kernels read starts with: the engine's device, no recorded launch sequence, an idle stream
 int begin_change(flowgnn_engine* e);
+// flowgnn_set_vocab_head's output buffer for the resident batch (db.tokens / db.scores), behind a change of the batch or of the head
+int place_tokens(flowgnn_engine* e);
 // the engine is GIN or GCN at width 300 (flowgnn_emb_dim is the model's own figure otherwise: 100, GAT's 16, PNA's 80)
 inline bool off_default_width(const flowgnn_engine* e) { return e->emb_dim != flowgnn_embedding_dim(e->model_id); }
 

@@ -349,7 +349,12 @@ public:
         const bool el_on = db.edge_lin != nullptr;
         if (el_on && (f16_ || res_on || jk_on || (db.b.e_tot > 0 && !db.edge_feat))) return FLOWGNN_ERR_STATE;
         if (int rc = readout_.reserve(db, exact_)) return rc;
-        {
+        if (db.ast_enc) {  // OGB's ASTNodeEncoder (flowgnn_set_ast_encoder, section 4.33) in the atom encoder's place
+            ProfScope p(prof, "ast_encoder", s);
+            if (int rc = launch_ast_encoder(D, db.ast_enc, db.ast_types, db.ast_attrs, db.ast_max_depth, db.ast_x, db.ast_depth, db.h[0], n, db.csr.err,
+                                            vn_on ? vnb : nullptr, s))
+                return rc;
+        } else {
             ProfScope p(prof, "atom_encoder", s);
             const int grid = grid_for((long long)n * M::C, 256, 256 * 8);
             if (vn_on)

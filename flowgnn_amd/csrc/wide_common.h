@@ -12,6 +12,7 @@
 #include "dense_split.h"
 #include "wide_attn.h"  // the attention readout's two launches
 #include "wide_s2s.h"   // the set2set readout's launches
+#include "wide_vocab.h" // the vocabulary head's launches (flowgnn_set_vocab_head)
 
 namespace fg {
 namespace {
@@ -205,6 +206,8 @@ struct GwReadout {
     GrowBuf attn_s;                          // the attention readout's gates [N] (section 4.20)
     GrowBuf s2s_h, s2s_c, s2s_r, s2s_e;      // the set2set readout's h_t, c_t, r_t [G][D] and dots e [N] (section 4.23)
     GrowBuf s2s_q, s2s_z;                    // ... and its exact form's q* [G][2 D] and z [G][4 D]
+    GrowBuf vh_part;                         // the vocabulary head's partial (max, index) pairs per slice (section 4.33)
+    int vh_cus = 0;                          // ... and the device's compute units, read once: they decide the slices
 
     int set_num_tasks(int t, bool& ready) {
         if (t < 1) return 8;
@@ -229,7 +232,33 @@ struct GwReadout {
                 if (int rc = s2s_z.reserve(G * 4 * D)) return rc;
             }
         }
+        if (db.vocab) {
+            if (!vh_cus) {
+                int dev = 0;
+                FG_HIP_TRY(hipGetDevice(&dev));
+                FG_HIP_TRY(hipDeviceGetAttribute(&vh_cus, hipDeviceAttributeMultiprocessorCount, dev));
+            }
+            const VocabHeadPlan pl = vocab_head_plan(db.b.num_graphs, db.vocab_v, vh_cus);
+            if (int rc = vh_part.reserve(vocab_head_part_words(pl, db.b.num_graphs, db.vocab_p))) return rc;
+        }
         return db.attn_pool ? attn_s.reserve((size_t)db.b.n_tot) : 0;
+    }
+    // flowgnn_set_vocab_head (section 4.33): tokens and scores from the pooled rows, beside the model's own head
+    int run_vocab_head(DeviceBatch& db, Profiler& prof, hipStream_t s, const float* rows, bool exact) {
+        const int G = db.b.num_graphs;
+        if (!db.tokens || !db.scores) return 6; /* FLOWGNN_ERR_STATE: the engine places them with the batch */
+        if (exact) {
+            ProfScope p(prof, "vocab_head_f32", s);
+            return launch_vocab_head_f32(D, db.vocab, db.vocab_p, db.vocab_v, rows, G, db.tokens, db.scores, s);
+        }
+        const VocabHeadPlan pl = vocab_head_plan(G, db.vocab_v, vh_cus);
+        {
+            ProfScope p(prof, "vocab_head", s);
+            if (int rc = launch_vocab_head(D, db.vocab, db.vocab_p, db.vocab_v, rows, G, pl, vh_part.p, db.tokens, db.scores, db.range_flag, s)) return rc;
+        }
+        if (pl.slices <= 1) return 0;
+        ProfScope p(prof, "vocab_head_fold", s);
+        return launch_vocab_head_fold(D, db.vocab, db.vocab_p, db.vocab_v, pl, vh_part.p, G, db.tokens, db.scores, s);
     }
     // h5: the rows the pool is taken over; hid: the exact attention gate's hidden rows [N][2 D]
     int run(DeviceBatch& db, Profiler& prof, hipStream_t s, const float* h5, bool exact, float* hid) {
@@ -274,6 +303,8 @@ struct GwReadout {
             ProfScope p(prof, "pooled_head", s);
             launch_pooled_head<D>(out, d_pw, d_pb, db.out, G, num_tasks, s);
         }
+        if (db.vocab)
+            if (int rc = run_vocab_head(db, prof, s, out, exact)) return rc;
         if (db.node_logits) {
             ProfScope p(prof, "node_logits", s);
             launch_node_logits_rows<D>(h5, d_pw, d_pb, db.node_logits, n, num_tasks, s);
@@ -285,6 +316,7 @@ struct GwReadout {
         if (d_pb) { (void)hipFree(d_pb); d_pb = nullptr; }
         pooled.release();
         attn_s.release();
+        vh_part.release();
         for (GrowBuf* b : {&s2s_h, &s2s_c, &s2s_r, &s2s_e, &s2s_q, &s2s_z}) b->release();
     }
 };

@@ -235,7 +235,8 @@ class Engine:
         self._check(self.lib.flowgnn_set_weights(self._h, len(arrs), ptrs), "flowgnn_set_weights")
 
     def load_weights_dir(self, directory: str, eps: bool = False, virtual_node: bool = False, attention_pooling: bool = False,
-                         set2set: bool = False, set2set_steps: int = 2, edge_linear: bool = False):
+                         set2set: bool = False, set2set_steps: int = 2, edge_linear: bool = False, ast_encoder: bool = False,
+                         vocab_head: bool = False):
         """eps=True (GIN, GIN-VN): also read the directory's eps file and apply it (set_gin_eps); virtual_node=True: also read
         gin_ep1_virtualnode_dim100.bin and apply it (GIN: set_ogb_virtual_node), or gcn_ep1_virtualnode_dim100.bin on a GCN engine
         (set_gcn_virtual_node; at width 300 gcn_ep1_virtualnode_dim300.bin, through flowgnn_set_gcn_virtual_node_dim).  The C call itself does neither.  A GIN engine at width 300 (set_emb_dim) reads the dim300 set, its eps
@@ -244,6 +245,8 @@ class Engine:
         (set_attention_pooling).
         set2set=True (GIN, GCN at width 300): also read gin_ep1_set2set_dim300.bin / gcn_ep1_set2set_dim300.bin and apply it with
         set2set_steps processing steps (set_set2set_pooling; OGB: 2).
+        ast_encoder=True, vocab_head=True (GIN at width 300, ogbg-code2): also read gin_ep1_astenc_dim300.bin / gin_ep1_vocabhead_dim300.bin
+        and apply them (set_ast_encoder, set_vocab_head); a code2 directory wants both beside edge_linear=True.
         After set_num_layers the files are read at the engine's depth: the per-layer tensors, num_layers eps values, num_layers - 1
         updates of the virtual node; a file of another depth is refused."""
         self._check(self.lib.flowgnn_load_weights_dir(self._h, directory.encode()), "flowgnn_load_weights_dir")
@@ -266,6 +269,14 @@ class Engine:
             from .weights import load_edge_linear
             el = load_edge_linear(directory, emb_dim=self.emb_dim, num_layers=self.num_layers, model=self.model)
             self.set_model_edge_linear(el["w"], el["b"])
+        if ast_encoder:
+            from .weights import load_ast_encoder
+            ast = load_ast_encoder(directory, emb_dim=self.emb_dim)
+            self.set_ast_encoder(ast["type"], ast["attr"], ast["depth"])
+        if vocab_head:
+            from .weights import load_vocab_head
+            head = load_vocab_head(directory, emb_dim=self.emb_dim)
+            self.set_vocab_head(head["w"], head["b"])
 
     # ---- batch
     def set_job_totals(self, job_nodes: int = -1, job_edges: int = -1):
@@ -566,9 +577,10 @@ class Engine:
         self._check(self.lib.flowgnn_set_results_buffer(self._h, C.c_void_p(device_ptr)), "flowgnn_set_results_buffer")
 
     def forward(self, batch: GraphBatch, return_embeddings: bool = False, return_node_embeddings: bool = False,
-                return_node_logits: bool = False, return_attention=None, edge_features=None):
+                return_node_logits: bool = False, return_attention=None, edge_features=None, ast_nodes=None):
         """set_batch + run + results; return_embeddings: (logits, embeddings) -- embeddings stay on for later runs;
         edge_features: what set_edge_features takes, attached behind set_batch (the batch's float edge features, for set_edge_linear);
+        ast_nodes: the pair (x, depth) that set_ast_nodes takes, attached likewise (for set_ast_encoder);
         return_node_embeddings: the node embeddings [N][embedding_dim] appended to the tuple (they stay on likewise);
         return_node_logits: the per-node readout terms [N] or [N][num_tasks] appended last (likewise);
         return_attention (GAT): what set_attention takes; the pair attention() returns is appended after everything else (likewise)."""
@@ -584,6 +596,8 @@ class Engine:
         self.set_batch(batch)
         if edge_features is not None:
             self.set_edge_features(edge_features)
+        if ast_nodes is not None:
+            self.set_ast_nodes(*ast_nodes)
         self.run()
         ret = (self.results(),) + ((self.embeddings(),) if return_embeddings else ()) + ((self.node_embeddings(),) if return_node_embeddings else ())
         ret += (self.node_logits(),) if return_node_logits else ()
@@ -832,6 +846,72 @@ class Engine:
         if ef.ndim != 2:
             raise ValueError(f"edge features: wanted [E][F], got {ef.shape}")
         self._check(self.lib.flowgnn_set_edge_features(self._h, ef.shape[1], _pf(ef), 0), "flowgnn_set_edge_features")
+
+    # ---- ogbg-code2 (flowgnn.h: flowgnn_set_vocab_head, flowgnn_set_ast_encoder)
+    def set_vocab_head(self, w=None, b=None):
+        """GIN at width 300: code2's sequence head, w [P][V][300] and b [P][V] (graph_pred_linear_list stacked); (None, None) turns
+        it off.  While it is on every run also leaves tokens(): per graph and position the argmax over the vocabulary of
+        b + W pooled, computed on the matrix pipe with the argmax fused, and its logit."""
+        if w is None and b is None:
+            self._check(self.lib.flowgnn_set_vocab_head(self._h, 300, 0, 0, None, None), "flowgnn_set_vocab_head")
+            return
+        w, b = _f32(w), _f32(b)
+        if w.ndim != 3 or b.shape != w.shape[:2]:
+            raise ValueError(f"vocabulary head: w is {w.shape} and b is {b.shape}; wanted [P][V][D] and [P][V]")
+        self._check(self.lib.flowgnn_set_vocab_head(self._h, w.shape[2], w.shape[0], w.shape[1], _pf(w), _pf(b)), "flowgnn_set_vocab_head")
+
+    @property
+    def vocab_head(self) -> int:
+        """The head's positions P, 0 while it is off (flowgnn.h: flowgnn_vocab_head)."""
+        return int(self.lib.flowgnn_vocab_head(self._h))
+
+    def tokens(self):
+        """(ids int32 [G][P], scores float32 [G][P]) of the last run (synchronises); FLOWGNN_ERR_STATE if that run had the head off, or
+        if the batch or the head has changed since (either drops them)."""
+        shape = (getattr(self, "num_graphs", 0), max(0, int(self.lib.flowgnn_tokens_positions(self._h))))  # (what the call copies; none: it says what is missing)
+        ids, scores = np.empty(shape, dtype=np.int32), np.empty(shape, dtype=np.float32)
+        self._check(self.lib.flowgnn_get_tokens(self._h, ids.ctypes.data_as(_lib.p_int), _pf(scores)), "flowgnn_get_tokens")
+        return ids, scores
+
+    def set_ast_encoder(self, type_tab=None, attr_tab=None, depth_tab=None):
+        """GIN at width 300: OGB's ASTNodeEncoder in the atom encoder's place, type_tab [n_types][300], attr_tab [n_attrs][300],
+        depth_tab [max_depth + 1][300]; three None turn it off.  While it is on every batch needs set_ast_nodes (or
+        forward(..., ast_nodes=(x, depth)))."""
+        if type_tab is None and attr_tab is None and depth_tab is None:
+            self._check(self.lib.flowgnn_set_ast_encoder(self._h, 300, 0, 0, 0, None, None, None), "flowgnn_set_ast_encoder")
+            return
+        t, a, d = _f32(type_tab), _f32(attr_tab), _f32(depth_tab)
+        if t.ndim != 2 or a.ndim != 2 or d.ndim != 2 or not (t.shape[1] == a.shape[1] == d.shape[1]):
+            raise ValueError(f"AST encoder: the tables are {t.shape}, {a.shape} and {d.shape}; wanted three [rows][D]")
+        self._check(self.lib.flowgnn_set_ast_encoder(self._h, t.shape[1], t.shape[0], a.shape[0], d.shape[0] - 1, _pf(t), _pf(a), _pf(d)),
+                    "flowgnn_set_ast_encoder")
+
+    @property
+    def ast_encoder(self) -> bool:
+        return int(self.lib.flowgnn_ast_encoder(self._h)) == 1
+
+    def set_ast_nodes(self, x, depth):
+        """x [N][2] (type, attribute) and depth [N] of the batch set last, in its node order (flowgnn.h: flowgnn_set_ast_nodes): NumPy
+        arrays, or int32 torch tensors on the engine's device, which are copied on the engine's launch stream.  The next set_batch
+        drops them."""
+        if hasattr(x, "data_ptr"):  # torch tensors
+            for t, nd in ((x, 2), (depth, 1)):
+                if not t.is_cuda or t.device.index != self.device or str(t.dtype) != "torch.int32" or t.dim() != nd:
+                    raise ValueError(f"AST nodes: wanted int32 tensors [N][2] and [N] on device {self.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+            import torch
+            x, depth = x.contiguous(), depth.contiguous()
+            es = torch.cuda.ExternalStream(self.stream_handle(), device=x.device)
+            es.wait_stream(torch.cuda.current_stream(x.device))  # what produced the tensors is done before the engine's copy reads them
+            ptr = lambda t: C.cast(C.c_void_p(t.data_ptr() if t.numel() else 0), _lib.p_int)
+            self._check(self.lib.flowgnn_set_ast_nodes(self._h, ptr(x), ptr(depth), 1), "flowgnn_set_ast_nodes")
+            x.record_stream(es)
+            depth.record_stream(es)
+            return
+        x = np.ascontiguousarray(x, dtype=np.int32)
+        depth = np.ascontiguousarray(depth, dtype=np.int32).reshape(-1)
+        if x.ndim != 2 or x.shape[1] != 2 or depth.shape[0] != x.shape[0]:
+            raise ValueError(f"AST nodes: wanted x [N][2] and depth [N], got {x.shape} and {depth.shape}")
+        self._check(self.lib.flowgnn_set_ast_nodes(self._h, x.ctypes.data_as(_lib.p_int), depth.ctypes.data_as(_lib.p_int), 0), "flowgnn_set_ast_nodes")
 
     def exact_reruns(self) -> int:
         """Forward passes repeated on the exact-fp32 kernels (flowgnn.h: flowgnn_exact_reruns)."""

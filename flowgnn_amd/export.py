@@ -244,6 +244,52 @@ def _ppa_as_molecular(sd: Mapping, num_layers: int) -> Dict:
     return out
 
 
+CODE2_KEY = "gnn_node.node_encoder.type_encoder.weight"  # what tells an ogbg-code2 state_dict (code2/utils.py: ASTNodeEncoder) from the others
+_CODE2_AST_KEYS = OrderedDict([("type", "gnn_node.node_encoder.type_encoder.weight"), ("attr", "gnn_node.node_encoder.attribute_encoder.weight"),
+                               ("depth", "gnn_node.node_encoder.depth_encoder.weight")])
+
+
+def ast_encoder_from_ogb_state_dict(sd: Mapping) -> Dict[str, np.ndarray]:
+    """The three embedding tables of an ogbg-code2 state_dict's ASTNodeEncoder, `gnn_node.node_encoder.{type,attribute,depth}_encoder.weight`,
+    as the tables Engine.set_ast_encoder / flowgnn_set_ast_encoder take: type [n_types][D], attr [n_attrs][D], depth [max_depth + 1][D]."""
+    out = OrderedDict((k, _get(sd, name)) for k, name in _CODE2_AST_KEYS.items())
+    d = out["type"].shape[-1]
+    for k, name in _CODE2_AST_KEYS.items():
+        if out[k].ndim != 2 or out[k].shape[0] < 1 or out[k].shape[1] != d:
+            raise ExportError(f"'{name}' is {out[k].shape}: wanted [rows][{d}], the width of '{CODE2_KEY}'")
+        if not np.isfinite(out[k]).all():
+            raise ExportError(f"'{name}': non-finite values")
+    return OrderedDict((k, v.astype(np.float32)) for k, v in out.items())
+
+
+def vocab_head_from_ogb_state_dict(sd: Mapping) -> Dict[str, np.ndarray]:
+    """code2's `graph_pred_linear_list.<p>` = Linear(D, V), p = 0 .. max_seq_len - 1, stacked into the two tensors Engine.set_vocab_head /
+    flowgnn_set_vocab_head take: w [P][V][D], b [P][V]."""
+    idx = sorted(int(str(k).split(".")[1]) for k in sd if str(k).startswith("graph_pred_linear_list.") and str(k).endswith(".weight"))
+    if not idx or idx != list(range(len(idx))):
+        raise ExportError(f"'graph_pred_linear_list' has the positions {idx}: wanted 0 .. P - 1 (ogbg-code2's sequence head)")
+    ws = [_get(sd, f"graph_pred_linear_list.{p}.weight") for p in idx]
+    bs = [_get(sd, f"graph_pred_linear_list.{p}.bias") for p in idx]
+    if any(w.ndim != 2 or w.shape != ws[0].shape or b.shape != w.shape[:1] for w, b in zip(ws, bs)):
+        raise ExportError(f"graph_pred_linear_list: the weights are {[w.shape for w in ws]} and the biases {[b.shape for b in bs]}; wanted P times [V][D] and [V]")
+    w, b = np.stack(ws), np.stack(bs)
+    if not (np.isfinite(w).all() and np.isfinite(b).all()):
+        raise ExportError("graph_pred_linear_list: non-finite values")
+    return OrderedDict([("w", w.astype(np.float32)), ("b", b.astype(np.float32))])
+
+
+def _code2_as_ppa(sd: Mapping, emb_dim: int) -> Dict:
+    """An ogbg-code2 state_dict with the keys of an ogbg-ppa one where the two differ, so that the rest of the export is one path: its
+    node encoder and its list head, which have files of their own, give way to a zero Embedding(1, D) row -- the atom table is then all
+    zero, and the engine does not read it while the AST encoder is on -- and to a zero one-task graph_pred_linear, as beside a set2set
+    file: a run that forgets the vocabulary head gives zeros, not plausible numbers."""
+    out = {k: v for k, v in sd.items() if not str(k).startswith("gnn_node.node_encoder.") and not str(k).startswith("graph_pred_linear_list.")}
+    out["gnn_node.node_encoder.weight"] = np.zeros((1, int(emb_dim)))
+    out["graph_pred_linear.weight"] = np.zeros((1, int(emb_dim)), np.float32)
+    out["graph_pred_linear.bias"] = np.zeros(1, np.float32)
+    return out
+
+
 def _mean_head_zeroed(sd: Mapping, emb_dim: int) -> Dict:
     """`sd` with graph_pred_linear replaced by an all-zero [T][D] head and bias: what the model's own set carries beside a set2set file"""
     t = _get(sd, "graph_pred_linear.weight").shape[0]
@@ -429,7 +475,13 @@ def export_weights(model: str, sd: Mapping, directory: str, multi_task: bool = F
     An ogbg-ppa state_dict (GIN or GCN with emb_dim=300; 300 wide) is recognised by `gnn_node.convs.0.edge_encoder.weight`: its per-layer Linear(F, D) edge
     encoders go into gin_ep1_edgelin_dim300.bin / gcn_ep1_edgelin_dim300.bin (w [L][D][F], then b [L][D]) for
     Engine.load_weights_dir(dir, edge_linear=True) to apply (flowgnn_set_edge_linear / flowgnn_set_model_edge_linear); its node_encoder = Embedding(1, D) becomes the atom table's row of feature 0, value 0, with every other
-    row zero, so ppa's all-zero x reproduces it; the bond tables are written as zeros, which the engine does not read then."""
+    row zero, so ppa's all-zero x reproduces it; the bond tables are written as zeros, which the engine does not read then.
+    An ogbg-code2 state_dict (GIN; 300 wide; gin or, with virtual_node=True, gin-virtual) is recognised by
+    `gnn_node.node_encoder.type_encoder.weight`: its ASTNodeEncoder goes into gin_ep1_astenc_dim300.bin (ast_encoder_from_ogb_state_dict)
+    and its graph_pred_linear_list into gin_ep1_vocabhead_dim300.bin (vocab_head_from_ogb_state_dict), for
+    Engine.load_weights_dir(dir, edge_linear=True, ast_encoder=True, vocab_head=True) to apply (flowgnn_set_ast_encoder,
+    flowgnn_set_vocab_head); its Linear(2, D) edge encoders go into the edge-encoder file as ppa's do, with F = 2.  The model's own set
+    then carries an all-zero atom table, which the engine does not read while the AST encoder is on, and an all-zero one-task head."""
     m = model.upper()
     if set2set and m not in ("GIN", "GCN"):
         raise ExportError(f"set2set=True is GIN's and GCN's (flowgnn_set_set2set_pooling); {model} has no such readout")
@@ -452,6 +504,19 @@ def export_weights(model: str, sd: Mapping, directory: str, multi_task: bool = F
     if virtual_node and m not in ("GIN", "GCN"):
         raise ExportError(f"virtual_node=True is OGB's gin-virtual or gcn-virtual, which the engine runs as GIN or GCN (not {model})")
     depth = num_layers_of_ogb_state_dict(sd) if m in ("GIN", "GIN-VN", "GCN") else 5
+    ast = head = None
+    if CODE2_KEY in sd:  # an ogbg-code2 model (before any file is written): its encoder and its head, then ppa's keys for the rest
+        if m != "GIN":
+            raise ExportError(f"the state_dict has '{CODE2_KEY}': it is an ogbg-code2 model, which the engine runs as GIN at width 300 "
+                              f"(flowgnn_set_ast_encoder, flowgnn_set_vocab_head), not as {model}")
+        ast, head = ast_encoder_from_ogb_state_dict(sd), vocab_head_from_ogb_state_dict(sd)
+        if ast["type"].shape[1] != 300 or head["w"].shape[2] != 300:
+            raise ExportError(f"the ogbg-code2 state_dict's encoder is {ast['type'].shape[1]} wide and its head {head['w'].shape[2]}: only the "
+                              f"300-wide GIN has the AST encoder and the vocabulary head")
+        if set2set:
+            raise ExportError("set2set=True with an ogbg-code2 state_dict: the vocabulary head reads a pooled row 300 wide and set2set's is 600 "
+                              "(flowgnn_set_vocab_head and flowgnn_set_set2set_pooling exclude each other)")
+        sd = _code2_as_ppa(sd, 300)
     edge_lin = None
     if EDGE_LIN_KEY in sd:  # an ogbg-ppa model (before any file is written): its edge encoders, then the molecular keys for the rest
         if m not in ("GIN", "GCN"):
@@ -488,6 +553,9 @@ def export_weights(model: str, sd: Mapping, directory: str, multi_task: bool = F
             _weights.save_set2set(s2s, directory, model="GIN")
         if edge_lin is not None:  # gin_ep1_edgelin_dim300.bin, for Engine.load_weights_dir(dir, edge_linear=True)
             _weights.save_edge_linear(edge_lin, directory)
+        if ast is not None:  # gin_ep1_astenc_dim300.bin, gin_ep1_vocabhead_dim300.bin, for Engine.load_weights_dir(dir, ast_encoder=True, vocab_head=True)
+            _weights.save_ast_encoder(ast, directory)
+            _weights.save_vocab_head(head, directory)
     elif m == "GCN":
         w = gcn_weights_from_ogb_state_dict(sd, num_layers=depth, multi_task=multi_task, virtual_node=virtual_node, emb_dim=emb_dim, virtual_node_dim=virtual_node_dim)
         vn = gcn_virtual_node_from_ogb_state_dict(sd, num_layers=depth, virtual_node_dim=virtual_node_dim) if virtual_node else None  # (before any file is written)

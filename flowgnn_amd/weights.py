@@ -388,6 +388,97 @@ def load_edge_linear(directory: str, emb_dim: int = 300, num_layers: int = 5, mo
     return OrderedDict([("w", _read(path, (n, d, f))), ("b", _read(path, (n, d), n * d * f))])
 
 
+# ogbg-code2 on GIN at width 300 (flowgnn.h: flowgnn_set_ast_encoder, flowgnn_set_vocab_head): two files beside the model's set.  Their
+# row counts are in no name and in no other file, so each starts with a small little-endian int32 header, then float32:
+#   gin_ep1_astenc_dim300.bin     int32 {D, n_types, n_attrs, max_depth}, then type [n_types][D], attr [n_attrs][D], depth [max_depth + 1][D]
+#   gin_ep1_vocabhead_dim300.bin  int32 {D, P, V}, then w [P][V][D], b [P][V]      (graph_pred_linear_list stacked)
+AST_ENCODER_KEYS = ("type", "attr", "depth")
+VOCAB_HEAD_KEYS = ("w", "b")
+
+
+def _code2_dim(emb_dim) -> int:
+    if int(emb_dim) != 300:
+        raise ValueError(f"ogbg-code2: emb_dim {emb_dim} is not 300 (only the 300-wide GIN has the AST encoder and the vocabulary head)")
+    return 300
+
+
+def ast_encoder_file(emb_dim: int = 300) -> str:
+    return f"gin_ep1_astenc_dim{_code2_dim(emb_dim)}.bin"
+
+
+def vocab_head_file(emb_dim: int = 300) -> str:
+    return f"gin_ep1_vocabhead_dim{_code2_dim(emb_dim)}.bin"
+
+
+def _save_headed(path: str, header, arrays) -> None:
+    with open(path, "wb") as f:
+        np.asarray(header, dtype="<i4").tofile(f)
+        for a in arrays:
+            np.ascontiguousarray(a, dtype="<f4").tofile(f)
+
+
+def _load_headed(path: str, counts: int, shapes_of, keys) -> Dict[str, np.ndarray]:
+    """The arrays `keys` behind a header of `counts` int32; shapes_of(header) gives their shapes, or raises for counts that are none"""
+    head = np.fromfile(path, dtype="<i4", count=counts)
+    if head.size != counts:
+        raise IOError(f"{path}: shorter than its header of {counts} int32")
+    shapes = shapes_of(*(int(x) for x in head))
+    floats = sum(int(np.prod(s)) for s in shapes)
+    if os.path.getsize(path) != 4 * (counts + floats):
+        raise ValueError(f"{path}: its header {head.tolist()} asks for {4 * (counts + floats)} bytes, and it holds {os.path.getsize(path)}")
+    out, at = OrderedDict(), counts  # (_read counts in 4-byte units, which the header's int32 are too)
+    for k, shp in zip(keys, shapes):
+        out[k] = _read(path, shp, at)
+        at += int(np.prod(shp))
+    return out
+
+
+def _ast_shapes(d, n_types, n_attrs, max_depth):
+    if _code2_dim(d) and (n_types < 1 or n_attrs < 1 or max_depth < 0):
+        raise ValueError(f"AST encoder: {n_types} types, {n_attrs} attributes and max_depth {max_depth}; wanted at least 1, 1 and 0")
+    return (n_types, d), (n_attrs, d), (max_depth + 1, d)
+
+
+def _vocab_shapes(d, positions, vocab):
+    if _code2_dim(d) and (positions < 1 or vocab < 1):
+        raise ValueError(f"vocabulary head: {positions} positions and {vocab} entries; wanted at least 1 of each")
+    return (positions, vocab, d), (positions, vocab)
+
+
+def save_ast_encoder(ast, directory: str) -> None:
+    """Write gin_ep1_astenc_dim300.bin from {"type": [n_types][D], "attr": [n_attrs][D], "depth": [max_depth + 1][D]}.  Nothing applies the
+    file unless asked to: Engine.load_weights_dir(dir, ast_encoder=True)."""
+    t, a, d = (np.asarray(ast[k], dtype=np.float32) for k in AST_ENCODER_KEYS)
+    if t.ndim != 2 or a.ndim != 2 or d.ndim != 2 or not (t.shape[1] == a.shape[1] == d.shape[1]):
+        raise ValueError(f"AST encoder: the tables are {t.shape}, {a.shape} and {d.shape}; wanted three [rows][D]")
+    header = (t.shape[1], t.shape[0], a.shape[0], d.shape[0] - 1)
+    _ast_shapes(*header)  # (refused before anything is created)
+    os.makedirs(directory, exist_ok=True)
+    _save_headed(os.path.join(directory, ast_encoder_file(t.shape[1])), header, (t, a, d))
+
+
+def load_ast_encoder(directory: str, emb_dim: int = 300) -> Dict[str, np.ndarray]:
+    """The three tables of a directory's AST-encoder file (for Engine.set_ast_encoder); a file whose size is not its header's is refused."""
+    return _load_headed(os.path.join(directory, ast_encoder_file(emb_dim)), 4, _ast_shapes, AST_ENCODER_KEYS)
+
+
+def save_vocab_head(head, directory: str) -> None:
+    """Write gin_ep1_vocabhead_dim300.bin from {"w": [P][V][D], "b": [P][V]}.  Nothing applies the file unless asked to:
+    Engine.load_weights_dir(dir, vocab_head=True)."""
+    w, b = np.asarray(head["w"], dtype=np.float32), np.asarray(head["b"], dtype=np.float32)
+    if w.ndim != 3 or b.shape != w.shape[:2]:
+        raise ValueError(f"vocabulary head: w is {w.shape} and b is {b.shape}; wanted [P][V][D] and [P][V]")
+    header = (w.shape[2], w.shape[0], w.shape[1])
+    _vocab_shapes(*header)  # (refused before anything is created)
+    os.makedirs(directory, exist_ok=True)
+    _save_headed(os.path.join(directory, vocab_head_file(w.shape[2])), header, (w, b))
+
+
+def load_vocab_head(directory: str, emb_dim: int = 300) -> Dict[str, np.ndarray]:
+    """The two tensors of a directory's vocabulary-head file (for Engine.set_vocab_head); a file whose size is not its header's is refused."""
+    return _load_headed(os.path.join(directory, vocab_head_file(emb_dim)), 3, _vocab_shapes, VOCAB_HEAD_KEYS)
+
+
 # OGB's set2set readout for GIN and GCN at width 300 (flowgnn.h: flowgnn_set_set2set_pooling): one file beside the model's set, PyG's
 # Set2Set LSTM (pool.lstm.weight_ih_l0, weight_hh_l0, bias_ih_l0, bias_hh_l0; gate order i, f, g, o) and OGB's Linear(2D, NUM_TASK) head,
 # in the order of the C call's arguments.  The number of processing steps is no tensor: it is given where the file is applied

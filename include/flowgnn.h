@@ -1072,6 +1072,62 @@ int flowgnn_set_edge_features(flowgnn_engine* e, int edge_dim, const float* ef /
 int flowgnn_set_model_edge_linear(flowgnn_engine* e, int emb_dim, int edge_dim, const float* w /* [L][300][edge_dim] */, const float* b /* [L][300] */);
 
 /*
+ * ogbg-code2 on GIN at width 300 (examples/graphproppred/code2).  Its message-passing layers are ppa's with
+ * F = 2 (flowgnn_set_edge_linear); two pieces around them are its own, each a call of its own and each off by default.
+ *
+ * The vocabulary head.  code2 predicts a sequence: graph_pred_linear_list is P = max_seq_len linear layers Linear(300, V) on the
+ * pooled row, and the prediction is the argmax of each (P = 5, V = 5002).  With the head on, every flowgnn_run also computes
+ *   logit[g][p][v] = b[p][v] + W[p][v] . pooled[g],   token[g][p] = argmax_v logit,   score[g][p] = that maximum
+ * on the matrix pipe (wide_vocab.hip: split f16, fp32-accurate) with the argmax fused: the logits are never stored.  Among equal
+ * fp32 logits the lowest v wins.  pooled is the [G][300] row the readout pools -- every pooling mode and the attention readout, and
+ * the f16 numeric mode of the layers (the head stays fp32-accurate) -- and the model's own head and flowgnn_get_results are what they
+ * were.  A pooled value at or beyond 6e4 or not finite repeats the pass on the exact fp32 kernels (flowgnn_exact_reruns).
+ *   flowgnn_set_vocab_head   w [P][V][300], b [P][V], host arrays, copied.  Both NULL: off.  Drops a recorded launch sequence.
+ *   flowgnn_vocab_head       P while on, 0 while off, -1 for a null handle.
+ *   flowgnn_get_tokens       after flowgnn_run: tokens [G][P] int32 and, unless NULL, scores [G][P], graphs in job order as for results.
+ *   flowgnn_tokens_device    the two device arrays of the last run (either argument may be NULL).
+ *   flowgnn_tokens_positions the P of the tokens those two calls give: the last run's, 0 when there are none (below), -1 for a null
+ *       handle.  A caller sizes its arrays by it, not by flowgnn_vocab_head, which is the P of the NEXT run.
+ * The tokens live until the batch or the head changes: flowgnn_set_batch / _device and flowgnn_set_vocab_head (on, off or another
+ * shape) drop them, and the two calls then answer FLOWGNN_ERR_STATE until the next flowgnn_run.
+ * FLOWGNN_ERR_ARG: a null handle; one of w, b NULL and not the other; positions outside 1 .. FLOWGNN_MAX_VOCAB_POSITIONS; vocab
+ * outside 1 .. FLOWGNN_MAX_VOCAB; emb_dim other than the engine's width; a non-finite weight.
+ * FLOWGNN_ERR_UNSUPPORTED: any engine but FLOWGNN_MODEL_GIN at width 300 (GCN, width 100, groups and the <M>_compute_graphs entry
+ * points have no form of it); and, while it is on, flowgnn_set_emb_dim to 100.
+ * FLOWGNN_ERR_STATE, from whichever call comes second: the head beside the set2set readout (flowgnn_set_set2set_pooling), whose
+ * pooled vector is 600 wide; flowgnn_get_tokens / flowgnn_tokens_device when the last run did not have the head on, or when the
+ * batch or the head has changed since.
+ *
+ * The AST node encoder.  OGB's ASTNodeEncoder in the atom encoder's place:
+ *   h0[v] = type_tab[x[v][0]] + attr_tab[x[v][1]] + depth_tab[min(depth[v], max_depth)]      (then the virtual node's E, when that is on)
+ * summed in that order (code2: 98, 10030 and 21 rows).
+ *   flowgnn_set_ast_encoder  the three tables, host arrays, copied.  All NULL: off.  Drops a recorded launch sequence.
+ *   flowgnn_ast_encoder      1 while on, 0 while off, -1 for a null handle.
+ *   flowgnn_set_ast_nodes    x [N_tot][2] and depth [N_tot] int32 in the node order of the batch set last, host arrays (on_device 0) or
+ *       memory of the engine's device (on_device 1, checked as flowgnn_set_batch_device checks its arrays); copied into a buffer of
+ *       the engine's own on its launch stream.  They belong to the batch: the next flowgnn_set_batch / _device drops them.
+ * flowgnn_set_batch and its validation do not change: node_feature stays required and is not read while the encoder is on (pass
+ * zeros, as ppa callers do).  flowgnn_run returns FLOWGNN_ERR_STATE while the encoder is on and the batch has no AST nodes.  A
+ * negative index, or a type or attribute at or beyond its table, fails the run as a node feature out of range does
+ * (FLOWGNN_ERR_NODE_FEAT from flowgnn_sync / flowgnn_get_*).
+ * FLOWGNN_ERR_ARG: a null handle; some tables NULL and some not; n_types < 1, n_attrs < 1, max_depth < 0; emb_dim other than the
+ * engine's width; a non-finite table entry; x or depth NULL with nodes in the batch; a device pointer that fails the check.
+ * FLOWGNN_ERR_UNSUPPORTED: any engine but FLOWGNN_MODEL_GIN at width 300 (GCN's projected table is not built); and, while it is on,
+ * flowgnn_set_emb_dim to 100.  FLOWGNN_ERR_STATE: flowgnn_set_ast_nodes without a batch.
+ */
+#define FLOWGNN_MAX_VOCAB_POSITIONS 64
+#define FLOWGNN_MAX_VOCAB (1 << 24)
+int flowgnn_set_vocab_head(flowgnn_engine* e, int emb_dim, int positions, int vocab, const float* w /* [P][V][300] */, const float* b /* [P][V] */);
+int flowgnn_vocab_head(const flowgnn_engine* e);
+int flowgnn_get_tokens(flowgnn_engine* e, int* tokens_host /* [G][P] */, float* scores_host /* [G][P], may be NULL */);
+int flowgnn_tokens_device(flowgnn_engine* e, void** d_tokens, void** d_scores);
+int flowgnn_tokens_positions(const flowgnn_engine* e);
+int flowgnn_set_ast_encoder(flowgnn_engine* e, int emb_dim, int n_types, int n_attrs, int max_depth, const float* type_tab /* [n_types][300] */,
+                            const float* attr_tab /* [n_attrs][300] */, const float* depth_tab /* [max_depth + 1][300] */);
+int flowgnn_ast_encoder(const flowgnn_engine* e);
+int flowgnn_set_ast_nodes(flowgnn_engine* e, const int* x /* [N_tot][2] */, const int* depth /* [N_tot] */, int on_device);
+
+/*
  * Laplacian eigenvectors: DGN's node_eigen from the graphs alone (the reference reads it from DGN/eig/g%d.txt and does not say where it
  * comes from).  For graph g with n nodes and edges (u, v) in local ids:
  *     A[u][v] = A[v][u] = 1 for every edge with u != v   (both directions and duplicates collapse to 1, self loops are ignored)
