@@ -195,6 +195,10 @@ struct DeviceBatch {
     int vocab_p, vocab_v;     // launch is the one it always was; its positions P and vocabulary V; where a forward that finds it set leaves
     int* tokens;              // argmax_v [G][P] and
     float* scores;            // the maxima [G][P] (the engine's buffers)
+    int topk_k;               // flowgnn_set_vocab_topk: 0 off, or the K of the head's top-k form (section 4.34), which also leaves the K best
+    int* topk_tokens;         // entries [G][P][K] (token -1 beyond the vocabulary),
+    float* topk_scores;       // their logits [G][P][K] (-inf there) and
+    float* topk_lse;          // the log-sum-exp of each position's V logits [G][P] (the engine's buffers as well)
     const void* ast_enc;      // flowgnn_set_ast_encoder (GIN at width 300): the three tables (wide_vocab.h), or null: off, the atom encoder runs;
     int ast_types, ast_attrs, ast_max_depth;  // their sizes; and the batch's x [N][2] and depth [N] (flowgnn_set_ast_nodes; flowgnn_run
     const int *ast_x, *ast_depth;             // refuses the run while the encoder is on and they are missing)

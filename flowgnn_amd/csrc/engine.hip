@@ -743,7 +743,7 @@ static int set_batch_state(flowgnn_engine* e, int num_graphs, const int* nums_of
     db.ast_types = e->ast_types; db.ast_attrs = e->ast_attrs; db.ast_max_depth = e->ast_max_depth;
     e->ast_nodes_set = false;  // flowgnn_set_ast_nodes: the nodes were the previous batch's
     db.ast_x = db.ast_depth = nullptr;
-    e->tokens_p = 0;
+    e->tokens_p = e->topk_k = 0;
     db.final_h = 0;
     db.tap = nullptr;
     db.tap_dim = 0;
@@ -766,15 +766,26 @@ static int set_batch_state(flowgnn_engine* e, int num_graphs, const int* nums_of
 // flowgnn_set_vocab_head's outputs of the resident batch: tokens [G][P] | scores [G][P] in one buffer of the engine's, behind a change of
 // the batch or of the head (both leave the stream idle and no recorded launch sequence).  Either change moves or frees what the last run
 // wrote, so that run's tokens are gone with it: flowgnn_get_tokens / flowgnn_tokens_device answer FLOWGNN_ERR_STATE until the next run
+// With flowgnn_set_vocab_topk on, the top-k form's outputs follow in the same buffer and live and die with the tokens: top-k tokens
+// [G][P][K] int32 | top-k scores [G][P][K] | lse [G][P]; a change of k comes through here as well
 int place_tokens(flowgnn_engine* e) {
-    e->tokens_p = 0;
+    e->tokens_p = e->topk_k = 0;
     e->db.tokens = nullptr;
     e->db.scores = nullptr;
+    e->db.topk_k = 0;
+    e->db.topk_tokens = nullptr;
+    e->db.topk_scores = e->db.topk_lse = nullptr;
     if (!e->vocab_p || !e->batch_ready) return FLOWGNN_OK;
-    const size_t items = (size_t)e->G * (size_t)e->vocab_p;
-    EHIP_TRY(e, e->tokens.reserve(items * (sizeof(int) + sizeof(float)), false));
+    const size_t items = (size_t)e->G * (size_t)e->vocab_p, K = (size_t)e->vocab_k;
+    EHIP_TRY(e, e->tokens.reserve(items * (sizeof(int) + sizeof(float)) + (K ? items * (2 * K + 1) * sizeof(float) : 0), false));
     e->db.tokens = (int*)e->tokens.p;
     e->db.scores = (float*)e->tokens.p + items;
+    if (K) {
+        e->db.topk_k = e->vocab_k;
+        e->db.topk_tokens = (int*)e->tokens.p + 2 * items;
+        e->db.topk_scores = (float*)e->tokens.p + (2 + K) * items;
+        e->db.topk_lse = (float*)e->tokens.p + (2 + 2 * K) * items;
+    }
     return FLOWGNN_OK;
 }
 
@@ -1084,6 +1095,7 @@ int flowgnn_run(flowgnn_engine* e) {
     }
     ENGINE_TRY(e, use_device(e));
     e->tokens_p = e->db.vocab ? e->db.vocab_p : 0;
+    e->topk_k = e->db.vocab ? e->db.topk_k : 0;
     for (const Output& o : kOutputs) (e->*o.slot).last = e->db.*o.field;
     e->attn_mask_last = e->db.attn_mask;
     if (e->G == 0) { e->ran = true; return FLOWGNN_OK; }
@@ -1215,6 +1227,37 @@ int flowgnn_tokens_device(flowgnn_engine* e, void** d_tokens, void** d_scores) {
     if (!e->ran || !e->tokens_p) return no_tokens(e, "flowgnn_tokens_device");
     if (d_tokens) *d_tokens = e->db.tokens;
     if (d_scores) *d_scores = e->db.scores;
+    return FLOWGNN_OK;
+}
+
+// flowgnn_set_vocab_topk's outputs of the last run
+static int no_topk(flowgnn_engine* e, const char* api) {
+    e->err = std::string(api) + ": the last flowgnn_run did not have the vocabulary head's top-k form on, or the batch, the head or k has changed since "
+                                "(flowgnn_set_vocab_head, flowgnn_set_vocab_topk)";
+    return FLOWGNN_ERR_STATE;
+}
+
+int flowgnn_topk_k(const flowgnn_engine* e) { return e ? (e->ran ? e->topk_k : 0) : -1; }
+
+int flowgnn_get_topk(flowgnn_engine* e, int* tokens_host, float* scores_host, float* lse_host) {
+    if (!e) return FLOWGNN_ERR_ARG;
+    if (!e->ran || !e->tokens_p || !e->topk_k) return no_topk(e, "flowgnn_get_topk");
+    if (int rc = flowgnn_sync(e)) return rc;
+    if (e->G == 0) return FLOWGNN_OK;
+    const size_t items = (size_t)e->G * (size_t)e->tokens_p, lists = items * (size_t)e->topk_k;
+    if (tokens_host)
+        if (int rc = d2h_sync(e, tokens_host, e->db.topk_tokens, sizeof(int) * lists, "copy top-k tokens")) return rc;
+    if (scores_host)
+        if (int rc = d2h_sync(e, scores_host, e->db.topk_scores, sizeof(float) * lists, "copy top-k scores")) return rc;
+    return lse_host ? d2h_sync(e, lse_host, e->db.topk_lse, sizeof(float) * items, "copy the log-sum-exp") : FLOWGNN_OK;
+}
+
+int flowgnn_topk_device(flowgnn_engine* e, void** d_tokens, void** d_scores, void** d_lse) {
+    if (!e) return FLOWGNN_ERR_ARG;
+    if (!e->ran || !e->tokens_p || !e->topk_k) return no_topk(e, "flowgnn_topk_device");
+    if (d_tokens) *d_tokens = e->db.topk_tokens;
+    if (d_scores) *d_scores = e->db.topk_scores;
+    if (d_lse) *d_lse = e->db.topk_lse;
     return FLOWGNN_OK;
 }
 

@@ -727,6 +727,21 @@ int flowgnn_set_vocab_head(flowgnn_engine* e, int emb_dim, int positions, int vo
 
 int flowgnn_vocab_head(const flowgnn_engine* e) { return e ? e->vocab_p : -1; }
 
+// the head's top-k form: one integer of the engine's, which place_tokens carries to db.topk_k while the head is on
+int flowgnn_set_vocab_topk(flowgnn_engine* e, int k) {
+    if (!e) return FLOWGNN_ERR_ARG;
+    const std::string who = "flowgnn_set_vocab_topk: ";
+    if (k < 0 || k > FLOWGNN_MAX_VOCAB_TOPK)
+        return refuse(e, FLOWGNN_ERR_ARG, who + "k is " + std::to_string(k) + "; the head keeps 1 .. " + std::to_string(FLOWGNN_MAX_VOCAB_TOPK) + " entries per position, 0 turns the top-k form off");
+    if (k)
+        if (int rc = code2_state(e, who, "vocabulary head's top-k form", e->emb_dim, e->emb_dim == FLOWGNN_EMB_DIM_OGB)) return rc;
+    ENGINE_TRY(e, begin_change(e));
+    e->vocab_k = k;
+    return place_tokens(e);
+}
+
+int flowgnn_vocab_topk(const flowgnn_engine* e) { return e ? e->vocab_k : -1; }
+
 int flowgnn_set_ast_encoder(flowgnn_engine* e, int emb_dim, int n_types, int n_attrs, int max_depth, const float* type_tab, const float* attr_tab,
                             const float* depth_tab) {
     if (!e) return FLOWGNN_ERR_ARG;

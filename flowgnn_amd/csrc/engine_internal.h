@@ -116,6 +116,8 @@ struct flowgnn_engine {
     fg::GrowBuf vocab;                // ... its tensors on the device (wide_vocab.h) ...
     fg::GrowBuf tokens;               // ... and tokens [G][P] int32 | scores [G][P] of the resident batch (db.tokens / db.scores)
     int tokens_p = 0;                 // the P of the last flowgnn_run (0: it ran with the head off): what flowgnn_get_tokens copies
+    int vocab_k = 0;                  // flowgnn_set_vocab_topk: the engine's, 0 = off (db.topk_k follows it while the head is on); the top-k
+    int topk_k = 0;                   // arrays follow the scores in `tokens`; the K of the last flowgnn_run: what flowgnn_get_topk copies
     bool ast_on = false;              // flowgnn_set_ast_encoder: the engine's as well (db.ast_enc and the three sizes follow it)
     int ast_types = 0, ast_attrs = 0, ast_max_depth = 0;
     fg::GrowBuf ast_enc;              // ... and its three tables on the device (wide_vocab.h)

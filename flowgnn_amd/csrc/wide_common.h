@@ -239,7 +239,7 @@ struct GwReadout {
                 FG_HIP_TRY(hipDeviceGetAttribute(&vh_cus, hipDeviceAttributeMultiprocessorCount, dev));
             }
             const VocabHeadPlan pl = vocab_head_plan(db.b.num_graphs, db.vocab_v, vh_cus);
-            if (int rc = vh_part.reserve(vocab_head_part_words(pl, db.b.num_graphs, db.vocab_p))) return rc;
+            if (int rc = vh_part.reserve(vocab_head_part_words(pl, db.b.num_graphs, db.vocab_p, db.topk_k))) return rc;
         }
         return db.attn_pool ? attn_s.reserve((size_t)db.b.n_tot) : 0;
     }
@@ -247,6 +247,7 @@ struct GwReadout {
     int run_vocab_head(DeviceBatch& db, Profiler& prof, hipStream_t s, const float* rows, bool exact) {
         const int G = db.b.num_graphs;
         if (!db.tokens || !db.scores) return 6; /* FLOWGNN_ERR_STATE: the engine places them with the batch */
+        if (db.topk_k) return run_vocab_topk(db, prof, s, rows, exact);
         if (exact) {
             ProfScope p(prof, "vocab_head_f32", s);
             return launch_vocab_head_f32(D, db.vocab, db.vocab_p, db.vocab_v, rows, G, db.tokens, db.scores, s);
@@ -259,6 +260,24 @@ struct GwReadout {
         if (pl.slices <= 1) return 0;
         ProfScope p(prof, "vocab_head_fold", s);
         return launch_vocab_head_fold(D, db.vocab, db.vocab_p, db.vocab_v, pl, vh_part.p, G, db.tokens, db.scores, s);
+    }
+    // flowgnn_set_vocab_topk (section 4.34): the head's top-k form in the same three places, under profiler slots of its own
+    int run_vocab_topk(DeviceBatch& db, Profiler& prof, hipStream_t s, const float* rows, bool exact) {
+        const int G = db.b.num_graphs;
+        if (!db.topk_tokens || !db.topk_scores || !db.topk_lse) return 6; /* FLOWGNN_ERR_STATE, as above */
+        const VocabTopk top{db.topk_k, db.topk_tokens, db.topk_scores, db.topk_lse};
+        if (exact) {
+            ProfScope p(prof, "vocab_topk_f32", s);
+            return launch_vocab_topk_f32(D, db.vocab, db.vocab_p, db.vocab_v, rows, G, db.tokens, db.scores, top, s);
+        }
+        const VocabHeadPlan pl = vocab_head_plan(G, db.vocab_v, vh_cus);
+        {
+            ProfScope p(prof, "vocab_topk", s);
+            if (int rc = launch_vocab_topk(D, db.vocab, db.vocab_p, db.vocab_v, rows, G, pl, vh_part.p, db.tokens, db.scores, top, db.range_flag, s)) return rc;
+        }
+        if (pl.slices <= 1) return 0;
+        ProfScope p(prof, "vocab_topk_fold", s);
+        return launch_vocab_topk_fold(D, db.vocab, db.vocab_p, db.vocab_v, pl, vh_part.p, G, db.tokens, db.scores, top, s);
     }
     // h5: the rows the pool is taken over; hid: the exact attention gate's hidden rows [N][2 D]
     int run(DeviceBatch& db, Profiler& prof, hipStream_t s, const float* h5, bool exact, float* hid) {

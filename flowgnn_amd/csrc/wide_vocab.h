@@ -23,7 +23,9 @@ struct VocabHeadPlan {
     int slices, graph_blocks;
 };
 VocabHeadPlan vocab_head_plan(int num_graphs, int vocab, int cus);
-size_t vocab_head_part_words(const VocabHeadPlan& plan, int num_graphs, int positions);
+// k: flowgnn_set_vocab_topk's (0: the argmax form).  The top-k form's part: K (float, int) pairs and one (m, s) pair per
+// [slice][graph][position]
+size_t vocab_head_part_words(const VocabHeadPlan& plan, int num_graphs, int positions, int k = 0);
 
 // pooled [G][D] -> tokens [G][P], scores [G][P].  exact: the fp32 VALU form (a plain fma chain, k ascending).  Otherwise the split-f16
 // matrix-pipe kernel, which raises *range_flag when a pooled value is at or beyond 6e4 or not finite; with plan.slices > 1 launch_vocab_head_fold
@@ -34,6 +36,22 @@ int launch_vocab_head_fold(int emb_dim, const void* blob, int positions, int voc
                            int* tokens, float* scores, hipStream_t s);
 int launch_vocab_head_f32(int emb_dim, const void* blob, int positions, int vocab, const float* pooled, int num_graphs, int* tokens, float* scores,
                           hipStream_t s);
+
+// The top-k form of the three (flowgnn_set_vocab_topk): beside tokens / scores (rank 0, the bits of the
+// launchers above) the k best entries of every position under the same order -- larger value, then lower index; token -1 and score
+// -inf at ranks beyond the vocabulary -- and lse = log sum_v exp(logit).  The same plan, the same range rule, a part sized with k
+struct VocabTopk {
+    int k;          // 1 .. FLOWGNN_MAX_VOCAB_TOPK
+    int* tokens;    // [G][P][k]
+    float* scores;  // [G][P][k]
+    float* lse;     // [G][P]
+};
+int launch_vocab_topk(int emb_dim, const void* blob, int positions, int vocab, const float* pooled, int num_graphs, const VocabHeadPlan& plan,
+                      void* part, int* tokens, float* scores, const VocabTopk& top, int* range_flag, hipStream_t s);
+int launch_vocab_topk_fold(int emb_dim, const void* blob, int positions, int vocab, const VocabHeadPlan& plan, const void* part, int num_graphs,
+                           int* tokens, float* scores, const VocabTopk& top, hipStream_t s);
+int launch_vocab_topk_f32(int emb_dim, const void* blob, int positions, int vocab, const float* pooled, int num_graphs, int* tokens, float* scores,
+                          const VocabTopk& top, hipStream_t s);
 
 // The AST node encoder: h0[v] = type_tab[x[v][0]] + attr_tab[x[v][1]] + depth_tab[min(depth[v], max_depth)] (+ vn_e, the virtual
 // node's E, when non-null), in that order.  The device form: type_tab [n_types][D] | attr_tab [n_attrs][D] | depth_tab [max_depth + 1][D]

@@ -873,6 +873,27 @@ class Engine:
         self._check(self.lib.flowgnn_get_tokens(self._h, ids.ctypes.data_as(_lib.p_int), _pf(scores)), "flowgnn_get_tokens")
         return ids, scores
 
+    def set_vocab_topk(self, k: int = 0):
+        """The head's top-k form (flowgnn.h: flowgnn_set_vocab_topk): with k in 1 .. 8 every run with the head on also leaves topk();
+        0, the default, turns it off.  tokens() keeps giving rank 0."""
+        self._check(self.lib.flowgnn_set_vocab_topk(self._h, int(k)), "flowgnn_set_vocab_topk")
+
+    @property
+    def vocab_topk(self) -> int:
+        """The k of the next run, 0 while the top-k form is off (flowgnn.h: flowgnn_vocab_topk)."""
+        return int(self.lib.flowgnn_vocab_topk(self._h))
+
+    def topk(self):
+        """(ids int32 [G][P][K], scores float32 [G][P][K], lse float32 [G][P]) of the last run (synchronises): per position the K best
+        vocabulary entries -- larger logit first, then lower index; (-1, -inf) at ranks beyond the vocabulary -- and the log-sum-exp
+        of all V logits, so scores - lse[..., None] are log-probabilities.  FLOWGNN_ERR_STATE if that run had the head or the top-k
+        form off, or if the batch, the head or k has changed since."""
+        G, P = getattr(self, "num_graphs", 0), max(0, int(self.lib.flowgnn_tokens_positions(self._h)))
+        K = max(0, int(self.lib.flowgnn_topk_k(self._h)))  # (what the call copies; none: it says what is missing)
+        ids, scores, lse = np.empty((G, P, K), dtype=np.int32), np.empty((G, P, K), dtype=np.float32), np.empty((G, P), dtype=np.float32)
+        self._check(self.lib.flowgnn_get_topk(self._h, ids.ctypes.data_as(_lib.p_int), _pf(scores), _pf(lse)), "flowgnn_get_topk")
+        return ids, scores, lse
+
     def set_ast_encoder(self, type_tab=None, attr_tab=None, depth_tab=None):
         """GIN at width 300: OGB's ASTNodeEncoder in the atom encoder's place, type_tab [n_types][300], attr_tab [n_attrs][300],
         depth_tab [max_depth + 1][300]; three None turn it off.  While it is on every batch needs set_ast_nodes (or

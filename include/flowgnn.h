@@ -1098,6 +1098,24 @@ int flowgnn_set_model_edge_linear(flowgnn_engine* e, int emb_dim, int edge_dim, 
  * pooled vector is 600 wide; flowgnn_get_tokens / flowgnn_tokens_device when the last run did not have the head on, or when the
  * batch or the head has changed since.
  *
+ * Top-k and the log-sum-exp.  A property of the head: with k in 1 .. FLOWGNN_MAX_VOCAB_TOPK a run with the
+ * head on also leaves, per graph and position, the k best entries of the V logits and the normaliser of all V of them,
+ *   rank r of (g, p): the r-th logit under the head's order -- larger value first, then lower index;  lse[g][p] = log sum_v exp(logit[g][p][v])
+ * so scores - lse are log-probabilities.  A new instance of the head's kernel keeps the candidates on chip: the logits still never
+ * reach memory.  Ranks at or beyond V hold token -1 and score -inf.  flowgnn_get_tokens keeps giving rank 0, bit for bit what k = 0
+ * gives.  With k = 0, the default, no launch differs from what it was.
+ *   flowgnn_set_vocab_topk   k; 0: off.  Takes effect while the head is on, and stays across flowgnn_set_vocab_head calls.  Drops a
+ *       recorded launch sequence.
+ *   flowgnn_vocab_topk       the k of the NEXT run, -1 for a null handle.
+ *   flowgnn_topk_k           the k of the results that flowgnn_get_topk / flowgnn_topk_device give now: the last run's, 0 when there
+ *       are none, -1 for a null handle.  A caller sizes its arrays by it (and by flowgnn_tokens_positions).
+ *   flowgnn_get_topk         tokens [G][P][K] int32, scores [G][P][K], lse [G][P]; any of the three may be NULL.
+ *   flowgnn_topk_device      the three device arrays of the last run (any argument may be NULL).
+ * They live as long as the tokens do: a change of the batch, the head or k drops them (and the tokens), and the two calls then answer
+ * FLOWGNN_ERR_STATE until the next flowgnn_run; so they do after a run with the head off or with k = 0.
+ * FLOWGNN_ERR_ARG: a null handle; k outside 0 .. FLOWGNN_MAX_VOCAB_TOPK.  FLOWGNN_ERR_UNSUPPORTED: any engine but FLOWGNN_MODEL_GIN
+ * at width 300, as for the head (k = 0 is accepted wherever a handle is valid).
+ *
  * The AST node encoder.  OGB's ASTNodeEncoder in the atom encoder's place:
  *   h0[v] = type_tab[x[v][0]] + attr_tab[x[v][1]] + depth_tab[min(depth[v], max_depth)]      (then the virtual node's E, when that is on)
  * summed in that order (code2: 98, 10030 and 21 rows).
@@ -1122,6 +1140,13 @@ int flowgnn_vocab_head(const flowgnn_engine* e);
 int flowgnn_get_tokens(flowgnn_engine* e, int* tokens_host /* [G][P] */, float* scores_host /* [G][P], may be NULL */);
 int flowgnn_tokens_device(flowgnn_engine* e, void** d_tokens, void** d_scores);
 int flowgnn_tokens_positions(const flowgnn_engine* e);
+#define FLOWGNN_MAX_VOCAB_TOPK 8
+int flowgnn_set_vocab_topk(flowgnn_engine* e, int k);
+int flowgnn_vocab_topk(const flowgnn_engine* e);
+int flowgnn_topk_k(const flowgnn_engine* e);
+int flowgnn_get_topk(flowgnn_engine* e, int* tokens_host /* [G][P][K], may be NULL */, float* scores_host /* [G][P][K], may be NULL */,
+                     float* lse_host /* [G][P], may be NULL */);
+int flowgnn_topk_device(flowgnn_engine* e, void** d_tokens, void** d_scores, void** d_lse);
 int flowgnn_set_ast_encoder(flowgnn_engine* e, int emb_dim, int n_types, int n_attrs, int max_depth, const float* type_tab /* [n_types][300] */,
                             const float* attr_tab /* [n_attrs][300] */, const float* depth_tab /* [max_depth + 1][300] */);
 int flowgnn_ast_encoder(const flowgnn_engine* e);
