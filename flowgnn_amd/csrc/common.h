@@ -195,6 +195,8 @@ struct DeviceBatch {
     int vocab_p, vocab_v;     // launch is the one it always was; its positions P and vocabulary V; where a forward that finds it set leaves
     int* tokens;              // argmax_v [G][P] and
     float* scores;            // the maxima [G][P] (the engine's buffers)
+    const void* vocab_f16;    // flowgnn_set_vocab_head_numeric(FLOWGNN_NUMERIC_F16) while the head is on: its hi-only stream (wide_vocab_f16.h,
+                              // section 4.35), or null: the head's launches are the ones they always were
     int topk_k;               // flowgnn_set_vocab_topk: 0 off, or the K of the head's top-k form (section 4.34), which also leaves the K best
     int* topk_tokens;         // entries [G][P][K] (token -1 beyond the vocabulary),
     float* topk_scores;       // their logits [G][P][K] (-inf there) and

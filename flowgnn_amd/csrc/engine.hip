@@ -421,7 +421,7 @@ int flowgnn_destroy(flowgnn_engine* e) {
     e->s2s.release();
     e->edge_lin.release();
     e->edge_feat.release();
-    for (fg::GrowBuf* b : {&e->vocab, &e->tokens, &e->ast_enc, &e->ast_nodes}) b->release();
+    for (fg::GrowBuf* b : {&e->vocab, &e->vocab_f16, &e->tokens, &e->ast_enc, &e->ast_nodes}) b->release();
     if (e->eig_done) (void)hipEventDestroy(e->eig_done);
     if (e->d_err) (void)hipFree(e->d_err);
     delete e->model;
@@ -739,7 +739,8 @@ static int set_batch_state(flowgnn_engine* e, int num_graphs, const int* nums_of
     db.vocab = e->vocab_p ? e->vocab.p : nullptr;
     db.vocab_p = e->vocab_p;
     db.vocab_v = e->vocab_v;
-    db.ast_enc = e->ast_on ? e->ast_enc.p : nullptr;
+    db.vocab_f16 = e->vocab_p && e->vocab_num == FLOWGNN_NUMERIC_F16 ? e->vocab_f16.p : nullptr;
+    db.ast_enc =e->ast_on ? e->ast_enc.p : nullptr;
     db.ast_types = e->ast_types; db.ast_attrs = e->ast_attrs; db.ast_max_depth = e->ast_max_depth;
     e->ast_nodes_set = false;  // flowgnn_set_ast_nodes: the nodes were the previous batch's
     db.ast_x = db.ast_depth = nullptr;

@@ -13,6 +13,7 @@
 #include "wide_attn.h"
 #include "wide_s2s.h"
 #include "wide_vocab.h"
+#include "wide_vocab_f16.h"
 #include <cmath>
 
 using namespace fg;
@@ -690,6 +691,24 @@ static int code2_state(flowgnn_engine* e, const std::string& who, const char* na
     return FLOWGNN_OK;
 }
 
+// The hi-only stream of the head's f16 mode: cut out of the head's own device form (its hi fragments, biases and 1 / scale), which
+// comes back to the host for it -- so either call can come second, and the engine keeps no host copy of the head
+int place_vocab_f16(flowgnn_engine* e) {
+    e->db.vocab_f16 = nullptr;
+    if (!e->vocab_p || e->vocab_num != FLOWGNN_NUMERIC_F16) {
+        e->vocab_f16.release();
+        return FLOWGNN_OK;
+    }
+    const int D = e->emb_dim, P = e->vocab_p, V = e->vocab_v;
+    std::vector<float> src(fg::vocab_head_f16_source_bytes(D, P, V) / sizeof(float));
+    EHIP_TRY(e, hipMemcpy(src.data(), e->vocab.p, src.size() * sizeof(float), hipMemcpyDeviceToHost));
+    if (int rc = upload_packed(e, e->vocab_f16, fg::vocab_head_f16_blob_bytes(D, P, V),
+                               [&](float* dst) { fg::vocab_head_f16_blob_pack(D, P, V, src.data(), dst); }))
+        return rc;
+    e->db.vocab_f16 = e->vocab_f16.p;
+    return FLOWGNN_OK;
+}
+
 extern "C" {
 
 int flowgnn_set_vocab_head(flowgnn_engine* e, int emb_dim, int positions, int vocab, const float* w, const float* b) {
@@ -722,10 +741,34 @@ int flowgnn_set_vocab_head(flowgnn_engine* e, int emb_dim, int positions, int vo
     e->db.vocab = on ? e->vocab.p : nullptr;  // (launches are stream-ordered: it matters to those enqueued after this call)
     e->db.vocab_p = e->vocab_p;
     e->db.vocab_v = e->vocab_v;
+    if (int rc = place_vocab_f16(e)) return rc;
     return place_tokens(e);
 }
 
 int flowgnn_vocab_head(const flowgnn_engine* e) { return e ? e->vocab_p : -1; }
+
+// the head's f16 numeric mode: one integer of the engine's, independent of numeric_mode; place_vocab_f16 packs
+// the hi-only stream while the head is on in it, whichever of the two calls comes second
+int flowgnn_set_vocab_head_numeric(flowgnn_engine* e, int emb_dim, int mode) {
+    if (!e) return FLOWGNN_ERR_ARG;
+    const std::string who = "flowgnn_set_vocab_head_numeric: ";
+    if (int rc = width_argument(e, who, emb_dim)) return rc;
+    if (mode != FLOWGNN_NUMERIC_F32 && mode != FLOWGNN_NUMERIC_F16)
+        return refuse(e, FLOWGNN_ERR_ARG, who + "mode is " + std::to_string(mode) + "; the head's modes are FLOWGNN_NUMERIC_F32 (0) and FLOWGNN_NUMERIC_F16 (2): it has no fixed-point form, and "
+                                              "flowgnn_set_numeric_mode / flowgnn_set_numeric_mode_dim set the layers' mode, not the head's");
+    if (mode == FLOWGNN_NUMERIC_F16) {
+        if (int rc = code2_state(e, who, "vocabulary head's f16 mode", emb_dim, emb_dim == FLOWGNN_EMB_DIM_OGB)) return rc;
+        if (e->vocab_k)
+            return refuse(e, FLOWGNN_ERR_STATE, who + "the head's top-k form is on (flowgnn_set_vocab_topk, k = " + std::to_string(e->vocab_k) +
+                                                    "), and that form has no f16 mode yet: flowgnn_set_vocab_topk(e, 0) first");
+    }
+    ENGINE_TRY(e, begin_change(e));
+    e->vocab_num = mode;
+    if (int rc = place_vocab_f16(e)) return rc;
+    return place_tokens(e);  // (the last run's tokens were another mode's)
+}
+
+int flowgnn_vocab_head_numeric(const flowgnn_engine* e) { return e ? e->vocab_num : -1; }
 
 // the head's top-k form: one integer of the engine's, which place_tokens carries to db.topk_k while the head is on
 int flowgnn_set_vocab_topk(flowgnn_engine* e, int k) {
@@ -735,6 +778,9 @@ int flowgnn_set_vocab_topk(flowgnn_engine* e, int k) {
         return refuse(e, FLOWGNN_ERR_ARG, who + "k is " + std::to_string(k) + "; the head keeps 1 .. " + std::to_string(FLOWGNN_MAX_VOCAB_TOPK) + " entries per position, 0 turns the top-k form off");
     if (k)
         if (int rc = code2_state(e, who, "vocabulary head's top-k form", e->emb_dim, e->emb_dim == FLOWGNN_EMB_DIM_OGB)) return rc;
+    if (k && e->vocab_num == FLOWGNN_NUMERIC_F16)
+        return refuse(e, FLOWGNN_ERR_STATE, who + "the head's f16 mode is on (flowgnn_set_vocab_head_numeric), and the top-k form has no f16 mode yet: "
+                                                "flowgnn_set_vocab_head_numeric(e, 300, FLOWGNN_NUMERIC_F32) first");
     ENGINE_TRY(e, begin_change(e));
     e->vocab_k = k;
     return place_tokens(e);

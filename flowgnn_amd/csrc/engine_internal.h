@@ -115,6 +115,8 @@ struct flowgnn_engine {
     int vocab_p = 0, vocab_v = 0;     // flowgnn_set_vocab_head: the engine's, vocab_p 0 = off (db.vocab / vocab_p / vocab_v follow it)
     fg::GrowBuf vocab;                // ... its tensors on the device (wide_vocab.h) ...
     fg::GrowBuf tokens;               // ... and tokens [G][P] int32 | scores [G][P] of the resident batch (db.tokens / db.scores)
+    int vocab_num = FLOWGNN_NUMERIC_F32;  // flowgnn_set_vocab_head_numeric: the engine's, independent of numeric_mode ...
+    fg::GrowBuf vocab_f16;            // ... and the head's hi-only stream (wide_vocab_f16.h) while the head is on in FLOWGNN_NUMERIC_F16 (db.vocab_f16)
     int tokens_p = 0;                 // the P of the last flowgnn_run (0: it ran with the head off): what flowgnn_get_tokens copies
     int vocab_k = 0;                  // flowgnn_set_vocab_topk: the engine's, 0 = off (db.topk_k follows it while the head is on); the top-k
     int topk_k = 0;                   // arrays follow the scores in `tokens`; the K of the last flowgnn_run: what flowgnn_get_topk copies
@@ -176,6 +178,9 @@ int use_device(flowgnn_engine* e);
 int begin_change(flowgnn_engine* e);
 // flowgnn_set_vocab_head's output buffer for the resident batch (db.tokens / db.scores), behind a change of the batch or of the head
 int place_tokens(flowgnn_engine* e);
+// engine_config.hip: the head's hi-only stream packed while the head is on in FLOWGNN_NUMERIC_F16 and freed otherwise (db.vocab_f16
+// follows); behind begin_change
+int place_vocab_f16(flowgnn_engine* e);
 // the engine is GIN or GCN at width 300 (flowgnn_emb_dim is the model's own figure otherwise: 100, GAT's 16, PNA's 80)
 inline bool off_default_width(const flowgnn_engine* e) { return e->emb_dim != flowgnn_embedding_dim(e->model_id); }
 

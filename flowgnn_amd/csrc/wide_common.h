@@ -13,6 +13,7 @@
 #include "wide_attn.h"  // the attention readout's two launches
 #include "wide_s2s.h"   // the set2set readout's launches
 #include "wide_vocab.h" // the vocabulary head's launches (flowgnn_set_vocab_head)
+#include "wide_vocab_f16.h"  // ... and its f16 numeric mode's (flowgnn_set_vocab_head_numeric)
 
 namespace fg {
 namespace {
@@ -238,10 +239,14 @@ struct GwReadout {
                 FG_HIP_TRY(hipGetDevice(&dev));
                 FG_HIP_TRY(hipDeviceGetAttribute(&vh_cus, hipDeviceAttributeMultiprocessorCount, dev));
             }
-            const VocabHeadPlan pl = vocab_head_plan(db.b.num_graphs, db.vocab_v, vh_cus);
+            const VocabHeadPlan pl = vh_plan(db, db.b.num_graphs);
             if (int rc = vh_part.reserve(vocab_head_part_words(pl, db.b.num_graphs, db.vocab_p, db.topk_k))) return rc;
         }
         return db.attn_pool ? attn_s.reserve((size_t)db.b.n_tot) : 0;
+    }
+    // the head's cut: the f16 mode's kernel (section 4.35) has a plan of its own, which the part and the fold take like the other
+    VocabHeadPlan vh_plan(const DeviceBatch& db, int G) const {
+        return db.vocab_f16 ? vocab_head_f16_plan(G, db.vocab_v, vh_cus) : vocab_head_plan(G, db.vocab_v, vh_cus);
     }
     // flowgnn_set_vocab_head (section 4.33): tokens and scores from the pooled rows, beside the model's own head
     int run_vocab_head(DeviceBatch& db, Profiler& prof, hipStream_t s, const float* rows, bool exact) {
@@ -252,8 +257,11 @@ struct GwReadout {
             ProfScope p(prof, "vocab_head_f32", s);
             return launch_vocab_head_f32(D, db.vocab, db.vocab_p, db.vocab_v, rows, G, db.tokens, db.scores, s);
         }
-        const VocabHeadPlan pl = vocab_head_plan(G, db.vocab_v, vh_cus);
-        {
+        const VocabHeadPlan pl = vh_plan(db, G);
+        if (db.vocab_f16) {  // flowgnn_set_vocab_head_numeric (section 4.35): one product per K-step, several graph tiles per wave
+            ProfScope p(prof, "vocab_head_f16", s);
+            if (int rc = launch_vocab_head_f16(D, db.vocab_f16, db.vocab_p, db.vocab_v, rows, G, pl, vh_part.p, db.tokens, db.scores, db.range_flag, s)) return rc;
+        } else {
             ProfScope p(prof, "vocab_head", s);
             if (int rc = launch_vocab_head(D, db.vocab, db.vocab_p, db.vocab_v, rows, G, pl, vh_part.p, db.tokens, db.scores, db.range_flag, s)) return rc;
         }

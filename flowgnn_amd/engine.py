@@ -236,7 +236,7 @@ class Engine:
 
     def load_weights_dir(self, directory: str, eps: bool = False, virtual_node: bool = False, attention_pooling: bool = False,
                          set2set: bool = False, set2set_steps: int = 2, edge_linear: bool = False, ast_encoder: bool = False,
-                         vocab_head: bool = False):
+                         vocab_head: bool = False, vocab_head_numeric: str = "f32"):
         """eps=True (GIN, GIN-VN): also read the directory's eps file and apply it (set_gin_eps); virtual_node=True: also read
         gin_ep1_virtualnode_dim100.bin and apply it (GIN: set_ogb_virtual_node), or gcn_ep1_virtualnode_dim100.bin on a GCN engine
         (set_gcn_virtual_node; at width 300 gcn_ep1_virtualnode_dim300.bin, through flowgnn_set_gcn_virtual_node_dim).  The C call itself does neither.  A GIN engine at width 300 (set_emb_dim) reads the dim300 set, its eps
@@ -246,7 +246,8 @@ class Engine:
         set2set=True (GIN, GCN at width 300): also read gin_ep1_set2set_dim300.bin / gcn_ep1_set2set_dim300.bin and apply it with
         set2set_steps processing steps (set_set2set_pooling; OGB: 2).
         ast_encoder=True, vocab_head=True (GIN at width 300, ogbg-code2): also read gin_ep1_astenc_dim300.bin / gin_ep1_vocabhead_dim300.bin
-        and apply them (set_ast_encoder, set_vocab_head); a code2 directory wants both beside edge_linear=True.
+        and apply them (set_ast_encoder, set_vocab_head); a code2 directory wants both beside edge_linear=True.  vocab_head_numeric:
+        the head's own numeric mode, "f32" or "f16" (set_vocab_head_numeric), applied with the head.
         After set_num_layers the files are read at the engine's depth: the per-layer tensors, num_layers eps values, num_layers - 1
         updates of the virtual node; a file of another depth is refused."""
         self._check(self.lib.flowgnn_load_weights_dir(self._h, directory.encode()), "flowgnn_load_weights_dir")
@@ -277,6 +278,7 @@ class Engine:
             from .weights import load_vocab_head
             head = load_vocab_head(directory, emb_dim=self.emb_dim)
             self.set_vocab_head(head["w"], head["b"])
+            self.set_vocab_head_numeric(vocab_head_numeric)
 
     # ---- batch
     def set_job_totals(self, job_nodes: int = -1, job_edges: int = -1):
@@ -864,6 +866,20 @@ class Engine:
     def vocab_head(self) -> int:
         """The head's positions P, 0 while it is off (flowgnn.h: flowgnn_vocab_head)."""
         return int(self.lib.flowgnn_vocab_head(self._h))
+
+    def set_vocab_head_numeric(self, mode: str = "f32"):
+        """The head's own numeric mode (flowgnn.h: flowgnn_set_vocab_head_numeric), independent of set_numeric_mode: "f32", the default,
+        or "f16" -- weights and pooled rows rounded to f16 once, one product per K-step, fp32 accumulation, for checkpoints that are
+        run for throughput.  GIN at width 300; takes effect while the head is on, in either call order; refused beside set_vocab_topk."""
+        if mode not in ("f32", "f16"):
+            raise ValueError(f"the head's numeric mode is {mode!r}, wanted 'f32' or 'f16'")
+        self._check(self.lib.flowgnn_set_vocab_head_numeric(self._h, self.emb_dim, NUMERIC_MODES[mode]), "flowgnn_set_vocab_head_numeric")
+
+    @property
+    def vocab_head_numeric(self) -> str:
+        """The head's numeric mode of the next run, "f32" or "f16" (flowgnn.h: flowgnn_vocab_head_numeric)."""
+        code = int(self.lib.flowgnn_vocab_head_numeric(self._h))
+        return next(k for k, v in NUMERIC_MODES.items() if v == code)
 
     def tokens(self):
         """(ids int32 [G][P], scores float32 [G][P]) of the last run (synchronises); FLOWGNN_ERR_STATE if that run had the head off, or

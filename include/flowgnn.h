@@ -1114,7 +1114,23 @@ int flowgnn_set_model_edge_linear(flowgnn_engine* e, int emb_dim, int edge_dim, 
  * They live as long as the tokens do: a change of the batch, the head or k drops them (and the tokens), and the two calls then answer
  * FLOWGNN_ERR_STATE until the next flowgnn_run; so they do after a run with the head off or with k = 0.
  * FLOWGNN_ERR_ARG: a null handle; k outside 0 .. FLOWGNN_MAX_VOCAB_TOPK.  FLOWGNN_ERR_UNSUPPORTED: any engine but FLOWGNN_MODEL_GIN
- * at width 300, as for the head (k = 0 is accepted wherever a handle is valid).
+ * at width 300, as for the head (k = 0 is accepted wherever a handle is valid).  FLOWGNN_ERR_STATE: k > 0 while the head's f16 mode
+ * is on (below).
+ *
+ * The head's f16 numeric mode.  A setting of the head alone, for checkpoints that are run for throughput:
+ *   logit[g][p][v] = (b[p][v] s + sum_k r(W[p][v][k] s) r(pooled[g][k])) / s
+ * s the head's power-of-two scale, r round-to-nearest-even to f16, exact products, fp32 accumulation on the matrix pipe from the
+ * pre-scaled bias: one product per K-step where the default form has three, half the weight stream, several graph tiles per wave
+ * (wide_vocab_f16.hip).  The tie rule, the range rule (the exact fp32 re-run) and the tokens' life are the head's.  It does NOT
+ * follow flowgnn_set_numeric_mode_dim: the layers' mode and the head's are independent, and all four combinations run.
+ *   flowgnn_set_vocab_head_numeric   mode FLOWGNN_NUMERIC_F32 (the default: the head's launches are what they were, bit for bit) or
+ *       FLOWGNN_NUMERIC_F16.  Takes effect while the head is on, in either call order, and stays across flowgnn_set_vocab_head
+ *       calls.  Drops a recorded launch sequence and the last run's tokens.
+ *   flowgnn_vocab_head_numeric       the mode of the NEXT run, -1 for a null handle.
+ * FLOWGNN_ERR_ARG: a null handle; any other mode, FLOWGNN_NUMERIC_Q6_10 included; emb_dim neither 100 nor 300, or, for
+ * FLOWGNN_NUMERIC_F16, not the engine's width.  FLOWGNN_ERR_UNSUPPORTED: FLOWGNN_NUMERIC_F16 on any engine but FLOWGNN_MODEL_GIN at
+ * width 300.  FLOWGNN_ERR_STATE, from whichever call comes second: FLOWGNN_NUMERIC_F16 beside flowgnn_set_vocab_topk(k > 0) -- the
+ * top-k form has no f16 mode yet.
  *
  * The AST node encoder.  OGB's ASTNodeEncoder in the atom encoder's place:
  *   h0[v] = type_tab[x[v][0]] + attr_tab[x[v][1]] + depth_tab[min(depth[v], max_depth)]      (then the virtual node's E, when that is on)
@@ -1147,6 +1163,8 @@ int flowgnn_topk_k(const flowgnn_engine* e);
 int flowgnn_get_topk(flowgnn_engine* e, int* tokens_host /* [G][P][K], may be NULL */, float* scores_host /* [G][P][K], may be NULL */,
                      float* lse_host /* [G][P], may be NULL */);
 int flowgnn_topk_device(flowgnn_engine* e, void** d_tokens, void** d_scores, void** d_lse);
+int flowgnn_set_vocab_head_numeric(flowgnn_engine* e, int emb_dim, int mode);
+int flowgnn_vocab_head_numeric(const flowgnn_engine* e);
 int flowgnn_set_ast_encoder(flowgnn_engine* e, int emb_dim, int n_types, int n_attrs, int max_depth, const float* type_tab /* [n_types][300] */,
                             const float* attr_tab /* [n_attrs][300] */, const float* depth_tab /* [max_depth + 1][300] */);
 int flowgnn_ast_encoder(const flowgnn_engine* e);
