@@ -109,6 +109,10 @@ def _declare(lib):
     lib.flowgnn_topk_device.argtypes = [eng, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     lib.flowgnn_set_vocab_head_numeric.argtypes = [eng, C.c_int, C.c_int]
     lib.flowgnn_vocab_head_numeric.argtypes = [eng]
+    lib.flowgnn_set_vocab_targets.argtypes = [eng, p_int, C.c_int, C.c_int]
+    lib.flowgnn_vocab_targets.argtypes = [eng]
+    lib.flowgnn_get_target_scores.argtypes = [eng, p_float, p_float, p_int]
+    lib.flowgnn_target_scores_device.argtypes = [eng, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     lib.flowgnn_set_ast_encoder.argtypes =[eng, C.c_int, C.c_int, C.c_int, C.c_int, p_float, p_float, p_float]
     lib.flowgnn_ast_encoder.argtypes = [eng]
     lib.flowgnn_set_ast_nodes.argtypes = [eng, p_int, p_int, C.c_int]
@@ -225,6 +229,7 @@ def _declare(lib):
                  "flowgnn_set_vocab_head", "flowgnn_vocab_head", "flowgnn_get_tokens", "flowgnn_tokens_device", "flowgnn_tokens_positions",
                  "flowgnn_set_vocab_topk", "flowgnn_vocab_topk", "flowgnn_topk_k", "flowgnn_get_topk", "flowgnn_topk_device",
                  "flowgnn_set_vocab_head_numeric", "flowgnn_vocab_head_numeric",
+                 "flowgnn_set_vocab_targets", "flowgnn_vocab_targets", "flowgnn_get_target_scores", "flowgnn_target_scores_device",
                  "flowgnn_set_ast_encoder", "flowgnn_ast_encoder", "flowgnn_set_ast_nodes",
                  "flowgnn_laplacian_eigen_max_nodes", "flowgnn_laplacian_eigen", "flowgnn_laplacian_eigen_device",
                  "GIN_compute_graphs_mt", "GCN_compute_graphs_mt", "GIN_compute_graphs", "GCN_compute_graphs", "PNA_compute_graphs", "DGN_compute_graphs", "GAT_compute_graphs"):

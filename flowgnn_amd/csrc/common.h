@@ -201,6 +201,10 @@ struct DeviceBatch {
     int* topk_tokens;         // entries [G][P][K] (token -1 beyond the vocabulary),
     float* topk_scores;       // their logits [G][P][K] (-inf there) and
     float* topk_lse;          // the log-sum-exp of each position's V logits [G][P] (the engine's buffers as well)
+    const int* targets;       // flowgnn_set_vocab_targets: the batch's target tokens [G][P] (-1: none) while the head is on in a form that scores them
+    float* target_logit;      // (section 4.36), or null: the head's launches are the ones they always were; the logit at the target [G][P],
+    float* target_lse;        // the log-sum-exp of each position's V logits [G][P] and
+    int* target_rank;         // the target's rank under (larger value, then lower index) [G][P] (the engine's buffers as well)
     const void* ast_enc;      // flowgnn_set_ast_encoder (GIN at width 300): the three tables (wide_vocab.h), or null: off, the atom encoder runs;
     int ast_types, ast_attrs, ast_max_depth;  // their sizes; and the batch's x [N][2] and depth [N] (flowgnn_set_ast_nodes; flowgnn_run
     const int *ast_x, *ast_depth;             // refuses the run while the encoder is on and they are missing)

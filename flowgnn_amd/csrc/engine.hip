@@ -421,7 +421,7 @@ int flowgnn_destroy(flowgnn_engine* e) {
     e->s2s.release();
     e->edge_lin.release();
     e->edge_feat.release();
-    for (fg::GrowBuf* b : {&e->vocab, &e->vocab_f16, &e->tokens, &e->ast_enc, &e->ast_nodes}) b->release();
+    for (fg::GrowBuf* b : {&e->vocab, &e->vocab_f16, &e->tokens, &e->targets, &e->ast_enc, &e->ast_nodes}) b->release();
     if (e->eig_done) (void)hipEventDestroy(e->eig_done);
     if (e->d_err) (void)hipFree(e->d_err);
     delete e->model;
@@ -744,6 +744,7 @@ static int set_batch_state(flowgnn_engine* e, int num_graphs, const int* nums_of
     db.ast_types = e->ast_types; db.ast_attrs = e->ast_attrs; db.ast_max_depth = e->ast_max_depth;
     e->ast_nodes_set = false;  // flowgnn_set_ast_nodes: the nodes were the previous batch's
     db.ast_x = db.ast_depth = nullptr;
+    e->targets_set = false;  // flowgnn_set_vocab_targets: the targets were the previous batch's
     e->tokens_p = e->topk_k = 0;
     db.final_h = 0;
     db.tap = nullptr;
@@ -769,8 +770,15 @@ static int set_batch_state(flowgnn_engine* e, int num_graphs, const int* nums_of
 // wrote, so that run's tokens are gone with it: flowgnn_get_tokens / flowgnn_tokens_device answer FLOWGNN_ERR_STATE until the next run
 // With flowgnn_set_vocab_topk on, the top-k form's outputs follow in the same buffer and live and die with the tokens: top-k tokens
 // [G][P][K] int32 | top-k scores [G][P][K] | lse [G][P]; a change of k comes through here as well
+// With targets attached (flowgnn_set_vocab_targets, section 4.36) their three results follow likewise: logit [G][P] | lse [G][P] | rank
+// [G][P] int32; db.targets is set only where the head can score them -- the positions agree, k = 0, the default arithmetic -- and
+// flowgnn_run refuses every other run with targets, so a non-null db.targets is one whose launches are in bounds
 int place_tokens(flowgnn_engine* e) {
     e->tokens_p = e->topk_k = 0;
+    e->targets_ran = false;
+    e->db.targets = nullptr;
+    e->db.target_logit = e->db.target_lse = nullptr;
+    e->db.target_rank = nullptr;
     e->db.tokens = nullptr;
     e->db.scores = nullptr;
     e->db.topk_k = 0;
@@ -778,7 +786,8 @@ int place_tokens(flowgnn_engine* e) {
     e->db.topk_scores = e->db.topk_lse = nullptr;
     if (!e->vocab_p || !e->batch_ready) return FLOWGNN_OK;
     const size_t items = (size_t)e->G * (size_t)e->vocab_p, K = (size_t)e->vocab_k;
-    EHIP_TRY(e, e->tokens.reserve(items * (sizeof(int) + sizeof(float)) + (K ? items * (2 * K + 1) * sizeof(float) : 0), false));
+    const bool scored = e->targets_set && e->targets_pos == e->vocab_p && !K && e->vocab_num == FLOWGNN_NUMERIC_F32;
+    EHIP_TRY(e, e->tokens.reserve(items * (sizeof(int) + sizeof(float)) + (K ? items * (2 * K + 1) * sizeof(float) : 0) + (scored ? items * 3 * sizeof(float) : 0), false));
     e->db.tokens = (int*)e->tokens.p;
     e->db.scores = (float*)e->tokens.p + items;
     if (K) {
@@ -786,6 +795,12 @@ int place_tokens(flowgnn_engine* e) {
         e->db.topk_tokens = (int*)e->tokens.p + 2 * items;
         e->db.topk_scores = (float*)e->tokens.p + (2 + K) * items;
         e->db.topk_lse = (float*)e->tokens.p + (2 + 2 * K) * items;
+    }
+    if (scored) {  // (K is 0)
+        e->db.targets = (const int*)e->targets.p;
+        e->db.target_logit = (float*)e->tokens.p + 2 * items;
+        e->db.target_lse = (float*)e->tokens.p + 3 * items;
+        e->db.target_rank = (int*)e->tokens.p + 4 * items;
     }
     return FLOWGNN_OK;
 }
@@ -977,6 +992,60 @@ int flowgnn_set_ast_nodes(flowgnn_engine* e, const int* x, const int* depth, int
     return FLOWGNN_OK;
 }
 
+// The target tokens of the resident batch, for the vocabulary head (flowgnn_set_vocab_head): attached as
+// flowgnn_set_ast_nodes attaches the nodes -- the engine's own copy, made on the launch stream.  Attaching or detaching them moves the
+// head's output buffer (place_tokens), so the last run's tokens and target scores are gone with it
+static int bad_target(flowgnn_engine* e, const char* api, int value, int vocab) {
+    e->err = std::string(api) + ": a target is " + std::to_string(value) + "; targets are -1 (no target at this position) or an index into the vocabulary" +
+             (vocab ? ", 0 .. " + std::to_string(vocab - 1) + " (flowgnn_set_vocab_head, flowgnn_set_vocab_targets)" : std::string(" (flowgnn_set_vocab_targets)"));
+    return FLOWGNN_ERR_ARG;
+}
+
+int flowgnn_set_vocab_targets(flowgnn_engine* e, const int* targets, int positions, int on_device) {
+    if (!e) return FLOWGNN_ERR_ARG;
+    static const char* const api = "flowgnn_set_vocab_targets";
+    if (!targets) {  // detach
+        if (!e->targets_set) return FLOWGNN_OK;
+        ENGINE_TRY(e, begin_change(e));
+        e->targets_set = false;
+        return place_tokens(e);
+    }
+    if (int rc = code2_state(e, std::string(api) + ": ", "vocabulary head's target scores", e->emb_dim, e->emb_dim == FLOWGNN_EMB_DIM_OGB)) return rc;
+    if (!e->batch_ready) {
+        e->err = std::string(api) + ": no batch is set, and the targets are a batch's (flowgnn_set_batch first)";
+        return FLOWGNN_ERR_STATE;
+    }
+    if (positions < 1 || positions > FLOWGNN_MAX_VOCAB_POSITIONS) {
+        e->err = std::string(api) + ": positions is " + std::to_string(positions) + "; the head has 1 .. " + std::to_string(FLOWGNN_MAX_VOCAB_POSITIONS) + " positions";
+        return FLOWGNN_ERR_ARG;
+    }
+    const size_t items = (size_t)e->G * (size_t)positions, bytes = sizeof(int) * items;
+    int lo = -1, hi = -1;
+    if (!on_device) {  // a host array is checked here, and against a head set later at flowgnn_run; a device array by the kernels
+        for (size_t i = 0; i < items; i++) {
+            lo = targets[i] < lo ? targets[i] : lo;
+            hi = targets[i] > hi ? targets[i] : hi;
+        }
+        if (lo < -1) return bad_target(e, api, lo, e->vocab_v);
+        if (e->vocab_p && hi >= e->vocab_v) return bad_target(e, api, hi, e->vocab_v);
+    }
+    ENGINE_TRY(e, use_device(e));
+    if (on_device) ENGINE_TRY(e, check_device_array(e, targets, bytes, "targets", api));
+    ENGINE_TRY(e, begin_change(e));
+    EHIP_TRY(e, e->targets.reserve(bytes, true));
+    if (bytes) {
+        EHIP_TRY(e, hipMemcpyAsync(e->targets.p, targets, bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, e->stream));
+        if (!on_device) EHIP_TRY(e, hipStreamSynchronize(e->stream));  // the caller's host array is its own again when the call returns
+    }
+    e->targets_set = true;
+    e->targets_pos = positions;
+    e->targets_lo = lo;
+    e->targets_hi = hi;
+    return place_tokens(e);
+}
+
+int flowgnn_vocab_targets(const flowgnn_engine* e) { return e ? (e->targets_set ? 1 : 0) : -1; }
+
 // ---- flowgnn_laplacian_eigen*: DGN's node_eigen from the graphs alone (kernels: eigen.hip).  Nothing of the resident batch, the
 // recorded launch sequence or the output slots is touched: the engine lends its device, its launch stream and scratch of its own.
 // The plan both functions share: counts -> offsets and the three size-class lists, one upload, one launch per non-empty class.
@@ -1094,8 +1163,22 @@ int flowgnn_run(flowgnn_engine* e) {
         e->err = "flowgnn_run: the AST node encoder is on (flowgnn_set_ast_encoder) and the batch has no AST nodes: flowgnn_set_ast_nodes after flowgnn_set_batch";
         return FLOWGNN_ERR_STATE;
     }
+    if (e->targets_set && e->vocab_p) {  // the head scores the batch's targets (section 4.36): in its default form only
+        if (e->targets_pos != e->vocab_p) {
+            e->err = "flowgnn_run: the batch's targets (flowgnn_set_vocab_targets) have " + std::to_string(e->targets_pos) + " positions and the vocabulary head (flowgnn_set_vocab_head) has " +
+                     std::to_string(e->vocab_p);
+            return FLOWGNN_ERR_STATE;
+        }
+        if (e->targets_hi >= e->vocab_v) return bad_target(e, "flowgnn_run", e->targets_hi, e->vocab_v);
+        if (e->vocab_k || e->vocab_num != FLOWGNN_NUMERIC_F32) {
+            e->err = std::string("flowgnn_run: targets are attached (flowgnn_set_vocab_targets) and the head is in its ") + (e->vocab_k ? "top-k form (flowgnn_set_vocab_topk)" : "f16 mode (flowgnn_set_vocab_head_numeric)") +
+                     ", which does not score targets yet: flowgnn_set_vocab_targets(e, NULL, 0, 0), or flowgnn_set_vocab_topk(e, 0) and flowgnn_set_vocab_head_numeric(e, 300, FLOWGNN_NUMERIC_F32)";
+            return FLOWGNN_ERR_STATE;
+        }
+    }
     ENGINE_TRY(e, use_device(e));
     e->tokens_p = e->db.vocab ? e->db.vocab_p : 0;
+    e->targets_ran = e->db.vocab && e->db.targets;
     e->topk_k = e->db.vocab ? e->db.topk_k : 0;
     for (const Output& o : kOutputs) (e->*o.slot).last = e->db.*o.field;
     e->attn_mask_last = e->db.attn_mask;
@@ -1190,7 +1273,9 @@ int flowgnn_sync(flowgnn_engine* e) {
     if (flag) {
         e->err = flag == FLOWGNN_ERR_UNSUPPORTED
                      ? "a node of a graph beyond the per-graph size classes has more than 16384 in-edges (the index build's rank sort is quadratic per row)"
-                     : "input validation failed on device (edge endpoint / edge attribute / node feature out of range)";
+                     : e->targets_ran ? "input validation failed on device (edge endpoint / edge attribute / node feature out of range, or a target of "
+                                        "flowgnn_set_vocab_targets outside -1 .. V - 1)"
+                                      : "input validation failed on device (edge endpoint / edge attribute / node feature out of range)";
         return flag;
     }
     return FLOWGNN_OK;
@@ -1259,6 +1344,35 @@ int flowgnn_topk_device(flowgnn_engine* e, void** d_tokens, void** d_scores, voi
     if (d_tokens) *d_tokens = e->db.topk_tokens;
     if (d_scores) *d_scores = e->db.topk_scores;
     if (d_lse) *d_lse = e->db.topk_lse;
+    return FLOWGNN_OK;
+}
+
+// flowgnn_set_vocab_targets' outputs of the last run
+static int no_target_scores(flowgnn_engine* e, const char* api) {
+    e->err = std::string(api) + ": the last flowgnn_run did not score targets, or the batch, the head or the targets have changed since "
+                                "(flowgnn_set_vocab_head, flowgnn_set_vocab_targets)";
+    return FLOWGNN_ERR_STATE;
+}
+
+int flowgnn_get_target_scores(flowgnn_engine* e, float* logit_host, float* lse_host, int* rank_host) {
+    if (!e) return FLOWGNN_ERR_ARG;
+    if (!e->ran || !e->tokens_p || !e->targets_ran) return no_target_scores(e, "flowgnn_get_target_scores");
+    if (int rc = flowgnn_sync(e)) return rc;
+    if (e->G == 0) return FLOWGNN_OK;
+    const size_t items = (size_t)e->G * (size_t)e->tokens_p;
+    if (logit_host)
+        if (int rc = d2h_sync(e, logit_host, e->db.target_logit, sizeof(float) * items, "copy the targets' logits")) return rc;
+    if (lse_host)
+        if (int rc = d2h_sync(e, lse_host, e->db.target_lse, sizeof(float) * items, "copy the log-sum-exp")) return rc;
+    return rank_host ? d2h_sync(e, rank_host, e->db.target_rank, sizeof(int) * items, "copy the targets' ranks") : FLOWGNN_OK;
+}
+
+int flowgnn_target_scores_device(flowgnn_engine* e, void** d_logit, void** d_lse, void** d_rank) {
+    if (!e) return FLOWGNN_ERR_ARG;
+    if (!e->ran || !e->tokens_p || !e->targets_ran) return no_target_scores(e, "flowgnn_target_scores_device");
+    if (d_logit) *d_logit = e->db.target_logit;
+    if (d_lse) *d_lse = e->db.target_lse;
+    if (d_rank) *d_rank = e->db.target_rank;
     return FLOWGNN_OK;
 }
 

@@ -682,7 +682,7 @@ int flowgnn_edge_linear(const flowgnn_engine* e) { return e ? e->edge_lin_dim : 
 // engine; db.vocab / db.ast_enc and their sizes carry them to GwReadout::run and GinWideModel::forward.  All NULL: off, at any width
 // and for any model.
 // what both calls refuse alike once their tensors are known to be sound; blob_bytes: the size of the device form (0: none at this width)
-static int code2_state(flowgnn_engine* e, const std::string& who, const char* name, int emb_dim, size_t blob_bytes) {
+int code2_state(flowgnn_engine* e, const std::string& who, const char* name, int emb_dim, size_t blob_bytes) {
     if (e->model_id != FLOWGNN_MODEL_GIN)
         return refuse(e, FLOWGNN_ERR_UNSUPPORTED, who + "the " + name + " exists for FLOWGNN_MODEL_GIN only (OGB's gin and gin-virtual of ogbg-code2; GCN's form is not built)");
     if (int rc = width_matches(e, who, true, emb_dim, e->emb_dim, "flowgnn_set_emb_dim")) return rc;

@@ -120,6 +120,11 @@ struct flowgnn_engine {
     int tokens_p = 0;                 // the P of the last flowgnn_run (0: it ran with the head off): what flowgnn_get_tokens copies
     int vocab_k = 0;                  // flowgnn_set_vocab_topk: the engine's, 0 = off (db.topk_k follows it while the head is on); the top-k
     int topk_k = 0;                   // arrays follow the scores in `tokens`; the K of the last flowgnn_run: what flowgnn_get_topk copies
+    bool targets_set = false;         // flowgnn_set_vocab_targets: the resident BATCH's (db.targets follows it while the head can score them) ...
+    int targets_pos = 0;              // ... their positions, and the least and the largest value of a host array (-1, -1 for a device array,
+    int targets_lo = -1, targets_hi = -1;  // whose values the kernels check) ...
+    fg::GrowBuf targets;              // ... and the engine's copy of them [G][targets_pos]; the three result arrays follow the top-k arrays in `tokens`
+    bool targets_ran = false;         // the last flowgnn_run scored targets: what flowgnn_get_target_scores copies
     bool ast_on = false;              // flowgnn_set_ast_encoder: the engine's as well (db.ast_enc and the three sizes follow it)
     int ast_types = 0, ast_attrs = 0, ast_max_depth = 0;
     fg::GrowBuf ast_enc;              // ... and its three tables on the device (wide_vocab.h)
@@ -181,6 +186,8 @@ int place_tokens(flowgnn_engine* e);
 // engine_config.hip: the head's hi-only stream packed while the head is on in FLOWGNN_NUMERIC_F16 and freed otherwise (db.vocab_f16
 // follows); behind begin_change
 int place_vocab_f16(flowgnn_engine* e);
+// engine_config.hip: what the code2 calls refuse alike (GIN at width 300 only); blob_bytes: the size of the device form (0: none at this width)
+int code2_state(flowgnn_engine* e, const std::string& who, const char* name, int emb_dim, size_t blob_bytes);
 // the engine is GIN or GCN at width 300 (flowgnn_emb_dim is the model's own figure otherwise: 100, GAT's 16, PNA's 80)
 inline bool off_default_width(const flowgnn_engine* e) { return e->emb_dim != flowgnn_embedding_dim(e->model_id); }
 

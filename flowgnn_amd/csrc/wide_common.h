@@ -14,6 +14,7 @@
 #include "wide_s2s.h"   // the set2set readout's launches
 #include "wide_vocab.h" // the vocabulary head's launches (flowgnn_set_vocab_head)
 #include "wide_vocab_f16.h"  // ... and its f16 numeric mode's (flowgnn_set_vocab_head_numeric)
+#include "wide_vocab_score.h"  // ... and its scoring of given targets (flowgnn_set_vocab_targets)
 
 namespace fg {
 namespace {
@@ -240,7 +241,8 @@ struct GwReadout {
                 FG_HIP_TRY(hipDeviceGetAttribute(&vh_cus, hipDeviceAttributeMultiprocessorCount, dev));
             }
             const VocabHeadPlan pl = vh_plan(db, db.b.num_graphs);
-            if (int rc = vh_part.reserve(vocab_head_part_words(pl, db.b.num_graphs, db.vocab_p, db.topk_k))) return rc;
+            const size_t words = db.targets ? vocab_score_part_words(pl, db.b.num_graphs, db.vocab_p) : vocab_head_part_words(pl, db.b.num_graphs, db.vocab_p, db.topk_k);
+            if (int rc = vh_part.reserve(words)) return rc;
         }
         return db.attn_pool ? attn_s.reserve((size_t)db.b.n_tot) : 0;
     }
@@ -252,6 +254,7 @@ struct GwReadout {
     int run_vocab_head(DeviceBatch& db, Profiler& prof, hipStream_t s, const float* rows, bool exact) {
         const int G = db.b.num_graphs;
         if (!db.tokens || !db.scores) return 6; /* FLOWGNN_ERR_STATE: the engine places them with the batch */
+        if (db.targets) return run_vocab_score(db, prof, s, rows, exact);
         if (db.topk_k) return run_vocab_topk(db, prof, s, rows, exact);
         if (exact) {
             ProfScope p(prof, "vocab_head_f32", s);
@@ -286,6 +289,29 @@ struct GwReadout {
         if (pl.slices <= 1) return 0;
         ProfScope p(prof, "vocab_topk_fold", s);
         return launch_vocab_topk_fold(D, db.vocab, db.vocab_p, db.vocab_v, pl, vh_part.p, G, db.tokens, db.scores, top, s);
+    }
+    // flowgnn_set_vocab_targets (section 4.36): the targets' logits first, then the head's stream pass with the rank and the log-sum-exp
+    // beside its argmax, under profiler slots of its own
+    int run_vocab_score(DeviceBatch& db, Profiler& prof, hipStream_t s, const float* rows, bool exact) {
+        const int G = db.b.num_graphs;
+        if (!db.target_logit || !db.target_lse || !db.target_rank) return 6; /* FLOWGNN_ERR_STATE, as above */
+        const VocabScore sc{db.targets, db.target_logit, db.target_lse, db.target_rank};
+        if (exact) {
+            ProfScope p(prof, "vocab_score_f32", s);
+            return launch_vocab_score_f32(D, db.vocab, db.vocab_p, db.vocab_v, rows, G, db.tokens, db.scores, sc, db.csr.err, s);
+        }
+        const VocabHeadPlan pl = vocab_head_plan(G, db.vocab_v, vh_cus);
+        {
+            ProfScope p(prof, "vocab_target", s);
+            if (int rc = launch_vocab_target(D, db.vocab, db.vocab_p, db.vocab_v, rows, G, vh_part.p, sc, db.csr.err, db.range_flag, s)) return rc;
+        }
+        {
+            ProfScope p(prof, "vocab_score", s);
+            if (int rc = launch_vocab_score(D, db.vocab, db.vocab_p, db.vocab_v, rows, G, pl, vh_part.p, db.tokens, db.scores, sc, db.range_flag, s)) return rc;
+        }
+        if (pl.slices <= 1) return 0;
+        ProfScope p(prof, "vocab_score_fold", s);
+        return launch_vocab_score_fold(D, db.vocab, db.vocab_p, db.vocab_v, pl, vh_part.p, G, db.tokens, db.scores, sc, s);
     }
     // h5: the rows the pool is taken over; hid: the exact attention gate's hidden rows [N][2 D]
     int run(DeviceBatch& db, Profiler& prof, hipStream_t s, const float* h5, bool exact, float* hid) {

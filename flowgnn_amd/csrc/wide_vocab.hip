@@ -31,65 +31,12 @@
 #include "dense_split.h"
 #include "wide_common.h"  // GW_WAVES, gw_issue_pieces, gw_pack_tile, gw_pow2_scale
 #include "wide_vocab.h"
+#include "wide_vocab_dev.h"  // VhDims, vh_take, vh_tile_logits, vh_lse_*, VhBlob: shared with wide_vocab_score.hip
 
 namespace fg {
 namespace {
 
-template <int D>
-struct VhDims {
-    static_assert(D % 4 == 0, "rows are read as float4 pieces");
-    static constexpr int KS = (D + 31) / 32;                   // K-steps (K padded to 32 KS)
-    static constexpr int BIAS_OFF = KS * 2 * 1024;             // fragment (ks * 2 + p), p = 0 hi, 1 lo; then 16 floats
-    static constexpr int CHUNK_BYTES = BIAS_OFF + 16 * 4;
-    static constexpr int PIECES = (CHUNK_BYTES + 1023) / 1024; // DMA pieces of 1 KiB, the last one partial
-    static constexpr int LAST_LANES = (CHUNK_BYTES - (PIECES - 1) * 1024) / 16;
-    static constexpr int CHUNK_STRIDE = PIECES * 1024;         // in global memory
-    static_assert(2 * CHUNK_BYTES <= 64 * 1024, "two chunk buffers, and room for three workgroups on a CU");
-};
-
 constexpr int VH_MIN_SLICE_TILES = 4;  // a slice is at least this many 16-row tiles per position: the B operands are set up once per block
-
-// (larger value, then lower index): the tie rule, wherever two candidates meet
-__device__ __forceinline__ void vh_take(float& m, int& idx, float cm, int cidx) {
-    if (cm > m || (cm == m && cidx < idx)) {
-        m = cm;
-        idx = cidx;
-    }
-}
-
-// ... and the same rule as the order of the top-k form's lists and of every merge of them (section 4.34): whether a comes before b,
-// asked of vh_take so that the rule stays stated once.  (a, b: two different candidates, so different indices unless both are the
-// empty entry, which comes before nothing)
-__device__ __forceinline__ bool vh_before(float av, int ai, float bv, int bi) {
-    vh_take(bv, bi, av, ai);
-    return bi == ai && ai != INT_MAX;
-}
-
-// One chunk from `wb`: the logits of a tile (rows 16 t + 4 g .. + 3 of the lane's graph), in the scaled domain
-template <int D>
-__device__ __forceinline__ float4_t vh_tile_logits(const char* wb, int lane, int g, const ds_uint4_t (&b_hi)[VhDims<D>::KS],
-                                                   const ds_uint4_t (&b_lo)[VhDims<D>::KS]) {
-    using M = VhDims<D>;
-    const float4 bv = *reinterpret_cast<const float4*>(wb + M::BIAS_OFF + g * 16);
-    float4_t acc = (float4_t){bv.x, bv.y, bv.z, bv.w};
-    // the fragments one K-step ahead of their MFMAs, and no further: the B operands leave few registers (the compiler barrier keeps the
-    // scheduler from hoisting all twenty reads of the chunk to the top)
-    ds_uint4_t n_hi = *reinterpret_cast<const ds_uint4_t*>(wb + lane * 16);
-    ds_uint4_t n_lo = *reinterpret_cast<const ds_uint4_t*>(wb + 1024 + lane * 16);
-#pragma unroll
-    for (int ks = 0; ks < M::KS; ks++) {
-        const ds_uint4_t a_hi = n_hi, a_lo = n_lo;
-        if (ks + 1 < M::KS) {
-            n_hi = *reinterpret_cast<const ds_uint4_t*>(wb + (ks * 2 + 2) * 1024 + lane * 16);
-            n_lo = *reinterpret_cast<const ds_uint4_t*>(wb + (ks * 2 + 3) * 1024 + lane * 16);
-        }
-        asm volatile("" ::: "memory");
-        acc = DS_MFMA16(a_hi, b_hi[ks], acc);
-        acc = DS_MFMA16(a_hi, b_lo[ks], acc);
-        acc = DS_MFMA16(a_lo, b_hi[ks], acc);
-    }
-    return acc;
-}
 
 // ... and the update of the running pairs
 template <int D>
@@ -128,7 +75,8 @@ __global__ __launch_bounds__(GW_WAVES * 64) void vh_kernel(const float* __restri
     };
     gw_issue_pieces<M::PIECES>(chunk(0), s_a, M::PIECES, M::LAST_LANES, wave, lane);
 
-    // ---- the B operands: the pooled rows of this wave's 16 graphs, split once
+    // ---- the B operands: the pooled rows of this wave's 16 graphs, split once (wide_vocab_dev.h's vh_load_b is this block as a
+    // function, for wide_vocab_score.hip; the two stay the same split, or a target's logit loses the stream's bits)
     ds_uint4_t b_hi[M::KS], b_lo[M::KS];
     const long long graph = ((long long)blockIdx.x * GW_WAVES + wave) * 16 + j;
     float vmax = 0.0f;
@@ -301,7 +249,6 @@ __global__ __launch_bounds__(256) void vh_f32_kernel(const float* __restrict__ p
 //     of a wave issue in order: a wave barrier, no workgroup barrier), the (m, s) pairs fold by two xor shuffles, everything is reset.
 //   * Slices: partial lists [S][G][P][K] and partial (m, s) [S][G][P] in the scaled / log2 domain; vh_topk_fold_kernel merges them.
 constexpr int VH_TOPK_MAX = FLOWGNN_MAX_VOCAB_TOPK;
-constexpr float VH_LOG2E = 1.44269504088896340736f, VH_LN2 = 0.69314718055994530942f;
 
 // The list at lv / li, slot q at [q * stride], sorted under vh_before; (v, idx) comes before its last entry, which leaves
 __device__ __forceinline__ void vh_list_insert(float* lv, int* li, int stride, int K, float v, int idx) {
@@ -321,24 +268,6 @@ __device__ __forceinline__ void vh_list_clear(float* lv, int* li, int stride, in
         li[q * stride] = INT_MAX;  // the empty entry: after every real one
     }
 }
-
-// one more y into (m, s)
-__device__ __forceinline__ void vh_lse_add(float& m, float& s, float y) {
-    if (y > m) {
-        s *= __builtin_amdgcn_exp2f(m - y);  // (m = -inf: s is 0 and stays 0)
-        m = y;
-    }
-    s += __builtin_amdgcn_exp2f(y - m);
-}
-
-// two pairs into one; a pair that has seen nothing is (-inf, 0)
-__device__ __forceinline__ void vh_lse_fold(float& m, float& s, float om, float os) {
-    const float nm = __builtin_fmaxf(m, om);
-    s = (m == nm ? s : s * __builtin_amdgcn_exp2f(m - nm)) + (om == nm ? os : os * __builtin_amdgcn_exp2f(om - nm));
-    m = nm;
-}
-
-__device__ __forceinline__ float vh_lse_value(float m, float s) { return (m + __builtin_amdgcn_logf(s)) * VH_LN2; }
 
 // out_val / out_idx [slice][G][P][K], out_m / out_s [slice][G][P]: the slice's partial lists and pair; or, with `final` (one slice),
 // the top-k scores and tokens, lse in out_m, and rank 0 in tokens / scores
@@ -672,26 +601,6 @@ __global__ __launch_bounds__(256) void ast_encoder_kernel(const int* __restrict_
         }
         reinterpret_cast<float4*>(h)[i] = s;
     }
-}
-
-constexpr int VH_D = FLOWGNN_EMB_DIM_OGB;  // the launchers' one width: the public constant's
-
-// the parts of the head's device form (wide_vocab.h)
-struct VhBlob {
-    size_t inv_off, wt_off, b_off, bytes;
-    int vtiles, v4;
-    VhBlob(int positions, int vocab) {
-        vtiles = (vocab + 15) / 16;
-        v4 = (vocab + 3) / 4 * 4;
-        inv_off = (size_t)positions * vtiles * VhDims<VH_D>::CHUNK_STRIDE;
-        wt_off = inv_off + 16;
-        b_off = wt_off + (size_t)positions * VH_D * v4 * 4;
-        bytes = b_off + (size_t)positions * v4 * 4;
-    }
-};
-
-inline bool vh_args(int emb_dim, int positions, int vocab) {
-    return emb_dim == VH_D && positions >= 1 && positions <= FLOWGNN_MAX_VOCAB_POSITIONS && vocab >= 1 && vocab <= FLOWGNN_MAX_VOCAB;
 }
 
 }  // namespace

@@ -579,10 +579,11 @@ class Engine:
         self._check(self.lib.flowgnn_set_results_buffer(self._h, C.c_void_p(device_ptr)), "flowgnn_set_results_buffer")
 
     def forward(self, batch: GraphBatch, return_embeddings: bool = False, return_node_embeddings: bool = False,
-                return_node_logits: bool = False, return_attention=None, edge_features=None, ast_nodes=None):
+                return_node_logits: bool = False, return_attention=None, edge_features=None, ast_nodes=None, targets=None):
         """set_batch + run + results; return_embeddings: (logits, embeddings) -- embeddings stay on for later runs;
         edge_features: what set_edge_features takes, attached behind set_batch (the batch's float edge features, for set_edge_linear);
         ast_nodes: the pair (x, depth) that set_ast_nodes takes, attached likewise (for set_ast_encoder);
+        targets: what set_vocab_targets takes, attached likewise (for set_vocab_head; target_scores() then has the run's);
         return_node_embeddings: the node embeddings [N][embedding_dim] appended to the tuple (they stay on likewise);
         return_node_logits: the per-node readout terms [N] or [N][num_tasks] appended last (likewise);
         return_attention (GAT): what set_attention takes; the pair attention() returns is appended after everything else (likewise)."""
@@ -600,6 +601,8 @@ class Engine:
             self.set_edge_features(edge_features)
         if ast_nodes is not None:
             self.set_ast_nodes(*ast_nodes)
+        if targets is not None:
+            self.set_vocab_targets(targets)
         self.run()
         ret = (self.results(),) + ((self.embeddings(),) if return_embeddings else ()) + ((self.node_embeddings(),) if return_node_embeddings else ())
         ret += (self.node_logits(),) if return_node_logits else ()
@@ -909,6 +912,44 @@ class Engine:
         ids, scores, lse = np.empty((G, P, K), dtype=np.int32), np.empty((G, P, K), dtype=np.float32), np.empty((G, P), dtype=np.float32)
         self._check(self.lib.flowgnn_get_topk(self._h, ids.ctypes.data_as(_lib.p_int), _pf(scores), _pf(lse)), "flowgnn_get_topk")
         return ids, scores, lse
+
+    def set_vocab_targets(self, targets=None):
+        """Reference tokens [G][P] of the batch set last (flowgnn.h: flowgnn_set_vocab_targets), -1 where a position has none: a NumPy
+        array, or an int32 torch tensor on the engine's device, which is copied on the engine's launch stream.  While they are
+        attached every run with the head on also leaves target_scores().  None detaches them; the next set_batch drops them."""
+        if targets is None:
+            self._check(self.lib.flowgnn_set_vocab_targets(self._h, None, 0, 0), "flowgnn_set_vocab_targets")
+            return
+        if hasattr(targets, "data_ptr"):  # a torch tensor
+            t = targets
+            G = getattr(self, "num_graphs", 0)
+            if not t.is_cuda or t.device.index != self.device or str(t.dtype) != "torch.int32" or t.dim() != 2 or t.shape[0] != G:
+                raise ValueError(f"targets: wanted an int32 tensor [G][P] for the batch's {G} graphs on device {self.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+            import torch
+            t = t.contiguous()
+            es = torch.cuda.ExternalStream(self.stream_handle(), device=t.device)
+            es.wait_stream(torch.cuda.current_stream(t.device))  # what produced the tensor is done before the engine's copy reads it
+            self._check(self.lib.flowgnn_set_vocab_targets(self._h, C.cast(C.c_void_p(t.data_ptr()), _lib.p_int), t.shape[1], 1), "flowgnn_set_vocab_targets")
+            t.record_stream(es)
+            return
+        t = np.ascontiguousarray(targets, dtype=np.int32)
+        if t.ndim != 2 or t.shape[0] != getattr(self, "num_graphs", 0):
+            raise ValueError(f"targets: wanted [G][P] for the batch's {getattr(self, 'num_graphs', 0)} graphs, got {t.shape}")
+        self._check(self.lib.flowgnn_set_vocab_targets(self._h, t.ctypes.data_as(_lib.p_int), t.shape[1], 0), "flowgnn_set_vocab_targets")
+
+    @property
+    def vocab_targets(self) -> bool:
+        return int(self.lib.flowgnn_vocab_targets(self._h)) == 1
+
+    def target_scores(self):
+        """(logit float32 [G][P], lse float32 [G][P], rank int32 [G][P]) of the last run (synchronises): the head's logit at each
+        target, the log-sum-exp of the position's V logits -- lse - logit is the negative log-likelihood -- and how many entries
+        come before the target under (larger logit, then lower index); (NaN, lse, -1) where the target is -1.
+        FLOWGNN_ERR_STATE if that run scored no targets, or if the batch, the head or the targets have changed since."""
+        shape = (getattr(self, "num_graphs", 0), max(0, int(self.lib.flowgnn_tokens_positions(self._h))))
+        logit, lse, rank = np.empty(shape, dtype=np.float32), np.empty(shape, dtype=np.float32), np.empty(shape, dtype=np.int32)
+        self._check(self.lib.flowgnn_get_target_scores(self._h, _pf(logit), _pf(lse), rank.ctypes.data_as(_lib.p_int)), "flowgnn_get_target_scores")
+        return logit, lse, rank
 
     def set_ast_encoder(self, type_tab=None, attr_tab=None, depth_tab=None):
         """GIN at width 300: OGB's ASTNodeEncoder in the atom encoder's place, type_tab [n_types][300], attr_tab [n_attrs][300],

@@ -1132,6 +1132,31 @@ int flowgnn_set_model_edge_linear(flowgnn_engine* e, int emb_dim, int edge_dim, 
  * width 300.  FLOWGNN_ERR_STATE, from whichever call comes second: FLOWGNN_NUMERIC_F16 beside flowgnn_set_vocab_topk(k > 0) -- the
  * top-k form has no f16 mode yet.
  *
+ * Scoring given target tokens.  An evaluation holds reference token sequences; with targets t [G][P] int32
+ * attached to the batch, a run with the head on also leaves per graph and position
+ *   target_logit = logit[g][p][t], with the bits the head's pass computes for that entry;  lse[g][p] as above (lse - target_logit is
+ *   the negative log-likelihood);  rank (int32) = how many entries v != t come before t under the head's order -- larger value first,
+ *   then lower index -- so rank is 0 exactly where the token is t, and MRR and hits@k follow from it
+ * t = -1 means no target at that position: rank -1, target_logit NaN, lse still written.  Tokens and scores are bit for bit what a run
+ * without targets gives; a gathered-row product and a new instance of the head's kernel compute the three (wide_vocab_score.hip), the
+ * logits still never reach memory.  With no targets attached no launch differs from what it was.
+ *   flowgnn_set_vocab_targets     targets [G][positions], a host array (on_device 0) or memory of the engine's device (on_device 1,
+ *       checked as flowgnn_set_batch_device checks its arrays); copied into a buffer of the engine's own on its launch stream.  They
+ *       belong to the batch set last: the next flowgnn_set_batch / _device drops them; NULL detaches them.  Attaching or detaching
+ *       drops a recorded launch sequence and the last run's tokens.  Without the head they are kept and not read.
+ *   flowgnn_vocab_targets         1 while targets are attached, 0 otherwise, -1 for a null handle.
+ *   flowgnn_get_target_scores     target_logit [G][P], lse [G][P], rank [G][P] int32 of the last run; any of the three may be NULL.
+ *   flowgnn_target_scores_device  the three device arrays of the last run (any argument may be NULL).
+ * They live as long as the tokens do: a change of the batch, the head or the targets drops them, and the two calls then answer
+ * FLOWGNN_ERR_STATE until the next flowgnn_run; so they do after a run without targets.
+ * FLOWGNN_ERR_ARG: a null handle; positions outside 1 .. FLOWGNN_MAX_VOCAB_POSITIONS; a device pointer that fails the check; a value
+ * of a host array below -1, or at or beyond V -- from flowgnn_set_vocab_targets while the head is on, from flowgnn_run when the head
+ * came later.  In a device array such a value fails the run as a node feature out of range does (FLOWGNN_ERR_NODE_FEAT from
+ * flowgnn_sync / flowgnn_get_*, the text names flowgnn_set_vocab_targets).  FLOWGNN_ERR_UNSUPPORTED: any engine but
+ * FLOWGNN_MODEL_GIN at width 300, as for the head.  FLOWGNN_ERR_STATE: flowgnn_set_vocab_targets without a batch; from flowgnn_run
+ * with the head on, positions other than the head's P, or targets beside flowgnn_set_vocab_topk(k > 0) or beside the head's
+ * FLOWGNN_NUMERIC_F16 -- neither form scores targets yet.
+ *
  * The AST node encoder.  OGB's ASTNodeEncoder in the atom encoder's place:
  *   h0[v] = type_tab[x[v][0]] + attr_tab[x[v][1]] + depth_tab[min(depth[v], max_depth)]      (then the virtual node's E, when that is on)
  * summed in that order (code2: 98, 10030 and 21 rows).
@@ -1165,6 +1190,11 @@ int flowgnn_get_topk(flowgnn_engine* e, int* tokens_host /* [G][P][K], may be NU
 int flowgnn_topk_device(flowgnn_engine* e, void** d_tokens, void** d_scores, void** d_lse);
 int flowgnn_set_vocab_head_numeric(flowgnn_engine* e, int emb_dim, int mode);
 int flowgnn_vocab_head_numeric(const flowgnn_engine* e);
+int flowgnn_set_vocab_targets(flowgnn_engine* e, const int* targets /* [G][P] */, int positions, int on_device);
+int flowgnn_vocab_targets(const flowgnn_engine* e);
+int flowgnn_get_target_scores(flowgnn_engine* e, float* logit_host /* [G][P], may be NULL */, float* lse_host /* [G][P], may be NULL */,
+                              int* rank_host /* [G][P], may be NULL */);
+int flowgnn_target_scores_device(flowgnn_engine* e, void** d_logit, void** d_lse, void** d_rank);
 int flowgnn_set_ast_encoder(flowgnn_engine* e, int emb_dim, int n_types, int n_attrs, int max_depth, const float* type_tab /* [n_types][300] */,
                             const float* attr_tab /* [n_attrs][300] */, const float* depth_tab /* [max_depth + 1][300] */);
 int flowgnn_ast_encoder(const flowgnn_engine* e);
