@@ -734,6 +734,7 @@ static int set_batch_state(flowgnn_engine* e, int num_graphs, const int* nums_of
     db.residual = e->residual;
     db.edge_lin = e->edge_lin_dim ? e->edge_lin.p : nullptr;
     db.edge_lin_dim = e->edge_lin_dim;
+    db.edge_lin_f16 = e->edge_lin_dim && e->edge_lin_num == FLOWGNN_NUMERIC_F16;
     e->edge_feat_dim = 0;  // flowgnn_set_edge_features: the features were the previous batch's
     db.edge_feat = nullptr;
     db.vocab = e->vocab_p ? e->vocab.p : nullptr;

@@ -598,6 +598,7 @@ int flowgnn_set_num_layers(flowgnn_engine* e, int emb_dim, int num_layers) {
     e->edge_lin_dim = 0;  // OGB's linear edge encoder (flowgnn_set_edge_linear): its tensors were the other depth's -- off, to be set again
     e->db.edge_lin = nullptr;
     e->db.edge_lin_dim = 0;
+    e->db.edge_lin_f16 = false;  // (flowgnn_set_edge_linear_numeric: the engine keeps the mode, which takes effect with the next encoder)
     e->batch_ready = false;  // as flowgnn_set_num_tasks: weights and batch are set again
     e->ran = false;
     e->force_exact = false;
@@ -655,6 +656,7 @@ static int set_edge_linear(flowgnn_engine* e, const char* fn, bool model_form, i
     e->edge_lin_dim = on ? edge_dim : 0;
     e->db.edge_lin = on ? e->edge_lin.p : nullptr;  // (launches are stream-ordered: it matters to those enqueued after this call)
     e->db.edge_lin_dim = e->edge_lin_dim;
+    e->db.edge_lin_f16 = on && e->edge_lin_num == FLOWGNN_NUMERIC_F16;  // flowgnn_set_edge_linear_numeric, whichever call came first
     if (!on && e->batch_ready && !e->has_attr && e->model->has_edge_attr()) {
         e->batch_ready = false;  // the batch was set without edge_attr, which the table path reads: set it again
         e->ran = false;
@@ -675,6 +677,33 @@ int flowgnn_set_model_edge_linear(flowgnn_engine* e, int emb_dim, int edge_dim, 
 }
 
 int flowgnn_edge_linear(const flowgnn_engine* e) { return e ? e->edge_lin_dim : -1; }
+
+// the f16 node MLP beside the encoder: one integer of the engine's, independent of numeric_mode, which stays
+// FLOWGNN_NUMERIC_F32 -- so flowgnn_set_numeric_mode_dim beside the encoder keeps its refusal.  db.edge_lin_f16 carries it to
+// GinWideModel::forward while the encoder is on, whichever of the two calls comes second; the hi-only weight stream it needs is packed
+// by set_weights whatever the mode is
+int flowgnn_set_edge_linear_numeric(flowgnn_engine* e, int emb_dim, int mode) {
+    if (!e) return FLOWGNN_ERR_ARG;
+    const std::string who = "flowgnn_set_edge_linear_numeric: ";
+    if (int rc = width_argument(e, who, emb_dim)) return rc;
+    if (mode != FLOWGNN_NUMERIC_F32 && mode != FLOWGNN_NUMERIC_F16)
+        return refuse(e, FLOWGNN_ERR_ARG, who + "mode is " + std::to_string(mode) + "; the modes of the layer beside the encoder are FLOWGNN_NUMERIC_F32 (0) and FLOWGNN_NUMERIC_F16 (2): "
+                                              "there is no fixed-point form at width 300");
+    if (mode == FLOWGNN_NUMERIC_F16) {
+        if (e->model_id != FLOWGNN_MODEL_GIN)
+            return refuse(e, FLOWGNN_ERR_UNSUPPORTED, who + "the f16 node MLP beside the linear edge encoder exists for FLOWGNN_MODEL_GIN only (OGB's gin and gin-virtual of ogbg-ppa and "
+                                                            "ogbg-code2; GCN's layer beside its encoder has no f16 form)");
+        if (int rc = width_matches(e, who, true, emb_dim, e->emb_dim, "flowgnn_set_emb_dim")) return rc;
+        if (emb_dim != FLOWGNN_EMB_DIM_OGB)
+            return refuse(e, FLOWGNN_ERR_UNSUPPORTED, who + "only the 300-wide GIN has the linear edge encoder and this mode of it: flowgnn_set_emb_dim(e, 300) first");
+    }
+    ENGINE_TRY(e, begin_change(e));  // (drops a recorded launch sequence: the layer's launches are other kernels)
+    e->edge_lin_num = mode;
+    e->db.edge_lin_f16 = e->edge_lin_dim && mode == FLOWGNN_NUMERIC_F16;
+    return FLOWGNN_OK;
+}
+
+int flowgnn_edge_linear_numeric(const flowgnn_engine* e) { return e ? e->edge_lin_num : -1; }
 }  // extern "C"
 
 // ------------------------------------------------------------------ ogbg-code2: the vocabulary head and the AST node encoder

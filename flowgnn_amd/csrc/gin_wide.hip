@@ -36,6 +36,7 @@
 #include "common.h"
 #include "dense_split.h"
 #include "gin_wide_el.h"  // flowgnn_set_edge_linear (section 4.31): the launchers of gin_wide_el.hip's kernels
+#include "gin_wide_el_f16.h"  // flowgnn_set_edge_linear_numeric (section 4.37): the launcher of gin_wide_el_f16.hip's kernels
 #include "gin_wide_body.h"  // GwDims, gw_step and gw_layer_body: the layer kernel's body, which gin_wide_jk.hip instantiates as well (section 4.24)
 #include "gin_wide_f16.h"  // FLOWGNN_NUMERIC_F16 at this width: the hi-only stream's layout and the launcher of gin_wide_f16.hip's kernels
 #include "gin_wide_jk.h"  // flowgnn_set_jk_residual (section 4.24): the launchers of gin_wide_jk.hip's instances
@@ -389,7 +390,13 @@ public:
                                                  !res_on ? nullptr : l == 0 ? vnb : vn_vec_[(l - 1) & 1].p, l == 0 ? 0 : D, s))
                     return rc;
             }
-            if (!exact_ && el_on) {
+            if (!exact_ && el_on && db.edge_lin_f16) {  // flowgnn_set_edge_linear_numeric (section 4.37): the same walk, the f16 node MLP
+                ProfScope p(prof, "gin_wide_layer_el_f16", s);
+                if (int rc = launch_gw_layer_el_f16(D, db.edge_lin, db.edge_lin_dim, l, db.h[cur], hn, db.csr.row_ptr, db.csr.src, db.csr.eid, db.edge_feat,
+                                                    d_chunks16_ + (size_t)l * F16::LAYER_BYTES, d_tails_ + (size_t)l * M::TAIL_FLOATS, n, relu_out, self_s,
+                                                    db.range_flag, vn_next ? node_graph_.p : nullptr, vn_next ? vnn : nullptr, s))
+                    return rc;
+            } else if (!exact_ && el_on) {
                 ProfScope p(prof, "gin_wide_layer_el", s);
                 if (int rc = launch_gw_layer_el(D, db.edge_lin, db.edge_lin_dim, l, db.h[cur], hn, db.csr.row_ptr, db.csr.src, db.csr.eid, db.edge_feat,
                                                 d_chunks_ + (size_t)l * M::LAYER_BYTES, d_tails_ + (size_t)l * M::TAIL_FLOATS, n, relu_out, self_s,

@@ -236,7 +236,7 @@ class Engine:
 
     def load_weights_dir(self, directory: str, eps: bool = False, virtual_node: bool = False, attention_pooling: bool = False,
                          set2set: bool = False, set2set_steps: int = 2, edge_linear: bool = False, ast_encoder: bool = False,
-                         vocab_head: bool = False, vocab_head_numeric: str = "f32"):
+                         vocab_head: bool = False, vocab_head_numeric: str = "f32", edge_linear_numeric: str = "f32"):
         """eps=True (GIN, GIN-VN): also read the directory's eps file and apply it (set_gin_eps); virtual_node=True: also read
         gin_ep1_virtualnode_dim100.bin and apply it (GIN: set_ogb_virtual_node), or gcn_ep1_virtualnode_dim100.bin on a GCN engine
         (set_gcn_virtual_node; at width 300 gcn_ep1_virtualnode_dim300.bin, through flowgnn_set_gcn_virtual_node_dim).  The C call itself does neither.  A GIN engine at width 300 (set_emb_dim) reads the dim300 set, its eps
@@ -247,7 +247,8 @@ class Engine:
         set2set_steps processing steps (set_set2set_pooling; OGB: 2).
         ast_encoder=True, vocab_head=True (GIN at width 300, ogbg-code2): also read gin_ep1_astenc_dim300.bin / gin_ep1_vocabhead_dim300.bin
         and apply them (set_ast_encoder, set_vocab_head); a code2 directory wants both beside edge_linear=True.  vocab_head_numeric:
-        the head's own numeric mode, "f32" or "f16" (set_vocab_head_numeric), applied with the head.
+        the head's own numeric mode, "f32" or "f16" (set_vocab_head_numeric), applied with the head.  edge_linear_numeric: the numeric
+        mode of the layer beside the encoder, "f32" or "f16" (set_edge_linear_numeric), applied with edge_linear=True.
         After set_num_layers the files are read at the engine's depth: the per-layer tensors, num_layers eps values, num_layers - 1
         updates of the virtual node; a file of another depth is refused."""
         self._check(self.lib.flowgnn_load_weights_dir(self._h, directory.encode()), "flowgnn_load_weights_dir")
@@ -270,6 +271,7 @@ class Engine:
             from .weights import load_edge_linear
             el = load_edge_linear(directory, emb_dim=self.emb_dim, num_layers=self.num_layers, model=self.model)
             self.set_model_edge_linear(el["w"], el["b"])
+            self.set_edge_linear_numeric(edge_linear_numeric)
         if ast_encoder:
             from .weights import load_ast_encoder
             ast = load_ast_encoder(directory, emb_dim=self.emb_dim)
@@ -831,6 +833,21 @@ class Engine:
     def edge_linear(self) -> int:
         """The edge encoder's features per edge, 0 while it is off (flowgnn.h: flowgnn_edge_linear)."""
         return int(self.lib.flowgnn_edge_linear(self._h))
+
+    def set_edge_linear_numeric(self, mode: str = "f32"):
+        """The numeric mode of the layer beside the edge encoder (flowgnn.h: flowgnn_set_edge_linear_numeric), independent of
+        set_numeric_mode, which stays refused beside the encoder: "f32", the default, or "f16" -- the aggregate, the hidden units and
+        both matrices of the node MLP rounded to f16 once, one product per K-step, fp32 accumulation; the encoder and the walk stay
+        fp32-accurate.  GIN at width 300; takes effect while the encoder is on, in either call order."""
+        if mode not in ("f32", "f16"):
+            raise ValueError(f"the edge encoder layer's numeric mode is {mode!r}, wanted 'f32' or 'f16'")
+        self._check(self.lib.flowgnn_set_edge_linear_numeric(self._h, self.emb_dim, NUMERIC_MODES[mode]), "flowgnn_set_edge_linear_numeric")
+
+    @property
+    def edge_linear_numeric(self) -> str:
+        """The numeric mode of the layer beside the encoder in the next run, "f32" or "f16" (flowgnn.h: flowgnn_edge_linear_numeric)."""
+        code = int(self.lib.flowgnn_edge_linear_numeric(self._h))
+        return next(k for k, v in NUMERIC_MODES.items() if v == code)
 
     def set_edge_features(self, ef):
         """The float edge features [E][F] of the batch set last, in its edge order (flowgnn.h: flowgnn_set_edge_features): a NumPy

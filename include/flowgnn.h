@@ -1058,6 +1058,30 @@ int flowgnn_edge_linear(const flowgnn_engine* e);
 int flowgnn_set_edge_features(flowgnn_engine* e, int edge_dim, const float* ef /* [E_tot][edge_dim] */, int on_device);
 
 /*
+ * The f16 node MLP beside the encoder: the throughput mode of ogbg-ppa's and ogbg-code2's layer.  A setting
+ * of the layer beside the encoder alone:
+ *   a[v] = fma(x[v], s_l, sum over v's in-edges of relu(x[src_e] + W_e e_uv + b_e))       fp32, CSR order, the encoder fp32-accurate by
+ *                                                                                        the split scheme: the walk above, unchanged
+ *   out[v] = (b2 s1 s2 + sum r(W2 s2) r(relu(b1 s1 + sum r(W1 s1) r(a[v])))) / (s1 s2)    r round-to-nearest-even to f16, exact products,
+ * fp32 accumulation on the matrix pipe, one product per K-step where the default form has three (FLOWGNN_NUMERIC_F16's rule for the
+ * node MLP at this width, flowgnn_set_numeric_mode_dim).  The layer runs gin_wide_el_f16.hip's kernels under the profile slot
+ * gin_wide_layer_el_f16.  fp32 and unchanged: the node encoders (atom and AST), eps, the virtual node, every pooling and readout, the
+ * vocabulary head (flowgnn_set_vocab_head_numeric is its own mode), node logits and embeddings.  a, a hidden unit or an edge feature at
+ * or beyond 6e4, or not finite, repeats the pass on the exact fp32 kernels: the default mode's exact path, byte for byte.
+ * It does NOT follow flowgnn_set_numeric_mode_dim, and that call beside the encoder stays refused as above: the engine's numeric mode
+ * stays FLOWGNN_NUMERIC_F32.
+ *   flowgnn_set_edge_linear_numeric   mode FLOWGNN_NUMERIC_F32 (the default: the layer's launches are what they were, bit for bit) or
+ *       FLOWGNN_NUMERIC_F16.  Takes effect while the encoder is on, in either call order, and stays across flowgnn_set_edge_linear
+ *       calls, weight sets, batches and changes of depth.  Drops a recorded launch sequence.
+ *   flowgnn_edge_linear_numeric       the mode of the NEXT run, -1 for a null handle.
+ * FLOWGNN_ERR_ARG: a null handle; any other mode, FLOWGNN_NUMERIC_Q6_10 included; emb_dim neither 100 nor 300, or, for
+ * FLOWGNN_NUMERIC_F16, not the engine's width.  FLOWGNN_ERR_UNSUPPORTED: FLOWGNN_NUMERIC_F16 on any engine but FLOWGNN_MODEL_GIN at
+ * width 300 (GCN's layer beside its encoder has no f16 form).  Single engines only, like the encoder.
+ */
+int flowgnn_set_edge_linear_numeric(flowgnn_engine* e, int emb_dim, int mode);  /* F32 (default) | F16 */
+int flowgnn_edge_linear_numeric(const flowgnn_engine* e);                       /* mode of the NEXT run; -1 for a null handle */
+
+/*
  * The model form of the call, like flowgnn_set_model_emb_dim and flowgnn_set_model_jk_residual: on a FLOWGNN_MODEL_GIN engine it is
  * flowgnn_set_edge_linear; on a FLOWGNN_MODEL_GCN engine at width 300 it turns on ppa's GCNConv,
  *   m[v] = sum over (u, v) of dinv[u] dinv[v] relu(x_u + W_e e_uv + b_e),   pre = BN(m + relu(x + root) / (deg + 1)),
