@@ -118,6 +118,7 @@ def _declare(lib):
     lib.flowgnn_set_ast_nodes.argtypes = [eng, p_int, p_int, C.c_int]
     lib.flowgnn_edge_linear.argtypes = [eng]
     lib.flowgnn_set_edge_linear_numeric.argtypes = [eng, C.c_int, C.c_int]
+    lib.flowgnn_set_model_edge_linear_numeric.argtypes = [eng, C.c_int, C.c_int]
     lib.flowgnn_edge_linear_numeric.argtypes = [eng]
     lib.flowgnn_set_edge_features.argtypes = [eng, C.c_int, p_float, C.c_int]
     lib.flowgnn_set_num_tasks.argtypes = [eng, C.c_int]
@@ -228,7 +229,7 @@ def _declare(lib):
                  "flowgnn_set_jk_residual", "flowgnn_jk_residual", "flowgnn_group_set_jk_residual", "flowgnn_set_model_jk_residual", "flowgnn_group_set_model_jk_residual",
                  "flowgnn_set_num_layers", "flowgnn_num_layers", "flowgnn_group_set_num_layers",
                  "flowgnn_set_edge_linear", "flowgnn_set_model_edge_linear", "flowgnn_edge_linear", "flowgnn_set_edge_features",
-                 "flowgnn_set_edge_linear_numeric", "flowgnn_edge_linear_numeric",
+                 "flowgnn_set_edge_linear_numeric", "flowgnn_set_model_edge_linear_numeric", "flowgnn_edge_linear_numeric",
                  "flowgnn_set_vocab_head", "flowgnn_vocab_head", "flowgnn_get_tokens", "flowgnn_tokens_device", "flowgnn_tokens_positions",
                  "flowgnn_set_vocab_topk", "flowgnn_vocab_topk", "flowgnn_topk_k", "flowgnn_get_topk", "flowgnn_topk_device",
                  "flowgnn_set_vocab_head_numeric", "flowgnn_vocab_head_numeric",

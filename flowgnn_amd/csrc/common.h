@@ -191,8 +191,9 @@ struct DeviceBatch {
     const void* edge_lin;     // flowgnn_set_edge_linear / _model_edge_linear (GIN, GCN at width 300): the encoder's tensors (gin_wide_el.h), or null: off, every
     int edge_lin_dim;         // launch is the one it always was; its edge_dim; and the batch's float edge features [E][edge_lin_dim] in the caller's
     const float* edge_feat;   // edge order (flowgnn_set_edge_features; flowgnn_run refuses the run while the encoder is on and they are missing)
-    bool edge_lin_f16;        // flowgnn_set_edge_linear_numeric(FLOWGNN_NUMERIC_F16) while the encoder is on (GIN at width 300, section 4.37): the layer
-                              // runs gin_wide_el_f16.hip's kernels; false: the layer's launches are the ones they always were
+    bool edge_lin_f16;        // flowgnn_set_edge_linear_numeric / _model_edge_linear_numeric(FLOWGNN_NUMERIC_F16) while the encoder is on (GIN, GCN at
+                              // width 300, sections 4.37 and 4.38): the layer runs gin_wide_el_f16.hip's / gcn_wide_el_f16.hip's kernels; false: the
+                              // layer's launches are the ones they always were
     const void* vocab;        // flowgnn_set_vocab_head (GIN at width 300): the head's tensors in the device form of wide_vocab.h, or null: off, every
     int vocab_p, vocab_v;     // launch is the one it always was; its positions P and vocabulary V; where a forward that finds it set leaves
     int* tokens;              // argmax_v [G][P] and

@@ -678,29 +678,48 @@ int flowgnn_set_model_edge_linear(flowgnn_engine* e, int emb_dim, int edge_dim, 
 
 int flowgnn_edge_linear(const flowgnn_engine* e) { return e ? e->edge_lin_dim : -1; }
 
-// the f16 node MLP beside the encoder: one integer of the engine's, independent of numeric_mode, which stays
-// FLOWGNN_NUMERIC_F32 -- so flowgnn_set_numeric_mode_dim beside the encoder keeps its refusal.  db.edge_lin_f16 carries it to
-// GinWideModel::forward while the encoder is on, whichever of the two calls comes second; the hi-only weight stream it needs is packed
-// by set_weights whatever the mode is
-int flowgnn_set_edge_linear_numeric(flowgnn_engine* e, int emb_dim, int mode) {
-    if (!e) return FLOWGNN_ERR_ARG;
-    const std::string who = "flowgnn_set_edge_linear_numeric: ";
+}  // extern "C"
+
+// the f16 node MLP (GIN) or the f16 product (GCN, section 4.38) beside the encoder: one integer of the engine's,
+// independent of numeric_mode, which stays FLOWGNN_NUMERIC_F32 -- so flowgnn_set_numeric_mode_dim / _model_numeric_mode_dim beside the
+// encoder keep their refusal.  db.edge_lin_f16 carries it to GinWideModel::forward / GcnWideModel::forward while the encoder is on,
+// whichever of the two calls comes second; the hi-only weight stream it needs is packed by set_weights whatever the mode is.
+// `fn`: the caller.  model_form: flowgnn_set_model_edge_linear_numeric, which a GCN engine accepts; on a GIN engine the two calls are one.
+static int set_edge_linear_numeric(flowgnn_engine* e, const char* fn, bool model_form, int emb_dim, int mode) {
+    const std::string who = std::string(fn) + ": ";
+    const bool gcn = e->model_id == FLOWGNN_MODEL_GCN;
     if (int rc = width_argument(e, who, emb_dim)) return rc;
     if (mode != FLOWGNN_NUMERIC_F32 && mode != FLOWGNN_NUMERIC_F16)
         return refuse(e, FLOWGNN_ERR_ARG, who + "mode is " + std::to_string(mode) + "; the modes of the layer beside the encoder are FLOWGNN_NUMERIC_F32 (0) and FLOWGNN_NUMERIC_F16 (2): "
                                               "there is no fixed-point form at width 300");
     if (mode == FLOWGNN_NUMERIC_F16) {
-        if (e->model_id != FLOWGNN_MODEL_GIN)
+        if (!model_form && e->model_id != FLOWGNN_MODEL_GIN)
             return refuse(e, FLOWGNN_ERR_UNSUPPORTED, who + "the f16 node MLP beside the linear edge encoder exists for FLOWGNN_MODEL_GIN only (OGB's gin and gin-virtual of ogbg-ppa and "
                                                             "ogbg-code2; GCN's layer beside its encoder has no f16 form)");
-        if (int rc = width_matches(e, who, true, emb_dim, e->emb_dim, "flowgnn_set_emb_dim")) return rc;
+        if (model_form && !gcn && e->model_id != FLOWGNN_MODEL_GIN)
+            return refuse(e, FLOWGNN_ERR_UNSUPPORTED, who + "the f16 layer beside the linear edge encoder exists for FLOWGNN_MODEL_GIN and FLOWGNN_MODEL_GCN only (OGB's gin, gin-virtual, gcn "
+                                                            "and gcn-virtual of ogbg-ppa)");
+        if (int rc = width_matches(e, who, true, emb_dim, e->emb_dim, gcn ? "flowgnn_set_model_emb_dim" : "flowgnn_set_emb_dim")) return rc;
         if (emb_dim != FLOWGNN_EMB_DIM_OGB)
-            return refuse(e, FLOWGNN_ERR_UNSUPPORTED, who + "only the 300-wide GIN has the linear edge encoder and this mode of it: flowgnn_set_emb_dim(e, 300) first");
+            return refuse(e, FLOWGNN_ERR_UNSUPPORTED, who + "only the 300-wide " + (gcn ? "GCN" : "GIN") + " has the linear edge encoder and this mode of it: " +
+                                                            (gcn ? "flowgnn_set_model_emb_dim" : "flowgnn_set_emb_dim") + "(e, 300) first");
     }
     ENGINE_TRY(e, begin_change(e));  // (drops a recorded launch sequence: the layer's launches are other kernels)
     e->edge_lin_num = mode;
     e->db.edge_lin_f16 = e->edge_lin_dim && mode == FLOWGNN_NUMERIC_F16;
     return FLOWGNN_OK;
+}
+
+extern "C" {
+
+int flowgnn_set_edge_linear_numeric(flowgnn_engine* e, int emb_dim, int mode) {
+    if (!e) return FLOWGNN_ERR_ARG;
+    return set_edge_linear_numeric(e, "flowgnn_set_edge_linear_numeric", false, emb_dim, mode);
+}
+
+int flowgnn_set_model_edge_linear_numeric(flowgnn_engine* e, int emb_dim, int mode) {
+    if (!e) return FLOWGNN_ERR_ARG;
+    return set_edge_linear_numeric(e, "flowgnn_set_model_edge_linear_numeric", true, emb_dim, mode);
 }
 
 int flowgnn_edge_linear_numeric(const flowgnn_engine* e) { return e ? e->edge_lin_num : -1; }

@@ -110,7 +110,7 @@ struct flowgnn_engine {
     int residual = 0;
     int edge_lin_dim = 0;             // flowgnn_set_edge_linear / flowgnn_set_model_edge_linear: the engine's, 0 = off (db.edge_lin / db.edge_lin_dim follow it)
     fg::GrowBuf edge_lin;             // ... and its tensors on the device (gin_wide_el.h)
-    int edge_lin_num = FLOWGNN_NUMERIC_F32;  // flowgnn_set_edge_linear_numeric: the engine's, independent of numeric_mode (db.edge_lin_f16 follows it while the encoder is on)
+    int edge_lin_num = FLOWGNN_NUMERIC_F32;  // flowgnn_set_edge_linear_numeric / _model_edge_linear_numeric: the engine's, independent of numeric_mode (db.edge_lin_f16 follows it while the encoder is on)
     int edge_feat_dim = 0;            // flowgnn_set_edge_features: the resident BATCH's, 0 = none attached (db.edge_feat follows it) ...
     fg::GrowBuf edge_feat;            // ... and the engine's copy of them [E][edge_feat_dim]
     int vocab_p = 0, vocab_v = 0;     // flowgnn_set_vocab_head: the engine's, vocab_p 0 = off (db.vocab / vocab_p / vocab_v follow it)

@@ -64,6 +64,7 @@
 #include "dense_split.h"
 #include "gcn_ogbvn.h"
 #include "gcn_wide_el.h"    // flowgnn_set_model_edge_linear (section 4.32): the launchers of gcn_wide_el.hip's kernels
+#include "gcn_wide_el_f16.h"  // flowgnn_set_model_edge_linear_numeric (section 4.38): the launcher of gcn_wide_el_f16.hip's kernels
 #include "gcn_wide_body.h"  // GcwDims, gcw_walk, gcw_step, gcw_vn_add_partials and the layer kernel's body, which gcn_wide_jk.hip instantiates as well (section 4.25)
 #include "gcn_wide_f16.h"   // FLOWGNN_NUMERIC_F16 (section 4.27): the hi-only stream's layout and the launcher of gcn_wide_f16.hip's kernels
 #include "gcn_wide_jk.h"    // flowgnn_set_model_jk_residual (section 4.25): the launchers of gcn_wide_jk.hip's instances
@@ -467,7 +468,14 @@ public:
             float* const rres = res_on ? res_.p : nullptr;
             const float* const jk_in = !jk_on ? nullptr : (l == 0 && res_on) ? res_.p : jk_.p;
             float* const jk_out = !jk_on ? nullptr : (last && db.node_emb) ? db.node_emb : jk_.p;
-            if (!exact_ && el_on) {
+            if (!exact_ && el_on && db.edge_lin_f16 && !last) {  // flowgnn_set_model_edge_linear_numeric (section 4.38): the same walk, the f16 product
+                ProfScope p(prof, "gcn_wide_layer_el_f16", s);
+                if (int rc = launch_gcw_layer_el_f16(D, db.edge_lin, db.edge_lin_dim, l, db.h[cur], hn, db.csr.row_ptr, db.csr.src, db.csr.eid, db.edge_feat,
+                                                     esc_.p, db.csr.out_deg, tab, d_chunks16_ + (size_t)l * F16::LAYER_BYTES,
+                                                     d_tails_ + (size_t)l * M::TAIL_FLOATS, n, db.range_flag, vn ? node_graph_.p : nullptr,
+                                                     vn ? vn_vec_[l & 1].p : nullptr, vn && feeds_update(l) ? vn_part_.p : nullptr, s))
+                    return rc;
+            } else if (!exact_ && el_on) {
                 ProfScope p(prof, "gcn_wide_layer_el", s);
                 int rc;
                 if (!last)

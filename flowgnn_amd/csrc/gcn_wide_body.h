@@ -77,8 +77,8 @@ __device__ __forceinline__ void gcw_el_issue_block(const uint8_t* __restrict__ l
                                   wave, lane);
 }
 
-// the trips of the EL walk: gcn_wide_el.hip, the one translation unit with EL = true, defines it in front of its kernels; in every
-// other instance the call in gcw_walk is discarded and nothing of it exists
+// the trips of the EL walk: defined in gcn_wide_el_walk.h, which the two translation units with EL = true include in front of their
+// kernels (gcn_wide_el.hip, gcn_wide_el_f16.hip); in every other instance the call in gcw_walk is discarded and nothing of it exists
 template <int D>
 __device__ __forceinline__ void gcw_el_trips(const float* __restrict__ x, const int* __restrict__ src, const float* __restrict__ esc,
                                              const GcwElArgs& el, const float* s_blk, int e, int e_end, float dinv_v, int g,

@@ -248,7 +248,7 @@ class Engine:
         ast_encoder=True, vocab_head=True (GIN at width 300, ogbg-code2): also read gin_ep1_astenc_dim300.bin / gin_ep1_vocabhead_dim300.bin
         and apply them (set_ast_encoder, set_vocab_head); a code2 directory wants both beside edge_linear=True.  vocab_head_numeric:
         the head's own numeric mode, "f32" or "f16" (set_vocab_head_numeric), applied with the head.  edge_linear_numeric: the numeric
-        mode of the layer beside the encoder, "f32" or "f16" (set_edge_linear_numeric), applied with edge_linear=True.
+        mode of the layer beside the encoder, "f32" or "f16" (set_model_edge_linear_numeric: GIN and GCN), applied with edge_linear=True.
         After set_num_layers the files are read at the engine's depth: the per-layer tensors, num_layers eps values, num_layers - 1
         updates of the virtual node; a file of another depth is refused."""
         self._check(self.lib.flowgnn_load_weights_dir(self._h, directory.encode()), "flowgnn_load_weights_dir")
@@ -271,7 +271,7 @@ class Engine:
             from .weights import load_edge_linear
             el = load_edge_linear(directory, emb_dim=self.emb_dim, num_layers=self.num_layers, model=self.model)
             self.set_model_edge_linear(el["w"], el["b"])
-            self.set_edge_linear_numeric(edge_linear_numeric)
+            self.set_model_edge_linear_numeric(edge_linear_numeric)
         if ast_encoder:
             from .weights import load_ast_encoder
             ast = load_ast_encoder(directory, emb_dim=self.emb_dim)
@@ -842,6 +842,15 @@ class Engine:
         if mode not in ("f32", "f16"):
             raise ValueError(f"the edge encoder layer's numeric mode is {mode!r}, wanted 'f32' or 'f16'")
         self._check(self.lib.flowgnn_set_edge_linear_numeric(self._h, self.emb_dim, NUMERIC_MODES[mode]), "flowgnn_set_edge_linear_numeric")
+
+    def set_model_edge_linear_numeric(self, mode: str = "f32"):
+        """The model form of set_edge_linear_numeric (flowgnn.h: flowgnn_set_model_edge_linear_numeric): the same on a GIN engine, and
+        on a GCN engine at width 300 the f16 product of ppa's gcn and gcn-virtual behind the encoder's walk -- the stage's a and its
+        matrix rounded to f16 once, one product per K-step, fp32 accumulation; the encoder, the walk, the epilogue and the virtual
+        node stay fp32 -- which set_edge_linear_numeric refuses.  Takes effect while the encoder is on, in either call order."""
+        if mode not in ("f32", "f16"):
+            raise ValueError(f"the edge encoder layer's numeric mode is {mode!r}, wanted 'f32' or 'f16'")
+        self._check(self.lib.flowgnn_set_model_edge_linear_numeric(self._h, self.emb_dim, NUMERIC_MODES[mode]), "flowgnn_set_model_edge_linear_numeric")
 
     @property
     def edge_linear_numeric(self) -> str:

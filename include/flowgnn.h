@@ -1076,7 +1076,8 @@ int flowgnn_set_edge_features(flowgnn_engine* e, int edge_dim, const float* ef /
  *   flowgnn_edge_linear_numeric       the mode of the NEXT run, -1 for a null handle.
  * FLOWGNN_ERR_ARG: a null handle; any other mode, FLOWGNN_NUMERIC_Q6_10 included; emb_dim neither 100 nor 300, or, for
  * FLOWGNN_NUMERIC_F16, not the engine's width.  FLOWGNN_ERR_UNSUPPORTED: FLOWGNN_NUMERIC_F16 on any engine but FLOWGNN_MODEL_GIN at
- * width 300 (GCN's layer beside its encoder has no f16 form).  Single engines only, like the encoder.
+ * width 300 (GCN's stage beside its encoder has its f16 form under the model form of the call, flowgnn_set_model_edge_linear_numeric
+ * below).  Single engines only, like the encoder.
  */
 int flowgnn_set_edge_linear_numeric(flowgnn_engine* e, int emb_dim, int mode);  /* F32 (default) | F16 */
 int flowgnn_edge_linear_numeric(const flowgnn_engine* e);                       /* mode of the NEXT run; -1 for a null handle */
@@ -1094,6 +1095,29 @@ int flowgnn_edge_linear_numeric(const flowgnn_engine* e);                       
  * any other model.  flowgnn_set_edge_linear itself keeps refusing a GCN engine, as the other GIN-only forms do.
  */
 int flowgnn_set_model_edge_linear(flowgnn_engine* e, int emb_dim, int edge_dim, const float* w /* [L][300][edge_dim] */, const float* b /* [L][300] */);
+
+/*
+ * The model form of flowgnn_set_edge_linear_numeric: on a FLOWGNN_MODEL_GIN engine it is that call; on a
+ * FLOWGNN_MODEL_GCN engine at width 300 it is the throughput mode of ppa's gcn and gcn-virtual, a setting of the stages beside the
+ * encoder alone:
+ *   m[v] = sum over (u, v) of dinv[u] dinv[v] relu(x_u + W_e e_uv + b_e),   a[v] = relu(BN(m + relu(x + root) / (deg + 1))) (+ vn[g(v)])
+ *                                                                  fp32, CSR order, the encoder fp32-accurate: the walk above, unchanged
+ *   x_next[v] = (b s + sum r(W s) r(a[v])) / s                     r round-to-nearest-even to f16, exact products, fp32 accumulation
+ * on the matrix pipe, one product per K-step where the default form has three (FLOWGNN_NUMERIC_F16's rule for GCN's product at this
+ * width, flowgnn_set_model_numeric_mode_dim).  Stages 0 .. L - 2 run gcn_wide_el_f16.hip's kernels under the profile slot
+ * gcn_wide_layer_el_f16.  fp32 and unchanged: the last stage (it has no product), the node encoder, the virtual node's update, every
+ * pooling and readout, node logits and embeddings.  An a or an edge feature at or beyond 6e4, or not finite, repeats the pass on the
+ * exact fp32 kernels: the default mode's exact path, byte for byte.
+ * It sets the same integer as flowgnn_set_edge_linear_numeric: flowgnn_edge_linear_numeric reads it, and it takes effect while the
+ * encoder is on, in either call order, across flowgnn_set_model_edge_linear calls, weight sets, batches and changes of depth.  Drops a
+ * recorded launch sequence.  The engine's numeric mode stays FLOWGNN_NUMERIC_F32: flowgnn_set_model_numeric_mode_dim beside the encoder
+ * stays refused as above, and flowgnn_set_edge_linear_numeric(FLOWGNN_NUMERIC_F16) keeps refusing a GCN engine, as the other GIN-only
+ * forms do.  JK sum and the residual beside the encoder stay refused.
+ * FLOWGNN_ERR_ARG: a null handle; any other mode, FLOWGNN_NUMERIC_Q6_10 included; emb_dim neither 100 nor 300, or, for
+ * FLOWGNN_NUMERIC_F16, not the engine's width.  FLOWGNN_ERR_UNSUPPORTED: FLOWGNN_NUMERIC_F16 on any model but FLOWGNN_MODEL_GIN and
+ * FLOWGNN_MODEL_GCN, or at width 100.  FLOWGNN_NUMERIC_F32 is accepted wherever a handle is valid.  Single engines only, like the encoder.
+ */
+int flowgnn_set_model_edge_linear_numeric(flowgnn_engine* e, int emb_dim, int mode);  /* F32 (default) | F16 */
 
 /*
  * ogbg-code2 on GIN at width 300 (examples/graphproppred/code2).  Its message-passing layers are ppa's with
